@@ -6,7 +6,7 @@ One "step" = one loop iteration of the reference's orchestrator.py:337-352 on sy
 resident in HBM: replay index draw + gather, critic update, (every 3rd iteration) 2x actor+alpha update on the
 same batch, Polyak.  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hopper_sac|halfcheetah_td3|humanoid_sac]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hopper_sac|halfcheetah_td3|humanoid_sac] [--dump-outputs DIR]
 
 `--gpus N` (N > 1) started WITHOUT a torch.distributed.run environment launches the N one-GPU ranks itself (the
 parent touches no GPU: it only starts `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` as a child,
@@ -119,6 +119,26 @@ def write_detail(full):
         except OSError:
             pass
     return done
+
+
+DUMP_MAX_BYTES = 64 << 20
+PARAM_GROUPS = (("actor", 0), ("critics", 1), ("actor_target", 2), ("critics_target", 3), ("log_alpha", 4))   # include/sactd3.h
+
+
+def dump_outputs(eng, metrics, out_dir):
+    """--dump-outputs: what the timed path hands its caller after its last step -> out_dir/<name>.npy, float32 -- the reported
+    scalars (`loss_qf_loss`, ..., `vitals_alpha`, one element each) and every parameter group as the flat vector
+    Engine.get_params returns (`params_actor`, `params_critics`, `params_actor_target`, `params_critics_target`,
+    `params_log_alpha`).  Same arguments = same seeds, replay rows and RNG streams, so two builds compare file for file."""
+    import numpy as np
+    arrays = {k.replace("/", "_"): np.array([v], np.float32) for k, v in metrics.items()}
+    arrays.update({f"params_{name}": eng.get_params(which) for name, which in PARAM_GROUPS})
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def gather_algo_bytes(o, a, batch):
@@ -523,7 +543,13 @@ def main():
                     help="run ONLY the eager PyTorch-ROCm restatement for ITERS iterations (for rocprofv3 launch counts)")
     ap.add_argument("--gather-profile", type=int, default=0, metavar="BATCH",
                     help="run ONLY the replay gather at this batch size 20 times (for rocprofv3 --pmc traffic counters)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write rank 0's reported scalars and parameters as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.dry_run_ranks or args.eager_profile or args.gather_profile):
+        ap.error("--dump-outputs needs the timed steps of a real run")
     w = WORKLOADS[args.workload]
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -576,6 +602,9 @@ def main():
         dt = float(t.item())
         dist.barrier()
     metrics = eng.read_metrics()
+    if args.dump_outputs and rank == 0:      # before anything below runs more iterations on this engine
+        names = dump_outputs(eng, metrics, args.dump_outputs)
+        print(f"bench.py: {len(names)} arrays of the last timed step ->", args.dump_outputs, file=sys.stderr, flush=True)
 
     if rank == 0:
         out = {

@@ -10,15 +10,19 @@
    Humanoid B = 1024): autograd gradients, w.r.t. every parameter (and the action input), of (a) the plain functionals
    `get_action(ob)["log_prob"].sum() + ["sample"].sum()`, `Critic(ob, ac).sum()`, `Actor(ob).sum()` and (b) the two losses the
    update path differentiates, written with the reference's modules and the formulas of agents/agent.py:216-233 (twin MSE against
-   a given target) and :272-281 (`(alpha * logp - min Q).mean()`, TD3: `(-Q1).mean()`).  tests/test_golden.py requires the
-   oracle's classes to reproduce every stored number bit for bit on the CPU; tests/test_gpu_engine.py drives the HIP kernels
-   with the same parameters / inputs / noise and compares per key.  Large matrices are stored as every 8th row + float64 row and
-   column sums (inputs are regenerated from their seed; a float64 digest guards the regeneration).
+   a given target) and :272-281 (`(alpha * logp - min Q).mean()`, TD3: `(-Q1).mean()`).  Large matrices are taken as every 8th
+   row + float64 row and column sums (inputs are regenerated from their seed; a float64 digest guards the regeneration).  The
+   file holds the SHA-256 of every such array (array_sha256), not the array: tests/test_golden.py requires the oracle's classes
+   to reproduce every one bit for bit on the CPU, and `make_golden.py --oracle-bwd ENV OUT` writes the arrays themselves,
+   recomputed with the oracle's classes and refused unless every hash matches, for tests/test_gpu_engine.py, which drives the
+   HIP kernels with the same parameters / inputs / noise and compares per key.
 3. `traj_*.npz`      -- a short injected-noise trajectory of the oracle agent (losses per iteration, parameter
    digests).  agents/agent.py cannot be imported here (tensordict / torchrl / omegaconf / wandb are absent) and the
    reference ships no golden vectors, so these pin the ORACLE against regressions and give the GPU tests a
    committed target; they are not reference outputs (parity unpinned at agent level, see oracle/sac_td3_ref.py).
 """
+import hashlib
+import math
 import os
 import sys
 import types
@@ -84,7 +88,9 @@ def bwd_inputs(env):
     y = torch.randn(B, generator=g)
     torch.manual_seed(12)
     eps = torch.empty(B, a).normal_()          # what Normal.rsample() draws under torch.manual_seed(12) (checked below)
-    digest = np.array([t.double().sum().item() for t in (ob, ac, y, eps)] + [t.double().abs().sum().item() for t in (ob, ac, y, eps)])
+    # exactly rounded sums (math.fsum): the same on every host, whatever order a vectorised or threaded sum would take
+    digest = np.array([math.fsum(t.double().reshape(-1).tolist()) for t in (ob, ac, y, eps)] +
+                      [math.fsum(t.double().abs().reshape(-1).tolist()) for t in (ob, ac, y, eps)])
     return ob, ac, y, eps, digest
 
 
@@ -97,6 +103,35 @@ def pack_grad(out, name, t):
         out[name + "/colsum"] = t.double().sum(0).numpy()
     else:
         out[name] = t.numpy()
+
+
+def array_sha256(x):
+    """hex SHA-256 of an array's dtype, shape and bytes"""
+    x = np.ascontiguousarray(x)
+    return hashlib.sha256(f"{x.dtype.str}{x.shape}".encode() + x.tobytes()).hexdigest()
+
+
+def packed_bwd(env, make_sac, make_q, make_td3):
+    """{fixture key: array} -- bwd_functionals' results through pack_grad"""
+    out = {}
+    for k, v in bwd_functionals(make_sac, make_q, make_td3, env).items():
+        pack_grad(out, k, v)
+    return out
+
+
+def oracle_bwd(env):
+    """packed_bwd with the oracle's network classes (the reference's numbers wherever tests/test_golden.py passes)"""
+    from oracle.sac_td3_ref import DetPolicy, QNet, SquashedGaussPolicy
+    o, a, bound = CASES[env]
+    mn, mx = torch.full((a,), -bound), torch.full((a,), bound)
+    return packed_bwd(env, lambda: SquashedGaussPolicy(o, a, mn, mx, True), lambda: QNet(o, a, True),
+                      lambda: DetPolicy(o, a, mn, mx, 0.1, True))
+
+
+def bwd_hash_mismatches(env, out):
+    """keys of nets_bwd_<env>.npz whose stored hash `out` does not reproduce (missing or extra keys included)"""
+    fx = np.load(os.path.join(HERE, f"nets_bwd_{env}.npz"))
+    return sorted(set(fx.files) ^ set(out)) + sorted(k for k in fx.files if k in out and array_sha256(out[k]) != str(fx[k]))
 
 
 def bwd_functionals(make_sac, make_q, make_td3, env, out=None):
@@ -194,14 +229,11 @@ def bwd_functionals(make_sac, make_q, make_td3, env, out=None):
 def make_bwd_fixture(R):
     for env, (o, a, bound) in CASES.items():
         mn, mx = torch.full((a,), -bound), torch.full((a,), bound)
-        res = bwd_functionals(lambda: R.TanhGaussActor((o,), (a,), (256, 256), mn, mx, layer_norm=True, device="cpu"),
-                              lambda: R.Critic((o,), (a,), (256, 256), layer_norm=True, device="cpu"),
-                              lambda: R.Actor((o,), (a,), (256, 256), mn, mx, exploration_noise=0.1, layer_norm=True, device="cpu"), env)
-        out = {}
-        for k, v in res.items():
-            pack_grad(out, k, v)
+        out = packed_bwd(env, lambda: R.TanhGaussActor((o,), (a,), (256, 256), mn, mx, layer_norm=True, device="cpu"),
+                         lambda: R.Critic((o,), (a,), (256, 256), layer_norm=True, device="cpu"),
+                         lambda: R.Actor((o,), (a,), (256, 256), mn, mx, exploration_noise=0.1, layer_norm=True, device="cpu"))
         path = os.path.join(HERE, f"nets_bwd_{env}.npz")
-        np.savez_compressed(path, **out)
+        np.savez_compressed(path, **{k: np.array(array_sha256(v)) for k, v in out.items()})
         print("wrote nets_bwd_%s.npz (%d arrays, %.0f KB)" % (env, len(out), os.path.getsize(path) / 1024))
 
 
@@ -241,6 +273,16 @@ def make_traj_fixture():
 
 
 if __name__ == "__main__":
+    from tests import helpers
+    helpers.pin_cpu_numerics()     # the CPU numerics the golden tests compute with (tests/helpers.py)
+    if sys.argv[1:2] == ["--oracle-bwd"]:      # --oracle-bwd ENV OUT: the nets_bwd arrays, recomputed by the oracle and checked
+        env, path = sys.argv[2], sys.argv[3]
+        arrays = oracle_bwd(env)
+        bad = bwd_hash_mismatches(env, arrays)
+        if bad:
+            sys.exit(f"the oracle does not reproduce nets_bwd_{env}.npz: {len(bad)} keys differ, e.g. {bad[:5]}")
+        np.savez(path, **arrays)
+        sys.exit(0)
     R = reference_nets()
     make_nets_fixture(R)
     make_bwd_fixture(R)

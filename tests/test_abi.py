@@ -65,12 +65,21 @@ def test_product_package_does_not_import_the_oracle():
                 assert not bad.search(open(os.path.join(dirpath, f)).read()), f
 
 
-def test_no_kernel_spills_to_scratch():
-    """Scratch (private) memory costs a global-memory round trip per access; a dynamically indexed local array is
-    enough to trigger it.  Every kernel must report ScratchSize 0 in hipcc's resource-usage remarks."""
+@pytest.fixture(scope="module")
+def engine_asm(tmp_path_factory):
+    """`make asm` once per module into a private temporary file: (hipcc's resource-usage remarks, gfx950 assembly text)."""
     import subprocess
     csrc = os.path.join(ROOT, "sac-td3-cudagraphs-pytorch_amd", "csrc")
-    out = subprocess.run(["make", "-C", csrc, "asm"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
+    path = tmp_path_factory.mktemp("asm") / "sactd3_engine.s"
+    out = subprocess.run(["make", "-C", csrc, "asm", f"ASM_OUT={path}"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert out.returncode == 0, out.stdout[-2000:]
+    return out.stdout, path.read_text()
+
+
+def test_no_kernel_spills_to_scratch(engine_asm):
+    """Scratch (private) memory costs a global-memory round trip per access; a dynamically indexed local array is
+    enough to trigger it.  Every kernel must report ScratchSize 0 in hipcc's resource-usage remarks."""
+    out = engine_asm[0]
     names = re.findall(r"Function Name: (\S+)", out)
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
     assert len(names) == len(scratch) and len(names) >= 15, out[-2000:]
@@ -78,15 +87,12 @@ def test_no_kernel_spills_to_scratch():
     assert not bad, bad
 
 
-def test_no_serialised_operand_loads():
+def test_no_serialised_operand_loads(engine_asm):
     """A load first used inside a divergent branch, or issued after a possibly aliasing store, makes the compiler drain
     the memory queue (s_waitcnt vmcnt(0)) before the next request goes out: an operand fetch written as
     `k < K ? load : 0` waits a full round trip per load.  Check the compiled gfx950 code of every kernel: no run of
     load -> drain -> load -> drain, and the GEMM kernels issue their operand fetch as one batch."""
-    import subprocess
-    csrc = os.path.join(ROOT, "sac-td3-cudagraphs-pytorch_amd", "csrc")
-    subprocess.run(["make", "-C", csrc, "asm"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, check=True)
-    txt = open("/tmp/sactd3_engine.s").read()
+    txt = engine_asm[1]
     seqs = {}
     for name in re.findall(r"^(_Z[\w]+):\s*;?.*$", txt, re.M):
         i = txt.index("\n" + name + ":")
@@ -125,7 +131,7 @@ def test_shipped_library_reads_no_environment_switches():
     assert "getenv" not in outside
 
 
-def test_fetch_width_table_matches_the_code_objects():
+def test_fetch_width_table_matches_the_code_objects(engine_asm):
     """tools/pmc_summary.py doubles rocprofv3's FETCH_SIZE (gfx950 tallies 16-byte-per-lane reads at half, MI355X_MICROARCH.md, HBM)
     only for kernels whose operand fetches are all global_load_dwordx4; its MIXED table names the kernels with 4-byte strided
     operand loads.  Check the table against the compiled gfx950 code: share of non-dwordx4 bytes among a kernel's load
@@ -134,9 +140,7 @@ def test_fetch_width_table_matches_the_code_objects():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pmc_summary
-    csrc = os.path.join(ROOT, "sac-td3-cudagraphs-pytorch_amd", "csrc")
-    subprocess.run(["make", "-C", csrc, "asm"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, check=True)
-    txt = open("/tmp/sactd3_engine.s").read()
+    txt = engine_asm[1]
     width = {"dwordx4": 16, "dwordx3": 12, "dwordx2": 8, "dword": 4, "ushort": 2, "sshort": 2, "ubyte": 1, "sbyte": 1}
     names = re.findall(r"^(_Z[\w]+):\s*;?.*$", txt, re.M)
     dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")

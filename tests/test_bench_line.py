@@ -110,3 +110,30 @@ def test_roofline_groups_sum_the_grids_of_one_kernel_instance():
     assert abs(nn["frac"] - nn["achieved"] / bench.MFMA_F32_PEAK_TF) < 1e-12 and abs(nn["traffic"] - (4e6 * 30 + 1e6 * 10) / 40) < 1e-6
     assert len([r for r in by_grid if r["kernel"] == "k_nn"]) == 2
     assert abs(sum(r["share_of_node_time"] for r in by_name) - 1.0) < 1e-9
+
+
+def test_dump_outputs_writes_the_scalars_and_every_parameter_group(tmp_path):
+    """--dump-outputs: one float32 .npy per reported scalar and per parameter group, named after them, under the size cap"""
+    import numpy as np
+
+    class Stub:
+        def get_params(self, which):
+            return np.arange(10 + which, dtype=np.float32) * (which + 1)
+
+    metrics = {"loss/qf_loss": 1.5, "loss/actor_loss": -0.25, "loss/alpha_loss": 0.125, "vitals/alpha": 0.2}
+    names = bench.dump_outputs(Stub(), metrics, str(tmp_path / "out"))
+    assert names == sorted(os.path.splitext(f)[0] for f in os.listdir(tmp_path / "out"))
+    assert set(names) == {"loss_qf_loss", "loss_actor_loss", "loss_alpha_loss", "vitals_alpha"} | {f"params_{n}" for n, _ in bench.PARAM_GROUPS}
+    for k, v in metrics.items():
+        a = np.load(tmp_path / "out" / (k.replace("/", "_") + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (1,) and a[0] == np.float32(v)
+    for name, which in bench.PARAM_GROUPS:
+        a = np.load(tmp_path / "out" / f"params_{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, Stub().get_params(which))
+
+
+def test_dump_outputs_is_refused_without_timed_steps():
+    import subprocess
+    for extra in (["--dry-run-ranks"], ["--steps", "0"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", "x"] + extra, capture_output=True, text=True)
+        assert out.returncode == 2 and "error" in out.stderr, out.stderr[-500:]

@@ -13,7 +13,7 @@ import torch
 from oracle import replay_ref
 from oracle.manual_grads import ManualAgent
 from oracle.sac_td3_ref import Hps, RefAgent
-from tests.helpers import DIMS, assert_params_close, observe, randomize_ln, synth_transitions
+from tests.helpers import DIMS, PINNED_CPU_ENV, assert_params_close, observe, randomize_ln, synth_transitions
 
 pytestmark = pytest.mark.gpu
 
@@ -360,8 +360,8 @@ def _grads_match_fixture(fx, prefix, got_dict, what):
 
 
 @pytest.mark.parametrize("env", ["hopper", "halfcheetah", "humanoid"])
-def test_kernels_reproduce_the_reference_nets_backward(env):
-    """HIP kernels against autograd through the REFERENCE's own network classes (tests/golden/nets_bwd_*.npz, written by
+def test_kernels_reproduce_the_reference_nets_backward(env, tmp_path):
+    """HIP kernels against autograd through the REFERENCE's own network classes (hashed in tests/golden/nets_bwd_*.npz, written by
     tests/golden/make_golden.py from /root/reference/agents/nets.py; the oracle reproduces them bit for bit on the CPU,
     tests/test_golden.py).  Same parameters (seeds 11 / 13 / 14 / 16), same inputs (seed 321), same rsample noise (seed 12), at the
     BASELINE batch sizes (Hopper / HalfCheetah 256, Humanoid 1024: the large-batch kernel forms).
@@ -371,6 +371,8 @@ def test_kernels_reproduce_the_reference_nets_backward(env):
                    k_nn -> k_ln_bwd (+dQ/da) -> k_actor_head_bwd(_s) -> k_nn -> k_ln_bwd -> k_tn, action / logp / Q / dL/da / every gradient."""
     import importlib.util
     import os
+    import subprocess
+    import sys
     here = os.path.dirname(os.path.abspath(__file__))
     spec = importlib.util.spec_from_file_location("make_golden", os.path.join(here, "golden", "make_golden.py"))
     mg = importlib.util.module_from_spec(spec)
@@ -378,7 +380,13 @@ def test_kernels_reproduce_the_reference_nets_backward(env):
     from oracle.sac_td3_ref import DetPolicy, QNet, SquashedGaussPolicy
     o, a, bound = DIMS[env]
     B = mg.BWD_B[env]
-    fx = np.load(os.path.join(here, "golden", f"nets_bwd_{env}.npz"))
+    # the reference's numbers: recomputed by the oracle's classes with the pinned CPU numerics (tests/helpers.py), and written only
+    # if every array hashes to its entry of tests/golden/nets_bwd_<env>.npz (tests/test_golden.py: the oracle reproduces them)
+    path = tmp_path / f"nets_bwd_{env}.npz"
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [os.path.join(here, "golden", "make_golden.py"), "--oracle-bwd", env, str(path)]
+    out = subprocess.run(cmd, env=dict(os.environ, **PINNED_CPU_ENV), capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    fx = np.load(path)
     ob, ac, y, eps, digest = mg.bwd_inputs(env)
     assert np.array_equal(digest, fx["digest"]) and np.array_equal(eps.numpy(), fx["eps"])      # the regenerated inputs ARE the fixture's
     mn, mx = torch.full((a,), -bound), torch.full((a,), bound)

@@ -281,3 +281,31 @@ def test_sweep_launcher_trains_on_the_gpu(tmp_path):
         assert {"progress.json", "progress.csv", "summary.json", "ckpt_best.pth"} <= files
     sweep = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("SWEEP ")][0][6:])
     assert sweep["jobs"] == 2 and sweep["gradient_steps"] == 2 * 626
+
+
+@pytest.mark.parametrize("workload", ["hopper_sac", "halfcheetah_td3"])
+def test_bench_dump_is_the_state_after_warmup_plus_timed_steps(workload, tmp_path):
+    """bench.py --steps K --warmup W --dump-outputs DIR: the line reports K timed steps, and DIR holds the reported scalars and
+    parameters of an engine made as bench.py makes it after exactly W + K iterations of the same schedule, bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 7, 5
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--steps", str(steps), "--warmup",
+                          str(warmup), "--timed-only", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    sys.path.insert(0, root)
+    import bench
+    eng = bench.make_engine(bench.WORKLOADS[workload], seed=0, device_id=0)
+    assert bench.run_steps(eng, (-warmup) % (bench.DELAY + 1), warmup + steps) == (-warmup) % (bench.DELAY + 1) + warmup + steps
+    eng.sync()
+    for k, v in eng.read_metrics().items():
+        assert np.load(tmp_path / (k.replace("/", "_") + ".npy")).tolist() == [np.float32(v)], k
+    for name, which in bench.PARAM_GROUPS:
+        got = np.load(tmp_path / f"params_{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, eng.get_params(which)), name
+    eng.close()

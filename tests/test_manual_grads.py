@@ -4,7 +4,7 @@ import torch
 
 from oracle.manual_grads import ManualAgent
 from oracle.sac_td3_ref import Hps, RefAgent
-from tests.helpers import DIMS, assert_params_close, randomize_ln, synth_transitions
+from tests.helpers import DIMS, assert_params_close, in_pinned_cpu_process, randomize_ln, synth_transitions
 
 
 def _close(a, b, rtol=2e-4, atol=2e-6):
@@ -56,7 +56,10 @@ def test_manual_matches_autograd(algo, env, ln):
                 _close(man.q_t[i][k], p, rtol=1e-6, atol=1e-7)
 
 
-def test_clip_norm():
+def test_clip_norm(request):
+    """first Adam step after clipping: which near-zero gradients flip sign depends on the CPU's summation order (tests/helpers.py)"""
+    if not in_pinned_cpu_process(request):
+        return
     o, a, bound = DIMS["hopper"]
     B = 32
     hps = Hps.sac(batch_size=B, clip_norm=0.05)
