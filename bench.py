@@ -6,7 +6,11 @@ One "step" = one loop iteration of the reference's orchestrator.py:337-352 on sy
 resident in HBM: replay index draw + gather, critic update, (every 3rd iteration) 2x actor+alpha update on the
 same batch, Polyak.  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hopper_sac|halfcheetah_td3|humanoid_sac] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hopper_sac|halfcheetah_td3|humanoid_sac] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` and prints the line with the contract keys: nothing
+else.  `--full` then measures everything beyond the headline (kernel-node counts, longer windows, acting-side figures, node
+budget and rooflines, parity, the CPU / eager / torch-graph baselines, the other BASELINE configs) into the line and `DETAIL_FILE`.
 
 `--gpus N` (N > 1) started WITHOUT a torch.distributed.run environment launches the N one-GPU ranks itself (the
 parent touches no GPU: it only starts `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` as a child,
@@ -64,8 +68,8 @@ def _pick(d, keys, n=5):
 
 
 def result_line(full, w):
-    """The ONE line the driver parses (<= LINE_MAX bytes): the contract's keys, the roofline of the dominant kernel, the CPU
-    baseline, and three numbers per secondary config.  Everything else (node tables, per-grid rooflines, sweeps, full
+    """The ONE line the driver parses (<= LINE_MAX bytes): the contract's keys and, after --full, the dominant kernel's roofline,
+    the CPU baseline, and three numbers per secondary config.  Everything else (node tables, per-grid rooflines, sweeps, full
     configs) is in the side file `DETAIL_FILE` (written next to bench.py and, when it exists, into gpurun_out/)."""
     out = {k: _sig(full[k]) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                       "vs_baseline", "dtype", "data") if k in full}
@@ -535,9 +539,13 @@ def main():
     ap.add_argument("--steps", type=int, default=3000)
     ap.add_argument("--warmup", type=int, default=300)
     ap.add_argument("--workload", default="hopper_sac", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-baselines", action="store_true", help="skip the baselines, the other configs and the extra figures")
-    ap.add_argument("--timed-only", action="store_true", help="only the warm-up and the timed steps (rocprofv3 runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline (rooflines, baselines, other configs, ...) "
+                         "-> more keys on the line and bench_detail.json")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: seconds of the CPU baseline")
+    ap.add_argument("--no-baselines", action="store_true", help="with --full: skip the baselines, the other configs and the extra figures")
+    ap.add_argument("--timed-only", action="store_true",
+                    help="with --full: stop after the kernel-node counts (a plain run already stops after the timed steps)")
     ap.add_argument("--dry-run-ranks", action="store_true", help="no GPU work: rehearse rank launching / rendezvous / aggregation on CPU")
     ap.add_argument("--eager-profile", type=int, default=0, metavar="ITERS",
                     help="run ONLY the eager PyTorch-ROCm restatement for ITERS iterations (for rocprofv3 launch counts)")
@@ -615,16 +623,17 @@ def main():
             "config": {"workload": describe(w), "parallelism": f"{world} independent seeds, one per GPU, no collective"},
             # one iteration = 1 critic update (+ Polyak) and, every 3rd iteration, 2 actor(+alpha) updates
             "critic_updates_per_s": world * args.steps / dt, "actor_updates_per_s": world * args.steps / dt * 2.0 / 3.0,
-            "kernels_per_iteration": kernel_counts(eng),
             "final_metrics": metrics,
         }
         if args.dry_run_ranks:
             out.update(dry_run=True, value=None, note="no GPU work was done: rank launching / rendezvous / aggregation rehearsal only")
-        elif not args.timed_only and world == 1:     # N > 1 lines carry the timed region only (roofline / cpu_baseline: N = 1)
-            extras(out, eng, w, args, local, world)
-            out["detail"] = DETAIL_FILE
-            print("bench.py: full record (node tables, per-grid rooflines, sweeps, secondary configs) ->", ", ".join(write_detail(out)),
-                  file=sys.stderr, flush=True)
+        if args.full:
+            out["kernels_per_iteration"] = kernel_counts(eng)
+            if not args.dry_run_ranks and not args.timed_only and world == 1:   # N > 1 lines: the timed region only (roofline / cpu_baseline: N = 1)
+                extras(out, eng, w, args, local, world)
+                out["detail"] = DETAIL_FILE
+                print("bench.py: full record (node tables, per-grid rooflines, sweeps, secondary configs) ->", ", ".join(write_detail(out)),
+                      file=sys.stderr, flush=True)
         print(result_line(out, w), flush=True)
     if dist:
         dist.destroy_process_group()

@@ -239,15 +239,21 @@ def make_bwd_fixture(R):
 
 def run_traj(algo, env, B=32, iters=6, seed=5):
     from oracle.sac_td3_ref import Hps, RefAgent
+    from sac_td3_cudagraphs_pytorch_amd import schema
     o, a, bound = CASES[env]
     hps = (Hps.td3 if algo == "td3" else Hps.sac)(batch_size=B)
+    # the agent's initial parameters in the engine's layout: orthogonal init runs a QR whose last bits depend on the CPU's numerics,
+    # so the GPU test starts from these rather than re-drawing them on its own host
+    torch.manual_seed(seed)
+    init_actor, init_critics = schema.reference_initial_params(o, a, algo == "td3", True)
     torch.manual_seed(seed)
     ag = RefAgent(o, a, [-bound] * a, [bound] * a, hps)
     g = torch.Generator().manual_seed(seed + 1)
     n = 500
     data = dict(obs=torch.randn(n, o, generator=g), act=(torch.rand(n, a, generator=g) * 2 - 1) * bound,
                 rew=torch.randn(n, generator=g), nobs=torch.randn(n, o, generator=g), done=torch.rand(n, generator=g) < 0.05)
-    out = {"seed": np.array(seed), "B": np.array(B), **{k: v.numpy() for k, v in data.items()}}
+    out = {"seed": np.array(seed), "B": np.array(B), "init_actor": init_actor, "init_critics": init_critics,
+           **{k: v.numpy() for k, v in data.items()}}
     losses = []
     for i in range(iters):
         idx = torch.randint(0, n, (B,), generator=g)

@@ -137,3 +137,18 @@ def test_dump_outputs_is_refused_without_timed_steps():
     for extra in (["--dry-run-ranks"], ["--steps", "0"]):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", "x"] + extra, capture_output=True, text=True)
         assert out.returncode == 2 and "error" in out.stderr, out.stderr[-500:]
+
+
+def test_plain_run_measures_the_headline_only_and_full_adds_the_rest():
+    """a plain run's line carries the contract keys and nothing measured beyond the timed steps; --full adds those (under
+    --dry-run-ranks only the kernel-node counts: the rehearsal has no engine for the rest)"""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines = {}
+    for extra in ([], ["--full"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--dry-run-ranks"] + extra,
+                             cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines[bool(extra)] = json.loads(out.stdout.splitlines()[-1])
+    assert set(lines[False]) == set(CONTRACT) | {"dry_run", "note"}
+    assert set(lines[True]) == set(lines[False]) | {"kernel_nodes_per_iteration"}

@@ -309,3 +309,26 @@ def test_bench_dump_is_the_state_after_warmup_plus_timed_steps(workload, tmp_pat
         got = np.load(tmp_path / f"params_{name}.npy")
         assert got.dtype == np.float32 and np.array_equal(got, eng.get_params(which)), name
     eng.close()
+
+
+def test_plain_bench_run_reports_the_headline_only():
+    """bench.py without --full: the line carries the contract keys alone and no side file is written; --full --timed-only adds
+    the kernel-node counts to the same line"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    detail = os.path.join(root, "bench_detail.json")
+    before = os.stat(detail).st_mtime_ns if os.path.exists(detail) else None
+    lines = {}
+    for extra in ([], ["--full", "--timed-only"]):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5"] + extra,
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines[bool(extra)] = json.loads(out.stdout.strip().splitlines()[-1])
+    contract = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                "data", "config"}
+    assert set(lines[False]) == contract and lines[False]["value"] > 0 and lines[False]["steps"] == 20
+    assert set(lines[True]) == contract | {"kernel_nodes_per_iteration"} and lines[True]["kernel_nodes_per_iteration"] > 0
+    assert (os.stat(detail).st_mtime_ns if os.path.exists(detail) else None) == before

@@ -8,6 +8,6 @@ if "--" in args:
 var, vals = args[0], args[1:]
 for v in vals:
     env = dict(os.environ); env[var] = v
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-baselines", "--steps", "3000"] + extra, env=env, capture_output=True, text=True).stdout.strip().splitlines()[-1]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-baselines", "--steps", "3000"] + extra, env=env, capture_output=True, text=True).stdout.strip().splitlines()[-1]
     d = json.loads(out)
-    print("%s=%s" % (var, v), round(d["value"]), "%.2f us" % (d["ms_per_step"] * 1e3), d["kernels_per_iteration"], flush=True)
+    print("%s=%s" % (var, v), round(d["value"]), "%.2f us" % (d["ms_per_step"] * 1e3), d["kernel_nodes_per_iteration"], flush=True)
