@@ -184,6 +184,34 @@ int sactd3_instantiate_graphs(sactd3_engine* e);
  * finished: [sync] in that sense -- with at most 4 rows (16 for wide heads) the wait is a spin on a pinned host word the last
  * kernel publishes, otherwise a stream synchronisation. */
 int sactd3_predict(sactd3_engine* e, const float* obs, int n, int explore, float* actions);
+/* Agent.predict in two halves, so that the update issued in between (orchestrator.py:337-352) overlaps with it: the same acting
+ * launches as sactd3_predict -- same kernels, same arguments, same (explore, n) graph, or the eager sequence with use_graphs == 0 --
+ * on a second, ACTING stream (hipStreamNonBlocking, created with its two events at the first sactd3_predict_begin: an engine that never
+ * calls it holds nothing more than before).  `begin` stages `obs`, issues the launches and returns; `end` waits for THOSE kernels
+ * only (the pinned-word spin of sactd3_predict for single-block tails, bounded, then a synchronisation of the acting stream) and
+ * copies the actions [n, ac_dim] out.  The result is, bit for bit, what sactd3_predict would have returned at the position of
+ * `begin` in the call sequence, the native exploration draw included (its counter advances once per call, whichever entry point).
+ * Order between the two streams is decided on the host and kept with events, only where the acting kernels (which read the actor
+ * parameters, the action bounds, their own scratch and their own control words) meet a learner call:
+ *   learner -> acting: if a call that writes the actor parameters was issued on the learner stream since the acting stream last
+ *     waited for it (sactd3_update_actor, sactd3_step with actor updates, sactd3_step_period, sactd3_step_prefix,
+ *     sactd3_set_params(ACTOR), sactd3_time_nodes), or if flags has SACTD3_ACT_AFTER_ALL, `begin` makes the acting stream wait for
+ *     everything issued on the learner stream so far -- as sactd3_predict does.  Otherwise it waits for nothing: behind a
+ *     critic-only iteration the action comes from the same parameters either way.
+ *   acting -> learner: while a call is in flight (begun, not ended) the first of the calls above makes the learner stream wait for
+ *     the acting kernels, so the actor is not overwritten under a running predict.  After `end` nothing is inserted.
+ *   Critic-only sactd3_step, sactd3_update_qnets, sactd3_update_targ_nets, sactd3_rb_* neither wait nor are waited for.
+ * A period graph (sactd3_step_period / _prefix) contains actor updates, so a `begin` behind one waits for all of it: the overlap
+ * pays with single-iteration sactd3_step loops.
+ * One call in flight at most.  While one is, a second `begin`, sactd3_predict, and sactd3_set_noise / _clear_noise / _read_noise on
+ * SACTD3_SITE_PREDICT return SACTD3_ESTATE; so does `end` without a `begin`.  sactd3_sync and sactd3_destroy drain the acting
+ * stream too (after sactd3_sync the call is still to be collected with `end`). */
+#define SACTD3_ACT_AFTER_ALL 1   /* flags: order behind everything issued so far, as sactd3_predict does */
+int sactd3_predict_begin(sactd3_engine* e, const float* obs, int n, int explore, int flags);
+int sactd3_predict_end(sactd3_engine* e, float* actions);          /* waits for ITS kernels only */
+/* host counters of the ordering policy: out = {calls begun, begins that made the acting stream wait for the learner, learner calls
+ * that waited for an acting call in flight, calls ended by the pinned-word spin} */
+int sactd3_acting_stats(const sactd3_engine* e, int64_t out[4]);
 
 int sactd3_read_metrics(sactd3_engine* e, float out[SACTD3_NUM_METRICS]);  /* [sync] */
 /* The engine's HIP stream (hipStream_t) and the DEVICE address of the metrics slots, for callers that want the values the

@@ -13,6 +13,8 @@ ABI_VERSION = 1
 ACTOR, CRITICS, ACTOR_TARGET, CRITICS_TARGET, LOG_ALPHA = range(5)
 SITE_CRITIC, SITE_ACTOR0, SITE_ACTOR1, SITE_ALPHA0, SITE_ALPHA1, SITE_PREDICT = range(6)
 NUM_METRICS = 8
+ACT_AFTER_ALL = 1   # sactd3_predict_begin flags
+ESTATE, EINVAL = -3, -1
 
 # every symbol include/sactd3.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -23,6 +25,7 @@ SYMBOLS = [
     "sactd3_update_qnets", "sactd3_update_actor", "sactd3_update_targ_nets", "sactd3_step", "sactd3_predict",
     "sactd3_read_metrics", "sactd3_sync", "sactd3_debug_read", "sactd3_debug_names", "sactd3_graph_kernel_count",
     "sactd3_time_kernel", "sactd3_time_gather_sweep", "sactd3_time_nodes", "sactd3_rb_layout", "sactd3_rb_extend_device", "sactd3_step_period", "sactd3_step_prefix", "sactd3_instantiate_graphs", "sactd3_device_handles",
+    "sactd3_predict_begin", "sactd3_predict_end", "sactd3_acting_stats",
 ]
 
 
@@ -100,6 +103,9 @@ def load_library():
         "sactd3_step_prefix": (C.c_int, [vp, C.c_int]),
         "sactd3_instantiate_graphs": (C.c_int, [vp]),
         "sactd3_predict": (C.c_int, [vp, fp, C.c_int, C.c_int, fp]),
+        "sactd3_predict_begin": (C.c_int, [vp, fp, C.c_int, C.c_int, C.c_int]),
+        "sactd3_predict_end": (C.c_int, [vp, fp]),
+        "sactd3_acting_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -211,6 +211,15 @@ class Agent:
         """agents/agent.py:172-181 -> np.ndarray[n, ac_dim] float32 on the host."""
         return self.engine.predict(_np(in_td["observations"]), explore)
 
+    def predict_begin(self, in_td: Mapping[str, Any], *, explore: bool) -> None:
+        """predict() in two halves (include/sactd3.h: sactd3_predict_begin): the acting kernels go out on the engine's acting
+        stream, and what is issued until predict_end() -- the iteration's update -- overlaps with them."""
+        self.engine.predict_begin(_np(in_td["observations"]), explore)
+
+    def predict_end(self) -> np.ndarray:
+        """-> np.ndarray[n, ac_dim] float32: the actions of the call begun with predict_begin()."""
+        return self.engine.predict_end()
+
     def _results(self, keys) -> Dict[str, Any]:
         if self._metric_tensors is None:
             return {k: LazyMetric(self, k) for k in keys}

@@ -139,6 +139,15 @@ struct sactd3_engine {
   int64_t rb_len = 0, rb_cursor = 0, qnet_updates = 0;
   hipGraphExec_t graphs[G_COUNT] = {}; int graph_nodes[G_COUNT] = {};
   std::vector<hipGraphExec_t> predict_graphs;   // [explore][n]: the two launches of sactd3_predict, captured per row count
+  // Acting on a stream of its own (sactd3_predict_begin / _end), created at the first begin.  Order between the two streams is kept
+  // by the host, with events, only where the acting kernels and a learner call touch the same memory -- the actor parameters:
+  //   actor_dirty   a write of them was issued on the learner stream since the acting stream last waited for it -> the next begin waits;
+  //   act_inflight  a call has begun and not ended -> the next learner call that writes them waits for it first (act_ordered: one did).
+  hipStream_t act_stream = nullptr;
+  hipEvent_t ev_learner = nullptr, ev_acting = nullptr;
+  bool actor_dirty = true, act_inflight = false, act_ordered = false, act_spin = false;
+  int act_n = 0, act_want = 0;
+  int64_t act_stats[4] = {};                    // sactd3_acting_stats
   // kernel-selection knobs: fixed defaults in the shipped library; tuning builds (-DSACTD3_TUNING) read them from the environment at create
   int tune_ks = 0, tune_nt = 0, tune_tn_kt = 0, tune_pad64 = 0, tune_tn64_min = 0, tune_rows4 = 0, tune_nn16 = 0, tune_xr = -1;
   // node registry of the enqueue_* sequences (sactd3_time_nodes): every kernel launch of the path goes through
@@ -1226,20 +1235,21 @@ static int enqueue_step(sactd3_engine* e, hipStream_t s, bool do_actor, bool do_
 }
 
 template <class F>
-static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&& enqueue, bool launch = true);
+static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&& enqueue, bool launch = true, hipStream_t on = nullptr);
 template <class F>
 static int run_graph(sactd3_engine* e, int which, F&& enqueue, bool launch = true) {
   return run_graph_slot(e, &e->graphs[which], &e->graph_nodes[which], enqueue, launch);
 }
-// launch == false: capture + instantiate only (sactd3_instantiate_graphs)
+// launch == false: capture + instantiate only (sactd3_instantiate_graphs); on: the stream to capture and launch on (default: the learner's)
 template <class F>
-static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&& enqueue, bool launch) {
-  if (!e->cfg.use_graphs) return launch ? enqueue(e->stream) : 0;
+static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&& enqueue, bool launch, hipStream_t on) {
+  const hipStream_t st = on ? on : e->stream;
+  if (!e->cfg.use_graphs) return launch ? enqueue(st) : 0;
   if (!*slot) {
     hipGraph_t g = nullptr;
-    HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue(e->stream);
-    hipError_t he = hipStreamEndCapture(e->stream, &g);
+    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue(st);
+    hipError_t he = hipStreamEndCapture(st, &g);
     if (rc != 0) { if (g) hipGraphDestroy(g); return rc; }
     if (he != hipSuccess) return e->fail(SACTD3_EHIP, "hipStreamEndCapture", he);
     size_t n = 0;
@@ -1250,9 +1260,22 @@ static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&
     if (he != hipSuccess) return e->fail(SACTD3_EHIP, "hipGraphInstantiate", he);
     // move the executable graph's launch resources to the device now, not inside its first launch (a loop that instantiates ahead --
     // sactd3_instantiate_graphs -- then pays nothing extra the first time each graph runs); not every runtime implements it: best effort
-    if (hipGraphUpload(*slot, e->stream) != hipSuccess) (void)hipGetLastError();
+    if (hipGraphUpload(*slot, st) != hipSuccess) (void)hipGetLastError();
   }
-  if (launch) HIPCHK(hipGraphLaunch(*slot, e->stream));
+  if (launch) HIPCHK(hipGraphLaunch(*slot, st));
+  return 0;
+}
+
+// A learner-stream call that writes the actor parameters (what the acting kernels read through that stream) is about to be issued:
+// if an acting call is in flight on the acting stream, the learner stream first waits for an event recorded behind its launches, so
+// the parameters are not overwritten under a running predict; and the next sactd3_predict_begin has to wait for this call.
+static int actor_write_begin(sactd3_engine* e) {
+  e->actor_dirty = true;
+  if (!e->act_inflight || e->act_ordered) return 0;      // (once predict_end has returned the host knows the kernels are done)
+  HIPCHK(hipEventRecord(e->ev_acting, e->act_stream));
+  HIPCHK(hipStreamWaitEvent(e->stream, e->ev_acting, 0));
+  e->act_ordered = true;
+  ++e->act_stats[2];
   return 0;
 }
 
@@ -1294,11 +1317,15 @@ void sactd3_destroy(sactd3_engine* e) {
   if (!e) return;
   if (e->stream) (void)hipSetDevice(e->cfg.device_id);   // (a failed create may carry a device_id that was never valid)
   if (e->stream) hipStreamSynchronize(e->stream);
+  if (e->act_stream) hipStreamSynchronize(e->act_stream);
   for (auto& g : e->graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_graphs) if (g) hipGraphExecDestroy(g);
   for (auto ev : e->events) hipEventDestroy(ev);
   for (void* p : e->dev_allocs) hipFree(p);
   for (void* p : e->host_allocs) hipHostFree(p);
+  if (e->ev_learner) hipEventDestroy(e->ev_learner);
+  if (e->ev_acting) hipEventDestroy(e->ev_acting);
+  if (e->act_stream) hipStreamDestroy(e->act_stream);
   if (e->stream) hipStreamDestroy(e->stream);
   delete e;
 }
@@ -1514,6 +1541,7 @@ int sactd3_set_params(sactd3_engine* e, int which, const float* src) {
   }
   float *P, *M, *V; const NetLayout* L; int nets; int* t;
   if (!which_arena(e, which, &P, &M, &V, &L, &nets, &t)) return e->fail(SACTD3_EINVAL, "bad `which`");
+  if (which == SACTD3_ACTOR) RCCHK(actor_write_begin(e));   // (write_arena synchronises the learner stream, hence the acting call too)
   return write_arena(e, P, *L, nets, src, true);
 }
 
@@ -1737,6 +1765,7 @@ int sactd3_set_noise(sactd3_engine* e, int site, const float* eps, int n) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   if (n < 1 || n > std::max(e->B, e->maxn)) return e->fail(SACTD3_EINVAL, "set_noise: too many rows");
+  if (e->act_inflight && site == SACTD3_SITE_PREDICT) return e->fail(SACTD3_ESTATE, "set_noise: an acting call is in flight (sactd3_predict_end first)");
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipMemcpy(e->eps[site], eps, sizeof(float) * (size_t)n * e->a, hipMemcpyHostToDevice));
   if (site == SACTD3_SITE_CRITIC)      // (every batch slot: injected draws are "sticky until cleared", whichever slot an iteration trains on)
@@ -1748,6 +1777,7 @@ int sactd3_set_noise(sactd3_engine* e, int site, const float* eps, int n) {
 int sactd3_clear_noise(sactd3_engine* e, int site) {
   if (!e || site >= SACTD3_NUM_SITES) return SACTD3_EINVAL;
   USE_DEVICE(e);
+  if (e->act_inflight && (site < 0 || site == SACTD3_SITE_PREDICT)) return e->fail(SACTD3_ESTATE, "clear_noise: an acting call is in flight (sactd3_predict_end first)");
   CHAIN_BREAK(e);
   HIPCHK(hipStreamSynchronize(e->stream));
   const int zeros[8] = {0};
@@ -1758,6 +1788,7 @@ int sactd3_clear_noise(sactd3_engine* e, int site) {
 int sactd3_read_noise(sactd3_engine* e, int site, float* eps, int n) {
   if (!e || !eps || site < 0 || site >= SACTD3_NUM_SITES || n < 1 || n > std::max(e->B, e->maxn)) return SACTD3_EINVAL;
   USE_DEVICE(e);
+  if (e->act_inflight && site == SACTD3_SITE_PREDICT) return e->fail(SACTD3_ESTATE, "read_noise: an acting call is in flight (sactd3_predict_end first)");
   HIPCHK(hipStreamSynchronize(e->stream));
   const float* src = site == SACTD3_SITE_CRITIC ? e->bs[e->cur_slot].eps_c : e->eps[site];
   HIPCHK(hipMemcpy(eps, src, sizeof(float) * (size_t)n * e->a, hipMemcpyDeviceToHost));
@@ -1776,6 +1807,7 @@ int sactd3_update_actor(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
+  RCCHK(actor_write_begin(e));
   return run_graph(e, G_A, [&](hipStream_t s) { return enqueue_update_actor(e, s, 0); });
 }
 int sactd3_update_targ_nets(sactd3_engine* e, int64_t qnet_updates_so_far) {
@@ -1795,6 +1827,7 @@ int sactd3_step(sactd3_engine* e, int do_actor) {
   const bool polyak = e->cfg.prefer_td3_over_sac || (updates % e->cfg.crit_targ_update_freq == 0);
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
   const int which = G_STEP00 + (act ? 2 : 0) + (polyak ? 1 : 0);
+  if (act) RCCHK(actor_write_begin(e));      // (a critic-only iteration touches nothing the acting kernels read: no order with them)
   RCCHK(run_graph(e, which, [&](hipStream_t s) { return enqueue_step(e, s, act, polyak); }));
   e->qnet_updates = updates;
   e->cur_slot = 0;
@@ -1861,6 +1894,7 @@ int sactd3_step_period(sactd3_engine* e) {
   const bool td3 = e->cfg.prefer_td3_over_sac;
   if (!td3 && e->cfg.crit_targ_update_freq != 1) return e->fail(SACTD3_ESTATE, "step_period: needs crit_targ_update_freq == 1");
   const int n = e->cfg.actor_update_delay + 1;
+  RCCHK(actor_write_begin(e));
   if (!period_is_pipelined(e)) {
     e->chain_ready = -1;
     RCCHK(run_graph(e, G_PERIOD, [&](hipStream_t s) { return enqueue_period(e, s); }));
@@ -1897,6 +1931,7 @@ int sactd3_step_prefix(sactd3_engine* e, int m) {
   const int v = e->chain_ready >= 0 ? e->chain_ready : 0;
   const bool have = e->chain_ready >= 0;
   e->chain_ready = -1;
+  RCCHK(actor_write_begin(e));
   if (!have) RCCHK(run_graph(e, G_OPENING, [&](hipStream_t s) { return enqueue_opening(e, s, 0); }));
   RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](hipStream_t s) { return enqueue_prefix(e, s, v, m); }));
   e->cur_slot = m - 1;
@@ -1929,62 +1964,133 @@ int sactd3_instantiate_graphs(sactd3_engine* e) {
   return 0;
 }
 
-int sactd3_predict(sactd3_engine* e, const float* obs, int n, int explore, float* actions) {
-  if (!e || !obs || !actions) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  if (n < 1 || n > e->maxn) return e->fail(SACTD3_EINVAL, "predict: 1 <= n <= max_envs");
+// The acting launches of one call -- trunk (with the exploration draw riding along) + tail (+ a counter kernel behind a multi-block
+// tail) -- on stream `s`: the learner's for sactd3_predict, the acting stream for sactd3_predict_begin.  The kernels read the
+// observations from, and write the actions to, the pinned host buffers themselves (a few hundred bytes over the host link): two
+// kernels and one synchronisation per call, no copy commands, no separate counter kernel.  Nothing in the launches depends on the
+// call but (n, explore): they are captured once per pair and replayed, on either stream.
+static bool predict_one_block(sactd3_engine* e, int n) {
+  return n <= tail_rows_per_block(tail_args(e, e->p_z2, e->Pa, n, 0, 0, SACTD3_SITE_PREDICT, 48u, e->h_act, e->a4, 0, nullptr));
+}
+static int enqueue_predict(sactd3_engine* e, hipStream_t s, int n, int explore) {
   const bool td3 = e->cfg.prefer_td3_over_sac;
-  // (the pinned staging is free: every call returns only after its own kernels have finished, see below)
+  bool eps_ready = false;
+  {
+    const TrunkGrp g{e->h_obs, e->Pa, e->p_z1, e->p_z2, nullptr, nullptr, nullptr};
+    TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
+    if (explore) { tk.nnoise = 1; tk.noise[0] = noise_job(e, SACTD3_SITE_PREDICT, 48u, 0, n); tk.noise_taken = &eps_ready; }
+    RCCHK(enqueue_trunk(e, s, e->ldo, e->o, n, e->La, 0, 1, 1, &g, tk));
+  }
+  const int mode = td3 ? (explore ? 2 : 0) : (explore ? 0 : 1);
+  ActorTail t = tail_args(e, e->p_z2, e->Pa, n, mode, 0, SACTD3_SITE_PREDICT, 48u, e->h_act, e->a4, 0, nullptr);
+  t.eps_ready = eps_ready;
+  // the tail reads predict_ctr (its noise stream) and may only advance it itself when it is a single block: with more
+  // rows than one block holds, a late block could read the counter after block 0 has bumped it
+  const bool one_block = n <= tail_rows_per_block(t);
+  if (explore && one_block) t.tick = &e->ctl->predict_ctr;
+  if (one_block) { t.seq = &e->ctl->predict_seq; t.done_flag = e->h_done; }
+  RCCHK(launch_tail(e, s, t));
+  if (explore && !one_block) {
+    hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, s, &e->ctl->predict_ctr, (int*)nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+static void predict_stage_obs(sactd3_engine* e, const float* obs, int n) {
+  // (the pinned staging is free: every call returns -- sactd3_predict_end for a begun one -- only after its own kernels have finished)
   for (int i = 0; i < n; ++i) {
     memset(e->h_obs + (size_t)i * e->ldo, 0, sizeof(float) * e->ldo);
     memcpy(e->h_obs + (size_t)i * e->ldo, obs + (size_t)i * e->o, sizeof(float) * e->o);
   }
-  // The kernels read the observations from, and write the actions to, the pinned host buffers themselves (a few hundred
-  // bytes over the host link): two kernels and one synchronisation per call, no copy commands, no separate counter kernel.
-  // Nothing in the launches depends on the call but (n, explore): they are captured once per pair and replayed.
+}
+static int predict_launch(sactd3_engine* e, hipStream_t s, int n, int explore) {
   if (e->predict_graphs.empty()) e->predict_graphs.assign(2 * (size_t)(e->maxn + 1), nullptr);
-  RCCHK(run_graph_slot(e, &e->predict_graphs[(size_t)(explore ? 1 : 0) * (e->maxn + 1) + n], nullptr, [&](hipStream_t) {
-    bool eps_ready = false;
-    {
-      const TrunkGrp g{e->h_obs, e->Pa, e->p_z1, e->p_z2, nullptr, nullptr, nullptr};
-      TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
-      if (explore) { tk.nnoise = 1; tk.noise[0] = noise_job(e, SACTD3_SITE_PREDICT, 48u, 0, n); tk.noise_taken = &eps_ready; }
-      RCCHK(enqueue_trunk(e, e->stream, e->ldo, e->o, n, e->La, 0, 1, 1, &g, tk));
-    }
-    const int mode = td3 ? (explore ? 2 : 0) : (explore ? 0 : 1);
-    ActorTail t = tail_args(e, e->p_z2, e->Pa, n, mode, 0, SACTD3_SITE_PREDICT, 48u, e->h_act, e->a4, 0, nullptr);
-    t.eps_ready = eps_ready;
-    // the tail reads predict_ctr (its noise stream) and may only advance it itself when it is a single block: with more
-    // rows than one block holds, a late block could read the counter after block 0 has bumped it
-    const bool one_block = n <= tail_rows_per_block(t);
-    if (explore && one_block) t.tick = &e->ctl->predict_ctr;
-    if (one_block) { t.seq = &e->ctl->predict_seq; t.done_flag = e->h_done; }
-    RCCHK(launch_tail(e, e->stream, t));
-    if (explore && !one_block) {
-      hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->predict_ctr, (int*)nullptr);
-      HIPCHK(hipGetLastError());
-    }
-    return 0;
-  }));
-  // completion: a single-block tail publishes the call's sequence number to a pinned host word after its last store; spin on
-  // it (a stream synchronisation costs a marker packet and a signal wake-up on top of the kernels).  Anything unexpected, or a
-  // multi-block tail: synchronise the stream.
+  return run_graph_slot(e, &e->predict_graphs[(size_t)(explore ? 1 : 0) * (e->maxn + 1) + n], nullptr,
+                        [&](hipStream_t st) { return enqueue_predict(e, st, n, explore); }, true, s);
+}
+// completion: a single-block tail publishes the call's sequence number `want` to a pinned host word after its last store; spin on
+// it (a stream synchronisation costs a marker packet and a signal wake-up on top of the kernels).  Anything unexpected, or a
+// multi-block tail (spin == false): synchronise the stream.  *by_spin: the word ended the wait.
+static int predict_wait(sactd3_engine* e, hipStream_t s, bool spin, int want, bool* by_spin) {
   bool done = false;
-  if (n <= tail_rows_per_block(tail_args(e, e->p_z2, e->Pa, n, 0, 0, SACTD3_SITE_PREDICT, 48u, e->h_act, e->a4, 0, nullptr))) {
-    const int want = ++e->predict_calls;
+  *by_spin = false;
+  if (spin) {
     const auto t0 = std::chrono::steady_clock::now();
     for (int spins = 0; !done; ++spins) {
       done = __atomic_load_n(e->h_done, __ATOMIC_ACQUIRE) == want;
       if (!done && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
     }
+    *by_spin = done;
     if (!done) {
-      HIPCHK(hipStreamSynchronize(e->stream));
+      HIPCHK(hipStreamSynchronize(s));
       if (__atomic_load_n(e->h_done, __ATOMIC_ACQUIRE) != want) return e->fail(SACTD3_ESTATE, "predict: the acting kernels did not report completion");
       done = true;
     }
   }
-  if (!done) HIPCHK(hipStreamSynchronize(e->stream));
+  if (!done) HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int sactd3_predict(sactd3_engine* e, const float* obs, int n, int explore, float* actions) {
+  if (!e || !obs || !actions) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (n < 1 || n > e->maxn) return e->fail(SACTD3_EINVAL, "predict: 1 <= n <= max_envs");
+  if (e->act_inflight) return e->fail(SACTD3_ESTATE, "predict: an acting call is in flight (sactd3_predict_end first)");
+  predict_stage_obs(e, obs, n);
+  RCCHK(predict_launch(e, e->stream, n, explore));
+  const bool spin = predict_one_block(e, n);
+  bool by_spin = false;
+  RCCHK(predict_wait(e, e->stream, spin, spin ? ++e->predict_calls : 0, &by_spin));
   for (int i = 0; i < n; ++i) memcpy(actions + (size_t)i * e->a, e->h_act + (size_t)i * e->a4, sizeof(float) * e->a);
+  return 0;
+}
+
+// sactd3_predict in two halves, the kernels on the acting stream: see include/sactd3.h.  The stream and its two events are made at
+// the first call, so an engine that never acts this way holds exactly what it always held.
+int sactd3_predict_begin(sactd3_engine* e, const float* obs, int n, int explore, int flags) {
+  if (!e || !obs) return e ? e->fail(SACTD3_EINVAL, "predict_begin: null argument") : SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (n < 1 || n > e->maxn) return e->fail(SACTD3_EINVAL, "predict_begin: 1 <= n <= max_envs");
+  if (flags & ~SACTD3_ACT_AFTER_ALL) return e->fail(SACTD3_EINVAL, "predict_begin: unknown flag");
+  if (e->act_inflight) return e->fail(SACTD3_ESTATE, "predict_begin: an acting call is already in flight (sactd3_predict_end first)");
+  if (!e->act_stream) {
+    HIPCHK(hipStreamCreateWithFlags(&e->act_stream, hipStreamNonBlocking));
+    if (!e->ev_learner) HIPCHK(hipEventCreateWithFlags(&e->ev_learner, hipEventDisableTiming));
+    if (!e->ev_acting) HIPCHK(hipEventCreateWithFlags(&e->ev_acting, hipEventDisableTiming));
+  }
+  predict_stage_obs(e, obs, n);
+  // learner -> acting: only behind an actor-parameter write (or on request) does the acting stream wait for the learner's
+  const bool wait = e->actor_dirty || (flags & SACTD3_ACT_AFTER_ALL);
+  if (wait) {
+    HIPCHK(hipEventRecord(e->ev_learner, e->stream));
+    HIPCHK(hipStreamWaitEvent(e->act_stream, e->ev_learner, 0));
+    e->actor_dirty = false;
+  }
+  RCCHK(predict_launch(e, e->act_stream, n, explore));
+  ++e->act_stats[0];
+  if (wait) ++e->act_stats[1];
+  e->act_spin = predict_one_block(e, n);
+  e->act_want = e->act_spin ? ++e->predict_calls : 0;
+  e->act_n = n; e->act_inflight = true; e->act_ordered = false;
+  return 0;
+}
+
+int sactd3_predict_end(sactd3_engine* e, float* actions) {
+  if (!e || !actions) return e ? e->fail(SACTD3_EINVAL, "predict_end: null argument") : SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!e->act_inflight) return e->fail(SACTD3_ESTATE, "predict_end: no acting call in flight (sactd3_predict_begin first)");
+  bool by_spin = false;
+  const int rc = predict_wait(e, e->act_stream, e->act_spin, e->act_want, &by_spin);
+  e->act_inflight = false; e->act_ordered = false;      // (whatever happened, the call is over: the engine stays usable)
+  RCCHK(rc);
+  if (by_spin) ++e->act_stats[3];
+  for (int i = 0; i < e->act_n; ++i) memcpy(actions + (size_t)i * e->a, e->h_act + (size_t)i * e->a4, sizeof(float) * e->a);
+  return 0;
+}
+
+int sactd3_acting_stats(const sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = e->act_stats[i];
   return 0;
 }
 
@@ -2020,7 +2126,9 @@ static int stream_wait(sactd3_engine* e) {
 int sactd3_sync(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
-  return stream_wait(e);
+  RCCHK(stream_wait(e));
+  if (e->act_stream) HIPCHK(hipStreamSynchronize(e->act_stream));      // (a begun call stays begun: sactd3_predict_end still collects it)
+  return 0;
 }
 
 // ---- introspection
@@ -2121,6 +2229,7 @@ int sactd3_time_nodes(sactd3_engine* e, int do_actor, int iters, int max_nodes, 
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_nodes: buffer is empty");
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
   const bool period = do_actor == 2 && e->cfg.actor_update_delay > 0 && (e->cfg.prefer_td3_over_sac || e->cfg.crit_targ_update_freq == 1);
+  if (act || period) RCCHK(actor_write_begin(e));
   std::vector<NodeInfo> log;
   auto seq = [&]() -> int { e->node_seq = 0; return period ? enqueue_period(e, e->stream) : enqueue_step(e, e->stream, act, true); };
   auto done = [&](int rc) { e->node_only = -1; e->node_log = nullptr; e->node_seq = 0; e->node_role = ""; return rc; };

@@ -33,6 +33,7 @@
 // Math follows oracle/manual_grads.py (which is checked against autograd) line by line.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 #include "philox.h"
@@ -81,16 +82,23 @@ struct DevCtl {
   unsigned long long seed;
   int sample_ctr;     // bumped after every index draw
   int noise_ctr;      // bumped at the end of every update graph
-  int predict_ctr;
+  int pad_ctr;        // (where predict_ctr used to live: the offsets of everything else are unchanged)
   int t_q, t_a, t_l;  // Adam step counts (critics, actor, log_alpha)
   int rb_len, rb_cursor;
   int inject_idx;
   int inject_eps[8];
-  int predict_seq;    // completed sactd3_predict calls (the acting tail publishes it to a pinned host word, see ActorTail::done_flag)
+  int pad_seq;        // (where predict_seq used to live)
   float metrics[8];
   float adam_q[2], adam_a[2];   // (lr / (1 - b1^t), sqrt(1 - b2^t)) of the critics' / actor's current step
   double pw_q[2], pw_a[2], pw_l[2];   // running b1^t, b2^t of the three optimisers (no pow() on the critical path)
+  // The two words the ACTING kernels write, on a 128-byte line of their own: with sactd3_predict_begin those kernels run on a second
+  // stream while learner kernels on other XCDs write sample_ctr / noise_ctr / the Adam counters above, and the per-XCD L2s are not
+  // coherent with each other -- no line is ever dirty in two of them.  (Kernels reach these words through host-computed pointers only.)
+  alignas(128) int predict_ctr;   // noise-stream counter of SACTD3_SITE_PREDICT, bumped once per exploring call
+  int predict_seq;    // completed single-block acting calls (the acting tail publishes it to a pinned host word, see ActorTail::done_flag)
+  int pad_acting[30];
 };
+static_assert(offsetof(DevCtl, predict_ctr) % 128 == 0 && sizeof(DevCtl) % 128 == 0, "acting words need a line of their own");
 
 struct NetLayout {   // float offsets inside one net's parameter block (all multiples of 4)
   int K, ld1, nh;

@@ -304,6 +304,41 @@ class Engine:
         self._ck(self.lib.sactd3_predict(self._h, _fp(obs), obs.shape[0], int(bool(explore)), _fp(out)))
         return out
 
+    def predict_begin(self, obs, explore: bool, after_all: bool = False) -> None:
+        """sactd3_predict_begin: stage `obs` and issue the acting kernels on the engine's acting stream, then return; the calls
+        made until predict_end() overlap with them.  `after_all` orders them behind everything issued so far, as predict() does;
+        otherwise they wait for the learner stream only behind a call that writes the actor (include/sactd3.h)."""
+        obs = np.asarray(obs)
+        n = obs.size // self.cfg.ob_dim
+        flags = _lib.ACT_AFTER_ALL if after_all else 0
+        if 0 < n <= self._st_n and obs.size == n * self.cfg.ob_dim:
+            self._st[5][:n] = obs.reshape(n, -1)
+            self._ck(self.lib.sactd3_predict_begin(self._h, self._st_p[5], n, 1 if explore else 0, flags))
+        else:
+            obs = _f32(obs).reshape(-1, self.cfg.ob_dim)
+            n = obs.shape[0]
+            self._ck(self.lib.sactd3_predict_begin(self._h, _fp(obs), n, int(bool(explore)), flags))   # (staged inside the call)
+        self._act_n = n
+
+    def predict_end(self) -> np.ndarray:
+        """sactd3_predict_end: wait for the kernels of the call begun with predict_begin() (for them only) -> actions [n, ac_dim]."""
+        n = getattr(self, "_act_n", 0)
+        if 0 < n <= self._st_n:
+            self._ck(self.lib.sactd3_predict_end(self._h, self._st_p[6]))
+            self._act_n = 0
+            return self._st[6][:n].copy()
+        out = np.empty((max(n, int(self.cfg.max_envs), 1), self.cfg.ac_dim), np.float32)      # (n == 0: the engine reports the state error)
+        self._ck(self.lib.sactd3_predict_end(self._h, _fp(out)))
+        self._act_n = 0
+        return out[:n].copy()
+
+    def acting_stats(self) -> Dict[str, int]:
+        """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.sactd3_acting_stats(self._h, out))
+        return dict(begun=int(out[0]), begin_waited_for_learner=int(out[1]), learner_waited_for_acting=int(out[2]),
+                    ended_by_spin=int(out[3]))
+
     def read_metrics(self) -> Dict[str, float]:
         m = np.empty(_lib.NUM_METRICS, np.float32)
         self._ck(self.lib.sactd3_read_metrics(self._h, _fp(m)))

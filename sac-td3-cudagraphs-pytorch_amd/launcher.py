@@ -202,7 +202,7 @@ def job_config(algo: str, env_id: str, seed: int, **over):
     return SimpleNamespace(**cfg)
 
 
-def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, **over):
+def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU."""
     import json
     import time
@@ -226,7 +226,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
     t0 = time.time()
-    metrics = loop.train(cfg, env, agent, fused=True, evaluator=ev)
+    metrics = loop.train(cfg, env, agent, fused=True, evaluator=ev, overlap=overlap_acting)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -253,7 +253,8 @@ def _worker_main(args) -> int:
         else:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
-                          eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity)
+                          eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity,
+                          overlap_acting=args.overlap_acting)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -279,6 +280,8 @@ def main(argv=None) -> int:
     ap.add_argument("--rb_capacity", type=int, default=None)
     ap.add_argument("--env_factory", default=None, help="module:function(env_id, num_envs, seed) -> gymnasium-protocol vector env (default: synthetic)")
     ap.add_argument("--device", type=int, default=-1, help="run every worker on this device ordinal (one-GPU rehearsals of N workers)")
+    ap.add_argument("--overlap_acting", action="store_true",
+                    help="compute the next action on the engine's acting stream while the iteration's update runs (loop.train overlap=True)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)

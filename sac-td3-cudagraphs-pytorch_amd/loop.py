@@ -34,10 +34,20 @@ class Rollout:
     `agent.timesteps_so_far < learning_starts` (:64-65), the policy's exploring action afterwards; an action stays in force for
     `action_repeat` steps (:62); a truncated env stores its true final observation as the transition's next observation while
     the rollout continues from the auto-reset one, terminated envs keep the auto-reset one (:86-89); the stored `dones` ARE the
-    terminations (:107-108); every stored field is float32 / bool with `[n, 1]` rewards and flags (:83,91-93,104-105)."""
+    terminations (:107-108); every stored field is float32 / bool with `[n, 1]` rewards and flags (:83,91-93,104-105).
 
-    def __init__(self, env, agent, seed: int, learning_starts: int, action_repeat: int):
+    `overlap=True`: `choose()` only BEGINS the policy's action (`agent.predict_begin`) and `advance()` starts by collecting it
+    (`agent.predict_end`), so whatever the caller issues in between -- the iteration's update -- runs while the action is being
+    computed.  The order of the reference is kept: the action was begun before that update.  A repeated action and the random
+    phase begin nothing.  Anything else that acts with the agent in between must call `resolve()` first."""
+
+    def __init__(self, env, agent, seed: int, learning_starts: int, action_repeat: int, overlap: bool = False):
         assert agent.rb is not None
+        if overlap:
+            for name in ("predict_begin", "predict_end"):
+                if not callable(getattr(agent, name, None)):
+                    raise TypeError(f"overlap=True needs an agent with {name}(); {type(agent).__name__} has none")
+        self.overlap, self.pending = overlap, False
         self.env, self.agent = env, agent
         self.learning_starts, self.action_repeat = learning_starts, action_repeat
         first, _ = env.reset(seed=seed)
@@ -50,10 +60,20 @@ class Rollout:
             return                                                   # the action in force is repeated
         if self.agent.timesteps_so_far < self.learning_starts:
             self.actions = self.env.action_space.sample()
+        elif self.overlap:
+            self.agent.predict_begin({"observations": self.obs}, explore=True)
+            self.pending = True
         else:
             self.actions = self.agent.predict({"observations": self.obs}, explore=True)
 
+    def resolve(self) -> None:
+        """collect the action begun by `choose()`, if one is pending, and keep it for `advance()`"""
+        if self.pending:
+            self.actions = self.agent.predict_end()
+            self.pending = False
+
     def advance(self) -> None:
+        self.resolve()
         arrived, rewards, terminations, truncations, infos = self.env.step(self.actions)
         arrived = np.asarray(arrived, np.float32)
         stored_next = arrived
@@ -71,11 +91,13 @@ class Rollout:
         self.steps += 1
 
 
-def segment(env, agent, seed: int, segment_len: int, learning_starts: int, action_repeat: int) -> Generator[None, None, None]:
+def segment(env, agent, seed: int, segment_len: int, learning_starts: int, action_repeat: int, overlap: bool = False,
+            rollout: Optional[Rollout] = None) -> Generator[None, None, None]:
     """orchestrator.py:42-118 as a generator over `Rollout`: control goes back to the caller every `segment_len` env steps, AFTER
     the next action has been chosen and BEFORE the env is stepped with it (:62-78) -- so the action that opens a segment was
-    computed with the parameters of the previous one."""
-    ro = Rollout(env, agent, seed, learning_starts, action_repeat)
+    computed with the parameters of the previous one.  `overlap`: see Rollout (the action that opens a segment is then still being
+    computed while the caller has control).  `rollout`: one the caller made itself, to `resolve()` it before it acts otherwise."""
+    ro = rollout if rollout is not None else Rollout(env, agent, seed, learning_starts, action_repeat, overlap)
     while True:
         ro.choose()
         if ro.steps and ro.steps % segment_len == 0:
@@ -84,13 +106,16 @@ def segment(env, agent, seed: int, segment_len: int, learning_starts: int, actio
 
 
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
-          evaluator: Optional["Evaluator"] = None) -> Dict[str, float]:
+          evaluator: Optional["Evaluator"] = None, overlap: bool = False) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
     launch (Agent.iteration); `fused=False` makes the reference's individual calls.  Every `eval_every` timesteps
-    `evaluator` (the reference's eval block, :354-403) and/or `on_eval` run.  Returns the last metrics."""
-    seg_gen = segment(env, agent, cfg.seed, cfg.segment_len, cfg.learning_starts, cfg.action_repeat)
+    `evaluator` (the reference's eval block, :354-403) and/or `on_eval` run.  Returns the last metrics.
+    `overlap=True` (an agent with predict_begin / predict_end): the action that opens the next segment is computed on the engine's
+    acting stream while this iteration's update runs; a pending action is collected before an evaluation acts with the agent."""
+    ro = Rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat, overlap=True) if overlap else None
+    seg_gen = segment(env, agent, cfg.seed, cfg.segment_len, cfg.learning_starts, cfg.action_repeat, rollout=ro)
     i = 0
     tlog: Dict[str, Any] = {}
     while agent.timesteps_so_far <= cfg.num_timesteps:
@@ -113,11 +138,15 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
                     agent.actor_updates_so_far += 1
             agent.update_targ_nets()
         if agent.timesteps_so_far % cfg.eval_every == 0:
+            if ro is not None:
+                ro.resolve()                                              # the evaluator / on_eval act (or load) with the same agent
             if evaluator is not None:
                 evaluator(agent)
             if on_eval is not None:
                 on_eval(agent, agent.timesteps_so_far)
         i += 1
+    if ro is not None:
+        ro.resolve()                                                      # leave no acting call in flight behind the loop
     return agent.engine.read_metrics()
 
 
