@@ -169,7 +169,11 @@ int sactd3_update_targ_nets(sactd3_engine* e, int64_t qnet_updates_so_far);
 int sactd3_step(sactd3_engine* e, int do_actor);
 /* actor_update_delay + 1 consecutive iterations of orchestrator.py:337-352 -- the first with the actor updates, the others
  * critic-only: one period of the schedule of :345-349 -- as ONE graph launch.  Equal to that many sactd3_step calls, bit for
- * bit.  Needs TD3 or crit_targ_update_freq == 1 (else SACTD3_ESTATE: issue the iterations with sactd3_step). */
+ * bit.  Needs TD3 or crit_targ_update_freq == 1 (else SACTD3_ESTATE: issue the iterations with sactd3_step).
+ * Without gradient clipping (clip_norm <= 0) a period -- and sactd3_step_prefix -- does not store what only inspection reads: the
+ * gradient arenas and the first layers' dz1.  sactd3_debug_read of "grad_critics" / "c_dz1" and "grad_actor" / "a_dz1" then fails
+ * with SACTD3_ESTATE until a call that writes that family again: sactd3_update_qnets or any sactd3_step (critics),
+ * sactd3_update_actor or sactd3_step with actor updates (actor). */
 int sactd3_step_period(sactd3_engine* e);
 /* The first m iterations of a period (1 <= m <= actor_update_delay: the one with the actor updates + m - 1 critic-only ones) as ONE
  * graph launch -- what a run of iterations leaves behind its last whole period (orchestrator.py:337-352 with a number of
@@ -223,7 +227,9 @@ int sactd3_sync(sactd3_engine* e);                                          /* [
 
 /* ---- introspection for tests / profiling (not part of the reference surface) ---- */
 /* copy a named internal device buffer to the host; returns the number of floats it holds (or < 0).
- * With dst == NULL only the size is returned. Names: see sactd3_debug_names(). [sync] */
+ * With dst == NULL only the size is returned. Names: see sactd3_debug_names(). [sync]
+ * "grad_critics", "c_dz1", "grad_actor", "a_dz1": SACTD3_ESTATE while the family's last writer was a period / cut-short period
+ * graph, which leaves them out (see sactd3_step_period) -- stale gradients are not handed out. */
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats);
 const char* sactd3_debug_names(void);
 /* number of kernel nodes in the instantiated graph of: 0 update_qnets, 1 update_actor, 2 step(do_actor=0), 3 step(do_actor=1), 4 step_period,

@@ -125,6 +125,11 @@ struct sactd3_engine {
   // and nothing has touched the state it depends on since (parameters, ring length, counters, noise injection, the slots);
   // -1: not so -- the next period starts with the opening graph.  Every state-changing ABI call resets it (CHAIN_BREAK).
   int chain_ready = -1;
+  // Stores that only inspection reads (debug_read: the gradient arenas, the folded launches' dz1) are left out of the period and cut-short
+  // period sequences when the optimiser step is fused and nothing clips (lean_stores, set while enqueue_period / enqueue_prefix run:
+  // launch_tn).  grads_stale[0 critics, 1 actor]: such a sequence ran since that family's arenas were last written in full --
+  // sactd3_debug_read refuses the family's names (grad_*, *_dz1) until an API-path update or a sactd3_step rewrites them.
+  bool lean_stores = false, grads_stale[2] = {false, false};
   float *c_z1 = nullptr, *c_xh1 = nullptr, *c_h1 = nullptr, *c_rs1 = nullptr, *c_z2 = nullptr, *c_dz2 = nullptr, *c_dh1 = nullptr, *c_dz1 = nullptr;
   float *t_z1 = nullptr, *t_z2 = nullptr, *q = nullptr, *qt = nullptr, *y = nullptr, *q_pi = nullptr, *dA = nullptr;
   float* s_h1 = nullptr;         // large-batch path: layer-1 activations of nets whose caller keeps no copy ([4][B][256])
@@ -414,20 +419,24 @@ static int launch_tn64(sactd3_engine* e, hipStream_t s, const char* name, const 
     snprintf(inst, sizeof(inst), "k_tn64<2,2,2,1,64>.dW(split-M x%d)", S);   // (instance = TN64_CFG: the name rocprofv3 reports)
     LAUNCH(inst, fl, by + 4.0 * S * nets * (double)size, TN64_KERNEL, grid, dim3(256), a);
   }
-  r.Gp = e->Gp; r.S = S; r.nets = nets; r.g_ns = size; r.G = g.G;
+  r.Gp = e->Gp; r.S = S; r.nets = nets; r.g_ns = size; r.G = g.G; r.keep_g = !(e->lean_stores && g.apply);
   r.apply = g.apply; r.P = g.P; r.Mo = g.Mo; r.Vo = g.Vo; r.T = g.T; r.tau = g.tau; r.adam = g.adam; r.b1 = g.b1; r.b2 = g.b2; r.eps = g.eps;
   r.part = g.part; r.pstride = g.pstride; r.part_s = g.part_s;
   r.loss_part = g.loss_part; r.loss_n = g.loss_n; r.loss_stride = g.loss_stride; r.loss_off = g.loss_off; r.loss_scale = g.loss_scale;
   r.loss_dst = g.loss_dst; r.tick = g.tick; r.tick_extra = tick_extra;
   const dim3 grid((unsigned)((size / 4 + 255) / 256 + 4 * r.nvec + 1), (unsigned)nets);
-  LAUNCH(g.apply ? (g.T ? "k_adam_red.sum+adam+polyak" : "k_adam_red.sum+adam") : "k_adam_red.sum", 0.0,
-         nets * (double)size * (4.0 * S + 4.0 + (g.apply ? 24.0 : 0.0) + (g.apply && g.T ? 8.0 : 0.0)), k_adam_red, grid, dim3(256), r);
+  const char* rname = g.apply ? (g.T ? "k_adam_red.sum+adam+polyak" : "k_adam_red.sum+adam") : "k_adam_red.sum";
+  const double rbytes = nets * (double)size * (4.0 * S + 4.0 + (g.apply ? 24.0 : 0.0) + (g.apply && g.T ? 8.0 : 0.0));
+  if (r.keep_g) LAUNCH(rname, 0.0, rbytes, k_adam_red<true>, grid, dim3(256), r);
+  else LAUNCH(rname, 0.0, rbytes, k_adam_red<false>, grid, dim3(256), r);
   (void)name;
   return 0;
 }
 
 static inline int tn_width(const TnProb& q) { return q.kw > 0 ? q.kw : q.ldw; }
 static int launch_tn(sactd3_engine* e, hipStream_t s, const char* name, TnArgs& g, int nets, int tick_extra = 0) {
+  g.keep_g = !(e->lean_stores && g.apply);      // (see sactd3_engine::lean_stores)
+  if (!g.keep_g) for (int i = 0; i < g.nprob; ++i) g.pr[i].f_dz = nullptr;
   if (g.M >= BIG_BATCH && e->Gp && !e->tune_tn_kt) {
     // the split-M form pays an extra node (k_adam_red): taken when the launch has enough 64 x 32 tiles to fill the chip with
     // long slices (the critics' 168 at Humanoid: 25.6 -> 18.6 us); the actor's 88 tiles gain nothing (14.3 vs 14.4 us)
@@ -473,7 +482,7 @@ static int launch_tn(sactd3_engine* e, hipStream_t s, const char* name, TnArgs& 
       for (int f = 0; f < q.nfin; ++f) { r.vec[r.nvec].off = q.fin_off[f]; r.vec[r.nvec].slot = q.fin_slot[f]; r.vec[r.nvec].nblk = q.fin_nblk[f]; ++r.nvec; }
       if (q.fin_s_off >= 0) { r.s_off = q.fin_s_off; r.s_nblk = q.fin_s_nblk; }
     }
-    r.nets = nets; r.g_ns = g.g_ns; r.G = g.G;
+    r.nets = nets; r.g_ns = g.g_ns; r.G = g.G; r.keep_g = g.keep_g;
     r.apply = g.apply; r.P = g.P; r.Mo = g.Mo; r.Vo = g.Vo; r.T = g.T; r.tau = g.tau; r.adam = g.adam; r.b1 = g.b1; r.b2 = g.b2; r.eps = g.eps;
     r.T2 = g.T2; r.T3 = g.T3;
     r.part = g.part; r.pstride = g.pstride; r.part_s = g.part_s;
@@ -483,11 +492,17 @@ static int launch_tn(sactd3_engine* e, hipStream_t s, const char* name, TnArgs& 
   }
   const dim3 grid((unsigned)((tiles + g.pk_blocks + g.fin_blocks + (nets > 1 ? 7 : 0)) & (nets > 1 ? ~7 : ~0)), 1, (unsigned)nets);
   if (!node_on(e, inst, fl, by, grid, dim3(256))) return 0;
-  if (fold) {
-    if (kt == 2) hipLaunchKernelGGL((k_tn<2, true>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((k_tn<1, true>), grid, dim3(256), 0, s, g);
-  } else if (kt == 2) hipLaunchKernelGGL(k_tn<2>, grid, dim3(256), 0, s, g);
-  else hipLaunchKernelGGL(k_tn<1>, grid, dim3(256), 0, s, g);
+  if (g.keep_g) {
+    if (fold) {
+      if (kt == 2) hipLaunchKernelGGL((k_tn<2, true>), grid, dim3(256), 0, s, g);
+      else hipLaunchKernelGGL((k_tn<1, true>), grid, dim3(256), 0, s, g);
+    } else if (kt == 2) hipLaunchKernelGGL(k_tn<2>, grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL(k_tn<1>, grid, dim3(256), 0, s, g);
+  } else if (fold) {      // the instances without the gradient-arena stores (TnArgs::keep_g)
+    if (kt == 2) hipLaunchKernelGGL((k_tn<2, true, false>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((k_tn<1, true, false>), grid, dim3(256), 0, s, g);
+  } else if (kt == 2) hipLaunchKernelGGL((k_tn<2, false, false>), grid, dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((k_tn<1, false, false>), grid, dim3(256), 0, s, g);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1801,14 +1816,18 @@ int sactd3_update_qnets(sactd3_engine* e) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   e->cur_slot = 0;
-  return run_graph(e, G_Q, [&](hipStream_t s) { return enqueue_update_qnets(e, s, false, nullptr); });
+  RCCHK(run_graph(e, G_Q, [&](hipStream_t s) { return enqueue_update_qnets(e, s, false, nullptr); }));
+  e->grads_stale[0] = false;
+  return 0;
 }
 int sactd3_update_actor(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   RCCHK(actor_write_begin(e));
-  return run_graph(e, G_A, [&](hipStream_t s) { return enqueue_update_actor(e, s, 0); });
+  RCCHK(run_graph(e, G_A, [&](hipStream_t s) { return enqueue_update_actor(e, s, 0); }));
+  e->grads_stale[1] = false;
+  return 0;
 }
 int sactd3_update_targ_nets(sactd3_engine* e, int64_t qnet_updates_so_far) {
   if (!e) return SACTD3_EINVAL;
@@ -1831,6 +1850,8 @@ int sactd3_step(sactd3_engine* e, int do_actor) {
   RCCHK(run_graph(e, which, [&](hipStream_t s) { return enqueue_step(e, s, act, polyak); }));
   e->qnet_updates = updates;
   e->cur_slot = 0;
+  e->grads_stale[0] = false;
+  if (act) e->grads_stale[1] = false;
   return 0;
 }
 
@@ -1855,8 +1876,20 @@ static bool period_is_pipelined(const sactd3_engine* e) {
 // variant (pipelined form only): which batch slot the period's first iteration trains on (0: slot 0, 1: slot 3) -- the other one
 // receives the opening pair of the NEXT period, so consecutive periods alternate (chain_ready).  The pipelined form assumes its own
 // opening pair is already in place: sactd3_step_period runs the opening graph first when it is not.
+struct LeanStores {       // scope of a period / cut-short period sequence
+  sactd3_engine* e;
+  explicit LeanStores(sactd3_engine* e_) : e(e_) { e->lean_stores = e->cfg.clip_norm <= 0.f; }
+  ~LeanStores() { e->lean_stores = false; }
+};
+// a period / cut-short period sequence was issued: what debug_read may no longer hand out (sactd3_engine::grads_stale)
+static void mark_grads_stale(sactd3_engine* e) {
+  if (e->cfg.clip_norm > 0.f) return;
+  e->grads_stale[0] = true;
+  if (e->cfg.actor_update_delay > 0) e->grads_stale[1] = true;
+}
 static int enqueue_period(sactd3_engine* e, hipStream_t s, int variant = 0) {
   const int n = e->cfg.actor_update_delay + 1;
+  LeanStores lean(e);
   if (!period_is_pipelined(e)) {
     for (int i = 0; i < n; ++i) RCCHK(enqueue_step(e, s, i == 0 && e->cfg.actor_update_delay > 0, true, i + 1 < n));
   } else {
@@ -1872,6 +1905,7 @@ static int enqueue_period(sactd3_engine* e, hipStream_t s, int variant = 0) {
 // nothing is left behind for a next period.
 static int enqueue_prefix(sactd3_engine* e, hipStream_t s, int variant, int m) {
   const int P = variant ? 3 : 0;
+  LeanStores lean(e);
   RCCHK(enqueue_step(e, s, true, true, m > 1, P, true, m - 1, -1, true));
   for (int i = 1; i < m; ++i) RCCHK(enqueue_step(e, s, false, true, i + 1 < m, i, true));
   if (e->alpha_pending) return e->fail(SACTD3_ESTATE, "step_prefix: a deferred temperature step was left over");
@@ -1895,6 +1929,7 @@ int sactd3_step_period(sactd3_engine* e) {
   if (!td3 && e->cfg.crit_targ_update_freq != 1) return e->fail(SACTD3_ESTATE, "step_period: needs crit_targ_update_freq == 1");
   const int n = e->cfg.actor_update_delay + 1;
   RCCHK(actor_write_begin(e));
+  mark_grads_stale(e);
   if (!period_is_pipelined(e)) {
     e->chain_ready = -1;
     RCCHK(run_graph(e, G_PERIOD, [&](hipStream_t s) { return enqueue_period(e, s); }));
@@ -1932,6 +1967,7 @@ int sactd3_step_prefix(sactd3_engine* e, int m) {
   const bool have = e->chain_ready >= 0;
   e->chain_ready = -1;
   RCCHK(actor_write_begin(e));
+  mark_grads_stale(e);
   if (!have) RCCHK(run_graph(e, G_OPENING, [&](hipStream_t s) { return enqueue_opening(e, s, 0); }));
   RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](hipStream_t s) { return enqueue_prefix(e, s, v, m); }));
   e->cur_slot = m - 1;
@@ -2153,6 +2189,8 @@ const char* sactd3_debug_names(void) {
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
   if (!e || !name) return SACTD3_EINVAL;
   USE_DEVICE(e);
+  if (((!strcmp(name, "grad_critics") || !strcmp(name, "c_dz1")) && e->grads_stale[0]) || ((!strcmp(name, "grad_actor") || !strcmp(name, "a_dz1")) && e->grads_stale[1]))
+    return e->fail(SACTD3_ESTATE, "debug_read: period graphs do not store this buffer; run an API-path update or sactd3_step first");
   if (!strcmp(name, "grad_actor") || !strcmp(name, "grad_critics")) {   // reference (unpadded) layout
     const bool act = !strcmp(name, "grad_actor");
     const int64_t n = sactd3_param_count(e, act ? SACTD3_ACTOR : SACTD3_CRITICS);
@@ -2230,6 +2268,7 @@ int sactd3_time_nodes(sactd3_engine* e, int do_actor, int iters, int max_nodes, 
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
   const bool period = do_actor == 2 && e->cfg.actor_update_delay > 0 && (e->cfg.prefer_td3_over_sac || e->cfg.crit_targ_update_freq == 1);
   if (act || period) RCCHK(actor_write_begin(e));
+  if (period) mark_grads_stale(e);
   std::vector<NodeInfo> log;
   auto seq = [&]() -> int { e->node_seq = 0; return period ? enqueue_period(e, e->stream) : enqueue_step(e, e->stream, act, true); };
   auto done = [&](int rc) { e->node_only = -1; e->node_log = nullptr; e->node_seq = 0; e->node_role = ""; return rc; };

@@ -189,6 +189,26 @@ __device__ __forceinline__ float sum4(float4 v) { return (v.x + v.y) + (v.z + v.
 __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// ---- store policy per output buffer (profiles/store_policy.json).  A plain store leaves its line dirty in the
+// XCD's write-back L2 until the release at the end of the kernel; a write-through store (`sc1`) sends it on at once and drops the
+// line, which a reader on ANOTHER XCD does not miss and a reader on the same XCD does.  The write-through forms are vector stores:
+// 16 bytes through a buffer resource on a block-uniform base (`buffer_store_dwordx4 ... offen sc1`), 4 bytes as a relaxed
+// agent-scope atomic store (`global_store_dword ... sc1`).  SACTD3_WT is a build-time mask of the classes that take them -- one
+// bit per class so that library builds can be compared class by class (make WT=<mask>); the shipped value is the measured choice.
+#ifndef SACTD3_WT
+#define SACTD3_WT 1
+#endif
+constexpr bool WT_ACT1 = (SACTD3_WT & 1) != 0;   // k_nt: first-layer activations kept for the backward pass (h1, xhat1)
+constexpr bool WT_Z2 = (SACTD3_WT & 2) != 0;     // k_nt: the trunk output z2 (read next by row / tail kernels with another block -> row map)
+constexpr bool WT_DZ = (SACTD3_WT & 4) != 0;     // k_ctail_nn / k_headbwd_nn: dz2 (read next by k_tn, an all-to-all)
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void st4_wt(float* base, long off, float4 v) {      // base[off .. off + 3], base block-uniform, 4 off < 2^31
+  const u32x4 u = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+  __builtin_amdgcn_raw_buffer_store_b128(u, __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000), (int)(4 * off), 0, 16);   // aux 16 = sc1
+}
+__device__ __forceinline__ void st1_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <bool WT> __device__ __forceinline__ void st4_pol(float* base, long off, float4 v) { if (WT) st4_wt(base, off, v); else st4(base + off, v); }
+template <bool WT> __device__ __forceinline__ void st1_pol(float* p, float v) { if (WT) st1_wt(p, v); else *p = v; }
 __device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
 __device__ __forceinline__ float4 operator+(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 operator-(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
@@ -778,8 +798,8 @@ __global__ __launch_bounds__(256) void k_nt(NtArgs p) {
     for (int c = 0; c < CW; ++c) {
       const int gc = ks * CW + c;                              // (wave-uniform)
       if (gc >= g0 && gc < g0 + gsz) {
-        if (G.xh_out) st4(G.xh_out + ro + 16 * c, xh[c]);
-        if (G.h_out) st4(G.h_out + ro + 16 * c, av[c]);
+        if (G.xh_out) st4_pol<WT_ACT1>(G.xh_out, ro + 16 * c, xh[c]);
+        if (G.h_out) st4_pol<WT_ACT1>(G.h_out, ro + 16 * c, av[c]);
       }
     }
     if (G.rstd_out && tn == 0 && ks == 0 && kq == 0) G.rstd_out[(long)ni * p.M + m0 + r] = rstd;
@@ -852,7 +872,7 @@ __global__ __launch_bounds__(256) void k_nt(NtArgs p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = m0 + 4 * (lane >> 4) + i;
-        if (row < p.M) y[(long)row * p.ldy + col] = acc[nt][i] + bias[nt];
+        if (row < p.M) st1_pol<WT_Z2>(y + (long)row * p.ldy + col, acc[nt][i] + bias[nt]);
       }
     }
   }
@@ -1328,7 +1348,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_nn64(NnArgs p) {        // dX[
 struct AdamRedVec { int off; int slot; int nblk; };
 struct AdamRedArgs {
   const float* Gp; int S; int nets; long g_ns;           // slabs [S][nets][g_ns]
-  float* G;                                              // gradient arena (always written)
+  float* G; int keep_g;                                  // gradient arena; keep_g (host side): which instance runs, see TnArgs::keep_g
   int apply; float* P; float* Mo; float* Vo; float* T; float tau;
   float* T2; float* T3;                                  // optional: the target one / two further Polyak steps ahead (see TnArgs)
   const float* adam; float b1, b2, eps;
@@ -1338,8 +1358,9 @@ struct AdamRedArgs {
   const float* loss_part; int loss_n, loss_stride, loss_off; float loss_scale; float* loss_dst; int* tick;
   int tick_extra;                                        // the counter advances by 1 + tick_extra (a deferred temperature step's tick)
 };
+template <bool KEEP_G>
 __device__ __forceinline__ void adam_red_commit(const AdamRedArgs& a, long off, float4 g, float4 w, float4 m, float4 v, float4 tt, float step, float sq2) {
-  st4(a.G + off, g);
+  if (KEEP_G) st4(a.G + off, g);
   if (a.apply) {
     const float omb1 = 1.0f - a.b1, omb2 = 1.0f - a.b2;
     m = m + (g - m) * omb1;
@@ -1362,6 +1383,7 @@ __device__ __forceinline__ void adam_red_commit(const AdamRedArgs& a, long off, 
 // (t >> 4) + 16 quarter; 16 threads share its row-block partials and DPP-reduce them); block 4 nvec = the scalar element
 // (critic head bias) + the loss finalisation + the counter tick.  Used by k_adam_red and, as riding blocks, by k_tn -- whose
 // tile blocks then do nothing but their GEMM tile and its optimiser step.
+template <bool KEEP_G>
 __device__ __forceinline__ void adam_red_tail_body(const AdamRedArgs& a, int rel, int net) {
   const int t = threadIdx.x;
   const float step = a.apply ? a.adam[0] : 0.f, sq2 = a.apply ? a.adam[1] : 1.f;
@@ -1387,7 +1409,7 @@ __device__ __forceinline__ void adam_red_tail_body(const AdamRedArgs& a, int rel
       if (blk + 48 < nb) g = g + v3;
     }
     g.x = row16_sum(g.x); g.y = row16_sum(g.y); g.z = row16_sum(g.z); g.w = row16_sum(g.w);
-    if (sub == 0) adam_red_commit(a, off, g, w, m, v, tt, step, sq2);
+    if (sub == 0) adam_red_commit<KEEP_G>(a, off, g, w, m, v, tt, step, sq2);
     return;
   }
   if (t >= 64) return;
@@ -1405,7 +1427,7 @@ __device__ __forceinline__ void adam_red_tail_body(const AdamRedArgs& a, int rel
     float sg = 0.f;
     for (int blk = t; blk < a.s_nblk; blk += 64) sg += a.part_s[((long)net * a.pstride + blk) * 2];
     sg = wave_sum(sg);
-    if (t == 0) adam_red_commit(a, off, make_float4(sg, 0.f, 0.f, 0.f), w, m, v, tt, step, sq2);
+    if (t == 0) adam_red_commit<KEEP_G>(a, off, make_float4(sg, 0.f, 0.f, 0.f), w, m, v, tt, step, sq2);
   }
   if (extras) {
     if (a.loss_dst) {
@@ -1453,7 +1475,13 @@ struct TnProb {              // one weight-gradient GEMM: dW[N, ldw] = dY[M,N]^T
 constexpr int PS_W = 32;                 // floats per row of the row-sum partials: 16 tiles x 2 sums
 struct TnArgs {              // up to 4 problems per launch; block = one 16 x 16 tile of one problem, M split over the 4 waves
   TnProb pr[4]; int nprob; int M;       // (a GEMM may be cut in two problems to steer which blocks share a CU: engine.hip, tn_split)
-  float* G; long g_ns;                   // gradient arena (always written; net stride g_ns)
+  float* G; long g_ns;                   // gradient arena (net stride g_ns), written by the KEEP_G instances
+  // keep_g == 0 (host side, launch_tn: period / cut-short period graphs with apply == 1 and no gradient clipping): the gradients are
+  // consumed by the fused optimiser step and go nowhere else -- G (and the folded problems' dz1, TnProb::f_dz == nullptr) are read by
+  // nothing but sactd3_debug_read, and a store that is not made is not written back at the node boundary either.  The choice is a
+  // kernel INSTANCE (k_tn<.., KEEP_G>), not a branch: a store behind a run-time flag made the compiler drain the memory queue in front
+  // of every row's group of epilogue stores (+0.2 us per Hopper iteration instead of a gain)
+  int keep_g;
   // optimiser step fused into the epilogue (torch.optim.Adam, agents/agent.py:236,286), optionally with the Polyak
   // update of the same element (agents/agent.py:328).  apply == 0: gradients only (clip_grad_norm_ path).
   // T2 / T3 (TD3 period graphs): the parameters do not change again before the next two Polyak updates of this target, so what
@@ -1480,8 +1508,9 @@ __device__ __forceinline__ AdamState adam_fetch(const TnArgs& p, long off) {
   if (p.apply) { s.w = p.P[off]; s.m = p.Mo[off]; s.v = p.Vo[off]; if (p.T) s.t = p.T[off]; }
   return s;
 }
+template <bool KEEP_G>
 __device__ __forceinline__ void adam_commit(const TnArgs& p, long off, float g, AdamState s, float step, float sq2) {
-  p.G[off] = g;
+  if (KEEP_G) p.G[off] = g;
   if (p.apply) {
     const float m = s.m + (g - s.m) * (1.0f - p.b1);
     const float v = s.v * p.b2 + g * g * (1.0f - p.b2);
@@ -1503,7 +1532,7 @@ __device__ __forceinline__ void adam_commit(const TnArgs& p, long off, float g, 
 // and wave 1 commit one each -- used when a launch would otherwise put more than two blocks on every CU.
 // FOLD: the instance whose layer-1 problem applies the LayerNorm backward itself (TnProb::fold); launches without such a problem
 // take the plain instance (the fold's operands cost registers: the actor's B = 1024 launch was 5 us slower through one kernel).
-template <int KT, bool FOLD = false>
+template <int KT, bool FOLD = false, bool KEEP_G = true>
 __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
   __shared__ __attribute__((aligned(16))) float red[KT * 4 * 64 * 4];
   __shared__ __attribute__((aligned(16))) float Ys[256 * YS];
@@ -1516,7 +1545,7 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
   if ((int)blockIdx.x >= p.tiles) {                         // (block-uniform) riding blocks
     const int x = (int)blockIdx.x - p.tiles;
     if (x < p.pk_blocks) { if (net == 0) polyak_body(p.pk, x, p.pk_blocks); }
-    else if (x - p.pk_blocks < p.fin_blocks) adam_red_tail_body(p.fin, x - p.pk_blocks, net);      // (behind them: padding up to a multiple of 8 blocks
+    else if (x - p.pk_blocks < p.fin_blocks) adam_red_tail_body<KEEP_G>(p.fin, x - p.pk_blocks, net);      // (behind them: padding up to a multiple of 8 blocks
     BLK_MARK(1);                                                                                  //  per net, so that every net's tile ids keep their XCDs)
     return;
   }
@@ -1648,6 +1677,11 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
   }
   __syncthreads();
   STAMP(3); BLK_PH(3);
+  if (!KEEP_G) {          // (without the arena store in front of it, each row's branch below would be the first use of its optimiser
+#pragma unroll           //  state, and every group of stores would wait for the previous group's: PIN)
+    for (int i = 0; i < 4; ++i) { PIN(st[i].w); PIN(st[i].m); PIN(st[i].v); PIN(st[i].t); }
+    PIN(fstate.w); PIN(fstate.m); PIN(fstate.v); PIN(fstate.t);
+  }
   if (wave < KT && ecol < kw) {
     const float* rr = red + (wave * 4 * 64 + lane) * 4;
     const float4 a = ld4(rr), b = ld4(rr + 256), c = ld4(rr + 512), d = ld4(rr + 768);
@@ -1655,7 +1689,7 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = n0 + 4 * (lane >> 4) + i;
-      if (row < q.N) adam_commit(p, nbase + q.w_off + (long)row * q.ldw + ecol, ecol < q.K ? o[i] : 0.f, st[i], step, sq2);
+      if (row < q.N) adam_commit<KEEP_G>(p, nbase + q.w_off + (long)row * q.ldw + ecol, ecol < q.K ? o[i] : 0.f, st[i], step, sq2);
     }
   }
   if (foff >= 0) {
@@ -1668,7 +1702,7 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) v += f[i * 32];
     }
-    adam_commit(p, foff, v, fstate, step, sq2);
+    adam_commit<KEEP_G>(p, foff, v, fstate, step, sq2);
   }
   STAMP(4); BLK_PH(4);
   BLK_MARK(1);
@@ -1886,11 +1920,12 @@ __global__ __launch_bounds__(256) void k_tn64(Tn64Args p) {
 }
 
 // grid = (main blocks + 4 nvec vector blocks + 1 scalar block, nets); main blocks = ceil(g_ns / 1024)
+template <bool KEEP_G = true>
 __global__ __launch_bounds__(256) void k_adam_red(AdamRedArgs a) {
   const int net = blockIdx.y, t = threadIdx.x;
   const int main_blocks = (int)((a.g_ns / 4 + 255) / 256);
   const int bx = blockIdx.x;
-  if (bx >= main_blocks) { adam_red_tail_body(a, bx - main_blocks, net); return; }
+  if (bx >= main_blocks) { adam_red_tail_body<KEEP_G>(a, bx - main_blocks, net); return; }
   const float step = a.apply ? a.adam[0] : 0.f, sq2 = a.apply ? a.adam[1] : 1.f;
   // slab-sourced elements: one float4 per thread (the vector ranges and the scalar's float4 belong to the tail blocks)
   const long i = ((long)bx * 256 + t) * 4;
@@ -1908,7 +1943,7 @@ __global__ __launch_bounds__(256) void k_adam_red(AdamRedArgs a) {
     float4 g = gs[0];
 #pragma unroll
     for (int sl = 1; sl < 8; ++sl) if (sl < a.S) g = g + gs[sl];
-    adam_red_commit(a, off, g, w, m, v, tt, step, sq2);
+    adam_red_commit<KEEP_G>(a, off, g, w, m, v, tt, step, sq2);
   }
 }
 
@@ -2539,7 +2574,7 @@ __global__ __launch_bounds__(256) void k_ctail_nn(CtailNn a) {
   for (int q = 0; q < 4; ++q) {
     const int col = 4 * sub + 64 * q;                      // (the thread's float4 of chunk q lies inside one 16-column tile)
     if (col >= c_lo && col < c_lo + CB) {
-      if (valid) st4(p.dz2 + ((long)net * p.B + b) * HID + col, dz.v[q]);
+      if (valid) st4_pol<WT_DZ>(p.dz2, ((long)net * p.B + b) * HID + col, dz.v[q]);
 #pragma unroll
       for (int sl = 0; sl < 3; ++sl) st4(cs + (sl * 16 + row) * CB + (col - c_lo), vals[sl].v[q]);
     }
@@ -3258,7 +3293,7 @@ __global__ __launch_bounds__(256) void k_headbwd_nn(HeadBwdNn a) {
   for (int q = 0; q < 4; ++q) {
     const int col = 4 * sub + 64 * q;
     if (col >= c_lo && col < c_lo + CB) {
-      if (valid) st4(p.dz2 + (long)b * HID + col, dz.v[q]);
+      if (valid) st4_pol<WT_DZ>(p.dz2, (long)b * HID + col, dz.v[q]);
 #pragma unroll
       for (int sl = 0; sl < 2; ++sl) st4(cs + (sl * 16 + row) * CB + (col - c_lo), vals[sl].v[q]);
     }

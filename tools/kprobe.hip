@@ -58,7 +58,7 @@ int main() {
     CK(hipMalloc(&adam, 16)); CK(hipMalloc(&part, 2 * 16 * NSLOT * 256 * 4)); CK(hipMalloc(&ps, 2 * 16 * 2 * 4));
     CK(hipMemset(G, 0, 2 * 80000 * 4)); CK(hipMemset(Mo, 0, 2 * 80000 * 4)); CK(hipMemset(Vo, 0, 2 * 80000 * 4)); CK(hipMemset(T, 0, 2 * 80000 * 4));
     float ha[2] = {1e-3f, 0.03f}; CK(hipMemcpy(adam, ha, 8, hipMemcpyHostToDevice)); CK(hipMemset(part, 0, 2 * 16 * NSLOT * 256 * 4)); CK(hipMemset(ps, 0, 2 * 16 * 2 * 4));
-    TnArgs g{}; g.nprob = 2; g.M = B; g.G = G; g.g_ns = 80000;
+    TnArgs g{}; g.nprob = 2; g.M = B; g.G = G; g.keep_g = 1; g.g_ns = 80000;
     TnProb q0{}; q0.dY = Z2; q0.ldy = 256; q0.dy_ns = B * 256; q0.N = 256; q0.X = H; q0.ldx = 256; q0.x_ns = B * 256; q0.K = 256; q0.w_off = W2; q0.ldw = 256; q0.b_off = b2;
     q0.nfin = 3; q0.fin_slot[0] = 0; q0.fin_off[0] = b2 + 256; q0.fin_slot[1] = 1; q0.fin_off[1] = b2 + 512; q0.fin_slot[2] = 2; q0.fin_off[2] = b2 + 768; q0.fin_s_off = b2 + 768 + 256; q0.fin_s_nblk = 16; q0.fin_nblk[0] = q0.fin_nblk[1] = q0.fin_nblk[2] = 16; q0.tile0 = 0;
     TnProb q1{}; q1.dY = Y; q1.ldy = 256; q1.dy_ns = B * 256; q1.N = 256; q1.X = X; q1.ldx = ldc; q1.x_ns = 0; q1.K = o + a; q1.w_off = W1; q1.ldw = 16; q1.b_off = b1;
