@@ -15,9 +15,8 @@
  *   - calls are asynchronous on the engine's HIP stream unless marked [sync];
  *   - one engine = one learner = one GPU; an engine is not thread-safe, different engines are.
  *   - all arithmetic is fp32, hidden width is 256 (agents/agent.py:56,101 hard-codes (256,256)).
- *   - the library reads NO environment variable: every behaviour is a field of sactd3_config.  (Kernel-selection A/B switches
- *     exist only in the separate tuning build, `make -C csrc tune` -> libsactd3_hip_tune.so, -DSACTD3_TUNING; they are listed in
- *     csrc/engine.hip:create_impl and never compiled into libsactd3_hip.so -- tests/test_abi.py checks the shipped binary.)
+ *   - the library reads NO environment variable: every behaviour is a field of sactd3_config (tests/test_abi.py checks the
+ *     source and the shipped binary).
  */
 #ifndef SACTD3_H
 #define SACTD3_H

@@ -153,8 +153,6 @@ struct sactd3_engine {
   bool actor_dirty = true, act_inflight = false, act_ordered = false, act_spin = false;
   int act_n = 0, act_want = 0;
   int64_t act_stats[4] = {};                    // sactd3_acting_stats
-  // kernel-selection knobs: fixed defaults in the shipped library; tuning builds (-DSACTD3_TUNING) read them from the environment at create
-  int tune_ks = 0, tune_nt = 0, tune_tn_kt = 0, tune_pad64 = 0, tune_tn64_min = 0, tune_rows4 = 0, tune_nn16 = 0, tune_xr = -1;
   // node registry of the enqueue_* sequences (sactd3_time_nodes): every kernel launch of the path goes through
   // node_on(), which numbers it; with node_only >= 0 only that launch is issued (the others are skipped), with
   // node_log set the launch's name and algorithmic FLOPs / bytes are recorded.
@@ -226,14 +224,13 @@ static inline bool node_on(sactd3_engine* e, const char* name, double flops, dou
   }
   return e->node_only < 0 || e->node_only == k;
 }
-#define LAUNCH_DYN(name, flops, bytes, kernel, grid, block, dyn_lds, ...)    \
+#define LAUNCH(name, flops, bytes, kernel, grid, block, ...)                 \
   do {                                                                      \
     if (node_on(e, name, flops, bytes, grid, block)) {                      \
-      hipLaunchKernelGGL(kernel, grid, block, dyn_lds, s, __VA_ARGS__);     \
+      hipLaunchKernelGGL(kernel, grid, block, 0, s, __VA_ARGS__);           \
       HIPCHK(hipGetLastError());                                            \
     }                                                                       \
   } while (0)
-#define LAUNCH(name, flops, bytes, kernel, grid, block, ...) LAUNCH_DYN(name, flops, bytes, kernel, grid, block, 0, __VA_ARGS__)
 
 static inline dim3 tile_grid(int tiles, int nets) { return dim3((unsigned)((tiles + 3) / 4), 1, (unsigned)nets); }
 
@@ -254,10 +251,9 @@ static GatherArgs gather_args(sactd3_engine* e, const float* ring, int identity_
   return g;
 }
 template <int PRO, bool F1, int C1>
-static void launch_nt_ks(hipStream_t s, int ks, dim3 grid, const NtArgs& g) {
+static void launch_nt_ks(hipStream_t s, int ks, dim3 grid, const NtArgs& g) {      // ks = 2 or 4
   if (ks == 4) hipLaunchKernelGGL((k_nt<PRO, F1, 4, C1>), grid, dim3(256), 0, s, g);
-  else if (ks == 2) hipLaunchKernelGGL((k_nt<PRO, F1, 2, C1>), grid, dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((k_nt<PRO, F1, 1, C1>), grid, dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((k_nt<PRO, F1, 2, C1>), grid, dim3(256), 0, s, g);
 }
 template <int PRO>
 static void launch_nt_f1(hipStream_t s, int ks, int nt, dim3 grid, const NtArgs& g) {
@@ -286,8 +282,7 @@ static void launch_nt_c4(hipStream_t s, int nt, dim3 grid, const NtArgs& g) {   
 }
 // XCD row groups for xcd_tile (kernels.h) of an R x C tile grid whose row operand is A bytes and column operand W bytes: the
 // split xr x xc = 8 with the least total fetch xc A + xr W among those that divide the grid; 0 = keep row-major numbering.
-static int pick_xr(const sactd3_engine* e, int R, int C, double A, double W) {
-  if (e->tune_xr >= 0) return (e->tune_xr == 0 || (R % e->tune_xr == 0 && C % (8 / e->tune_xr) == 0)) ? e->tune_xr : 0;
+static int pick_xr(int R, int C, double A, double W) {
   int best = 0; double cost = 1e300;
   for (int xr = 1; xr <= 8; xr *= 2) {
     const int xc = 8 / xr;
@@ -314,17 +309,16 @@ static int launch_nt(sactd3_engine* e, hipStream_t s, const char* name, int pro,
   } else {
     const int tiles = tiles_m * tiles_n * nets;
     int ks = tiles >= 2 * e->num_cus ? 2 : 4;   // measured on 256 .. 4096-tile launches (KS = 1 never won)
-    if (e->tune_ks) ks = e->tune_ks;
     if (force_ks) ks = force_ks;
     // a launch that must reproduce the KS = 4 sums (force_ks: the run-ahead passes of a period graph) but holds several groups: 32-row
     // blocks with the KS = 4 summation tree (k_nt's C4 form) -- half as many blocks fetch W1 and their W2 tile
-    const bool c4 = force_ks == 4 && fuse1 && pro == 1 && tiles >= 2 * e->num_cus && !(e->tune_rows4 & 32768);
+    const bool c4 = force_ks == 4 && fuse1 && pro == 1 && tiles >= 2 * e->num_cus;
     if (c4) ks = 2;
     const int rb = 64 / ks;
     // two column tiles per block when the launch would otherwise put two rounds of blocks on every CU: the fused first
     // layer is then recomputed (or the A rows fetched and normalised) by half as many blocks
     int nt = (ks == 2 && ((g.M + rb - 1) / rb) * tiles_n * nets >= 2 * e->num_cus && tiles_n % 2 == 0) ? 2 : 1;
-    if (e->tune_nt == 1 || (force_ks && !c4)) nt = 1;
+    if (force_ks && !c4) nt = 1;
     // (C4: two column tiles per block only when that leaves at most one block per CU: 4 groups -> 256 blocks; 5 groups would be 320,
     //  a quarter of the CUs with two -- they take 640 single-tile blocks instead)
     if (c4 && nt == 2 && ((g.M + rb - 1) / rb) * (tiles_n / 2) * nets > e->num_cus) nt = 1;
@@ -332,14 +326,14 @@ static int launch_nt(sactd3_engine* e, hipStream_t s, const char* name, int pro,
     gg.nt_blocks = ((g.M + rb - 1) / rb) * (tiles_n / nt);
     // unfused launches read whole input rows: place the tiles so that an XCD pulls few rows and few weight columns (the fused
     // form's input rows are a few dozen bytes: it keeps one weight column tile per XCD, the row-major numbering)
-    gg.xr = fuse1 ? 0 : pick_xr(e, (g.M + rb - 1) / rb, tiles_n / nt, 4.0 * g.M * g.K, 4.0 * g.N * g.K);
+    gg.xr = fuse1 ? 0 : pick_xr((g.M + rb - 1) / rb, tiles_n / nt, 4.0 * g.M * g.K, 4.0 * g.N * g.K);
     int nzb = 0;
     for (int i = 0; i < gg.nz_n && i < 5; ++i) nzb += gg.nz[i].blocks;
     const int riders = gg.gblocks + gg.alpha_block + nzb;
     // (see NtArgs::flat; with many riders -- the run-ahead launches' gathers and noise blocks -- the 3-D grid's order, net 0's tiles,
     //  the riders, then the other nets' tiles, measured 0.3 us per TD3 iteration better; TD3's 4-net critic trunk, one block per CU by
     //  its LDS, with its 1-3 noise riders: 0.5 us better in the 3-D grid too)
-    gg.flat = (nets > 1 && gg.alpha_block && riders <= 8 && !(e->tune_rows4 & 65536)) ? nets : 0;      // (the critic trunk that carries a deferred temperature step)
+    gg.flat = (nets > 1 && gg.alpha_block && riders <= 8) ? nets : 0;      // (the critic trunk that carries a deferred temperature step)
     gg.flat_r = gg.flat ? (riders + 7) & ~7 : 0; gg.flat_n = riders;
     const dim3 grid = gg.flat ? dim3((unsigned)(gg.nt_blocks * nets + gg.flat_r)) : dim3((unsigned)(gg.nt_blocks + riders), 1, (unsigned)nets);
     char inst[64] = "k_nt";
@@ -359,7 +353,7 @@ static int launch_nt(sactd3_engine* e, hipStream_t s, const char* name, int pro,
   return 0;
 }
 static int launch_nn(sactd3_engine* e, hipStream_t s, const char* name, const NnArgs& g, int nets) {
-  if (g.M >= BIG_BATCH && g.Kout == HID && g.k_off == 0 && !e->tune_nn16) {   // large batch: LDS-tiled form, ~1 block per CU
+  if (g.M >= BIG_BATCH && g.Kout == HID && g.k_off == 0) {   // large batch: LDS-tiled form, ~1 block per CU
     const double fl = 2.0 * nets * (double)g.M * HID * HID, by = 4.0 * nets * (2.0 * g.M * HID + (double)HID * HID);
     if (nets >= 2) {
       const dim3 grid((unsigned)(((g.M + 31) / 32) * (HID / 64) * nets));
@@ -373,7 +367,7 @@ static int launch_nn(sactd3_engine* e, hipStream_t s, const char* name, const Nn
   }
   const dim3 grid((unsigned)(((g.M + 15) / 16) * ((g.Kout + 15) / 16)), 1, (unsigned)nets);
   NnArgs gg = g;
-  gg.xr = pick_xr(e, (g.M + 15) / 16, (g.Kout + 15) / 16, 4.0 * g.M * HID, 4.0 * HID * g.Kout);
+  gg.xr = pick_xr((g.M + 15) / 16, (g.Kout + 15) / 16, 4.0 * g.M * HID, 4.0 * HID * g.Kout);
   LAUNCH(name, 2.0 * nets * (double)g.M * HID * g.Kout, 4.0 * nets * ((double)g.M * HID + (double)HID * g.Kout + (double)g.M * g.Kout),
          k_nn, grid, dim3(256), gg);
   return 0;
@@ -434,15 +428,18 @@ static int launch_tn64(sactd3_engine* e, hipStream_t s, const char* name, const 
 }
 
 static inline int tn_width(const TnProb& q) { return q.kw > 0 ? q.kw : q.ldw; }
+// The split-M form pays an extra node (k_adam_red): taken at large batch when the launch has enough 64 x 32 tiles (over all of its
+// nets) to fill the chip with long slices (the critics' 168 at Humanoid: 25.6 -> 18.6 us); the actor's 88 tiles gain nothing (14.3
+// vs 14.4 us)
+static bool tn_is_tiled64(const sactd3_engine* e, int M, int tiles64) { return M >= BIG_BATCH && e->Gp && tiles64 >= e->num_cus / 2; }
+static inline int tn64_tiles(int N, int ldw) { return ((N + TN64_N - 1) / TN64_N) * ((ldw + TN64_K - 1) / TN64_K); }
 static int launch_tn(sactd3_engine* e, hipStream_t s, const char* name, TnArgs& g, int nets, int tick_extra = 0) {
   g.keep_g = !(e->lean_stores && g.apply);      // (see sactd3_engine::lean_stores)
   if (!g.keep_g) for (int i = 0; i < g.nprob; ++i) g.pr[i].f_dz = nullptr;
-  if (g.M >= BIG_BATCH && e->Gp && !e->tune_tn_kt) {
-    // the split-M form pays an extra node (k_adam_red): taken when the launch has enough 64 x 32 tiles to fill the chip with
-    // long slices (the critics' 168 at Humanoid: 25.6 -> 18.6 us); the actor's 88 tiles gain nothing (14.3 vs 14.4 us)
+  {
     int tiles = 0;
-    for (int i = 0; i < g.nprob; ++i) tiles += ((g.pr[i].N + TN64_N - 1) / TN64_N) * ((g.pr[i].ldw + TN64_K - 1) / TN64_K);
-    if (tiles * nets >= e->tune_tn64_min) return launch_tn64(e, s, name, g, nets, tick_extra);
+    for (int i = 0; i < g.nprob; ++i) tiles += tn64_tiles(g.pr[i].N, g.pr[i].ldw);
+    if (tn_is_tiled64(e, g.M, tiles * nets)) return launch_tn64(e, s, name, g, nets, tick_extra);
   }
   auto count = [&](int kt) {
     int tiles = 0;
@@ -455,11 +452,10 @@ static int launch_tn(sactd3_engine* e, hipStream_t s, const char* name, TnArgs& 
   // two k tiles per block (one dY slice fetched and transposed for both) once single tiles would be more than two blocks per CU
   // (the critics' launch at B = 256: 544 blocks -> 288, -0.6 us per iteration)
   int kt = (count(1) * nets > 2 * e->num_cus && g.M < BIG_BATCH) ? 2 : 1;   // (measured: no gain with a thousand rows per tile)
-  if (e->tune_tn_kt) kt = e->tune_tn_kt;
   const int tiles = count(kt);
   for (int i = 0; i < g.nprob; ++i)      // n tiles need dY columns, k tiles X columns (both M rows long)
     g.pr[i].xr = g.pr[i].xr_force ? g.pr[i].xr_force
-                                  : pick_xr(e, (g.pr[i].N + 15) / 16, ((tn_width(g.pr[i]) + 15) / 16 + kt - 1) / kt, 4.0 * g.M * g.pr[i].N, 4.0 * g.M * tn_width(g.pr[i]));
+                                  : pick_xr((g.pr[i].N + 15) / 16, ((tn_width(g.pr[i]) + 15) / 16 + kt - 1) / kt, 4.0 * g.M * g.pr[i].N, 4.0 * g.M * tn_width(g.pr[i]));
   // dW = dY^T X of every problem; operands dY, X once each; the weight block's gradient written, and with the fused
   // optimiser step p, m, v read and written (+ the Polyak target): 4 (g) + 24 (Adam) + 8 (Polyak) bytes per parameter
   double fl = 0.0, by = 0.0;
@@ -572,7 +568,7 @@ static int enqueue_trunk(sactd3_engine* e, hipStream_t s, int ldx, int K, int M,
     for (int i = 0; i < tk.nnoise; ++i) { a.nz[i] = tk.noise[i]; a.nz[i].blocks = (tk.noise[i].n + 1023) / 1024; }
     if (tk.noise_taken) *tk.noise_taken = true;
   };
-  // MFMA-bound sizes with enough 64 x 64 tiles to fill the chip: tiled GEMM -> LayerNorm row kernel -> tiled GEMM
+  // MFMA-bound sizes with enough 64 x 64 tiles to fill the chip: tiled GEMM -> tiled GEMM with the LayerNorm + ReLU prologue
   if (big_path) {
     NtArgs g{};
     g.npg = npg; g.oW = L.W1; g.ldw = L.ld1; g.oBias = L.b1; g.p_ns = p_ns; g.ld_in = ldx; g.in_ns = 0;
@@ -585,28 +581,8 @@ static int enqueue_trunk(sactd3_engine* e, hipStream_t s, int ldx, int K, int M,
     {   // a pending temperature step rides as one extra block of the first-layer launch (nothing in the trunk reads log_alpha)
       dim3 grid1 = grid;
       if (tk.alpha) { g.alpha_block = 1; g.al = *tk.alpha; g.nt_blocks = (int)grid.x; grid1.x += 1; }
-      LAUNCH_DYN("k_nt64<4,2,2>.layer1", 2.0 * nets * (double)M * HID * K, by_w * (K + 1) + 4.0 * ngrp * (double)M * K + by_rows,
-                 (k_nt64<4, 2, 2>), grid1, dim3(512), e->tune_pad64, g);
-    }
-    if (e->tune_rows4 & 128) {   // (A/B: the separate LayerNorm row kernel between the two tiled GEMMs)
-      LnFwd l{};
-      l.npg = npg; l.oG = L.g1; l.oBe = L.be1; l.p_ns = p_ns; l.B = M; l.ln = e->cfg.layer_norm;
-      for (int i = 0; i < ngrp; ++i) {
-        l.P[i] = grp[i].P; l.zin[i] = grp[i].z1;
-        l.h[i] = grp[i].h ? grp[i].h : e->s_h1 + (size_t)i * npg * M * HID;
-        l.xh[i] = grp[i].xh; l.rstd[i] = grp[i].rstd;
-      }
-      {
-        double st = 1.0;   // rows written: h always, xhat where the caller keeps it
-        for (int i = 0; i < ngrp; ++i) st += grp[i].xh ? 1.0 / ngrp : 0.0;
-        LAUNCH("k_ln_fwd", 0.0, by_rows * (1.0 + st), k_ln_fwd, dim3((unsigned)((M + 15) / 16), (unsigned)nets), dim3(256), l);
-      }
-      NtArgs h2{};
-      h2.npg = npg; h2.oW = L.W2; h2.ldw = HID; h2.oBias = L.b2; h2.p_ns = p_ns; h2.ld_in = HID; h2.in_ns = (long)M * HID;
-      h2.ldy = HID; h2.y_ns = (long)M * HID; h2.M = M; h2.N = HID; h2.K = HID;
-      for (int i = 0; i < ngrp; ++i) { h2.g[i].in = l.h[i]; h2.g[i].P = grp[i].P; h2.g[i].Y = grp[i].z2; }
-      LAUNCH_DYN("k_nt64<4,2,2>.layer2", 2.0 * nets * (double)M * HID * HID, by_w * (HID + 1) + 2.0 * by_rows, (k_nt64<4, 2, 2>), grid, dim3(512), e->tune_pad64, h2);
-      return 0;
+      LAUNCH("k_nt64<4,2,2>.layer1", 2.0 * nets * (double)M * HID * K, by_w * (K + 1) + 4.0 * ngrp * (double)M * K + by_rows,
+             (k_nt64<4, 2, 2>), grid1, dim3(512), g);
     }
     // second layer with the LayerNorm + ReLU of the first as its prologue (k_nt64_ln): no row kernel in between
     NtArgs h2{};
@@ -619,7 +595,7 @@ static int enqueue_trunk(sactd3_engine* e, hipStream_t s, int ldx, int K, int M,
     {
       double st = 0.0;   // rows written besides the output: h and xhat where the caller keeps them
       for (int i = 0; i < ngrp; ++i) st += ((grp[i].xh ? 1.0 : 0.0) + (grp[i].h ? 1.0 : 0.0)) / ngrp;
-      LAUNCH_DYN("k_nt64_ln<4,2,2>.layer2", 2.0 * nets * (double)M * HID * HID, by_w * (HID + 3) + by_rows * (2.0 + st), (k_nt64_ln<4, 2, 2>), grid, dim3(512), e->tune_pad64, h2);
+      LAUNCH("k_nt64_ln<4,2,2>.layer2", 2.0 * nets * (double)M * HID * HID, by_w * (HID + 3) + by_rows * (2.0 + st), (k_nt64_ln<4, 2, 2>), grid, dim3(512), h2);
     }
     return 0;
   }
@@ -653,7 +629,7 @@ static int enqueue_trunk(sactd3_engine* e, hipStream_t s, int ldx, int K, int M,
   h.ld_in = HID; h.in_ns = (long)M * HID;
   if (tk.alpha) { h.alpha_block = 1; h.al = *tk.alpha; }   // (never together with noise blocks: those read the counter it ticks)
   set_noise(h);            // (as in the fused form) the following tail's draws as extra blocks of the layer-2 launch
-  if (M >= BIG_BATCH && M == e->B && !(e->tune_rows4 & 256)) {   // large batch: the 32 x 32 LDS-tiled form with the LayerNorm prologue
+  if (M >= BIG_BATCH && M == e->B) {   // large batch: the 32 x 32 LDS-tiled form with the LayerNorm prologue
     h.ln_pro = e->cfg.layer_norm ? 1 : 0;
     h.nt_blocks = ((M + 31) / 32) * (HID / 32) * nets;
     int nzb = 0;
@@ -728,7 +704,6 @@ static bool opening_trunk_carries_alpha(const sactd3_engine* e);
 // Does the actor trunk that opens a fused iteration read its rows from the ring itself, with the gather into the batch slot riding in
 // the same launch?  Narrow observations below the large-batch threshold (fused k_nt), and wide ones at large batch (k_nt64<2,2,1>).
 static bool opening_trunk_gathers(const sactd3_engine* e) {
-  if (e->tune_rows4 & 32) return e->o <= 64 && e->B < BIG_BATCH;
   return (e->o <= 64 && e->B < BIG_BATCH) || (e->o > 64 && e->B >= BIG_BATCH && opening_trunk_carries_alpha(e));
 }
 static bool opening_trunk_carries_alpha(const sactd3_engine* e) {
@@ -764,7 +739,7 @@ static int enqueue_update_qnets(sactd3_engine* e, hipStream_t s, bool fused_samp
     const bool in_kernel_gather = fused_sample && opening_trunk_gathers(e);
     // the FIRST actor update's pi(s) pass rides along (see enqueue_step): in the fused-first-layer launches of narrow observations,
     // and as a second group of the layer-by-layer launches of wide ones at large batch (Humanoid: two nodes fewer per actor iteration)
-    const bool wide_merge = with_policy && fused_sample && e->o > 64 && B >= BIG_BATCH && !(e->tune_rows4 & 16);
+    const bool wide_merge = with_policy && fused_sample && e->o > 64 && B >= BIG_BATCH;
     const bool merge_policy = with_policy && ((in_kernel_gather && e->o <= 64) || wide_merge);
     e->node_role = fused_sample ? (merge_policy ? "critic/next-action+sample & actor0/policy" : "critic/next-action+sample") : "critic/next-action";
     // (layer-by-layer launches materialise z1: the target-action group borrows the target critics' z1 slab, idle until the next launch)
@@ -836,24 +811,22 @@ static int enqueue_update_qnets(sactd3_engine* e, hipStream_t s, bool fused_samp
     RCCHK(enqueue_trunk(e, s, e->ldc, e->o + e->a, B, e->Lc, e->Lc.size, 2, 2, g, tk));
   }
   e->node_role = "critic/loss+backward";
-  bool fused_tail_nn = false, fold_ln1 = false;
+  const bool fused_tail_nn = B < BIG_BATCH;   // the tail AND dh1 = dz2 W2 in one launch (k_ctail_nn)
+  const bool fold_ln1 = fused_tail_nn;       // ... then with layer 1's LayerNorm backward inside the weight-gradient launch (TnProb::fold)
   {
     CriticTail t{};
     t.z2t = e->t_z2; t.z2 = e->c_z2; t.PT = e->Tc; t.P = e->Pc; t.p_ns = e->Lc.size; t.L = e->Lc;
     t.rew = S.rew; t.done = S.done; t.logp_next = S.logp_n; t.log_alpha = e->la;
     t.B = B; t.ln = ln; t.sac = !td3; t.bcq = c.bcq_style_targ_mix; t.gamma = c.gamma;
     t.qt = e->qt; t.y = e->y; t.q = e->q; t.dz2 = e->c_dz2; t.part = e->part; t.part_s = e->part_s; t.pstride = e->nblk4;
-    fused_tail_nn = B < BIG_BATCH && !(e->tune_rows4 & 2048);
-    if (fused_tail_nn) {   // the tail AND dh1 = dz2 W2 in one launch (k_ctail_nn): 16-row blocks x 32-column tiles
+    if (fused_tail_nn) {   // 16-row blocks x 32-column tiles
       CtailNn f{};
       f.c = t; f.c.pstride = e->nblk4; f.Wt = e->Pc + e->Lc.W2; f.ldw = HID; f.dX = e->c_dh1;
-      fold_ln1 = !(e->tune_rows4 & 4096);   // layer 1's LayerNorm backward inside the weight-gradient launch (TnProb::fold)
       f.f.fold = fold_ln1; f.f.ln = ln; f.f.h1 = e->c_h1; f.f.xh1 = e->c_xh1; f.f.g1_off = e->Lc.g1; f.f.ps = e->c_ps; f.f.gsnap = e->c_ps + 2L * B * PS_W;
-      f.xr = pick_xr(e, e->nblk, HID / 32, 4.0 * 3 * B * HID, 4.0 * HID * HID);
+      f.xr = pick_xr(e->nblk, HID / 32, 4.0 * 3 * B * HID, 4.0 * HID * HID);
       LAUNCH("k_ctail_nn<2>", 2.0 * 4 * B * (double)HID + 2.0 * 2 * (double)B * HID * HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B) + 4.0 * 2 * ((double)HID * HID + (double)B * HID),
              k_ctail_nn<2>, dim3((unsigned)(e->nblk * (HID / 32)), 1, 2), dim3(256), f);
-    } else if (e->tune_rows4 & 1) LAUNCH("k_critic_tail<4>", 2.0 * 4 * B * (double)HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B), k_critic_tail<4>, dim3(e->nblk4, 2), dim3(64), t);
-    else LAUNCH("k_critic_tail<16>", 2.0 * 4 * B * (double)HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B), k_critic_tail<16>, dim3(e->nblk, 2), dim3(256), t);
+    } else LAUNCH("k_critic_tail<16>", 2.0 * 4 * B * (double)HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B), k_critic_tail<16>, dim3(e->nblk, 2), dim3(256), t);
   }
   if (!fused_tail_nn) {  // dh1 = dz2 W2
     NnArgs g{};
@@ -866,27 +839,24 @@ static int enqueue_update_qnets(sactd3_engine* e, hipStream_t s, bool fused_samp
     l.dh = e->c_dh1; l.xh = e->c_xh1; l.h = e->c_h1; l.rstd = e->c_rs1;
     l.gamma = e->Pc + e->Lc.g1; l.p_ns = e->Lc.size; l.B = B; l.ln = ln; l.want_part = ln;
     l.dz = e->c_dz1; l.part = e->part; l.pstride = e->nblk4;
-    if (e->tune_rows4 & 2) LAUNCH("k_ln_bwd<4>", 0.0, 4.0 * 2 * (4.0 * BH + B + HID), k_ln_bwd<4>, dim3(e->nblk4, 2), dim3(64), l);
-    else LAUNCH("k_ln_bwd<16>", 0.0, 4.0 * 2 * (4.0 * BH + B + HID), k_ln_bwd<16>, dim3(e->nblk, 2), dim3(256), l);
+    LAUNCH("k_ln_bwd<16>", 0.0, 4.0 * 2 * (4.0 * BH + B + HID), k_ln_bwd<16>, dim3(e->nblk, 2), dim3(256), l);
   }
   {  // every critic gradient + the Adam step (+ Polyak) in one launch:
      //   dW2 = dz2^T h1, db2, dgamma2, dbeta2, dWhead, dbhead ; dW1 = dz1^T [s|a], db1, dgamma1, dbeta1
     TnArgs g{};
     g.nprob = 2; g.M = B; g.G = e->Gc; g.g_ns = e->Lc.size;
-    const int i2 = 0, i1 = fold_ln1 ? 2 : 1;           // folded: [W2 rows 0 .. 127][layer 1][W2 rows 128 .. 255] (tn_rows)
+    const int i2 = 0, i1 = fold_ln1 ? 2 : 1;           // folded: [W2 columns 0 .. 127][layer 1][W2 columns 128 .. 255] (tn_cols)
     g.pr[i2] = tn_prob(e->c_dz2, HID, BH, HID, e->c_h1, HID, BH, HID, e->Lc.W2, HID, e->Lc.b2);
-    const int nb_tail = (!fused_tail_nn && (e->tune_rows4 & 1)) ? e->nblk4 : e->nblk, nb_ln = (e->tune_rows4 & 2) ? e->nblk4 : e->nblk;   // row blocks that wrote the partials
-    if (ln) { tn_fin(g.pr[i2], 0, e->Lc.g2, nb_tail); tn_fin(g.pr[i2], 1, e->Lc.be2, nb_tail); }
-    tn_fin(g.pr[i2], 2, e->Lc.Wh, nb_tail); g.pr[i2].fin_s_off = e->Lc.bh; g.pr[i2].fin_s_nblk = nb_tail;
+    if (ln) { tn_fin(g.pr[i2], 0, e->Lc.g2, e->nblk); tn_fin(g.pr[i2], 1, e->Lc.be2, e->nblk); }
+    tn_fin(g.pr[i2], 2, e->Lc.Wh, e->nblk); g.pr[i2].fin_s_off = e->Lc.bh; g.pr[i2].fin_s_nblk = e->nblk;
     g.pr[i1] = tn_prob(fold_ln1 ? e->c_dh1 : e->c_dz1, HID, BH, HID, S.X, e->ldc, 0, e->o + e->a, e->Lc.W1, e->Lc.ld1, e->Lc.b1);
     if (fold_ln1) {
       TnProb& q = g.pr[i1];
       q.fold = 1; q.f_ln = ln; q.f_g_off = e->Lc.g1; q.f_be_off = e->Lc.be1; q.f_xh = e->c_xh1; q.f_rstd = e->c_rs1; q.f_ps = e->c_ps; q.f_dz = e->c_dz1; q.f_g = e->c_ps + 2L * B * PS_W;
-    } else if (ln) { tn_fin(g.pr[i1], 3, e->Lc.g1, nb_ln); tn_fin(g.pr[i1], 4, e->Lc.be1, nb_ln); }
+    } else if (ln) { tn_fin(g.pr[i1], 3, e->Lc.g1, e->nblk); tn_fin(g.pr[i1], 4, e->Lc.be1, e->nblk); }
     if (fold_ln1) {
       g.nprob = 3;
-      if (e->tune_rows4 & 262144) { g.pr[1] = tn_rows(g.pr[0], HID / 2, HID / 2); g.pr[0] = tn_rows(g.pr[0], 0, HID / 2); }
-      else { g.pr[1] = tn_cols(g.pr[0], HID / 2, HID / 2); g.pr[0] = tn_cols(g.pr[0], 0, HID / 2); g.pr[0].xr_force = g.pr[1].xr_force = 8; }
+      g.pr[1] = tn_cols(g.pr[0], HID / 2, HID / 2); g.pr[0] = tn_cols(g.pr[0], 0, HID / 2); g.pr[0].xr_force = g.pr[1].xr_force = 8;
       std::swap(g.pr[1], g.pr[2]);
     }
     g.part = e->part; g.pstride = e->nblk4; g.part_s = e->part_s;
@@ -928,7 +898,7 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
   const int sb_a = SACTD3_SITE_ACTOR0 + (j & 1), sb_l = SACTD3_SITE_ALPHA0 + (j & 1);
   const bool clip = c.clip_norm > 0.f;
   const float* SX = e->bs[slot].X;          // the observations of the batch this iteration trains on
-  const bool small_head = e->nh <= 8 && e->a <= 8 && !(e->tune_rows4 & 4);      // single-wave 4-row head backward (k_actor_head_bwd_s)
+  const bool small_head = e->nh <= 8 && e->a <= 8;      // single-wave 4-row head backward (k_actor_head_bwd_s)
   e->node_role = (j & 1) ? "actor1/policy" : "actor0/policy";
   if (!head_done) {  // a_pi, logp = pi(s) with stores for the backward pass
     const TrunkGrp g{SX, e->Pa, e->a_z1, e->a_z2, e->a_xh1, e->a_h1, e->a_rs1};
@@ -949,9 +919,9 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
     RCCHK(enqueue_trunk(e, s, e->ldc, e->o + e->a, B, e->Lc, e->Lc.size, 1, nq, &g, tk));
   }
   e->node_role = (j & 1) ? "actor1/loss+backward" : "actor0/loss+backward";
-  const bool fused_qtail_nn = B < BIG_BATCH && !(e->tune_rows4 & 2048);
+  const bool fused_qtail_nn = B < BIG_BATCH;
   // dQ/da finished inside the two fused launches around it (QaFold): narrow heads, ac_dim <= 7
-  const bool qa_fold = fused_qtail_nn && small_head && e->a <= 7 && !(e->tune_rows4 & 16384);    // (small_head: k_headbwd_nn is the consumer)
+  const bool qa_fold = fused_qtail_nn && small_head && e->a <= 7;    // (small_head: k_headbwd_nn is the consumer)
   const int qa_ntile = HID / (nq == 2 ? 32 : 16), qa_pqw = e->a <= 3 ? 8 : 16;
   {
     ActorQTail t{};
@@ -966,10 +936,10 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
       }
       const double fl = 2.0 * nq * B * (double)HID + 2.0 * nq * (double)B * HID * HID, by = 4.0 * nq * (2.0 * BH + 4.0 * HID + 2.0 * B) + 4.0 * nq * ((double)HID * HID + (double)B * HID);
       if (nq == 2) {
-        f.xr = pick_xr(e, e->nblk, HID / 32, 4.0 * 2 * B * HID, 4.0 * HID * HID);
+        f.xr = pick_xr(e->nblk, HID / 32, 4.0 * 2 * B * HID, 4.0 * HID * HID);
         LAUNCH("k_qtail_nn<2>", fl, by, k_qtail_nn<2>, dim3((unsigned)(e->nblk * (HID / 32)), 1, 2), dim3(256), f);
       } else {
-        f.xr = pick_xr(e, e->nblk, HID / 16, 4.0 * B * HID, 4.0 * HID * HID);
+        f.xr = pick_xr(e->nblk, HID / 16, 4.0 * B * HID, 4.0 * HID * HID);
         LAUNCH("k_qtail_nn<1>", fl, by, k_qtail_nn<1>, dim3((unsigned)(e->nblk * (HID / 16)), 1, 1), dim3(256), f);
       }
     } else LAUNCH("k_actorq_tail<4>", 2.0 * nq * B * (double)HID, 4.0 * nq * (2.0 * BH + 4.0 * HID + 2.0 * B), k_actorq_tail<4>, dim3(e->nblk4), dim3(64), t);
@@ -990,24 +960,23 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
     LAUNCH("k_ln_bwd<16>.dQ/da", 2.0 * nq * B * (double)HID * e->a, 4.0 * nq * (4.0 * BH + B + HID + (double)HID * e->a + (double)B * e->a),
            k_ln_bwd<16>, dim3(e->nblk, nq), dim3(256), l);
   }
-  bool fused_head_nn = false, fold_ln1 = false;
+  const bool fused_head_nn = small_head && B < BIG_BATCH;   // the head backward AND dh1 = dz2 W2 in one launch (k_headbwd_nn)
+  const bool fold_ln1 = fused_head_nn;                     // as the critics' (enqueue_update_qnets)
   {
     ActorHeadBwd h{};
     h.dA = e->dA; h.dA_ns = (long)B * e->a4; h.ldA = e->a4; h.nq = nq; h.tg = e->a_tg; h.a4 = e->a4; h.eps = e->eps[sb_a];
     h.log_alpha = e->la; h.scale = e->scale; h.P = e->Pa; h.L = e->La; h.xh2 = e->a_xh2; h.rstd2 = e->a_rs2; h.h2 = e->a_h2;
     h.B = B; h.a = e->a; h.ln = ln; h.sac = !td3; h.du = e->a_du; h.ldu = e->ldu; h.dz2 = e->a_dz2;
     h.part = e->part;
-    fused_head_nn = small_head && B < BIG_BATCH && !(e->tune_rows4 & 2048);
-    if (fused_head_nn) {   // the head backward AND dh1 = dz2 W2 in one launch (k_headbwd_nn): column partials per 16-row block
+    if (fused_head_nn) {   // column partials per 16-row block
       HeadBwdNn f{};
       f.c = h; f.Wt = e->Pa + e->La.W2; f.ldw = HID; f.dX = e->a_dh1;
       if (qa_fold) {
         f.qa.on = 1; f.qa.ln = ln; f.qa.a = e->a; f.qa.pqw = qa_pqw; f.qa.ntile = qa_ntile; f.qa.ps = e->qa_ps; f.qa.S = e->qa_S;
         f.qa.rstd = e->c_rs1; f.qa.dA = e->dA;
       }
-      fold_ln1 = !(e->tune_rows4 & 4096);   // as the critics' (enqueue_update_qnets)
       f.f.fold = fold_ln1; f.f.ln = ln; f.f.h1 = e->a_h1; f.f.xh1 = e->a_xh1; f.f.g1_off = e->La.g1; f.f.ps = e->a_ps; f.f.gsnap = e->a_ps + (long)B * PS_W;
-      f.xr = pick_xr(e, e->nblk, HID / 16, 4.0 * 2 * B * HID, 4.0 * HID * HID);
+      f.xr = pick_xr(e->nblk, HID / 16, 4.0 * 2 * B * HID, 4.0 * HID * HID);
       LAUNCH("k_headbwd_nn", 2.0 * B * (double)HID * e->nh + 2.0 * (double)B * HID * HID,
              4.0 * (3.0 * BH + (double)e->nh * HID + (double)B * (nq * e->a + 4 * e->a + e->nh)) + 4.0 * ((double)HID * HID + (double)B * HID),
              k_headbwd_nn, dim3((unsigned)(e->nblk * (HID / 16))), dim3(256), f);
@@ -1361,28 +1330,6 @@ static int create_impl(sactd3_engine* e, const float* min_ac, const float* max_a
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return e->fail(SACTD3_ENODEV, "device is not gfx950 (this library carries gfx950 code objects only)");
   e->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  // kernel-selection defaults (what the shipped library always runs): 4-row single-wave k_critic_tail / k_ln_bwd below B = 1024
-  // (-1.0 us per Hopper iteration, +-0 at Humanoid); the split-M weight-gradient route from half a chip's worth of 64 x 32 tiles
-  e->tune_rows4 = c.batch_size < BIG_BATCH ? 3 : 0;
-  e->tune_tn64_min = e->num_cus / 2;
-#ifdef SACTD3_TUNING
-  // A/B switches of the tuning builds ONLY (`make tune` -> libsactd3_hip_tune.so, used by tools/ab_*.py / tools/ab_iter.sh through
-  // SACTD3_LIBRARY): the shipped library reads no environment variable at all.  Read once here, never on a launch path.
-  //   SACTD3_KS 1|2|4 / SACTD3_NT 1 / SACTD3_TN_KT 1|2: block shapes of k_nt / k_tn;  SACTD3_PAD64: dynamic-LDS pad of k_nt64;
-  //   SACTD3_NN16 1: k_nn instead of k_nn64;  SACTD3_XR -1|0|1|2|4|8: XCD tile placement (-1 = least-fetch split per launch);
-  //   SACTD3_TN64_MIN: tiles x nets from which the split-M route is taken;
-  //   SACTD3_ROWS4: bit mask.  1 / 2: the 4-row single-wave k_critic_tail / k_ln_bwd.  The other bits turn a default OFF:
-  //   4 k_actor_head_bwd_s, 16 the policy-pass merge for wide observations, 32 the in-kernel replay gather of the wide opening trunk,
-  //   128 k_nt64_ln in the 4-net trunk (-> k_ln_fwd + k_nt64), 256 k_nt64_ln<2,2,1> for the 1- / 2-net second layers (-> k_nt).
-  if (const char* f = getenv("SACTD3_KS")) { const int v = atoi(f); if (v == 1 || v == 2 || v == 4) e->tune_ks = v; }
-  if (const char* f = getenv("SACTD3_NT")) { if (atoi(f) == 1) e->tune_nt = 1; }
-  if (const char* f = getenv("SACTD3_PAD64")) e->tune_pad64 = atoi(f);
-  if (const char* f = getenv("SACTD3_NN16")) e->tune_nn16 = atoi(f);
-  if (const char* f = getenv("SACTD3_XR")) e->tune_xr = atoi(f);
-  if (const char* f = getenv("SACTD3_ROWS4")) e->tune_rows4 = atoi(f);
-  if (const char* f = getenv("SACTD3_TN64_MIN")) e->tune_tn64_min = atoi(f);
-  if (const char* f = getenv("SACTD3_TN_KT")) { const int v = atoi(f); if (v == 1 || v == 2) e->tune_tn_kt = v; }
-#endif
   HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
 
   e->o = c.ob_dim; e->a = c.ac_dim; e->B = c.batch_size;
@@ -1859,10 +1806,7 @@ int sactd3_step(sactd3_engine* e, int do_actor) {
 // updates, and an opening trunk that reads ring rows itself (narrow observations below the large-batch threshold, wide ones at large batch).
 // does the actor's weight-gradient launch take the split-M route (k_tn64 + k_adam_red: no T2 / T3 support)?  (launch_tn's rule)
 static bool actor_dw_is_tiled64(const sactd3_engine* e) {
-  if (e->B < BIG_BATCH || !e->Gp || e->tune_tn_kt) return false;
-  const int tiles = ((e->nh + TN64_N - 1) / TN64_N) * ((HID + TN64_K - 1) / TN64_K) + ((HID + TN64_N - 1) / TN64_N) * ((HID + TN64_K - 1) / TN64_K)
-                    + ((HID + TN64_N - 1) / TN64_N) * ((e->La.ld1 + TN64_K - 1) / TN64_K);
-  return tiles >= e->tune_tn64_min;
+  return tn_is_tiled64(e, e->B, tn64_tiles(e->nh, HID) + tn64_tiles(HID, HID) + tn64_tiles(HID, e->La.ld1));   // head, layer 2, layer 1
 }
 static bool period_is_pipelined(const sactd3_engine* e) {
   const sactd3_config& c = e->cfg;

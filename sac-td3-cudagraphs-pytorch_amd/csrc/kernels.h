@@ -10,7 +10,7 @@
 //   k_nt / k_nt_wide  Y = pro(A) W^T + b on v_mfma_f32_16x16x4_f32; pro = LayerNorm+ReLU of the producing layer applied to
 //                     the A fragments in registers; optionally the FIRST layer (x W1^T + b1) is computed in the same kernel
 //                     straight into those fragments (narrow inputs); W tiles parked in LDS, block shape picked per launch
-//   k_nt64 / k_ln_fwd large-batch form of the hidden layers: 64 x 64 LDS-tiled GEMM -> LayerNorm row kernel -> tiled GEMM
+//   k_nt64 / k_nt64_ln  large-batch form of the hidden layers: 64 x 64 LDS-tiled GEMM -> tiled GEMM with LayerNorm + ReLU (ln_fwd) as prologue
 //   k_nn / k_nn64     dX = dY W                     (16 x 16 tile per block, reduction split over the 4 waves; B >= 1024: LDS-tiled)
 //   k_tn              dW = dY^T X for every weight of an update in one launch (+ bias gradient) with the Adam step and the Polyak
 //                     update in the tile's epilogue; extra blocks of the launch finalise the LayerNorm-affine / head gradients
@@ -1064,11 +1064,12 @@ __global__ __launch_bounds__(64 * WM * WN) void k_nt64(NtArgs p) {       // Y[M,
   STAMP(2);
 }
 
-// Second hidden layer of the large-batch multi-net trunks WITH the first layer's LayerNorm + ReLU as its prologue (the k_ln_fwd row
-// kernel between the two tiled GEMMs, one graph node and 10 MB of traffic, folded in).  K = 256 = one row per 16 threads in exactly
+// Second hidden layer of the large-batch multi-net trunks WITH the first layer's LayerNorm + ReLU as its prologue (a row kernel
+// between the two tiled GEMMs would be one more graph node and 10 MB of traffic).  K = 256 = one row per 16 threads in exactly
 // k_nt64's staging map (thread (row = t >> 4 + SR u, sub = t & 15) owns columns 4 sub + 64 q -- the Row16 layout), so a block loads
-// its TM rows ONCE, up front, normalises them in registers with the same two DPP row reductions as k_ln_fwd (bit-identical
-// statistics), and parks chunk c of the activated rows from registers while the loop streams only W.  The column-tile-0 block of
+// its TM rows ONCE, up front, normalises them in registers with ln_fwd (mean, then the variance of the centred row, each one DPP
+// reduction over the row's 16 threads: the statistics of every other row kernel, bit for bit), and parks chunk c of the activated
+// rows from registers while the loop streams only W.  The column-tile-0 block of
 // every row block stores h / xhat / rstd where the backward pass wants them.
 template <int WM, int WN, int TT>
 __global__ __launch_bounds__(64 * WM * WN) void k_nt64_ln(NtArgs p) {       // Y[M,N] = relu(LN(Z))[M,256] W[N,256]^T + bias
@@ -1113,7 +1114,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_nt64_ln(NtArgs p) {       // Y
     for (int u = 0; u < RW; ++u) rw[u] = ld4(wp[u] + c * KC64 + sc);
   };
   fetch(0);
-  // ---- LayerNorm + ReLU of this thread's rows (k_ln_fwd's arithmetic), stores by the column-tile-0 block
+  // ---- LayerNorm + ReLU of this thread's rows (h = relu(xhat gamma + beta), ln_fwd), stores by the column-tile-0 block
   Row16 h[RA];
 #pragma unroll
   for (int u = 0; u < RA; ++u) {
@@ -1176,32 +1177,6 @@ __global__ __launch_bounds__(64 * WM * WN) void k_nt64_ln(NtArgs p) {       // Y
       if (row < p.M) y[(long)row * p.ldy + col] = acc[tt][i] + bias[tt];
     }
   }
-}
-
-struct LnFwd {               // h = relu(LN(z) * gamma + beta) per row; stores h, xhat, rstd   (nets on blockIdx.y)
-  const float* P[2]; int npg; int oG, oBe; long p_ns;
-  float* h[2]; float* xh[2]; float* rstd[2];     // per group; xh / rstd may be null
-  const float* zin[2];                           // per group input rows [npg][B][HID]
-  int B, ln;
-};
-__global__ __launch_bounds__(256) void k_ln_fwd(LnFwd p) {
-  const int t = threadIdx.x, row = t >> 4, sub = t & 15, net = blockIdx.y;
-  const int grp = net / p.npg, ni = net - grp * p.npg;
-  const int b = blockIdx.x * 16 + row;
-  if (b >= p.B) return;
-  const long ro = ((long)ni * p.B + b) * HID;
-  const float* Pn = p.P[grp] + ni * p.p_ns;
-  const Row16 z = row_ld(p.zin[grp] + ro, sub);
-  Row16 g = row_ld(Pn + (p.ln ? p.oG : 0), sub), be = row_ld(Pn + (p.ln ? p.oBe : 0), sub);   // unconditional: one batch of requests
-  row_pin(g); row_pin(be);
-  Row16 xh, y, hh;
-  float rstd;
-  ln_fwd(z, g, be, p.ln, xh, y, rstd);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) hh.v[q] = relu4(y.v[q]);
-  row_st(p.h[grp] + ro, sub, hh);
-  if (p.xh[grp]) row_st(p.xh[grp] + ro, sub, xh);
-  if (p.rstd[grp] && sub == 0) p.rstd[grp][(long)ni * p.B + b] = rstd;
 }
 
 struct NnArgs {              // dX[M,Kout] = dY[M,256] * W[256, k_off : k_off+Kout] ; block = one 16 x 16 tile, n split over waves

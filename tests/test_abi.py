@@ -119,16 +119,20 @@ def test_no_serialised_operand_loads(engine_asm):
 
 
 def test_shipped_library_reads_no_environment_switches():
-    """include/sactd3.h: every behaviour of libsactd3_hip.so is a field of sactd3_config; the kernel-selection A/B switches
-    (SACTD3_KS, SACTD3_ROWS4, ...) and the any-arch override exist only in the tuning build (-DSACTD3_TUNING)."""
+    """include/sactd3.h: every behaviour of libsactd3_hip.so is a field of sactd3_config.  The kernel-selection A/B switches
+    (SACTD3_KS, SACTD3_ROWS4, ...) of the former tuning build are gone: neither the binary nor any file of csrc/ knows them."""
     import sac_td3_cudagraphs_pytorch_amd as pkg
     blob = open(os.path.join(os.path.dirname(pkg.__file__), "libsactd3_hip.so"), "rb").read()
     for name in (b"SACTD3_KS", b"SACTD3_NT", b"SACTD3_ROWS4", b"SACTD3_XR", b"SACTD3_TN64_MIN", b"SACTD3_TN_KT", b"SACTD3_PAD64", b"SACTD3_NN16",
                  b"SACTD3_ALLOW_ANY_ARCH"):
         assert name not in blob, name
-    src = open(os.path.join(ROOT, "sac-td3-cudagraphs-pytorch_amd", "csrc", "engine.hip")).read()
-    outside = re.sub(r"#ifdef SACTD3_TUNING.*?#endif", "", src, flags=re.S)
-    assert "getenv" not in outside
+    csrc = os.path.join(ROOT, "sac-td3-cudagraphs-pytorch_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    assert "engine.hip" in files and "kernels.h" in files
+    for f in files:
+        src = open(os.path.join(csrc, f), errors="replace").read()
+        for word in ("getenv", "SACTD3_TUNING", "tune_"):
+            assert word not in src, (f, word)
 
 
 def test_fetch_width_table_matches_the_code_objects(engine_asm):
