@@ -90,8 +90,6 @@ struct sactd3_engine {
   int o = 0, a = 0, B = 0, ldc = 0, ldo = 0, a4 = 0, nh = 0, ldu = 0, rec_f = 0, rec4 = 0, cx = 0, cn = 0;
   int nq_actor = 2;            // critics evaluated in the actor update (SAC 2, TD3 1)
   int nblk = 0, nblk4 = 0;     // row-kernel blocks for B rows: 16 rows each (MFMA-using tails) / 4 rows each (plain row kernels)
-  AlphaArgs pending_alpha{}; bool alpha_pending = false;   // a temperature step deferred into the next update's trunk launch (enqueue time only)
-  bool alpha_tick_owed = false;   // ... deferred across an ITERATION boundary (period graphs): its counter tick is made up by the next critic update
   int maxn = 0;                // rows accepted by predict
   int num_cus = 256;
   int stage_rows = 0;
@@ -126,10 +124,10 @@ struct sactd3_engine {
   // -1: not so -- the next period starts with the opening graph.  Every state-changing ABI call resets it (CHAIN_BREAK).
   int chain_ready = -1;
   // Stores that only inspection reads (debug_read: the gradient arenas, the folded launches' dz1) are left out of the period and cut-short
-  // period sequences when the optimiser step is fused and nothing clips (lean_stores, set while enqueue_period / enqueue_prefix run:
+  // period sequences when the optimiser step is fused and nothing clips (EnqCtx::lean_stores, set by enqueue_period:
   // launch_tn).  grads_stale[0 critics, 1 actor]: such a sequence ran since that family's arenas were last written in full --
   // sactd3_debug_read refuses the family's names (grad_*, *_dz1) until an API-path update or a sactd3_step rewrites them.
-  bool lean_stores = false, grads_stale[2] = {false, false};
+  bool grads_stale[2] = {false, false};
   float *c_z1 = nullptr, *c_xh1 = nullptr, *c_h1 = nullptr, *c_rs1 = nullptr, *c_z2 = nullptr, *c_dz2 = nullptr, *c_dh1 = nullptr, *c_dz1 = nullptr;
   float *t_z1 = nullptr, *t_z2 = nullptr, *q = nullptr, *qt = nullptr, *y = nullptr, *q_pi = nullptr, *dA = nullptr;
   float* s_h1 = nullptr;         // large-batch path: layer-1 activations of nets whose caller keeps no copy ([4][B][256])
@@ -153,12 +151,6 @@ struct sactd3_engine {
   bool actor_dirty = true, act_inflight = false, act_ordered = false, act_spin = false;
   int act_n = 0, act_want = 0;
   int64_t act_stats[4] = {};                    // sactd3_acting_stats
-  // node registry of the enqueue_* sequences (sactd3_time_nodes): every kernel launch of the path goes through
-  // node_on(), which numbers it; with node_only >= 0 only that launch is issued (the others are skipped), with
-  // node_log set the launch's name and algorithmic FLOPs / bytes are recorded.
-  int node_seq = 0, node_only = -1;
-  const char* node_role = "";                 // which part of the iteration is being enqueued (names the nodes)
-  std::vector<NodeInfo>* node_log = nullptr;
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -207,28 +199,47 @@ static int halloc(sactd3_engine* e, T** p, size_t count) {
 }
 
 // ------------------------------------------------------------------------------------------------ launches
-// Every kernel launch of the update path is numbered here (see sactd3_engine::node_seq).  flops = 2 x MACs of the GEMMs
+// What exists only while ONE sequence of launches is enqueued (one graph capture, or one pass of its eager form): created where the
+// sequence starts, handed down to every enqueue_* / launch_* function, gone when it ends -- a failed enqueue leaves nothing behind.
+struct EnqCtx {
+  sactd3_engine* e; hipStream_t s;
+  const char* role = "";          // which part of the iteration is being enqueued (names the nodes)
+  bool lean_stores = false;       // leave out the stores that only inspection reads (see sactd3_engine::grads_stale)
+  // a temperature step deferred into the next update's trunk launch ...
+  AlphaArgs alpha{}; bool alpha_pending = false;
+  bool alpha_tick_owed = false;   // ... across an ITERATION boundary (period graphs): its counter tick is owed until the next critic update's last kernel
+  // node registry (sactd3_time_nodes, see node_on)
+  int node_seq = 0, node_only = -1;
+  std::vector<NodeInfo>* node_log = nullptr;
+};
+// where every sequence ends: nothing deferred may be left over (it would never run)
+static int enqueue_end(EnqCtx& x, int rc) {
+  return (rc == 0 && (x.alpha_pending || x.alpha_tick_owed)) ? x.e->fail(SACTD3_ESTATE, "enqueue: a deferred temperature step was left over") : rc;
+}
+// Every kernel launch of the update path is numbered here (EnqCtx::node_seq); with node_only >= 0 only that launch is issued (the
+// others are skipped), with node_log set the launch's name and algorithmic FLOPs / bytes are recorded.  flops = 2 x MACs of the GEMMs
 // the launch contains (SURVEY.md 8d counts GEMM FLOPs only); bytes = the operands it has to read and the results it has
 // to write, each counted once (what a perfect cache hierarchy would move).
 // `name` = "<kernel instance as rocprofv3 prints it, without blanks>[.detail]"; logged as "instance:role[/detail]" with
 // the launch's total thread count (what rocprofv3 calls Grid_Size), so that a profile row can be matched to a node.
-static inline bool node_on(sactd3_engine* e, const char* name, double flops, double bytes, dim3 grid, dim3 block) {
-  if (e->node_only < 0 && !e->node_log) return true;      // the normal case: not being timed
-  const int k = e->node_seq++;
-  if (e->node_log) {
+static inline bool node_on(EnqCtx& x, const char* name, double flops, double bytes, dim3 grid, dim3 block) {
+  if (x.node_only < 0 && !x.node_log) return true;      // the normal case: not being timed
+  const int k = x.node_seq++;
+  if (x.node_log) {
     std::string n(name), detail;
     const size_t dot = n.find('.');
     if (dot != std::string::npos) { detail = "/" + n.substr(dot + 1); n.resize(dot); }
-    e->node_log->push_back(NodeInfo{n + ":" + e->node_role + detail, flops, bytes,
+    x.node_log->push_back(NodeInfo{n + ":" + x.role + detail, flops, bytes,
                                     (long)grid.x * grid.y * grid.z * block.x * block.y * block.z});
   }
-  return e->node_only < 0 || e->node_only == k;
+  return x.node_only < 0 || x.node_only == k;
 }
 #define LAUNCH(name, flops, bytes, kernel, grid, block, ...)                 \
   do {                                                                      \
-    if (node_on(e, name, flops, bytes, grid, block)) {                      \
-      hipLaunchKernelGGL(kernel, grid, block, 0, s, __VA_ARGS__);           \
-      HIPCHK(hipGetLastError());                                            \
+    if (node_on(x, name, flops, bytes, grid, block)) {                      \
+      hipLaunchKernelGGL(kernel, grid, block, 0, x.s, __VA_ARGS__);         \
+      const hipError_t _he = hipGetLastError();                             \
+      if (_he != hipSuccess) return x.e->fail(SACTD3_EHIP, "hipGetLastError()", _he); \
     }                                                                       \
   } while (0)
 
@@ -294,7 +305,9 @@ static int pick_xr(int R, int C, double A, double W) {
 }
 // pro == 0: the generic-K form (unfused first layer).  Otherwise K == 256 and the block shape (16 / 32 / 64 rows x 16
 // columns) is chosen so that the launch has about one block per CU.
-static int launch_nt(sactd3_engine* e, hipStream_t s, const char* name, int pro, bool fuse1, const NtArgs& g, int nets, int force_ks = 0) {
+static int launch_nt(EnqCtx& x, const char* name, int pro, bool fuse1, const NtArgs& g, int nets, int force_ks = 0) {
+  sactd3_engine* e = x.e;
+  const hipStream_t s = x.s;
   const int tiles_m = (g.M + 15) / 16, tiles_n = (g.N + 15) / 16;
   // algorithmic work: the (fused) first layer + this layer; operands: input rows, the weight blocks, the output (+ stored activations)
   const double fl = 2.0 * nets * (double)g.M * g.N * (g.K + (fuse1 ? g.K1 : 0));
@@ -304,7 +317,7 @@ static int launch_nt(sactd3_engine* e, hipStream_t s, const char* name, int pro,
   if (g.gblocks) by += (g.gblocks / std::max(g.gb_each, 1)) * 8.0 * (double)g.ga[0].B * 4 * (g.ga[0].cx + g.ga[0].cn + 1);
   if (pro == 0) {
     const dim3 grid((unsigned)(tiles_m * tiles_n), 1, (unsigned)nets);
-    if (!node_on(e, "k_nt_wide.layer1", fl, by, grid, dim3(256))) return 0;
+    if (!node_on(x, "k_nt_wide.layer1", fl, by, grid, dim3(256))) return 0;
     hipLaunchKernelGGL(k_nt_wide, grid, dim3(256), 0, s, g);
   } else {
     const int tiles = tiles_m * tiles_n * nets;
@@ -337,11 +350,11 @@ static int launch_nt(sactd3_engine* e, hipStream_t s, const char* name, int pro,
     gg.flat_r = gg.flat ? (riders + 7) & ~7 : 0; gg.flat_n = riders;
     const dim3 grid = gg.flat ? dim3((unsigned)(gg.nt_blocks * nets + gg.flat_r)) : dim3((unsigned)(gg.nt_blocks + riders), 1, (unsigned)nets);
     char inst[64] = "k_nt";
-    if (e->node_log) {
+    if (x.node_log) {
       const int c1 = (g.K1 + 15) / 16;
       snprintf(inst, sizeof(inst), c4 ? "k_nt<%d,%s,%d,%d,%d,true>.%s" : "k_nt<%d,%s,%d,%d,%d>.%s", pro, fuse1 ? "true" : "false", ks, fuse1 ? (c1 <= 1 ? 1 : (c1 == 2 ? 2 : 4)) : 0, nt, name);
     }
-    if (!node_on(e, inst, fl, by, grid, dim3(256))) return 0;
+    if (!node_on(x, inst, fl, by, grid, dim3(256))) return 0;
     if (c4) launch_nt_c4(s, nt, grid, gg);
     else if (fuse1) { if (pro == 1) launch_nt_f1<1>(s, ks, nt, grid, gg); else launch_nt_f1<2>(s, ks, nt, grid, gg); }
     else if (nt == 2) {   // (KS == 2) the A rows are fetched and normalised by half as many blocks
@@ -352,7 +365,7 @@ static int launch_nt(sactd3_engine* e, hipStream_t s, const char* name, int pro,
   HIPCHK(hipGetLastError());
   return 0;
 }
-static int launch_nn(sactd3_engine* e, hipStream_t s, const char* name, const NnArgs& g, int nets) {
+static int launch_nn(EnqCtx& x, const char* name, const NnArgs& g, int nets) {
   if (g.M >= BIG_BATCH && g.Kout == HID && g.k_off == 0) {   // large batch: LDS-tiled form, ~1 block per CU
     const double fl = 2.0 * nets * (double)g.M * HID * HID, by = 4.0 * nets * (2.0 * g.M * HID + (double)HID * HID);
     if (nets >= 2) {
@@ -380,12 +393,30 @@ static int launch_nn(sactd3_engine* e, hipStream_t s, const char* name, const Nn
 #define TN64_M 64
 #endif
 #define TN64_KERNEL (k_tn64<TN64_CFG>)
-// Large batches: split-M GEMM into partial slabs (k_tn64) + slab sum / vector gradients / Adam / Polyak (k_adam_red).
-static int launch_tn64(sactd3_engine* e, hipStream_t s, const char* name, const TnArgs& g, int nets, int tick_extra = 0) {
-  Tn64Args a{};
-  a.nprob = g.nprob; a.M = g.M; a.nets = nets; a.Gp = e->Gp; a.g_ns = nets > 1 ? g.g_ns : (long)e->La.size;
+// What is not a GEMM tile of a weight-gradient launch: the vector finalisations of its problems, the optimiser step (+ Polyak), the
+// loss and the counter tick -- k_adam_red's arguments in the split-M form, the riding blocks' in k_tn (see TnArgs::fin)
+static AdamRedArgs adam_red_args(const TnArgs& g, int nets, long g_ns, int tick_extra) {
   AdamRedArgs r{};
   r.s_off = -1;
+  for (int i = 0; i < g.nprob; ++i) {
+    const TnProb& q = g.pr[i];
+    for (int f = 0; f < q.nfin; ++f) { r.vec[r.nvec].off = q.fin_off[f]; r.vec[r.nvec].slot = q.fin_slot[f]; r.vec[r.nvec].nblk = q.fin_nblk[f]; ++r.nvec; }
+    if (q.fin_s_off >= 0) { r.s_off = q.fin_s_off; r.s_nblk = q.fin_s_nblk; }
+  }
+  r.nets = nets; r.g_ns = g_ns; r.G = g.G; r.keep_g = g.keep_g;
+  r.apply = g.apply; r.P = g.P; r.Mo = g.Mo; r.Vo = g.Vo; r.T = g.T; r.tau = g.tau; r.adam = g.adam; r.b1 = g.b1; r.b2 = g.b2; r.eps = g.eps;
+  r.T2 = g.T2; r.T3 = g.T3;      // (never set on the split-M route: actor_dw_is_tiled64)
+  r.part = g.part; r.pstride = g.pstride; r.part_s = g.part_s;
+  r.loss_part = g.loss_part; r.loss_n = g.loss_n; r.loss_stride = g.loss_stride; r.loss_off = g.loss_off; r.loss_scale = g.loss_scale;
+  r.loss_dst = g.loss_dst; r.tick = g.tick; r.tick_extra = tick_extra;
+  return r;
+}
+// Large batches: split-M GEMM into partial slabs (k_tn64) + slab sum / vector gradients / Adam / Polyak (k_adam_red).
+// (called by launch_tn, which has set g.keep_g)
+static int launch_tn64(EnqCtx& x, const char* name, const TnArgs& g, int nets, int tick_extra = 0) {
+  sactd3_engine* e = x.e;
+  Tn64Args a{};
+  a.nprob = g.nprob; a.M = g.M; a.nets = nets; a.Gp = e->Gp; a.g_ns = nets > 1 ? g.g_ns : (long)e->La.size;
   int tiles = 0;
   double fl = 0.0, by = 0.0;
   for (int i = 0; i < g.nprob; ++i) {
@@ -395,8 +426,6 @@ static int launch_tn64(sactd3_engine* e, hipStream_t s, const char* name, const 
     t.w_off = q.w_off; t.ldw = q.ldw; t.b_off = q.b_off;
     t.tiles_n = (q.N + TN64_N - 1) / TN64_N; t.tiles_k = (q.ldw + TN64_K - 1) / TN64_K; t.tile0 = tiles;
     tiles += t.tiles_n * t.tiles_k;
-    for (int f = 0; f < q.nfin; ++f) { r.vec[r.nvec].off = q.fin_off[f]; r.vec[r.nvec].slot = q.fin_slot[f]; r.vec[r.nvec].nblk = q.fin_nblk[f]; ++r.nvec; }
-    if (q.fin_s_off >= 0) { r.s_off = q.fin_s_off; r.s_nblk = q.fin_s_nblk; }
     fl += 2.0 * nets * (double)g.M * q.N * q.K;
     by += 4.0 * nets * (double)g.M * (q.N + q.K);
   }
@@ -413,11 +442,8 @@ static int launch_tn64(sactd3_engine* e, hipStream_t s, const char* name, const 
     snprintf(inst, sizeof(inst), "k_tn64<2,2,2,1,64>.dW(split-M x%d)", S);   // (instance = TN64_CFG: the name rocprofv3 reports)
     LAUNCH(inst, fl, by + 4.0 * S * nets * (double)size, TN64_KERNEL, grid, dim3(256), a);
   }
-  r.Gp = e->Gp; r.S = S; r.nets = nets; r.g_ns = size; r.G = g.G; r.keep_g = !(e->lean_stores && g.apply);
-  r.apply = g.apply; r.P = g.P; r.Mo = g.Mo; r.Vo = g.Vo; r.T = g.T; r.tau = g.tau; r.adam = g.adam; r.b1 = g.b1; r.b2 = g.b2; r.eps = g.eps;
-  r.part = g.part; r.pstride = g.pstride; r.part_s = g.part_s;
-  r.loss_part = g.loss_part; r.loss_n = g.loss_n; r.loss_stride = g.loss_stride; r.loss_off = g.loss_off; r.loss_scale = g.loss_scale;
-  r.loss_dst = g.loss_dst; r.tick = g.tick; r.tick_extra = tick_extra;
+  AdamRedArgs r = adam_red_args(g, nets, size, tick_extra);
+  r.Gp = e->Gp; r.S = S;
   const dim3 grid((unsigned)((size / 4 + 255) / 256 + 4 * r.nvec + 1), (unsigned)nets);
   const char* rname = g.apply ? (g.T ? "k_adam_red.sum+adam+polyak" : "k_adam_red.sum+adam") : "k_adam_red.sum";
   const double rbytes = nets * (double)size * (4.0 * S + 4.0 + (g.apply ? 24.0 : 0.0) + (g.apply && g.T ? 8.0 : 0.0));
@@ -433,13 +459,15 @@ static inline int tn_width(const TnProb& q) { return q.kw > 0 ? q.kw : q.ldw; }
 // vs 14.4 us)
 static bool tn_is_tiled64(const sactd3_engine* e, int M, int tiles64) { return M >= BIG_BATCH && e->Gp && tiles64 >= e->num_cus / 2; }
 static inline int tn64_tiles(int N, int ldw) { return ((N + TN64_N - 1) / TN64_N) * ((ldw + TN64_K - 1) / TN64_K); }
-static int launch_tn(sactd3_engine* e, hipStream_t s, const char* name, TnArgs& g, int nets, int tick_extra = 0) {
-  g.keep_g = !(e->lean_stores && g.apply);      // (see sactd3_engine::lean_stores)
+static int launch_tn(EnqCtx& x, const char* name, TnArgs& g, int nets, int tick_extra = 0) {
+  sactd3_engine* e = x.e;
+  const hipStream_t s = x.s;
+  g.keep_g = !(x.lean_stores && g.apply);      // (see sactd3_engine::grads_stale)
   if (!g.keep_g) for (int i = 0; i < g.nprob; ++i) g.pr[i].f_dz = nullptr;
   {
     int tiles = 0;
     for (int i = 0; i < g.nprob; ++i) tiles += tn64_tiles(g.pr[i].N, g.pr[i].ldw);
-    if (tn_is_tiled64(e, g.M, tiles * nets)) return launch_tn64(e, s, name, g, nets, tick_extra);
+    if (tn_is_tiled64(e, g.M, tiles * nets)) return launch_tn64(x, name, g, nets, tick_extra);
   }
   auto count = [&](int kt) {
     int tiles = 0;
@@ -469,25 +497,10 @@ static int launch_tn(sactd3_engine* e, hipStream_t s, const char* name, TnArgs& 
   snprintf(inst, sizeof(inst), fold ? "k_tn<%d,true>.%s" : "k_tn<%d>.%s", kt, name);
   g.tiles = tiles;
   if (g.pk_blocks) by += 12.0 * (g.pk.n0 + g.pk.n1);
-  {   // what is not a GEMM tile goes to riding blocks (see TnArgs::fin)
-    AdamRedArgs& r = g.fin;
-    r = AdamRedArgs{};
-    r.s_off = -1;
-    for (int i = 0; i < g.nprob; ++i) {
-      const TnProb& q = g.pr[i];
-      for (int f = 0; f < q.nfin; ++f) { r.vec[r.nvec].off = q.fin_off[f]; r.vec[r.nvec].slot = q.fin_slot[f]; r.vec[r.nvec].nblk = q.fin_nblk[f]; ++r.nvec; }
-      if (q.fin_s_off >= 0) { r.s_off = q.fin_s_off; r.s_nblk = q.fin_s_nblk; }
-    }
-    r.nets = nets; r.g_ns = g.g_ns; r.G = g.G; r.keep_g = g.keep_g;
-    r.apply = g.apply; r.P = g.P; r.Mo = g.Mo; r.Vo = g.Vo; r.T = g.T; r.tau = g.tau; r.adam = g.adam; r.b1 = g.b1; r.b2 = g.b2; r.eps = g.eps;
-    r.T2 = g.T2; r.T3 = g.T3;
-    r.part = g.part; r.pstride = g.pstride; r.part_s = g.part_s;
-    r.loss_part = g.loss_part; r.loss_n = g.loss_n; r.loss_stride = g.loss_stride; r.loss_off = g.loss_off; r.loss_scale = g.loss_scale;
-    r.loss_dst = g.loss_dst; r.tick = g.tick; r.tick_extra = tick_extra;
-    g.fin_blocks = 4 * r.nvec + 1;
-  }
+  g.fin = adam_red_args(g, nets, g.g_ns, tick_extra);      // what is not a GEMM tile goes to riding blocks (see TnArgs::fin)
+  g.fin_blocks = 4 * g.fin.nvec + 1;
   const dim3 grid((unsigned)((tiles + g.pk_blocks + g.fin_blocks + (nets > 1 ? 7 : 0)) & (nets > 1 ? ~7 : ~0)), 1, (unsigned)nets);
-  if (!node_on(e, inst, fl, by, grid, dim3(256))) return 0;
+  if (!node_on(x, inst, fl, by, grid, dim3(256))) return 0;
   if (g.keep_g) {
     if (fold) {
       if (kt == 2) hipLaunchKernelGGL((k_tn<2, true>), grid, dim3(256), 0, s, g);
@@ -544,8 +557,9 @@ struct TrunkTicks { int* tick0; int* tick1; float* adam_out; double* adam_pw; fl
                     int force_ks = 0;                      // keep the single-net launch's K split (bit-equal results across launch shapes)
                     bool no_tiled64 = false;               // keep the 32 x 32-tile launches (the ones that can read ring rows / carry gathers)
                     int* tick0b = nullptr; float* adam_out_b = nullptr; double* adam_pw_b = nullptr; float lr_b = 0.f; };   // a second step counter
-static int enqueue_trunk(sactd3_engine* e, hipStream_t s, int ldx, int K, int M, const NetLayout& L, long p_ns,
+static int enqueue_trunk(EnqCtx& x, int ldx, int K, int M, const NetLayout& L, long p_ns,
                          int ngrp, int npg, const TrunkGrp* grp, TrunkTicks tk) {
+  sactd3_engine* e = x.e;
   const int pro = e->cfg.layer_norm ? 1 : 2;
   NtArgs h{};
   h.npg = npg; h.oW = L.W2; h.ldw = HID; h.oBias = L.b2; h.oG = L.g1; h.oBe = L.be1; h.p_ns = p_ns;
@@ -568,14 +582,17 @@ static int enqueue_trunk(sactd3_engine* e, hipStream_t s, int ldx, int K, int M,
     for (int i = 0; i < tk.nnoise; ++i) { a.nz[i] = tk.noise[i]; a.nz[i].blocks = (tk.noise[i].n + 1023) / 1024; }
     if (tk.noise_taken) *tk.noise_taken = true;
   };
+  // the first layer as a launch of its own (every form but the fused one of narrow inputs); it makes the ticks
+  NtArgs g{};
+  g.npg = npg; g.oW = L.W1; g.ldw = L.ld1; g.oBias = L.b1; g.p_ns = p_ns; g.ld_in = ldx; g.in_ns = 0;
+  g.ldy = HID; g.y_ns = (long)M * HID; g.M = M; g.N = HID; g.K = K;
+  for (int i = 0; i < ngrp; ++i) { g.g[i].in = grp[i].x; g.g[i].P = grp[i].P; g.g[i].Y = grp[i].z1; }
+  g.tick0 = tk.tick0; g.tick1 = tk.tick1; g.adam_out = tk.adam_out; g.adam_pw = tk.adam_pw; g.lr = tk.lr; g.b1 = e->cfg.adam_beta1; g.b2 = e->cfg.adam_beta2;
+  g.tick0b = tk.tick0b; g.adam_out_b = tk.adam_out_b; g.adam_pw_b = tk.adam_pw_b; g.lr_b = tk.lr_b;
+  double st = 0.0;   // rows the large-batch layer-2 launches write besides the output: h and xhat where the caller keeps them
+  for (int i = 0; i < ngrp; ++i) st += ((grp[i].xh ? 1.0 : 0.0) + (grp[i].h ? 1.0 : 0.0)) / ngrp;
   // MFMA-bound sizes with enough 64 x 64 tiles to fill the chip: tiled GEMM -> tiled GEMM with the LayerNorm + ReLU prologue
   if (big_path) {
-    NtArgs g{};
-    g.npg = npg; g.oW = L.W1; g.ldw = L.ld1; g.oBias = L.b1; g.p_ns = p_ns; g.ld_in = ldx; g.in_ns = 0;
-    g.ldy = HID; g.y_ns = (long)M * HID; g.M = M; g.N = HID; g.K = K;
-    for (int i = 0; i < ngrp; ++i) { g.g[i].in = grp[i].x; g.g[i].P = grp[i].P; g.g[i].Y = grp[i].z1; }
-    g.tick0 = tk.tick0; g.tick1 = tk.tick1; g.adam_out = tk.adam_out; g.adam_pw = tk.adam_pw; g.lr = tk.lr; g.b1 = e->cfg.adam_beta1; g.b2 = e->cfg.adam_beta2;
-    g.tick0b = tk.tick0b; g.adam_out_b = tk.adam_out_b; g.adam_pw_b = tk.adam_pw_b; g.lr_b = tk.lr_b;
     const dim3 grid((unsigned)(((M + 63) / 64) * (HID / 64) * nets));
     const double by_w = 4.0 * nets * (double)HID, by_rows = 4.0 * nets * (double)M * HID;
     {   // a pending temperature step rides as one extra block of the first-layer launch (nothing in the trunk reads log_alpha)
@@ -585,37 +602,24 @@ static int enqueue_trunk(sactd3_engine* e, hipStream_t s, int ldx, int K, int M,
              (k_nt64<4, 2, 2>), grid1, dim3(512), g);
     }
     // second layer with the LayerNorm + ReLU of the first as its prologue (k_nt64_ln): no row kernel in between
-    NtArgs h2{};
-    h2.npg = npg; h2.oW = L.W2; h2.ldw = HID; h2.oBias = L.b2; h2.oG = L.g1; h2.oBe = L.be1; h2.p_ns = p_ns; h2.ld_in = HID; h2.in_ns = (long)M * HID;
-    h2.ldy = HID; h2.y_ns = (long)M * HID; h2.M = M; h2.N = HID; h2.K = HID; h2.act_ns = (long)M * HID; h2.ln_pro = e->cfg.layer_norm ? 1 : 0;
-    for (int i = 0; i < ngrp; ++i) {
-      h2.g[i].in = grp[i].z1; h2.g[i].P = grp[i].P; h2.g[i].Y = grp[i].z2;
-      h2.g[i].h_out = grp[i].h; h2.g[i].xh_out = grp[i].xh; h2.g[i].rstd_out = grp[i].rstd;
-    }
-    {
-      double st = 0.0;   // rows written besides the output: h and xhat where the caller keeps them
-      for (int i = 0; i < ngrp; ++i) st += ((grp[i].xh ? 1.0 : 0.0) + (grp[i].h ? 1.0 : 0.0)) / ngrp;
-      LAUNCH("k_nt64_ln<4,2,2>.layer2", 2.0 * nets * (double)M * HID * HID, by_w * (HID + 3) + by_rows * (2.0 + st), (k_nt64_ln<4, 2, 2>), grid, dim3(512), h2);
-    }
+    for (int i = 0; i < ngrp; ++i) h.g[i].in = grp[i].z1;
+    h.ld_in = HID; h.in_ns = (long)M * HID; h.ln_pro = e->cfg.layer_norm ? 1 : 0;
+    LAUNCH("k_nt64_ln<4,2,2>.layer2", 2.0 * nets * (double)M * HID * HID, by_w * (HID + 3) + by_rows * (2.0 + st), (k_nt64_ln<4, 2, 2>), grid, dim3(512), h);
     return 0;
   }
+  // the k_nt forms and the 32 x 32-tiled one: the launch that holds layer 2 carries a pending temperature step as one extra block
+  // (never together with noise blocks: those read the counter it ticks) and the following tail's draws as a few more
+  if (tk.alpha) { h.alpha_block = 1; h.al = *tk.alpha; }
+  set_noise(h);
   if (K <= 64) {
     for (int i = 0; i < ngrp; ++i) h.g[i].in = grp[i].x;
     h.ld_in = ldx; h.in_ns = 0; h.K1 = K; h.oW1 = L.W1; h.ldw1 = L.ld1; h.oB1 = L.b1;
     h.tick0 = tk.tick0; h.tick1 = tk.tick1; h.adam_out = tk.adam_out; h.adam_pw = tk.adam_pw; h.lr = tk.lr; h.b1 = e->cfg.adam_beta1; h.b2 = e->cfg.adam_beta2;
     h.w1_magic = magic_div((unsigned)L.ld1, 4u * HID * (unsigned)L.ld1);
-    if (tk.alpha) { h.alpha_block = 1; h.al = *tk.alpha; }
-    set_noise(h);
     set_ring(h);            // x = a field of the sampled records; extra blocks fill the batch slot(s) (see NtArgs)
     h.tick0b = tk.tick0b; h.adam_out_b = tk.adam_out_b; h.adam_pw_b = tk.adam_pw_b; h.lr_b = tk.lr_b;
-    return launch_nt(e, s, "layers1+2", pro, true, h, nets, tk.force_ks);
+    return launch_nt(x, "layers1+2", pro, true, h, nets, tk.force_ks);
   }
-  NtArgs g{};
-  g.npg = npg; g.oW = L.W1; g.ldw = L.ld1; g.oBias = L.b1; g.p_ns = p_ns; g.ld_in = ldx; g.in_ns = 0;
-  g.ldy = HID; g.y_ns = (long)M * HID; g.M = M; g.N = HID; g.K = K;
-  for (int i = 0; i < ngrp; ++i) { g.g[i].in = grp[i].x; g.g[i].P = grp[i].P; g.g[i].Y = grp[i].z1; }
-  g.tick0 = tk.tick0; g.tick1 = tk.tick1; g.adam_out = tk.adam_out; g.adam_pw = tk.adam_pw; g.lr = tk.lr; g.b1 = e->cfg.adam_beta1; g.b2 = e->cfg.adam_beta2;
-  g.tick0b = tk.tick0b; g.adam_out_b = tk.adam_out_b; g.adam_pw_b = tk.adam_pw_b; g.lr_b = tk.lr_b;
   if (M >= BIG_BATCH && M == e->B) {   // large batch, too few nets for 64 x 64 tiles to fill the chip: 32 x 32 LDS-tiled form
     unsigned nblk = (unsigned)(((M + 31) / 32) * (HID / 32) * nets);
     set_ring(g);            // x = the field of the sampled records itself; extra blocks fill the batch slot(s) (as in the fused k_nt form)
@@ -624,23 +628,19 @@ static int enqueue_trunk(sactd3_engine* e, hipStream_t s, int ldx, int K, int M,
     const dim3 grid(nblk);
     LAUNCH("k_nt64<2,2,1>.layer1", 2.0 * nets * (double)M * HID * K, 4.0 * (nets * (double)HID * (K + 1) + ngrp * (double)M * K + nets * (double)M * HID),
            (k_nt64<2, 2, 1>), grid, dim3(256), g);
-  } else RCCHK(launch_nt(e, s, "layer1", 0, false, g, nets));
+  } else RCCHK(launch_nt(x, "layer1", 0, false, g, nets));
   for (int i = 0; i < ngrp; ++i) h.g[i].in = grp[i].z1;
   h.ld_in = HID; h.in_ns = (long)M * HID;
-  if (tk.alpha) { h.alpha_block = 1; h.al = *tk.alpha; }   // (never together with noise blocks: those read the counter it ticks)
-  set_noise(h);            // (as in the fused form) the following tail's draws as extra blocks of the layer-2 launch
   if (M >= BIG_BATCH && M == e->B) {   // large batch: the 32 x 32 LDS-tiled form with the LayerNorm prologue
     h.ln_pro = e->cfg.layer_norm ? 1 : 0;
     h.nt_blocks = ((M + 31) / 32) * (HID / 32) * nets;
     int nzb = 0;
     for (int i = 0; i < h.nz_n && i < 5; ++i) nzb += h.nz[i].blocks;
-    double st = 0.0;
-    for (int i = 0; i < ngrp; ++i) st += ((grp[i].xh ? 1.0 : 0.0) + (grp[i].h ? 1.0 : 0.0)) / ngrp;
     LAUNCH("k_nt64_ln<2,2,1>.layer2", 2.0 * nets * (double)M * HID * HID, 4.0 * nets * ((double)HID * (HID + 3) + (double)M * HID * (2.0 + st)),
            (k_nt64_ln<2, 2, 1>), dim3((unsigned)(h.nt_blocks + h.alpha_block + nzb)), dim3(256), h);
     return 0;
   }
-  return launch_nt(e, s, "layer2", pro, false, h, nets);
+  return launch_nt(x, "layer2", pro, false, h, nets);
 }
 
 static ActorTail tail_args(sactd3_engine* e, const float* z2, const float* P, int M, int mode, int train,
@@ -664,25 +664,46 @@ static NoiseJob noise_job(sactd3_engine* e, int site_buf, unsigned site_code, in
 }
 // rows of the batch one block of the actor-tail kernel handles (narrow heads: one wave per 4 rows, see k_actor_tail_s)
 static int tail_rows_per_block(const ActorTail& t) { return (t.L.nh <= 8 && t.a <= 8) ? 4 : 16; }
-static int launch_tail(sactd3_engine* e, hipStream_t s, const ActorTail& t) {
-  const int nh = t.L.nh;
-  if (tail_rows_per_block(t) == 4) {
-    LAUNCH("k_actor_tail_s<4>", 2.0 * t.B * (double)HID * nh,
-           4.0 * ((double)t.B * HID * (t.train ? 3 : 1) + (double)nh * (HID + 1) + 2.0 * HID + (double)t.B * (3 * t.a + 2) + (t.obs_src ? 2.0 * t.B * t.o : 0.0)),
-           k_actor_tail_s<4>, dim3((t.B + 3) / 4), dim3(64), t);
-    return 0;
+// The tails t[0 .. n) (all of B rows through the same head shape) as ONE launch of the kernel that holds `width` of them: 1; 2 (the
+// opening pair's target-action and policy tails); 5 (the run-ahead: n <= 5, blocks exist for n tails only).  4-row or 16-row form.
+// (The 5-tail form's launch stands behind enqueue_update_actor: the compiler emits kernel template instances in the order this file
+//  first names them, and k_ln_bwd<16> came out with other instructions when k_actor_tail_s5<4> was named here, ahead of it.)
+static int launch_tails5(EnqCtx& x, const ActorTail5& T, double fl, double by, dim3 grid, dim3 block);
+static int launch_tails(EnqCtx& x, int width, const ActorTail* t, int n) {
+  const int B = t[0].B, nh = t[0].L.nh, a = t[0].a, o = t[0].o;
+  const bool rows4 = tail_rows_per_block(t[0]) == 4;
+  const int nb = rows4 ? (B + 3) / 4 : (B + 15) / 16;
+  const dim3 grid((unsigned)(n * nb)), block(rows4 ? 64 : 256);
+  const double fl = 2.0 * n * B * (double)HID * nh;
+  if (width == 1) {
+    const double by = 4.0 * ((double)B * HID * (t->train ? 3 : 1) + (double)nh * (HID + 1) + 2.0 * HID + (double)B * (3 * a + 2) + (t->obs_src ? 2.0 * B * o : 0.0));
+    if (rows4) LAUNCH("k_actor_tail_s<4>", fl, by, k_actor_tail_s<4>, grid, block, t[0]);
+    else LAUNCH("k_actor_tail", fl, by, k_actor_tail, grid, block, t[0]);
+  } else if (width == 2) {
+    const double by = 4.0 * ((double)B * HID * 4 + 2.0 * nh * (HID + 1) + 4.0 * HID + (double)B * (6 * a + 4 + 2 * o));
+    if (rows4) LAUNCH("k_actor_tail_s2<4>", fl, by, k_actor_tail_s2<4>, grid, block, t[0], t[1], nb);
+    else LAUNCH("k_actor_tail2", fl, by, k_actor_tail2, grid, block, t[0], t[1], nb);      // (wide heads: the two tails as one launch of the general kernel)
+  } else {
+    ActorTail5 T{};
+    for (int i = 0; i < 5; ++i) T.t[i] = t[i < n ? i : 0];                               // (the copies never run: blocks exist for n tails only)
+    T.nb = nb; T.n = n;
+    // (a policy pass at the end -- the next period's -- also writes its backward stores and [s | pi(s)])
+    return launch_tails5(x, T, fl, 4.0 * n * ((double)B * HID + (double)nh * (HID + 1) + 2.0 * HID + (double)B * (3 * a + 2)) + (t[n - 1].train ? 8.0 * (double)B * (HID + o) : 0.0), grid, block);
   }
-  LAUNCH("k_actor_tail", 2.0 * t.B * (double)HID * nh,
-         4.0 * ((double)t.B * HID * (t.train ? 3 : 1) + (double)nh * (HID + 1) + 2.0 * HID + (double)t.B * (3 * t.a + 2) + (t.obs_src ? 2.0 * t.B * t.o : 0.0)),
-         k_actor_tail, dim3((t.B + 15) / 16), dim3(256), t);
   return 0;
 }
+static int launch_tail(EnqCtx& x, const ActorTail& t) { return launch_tails(x, 1, &t, 1); }
 
-static int enqueue_gather(sactd3_engine* e, hipStream_t s, const float* ring, int identity_len) {
+static int enqueue_gather(EnqCtx& x, const float* ring, int identity_len) {
+  sactd3_engine* e = x.e;
   const GatherArgs g = gather_args(e, ring, identity_len);
   // 2 B T + 4 B, T = 4 (2o + a + 1) + 1
   LAUNCH("k_gather", 0.0, 2.0 * e->B * (4.0 * (2 * e->o + e->a + 1) + 1.0) + 4.0 * e->B, k_gather, dim3(gather_blocks((long)e->B * e->rec4)), dim3(256), g);
   return 0;
+}
+static int gather_now(sactd3_engine* e, const float* ring, int identity_len) {      // (the API path: a sequence of this one launch)
+  EnqCtx x{e, e->stream};
+  return enqueue_gather(x, ring, identity_len);
 }
 
 static AdamArgs adam_args(sactd3_engine* e, float* p, const float* g, float* m, float* v, long n, const float* adam) {
@@ -691,7 +712,7 @@ static AdamArgs adam_args(sactd3_engine* e, float* p, const float* g, float* m, 
   a.b1 = e->cfg.adam_beta1; a.b2 = e->cfg.adam_beta2; a.eps = e->cfg.adam_eps;
   return a;
 }
-static int launch_adam(sactd3_engine* e, hipStream_t s, const AdamArgs& a) {
+static int launch_adam(EnqCtx& x, const AdamArgs& a) {
   const int blocks = (int)std::min<long>(512, (a.n / 4 + 255) / 256);
   LAUNCH("k_adam", 0.0, 28.0 * a.n, k_adam, dim3(std::max(blocks, 1)), dim3(256), a);
   return 0;
@@ -700,117 +721,136 @@ static int launch_adam(sactd3_engine* e, hipStream_t s, const AdamArgs& a) {
 // Can the actor trunk that opens an iteration (1 net, or 2 groups when the policy pass is merged in) carry a temperature step as an
 // extra block?  The k_nt launches can (fused first layer, or the layer-2 launch of the layer-by-layer form); the tiled k_nt64 pair
 // of launches with >= 3/4 of the chip in 64 x 64 tiles cannot (see enqueue_trunk).
-static bool opening_trunk_carries_alpha(const sactd3_engine* e);
-// Does the actor trunk that opens a fused iteration read its rows from the ring itself, with the gather into the batch slot riding in
-// the same launch?  Narrow observations below the large-batch threshold (fused k_nt), and wide ones at large batch (k_nt64<2,2,1>).
-static bool opening_trunk_gathers(const sactd3_engine* e) {
-  return (e->o <= 64 && e->B < BIG_BATCH) || (e->o > 64 && e->B >= BIG_BATCH && opening_trunk_carries_alpha(e));
-}
 static bool opening_trunk_carries_alpha(const sactd3_engine* e) {
   const int B = e->B;
   const bool tiled = B >= BIG_BATCH && ((B + 63) / 64) * (HID / 64) * 2 >= (3 * e->num_cus) / 4;
   return !tiled;
 }
+// Does the actor trunk that opens a fused iteration read its rows from the ring itself, with the gather into the batch slot riding in
+// the same launch?  Narrow observations below the large-batch threshold (fused k_nt), and wide ones at large batch (k_nt64<2,2,1>).
+static bool opening_trunk_gathers(const sactd3_engine* e) {
+  return (e->o <= 64 && e->B < BIG_BATCH) || (e->o > 64 && e->B >= BIG_BATCH && opening_trunk_carries_alpha(e));
+}
+
+// Does the opening pair of a fused iteration with actor updates hold the FIRST actor update's pi(s) pass too (see enqueue_opening_pair)?
+// In the fused-first-layer launches of narrow observations, and as a second group of the layer-by-layer launches of wide ones at
+// large batch (Humanoid: two nodes fewer per actor iteration).
+static bool opening_merges_policy(const sactd3_engine* e) {
+  return (opening_trunk_gathers(e) && e->o <= 64) || (e->o > 64 && e->B >= BIG_BATCH);
+}
+// (TD3, fused iteration without actor updates) can the critics' weight-gradient launch carry the actor target's Polyak update as
+// extra blocks?  (the split-M route has no riding blocks)
+static bool actor_target_rides(const sactd3_engine* e) { return !(e->B >= BIG_BATCH && e->Gp); }
+
+// An iteration's place in the sequence being enqueued (orchestrator.py:337-352 decides the first two).
+// slot / pre_sampled / ahead: the pipelined form of a period graph (period_is_pipelined): iteration i of the period trains on batch
+// slot i; the first one (with the actor updates) also runs the sampling + next-action passes of the `ahead` iterations behind it,
+// which are then `pre_sampled`: their sample, gather and next-action pass (a', log pi(a'|s')) are there, the update starts at the
+// twin-critic trunk.  The first iteration is itself pre_sampled: its opening pair (with the first actor update's policy pass) was
+// left by the previous period or by the opening graph.
+// chain_slot >= 0: (chained periods) ... and the opening pair of the NEXT period's first iteration into that batch slot.
+struct IterPlace {
+  bool actor = false, targets = false;      // the iteration has actor updates / a target update
+  bool more = false;                        // another iteration follows in the same graph
+  int slot = 0; bool pre_sampled = false; int ahead = 0, chain_slot = -1;
+};
+static IterPlace single_iteration(bool actor, bool targets) {      // (sactd3_step)
+  IterPlace it;
+  it.actor = actor; it.targets = targets;
+  return it;
+}
+
+// The opening pair of a critic update (agents/agent.py:194-205): the actor trunk on s' and its tail, the target action.
+// fused_sample: the update opens a fused iteration and owns the replay sampling (orchestrator.py:338); with a narrow
+// observation the gather rides in the trunk kernel, otherwise enqueue_step has launched k_gather just before.
+// it.actor: also run the first actor update's policy pass pi(s) in the same two launches where they can (opening_merges_policy).
+// it.pre_sampled: the pair runs ahead of its iteration (the opening graph): the counter ticks -- critics' and actor's step counters,
+// sample counter -- are left to that iteration's twin-critic trunk (enqueue_update_qnets).
+static int enqueue_opening_pair(EnqCtx& x, const IterPlace& it, bool fused_sample) {
+  sactd3_engine* e = x.e;
+  const bool ticks = !it.pre_sampled;
+  const sactd3_config& c = e->cfg;
+  const int B = e->B, td3 = c.prefer_td3_over_sac;
+  const sactd3_engine::BatchSlot& S = e->bs[it.slot];
+  // target action: SAC a' ~ pi(s') with the ONLINE actor (agent.py:205); TD3 pi_targ(s') + clipped noise (agent.py:194-200)
+  const float* Pact = td3 ? e->Ta : e->Pa;
+  const bool in_kernel_gather = fused_sample && opening_trunk_gathers(e);
+  const bool merge_policy = it.actor && fused_sample && opening_merges_policy(e);
+  const bool wide_merge = merge_policy && e->o > 64;
+  x.role = fused_sample ? (merge_policy ? "critic/next-action+sample & actor0/policy" : "critic/next-action+sample") : "critic/next-action";
+  // (layer-by-layer launches materialise z1: the target-action group borrows the target critics' z1 slab, idle until the next launch)
+  TrunkGrp g[2] = {{S.Xn, Pact, wide_merge ? e->t_z1 : e->a_z1, merge_policy ? e->a_z2n : e->a_z2, nullptr, nullptr, nullptr, e->ldc},
+                   {S.X, e->Pa, e->a_z1, e->a_z2, e->a_xh1, e->a_h1, e->a_rs1, 0}};
+  TrunkTicks tk{&e->ctl->t_q, (fused_sample && !in_kernel_gather) ? &e->ctl->sample_ctr : nullptr, e->ctl->adam_q, e->ctl->pw_q, c.qnets_lr};
+  if (!ticks) { tk.tick0 = nullptr; tk.tick1 = nullptr; tk.adam_out = nullptr; tk.adam_pw = nullptr; }
+  if (in_kernel_gather) {   // the trunk reads its rows from the ring itself; the gather into the batch slot rides along
+    tk.ngather = 1; tk.gather[0] = gather_args(e, e->ring, -1, it.slot);
+    for (auto& gg : g) { gg.ring = true; gg.ring_idx = S.idx; }
+  }
+  const int mode = td3 ? (c.targ_actor_smoothing ? 1 : 0) : 0;
+  bool eps_ready = false;
+  if (!td3 || mode == 1) { tk.noise[tk.nnoise++] = noise_job(e, SACTD3_SITE_CRITIC, 0u, 0, B); tk.noise[tk.nnoise - 1].eps = S.eps_c; tk.noise_taken = &eps_ready; }
+  // a temperature step deferred from the previous iteration of the same graph (sactd3_step_period) rides in this launch; its
+  // tick of the noise counter stays owed: this iteration's draws count one ahead and the critics' last kernel ticks by two
+  int owed = 0;
+  if (x.alpha_pending && x.alpha_tick_owed && fused_sample && opening_trunk_carries_alpha(e)) {
+    tk.alpha = &x.alpha; x.alpha_pending = false;
+    owed = 1;
+    for (int i = 0; i < tk.nnoise; ++i) tk.noise[i].ctr_add += 1;
+  }
+  if (merge_policy) {
+    // the policy sample of the first actor update: same actor parameters (the critic update does not touch them), the stream
+    // counter one ahead (the critic update's last kernel bumps it before the actor update would have read it)
+    if (!td3) { tk.noise[tk.nnoise++] = noise_job(e, SACTD3_SITE_ACTOR0, 16u, 1 + owed, B); tk.noise_taken = &eps_ready; }
+    if (!wide_merge) tk.force_ks = 4;
+    if (ticks) { tk.tick0b = &e->ctl->t_a; tk.adam_out_b = e->ctl->adam_a; tk.adam_pw_b = e->ctl->pw_a; tk.lr_b = c.actor_lr; }
+  }
+  RCCHK(enqueue_trunk(x, e->ldc, e->o, B, e->La, 0, merge_policy ? 2 : 1, 1, g, tk));
+  ActorTail t[2];
+  t[0] = tail_args(e, merge_policy ? e->a_z2n : e->a_z2, Pact, B, mode, 0, SACTD3_SITE_CRITIC, 0u, S.Xn, e->ldc, e->o, S.logp_n);
+  t[0].eps = S.eps_c;
+  t[0].eps_ready = eps_ready; t[0].ctr_add = owed;
+  if (in_kernel_gather && ticks) t[0].tick = &e->ctl->sample_ctr;   // every reader of the index stream (the trunk kernel) is done
+  if (!merge_policy) return launch_tail(x, t[0]);
+  t[1] = tail_args(e, e->a_z2, e->Pa, B, 0, 1, SACTD3_SITE_ACTOR0, 16u, e->Xp, e->ldc, e->o, e->logp_pi);
+  t[1].obs_src = S.X; t[1].lds = e->ldc; t[1].ctr_add = 1 + owed; t[1].eps_ready = eps_ready;     // Xp = [s | pi(s)]
+  return launch_tails(x, 2, t, 2);
+}
 
 // agents/agent.py:183-242
-// fused_sample: this update opens a fused iteration and owns the replay sampling (orchestrator.py:338); with a narrow
-// observation the gather rides in the first trunk kernel, otherwise enqueue_step has launched k_gather just before.
-// with_policy: also run the first actor update's policy pass pi(s) in the opening launches (fused iterations with actor updates);
-// *policy_done tells the caller whether that happened.
-// actor_targ_rides: (TD3, fused iteration without actor updates) the actor target's Polyak update as extra blocks of the
-// weight-gradient launch; *actor_targ_done reports whether the launch could carry it.
-// slot / pre_sampled: (pipelined period, SAC) the batch slot this update trains on; pre_sampled = its sample, gather and next-action
-// pass (a', log pi(a'|s')) were already produced ahead by the last actor update of the period's first iteration (enqueue_update_actor,
-// `ahead`): the update starts at the twin-critic trunk, which then carries the step-counter tick and a deferred temperature step.
-static int enqueue_update_qnets(sactd3_engine* e, hipStream_t s, bool fused_sample, float* fused_polyak_targ,
-                                bool with_policy = false, bool* policy_done = nullptr, bool actor_targ_rides = false, bool* actor_targ_done = nullptr,
-                                int slot = 0, bool pre_sampled = false, int open_mode = 0) {
-  // open_mode (chained periods): 1 = ONLY the opening pair (trunk + tails incl. the first actor update's policy pass), without the
-  // step-counter / sample-counter ticks, then return -- the "opening graph"; 2 = (with pre_sampled) this is the period's first
-  // iteration whose opening pair was precomputed: the twin-critic trunk also makes those ticks (critics', actor's, sample counter)
+// fused_sample: see enqueue_opening_pair (false: the API path -- the batch slot was filled by the caller, no policy pass, no target update).
+// it.targets: with the target updates in the optimiser epilogue (see enqueue_step, actor_target_rides).
+// it.pre_sampled: the opening pair is already there: the update starts at the twin-critic trunk, which then makes its ticks.
+static int enqueue_update_qnets(EnqCtx& x, const IterPlace& it, bool fused_sample) {
+  sactd3_engine* e = x.e;
   const sactd3_config& c = e->cfg;
   const int B = e->B, ln = c.layer_norm, td3 = c.prefer_td3_over_sac;
   const long BH = (long)B * HID;
-  const sactd3_engine::BatchSlot& S = e->bs[slot];
-  int ctr_owed = 0;
-  // target action: SAC a' ~ pi(s') with the ONLINE actor (agent.py:205); TD3 pi_targ(s') + clipped noise (agent.py:194-200)
-  const float* Pact = td3 ? e->Ta : e->Pa;
-  if (!pre_sampled) {
-    const bool in_kernel_gather = fused_sample && opening_trunk_gathers(e);
-    // the FIRST actor update's pi(s) pass rides along (see enqueue_step): in the fused-first-layer launches of narrow observations,
-    // and as a second group of the layer-by-layer launches of wide ones at large batch (Humanoid: two nodes fewer per actor iteration)
-    const bool wide_merge = with_policy && fused_sample && e->o > 64 && B >= BIG_BATCH;
-    const bool merge_policy = with_policy && ((in_kernel_gather && e->o <= 64) || wide_merge);
-    e->node_role = fused_sample ? (merge_policy ? "critic/next-action+sample & actor0/policy" : "critic/next-action+sample") : "critic/next-action";
-    // (layer-by-layer launches materialise z1: the target-action group borrows the target critics' z1 slab, idle until the next launch)
-    TrunkGrp g[2] = {{S.Xn, Pact, wide_merge ? e->t_z1 : e->a_z1, merge_policy ? e->a_z2n : e->a_z2, nullptr, nullptr, nullptr, e->ldc},
-                     {S.X, e->Pa, e->a_z1, e->a_z2, e->a_xh1, e->a_h1, e->a_rs1, 0}};
-    TrunkTicks tk{&e->ctl->t_q, (fused_sample && !in_kernel_gather) ? &e->ctl->sample_ctr : nullptr, e->ctl->adam_q, e->ctl->pw_q, c.qnets_lr};
-    if (open_mode == 1) { tk.tick0 = nullptr; tk.tick1 = nullptr; tk.adam_out = nullptr; tk.adam_pw = nullptr; }
-    if (in_kernel_gather) {   // the trunk reads its rows from the ring itself; the gather into the batch slot rides along
-      tk.ngather = 1; tk.gather[0] = gather_args(e, e->ring, -1, slot);
-      for (auto& gg : g) { gg.ring = true; gg.ring_idx = S.idx; }
-    }
-    const int mode = td3 ? (c.targ_actor_smoothing ? 1 : 0) : 0;
-    bool eps_ready = false;
-    if (!td3 || mode == 1) { tk.noise[tk.nnoise++] = noise_job(e, SACTD3_SITE_CRITIC, 0u, 0, B); tk.noise[tk.nnoise - 1].eps = S.eps_c; tk.noise_taken = &eps_ready; }
-    // a temperature step deferred from the previous iteration of the same graph (sactd3_step_period) rides in this launch; its
-    // tick of the noise counter is owed: this iteration's draws count one ahead and the critics' last kernel ticks by two
-    int owed = 0;
-    if (e->alpha_pending && e->alpha_tick_owed && fused_sample && opening_trunk_carries_alpha(e)) {
-      tk.alpha = &e->pending_alpha; e->alpha_pending = false; e->alpha_tick_owed = false;
-      owed = 1;
-      for (int i = 0; i < tk.nnoise; ++i) tk.noise[i].ctr_add += 1;
-    }
-    ctr_owed = owed;
-    if (merge_policy) {
-      // the policy sample of the first actor update: same actor parameters (the critic update does not touch them), the stream
-      // counter one ahead (the critic update's last kernel bumps it before the actor update would have read it)
-      if (!td3) { tk.noise[tk.nnoise++] = noise_job(e, SACTD3_SITE_ACTOR0, 16u, 1 + owed, B); tk.noise_taken = &eps_ready; }
-      if (!wide_merge) tk.force_ks = 4;
-      if (open_mode != 1) { tk.tick0b = &e->ctl->t_a; tk.adam_out_b = e->ctl->adam_a; tk.adam_pw_b = e->ctl->pw_a; tk.lr_b = c.actor_lr; }
-    }
-    RCCHK(enqueue_trunk(e, s, e->ldc, e->o, B, e->La, 0, merge_policy ? 2 : 1, 1, g, tk));
-    ActorTail t = tail_args(e, merge_policy ? e->a_z2n : e->a_z2, Pact, B, mode, 0, SACTD3_SITE_CRITIC, 0u, S.Xn, e->ldc, e->o, S.logp_n);
-    t.eps = S.eps_c;
-    t.eps_ready = eps_ready; t.ctr_add = owed;
-    if (in_kernel_gather && open_mode != 1) t.tick = &e->ctl->sample_ctr;   // every reader of the index stream (the trunk kernel) is done
-    if (merge_policy && tail_rows_per_block(t) == 4) {
-      ActorTail t1 = tail_args(e, e->a_z2, e->Pa, B, 0, 1, SACTD3_SITE_ACTOR0, 16u, e->Xp, e->ldc, e->o, e->logp_pi);
-      t1.obs_src = S.X; t1.lds = e->ldc; t1.ctr_add = 1 + owed; t1.eps_ready = eps_ready;     // Xp = [s | pi(s)]
-      const int nb = (B + 3) / 4;
-      LAUNCH("k_actor_tail_s2<4>", 2.0 * 2 * B * (double)HID * t.L.nh, 4.0 * ((double)B * HID * 4 + 2.0 * t.L.nh * (HID + 1) + 4.0 * HID + (double)B * (6 * e->a + 4 + 2 * e->o)),
-             k_actor_tail_s2<4>, dim3(2 * nb), dim3(64), t, t1, nb);
-      if (policy_done) *policy_done = true;
-    } else if (merge_policy) {                  // (wide heads: the two tails as one launch of the general kernel)
-      ActorTail t1 = tail_args(e, e->a_z2, e->Pa, B, 0, 1, SACTD3_SITE_ACTOR0, 16u, e->Xp, e->ldc, e->o, e->logp_pi);
-      t1.obs_src = S.X; t1.lds = e->ldc; t1.ctr_add = 1 + owed; t1.eps_ready = eps_ready;
-      const int nb = (B + 15) / 16;
-      LAUNCH("k_actor_tail2", 2.0 * 2 * B * (double)HID * t.L.nh, 4.0 * ((double)B * HID * 4 + 2.0 * t.L.nh * (HID + 1) + 4.0 * HID + (double)B * (6 * e->a + 4 + 2 * e->o)),
-             k_actor_tail2, dim3(2 * nb), dim3(256), t, t1, nb);
-      if (policy_done) *policy_done = true;
-    } else RCCHK(launch_tail(e, s, t));
-    if (open_mode == 1) return (merge_policy && policy_done && *policy_done) ? 0 : e->fail(SACTD3_ESTATE, "opening graph: the policy pass did not merge");
-  }
+  const sactd3_engine::BatchSlot& S = e->bs[it.slot];
+  float* const fused_polyak_targ = it.targets ? e->Tc : nullptr;
+  if (!it.pre_sampled) RCCHK(enqueue_opening_pair(x, it, fused_sample));
   {  // twin target critics on (s', a') and twin online critics on (s, a) in one launch (agent.py:208-210, 230-232).
      // (Measured: running the online pair on a fork/join side branch of the graph instead costs +30 us per replay on
      //  ROCm 7.2 -- cross-stream edges are far dearer than the 1.7 us of a linear edge -- so graphs stay linear.)
     const TrunkGrp g[2] = {{S.Xn, e->Tc, e->t_z1, e->t_z2, nullptr, nullptr, nullptr},
                            {S.X, e->Pc, e->c_z1, e->c_z2, e->c_xh1, e->c_h1, e->c_rs1}};
-    e->node_role = "critic/twin-q(2 target + 2 online)";
+    x.role = "critic/twin-q(2 target + 2 online)";
     TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
-    if (pre_sampled) {   // this launch opens the update: the critics' step counter + Adam scalars, and a temperature step deferred from the
-                         // period's first iteration (its tick of the noise counter is made up by this update's last kernel)
+    if (it.pre_sampled) {   // this launch opens the update: the critics' step counter + Adam scalars, and a temperature step deferred from the
+                            // period's first iteration (its tick of the noise counter is made up by this update's last kernel)
       tk.tick0 = &e->ctl->t_q; tk.adam_out = e->ctl->adam_q; tk.adam_pw = e->ctl->pw_q; tk.lr = c.qnets_lr;
-      if (open_mode == 2) {   // ... the ticks the precomputed opening pair left undone: the sample counter and the actor's step counter
+      if (it.actor) {   // ... the ticks the precomputed opening pair left undone: the sample counter and the actor's step counter
         tk.tick1 = &e->ctl->sample_ctr;
         tk.tick0b = &e->ctl->t_a; tk.adam_out_b = e->ctl->adam_a; tk.adam_pw_b = e->ctl->pw_a; tk.lr_b = c.actor_lr;
       }
-      if (e->alpha_pending && e->alpha_tick_owed) { tk.alpha = &e->pending_alpha; e->alpha_pending = false; e->alpha_tick_owed = false; ctr_owed = 1; }
+      if (x.alpha_pending && x.alpha_tick_owed) { tk.alpha = &x.alpha; x.alpha_pending = false; }
     }
-    RCCHK(enqueue_trunk(e, s, e->ldc, e->o + e->a, B, e->Lc, e->Lc.size, 2, 2, g, tk));
+    RCCHK(enqueue_trunk(x, e->ldc, e->o + e->a, B, e->Lc, e->Lc.size, 2, 2, g, tk));
   }
-  e->node_role = "critic/loss+backward";
+  // the tick a deferred temperature step owes, once one of the two trunk launches above has carried the step
+  const int ctr_owed = (x.alpha_tick_owed && !x.alpha_pending) ? 1 : 0;
+  if (ctr_owed) x.alpha_tick_owed = false;
+  x.role = "critic/loss+backward";
   const bool fused_tail_nn = B < BIG_BATCH;   // the tail AND dh1 = dz2 W2 in one launch (k_ctail_nn)
   const bool fold_ln1 = fused_tail_nn;       // ... then with layer 1's LayerNorm backward inside the weight-gradient launch (TnProb::fold)
   {
@@ -832,7 +872,7 @@ static int enqueue_update_qnets(sactd3_engine* e, hipStream_t s, bool fused_samp
     NnArgs g{};
     g.dY = e->c_dz2; g.dy_ns = BH; g.Wt = e->Pc + e->Lc.W2; g.ldw = HID; g.p_ns = e->Lc.size; g.k_off = 0;
     g.dX = e->c_dh1; g.ldx = HID; g.dx_ns = BH; g.M = B; g.Kout = HID;
-    RCCHK(launch_nn(e, s, "k_nn.dh1", g, 2));
+    RCCHK(launch_nn(x, "k_nn.dh1", g, 2));
   }
   if (!fold_ln1) {
     LnBwd l{};
@@ -864,61 +904,109 @@ static int enqueue_update_qnets(sactd3_engine* e, hipStream_t s, bool fused_samp
     g.b1 = c.adam_beta1; g.b2 = c.adam_beta2; g.eps = c.adam_eps;
     g.loss_part = e->part_s; g.loss_n = 2 * e->nblk4; g.loss_stride = 2; g.loss_off = 1; g.loss_scale = 1.0f / (float)B;   // unused tail entries stay 0
     g.loss_dst = &e->ctl->metrics[SACTD3_M_QF_LOSS]; g.tick = &e->ctl->noise_ctr;
-    const bool rides = actor_targ_rides && !(B >= BIG_BATCH && e->Gp);       // (the split-M route has no riding blocks)
+    const bool rides = it.targets && td3 && !it.actor && actor_target_rides(e);
     if (rides) {
       g.pk.t0 = e->Ta; g.pk.p0 = e->Pa; g.pk.n0 = e->La.size; g.pk.tau = c.polyak;
       // (few of them: the launch already has more blocks than the chip has CUs, and every extra one lands beside a tile block --
       //  64 riding blocks instead of 8: +0.8 us per TD3 iteration)
       g.pk_blocks = (int)std::min<long>(8, (e->La.size / 4 + 255) / 256);
-      if (actor_targ_done) *actor_targ_done = true;
     }
-    RCCHK(launch_tn(e, s, fused_polyak_targ ? (rides ? "dW+adam+polyak & actor-target polyak" : "dW+adam+polyak") : "dW+adam", g, 2, ctr_owed));
+    RCCHK(launch_tn(x, fused_polyak_targ ? (rides ? "dW+adam+polyak & actor-target polyak" : "dW+adam+polyak") : "dW+adam", g, 2, ctr_owed));
   }
   return 0;
 }
 
+// The run-ahead of a pipelined period (see BatchSlot): passes through the actor that later iterations would open with, as extra groups
+// of ONE trunk + tail pair inside the last actor update of the period's first iteration -- the actor does not change any more before
+// those iterations run.  Every pass reads its rows from the ring itself (the sample drawn with sample_ctr + sample_add), the gathers
+// into the batch slots and the tails' draws ride in the trunk launch.  buf: which of ah_z1 / ah_z2 holds the pass's layer outputs.
+struct RunAhead {
+  sactd3_engine* e;
+  TrunkGrp g[5] = {};
+  TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
+  ActorTail t[5] = {};
+  int n = 0;
+  // the next-action pass a'(s') of the iteration that trains on batch slot k, through the actor parameters P (SAC: the online actor,
+  // TD3: the target actor as it will be then); its draws are those of noise counter + noise_add
+  void add_next(int k, const float* P, int buf, int sample_add, int noise_add) {
+    const sactd3_engine::BatchSlot& S = e->bs[k];
+    const bool td3 = e->cfg.prefer_td3_over_sac;
+    const int mode = (td3 && e->cfg.targ_actor_smoothing) ? 1 : 0;
+    g[n] = TrunkGrp{S.Xn, P, e->ah_z1[buf], e->ah_z2[buf], nullptr, nullptr, nullptr, e->ldc};
+    g[n].ring = true; g[n].sctr_add = sample_add; g[n].ring_idx = S.idx;
+    tk.gather[tk.ngather++] = gather_args(e, e->ring, -1, k, sample_add);
+    if (!td3 || mode == 1) { tk.noise[tk.nnoise] = noise_job(e, SACTD3_SITE_CRITIC, 0u, noise_add, e->B); tk.noise[tk.nnoise++].eps = S.eps_c; }
+    t[n] = tail_args(e, e->ah_z2[buf], P, e->B, mode, 0, SACTD3_SITE_CRITIC, 0u, S.Xn, e->ldc, e->o, S.logp_n);
+    t[n].eps = S.eps_c; t[n].ctr_add = noise_add;
+    ++n;
+  }
+  // the first actor update's policy pass pi(s) of the iteration that trains on batch slot k (behind add_next(k, ...): the same sample,
+  // that gather fills S.X); it keeps its stores for the backward pass
+  void add_policy(int k, int buf, int sample_add, int noise_add) {
+    const sactd3_engine::BatchSlot& S = e->bs[k];
+    g[n] = TrunkGrp{S.X, e->Pa, e->ah_z1[buf], e->ah_z2[buf], e->a_xh1, e->a_h1, e->a_rs1, 0};
+    g[n].ring = true; g[n].sctr_add = sample_add; g[n].ring_idx = S.idx;
+    if (!e->cfg.prefer_td3_over_sac) tk.noise[tk.nnoise++] = noise_job(e, SACTD3_SITE_ACTOR0, 16u, noise_add, e->B);
+    t[n] = tail_args(e, e->ah_z2[buf], e->Pa, e->B, 0, 1, SACTD3_SITE_ACTOR0, 16u, e->Xp, e->ldc, e->o, e->logp_pi);
+    t[n].obs_src = S.X; t[n].lds = e->ldc; t[n].ctr_add = noise_add;      // Xp = [s | pi(s)]
+    ++n;
+  }
+  // the trunk + tail pair; tail 0 moves the sample counter past the `ahead` samples drawn here
+  int launch(EnqCtx& x, int ahead) {
+    bool eps_ready = false;
+    if (tk.nnoise) tk.noise_taken = &eps_ready;
+    if (tk.ngather) { tk.force_ks = 4; tk.no_tiled64 = true; }      // (the launch shapes of the single-net passes: ring rows, riding gathers, bit-equal results)
+    RCCHK(enqueue_trunk(x, e->ldc, e->o, e->B, e->La, 0, n, 1, g, tk));
+    if (ahead) { t[0].tick = &e->ctl->sample_ctr; t[0].tick_add = ahead - 1; }      // every reader of the index streams (the trunk launch above) is done
+    for (int i = 0; i < n; ++i) t[i].eps_ready = eps_ready;
+    return launch_tails(x, tk.ngather ? 5 : 1, t, n);
+  }
+};
+
 // agents/agent.py:244-318.  j = index of this actor update inside the iteration (selects the noise buffers).
-// head_done: this update's policy sample was already produced by the previous update's dual tail (fused iteration);
-// merge_next: produce the NEXT update's policy sample together with this update's temperature draw.
-// polyak_targ: (TD3, last actor update of a fused iteration) lerp the actor target towards the freshly stepped actor in the same
-// kernel that applies the step (agents/agent.py:331 after :286)
-// defer_alpha: (last actor update of an iteration that is followed by another one in the same graph) leave the temperature step
-// to the next iteration's opening launch
-// ahead: (pipelined period, SAC with autotune, last actor update of the period's first iteration) the sampling, gather and
-// next-action pass a' ~ pi(s') of the `ahead` critic-only iterations that follow, into batch slots 1 .. ahead: the actor does not
-// change any more before they run, so their passes ride in this update's last trunk / tail launches (the temperature draw's) as
-// extra groups -- those iterations then start at their twin-critic trunk (enqueue_update_qnets, pre_sampled).
-// chain_slot >= 0: ... and the opening pair of the NEXT period's first iteration into that batch slot (see BatchSlot, chain_ready).
-// slot: the batch slot this iteration trains on.
-static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool head_done = false, bool merge_next = false, float* polyak_targ = nullptr,
-                                bool defer_alpha = false, int ahead = 0, int chain_slot = -1, int slot = 0) {
+// fused == false: the API path -- one update on its own (a default place: batch slot 0, nothing ahead, nothing deferred).
+static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fused) {
+  sactd3_engine* e = x.e;
   const sactd3_config& c = e->cfg;
   const int B = e->B, ln = c.layer_norm, td3 = c.prefer_td3_over_sac, nq = e->nq_actor;
   const long BH = (long)B * HID;
+  const bool last = j + 1 == c.actor_update_delay, can_merge = fused && !td3 && c.autotune;
+  // head_done: this update's policy sample was already produced -- by the opening pair (first update), or by the previous update's dual tail
+  const bool head_done = j == 0 ? fused && (it.pre_sampled || opening_merges_policy(e)) : can_merge;
+  const bool merge_next = can_merge && !last;      // produce the NEXT update's policy sample together with this update's temperature draw
+  // (TD3, last actor update of a fused iteration) lerp the actor target towards the freshly stepped actor in the same kernel that applies
+  // the step (agents/agent.py:331 after :286)
+  float* const polyak_targ = (it.targets && td3 && last) ? e->Ta : nullptr;
+  // (last actor update of an iteration that is followed by another one in the same graph) leave the temperature step to the next
+  // iteration's opening launch, when that launch can carry it
+  const bool defer_alpha = last && it.more && !td3 && (it.ahead > 0 || opening_trunk_carries_alpha(e));
+  // (last actor update) the run-ahead of a pipelined period, see RunAhead and IterPlace -- SAC: in this update's last trunk / tail
+  // launches (the temperature draw's), TD3: as a pair of its own
+  const int ahead = last ? it.ahead : 0, chain_slot = last ? it.chain_slot : -1;
   const int sb_a = SACTD3_SITE_ACTOR0 + (j & 1), sb_l = SACTD3_SITE_ALPHA0 + (j & 1);
   const bool clip = c.clip_norm > 0.f;
-  const float* SX = e->bs[slot].X;          // the observations of the batch this iteration trains on
+  const float* SX = e->bs[it.slot].X;       // the observations of the batch this iteration trains on
   const bool small_head = e->nh <= 8 && e->a <= 8;      // single-wave 4-row head backward (k_actor_head_bwd_s)
-  e->node_role = (j & 1) ? "actor1/policy" : "actor0/policy";
+  x.role = (j & 1) ? "actor1/policy" : "actor0/policy";
   if (!head_done) {  // a_pi, logp = pi(s) with stores for the backward pass
     const TrunkGrp g{SX, e->Pa, e->a_z1, e->a_z2, e->a_xh1, e->a_h1, e->a_rs1};
     TrunkTicks tk{&e->ctl->t_a, nullptr, e->ctl->adam_a, e->ctl->pw_a, c.actor_lr};
     bool eps_ready = false;
     if (!td3) { tk.nnoise = 1; tk.noise[0] = noise_job(e, sb_a, 16u, 0, B); tk.noise_taken = &eps_ready; }
-    RCCHK(enqueue_trunk(e, s, e->ldc, e->o, B, e->La, 0, 1, 1, &g, tk));
+    RCCHK(enqueue_trunk(x, e->ldc, e->o, B, e->La, 0, 1, 1, &g, tk));
     ActorTail t = tail_args(e, e->a_z2, e->Pa, B, 0, 1, sb_a, 16u, e->Xp, e->ldc, e->o, e->logp_pi);
     t.obs_src = SX; t.lds = e->ldc;   // Xp = [s | pi(s)]
     t.eps_ready = eps_ready;
-    RCCHK(launch_tail(e, s, t));
+    RCCHK(launch_tail(x, t));
   }
-  e->node_role = (j & 1) ? "actor1/q(s,pi)" : "actor0/q(s,pi)";
+  x.role = (j & 1) ? "actor1/q(s,pi)" : "actor0/q(s,pi)";
   {  // Q_i(s, a_pi) through the online critics as constants (agent.py:272-278)
     const TrunkGrp g{e->Xp, e->Pc, e->c_z1, e->c_z2, e->c_xh1, e->c_h1, e->c_rs1};
     TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
-    if (e->alpha_pending) { tk.alpha = &e->pending_alpha; e->alpha_pending = false; }   // the previous update's temperature step
-    RCCHK(enqueue_trunk(e, s, e->ldc, e->o + e->a, B, e->Lc, e->Lc.size, 1, nq, &g, tk));
+    if (x.alpha_pending) { tk.alpha = &x.alpha; x.alpha_pending = false; }   // the previous update's temperature step
+    RCCHK(enqueue_trunk(x, e->ldc, e->o + e->a, B, e->Lc, e->Lc.size, 1, nq, &g, tk));
   }
-  e->node_role = (j & 1) ? "actor1/loss+backward" : "actor0/loss+backward";
+  x.role = (j & 1) ? "actor1/loss+backward" : "actor0/loss+backward";
   const bool fused_qtail_nn = B < BIG_BATCH;
   // dQ/da finished inside the two fused launches around it (QaFold): narrow heads, ac_dim <= 7
   const bool qa_fold = fused_qtail_nn && small_head && e->a <= 7;    // (small_head: k_headbwd_nn is the consumer)
@@ -948,7 +1036,7 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
     NnArgs g{};
     g.dY = e->c_dz2; g.dy_ns = BH; g.Wt = e->Pc + e->Lc.W2; g.ldw = HID; g.p_ns = e->Lc.size; g.k_off = 0;
     g.dX = e->c_dh1; g.ldx = HID; g.dx_ns = BH; g.M = B; g.Kout = HID;
-    RCCHK(launch_nn(e, s, "k_nn.dh1", g, nq));
+    RCCHK(launch_nn(x, "k_nn.dh1", g, nq));
   }
   if (!qa_fold) {
     LnBwd l{};
@@ -988,7 +1076,7 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
   if (!fused_head_nn) {
     NnArgs g{};
     g.dY = e->a_dz2; g.Wt = e->Pa + e->La.W2; g.ldw = HID; g.k_off = 0; g.dX = e->a_dh1; g.ldx = HID; g.M = B; g.Kout = HID;
-    RCCHK(launch_nn(e, s, "k_nn.dh1", g, 1));
+    RCCHK(launch_nn(x, "k_nn.dh1", g, 1));
   }
   if (!fold_ln1) {
     LnBwd l{};
@@ -1017,7 +1105,7 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
     g.b1 = c.adam_beta1; g.b2 = c.adam_beta2; g.eps = c.adam_eps;
     g.loss_part = e->part_sa; g.loss_n = e->nblk4; g.loss_stride = 2; g.loss_off = 1; g.loss_scale = 1.0f / (float)B;
     g.loss_dst = &e->ctl->metrics[SACTD3_M_ACTOR_LOSS]; g.tick = (td3 && !clip) ? &e->ctl->noise_ctr : nullptr;
-    RCCHK(launch_tn(e, s, clip ? "dW" : (polyak_targ ? "dW+adam+polyak" : "dW+adam"), g, 1));
+    RCCHK(launch_tn(x, clip ? "dW" : (polyak_targ ? "dW+adam+polyak" : "dW+adam"), g, 1));
   }
   if (clip) {
     NormArgs n{e->Ga, (long)e->La.size, c.clip_norm, e->gscale};
@@ -1026,7 +1114,7 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
     a.gscale = e->gscale;
     a.targ = polyak_targ; a.tau = c.polyak;
     a.tick = td3 ? &e->ctl->noise_ctr : nullptr;
-    RCCHK(launch_adam(e, s, a));
+    RCCHK(launch_adam(x, a));
   }
   if (td3 && (ahead > 0 || chain_slot >= 0)) {
     // TD3, pipelined period (see BatchSlot): the online actor is final until the next period's actor updates, and the TARGET actor
@@ -1036,47 +1124,17 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
     // as ONE trunk + tail pair.  Streams: iteration k samples with sample_ctr + (k - 1) and draws its smoothing noise with noise
     // counter + (k - 1) (the counter already counts this update's tick; one tick per critic update in between); the next period's
     // first iteration with + ahead -- the values their own opening launches would use.
-    e->node_role = chain_slot >= 0 ? "next-action passes ahead & next period's opening" : "next-action passes ahead";
+    x.role = chain_slot >= 0 ? "next-action passes ahead & next period's opening" : "next-action passes ahead";
     const float* Tk[3] = {e->Ta, e->Ta2, e->Ta3};
-    const int mode = c.targ_actor_smoothing ? 1 : 0;
-    TrunkGrp g[5] = {};
-    TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
-    ActorTail5 T{};
-    bool eps_ready = false;
-    int ng = 0;
-    auto add_next = [&](int slot_k, int order) {
-      const sactd3_engine::BatchSlot& S = e->bs[slot_k];
-      g[ng] = TrunkGrp{S.Xn, Tk[order], e->ah_z1[ng], e->ah_z2[ng], nullptr, nullptr, nullptr, e->ldc};
-      g[ng].ring = true; g[ng].sctr_add = order; g[ng].ring_idx = S.idx;
-      tk.gather[tk.ngather++] = gather_args(e, e->ring, -1, slot_k, order);
-      if (mode == 1) { tk.noise[tk.nnoise] = noise_job(e, SACTD3_SITE_CRITIC, 0u, order, B); tk.noise[tk.nnoise++].eps = S.eps_c; tk.noise_taken = &eps_ready; }
-      T.t[ng] = tail_args(e, e->ah_z2[ng], Tk[order], B, mode, 0, SACTD3_SITE_CRITIC, 0u, S.Xn, e->ldc, e->o, S.logp_n);
-      T.t[ng].eps = S.eps_c; T.t[ng].ctr_add = order;
-      ++ng;
-    };
-    for (int k = 1; k <= ahead; ++k) add_next(k, k - 1);
+    RunAhead ra{e};
+    for (int k = 1; k <= ahead; ++k) ra.add_next(k, Tk[k - 1], k - 1, k - 1, k - 1);
     if (chain_slot >= 0) {
-      add_next(chain_slot, ahead);
-      const sactd3_engine::BatchSlot& S = e->bs[chain_slot];
-      g[ng] = TrunkGrp{S.X, e->Pa, e->ah_z1[ng], e->ah_z2[ng], e->a_xh1, e->a_h1, e->a_rs1, 0};
-      g[ng].ring = true; g[ng].sctr_add = ahead; g[ng].ring_idx = S.idx;
-      T.t[ng] = tail_args(e, e->ah_z2[ng], e->Pa, B, 0, 1, SACTD3_SITE_ACTOR0, 16u, e->Xp, e->ldc, e->o, e->logp_pi);
-      T.t[ng].obs_src = S.X; T.t[ng].lds = e->ldc;                      // Xp = [s | pi(s)] (the gather above has filled S.X)
-      ++ng;
+      ra.add_next(chain_slot, Tk[ahead], ahead, ahead, ahead);
+      ra.add_policy(chain_slot, ahead + 1, ahead, 0);                       // (TD3's policy pass draws nothing)
     }
-    tk.force_ks = 4; tk.no_tiled64 = true;      // (the launch shapes of the single-net passes: ring rows, riding gathers, bit-equal results)
-    RCCHK(enqueue_trunk(e, s, e->ldc, e->o, B, e->La, 0, ng, 1, g, tk));
-    if (ahead) { T.t[0].tick = &e->ctl->sample_ctr; T.t[0].tick_add = ahead - 1; }      // every reader of the index streams is done
-    for (int i = 0; i < ng; ++i) T.t[i].eps_ready = eps_ready;
-    for (int i = ng; i < 5; ++i) T.t[i] = T.t[0];
-    const int rpb = tail_rows_per_block(T.t[0]);
-    T.nb = (B + rpb - 1) / rpb; T.n = ng;
-    const double fl = 2.0 * ng * B * (double)HID * e->nh;
-    const double by = 4.0 * ng * ((double)B * HID + (double)e->nh * (HID + 1) + 2.0 * HID + (double)B * (3 * e->a + 2)) + (chain_slot >= 0 ? 8.0 * (double)B * (HID + e->o) : 0.0);
-    if (rpb == 4) LAUNCH("k_actor_tail_s5<4>", fl, by, k_actor_tail_s5<4>, dim3(ng * T.nb), dim3(64), T);
-    else LAUNCH("k_actor_tail5", fl, by, k_actor_tail5, dim3(ng * T.nb), dim3(256), T);
+    RCCHK(ra.launch(x, ahead));
   }
-  e->node_role = (j & 1) ? "actor1/alpha" : "actor0/alpha";
+  x.role = (j & 1) ? "actor1/alpha" : "actor0/alpha";
   if (!td3) {
     if (c.autotune && merge_next) {
       // The temperature draw (agent.py:297-299) and the next actor update's policy sample (agent.py:254) both go through
@@ -1088,77 +1146,39 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
       TrunkTicks tk{&e->ctl->t_a, nullptr, e->ctl->adam_a, e->ctl->pw_a, c.actor_lr};
       bool eps_ready = false;
       tk.nnoise = 2; tk.noise[0] = noise_job(e, sb_a_next, 16u, 1, B); tk.noise[1] = noise_job(e, sb_l, 32u, 0, B); tk.noise_taken = &eps_ready;
-      RCCHK(enqueue_trunk(e, s, e->ldc, e->o, B, e->La, 0, 1, 1, &g, tk));
+      RCCHK(enqueue_trunk(x, e->ldc, e->o, B, e->La, 0, 1, 1, &g, tk));
       ActorTail t = tail_args(e, e->a_z2, e->Pa, B, 0, 1, sb_a_next, 16u, e->Xp, e->ldc, e->o, e->logp_pi);
       t.obs_src = SX; t.lds = e->ldc; t.ctr_add = 1;
       t.dual = 1; t.site_buf2 = sb_l; t.site_code2 = 32u; t.eps2 = e->eps[sb_l]; t.logp2 = e->logp_al;
       t.eps_ready = eps_ready;
-      RCCHK(launch_tail(e, s, t));
-    } else if (c.autotune) {  // fresh draw through the already-updated actor (agent.py:297-299)
-      TrunkGrp g[5] = {{e->bs[slot].X, e->Pa, e->a_z1, e->a_z2, nullptr, nullptr, nullptr}, {}, {}, {}, {}};
-      TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
-      bool eps_ready = false;
-      tk.nnoise = 1; tk.noise[0] = noise_job(e, sb_l, 32u, 0, B); tk.noise_taken = &eps_ready;
-      ActorTail5 T{};
-      int ng = 1;
-      // The noise counter stands at N + (this update's index + 1) here (one tick by the critic update, one per finished temperature
-      // step), the sample counter already counts this iteration.  Iteration k of the period (k = 1 .. ahead): its sample is the
-      // one drawn with sample_ctr + (k - 1), its critic-site draws those of noise counter + k (the tick owed by this update's
-      // deferred temperature step, one per critic update in between) -- exactly what its own opening launches would have used.
-      for (int k = 1; k <= ahead; ++k) {
-        const sactd3_engine::BatchSlot& S = e->bs[k];
-        g[ng] = TrunkGrp{S.Xn, e->Pa, e->ah_z1[k - 1], e->ah_z2[k - 1], nullptr, nullptr, nullptr, e->ldc};
-        g[ng].ring = true; g[ng].sctr_add = k - 1; g[ng].ring_idx = S.idx;
-        tk.gather[tk.ngather++] = gather_args(e, e->ring, -1, k, k - 1);
-        tk.noise[tk.nnoise] = noise_job(e, SACTD3_SITE_CRITIC, 0u, k, B); tk.noise[tk.nnoise++].eps = S.eps_c;
-        T.t[ng] = tail_args(e, e->ah_z2[k - 1], e->Pa, B, 0, 0, SACTD3_SITE_CRITIC, 0u, S.Xn, e->ldc, e->o, S.logp_n);
-        T.t[ng].eps = S.eps_c; T.t[ng].ctr_add = k;
-        ++ng;
-      }
+      RCCHK(launch_tail(x, t));
+    } else if (c.autotune) {  // fresh draw through the already-updated actor (agent.py:297-299): group 0 / tail 0 of the pair ...
+      RunAhead ra{e};
+      ra.g[0] = TrunkGrp{SX, e->Pa, e->a_z1, e->a_z2, nullptr, nullptr, nullptr};
+      ra.tk.noise[ra.tk.nnoise++] = noise_job(e, sb_l, 32u, 0, B);
+      ra.t[0] = tail_args(e, e->a_z2, e->Pa, B, 0, 0, sb_l, 32u, e->act_scratch, e->a4, 0, e->logp_al);
+      ra.n = 1;
+      // ... that also holds the run-ahead (SAC, pipelined period).  The noise counter stands at N + (this update's index + 1) here
+      // (one tick by the critic update, one per finished temperature step), the sample counter already counts this iteration.
+      // Iteration k of the period (k = 1 .. ahead): its sample is the one drawn with sample_ctr + (k - 1), its critic-site draws those
+      // of noise counter + k (the tick owed by this update's deferred temperature step, one per critic update in between) -- exactly
+      // what its own opening launches would have used.
+      for (int k = 1; k <= ahead; ++k) ra.add_next(k, e->Pa, k - 1, k - 1, k);
       // ... and the opening pair of the NEXT period's first iteration, into batch slot `chain_slot`: sample sample_ctr + ahead,
       // critic-site draws of noise counter + ahead + 1 (where that period starts), policy draws (site 16) one further -- the values
-      // its own opening launches use (enqueue_update_qnets: merge_policy); the policy pass keeps its stores for the backward pass
+      // its own opening launches use (enqueue_opening_pair: merge_policy)
       if (chain_slot >= 0) {
-        const sactd3_engine::BatchSlot& S = e->bs[chain_slot];
-        g[ng] = TrunkGrp{S.Xn, e->Pa, e->ah_z1[2], e->ah_z2[2], nullptr, nullptr, nullptr, e->ldc};
-        g[ng].ring = true; g[ng].sctr_add = ahead; g[ng].ring_idx = S.idx;
-        g[ng + 1] = TrunkGrp{S.X, e->Pa, e->ah_z1[3], e->ah_z2[3], e->a_xh1, e->a_h1, e->a_rs1, 0};
-        g[ng + 1].ring = true; g[ng + 1].sctr_add = ahead; g[ng + 1].ring_idx = S.idx;
-        tk.gather[tk.ngather++] = gather_args(e, e->ring, -1, chain_slot, ahead);
-        tk.noise[tk.nnoise] = noise_job(e, SACTD3_SITE_CRITIC, 0u, ahead + 1, B); tk.noise[tk.nnoise++].eps = S.eps_c;
-        tk.noise[tk.nnoise++] = noise_job(e, SACTD3_SITE_ACTOR0, 16u, ahead + 2, B);
-        T.t[ng] = tail_args(e, e->ah_z2[2], e->Pa, B, 0, 0, SACTD3_SITE_CRITIC, 0u, S.Xn, e->ldc, e->o, S.logp_n);
-        T.t[ng].eps = S.eps_c; T.t[ng].ctr_add = ahead + 1;
-        T.t[ng + 1] = tail_args(e, e->ah_z2[3], e->Pa, B, 0, 1, SACTD3_SITE_ACTOR0, 16u, e->Xp, e->ldc, e->o, e->logp_pi);
-        T.t[ng + 1].obs_src = S.X; T.t[ng + 1].lds = e->ldc; T.t[ng + 1].ctr_add = ahead + 2;      // Xp = [s | pi(s)] (the gather above has filled S.X)
-        ng += 2;
+        ra.add_next(chain_slot, e->Pa, 2, ahead, ahead + 1);
+        ra.add_policy(chain_slot, 3, ahead, ahead + 2);
       }
-      if (ng > 1) {
-        tk.force_ks = 4; tk.no_tiled64 = true;
-        e->node_role = chain_slot >= 0 ? "alpha & next-action passes ahead & next period's opening" : "alpha & next-action passes ahead";
-      }
-      RCCHK(enqueue_trunk(e, s, e->ldc, e->o, B, e->La, 0, ng, 1, g, tk));
-      ActorTail t = tail_args(e, e->a_z2, e->Pa, B, 0, 0, sb_l, 32u, e->act_scratch, e->a4, 0, e->logp_al);
-      t.eps_ready = eps_ready;
-      if (ng == 1) RCCHK(launch_tail(e, s, t));
-      else {
-        if (ahead) { t.tick = &e->ctl->sample_ctr; t.tick_add = ahead - 1; }      // every reader of the index streams (the trunk launch above) is done
-        T.t[0] = t;
-        for (int i = 1; i < ng; ++i) T.t[i].eps_ready = eps_ready;
-        for (int i = ng; i < 5; ++i) T.t[i] = T.t[0];                               // (never run: blocks exist for n tails only)
-        const int rpb = tail_rows_per_block(t);
-        T.nb = (B + rpb - 1) / rpb; T.n = ng;
-        const double fl = 2.0 * ng * B * (double)HID * t.L.nh;
-        const double by = 4.0 * ng * ((double)B * HID + (double)t.L.nh * (HID + 1) + 2.0 * HID + (double)B * (3 * e->a + 2)) + (chain_slot >= 0 ? 8.0 * (double)B * (HID + e->o) : 0.0);
-        if (rpb == 4) LAUNCH("k_actor_tail_s5<4>", fl, by, k_actor_tail_s5<4>, dim3(ng * T.nb), dim3(64), T);
-        else LAUNCH("k_actor_tail5", fl, by, k_actor_tail5, dim3(ng * T.nb), dim3(256), T);
-      }
+      if (ra.n > 1) x.role = chain_slot >= 0 ? "alpha & next-action passes ahead & next period's opening" : "alpha & next-action passes ahead";
+      RCCHK(ra.launch(x, ahead));
     }
     AlphaArgs al{};
     al.logp = e->logp_al; al.B = B; al.targ_ent = -(float)e->a; al.autotune = c.autotune; al.la = e->la; al.ctl = e->ctl;
     al.lr = c.log_alpha_lr; al.b1 = c.adam_beta1; al.b2 = c.adam_beta2; al.eps = c.adam_eps; al.tick = &e->ctl->noise_ctr;
-    if (merge_next) { e->pending_alpha = al; e->alpha_pending = true; }   // rides in the next update's critic-trunk launch
-    else if (defer_alpha) { al.tick = nullptr; e->pending_alpha = al; e->alpha_pending = true; e->alpha_tick_owed = true; }
+    if (merge_next) { x.alpha = al; x.alpha_pending = true; }   // rides in the next update's critic-trunk launch
+    else if (defer_alpha) { al.tick = nullptr; x.alpha = al; x.alpha_pending = true; x.alpha_tick_owed = true; }
     else {
       LAUNCH("k_alpha_step", 0.0, 4.0 * B, k_alpha_step, dim3(1), dim3(256), al);
     }
@@ -1166,73 +1186,55 @@ static int enqueue_update_actor(sactd3_engine* e, hipStream_t s, int j, bool hea
   return 0;
 }
 
+static int launch_tails5(EnqCtx& x, const ActorTail5& T, double fl, double by, dim3 grid, dim3 block) {      // (see launch_tails)
+  if (block.x == 64) LAUNCH("k_actor_tail_s5<4>", fl, by, k_actor_tail_s5<4>, grid, block, T);
+  else LAUNCH("k_actor_tail5", fl, by, k_actor_tail5, grid, block, T);
+  return 0;
+}
+
 // agents/agent.py:328-331
-static int enqueue_polyak(sactd3_engine* e, hipStream_t s, bool critics, bool actor) {
-  e->node_role = "targets";
+enum { POLYAK_CRITICS = 1, POLYAK_ACTOR = 2 };
+static int enqueue_polyak(EnqCtx& x, int which) {
+  sactd3_engine* e = x.e;
+  x.role = "targets";
   PolyakArgs p{};
   p.tau = e->cfg.polyak;
-  if (critics) { p.t0 = e->Tc; p.p0 = e->Pc; p.n0 = 2L * e->Lc.size; }
-  if (actor) { p.t1 = e->Ta; p.p1 = e->Pa; p.n1 = e->La.size; }
+  if (which & POLYAK_CRITICS) { p.t0 = e->Tc; p.p0 = e->Pc; p.n0 = 2L * e->Lc.size; }
+  if (which & POLYAK_ACTOR) { p.t1 = e->Ta; p.p1 = e->Pa; p.n1 = e->La.size; }
   const long n = p.n0 + p.n1;
   if (n == 0) return 0;
   LAUNCH("k_polyak", 0.0, 12.0 * n, k_polyak, dim3((unsigned)std::min<long>(512, (n / 4 + 255) / 256)), dim3(256), p);
   return 0;
 }
 
-// orchestrator.py:337-352 as one sequence
-// slot / pre_sampled / ahead: the pipelined form of a period graph (period_is_pipelined): iteration i of the period trains on batch
-// slot i; the first one (with the actor updates) also runs the sampling + next-action passes of the `ahead` iterations behind it,
-// which are then `pre_sampled`.
-// chain_slot / policy_pre: ... and, chained periods, the opening pair of the next period's first iteration into batch slot chain_slot;
-// policy_pre = this iteration's own opening pair (sample, next-action pass, the first actor update's policy pass) is already there.
-static int enqueue_step(sactd3_engine* e, hipStream_t s, bool do_actor, bool do_polyak, bool next_in_same_graph = false,
-                        int slot = 0, bool pre_sampled = false, int ahead = 0, int chain_slot = -1, bool policy_pre = false) {
+// orchestrator.py:337-352 as one sequence (see IterPlace)
+static int enqueue_step(EnqCtx& x, const IterPlace& it) {
+  sactd3_engine* e = x.e;
   const bool td3 = e->cfg.prefer_td3_over_sac;
-  e->node_role = "sample";
-  if (!pre_sampled && !opening_trunk_gathers(e)) RCCHK(enqueue_gather(e, s, e->ring, -1));   // otherwise the gather is inside the first trunk kernel
-  // SAC: critic targets are lerped towards the freshly stepped critics inside the Adam kernel (same element,
-  // same order as agent.py:328 after :236); TD3 also needs the actor target, done after the actor updates.
+  x.role = "sample";
+  if (!it.pre_sampled && !opening_trunk_gathers(e)) RCCHK(enqueue_gather(x, e->ring, -1));   // otherwise the gather is inside the first trunk kernel
   // Target updates (agents/agent.py:320-331) are folded into the kernels that apply the optimiser steps: the critic targets are
   // lerped towards the freshly stepped critics inside the critics' Adam epilogue (same element, same order as :328 after :236;
   // nothing between there and the end of the iteration reads the targets).  TD3 also moves the actor target every iteration:
   // in the last actor update's Adam epilogue when the iteration has actor updates, otherwise -- the actor did not change -- as a
   // few extra blocks of the critics' weight-gradient launch.
-  bool policy_done = false, actor_targ_done = false;
-  const bool actor_targ = do_polyak && td3;
-  RCCHK(enqueue_update_qnets(e, s, true, do_polyak ? e->Tc : nullptr, do_actor, &policy_done, actor_targ && !do_actor, &actor_targ_done, slot, pre_sampled,
-                             policy_pre ? 2 : 0));
-  if (policy_pre) policy_done = true;
-  if (do_actor) {
-    const int n = e->cfg.actor_update_delay;
-    const bool can_merge = !td3 && e->cfg.autotune;
-    for (int j = 0; j < n; ++j) {
-      const bool last = j + 1 == n;
-      float* pt = nullptr;
-      if (actor_targ && last) { pt = e->Ta; actor_targ_done = true; }
-      // the last temperature step can wait for the next iteration's opening trunk launch when that launch can carry it
-      const bool defer = last && next_in_same_graph && !td3 && (ahead > 0 || opening_trunk_carries_alpha(e));
-      RCCHK(enqueue_update_actor(e, s, j, j == 0 ? policy_done : can_merge, can_merge && !last, pt, defer, last ? ahead : 0, last ? chain_slot : -1, slot));
-    }
-  }
-  if (actor_targ && !actor_targ_done) RCCHK(enqueue_polyak(e, s, false, true));
+  RCCHK(enqueue_update_qnets(x, it, true));
+  if (it.actor)
+    for (int j = 0; j < e->cfg.actor_update_delay; ++j) RCCHK(enqueue_update_actor(x, it, j, true));
+  else if (it.targets && td3 && !actor_target_rides(e)) RCCHK(enqueue_polyak(x, POLYAK_ACTOR));
   return 0;
 }
 
-template <class F>
-static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&& enqueue, bool launch = true, hipStream_t on = nullptr);
-template <class F>
-static int run_graph(sactd3_engine* e, int which, F&& enqueue, bool launch = true) {
-  return run_graph_slot(e, &e->graphs[which], &e->graph_nodes[which], enqueue, launch);
-}
 // launch == false: capture + instantiate only (sactd3_instantiate_graphs); on: the stream to capture and launch on (default: the learner's)
 template <class F>
-static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&& enqueue, bool launch, hipStream_t on) {
+static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&& enqueue, bool launch = true, hipStream_t on = nullptr) {
   const hipStream_t st = on ? on : e->stream;
-  if (!e->cfg.use_graphs) return launch ? enqueue(st) : 0;
+  auto sequence = [&]() { EnqCtx x{e, st}; return enqueue_end(x, enqueue(x)); };      // a context per sequence: begins and ends here
+  if (!e->cfg.use_graphs) return launch ? sequence() : 0;
   if (!*slot) {
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue(st);
+    const int rc = sequence();
     hipError_t he = hipStreamEndCapture(st, &g);
     if (rc != 0) { if (g) hipGraphDestroy(g); return rc; }
     if (he != hipSuccess) return e->fail(SACTD3_EHIP, "hipStreamEndCapture", he);
@@ -1248,6 +1250,10 @@ static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&
   }
   if (launch) HIPCHK(hipGraphLaunch(*slot, st));
   return 0;
+}
+template <class F>
+static int run_graph(sactd3_engine* e, int which, F&& enqueue, bool launch = true) {
+  return run_graph_slot(e, &e->graphs[which], &e->graph_nodes[which], enqueue, launch);
 }
 
 // A learner-stream call that writes the actor parameters (what the acting kernels read through that stream) is about to be issued:
@@ -1640,7 +1646,7 @@ int sactd3_rb_sample(sactd3_engine* e) {
   CHAIN_BREAK(e);
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample: buffer is empty");
   e->cur_slot = 0;
-  RCCHK(enqueue_gather(e, e->stream, e->ring, -1));
+  RCCHK(gather_now(e, e->ring, -1));
   hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
   HIPCHK(hipGetLastError());
   return 0;
@@ -1660,7 +1666,7 @@ int sactd3_rb_sample_with_indices(sactd3_engine* e, const int64_t* idx, int n) {
   HIPCHK(hipMemcpy(e->idx, h.data(), sizeof(int) * n, hipMemcpyHostToDevice));
   e->cur_slot = 0;
   RCCHK(set_flag(e, &e->ctl->inject_idx, 1));
-  RCCHK(enqueue_gather(e, e->stream, e->ring, -1));
+  RCCHK(gather_now(e, e->ring, -1));
   return set_flag(e, &e->ctl->inject_idx, 0);
 }
 
@@ -1679,7 +1685,7 @@ int sactd3_load_batch(sactd3_engine* e, const float* obs, const float* act, cons
   HIPCHK(hipMemcpy(e->stage_dev, e->h_batch, sizeof(float) * (size_t)n * e->rec_f, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(e->idx, h.data(), sizeof(int) * n, hipMemcpyHostToDevice));
   RCCHK(set_flag(e, &e->ctl->inject_idx, 1));
-  RCCHK(enqueue_gather(e, e->stream, e->stage_dev, n));
+  RCCHK(gather_now(e, e->stage_dev, n));
   return set_flag(e, &e->ctl->inject_idx, 0);
 }
 
@@ -1763,7 +1769,7 @@ int sactd3_update_qnets(sactd3_engine* e) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   e->cur_slot = 0;
-  RCCHK(run_graph(e, G_Q, [&](hipStream_t s) { return enqueue_update_qnets(e, s, false, nullptr); }));
+  RCCHK(run_graph(e, G_Q, [&](EnqCtx& x) { return enqueue_update_qnets(x, IterPlace{}, false); }));
   e->grads_stale[0] = false;
   return 0;
 }
@@ -1772,7 +1778,7 @@ int sactd3_update_actor(sactd3_engine* e) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   RCCHK(actor_write_begin(e));
-  RCCHK(run_graph(e, G_A, [&](hipStream_t s) { return enqueue_update_actor(e, s, 0); }));
+  RCCHK(run_graph(e, G_A, [&](EnqCtx& x) { return enqueue_update_actor(x, IterPlace{}, 0, false); }));
   e->grads_stale[1] = false;
   return 0;
 }
@@ -1781,7 +1787,8 @@ int sactd3_update_targ_nets(sactd3_engine* e, int64_t qnet_updates_so_far) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   const bool td3 = e->cfg.prefer_td3_over_sac;
-  if (td3 || qnet_updates_so_far % e->cfg.crit_targ_update_freq == 0) return enqueue_polyak(e, e->stream, true, td3);
+  EnqCtx x{e, e->stream};
+  if (td3 || qnet_updates_so_far % e->cfg.crit_targ_update_freq == 0) return enqueue_polyak(x, POLYAK_CRITICS | (td3 ? POLYAK_ACTOR : 0));
   return 0;
 }
 int sactd3_step(sactd3_engine* e, int do_actor) {
@@ -1794,7 +1801,7 @@ int sactd3_step(sactd3_engine* e, int do_actor) {
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
   const int which = G_STEP00 + (act ? 2 : 0) + (polyak ? 1 : 0);
   if (act) RCCHK(actor_write_begin(e));      // (a critic-only iteration touches nothing the acting kernels read: no order with them)
-  RCCHK(run_graph(e, which, [&](hipStream_t s) { return enqueue_step(e, s, act, polyak); }));
+  RCCHK(run_graph(e, which, [&](EnqCtx& x) { return enqueue_step(x, single_iteration(act, polyak)); }));
   e->qnet_updates = updates;
   e->cur_slot = 0;
   e->grads_stale[0] = false;
@@ -1817,48 +1824,38 @@ static bool period_is_pipelined(const sactd3_engine* e) {
   if (c.prefer_td3_over_sac) return c.clip_norm <= 0.f && !actor_dw_is_tiled64(e);
   return c.autotune != 0;
 }
-// variant (pipelined form only): which batch slot the period's first iteration trains on (0: slot 0, 1: slot 3) -- the other one
-// receives the opening pair of the NEXT period, so consecutive periods alternate (chain_ready).  The pipelined form assumes its own
-// opening pair is already in place: sactd3_step_period runs the opening graph first when it is not.
-struct LeanStores {       // scope of a period / cut-short period sequence
-  sactd3_engine* e;
-  explicit LeanStores(sactd3_engine* e_) : e(e_) { e->lean_stores = e->cfg.clip_norm <= 0.f; }
-  ~LeanStores() { e->lean_stores = false; }
-};
 // a period / cut-short period sequence was issued: what debug_read may no longer hand out (sactd3_engine::grads_stale)
 static void mark_grads_stale(sactd3_engine* e) {
   if (e->cfg.clip_norm > 0.f) return;
   e->grads_stale[0] = true;
   if (e->cfg.actor_update_delay > 0) e->grads_stale[1] = true;
 }
-static int enqueue_period(sactd3_engine* e, hipStream_t s, int variant = 0) {
-  const int n = e->cfg.actor_update_delay + 1;
-  LeanStores lean(e);
-  if (!period_is_pipelined(e)) {
-    for (int i = 0; i < n; ++i) RCCHK(enqueue_step(e, s, i == 0 && e->cfg.actor_update_delay > 0, true, i + 1 < n));
-  } else {
-    const int P = variant ? 3 : 0, Pnext = variant ? 0 : 3;
-    RCCHK(enqueue_step(e, s, true, true, true, P, true, n - 1, Pnext, true));
-    for (int i = 1; i < n; ++i) RCCHK(enqueue_step(e, s, false, true, i + 1 < n, i, true));
+// The first m iterations of a period, m = delay + 1: all of it (sactd3_step_period); fewer: the period graph cut short (pipelined form
+// only, sactd3_step_prefix) -- nothing is left behind for a next period.  Pipelined: the iteration with the actor updates on the
+// precomputed opening pair of its slot, with the sampling and next-action passes of the m - 1 critic-only iterations behind it run ahead
+// (and, the whole period, the next period's opening pair into the other slot); then those iterations on slots 1 .. m - 1.
+// variant (pipelined form only): which batch slot the period's first iteration trains on (0: slot 0, 1: slot 3) -- the other one
+// receives the opening pair of the NEXT period, so consecutive periods alternate (chain_ready).  The pipelined form assumes its own
+// opening pair is already in place: sactd3_step_period runs the opening graph first when it is not.
+static int enqueue_period(EnqCtx& x, int variant, int m) {
+  sactd3_engine* e = x.e;
+  const bool pipelined = period_is_pipelined(e), whole = m == e->cfg.actor_update_delay + 1;
+  x.lean_stores = e->cfg.clip_norm <= 0.f;      // (see sactd3_engine::grads_stale)
+  for (int i = 0; i < m; ++i) {
+    IterPlace it;
+    it.actor = i == 0 && e->cfg.actor_update_delay > 0; it.targets = true; it.more = i + 1 < m;
+    if (pipelined) { it.slot = i ? i : (variant ? 3 : 0); it.pre_sampled = true; }
+    if (pipelined && i == 0) { it.ahead = m - 1; it.chain_slot = whole ? (variant ? 0 : 3) : -1; }
+    RCCHK(enqueue_step(x, it));
   }
-  if (e->alpha_pending) return e->fail(SACTD3_ESTATE, "step_period: a deferred temperature step was left over");
   return 0;
 }
-// The first m <= delay iterations of a period (pipelined form): the period graph cut short -- the iteration with the actor updates on
-// the precomputed opening pair of slot P, the sampling and next-action passes of the m - 1 critic-only iterations behind it run ahead,
-// nothing is left behind for a next period.
-static int enqueue_prefix(sactd3_engine* e, hipStream_t s, int variant, int m) {
-  const int P = variant ? 3 : 0;
-  LeanStores lean(e);
-  RCCHK(enqueue_step(e, s, true, true, m > 1, P, true, m - 1, -1, true));
-  for (int i = 1; i < m; ++i) RCCHK(enqueue_step(e, s, false, true, i + 1 < m, i, true));
-  if (e->alpha_pending) return e->fail(SACTD3_ESTATE, "step_prefix: a deferred temperature step was left over");
-  return 0;
-}
-// the opening pair of a period's first iteration into batch slot `slot`, without its counter ticks (enqueue_update_qnets, open_mode 1)
-static int enqueue_opening(sactd3_engine* e, hipStream_t s, int slot) {
-  bool policy_done = false;
-  return enqueue_update_qnets(e, s, true, nullptr, true, &policy_done, false, nullptr, slot, false, 1);
+// The opening graph: the opening pair of a period's first iteration into batch slot 0, its counter ticks left to the period graph
+static int enqueue_opening(EnqCtx& x) {
+  if (!opening_merges_policy(x.e)) return x.e->fail(SACTD3_ESTATE, "opening graph: the policy pass did not merge");
+  IterPlace it;
+  it.actor = true; it.pre_sampled = true;
+  return enqueue_opening_pair(x, it, true);
 }
 
 // One period of the actor schedule (orchestrator.py:345-349: iteration i with i % (delay + 1) == 0 runs the actor updates,
@@ -1876,7 +1873,7 @@ int sactd3_step_period(sactd3_engine* e) {
   mark_grads_stale(e);
   if (!period_is_pipelined(e)) {
     e->chain_ready = -1;
-    RCCHK(run_graph(e, G_PERIOD, [&](hipStream_t s) { return enqueue_period(e, s); }));
+    RCCHK(run_graph(e, G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, 0, n); }));
     e->cur_slot = 0;
   } else {
     // chained periods: this period's opening pair is either left over from the previous one (chain_ready names the variant) or is
@@ -1884,8 +1881,8 @@ int sactd3_step_period(sactd3_engine* e) {
     const int v = e->chain_ready >= 0 ? e->chain_ready : 0;
     const bool have = e->chain_ready >= 0;
     e->chain_ready = -1;
-    if (!have) RCCHK(run_graph(e, G_OPENING, [&](hipStream_t s) { return enqueue_opening(e, s, 0); }));
-    RCCHK(run_graph(e, v ? G_PERIOD_B : G_PERIOD, [&](hipStream_t s) { return enqueue_period(e, s, v); }));
+    if (!have) RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }));
+    RCCHK(run_graph(e, v ? G_PERIOD_B : G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, v, n); }));
     e->chain_ready = 1 - v;
     e->cur_slot = n - 1;
   }
@@ -1912,8 +1909,8 @@ int sactd3_step_prefix(sactd3_engine* e, int m) {
   e->chain_ready = -1;
   RCCHK(actor_write_begin(e));
   mark_grads_stale(e);
-  if (!have) RCCHK(run_graph(e, G_OPENING, [&](hipStream_t s) { return enqueue_opening(e, s, 0); }));
-  RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](hipStream_t s) { return enqueue_prefix(e, s, v, m); }));
+  if (!have) RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }));
+  RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](EnqCtx& x) { return enqueue_period(x, v, m); }));
   e->cur_slot = m - 1;
   e->qnet_updates += m;
   return 0;
@@ -1929,16 +1926,16 @@ int sactd3_instantiate_graphs(sactd3_engine* e) {
   for (int act = 0; act < 2; ++act)
     for (int pol = same_branch ? 1 : 0; pol < 2; ++pol) {      // (the variants without the target update exist only when it is gated)
       const bool a = act != 0 && e->cfg.actor_update_delay > 0, py = pol != 0;
-      RCCHK(run_graph(e, G_STEP00 + (a ? 2 : 0) + (py ? 1 : 0), [&](hipStream_t s) { return enqueue_step(e, s, a, py); }, false));
+      RCCHK(run_graph(e, G_STEP00 + (a ? 2 : 0) + (py ? 1 : 0), [&](EnqCtx& x) { return enqueue_step(x, single_iteration(a, py)); }, false));
     }
   if (same_branch && e->cfg.actor_update_delay > 0) {
-    RCCHK(run_graph(e, G_PERIOD, [&](hipStream_t s) { return enqueue_period(e, s, 0); }, false));
+    RCCHK(run_graph(e, G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, 0, e->cfg.actor_update_delay + 1); }, false));
     if (period_is_pipelined(e)) {
-      RCCHK(run_graph(e, G_PERIOD_B, [&](hipStream_t s) { return enqueue_period(e, s, 1); }, false));
-      RCCHK(run_graph(e, G_OPENING, [&](hipStream_t s) { return enqueue_opening(e, s, 0); }, false));
+      RCCHK(run_graph(e, G_PERIOD_B, [&](EnqCtx& x) { return enqueue_period(x, 1, e->cfg.actor_update_delay + 1); }, false));
+      RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }, false));
       for (int m = 1; m <= e->cfg.actor_update_delay && m <= 2; ++m)
         for (int v = 0; v < 2; ++v)
-          RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](hipStream_t s) { return enqueue_prefix(e, s, v, m); }, false));
+          RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](EnqCtx& x) { return enqueue_period(x, v, m); }, false));
     }
   }
   return 0;
@@ -1952,14 +1949,15 @@ int sactd3_instantiate_graphs(sactd3_engine* e) {
 static bool predict_one_block(sactd3_engine* e, int n) {
   return n <= tail_rows_per_block(tail_args(e, e->p_z2, e->Pa, n, 0, 0, SACTD3_SITE_PREDICT, 48u, e->h_act, e->a4, 0, nullptr));
 }
-static int enqueue_predict(sactd3_engine* e, hipStream_t s, int n, int explore) {
+static int enqueue_predict(EnqCtx& x, int n, int explore) {
+  sactd3_engine* e = x.e;
   const bool td3 = e->cfg.prefer_td3_over_sac;
   bool eps_ready = false;
   {
     const TrunkGrp g{e->h_obs, e->Pa, e->p_z1, e->p_z2, nullptr, nullptr, nullptr};
     TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
     if (explore) { tk.nnoise = 1; tk.noise[0] = noise_job(e, SACTD3_SITE_PREDICT, 48u, 0, n); tk.noise_taken = &eps_ready; }
-    RCCHK(enqueue_trunk(e, s, e->ldo, e->o, n, e->La, 0, 1, 1, &g, tk));
+    RCCHK(enqueue_trunk(x, e->ldo, e->o, n, e->La, 0, 1, 1, &g, tk));
   }
   const int mode = td3 ? (explore ? 2 : 0) : (explore ? 0 : 1);
   ActorTail t = tail_args(e, e->p_z2, e->Pa, n, mode, 0, SACTD3_SITE_PREDICT, 48u, e->h_act, e->a4, 0, nullptr);
@@ -1969,9 +1967,9 @@ static int enqueue_predict(sactd3_engine* e, hipStream_t s, int n, int explore) 
   const bool one_block = n <= tail_rows_per_block(t);
   if (explore && one_block) t.tick = &e->ctl->predict_ctr;
   if (one_block) { t.seq = &e->ctl->predict_seq; t.done_flag = e->h_done; }
-  RCCHK(launch_tail(e, s, t));
+  RCCHK(launch_tail(x, t));
   if (explore && !one_block) {
-    hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, s, &e->ctl->predict_ctr, (int*)nullptr);
+    hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, x.s, &e->ctl->predict_ctr, (int*)nullptr);
     HIPCHK(hipGetLastError());
   }
   return 0;
@@ -1986,7 +1984,7 @@ static void predict_stage_obs(sactd3_engine* e, const float* obs, int n) {
 static int predict_launch(sactd3_engine* e, hipStream_t s, int n, int explore) {
   if (e->predict_graphs.empty()) e->predict_graphs.assign(2 * (size_t)(e->maxn + 1), nullptr);
   return run_graph_slot(e, &e->predict_graphs[(size_t)(explore ? 1 : 0) * (e->maxn + 1) + n], nullptr,
-                        [&](hipStream_t st) { return enqueue_predict(e, st, n, explore); }, true, s);
+                        [&](EnqCtx& x) { return enqueue_predict(x, n, explore); }, true, s);
 }
 // completion: a single-block tail publishes the call's sequence number `want` to a pinned host word after its last store; spin on
 // it (a stream synchronisation costs a marker packet and a signal wake-up on top of the kernels).  Anything unexpected, or a
@@ -2171,17 +2169,18 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
   HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1));
   int rc = 0;
   auto body = [&]() -> int {
+    EnqCtx x{e, e->stream};
     if (!strcmp(kernel, "gather")) {   // a fresh index draw per launch (k_tick bumps the sample counter): rows come from HBM, not from the caches
-      RCCHK(enqueue_gather(e, e->stream, e->ring, -1));
+      RCCHK(enqueue_gather(x, e->ring, -1));
       hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
       HIPCHK(hipGetLastError());
       return 0;
     }
-    if (!strcmp(kernel, "polyak")) return enqueue_polyak(e, e->stream, true, e->cfg.prefer_td3_over_sac);
+    if (!strcmp(kernel, "polyak")) return enqueue_polyak(x, POLYAK_CRITICS | (e->cfg.prefer_td3_over_sac ? POLYAK_ACTOR : 0));
     if (!strcmp(kernel, "trunk_critics")) {   // the 4-net hidden-layer launch of update_qnets (no state is modified)
       const TrunkGrp g[2] = {{e->Xn, e->Tc, e->t_z1, e->t_z2, nullptr, nullptr, nullptr},
                              {e->X, e->Pc, e->c_z1, e->c_z2, e->c_xh1, e->c_h1, e->c_rs1}};
-      return enqueue_trunk(e, e->stream, e->ldc, e->o + e->a, e->B, e->Lc, e->Lc.size, 2, 2, g, TrunkTicks{nullptr, nullptr, nullptr, nullptr, 0.f});
+      return enqueue_trunk(x, e->ldc, e->o + e->a, e->B, e->Lc, e->Lc.size, 2, 2, g, TrunkTicks{nullptr, nullptr, nullptr, nullptr, 0.f});
     }
     return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics)");
   };
@@ -2214,18 +2213,19 @@ int sactd3_time_nodes(sactd3_engine* e, int do_actor, int iters, int max_nodes, 
   if (act || period) RCCHK(actor_write_begin(e));
   if (period) mark_grads_stale(e);
   std::vector<NodeInfo> log;
-  auto seq = [&]() -> int { e->node_seq = 0; return period ? enqueue_period(e, e->stream) : enqueue_step(e, e->stream, act, true); };
-  auto done = [&](int rc) { e->node_only = -1; e->node_log = nullptr; e->node_seq = 0; e->node_role = ""; return rc; };
-  e->node_log = &log; e->node_only = 1 << 30;               // list only, launch nothing
-  int rc = seq();
-  e->node_log = nullptr;
-  if (rc != 0) return done(rc);
+  auto seq = [&](int only, std::vector<NodeInfo>* into = nullptr) -> int {      // the sequence with launch `only` alone issued (-1: all of them)
+    EnqCtx x{e, e->stream};
+    x.node_only = only; x.node_log = into;
+    return enqueue_end(x, period ? enqueue_period(x, 0, e->cfg.actor_update_delay + 1) : enqueue_step(x, single_iteration(act, true)));
+  };
+  int rc = seq(1 << 30, &log);               // list only, launch nothing
+  if (rc != 0) return rc;
   const int n = (int)log.size();
-  if (n > max_nodes) return done(e->fail(SACTD3_EINVAL, "time_nodes: max_nodes too small"));
+  if (n > max_nodes) return e->fail(SACTD3_EINVAL, "time_nodes: max_nodes too small");
   std::string joined;
   for (int k = 0; k < n; ++k) { joined += log[k].name; joined += '\n'; }
   if (names) {
-    if ((int)joined.size() + 1 > names_cap) return done(e->fail(SACTD3_EINVAL, "time_nodes: names buffer too small"));
+    if ((int)joined.size() + 1 > names_cap) return e->fail(SACTD3_EINVAL, "time_nodes: names buffer too small");
     memcpy(names, joined.c_str(), joined.size() + 1);
   }
   hipEvent_t t0, t1;
@@ -2233,15 +2233,13 @@ int sactd3_time_nodes(sactd3_engine* e, int do_actor, int iters, int max_nodes, 
   // clocks up before anything is timed (an engine is usually created just before this call: the GPU has been idle), then
   // every node in 3 batches of `iters` launches, the fastest batch counting (a batch hit by a clock ramp or by another
   // process's work on the card would otherwise show up as a 100x outlier)
-  e->node_only = -1;
-  for (int i = 0; i < 60 && rc == 0; ++i) rc = seq();
+  for (int i = 0; i < 60 && rc == 0; ++i) rc = seq(-1);
   for (int k = 0; k < n && rc == 0; ++k) {
-    e->node_only = k;
-    for (int i = 0; i < 3 && rc == 0; ++i) rc = seq();
+    for (int i = 0; i < 3 && rc == 0; ++i) rc = seq(k);
     float best = 0.f;
     for (int rep = 0; rep < 3 && rc == 0; ++rep) {
       hipEventRecord(t0, e->stream);
-      for (int i = 0; i < iters && rc == 0; ++i) rc = seq();
+      for (int i = 0; i < iters && rc == 0; ++i) rc = seq(k);
       hipEventRecord(t1, e->stream);
       if (hipEventSynchronize(t1) != hipSuccess) rc = e->fail(SACTD3_EHIP, "time_nodes: hipEventSynchronize");
       float ms = 0.f;
@@ -2254,7 +2252,7 @@ int sactd3_time_nodes(sactd3_engine* e, int do_actor, int iters, int max_nodes, 
     if (threads) threads[k] = log[k].threads;
   }
   hipEventDestroy(t0); hipEventDestroy(t1);
-  return done(rc == 0 ? n : rc);
+  return rc == 0 ? n : rc;
 }
 
 int sactd3_time_gather_sweep(sactd3_engine* e, int batch, int iters, float* usec, double* algo_bytes) {

@@ -713,19 +713,38 @@ def test_fused_step_equals_api_sequence(algo, env, B):
         assert np.array_equal(x, y)
 
 
-@pytest.mark.parametrize("algo,env,B", [("sac", "hopper", 256), ("td3", "halfcheetah", 256), ("sac", "humanoid", 1024), ("sac", "hopper", 64),
-                                        ("td3", "humanoid", 1024), ("sac", "sac4", 128), ("td3", "td3_7", 300), ("td3", "td3_2", 64),
-                                        ("sac", "humanoid", 1473), ("sac", "hopper", 3009), ("td3", "halfcheetah", 4095)])
-def test_period_graph_equals_single_iterations(algo, env, B):
-    """sactd3_step_period (3 iterations of the schedule of orchestrator.py:345-349 in ONE graph: actor updates in the first,
-    then two critic-only ones) == three sactd3_step calls, bit for bit; Engine.run_iterations mixes both forms around period
+# (algo, env, B, actor_update_delay, (first iteration, number of iterations))
+PERIOD_CASES = [(algo, env, B, 2, (1, 10)) for algo, env, B in [
+    ("sac", "hopper", 256), ("td3", "halfcheetah", 256), ("sac", "humanoid", 1024), ("sac", "hopper", 64),
+    ("td3", "humanoid", 1024), ("sac", "sac4", 128), ("td3", "td3_7", 300), ("td3", "td3_2", 64),
+    ("sac", "humanoid", 1473), ("sac", "hopper", 3009), ("td3", "halfcheetah", 4095)]]
+# delay 1: the pipelined period with ONE critic-only iteration run ahead; delay 3: the period as four iterations back to back with
+# deferred temperature steps (csrc/engine.hip period_is_pipelined); the smallest batch, where every launch is more than one block
+PERIOD_CASES += [(algo, env, 64, delay, (1, 10)) for delay in (1, 3) for algo, env in (("sac", "hopper"), ("td3", "halfcheetah"))]
+# a period, then step_prefix(1) on the opening pair that period left in the OTHER batch slot (the cut-short period graph of variant 1)
+PERIOD_CASES += [(algo, env, 64, 2, (0, 4)) for algo, env in (("sac", "hopper"), ("td3", "halfcheetah"))]
+
+
+def _period_case_id(case):
+    algo, env, B, delay, span = case
+    return f"{algo}-{env}-{B}" + (f"-delay{delay}" if delay != 2 else "") + (f"-from{span[0]}x{span[1]}" if span != (1, 10) else "")
+
+
+@pytest.mark.parametrize("algo,env,B,delay,span", [pytest.param(*c, id=_period_case_id(c)) for c in PERIOD_CASES])
+def test_period_graph_equals_single_iterations(algo, env, B, delay, span):
+    """sactd3_step_period (delay + 1 iterations of the schedule of orchestrator.py:345-349 in ONE graph: actor updates in the first,
+    then `delay` critic-only ones) == as many sactd3_step calls, bit for bit; Engine.run_iterations mixes both forms around period
     boundaries; with crit_targ_update_freq != 1 (SAC) the period form is refused and run_iterations falls back."""
+    i0, n_iter = span
+    hp = {} if delay == 2 else {"actor_update_delay": delay}
     res = []
     for mode in ("period", "single"):
-        ref, eng, (o, a, bound) = make_pair(algo, env, B, seed=4)
+        ref, eng, (o, a, bound) = make_pair(algo, env, B, seed=4, **hp)
         eng.rb_extend(*[t.numpy() for t in synth_transitions(3000, o, a, bound, seed=23)])
         if mode == "period":
-            assert eng.run_iterations(1, 10) == 11          # iterations 1, 2 singly, periods 3-5 and 6-8, then 9, 10 as a cut-short period
+            # delay 2 from 1: iterations 1, 2 singly, periods 3-5 and 6-8, then 9, 10 as a cut-short period
+            assert eng.run_iterations(i0, n_iter) == i0 + n_iter
+        if mode == "period" and delay == 2 and span == (1, 10):
             eng.instantiate_graphs()                        # (the single iteration with actor updates was not needed so far: count its nodes)
             # SAC (pipelined, chained periods -- csrc/engine.hip BatchSlot / chain_ready): the period's last temperature step rides in the
             # next iteration's first launch (one node fewer); the critic-only iterations' sampling + next-action passes (trunk launch(es)
@@ -752,14 +771,19 @@ def test_period_graph_equals_single_iterations(algo, env, B):
                 # iteration whose opening pair ran ahead (SAC: in the temperature pair, whose step is deferred; TD3: a trunk + tail pair of its own)
                 assert eng.graph_kernel_count(6) == c1 - opening
                 assert eng.graph_kernel_count(7) == c1 - opening + (c0 - opening) + (-1 if algo == "sac" else opening)
-        else:
-            for i in range(1, 11):
-                eng.step(i % 3 == 0)
-        res.append((eng.get_params(_lib.ACTOR), eng.get_params(_lib.CRITICS), eng.get_params(_lib.CRITICS_TARGET), eng.get_params(_lib.ACTOR_TARGET),
-                    eng.get_params(_lib.LOG_ALPHA), eng.read_batch()["index"], eng.get_adam_state(_lib.CRITICS)[2], eng.get_adam_state(_lib.ACTOR)[2]))
+        if mode == "single":
+            for i in range(i0, i0 + n_iter):
+                eng.step(i % (delay + 1) == 0)
+        res.append([eng.get_params(_lib.ACTOR), eng.get_params(_lib.CRITICS), eng.get_params(_lib.CRITICS_TARGET), eng.get_params(_lib.ACTOR_TARGET),
+                    eng.get_params(_lib.LOG_ALPHA), eng.get_adam_state(_lib.CRITICS)[2], eng.get_adam_state(_lib.ACTOR)[2]])
+        if span == (1, 10):
+            res[-1].append(eng.read_batch()["index"])
+        else:   # behind step_prefix(1) on the other slot the engine reports the wrong slot's batch: the metrics instead
+            res[-1].append(np.array(list(eng.read_metrics().values())))
     for x, y in zip(*res):
         assert np.array_equal(x, y)
-    assert res[0][6] == 10 and res[0][7] == 6
+    n_act = delay * len([i for i in range(i0, i0 + n_iter) if i % (delay + 1) == 0])
+    assert res[0][5] == n_iter and res[0][6] == n_act      # counters of orchestrator.py:342,349 (10 and 6 at delay 2 from 1)
     if algo == "sac":
         ref, eng, (o, a, bound) = make_pair(algo, env, 32, crit_targ_update_freq=2)
         eng.rb_fill_synthetic(500)
