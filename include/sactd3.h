@@ -137,6 +137,32 @@ int sactd3_rb_layout(const sactd3_engine* e, int32_t out[4]);
  * variant of BASELINE.json's north_star (not in the reference) all-gathers every rank's new rows over RCCL into one device
  * slab and appends it here with one kernel, no host round trip.  `records` must stay valid until sactd3_sync. */
 int sactd3_rb_extend_device(sactd3_engine* e, const float* records, int n);
+/* ---- the device boundary: the reference's loop hands the agent DEVICE tensors -- rb.extend gets a device TensorDict
+ * (orchestrator.py:100-113), update_qnets / update_actor get a device batch (agents/agent.py:183,245) -- and the two calls below take
+ * them where they are: five arrays in the memory of the engine's device, each with a row stride in elements and a contiguous inner
+ * dimension (rows need not be 16-byte aligned; a [n, 1] or [n] array has width 1).  One kernel launch assembles the records from
+ * them; nothing is copied through the host, the host never waits. */
+typedef struct sactd3_device_fields {     /* device pointers; *_ld = row stride in elements */
+  const float* obs;      int64_t obs_ld;
+  const float* actions;  int64_t actions_ld;
+  const float* rewards;  int64_t rewards_ld;
+  const float* next_obs; int64_t next_obs_ld;
+  const uint8_t* dones;  int64_t dones_ld;  /* any non-zero byte = done (torch.bool storage) */
+} sactd3_device_fields;
+/* flags: order the read against `producer_stream` -- the hipStream_t on which the caller last wrote the arrays and will next overwrite
+ * or free them (NULL = the legacy default stream, which is torch's default stream: the flag is the switch, not the pointer) -- on the GPU:
+ * the learner stream waits for an event recorded on `producer_stream` now, and `producer_stream` then waits for an event recorded behind
+ * the launch, so neither a later write by the caller nor a same-stream reuse of the freed memory overtakes the read.  Without the flag
+ * nothing is inserted: the caller has synchronised and leaves the arrays untouched until sactd3_sync (as for sactd3_rb_extend_device). */
+#define SACTD3_SRC_ORDERED 1
+/* rb.extend (orchestrator.py:100-113) of n >= 0 rows from device fields: same ring state as sactd3_rb_extend of the same rows. */
+int sactd3_rb_extend_fields_device(sactd3_engine* e, const sactd3_device_fields* f, int n, void* producer_stream, int flags);
+/* a caller-owned device batch (agents/agent.py:183,245), n == batch_size: same batch slot, bit for bit, as sactd3_load_batch. */
+int sactd3_load_batch_device(sactd3_engine* e, const sactd3_device_fields* f, int n, void* producer_stream, int flags);
+/* Both: SACTD3_EINVAL for a NULL field, a stride below the field's width, a pointer that is not memory of the engine's device, n out
+ * of range.  Like the other sactd3_rb_* calls they neither wait for nor are waited for by an acting call in flight.
+ * host counters: out = {device-field extends, rows they appended, device batches staged, calls that inserted event waits} */
+int sactd3_boundary_stats(const sactd3_engine* e, int64_t out[4]);
 /* rb.sample(batch_size) (orchestrator.py:338): uniform-with-replacement indices from the engine's
  * Philox stream + gather into the engine-owned batch slot. */
 int sactd3_rb_sample(sactd3_engine* e);
@@ -236,7 +262,8 @@ const char* sactd3_debug_names(void);
 int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
 /* average device time in microseconds of `iters` back-to-back launches of one kernel of the path,
  * measured with hipEvents on the engine's stream: "gather" (a fresh index draw per launch), "polyak", "trunk_critics" (the 4-net
- * hidden-layer launch of update_qnets; on wide inputs it is two launches). [sync] */
+ * hidden-layer launch of update_qnets; on wide inputs it is two launches), "batch_from_fields" / "rb_ingest_fields" (the device-boundary
+ * pack kernels on batch_size / max_envs rows of the engine's own staging slab; they overwrite the batch slot / append to the ring). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

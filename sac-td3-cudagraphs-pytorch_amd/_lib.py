@@ -14,6 +14,7 @@ ACTOR, CRITICS, ACTOR_TARGET, CRITICS_TARGET, LOG_ALPHA = range(5)
 SITE_CRITIC, SITE_ACTOR0, SITE_ACTOR1, SITE_ALPHA0, SITE_ALPHA1, SITE_PREDICT = range(6)
 NUM_METRICS = 8
 ACT_AFTER_ALL = 1   # sactd3_predict_begin flags
+SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device flags
 ESTATE, EINVAL = -3, -1
 
 # every symbol include/sactd3.h declares (tests/test_abi.py checks the header against this list)
@@ -26,6 +27,7 @@ SYMBOLS = [
     "sactd3_read_metrics", "sactd3_sync", "sactd3_debug_read", "sactd3_debug_names", "sactd3_graph_kernel_count",
     "sactd3_time_kernel", "sactd3_time_gather_sweep", "sactd3_time_nodes", "sactd3_rb_layout", "sactd3_rb_extend_device", "sactd3_step_period", "sactd3_step_prefix", "sactd3_instantiate_graphs", "sactd3_device_handles",
     "sactd3_predict_begin", "sactd3_predict_end", "sactd3_acting_stats",
+    "sactd3_rb_extend_fields_device", "sactd3_load_batch_device", "sactd3_boundary_stats",
 ]
 
 
@@ -40,6 +42,11 @@ class CConfig(C.Structure):
         "crit_targ_update_freq", "use_graphs", "device_id", "reserved0")] + [(n, C.c_float) for n in (
         "actor_lr", "qnets_lr", "log_alpha_lr", "gamma", "polyak", "alpha_init", "clip_norm", "td3_std", "td3_c",
         "actor_noise_std", "adam_beta1", "adam_beta2", "adam_eps", "reserved1")] + [("seed", C.c_uint64)]
+
+
+class CDeviceFields(C.Structure):
+    """sactd3_device_fields: five device pointers, each with its row stride in elements"""
+    _fields_ = [(n, t) for f in ("obs", "actions", "rewards", "next_obs", "dones") for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
 
 
 def library_path() -> str:
@@ -106,6 +113,9 @@ def load_library():
         "sactd3_predict_begin": (C.c_int, [vp, fp, C.c_int, C.c_int, C.c_int]),
         "sactd3_predict_end": (C.c_int, [vp, fp]),
         "sactd3_acting_stats": (C.c_int, [vp, i64p]),
+        "sactd3_rb_extend_fields_device": (C.c_int, [vp, C.POINTER(CDeviceFields), C.c_int, vp, C.c_int]),
+        "sactd3_load_batch_device": (C.c_int, [vp, C.POINTER(CDeviceFields), C.c_int, vp, C.c_int]),
+        "sactd3_boundary_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -6,6 +6,7 @@ change in main.py.  Nothing here computes on the CPU: every method is a call int
 """
 from __future__ import annotations
 
+import sys
 from pathlib import Path
 from typing import Any, Dict, Mapping, Optional
 
@@ -19,6 +20,80 @@ def _np(x) -> np.ndarray:
     if hasattr(x, "detach"):
         x = x.detach().cpu().numpy()
     return np.asarray(x)
+
+
+def _cai(x):
+    """the __cuda_array_interface__ of a device array (None: a host array, or a dtype the interface cannot describe)"""
+    try:
+        return getattr(x, "__cuda_array_interface__", None)
+    except (TypeError, RuntimeError, ValueError):
+        return None
+
+
+def _cai_field(cai, width: int, item: int):
+    """(address, rows, row stride in elements) of a device array [n, width] -- or [n] when width == 1 -- of `item`-byte elements
+    with a contiguous inner dimension, from its __cuda_array_interface__; None when the layout needs a copy first."""
+    shape, strides = tuple(cai["shape"]), cai.get("strides")
+    if not ((len(shape) == 2 and shape[1] == width) or (len(shape) == 1 and width == 1)):
+        raise ValueError(f"expected [n, {width}]" + (" or [n]" if width == 1 else "") + f", got {list(shape)}")
+    n, ld = int(shape[0]), width
+    if strides is not None and n > 1:
+        if len(shape) == 2 and width > 1 and strides[1] != item:
+            return None
+        if strides[0] % item or strides[0] // item < width:
+            return None
+        ld = strides[0] // item
+    return int(cai["data"][0]), n, int(ld)
+
+
+def _device_route(engine: Engine, obs, act, rew, nobs, done):
+    """The one place that decides how five arrays reach the engine.  -> (fields, n, keep) for Engine.rb_extend_fields_device /
+    load_batch_device when ALL of them are arrays on the engine's device (`keep` holds converted copies alive across the call),
+    None for the host route (numpy, a mix of host and device, another device, `engine.device_inputs` off).
+    Pointer, shape and strides come from __cuda_array_interface__; a field that is not float32 (flags: not 1-byte), or whose inner
+    dimension is not contiguous, is first converted ON the device with the array library's own ops (.to(float32), != 0, .contiguous())."""
+    if not getattr(engine, "device_inputs", False):
+        return None
+    xs = [x.detach() if hasattr(x, "detach") else x for x in (obs, act, rew, nobs, done)]
+    cais = [_cai(x) for x in xs]      # (read once per array: building the dictionary is the expensive part of this function)
+    if any(c is None for c in cais):
+        return None
+    for x in xs:      # another GPU's arrays take the host route (the C side refuses them too)
+        dev = getattr(x, "device", None)
+        ordinal = getattr(dev, "index", getattr(dev, "id", None))
+        if ordinal is not None and int(ordinal) != int(engine.cfg.device_id):
+            return None
+    o, a = engine.cfg.ob_dim, engine.cfg.ac_dim
+    fields, rows, keep = [], [], []
+    for x, cai, width, is_flag in zip(xs, cais, (o, a, 1, o, 1), (False, False, False, False, True)):
+        typestr, item = cai["typestr"], 1 if is_flag else 4
+        if is_flag and int(typestr[2:]) != 1:
+            x = x != 0
+            cai = _cai(x)
+        elif not is_flag and typestr[1:] != "f4":
+            lib = sys.modules.get(type(x).__module__.partition(".")[0])
+            x = x.to(getattr(lib, "float32", "float32"))
+            cai = _cai(x)
+        got = _cai_field(cai, width, item)
+        if got is None:
+            x = x.contiguous()
+            got = _cai_field(_cai(x), width, item)
+        keep.append(x)
+        fields.append((got[0], got[2]))
+        rows.append(got[1])
+    if len(set(rows)) != 1:
+        raise ValueError(f"fields disagree on the number of rows: {rows}")
+    if rows[0] == 0:
+        return None      # (nothing to read: the host route's n == 0 case)
+    return fields, rows[0], keep
+
+
+def _producer_stream(x, device_id: int) -> int:
+    """the stream the caller's arrays were written on, as far as the array library tells: torch's current stream of the device"""
+    if type(x).__module__.partition(".")[0] == "torch":
+        import torch
+        return int(torch.cuda.current_stream(device_id).cuda_stream)
+    return 0      # the default stream
 
 
 class LazyMetric:
@@ -100,8 +175,13 @@ class ReplayBuffer:
     def extend(self, td: Mapping[str, Any]) -> None:
         """orchestrator.py:100-113: keys observations, next_observations, actions, rewards, terminations, dones."""
         done = td["dones"] if "dones" in td else td["terminations"]
-        self._need().rb_extend(_np(td["observations"]), _np(td["actions"]), _np(td["rewards"]),
-                               _np(td["next_observations"]), _np(done))
+        eng = self._need()
+        five = (td["observations"], td["actions"], td["rewards"], td["next_observations"], done)
+        dev = _device_route(eng, *five)
+        if dev is not None:      # device tensors stay where they are: one pack kernel, ordered against the caller's stream on the GPU
+            eng.rb_extend_fields_device(dev[0], dev[1], _producer_stream(five[0], eng.cfg.device_id))
+            return
+        eng.rb_extend(*[_np(x) for x in five])
 
     def sample(self, batch_size: int) -> BatchHandle:
         eng = self._need()
@@ -204,8 +284,12 @@ class Agent:
                                       "(keep the rows, e.g. dict(handle), to train on them again)")
             return  # already in the engine's batch slot
         self.engine._batch_generation = getattr(self.engine, "_batch_generation", 0) + 1   # a caller-owned batch replaces the slot
-        self.engine.load_batch(_np(batch["observations"]), _np(batch["actions"]), _np(batch["rewards"]),
-                               _np(batch["next_observations"]), _np(batch["dones"]))
+        five = (batch["observations"], batch["actions"], batch["rewards"], batch["next_observations"], batch["dones"])
+        dev = _device_route(self.engine, *five)
+        if dev is not None:
+            self.engine.load_batch_device(dev[0], dev[1], _producer_stream(five[0], self.engine.cfg.device_id))
+            return
+        self.engine.load_batch(*[_np(x) for x in five])
 
     def predict(self, in_td: Mapping[str, Any], *, explore: bool) -> np.ndarray:
         """agents/agent.py:172-181 -> np.ndarray[n, ac_dim] float32 on the host."""

@@ -151,6 +151,10 @@ struct sactd3_engine {
   bool actor_dirty = true, act_inflight = false, act_ordered = false, act_spin = false;
   int act_n = 0, act_want = 0;
   int64_t act_stats[4] = {};                    // sactd3_acting_stats
+  // The device boundary (sactd3_rb_extend_fields_device / sactd3_load_batch_device): the two events that order the learner stream
+  // against the caller's producer stream, created at the first SACTD3_SRC_ORDERED call, and the host counters of sactd3_boundary_stats.
+  hipEvent_t ev_src_ready = nullptr, ev_src_read = nullptr;
+  int64_t bnd_stats[4] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -1315,6 +1319,8 @@ void sactd3_destroy(sactd3_engine* e) {
   for (void* p : e->host_allocs) hipHostFree(p);
   if (e->ev_learner) hipEventDestroy(e->ev_learner);
   if (e->ev_acting) hipEventDestroy(e->ev_acting);
+  if (e->ev_src_ready) hipEventDestroy(e->ev_src_ready);
+  if (e->ev_src_read) hipEventDestroy(e->ev_src_read);
   if (e->act_stream) hipStreamDestroy(e->act_stream);
   if (e->stream) hipStreamDestroy(e->stream);
   delete e;
@@ -1687,6 +1693,115 @@ int sactd3_load_batch(sactd3_engine* e, const float* obs, const float* act, cons
   RCCHK(set_flag(e, &e->ctl->inject_idx, 1));
   RCCHK(gather_now(e, e->stage_dev, n));
   return set_flag(e, &e->ctl->inject_idx, 0);
+}
+
+// ---- the device boundary: the caller's five arrays are already in this device's memory (include/sactd3.h)
+static int fields_check(sactd3_engine* e, const sactd3_device_fields* f, const char* what) {
+  const struct { const void* p; int64_t ld; int width; const char* name; } fld[5] = {
+      {f->obs, f->obs_ld, e->o, "obs"}, {f->actions, f->actions_ld, e->a, "actions"}, {f->rewards, f->rewards_ld, 1, "rewards"},
+      {f->next_obs, f->next_obs_ld, e->o, "next_obs"}, {f->dones, f->dones_ld, 1, "dones"}};
+  for (const auto& x : fld) {
+    if (!x.p) { e->err = std::string(what) + ": `" + x.name + "` is NULL"; return SACTD3_EINVAL; }
+    if (x.ld < x.width) { e->err = std::string(what) + ": row stride of `" + x.name + "` is below its width"; return SACTD3_EINVAL; }
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, x.p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
+      (void)hipGetLastError();
+      e->err = std::string(what) + ": `" + x.name + "` is not device memory of the engine's device";
+      return SACTD3_EINVAL;
+    }
+  }
+  return 0;
+}
+static FieldSrc field_src(const sactd3_engine* e, const sactd3_device_fields* f, int64_t row0) {
+  FieldSrc s{};
+  s.obs = f->obs + row0 * f->obs_ld; s.act = f->actions + row0 * f->actions_ld; s.rew = f->rewards + row0 * f->rewards_ld;
+  s.nobs = f->next_obs + row0 * f->next_obs_ld; s.done = f->dones + row0 * f->dones_ld;
+  s.obs_ld = (long)f->obs_ld; s.act_ld = (long)f->actions_ld; s.rew_ld = (long)f->rewards_ld; s.nobs_ld = (long)f->next_obs_ld; s.done_ld = (long)f->dones_ld;
+  s.o = e->o; s.a = e->a; s.cx = e->cx; s.cn = e->cn;
+  return s;
+}
+// SACTD3_SRC_ORDERED, first half: the learner stream waits for what the caller has queued on its producer stream so far
+static int src_order_begin(sactd3_engine* e, hipStream_t producer, int flags) {
+  if (!(flags & SACTD3_SRC_ORDERED)) return 0;
+  if (!e->ev_src_ready) HIPCHK(hipEventCreateWithFlags(&e->ev_src_ready, hipEventDisableTiming));
+  if (!e->ev_src_read) HIPCHK(hipEventCreateWithFlags(&e->ev_src_read, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(e->ev_src_ready, producer));
+  HIPCHK(hipStreamWaitEvent(e->stream, e->ev_src_ready, 0));
+  return 0;
+}
+// ... second half: whatever the caller queues there next (an overwrite, the reuse of the freed block) waits for the read
+static int src_order_end(sactd3_engine* e, hipStream_t producer, int flags) {
+  if (!(flags & SACTD3_SRC_ORDERED)) return 0;
+  HIPCHK(hipEventRecord(e->ev_src_read, e->stream));
+  HIPCHK(hipStreamWaitEvent(producer, e->ev_src_read, 0));
+  ++e->bnd_stats[3];
+  return 0;
+}
+static int launch_ingest_fields(sactd3_engine* e, const FieldSrc& src, int chunk) {
+  const int64_t cap = e->cfg.rb_capacity;
+  IngestFieldsArgs g{};
+  g.ring = (float4*)e->ring; g.rec4 = e->rec4; g.n = chunk; g.cursor = (int)e->rb_cursor; g.cap = (int)cap;
+  e->rb_cursor = (e->rb_cursor + chunk) % cap;
+  e->rb_len = std::min<int64_t>(cap, e->rb_len + chunk);
+  g.len_cursor = &e->ctl->rb_len; g.new_len = (int)e->rb_len; g.new_cursor = (int)e->rb_cursor;
+  const long chunks = (long)chunk * e->rec4;
+  hipLaunchKernelGGL(k_rb_ingest_fields, dim3((unsigned)((chunks + 256L * FIELDS_CPT - 1) / (256L * FIELDS_CPT))), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_batch_fields(sactd3_engine* e, const FieldSrc& src) {
+  const sactd3_engine::BatchSlot& S = e->bs[0];
+  BatchFieldsArgs g{};
+  g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.idx = S.idx; g.B = e->B;
+  const long chunks = (long)e->B * (e->cx + e->cn + 1);      // (< B * rec4 < 2^31: create_impl)
+  hipLaunchKernelGGL(k_batch_from_fields, dim3((unsigned)((chunks + 256L * FIELDS_CPT - 1) / (256L * FIELDS_CPT))), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// rb.extend (orchestrator.py:100-113) with the TensorDict's fields where they are, in device memory: one k_rb_ingest_fields launch
+// per at most rb_capacity rows, no host pack, no copy, no wait on the host.
+int sactd3_rb_extend_fields_device(sactd3_engine* e, const sactd3_device_fields* f, int n, void* producer_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!f || n < 0) return e->fail(SACTD3_EINVAL, "rb_extend_fields_device: bad argument");
+  USE_DEVICE(e);
+  CHAIN_BREAK(e);
+  RCCHK(fields_check(e, f, "rb_extend_fields_device"));
+  const hipStream_t producer = (hipStream_t)producer_stream;
+  const int64_t per_launch = std::min<int64_t>(e->cfg.rb_capacity, ((1ll << 31) - 1) / e->rec4);
+  if (n > 0) RCCHK(src_order_begin(e, producer, flags));
+  for (int done_rows = 0; done_rows < n;) {
+    const int chunk = (int)std::min<int64_t>(n - done_rows, per_launch);
+    RCCHK(launch_ingest_fields(e, field_src(e, f, done_rows), chunk));
+    done_rows += chunk;
+  }
+  if (n > 0) RCCHK(src_order_end(e, producer, flags));
+  ++e->bnd_stats[0]; e->bnd_stats[1] += n;
+  return 0;
+}
+
+// a caller-owned DEVICE batch (what update_qnets(batch) / update_actor(batch) receive in the reference, agents/agent.py:183,245):
+// one k_batch_from_fields launch fills batch slot 0 as sactd3_load_batch would have.
+int sactd3_load_batch_device(sactd3_engine* e, const sactd3_device_fields* f, int n, void* producer_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!f) return e->fail(SACTD3_EINVAL, "load_batch_device: bad argument");
+  USE_DEVICE(e);
+  CHAIN_BREAK(e);
+  if (n != e->B) return e->fail(SACTD3_EINVAL, "load_batch_device: n must equal batch_size");
+  RCCHK(fields_check(e, f, "load_batch_device"));
+  const hipStream_t producer = (hipStream_t)producer_stream;
+  RCCHK(src_order_begin(e, producer, flags));
+  e->cur_slot = 0;
+  RCCHK(launch_batch_fields(e, field_src(e, f, 0)));
+  RCCHK(src_order_end(e, producer, flags));
+  ++e->bnd_stats[2];
+  return 0;
+}
+
+int sactd3_boundary_stats(const sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = e->bnd_stats[i];
+  return 0;
 }
 
 int sactd3_read_batch(sactd3_engine* e, float* obs, float* act, float* rew, float* nobs, uint8_t* dones, int64_t* idx) {
@@ -2182,7 +2297,17 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
                              {e->X, e->Pc, e->c_z1, e->c_z2, e->c_xh1, e->c_h1, e->c_rs1}};
       return enqueue_trunk(x, e->ldc, e->o + e->a, e->B, e->Lc, e->Lc.size, 2, 2, g, TrunkTicks{nullptr, nullptr, nullptr, nullptr, 0.f});
     }
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics)");
+    if (!strcmp(kernel, "batch_from_fields") || !strcmp(kernel, "rb_ingest_fields")) {
+      // the device-boundary pack kernels, fed from the engine's own staging slab read as five strided fields (batch_size rows into
+      // the batch slot / an env step's max_envs rows into the ring: both are overwritten)
+      sactd3_device_fields f{};
+      f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
+      f.dones = (const uint8_t*)(e->stage_dev + e->ldc + e->ldo + 1);
+      f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f;
+      if (!strcmp(kernel, "batch_from_fields")) { e->cur_slot = 0; return launch_batch_fields(e, field_src(e, &f, 0)); }
+      return launch_ingest_fields(e, field_src(e, &f, 0), (int)std::min<int64_t>(std::min(e->maxn, e->B), e->cfg.rb_capacity));
+    }
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields)");
   };
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up
   if (rc == 0) {

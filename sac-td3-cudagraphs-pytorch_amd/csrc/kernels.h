@@ -426,6 +426,113 @@ __global__ __launch_bounds__(256) void k_rb_ingest(IngestArgs p) {
   if (blockIdx.x == 0 && threadIdx.x == 0) { p.len_cursor[0] = p.new_len; p.len_cursor[1] = p.new_cursor; }
 }
 
+// The same two destinations -- ring records, the batch slot -- filled from the CALLER's five arrays in device memory (the reference's
+// loop hands the agent device tensors: orchestrator.py:100-113 extends with one, :338-348 updates on one): obs [n, o], act [n, a],
+// rew [n], next_obs [n, o], dones [n] bytes, each with a row stride in elements and a contiguous inner dimension.  A source row
+// need not be 16-byte aligned (Hopper: o = 11) and a destination chunk may hold the end of s and the start of a, or the end of a
+// field and its zero pad: every one of the chunk's four floats is ONE dword load whose address is always valid (what has no source
+// reads column 0 of the row's observation) and whose value a select keeps or zeroes.  One thread per destination float4 chunk,
+// FIELDS_CPT chunks per thread (consecutive threads -> consecutive chunks), all loads first, all stores last.
+struct FieldSrc {
+  const float* obs; const float* act; const float* rew; const float* nobs; const unsigned char* done;
+  long obs_ld, act_ld, rew_ld, nobs_ld, done_ld;
+  int o, a, cx, cn;                       // record chunk c: [0, cx) = [s|a|0], [cx, cx + cn) = [s'|0], cx + cn = [r, d, 0, 0], beyond: 0
+};
+#define FIELDS_CPT 4
+typedef const __attribute__((address_space(1))) float* gfloat_p;      // device memory for certain (the host checked): global_load, not flat_load
+typedef const __attribute__((address_space(1))) unsigned char* gbyte_p;
+// float i of chunk c of row r: where it comes from (`ok`: it has a source at all)
+__device__ __forceinline__ gfloat_p field_addr(const FieldSrc& f, long r, int c, int i, bool& ok) {
+  const int e = 4 * c + i, en = e - 4 * f.cx;
+  const bool is_s = e < f.o, is_a = !is_s && e < f.o + f.a, is_n = en >= 0 && en < f.o, is_r = en == 4 * f.cn;
+  ok = is_s || is_a || is_n || is_r;
+  // exactly one of the four terms is non-zero.  (Written as a sum of two-way selects on purpose: a chain of selects between the
+  // pointers is compiled into a per-lane LOAD of the chosen pointer from an in-memory table -- a second, dependent round trip.)
+  const bool is_o = !is_a && !is_n && !is_r;
+  const uintptr_t base = (is_a ? (uintptr_t)f.act : 0) + (is_n ? (uintptr_t)f.nobs : 0) + (is_r ? (uintptr_t)f.rew : 0) + (is_o ? (uintptr_t)f.obs : 0);
+  const long ld = (is_a ? f.act_ld : 0) + (is_n ? f.nobs_ld : 0) + (is_r ? f.rew_ld : 0) + (is_o ? f.obs_ld : 0);
+  const int col = (is_s ? e : 0) + (is_a ? e - f.o : 0) + (is_n ? en : 0);
+  return (gfloat_p)(base + 4 * (uintptr_t)(r * ld + col));
+}
+struct FieldChunk { float x, y, z, w; unsigned d; };
+__device__ __forceinline__ FieldChunk field_ld(const FieldSrc& f, long r, int c) {      // the requests only
+  bool ok;
+  FieldChunk v;
+  v.x = *field_addr(f, r, c, 0, ok); v.y = *field_addr(f, r, c, 1, ok); v.z = *field_addr(f, r, c, 2, ok); v.w = *field_addr(f, r, c, 3, ok);
+  v.d = *(gbyte_p)((uintptr_t)f.done + (uintptr_t)(r * f.done_ld));
+  return v;
+}
+__device__ __forceinline__ float4 field_sel(const FieldSrc& f, int c, const FieldChunk& v) {   // ... and what the chunk holds
+  bool k0, k1, k2, k3;
+  (void)field_addr(f, 0, c, 0, k0); (void)field_addr(f, 0, c, 1, k1); (void)field_addr(f, 0, c, 2, k2); (void)field_addr(f, 0, c, 3, k3);
+  const float flag = v.d ? 1.f : 0.f;      // any non-zero byte = done
+  return make_float4(k0 ? v.x : 0.f, c == f.cx + f.cn ? flag : (k1 ? v.y : 0.f), k2 ? v.z : 0.f, k3 ? v.w : 0.f);
+}
+
+// rb.extend from device fields: n records into the ring (round-robin from `cursor`, wrapping at `cap`), new length / cursor
+// published with them as k_rb_ingest does.  The host keeps n * rec4 < 2^31 per launch.
+// (The sources are separate kernel arguments, not a struct: the per-lane choice between members of an argument STRUCT in field_addr is
+// compiled into a per-lane load from the argument block in front of every source load -- two dependent round trips per float.)
+#define FIELD_PARAMS const float* f_obs, const float* f_act, const float* f_rew, const float* f_nobs, const unsigned char* f_done, \
+                     long obs_ld, long act_ld, long rew_ld, long nobs_ld, long done_ld, int f_o, int f_a, int f_cx, int f_cn
+#define FIELD_SRC FieldSrc{f_obs, f_act, f_rew, f_nobs, f_done, obs_ld, act_ld, rew_ld, nobs_ld, done_ld, f_o, f_a, f_cx, f_cn}
+#define FIELD_ARGS(s) (s).obs, (s).act, (s).rew, (s).nobs, (s).done, (s).obs_ld, (s).act_ld, (s).rew_ld, (s).nobs_ld, (s).done_ld, (s).o, (s).a, (s).cx, (s).cn
+struct IngestFieldsArgs { float4* ring; int rec4, n, cursor, cap; int* len_cursor; int new_len, new_cursor; };
+__global__ __launch_bounds__(256) void k_rb_ingest_fields(FIELD_PARAMS, IngestFieldsArgs p) {
+  const unsigned total = (unsigned)p.n * (unsigned)p.rec4;      // >= 1
+  const FieldSrc f = FIELD_SRC;
+  int row[FIELDS_CPT], cc[FIELDS_CPT]; bool on[FIELDS_CPT]; FieldChunk v[FIELDS_CPT];
+#pragma unroll
+  for (int u = 0; u < FIELDS_CPT; ++u) {
+    const unsigned g = (blockIdx.x * (unsigned)FIELDS_CPT + (unsigned)u) * 256u + threadIdx.x;
+    on[u] = g < total;
+    const unsigned gc = min(g, total - 1u), q = gc / (unsigned)p.rec4;      // (a chunk past the end reads what the last one reads)
+    row[u] = (int)q; cc[u] = (int)(gc - q * (unsigned)p.rec4);
+  }
+#pragma unroll
+  for (int u = 0; u < FIELDS_CPT; ++u) v[u] = field_ld(f, row[u], cc[u]);
+#pragma unroll
+  for (int u = 0; u < FIELDS_CPT; ++u) { PIN(v[u].x); PIN(v[u].y); PIN(v[u].z); PIN(v[u].w); PIN(v[u].d); }      // every request is out before the first store
+#pragma unroll
+  for (int u = 0; u < FIELDS_CPT; ++u) {
+    if (!on[u]) continue;
+    int dst = p.cursor + row[u];
+    if (dst >= p.cap) dst -= p.cap;
+    p.ring[(long)dst * p.rec4 + cc[u]] = field_sel(f, cc[u], v[u]);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) { p.len_cursor[0] = p.new_len; p.len_cursor[1] = p.new_cursor; }
+}
+
+// A caller-owned batch from device fields, written straight into a batch slot: X, the s' columns of Xn, rew, done and idx[b] = b --
+// what sactd3_load_batch leaves there through its staging slab and an index-injected gather, in one launch.  B * (cx + cn + 1) < 2^31.
+struct BatchFieldsArgs { float4* X; float4* Xn; float* rew; float* done; int* idx; int B; };
+__global__ __launch_bounds__(256) void k_batch_from_fields(FIELD_PARAMS, BatchFieldsArgs p) {
+  const FieldSrc f = FIELD_SRC;
+  const int W = f.cx + f.cn + 1;          // chunks moved per row: the record without its trailing pad
+  const unsigned total = (unsigned)p.B * (unsigned)W;
+  int row[FIELDS_CPT], cc[FIELDS_CPT]; bool on[FIELDS_CPT]; FieldChunk v[FIELDS_CPT];
+#pragma unroll
+  for (int u = 0; u < FIELDS_CPT; ++u) {
+    const unsigned g = (blockIdx.x * (unsigned)FIELDS_CPT + (unsigned)u) * 256u + threadIdx.x;
+    on[u] = g < total;
+    const unsigned gc = min(g, total - 1u), q = gc / (unsigned)W;
+    row[u] = (int)q; cc[u] = (int)(gc - q * (unsigned)W);
+  }
+#pragma unroll
+  for (int u = 0; u < FIELDS_CPT; ++u) v[u] = field_ld(f, row[u], cc[u]);
+#pragma unroll
+  for (int u = 0; u < FIELDS_CPT; ++u) { PIN(v[u].x); PIN(v[u].y); PIN(v[u].z); PIN(v[u].w); PIN(v[u].d); }      // every request is out before the first store
+#pragma unroll
+  for (int u = 0; u < FIELDS_CPT; ++u) {
+    if (!on[u]) continue;
+    const int b = row[u], c = cc[u];
+    const float4 o4 = field_sel(f, c, v[u]);
+    if (c < f.cx) p.X[(long)b * f.cx + c] = o4;
+    else if (c < f.cx + f.cn) p.Xn[(long)b * f.cx + (c - f.cx)] = o4;
+    else { p.rew[b] = o4.x; p.done[b] = o4.y; p.idx[b] = b; }
+  }
+}
+
 struct FillArgs { float4* ring; int rec4, cx, cn, o, a; long n; unsigned long long seed; const float* min_ac; const float* max_ac; };
 __global__ __launch_bounds__(256) void k_rb_fill(FillArgs p) {
   const long g = (long)blockIdx.x * 256 + threadIdx.x;

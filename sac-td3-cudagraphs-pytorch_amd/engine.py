@@ -93,6 +93,10 @@ class Config:
 class Engine:
     """One learner on one MI355X.  All update calls are asynchronous on the engine's HIP stream."""
 
+    # ReplayBuffer.extend / Agent._stage hand device arrays to the device entry points (rb_extend_fields_device /
+    # load_batch_device); False forces the host route (copy to the host, pack there), e.g. to compare the two in one process
+    device_inputs = True
+
     def __init__(self, cfg: Config, min_ac, max_ac):
         self.lib = _lib.load_library()
         self.cfg = cfg
@@ -112,6 +116,7 @@ class Engine:
         self._st = [np.zeros((n0, o), np.float32), np.zeros((n0, a), np.float32), np.zeros(n0, np.float32),
                     np.zeros((n0, o), np.float32), np.zeros(n0, np.uint8), np.zeros((n0, o), np.float32), np.zeros((n0, a), np.float32)]
         self._st_p = [x.ctypes.data_as(C.POINTER(C.c_uint8) if x.dtype == np.uint8 else _F) for x in self._st]
+        self._df = _lib.CDeviceFields()     # argument block of the device-field calls, filled per call
 
     # -- plumbing
     def _ck(self, rc):
@@ -204,6 +209,30 @@ class Engine:
     def rb_extend_device(self, device_ptr: int, n: int) -> None:
         """append n packed records that already live in device memory (kept alive by the caller until sync())."""
         self._ck(self.lib.sactd3_rb_extend_device(self._h, C.c_void_p(int(device_ptr)), int(n)))
+
+    def _fields(self, fields):
+        df = self._df
+        (df.obs, df.obs_ld), (df.actions, df.actions_ld), (df.rewards, df.rewards_ld), (df.next_obs, df.next_obs_ld), (df.dones, df.dones_ld) = fields
+        return C.byref(df)
+
+    def rb_extend_fields_device(self, fields, n: int, producer_stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_rb_extend_fields_device: append n rows whose five fields -- `fields` = (device address, row stride in elements) of
+        obs, actions, rewards, next_obs, dones (bytes) -- are in this device's memory.  `ordered`: the engine orders its read against
+        `producer_stream` (a hipStream_t as an integer; 0 = the default stream) on the GPU; otherwise the caller has synchronised and
+        keeps the arrays untouched until sync()."""
+        self._ck(self.lib.sactd3_rb_extend_fields_device(self._h, self._fields(fields), int(n), C.c_void_p(int(producer_stream) or None),
+                                                         _lib.SRC_ORDERED if ordered else 0))
+
+    def load_batch_device(self, fields, n: int, producer_stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_load_batch_device: a caller-owned device batch (arguments as rb_extend_fields_device, n == batch_size) into the batch slot."""
+        self._ck(self.lib.sactd3_load_batch_device(self._h, self._fields(fields), int(n), C.c_void_p(int(producer_stream) or None),
+                                                   _lib.SRC_ORDERED if ordered else 0))
+
+    def boundary_stats(self) -> Dict[str, int]:
+        """host counters of the device boundary (sactd3_boundary_stats)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.sactd3_boundary_stats(self._h, out))
+        return dict(device_extends=int(out[0]), device_rows=int(out[1]), device_batches=int(out[2]), ordered_calls=int(out[3]))
 
     def rb_len(self) -> int:
         return int(self._ck(self.lib.sactd3_rb_len(self._h)))
