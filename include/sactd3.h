@@ -224,7 +224,7 @@ int sactd3_predict(sactd3_engine* e, const float* obs, int n, int explore, float
  * parameters, the action bounds, their own scratch and their own control words) meet a learner call:
  *   learner -> acting: if a call that writes the actor parameters was issued on the learner stream since the acting stream last
  *     waited for it (sactd3_update_actor, sactd3_step with actor updates, sactd3_step_period, sactd3_step_prefix,
- *     sactd3_set_params(ACTOR), sactd3_time_nodes), or if flags has SACTD3_ACT_AFTER_ALL, `begin` makes the acting stream wait for
+ *     sactd3_set_params(ACTOR), sactd3_time_nodes), or a sactd3_predict_device call (its queued kernels use the acting scratch), or if flags has SACTD3_ACT_AFTER_ALL, `begin` makes the acting stream wait for
  *     everything issued on the learner stream so far -- as sactd3_predict does.  Otherwise it waits for nothing: behind a
  *     critic-only iteration the action comes from the same parameters either way.
  *   acting -> learner: while a call is in flight (begun, not ended) the first of the calls above makes the learner stream wait for
@@ -241,6 +241,32 @@ int sactd3_predict_end(sactd3_engine* e, float* actions);          /* waits for 
 /* host counters of the ordering policy: out = {calls begun, begins that made the acting stream wait for the learner, learner calls
  * that waited for an acting call in flight, calls ended by the pinned-word spin} */
 int sactd3_acting_stats(const sactd3_engine* e, int64_t out[4]);
+
+/* ---- acting for an environment that lives on the GPU: Agent.predict (agents/agent.py:172-181) with the observations where a batched
+ * simulator, a learned world model or a torch-written env left them, and the actions left where its next step reads them.
+ * `obs` [n, ob_dim] and `actions` [n, ac_dim] are DEVICE pointers in the memory of the engine's device, each with a row stride in elements
+ * (>= the width), a contiguous inner dimension and no alignment beyond 4 bytes; 1 <= n <= max_envs.  The call launches on the learner
+ * stream and returns: no copy command, no wait, spin or synchronisation on the host.  One kernel packs the rows into the zero-padded layout
+ * the trunk reads, the acting pair of sactd3_predict runs on engine-owned device buffers (captured once per (explore, n); the eager
+ * sequence with use_graphs == 0), one kernel writes the [n, ac_dim] window of `actions` and nothing outside it.
+ * Like sactd3_predict it is stream-ordered behind every update issued before it and acts with the updated parameters; its result is,
+ * bit for bit, what sactd3_predict returns for the same rows at the same position in the call sequence, the native exploration draw
+ * included: host and device calls may be mixed and share one noise stream (one counter tick per call, whichever entry point).  It
+ * reads the actor parameters, the action bounds, the acting control words and its own scratch only: a precomputed opening pair of
+ * sactd3_step_period stays valid across it, as across sactd3_predict.
+ * flags & SACTD3_SRC_ORDERED orders both arrays against `caller_stream` (a hipStream_t; NULL = the legacy default stream) on the GPU, as
+ * sactd3_load_batch_device does for its sources: the learner stream waits for what the caller has queued there so far, and
+ * `caller_stream` then waits for an event recorded behind the last launch -- the caller may read `actions` on its stream at once, and a
+ * later overwrite of `obs` there cannot overtake the read.  Without the flag nothing is inserted: the caller has synchronised, and
+ * leaves both arrays alone until sactd3_sync.
+ * SACTD3_EINVAL: a NULL pointer, a stride below the width, n out of range, a pointer that is not memory of the engine's device, an
+ * unknown flag.  SACTD3_ESTATE while a sactd3_predict_begin call is in flight (it shares the exploration counter, the draw buffer and
+ * the acting scratch with that call).  The other way round the engine orders the streams itself: this call returns with its kernels
+ * queued, so the next sactd3_predict_begin makes the acting stream wait for the learner stream, as it does behind an actor update. */
+int sactd3_predict_device(sactd3_engine* e, const float* obs, int64_t obs_ld, int n, int explore,
+                          float* actions, int64_t actions_ld, void* caller_stream, int flags);
+/* host counters: out = {calls, rows, calls that inserted event waits, calls that took a multi-block tail} */
+int sactd3_predict_device_stats(const sactd3_engine* e, int64_t out[4]);
 
 int sactd3_read_metrics(sactd3_engine* e, float out[SACTD3_NUM_METRICS]);  /* [sync] */
 /* The engine's HIP stream (hipStream_t) and the DEVICE address of the metrics slots, for callers that want the values the
@@ -263,7 +289,8 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
 /* average device time in microseconds of `iters` back-to-back launches of one kernel of the path,
  * measured with hipEvents on the engine's stream: "gather" (a fresh index draw per launch), "polyak", "trunk_critics" (the 4-net
  * hidden-layer launch of update_qnets; on wide inputs it is two launches), "batch_from_fields" / "rb_ingest_fields" (the device-boundary
- * pack kernels on batch_size / max_envs rows of the engine's own staging slab; they overwrite the batch slot / append to the ring). [sync] */
+ * pack kernels on batch_size / max_envs rows of the engine's own staging slab; they overwrite the batch slot / append to the ring),
+ * "obs_from_field" / "act_to_field" (the pack / unpack kernels of sactd3_predict_device on max_envs rows of engine-owned memory). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

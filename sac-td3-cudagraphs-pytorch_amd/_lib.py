@@ -14,7 +14,7 @@ ACTOR, CRITICS, ACTOR_TARGET, CRITICS_TARGET, LOG_ALPHA = range(5)
 SITE_CRITIC, SITE_ACTOR0, SITE_ACTOR1, SITE_ALPHA0, SITE_ALPHA1, SITE_PREDICT = range(6)
 NUM_METRICS = 8
 ACT_AFTER_ALL = 1   # sactd3_predict_begin flags
-SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device flags
+SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device / sactd3_predict_device flags
 ESTATE, EINVAL = -3, -1
 
 # every symbol include/sactd3.h declares (tests/test_abi.py checks the header against this list)
@@ -28,6 +28,7 @@ SYMBOLS = [
     "sactd3_time_kernel", "sactd3_time_gather_sweep", "sactd3_time_nodes", "sactd3_rb_layout", "sactd3_rb_extend_device", "sactd3_step_period", "sactd3_step_prefix", "sactd3_instantiate_graphs", "sactd3_device_handles",
     "sactd3_predict_begin", "sactd3_predict_end", "sactd3_acting_stats",
     "sactd3_rb_extend_fields_device", "sactd3_load_batch_device", "sactd3_boundary_stats",
+    "sactd3_predict_device", "sactd3_predict_device_stats",
 ]
 
 
@@ -116,6 +117,8 @@ def load_library():
         "sactd3_rb_extend_fields_device": (C.c_int, [vp, C.POINTER(CDeviceFields), C.c_int, vp, C.c_int]),
         "sactd3_load_batch_device": (C.c_int, [vp, C.POINTER(CDeviceFields), C.c_int, vp, C.c_int]),
         "sactd3_boundary_stats": (C.c_int, [vp, i64p]),
+        "sactd3_predict_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int]),
+        "sactd3_predict_device_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -37,13 +37,20 @@ def _cai_field(cai, width: int, item: int):
     if not ((len(shape) == 2 and shape[1] == width) or (len(shape) == 1 and width == 1)):
         raise ValueError(f"expected [n, {width}]" + (" or [n]" if width == 1 else "") + f", got {list(shape)}")
     n, ld = int(shape[0]), width
-    if strides is not None and n > 1:
-        if len(shape) == 2 and width > 1 and strides[1] != item:
+    if strides is not None:
+        if len(shape) == 2 and width > 1 and strides[1] != item:      # (whatever n is: one row with an inner stride is not a row)
             return None
-        if strides[0] % item or strides[0] // item < width:
-            return None
-        ld = strides[0] // item
+        if n > 1:                                                     # (one row: whatever its row stride is reported as, the width will do)
+            if strides[0] % item or strides[0] // item < width:
+                return None
+            ld = strides[0] // item
     return int(cai["data"][0]), n, int(ld)
+
+
+def _on_engine_device(engine: Engine, x) -> bool:
+    dev = getattr(x, "device", None)
+    ordinal = getattr(dev, "index", getattr(dev, "id", None))
+    return ordinal is None or int(ordinal) == int(engine.cfg.device_id)
 
 
 def _device_route(engine: Engine, obs, act, rew, nobs, done):
@@ -58,11 +65,8 @@ def _device_route(engine: Engine, obs, act, rew, nobs, done):
     cais = [_cai(x) for x in xs]      # (read once per array: building the dictionary is the expensive part of this function)
     if any(c is None for c in cais):
         return None
-    for x in xs:      # another GPU's arrays take the host route (the C side refuses them too)
-        dev = getattr(x, "device", None)
-        ordinal = getattr(dev, "index", getattr(dev, "id", None))
-        if ordinal is not None and int(ordinal) != int(engine.cfg.device_id):
-            return None
+    if not all(_on_engine_device(engine, x) for x in xs):      # another GPU's arrays take the host route (the C side refuses them too)
+        return None
     o, a = engine.cfg.ob_dim, engine.cfg.ac_dim
     fields, rows, keep = [], [], []
     for x, cai, width, is_flag in zip(xs, cais, (o, a, 1, o, 1), (False, False, False, False, True)):
@@ -294,6 +298,48 @@ class Agent:
     def predict(self, in_td: Mapping[str, Any], *, explore: bool) -> np.ndarray:
         """agents/agent.py:172-181 -> np.ndarray[n, ac_dim] float32 on the host."""
         return self.engine.predict(_np(in_td["observations"]), explore)
+
+    def predict_device(self, in_td: Mapping[str, Any], *, explore: bool, out: Any = None):
+        """Acting for an environment that lives on the GPU (include/sactd3.h: sactd3_predict_device): observations [n, ob_dim] in
+        the memory of the engine's device -> actions [n, ac_dim], float32, on that device.  Nothing goes through the host and the
+        host does not wait: the kernels run on the engine's stream, ordered on the GPU behind what the caller's current stream has
+        queued, and that stream is made to wait for them -- the result can be used there at once and the observations may be
+        overwritten there next.  The action is, bit for bit, what predict() returns for the same rows at this point of the call
+        sequence.  `out`: a preallocated float32 array or view with at least n rows of ac_dim (contiguous inner dimension) to
+        write into -- its rows [0, n) are returned; otherwise torch.empty on the current stream.  An observation that is not
+        float32, or whose inner dimension is not contiguous, is converted on the device first."""
+        eng = self.engine
+        o, a = eng.cfg.ob_dim, eng.cfg.ac_dim
+        obs = in_td["observations"]
+        obs = obs.detach() if hasattr(obs, "detach") else obs
+        if not getattr(eng, "device_inputs", False):
+            raise TypeError("predict_device: engine.device_inputs is off (predict() takes host data)")
+        cai = _cai(obs)
+        if cai is None or not _on_engine_device(eng, obs):
+            raise TypeError("predict_device: the observations are not an array in the memory of the engine's device (predict() takes host data)")
+        if cai["typestr"][1:] != "f4":
+            lib = sys.modules.get(type(obs).__module__.partition(".")[0])
+            obs = obs.to(getattr(lib, "float32", "float32"))
+            cai = _cai(obs)
+        got = _cai_field(cai, o, 4)
+        if got is None:
+            obs = obs.contiguous()
+            got = _cai_field(_cai(obs), o, 4)
+        ptr, n, ld = got
+        if out is None:
+            try:
+                import torch
+            except ImportError:
+                raise TypeError("predict_device: without torch the caller passes `out`") from None
+            out = torch.empty((n, a), dtype=torch.float32, device=torch.device("cuda", eng.cfg.device_id))
+        ocai = _cai(out.detach() if hasattr(out, "detach") else out)
+        if ocai is None or not _on_engine_device(eng, out) or ocai["typestr"][1:] != "f4":
+            raise TypeError("predict_device: `out` must be a float32 array in the memory of the engine's device")
+        ogot = _cai_field(ocai, a, 4)
+        if ogot is None or ogot[1] < n:
+            raise ValueError(f"predict_device: `out` needs at least {n} rows of {a} with a contiguous inner dimension")
+        eng.predict_device(ptr, ld, n, explore, ogot[0], ogot[2], _producer_stream(obs, eng.cfg.device_id))
+        return out[:n] if ogot[1] > n else out
 
     def predict_begin(self, in_td: Mapping[str, Any], *, explore: bool) -> None:
         """predict() in two halves (include/sactd3.h: sactd3_predict_begin): the acting kernels go out on the engine's acting

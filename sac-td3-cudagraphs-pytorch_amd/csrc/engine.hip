@@ -144,7 +144,8 @@ struct sactd3_engine {
   std::vector<hipGraphExec_t> predict_graphs;   // [explore][n]: the two launches of sactd3_predict, captured per row count
   // Acting on a stream of its own (sactd3_predict_begin / _end), created at the first begin.  Order between the two streams is kept
   // by the host, with events, only where the acting kernels and a learner call touch the same memory -- the actor parameters:
-  //   actor_dirty   a write of them was issued on the learner stream since the acting stream last waited for it -> the next begin waits;
+  //   actor_dirty   a write of them was issued on the learner stream since the acting stream last waited for it -> the next begin waits
+  //                 (also set by sactd3_predict_device, whose queued kernels use the acting scratch, draw buffer and counter);
   //   act_inflight  a call has begun and not ended -> the next learner call that writes them waits for it first (act_ordered: one did).
   hipStream_t act_stream = nullptr;
   hipEvent_t ev_learner = nullptr, ev_acting = nullptr;
@@ -155,6 +156,10 @@ struct sactd3_engine {
   // against the caller's producer stream, created at the first SACTD3_SRC_ORDERED call, and the host counters of sactd3_boundary_stats.
   hipEvent_t ev_src_ready = nullptr, ev_src_read = nullptr;
   int64_t bnd_stats[4] = {};
+  // Acting on device observations (sactd3_predict_device): [explore][n] graphs of the acting pair on p_x / p_act -- they hold no
+  // caller pointer -- and the host counters of sactd3_predict_device_stats.
+  std::vector<hipGraphExec_t> predict_dev_graphs;
+  int64_t pdev_stats[4] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -1314,6 +1319,7 @@ void sactd3_destroy(sactd3_engine* e) {
   if (e->act_stream) hipStreamSynchronize(e->act_stream);
   for (auto& g : e->graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_graphs) if (g) hipGraphExecDestroy(g);
+  for (auto& g : e->predict_dev_graphs) if (g) hipGraphExecDestroy(g);
   for (auto ev : e->events) hipEventDestroy(ev);
   for (void* p : e->dev_allocs) hipFree(p);
   for (void* p : e->host_allocs) hipHostFree(p);
@@ -2064,24 +2070,26 @@ int sactd3_instantiate_graphs(sactd3_engine* e) {
 static bool predict_one_block(sactd3_engine* e, int n) {
   return n <= tail_rows_per_block(tail_args(e, e->p_z2, e->Pa, n, 0, 0, SACTD3_SITE_PREDICT, 48u, e->h_act, e->a4, 0, nullptr));
 }
-static int enqueue_predict(EnqCtx& x, int n, int explore) {
+// `on_device`: the pair of sactd3_predict_device -- observations from p_x, actions to p_act (both engine-owned device memory), and no
+// completion word: nobody on the host waits for it.
+static int enqueue_predict(EnqCtx& x, int n, int explore, bool on_device = false) {
   sactd3_engine* e = x.e;
   const bool td3 = e->cfg.prefer_td3_over_sac;
   bool eps_ready = false;
   {
-    const TrunkGrp g{e->h_obs, e->Pa, e->p_z1, e->p_z2, nullptr, nullptr, nullptr};
+    const TrunkGrp g{on_device ? e->p_x : e->h_obs, e->Pa, e->p_z1, e->p_z2, nullptr, nullptr, nullptr};
     TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
     if (explore) { tk.nnoise = 1; tk.noise[0] = noise_job(e, SACTD3_SITE_PREDICT, 48u, 0, n); tk.noise_taken = &eps_ready; }
     RCCHK(enqueue_trunk(x, e->ldo, e->o, n, e->La, 0, 1, 1, &g, tk));
   }
   const int mode = td3 ? (explore ? 2 : 0) : (explore ? 0 : 1);
-  ActorTail t = tail_args(e, e->p_z2, e->Pa, n, mode, 0, SACTD3_SITE_PREDICT, 48u, e->h_act, e->a4, 0, nullptr);
+  ActorTail t = tail_args(e, e->p_z2, e->Pa, n, mode, 0, SACTD3_SITE_PREDICT, 48u, on_device ? e->p_act : e->h_act, e->a4, 0, nullptr);
   t.eps_ready = eps_ready;
   // the tail reads predict_ctr (its noise stream) and may only advance it itself when it is a single block: with more
   // rows than one block holds, a late block could read the counter after block 0 has bumped it
   const bool one_block = n <= tail_rows_per_block(t);
   if (explore && one_block) t.tick = &e->ctl->predict_ctr;
-  if (one_block) { t.seq = &e->ctl->predict_seq; t.done_flag = e->h_done; }
+  if (one_block && !on_device) { t.seq = &e->ctl->predict_seq; t.done_flag = e->h_done; }
   RCCHK(launch_tail(x, t));
   if (explore && !one_block) {
     hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, x.s, &e->ctl->predict_ctr, (int*)nullptr);
@@ -2178,6 +2186,68 @@ int sactd3_predict_end(sactd3_engine* e, float* actions) {
   RCCHK(rc);
   if (by_spin) ++e->act_stats[3];
   for (int i = 0; i < e->act_n; ++i) memcpy(actions + (size_t)i * e->a, e->h_act + (size_t)i * e->a4, sizeof(float) * e->a);
+  return 0;
+}
+
+static int launch_obs_pack(sactd3_engine* e, const float* obs, int64_t obs_ld, int n) {
+  const ObsFieldArgs g{(float4*)e->p_x, n, e->ldo / 4};
+  const long chunks = (long)n * g.c4;
+  hipLaunchKernelGGL(k_obs_from_field, dim3((unsigned)((chunks + 256L * OBS_CPT - 1) / (256L * OBS_CPT))), dim3(256), 0, e->stream, obs, (long)obs_ld, e->o, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_act_unpack(sactd3_engine* e, float* actions, int64_t actions_ld, int n) {
+  const ActFieldArgs g{(const float4*)e->p_act, n, e->a4 / 4, e->a};
+  const long chunks = (long)n * g.c4;
+  hipLaunchKernelGGL(k_act_to_field, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, e->stream, actions, (long)actions_ld, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// Agent.predict for observations that are ALREADY in this device's memory, actions left there: include/sactd3.h.  Four launches on
+// the learner stream -- pack, the acting pair of sactd3_predict on p_x / p_act (its own (explore, n) graph, or the eager sequence),
+// unpack -- five behind an exploring multi-block tail (the counter kernel is part of the pair); the caller's pointers travel by value
+// in the two eager launches, so no graph is ever updated or re-instantiated.  Nothing waits on the host.
+int sactd3_predict_device(sactd3_engine* e, const float* obs, int64_t obs_ld, int n, int explore, float* actions, int64_t actions_ld,
+                          void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!obs || !actions) return e->fail(SACTD3_EINVAL, "predict_device: null argument");
+  USE_DEVICE(e);
+  if (n < 1 || n > e->maxn) return e->fail(SACTD3_EINVAL, "predict_device: 1 <= n <= max_envs");
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "predict_device: unknown flag");
+  if (obs_ld < e->o) return e->fail(SACTD3_EINVAL, "predict_device: row stride of `obs` is below its width");
+  if (actions_ld < e->a) return e->fail(SACTD3_EINVAL, "predict_device: row stride of `actions` is below its width");
+  if ((int64_t)n * std::max(e->ldo, e->a4) / 4 >= (1ll << 31)) return e->fail(SACTD3_EINVAL, "predict_device: too many rows for one launch");
+  for (const void* ptr : {(const void*)obs, (const void*)actions}) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
+      (void)hipGetLastError();
+      return e->fail(SACTD3_EINVAL, ptr == (const void*)obs ? "predict_device: `obs` is not device memory of the engine's device"
+                                                            : "predict_device: `actions` is not device memory of the engine's device");
+    }
+  }
+  // (it shares predict_ctr and eps[SITE_PREDICT] with a call on the acting stream)
+  if (e->act_inflight) return e->fail(SACTD3_ESTATE, "predict_device: an acting call is in flight (sactd3_predict_end first)");
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  RCCHK(launch_obs_pack(e, obs, obs_ld, n));
+  if (e->predict_dev_graphs.empty()) e->predict_dev_graphs.assign(2 * (size_t)(e->maxn + 1), nullptr);
+  RCCHK(run_graph_slot(e, &e->predict_dev_graphs[(size_t)(explore ? 1 : 0) * (e->maxn + 1) + n], nullptr,
+                       [&](EnqCtx& x) { return enqueue_predict(x, n, explore, true); }));
+  RCCHK(launch_act_unpack(e, actions, actions_ld, n));
+  RCCHK(src_order_end(e, caller, flags));
+  // The call returns with its kernels still queued, and they use the scratch, the draw buffer and the counter that an acting-stream
+  // call uses too: the next sactd3_predict_begin has to wait for the learner stream, exactly as behind a write of the actor.
+  e->actor_dirty = true;
+  ++e->pdev_stats[0]; e->pdev_stats[1] += n;
+  if (flags & SACTD3_SRC_ORDERED) ++e->pdev_stats[2];
+  if (!predict_one_block(e, n)) ++e->pdev_stats[3];
+  return 0;
+}
+
+int sactd3_predict_device_stats(const sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = e->pdev_stats[i];
   return 0;
 }
 
@@ -2307,7 +2377,11 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       if (!strcmp(kernel, "batch_from_fields")) { e->cur_slot = 0; return launch_batch_fields(e, field_src(e, &f, 0)); }
       return launch_ingest_fields(e, field_src(e, &f, 0), (int)std::min<int64_t>(std::min(e->maxn, e->B), e->cfg.rb_capacity));
     }
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields)");
+    // the pack / unpack kernels of sactd3_predict_device on max_envs rows: observations read from the ring's records (the s columns,
+    // row stride = the record), actions written to the acting scratch p_z1 (row stride = its 256 columns; the next trunk overwrites it)
+    if (!strcmp(kernel, "obs_from_field")) return launch_obs_pack(e, e->ring, e->rec_f, (int)std::min<int64_t>(e->maxn, e->cfg.rb_capacity));
+    if (!strcmp(kernel, "act_to_field")) return launch_act_unpack(e, e->p_z1, HID, e->maxn);
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field)");
   };
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up
   if (rc == 0) {

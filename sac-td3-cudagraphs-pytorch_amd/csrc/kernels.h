@@ -533,6 +533,58 @@ __global__ __launch_bounds__(256) void k_batch_from_fields(FIELD_PARAMS, BatchFi
   }
 }
 
+// Acting on DEVICE observations (sactd3_predict_device): the way in and the way out of the engine's own acting buffers.
+// k_obs_from_field packs the caller's obs [n, o] (row stride obs_ld elements, rows 4-byte aligned only) into x [n][4 * c4], the
+// zero-padded rows the trunk reads -- the pad is WRITTEN: the parameter arena's pad columns are zero, but 0 x garbage can be NaN.
+// Same discipline as the two kernels above: one thread per destination float4 chunk, OBS_CPT chunks per thread (consecutive threads ->
+// consecutive chunks), every float one dword load from an always-valid address (what has no source reads column 0 of its row)
+// kept or zeroed by a select, all loads out before the single wait, then the stores.  The host keeps n * c4 < 2^31.
+#define OBS_CPT 2
+struct ObsFieldArgs { float4* x; int n, c4; };
+__global__ __launch_bounds__(256) void k_obs_from_field(const float* f_obs, long obs_ld, int o, ObsFieldArgs p) {
+  const unsigned total = (unsigned)p.n * (unsigned)p.c4;      // >= 1
+  int row[OBS_CPT], cc[OBS_CPT]; bool on[OBS_CPT]; float v[OBS_CPT][4];
+#pragma unroll
+  for (int u = 0; u < OBS_CPT; ++u) {
+    const unsigned g = (blockIdx.x * (unsigned)OBS_CPT + (unsigned)u) * 256u + threadIdx.x;
+    on[u] = g < total;
+    const unsigned gc = min(g, total - 1u), q = gc / (unsigned)p.c4;      // (a chunk past the end reads what the last one reads)
+    row[u] = (int)q; cc[u] = (int)(gc - q * (unsigned)p.c4);
+  }
+#pragma unroll
+  for (int u = 0; u < OBS_CPT; ++u)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = 4 * cc[u] + i;
+      v[u][i] = *(gfloat_p)((uintptr_t)f_obs + 4 * (uintptr_t)((long)row[u] * obs_ld + (e < o ? e : 0)));
+    }
+#pragma unroll
+  for (int u = 0; u < OBS_CPT; ++u) { PIN(v[u][0]); PIN(v[u][1]); PIN(v[u][2]); PIN(v[u][3]); }      // every request is out before the first store
+#pragma unroll
+  for (int u = 0; u < OBS_CPT; ++u) {
+    if (!on[u]) continue;
+    const int e = 4 * cc[u];
+    p.x[(long)row[u] * p.c4 + cc[u]] = make_float4(e < o ? v[u][0] : 0.f, e + 1 < o ? v[u][1] : 0.f, e + 2 < o ? v[u][2] : 0.f, e + 3 < o ? v[u][3] : 0.f);
+  }
+}
+// ... and out: act [n][4 * c4] (what the acting tail wrote: a actions per row, then its pad) into the caller's actions [n, a] (row
+// stride act_ld elements, 4-byte aligned only).  One thread per source float4 chunk, one aligned 16-byte load, up to four dword
+// stores: nothing outside the [n, a] window is written.  n * c4 < 2^31.
+struct ActFieldArgs { const float4* act; int n, c4, a; };
+__global__ __launch_bounds__(256) void k_act_to_field(float* f_act, long act_ld, ActFieldArgs p) {
+  const unsigned total = (unsigned)p.n * (unsigned)p.c4, g = blockIdx.x * 256u + threadIdx.x;
+  if (g >= total) return;
+  const unsigned q = g / (unsigned)p.c4;
+  const int c = (int)(g - q * (unsigned)p.c4), e = 4 * c;
+  float4 v = p.act[g];
+  PIN(v.x); PIN(v.y); PIN(v.z); PIN(v.w);      // one request, one wait, then the stores
+  float* dst = f_act + (long)q * act_ld + e;
+  if (e < p.a) dst[0] = v.x;
+  if (e + 1 < p.a) dst[1] = v.y;
+  if (e + 2 < p.a) dst[2] = v.z;
+  if (e + 3 < p.a) dst[3] = v.w;
+}
+
 struct FillArgs { float4* ring; int rec4, cx, cn, o, a; long n; unsigned long long seed; const float* min_ac; const float* max_ac; };
 __global__ __launch_bounds__(256) void k_rb_fill(FillArgs p) {
   const long g = (long)blockIdx.x * 256 + threadIdx.x;

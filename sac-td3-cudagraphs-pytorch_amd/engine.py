@@ -361,6 +361,23 @@ class Engine:
         self._act_n = 0
         return out[:n].copy()
 
+    def predict_device(self, obs_ptr: int, obs_ld: int, n: int, explore: bool, out_ptr: int, out_ld: int,
+                       caller_stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_predict_device: act on n observation rows that live in this device's memory (`obs_ptr`: device address, `obs_ld`: row
+        stride in elements) and write the actions to device memory (`out_ptr`, `out_ld`) -- asynchronous, stream-ordered behind the
+        updates issued so far, no host wait.  `ordered`: the engine orders its read and the caller's next use of both arrays against
+        `caller_stream` (a hipStream_t as an integer; 0 = the default stream) on the GPU; otherwise the caller has synchronised and
+        leaves both arrays alone until sync()."""
+        self._ck(self.lib.sactd3_predict_device(self._h, C.c_void_p(int(obs_ptr) or None), int(obs_ld), int(n), 1 if explore else 0,
+                                                C.c_void_p(int(out_ptr) or None), int(out_ld), C.c_void_p(int(caller_stream) or None),
+                                                _lib.SRC_ORDERED if ordered else 0))
+
+    def predict_device_stats(self) -> Dict[str, int]:
+        """host counters of the device acting route (sactd3_predict_device_stats)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.sactd3_predict_device_stats(self._h, out))
+        return dict(calls=int(out[0]), rows=int(out[1]), ordered_calls=int(out[2]), multi_block_tails=int(out[3]))
+
     def acting_stats(self) -> Dict[str, int]:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
         out = (C.c_int64 * 4)()

@@ -202,7 +202,8 @@ def job_config(algo: str, env_id: str, seed: int, **over):
     return SimpleNamespace(**cfg)
 
 
-def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False, **over):
+def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
+            device_env: bool = False, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU."""
     import json
     import time
@@ -218,6 +219,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     else:
         make = lambda n: env_factory(env_id, n, seed)
     env, eval_env = make(cfg.num_envs), make(1)
+    if device_env:            # the training env lives on the GPU (loop.DeviceRollout); evaluation keeps its host env and predict()
+        env = loop.SyntheticDeviceVecEnv(o, a, cfg.num_envs, horizon=200, term_at=6.0, bound=bound, device=torch.device("cuda", device_index))
     torch.manual_seed(seed)                                           # main.py:145-146
     rb = ReplayBuffer(cfg.rb_capacity)
     agent = Agent({"ob_shape": (o,), "ac_shape": (a,)}, np.full(a, -bound, np.float32), np.full(a, bound, np.float32),
@@ -226,7 +229,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
     t0 = time.time()
-    metrics = loop.train(cfg, env, agent, fused=True, evaluator=ev, overlap=overlap_acting)
+    metrics = loop.train(cfg, env, agent, fused=True, evaluator=ev, overlap=overlap_acting, device_env=device_env)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -254,7 +257,7 @@ def _worker_main(args) -> int:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
                           eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity,
-                          overlap_acting=args.overlap_acting)
+                          overlap_acting=args.overlap_acting, device_env=args.device_env)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -282,6 +285,8 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=-1, help="run every worker on this device ordinal (one-GPU rehearsals of N workers)")
     ap.add_argument("--overlap_acting", action="store_true",
                     help="compute the next action on the engine's acting stream while the iteration's update runs (loop.train overlap=True)")
+    ap.add_argument("--device_env", action="store_true",
+                    help="train on the GPU-resident synthetic vector env: observations and actions never leave the device (loop.train device_env=True)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)

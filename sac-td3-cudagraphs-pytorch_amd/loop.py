@@ -2,6 +2,7 @@
 be driven end to end without tensordict / torchrl / gymnasium being importable:
 
   Rollout / segment()   the acting side + its generator  orchestrator.py:42-118   
+  DeviceRollout         the same acting side for a vector env that lives on the GPU: every array a device tensor, no host wait
   train()       the training loop's control flow       orchestrator.py:317-352 (+ counters :326,342,349)
   episode()     evaluation-episode generator           orchestrator.py:121-246 (lengths / returns, trajectories with need_lists; no pixels)
   evaluate()    offline evaluation of a checkpoint     orchestrator.py:415-481 (trajectory files as .npz)
@@ -12,7 +13,8 @@ be driven end to end without tensordict / torchrl / gymnasium being importable:
 `step(actions[n, a]) -> (next_obs, rewards[n], terminations[n], truncations[n], infos)` with autoreset and
 `infos["final_observation"][k]` holding the true last observation of an env that just ended, and
 `action_space.sample() -> actions[n, a]`.  `SyntheticVecEnv` below is a dependency-free stand-in of that protocol
-(the image has no gymnasium / MuJoCo); it is a test double, not a port of any environment.
+(the image has no gymnasium / MuJoCo); it is a test double, not a port of any environment.  `SyntheticDeviceVecEnv` is the same
+env on torch tensors of one device, for `DeviceRollout`.
 """
 from __future__ import annotations
 
@@ -91,6 +93,49 @@ class Rollout:
         self.steps += 1
 
 
+class DeviceRollout:
+    """`Rollout` for a vector env that lives on the GPU: observations, actions, rewards and flags are tensors of the engine's device
+    from `env.reset` to `rb.extend`, the action comes from `agent.predict_device`, and nothing in `choose()` / `advance()` copies to
+    the host or waits for the device -- the env's kernels, the acting kernels and the ring append are ordered on the GPU
+    (what the env does inside its own `step` / `action_space.sample()` is the env's business: see SyntheticDeviceVecEnv).
+    Same two half-steps and the same reference behaviour as `Rollout` (orchestrator.py:42-118): one seeded reset; random actions
+    while `agent.timesteps_so_far < learning_starts`, exploring actions afterwards; `action_repeat`; a truncated env stores its
+    true final observation (a select over the truncation mask: `infos["final_observation"]` is an [n, o] tensor here); `dones`
+    are the terminations; [n, 1] float32 / bool fields."""
+
+    def __init__(self, env, agent, seed: int, learning_starts: int, action_repeat: int):
+        assert agent.rb is not None
+        if not callable(getattr(agent, "predict_device", None)):
+            raise TypeError(f"a device env needs an agent with predict_device(); {type(agent).__name__} has none")
+        import torch
+        self._where = torch.where
+        self.env, self.agent = env, agent
+        self.learning_starts, self.action_repeat = learning_starts, action_repeat
+        self.obs, _ = env.reset(seed=seed)
+        self.actions = None
+        self.steps = 0
+
+    def choose(self) -> None:
+        if self.steps % self.action_repeat:
+            return
+        if self.agent.timesteps_so_far < self.learning_starts:
+            self.actions = self.env.action_space.sample()
+        else:
+            self.actions = self.agent.predict_device({"observations": self.obs}, explore=True)
+
+    def resolve(self) -> None:
+        """nothing is ever pending here (the protocol of `Rollout`, for `segment` / `train`)"""
+
+    def advance(self) -> None:
+        arrived, rewards, terminations, truncations, infos = self.env.step(self.actions)
+        stored_next = self._where(truncations.reshape(-1, 1), infos["final_observation"], arrived)
+        ended = terminations.reshape(-1, 1)
+        self.agent.rb.extend({"observations": self.obs, "next_observations": stored_next, "actions": self.actions,
+                              "rewards": rewards.reshape(-1, 1), "terminations": ended, "dones": ended})
+        self.obs = arrived
+        self.steps += 1
+
+
 def segment(env, agent, seed: int, segment_len: int, learning_starts: int, action_repeat: int, overlap: bool = False,
             rollout: Optional[Rollout] = None) -> Generator[None, None, None]:
     """orchestrator.py:42-118 as a generator over `Rollout`: control goes back to the caller every `segment_len` env steps, AFTER
@@ -106,15 +151,21 @@ def segment(env, agent, seed: int, segment_len: int, learning_starts: int, actio
 
 
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
-          evaluator: Optional["Evaluator"] = None, overlap: bool = False) -> Dict[str, float]:
+          evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
     launch (Agent.iteration); `fused=False` makes the reference's individual calls.  Every `eval_every` timesteps
     `evaluator` (the reference's eval block, :354-403) and/or `on_eval` run.  Returns the last metrics.
     `overlap=True` (an agent with predict_begin / predict_end): the action that opens the next segment is computed on the engine's
-    acting stream while this iteration's update runs; a pending action is collected before an evaluation acts with the agent."""
+    acting stream while this iteration's update runs; a pending action is collected before an evaluation acts with the agent.
+    `device_env=True`: `env` lives on the GPU (device tensors in and out, e.g. SyntheticDeviceVecEnv) and is driven by `DeviceRollout`
+    -- `agent.predict_device`, no host round trip per env step.  It acts on the learner stream, so it excludes `overlap`."""
+    if overlap and device_env:
+        raise ValueError("overlap=True and device_env=True exclude each other: predict_device acts on the learner stream")
     ro = Rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat, overlap=True) if overlap else None
+    if device_env:
+        ro = DeviceRollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat)
     seg_gen = segment(env, agent, cfg.seed, cfg.segment_len, cfg.learning_starts, cfg.action_repeat, rollout=ro)
     i = 0
     tlog: Dict[str, Any] = {}
@@ -347,6 +398,27 @@ def evaluate(cfg: Any, env, agent, name: str = "eval", tabular: Optional[Tabular
     return out
 
 
+def _fold_sum(x):
+    """The sum over axis 1 of a numpy array or torch tensor `x` (which it overwrites) in ONE fixed order, by element-wise additions
+    only: the upper half is folded onto the lower until one column is left.  A library reduction or matrix product adds in an order
+    of its own choice; this one gives the same bits in numpy, in torch on the host and in torch on the GPU."""
+    k = x.shape[1]
+    while k > 1:
+        h = k // 2
+        x[:, :h] += x[:, k - h:k]
+        k -= h
+    return x[:, 0]
+
+
+def _dynamics(s, actions, A, Bm, noise):
+    """s' = s A + a B + 0.05 noise and reward = -|s|^2 / o - |a|^2 / a of the synthetic envs, float32, on numpy arrays or torch
+    tensors alike: element-wise products and `_fold_sum`, so that both envs compute the same bits wherever they run."""
+    s2 = _fold_sum(s[:, :, None] * A[None]) + _fold_sum(actions[:, :, None] * Bm[None]) + 0.05 * noise
+    # (means as products with 1 / width: an array library may turn a division by a scalar into one, and then not divide as numpy does)
+    rew = -(_fold_sum(s * s) * (1.0 / s.shape[1])) - (_fold_sum(actions * actions) * (1.0 / actions.shape[1]))
+    return s2, rew
+
+
 class _Box:
     def __init__(self, low, high, n, rng):
         self.low, self.high, self._n, self._rng = low, high, n, rng
@@ -387,8 +459,8 @@ class SyntheticVecEnv:
 
     def step(self, actions):
         actions = np.clip(np.asarray(actions, np.float32).reshape(self.n, self.a), self.action_space.low, self.action_space.high)
-        s2 = self.s @ self.A + actions @ self.Bm + 0.05 * self._rng.standard_normal((self.n, self.o)).astype(np.float32)
-        rew = -(self.s ** 2).mean(1) - (actions ** 2).mean(1)
+        noise = self._rng.standard_normal((self.n, self.o)).astype(np.float32)
+        s2, rew = _dynamics(self.s, actions, self.A, self.Bm, noise)
         self.t += 1
         self.ret += rew
         term = np.abs(s2).max(1) > self.term_at
@@ -405,3 +477,121 @@ class SyntheticVecEnv:
             self.ret[ended] = 0.0
         self.s = s2.astype(np.float32)
         return self.s.copy(), rew.astype(np.float32), term, trunc, infos
+
+
+class _DeviceBox(_Box):
+    """`_Box` whose samples are tensors of one device: the same host generator, so the same actions as the host env's space"""
+
+    def __init__(self, low, high, n, rng, to_device):
+        super().__init__(low, high, n, rng)
+        self._to_device = to_device
+
+    def sample(self):
+        return self._to_device(super().sample())
+
+
+class SyntheticDeviceVecEnv:
+    """`SyntheticVecEnv` on torch tensors of one device (default: the current CUDA device) -- for `DeviceRollout`, and on
+    torch.device("cpu") for tests: same dynamics (`_dynamics`), horizon, termination rule and auto-reset, and with the same seed the
+    same observations, rewards and flags, bit for bit.  `step` takes an [n, a] tensor and returns tensors; nothing in it depends on
+    the host knowing a value the device computed: envs are reset with selects over the `ended` mask, `infos` always holds
+    `final_observation` -- an [n, o] tensor: the observation the step arrived at BEFORE any reset, for every env -- and its mask
+    `_final_observation`; there is no `final_info` (evaluation episodes run on the host env).
+    The host env draws its normals from one numpy generator, k x o fresh ones behind a step in which k envs ended.  The draws come
+    from the same generator here, made on the host in blocks ahead of their use and kept in a device pool; the position in that
+    sequence is a device scalar, advanced by n x o + k x o per step on the device.  The host only knows bounds of it (it grows by
+    one to two times n x o per step): it draws up to the upper one and drops what lies below the lower one; the bounds are tightened
+    from a copy of the device scalar that is requested now and then and used once it has arrived, never waited for.
+    It is a test double: `action_space.sample()` (the random phase before `learning_starts`) and the block of normals drawn every few
+    hundred steps are made by numpy on the host and uploaded from pageable memory, which holds the host for the length of that copy --
+    the only host-side waits of a `DeviceRollout` step on this env, and neither waits for the device's queued work.  The fixed-order
+    sums (`_dynamics`) cost an [n, o, o] temporary per step: at Humanoid's o = 376 the env, not the agent, is what a step of many
+    envs spends its time on."""
+
+    def __init__(self, ob_dim: int, ac_dim: int, num_envs: int, horizon: int = 50, term_at: float = 4.0, bound: float = 1.0,
+                 device: Any = None):
+        import torch
+        self._t = torch
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.o, self.a, self.n, self.horizon, self.term_at = ob_dim, ac_dim, num_envs, horizon, term_at
+        host = SyntheticVecEnv(ob_dim, ac_dim, num_envs, horizon, term_at, bound)           # the same matrices and bounds
+        self.A, self.Bm = self._dev(host.A), self._dev(host.Bm)
+        self.low, self.high = self._dev(host.action_space.low), self._dev(host.action_space.high)
+        self.action_space = _DeviceBox(host.action_space.low, host.action_space.high, num_envs, np.random.default_rng(0), self._dev)
+        self._rng = np.random.default_rng(0)
+        self.num_envs = num_envs
+        no = num_envs * ob_dim
+        self._i_no = torch.arange(no, device=self.device)
+        self._i_o = torch.arange(ob_dim, device=self.device).reshape(1, -1)
+        self._block = max(64 * no, 1 << 16)        # normals drawn per host block
+        self._refresh_every = 256
+
+    def _dev(self, x):
+        return self._t.from_numpy(np.ascontiguousarray(x)).to(self.device)
+
+    def _draw_to(self, need: int) -> None:
+        """make the pool hold the sequence of normals up to position `need`"""
+        if self._drawn < need:
+            k = max(need - self._drawn, self._block)
+            self._pool = self._t.cat([self._pool, self._dev(self._rng.standard_normal(k).astype(np.float32))])
+            self._drawn += k
+
+    def _snapshot(self):
+        """a copy of the position that the host may read later without waiting: -> (holder, arrived())"""
+        if self.device.type == "cpu":
+            return self._cur.clone(), lambda: True
+        self._cur_host.copy_(self._cur, non_blocking=True)              # pinned: the copy is asynchronous
+        ev = self._t.cuda.Event()
+        ev.record(self._t.cuda.current_stream(self.device))
+        return self._cur_host, ev.query
+
+    def _tighten(self) -> None:
+        """Every `_refresh_every` steps a copy of the position is requested; once it has arrived (asked, never waited for) the
+        bounds restart from it, widened by the steps taken since.  Then the normals below the lower bound are dropped."""
+        no = self.n * self.o
+        if self._ask is None:
+            if self._steps % self._refresh_every == 0:
+                self._ask = self._snapshot() + (self._steps,)
+        elif self._ask[1]():
+            d, at = self._steps - self._ask[2], int(self._ask[0])
+            self._lo, self._hi, self._ask = at + d * no, at + 2 * d * no, None
+        if self._lo - self._base >= self._block:                 # no step can ask for these again
+            self._pool = self._pool[self._lo - self._base:].clone()
+            self._base = self._lo
+
+    def reset(self, seed=None):
+        t = self._t
+        if seed is not None:
+            self._rng = np.random.default_rng(seed)
+        no = self.n * self.o
+        self._pool, self._base, self._drawn = t.empty(0, dtype=t.float32, device=self.device), 0, 0
+        self._draw_to(no)
+        self.s = self._pool[:no].reshape(self.n, self.o).clone()
+        self.t = t.zeros(self.n, dtype=t.int64, device=self.device)
+        self._cur = t.full((), no, dtype=t.int64, device=self.device)         # position in the sequence of normals
+        self._lo = self._hi = no
+        self._steps, self._ask = 0, None
+        if self.device.type != "cpu":
+            self._cur_host = t.zeros((), dtype=t.int64).pin_memory()
+        return self.s.clone(), {}
+
+    def step(self, actions):
+        t, n, o = self._t, self.n, self.o
+        no = n * o
+        self._tighten()
+        self._draw_to(self._hi + 2 * no)
+        actions = t.clamp(actions.to(t.float32).reshape(n, self.a), self.low, self.high)
+        at = self._cur - self._base
+        noise = self._pool[at + self._i_no].reshape(n, o)
+        s2, rew = _dynamics(self.s, actions, self.A, self.Bm, noise)
+        self.t = self.t + 1
+        term = s2.abs().amax(1) > self.term_at
+        trunc = (self.t >= self.horizon) & ~term
+        ended = term | trunc
+        rank = t.cumsum(ended.to(t.int64), 0) - 1                # the k-th env that ended takes the k-th row of fresh normals
+        fresh = self._pool[(at + no + t.clamp(rank, min=0) * o).reshape(-1, 1) + self._i_o]
+        self.s = t.where(ended.reshape(-1, 1), fresh, s2)
+        self.t = t.where(ended, t.zeros_like(self.t), self.t)
+        self._cur = self._cur + no + ended.sum() * o
+        self._lo, self._hi, self._steps = self._lo + no, self._hi + 2 * no, self._steps + 1
+        return self.s.clone(), rew, term, trunc, {"final_observation": s2, "_final_observation": ended}

@@ -5,8 +5,8 @@ OTHER_CHECKOUT is another checkout of this repository with its own built libsact
 package is imported under a second module name, so each build runs through its own Python binding; one engine per build, and every
 measurement alternates between the two live engines, 9 rounds, the order reversed every round.  Two processes of the SAME build
 differ by more than most changes are worth (a 4-row predict: 15.0 .. 16.6 us from one process to the next); two engines in one
-process share the clocks, the runtime and the moment.  Measures what both builds have: the predict round trip, the step-only rate
-and the serial acting loops (a) predict -> rb_extend -> step and (b) predict -> step -> rb_extend.  One JSON object per workload."""
+process share the clocks, the runtime and the moment.  Measures what both builds have: the predict round trip, the step-only rate,
+the rate of whole periods (sactd3_step_period, in iterations per second) and the serial acting loops (a) predict -> rb_extend -> step and (b) predict -> step -> rb_extend.  One JSON object per workload."""
 import importlib.util
 import json
 import os
@@ -66,6 +66,7 @@ def compare(name, pkgs):
 
     forms = {"predict_us": lambda e: 1e6 / rate(e, lambda i: e.predict(ob, True), 300),
              "step_per_s": lambda e: rate(e, lambda i: e.step(i % 3 == 0)),
+             "period_iters_per_s": lambda e: 3 * rate(e, lambda i: e.step_period(), 200),
              "loop_a_per_s": lambda e: rate(e, lambda i: (e.predict(ob, True), e.rb_extend(*rows), e.step(i % 3 == 0))),
              "loop_b_per_s": lambda e: rate(e, lambda i: (e.predict(ob, True), e.step(i % 3 == 0), e.rb_extend(*rows)))}
     for e in engs.values():          # warm: signal pools of the async copies, graphs, clocks
