@@ -163,6 +163,42 @@ int sactd3_load_batch_device(sactd3_engine* e, const sactd3_device_fields* f, in
  * of range.  Like the other sactd3_rb_* calls they neither wait for nor are waited for by an acting call in flight.
  * host counters: out = {device-field extends, rows they appended, device batches staged, calls that inserted event waits} */
 int sactd3_boundary_stats(const sactd3_engine* e, int64_t out[4]);
+/* ---- the device boundary, outwards: the reference's rb.sample() returns a DEVICE TensorDict (main.py:167-171:
+ * LazyTensorStorage(capacity, device); orchestrator.py:338), and whatever is written against it -- an auxiliary loss, a logging hook on
+ * batch["rewards"], a sampler of its own that relabels or chains ring rows -- does torch math on device tensors.  The two calls below hand
+ * the batch slot and ring records out where they are: six arrays in the memory of the engine's device, each with a row stride in
+ * elements (>= its width), a contiguous inner dimension and no alignment beyond its element type's (4 bytes for the floats, 8 for the
+ * index, 1 for the flags); a NULL pointer means that field is not wanted.  One kernel launch on the learner stream fills all of them and
+ * writes nothing outside the [n, width] windows; no copy command, no wait or synchronisation on the host. */
+typedef struct sactd3_device_fields_out {   /* device pointers (NULL = field not wanted); *_ld = row stride in elements */
+  float* obs;      int64_t obs_ld;
+  float* actions;  int64_t actions_ld;
+  float* rewards;  int64_t rewards_ld;
+  float* next_obs; int64_t next_obs_ld;
+  uint8_t* dones;  int64_t dones_ld;        /* bytes 0 / 1 (torch.bool storage) */
+  int64_t* index;  int64_t index_ld;        /* the ring slot of every row */
+} sactd3_device_fields_out;
+/* flags: order the write against `consumer_stream` -- the hipStream_t on which the caller last used the destinations (and produced `idx`,
+ * and on which its allocator hands the blocks out) and will read them next -- with the same bit and the same two events as
+ * SACTD3_SRC_ORDERED: the learner stream first waits for what the caller has queued there, and `consumer_stream` then waits for an event
+ * recorded behind the launch, so the caller may read the arrays on it at once.  Without the flag nothing is inserted: the caller has
+ * synchronised, and calls sactd3_sync before it reads. */
+#define SACTD3_DST_ORDERED 1
+/* the batch slot sactd3_read_batch reports (the most recent iteration's), n = batch_size rows: the destinations hold, bit for bit, what
+ * sactd3_read_batch returns at the same position of the call sequence. */
+int sactd3_read_batch_device(sactd3_engine* e, const sactd3_device_fields_out* f, void* consumer_stream, int flags);
+/* n >= 1 ring records chosen by a DEVICE int64 array (`idx[i * idx_ld]`: the ring slot, what `index` of a sample and the argument of
+ * sactd3_rb_sample_with_indices mean), for a replay sampler the engine does not own.  Indices are checked on the device against the
+ * ring length at the call: a row whose index is outside [0, sactd3_rb_len) is handed out as zeros with flag 0 and its index as given,
+ * and counted (sactd3_readout_stats); it never becomes an address.  SACTD3_ESTATE on an empty ring. */
+int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, int n, const sactd3_device_fields_out* f,
+                               void* consumer_stream, int flags);
+/* Both: SACTD3_EINVAL for all six destinations NULL, a stride below the width, a non-NULL pointer (or `idx`) that is not memory of the
+ * engine's device, n < 1, an unknown flag; the engine stays usable.  A read-out changes nothing an update depends on: the batch slot, the
+ * sample counter and a precomputed opening pair of sactd3_step_period stay as they are.  Like the other sactd3_rb_* calls they neither
+ * wait for nor are waited for by an acting call in flight.
+ * [sync] out = {batch read-outs, row read-outs, rows requested, rows refused for their index (counted on the device)} */
+int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]);
 /* rb.sample(batch_size) (orchestrator.py:338): uniform-with-replacement indices from the engine's
  * Philox stream + gather into the engine-owned batch slot. */
 int sactd3_rb_sample(sactd3_engine* e);
@@ -290,7 +326,9 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
  * measured with hipEvents on the engine's stream: "gather" (a fresh index draw per launch), "polyak", "trunk_critics" (the 4-net
  * hidden-layer launch of update_qnets; on wide inputs it is two launches), "batch_from_fields" / "rb_ingest_fields" (the device-boundary
  * pack kernels on batch_size / max_envs rows of the engine's own staging slab; they overwrite the batch slot / append to the ring),
- * "obs_from_field" / "act_to_field" (the pack / unpack kernels of sactd3_predict_device on max_envs rows of engine-owned memory). [sync] */
+ * "obs_from_field" / "act_to_field" (the pack / unpack kernels of sactd3_predict_device on max_envs rows of engine-owned memory),
+ * "batch_to_fields" / "rows_to_fields" (the read-out kernels of sactd3_read_batch_device / sactd3_rb_read_rows_device on batch_size rows,
+ * written into the engine's own staging slab; the rows kernel takes its indices from the current slot's, widened to int64). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

@@ -15,6 +15,7 @@ SITE_CRITIC, SITE_ACTOR0, SITE_ACTOR1, SITE_ALPHA0, SITE_ALPHA1, SITE_PREDICT = 
 NUM_METRICS = 8
 ACT_AFTER_ALL = 1   # sactd3_predict_begin flags
 SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device / sactd3_predict_device flags
+DST_ORDERED = 1     # sactd3_read_batch_device / sactd3_rb_read_rows_device flags (the same bit, the same two events)
 ESTATE, EINVAL = -3, -1
 
 # every symbol include/sactd3.h declares (tests/test_abi.py checks the header against this list)
@@ -29,6 +30,7 @@ SYMBOLS = [
     "sactd3_predict_begin", "sactd3_predict_end", "sactd3_acting_stats",
     "sactd3_rb_extend_fields_device", "sactd3_load_batch_device", "sactd3_boundary_stats",
     "sactd3_predict_device", "sactd3_predict_device_stats",
+    "sactd3_read_batch_device", "sactd3_rb_read_rows_device", "sactd3_readout_stats",
 ]
 
 
@@ -48,6 +50,11 @@ class CConfig(C.Structure):
 class CDeviceFields(C.Structure):
     """sactd3_device_fields: five device pointers, each with its row stride in elements"""
     _fields_ = [(n, t) for f in ("obs", "actions", "rewards", "next_obs", "dones") for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
+
+
+class CDeviceFieldsOut(C.Structure):
+    """sactd3_device_fields_out: six device pointers (None = field not wanted), each with its row stride in elements"""
+    _fields_ = [(n, t) for f in ("obs", "actions", "rewards", "next_obs", "dones", "index") for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
 
 
 def library_path() -> str:
@@ -119,6 +126,9 @@ def load_library():
         "sactd3_boundary_stats": (C.c_int, [vp, i64p]),
         "sactd3_predict_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int]),
         "sactd3_predict_device_stats": (C.c_int, [vp, i64p]),
+        "sactd3_read_batch_device": (C.c_int, [vp, C.POINTER(CDeviceFieldsOut), vp, C.c_int]),
+        "sactd3_rb_read_rows_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.POINTER(CDeviceFieldsOut), vp, C.c_int]),
+        "sactd3_readout_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

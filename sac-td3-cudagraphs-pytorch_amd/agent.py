@@ -92,6 +92,64 @@ def _device_route(engine: Engine, obs, act, rew, nobs, done):
     return fields, rows[0], keep
 
 
+# the six destinations of a read-out, in the order of sactd3_device_fields_out: (key, width -- "o" / "a" = the engine's dims --, kind)
+_OUT_FIELDS = (("observations", "o", "f4"), ("actions", "a", "f4"), ("rewards", 1, "f4"), ("next_observations", "o", "f4"),
+               ("dones", 1, "b1"), ("index", 1, "i8"))
+_OUT_ITEM = {"f4": 4, "b1": 1, "i8": 8}
+
+
+def _torch_alloc(engine: Engine):
+    import torch
+    dev = torch.device("cuda", int(engine.cfg.device_id))
+    kinds = {"f4": torch.float32, "b1": torch.bool, "i8": torch.int64}
+    return lambda shape, kind: torch.empty(shape, dtype=kinds[kind], device=dev)
+
+
+def _device_outputs(engine: Engine, n: int, out: Optional[Mapping[str, Any]] = None, alloc=None):
+    """The one place that decides where a read-out lands.  -> (tensors, fields): `tensors` has the reference's keys -- observations
+    [n, o], actions [n, a], rewards [n, 1], next_observations [n, o] float32; dones [n, 1] bool, terminations (the same array, as the
+    reference stores it); index [n] int64 -- and `fields` the six (device address, row stride in elements) pairs for
+    Engine.read_batch_device / rb_read_rows_device.  Arrays come from `alloc(shape, kind)` (default: torch.empty on the engine's
+    device); `out` may replace any of them with a preallocated array or view (rewards / dones / index as [n, 1] or [n]; `terminations`
+    names the dones array).  Pointer, shape and strides come from __cuda_array_interface__.  An output cannot be converted the way an
+    input can: a wrong dtype or another device's array is a TypeError, a wrong shape or an inner stride a ValueError."""
+    out = dict(out) if out else {}
+    known = {k for k, _, _ in _OUT_FIELDS} | {"terminations"}
+    if set(out) - known:
+        raise ValueError(f"unknown output key(s) {sorted(set(out) - known)}: expected a subset of {sorted(known)}")
+    if "terminations" in out:
+        if "dones" in out and out["dones"] is not out["terminations"]:
+            raise ValueError("`dones` and `terminations` are one array (the reference stores the same flags under both keys)")
+        out["dones"] = out.pop("terminations")
+    dims = {"o": int(engine.cfg.ob_dim), "a": int(engine.cfg.ac_dim)}
+    tensors, fields = {}, []
+    for key, width, kind in _OUT_FIELDS:
+        width = dims.get(width, width)
+        x = out.get(key)
+        if x is None:
+            if alloc is None:
+                alloc = _torch_alloc(engine)
+            x = alloc((n,) if key == "index" else (n, width), kind)
+        cai = _cai(x.detach() if hasattr(x, "detach") else x)
+        if cai is None or not _on_engine_device(engine, x):
+            raise TypeError(f"`{key}` must be an array in the memory of the engine's device")
+        typestr, item = cai["typestr"], _OUT_ITEM[kind]
+        if (kind == "b1" and int(typestr[2:]) != 1) or (kind != "b1" and typestr[1:] != kind):
+            raise TypeError(f"`{key}` must be " + {"f4": "float32", "b1": "bool (one byte per flag)", "i8": "int64"}[kind] + f", got {typestr}")
+        try:
+            got = _cai_field(cai, width, item)
+        except ValueError as ex:
+            raise ValueError(f"`{key}`: {ex}") from None
+        if got is None:
+            raise ValueError(f"`{key}` needs a contiguous inner dimension and a row stride of at least its width")
+        if got[1] != n:
+            raise ValueError(f"`{key}` has {got[1]} rows, expected {n}")
+        tensors[key] = x
+        fields.append((got[0], got[2]))
+    tensors["terminations"] = tensors["dones"]
+    return tensors, fields
+
+
 def _producer_stream(x, device_id: int) -> int:
     """the stream the caller's arrays were written on, as far as the array library tells: torch's current stream of the device"""
     if type(x).__module__.partition(".")[0] == "torch":
@@ -139,18 +197,34 @@ class StaleBatchError(RuntimeError):
 class BatchHandle(dict):
     """What `rb.sample()` returns: the batch lives in the engine's HBM batch slot; indexing a key reads it back
     (host sync) as the reference's TensorDict keys would (observations, actions, rewards, next_observations,
-    terminations, dones, index)."""
+    terminations, dones, index).  `on_device()` -- and key access on a handle of ReplayBuffer(..., device_batches=True) -- hands
+    the same keys out as device tensors instead, as the reference's rb.sample() does (main.py:167-171, orchestrator.py:338)."""
 
-    def __init__(self, engine: Engine, generation: int = 0):
+    def __init__(self, engine: Engine, generation: int = 0, device: bool = False):
         super().__init__()
         self._engine = engine
         self._generation = generation      # which rb.sample() filled the batch slot when this handle was made (see StaleBatchError)
-        self._cache: Optional[Dict[str, np.ndarray]] = None
+        self._device = device              # key access: device tensors (one read-out launch, cached) instead of numpy arrays
+        self._cache: Optional[Dict[str, Any]] = None
 
     def _is_current(self) -> bool:
         return getattr(self._engine, "_batch_generation", 0) == self._generation
 
+    def on_device(self, out: Optional[Mapping[str, Any]] = None) -> Dict[str, Any]:
+        """The batch as a dict of tensors on the engine's device (include/sactd3.h: sactd3_read_batch_device), all keys filled by ONE
+        launch on the engine's stream: nothing goes through the host and the host does not wait.  The write is ordered on the GPU
+        against torch's current stream, which may use the tensors at once.  `out`: preallocated tensors or views (any subset of the
+        keys) to write into.  Raises StaleBatchError where the host read-back does."""
+        if not self._is_current():
+            raise StaleBatchError("this batch handle is older than the engine's batch slot: a later rb.sample() / staged batch replaced its rows")
+        eng = self._engine
+        tensors, fields = _device_outputs(eng, int(eng.cfg.batch_size), out)
+        eng.read_batch_device(fields, _producer_stream(tensors["observations"], eng.cfg.device_id))
+        return tensors
+
     def __missing__(self, key):
+        if self._cache is None and self._device:
+            self._cache = self.on_device()
         if self._cache is None:
             if not self._is_current():
                 raise StaleBatchError("this batch handle is older than the engine's batch slot: a later rb.sample() / staged batch replaced its rows")
@@ -165,8 +239,10 @@ class ReplayBuffer:
     """TensorDictReplayBuffer(storage=LazyTensorStorage(capacity, device)) stand-in (main.py:167-171): built by
     the caller BEFORE the agent, bound to the engine's HBM ring when the agent receives it."""
 
-    def __init__(self, capacity: int, device: Any = None):
-        self.capacity, self.device = int(capacity), device
+    def __init__(self, capacity: int, device: Any = None, device_batches: bool = False):
+        """`device_batches`: sample() returns handles whose keys are tensors on the engine's device, as the reference's are (the
+        first key access fills all of them with one launch); the default keeps the host read-back to numpy arrays."""
+        self.capacity, self.device, self.device_batches = int(capacity), device, bool(device_batches)
         self._engine: Optional[Engine] = None
 
     def _bind(self, engine: Engine):
@@ -192,7 +268,28 @@ class ReplayBuffer:
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
         eng.rb_sample()
         eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1
-        return BatchHandle(eng, eng._batch_generation)
+        return BatchHandle(eng, eng._batch_generation, device=self.device_batches)
+
+    def rows(self, index, out: Optional[Mapping[str, Any]] = None) -> Dict[str, Any]:
+        """The ring records `index` names (ring slots: what `index` of a sample holds), as a dict of tensors on the engine's device
+        with the keys of a batch -- for a sampler of the caller's own (prioritised, n-step, hindsight) that reads the rows it relabels
+        or chains where they are (include/sactd3.h: sactd3_rb_read_rows_device).  `index`: an int64 tensor on the engine's device, any
+        length >= 1, or anything torch can turn into one (uploaded first).  A slot outside [0, len(rb)) yields a zero row with flag
+        False.  `out` as for BatchHandle.on_device."""
+        eng = self._need()
+        cai = _cai(index.detach() if hasattr(index, "detach") else index)
+        if cai is None or not _on_engine_device(eng, index) or cai["typestr"][1:] != "i8":
+            import torch
+            index = torch.as_tensor(index, dtype=torch.int64).to(torch.device("cuda", int(eng.cfg.device_id)))
+            cai = _cai(index)
+        got = _cai_field(cai, 1, 8)
+        if got is None:
+            index = index.contiguous()
+            got = _cai_field(_cai(index), 1, 8)
+        ptr, n, ld = got
+        tensors, fields = _device_outputs(eng, n, out)
+        eng.rb_read_rows_device(ptr, ld, n, fields, _producer_stream(index, eng.cfg.device_id))
+        return tensors
 
     def __len__(self) -> int:
         return 0 if self._engine is None else self._engine.rb_len()
@@ -286,7 +383,7 @@ class Agent:
             if not batch._is_current():
                 raise StaleBatchError("update called with an old batch handle: the engine's batch slot holds a later sample "
                                       "(keep the rows, e.g. dict(handle), to train on them again)")
-            return  # already in the engine's batch slot
+            return  # already in the engine's batch slot (a device-backed handle too: its tensors are copies OF the slot)
         self.engine._batch_generation = getattr(self.engine, "_batch_generation", 0) + 1   # a caller-owned batch replaces the slot
         five = (batch["observations"], batch["actions"], batch["rewards"], batch["next_observations"], batch["dones"])
         dev = _device_route(self.engine, *five)

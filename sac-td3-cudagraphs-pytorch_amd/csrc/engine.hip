@@ -156,6 +156,10 @@ struct sactd3_engine {
   // against the caller's producer stream, created at the first SACTD3_SRC_ORDERED call, and the host counters of sactd3_boundary_stats.
   hipEvent_t ev_src_ready = nullptr, ev_src_read = nullptr;
   int64_t bnd_stats[4] = {};
+  // The same boundary outwards (sactd3_read_batch_device / sactd3_rb_read_rows_device): host counters of sactd3_readout_stats
+  // {batch read-outs, row read-outs, rows requested}; the fourth, rows refused, is DevCtl::readout_refused.
+  int64_t ro_stats[3] = {};
+  long long* time_idx = nullptr;                // sactd3_time_kernel("rows_to_fields"): its index array
   // Acting on device observations (sactd3_predict_device): [explore][n] graphs of the acting pair on p_x / p_act -- they hold no
   // caller pointer -- and the host counters of sactd3_predict_device_stats.
   std::vector<hipGraphExec_t> predict_dev_graphs;
@@ -1834,6 +1838,118 @@ int sactd3_read_batch(sactd3_engine* e, float* obs, float* act, float* rew, floa
   return 0;
 }
 
+// ---- the device boundary, outwards: a batch slot / ring rows into the caller's six arrays in this device's memory (include/sactd3.h)
+static int fields_out_check(sactd3_engine* e, const sactd3_device_fields_out* f, const char* what) {
+  const struct { const void* p; int64_t ld; int width; const char* name; } fld[6] = {
+      {f->obs, f->obs_ld, e->o, "obs"}, {f->actions, f->actions_ld, e->a, "actions"}, {f->rewards, f->rewards_ld, 1, "rewards"},
+      {f->next_obs, f->next_obs_ld, e->o, "next_obs"}, {f->dones, f->dones_ld, 1, "dones"}, {f->index, f->index_ld, 1, "index"}};
+  int wanted = 0;
+  for (const auto& x : fld) {
+    if (!x.p) continue;
+    ++wanted;
+    if (x.ld < x.width) { e->err = std::string(what) + ": row stride of `" + x.name + "` is below its width"; return SACTD3_EINVAL; }
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, x.p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
+      (void)hipGetLastError();
+      e->err = std::string(what) + ": `" + x.name + "` is not device memory of the engine's device";
+      return SACTD3_EINVAL;
+    }
+  }
+  if (!wanted) { e->err = std::string(what) + ": all six destinations (obs, actions, rewards, next_obs, dones, index) are NULL"; return SACTD3_EINVAL; }
+  return 0;
+}
+static FieldDst field_dst(const sactd3_engine* e, const sactd3_device_fields_out* f, int64_t row0) {
+  FieldDst d{};
+  d.obs = f->obs ? f->obs + row0 * f->obs_ld : nullptr; d.act = f->actions ? f->actions + row0 * f->actions_ld : nullptr;
+  d.rew = f->rewards ? f->rewards + row0 * f->rewards_ld : nullptr; d.nobs = f->next_obs ? f->next_obs + row0 * f->next_obs_ld : nullptr;
+  d.done = f->dones ? f->dones + row0 * f->dones_ld : nullptr; d.index = f->index ? (long long*)f->index + row0 * f->index_ld : nullptr;
+  d.obs_ld = (long)f->obs_ld; d.act_ld = (long)f->actions_ld; d.rew_ld = (long)f->rewards_ld; d.nobs_ld = (long)f->next_obs_ld;
+  d.done_ld = (long)f->dones_ld; d.index_ld = (long)f->index_ld;
+  d.o = e->o; d.a = e->a; d.cx = e->cx; d.cn = e->cn;
+  return d;
+}
+static int launch_batch_out(sactd3_engine* e, const FieldDst& dst) {
+  const sactd3_engine::BatchSlot& S = e->bs[e->cur_slot];      // the slot sactd3_read_batch reports
+  const BatchOutArgs g{(const float4*)S.X, (const float4*)S.Xn, S.rew, S.done, S.idx, e->B};
+  const long chunks = (long)e->B * (e->cx + e->cn + 1);      // (< B * rec4 < 2^31: create_impl)
+  hipLaunchKernelGGL(k_batch_to_fields, dim3((unsigned)((chunks + 256L * TOFIELDS_CPT - 1) / (256L * TOFIELDS_CPT))), dim3(256), 0, e->stream, dst, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// rows [0, n) of `idx` (n * rec4 < 2^31), `len` = the ring length the indices are checked against
+static int launch_rows_out(sactd3_engine* e, const FieldDst& dst, const long long* idx, int64_t idx_ld, int n, int len) {
+  RowsOutArgs g{};
+  g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.n = n; g.len = len; g.idx = idx; g.idx_ld = (long)idx_ld;
+  const long chunks = (long)n * e->rec4;
+  g.rec4_magic = magic_div((unsigned)e->rec4, (unsigned long long)chunks + 1);
+  const unsigned blocks = gather_blocks(chunks);
+  g.cpb = (int)((chunks + 256L * blocks - 1) / (256L * blocks));
+  g.refused = &e->ctl->readout_refused;
+  hipLaunchKernelGGL(k_rows_to_fields, dim3(blocks), dim3(256), 0, e->stream, dst, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// rb.sample()'s batch as the reference hands it out -- on the device (main.py:167-171, orchestrator.py:338): one k_batch_to_fields launch
+// on the learner stream copies the current slot to the caller's arrays.  No host wait, no copy command; it changes nothing an update
+// or a precomputed opening pair depends on, so the run-ahead chain stays intact.
+int sactd3_read_batch_device(sactd3_engine* e, const sactd3_device_fields_out* f, void* consumer_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!f) return e->fail(SACTD3_EINVAL, "read_batch_device: bad argument");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "read_batch_device: unknown flag");
+  RCCHK(fields_out_check(e, f, "read_batch_device"));
+  const hipStream_t consumer = (hipStream_t)consumer_stream;
+  RCCHK(src_order_begin(e, consumer, flags));
+  RCCHK(launch_batch_out(e, field_dst(e, f, 0)));
+  RCCHK(src_order_end(e, consumer, flags));
+  ++e->ro_stats[0];
+  return 0;
+}
+
+// ring records by index, for a sampler the engine does not own (prioritised / n-step / hindsight: it reads the rows it relabels or
+// chains where they are): one k_rows_to_fields launch per at most (2^31 - 1) / rec4 rows.
+int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, int n, const sactd3_device_fields_out* f,
+                               void* consumer_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!f || !idx) return e->fail(SACTD3_EINVAL, "rb_read_rows_device: bad argument (`idx` or the field block is NULL)");
+  USE_DEVICE(e);
+  if (n < 1) return e->fail(SACTD3_EINVAL, "rb_read_rows_device: n >= 1 required");
+  if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "rb_read_rows_device: unknown flag");
+  if (idx_ld < 1) return e->fail(SACTD3_EINVAL, "rb_read_rows_device: row stride of `idx` is below its width");
+  RCCHK(fields_out_check(e, f, "rb_read_rows_device"));
+  {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, idx) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
+      (void)hipGetLastError();
+      return e->fail(SACTD3_EINVAL, "rb_read_rows_device: `idx` is not device memory of the engine's device");
+    }
+  }
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_read_rows_device: buffer is empty");
+  const hipStream_t consumer = (hipStream_t)consumer_stream;
+  const int64_t per_launch = ((1ll << 31) - 1) / e->rec4;
+  RCCHK(src_order_begin(e, consumer, flags));
+  for (int done_rows = 0; done_rows < n;) {
+    const int chunk = (int)std::min<int64_t>(n - done_rows, per_launch);
+    RCCHK(launch_rows_out(e, field_dst(e, f, done_rows), (const long long*)idx + (int64_t)done_rows * idx_ld, idx_ld, chunk, (int)e->rb_len));
+    done_rows += chunk;
+  }
+  RCCHK(src_order_end(e, consumer, flags));
+  ++e->ro_stats[1]; e->ro_stats[2] += n;
+  return 0;
+}
+
+int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int refused = 0;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(&refused, &e->ctl->readout_refused, sizeof(int), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 3; ++i) out[i] = e->ro_stats[i];
+  out[3] = refused;
+  return 0;
+}
+
 int sactd3_rb_fill_synthetic(sactd3_engine* e, int64_t n, uint64_t seed) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
@@ -2346,6 +2462,20 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph) {
   return e->graph_nodes[w];
 }
 
+// sactd3_time_kernel("rows_to_fields"): the current slot's idx widened to int64 in a device array of the engine's own (made at the
+// first use), folded into [0, rb_len) so that a slot filled by sactd3_load_batch on a short ring does not count as refused rows
+static int time_rows_indices(sactd3_engine* e) {
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_kernel: buffer is empty");
+  if (!e->time_idx) RCCHK(dalloc(e, &e->time_idx, (size_t)e->B));
+  std::vector<int> h(e->B);
+  std::vector<long long> w(e->B);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(h.data(), e->bs[e->cur_slot].idx, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
+  for (int b = 0; b < e->B; ++b) w[b] = (long long)((h[b] < 0 ? 0 : h[b]) % e->rb_len);
+  HIPCHK(hipMemcpy(e->time_idx, w.data(), sizeof(long long) * w.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec) {
   if (!e || !kernel || !usec || iters < 1) return SACTD3_EINVAL;
   USE_DEVICE(e);
@@ -2381,8 +2511,20 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
     // row stride = the record), actions written to the acting scratch p_z1 (row stride = its 256 columns; the next trunk overwrites it)
     if (!strcmp(kernel, "obs_from_field")) return launch_obs_pack(e, e->ring, e->rec_f, (int)std::min<int64_t>(e->maxn, e->cfg.rb_capacity));
     if (!strcmp(kernel, "act_to_field")) return launch_act_unpack(e, e->p_z1, HID, e->maxn);
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field)");
+    if (!strcmp(kernel, "batch_to_fields") || !strcmp(kernel, "rows_to_fields")) {
+      // the read-out kernels on batch_size rows, written into the engine's own staging slab as six strided fields (the mirror image
+      // of the pack kernels' sources above; the index goes to the two pad floats behind [r, d], which are 8-byte aligned); the rows
+      // kernel takes its indices from time_idx (the current slot's idx, widened: prepared below, before anything is timed)
+      sactd3_device_fields_out f{};
+      f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
+      f.dones = (uint8_t*)(e->stage_dev + e->ldc + e->ldo + 1); f.index = (int64_t*)(e->stage_dev + e->ldc + e->ldo + 2);
+      f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f; f.index_ld = e->rec_f / 2;
+      if (!strcmp(kernel, "batch_to_fields")) return launch_batch_out(e, field_dst(e, &f, 0));
+      return launch_rows_out(e, field_dst(e, &f, 0), e->time_idx, 1, e->B, (int)e->rb_len);
+    }
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields)");
   };
+  if (!strcmp(kernel, "rows_to_fields")) rc = time_rows_indices(e);
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up
   if (rc == 0) {
     hipEventRecord(t0, e->stream);

@@ -97,8 +97,13 @@ struct DevCtl {
   alignas(128) int predict_ctr;   // noise-stream counter of SACTD3_SITE_PREDICT, bumped once per exploring call
   int predict_seq;    // completed single-block acting calls (the acting tail publishes it to a pinned host word, see ActorTail::done_flag)
   int pad_acting[30];
+  // The word k_rows_to_fields adds to (atomicAdd, once per refused row), behind everything else and on a line of its own for the same
+  // reason: a read-out on the learner stream may run beside acting kernels on other XCDs.
+  alignas(128) int readout_refused;   // rows whose ring index was outside [0, len): handed out as zeros (sactd3_readout_stats)
+  int pad_readout[31];
 };
 static_assert(offsetof(DevCtl, predict_ctr) % 128 == 0 && sizeof(DevCtl) % 128 == 0, "acting words need a line of their own");
+static_assert(offsetof(DevCtl, readout_refused) % 128 == 0 && offsetof(DevCtl, readout_refused) == offsetof(DevCtl, predict_ctr) + 128, "the read-out word sits behind the existing ones");
 
 struct NetLayout {   // float offsets inside one net's parameter block (all multiples of 4)
   int K, ld1, nh;
@@ -530,6 +535,123 @@ __global__ __launch_bounds__(256) void k_batch_from_fields(FIELD_PARAMS, BatchFi
     if (c < f.cx) p.X[(long)b * f.cx + c] = o4;
     else if (c < f.cx + f.cn) p.Xn[(long)b * f.cx + (c - f.cx)] = o4;
     else { p.rew[b] = o4.x; p.done[b] = o4.y; p.idx[b] = b; }
+  }
+}
+
+// ... and the way OUT (the reference's rb.sample() hands out a device TensorDict, main.py:167-171 / orchestrator.py:338): a batch slot,
+// or ring records chosen by the caller, copied to the caller's six arrays in device memory -- obs [n, o], act [n, a], rew [n], next_obs
+// [n, o], dones [n] bytes 0/1, index [n] int64 -- each with a row stride in elements, a contiguous inner dimension and no alignment
+// beyond its element's; a NULL array is not wanted.  The mirror image of the two pack kernels: one thread per SOURCE float4 chunk, one
+// aligned 16-byte load, then up to four dword stores, each to the field its float belongs to (a chunk may hold the end of s and the
+// start of a); pad floats and pad chunks are stored nowhere, and nothing outside the [n, width] windows is written.  The [r, d] chunk
+// also stores the flag byte and the row's index.  Several chunks per thread, every load out (PIN) before the first store.
+__device__ __forceinline__ float f4c(const float4& v, int i);      // (defined with the GEMM helpers below)
+struct FieldDst {
+  float* obs; float* act; float* rew; float* nobs; unsigned char* done; long long* index;
+  long obs_ld, act_ld, rew_ld, nobs_ld, done_ld, index_ld;
+  int o, a, cx, cn;                       // record chunk c: [0, cx) = [s|a|pad], [cx, cx + cn) = [s'|pad], cx + cn = [r, d, -, -]
+};
+// chunk c of row r holds v (the [r, d] chunk: v.x = reward, v.y = flag as a float); `index`: what the row's index entry gets
+__device__ __forceinline__ void field_st(const FieldDst& d, long r, int c, const float4& v, long long index) {
+  if (c < d.cx) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = 4 * c + i;
+      if (e < d.o) { if (d.obs) d.obs[r * d.obs_ld + e] = f4c(v, i); }
+      else if (e < d.o + d.a) { if (d.act) d.act[r * d.act_ld + (e - d.o)] = f4c(v, i); }
+    }
+  } else if (c < d.cx + d.cn) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = 4 * (c - d.cx) + i;
+      if (e < d.o && d.nobs) d.nobs[r * d.nobs_ld + e] = f4c(v, i);
+    }
+  } else if (c == d.cx + d.cn) {
+    if (d.rew) d.rew[r * d.rew_ld] = v.x;
+    if (d.done) d.done[r * d.done_ld] = v.y != 0.f ? 1 : 0;
+    if (d.index) d.index[r * d.index_ld] = index;
+  }
+}
+
+// One batch slot -> the caller's arrays: what sactd3_read_batch returns, left in device memory.  Chunk c of row b: c < cx from X,
+// c < cx + cn from Xn (its s' columns: the action columns of Xn hold a', which no field owns), c = cx + cn = (rew[b], done[b], idx[b]) --
+// three dword loads every thread issues, from addresses that are always valid (b is a row of the slot), next to its 16-byte one (the
+// [r, d] chunk re-reads chunk 0 of its row); a select keeps what the chunk owns.  B * (cx + cn + 1) < 2^31.
+#define TOFIELDS_CPT 4
+struct BatchOutArgs { const float4* X; const float4* Xn; const float* rew; const float* done; const int* idx; int B; };
+__global__ __launch_bounds__(256) void k_batch_to_fields(FieldDst d, BatchOutArgs p) {
+  const int W = d.cx + d.cn + 1;
+  const unsigned total = (unsigned)p.B * (unsigned)W;      // >= 1
+  int row[TOFIELDS_CPT], cc[TOFIELDS_CPT]; bool on[TOFIELDS_CPT]; float4 v[TOFIELDS_CPT]; float rw[TOFIELDS_CPT], dn[TOFIELDS_CPT]; int ix[TOFIELDS_CPT];
+#pragma unroll
+  for (int u = 0; u < TOFIELDS_CPT; ++u) {
+    const unsigned g = (blockIdx.x * (unsigned)TOFIELDS_CPT + (unsigned)u) * 256u + threadIdx.x;
+    on[u] = g < total;
+    const unsigned gc = min(g, total - 1u), q = gc / (unsigned)W;      // (a chunk past the end reads what the last one reads)
+    row[u] = (int)q; cc[u] = (int)(gc - q * (unsigned)W);
+  }
+#pragma unroll
+  for (int u = 0; u < TOFIELDS_CPT; ++u) {
+    const int c = cc[u];
+    const bool nx = c >= d.cx && c < d.cx + d.cn;
+    const float4* src = nx ? p.Xn : p.X;
+    v[u] = src[(long)row[u] * d.cx + (nx ? c - d.cx : (c < d.cx ? c : 0))];
+    rw[u] = p.rew[row[u]]; dn[u] = p.done[row[u]]; ix[u] = p.idx[row[u]];
+  }
+#pragma unroll
+  for (int u = 0; u < TOFIELDS_CPT; ++u) { PIN(v[u].x); PIN(v[u].y); PIN(v[u].z); PIN(v[u].w); PIN(rw[u]); PIN(dn[u]); PIN(ix[u]); }      // every request is out before the first store
+#pragma unroll
+  for (int u = 0; u < TOFIELDS_CPT; ++u) {
+    if (!on[u]) continue;
+    const bool rd = cc[u] == d.cx + d.cn;
+    field_st(d, row[u], cc[u], make_float4(rd ? rw[u] : v[u].x, rd ? dn[u] : v[u].y, v[u].z, v[u].w), (long long)ix[u]);
+  }
+}
+
+// Ring records chosen by a DEVICE int64 index array (the ring slot: what `index` of a sample means) -> the caller's arrays, any n >= 1.
+// gather_body's discipline: a block moves a CONTIGUOUS span of cpb * 256 (row, chunk) pairs, fetches each of its rows' indices once
+// into LDS, then issues all its ring loads, then all its stores.  `len` is the host's ring length at the call (every append issued
+// before it is ahead of this launch on the learner stream).  An index outside [0, len) never becomes an address: the row reads ring
+// slot 0, is stored as zeros with flag 0 and its index as given, and the thread that owns its first chunk counts it in `refused`.
+// The host keeps n * rec4 < 2^31 per launch.
+struct RowsOutArgs {
+  const float4* ring; int rec4; int n; int len;
+  const long long* idx; long idx_ld;      // index of row r: idx[r * idx_ld]
+  unsigned rec4_magic;                    // as GatherArgs
+  int cpb;                                // chunks per thread, <= GATHER_CPT
+  int* refused;                           // DevCtl::readout_refused
+};
+__global__ __launch_bounds__(256) void k_rows_to_fields(FieldDst d, RowsOutArgs p) {
+  __shared__ long long ids_s[GATHER_CPT * 256 + 2];
+  const unsigned total = (unsigned)p.n * (unsigned)p.rec4;
+  const unsigned c0 = blockIdx.x * (unsigned)p.cpb * 256u;
+  if (c0 >= total) return;                                             // (block-uniform)
+  const unsigned c1 = min(c0 + (unsigned)p.cpb * 256u, total);
+  const unsigned r0 = fast_div(c0, (unsigned)p.rec4, p.rec4_magic), r1 = fast_div(c1 - 1u, (unsigned)p.rec4, p.rec4_magic);
+  for (unsigned i = threadIdx.x; i <= r1 - r0; i += 256u) ids_s[i] = p.idx[(long)(r0 + i) * p.idx_ld];
+  __syncthreads();
+  int bb[GATHER_CPT], cc[GATHER_CPT], slot[GATHER_CPT]; long long raw[GATHER_CPT]; float4 v[GATHER_CPT]; bool on[GATHER_CPT], ok[GATHER_CPT], first[GATHER_CPT];
+#pragma unroll
+  for (int u = 0; u < GATHER_CPT; ++u) {            // consecutive threads -> consecutive chunks of a record
+    const unsigned g = c0 + (unsigned)u * 256u + threadIdx.x;
+    on[u] = u < p.cpb && g < c1;
+    const unsigned q = on[u] ? fast_div(g, (unsigned)p.rec4, p.rec4_magic) : r0;
+    bb[u] = (int)q; cc[u] = on[u] ? (int)(g - q * (unsigned)p.rec4) : 0;
+    raw[u] = ids_s[q - r0];
+    ok[u] = raw[u] >= 0 && raw[u] < (long long)p.len;
+    slot[u] = ok[u] ? (int)raw[u] : 0;
+    first[u] = on[u] && cc[u] == 0 && !ok[u];
+    on[u] = on[u] && cc[u] <= d.cx + d.cn;           // trailing pad chunk(s) are not moved
+  }
+#pragma unroll
+  for (int u = 0; u < GATHER_CPT; ++u) v[u] = p.ring[(long)slot[u] * p.rec4 + (on[u] ? cc[u] : 0)];
+#pragma unroll
+  for (int u = 0; u < GATHER_CPT; ++u) { PIN(v[u].x); PIN(v[u].y); PIN(v[u].z); PIN(v[u].w); }      // every request is out before the first store
+#pragma unroll
+  for (int u = 0; u < GATHER_CPT; ++u) {
+    if (first[u]) atomicAdd(p.refused, 1);
+    if (!on[u]) continue;
+    field_st(d, bb[u], cc[u], ok[u] ? v[u] : make_float4(0.f, 0.f, 0.f, 0.f), raw[u]);
   }
 }
 

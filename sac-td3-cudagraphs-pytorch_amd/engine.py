@@ -117,6 +117,7 @@ class Engine:
                     np.zeros((n0, o), np.float32), np.zeros(n0, np.uint8), np.zeros((n0, o), np.float32), np.zeros((n0, a), np.float32)]
         self._st_p = [x.ctypes.data_as(C.POINTER(C.c_uint8) if x.dtype == np.uint8 else _F) for x in self._st]
         self._df = _lib.CDeviceFields()     # argument block of the device-field calls, filled per call
+        self._dfo = _lib.CDeviceFieldsOut()  # ... and of the two read-out calls
 
     # -- plumbing
     def _ck(self, rc):
@@ -233,6 +234,34 @@ class Engine:
         out = (C.c_int64 * 4)()
         self._ck(self.lib.sactd3_boundary_stats(self._h, out))
         return dict(device_extends=int(out[0]), device_rows=int(out[1]), device_batches=int(out[2]), ordered_calls=int(out[3]))
+
+    def _fields_out(self, fields):
+        dfo = self._dfo
+        ((dfo.obs, dfo.obs_ld), (dfo.actions, dfo.actions_ld), (dfo.rewards, dfo.rewards_ld), (dfo.next_obs, dfo.next_obs_ld),
+         (dfo.dones, dfo.dones_ld), (dfo.index, dfo.index_ld)) = [(int(p) or None, int(ld)) for p, ld in fields]
+        return C.byref(dfo)
+
+    def read_batch_device(self, fields, consumer_stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_read_batch_device: the batch slot read_batch() reports, left in this device's memory.  `fields` = (device address,
+        row stride in elements) of obs, actions, rewards, next_obs, dones (bytes), index (int64); address 0 = field not wanted.  One
+        launch on the engine's stream, no host wait.  `ordered`: the engine orders its write against `consumer_stream` (a hipStream_t
+        as an integer; 0 = the default stream) on the GPU and that stream may read the arrays at once; otherwise the caller has
+        synchronised and calls sync() before it reads."""
+        self._ck(self.lib.sactd3_read_batch_device(self._h, self._fields_out(fields), C.c_void_p(int(consumer_stream) or None),
+                                                   _lib.DST_ORDERED if ordered else 0))
+
+    def rb_read_rows_device(self, idx_ptr: int, idx_ld: int, n: int, fields, consumer_stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_rb_read_rows_device: n ring records chosen by a device int64 array (`idx_ptr`, stride `idx_ld` elements) into `fields`
+        (as read_batch_device).  An index outside [0, rb_len) yields a zero row with flag 0, its index echoed, and is counted in
+        readout_stats()["rows_refused"]."""
+        self._ck(self.lib.sactd3_rb_read_rows_device(self._h, C.c_void_p(int(idx_ptr) or None), int(idx_ld), int(n), self._fields_out(fields),
+                                                     C.c_void_p(int(consumer_stream) or None), _lib.DST_ORDERED if ordered else 0))
+
+    def readout_stats(self) -> Dict[str, int]:
+        """counters of the outward device boundary (sactd3_readout_stats; waits for the engine's stream: the last one lives on the device)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.sactd3_readout_stats(self._h, out))
+        return dict(batch_readouts=int(out[0]), row_readouts=int(out[1]), rows_requested=int(out[2]), rows_refused=int(out[3]))
 
     def rb_len(self) -> int:
         return int(self._ck(self.lib.sactd3_rb_len(self._h)))
