@@ -304,6 +304,36 @@ int sactd3_predict_device(sactd3_engine* e, const float* obs, int64_t obs_ld, in
 /* host counters: out = {calls, rows, calls that inserted event waits, calls that took a multi-block tail} */
 int sactd3_predict_device_stats(const sactd3_engine* e, int64_t out[4]);
 
+/* ---- scoring state-action pairs on the device: Agent.batched_qf(params, ob, action) and pi(params, ob) (agents/agent.py:146-163) as a
+ * read path -- a forward-only evaluation of the twin critics, online (SACTD3_Q_ONLINE) or target (SACTD3_Q_TARGET), on n >= 1 rows the
+ * caller supplies; any n (the engine works through them 1024 rows at a time on its stream).  What a prioritised sampler (|Q(s,a) - y|),
+ * an n-step or hindsight relabeller (the value of the state it bootstraps from) or an evaluation (min Q(s, pi(s))) asks of rows it got
+ * from sactd3_rb_read_rows_device.
+ * `obs` [n, ob_dim], `actions` [n, ac_dim] and `q` are DEVICE pointers in the memory of the engine's device, each with a row stride in
+ * elements (>= the width), a contiguous inner dimension and no alignment beyond 4 bytes.  Q_k(obs_i, actions_i) of critic k is stored to
+ * q[k * q_ns + i * q_ld] (q_ld, q_ns >= 1; a contiguous [2, n] array: q_ld = 1, q_ns = n) and nothing else of `q` is written.
+ * actions == NULL: the pairs are (s, pi(s)), pi(s) = the ONLINE actor's exploit action -- what sactd3_predict(explore = 0) returns --
+ * whichever critics `which` names (SAC: tanh(mean); TD3: actor(s)).
+ * The launches go on the learner stream, eagerly, stream-ordered behind every update issued before the call (it scores with the updated
+ * parameters); no copy command, no wait or synchronisation on the host.  flags & SACTD3_SRC_ORDERED orders all three arrays against
+ * `caller_stream` exactly as sactd3_predict_device does.  A row's two values are the same bits whatever n is and whichever rows are
+ * scored with it: the hidden layers run in one pinned launch shape (the K split of the B < 1024 update kernels), the head is the
+ * forward third of the critic update's tail, so a row is scored with the arithmetic the engine trains with.
+ * The call is invisible to training: it writes its own scratch (made at the first call) and its own counters only -- no batch slot, no
+ * noise buffer, no acting scratch, no sample / noise / predict counter, and a precomputed opening pair of sactd3_step_period stays
+ * valid across it.  It is therefore allowed while a sactd3_predict_begin call is in flight.
+ * SACTD3_EINVAL, before anything is launched: a NULL `obs` or `q`, n < 1, a stride below the width, `which` other than the two values,
+ * an unknown flag, a pointer that is not memory of the engine's device; the engine stays usable. */
+#define SACTD3_Q_ONLINE 0
+#define SACTD3_Q_TARGET 1
+int sactd3_qvalues_device(sactd3_engine* e, const float* obs, int64_t obs_ld, const float* actions, int64_t actions_ld, int n, int which,
+                          float* q, int64_t q_ld, int64_t q_ns, void* caller_stream, int flags /* SACTD3_SRC_ORDERED */);
+/* The same for host arrays: obs [n, ob_dim], actions [n, ac_dim] or NULL, q [2 * n] (critic-major), through device staging of the
+ * engine's own; bit for bit the values of the device call.  [sync] */
+int sactd3_qvalues(sactd3_engine* e, const float* obs, const float* actions, int n, int which, float* q);
+/* host counters: out = {calls, rows, calls that inserted event waits, calls in the policy form (actions == NULL)} */
+int sactd3_qvalues_stats(const sactd3_engine* e, int64_t out[4]);
+
 int sactd3_read_metrics(sactd3_engine* e, float out[SACTD3_NUM_METRICS]);  /* [sync] */
 /* The engine's HIP stream (hipStream_t) and the DEVICE address of the metrics slots, for callers that want the values the
  * way the reference hands them out -- 0-dim device tensors that are only materialised at evaluation time (agents/agent.py:
@@ -328,7 +358,9 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
  * pack kernels on batch_size / max_envs rows of the engine's own staging slab; they overwrite the batch slot / append to the ring),
  * "obs_from_field" / "act_to_field" (the pack / unpack kernels of sactd3_predict_device on max_envs rows of engine-owned memory),
  * "batch_to_fields" / "rows_to_fields" (the read-out kernels of sactd3_read_batch_device / sactd3_rb_read_rows_device on batch_size rows,
- * written into the engine's own staging slab; the rows kernel takes its indices from the current slot's, widened to int64). [sync] */
+ * written into the engine's own staging slab; the rows kernel takes its indices from the current slot's, widened to int64),
+ * "sa_from_fields" / "q_head" (the pack / head kernels of sactd3_qvalues_device on 1024 rows of the scoring scratch, [s | a] read from
+ * the ring's records). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

@@ -438,6 +438,72 @@ class Agent:
         eng.predict_device(ptr, ld, n, explore, ogot[0], ogot[2], _producer_stream(obs, eng.cfg.device_id))
         return out[:n] if ogot[1] > n else out
 
+    def q_values(self, in_td: Mapping[str, Any], *, target: bool = False, out: Any = None):
+        """What the critics think of these rows: vmap(batched_qf) of the reference (agents/agent.py:146-163) on `observations`
+        [n, ob_dim] and `actions` [n, ac_dim] -> [2, n, 1] float32, from the online critics or (`target`) the target pair, computed
+        by the engine's own kernels (include/sactd3.h: sactd3_qvalues_device), any n.  Without an `actions` key the pairs are
+        (s, pi(s)): pi(s) is what predict(explore=False) returns, scored without leaving the device.
+        Routed by where the data lives, as ReplayBuffer.extend is.  Arrays in the memory of the engine's device give a tensor on
+        that device: nothing is copied, the host does not wait; the kernels run on the engine's stream, ordered on the GPU behind
+        what the caller's current stream has queued, and that stream is made to wait for them.  `out`: a preallocated float32
+        [2, >= n, 1] array or view of that device to write into -- its rows [:, :n] are returned; otherwise torch.empty.  A field
+        that is not float32, or whose inner dimension is not contiguous, is converted on the device first.  Host arrays give a
+        numpy array (and wait for it).  A mix of host and device arrays is a TypeError, as is everything predict_device refuses.
+        Training does not see the call: no sample is drawn, no counter moves, a BatchHandle stays current across it."""
+        eng = self.engine
+        o, a = eng.cfg.ob_dim, eng.cfg.ac_dim
+        given = [("observations", in_td["observations"], o)] + ([("actions", in_td["actions"], a)] if "actions" in in_td else [])
+        given = [(k, x.detach() if hasattr(x, "detach") else x, w) for k, x, w in given]
+        cais = [_cai(x) for _, x, _ in given]
+        if all(c is None for c in cais):                     # host data: numpy out
+            if out is not None:
+                raise TypeError("q_values: `out` is for arrays in the memory of the engine's device (host arrays return a numpy array)")
+            got = eng.q_values(_np(given[0][1]), _np(given[1][1]) if len(given) > 1 else None, target)
+            return got.reshape(2, -1, 1)
+        if any(c is None for c in cais):
+            raise TypeError("q_values: observations and actions must both be host arrays or both be arrays in the memory of the engine's device")
+        if not getattr(eng, "device_inputs", False):
+            raise TypeError("q_values: engine.device_inputs is off (pass host arrays)")
+        fields, rows, keep = [], [], []
+        for (key, x, width), cai in zip(given, cais):
+            if not _on_engine_device(eng, x):
+                raise TypeError(f"q_values: `{key}` is not an array in the memory of the engine's device")
+            if cai["typestr"][1:] != "f4":
+                lib = sys.modules.get(type(x).__module__.partition(".")[0])
+                x = x.to(getattr(lib, "float32", "float32"))
+                cai = _cai(x)
+            got = _cai_field(cai, width, 4)
+            if got is None:
+                x = x.contiguous()
+                got = _cai_field(_cai(x), width, 4)
+            keep.append(x)
+            fields.append((got[0], got[2]))
+            rows.append(got[1])
+        if len(set(rows)) != 1:
+            raise ValueError(f"q_values: observations and actions disagree on the number of rows: {rows}")
+        n = rows[0]
+        if out is None:
+            try:
+                import torch
+            except ImportError:
+                raise TypeError("q_values: without torch the caller passes `out`") from None
+            out = torch.empty((2, n, 1), dtype=torch.float32, device=torch.device("cuda", eng.cfg.device_id))
+        ocai = _cai(out.detach() if hasattr(out, "detach") else out)
+        if ocai is None or not _on_engine_device(eng, out) or ocai["typestr"][1:] != "f4":
+            raise TypeError("q_values: `out` must be a float32 array in the memory of the engine's device")
+        shape, strides = tuple(ocai["shape"]), ocai.get("strides")
+        if len(shape) != 3 or shape[0] != 2 or shape[2] != 1 or shape[1] < n:
+            raise ValueError(f"q_values: `out` must be [2, >= {n}, 1], got {list(shape)}")
+        q_ns, q_ld = int(shape[1]), 1
+        if strides is not None:                              # (the inner dimension has one element: its stride does not matter)
+            if strides[0] % 4 or strides[1] % 4 or strides[0] < 4 or (shape[1] > 1 and strides[1] < 4):
+                raise ValueError("q_values: `out` needs positive strides in whole elements")
+            q_ns, q_ld = strides[0] // 4, (strides[1] // 4 if shape[1] > 1 else 1)
+        obs_f, act_f = fields[0], (fields[1] if len(fields) > 1 else (0, a))
+        eng.q_values_device(obs_f[0], obs_f[1], act_f[0], act_f[1], n, target, int(ocai["data"][0]), q_ld, q_ns,
+                            _producer_stream(keep[0], eng.cfg.device_id))
+        return out[:, :n] if shape[1] > n else out
+
     def predict_begin(self, in_td: Mapping[str, Any], *, explore: bool) -> None:
         """predict() in two halves (include/sactd3.h: sactd3_predict_begin): the acting kernels go out on the engine's acting
         stream, and what is issued until predict_end() -- the iteration's update -- overlaps with them."""

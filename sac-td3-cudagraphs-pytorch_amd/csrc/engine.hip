@@ -164,6 +164,13 @@ struct sactd3_engine {
   // caller pointer -- and the host counters of sactd3_predict_device_stats.
   std::vector<hipGraphExec_t> predict_dev_graphs;
   int64_t pdev_stats[4] = {};
+  // Scoring caller-supplied rows (sactd3_qvalues_device): scratch for Q_CHUNK rows, made at the first call (the actor's at the first
+  // policy-form call) -- packed [s | a | 0] rows at ldc and z1 / z2 of the two critics; the actor's x / z1 / z2 / action rows -- and the
+  // host counters of sactd3_qvalues_stats.  Nothing else of the engine is written by a scoring call.
+  float *qs_sa = nullptr, *qs_z1 = nullptr, *qs_z2 = nullptr;
+  float *qs_x = nullptr, *qs_az1 = nullptr, *qs_az2 = nullptr, *qs_act = nullptr;
+  float *qs_hq = nullptr, *qs_hobs = nullptr, *qs_hact = nullptr;      // sactd3_qvalues (host arrays): device staging of one chunk
+  int64_t q_stats[4] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -569,6 +576,8 @@ struct TrunkTicks { int* tick0; int* tick1; float* adam_out; double* adam_pw; fl
                     int nnoise = 0; NoiseJob noise[5] = {}; bool* noise_taken = nullptr;      // the following tails' draws (see NoiseJob)
                     int force_ks = 0;                      // keep the single-net launch's K split (bit-equal results across launch shapes)
                     bool no_tiled64 = false;               // keep the 32 x 32-tile launches (the ones that can read ring rows / carry gathers)
+                    bool pin_shape = false;                // scoring (sactd3_qvalues_device): a row's bits must not depend on M -- the KS = 4 sums in both
+                                                           // k_nt launches (fused, and the unfused layer 2), no large-batch form even when M == B
                     int* tick0b = nullptr; float* adam_out_b = nullptr; double* adam_pw_b = nullptr; float lr_b = 0.f; };   // a second step counter
 static int enqueue_trunk(EnqCtx& x, int ldx, int K, int M, const NetLayout& L, long p_ns,
                          int ngrp, int npg, const TrunkGrp* grp, TrunkTicks tk) {
@@ -581,7 +590,8 @@ static int enqueue_trunk(EnqCtx& x, int ldx, int K, int M, const NetLayout& L, l
     h.g[i].P = grp[i].P; h.g[i].Y = grp[i].z2; h.g[i].xh_out = grp[i].xh; h.g[i].h_out = grp[i].h; h.g[i].rstd_out = grp[i].rstd;
   }
   const int nets = ngrp * npg;
-  const bool big_path = M >= BIG_BATCH && M == e->B && ((M + 63) / 64) * (HID / 64) * nets >= (3 * e->num_cus) / 4 && !tk.no_tiled64;
+  const bool big_m = M >= BIG_BATCH && M == e->B && !tk.pin_shape;
+  const bool big_path = big_m && ((M + 63) / 64) * (HID / 64) * nets >= (3 * e->num_cus) / 4 && !tk.no_tiled64;
   auto set_ring = [&](NtArgs& a) {   // which groups read their rows from the replay ring, and the gathers that ride along
     for (int i = 0; i < ngrp; ++i) { a.g[i].ring = grp[i].ring ? 1 : 0; a.g[i].ring_off = grp[i].ring_off; a.g[i].sctr_add = grp[i].sctr_add; a.g[i].ring_idx = grp[i].ring_idx; }
     a.ga[0] = gather_args(e, e->ring, -1);                                     // (ring groups take the ring / control block from ga[0])
@@ -631,9 +641,9 @@ static int enqueue_trunk(EnqCtx& x, int ldx, int K, int M, const NetLayout& L, l
     h.w1_magic = magic_div((unsigned)L.ld1, 4u * HID * (unsigned)L.ld1);
     set_ring(h);            // x = a field of the sampled records; extra blocks fill the batch slot(s) (see NtArgs)
     h.tick0b = tk.tick0b; h.adam_out_b = tk.adam_out_b; h.adam_pw_b = tk.adam_pw_b; h.lr_b = tk.lr_b;
-    return launch_nt(x, "layers1+2", pro, true, h, nets, tk.force_ks);
+    return launch_nt(x, "layers1+2", pro, true, h, nets, tk.pin_shape ? 4 : tk.force_ks);
   }
-  if (M >= BIG_BATCH && M == e->B) {   // large batch, too few nets for 64 x 64 tiles to fill the chip: 32 x 32 LDS-tiled form
+  if (big_m) {   // large batch, too few nets for 64 x 64 tiles to fill the chip: 32 x 32 LDS-tiled form
     unsigned nblk = (unsigned)(((M + 31) / 32) * (HID / 32) * nets);
     set_ring(g);            // x = the field of the sampled records itself; extra blocks fill the batch slot(s) (as in the fused k_nt form)
     g.nt_blocks = (int)nblk;
@@ -644,7 +654,7 @@ static int enqueue_trunk(EnqCtx& x, int ldx, int K, int M, const NetLayout& L, l
   } else RCCHK(launch_nt(x, "layer1", 0, false, g, nets));
   for (int i = 0; i < ngrp; ++i) h.g[i].in = grp[i].z1;
   h.ld_in = HID; h.in_ns = (long)M * HID;
-  if (M >= BIG_BATCH && M == e->B) {   // large batch: the 32 x 32 LDS-tiled form with the LayerNorm prologue
+  if (big_m) {   // large batch: the 32 x 32 LDS-tiled form with the LayerNorm prologue
     h.ln_pro = e->cfg.layer_norm ? 1 : 0;
     h.nt_blocks = ((M + 31) / 32) * (HID / 32) * nets;
     int nzb = 0;
@@ -653,7 +663,7 @@ static int enqueue_trunk(EnqCtx& x, int ldx, int K, int M, const NetLayout& L, l
            (k_nt64_ln<2, 2, 1>), dim3((unsigned)(h.nt_blocks + h.alpha_block + nzb)), dim3(256), h);
     return 0;
   }
-  return launch_nt(x, "layer2", pro, false, h, nets);
+  return launch_nt(x, "layer2", pro, false, h, nets, tk.pin_shape ? 4 : 0);
 }
 
 static ActorTail tail_args(sactd3_engine* e, const float* z2, const float* P, int M, int mode, int train,
@@ -2367,6 +2377,136 @@ int sactd3_predict_device_stats(const sactd3_engine* e, int64_t out[4]) {
   return 0;
 }
 
+// ---- scoring caller-supplied state-action pairs: Agent.batched_qf / pi of the reference (agents/agent.py:146-163) as a read path.
+// A forward-only pass of the twin critics (online or target arena) on Q_CHUNK rows at a time, eager launches on the learner stream:
+// pack -> trunk (pinned launch shape, see TrunkTicks::pin_shape) -> head, which stores straight into the caller's array.  The policy
+// form (no actions) first runs the online actor's trunk and its exploit-mode tail into the scoring scratch.  It writes its own
+// scratch and its own counters only: no CHAIN_BREAK, no counter tick, actor_dirty untouched, no batch slot / noise buffer / p_* use.
+static const int Q_CHUNK = 1024;      // rows per pass: what the scoring scratch is sized for
+static int q_scratch(sactd3_engine* e, bool policy) {      // (never zeroed: every float a launch reads was written by the one before it)
+  if (!e->qs_sa) {
+    RCCHK(dalloc(e, &e->qs_z1, (size_t)2 * Q_CHUNK * HID, false));
+    RCCHK(dalloc(e, &e->qs_z2, (size_t)2 * Q_CHUNK * HID, false));
+    RCCHK(dalloc(e, &e->qs_sa, (size_t)Q_CHUNK * e->ldc, false));
+  }
+  if (policy && !e->qs_act) {
+    RCCHK(dalloc(e, &e->qs_x, (size_t)Q_CHUNK * e->ldo, false));
+    RCCHK(dalloc(e, &e->qs_az1, (size_t)Q_CHUNK * HID, false));
+    RCCHK(dalloc(e, &e->qs_az2, (size_t)Q_CHUNK * HID, false));
+    RCCHK(dalloc(e, &e->qs_act, (size_t)Q_CHUNK * e->a4, false));
+  }
+  return 0;
+}
+static int launch_sa_pack(sactd3_engine* e, const float* obs, int64_t obs_ld, const float* act, int64_t act_ld, int m) {
+  const SaFieldArgs g{(float4*)e->qs_sa, m, e->ldc / 4};
+  const long chunks = (long)m * g.c4;
+  hipLaunchKernelGGL(k_sa_from_fields, dim3((unsigned)((chunks + 256L * SA_CPT - 1) / (256L * SA_CPT))), dim3(256), 0, e->stream,
+                     obs, (long)obs_ld, act, (long)act_ld, e->o, e->a, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_q_head(sactd3_engine* e, const float* P, int m, float* q, int64_t q_ld, int64_t q_ns) {
+  QHead h{};
+  h.z2 = e->qs_z2; h.P = P; h.p_ns = e->Lc.size; h.L = e->Lc; h.n = m; h.ln = e->cfg.layer_norm; h.q = q; h.q_ld = (long)q_ld; h.q_ns = (long)q_ns;
+  hipLaunchKernelGGL(k_q_head<4>, dim3((unsigned)((m + 3) / 4), 2), dim3(64), 0, e->stream, h);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int enqueue_qvalues(sactd3_engine* e, const float* obs, int64_t obs_ld, const float* act, int64_t act_ld, int n, int which,
+                           float* q, int64_t q_ld, int64_t q_ns) {
+  RCCHK(q_scratch(e, act == nullptr));
+  EnqCtx x{e, e->stream};
+  TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
+  tk.pin_shape = true;
+  const float* P = which == SACTD3_Q_TARGET ? e->Tc : e->Pc;
+  for (int64_t row0 = 0; row0 < n; row0 += Q_CHUNK) {
+    const int m = (int)std::min<int64_t>(Q_CHUNK, n - row0);
+    const float* obs_c = obs + row0 * obs_ld;
+    if (!act) {      // pi(s): the online actor's exploit action, what sactd3_predict(explore = 0) returns
+      const ObsFieldArgs og{(float4*)e->qs_x, m, e->ldo / 4};
+      const long chunks = (long)m * og.c4;
+      hipLaunchKernelGGL(k_obs_from_field, dim3((unsigned)((chunks + 256L * OBS_CPT - 1) / (256L * OBS_CPT))), dim3(256), 0, e->stream, obs_c, (long)obs_ld, e->o, og);
+      HIPCHK(hipGetLastError());
+      const TrunkGrp ga{e->qs_x, e->Pa, e->qs_az1, e->qs_az2, nullptr, nullptr, nullptr};
+      RCCHK(enqueue_trunk(x, e->ldo, e->o, m, e->La, 0, 1, 1, &ga, tk));
+      // (exploit mode draws nothing: the tail reads neither the draw buffer nor -- for its result -- the counter, and ticks nothing)
+      const ActorTail t = tail_args(e, e->qs_az2, e->Pa, m, e->cfg.prefer_td3_over_sac ? 0 : 1, 0, SACTD3_SITE_PREDICT, 48u, e->qs_act, e->a4, 0, nullptr);
+      RCCHK(launch_tail(x, t));
+      RCCHK(launch_sa_pack(e, obs_c, obs_ld, e->qs_act, e->a4, m));
+    } else RCCHK(launch_sa_pack(e, obs_c, obs_ld, act + row0 * act_ld, act_ld, m));
+    const TrunkGrp gc{e->qs_sa, P, e->qs_z1, e->qs_z2, nullptr, nullptr, nullptr};
+    RCCHK(enqueue_trunk(x, e->ldc, e->o + e->a, m, e->Lc, e->Lc.size, 1, 2, &gc, tk));
+    RCCHK(launch_q_head(e, P, m, q + row0 * q_ld, q_ld, q_ns));
+  }
+  return 0;
+}
+static int qvalues_args(sactd3_engine* e, const char* what, int n, int which) {
+  if (n < 1) { e->err = std::string(what) + ": n >= 1"; return SACTD3_EINVAL; }
+  if (which != SACTD3_Q_ONLINE && which != SACTD3_Q_TARGET) { e->err = std::string(what) + ": `which` is SACTD3_Q_ONLINE or SACTD3_Q_TARGET"; return SACTD3_EINVAL; }
+  return 0;
+}
+
+int sactd3_qvalues_device(sactd3_engine* e, const float* obs, int64_t obs_ld, const float* actions, int64_t actions_ld, int n, int which,
+                          float* q, int64_t q_ld, int64_t q_ns, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!obs || !q) return e->fail(SACTD3_EINVAL, "qvalues_device: null argument");
+  USE_DEVICE(e);
+  RCCHK(qvalues_args(e, "qvalues_device", n, which));
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "qvalues_device: unknown flag");
+  if (obs_ld < e->o) return e->fail(SACTD3_EINVAL, "qvalues_device: row stride of `obs` is below its width");
+  if (actions && actions_ld < e->a) return e->fail(SACTD3_EINVAL, "qvalues_device: row stride of `actions` is below its width");
+  if (q_ld < 1 || q_ns < 1) return e->fail(SACTD3_EINVAL, "qvalues_device: strides of `q` are below its width");
+  const struct { const void* p; const char* name; } ptrs[3] = {{obs, "obs"}, {actions, "actions"}, {q, "q"}};
+  for (const auto& a : ptrs) {
+    if (!a.p) continue;      // (actions: the policy form)
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, a.p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
+      (void)hipGetLastError();
+      e->err = std::string("qvalues_device: `") + a.name + "` is not device memory of the engine's device";
+      return SACTD3_EINVAL;
+    }
+  }
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  RCCHK(enqueue_qvalues(e, obs, obs_ld, actions, actions_ld, n, which, q, q_ld, q_ns));
+  RCCHK(src_order_end(e, caller, flags));
+  ++e->q_stats[0]; e->q_stats[1] += n;
+  if (flags & SACTD3_SRC_ORDERED) ++e->q_stats[2];
+  if (!actions) ++e->q_stats[3];
+  return 0;
+}
+
+// the same for host arrays: a chunk at a time through device staging of the engine's own (made at the first call)
+int sactd3_qvalues(sactd3_engine* e, const float* obs, const float* actions, int n, int which, float* q) {
+  if (!e) return SACTD3_EINVAL;
+  if (!obs || !q) return e->fail(SACTD3_EINVAL, "qvalues: null argument");
+  USE_DEVICE(e);
+  RCCHK(qvalues_args(e, "qvalues", n, which));
+  if (!e->qs_hq) {
+    RCCHK(dalloc(e, &e->qs_hq, (size_t)2 * Q_CHUNK, false));
+    RCCHK(dalloc(e, &e->qs_hobs, (size_t)Q_CHUNK * e->o, false));
+    RCCHK(dalloc(e, &e->qs_hact, (size_t)Q_CHUNK * e->a, false));
+  }
+  for (int64_t row0 = 0; row0 < n; row0 += Q_CHUNK) {
+    const int m = (int)std::min<int64_t>(Q_CHUNK, n - row0);
+    HIPCHK(hipMemcpy(e->qs_hobs, obs + row0 * e->o, sizeof(float) * (size_t)m * e->o, hipMemcpyHostToDevice));
+    if (actions) HIPCHK(hipMemcpy(e->qs_hact, actions + row0 * e->a, sizeof(float) * (size_t)m * e->a, hipMemcpyHostToDevice));
+    RCCHK(enqueue_qvalues(e, e->qs_hobs, e->o, actions ? e->qs_hact : nullptr, e->a, m, which, e->qs_hq, 1, Q_CHUNK));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int k = 0; k < 2; ++k)
+      HIPCHK(hipMemcpy(q + (int64_t)k * n + row0, e->qs_hq + (size_t)k * Q_CHUNK, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost));
+  }
+  ++e->q_stats[0]; e->q_stats[1] += n;
+  if (!actions) ++e->q_stats[3];
+  return 0;
+}
+
+int sactd3_qvalues_stats(const sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = e->q_stats[i];
+  return 0;
+}
+
 int sactd3_acting_stats(const sactd3_engine* e, int64_t out[4]) {
   if (!e || !out) return SACTD3_EINVAL;
   for (int i = 0; i < 4; ++i) out[i] = e->act_stats[i];
@@ -2522,7 +2662,15 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       if (!strcmp(kernel, "batch_to_fields")) return launch_batch_out(e, field_dst(e, &f, 0));
       return launch_rows_out(e, field_dst(e, &f, 0), e->time_idx, 1, e->B, (int)e->rb_len);
     }
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields)");
+    // the pack / head kernels of sactd3_qvalues_device on Q_CHUNK rows of the scoring scratch: [s | a] read from the ring's records (row
+    // stride = the record); the head on whatever the scratch's z2 holds, its values written over the scratch's z1
+    if (!strcmp(kernel, "sa_from_fields") || !strcmp(kernel, "q_head")) {
+      RCCHK(q_scratch(e, false));
+      const int m = (int)std::min<int64_t>(Q_CHUNK, e->cfg.rb_capacity);
+      if (!strcmp(kernel, "sa_from_fields")) return launch_sa_pack(e, e->ring, e->rec_f, e->ring + e->o, e->rec_f, m);
+      return launch_q_head(e, e->Pc, m, e->qs_z1, 1, Q_CHUNK);
+    }
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head)");
   };
   if (!strcmp(kernel, "rows_to_fields")) rc = time_rows_indices(e);
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up

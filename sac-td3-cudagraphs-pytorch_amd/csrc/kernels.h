@@ -707,6 +707,47 @@ __global__ __launch_bounds__(256) void k_act_to_field(float* f_act, long act_ld,
   if (e + 3 < p.a) dst[3] = v.w;
 }
 
+// Scoring caller-supplied state-action pairs (sactd3_qvalues_device): the way in.  k_sa_from_fields packs obs [n, o] and act [n, a]
+// (row strides obs_ld / act_ld elements, rows 4-byte aligned only) into x [n][4 * c4], the zero-padded [s | a | 0] rows the critics'
+// trunk reads -- the pad is WRITTEN, as in k_obs_from_field.  In the policy form `f_act` is the engine's own action rows (what the
+// exploit-mode actor tail left in the scoring scratch).  The discipline of k_obs_from_field: one thread per destination float4 chunk
+// (a chunk may hold the end of s and the start of a), SA_CPT chunks per thread, every float one dword load from an always-valid
+// address (what has no source reads column 0 of the row's observation) kept or zeroed by a select, all loads out before the single
+// wait, then the stores.  The sources are separate kernel arguments and the address a sum of two-way selects: see field_addr.
+// The host keeps n * c4 < 2^31.
+#define SA_CPT 2
+struct SaFieldArgs { float4* x; int n, c4; };
+__global__ __launch_bounds__(256) void k_sa_from_fields(const float* f_obs, long obs_ld, const float* f_act, long act_ld, int o, int a, SaFieldArgs p) {
+  const unsigned total = (unsigned)p.n * (unsigned)p.c4;      // >= 1
+  int row[SA_CPT], cc[SA_CPT]; bool on[SA_CPT]; float v[SA_CPT][4];
+#pragma unroll
+  for (int u = 0; u < SA_CPT; ++u) {
+    const unsigned g = (blockIdx.x * (unsigned)SA_CPT + (unsigned)u) * 256u + threadIdx.x;
+    on[u] = g < total;
+    const unsigned gc = min(g, total - 1u), q = gc / (unsigned)p.c4;      // (a chunk past the end reads what the last one reads)
+    row[u] = (int)q; cc[u] = (int)(gc - q * (unsigned)p.c4);
+  }
+#pragma unroll
+  for (int u = 0; u < SA_CPT; ++u)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = 4 * cc[u] + i;
+      const bool is_a = e >= o && e < o + a;
+      const uintptr_t base = (is_a ? (uintptr_t)f_act : 0) + (is_a ? 0 : (uintptr_t)f_obs);
+      const long ld = (is_a ? act_ld : 0) + (is_a ? 0 : obs_ld);
+      const int col = (e < o ? e : 0) + (is_a ? e - o : 0);
+      v[u][i] = *(gfloat_p)(base + 4 * (uintptr_t)((long)row[u] * ld + col));
+    }
+#pragma unroll
+  for (int u = 0; u < SA_CPT; ++u) { PIN(v[u][0]); PIN(v[u][1]); PIN(v[u][2]); PIN(v[u][3]); }      // every request is out before the first store
+#pragma unroll
+  for (int u = 0; u < SA_CPT; ++u) {
+    if (!on[u]) continue;
+    const int e = 4 * cc[u], w = o + a;
+    p.x[(long)row[u] * p.c4 + cc[u]] = make_float4(e < w ? v[u][0] : 0.f, e + 1 < w ? v[u][1] : 0.f, e + 2 < w ? v[u][2] : 0.f, e + 3 < w ? v[u][3] : 0.f);
+  }
+}
+
 struct FillArgs { float4* ring; int rec4, cx, cn, o, a; long n; unsigned long long seed; const float* min_ac; const float* max_ac; };
 __global__ __launch_bounds__(256) void k_rb_fill(FillArgs p) {
   const long g = (long)blockIdx.x * 256 + threadIdx.x;
@@ -2713,6 +2754,35 @@ __global__ __launch_bounds__(16 * RPB) void k_critic_tail(CriticTail p) {
     p.part_s[blk * 2 + t] = s;
   }
   STAMP(3);
+}
+
+// The forward third of k_critic_tail and nothing else (sactd3_qvalues_device): Q_net(row) = relu(LN(z2)) . Wh + bh for the twin
+// critics (blockIdx.y = net) of ONE parameter arena, online or target, on n caller-supplied rows -- ln_fwd, relu4, row16_sum(row_dot)
+// + bh in k_critic_tail's order of operations, 16 threads per row, so that a scored row is computed the way training computes it.
+// The value goes straight to the caller's array, q[net * q_ns + b * q_ld]; rows past n load a clamped row and store nothing.
+struct QHead {
+  const float* z2;                       // [2][n][HID] pre-LN layer-2 outputs
+  const float* P; long p_ns; NetLayout L;
+  int n, ln;
+  float* q; long q_ld, q_ns;
+};
+template <int RPB>
+__global__ __launch_bounds__(16 * RPB) void k_q_head(QHead p) {
+  const int t = threadIdx.x, row = t >> 4, sub = t & 15, net = blockIdx.y;
+  const int b = blockIdx.x * RPB + row, bc = min(b, p.n - 1);
+  const float* Pn = p.P + net * p.p_ns;
+  // loads first
+  const Row16 z = row_ld(p.z2 + ((long)net * p.n + bc) * HID, sub);
+  const Row16 w = row_ld(Pn + p.L.Wh, sub);
+  Row16 g, be;
+  if (p.ln) { g = row_ld(Pn + p.L.g2, sub); be = row_ld(Pn + p.L.be2, sub); }
+  const float bh = Pn[p.L.bh];
+  Row16 xh, y, h; float rstd;
+  ln_fwd(z, g, be, p.ln, xh, y, rstd);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) h.v[q] = relu4(y.v[q]);
+  const float qv = row16_sum(row_dot(h, w)) + bh;
+  if (sub == 0 && b < p.n) p.q[(long)net * p.q_ns + (long)b * p.q_ld] = qv;
 }
 
 // k_critic_tail + k_nn in ONE launch (B < 1024): a block = 16 batch rows x 16 NT columns of dh1 = dz2 W2.  Every block redoes the

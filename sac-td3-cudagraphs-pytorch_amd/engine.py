@@ -407,6 +407,38 @@ class Engine:
         self._ck(self.lib.sactd3_predict_device_stats(self._h, out))
         return dict(calls=int(out[0]), rows=int(out[1]), ordered_calls=int(out[2]), multi_block_tails=int(out[3]))
 
+    def q_values(self, obs, act=None, target: bool = False) -> np.ndarray:
+        """sactd3_qvalues: Q_k(obs_i, act_i) of the twin critics -- the target pair with `target` -- for host rows -> [2, n] float32.
+        `act` None: the pairs are (s, pi(s)), pi(s) = what predict(explore=False) returns.  Waits for the result; bit for bit the
+        values q_values_device() leaves on the device, and training does not see the call."""
+        obs = _f32(obs).reshape(-1, self.cfg.ob_dim)
+        n = obs.shape[0]
+        if act is not None:
+            act = _f32(act).reshape(-1, self.cfg.ac_dim)
+            if act.shape[0] != n:
+                raise ValueError(f"observations and actions disagree on the number of rows: {n}, {act.shape[0]}")
+        out = np.empty((2, n), np.float32)
+        self._ck(self.lib.sactd3_qvalues(self._h, _fp(obs), _fp(act), n, _lib.Q_TARGET if target else _lib.Q_ONLINE, _fp(out)))
+        return out
+
+    def q_values_device(self, obs_ptr: int, obs_ld: int, act_ptr: int, act_ld: int, n: int, target: bool, q_ptr: int, q_ld: int,
+                        q_ns: int, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_qvalues_device: score n rows that live in this device's memory -- `obs_ptr` / `act_ptr`: device addresses, `*_ld`: row
+        strides in elements; `act_ptr` 0: the policy form, (s, pi(s)) -- with the online or (`target`) the target critics; critic k's
+        value of row i goes to the float32 at `q_ptr` + 4 (k `q_ns` + i `q_ld`).  Asynchronous on the engine's stream behind the updates
+        issued so far, no host wait, invisible to training.  `ordered`: the engine orders its reads and its write against `stream` (a
+        hipStream_t as an integer; 0 = the default stream) on the GPU; otherwise the caller has synchronised and calls sync()."""
+        self._ck(self.lib.sactd3_qvalues_device(self._h, C.c_void_p(int(obs_ptr) or None), int(obs_ld), C.c_void_p(int(act_ptr) or None),
+                                                int(act_ld), int(n), _lib.Q_TARGET if target else _lib.Q_ONLINE,
+                                                C.c_void_p(int(q_ptr) or None), int(q_ld), int(q_ns), C.c_void_p(int(stream) or None),
+                                                _lib.SRC_ORDERED if ordered else 0))
+
+    def qvalues_stats(self) -> Dict[str, int]:
+        """host counters of the scoring route (sactd3_qvalues_stats)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.sactd3_qvalues_stats(self._h, out))
+        return dict(calls=int(out[0]), rows=int(out[1]), ordered_calls=int(out[2]), policy_calls=int(out[3]))
+
     def acting_stats(self) -> Dict[str, int]:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
         out = (C.c_int64 * 4)()
