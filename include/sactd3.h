@@ -199,6 +199,42 @@ int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx
  * wait for nor are waited for by an acting call in flight.
  * [sync] out = {batch read-outs, row read-outs, rows requested, rows refused for their index (counted on the device)} */
 int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]);
+/* ---- training on rows a sampler of the caller's own chose, with loss weights, and the TD errors back: what a prioritised replay
+ * iteration needs to stay on the device end to end (index staging, a weighted critic loss, a TD read-out).  Nothing here changes what the
+ * calls above and below compute; the fused sactd3_step* paths keep their own uniform sampler and are never weighted.
+ * rb.sample() with the caller's indices: one kernel launch on the learner stream fills batch slot 0 (the rows, their ring slots) from the
+ * ring -- bit for bit what sactd3_rb_sample_with_indices leaves for the same indices -- and the slot's per-row loss weights from `w`
+ * (w[i * w_ld]; NULL: all 1).  `idx` (idx[i * idx_ld], the ring slot of row i) and `w` are DEVICE pointers in the memory of the engine's
+ * device, strides in elements (>= 1); n == batch_size.  No host wait, no copy command, no tick of the sample counter.  Indices are checked
+ * on the device against the ring length at the call: a row whose index is outside [0, sactd3_rb_len) never becomes an address -- it is
+ * stored as a zero record with ring slot -1 and weight 0, contributes nothing to the loss or to any gradient, and is counted
+ * (sactd3_priority_stats).  A weight that is negative, NaN or infinite is stored as 0 and counted: a device value cannot poison the
+ * parameters.  flags & SACTD3_SRC_ORDERED orders the reads against `caller_stream` as sactd3_load_batch_device does.
+ * SACTD3_ESTATE on an empty ring; SACTD3_EINVAL for n != batch_size, a stride below 1, a pointer that is not memory of the engine's
+ * device, an unknown flag; the engine stays usable. */
+int sactd3_rb_sample_indices_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n,
+                                    void* caller_stream, int flags /* SACTD3_SRC_ORDERED */);
+/* Loss weights for whatever batch slot 0 holds -- a caller-owned batch of sactd3_load_batch_device, an index-staged one: one launch, same
+ * rules for `w`, n, the flag and the errors as above; rows stored with ring slot -1 stay at weight 0.  w == NULL drops the weights.
+ * "The slot carries weights" is host state: the two calls above set it; every other refill of the slot clears it (sactd3_rb_sample,
+ * _with_indices, sactd3_load_batch, _device, every sactd3_step*, sactd3_time_nodes, sactd3_time_kernel of a kernel that overwrites the slot).  While it is set,
+ * sactd3_update_qnets runs in its weighted form, a captured graph of its own with the same nodes, captured at its first use
+ * (sactd3_instantiate_graphs does not make it, the first staging call allocates the weights: an engine that never stages weights holds
+ * nothing more than before), with the loss
+ *     L = sum_k (1 / B) sum_i w_i (Q_k(s_i, a_i) - y_i)^2        (the divisor is B, not sum w; SACTD3_M_QF_LOSS reports L)
+ * sactd3_update_actor is never weighted. */
+int sactd3_batch_weights_device(sactd3_engine* e, const float* w, int64_t w_ld, int n, void* caller_stream, int flags /* SACTD3_SRC_ORDERED */);
+/* Per-row TD errors of the most recent critic update, whichever entry point issued it (sactd3_update_qnets, sactd3_step,
+ * sactd3_step_period, sactd3_step_prefix): td[k * td_ns + i * td_ld] = Q_k(s_i, a_i) - y_i, signed, per critic, the values the update
+ * itself computed (its own policy draw included), in the layout of sactd3_qvalues_device's `q`; row i is row i of the batch slot
+ * sactd3_read_batch reports.  `td` is a DEVICE pointer, strides in elements (>= 1).  One launch on the learner stream, no host wait;
+ * flags & SACTD3_DST_ORDERED orders the write against `caller_stream` as sactd3_read_batch_device does.  Invisible to training in the
+ * sense of sactd3_qvalues_device: it reads the stored q and y only, and a precomputed opening pair of sactd3_step_period stays valid.
+ * SACTD3_ESTATE when no critic update has run on the rows now in that slot (before the first update, or after a refill of the slot
+ * since); SACTD3_EINVAL as above. */
+int sactd3_td_errors_device(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns, void* caller_stream, int flags /* SACTD3_DST_ORDERED */);
+/* [sync] out = {index stagings, weight stagings, td read-outs, rows refused on the device (bad index or bad weight; one per row and call)} */
+int sactd3_priority_stats(sactd3_engine* e, int64_t out[4]);
 /* rb.sample(batch_size) (orchestrator.py:338): uniform-with-replacement indices from the engine's
  * Philox stream + gather into the engine-owned batch slot. */
 int sactd3_rb_sample(sactd3_engine* e);
@@ -350,7 +386,8 @@ int sactd3_sync(sactd3_engine* e);                                          /* [
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats);
 const char* sactd3_debug_names(void);
 /* number of kernel nodes in the instantiated graph of: 0 update_qnets, 1 update_actor, 2 step(do_actor=0), 3 step(do_actor=1), 4 step_period,
- * 5 the opening graph of a period that cannot use a precomputed opening pair, 6 / 7 step_prefix(1) / step_prefix(2) */
+ * 5 the opening graph of a period that cannot use a precomputed opening pair, 6 / 7 step_prefix(1) / step_prefix(2),
+ * 8 update_qnets in its weighted form (0 until its first use; the same count as 0) */
 int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
 /* average device time in microseconds of `iters` back-to-back launches of one kernel of the path,
  * measured with hipEvents on the engine's stream: "gather" (a fresh index draw per launch), "polyak", "trunk_critics" (the 4-net
@@ -360,7 +397,9 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
  * "batch_to_fields" / "rows_to_fields" (the read-out kernels of sactd3_read_batch_device / sactd3_rb_read_rows_device on batch_size rows,
  * written into the engine's own staging slab; the rows kernel takes its indices from the current slot's, widened to int64),
  * "sa_from_fields" / "q_head" (the pack / head kernels of sactd3_qvalues_device on 1024 rows of the scoring scratch, [s | a] read from
- * the ring's records). [sync] */
+ * the ring's records), "batch_from_index" / "td_to_field" (the staging and TD read-out kernels of sactd3_rb_sample_indices_device /
+ * sactd3_td_errors_device on batch_size rows: indices as for "rows_to_fields", no weights, into the batch slot; the TD errors into the
+ * engine's own staging slab). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

@@ -14,8 +14,8 @@ ACTOR, CRITICS, ACTOR_TARGET, CRITICS_TARGET, LOG_ALPHA = range(5)
 SITE_CRITIC, SITE_ACTOR0, SITE_ACTOR1, SITE_ALPHA0, SITE_ALPHA1, SITE_PREDICT = range(6)
 NUM_METRICS = 8
 ACT_AFTER_ALL = 1   # sactd3_predict_begin flags
-SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device / sactd3_predict_device / sactd3_qvalues_device flags
-DST_ORDERED = 1     # sactd3_read_batch_device / sactd3_rb_read_rows_device flags (the same bit, the same two events)
+SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device / sactd3_predict_device / sactd3_qvalues_device / sactd3_rb_sample_indices_device / sactd3_batch_weights_device flags
+DST_ORDERED = 1     # sactd3_read_batch_device / sactd3_rb_read_rows_device / sactd3_td_errors_device flags (the same bit, the same two events)
 Q_ONLINE, Q_TARGET = 0, 1   # sactd3_qvalues / sactd3_qvalues_device `which`
 ESTATE, EINVAL = -3, -1
 
@@ -33,6 +33,7 @@ SYMBOLS = [
     "sactd3_predict_device", "sactd3_predict_device_stats",
     "sactd3_read_batch_device", "sactd3_rb_read_rows_device", "sactd3_readout_stats",
     "sactd3_qvalues_device", "sactd3_qvalues", "sactd3_qvalues_stats",
+    "sactd3_rb_sample_indices_device", "sactd3_batch_weights_device", "sactd3_td_errors_device", "sactd3_priority_stats",
 ]
 
 
@@ -134,6 +135,10 @@ def load_library():
         "sactd3_qvalues_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int]),
         "sactd3_qvalues": (C.c_int, [vp, fp, fp, C.c_int, C.c_int, fp]),
         "sactd3_qvalues_stats": (C.c_int, [vp, i64p]),
+        "sactd3_rb_sample_indices_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int]),
+        "sactd3_batch_weights_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int]),
+        "sactd3_td_errors_device": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, C.c_int]),
+        "sactd3_priority_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -150,6 +150,71 @@ def _device_outputs(engine: Engine, n: int, out: Optional[Mapping[str, Any]] = N
     return tensors, fields
 
 
+def _index_field(engine: Engine, index):
+    """-> (index, address, n, stride in elements) of a ring-slot index for Engine.rb_read_rows_device / rb_sample_indices_device: an
+    int64 array on the engine's device is taken where it is (made contiguous on the device if its stride is not whole elements);
+    anything else goes through torch.as_tensor and is uploaded first."""
+    cai = _cai(index.detach() if hasattr(index, "detach") else index)
+    if cai is None or not _on_engine_device(engine, index) or cai["typestr"][1:] != "i8":
+        import torch
+        index = torch.as_tensor(index, dtype=torch.int64).to(torch.device("cuda", int(engine.cfg.device_id)))
+        cai = _cai(index)
+    got = _cai_field(cai, 1, 8)
+    if got is None:
+        index = index.contiguous()
+        got = _cai_field(_cai(index), 1, 8)
+    return (index,) + got
+
+
+def _weight_field(engine: Engine, weights, n: int, what: str):
+    """-> (array kept alive, address, stride in elements) of per-row loss weights for Engine.rb_sample_indices_device /
+    batch_weights_device: [n] or [n, 1] on the engine's device; converted ON the device when not float32 or not strided in whole
+    elements, as _device_route does for its fields.  Not an array of that device: TypeError; another row count: ValueError."""
+    w = weights.detach() if hasattr(weights, "detach") else weights
+    cai = _cai(w)
+    if cai is None or not _on_engine_device(engine, w):
+        raise TypeError(f"{what}: the weights must be an array in the memory of the engine's device")
+    if cai["typestr"][1:] != "f4":
+        lib = sys.modules.get(type(w).__module__.partition(".")[0])
+        w = w.to(getattr(lib, "float32", "float32"))
+        cai = _cai(w)
+    try:
+        got = _cai_field(cai, 1, 4)
+    except ValueError as ex:
+        raise ValueError(f"{what}: weights: {ex}") from None
+    if got is None:
+        w = w.contiguous()
+        got = _cai_field(_cai(w), 1, 4)
+    if got[1] != n:
+        raise ValueError(f"{what}: expected {n} weights (one per batch row), got {got[1]}")
+    return w, got[0], got[2]
+
+
+def _critic_major_out(engine: Engine, n: int, out, what: str):
+    """Where a [2, n, 1] float32 result of the twin critics lands (Agent.q_values, Agent.td_errors).  -> (out, address, row stride,
+    critic stride in elements, rows of `out`).  `out` None: torch.empty on the engine's device; otherwise a preallocated float32
+    [2, >= n, 1] array or view of that device with positive strides in whole elements -- a wrong dtype or another device's array is a
+    TypeError, a wrong shape or stride a ValueError."""
+    if out is None:
+        try:
+            import torch
+        except ImportError:
+            raise TypeError(f"{what}: without torch the caller passes `out`") from None
+        out = torch.empty((2, n, 1), dtype=torch.float32, device=torch.device("cuda", engine.cfg.device_id))
+    ocai = _cai(out.detach() if hasattr(out, "detach") else out)
+    if ocai is None or not _on_engine_device(engine, out) or ocai["typestr"][1:] != "f4":
+        raise TypeError(f"{what}: `out` must be a float32 array in the memory of the engine's device")
+    shape, strides = tuple(ocai["shape"]), ocai.get("strides")
+    if len(shape) != 3 or shape[0] != 2 or shape[2] != 1 or shape[1] < n:
+        raise ValueError(f"{what}: `out` must be [2, >= {n}, 1], got {list(shape)}")
+    q_ns, q_ld = int(shape[1]), 1
+    if strides is not None:                              # (the inner dimension has one element: its stride does not matter)
+        if strides[0] % 4 or strides[1] % 4 or strides[0] < 4 or (shape[1] > 1 and strides[1] < 4):
+            raise ValueError(f"{what}: `out` needs positive strides in whole elements")
+        q_ns, q_ld = strides[0] // 4, (strides[1] // 4 if shape[1] > 1 else 1)
+    return out, int(ocai["data"][0]), q_ld, q_ns, int(shape[1])
+
+
 def _producer_stream(x, device_id: int) -> int:
     """the stream the caller's arrays were written on, as far as the array library tells: torch's current stream of the device"""
     if type(x).__module__.partition(".")[0] == "torch":
@@ -270,6 +335,26 @@ class ReplayBuffer:
         eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1
         return BatchHandle(eng, eng._batch_generation, device=self.device_batches)
 
+    def sample_at(self, index, weights=None) -> BatchHandle:
+        """sample() with the caller's rows: the ring records `index` names (batch_size ring slots: an int64 tensor on the engine's
+        device, or anything torch can turn into one, as for rows()) become the batch, staged by ONE launch on the engine's stream
+        (include/sactd3.h: sactd3_rb_sample_indices_device) -- no copy out and back in, no host wait.  `weights`: per-row loss
+        weights, float32 [batch_size] or [batch_size, 1] on the engine's device (converted on the device if not float32 or not
+        contiguous) -- the importance-sampling weights of a prioritised sampler; None: all 1.  The critic update on the returned
+        handle minimises (1 / B) sum_i w_i (Q(s_i, a_i) - y_i)^2; Agent.td_errors() then gives the rows' TD errors.  A slot outside
+        [0, len(rb)) becomes a zero record with index -1 and weight 0, a weight that is negative, NaN or infinite becomes 0: neither
+        reaches the parameters.  The handle is a sample()'s in every other respect (generation, device_batches)."""
+        eng = self._need()
+        B = int(eng.cfg.batch_size)
+        index, ptr, n, ld = _index_field(eng, index)
+        if n != B:
+            raise ValueError(f"sample_at: expected {B} indices (the engine is built for one batch size), got {n}")
+        keep, w_ptr, w_ld = (None, 0, 1) if weights is None else _weight_field(eng, weights, B, "sample_at")
+        eng.rb_sample_indices_device(ptr, ld, w_ptr, w_ld, n, _producer_stream(index, eng.cfg.device_id))
+        del keep      # (the engine's read is ordered against the stream the allocator hands the block out on)
+        eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1
+        return BatchHandle(eng, eng._batch_generation, device=self.device_batches)
+
     def rows(self, index, out: Optional[Mapping[str, Any]] = None) -> Dict[str, Any]:
         """The ring records `index` names (ring slots: what `index` of a sample holds), as a dict of tensors on the engine's device
         with the keys of a batch -- for a sampler of the caller's own (prioritised, n-step, hindsight) that reads the rows it relabels
@@ -277,16 +362,7 @@ class ReplayBuffer:
         length >= 1, or anything torch can turn into one (uploaded first).  A slot outside [0, len(rb)) yields a zero row with flag
         False.  `out` as for BatchHandle.on_device."""
         eng = self._need()
-        cai = _cai(index.detach() if hasattr(index, "detach") else index)
-        if cai is None or not _on_engine_device(eng, index) or cai["typestr"][1:] != "i8":
-            import torch
-            index = torch.as_tensor(index, dtype=torch.int64).to(torch.device("cuda", int(eng.cfg.device_id)))
-            cai = _cai(index)
-        got = _cai_field(cai, 1, 8)
-        if got is None:
-            index = index.contiguous()
-            got = _cai_field(_cai(index), 1, 8)
-        ptr, n, ld = got
+        index, ptr, n, ld = _index_field(eng, index)
         tensors, fields = _device_outputs(eng, n, out)
         eng.rb_read_rows_device(ptr, ld, n, fields, _producer_stream(index, eng.cfg.device_id))
         return tensors
@@ -482,27 +558,24 @@ class Agent:
         if len(set(rows)) != 1:
             raise ValueError(f"q_values: observations and actions disagree on the number of rows: {rows}")
         n = rows[0]
-        if out is None:
-            try:
-                import torch
-            except ImportError:
-                raise TypeError("q_values: without torch the caller passes `out`") from None
-            out = torch.empty((2, n, 1), dtype=torch.float32, device=torch.device("cuda", eng.cfg.device_id))
-        ocai = _cai(out.detach() if hasattr(out, "detach") else out)
-        if ocai is None or not _on_engine_device(eng, out) or ocai["typestr"][1:] != "f4":
-            raise TypeError("q_values: `out` must be a float32 array in the memory of the engine's device")
-        shape, strides = tuple(ocai["shape"]), ocai.get("strides")
-        if len(shape) != 3 or shape[0] != 2 or shape[2] != 1 or shape[1] < n:
-            raise ValueError(f"q_values: `out` must be [2, >= {n}, 1], got {list(shape)}")
-        q_ns, q_ld = int(shape[1]), 1
-        if strides is not None:                              # (the inner dimension has one element: its stride does not matter)
-            if strides[0] % 4 or strides[1] % 4 or strides[0] < 4 or (shape[1] > 1 and strides[1] < 4):
-                raise ValueError("q_values: `out` needs positive strides in whole elements")
-            q_ns, q_ld = strides[0] // 4, (strides[1] // 4 if shape[1] > 1 else 1)
+        out, q_ptr, q_ld, q_ns, out_rows = _critic_major_out(eng, n, out, "q_values")
         obs_f, act_f = fields[0], (fields[1] if len(fields) > 1 else (0, a))
-        eng.q_values_device(obs_f[0], obs_f[1], act_f[0], act_f[1], n, target, int(ocai["data"][0]), q_ld, q_ns,
+        eng.q_values_device(obs_f[0], obs_f[1], act_f[0], act_f[1], n, target, q_ptr, q_ld, q_ns,
                             _producer_stream(keep[0], eng.cfg.device_id))
-        return out[:, :n] if shape[1] > n else out
+        return out[:, :n] if out_rows > n else out
+
+    def td_errors(self, out: Any = None):
+        """The per-row TD errors of the most recent critic update (include/sactd3.h: sactd3_td_errors_device): Q_k(s_i, a_i) - y_i as
+        the update itself computed them (its Bellman target, its policy draw), signed, per critic -> [2, batch_size, 1] float32 on
+        the engine's device; row i is row i of the batch that update trained on.  What a prioritised sampler turns into the next
+        priorities, without a second forward pass.  One launch on the engine's stream, no host wait, ordered on the GPU against the
+        caller's current stream; training does not see the call.  `out` as for q_values.  Raises EngineError (SACTD3_ESTATE) when no
+        critic update has run on the rows now in the batch slot."""
+        eng = self.engine
+        n = int(eng.cfg.batch_size)
+        out, ptr, ld, ns, out_rows = _critic_major_out(eng, n, out, "td_errors")
+        eng.td_errors_device(ptr, ld, ns, _producer_stream(out, eng.cfg.device_id))
+        return out[:, :n] if out_rows > n else out
 
     def predict_begin(self, in_td: Mapping[str, Any], *, explore: bool) -> None:
         """predict() in two halves (include/sactd3.h: sactd3_predict_begin): the acting kernels go out on the engine's acting
@@ -523,7 +596,16 @@ class Agent:
         return {k: self._metric_tensors[k] for k in keys}
 
     def update_qnets(self, batch) -> Dict[str, Any]:
+        """agents/agent.py:183-242.  A mapping batch with a "_weight" key (what torchrl's prioritised sampler adds: float32
+        [batch_size] or [batch_size, 1] on the engine's device) is trained on with those per-row loss weights, staged behind the batch
+        (include/sactd3.h: sactd3_batch_weights_device); a handle of ReplayBuffer.sample_at() carries its weights already.  The
+        weights are never dropped silently: a "_weight" that is not an array on the engine's device (a host array, another GPU's) is a
+        TypeError, whichever route the batch's five fields take; a wrong row count is a ValueError."""
         self._stage(batch)
+        if batch is not None and not isinstance(batch, BatchHandle) and "_weight" in batch.keys():      # (a TensorDict refuses `key in td`)
+            eng = self.engine
+            keep, w_ptr, w_ld = _weight_field(eng, batch["_weight"], int(eng.cfg.batch_size), "update_qnets")
+            eng.batch_weights_device(w_ptr, w_ld, int(eng.cfg.batch_size), _producer_stream(keep, eng.cfg.device_id))
         self.engine.update_qnets()
         return self._results(["loss/qf_loss"])
 

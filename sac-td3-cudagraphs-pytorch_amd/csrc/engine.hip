@@ -75,7 +75,8 @@ static void unpack_net(const NetLayout& L, int ln, const float* src, float* dst)
 
 static const int BIG_BATCH = 1024;   // from here on the hidden layers run as 64 x 64-tiled GEMMs + a LayerNorm row kernel
 enum { G_Q = 0, G_A = 1, G_STEP00 = 2, G_STEP01 = 3, G_STEP10 = 4, G_STEP11 = 5, G_PERIOD = 6, G_PERIOD_B = 7, G_OPENING = 8,
-       G_PREFIX = 9 /* + 2 (m - 1) + variant, m = 1, 2: the first m iterations of a period (sactd3_step_prefix) */, G_COUNT = 13 };
+       G_PREFIX = 9 /* + 2 (m - 1) + variant, m = 1, 2: the first m iterations of a period (sactd3_step_prefix) */,
+       G_QW = 13 /* update_qnets in its weighted form: captured at its first use only */, G_COUNT = 14 };
 static const int NSTAGE = 32;
 
 struct NodeInfo { std::string name; double flops; double bytes; long threads; };
@@ -117,7 +118,7 @@ struct sactd3_engine {
   // update's launches -- the actor does not change in between -- into slots 1 and 2, which those iterations then train on; and it
   // does the same for the opening pair of the NEXT period's first iteration (next-action pass on s' and the first actor update's
   // policy pass on s), whose slot alternates between 0 and 3 from one period to the next (the running period still reads its own).
-  struct BatchSlot { float *X, *Xn, *rew, *done, *logp_n, *eps_c; int* idx; } bs[4] = {};
+  struct BatchSlot { float *X, *Xn, *rew, *done, *logp_n, *eps_c; int* idx; float* w; } bs[4] = {};      // w: loss weights [B], slot 0 only, see below
   int cur_slot = 0;              // the slot the most recent iteration trained on (what read_batch / read_noise / debug_read report)
   // chain_ready = v (0 / 1): the previous sactd3_step_period left the opening pair of the next period precomputed in slot (v ? 3 : 0)
   // and nothing has touched the state it depends on since (parameters, ring length, counters, noise injection, the slots);
@@ -171,6 +172,14 @@ struct sactd3_engine {
   float *qs_x = nullptr, *qs_az1 = nullptr, *qs_az2 = nullptr, *qs_act = nullptr;
   float *qs_hq = nullptr, *qs_hobs = nullptr, *qs_hact = nullptr;      // sactd3_qvalues (host arrays): device staging of one chunk
   int64_t q_stats[4] = {};
+  // Training on caller-chosen rows with loss weights (sactd3_rb_sample_indices_device / sactd3_batch_weights_device): bs[0].w is made at
+  // the first staging call -- an engine that never stages weights holds nothing more than before.  slot_weighted: slot 0 carries
+  // weights -> sactd3_update_qnets replays the weighted graph (G_QW); set by the two staging calls, cleared by every other refill.
+  // td_valid: e->q / e->y belong to a critic update on the rows now in bs[cur_slot] (sactd3_td_errors_device): set by every critic
+  // update, cleared by every refill of a slot outside one.  prio_stats: {index stagings, weight stagings, td read-outs}; the fourth
+  // value of sactd3_priority_stats is DevCtl::priority_refused.
+  bool slot_weighted = false, td_valid = false;
+  int64_t prio_stats[3] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -193,6 +202,8 @@ struct sactd3_engine {
   } while (0)
 // any call that changes what a precomputed opening pair depends on (see sactd3_engine::chain_ready)
 #define CHAIN_BREAK(e) do { (e)->chain_ready = -1; } while (0)
+// batch slot 0 is refilled outside an update: it carries no weights any more, and e->q / e->y are no longer its rows
+#define SLOT_REFILL(e) do { (e)->slot_weighted = false; (e)->td_valid = false; } while (0)
 #define RCCHK(call)                    \
   do {                                 \
     int _rc = (call);                  \
@@ -775,6 +786,7 @@ static bool actor_target_rides(const sactd3_engine* e) { return !(e->B >= BIG_BA
 struct IterPlace {
   bool actor = false, targets = false;      // the iteration has actor updates / a target update
   bool more = false;                        // another iteration follows in the same graph
+  bool weighted = false;                    // (the API path only) the critic loss is weighted by the slot's w
   int slot = 0; bool pre_sampled = false; int ahead = 0, chain_slot = -1;
 };
 static IterPlace single_iteration(bool actor, bool targets) {      // (sactd3_step)
@@ -840,6 +852,11 @@ static int enqueue_opening_pair(EnqCtx& x, const IterPlace& it, bool fused_sampl
   return launch_tails(x, 2, t, 2);
 }
 
+// The weighted critic tails (IterPlace::weighted) are launched from the end of this file: the compiler emits kernel template instances in
+// the order the file first names them (see launch_tails), and the new instances are named behind every existing one.
+static int launch_ctail_nn_w(EnqCtx& x, const CtailNn& f, const float* w, double fl, double by, dim3 grid);
+static int launch_critic_tail_w(EnqCtx& x, const CriticTail& t, const float* w, double fl, double by, dim3 grid);
+
 // agents/agent.py:183-242
 // fused_sample: see enqueue_opening_pair (false: the API path -- the batch slot was filled by the caller, no policy pass, no target update).
 // it.targets: with the target updates in the optimiser epilogue (see enqueue_step, actor_target_rides).
@@ -887,9 +904,12 @@ static int enqueue_update_qnets(EnqCtx& x, const IterPlace& it, bool fused_sampl
       f.c = t; f.c.pstride = e->nblk4; f.Wt = e->Pc + e->Lc.W2; f.ldw = HID; f.dX = e->c_dh1;
       f.f.fold = fold_ln1; f.f.ln = ln; f.f.h1 = e->c_h1; f.f.xh1 = e->c_xh1; f.f.g1_off = e->Lc.g1; f.f.ps = e->c_ps; f.f.gsnap = e->c_ps + 2L * B * PS_W;
       f.xr = pick_xr(e->nblk, HID / 32, 4.0 * 3 * B * HID, 4.0 * HID * HID);
-      LAUNCH("k_ctail_nn<2>", 2.0 * 4 * B * (double)HID + 2.0 * 2 * (double)B * HID * HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B) + 4.0 * 2 * ((double)HID * HID + (double)B * HID),
-             k_ctail_nn<2>, dim3((unsigned)(e->nblk * (HID / 32)), 1, 2), dim3(256), f);
-    } else LAUNCH("k_critic_tail<16>", 2.0 * 4 * B * (double)HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B), k_critic_tail<16>, dim3(e->nblk, 2), dim3(256), t);
+      const double fl = 2.0 * 4 * B * (double)HID + 2.0 * 2 * (double)B * HID * HID, by = 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B) + 4.0 * 2 * ((double)HID * HID + (double)B * HID);
+      const dim3 grid((unsigned)(e->nblk * (HID / 32)), 1, 2);
+      if (it.weighted) RCCHK(launch_ctail_nn_w(x, f, S.w, fl, by + 4.0 * B, grid));
+      else LAUNCH("k_ctail_nn<2>", fl, by, k_ctail_nn<2>, grid, dim3(256), f);
+    } else if (it.weighted) RCCHK(launch_critic_tail_w(x, t, S.w, 2.0 * 4 * B * (double)HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 9.0 * B), dim3(e->nblk, 2)));
+    else LAUNCH("k_critic_tail<16>", 2.0 * 4 * B * (double)HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B), k_critic_tail<16>, dim3(e->nblk, 2), dim3(256), t);
   }
   if (!fused_tail_nn) {  // dh1 = dz2 W2
     NnArgs g{};
@@ -1305,6 +1325,11 @@ static int publish_rb_state(sactd3_engine* e) {
   return 0;
 }
 
+// the launches of the prioritised route (defined at the end of this file, see launch_ctail_nn_w)
+static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld);
+static int launch_batch_weights(sactd3_engine* e, const float* w, int64_t w_ld);
+static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns);
+
 // ------------------------------------------------------------------------------------------------ C ABI
 #pragma GCC visibility push(default)
 extern "C" {
@@ -1671,6 +1696,7 @@ int sactd3_rb_sample(sactd3_engine* e) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample: buffer is empty");
+  SLOT_REFILL(e);
   e->cur_slot = 0;
   RCCHK(gather_now(e, e->ring, -1));
   hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
@@ -1690,6 +1716,7 @@ int sactd3_rb_sample_with_indices(sactd3_engine* e, const int64_t* idx, int n) {
   }
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipMemcpy(e->idx, h.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+  SLOT_REFILL(e);
   e->cur_slot = 0;
   RCCHK(set_flag(e, &e->ctl->inject_idx, 1));
   RCCHK(gather_now(e, e->ring, -1));
@@ -1702,6 +1729,7 @@ int sactd3_load_batch(sactd3_engine* e, const float* obs, const float* act, cons
   CHAIN_BREAK(e);
   if (n != e->B) return e->fail(SACTD3_EINVAL, "load_batch: n must equal batch_size");
   HIPCHK(hipStreamSynchronize(e->stream));
+  SLOT_REFILL(e);
   std::vector<int> h(n);
   for (int i = 0; i < n; ++i) {
     pack_record(e, e->h_batch + (size_t)i * e->rec_f, obs + (size_t)i * e->o, act + (size_t)i * e->a, rew[i], nobs + (size_t)i * e->o, dones[i]);
@@ -1811,6 +1839,7 @@ int sactd3_load_batch_device(sactd3_engine* e, const sactd3_device_fields* f, in
   RCCHK(fields_check(e, f, "load_batch_device"));
   const hipStream_t producer = (hipStream_t)producer_stream;
   RCCHK(src_order_begin(e, producer, flags));
+  SLOT_REFILL(e);
   e->cur_slot = 0;
   RCCHK(launch_batch_fields(e, field_src(e, f, 0)));
   RCCHK(src_order_end(e, producer, flags));
@@ -1960,6 +1989,97 @@ int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]) {
   return 0;
 }
 
+// ---- training on caller-chosen ring rows with loss weights, TD errors out (include/sactd3.h): what closes a prioritised sampler's loop
+// on the device.  (Its launches stand at the end of this file, see launch_ctail_nn_w.)
+static int device_ptr_check(sactd3_engine* e, const void* p, const char* what, const char* name) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
+    (void)hipGetLastError();
+    e->err = std::string(what) + ": `" + name + "` is not device memory of the engine's device";
+    return SACTD3_EINVAL;
+  }
+  return 0;
+}
+static int slot_weights_alloc(sactd3_engine* e) {      // (never zeroed: both staging kernels write all B entries before anything reads them)
+  return e->bs[0].w ? 0 : dalloc(e, &e->bs[0].w, (size_t)e->B, false);
+}
+
+// rb.sample() with the caller's indices and importance weights, all on the device: one k_batch_from_index launch fills slot 0 as the
+// index-injected gather of sactd3_rb_sample_with_indices does, plus the slot's w.  No host wait, no copy command, no sample-counter tick.
+int sactd3_rb_sample_indices_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n,
+                                    void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!idx) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: `idx` is NULL");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: unknown flag");
+  if (n != e->B) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: n must equal batch_size");
+  if (idx_ld < 1) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: row stride of `idx` is below its width");
+  if (w && w_ld < 1) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: row stride of `w` is below its width");
+  RCCHK(device_ptr_check(e, idx, "rb_sample_indices_device", "idx"));
+  if (w) RCCHK(device_ptr_check(e, w, "rb_sample_indices_device", "w"));
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_indices_device: buffer is empty");
+  CHAIN_BREAK(e);
+  RCCHK(slot_weights_alloc(e));
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  SLOT_REFILL(e);
+  e->cur_slot = 0;
+  RCCHK(launch_batch_index(e, (const long long*)idx, idx_ld, w, w_ld));
+  RCCHK(src_order_end(e, caller, flags));
+  e->slot_weighted = true;
+  ++e->prio_stats[0];
+  return 0;
+}
+
+// loss weights for whatever slot 0 holds (a caller-owned device batch, an index-staged one); NULL drops them
+int sactd3_batch_weights_device(sactd3_engine* e, const float* w, int64_t w_ld, int n, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "batch_weights_device: unknown flag");
+  if (n != e->B) return e->fail(SACTD3_EINVAL, "batch_weights_device: n must equal batch_size");
+  if (!w) { e->slot_weighted = false; return 0; }
+  if (w_ld < 1) return e->fail(SACTD3_EINVAL, "batch_weights_device: row stride of `w` is below its width");
+  RCCHK(device_ptr_check(e, w, "batch_weights_device", "w"));
+  CHAIN_BREAK(e);
+  RCCHK(slot_weights_alloc(e));
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  RCCHK(launch_batch_weights(e, w, w_ld));
+  RCCHK(src_order_end(e, caller, flags));
+  e->slot_weighted = true;
+  ++e->prio_stats[1];
+  return 0;
+}
+
+// q_k(i) - y(i) of the most recent critic update, left in the caller's device array: one k_td_to_field launch on the learner stream.
+// Reads e->q / e->y only; no CHAIN_BREAK: a precomputed opening pair stays valid across it.
+int sactd3_td_errors_device(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!td) return e->fail(SACTD3_EINVAL, "td_errors_device: `td` is NULL");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "td_errors_device: unknown flag");
+  if (td_ld < 1 || td_ns < 1) return e->fail(SACTD3_EINVAL, "td_errors_device: a stride of `td` is below 1");
+  RCCHK(device_ptr_check(e, td, "td_errors_device", "td"));
+  if (!e->td_valid) return e->fail(SACTD3_ESTATE, "td_errors_device: no critic update has run on the rows now in the batch slot");
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  RCCHK(launch_td_out(e, td, td_ld, td_ns));
+  RCCHK(src_order_end(e, caller, flags));
+  ++e->prio_stats[2];
+  return 0;
+}
+
+int sactd3_priority_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int refused = 0;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(&refused, &e->ctl->priority_refused, sizeof(int), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 3; ++i) out[i] = e->prio_stats[i];
+  out[3] = refused;
+  return 0;
+}
+
 int sactd3_rb_fill_synthetic(sactd3_engine* e, int64_t n, uint64_t seed) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
@@ -2016,8 +2136,13 @@ int sactd3_update_qnets(sactd3_engine* e) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   e->cur_slot = 0;
-  RCCHK(run_graph(e, G_Q, [&](EnqCtx& x) { return enqueue_update_qnets(x, IterPlace{}, false); }));
+  if (e->slot_weighted) {      // the weighted form: the same sequence with the weighted critic tail, a graph of its own
+    IterPlace it;
+    it.weighted = true;
+    RCCHK(run_graph(e, G_QW, [&](EnqCtx& x) { return enqueue_update_qnets(x, it, false); }));
+  } else RCCHK(run_graph(e, G_Q, [&](EnqCtx& x) { return enqueue_update_qnets(x, IterPlace{}, false); }));
   e->grads_stale[0] = false;
+  e->td_valid = true;
   return 0;
 }
 int sactd3_update_actor(sactd3_engine* e) {
@@ -2051,6 +2176,7 @@ int sactd3_step(sactd3_engine* e, int do_actor) {
   RCCHK(run_graph(e, which, [&](EnqCtx& x) { return enqueue_step(x, single_iteration(act, polyak)); }));
   e->qnet_updates = updates;
   e->cur_slot = 0;
+  e->slot_weighted = false; e->td_valid = true;      // (the fused paths draw their own sample and are never weighted)
   e->grads_stale[0] = false;
   if (act) e->grads_stale[1] = false;
   return 0;
@@ -2134,6 +2260,10 @@ int sactd3_step_period(sactd3_engine* e) {
     e->cur_slot = n - 1;
   }
   e->qnet_updates += n;
+  // (the period's iterations run one behind the other, each writing e->q / e->y in its critic tail; what runs ahead inside the first one
+  //  -- the later iterations' and the next period's opening passes -- goes through the actor only: cur_slot, e->q and e->y all belong to
+  //  the period's last iteration)
+  e->slot_weighted = false; e->td_valid = true;
   return 0;
 }
 
@@ -2160,6 +2290,7 @@ int sactd3_step_prefix(sactd3_engine* e, int m) {
   RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](EnqCtx& x) { return enqueue_period(x, v, m); }));
   e->cur_slot = m - 1;
   e->qnet_updates += m;
+  e->slot_weighted = false; e->td_valid = true;      // (as sactd3_step_period)
   return 0;
 }
 
@@ -2595,8 +2726,8 @@ int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_
 
 int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph) {
   if (!e) return SACTD3_EINVAL;
-  static const int map[8] = {G_Q, G_A, G_STEP01, G_STEP11, G_PERIOD, G_OPENING, G_PREFIX, G_PREFIX + 2};
-  if (which_graph < 0 || which_graph > 7) return SACTD3_EINVAL;
+  static const int map[9] = {G_Q, G_A, G_STEP01, G_STEP11, G_PERIOD, G_OPENING, G_PREFIX, G_PREFIX + 2, G_QW};
+  if (which_graph < 0 || which_graph > 8) return SACTD3_EINVAL;
   int w = map[which_graph];
   if (!e->graphs[w] && (which_graph == 2 || which_graph == 3)) w -= 1;   // the no-Polyak variant, if that is the one in use
   return e->graph_nodes[w];
@@ -2625,7 +2756,9 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
   int rc = 0;
   auto body = [&]() -> int {
     EnqCtx x{e, e->stream};
+    // (SLOT_REFILL: only where the kernel being timed overwrites batch slot 0)
     if (!strcmp(kernel, "gather")) {   // a fresh index draw per launch (k_tick bumps the sample counter): rows come from HBM, not from the caches
+      SLOT_REFILL(e);
       RCCHK(enqueue_gather(x, e->ring, -1));
       hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
       HIPCHK(hipGetLastError());
@@ -2644,7 +2777,7 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
       f.dones = (const uint8_t*)(e->stage_dev + e->ldc + e->ldo + 1);
       f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f;
-      if (!strcmp(kernel, "batch_from_fields")) { e->cur_slot = 0; return launch_batch_fields(e, field_src(e, &f, 0)); }
+      if (!strcmp(kernel, "batch_from_fields")) { SLOT_REFILL(e); e->cur_slot = 0; return launch_batch_fields(e, field_src(e, &f, 0)); }
       return launch_ingest_fields(e, field_src(e, &f, 0), (int)std::min<int64_t>(std::min(e->maxn, e->B), e->cfg.rb_capacity));
     }
     // the pack / unpack kernels of sactd3_predict_device on max_envs rows: observations read from the ring's records (the s columns,
@@ -2670,9 +2803,13 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       if (!strcmp(kernel, "sa_from_fields")) return launch_sa_pack(e, e->ring, e->rec_f, e->ring + e->o, e->rec_f, m);
       return launch_q_head(e, e->Pc, m, e->qs_z1, 1, Q_CHUNK);
     }
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head)");
+    // the staging and TD read-out kernels of the prioritised route on batch_size rows: indices from time_idx (as "rows_to_fields"), no
+    // weights, into batch slot 0 (overwritten); the TD errors of whatever e->q / e->y hold, written into the engine's own staging slab
+    if (!strcmp(kernel, "batch_from_index")) { RCCHK(slot_weights_alloc(e)); SLOT_REFILL(e); e->cur_slot = 0; return launch_batch_index(e, e->time_idx, 1, nullptr, 1); }
+    if (!strcmp(kernel, "td_to_field")) return launch_td_out(e, e->stage_dev, 1, e->B);
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field)");
   };
-  if (!strcmp(kernel, "rows_to_fields")) rc = time_rows_indices(e);
+  if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index")) rc = time_rows_indices(e);
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up
   if (rc == 0) {
     hipEventRecord(t0, e->stream);
@@ -2697,6 +2834,7 @@ int sactd3_time_nodes(sactd3_engine* e, int do_actor, int iters, int max_nodes, 
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_nodes: buffer is empty");
+  SLOT_REFILL(e);
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
   const bool period = do_actor == 2 && e->cfg.actor_update_delay > 0 && (e->cfg.prefer_td3_over_sac || e->cfg.crit_targ_update_freq == 1);
   if (act || period) RCCHK(actor_write_begin(e));
@@ -2817,3 +2955,45 @@ extern "C" __attribute__((visibility("default"))) int sactd3_debug_phases(sactd3
   return 0;
 }
 #endif
+
+// ---- the launches of the prioritised route (sactd3_rb_sample_indices_device, sactd3_batch_weights_device, sactd3_td_errors_device and
+// the weighted form of sactd3_update_qnets).  They stand here, behind everything else, because the compiler emits kernel template
+// instances in the order this file first names them (see launch_tails): the instances that existed before keep their place, and with
+// it their machine code.
+static int launch_ctail_nn_w(EnqCtx& x, const CtailNn& f, const float* w, double fl, double by, dim3 grid) {
+  const CtailNnW g{f, w};
+  LAUNCH("k_ctail_nn_w<2>", fl, by, k_ctail_nn_w<2>, grid, dim3(256), g);
+  return 0;
+}
+static int launch_critic_tail_w(EnqCtx& x, const CriticTail& t, const float* w, double fl, double by, dim3 grid) {
+  const CriticTailW g{t, w};
+  LAUNCH("k_critic_tail_w<16>", fl, by, k_critic_tail_w<16>, grid, dim3(256), g);
+  return 0;
+}
+static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld) {
+  const sactd3_engine::BatchSlot& S = e->bs[0];
+  IndexBatchArgs g{};
+  g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.cx = e->cx; g.cn = e->cn; g.B = e->B; g.len = (int)e->rb_len;
+  g.idx = idx; g.idx_ld = (long)idx_ld; g.w = w; g.w_ld = (long)w_ld;
+  g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.slot_idx = S.idx; g.wdst = S.w;
+  const long chunks = (long)e->B * e->rec4;      // (< 2^31: create_impl)
+  g.rec4_magic = magic_div((unsigned)e->rec4, (unsigned long long)chunks + 1);
+  const unsigned blocks = gather_blocks(chunks);
+  g.cpb = (int)((chunks + 256L * blocks - 1) / (256L * blocks));
+  g.refused = &e->ctl->priority_refused;
+  hipLaunchKernelGGL(k_batch_from_index, dim3(blocks), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_batch_weights(sactd3_engine* e, const float* w, int64_t w_ld) {
+  const WeightArgs g{w, (long)w_ld, e->bs[0].idx, e->bs[0].w, e->B, &e->ctl->priority_refused};
+  hipLaunchKernelGGL(k_batch_weights, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns) {
+  const TdArgs g{e->q, e->y, e->B, td, (long)td_ld, (long)td_ns};
+  hipLaunchKernelGGL(k_td_to_field, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}

@@ -101,9 +101,14 @@ struct DevCtl {
   // reason: a read-out on the learner stream may run beside acting kernels on other XCDs.
   alignas(128) int readout_refused;   // rows whose ring index was outside [0, len): handed out as zeros (sactd3_readout_stats)
   int pad_readout[31];
+  // ... and the word k_batch_from_index / k_batch_weights add to, once per row they neutralise (an index outside the ring, a weight that
+  // is negative, NaN or infinite): behind everything else again, so no existing offset moves (sactd3_priority_stats)
+  alignas(128) int priority_refused;
+  int pad_priority[31];
 };
 static_assert(offsetof(DevCtl, predict_ctr) % 128 == 0 && sizeof(DevCtl) % 128 == 0, "acting words need a line of their own");
 static_assert(offsetof(DevCtl, readout_refused) % 128 == 0 && offsetof(DevCtl, readout_refused) == offsetof(DevCtl, predict_ctr) + 128, "the read-out word sits behind the existing ones");
+static_assert(offsetof(DevCtl, priority_refused) == offsetof(DevCtl, readout_refused) + 128, "the priority word sits behind the read-out word");
 
 struct NetLayout {   // float offsets inside one net's parameter block (all multiples of 4)
   int K, ld1, nh;
@@ -653,6 +658,103 @@ __global__ __launch_bounds__(256) void k_rows_to_fields(FieldDst d, RowsOutArgs 
     if (!on[u]) continue;
     field_st(d, bb[u], cc[u], ok[u] ? v[u] : make_float4(0.f, 0.f, 0.f, 0.f), raw[u]);
   }
+}
+
+// Ring records chosen by a DEVICE int64 index array -> batch slot 0, with a per-row loss weight (sactd3_rb_sample_indices_device):
+// k_rows_to_fields's index discipline with gather_body's destinations.  A block moves a CONTIGUOUS span of cpb * 256 (row, chunk) pairs;
+// its rows' indices and weights are read once into LDS; then every ring load is issued, then every store.  X, Xn, rew, done receive
+// what the index-injected k_gather writes for the same indices, bit for bit.  An index outside [0, len) never becomes an address: the
+// row reads ring slot 0 and is stored as a zero record with slot index -1 and weight 0.  A weight that is negative, NaN or infinite is
+// stored as 0.  Either way the thread that owns the row's first chunk counts the row in `refused`, once.  w == NULL: every weight is 1.
+// The host keeps B * rec4 < 2^31.
+struct IndexBatchArgs {
+  const float4* ring; int rec4, cx, cn; int B, len;
+  const long long* idx; long idx_ld;      // index of row r: idx[r * idx_ld]
+  const float* w; long w_ld;              // weight of row r: w[r * w_ld] (NULL: 1)
+  float4* X; float4* Xn; float* rew; float* done; int* slot_idx; float* wdst;
+  unsigned rec4_magic;                    // as GatherArgs
+  int cpb;                                // chunks per thread, <= GATHER_CPT
+  int* refused;                           // DevCtl::priority_refused
+};
+// (w >= 0 is false for NaN, w < inf for +inf)
+__device__ __forceinline__ bool weight_ok(float w) { return w >= 0.f && w < __builtin_huge_valf(); }
+__global__ __launch_bounds__(256) void k_batch_from_index(IndexBatchArgs p) {
+  __shared__ long long ids_s[GATHER_CPT * 256 + 2];
+  __shared__ float w_s[GATHER_CPT * 256 + 2];
+  const unsigned total = (unsigned)p.B * (unsigned)p.rec4;
+  const unsigned c0 = blockIdx.x * (unsigned)p.cpb * 256u;
+  if (c0 >= total) return;                                             // (block-uniform)
+  const unsigned c1 = min(c0 + (unsigned)p.cpb * 256u, total);
+  const unsigned r0 = fast_div(c0, (unsigned)p.rec4, p.rec4_magic), r1 = fast_div(c1 - 1u, (unsigned)p.rec4, p.rec4_magic);
+  // both requests of a row go out before the first LDS store: one round trip, not two.  (w == NULL: the weight load reads the first
+  // word of the index array instead -- an address that is always valid -- and a select drops the value.)
+  const float* const wsrc = p.w ? p.w : reinterpret_cast<const float*>(p.idx);
+  const long wld = p.w ? p.w_ld : 0;
+  for (unsigned i = threadIdx.x; i <= r1 - r0; i += 256u) {
+    long long id = p.idx[(long)(r0 + i) * p.idx_ld];
+    float wi = wsrc[(long)(r0 + i) * wld];
+    PIN(wi);
+    ids_s[i] = id;
+    w_s[i] = p.w ? wi : 1.f;
+  }
+  __syncthreads();
+  int bb[GATHER_CPT], cc[GATHER_CPT], slot[GATHER_CPT]; float wv[GATHER_CPT]; float4 v[GATHER_CPT]; bool on[GATHER_CPT], ok[GATHER_CPT], first[GATHER_CPT];
+#pragma unroll
+  for (int u = 0; u < GATHER_CPT; ++u) {            // consecutive threads -> consecutive chunks of a record
+    const unsigned g = c0 + (unsigned)u * 256u + threadIdx.x;
+    on[u] = u < p.cpb && g < c1;
+    const unsigned q = on[u] ? fast_div(g, (unsigned)p.rec4, p.rec4_magic) : r0;
+    bb[u] = (int)q; cc[u] = on[u] ? (int)(g - q * (unsigned)p.rec4) : 0;
+    const long long raw = ids_s[q - r0];
+    wv[u] = w_s[q - r0];
+    ok[u] = raw >= 0 && raw < (long long)p.len;
+    slot[u] = ok[u] ? (int)raw : 0;
+    first[u] = on[u] && cc[u] == 0;
+    on[u] = on[u] && cc[u] <= p.cx + p.cn;           // trailing pad chunk(s) are not moved
+  }
+#pragma unroll
+  for (int u = 0; u < GATHER_CPT; ++u) v[u] = p.ring[(long)slot[u] * p.rec4 + (on[u] ? cc[u] : 0)];
+#pragma unroll
+  for (int u = 0; u < GATHER_CPT; ++u) { PIN(v[u].x); PIN(v[u].y); PIN(v[u].z); PIN(v[u].w); }      // every request is out before the first store
+#pragma unroll
+  for (int u = 0; u < GATHER_CPT; ++u) {
+    const int b = bb[u], c = cc[u];
+    if (first[u]) {
+      const bool wok = weight_ok(wv[u]);
+      p.slot_idx[b] = ok[u] ? slot[u] : -1;
+      p.wdst[b] = (ok[u] && wok) ? wv[u] : 0.f;
+      if (!ok[u] || !wok) atomicAdd(p.refused, 1);
+    }
+    if (!on[u]) continue;
+    const float4 o4 = ok[u] ? v[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < p.cx) p.X[(long)b * p.cx + c] = o4;
+    else if (c < p.cx + p.cn) p.Xn[(long)b * p.cx + (c - p.cx)] = o4;
+    else { p.rew[b] = o4.x; p.done[b] = o4.y; }
+  }
+}
+
+// Loss weights for whatever batch slot 0 holds (sactd3_batch_weights_device): one thread per row.  A weight that is negative, NaN or
+// infinite is stored as 0 and counted; a row whose slot index is -1 (refused by k_batch_from_index) keeps weight 0.
+struct WeightArgs { const float* w; long w_ld; const int* slot_idx; float* wdst; int B; int* refused; };
+__global__ __launch_bounds__(256) void k_batch_weights(WeightArgs p) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= p.B) return;
+  const float wv = p.w[(long)b * p.w_ld];
+  const int ix = p.slot_idx[b];
+  const bool wok = weight_ok(wv);
+  if (!wok) atomicAdd(p.refused, 1);
+  p.wdst[b] = (wok && ix >= 0) ? wv : 0.f;
+}
+
+// The per-row TD errors of the most recent critic update (sactd3_td_errors_device): td[k * td_ns + b * td_ld] = q[k][b] - y[b], one
+// thread per row, from the values the critic tail stored; nothing else is read, nothing else written.
+struct TdArgs { const float* q; const float* y; int B; float* td; long td_ld, td_ns; };
+__global__ __launch_bounds__(256) void k_td_to_field(TdArgs p) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= p.B) return;
+  const float q0 = p.q[b], q1 = p.q[p.B + b], yv = p.y[b];
+  p.td[(long)b * p.td_ld] = q0 - yv;
+  p.td[p.td_ns + (long)b * p.td_ld] = q1 - yv;
 }
 
 // Acting on DEVICE observations (sactd3_predict_device): the way in and the way out of the engine's own acting buffers.
@@ -2686,74 +2788,22 @@ struct CriticTail {
 };
 
 // RPB rows per block (blockDim = 16 RPB): fewer rows per block = fewer bytes fetched per CU for these fetch-bound kernels
+// (the body lives in critic_tail_body.inc, shared with the weighted form below)
 template <int RPB>
 __global__ __launch_bounds__(16 * RPB) void k_critic_tail(CriticTail p) {
-  __shared__ __attribute__((aligned(16))) float cs[3 * RPB * HID];
-  __shared__ float sc[RPB][2];
-  const int t = threadIdx.x, row = t >> 4, sub = t & 15, net = blockIdx.y;
-  const int b = blockIdx.x * RPB + row, bc = min(b, p.B - 1);
-  const bool valid = b < p.B;
-  const float* Pn = p.P + net * p.p_ns;
-  STAMP(0);
-  // loads first
-  const Row16 zt0 = row_ld(p.z2t + (long)bc * HID, sub), zt1 = row_ld(p.z2t + ((long)p.B + bc) * HID, sub);
-  const Row16 zo = row_ld(p.z2 + ((long)net * p.B + bc) * HID, sub);
-  const Row16 wt0 = row_ld(p.PT + p.L.Wh, sub), wt1 = row_ld(p.PT + p.p_ns + p.L.Wh, sub), wo = row_ld(Pn + p.L.Wh, sub);
-  Row16 gt0, bt0, gt1, bt1, go, bo;
-  if (p.ln) {
-    gt0 = row_ld(p.PT + p.L.g2, sub); bt0 = row_ld(p.PT + p.L.be2, sub);
-    gt1 = row_ld(p.PT + p.p_ns + p.L.g2, sub); bt1 = row_ld(p.PT + p.p_ns + p.L.be2, sub);
-    go = row_ld(Pn + p.L.g2, sub); bo = row_ld(Pn + p.L.be2, sub);
-  }
-  const float bht0 = p.PT[p.L.bh], bht1 = p.PT[p.p_ns + p.L.bh], bho = Pn[p.L.bh];
-  const float rw = p.rew[bc], dn = p.done[bc];
-  const float alpha = p.sac ? expf(*p.log_alpha) : 0.f;
-  const float lpn = p.sac ? p.logp_next[bc] : 0.f;
-  STAMP(1);
-  Row16 xh, y, h; float rs;
-  ln_fwd(zt0, gt0, bt0, p.ln, xh, y, rs);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) h.v[q] = relu4(y.v[q]);
-  const float qt0 = row16_sum(row_dot(h, wt0)) + bht0;
-  ln_fwd(zt1, gt1, bt1, p.ln, xh, y, rs);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) h.v[q] = relu4(y.v[q]);
-  const float qt1 = row16_sum(row_dot(h, wt1)) + bht1;
-  const float qmin = fminf(qt0, qt1);
-  float qp = p.bcq ? 0.75f * qmin + 0.25f * fmaxf(qt0, qt1) : qmin;
-  if (p.sac) qp -= alpha * lpn;
-  const float yv = rw + (1.0f - dn) * p.gamma * qp;
-  float rstd;
-  ln_fwd(zo, go, bo, p.ln, xh, y, rstd);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) h.v[q] = relu4(y.v[q]);
-  const float qv = row16_sum(row_dot(h, wo)) + bho;
-  const float err = valid ? qv - yv : 0.f;
-  const float dq = 2.0f * err / (float)p.B;
-  Row16 dy, vals[3];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dy.v[q] = gate4(wo.v[q] * dq, y.v[q]);
-  const Row16 dz = ln_bwd(dy, xh, rstd, go, p.ln);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { vals[0].v[q] = dy.v[q] * xh.v[q]; vals[1].v[q] = dy.v[q]; vals[2].v[q] = h.v[q] * dq; }
-  if (valid) {
-    row_st(p.dz2 + ((long)net * p.B + b) * HID, sub, dz);
-    if (sub == 0) {
-      p.q[(long)net * p.B + b] = qv;
-      if (net == 0) { p.qt[b] = qt0; p.qt[p.B + b] = qt1; p.y[b] = yv; }
-    }
-  }
-  if (sub == 0) { sc[row][0] = dq; sc[row][1] = err * err; }
-  STAMP(2);
-  const long blk = (long)net * p.pstride + blockIdx.x;
-  block_colsum<RPB>(cs, vals, 3, row, sub, p.part + blk * NSLOT * HID);   // (has the barrier that publishes sc)
-  if (t < 2) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < RPB; ++i) s += sc[i][t];
-    p.part_s[blk * 2 + t] = s;
-  }
-  STAMP(3);
+#define TAIL_WEIGHTED 0
+#include "critic_tail_body.inc"
+#undef TAIL_WEIGHTED
+}
+// The weighted form (sactd3_update_qnets on a slot that carries loss weights): w[b] multiplies the row's dq and its err^2.
+struct CriticTailW { CriticTail c; const float* w; };      // w [B]
+template <int RPB>
+__global__ __launch_bounds__(16 * RPB) void k_critic_tail_w(CriticTailW pw) {
+  const CriticTail& p = pw.c;
+  const float* const wp = pw.w;
+#define TAIL_WEIGHTED 1
+#include "critic_tail_body.inc"
+#undef TAIL_WEIGHTED
 }
 
 // The forward third of k_critic_tail and nothing else (sactd3_qvalues_device): Q_net(row) = relu(LN(z2)) . Wh + bh for the twin
@@ -2812,141 +2862,21 @@ __device__ __forceinline__ void nn_fold_store(const NnFold& f, const float* o, c
     }
   }
 }
+// (the body lives in ctail_nn_body.inc, shared with the weighted form below)
 template <int NT>
 __global__ __launch_bounds__(256) void k_ctail_nn(CtailNn a) {
-  const CriticTail& p = a.c;
-  constexpr int CB = 16 * NT;                               // columns per block
-  __shared__ __attribute__((aligned(16))) float Dz[16 * AS];
-  __shared__ __attribute__((aligned(16))) float cs[3 * 16 * CB];
-  __shared__ __attribute__((aligned(16))) float red[NT * 4 * 64 * 4];
-  __shared__ float sc[16][2];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, row = t >> 4, sub = t & 15, net = blockIdx.z;
-  const int r = lane & 15, kq = lane >> 4;
-  int tm, tk;
-  xcd_tile(blockIdx.x, (p.B + 15) >> 4, HID / CB, a.xr, tm, tk);
-  const int b = tm * 16 + row, bc = min(b, p.B - 1), c_lo = tk * CB;
-  const bool valid = b < p.B;
-  const float* Pn = p.P + net * p.p_ns;
-  // ---- every load: the tail's rows and parameters, then this block's W2 fragments (k_nn's B operand)
-  const Row16 zt0 = row_ld(p.z2t + (long)bc * HID, sub), zt1 = row_ld(p.z2t + ((long)p.B + bc) * HID, sub);
-  const Row16 zo = row_ld(p.z2 + ((long)net * p.B + bc) * HID, sub);
-  const Row16 wt0 = row_ld(p.PT + p.L.Wh, sub), wt1 = row_ld(p.PT + p.p_ns + p.L.Wh, sub), wo = row_ld(Pn + p.L.Wh, sub);
-  Row16 gt0, bt0, gt1, bt1, go, bo;
-  if (p.ln) {
-    gt0 = row_ld(p.PT + p.L.g2, sub); bt0 = row_ld(p.PT + p.L.be2, sub);
-    gt1 = row_ld(p.PT + p.p_ns + p.L.g2, sub); bt1 = row_ld(p.PT + p.p_ns + p.L.be2, sub);
-    go = row_ld(Pn + p.L.g2, sub); bo = row_ld(Pn + p.L.be2, sub);
-  }
-  const float bht0 = p.PT[p.L.bh], bht1 = p.PT[p.p_ns + p.L.bh], bho = Pn[p.L.bh];
-  const float rw = p.rew[bc], dn = p.done[bc];
-  const float alpha = p.sac ? expf(*p.log_alpha) : 0.f;
-  const float lpn = p.sac ? p.logp_next[bc] : 0.f;
-  const int nb = 64 * wave + 4 * kq;
-  float4 bv[NT][4];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const float* Wc = a.Wt + net * p.p_ns + (long)nb * a.ldw + c_lo + 16 * nt + r;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float* w = Wc + (long)(16 * c) * a.ldw;
-      bv[nt][c] = make_float4(w[0], w[a.ldw], w[2 * (long)a.ldw], w[3 * (long)a.ldw]);
-    }
-  }
-  float fh[4] = {1.f, 1.f, 1.f, 1.f}, fx[4] = {0.f, 0.f, 0.f, 0.f}, fg = 1.f;      // the epilogue's layer-1 operands (waves < NT)
-  if (a.f.fold && wave < NT) {
-    const int col = c_lo + 16 * wave + (lane & 15);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const long o = ((long)net * p.B + min(tm * 16 + 4 * (lane >> 4) + i, p.B - 1)) * HID + col;
-      fh[i] = a.f.h1[o]; if (a.f.ln) fx[i] = a.f.xh1[o];
-    }
-    if (a.f.ln) fg = Pn[a.f.g1_off + col];
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  // ---- the tail (k_critic_tail's arithmetic, agents/agent.py:208-233)
-  Row16 xh, y, h; float rs;
-  ln_fwd(zt0, gt0, bt0, p.ln, xh, y, rs);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) h.v[q] = relu4(y.v[q]);
-  const float qt0 = row16_sum(row_dot(h, wt0)) + bht0;
-  ln_fwd(zt1, gt1, bt1, p.ln, xh, y, rs);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) h.v[q] = relu4(y.v[q]);
-  const float qt1 = row16_sum(row_dot(h, wt1)) + bht1;
-  const float qmin = fminf(qt0, qt1);
-  float qp = p.bcq ? 0.75f * qmin + 0.25f * fmaxf(qt0, qt1) : qmin;
-  if (p.sac) qp -= alpha * lpn;
-  const float yv = rw + (1.0f - dn) * p.gamma * qp;
-  float rstd;
-  ln_fwd(zo, go, bo, p.ln, xh, y, rstd);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) h.v[q] = relu4(y.v[q]);
-  const float qv = row16_sum(row_dot(h, wo)) + bho;
-  const float err = valid ? qv - yv : 0.f;
-  const float dq = 2.0f * err / (float)p.B;
-  Row16 dy, vals[3];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dy.v[q] = gate4(wo.v[q] * dq, y.v[q]);
-  const Row16 dz = ln_bwd(dy, xh, rstd, go, p.ln);          // (rows beyond the batch: err = 0 -> all zeros)
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { vals[0].v[q] = dy.v[q] * xh.v[q]; vals[1].v[q] = dy.v[q]; vals[2].v[q] = h.v[q] * dq; }
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { PIN(bv[nt][c].x); PIN(bv[nt][c].y); PIN(bv[nt][c].z); PIN(bv[nt][c].w); }
-  // ---- stores of this block's share: its columns of dz2 and of the three column partials; scalars by the column-tile-0 block
-  row_st(Dz + row * AS, sub, dz);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int col = 4 * sub + 64 * q;                      // (the thread's float4 of chunk q lies inside one 16-column tile)
-    if (col >= c_lo && col < c_lo + CB) {
-      if (valid) st4_pol<WT_DZ>(p.dz2, ((long)net * p.B + b) * HID + col, dz.v[q]);
-#pragma unroll
-      for (int sl = 0; sl < 3; ++sl) st4(cs + (sl * 16 + row) * CB + (col - c_lo), vals[sl].v[q]);
-    }
-  }
-  if (tk == 0 && sub == 0) {
-    sc[row][0] = dq; sc[row][1] = err * err;
-    if (valid) {
-      p.q[(long)net * p.B + b] = qv;
-      if (net == 0) { p.qt[b] = qt0; p.qt[p.B + b] = qt1; p.y[b] = yv; }
-    }
-  }
-  __syncthreads();
-  const long blk = (long)net * p.pstride + tm;
-  if (t < 3 * CB) {
-    const int sl = t / CB, c = t - sl * CB;
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sum += cs[(sl * 16 + i) * CB + c];
-    p.part[(blk * NSLOT + sl) * HID + c_lo + c] = sum;
-  }
-  if (tk == 0 && t >= 128 && t < 130) {
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sum += sc[i][t - 128];
-    p.part_s[blk * 2 + (t - 128)] = sum;
-  }
-  // ---- dh1 tile(s): rows from LDS, W2 fragments from registers, the 256-long reduction split over the 4 waves (k_nn)
-  f32x4 acc[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const float4 av = ld4(Dz + r * AS + nb + 16 * c);
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) { MFMA4(acc[nt], av, bv[nt][c]); }
-  }
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) st4(red + ((nt * 4 + wave) * 64 + lane) * 4, make_float4(acc[nt][0], acc[nt][1], acc[nt][2], acc[nt][3]));
-  __syncthreads();
-  if (wave < NT) {
-    const float* rr = red + (wave * 4 * 64 + lane) * 4;
-    const float4 x0 = ld4(rr), x1 = ld4(rr + 256), x2 = ld4(rr + 512), x3 = ld4(rr + 768);
-    const float o[4] = {(x0.x + x1.x) + (x2.x + x3.x), (x0.y + x1.y) + (x2.y + x3.y), (x0.z + x1.z) + (x2.z + x3.z), (x0.w + x1.w) + (x2.w + x3.w)};
-    const int col = c_lo + 16 * wave + (lane & 15);
-    nn_fold_store(a.f, o, fh, fx, fg, a.dX + (long)net * p.B * HID, a.f.ps + (long)net * p.B * PS_W, a.f.gsnap + net * HID, tm * 16, p.B, col, lane);
-  }
+#define TAIL_WEIGHTED 0
+#include "ctail_nn_body.inc"
+#undef TAIL_WEIGHTED
+}
+struct CtailNnW { CtailNn a; const float* w; };      // w [B]: the slot's loss weights (see k_critic_tail_w)
+template <int NT>
+__global__ __launch_bounds__(256) void k_ctail_nn_w(CtailNnW aw) {
+  const CtailNn& a = aw.a;
+  const float* const wp = aw.w;
+#define TAIL_WEIGHTED 1
+#include "ctail_nn_body.inc"
+#undef TAIL_WEIGHTED
 }
 
 struct ActorQTail {

@@ -439,6 +439,33 @@ class Engine:
         self._ck(self.lib.sactd3_qvalues_stats(self._h, out))
         return dict(calls=int(out[0]), rows=int(out[1]), ordered_calls=int(out[2]), policy_calls=int(out[3]))
 
+    def rb_sample_indices_device(self, idx_ptr: int, idx_ld: int, w_ptr: int, w_ld: int, n: int, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_rb_sample_indices_device: fill the batch slot with the ring records a device int64 array names (`idx_ptr`, stride
+        `idx_ld` elements; n == batch_size) and the slot's loss weights from a device float32 array (`w_ptr`, `w_ld`; address 0: all 1).
+        One launch, no host wait.  An index outside [0, rb_len) gives a zero record with slot index -1 and weight 0; a weight that is
+        negative, NaN or infinite is staged as 0; both are counted in priority_stats()["rows_refused"]."""
+        self._ck(self.lib.sactd3_rb_sample_indices_device(self._h, C.c_void_p(int(idx_ptr) or None), int(idx_ld), C.c_void_p(int(w_ptr) or None),
+                                                          int(w_ld), int(n), C.c_void_p(int(stream) or None), _lib.SRC_ORDERED if ordered else 0))
+
+    def batch_weights_device(self, w_ptr: int, w_ld: int, n: int, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_batch_weights_device: loss weights (device float32, `w_ptr` / `w_ld`, n == batch_size) for whatever the batch slot
+        holds; address 0 drops the weights.  While the slot carries weights update_qnets() minimises (1 / B) sum_i w_i err_i^2."""
+        self._ck(self.lib.sactd3_batch_weights_device(self._h, C.c_void_p(int(w_ptr) or None), int(w_ld), int(n),
+                                                      C.c_void_p(int(stream) or None), _lib.SRC_ORDERED if ordered else 0))
+
+    def td_errors_device(self, td_ptr: int, td_ld: int, td_ns: int, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_td_errors_device: Q_k(s_i, a_i) - y_i of the most recent critic update to the float32 at `td_ptr` + 4 (k `td_ns` +
+        i `td_ld`), in this device's memory.  One launch, no host wait; EngineError (SACTD3_ESTATE) when no critic update has run on
+        the rows now in the batch slot."""
+        self._ck(self.lib.sactd3_td_errors_device(self._h, C.c_void_p(int(td_ptr) or None), int(td_ld), int(td_ns),
+                                                  C.c_void_p(int(stream) or None), _lib.DST_ORDERED if ordered else 0))
+
+    def priority_stats(self) -> Dict[str, int]:
+        """counters of the prioritised route (sactd3_priority_stats; waits for the engine's stream: the last one lives on the device)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.sactd3_priority_stats(self._h, out))
+        return dict(index_stagings=int(out[0]), weight_stagings=int(out[1]), td_readouts=int(out[2]), rows_refused=int(out[3]))
+
     def acting_stats(self) -> Dict[str, int]:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
         out = (C.c_int64 * 4)()

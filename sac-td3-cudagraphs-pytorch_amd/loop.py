@@ -4,6 +4,7 @@ be driven end to end without tensordict / torchrl / gymnasium being importable:
   Rollout / segment()   the acting side + its generator  orchestrator.py:42-118   
   DeviceRollout         the same acting side for a vector env that lives on the GPU: every array a device tensor, no host wait
   train()       the training loop's control flow       orchestrator.py:317-352 (+ counters :326,342,349)
+  ProportionalSampler   proportional prioritised replay (not in the reference): a priority array on the device for train(sampler=...)
   episode()     evaluation-episode generator           orchestrator.py:121-246 (lengths / returns, trajectories with need_lists; no pixels)
   evaluate()    offline evaluation of a checkpoint     orchestrator.py:415-481 (trajectory files as .npz)
   Evaluator     the eval block of the loop             orchestrator.py:303-305,354-403 (rolling window, best model, speed)
@@ -150,8 +151,50 @@ def segment(env, agent, seed: int, segment_len: int, learning_starts: int, actio
         ro.advance()
 
 
+class ProportionalSampler:
+    """Proportional prioritised replay (Schaul et al. 2016) as a sampler the engine does not own: one float32 priority per ring slot in
+    a torch tensor on `device`, nothing else -- no tree, no storage (the rows stay in the engine's ring).  Every method is torch ops on
+    that device and never reads a device value on the host.
+      extend(n)          the n rows the ring just received (its cursor is mirrored here, wrapping at `capacity`) enter at the current
+                         maximum priority
+      sample(B)          -> (index [B] int64, weights [B] float32): index ~ P(i) = p_i^alpha / sum_j p_j^alpha over the N rows held
+                         (torch.multinomial, with replacement: N <= 2^24), weights = (N P(i))^-beta / the batch's largest
+      update(index, td)  p_index = max over critics of |td| + eps, td = Agent.td_errors() ([2, B, 1]) of the update on those rows
+    Meant for ReplayBuffer.sample_at(index, weights) -> Agent.update_qnets -> Agent.td_errors(): see train(sampler=...)."""
+
+    def __init__(self, capacity: int, alpha: float = 0.6, beta: float = 0.4, eps: float = 1e-6, device: Any = None):
+        import torch
+        self._torch = torch
+        self.capacity, self.alpha, self.beta, self.eps = int(capacity), float(alpha), float(beta), float(eps)
+        self.priorities = torch.zeros(self.capacity, dtype=torch.float32, device=device)
+        self.max_priority = torch.ones((), dtype=torch.float32, device=device)
+        self.len, self.cursor = 0, 0                                  # host mirrors of the ring's length and write cursor
+
+    def extend(self, n: int) -> None:
+        torch = self._torch
+        slots = (torch.arange(int(n), device=self.priorities.device) + self.cursor) % self.capacity
+        self.priorities[slots] = self.max_priority
+        self.cursor = (self.cursor + int(n)) % self.capacity
+        self.len = min(self.capacity, self.len + int(n))
+
+    def sample(self, batch_size: int):
+        if self.len < 1:
+            raise ValueError("ProportionalSampler.sample: no rows yet (extend() first)")
+        torch = self._torch
+        scaled = self.priorities[:self.len].pow(self.alpha)
+        index = torch.multinomial(scaled, int(batch_size), replacement=True)
+        weights = (scaled[index] * (self.len / scaled.sum())).pow(-self.beta)
+        return index, weights / weights.max()
+
+    def update(self, index, td) -> None:
+        new = td.detach().abs().amax(dim=0).reshape(-1) + self.eps
+        self.priorities[index] = new
+        self.max_priority = self._torch.maximum(self.max_priority, new.max())
+
+
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
-          evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False) -> Dict[str, float]:
+          evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
+          sampler: Optional[ProportionalSampler] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -160,7 +203,12 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     `overlap=True` (an agent with predict_begin / predict_end): the action that opens the next segment is computed on the engine's
     acting stream while this iteration's update runs; a pending action is collected before an evaluation acts with the agent.
     `device_env=True`: `env` lives on the GPU (device tensors in and out, e.g. SyntheticDeviceVecEnv) and is driven by `DeviceRollout`
-    -- `agent.predict_device`, no host round trip per env step.  It acts on the learner stream, so it excludes `overlap`."""
+    -- `agent.predict_device`, no host round trip per env step.  It acts on the learner stream, so it excludes `overlap`.
+    `sampler` (a ProportionalSampler; needs `fused=False`: the fused iteration owns its uniform sampler): prioritised replay, call
+    by call on the device -- the sampler's rows and importance weights through `rb.sample_at`, the critic update weighted by them,
+    its TD errors (`agent.td_errors`) back into the sampler's priorities; the actor updates train on the same rows, unweighted."""
+    if sampler is not None and fused:
+        raise ValueError("sampler=... needs fused=False: the fused iteration samples uniformly inside its graph")
     if overlap and device_env:
         raise ValueError("overlap=True and device_env=True exclude each other: predict_device acts on the learner stream")
     ro = Rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat, overlap=True) if overlap else None
@@ -174,14 +222,22 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
             evaluator.maybe_start_clock(agent.timesteps_so_far)           # orchestrator.py:319-322
         next(seg_gen)
         agent.timesteps_so_far += cfg.segment_len * cfg.num_envs
+        if sampler is not None:
+            sampler.extend(cfg.segment_len * cfg.num_envs)                # the rows the segment just appended
         if agent.timesteps_so_far <= cfg.learning_starts:
             i += 1
             continue
         if fused:
             agent.iteration(i)
         else:
-            batch = agent.rb.sample(cfg.batch_size)
+            if sampler is None:
+                batch = agent.rb.sample(cfg.batch_size)
+            else:
+                index, weights = sampler.sample(cfg.batch_size)
+                batch = agent.rb.sample_at(index, weights)
             tlog.update(agent.update_qnets(batch))
+            if sampler is not None:
+                sampler.update(index, agent.td_errors())
             agent.qnet_updates_so_far += 1
             if i % (cfg.actor_update_delay + 1) == 0:
                 for _ in range(cfg.actor_update_delay):
