@@ -235,6 +235,55 @@ int sactd3_batch_weights_device(sactd3_engine* e, const float* w, int64_t w_ld, 
 int sactd3_td_errors_device(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns, void* caller_stream, int flags /* SACTD3_DST_ORDERED */);
 /* [sync] out = {index stagings, weight stagings, td read-outs, rows refused on the device (bad index or bad weight; one per row and call)} */
 int sactd3_priority_stats(sactd3_engine* e, int64_t out[4]);
+/* ---- prioritised replay the engine owns: proportional prioritisation (Schaul et al. 2016, proportional variant, draws with replacement)
+ * with the priorities, their partial sums, the running maximum and the draw counter all in device memory, maintained by kernels on the
+ * learner stream.  A prioritised iteration is four calls with no arithmetic of the caller's in between:
+ *     sactd3_rb_sample_prioritized -> sactd3_update_qnets (its weighted form) -> sactd3_prio_update_from_td -> [sactd3_update_actor] ->
+ *     sactd3_update_targ_nets
+ * Nothing above changes: an engine that never calls sactd3_prio_enable allocates nothing more and launches nothing more.
+ * State: leaf[rb_capacity] = p_i^alpha per ring slot (0 for a slot the ring has not filled) and one sum per group of 1024 consecutive
+ * slots, ALWAYS recomputed from the group's leaves in a fixed order, never adjusted incrementally: two histories that reach the same
+ * leaves reach the same sums bit for bit.  The top level is as wide as the ring needs; any rb_capacity works.
+ * Allocates and builds the table; rows already in the ring enter at priority 1 (the starting maximum).  alpha >= 0 and eps > 0, both
+ * finite, else SACTD3_EINVAL; a second call with the same values does nothing, with other values SACTD3_ESTATE.  From then on every
+ * append path (sactd3_rb_extend, _extend_device, _extend_fields_device -- across the wrap too -- and sactd3_rb_fill_synthetic) issues one
+ * more launch behind its own, which gives the rows it wrote the current maximum priority and re-sums the groups they touch. [sync] */
+int sactd3_prio_enable(sactd3_engine* e, float alpha, float eps);
+/* rb.sample(batch_size) by priority.  batch_size uniforms u_b come from the Philox stream SACTD3_STREAM_PRIO (0x300: counter words
+ * (draw counter, 0, 0x300, b >> 2), word b & 3, mapped to (0, 1) with 24 bits and kept below 1); the draw counter is a device word of its
+ * own, advanced on the device once per call -- the uniform sampler's counter is not consumed.  With T the total of the leaves of rows
+ * [0, sactd3_rb_len) and c their inclusive running sum, row b gets the smallest slot i with c[i] > u_b * T (one fp32 multiply) and a
+ * positive leaf: a slot of priority 0 or beyond the ring length is never drawn.  (In fp32 the running sums are those of the two-level
+ * table: where they are exact -- integer priorities -- the rule above holds to the letter.)  Batch slot 0 receives those rows and
+ * their ring slots, bit for bit what sactd3_rb_sample_indices_device leaves for the same indices, and the per-row weights
+ *     w_b = (N leaf_i / T)^(-beta) / max_b' (...),   N = sactd3_rb_len   (beta == 0: exactly 1; the batch's largest: exactly 1)
+ * and "the slot carries weights" is set: sactd3_update_qnets runs its weighted graph.  Three launches (draw, weights, staging), no copy
+ * command, no host wait.  T == 0 (every priority 0): every row is stored as a refused row (ring slot -1, weight 0) and counted in
+ * sactd3_priority_stats; never a fault.  SACTD3_ESTATE if priorities are not enabled or the ring is empty; SACTD3_EINVAL for a
+ * negative or non-finite beta. */
+int sactd3_rb_sample_prioritized(sactd3_engine* e, float beta);
+/* Injected uniforms for parity tests, like sactd3_set_noise: host array, n == batch_size, clamped into [0, 1), sticky; the draw counter
+ * stands still while they are in use.  u == NULL: back to the native draws. [sync] */
+int sactd3_prio_set_uniforms(sactd3_engine* e, const float* u, int n);
+/* The write-back for the rows in the batch slot from the critic update that just ran on them (preconditions of
+ * sactd3_td_errors_device, SACTD3_ESTATE otherwise): p = max_k |Q_k - y| + eps, leaf[slot] = p^alpha (alpha == 1: p itself, no pow),
+ * max priority = max(max priority, p).  Rows with ring slot -1 are skipped; a non-finite TD error leaves its leaf untouched; both are
+ * counted (sactd3_prio_stats).  Where a slot occurs several times in the batch the occurrence at the highest batch position wins --
+ * decided by position, not by which store lands last.  One launch, one workgroup per batch row; no host wait.  Invisible to the
+ * uniform sampler and the fused paths: a precomputed opening pair of sactd3_step_period stays valid.
+ * Known and accepted: a row an append overwrote between its draw and this call receives the stale TD error's priority. */
+int sactd3_prio_update_from_td(sactd3_engine* e);
+/* The same write-back for caller-supplied DEVICE arrays (idx[i * idx_ld] the ring slot, prio[i * prio_ld] the UNSCALED priority), any
+ * n >= 1.  A priority >= 0 and finite is taken as given (no eps is added; 0 excludes the row from the draws).  A negative, NaN or
+ * infinite priority or an index outside [0, sactd3_rb_len) is refused: it never becomes an address, the leaf stays untouched, the row
+ * is counted.  Same duplicate rule.  Each workgroup walks all n rows: meant for batches, not for whole rings.
+ * flags & SACTD3_SRC_ORDERED as sactd3_load_batch_device.  SACTD3_EINVAL (NULL or non-device pointers, n < 1, a stride below 1, an
+ * unknown flag) leaves the engine usable; SACTD3_ESTATE if priorities are not enabled. */
+int sactd3_prio_update_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* prio, int64_t prio_ld, int n,
+                              void* caller_stream, int flags /* SACTD3_SRC_ORDERED */);
+/* [sync] out = {prioritised samples, write-backs, rows a write-back refused (counted on the device), rows that entered at the maximum
+ * priority (sactd3_prio_enable's included)} */
+int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]);
 /* rb.sample(batch_size) (orchestrator.py:338): uniform-with-replacement indices from the engine's
  * Philox stream + gather into the engine-owned batch slot. */
 int sactd3_rb_sample(sactd3_engine* e);
@@ -382,7 +431,9 @@ int sactd3_sync(sactd3_engine* e);                                          /* [
 /* copy a named internal device buffer to the host; returns the number of floats it holds (or < 0).
  * With dst == NULL only the size is returned. Names: see sactd3_debug_names(). [sync]
  * "grad_critics", "c_dz1", "grad_actor", "a_dz1": SACTD3_ESTATE while the family's last writer was a period / cut-short period
- * graph, which leaves them out (see sactd3_step_period) -- stale gradients are not handed out. */
+ * graph, which leaves them out (see sactd3_step_period) -- stale gradients are not handed out.
+ * "prio_leaf" [rb_capacity], "prio_sums" (the level above the leaves: one sum per 1024 slots), "prio_max" [1] and "prio_weights"
+ * [batch_size] (the loss weights batch slot 0 carries, whichever call staged them): SACTD3_ESTATE before sactd3_prio_enable. */
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats);
 const char* sactd3_debug_names(void);
 /* number of kernel nodes in the instantiated graph of: 0 update_qnets, 1 update_actor, 2 step(do_actor=0), 3 step(do_actor=1), 4 step_period,
@@ -399,7 +450,9 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
  * "sa_from_fields" / "q_head" (the pack / head kernels of sactd3_qvalues_device on 1024 rows of the scoring scratch, [s | a] read from
  * the ring's records), "batch_from_index" / "td_to_field" (the staging and TD read-out kernels of sactd3_rb_sample_indices_device /
  * sactd3_td_errors_device on batch_size rows: indices as for "rows_to_fields", no weights, into the batch slot; the TD errors into the
- * engine's own staging slab). [sync] */
+ * engine's own staging slab), "prio_sample" / "prio_update" (SACTD3_ESTATE before sactd3_prio_enable: one whole
+ * sactd3_rb_sample_prioritized with beta 0.4 -- its three launches, the batch slot overwritten, the draw counter advanced -- / the
+ * write-back kernel on batch_size rows, indices as for "rows_to_fields", every priority 1: those rows' priorities are overwritten). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

@@ -34,6 +34,8 @@ SYMBOLS = [
     "sactd3_read_batch_device", "sactd3_rb_read_rows_device", "sactd3_readout_stats",
     "sactd3_qvalues_device", "sactd3_qvalues", "sactd3_qvalues_stats",
     "sactd3_rb_sample_indices_device", "sactd3_batch_weights_device", "sactd3_td_errors_device", "sactd3_priority_stats",
+    "sactd3_prio_enable", "sactd3_rb_sample_prioritized", "sactd3_prio_set_uniforms", "sactd3_prio_update_from_td", "sactd3_prio_update_device",
+    "sactd3_prio_stats",
 ]
 
 
@@ -139,6 +141,12 @@ def load_library():
         "sactd3_batch_weights_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int]),
         "sactd3_td_errors_device": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, C.c_int]),
         "sactd3_priority_stats": (C.c_int, [vp, i64p]),
+        "sactd3_prio_enable": (C.c_int, [vp, C.c_float, C.c_float]),
+        "sactd3_rb_sample_prioritized": (C.c_int, [vp, C.c_float]),
+        "sactd3_prio_set_uniforms": (C.c_int, [vp, fp, C.c_int]),
+        "sactd3_prio_update_from_td": (C.c_int, [vp]),
+        "sactd3_prio_update_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int]),
+        "sactd3_prio_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -309,9 +309,12 @@ class ReplayBuffer:
         first key access fills all of them with one launch); the default keeps the host read-back to numpy arrays."""
         self.capacity, self.device, self.device_batches = int(capacity), device, bool(device_batches)
         self._engine: Optional[Engine] = None
+        self._priorities: Optional[Dict[str, float]] = None      # enable_priorities' arguments, once it was called
 
     def _bind(self, engine: Engine):
         self._engine = engine
+        if self._priorities is not None:      # enabled before the agent existed: the engine learns it now
+            engine.prio_enable(**self._priorities)
 
     def _need(self) -> Engine:
         assert self._engine is not None, "replay buffer is not attached to an Agent yet"
@@ -354,6 +357,45 @@ class ReplayBuffer:
         del keep      # (the engine's read is ordered against the stream the allocator hands the block out on)
         eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1
         return BatchHandle(eng, eng._batch_generation, device=self.device_batches)
+
+    def enable_priorities(self, alpha: float = 0.6, eps: float = 1e-6) -> None:
+        """Proportional prioritised replay kept by the engine (include/sactd3.h: sactd3_prio_enable): one priority per ring slot in
+        device memory.  Rows already held enter at priority 1, every later extend() at the running maximum -- the engine sees its own
+        appends, there is no cursor to mirror.  Before the buffer is attached to an Agent the call is remembered and made then."""
+        if not (alpha >= 0.0 and eps > 0.0):
+            raise ValueError("enable_priorities: alpha >= 0 and eps > 0 required")
+        if self._engine is not None:
+            self._engine.prio_enable(alpha, eps)
+        self._priorities = dict(alpha=float(alpha), eps=float(eps))
+
+    def sample_prioritized(self, batch_size: int, beta: float) -> BatchHandle:
+        """sample() by priority (sactd3_rb_sample_prioritized): P(i) ~ p_i^alpha, with replacement, drawn, staged and weighted on the
+        device by three launches; the slot carries the importance weights (N P(i))^(-beta) over the batch's largest, so the critic
+        update on the returned handle is the weighted one.  The handle is a sample()'s in every other respect."""
+        if self._priorities is None:
+            raise RuntimeError("sample_prioritized: call enable_priorities() first")
+        eng = self._need()
+        assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
+        eng.rb_sample_prioritized(beta)
+        eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1
+        return BatchHandle(eng, eng._batch_generation, device=self.device_batches)
+
+    def update_priorities(self, index=None, priorities=None) -> None:
+        """The write-back.  No arguments: the rows of the batch slot get |TD error| (the larger of the twin critics') + eps of the
+        critic update that just ran on them (sactd3_prio_update_from_td).  Both arguments: ring slots (int64, as for rows()) and their
+        unscaled priorities (float32 [n] or [n, 1] on the engine's device), taken where they are (sactd3_prio_update_device)."""
+        if self._priorities is None:
+            raise RuntimeError("update_priorities: call enable_priorities() first")
+        if (index is None) != (priorities is None):
+            raise ValueError("update_priorities: pass both `index` and `priorities`, or neither")
+        eng = self._need()
+        if index is None:
+            eng.prio_update_from_td()
+            return
+        index, ptr, n, ld = _index_field(eng, index)
+        keep, p_ptr, p_ld = _weight_field(eng, priorities, n, "update_priorities")
+        eng.prio_update_device(ptr, ld, p_ptr, p_ld, n, _producer_stream(index, eng.cfg.device_id))
+        del keep
 
     def rows(self, index, out: Optional[Mapping[str, Any]] = None) -> Dict[str, Any]:
         """The ring records `index` names (ring slots: what `index` of a sample holds), as a dict of tensors on the engine's device

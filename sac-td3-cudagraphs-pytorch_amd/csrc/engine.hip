@@ -180,6 +180,19 @@ struct sactd3_engine {
   // value of sactd3_priority_stats is DevCtl::priority_refused.
   bool slot_weighted = false, td_valid = false;
   int64_t prio_stats[3] = {};
+  // Proportional prioritised replay as engine state (sactd3_prio_enable; device code and table layout: prio_kernels.h).  Everything
+  // below is made by sactd3_prio_enable -- an engine that never calls it holds nothing more and launches nothing more than before.
+  // pt_leaf [groups x 1024] = p^alpha per ring slot (0: not filled), pt_sums [ceil(groups / 1024) x 1024] the group sums, both
+  // zero-padded; pt_ctl the device words (maximum priority, draw counter, refused rows); pt_idx / pt_dleaf / pt_w / pt_total what a
+  // draw leaves for the staging launch; pt_u the injected uniforms (pt_inject: in use).  pt_host: {prioritised samples, write-backs,
+  // rows that entered at the maximum priority}; the rows refused on the device are PrioCtl::refused.
+  bool pt_on = false, pt_inject = false;
+  float pt_alpha = 0.f, pt_eps = 0.f;
+  int pt_groups = 0;
+  float *pt_leaf = nullptr, *pt_sums = nullptr, *pt_dleaf = nullptr, *pt_w = nullptr, *pt_total = nullptr, *pt_u = nullptr, *pt_ones = nullptr;
+  long long* pt_idx = nullptr;
+  struct PrioCtl* pt_ctl = nullptr;
+  int64_t pt_host[3] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -1329,6 +1342,11 @@ static int publish_rb_state(sactd3_engine* e) {
 static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld);
 static int launch_batch_weights(sactd3_engine* e, const float* w, int64_t w_ld);
 static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns);
+// ... and of the engine-owned priorities (prio_kernels.h; defined at the end of this file for the same reason).  prio_after_append:
+// rows [first, first + n) of the ring, wrapping at the capacity, have just been written -- nothing is launched while priorities are off.
+static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n);
+static int64_t prio_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats);
+static int prio_time_body(sactd3_engine* e, const char* kernel);
 
 // ------------------------------------------------------------------------------------------------ C ABI
 #pragma GCC visibility push(default)
@@ -1649,6 +1667,7 @@ int sactd3_rb_extend(sactd3_engine* e, const float* obs, const float* act, const
     const int blocks = (int)std::min<long>(256, ((long)chunk * e->rec4 + 255) / 256);
     hipLaunchKernelGGL(k_rb_ingest, dim3(std::max(blocks, 1)), dim3(256), 0, e->stream, g);
     HIPCHK(hipGetLastError());
+    RCCHK(prio_after_append(e, g.cursor, chunk));
     done_rows += chunk;
   }
   return 0;
@@ -1684,6 +1703,7 @@ int sactd3_rb_extend_device(sactd3_engine* e, const float* records, int n) {
     const int blocks = (int)std::min<long>(1024, ((long)chunk * e->rec4 + 255) / 256);
     hipLaunchKernelGGL(k_rb_ingest, dim3(std::max(blocks, 1)), dim3(256), 0, e->stream, g);
     HIPCHK(hipGetLastError());
+    RCCHK(prio_after_append(e, g.cursor, chunk));
     done_rows += chunk;
   }
   return 0;
@@ -1795,7 +1815,7 @@ static int launch_ingest_fields(sactd3_engine* e, const FieldSrc& src, int chunk
   const long chunks = (long)chunk * e->rec4;
   hipLaunchKernelGGL(k_rb_ingest_fields, dim3((unsigned)((chunks + 256L * FIELDS_CPT - 1) / (256L * FIELDS_CPT))), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
   HIPCHK(hipGetLastError());
-  return 0;
+  return prio_after_append(e, g.cursor, chunk);
 }
 static int launch_batch_fields(sactd3_engine* e, const FieldSrc& src) {
   const sactd3_engine::BatchSlot& S = e->bs[0];
@@ -2091,7 +2111,8 @@ int sactd3_rb_fill_synthetic(sactd3_engine* e, int64_t n, uint64_t seed) {
   HIPCHK(hipGetLastError());
   e->rb_len = std::max<int64_t>(e->rb_len, n);
   e->rb_cursor = n % e->cfg.rb_capacity;
-  return publish_rb_state(e);
+  RCCHK(publish_rb_state(e));
+  return prio_after_append(e, 0, n);
 }
 
 // ---- noise
@@ -2698,7 +2719,7 @@ static std::vector<DbgEntry> dbg_table(sactd3_engine* e) {
 }
 const char* sactd3_debug_names(void) {
   return "X Xn Xp rew done logp_next logp_pi logp_alpha a_xh1 a_h1 a_z2 a_h2 a_du a_dz2 a_dh1 a_dz1 c_xh1 c_h1 c_z2 c_dz2 c_dh1 c_dz1 "
-         "t_z2 q q_target targ_q q_pi dA grad_actor grad_critics";
+         "t_z2 q q_target targ_q q_pi dA grad_actor grad_critics prio_leaf prio_sums prio_max prio_weights";
 }
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
   if (!e || !name) return SACTD3_EINVAL;
@@ -2713,6 +2734,7 @@ int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_
     RCCHK(read_arena(e, act ? e->Ga : e->Gc, act ? e->La : e->Lc, act ? 1 : 2, dst));
     return n;
   }
+  if (!strncmp(name, "prio_", 5)) return prio_debug_read(e, name, dst, max_floats);
   for (const DbgEntry& d : dbg_table(e)) {
     if (strcmp(d.name, name)) continue;
     if (!dst) return d.n;
@@ -2807,9 +2829,13 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
     // weights, into batch slot 0 (overwritten); the TD errors of whatever e->q / e->y hold, written into the engine's own staging slab
     if (!strcmp(kernel, "batch_from_index")) { RCCHK(slot_weights_alloc(e)); SLOT_REFILL(e); e->cur_slot = 0; return launch_batch_index(e, e->time_idx, 1, nullptr, 1); }
     if (!strcmp(kernel, "td_to_field")) return launch_td_out(e, e->stage_dev, 1, e->B);
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field)");
+    // the engine-owned priorities (SACTD3_ESTATE before sactd3_prio_enable): one whole sactd3_rb_sample_prioritized (beta 0.4: three
+    // launches, batch slot 0 overwritten, the draw counter advanced) / the write-back kernel on batch_size rows, indices as for
+    // "rows_to_fields", every priority 1 (those rows' priorities ARE overwritten)
+    if (!strcmp(kernel, "prio_sample") || !strcmp(kernel, "prio_update")) return prio_time_body(e, kernel);
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update)");
   };
-  if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index")) rc = time_rows_indices(e);
+  if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index") || !strcmp(kernel, "prio_update")) rc = time_rows_indices(e);
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up
   if (rc == 0) {
     hipEventRecord(t0, e->stream);
@@ -2997,3 +3023,186 @@ static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_
   HIPCHK(hipGetLastError());
   return 0;
 }
+
+// ---- proportional prioritised replay as engine state (include/sactd3.h: sactd3_prio_*, sactd3_rb_sample_prioritized).  Kernels, launches
+// and entry points all stand here, behind everything that existed before (see launch_ctail_nn_w).
+#include "prio_kernels.h"
+
+static int prio_refresh(sactd3_engine* e, int64_t first, int64_t n) {
+  const int64_t cap = e->cfg.rb_capacity;
+  PrioRefreshArgs g{};
+  g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.pc = e->pt_ctl; g.alpha = e->pt_alpha;
+  if (n >= cap) { first = 0; n = cap; }
+  g.lo0 = (int)first; g.hi0 = (int)std::min(first + n, cap);
+  g.lo1 = 0; g.hi1 = (int)std::max<int64_t>(first + n - cap, 0);
+  g.g0 = g.lo0 / PRIO_G; g.n0 = (g.hi0 - 1) / PRIO_G - g.g0 + 1;
+  g.g1 = 0;
+  const int n1 = g.hi1 > 0 ? (g.hi1 - 1) / PRIO_G + 1 : 0;
+  hipLaunchKernelGGL(k_prio_refresh, dim3((unsigned)(g.n0 + n1)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  e->pt_host[2] += n;
+  return 0;
+}
+static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n) {
+  return (e->pt_on && n > 0) ? prio_refresh(e, first, n) : 0;
+}
+// the three launches of a prioritised sample: draw, weights (+ counter tick), staging
+static int prio_sample_launches(sactd3_engine* e, float beta) {
+  PrioDrawArgs d{};
+  d.leaf4 = (const float4*)e->pt_leaf; d.sums4 = (const float4*)e->pt_sums;
+  d.ngroups = e->pt_groups; d.nch = (e->pt_groups + PRIO_G - 1) / PRIO_G; d.len = (int)e->rb_len;
+  d.u_inj = e->pt_inject ? e->pt_u : nullptr; d.ctl = e->ctl; d.pc = e->pt_ctl;
+  d.idx_out = e->pt_idx; d.leaf_out = e->pt_dleaf; d.total_out = e->pt_total;
+  hipLaunchKernelGGL(k_prio_draw, dim3((unsigned)e->B), dim3(256), 0, e->stream, d);
+  HIPCHK(hipGetLastError());
+  const PrioWeightArgs w{e->pt_idx, e->pt_dleaf, e->pt_total, e->pt_w, e->B, (float)e->rb_len, beta, e->pt_inject ? nullptr : &e->pt_ctl->draw_ctr};
+  hipLaunchKernelGGL(k_prio_weights, dim3(1), dim3(256), 0, e->stream, w);
+  HIPCHK(hipGetLastError());
+  return launch_batch_index(e, e->pt_idx, 1, e->pt_w, 1);
+}
+static int launch_prio_update(sactd3_engine* e, PrioUpdateArgs g) {
+  g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.len = (int)e->rb_len; g.alpha = e->pt_alpha; g.eps = e->pt_eps; g.pc = e->pt_ctl;
+  hipLaunchKernelGGL(k_prio_update, dim3((unsigned)g.n), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int prio_time_body(sactd3_engine* e, const char* kernel) {
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "time_kernel: priorities are not enabled");
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_kernel: buffer is empty");
+  if (!strcmp(kernel, "prio_sample")) {
+    SLOT_REFILL(e);
+    e->cur_slot = 0;
+    RCCHK(prio_sample_launches(e, 0.4f));
+    e->slot_weighted = true;
+    return 0;
+  }
+  if (!e->pt_ones) {
+    RCCHK(dalloc(e, &e->pt_ones, (size_t)e->B, false));
+    const std::vector<float> one((size_t)e->B, 1.f);
+    HIPCHK(hipMemcpy(e->pt_ones, one.data(), sizeof(float) * one.size(), hipMemcpyHostToDevice));
+  }
+  PrioUpdateArgs g{};
+  g.n = e->B; g.idx = e->time_idx; g.idx_ld = 1; g.prio = e->pt_ones; g.prio_ld = 1;
+  return launch_prio_update(e, g);
+}
+static int64_t prio_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
+  const float* src = nullptr; int64_t n = 0;
+  if (e->pt_on && !strcmp(name, "prio_leaf")) { src = e->pt_leaf; n = e->cfg.rb_capacity; }
+  else if (e->pt_on && !strcmp(name, "prio_sums")) { src = e->pt_sums; n = e->pt_groups; }      // (the one level above the leaves)
+  else if (e->pt_on && !strcmp(name, "prio_max")) { src = &e->pt_ctl->max_prio; n = 1; }
+  else if (e->pt_on && !strcmp(name, "prio_weights")) { src = e->bs[0].w; n = e->B; }           // (the loss weights batch slot 0 carries)
+  else if (!strcmp(name, "prio_leaf") || !strcmp(name, "prio_sums") || !strcmp(name, "prio_max") || !strcmp(name, "prio_weights")) return e->fail(SACTD3_ESTATE, "debug_read: priorities are not enabled");
+  else return e->fail(SACTD3_EINVAL, "debug_read: unknown buffer name");
+  if (!dst) return n;
+  if (max_floats < n) return e->fail(SACTD3_EINVAL, "debug_read: buffer too small");
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost));
+  return n;
+}
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+// One leaf per ring slot plus the group sums, built for the rows the ring holds now (priority 1 = the starting maximum).
+int sactd3_prio_enable(sactd3_engine* e, float alpha, float eps) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!(alpha >= 0.f) || !std::isfinite(alpha)) return e->fail(SACTD3_EINVAL, "prio_enable: alpha must be finite and >= 0");
+  if (!(eps > 0.f) || !std::isfinite(eps)) return e->fail(SACTD3_EINVAL, "prio_enable: eps must be finite and > 0");
+  if (e->pt_on) return (alpha == e->pt_alpha && eps == e->pt_eps) ? 0 : e->fail(SACTD3_ESTATE, "prio_enable: already enabled with other values");
+  const int64_t groups = ((int64_t)e->cfg.rb_capacity + PRIO_G - 1) / PRIO_G, chunks = (groups + PRIO_G - 1) / PRIO_G;
+  if (!e->pt_leaf) {      // (a call that failed half way keeps what it had made)
+    RCCHK(dalloc(e, &e->pt_leaf, (size_t)groups * PRIO_G)); RCCHK(dalloc(e, &e->pt_sums, (size_t)chunks * PRIO_G));
+    RCCHK(dalloc(e, &e->pt_ctl, 1));
+    RCCHK(dalloc(e, &e->pt_idx, (size_t)e->B)); RCCHK(dalloc(e, &e->pt_dleaf, (size_t)e->B)); RCCHK(dalloc(e, &e->pt_w, (size_t)e->B));
+    RCCHK(dalloc(e, &e->pt_total, 4)); RCCHK(dalloc(e, &e->pt_u, (size_t)e->B));
+  }
+  RCCHK(slot_weights_alloc(e));
+  PrioCtl h{};
+  h.max_prio = 1.f;
+  HIPCHK(hipMemcpy(e->pt_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
+  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
+  e->pt_groups = (int)groups; e->pt_alpha = alpha; e->pt_eps = eps; e->pt_on = true;
+  return prio_after_append(e, 0, e->rb_len);
+}
+
+// rb.sample by priority: three launches on the learner stream (k_prio_draw, k_prio_weights, k_batch_from_index), no copy command, no
+// host wait.  The uniform sampler's counter is not touched.
+int sactd3_rb_sample_prioritized(sactd3_engine* e, float beta) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!(beta >= 0.f) || !std::isfinite(beta)) return e->fail(SACTD3_EINVAL, "rb_sample_prioritized: beta must be finite and >= 0");
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "rb_sample_prioritized: priorities are not enabled (sactd3_prio_enable)");
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_prioritized: buffer is empty");
+  CHAIN_BREAK(e);
+  SLOT_REFILL(e);
+  e->cur_slot = 0;
+  RCCHK(prio_sample_launches(e, beta));
+  e->slot_weighted = true;
+  ++e->pt_host[0];
+  return 0;
+}
+
+int sactd3_prio_set_uniforms(sactd3_engine* e, const float* u, int n) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_set_uniforms: priorities are not enabled (sactd3_prio_enable)");
+  if (!u) { e->pt_inject = false; return 0; }
+  if (n != e->B) return e->fail(SACTD3_EINVAL, "prio_set_uniforms: n must equal batch_size");
+  std::vector<float> h((size_t)n);
+  for (int i = 0; i < n; ++i) h[i] = u[i] >= 0.f ? std::min(u[i], 0x1.fffffep-1f) : 0.f;      // into [0, 1); NaN -> 0
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(e->pt_u, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
+  e->pt_inject = true;
+  return 0;
+}
+
+// The write-back from the critic update that just ran on the batch slot: one k_prio_update launch.  It reads e->q / e->y and the slot's
+// ring indices and writes the priority table only: no CHAIN_BREAK, a precomputed opening pair of sactd3_step_period stays valid.
+int sactd3_prio_update_from_td(sactd3_engine* e) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_from_td: priorities are not enabled (sactd3_prio_enable)");
+  if (!e->td_valid) return e->fail(SACTD3_ESTATE, "prio_update_from_td: no critic update has run on the rows now in the batch slot");
+  PrioUpdateArgs g{};
+  g.n = e->B; g.slot_idx = e->bs[e->cur_slot].idx; g.q = e->q; g.y = e->y; g.B = e->B;
+  RCCHK(launch_prio_update(e, g));
+  ++e->pt_host[1];
+  return 0;
+}
+
+int sactd3_prio_update_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* prio, int64_t prio_ld, int n,
+                              void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!idx || !prio) return e->fail(SACTD3_EINVAL, "prio_update_device: `idx` or `prio` is NULL");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "prio_update_device: unknown flag");
+  if (n < 1) return e->fail(SACTD3_EINVAL, "prio_update_device: n must be at least 1");
+  if (idx_ld < 1 || prio_ld < 1) return e->fail(SACTD3_EINVAL, "prio_update_device: a row stride is below 1");
+  RCCHK(device_ptr_check(e, idx, "prio_update_device", "idx"));
+  RCCHK(device_ptr_check(e, prio, "prio_update_device", "prio"));
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_device: priorities are not enabled (sactd3_prio_enable)");
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  PrioUpdateArgs g{};
+  g.n = n; g.idx = (const long long*)idx; g.idx_ld = (long)idx_ld; g.prio = prio; g.prio_ld = (long)prio_ld;
+  RCCHK(launch_prio_update(e, g));
+  RCCHK(src_order_end(e, caller, flags));
+  ++e->pt_host[1];
+  return 0;
+}
+
+int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int refused = 0;
+  if (e->pt_on) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(&refused, &e->pt_ctl->refused, sizeof(int), hipMemcpyDeviceToHost));
+  }
+  out[0] = e->pt_host[0]; out[1] = e->pt_host[1]; out[2] = refused; out[3] = e->pt_host[2];
+  return 0;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

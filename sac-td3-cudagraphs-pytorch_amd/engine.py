@@ -466,6 +466,41 @@ class Engine:
         self._ck(self.lib.sactd3_priority_stats(self._h, out))
         return dict(index_stagings=int(out[0]), weight_stagings=int(out[1]), td_readouts=int(out[2]), rows_refused=int(out[3]))
 
+    # -- prioritised replay the engine owns (include/sactd3.h: sactd3_prio_*)
+    def prio_enable(self, alpha: float = 0.6, eps: float = 1e-6) -> None:
+        """sactd3_prio_enable: one priority per ring slot and their group sums, in device memory; rows already held enter at priority
+        1, every later append at the running maximum."""
+        self._ck(self.lib.sactd3_prio_enable(self._h, float(alpha), float(eps)))
+
+    def rb_sample_prioritized(self, beta: float) -> None:
+        """sactd3_rb_sample_prioritized: the batch slot filled by priority (three launches, no host wait), with the importance
+        weights (N p_i^alpha / T)^(-beta) over the batch's largest as the slot's loss weights."""
+        self._ck(self.lib.sactd3_rb_sample_prioritized(self._h, float(beta)))
+
+    def prio_set_uniforms(self, u=None) -> None:
+        """sactd3_prio_set_uniforms: batch_size uniforms in [0, 1) to draw with instead of the Philox stream (sticky); None: native."""
+        if u is None:
+            self._ck(self.lib.sactd3_prio_set_uniforms(self._h, None, 0))
+            return
+        u = np.ascontiguousarray(np.asarray(u, dtype=np.float32).reshape(-1))
+        self._ck(self.lib.sactd3_prio_set_uniforms(self._h, _fp(u), int(u.size)))
+
+    def prio_update_from_td(self) -> None:
+        """sactd3_prio_update_from_td: the batch rows' priorities from the TD errors of the critic update that just ran on them."""
+        self._ck(self.lib.sactd3_prio_update_from_td(self._h))
+
+    def prio_update_device(self, idx_ptr: int, idx_ld: int, prio_ptr: int, prio_ld: int, n: int, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_prio_update_device: unscaled priorities (device float32 at `prio_ptr`, stride `prio_ld`) for the ring slots a device
+        int64 array names; a bad index or priority is refused on the device and counted in prio_stats()["rows_refused"]."""
+        self._ck(self.lib.sactd3_prio_update_device(self._h, C.c_void_p(int(idx_ptr) or None), int(idx_ld), C.c_void_p(int(prio_ptr) or None),
+                                                    int(prio_ld), int(n), C.c_void_p(int(stream) or None), _lib.SRC_ORDERED if ordered else 0))
+
+    def prio_stats(self) -> Dict[str, int]:
+        """counters of the engine-owned priorities (sactd3_prio_stats; waits for the engine's stream)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.sactd3_prio_stats(self._h, out))
+        return dict(samples=int(out[0]), write_backs=int(out[1]), rows_refused=int(out[2]), rows_entered_at_max=int(out[3]))
+
     def acting_stats(self) -> Dict[str, int]:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
         out = (C.c_int64 * 4)()

@@ -203,7 +203,7 @@ def job_config(algo: str, env_id: str, seed: int, **over):
 
 
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
-            device_env: bool = False, **over):
+            device_env: bool = False, prioritized: bool = False, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU."""
     import json
     import time
@@ -229,7 +229,9 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
     t0 = time.time()
-    metrics = loop.train(cfg, env, agent, fused=True, evaluator=ev, overlap=overlap_acting, device_env=device_env)
+    # --prioritized: the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4), call by call
+    metrics = loop.train(cfg, env, agent, fused=not prioritized, evaluator=ev, overlap=overlap_acting, device_env=device_env,
+                         prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -257,7 +259,7 @@ def _worker_main(args) -> int:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
                           eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity,
-                          overlap_acting=args.overlap_acting, device_env=args.device_env)
+                          overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -287,6 +289,8 @@ def main(argv=None) -> int:
                     help="compute the next action on the engine's acting stream while the iteration's update runs (loop.train overlap=True)")
     ap.add_argument("--device_env", action="store_true",
                     help="train on the GPU-resident synthetic vector env: observations and actions never leave the device (loop.train device_env=True)")
+    ap.add_argument("--prioritized", action="store_true",
+                    help="proportional prioritised replay kept by the engine (loop.train prioritized=...; the iteration is issued call by call)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)

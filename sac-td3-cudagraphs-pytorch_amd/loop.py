@@ -194,7 +194,7 @@ class ProportionalSampler:
 
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
           evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
-          sampler: Optional[ProportionalSampler] = None) -> Dict[str, float]:
+          sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -206,9 +206,22 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     -- `agent.predict_device`, no host round trip per env step.  It acts on the learner stream, so it excludes `overlap`.
     `sampler` (a ProportionalSampler; needs `fused=False`: the fused iteration owns its uniform sampler): prioritised replay, call
     by call on the device -- the sampler's rows and importance weights through `rb.sample_at`, the critic update weighted by them,
-    its TD errors (`agent.td_errors`) back into the sampler's priorities; the actor updates train on the same rows, unweighted."""
+    its TD errors (`agent.td_errors`) back into the sampler's priorities; the actor updates train on the same rows, unweighted.
+    `prioritized` (dict(alpha=, beta=, eps=), any subset; needs `fused=False`, excludes `sampler`): the same iteration with the
+    priorities kept by the ENGINE -- `rb.sample_prioritized` -> weighted critic update -> `rb.update_priorities()` -- with no torch
+    arithmetic in between and nothing to mirror on the host: the engine sees its own appends."""
     if sampler is not None and fused:
         raise ValueError("sampler=... needs fused=False: the fused iteration samples uniformly inside its graph")
+    if prioritized is not None:
+        if fused:
+            raise ValueError("prioritized=... needs fused=False: the fused iteration samples uniformly inside its graph")
+        if sampler is not None:
+            raise ValueError("prioritized=... and sampler=... exclude each other: one owner for the priorities")
+        unknown = set(prioritized) - {"alpha", "beta", "eps"}
+        if unknown:
+            raise ValueError(f"prioritized: unknown keys {sorted(unknown)}")
+        prio_beta = float(prioritized.get("beta", 0.4))
+        agent.rb.enable_priorities(alpha=float(prioritized.get("alpha", 0.6)), eps=float(prioritized.get("eps", 1e-6)))
     if overlap and device_env:
         raise ValueError("overlap=True and device_env=True exclude each other: predict_device acts on the learner stream")
     ro = Rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat, overlap=True) if overlap else None
@@ -230,7 +243,9 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
         if fused:
             agent.iteration(i)
         else:
-            if sampler is None:
+            if prioritized is not None:
+                batch = agent.rb.sample_prioritized(cfg.batch_size, prio_beta)
+            elif sampler is None:
                 batch = agent.rb.sample(cfg.batch_size)
             else:
                 index, weights = sampler.sample(cfg.batch_size)
@@ -238,6 +253,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
             tlog.update(agent.update_qnets(batch))
             if sampler is not None:
                 sampler.update(index, agent.td_errors())
+            if prioritized is not None:
+                agent.rb.update_priorities()
             agent.qnet_updates_so_far += 1
             if i % (cfg.actor_update_delay + 1) == 0:
                 for _ in range(cfg.actor_update_delay):
