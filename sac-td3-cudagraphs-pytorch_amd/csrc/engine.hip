@@ -307,16 +307,16 @@ static GatherArgs gather_args(sactd3_engine* e, const float* ring, int identity_
 }
 template <int PRO, bool F1, int C1>
 static void launch_nt_ks(hipStream_t s, int ks, dim3 grid, const NtArgs& g) {      // ks = 2 or 4
-  if (ks == 4) hipLaunchKernelGGL((k_nt<PRO, F1, 4, C1>), grid, dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((k_nt<PRO, F1, 2, C1>), grid, dim3(256), 0, s, g);
+  if (ks == 4) launch_k_nt(k_nt<PRO, F1, 4, C1>, grid, s, g);
+  else launch_k_nt(k_nt<PRO, F1, 2, C1>, grid, s, g);
 }
 template <int PRO>
 static void launch_nt_f1(hipStream_t s, int ks, int nt, dim3 grid, const NtArgs& g) {
   const int c1 = (g.K1 + 15) / 16;
   if (nt == 2) {   // (KS == 2 only) two column tiles per block
-    if (c1 <= 1) hipLaunchKernelGGL((k_nt<PRO, true, 2, 1, 2>), grid, dim3(256), 0, s, g);
-    else if (c1 == 2) hipLaunchKernelGGL((k_nt<PRO, true, 2, 2, 2>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((k_nt<PRO, true, 2, 4, 2>), grid, dim3(256), 0, s, g);
+    if (c1 <= 1) launch_k_nt(k_nt<PRO, true, 2, 1, 2>, grid, s, g);
+    else if (c1 == 2) launch_k_nt(k_nt<PRO, true, 2, 2, 2>, grid, s, g);
+    else launch_k_nt(k_nt<PRO, true, 2, 4, 2>, grid, s, g);
     return;
   }
   if (c1 <= 1) launch_nt_ks<PRO, true, 1>(s, ks, grid, g);
@@ -326,13 +326,13 @@ static void launch_nt_f1(hipStream_t s, int ks, int nt, dim3 grid, const NtArgs&
 static void launch_nt_c4(hipStream_t s, int nt, dim3 grid, const NtArgs& g) {      // (LayerNorm form, fused first layer, KS = 2 with KS = 4's sums)
   const int c1 = (g.K1 + 15) / 16;
   if (nt == 2) {
-    if (c1 <= 1) hipLaunchKernelGGL((k_nt<1, true, 2, 1, 2, true>), grid, dim3(256), 0, s, g);
-    else if (c1 == 2) hipLaunchKernelGGL((k_nt<1, true, 2, 2, 2, true>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((k_nt<1, true, 2, 4, 2, true>), grid, dim3(256), 0, s, g);
+    if (c1 <= 1) launch_k_nt(k_nt<1, true, 2, 1, 2, true>, grid, s, g);
+    else if (c1 == 2) launch_k_nt(k_nt<1, true, 2, 2, 2, true>, grid, s, g);
+    else launch_k_nt(k_nt<1, true, 2, 4, 2, true>, grid, s, g);
   } else {
-    if (c1 <= 1) hipLaunchKernelGGL((k_nt<1, true, 2, 1, 1, true>), grid, dim3(256), 0, s, g);
-    else if (c1 == 2) hipLaunchKernelGGL((k_nt<1, true, 2, 2, 1, true>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((k_nt<1, true, 2, 4, 1, true>), grid, dim3(256), 0, s, g);
+    if (c1 <= 1) launch_k_nt(k_nt<1, true, 2, 1, 1, true>, grid, s, g);
+    else if (c1 == 2) launch_k_nt(k_nt<1, true, 2, 2, 1, true>, grid, s, g);
+    else launch_k_nt(k_nt<1, true, 2, 4, 1, true>, grid, s, g);
   }
 }
 // XCD row groups for xcd_tile (kernels.h) of an R x C tile grid whose row operand is A bytes and column operand W bytes: the
@@ -381,6 +381,7 @@ static int launch_nt(EnqCtx& x, const char* name, int pro, bool fuse1, const NtA
     if (c4 && nt == 2 && ((g.M + rb - 1) / rb) * (tiles_n / 2) * nets > e->num_cus) nt = 1;
     NtArgs gg = g;
     gg.nt_blocks = ((g.M + rb - 1) / rb) * (tiles_n / nt);
+    if (!gg.ga[0].ctl) gg.ga[0].ctl = e->ctl;      // (the launch header hands it to every block: k_nt reads the ring's control words through it before it knows its group)
     // unfused launches read whole input rows: place the tiles so that an XCD pulls few rows and few weight columns (the fused
     // form's input rows are a few dozen bytes: it keeps one weight column tile per XCD, the row-major numbering)
     gg.xr = fuse1 ? 0 : pick_xr((g.M + rb - 1) / rb, tiles_n / nt, 4.0 * g.M * g.K, 4.0 * g.N * g.K);
@@ -402,8 +403,8 @@ static int launch_nt(EnqCtx& x, const char* name, int pro, bool fuse1, const NtA
     if (c4) launch_nt_c4(s, nt, grid, gg);
     else if (fuse1) { if (pro == 1) launch_nt_f1<1>(s, ks, nt, grid, gg); else launch_nt_f1<2>(s, ks, nt, grid, gg); }
     else if (nt == 2) {   // (KS == 2) the A rows are fetched and normalised by half as many blocks
-      if (pro == 1) hipLaunchKernelGGL((k_nt<1, false, 2, 0, 2>), grid, dim3(256), 0, s, gg);
-      else hipLaunchKernelGGL((k_nt<2, false, 2, 0, 2>), grid, dim3(256), 0, s, gg);
+      if (pro == 1) launch_k_nt(k_nt<1, false, 2, 0, 2>, grid, s, gg);
+      else launch_k_nt(k_nt<2, false, 2, 0, 2>, grid, s, gg);
     } else { if (pro == 1) launch_nt_ks<1, false, 0>(s, ks, grid, gg); else launch_nt_ks<2, false, 0>(s, ks, grid, gg); }
   }
   HIPCHK(hipGetLastError());
@@ -547,15 +548,15 @@ static int launch_tn(EnqCtx& x, const char* name, TnArgs& g, int nets, int tick_
   if (!node_on(x, inst, fl, by, grid, dim3(256))) return 0;
   if (g.keep_g) {
     if (fold) {
-      if (kt == 2) hipLaunchKernelGGL((k_tn<2, true>), grid, dim3(256), 0, s, g);
-      else hipLaunchKernelGGL((k_tn<1, true>), grid, dim3(256), 0, s, g);
-    } else if (kt == 2) hipLaunchKernelGGL(k_tn<2>, grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL(k_tn<1>, grid, dim3(256), 0, s, g);
+      if (kt == 2) launch_k_tn<2, true, true>(grid, s, g);
+      else launch_k_tn<1, true, true>(grid, s, g);
+    } else if (kt == 2) launch_k_tn<2, false, true>(grid, s, g);
+    else launch_k_tn<1, false, true>(grid, s, g);
   } else if (fold) {      // the instances without the gradient-arena stores (TnArgs::keep_g)
-    if (kt == 2) hipLaunchKernelGGL((k_tn<2, true, false>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((k_tn<1, true, false>), grid, dim3(256), 0, s, g);
-  } else if (kt == 2) hipLaunchKernelGGL((k_tn<2, false, false>), grid, dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((k_tn<1, false, false>), grid, dim3(256), 0, s, g);
+    if (kt == 2) launch_k_tn<2, true, false>(grid, s, g);
+    else launch_k_tn<1, true, false>(grid, s, g);
+  } else if (kt == 2) launch_k_tn<2, false, false>(grid, s, g);
+  else launch_k_tn<1, false, false>(grid, s, g);
   HIPCHK(hipGetLastError());
   return 0;
 }

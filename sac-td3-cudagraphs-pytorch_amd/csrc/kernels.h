@@ -177,6 +177,10 @@ __device__ __forceinline__ void tick_all(int* t0, int* t1, double* pw, float* ou
 // Make a loaded value materialise HERE: without it the compiler sinks an early load into the (divergent) epilogue
 // branch that uses it, and every conditional store there then drains the memory queue (s_waitcnt vmcnt(0)) in turn.
 #define PIN(x) asm volatile("" : "+v"(x))
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }      // block-uniform values, said so
+__device__ __forceinline__ long uni(long v) { return (long)(((unsigned long)(unsigned)uni((int)((unsigned long)v >> 32)) << 32) | (unsigned)uni((int)v)); }
+#define PIN_S(x) asm volatile("" : "+s"(x))    /* the same for a block-uniform value: it is in its SGPR HERE (its scalar load cannot be sunk past this point) */
+
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
@@ -211,6 +215,19 @@ __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<floa
 constexpr bool WT_ACT1 = (SACTD3_WT & 1) != 0;   // k_nt: first-layer activations kept for the backward pass (h1, xhat1)
 constexpr bool WT_Z2 = (SACTD3_WT & 2) != 0;     // k_nt: the trunk output z2 (read next by row / tail kernels with another block -> row map)
 constexpr bool WT_DZ = (SACTD3_WT & 4) != 0;     // k_ctail_nn / k_headbwd_nn: dz2 (read next by k_tn, an all-to-all)
+// ---- launch headers.  A block's first scalar loads -- the words that decide its role and pick its descriptor --
+// are dependent rounds in front of the first operand request.  The families below take those words a second time as leading scalar
+// parameters ("header") in front of their argument struct; the library is built with kernel-argument preloading, so the packet
+// processor delivers the header in user SGPRs and the decisions need no load.  SACTD3_HDR is a build-time mask of the families that
+// READ their header (make HDR=<mask>, one bit per family, for A/B builds); with a bit off the kernel has the same parameters and
+// takes the decisions from the struct.  The host builds a header from the struct it launches with (launch_k_tn, launch_k_nt below the kernels).
+#ifndef SACTD3_HDR
+#define SACTD3_HDR 3
+#endif
+constexpr bool HDR_TN = (SACTD3_HDR & 1) != 0;   // k_tn<KT,FOLD,KEEP_G>: tiles, pk_blocks, fin_blocks, nprob, pr[1..3].tile0, M
+constexpr int HDR_TN_DWORDS = 8;
+constexpr bool HDR_NT = (SACTD3_HDR & 2) != 0;   // k_nt<...>: flat, flat_r, flat_n, nt_blocks, "has riders", npg, M, N, the ring's control block
+constexpr int HDR_NT_DWORDS = 10;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st4_wt(float* base, long off, float4 v) {      // base[off .. off + 3], base block-uniform, 4 off < 2^31
   const u32x4 u = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
@@ -944,8 +961,9 @@ struct NtGrp {               // one group of nets sharing an input and a paramet
   // ring != 0: the input rows of this group are read straight from the replay ring -- row m = the record drawn for batch row m with
   // stream counter sample_ctr + sctr_add (0: this iteration's sample; > 0: a later iteration's, whose next-action pass runs ahead),
   // field at float offset ring_off; ring_idx = where the (injected) indices of that sample live
-  int ring; int ring_off; int sctr_add; const int* ring_idx;
+  int ring; int ring_off; int sctr_add; int pad_; const int* ring_idx;      // (pad_: the alignment hole, named so that k_nt can pin the whole descriptor)
 };
+static_assert(sizeof(NtGrp) == 72, "NtGrp layout");
 struct NtArgs {              // Y[M,N] = pro(A)[M,K] * W[N,K]^T + bias ; block = one 16 x 16 output tile, K split over the 4 waves
   NtGrp g[5]; int npg;                      // blockIdx.z = grp * npg + net-in-group
   int ld_in; long in_ns;
@@ -1028,7 +1046,8 @@ __device__ __forceinline__ void riding_gather(const NtArgs& p, int x) {
 // launch of the same rows.  The run-ahead launches of a period graph (up to 5 groups: 1 280 blocks of 16 rows, each fetching the
 // whole of W1 and a W2 tile) use it: they must reproduce, bit for bit, what the single-net KS = 4 launches of those passes compute.
 template <int PRO, bool FUSE1, int KS, int C1, int NT = 1, bool C4 = false>      // C1 = 16-wide k chunks of the fused first layer (1, 2 or 4)
-__global__ __launch_bounds__(256) void k_nt(NtArgs p) {
+__global__ __launch_bounds__(256) void k_nt(int h_flat, int h_flat_r, int h_flat_n, int h_nt_blocks, int h_riders, int h_npg, int h_M, int h_N,
+                                            const DevCtl* h_ctl, NtArgs p) {
   static_assert(!C4 || (KS == 2 && PRO == 1), "C4: the KS = 2 LayerNorm form only");
   constexpr int RB = 64 / KS, CW = 16 / KS, NP = C4 ? 16 : 4 * KS, SS = 2 * NP + 4;   // rows/block, k chunks/wave, stat partials/row
   constexpr int W1S = 16 * (C1 > 0 ? C1 : 1) + 4;                           // LDS row stride of W1 (K1 <= 16 C1)
@@ -1045,13 +1064,18 @@ __global__ __launch_bounds__(256) void k_nt(NtArgs p) {
   BLK_MARK_K(1, 0);
   int bx = blockIdx.x, net = blockIdx.z;                      // tile block within the net / net (3-D grid)
   bool rider_net0 = blockIdx.z == 0;
-  if (p.flat) {                                               // 1-D grid: flat_r rider slots, then flat x nt_blocks tile blocks
+  // role, net and group from the launch header (HDR_NT): no load in front of the group's own batch
+  const int flat = HDR_NT ? h_flat : p.flat, flat_r = HDR_NT ? h_flat_r : p.flat_r, flat_n = HDR_NT ? h_flat_n : p.flat_n;
+  const int nt_blocks = HDR_NT ? h_nt_blocks : p.nt_blocks, npg = HDR_NT ? h_npg : p.npg, M = HDR_NT ? h_M : p.M, N = HDR_NT ? h_N : p.N;
+  const bool riders = HDR_NT ? h_riders != 0 : (p.gblocks || p.alpha_block || p.nz_n);
+  const DevCtl* ctl = HDR_NT ? h_ctl : p.ga[0].ctl;
+  if (flat) {                                                 // 1-D grid: flat_r rider slots, then flat x nt_blocks tile blocks
     rider_net0 = true;
-    if (bx < p.flat_r) { if (bx >= p.flat_n) return; bx += p.nt_blocks; net = 0; }      // (padding slots exit)
-    else { bx -= p.flat_r; net = small_div(bx, p.nt_blocks); bx -= net * p.nt_blocks; }
+    if (bx < flat_r) { if (bx >= flat_n) return; bx += nt_blocks; net = 0; }      // (padding slots exit)
+    else { bx -= flat_r; net = small_div(bx, nt_blocks); bx -= net * nt_blocks; }
   }
-  if ((p.gblocks || p.alpha_block || p.nz_n) && bx >= p.nt_blocks) {   // block-uniform: replay gather / temperature step / noise
-    const int x = bx - p.nt_blocks;
+  if (riders && bx >= nt_blocks) {                            // block-uniform: replay gather / temperature step / noise
+    const int x = bx - nt_blocks;
     if (x < p.gblocks) { if (rider_net0) riding_gather(p, x); }
     else if (!rider_net0) { }
     else riding_body(p, x - p.gblocks);
@@ -1065,57 +1089,86 @@ __global__ __launch_bounds__(256) void k_nt(NtArgs p) {
     if (t == 0 && (p.tick0 || p.tick1)) tick_all(p.tick0, p.tick1, p.adam_pw, p.adam_out, p.lr, p.b1, p.b2);
     if (t == 64 && p.tick0b) tick_all(p.tick0b, nullptr, p.adam_pw_b, p.adam_out_b, p.lr_b, p.b1, p.b2);
   }
-  const int grp = net / p.npg, ni = net - grp * p.npg;
-  const NtGrp G = p.g[grp];
-  const float* Pn = G.P + ni * p.p_ns;
-  const int tiles_n = (p.N + 16 * NT - 1) / (16 * NT);
+  const int grp = net / npg, ni = net - grp * npg;
+  // a ring group's four control words are asked for NOW, through the header's pointer, beside the descriptor (unconditionally: the
+  // host passes the engine's control block in every launch, ring groups or not -- a request behind a test would be waited for there)
+  int c_inject = 0, c_rb_len = 0, c_sctr = 0; unsigned long long c_seed = 0;
+  if (HDR_NT && FUSE1) { c_inject = ctl->inject_idx; c_rb_len = ctl->rb_len; c_sctr = ctl->sample_ctr; c_seed = ctl->seed; }
+  NtGrp G = p.g[grp];
+  // the common words of the first requests, asked for in the SAME round as the group's descriptor (HDR_NT; left alone, the compiler
+  // fetches each one where it is first used: two more dependent rounds in front of the operand batch).  ONE pin for all of them and
+  // for every integer word of the descriptor: values that are live together cannot share a register, and a scalar load into a register that
+  // an earlier load still owes (out-of-order returns) would be a wait -- a round -- of its own (NtGrp::pad_ was such a register).
+  // Everything below depends on the pin's outputs, so nothing is scheduled in front of it (a read-only pin let the compiler split
+  // the batch in two again).  The descriptor's POINTERS stay out of it -- they arrive in the same loads as its integers, and a
+  // pointer that went through a pin is no longer known to be global: flat loads
+  long p_ns = p.p_ns, in_ns = p.in_ns;
+  int oBias = p.oBias, ld_in = p.ld_in, oW1 = p.oW1, ldw1 = p.ldw1, K1 = p.K1, oW = p.oW, ldw = p.ldw, oB1 = p.oB1, oG = p.oG, oBe = p.oBe, xr = p.xr;
+  // what a ring-reading group's row address needs beyond its control words: the ring's record size, and COPIES of two pointers' bits
+  // (the ring, the injected indices) -- the copies go through the pin, so the loads they share with the pointers are part of the
+  // batch, and the pointers themselves stay known to be global
+  int rec4 = FUSE1 ? p.ga[0].rec4 : 0;
+  unsigned long ring_bits = FUSE1 ? (unsigned long)p.ga[0].ring : 0, idx_bits = FUSE1 ? (unsigned long)G.ring_idx : 0;
+  if (HDR_NT) {
+    rec4 = uni(rec4); ring_bits = (unsigned long)uni((long)ring_bits); idx_bits = (unsigned long)uni((long)idx_bits);
+    // (readfirstlane: a no-op on a value the compiler knows to be uniform; the stamps build loses track of that behind its per-thread
+    //  stamp branches, and an "s" operand it believes divergent does not compile)
+    G.ring = uni(G.ring); G.ring_off = uni(G.ring_off); G.sctr_add = uni(G.sctr_add); G.pad_ = uni(G.pad_); p_ns = uni(p_ns); in_ns = uni(in_ns);
+    oBias = uni(oBias); ld_in = uni(ld_in); oW = uni(oW); ldw = uni(ldw); xr = uni(xr); oW1 = uni(oW1); ldw1 = uni(ldw1); K1 = uni(K1);
+    oB1 = uni(oB1); oG = uni(oG); oBe = uni(oBe);
+    asm volatile("" : "+s"(G.ring), "+s"(G.ring_off), "+s"(G.sctr_add), "+s"(G.pad_), "+s"(p_ns), "+s"(in_ns), "+s"(oBias), "+s"(ld_in), "+s"(oW),
+                      "+s"(ldw), "+s"(xr), "+s"(oW1), "+s"(ldw1), "+s"(K1), "+s"(oB1), "+s"(oG), "+s"(oBe), "+s"(rec4), "+s"(ring_bits), "+s"(idx_bits));
+  }
+  const float* Pn = G.P + ni * p_ns;
+  const int tiles_n = (N + 16 * NT - 1) / (16 * NT);
   int tmb, tn;
-  xcd_tile(bx, (p.M + RB - 1) / RB, tiles_n, FUSE1 ? 0 : p.xr, tmb, tn);
+  xcd_tile(bx, (M + RB - 1) / RB, tiles_n, FUSE1 ? 0 : xr, tmb, tn);
   const int m0 = tmb * RB + 16 * mt, n0 = tn * 16 * NT;          // this wave's rows / the block's columns
-  const int mrow = min(m0 + r, p.M - 1);
+  const int mrow = min(m0 + r, M - 1);
   const int kb = (ks * CW) * 16 + 4 * kq;                    // first k of this lane's fragments
   // requested here, used by the epilogue: a load issued among the epilogue's stores makes each store wait for the last
   float bias[NT];
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt) bias[nt] = p.oBias >= 0 ? Pn[p.oBias + min(n0 + 16 * nt + r, p.N - 1)] : 0.f;
+  for (int nt = 0; nt < NT; ++nt) bias[nt] = oBias >= 0 ? Pn[oBias + min(n0 + 16 * nt + r, N - 1)] : 0.f;
   STAMP(0); BLK_PH_K(1, 0);
   // ---- 1. every global load, coalesced where the data is shared by the block
   float4 w2r[4 * NT], w1r[C1 > 0 ? 4 * C1 : 1], vr = f4(0.f), xv[C1 > 0 ? C1 : 1], av[CW];
-  const int w1n = FUSE1 ? (HID * p.ldw1) >> 2 : 0;           // float4s of W1 (rows are 16-byte multiples, contiguous)
+  const int w1n = FUSE1 ? (HID * ldw1) >> 2 : 0;           // float4s of W1 (rows are 16-byte multiples, contiguous)
   if (FUSE1) {
 #pragma unroll
     for (int u = 0; u < 4 * C1; ++u) {                        // ldw1 <= 16 C1 floats -> at most 4 C1 float4 per thread
       const int f = min(t + 256 * u, w1n - 1);               // clamped, not predicated: parked only where t + 256 u < w1n
-      w1r[u] = ld4(Pn + p.oW1 + 4 * (long)f);
+      w1r[u] = ld4(Pn + oW1 + 4 * (long)f);
     }
-    const float* xrow = G.in + ni * p.in_ns + (long)mrow * p.ld_in;
+    const float* xrow = G.in + ni * in_ns + (long)mrow * ld_in;
     if (G.ring) {                                            // (block-uniform) this sample's record in the replay ring
-      const int inject = p.ga[0].ctl->inject_idx, rb_len = p.ga[0].ctl->rb_len, sctr = p.ga[0].ctl->sample_ctr + G.sctr_add;   // one batch of requests
-      const unsigned long long seed = p.ga[0].ctl->seed;
+      const int inject = HDR_NT ? c_inject : ctl->inject_idx, rb_len = HDR_NT ? c_rb_len : ctl->rb_len;   // one batch of requests
+      const int sctr = (HDR_NT ? c_sctr : ctl->sample_ctr) + G.sctr_add;
+      const unsigned long long seed = HDR_NT ? c_seed : ctl->seed;
       int id = (int)philox_index(seed, (unsigned)sctr, (unsigned)mrow, (unsigned)max(rb_len, 1));
       if (inject) id = G.ring_idx[mrow];
-      xrow = reinterpret_cast<const float*>(p.ga[0].ring) + (long)id * (4 * p.ga[0].rec4) + G.ring_off;
+      xrow = reinterpret_cast<const float*>(p.ga[0].ring) + (long)id * (4 * rec4) + G.ring_off;
     }
 #pragma unroll
     for (int c1 = 0; c1 < C1; ++c1) {
       const int k = 16 * c1 + 4 * kq;
-      xv[c1] = ld4_cols(xrow, k, p.K1, (p.K1 + 3) & ~3);
+      xv[c1] = ld4_cols(xrow, k, K1, (K1 + 3) & ~3);
     }
   } else {
 #pragma unroll
-    for (int c = 0; c < CW; ++c) av[c] = ld4(G.in + ni * p.in_ns + (long)mrow * p.ld_in + kb + 16 * c);
+    for (int c = 0; c < CW; ++c) av[c] = ld4(G.in + ni * in_ns + (long)mrow * ld_in + kb + 16 * c);
   }
   if (t < 192) {                                             // b1 | gamma | beta as one 3 x 256 vector
     const int which = t >> 6, c4 = t & 63;
-    const int off = which == 0 ? p.oB1 : (which == 1 ? p.oG : p.oBe);
+    const int off = which == 0 ? oB1 : (which == 1 ? oG : oBe);
     if ((which == 0 && FUSE1) || (which != 0 && PRO == 1)) vr = ld4(Pn + off + 4 * c4);
   }
   // the second layer's W tile is requested LAST (loads return in order): the first layer and the row statistics run
   // while it is still in flight
 #pragma unroll
   for (int u = 0; u < 4 * NT; ++u) {                         // 16 NT rows x 256 floats, one row per wave-instruction
-    const int i = t + 256 * u, row = i >> 6, c4 = i & 63, n = min(n0 + row, p.N - 1);
-    w2r[u] = ld4(Pn + p.oW + (long)n * p.ldw + 4 * c4);
+    const int i = t + 256 * u, row = i >> 6, c4 = i & 63, n = min(n0 + row, N - 1);
+    w2r[u] = ld4(Pn + oW + (long)n * ldw + 4 * c4);
   }
   __builtin_amdgcn_sched_barrier(0);
   // ---- 2. park the shared operands in LDS (W1 first: the first layer only needs W1, x, b1)
@@ -1215,7 +1268,7 @@ __global__ __launch_bounds__(256) void k_nt(NtArgs p) {
   // The normalised rows are kept for the backward pass.  Every column-tile block of a row block holds the same rows, so
   // each stores only ITS share of the 16 column chunks (16 / tiles_n of them) instead of the tn == 0 blocks storing whole
   // rows: 64 KB per row block spread over all of its blocks -- those few blocks were the launch's long pole.
-  if (PRO != 0 && m0 + r < p.M) {
+  if (PRO != 0 && m0 + r < M) {
     const long ro = ni * p.act_ns + (long)(m0 + r) * HID + kb;
     const int gsz = 16 / tiles_n, g0 = tn * gsz;               // this block's chunks: [g0, g0 + gsz) (tiles_n is 8 or 16)
 #pragma unroll
@@ -1226,7 +1279,7 @@ __global__ __launch_bounds__(256) void k_nt(NtArgs p) {
         if (G.h_out) st4_pol<WT_ACT1>(G.h_out, ro + 16 * c, av[c]);
       }
     }
-    if (G.rstd_out && tn == 0 && ks == 0 && kq == 0) G.rstd_out[(long)ni * p.M + m0 + r] = rstd;
+    if (G.rstd_out && tn == 0 && ks == 0 && kq == 0) G.rstd_out[(long)ni * M + m0 + r] = rstd;
   }
   // ---- 4. second layer: this wave's rows x the block's 16 NT columns over its K range (W tiles from LDS)
   // Even chunks accumulate in a0, odd ones in a1 (per column tile): 2 NT independent MFMA chains, issued alternately, with the W
@@ -1292,16 +1345,24 @@ __global__ __launch_bounds__(256) void k_nt(NtArgs p) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const int col = n0 + 16 * nt + (lane & 15);
-      if (col >= p.N) continue;
+      if (col >= N) continue;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = m0 + 4 * (lane >> 4) + i;
-        if (row < p.M) st1_pol<WT_Z2>(y + (long)row * p.ldy + col, acc[nt][i] + bias[nt]);
+        if (row < M) st1_pol<WT_Z2>(y + (long)row * p.ldy + col, acc[nt][i] + bias[nt]);
       }
     }
   }
   STAMP(5); BLK_PH_K(1, 5);
   BLK_MARK_K(1, 1);
+}
+
+// k_nt's launch header (SACTD3_HDR; host side: engine.hip and the tools launch the family through this one function): what a block needs to find its role, its net and its group, taken from the struct that
+// follows it
+template <typename K>
+static inline void launch_k_nt(K kernel, dim3 grid, hipStream_t s, const NtArgs& g) {
+  const int riders = (g.gblocks | g.alpha_block | g.nz_n) != 0;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, g.flat, g.flat_r, g.flat_n, g.nt_blocks, riders, g.npg, g.M, g.N, g.ga[0].ctl, g);      // (ga[0].ctl: a valid control block in EVERY launch, the fused instances read through it)
 }
 
 // Generic-K form (an unfused first layer wider than 64 inputs): 16 x 16 tile per block, wave w takes k chunks w, w+4, ...
@@ -1932,7 +1993,7 @@ __device__ __forceinline__ void adam_commit(const TnArgs& p, long off, float g, 
 // FOLD: the instance whose layer-1 problem applies the LayerNorm backward itself (TnProb::fold); launches without such a problem
 // take the plain instance (the fold's operands cost registers: the actor's B = 1024 launch was 5 us slower through one kernel).
 template <int KT, bool FOLD = false, bool KEEP_G = true>
-__global__ __launch_bounds__(256) void k_tn(TnArgs p) {
+__global__ __launch_bounds__(256) void k_tn(int h_tiles, int h_pk_blocks, int h_fin_blocks, int h_nprob, int h_tile1, int h_tile2, int h_tile3, int h_M, TnArgs p) {
   __shared__ __attribute__((aligned(16))) float red[KT * 4 * 64 * 4];
   __shared__ __attribute__((aligned(16))) float Ys[256 * YS];
   __shared__ __attribute__((aligned(16))) float Xs[KT * 256 * YS];
@@ -1941,25 +2002,41 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, net = blockIdx.z;
   const int r = lane & 15, kq = lane >> 4;
   BLK_MARK(0);
-  if ((int)blockIdx.x >= p.tiles) {                         // (block-uniform) riding blocks
-    const int x = (int)blockIdx.x - p.tiles;
-    if (x < p.pk_blocks) { if (net == 0) polyak_body(p.pk, x, p.pk_blocks); }
-    else if (x - p.pk_blocks < p.fin_blocks) adam_red_tail_body<KEEP_G>(p.fin, x - p.pk_blocks, net);      // (behind them: padding up to a multiple of 8 blocks
+  // role and problem from the launch header (HDR_TN): no load in front of the problem's own batch
+  const int tiles = HDR_TN ? h_tiles : p.tiles, pk_blocks = HDR_TN ? h_pk_blocks : p.pk_blocks, fin_blocks = HDR_TN ? h_fin_blocks : p.fin_blocks;
+  const int M = HDR_TN ? h_M : p.M;
+  if ((int)blockIdx.x >= tiles) {                           // (block-uniform) riding blocks
+    const int x = (int)blockIdx.x - tiles;
+    if (x < pk_blocks) { if (net == 0) polyak_body(p.pk, x, pk_blocks); }
+    else if (x - pk_blocks < fin_blocks) adam_red_tail_body<KEEP_G>(p.fin, x - pk_blocks, net);      // (behind them: padding up to a multiple of 8 blocks
     BLK_MARK(1);                                                                                  //  per net, so that every net's tile ids keep their XCDs)
     return;
   }
+  const int nprob = HDR_TN ? h_nprob : p.nprob;
   int pi = 0;
-  if (p.nprob > 1 && (int)blockIdx.x >= p.pr[1].tile0) pi = 1;
-  if (p.nprob > 2 && (int)blockIdx.x >= p.pr[2].tile0) pi = 2;
-  if (p.nprob > 3 && (int)blockIdx.x >= p.pr[3].tile0) pi = 3;
+  if (nprob > 1 && (int)blockIdx.x >= (HDR_TN ? h_tile1 : p.pr[1].tile0)) pi = 1;
+  if (nprob > 2 && (int)blockIdx.x >= (HDR_TN ? h_tile2 : p.pr[2].tile0)) pi = 2;
+  if (nprob > 3 && (int)blockIdx.x >= (HDR_TN ? h_tile3 : p.pr[3].tile0)) pi = 3;
   const TnProb q = p.pr[pi];     // ONE batch of scalar loads for the whole problem (field-by-field they came in 3-4 dependent rounds)
+  int ldy = q.ldy, ldx = q.ldx;  // (left alone, the compiler fetches these two again in a round of their own, waited for in front of the first operand load)
+  // ... and with them what the requests BEHIND the operand batch need (the optimiser state of the block's elements): integers, and
+  // copies of the pointers' bits -- a pointer that went through a pin itself would no longer be known to be global (see k_nt)
+  long g_ns = p.g_ns;
+  int apply = p.apply;
+  unsigned long adam_bits = (unsigned long)p.adam, P_bits = (unsigned long)p.P, Mo_bits = (unsigned long)p.Mo, Vo_bits = (unsigned long)p.Vo, T_bits = (unsigned long)p.T;
+  if (HDR_TN) {
+    ldy = uni(ldy); ldx = uni(ldx); g_ns = uni(g_ns); apply = uni(apply);
+    adam_bits = (unsigned long)uni((long)adam_bits); P_bits = (unsigned long)uni((long)P_bits); Mo_bits = (unsigned long)uni((long)Mo_bits);
+    Vo_bits = (unsigned long)uni((long)Vo_bits); T_bits = (unsigned long)uni((long)T_bits);
+    asm volatile("" : "+s"(ldy), "+s"(ldx), "+s"(g_ns), "+s"(apply), "+s"(adam_bits), "+s"(P_bits), "+s"(Mo_bits), "+s"(Vo_bits), "+s"(T_bits));
+  }
   const int local = blockIdx.x - q.tile0;
   const int kw = q.kw > 0 ? q.kw : q.ldw;                 // columns of this problem's piece of dW
   const int tiles_k = (((kw + 15) >> 4) + KT - 1) / KT;
   int tn, tk;
   xcd_tile(local, (q.N + 15) >> 4, tiles_k, q.xr, tn, tk);
   const int n0 = tn * 16, k0 = tk * 16 * KT;
-  const long nbase = net * p.g_ns;
+  const long nbase = net * g_ns;
   // the epilogue's elements: wave kt < KT, lane (j = lane & 15, rq = lane >> 4) owns rows n0 + 4 rq + i, column k0 + 16 kt + j
   const int ecol = k0 + 16 * min(wave, KT - 1) + (lane & 15);
   AdamState st[4], sv = {0.f, 0.f, 0.f, 0.f};
@@ -1980,12 +2057,12 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = t + 256 * u, row = i >> 2, c4 = i & 3, m = mb + row, n = n0 + 4 * c4, k = k0 + 4 * c4;
-      const long mc = min(m, p.M - 1);
-      vy[u] = ld4_raw(dYn + mc * q.ldy, n, Nr);
+      const long mc = min(m, M - 1);
+      vy[u] = ld4_raw(dYn + mc * ldy, n, Nr);
 #pragma unroll
-      for (int kt = 0; kt < KT; ++kt) vx[kt][u] = ld4_raw(Xn + mc * q.ldx, k + 16 * kt, Kr);
+      for (int kt = 0; kt < KT; ++kt) vx[kt][u] = ld4_raw(Xn + mc * ldx, k + 16 * kt, Kr);
       if (fold_ln) {
-        const long rn = (long)net * p.M + mc;
+        const long rn = (long)net * M + mc;
         vxh[u] = ld4(q.f_xh + rn * HID + n);
         vp1[u] = ld4(q.f_ps + rn * PS_W + 4 * c4);
         vp2[u] = ld4(q.f_ps + rn * PS_W + 16 + 4 * c4);
@@ -1995,7 +2072,7 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
   };
   fetch(0);
   if (fold_ln) gq = ld4(q.f_g + net * HID + n0 + 4 * (t & 3));
-  const float step = p.apply ? p.adam[0] : 0.f, sq2 = p.apply ? p.adam[1] : 1.f;
+  const float step = apply ? p.adam[0] : 0.f, sq2 = apply ? p.adam[1] : 1.f;
   if (wave < KT) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {          // clamped, not predicated (the commit is predicated)
@@ -2012,14 +2089,14 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
   if (want_bias && wave == 3 && lane < 16 && fn < q.N) { foff = nbase + q.b_off + fn; fstate = adam_fetch(p, foff); }
   const bool fold_vec = fold_ln && tk == 0;                // dgamma1 / dbeta1 of the 16 columns: wave 3, lanes 16 .. 31 / 32 .. 47
   if (fold_vec && wave == 3 && lane >= 16 && lane < 48) { foff = nbase + (lane < 32 ? q.f_g_off : q.f_be_off) + fn; fstate = adam_fetch(p, foff); }
-  for (int mb = 0; mb < p.M; mb += 256) {
+  for (int mb = 0; mb < M; mb += 256) {
     if (mb) __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
     STAMP(1); BLK_PH(1);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = t + 256 * u, c4 = i & 3;
-      const bool row_ok = mb + (i >> 2) < p.M;
+      const bool row_ok = mb + (i >> 2) < M;
       if (fold) {                                          // N = HID: no column mask
         float4 dz = row_ok ? vy[u] : f4(0.f);
         if (fold_ln) {
@@ -2033,14 +2110,14 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
           if (!row_ok) dz = f4(0.f);
         }
         st4(Ys + (i >> 2) * YS + 4 * c4, dz);
-        if (tk == 0 && row_ok && q.f_dz) st4(q.f_dz + ((long)net * p.M + mb + (i >> 2)) * HID + n0 + 4 * c4, dz);
+        if (tk == 0 && row_ok && q.f_dz) st4(q.f_dz + ((long)net * M + mb + (i >> 2)) * HID + n0 + 4 * c4, dz);
       } else
       st4(Ys + (i >> 2) * YS + 4 * c4, mask4_cols(vy[u], n0 + 4 * c4, q.N, row_ok));
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) st4(Xs + kt * 256 * YS + (i >> 2) * YS + 4 * c4, mask4_cols(vx[kt][u], k0 + 4 * c4 + 16 * kt, q.K, row_ok));
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (mb + 256 < p.M) fetch(mb + 256);                   // the next slab's rows fly under this slab's MFMAs
+    if (mb + 256 < M) fetch(mb + 256);                   // the next slab's rows fly under this slab's MFMAs
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
 #pragma unroll
@@ -2105,6 +2182,14 @@ __global__ __launch_bounds__(256) void k_tn(TnArgs p) {
   }
   STAMP(4); BLK_PH(4);
   BLK_MARK(1);
+}
+
+// k_tn's launch header (SACTD3_HDR; host side): the words a block needs to find its role and its problem, taken from the very struct
+// that follows them -- a header cannot disagree with its struct
+template <int KT, bool FOLD, bool KEEP_G>
+static inline void launch_k_tn(dim3 grid, hipStream_t s, const TnArgs& g) {
+  hipLaunchKernelGGL((k_tn<KT, FOLD, KEEP_G>), grid, dim3(256), 0, s, g.tiles, g.pk_blocks, g.fin_blocks, g.nprob,
+                     g.pr[1].tile0, g.pr[2].tile0, g.pr[3].tile0, g.M, g);
 }
 
 // ---- large-batch form of the weight gradients (M >= 1024).  k_tn's 16 x 16 tiles make every block re-read a [M][16]

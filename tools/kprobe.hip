@@ -38,18 +38,20 @@ int main() {
   CK(hipMemcpy(P, hp.data(), hp.size() * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(X, hp.data(), B * ldc * 4, hipMemcpyHostToDevice));
   CK(hipMemcpy(Z2, hp.data(), 2 * B * 256 * 4, hipMemcpyHostToDevice));
   const int W1 = 0, b1 = 256 * 16, g1 = b1 + 256, be1 = g1 + 256, W2 = be1 + 256, b2 = W2 + 65536;
+  DevCtl hc0{}; hc0.rb_len = 1; DevCtl* ctl0; CK(hipMalloc(&ctl0, sizeof(DevCtl))); CK(hipMemcpy(ctl0, &hc0, sizeof(hc0), hipMemcpyHostToDevice));
   for (int ks : {4, 2, 1}) {
     const int nets = ks == 4 ? 1 : (ks == 2 ? 2 : 4);
     NtArgs h{};
+    h.ga[0].ctl = ctl0;      // (k_nt's launch header: the fused instances read the control block through it)
     h.npg = nets; h.g[0].in = X; h.g[0].P = P; h.g[0].Y = Z2; h.g[0].xh_out = XH; h.g[0].h_out = H; h.g[0].rstd_out = RS;
     h.ld_in = ldc; h.in_ns = 0; h.oW = W2; h.ldw = 256; h.oBias = b2; h.oG = g1; h.oBe = be1; h.p_ns = 0;
     h.ldy = 256; h.y_ns = 0; h.M = B; h.N = 256; h.K = 256; h.K1 = o + a; h.oW1 = W1; h.ldw1 = 16; h.oB1 = b1; h.act_ns = 0;
     const int rb = 64 / ks;
     const dim3 grid((B / rb) * 16, 1, nets);
     double us;
-    if (ks == 4) us = graph_us(s, [&] { hipLaunchKernelGGL((k_nt<1, true, 4, 1>), grid, dim3(256), 0, s, h); }, 20, 50);
-    else if (ks == 2) us = graph_us(s, [&] { hipLaunchKernelGGL((k_nt<1, true, 2, 1>), grid, dim3(256), 0, s, h); }, 20, 50);
-    else us = graph_us(s, [&] { hipLaunchKernelGGL((k_nt<1, true, 1, 1>), grid, dim3(256), 0, s, h); }, 20, 50);
+    if (ks == 4) us = graph_us(s, [&] { launch_k_nt(k_nt<1, true, 4, 1>, grid, s, h); }, 20, 50);
+    else if (ks == 2) us = graph_us(s, [&] { launch_k_nt(k_nt<1, true, 2, 1>, grid, s, h); }, 20, 50);
+    else us = graph_us(s, [&] { launch_k_nt(k_nt<1, true, 1, 1>, grid, s, h); }, 20, 50);
     char nm[64]; snprintf(nm, 64, "k_nt<1,fused,KS=%d> nets=%d", ks, nets); show(nm, us, 6);
   }
   {  // critic weight-gradient launch: dW2 (256 x 256) + dW1 (256 x 16), 2 nets, Adam on
@@ -65,10 +67,10 @@ int main() {
     q1.nfin = 2; q1.fin_slot[0] = 3; q1.fin_off[0] = g1; q1.fin_slot[1] = 4; q1.fin_off[1] = be1; q1.fin_s_off = -1; q1.fin_nblk[0] = q1.fin_nblk[1] = 16; q1.tile0 = 256;
     g.pr[0] = q0; g.pr[1] = q1; g.tiles = 272; g.apply = 1; g.P = P; g.Mo = Mo; g.Vo = Vo; g.T = T; g.tau = 0.005f; g.adam = adam; g.b1 = 0.9f; g.b2 = 0.999f; g.eps = 1e-8f;
     g.part = part; g.pstride = 16; g.part_s = ps; g.loss_part = ps; g.loss_n = 32; g.loss_stride = 2; g.loss_off = 1; g.loss_scale = 1.f / B; g.loss_dst = adam + 2;
-    double us = graph_us(s, [&] { hipLaunchKernelGGL(k_tn<1>, dim3(272, 1, 2), dim3(256), 0, s, g); }, 20, 50);
+    double us = graph_us(s, [&] { launch_k_tn<1, false, true>(dim3(272, 1, 2), s, g); }, 20, 50);
     show("k_tn critics (+Adam)", us, 5);
     g.apply = 0;
-    us = graph_us(s, [&] { hipLaunchKernelGGL(k_tn<1>, dim3(272, 1, 2), dim3(256), 0, s, g); }, 20, 50);
+    us = graph_us(s, [&] { launch_k_tn<1, false, true>(dim3(272, 1, 2), s, g); }, 20, 50);
     show("k_tn critics (grads only)", us, 5);
   }
   {
