@@ -53,56 +53,108 @@ def _on_engine_device(engine: Engine, x) -> bool:
     return ordinal is None or int(ordinal) == int(engine.cfg.device_id)
 
 
+def _detached(x):
+    return x.detach() if hasattr(x, "detach") else x
+
+
+_ITEM = {"f4": 4, "b1": 1, "i8": 8}      # the element kinds of a field -- float32, flags, int64 -- and their sizes in bytes
+
+
+def _is_kind(typestr: str, kind: str) -> bool:
+    return typestr[1:] == kind or (kind == "b1" and typestr[2:] == "1")      # (flags: any one-byte type)
+
+
+def _read_input(engine: Engine, x, width: int, kind: str, cai=None):
+    """THE reader of an array the caller hands in.  -> (array to keep alive across the call, address, rows, row stride in elements),
+    or None when `x` is not an array in the memory of the engine's device: the host route, an upload or a TypeError is the caller's.
+    Pointer, shape and strides come from __cuda_array_interface__, read once unless the array is converted; a caller that has read it
+    already and routed on it passes it as `cai`, with the detached array it belongs to.  A field that is not float32 (flags: not
+    1-byte), or whose inner dimension is not contiguous, is first converted ON the device with the array library's own ops
+    (.to(float32), != 0, .contiguous()); nothing converts to int64: an index of another dtype is None too."""
+    if cai is None:
+        x = _detached(x)
+        cai = _cai(x)
+        if cai is None or not _on_engine_device(engine, x):
+            return None
+    if not _is_kind(cai["typestr"], kind):
+        if kind == "i8":
+            return None
+        if kind == "b1":
+            x = x != 0
+        else:
+            lib = sys.modules.get(type(x).__module__.partition(".")[0])
+            x = x.to(getattr(lib, "float32", "float32"))
+        cai = _cai(x)
+    got = _cai_field(cai, width, _ITEM[kind])
+    if got is None:
+        x = x.contiguous()
+        got = _cai_field(_cai(x), width, _ITEM[kind])
+    return x, got[0], got[1], got[2]
+
+
+def _output_cai(engine: Engine, x, kind: str, name: str):
+    """the __cuda_array_interface__ of an array the engine is to write, which cannot be converted the way an input can: anything but
+    elements of `kind` in the memory of the engine's device is a TypeError"""
+    cai = _cai(_detached(x))
+    if cai is None or not _on_engine_device(engine, x):
+        raise TypeError(f"{name} must be an array in the memory of the engine's device")
+    if not _is_kind(cai["typestr"], kind):
+        raise TypeError(f"{name} must be " + {"f4": "float32", "b1": "bool (one byte per flag)", "i8": "int64"}[kind] + f", got {cai['typestr']}")
+    return cai
+
+
+def _read_output(engine: Engine, x, width: int, kind: str, name: str, n: int, more_rows: bool = False):
+    """THE reader of an array the engine is to write.  -> (address, rows, row stride in elements) of n rows -- `more_rows`: or more
+    -- as _cai_field reads them; a wrong shape, an inner stride or a wrong row count is a ValueError.  `name` opens every message."""
+    cai = _output_cai(engine, x, kind, name)
+    try:
+        got = _cai_field(cai, width, _ITEM[kind])
+    except ValueError as ex:
+        raise ValueError(f"{name}: {ex}") from None
+    if got is None:
+        raise ValueError(f"{name} needs a contiguous inner dimension and a row stride of at least its width")
+    if got[1] < n or (got[1] > n and not more_rows):
+        raise ValueError(f"{name} has {got[1]} rows, expected {'at least ' if more_rows else ''}{n}")
+    return got
+
+
+def _torch_alloc(engine: Engine, what: str):
+    """alloc(shape, kind) of an output nobody passed: torch.empty on the engine's device"""
+    try:
+        import torch
+    except ImportError:
+        raise TypeError(f"{what}: without torch the caller passes `out`") from None
+    dev = torch.device("cuda", int(engine.cfg.device_id))
+    kinds = {"f4": torch.float32, "b1": torch.bool, "i8": torch.int64}
+    return lambda shape, kind: torch.empty(shape, dtype=kinds[kind], device=dev)
+
+
 def _device_route(engine: Engine, obs, act, rew, nobs, done):
     """The one place that decides how five arrays reach the engine.  -> (fields, n, keep) for Engine.rb_extend_fields_device /
     load_batch_device when ALL of them are arrays on the engine's device (`keep` holds converted copies alive across the call),
-    None for the host route (numpy, a mix of host and device, another device, `engine.device_inputs` off).
-    Pointer, shape and strides come from __cuda_array_interface__; a field that is not float32 (flags: not 1-byte), or whose inner
-    dimension is not contiguous, is first converted ON the device with the array library's own ops (.to(float32), != 0, .contiguous())."""
+    None for the host route (numpy, a mix of host and device, another device, `engine.device_inputs` off).  It is _read_input for
+    five arrays that go one way together: where all of them live is settled first, then each field is read."""
     if not getattr(engine, "device_inputs", False):
         return None
-    xs = [x.detach() if hasattr(x, "detach") else x for x in (obs, act, rew, nobs, done)]
+    xs = [_detached(x) for x in (obs, act, rew, nobs, done)]
     cais = [_cai(x) for x in xs]      # (read once per array: building the dictionary is the expensive part of this function)
     if any(c is None for c in cais):
         return None
     if not all(_on_engine_device(engine, x) for x in xs):      # another GPU's arrays take the host route (the C side refuses them too)
         return None
     o, a = engine.cfg.ob_dim, engine.cfg.ac_dim
-    fields, rows, keep = [], [], []
-    for x, cai, width, is_flag in zip(xs, cais, (o, a, 1, o, 1), (False, False, False, False, True)):
-        typestr, item = cai["typestr"], 1 if is_flag else 4
-        if is_flag and int(typestr[2:]) != 1:
-            x = x != 0
-            cai = _cai(x)
-        elif not is_flag and typestr[1:] != "f4":
-            lib = sys.modules.get(type(x).__module__.partition(".")[0])
-            x = x.to(getattr(lib, "float32", "float32"))
-            cai = _cai(x)
-        got = _cai_field(cai, width, item)
-        if got is None:
-            x = x.contiguous()
-            got = _cai_field(_cai(x), width, item)
-        keep.append(x)
-        fields.append((got[0], got[2]))
-        rows.append(got[1])
+    got = [_read_input(engine, x, width, kind, cai) for x, cai, width, kind in zip(xs, cais, (o, a, 1, o, 1), ("f4", "f4", "f4", "f4", "b1"))]
+    rows = [n for _, _, n, _ in got]
     if len(set(rows)) != 1:
         raise ValueError(f"fields disagree on the number of rows: {rows}")
     if rows[0] == 0:
         return None      # (nothing to read: the host route's n == 0 case)
-    return fields, rows[0], keep
+    return [(ptr, ld) for _, ptr, _, ld in got], rows[0], [x for x, _, _, _ in got]
 
 
 # the six destinations of a read-out, in the order of sactd3_device_fields_out: (key, width -- "o" / "a" = the engine's dims --, kind)
 _OUT_FIELDS = (("observations", "o", "f4"), ("actions", "a", "f4"), ("rewards", 1, "f4"), ("next_observations", "o", "f4"),
                ("dones", 1, "b1"), ("index", 1, "i8"))
-_OUT_ITEM = {"f4": 4, "b1": 1, "i8": 8}
-
-
-def _torch_alloc(engine: Engine):
-    import torch
-    dev = torch.device("cuda", int(engine.cfg.device_id))
-    kinds = {"f4": torch.float32, "b1": torch.bool, "i8": torch.int64}
-    return lambda shape, kind: torch.empty(shape, dtype=kinds[kind], device=dev)
 
 
 def _device_outputs(engine: Engine, n: int, out: Optional[Mapping[str, Any]] = None, alloc=None):
@@ -111,8 +163,8 @@ def _device_outputs(engine: Engine, n: int, out: Optional[Mapping[str, Any]] = N
     reference stores it); index [n] int64 -- and `fields` the six (device address, row stride in elements) pairs for
     Engine.read_batch_device / rb_read_rows_device.  Arrays come from `alloc(shape, kind)` (default: torch.empty on the engine's
     device); `out` may replace any of them with a preallocated array or view (rewards / dones / index as [n, 1] or [n]; `terminations`
-    names the dones array).  Pointer, shape and strides come from __cuda_array_interface__.  An output cannot be converted the way an
-    input can: a wrong dtype or another device's array is a TypeError, a wrong shape or an inner stride a ValueError."""
+    names the dones array).  Each is read by _read_output: a wrong dtype or another device's array is a TypeError, a wrong shape, an
+    inner stride or another row count a ValueError."""
     out = dict(out) if out else {}
     known = {k for k, _, _ in _OUT_FIELDS} | {"terminations"}
     if set(out) - known:
@@ -128,24 +180,11 @@ def _device_outputs(engine: Engine, n: int, out: Optional[Mapping[str, Any]] = N
         x = out.get(key)
         if x is None:
             if alloc is None:
-                alloc = _torch_alloc(engine)
+                alloc = _torch_alloc(engine, "device read-out")
             x = alloc((n,) if key == "index" else (n, width), kind)
-        cai = _cai(x.detach() if hasattr(x, "detach") else x)
-        if cai is None or not _on_engine_device(engine, x):
-            raise TypeError(f"`{key}` must be an array in the memory of the engine's device")
-        typestr, item = cai["typestr"], _OUT_ITEM[kind]
-        if (kind == "b1" and int(typestr[2:]) != 1) or (kind != "b1" and typestr[1:] != kind):
-            raise TypeError(f"`{key}` must be " + {"f4": "float32", "b1": "bool (one byte per flag)", "i8": "int64"}[kind] + f", got {typestr}")
-        try:
-            got = _cai_field(cai, width, item)
-        except ValueError as ex:
-            raise ValueError(f"`{key}`: {ex}") from None
-        if got is None:
-            raise ValueError(f"`{key}` needs a contiguous inner dimension and a row stride of at least its width")
-        if got[1] != n:
-            raise ValueError(f"`{key}` has {got[1]} rows, expected {n}")
+        ptr, _, ld = _read_output(engine, x, width, kind, f"`{key}`", n)
         tensors[key] = x
-        fields.append((got[0], got[2]))
+        fields.append((ptr, ld))
     tensors["terminations"] = tensors["dones"]
     return tensors, fields
 
@@ -154,40 +193,26 @@ def _index_field(engine: Engine, index):
     """-> (index, address, n, stride in elements) of a ring-slot index for Engine.rb_read_rows_device / rb_sample_indices_device: an
     int64 array on the engine's device is taken where it is (made contiguous on the device if its stride is not whole elements);
     anything else goes through torch.as_tensor and is uploaded first."""
-    cai = _cai(index.detach() if hasattr(index, "detach") else index)
-    if cai is None or not _on_engine_device(engine, index) or cai["typestr"][1:] != "i8":
-        import torch
-        index = torch.as_tensor(index, dtype=torch.int64).to(torch.device("cuda", int(engine.cfg.device_id)))
-        cai = _cai(index)
-    got = _cai_field(cai, 1, 8)
+    got = _read_input(engine, index, 1, "i8")
     if got is None:
-        index = index.contiguous()
-        got = _cai_field(_cai(index), 1, 8)
-    return (index,) + got
+        import torch
+        got = _read_input(engine, torch.as_tensor(index, dtype=torch.int64).to(torch.device("cuda", int(engine.cfg.device_id))), 1, "i8")
+    return got
 
 
 def _weight_field(engine: Engine, weights, n: int, what: str):
     """-> (array kept alive, address, stride in elements) of per-row loss weights for Engine.rb_sample_indices_device /
     batch_weights_device: [n] or [n, 1] on the engine's device; converted ON the device when not float32 or not strided in whole
     elements, as _device_route does for its fields.  Not an array of that device: TypeError; another row count: ValueError."""
-    w = weights.detach() if hasattr(weights, "detach") else weights
-    cai = _cai(w)
-    if cai is None or not _on_engine_device(engine, w):
-        raise TypeError(f"{what}: the weights must be an array in the memory of the engine's device")
-    if cai["typestr"][1:] != "f4":
-        lib = sys.modules.get(type(w).__module__.partition(".")[0])
-        w = w.to(getattr(lib, "float32", "float32"))
-        cai = _cai(w)
     try:
-        got = _cai_field(cai, 1, 4)
+        got = _read_input(engine, weights, 1, "f4")
     except ValueError as ex:
         raise ValueError(f"{what}: weights: {ex}") from None
     if got is None:
-        w = w.contiguous()
-        got = _cai_field(_cai(w), 1, 4)
-    if got[1] != n:
-        raise ValueError(f"{what}: expected {n} weights (one per batch row), got {got[1]}")
-    return w, got[0], got[2]
+        raise TypeError(f"{what}: the weights must be an array in the memory of the engine's device")
+    if got[2] != n:
+        raise ValueError(f"{what}: expected {n} weights (one per batch row), got {got[2]}")
+    return got[0], got[1], got[3]
 
 
 def _critic_major_out(engine: Engine, n: int, out, what: str):
@@ -196,14 +221,8 @@ def _critic_major_out(engine: Engine, n: int, out, what: str):
     [2, >= n, 1] array or view of that device with positive strides in whole elements -- a wrong dtype or another device's array is a
     TypeError, a wrong shape or stride a ValueError."""
     if out is None:
-        try:
-            import torch
-        except ImportError:
-            raise TypeError(f"{what}: without torch the caller passes `out`") from None
-        out = torch.empty((2, n, 1), dtype=torch.float32, device=torch.device("cuda", engine.cfg.device_id))
-    ocai = _cai(out.detach() if hasattr(out, "detach") else out)
-    if ocai is None or not _on_engine_device(engine, out) or ocai["typestr"][1:] != "f4":
-        raise TypeError(f"{what}: `out` must be a float32 array in the memory of the engine's device")
+        out = _torch_alloc(engine, what)((2, n, 1), "f4")
+    ocai = _output_cai(engine, out, "f4", f"{what}: `out`")
     shape, strides = tuple(ocai["shape"]), ocai.get("strides")
     if len(shape) != 3 or shape[0] != 2 or shape[2] != 1 or shape[1] < n:
         raise ValueError(f"{what}: `out` must be [2, >= {n}, 1], got {list(shape)}")
@@ -250,6 +269,12 @@ class _DeviceScalar:
 
 
 _METRIC_SLOT = {"loss/qf_loss": 0, "loss/actor_loss": 1, "loss/alpha_loss": 2, "vitals/alpha": 3}   # SACTD3_M_*
+
+
+def _bump_generation(engine: Engine) -> int:
+    """the engine's batch slot has new rows: handles made for the old ones go stale (see StaleBatchError)"""
+    engine._batch_generation = getattr(engine, "_batch_generation", 0) + 1
+    return engine._batch_generation
 
 
 class StaleBatchError(RuntimeError):
@@ -320,6 +345,9 @@ class ReplayBuffer:
         assert self._engine is not None, "replay buffer is not attached to an Agent yet"
         return self._engine
 
+    def _new_handle(self, eng: Engine) -> BatchHandle:
+        return BatchHandle(eng, _bump_generation(eng), device=self.device_batches)
+
     def extend(self, td: Mapping[str, Any]) -> None:
         """orchestrator.py:100-113: keys observations, next_observations, actions, rewards, terminations, dones."""
         done = td["dones"] if "dones" in td else td["terminations"]
@@ -335,8 +363,7 @@ class ReplayBuffer:
         eng = self._need()
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
         eng.rb_sample()
-        eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1
-        return BatchHandle(eng, eng._batch_generation, device=self.device_batches)
+        return self._new_handle(eng)
 
     def sample_at(self, index, weights=None) -> BatchHandle:
         """sample() with the caller's rows: the ring records `index` names (batch_size ring slots: an int64 tensor on the engine's
@@ -355,8 +382,7 @@ class ReplayBuffer:
         keep, w_ptr, w_ld = (None, 0, 1) if weights is None else _weight_field(eng, weights, B, "sample_at")
         eng.rb_sample_indices_device(ptr, ld, w_ptr, w_ld, n, _producer_stream(index, eng.cfg.device_id))
         del keep      # (the engine's read is ordered against the stream the allocator hands the block out on)
-        eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1
-        return BatchHandle(eng, eng._batch_generation, device=self.device_batches)
+        return self._new_handle(eng)
 
     def enable_priorities(self, alpha: float = 0.6, eps: float = 1e-6) -> None:
         """Proportional prioritised replay kept by the engine (include/sactd3.h: sactd3_prio_enable): one priority per ring slot in
@@ -377,8 +403,7 @@ class ReplayBuffer:
         eng = self._need()
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
         eng.rb_sample_prioritized(beta)
-        eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1
-        return BatchHandle(eng, eng._batch_generation, device=self.device_batches)
+        return self._new_handle(eng)
 
     def update_priorities(self, index=None, priorities=None) -> None:
         """The write-back.  No arguments: the rows of the batch slot get |TD error| (the larger of the twin critics') + eps of the
@@ -502,7 +527,7 @@ class Agent:
                 raise StaleBatchError("update called with an old batch handle: the engine's batch slot holds a later sample "
                                       "(keep the rows, e.g. dict(handle), to train on them again)")
             return  # already in the engine's batch slot (a device-backed handle too: its tensors are copies OF the slot)
-        self.engine._batch_generation = getattr(self.engine, "_batch_generation", 0) + 1   # a caller-owned batch replaces the slot
+        _bump_generation(self.engine)      # a caller-owned batch replaces the slot
         five = (batch["observations"], batch["actions"], batch["rewards"], batch["next_observations"], batch["dones"])
         dev = _device_route(self.engine, *five)
         if dev is not None:
@@ -526,35 +551,17 @@ class Agent:
         eng = self.engine
         o, a = eng.cfg.ob_dim, eng.cfg.ac_dim
         obs = in_td["observations"]
-        obs = obs.detach() if hasattr(obs, "detach") else obs
         if not getattr(eng, "device_inputs", False):
             raise TypeError("predict_device: engine.device_inputs is off (predict() takes host data)")
-        cai = _cai(obs)
-        if cai is None or not _on_engine_device(eng, obs):
-            raise TypeError("predict_device: the observations are not an array in the memory of the engine's device (predict() takes host data)")
-        if cai["typestr"][1:] != "f4":
-            lib = sys.modules.get(type(obs).__module__.partition(".")[0])
-            obs = obs.to(getattr(lib, "float32", "float32"))
-            cai = _cai(obs)
-        got = _cai_field(cai, o, 4)
+        got = _read_input(eng, obs, o, "f4")
         if got is None:
-            obs = obs.contiguous()
-            got = _cai_field(_cai(obs), o, 4)
-        ptr, n, ld = got
+            raise TypeError("predict_device: the observations are not an array in the memory of the engine's device (predict() takes host data)")
+        obs, ptr, n, ld = got
         if out is None:
-            try:
-                import torch
-            except ImportError:
-                raise TypeError("predict_device: without torch the caller passes `out`") from None
-            out = torch.empty((n, a), dtype=torch.float32, device=torch.device("cuda", eng.cfg.device_id))
-        ocai = _cai(out.detach() if hasattr(out, "detach") else out)
-        if ocai is None or not _on_engine_device(eng, out) or ocai["typestr"][1:] != "f4":
-            raise TypeError("predict_device: `out` must be a float32 array in the memory of the engine's device")
-        ogot = _cai_field(ocai, a, 4)
-        if ogot is None or ogot[1] < n:
-            raise ValueError(f"predict_device: `out` needs at least {n} rows of {a} with a contiguous inner dimension")
-        eng.predict_device(ptr, ld, n, explore, ogot[0], ogot[2], _producer_stream(obs, eng.cfg.device_id))
-        return out[:n] if ogot[1] > n else out
+            out = _torch_alloc(eng, "predict_device")((n, a), "f4")
+        out_ptr, out_rows, out_ld = _read_output(eng, out, a, "f4", "predict_device: `out`", n, more_rows=True)
+        eng.predict_device(ptr, ld, n, explore, out_ptr, out_ld, _producer_stream(obs, eng.cfg.device_id))
+        return out[:n] if out_rows > n else out
 
     def q_values(self, in_td: Mapping[str, Any], *, target: bool = False, out: Any = None):
         """What the critics think of these rows: vmap(batched_qf) of the reference (agents/agent.py:146-163) on `observations`
@@ -571,7 +578,7 @@ class Agent:
         eng = self.engine
         o, a = eng.cfg.ob_dim, eng.cfg.ac_dim
         given = [("observations", in_td["observations"], o)] + ([("actions", in_td["actions"], a)] if "actions" in in_td else [])
-        given = [(k, x.detach() if hasattr(x, "detach") else x, w) for k, x, w in given]
+        given = [(k, _detached(x), w) for k, x, w in given]
         cais = [_cai(x) for _, x, _ in given]
         if all(c is None for c in cais):                     # host data: numpy out
             if out is not None:
@@ -582,28 +589,18 @@ class Agent:
             raise TypeError("q_values: observations and actions must both be host arrays or both be arrays in the memory of the engine's device")
         if not getattr(eng, "device_inputs", False):
             raise TypeError("q_values: engine.device_inputs is off (pass host arrays)")
-        fields, rows, keep = [], [], []
+        got = []
         for (key, x, width), cai in zip(given, cais):
             if not _on_engine_device(eng, x):
                 raise TypeError(f"q_values: `{key}` is not an array in the memory of the engine's device")
-            if cai["typestr"][1:] != "f4":
-                lib = sys.modules.get(type(x).__module__.partition(".")[0])
-                x = x.to(getattr(lib, "float32", "float32"))
-                cai = _cai(x)
-            got = _cai_field(cai, width, 4)
-            if got is None:
-                x = x.contiguous()
-                got = _cai_field(_cai(x), width, 4)
-            keep.append(x)
-            fields.append((got[0], got[2]))
-            rows.append(got[1])
+            got.append(_read_input(eng, x, width, "f4", cai))
+        rows = [n for _, _, n, _ in got]
         if len(set(rows)) != 1:
             raise ValueError(f"q_values: observations and actions disagree on the number of rows: {rows}")
         n = rows[0]
         out, q_ptr, q_ld, q_ns, out_rows = _critic_major_out(eng, n, out, "q_values")
-        obs_f, act_f = fields[0], (fields[1] if len(fields) > 1 else (0, a))
-        eng.q_values_device(obs_f[0], obs_f[1], act_f[0], act_f[1], n, target, q_ptr, q_ld, q_ns,
-                            _producer_stream(keep[0], eng.cfg.device_id))
+        (keep, obs_ptr, _, obs_ld), (_, act_ptr, _, act_ld) = got[0], (got[1] if len(got) > 1 else (None, 0, n, a))
+        eng.q_values_device(obs_ptr, obs_ld, act_ptr, act_ld, n, target, q_ptr, q_ld, q_ns, _producer_stream(keep, eng.cfg.device_id))
         return out[:, :n] if out_rows > n else out
 
     def td_errors(self, out: Any = None):
@@ -669,7 +666,7 @@ class Agent:
         reference's counters."""
         do_actor = i % (self.engine.cfg.actor_update_delay + 1) == 0
         self.engine.step(do_actor)
-        self.engine._batch_generation = getattr(self.engine, "_batch_generation", 0) + 1      # the fused step drew a new sample
+        _bump_generation(self.engine)      # the fused step drew a new sample
         self.qnet_updates_so_far += 1
         if do_actor:
             self.actor_updates_so_far += self.engine.cfg.actor_update_delay

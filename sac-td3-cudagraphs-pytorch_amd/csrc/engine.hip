@@ -288,11 +288,13 @@ static inline bool node_on(EnqCtx& x, const char* name, double flops, double byt
   } while (0)
 
 static inline dim3 tile_grid(int tiles, int nets) { return dim3((unsigned)((tiles + 3) / 4), 1, (unsigned)nets); }
+// blocks of 256 threads at `cpt` chunks per thread
+static inline unsigned cpt_blocks(long chunks, int cpt) { return (unsigned)((chunks + 256L * cpt - 1) / (256L * cpt)); }
 
 // one float4 chunk per thread while that still fills the chip; GATHER_CPT chunks (loads in flight) per thread beyond
 static unsigned gather_blocks(long chunks) {
   const long one = (chunks + 255) / 256;
-  return (unsigned)(one <= 4096 ? one : (chunks + 256L * GATHER_CPT - 1) / (256L * GATHER_CPT));
+  return one <= 4096 ? (unsigned)one : cpt_blocks(chunks, GATHER_CPT);
 }
 static GatherArgs gather_args(sactd3_engine* e, const float* ring, int identity_len, int slot = 0, int ctr_add = 0) {
   GatherArgs g{};
@@ -1765,20 +1767,50 @@ int sactd3_load_batch(sactd3_engine* e, const float* obs, const float* act, cons
 }
 
 // ---- the device boundary: the caller's five arrays are already in this device's memory (include/sactd3.h)
+// THE rule for a caller's pointer, for every entry point from here on: device memory of the engine's device
+static int device_ptr_check(sactd3_engine* e, const void* p, const char* what, const char* name) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
+    (void)hipGetLastError();
+    e->err = std::string(what) + ": `" + name + "` is not device memory of the engine's device";
+    return SACTD3_EINVAL;
+  }
+  return 0;
+}
+// one row per field of a caller's field block.  Inputs (`required`): a NULL pointer is refused; outputs: it is a field not wanted
+struct FieldRow { const void* p; int64_t ld; int width; const char* name; };
+static int field_rows_check(sactd3_engine* e, const FieldRow* rows, int count, bool required, const char* what) {
+  int wanted = 0;
+  for (const FieldRow* x = rows; x != rows + count; ++x) {
+    if (!x->p && !required) continue;
+    if (!x->p) { e->err = std::string(what) + ": `" + x->name + "` is NULL"; return SACTD3_EINVAL; }
+    ++wanted;
+    if (x->ld < x->width) { e->err = std::string(what) + ": row stride of `" + x->name + "` is below its width"; return SACTD3_EINVAL; }
+    RCCHK(device_ptr_check(e, x->p, what, x->name));
+  }
+  if (!wanted) { e->err = std::string(what) + ": all six destinations (obs, actions, rewards, next_obs, dones, index) are NULL"; return SACTD3_EINVAL; }
+  return 0;
+}
 static int fields_check(sactd3_engine* e, const sactd3_device_fields* f, const char* what) {
-  const struct { const void* p; int64_t ld; int width; const char* name; } fld[5] = {
+  const FieldRow rows[5] = {
       {f->obs, f->obs_ld, e->o, "obs"}, {f->actions, f->actions_ld, e->a, "actions"}, {f->rewards, f->rewards_ld, 1, "rewards"},
       {f->next_obs, f->next_obs_ld, e->o, "next_obs"}, {f->dones, f->dones_ld, 1, "dones"}};
-  for (const auto& x : fld) {
-    if (!x.p) { e->err = std::string(what) + ": `" + x.name + "` is NULL"; return SACTD3_EINVAL; }
-    if (x.ld < x.width) { e->err = std::string(what) + ": row stride of `" + x.name + "` is below its width"; return SACTD3_EINVAL; }
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, x.p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
-      (void)hipGetLastError();
-      e->err = std::string(what) + ": `" + x.name + "` is not device memory of the engine's device";
-      return SACTD3_EINVAL;
-    }
-  }
+  return field_rows_check(e, rows, 5, true, what);
+}
+// the *_stats getters: four host counters; or three and one the kernels keep on the device, read behind a stream sync
+static int host_stats(const sactd3_engine* e, int64_t (sactd3_engine::*stats)[4], int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = (e->*stats)[i];
+  return 0;
+}
+static int stats_with_refused(sactd3_engine* e, int64_t (sactd3_engine::*stats)[3], int DevCtl::*refused_word, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int refused = 0;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(&refused, &(e->ctl->*refused_word), sizeof(int), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 3; ++i) out[i] = (e->*stats)[i];
+  out[3] = refused;
   return 0;
 }
 static FieldSrc field_src(const sactd3_engine* e, const sactd3_device_fields* f, int64_t row0) {
@@ -1814,7 +1846,7 @@ static int launch_ingest_fields(sactd3_engine* e, const FieldSrc& src, int chunk
   e->rb_len = std::min<int64_t>(cap, e->rb_len + chunk);
   g.len_cursor = &e->ctl->rb_len; g.new_len = (int)e->rb_len; g.new_cursor = (int)e->rb_cursor;
   const long chunks = (long)chunk * e->rec4;
-  hipLaunchKernelGGL(k_rb_ingest_fields, dim3((unsigned)((chunks + 256L * FIELDS_CPT - 1) / (256L * FIELDS_CPT))), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
+  hipLaunchKernelGGL(k_rb_ingest_fields, dim3(cpt_blocks(chunks, FIELDS_CPT)), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
   HIPCHK(hipGetLastError());
   return prio_after_append(e, g.cursor, chunk);
 }
@@ -1823,7 +1855,7 @@ static int launch_batch_fields(sactd3_engine* e, const FieldSrc& src) {
   BatchFieldsArgs g{};
   g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.idx = S.idx; g.B = e->B;
   const long chunks = (long)e->B * (e->cx + e->cn + 1);      // (< B * rec4 < 2^31: create_impl)
-  hipLaunchKernelGGL(k_batch_from_fields, dim3((unsigned)((chunks + 256L * FIELDS_CPT - 1) / (256L * FIELDS_CPT))), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
+  hipLaunchKernelGGL(k_batch_from_fields, dim3(cpt_blocks(chunks, FIELDS_CPT)), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1868,11 +1900,7 @@ int sactd3_load_batch_device(sactd3_engine* e, const sactd3_device_fields* f, in
   return 0;
 }
 
-int sactd3_boundary_stats(const sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  for (int i = 0; i < 4; ++i) out[i] = e->bnd_stats[i];
-  return 0;
-}
+int sactd3_boundary_stats(const sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::bnd_stats, out); }
 
 int sactd3_read_batch(sactd3_engine* e, float* obs, float* act, float* rew, float* nobs, uint8_t* dones, int64_t* idx) {
   if (!e) return SACTD3_EINVAL;
@@ -1900,23 +1928,10 @@ int sactd3_read_batch(sactd3_engine* e, float* obs, float* act, float* rew, floa
 
 // ---- the device boundary, outwards: a batch slot / ring rows into the caller's six arrays in this device's memory (include/sactd3.h)
 static int fields_out_check(sactd3_engine* e, const sactd3_device_fields_out* f, const char* what) {
-  const struct { const void* p; int64_t ld; int width; const char* name; } fld[6] = {
+  const FieldRow rows[6] = {
       {f->obs, f->obs_ld, e->o, "obs"}, {f->actions, f->actions_ld, e->a, "actions"}, {f->rewards, f->rewards_ld, 1, "rewards"},
       {f->next_obs, f->next_obs_ld, e->o, "next_obs"}, {f->dones, f->dones_ld, 1, "dones"}, {f->index, f->index_ld, 1, "index"}};
-  int wanted = 0;
-  for (const auto& x : fld) {
-    if (!x.p) continue;
-    ++wanted;
-    if (x.ld < x.width) { e->err = std::string(what) + ": row stride of `" + x.name + "` is below its width"; return SACTD3_EINVAL; }
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, x.p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
-      (void)hipGetLastError();
-      e->err = std::string(what) + ": `" + x.name + "` is not device memory of the engine's device";
-      return SACTD3_EINVAL;
-    }
-  }
-  if (!wanted) { e->err = std::string(what) + ": all six destinations (obs, actions, rewards, next_obs, dones, index) are NULL"; return SACTD3_EINVAL; }
-  return 0;
+  return field_rows_check(e, rows, 6, false, what);
 }
 static FieldDst field_dst(const sactd3_engine* e, const sactd3_device_fields_out* f, int64_t row0) {
   FieldDst d{};
@@ -1932,7 +1947,7 @@ static int launch_batch_out(sactd3_engine* e, const FieldDst& dst) {
   const sactd3_engine::BatchSlot& S = e->bs[e->cur_slot];      // the slot sactd3_read_batch reports
   const BatchOutArgs g{(const float4*)S.X, (const float4*)S.Xn, S.rew, S.done, S.idx, e->B};
   const long chunks = (long)e->B * (e->cx + e->cn + 1);      // (< B * rec4 < 2^31: create_impl)
-  hipLaunchKernelGGL(k_batch_to_fields, dim3((unsigned)((chunks + 256L * TOFIELDS_CPT - 1) / (256L * TOFIELDS_CPT))), dim3(256), 0, e->stream, dst, g);
+  hipLaunchKernelGGL(k_batch_to_fields, dim3(cpt_blocks(chunks, TOFIELDS_CPT)), dim3(256), 0, e->stream, dst, g);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1978,13 +1993,7 @@ int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx
   if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "rb_read_rows_device: unknown flag");
   if (idx_ld < 1) return e->fail(SACTD3_EINVAL, "rb_read_rows_device: row stride of `idx` is below its width");
   RCCHK(fields_out_check(e, f, "rb_read_rows_device"));
-  {
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, idx) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
-      (void)hipGetLastError();
-      return e->fail(SACTD3_EINVAL, "rb_read_rows_device: `idx` is not device memory of the engine's device");
-    }
-  }
+  RCCHK(device_ptr_check(e, idx, "rb_read_rows_device", "idx"));
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_read_rows_device: buffer is empty");
   const hipStream_t consumer = (hipStream_t)consumer_stream;
   const int64_t per_launch = ((1ll << 31) - 1) / e->rec4;
@@ -1999,28 +2008,10 @@ int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx
   return 0;
 }
 
-int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  int refused = 0;
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(&refused, &e->ctl->readout_refused, sizeof(int), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 3; ++i) out[i] = e->ro_stats[i];
-  out[3] = refused;
-  return 0;
-}
+int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]) { return stats_with_refused(e, &sactd3_engine::ro_stats, &DevCtl::readout_refused, out); }
 
 // ---- training on caller-chosen ring rows with loss weights, TD errors out (include/sactd3.h): what closes a prioritised sampler's loop
 // on the device.  (Its launches stand at the end of this file, see launch_ctail_nn_w.)
-static int device_ptr_check(sactd3_engine* e, const void* p, const char* what, const char* name) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
-    (void)hipGetLastError();
-    e->err = std::string(what) + ": `" + name + "` is not device memory of the engine's device";
-    return SACTD3_EINVAL;
-  }
-  return 0;
-}
 static int slot_weights_alloc(sactd3_engine* e) {      // (never zeroed: both staging kernels write all B entries before anything reads them)
   return e->bs[0].w ? 0 : dalloc(e, &e->bs[0].w, (size_t)e->B, false);
 }
@@ -2090,16 +2081,7 @@ int sactd3_td_errors_device(sactd3_engine* e, float* td, int64_t td_ld, int64_t 
   return 0;
 }
 
-int sactd3_priority_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  int refused = 0;
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(&refused, &e->ctl->priority_refused, sizeof(int), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 3; ++i) out[i] = e->prio_stats[i];
-  out[3] = refused;
-  return 0;
-}
+int sactd3_priority_stats(sactd3_engine* e, int64_t out[4]) { return stats_with_refused(e, &sactd3_engine::prio_stats, &DevCtl::priority_refused, out); }
 
 int sactd3_rb_fill_synthetic(sactd3_engine* e, int64_t n, uint64_t seed) {
   if (!e) return SACTD3_EINVAL;
@@ -2468,10 +2450,10 @@ int sactd3_predict_end(sactd3_engine* e, float* actions) {
   return 0;
 }
 
-static int launch_obs_pack(sactd3_engine* e, const float* obs, int64_t obs_ld, int n) {
-  const ObsFieldArgs g{(float4*)e->p_x, n, e->ldo / 4};
+static int launch_obs_pack(sactd3_engine* e, const float* obs, int64_t obs_ld, float* x, int n) {      // x: n packed rows at ldo
+  const ObsFieldArgs g{(float4*)x, n, e->ldo / 4};
   const long chunks = (long)n * g.c4;
-  hipLaunchKernelGGL(k_obs_from_field, dim3((unsigned)((chunks + 256L * OBS_CPT - 1) / (256L * OBS_CPT))), dim3(256), 0, e->stream, obs, (long)obs_ld, e->o, g);
+  hipLaunchKernelGGL(k_obs_from_field, dim3(cpt_blocks(chunks, OBS_CPT)), dim3(256), 0, e->stream, obs, (long)obs_ld, e->o, g);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2497,19 +2479,13 @@ int sactd3_predict_device(sactd3_engine* e, const float* obs, int64_t obs_ld, in
   if (obs_ld < e->o) return e->fail(SACTD3_EINVAL, "predict_device: row stride of `obs` is below its width");
   if (actions_ld < e->a) return e->fail(SACTD3_EINVAL, "predict_device: row stride of `actions` is below its width");
   if ((int64_t)n * std::max(e->ldo, e->a4) / 4 >= (1ll << 31)) return e->fail(SACTD3_EINVAL, "predict_device: too many rows for one launch");
-  for (const void* ptr : {(const void*)obs, (const void*)actions}) {
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
-      (void)hipGetLastError();
-      return e->fail(SACTD3_EINVAL, ptr == (const void*)obs ? "predict_device: `obs` is not device memory of the engine's device"
-                                                            : "predict_device: `actions` is not device memory of the engine's device");
-    }
-  }
+  RCCHK(device_ptr_check(e, obs, "predict_device", "obs"));
+  RCCHK(device_ptr_check(e, actions, "predict_device", "actions"));
   // (it shares predict_ctr and eps[SITE_PREDICT] with a call on the acting stream)
   if (e->act_inflight) return e->fail(SACTD3_ESTATE, "predict_device: an acting call is in flight (sactd3_predict_end first)");
   const hipStream_t caller = (hipStream_t)caller_stream;
   RCCHK(src_order_begin(e, caller, flags));
-  RCCHK(launch_obs_pack(e, obs, obs_ld, n));
+  RCCHK(launch_obs_pack(e, obs, obs_ld, e->p_x, n));
   if (e->predict_dev_graphs.empty()) e->predict_dev_graphs.assign(2 * (size_t)(e->maxn + 1), nullptr);
   RCCHK(run_graph_slot(e, &e->predict_dev_graphs[(size_t)(explore ? 1 : 0) * (e->maxn + 1) + n], nullptr,
                        [&](EnqCtx& x) { return enqueue_predict(x, n, explore, true); }));
@@ -2524,11 +2500,7 @@ int sactd3_predict_device(sactd3_engine* e, const float* obs, int64_t obs_ld, in
   return 0;
 }
 
-int sactd3_predict_device_stats(const sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  for (int i = 0; i < 4; ++i) out[i] = e->pdev_stats[i];
-  return 0;
-}
+int sactd3_predict_device_stats(const sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::pdev_stats, out); }
 
 // ---- scoring caller-supplied state-action pairs: Agent.batched_qf / pi of the reference (agents/agent.py:146-163) as a read path.
 // A forward-only pass of the twin critics (online or target arena) on Q_CHUNK rows at a time, eager launches on the learner stream:
@@ -2553,7 +2525,7 @@ static int q_scratch(sactd3_engine* e, bool policy) {      // (never zeroed: eve
 static int launch_sa_pack(sactd3_engine* e, const float* obs, int64_t obs_ld, const float* act, int64_t act_ld, int m) {
   const SaFieldArgs g{(float4*)e->qs_sa, m, e->ldc / 4};
   const long chunks = (long)m * g.c4;
-  hipLaunchKernelGGL(k_sa_from_fields, dim3((unsigned)((chunks + 256L * SA_CPT - 1) / (256L * SA_CPT))), dim3(256), 0, e->stream,
+  hipLaunchKernelGGL(k_sa_from_fields, dim3(cpt_blocks(chunks, SA_CPT)), dim3(256), 0, e->stream,
                      obs, (long)obs_ld, act, (long)act_ld, e->o, e->a, g);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2576,10 +2548,7 @@ static int enqueue_qvalues(sactd3_engine* e, const float* obs, int64_t obs_ld, c
     const int m = (int)std::min<int64_t>(Q_CHUNK, n - row0);
     const float* obs_c = obs + row0 * obs_ld;
     if (!act) {      // pi(s): the online actor's exploit action, what sactd3_predict(explore = 0) returns
-      const ObsFieldArgs og{(float4*)e->qs_x, m, e->ldo / 4};
-      const long chunks = (long)m * og.c4;
-      hipLaunchKernelGGL(k_obs_from_field, dim3((unsigned)((chunks + 256L * OBS_CPT - 1) / (256L * OBS_CPT))), dim3(256), 0, e->stream, obs_c, (long)obs_ld, e->o, og);
-      HIPCHK(hipGetLastError());
+      RCCHK(launch_obs_pack(e, obs_c, obs_ld, e->qs_x, m));
       const TrunkGrp ga{e->qs_x, e->Pa, e->qs_az1, e->qs_az2, nullptr, nullptr, nullptr};
       RCCHK(enqueue_trunk(x, e->ldo, e->o, m, e->La, 0, 1, 1, &ga, tk));
       // (exploit mode draws nothing: the tail reads neither the draw buffer nor -- for its result -- the counter, and ticks nothing)
@@ -2609,16 +2578,9 @@ int sactd3_qvalues_device(sactd3_engine* e, const float* obs, int64_t obs_ld, co
   if (obs_ld < e->o) return e->fail(SACTD3_EINVAL, "qvalues_device: row stride of `obs` is below its width");
   if (actions && actions_ld < e->a) return e->fail(SACTD3_EINVAL, "qvalues_device: row stride of `actions` is below its width");
   if (q_ld < 1 || q_ns < 1) return e->fail(SACTD3_EINVAL, "qvalues_device: strides of `q` are below its width");
-  const struct { const void* p; const char* name; } ptrs[3] = {{obs, "obs"}, {actions, "actions"}, {q, "q"}};
-  for (const auto& a : ptrs) {
-    if (!a.p) continue;      // (actions: the policy form)
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, a.p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device_id) {
-      (void)hipGetLastError();
-      e->err = std::string("qvalues_device: `") + a.name + "` is not device memory of the engine's device";
-      return SACTD3_EINVAL;
-    }
-  }
+  RCCHK(device_ptr_check(e, obs, "qvalues_device", "obs"));
+  if (actions) RCCHK(device_ptr_check(e, actions, "qvalues_device", "actions"));      // (NULL: the policy form)
+  RCCHK(device_ptr_check(e, q, "qvalues_device", "q"));
   const hipStream_t caller = (hipStream_t)caller_stream;
   RCCHK(src_order_begin(e, caller, flags));
   RCCHK(enqueue_qvalues(e, obs, obs_ld, actions, actions_ld, n, which, q, q_ld, q_ns));
@@ -2654,17 +2616,9 @@ int sactd3_qvalues(sactd3_engine* e, const float* obs, const float* actions, int
   return 0;
 }
 
-int sactd3_qvalues_stats(const sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  for (int i = 0; i < 4; ++i) out[i] = e->q_stats[i];
-  return 0;
-}
+int sactd3_qvalues_stats(const sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::q_stats, out); }
 
-int sactd3_acting_stats(const sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  for (int i = 0; i < 4; ++i) out[i] = e->act_stats[i];
-  return 0;
-}
+int sactd3_acting_stats(const sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::act_stats, out); }
 
 int sactd3_read_metrics(sactd3_engine* e, float out[SACTD3_NUM_METRICS]) {
   if (!e || !out) return SACTD3_EINVAL;
@@ -2805,7 +2759,7 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
     }
     // the pack / unpack kernels of sactd3_predict_device on max_envs rows: observations read from the ring's records (the s columns,
     // row stride = the record), actions written to the acting scratch p_z1 (row stride = its 256 columns; the next trunk overwrites it)
-    if (!strcmp(kernel, "obs_from_field")) return launch_obs_pack(e, e->ring, e->rec_f, (int)std::min<int64_t>(e->maxn, e->cfg.rb_capacity));
+    if (!strcmp(kernel, "obs_from_field")) return launch_obs_pack(e, e->ring, e->rec_f, e->p_x, (int)std::min<int64_t>(e->maxn, e->cfg.rb_capacity));
     if (!strcmp(kernel, "act_to_field")) return launch_act_unpack(e, e->p_z1, HID, e->maxn);
     if (!strcmp(kernel, "batch_to_fields") || !strcmp(kernel, "rows_to_fields")) {
       // the read-out kernels on batch_size rows, written into the engine's own staging slab as six strided fields (the mirror image

@@ -24,6 +24,15 @@ def _fp(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_F)
 
 
+def _vp(address) -> C.c_void_p:
+    """a device address or stream handle the caller holds as an integer, as the C ABI takes it (0 = NULL)"""
+    return C.c_void_p(int(address) or None)
+
+
+def _flag(bit: int, on) -> int:
+    return bit if on else 0
+
+
 @dataclass
 class Config:
     """Mirror of `sactd3_config`; defaults = tasks/defaults/sac.yml of the reference."""
@@ -126,6 +135,12 @@ class Engine:
             raise EngineError(f"libsactd3_hip error {rc}: {msg.decode() if msg else '?'}")
         return rc
 
+    def _stats(self, fn, names) -> Dict[str, int]:
+        """the four int64 counters a sactd3_*_stats call fills, under `names`"""
+        out = (C.c_int64 * 4)()
+        self._ck(fn(self._h, out))
+        return {k: int(v) for k, v in zip(names, out)}
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self.lib.sactd3_destroy(self._h)
@@ -221,19 +236,15 @@ class Engine:
         obs, actions, rewards, next_obs, dones (bytes) -- are in this device's memory.  `ordered`: the engine orders its read against
         `producer_stream` (a hipStream_t as an integer; 0 = the default stream) on the GPU; otherwise the caller has synchronised and
         keeps the arrays untouched until sync()."""
-        self._ck(self.lib.sactd3_rb_extend_fields_device(self._h, self._fields(fields), int(n), C.c_void_p(int(producer_stream) or None),
-                                                         _lib.SRC_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_rb_extend_fields_device(self._h, self._fields(fields), int(n), _vp(producer_stream), _flag(_lib.SRC_ORDERED, ordered)))
 
     def load_batch_device(self, fields, n: int, producer_stream: int = 0, ordered: bool = True) -> None:
         """sactd3_load_batch_device: a caller-owned device batch (arguments as rb_extend_fields_device, n == batch_size) into the batch slot."""
-        self._ck(self.lib.sactd3_load_batch_device(self._h, self._fields(fields), int(n), C.c_void_p(int(producer_stream) or None),
-                                                   _lib.SRC_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_load_batch_device(self._h, self._fields(fields), int(n), _vp(producer_stream), _flag(_lib.SRC_ORDERED, ordered)))
 
     def boundary_stats(self) -> Dict[str, int]:
         """host counters of the device boundary (sactd3_boundary_stats)"""
-        out = (C.c_int64 * 4)()
-        self._ck(self.lib.sactd3_boundary_stats(self._h, out))
-        return dict(device_extends=int(out[0]), device_rows=int(out[1]), device_batches=int(out[2]), ordered_calls=int(out[3]))
+        return self._stats(self.lib.sactd3_boundary_stats, ("device_extends", "device_rows", "device_batches", "ordered_calls"))
 
     def _fields_out(self, fields):
         dfo = self._dfo
@@ -247,21 +258,18 @@ class Engine:
         launch on the engine's stream, no host wait.  `ordered`: the engine orders its write against `consumer_stream` (a hipStream_t
         as an integer; 0 = the default stream) on the GPU and that stream may read the arrays at once; otherwise the caller has
         synchronised and calls sync() before it reads."""
-        self._ck(self.lib.sactd3_read_batch_device(self._h, self._fields_out(fields), C.c_void_p(int(consumer_stream) or None),
-                                                   _lib.DST_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_read_batch_device(self._h, self._fields_out(fields), _vp(consumer_stream), _flag(_lib.DST_ORDERED, ordered)))
 
     def rb_read_rows_device(self, idx_ptr: int, idx_ld: int, n: int, fields, consumer_stream: int = 0, ordered: bool = True) -> None:
         """sactd3_rb_read_rows_device: n ring records chosen by a device int64 array (`idx_ptr`, stride `idx_ld` elements) into `fields`
         (as read_batch_device).  An index outside [0, rb_len) yields a zero row with flag 0, its index echoed, and is counted in
         readout_stats()["rows_refused"]."""
-        self._ck(self.lib.sactd3_rb_read_rows_device(self._h, C.c_void_p(int(idx_ptr) or None), int(idx_ld), int(n), self._fields_out(fields),
-                                                     C.c_void_p(int(consumer_stream) or None), _lib.DST_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_rb_read_rows_device(self._h, _vp(idx_ptr), int(idx_ld), int(n), self._fields_out(fields),
+                                                     _vp(consumer_stream), _flag(_lib.DST_ORDERED, ordered)))
 
     def readout_stats(self) -> Dict[str, int]:
         """counters of the outward device boundary (sactd3_readout_stats; waits for the engine's stream: the last one lives on the device)"""
-        out = (C.c_int64 * 4)()
-        self._ck(self.lib.sactd3_readout_stats(self._h, out))
-        return dict(batch_readouts=int(out[0]), row_readouts=int(out[1]), rows_requested=int(out[2]), rows_refused=int(out[3]))
+        return self._stats(self.lib.sactd3_readout_stats, ("batch_readouts", "row_readouts", "rows_requested", "rows_refused"))
 
     def rb_len(self) -> int:
         return int(self._ck(self.lib.sactd3_rb_len(self._h)))
@@ -368,7 +376,7 @@ class Engine:
         otherwise they wait for the learner stream only behind a call that writes the actor (include/sactd3.h)."""
         obs = np.asarray(obs)
         n = obs.size // self.cfg.ob_dim
-        flags = _lib.ACT_AFTER_ALL if after_all else 0
+        flags = _flag(_lib.ACT_AFTER_ALL, after_all)
         if 0 < n <= self._st_n and obs.size == n * self.cfg.ob_dim:
             self._st[5][:n] = obs.reshape(n, -1)
             self._ck(self.lib.sactd3_predict_begin(self._h, self._st_p[5], n, 1 if explore else 0, flags))
@@ -397,15 +405,12 @@ class Engine:
         updates issued so far, no host wait.  `ordered`: the engine orders its read and the caller's next use of both arrays against
         `caller_stream` (a hipStream_t as an integer; 0 = the default stream) on the GPU; otherwise the caller has synchronised and
         leaves both arrays alone until sync()."""
-        self._ck(self.lib.sactd3_predict_device(self._h, C.c_void_p(int(obs_ptr) or None), int(obs_ld), int(n), 1 if explore else 0,
-                                                C.c_void_p(int(out_ptr) or None), int(out_ld), C.c_void_p(int(caller_stream) or None),
-                                                _lib.SRC_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_predict_device(self._h, _vp(obs_ptr), int(obs_ld), int(n), 1 if explore else 0,
+                                                _vp(out_ptr), int(out_ld), _vp(caller_stream), _flag(_lib.SRC_ORDERED, ordered)))
 
     def predict_device_stats(self) -> Dict[str, int]:
         """host counters of the device acting route (sactd3_predict_device_stats)"""
-        out = (C.c_int64 * 4)()
-        self._ck(self.lib.sactd3_predict_device_stats(self._h, out))
-        return dict(calls=int(out[0]), rows=int(out[1]), ordered_calls=int(out[2]), multi_block_tails=int(out[3]))
+        return self._stats(self.lib.sactd3_predict_device_stats, ("calls", "rows", "ordered_calls", "multi_block_tails"))
 
     def q_values(self, obs, act=None, target: bool = False) -> np.ndarray:
         """sactd3_qvalues: Q_k(obs_i, act_i) of the twin critics -- the target pair with `target` -- for host rows -> [2, n] float32.
@@ -428,43 +433,36 @@ class Engine:
         value of row i goes to the float32 at `q_ptr` + 4 (k `q_ns` + i `q_ld`).  Asynchronous on the engine's stream behind the updates
         issued so far, no host wait, invisible to training.  `ordered`: the engine orders its reads and its write against `stream` (a
         hipStream_t as an integer; 0 = the default stream) on the GPU; otherwise the caller has synchronised and calls sync()."""
-        self._ck(self.lib.sactd3_qvalues_device(self._h, C.c_void_p(int(obs_ptr) or None), int(obs_ld), C.c_void_p(int(act_ptr) or None),
-                                                int(act_ld), int(n), _lib.Q_TARGET if target else _lib.Q_ONLINE,
-                                                C.c_void_p(int(q_ptr) or None), int(q_ld), int(q_ns), C.c_void_p(int(stream) or None),
-                                                _lib.SRC_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_qvalues_device(self._h, _vp(obs_ptr), int(obs_ld), _vp(act_ptr), int(act_ld), int(n),
+                                                _lib.Q_TARGET if target else _lib.Q_ONLINE, _vp(q_ptr), int(q_ld), int(q_ns), _vp(stream),
+                                                _flag(_lib.SRC_ORDERED, ordered)))
 
     def qvalues_stats(self) -> Dict[str, int]:
         """host counters of the scoring route (sactd3_qvalues_stats)"""
-        out = (C.c_int64 * 4)()
-        self._ck(self.lib.sactd3_qvalues_stats(self._h, out))
-        return dict(calls=int(out[0]), rows=int(out[1]), ordered_calls=int(out[2]), policy_calls=int(out[3]))
+        return self._stats(self.lib.sactd3_qvalues_stats, ("calls", "rows", "ordered_calls", "policy_calls"))
 
     def rb_sample_indices_device(self, idx_ptr: int, idx_ld: int, w_ptr: int, w_ld: int, n: int, stream: int = 0, ordered: bool = True) -> None:
         """sactd3_rb_sample_indices_device: fill the batch slot with the ring records a device int64 array names (`idx_ptr`, stride
         `idx_ld` elements; n == batch_size) and the slot's loss weights from a device float32 array (`w_ptr`, `w_ld`; address 0: all 1).
         One launch, no host wait.  An index outside [0, rb_len) gives a zero record with slot index -1 and weight 0; a weight that is
         negative, NaN or infinite is staged as 0; both are counted in priority_stats()["rows_refused"]."""
-        self._ck(self.lib.sactd3_rb_sample_indices_device(self._h, C.c_void_p(int(idx_ptr) or None), int(idx_ld), C.c_void_p(int(w_ptr) or None),
-                                                          int(w_ld), int(n), C.c_void_p(int(stream) or None), _lib.SRC_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_rb_sample_indices_device(self._h, _vp(idx_ptr), int(idx_ld), _vp(w_ptr), int(w_ld), int(n), _vp(stream),
+                                                          _flag(_lib.SRC_ORDERED, ordered)))
 
     def batch_weights_device(self, w_ptr: int, w_ld: int, n: int, stream: int = 0, ordered: bool = True) -> None:
         """sactd3_batch_weights_device: loss weights (device float32, `w_ptr` / `w_ld`, n == batch_size) for whatever the batch slot
         holds; address 0 drops the weights.  While the slot carries weights update_qnets() minimises (1 / B) sum_i w_i err_i^2."""
-        self._ck(self.lib.sactd3_batch_weights_device(self._h, C.c_void_p(int(w_ptr) or None), int(w_ld), int(n),
-                                                      C.c_void_p(int(stream) or None), _lib.SRC_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_batch_weights_device(self._h, _vp(w_ptr), int(w_ld), int(n), _vp(stream), _flag(_lib.SRC_ORDERED, ordered)))
 
     def td_errors_device(self, td_ptr: int, td_ld: int, td_ns: int, stream: int = 0, ordered: bool = True) -> None:
         """sactd3_td_errors_device: Q_k(s_i, a_i) - y_i of the most recent critic update to the float32 at `td_ptr` + 4 (k `td_ns` +
         i `td_ld`), in this device's memory.  One launch, no host wait; EngineError (SACTD3_ESTATE) when no critic update has run on
         the rows now in the batch slot."""
-        self._ck(self.lib.sactd3_td_errors_device(self._h, C.c_void_p(int(td_ptr) or None), int(td_ld), int(td_ns),
-                                                  C.c_void_p(int(stream) or None), _lib.DST_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_td_errors_device(self._h, _vp(td_ptr), int(td_ld), int(td_ns), _vp(stream), _flag(_lib.DST_ORDERED, ordered)))
 
     def priority_stats(self) -> Dict[str, int]:
         """counters of the prioritised route (sactd3_priority_stats; waits for the engine's stream: the last one lives on the device)"""
-        out = (C.c_int64 * 4)()
-        self._ck(self.lib.sactd3_priority_stats(self._h, out))
-        return dict(index_stagings=int(out[0]), weight_stagings=int(out[1]), td_readouts=int(out[2]), rows_refused=int(out[3]))
+        return self._stats(self.lib.sactd3_priority_stats, ("index_stagings", "weight_stagings", "td_readouts", "rows_refused"))
 
     # -- prioritised replay the engine owns (include/sactd3.h: sactd3_prio_*)
     def prio_enable(self, alpha: float = 0.6, eps: float = 1e-6) -> None:
@@ -492,21 +490,16 @@ class Engine:
     def prio_update_device(self, idx_ptr: int, idx_ld: int, prio_ptr: int, prio_ld: int, n: int, stream: int = 0, ordered: bool = True) -> None:
         """sactd3_prio_update_device: unscaled priorities (device float32 at `prio_ptr`, stride `prio_ld`) for the ring slots a device
         int64 array names; a bad index or priority is refused on the device and counted in prio_stats()["rows_refused"]."""
-        self._ck(self.lib.sactd3_prio_update_device(self._h, C.c_void_p(int(idx_ptr) or None), int(idx_ld), C.c_void_p(int(prio_ptr) or None),
-                                                    int(prio_ld), int(n), C.c_void_p(int(stream) or None), _lib.SRC_ORDERED if ordered else 0))
+        self._ck(self.lib.sactd3_prio_update_device(self._h, _vp(idx_ptr), int(idx_ld), _vp(prio_ptr), int(prio_ld), int(n), _vp(stream),
+                                                    _flag(_lib.SRC_ORDERED, ordered)))
 
     def prio_stats(self) -> Dict[str, int]:
         """counters of the engine-owned priorities (sactd3_prio_stats; waits for the engine's stream)"""
-        out = (C.c_int64 * 4)()
-        self._ck(self.lib.sactd3_prio_stats(self._h, out))
-        return dict(samples=int(out[0]), write_backs=int(out[1]), rows_refused=int(out[2]), rows_entered_at_max=int(out[3]))
+        return self._stats(self.lib.sactd3_prio_stats, ("samples", "write_backs", "rows_refused", "rows_entered_at_max"))
 
     def acting_stats(self) -> Dict[str, int]:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
-        out = (C.c_int64 * 4)()
-        self._ck(self.lib.sactd3_acting_stats(self._h, out))
-        return dict(begun=int(out[0]), begin_waited_for_learner=int(out[1]), learner_waited_for_acting=int(out[2]),
-                    ended_by_spin=int(out[3]))
+        return self._stats(self.lib.sactd3_acting_stats, ("begun", "begin_waited_for_learner", "learner_waited_for_acting", "ended_by_spin"))
 
     def read_metrics(self) -> Dict[str, float]:
         m = np.empty(_lib.NUM_METRICS, np.float32)

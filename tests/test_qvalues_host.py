@@ -143,6 +143,8 @@ def test_without_torch_the_caller_brings_out(monkeypatch):
     monkeypatch.setitem(sys.modules, "torch", None)                        # `import torch` now raises ImportError
     with pytest.raises(TypeError, match="torch"):
         mirror().q_values({"observations": FakeDeviceArray((8, O))})
+    with pytest.raises(TypeError, match="without torch the caller passes `out`"):      # a read-out that has to allocate says the same
+        agent_mod._device_outputs(RecordingEngine(), 8)
 
 
 def test_host_arrays_take_the_host_call_and_come_back_as_numpy():
