@@ -284,6 +284,57 @@ int sactd3_prio_update_device(sactd3_engine* e, const int64_t* idx, int64_t idx_
 /* [sync] out = {prioritised samples, write-backs, rows a write-back refused (counted on the device), rows that entered at the maximum
  * priority (sactd3_prio_enable's included)} */
 int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]);
+
+/* ---- n-step returns staged in the engine: the batch slot receives, per row, a chain of up to `steps` consecutive ring rows of one env,
+ * gathered and summed by ONE launch (k_batch_from_index_nstep), in place of 2n + 1 read-out launches, torch arithmetic and a
+ * sactd3_load_batch_device.  No critic kernel changes: every form of the Bellman target is rw + (1 - dn) * gamma * q', so staging
+ * rw = sum_j gamma^j r_j and dn = 1 - (1 - d_last) * gamma^(k-1) makes each of them compute the k-step target.
+ * Inputs per batch row: a start slot i0; `steps` in [1, 16]; `stride` >= 1 = the rows appended per env step (the env count, or for
+ *   shared replay the all-gathered row count); the host's ring state at the call: len, cursor, cap (capacity).
+ * Age and chain slots: age(i) = i while len < cap, else (i - cursor) mod cap.  slot_j = (i0 + j * stride) mod cap.  slot_j exists iff
+ *   age(i0) + j * stride < len.  This is right for any cap, also when cap % stride != 0, and makes the newest `stride` rows
+ *   successor-less without looking at data.
+ * Link j -> j+1 holds iff all three are true: slot_{j+1} exists; the flag float of slot_j is 0; the first ob_dim floats of the s' field
+ *   of slot_j equal, as 32-bit patterns, the first ob_dim floats of slot_{j+1}'s record (the action columns and zero pad that share the
+ *   last chunk are not compared; -0.0 and +0.0 differ; equal NaN patterns are equal).  This is "row t+1 continues row t" without a new
+ *   ring field: Rollout / DeviceRollout store the true final observation as next_observations of a truncated row, and the env's
+ *   following row starts from the reset observation.
+ * Chain length: k = 1 + the number of leading links that hold, 1 <= k <= steps.
+ * Staged into batch slot 0: X = the [s|a] chunks of slot_0, as k_batch_from_index writes them; Xn = the s' chunks of slot_{k-1}; the
+ *   slot index = i0; rew = R_{k-1} with R_0 = r_0, G_0 = 1, G_j = G_{j-1} * gamma, R_j = R_{j-1} + G_j * r_j -- each operation one
+ *   correctly rounded fp32 operation in this order, no fma contraction, so a float32 numpy loop gives the same bits;
+ *   done = 1 - (1 - d_{k-1}) * G_{k-1}, which is d_0 exactly when k = 1.  Weights exactly as sactd3_rb_sample_indices_device stages them.
+ * Two per-slot int32 arrays, made at the first n-step call (an engine that never makes one holds nothing more than before):
+ *   nstep_k[b] = k and nstep_last[b] = slot_{k-1}; read with sactd3_nstep_info_device.
+ * Refused rows: a start index outside [0, len) is refused as k_batch_from_index refuses it -- a zero record, slot -1, weight 0, k = 0,
+ *   last = -1, counted -- and never becomes an address; nor does a chain slot that does not exist.  A bad weight (negative, NaN,
+ *   infinite) is stored as 0 and the row counted as refused, its chain staged all the same, as sactd3_rb_sample_indices_device does.
+ *   An accepted row whose chain was cut short (k < steps) is counted too, once per row and call, on the device.
+ * For SAC this is the plain n-step target R + gamma^k (min Q' - alpha logp'): the entropy terms of the intermediate steps are NOT added.
+ * Read-outs: sactd3_read_batch / _device are unchanged; on an n-step slot they report rewards = the n-step return, next_observations =
+ *   the bootstrap state s' of slot_{k-1}, and dones = (mask != 0).  For k > 1 that `dones` is NOT the termination flag (the mask
+ *   1 - (1 - d) gamma^(k-1) is non-zero for every chain longer than one row); the mask is exactly 1.0 iff the chain's last row terminated.
+ * "Slot 0 is an n-step slot" is host state next to the weighted flag: the three staging calls set it; every other refill of the slot and
+ *   every sactd3_step* clears it (the fused paths keep their own 1-step uniform gather inside their graphs: n-step there is out of
+ *   scope).  The three calls break the run-ahead chain and make slot 0 current, exactly as their 1-step counterparts do. */
+/* sactd3_rb_sample_indices_device with the chain: same pointer, stride, flag and error rules; in addition SACTD3_EINVAL for `steps`
+ * outside [1, 16] or `stride` < 1.  One launch.  With steps == 1 it leaves, bit for bit, what sactd3_rb_sample_indices_device leaves. */
+int sactd3_rb_sample_nstep_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n, int steps,
+                                  int stride, void* caller_stream, int flags /* SACTD3_SRC_ORDERED */);
+/* The engine's own uniform draw: the start slots are those sactd3_rb_sample would draw at the same sample counter
+ * (philox_index(seed, sample_ctr, b, len)); the counter advances once, as it does there.  The slot carries no weights. */
+int sactd3_rb_sample_nstep(sactd3_engine* e, int steps, int stride);
+/* sactd3_rb_sample_prioritized with the chain: k_prio_draw, k_prio_weights, then the n-step staging kernel in place of
+ * k_batch_from_index.  Same preconditions.  sactd3_prio_update_from_td afterwards writes to the START slots, unchanged. */
+int sactd3_rb_sample_prioritized_nstep(sactd3_engine* e, float beta, int steps, int stride);
+/* k[b * k_ld] = nstep_k[b], last[b * last_ld] = nstep_last[b], DEVICE int32 arrays in the memory of the engine's device; either pointer
+ * may be NULL, but not both.  One launch on the learner stream; flags & SACTD3_DST_ORDERED orders the arrays against `caller_stream` as
+ * sactd3_td_errors_device does.  SACTD3_ESTATE unless batch slot 0 was filled by an n-step call and not refilled since. */
+int sactd3_nstep_info_device(sactd3_engine* e, int32_t* k, int64_t k_ld, int32_t* last, int64_t last_ld, void* caller_stream,
+                             int flags /* SACTD3_DST_ORDERED */);
+/* [sync] out = {n-step stagings, rows staged, rows cut short (k < steps), rows refused}; the last two are counted on the device */
+int sactd3_nstep_stats(sactd3_engine* e, int64_t out[4]);
+
 /* rb.sample(batch_size) (orchestrator.py:338): uniform-with-replacement indices from the engine's
  * Philox stream + gather into the engine-owned batch slot. */
 int sactd3_rb_sample(sactd3_engine* e);
@@ -452,7 +503,9 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
  * sactd3_td_errors_device on batch_size rows: indices as for "rows_to_fields", no weights, into the batch slot; the TD errors into the
  * engine's own staging slab), "prio_sample" / "prio_update" (SACTD3_ESTATE before sactd3_prio_enable: one whole
  * sactd3_rb_sample_prioritized with beta 0.4 -- its three launches, the batch slot overwritten, the draw counter advanced -- / the
- * write-back kernel on batch_size rows, indices as for "rows_to_fields", every priority 1: those rows' priorities are overwritten). [sync] */
+ * write-back kernel on batch_size rows, indices as for "rows_to_fields", every priority 1: those rows' priorities are overwritten),
+ * "batch_from_index_nstep" (the staging kernel of sactd3_rb_sample_nstep_device on batch_size rows with steps = 3, stride = 1: indices
+ * as for "rows_to_fields", no weights, into the batch slot). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

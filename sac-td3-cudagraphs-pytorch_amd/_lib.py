@@ -36,6 +36,8 @@ SYMBOLS = [
     "sactd3_rb_sample_indices_device", "sactd3_batch_weights_device", "sactd3_td_errors_device", "sactd3_priority_stats",
     "sactd3_prio_enable", "sactd3_rb_sample_prioritized", "sactd3_prio_set_uniforms", "sactd3_prio_update_from_td", "sactd3_prio_update_device",
     "sactd3_prio_stats",
+    "sactd3_rb_sample_nstep_device", "sactd3_rb_sample_nstep", "sactd3_rb_sample_prioritized_nstep", "sactd3_nstep_info_device",
+    "sactd3_nstep_stats",
 ]
 
 
@@ -147,6 +149,11 @@ def load_library():
         "sactd3_prio_update_from_td": (C.c_int, [vp]),
         "sactd3_prio_update_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int]),
         "sactd3_prio_stats": (C.c_int, [vp, i64p]),
+        "sactd3_rb_sample_nstep_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int]),
+        "sactd3_rb_sample_nstep": (C.c_int, [vp, C.c_int, C.c_int]),
+        "sactd3_rb_sample_prioritized_nstep": (C.c_int, [vp, C.c_float, C.c_int, C.c_int]),
+        "sactd3_nstep_info_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int]),
+        "sactd3_nstep_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

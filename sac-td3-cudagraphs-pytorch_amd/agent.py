@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import sys
 from pathlib import Path
-from typing import Any, Dict, Mapping, Optional
+from typing import Any, Dict, Mapping, Optional, Tuple
 
 import numpy as np
 
@@ -324,6 +324,37 @@ class BatchHandle(dict):
                 self._cache[k] = self._cache[k].reshape(-1, 1)
         return self._cache[key]
 
+    def n_step_info(self) -> Dict[str, Any]:
+        """{"steps": int32 [B], "last_index": int32 [B]} on the engine's device, for a handle made with n_step > 1: the chain length k
+        of every row (0: the row was refused) and the ring slot of the chain's last row (-1), written by one launch ordered against
+        torch's current stream (include/sactd3.h: sactd3_nstep_info_device).  On such a handle `rewards` is the n-step return,
+        `next_observations` the state the target bootstraps from, and `dones` is (mask != 0) with mask = 1 - (1 - d_last) gamma^(k-1):
+        for k > 1 that is NOT the termination flag -- the mask is exactly 1.0 iff the chain's last row terminated.  StaleBatchError
+        when the handle is not current, RuntimeError on a handle that is not n-step."""
+        if not self._is_current():
+            raise StaleBatchError("this batch handle is older than the engine's batch slot: a later rb.sample() / staged batch replaced its rows")
+        if not getattr(self, "_n_step", False):
+            raise RuntimeError("n_step_info: this batch was not sampled with n_step > 1")
+        import torch
+        eng = self._engine
+        dev = torch.device("cuda", int(eng.cfg.device_id))
+        steps = torch.empty(int(eng.cfg.batch_size), dtype=torch.int32, device=dev)
+        last = torch.empty_like(steps)
+        eng.nstep_info_device(steps.data_ptr(), 1, last.data_ptr(), 1, _producer_stream(steps, eng.cfg.device_id))
+        return {"steps": steps, "last_index": last}
+
+
+def _n_step_args(what: str, n_step, stride) -> Tuple[int, int]:
+    """(steps, stride) of a sampling call, checked before the engine is touched"""
+    n_step = int(n_step)
+    if not 1 <= n_step <= 16:
+        raise ValueError(f"{what}: n_step must be in [1, 16], got {n_step}")
+    if n_step > 1 and stride is None:
+        raise ValueError(f"{what}: n_step > 1 needs `stride`, the rows appended per env step (the env count)")
+    if stride is not None and int(stride) < 1:
+        raise ValueError(f"{what}: stride must be at least 1, got {stride}")
+    return n_step, (1 if stride is None else int(stride))
+
 
 class ReplayBuffer:
     """TensorDictReplayBuffer(storage=LazyTensorStorage(capacity, device)) stand-in (main.py:167-171): built by
@@ -345,8 +376,10 @@ class ReplayBuffer:
         assert self._engine is not None, "replay buffer is not attached to an Agent yet"
         return self._engine
 
-    def _new_handle(self, eng: Engine) -> BatchHandle:
-        return BatchHandle(eng, _bump_generation(eng), device=self.device_batches)
+    def _new_handle(self, eng: Engine, n_step: bool = False) -> BatchHandle:
+        h = BatchHandle(eng, _bump_generation(eng), device=self.device_batches)
+        h._n_step = n_step
+        return h
 
     def extend(self, td: Mapping[str, Any]) -> None:
         """orchestrator.py:100-113: keys observations, next_observations, actions, rewards, terminations, dones."""
@@ -359,13 +392,22 @@ class ReplayBuffer:
             return
         eng.rb_extend(*[_np(x) for x in five])
 
-    def sample(self, batch_size: int) -> BatchHandle:
+    def sample(self, batch_size: int, *, n_step: int = 1, stride: Optional[int] = None) -> BatchHandle:
+        """`n_step` > 1: every drawn row starts a chain of up to n_step consecutive rows of its env (`stride` = the rows appended per
+        env step, i.e. the env count), cut where an episode ends or the ring does; the slot holds the discounted return, the last
+        row's next observation and the mask that make the critic update the n-step one, staged by one launch
+        (include/sactd3.h: sactd3_rb_sample_nstep).  For SAC the entropy terms of the intermediate steps are not added.  The start rows
+        are those sample() would draw; BatchHandle.n_step_info() gives the chain lengths."""
+        n_step, stride = _n_step_args("sample", n_step, stride)
         eng = self._need()
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
-        eng.rb_sample()
-        return self._new_handle(eng)
+        if n_step == 1:
+            eng.rb_sample()
+            return self._new_handle(eng)
+        eng.rb_sample_nstep(n_step, stride)
+        return self._new_handle(eng, True)
 
-    def sample_at(self, index, weights=None) -> BatchHandle:
+    def sample_at(self, index, weights=None, *, n_step: int = 1, stride: Optional[int] = None) -> BatchHandle:
         """sample() with the caller's rows: the ring records `index` names (batch_size ring slots: an int64 tensor on the engine's
         device, or anything torch can turn into one, as for rows()) become the batch, staged by ONE launch on the engine's stream
         (include/sactd3.h: sactd3_rb_sample_indices_device) -- no copy out and back in, no host wait.  `weights`: per-row loss
@@ -373,16 +415,21 @@ class ReplayBuffer:
         contiguous) -- the importance-sampling weights of a prioritised sampler; None: all 1.  The critic update on the returned
         handle minimises (1 / B) sum_i w_i (Q(s_i, a_i) - y_i)^2; Agent.td_errors() then gives the rows' TD errors.  A slot outside
         [0, len(rb)) becomes a zero record with index -1 and weight 0, a weight that is negative, NaN or infinite becomes 0: neither
-        reaches the parameters.  The handle is a sample()'s in every other respect (generation, device_batches)."""
+        reaches the parameters.  The handle is a sample()'s in every other respect (generation, device_batches).  `n_step`, `stride`:
+        as for sample(), the chains starting at `index` (sactd3_rb_sample_nstep_device)."""
+        n_step, stride = _n_step_args("sample_at", n_step, stride)
         eng = self._need()
         B = int(eng.cfg.batch_size)
         index, ptr, n, ld = _index_field(eng, index)
         if n != B:
             raise ValueError(f"sample_at: expected {B} indices (the engine is built for one batch size), got {n}")
         keep, w_ptr, w_ld = (None, 0, 1) if weights is None else _weight_field(eng, weights, B, "sample_at")
-        eng.rb_sample_indices_device(ptr, ld, w_ptr, w_ld, n, _producer_stream(index, eng.cfg.device_id))
+        if n_step == 1:
+            eng.rb_sample_indices_device(ptr, ld, w_ptr, w_ld, n, _producer_stream(index, eng.cfg.device_id))
+        else:
+            eng.rb_sample_nstep_device(ptr, ld, w_ptr, w_ld, n, n_step, stride, _producer_stream(index, eng.cfg.device_id))
         del keep      # (the engine's read is ordered against the stream the allocator hands the block out on)
-        return self._new_handle(eng)
+        return self._new_handle(eng, n_step > 1)
 
     def enable_priorities(self, alpha: float = 0.6, eps: float = 1e-6) -> None:
         """Proportional prioritised replay kept by the engine (include/sactd3.h: sactd3_prio_enable): one priority per ring slot in
@@ -394,16 +441,22 @@ class ReplayBuffer:
             self._engine.prio_enable(alpha, eps)
         self._priorities = dict(alpha=float(alpha), eps=float(eps))
 
-    def sample_prioritized(self, batch_size: int, beta: float) -> BatchHandle:
+    def sample_prioritized(self, batch_size: int, beta: float, *, n_step: int = 1, stride: Optional[int] = None) -> BatchHandle:
         """sample() by priority (sactd3_rb_sample_prioritized): P(i) ~ p_i^alpha, with replacement, drawn, staged and weighted on the
         device by three launches; the slot carries the importance weights (N P(i))^(-beta) over the batch's largest, so the critic
-        update on the returned handle is the weighted one.  The handle is a sample()'s in every other respect."""
+        update on the returned handle is the weighted one.  The handle is a sample()'s in every other respect.  `n_step`, `stride`: as
+        for sample(), the chains starting at the drawn slots (sactd3_rb_sample_prioritized_nstep); update_priorities() afterwards
+        writes to the start slots."""
+        n_step, stride = _n_step_args("sample_prioritized", n_step, stride)
         if self._priorities is None:
             raise RuntimeError("sample_prioritized: call enable_priorities() first")
         eng = self._need()
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
-        eng.rb_sample_prioritized(beta)
-        return self._new_handle(eng)
+        if n_step == 1:
+            eng.rb_sample_prioritized(beta)
+            return self._new_handle(eng)
+        eng.rb_sample_prioritized_nstep(beta, n_step, stride)
+        return self._new_handle(eng, True)
 
     def update_priorities(self, index=None, priorities=None) -> None:
         """The write-back.  No arguments: the rows of the batch slot get |TD error| (the larger of the twin critics') + eps of the

@@ -193,6 +193,13 @@ struct sactd3_engine {
   long long* pt_idx = nullptr;
   struct PrioCtl* pt_ctl = nullptr;
   int64_t pt_host[3] = {};
+  // N-step returns staged from the ring (sactd3_rb_sample_nstep*; device code: nstep_kernels.h).  slot_nstep: slot 0 was filled by an
+  // n-step staging and not refilled since (host state next to slot_weighted; SLOT_REFILL clears it).  ns_k / ns_last [B] and the two
+  // device counters ns_ctr {rows cut short, rows refused} are made at the first n-step call -- an engine that never makes one holds
+  // nothing more than before.  ns_host: {n-step stagings, rows staged}.
+  bool slot_nstep = false;
+  int *ns_k = nullptr, *ns_last = nullptr, *ns_ctr = nullptr;
+  int64_t ns_host[2] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -216,7 +223,7 @@ struct sactd3_engine {
 // any call that changes what a precomputed opening pair depends on (see sactd3_engine::chain_ready)
 #define CHAIN_BREAK(e) do { (e)->chain_ready = -1; } while (0)
 // batch slot 0 is refilled outside an update: it carries no weights any more, and e->q / e->y are no longer its rows
-#define SLOT_REFILL(e) do { (e)->slot_weighted = false; (e)->td_valid = false; } while (0)
+#define SLOT_REFILL(e) do { (e)->slot_weighted = false; (e)->td_valid = false; (e)->slot_nstep = false; } while (0)
 #define RCCHK(call)                    \
   do {                                 \
     int _rc = (call);                  \
@@ -1350,6 +1357,8 @@ static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_
 static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n);
 static int64_t prio_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats);
 static int prio_time_body(sactd3_engine* e, const char* kernel);
+// ... and of the n-step staging (nstep_kernels.h; again at the end of this file)
+static int nstep_time_body(sactd3_engine* e);
 
 // ------------------------------------------------------------------------------------------------ C ABI
 #pragma GCC visibility push(default)
@@ -2180,7 +2189,7 @@ int sactd3_step(sactd3_engine* e, int do_actor) {
   RCCHK(run_graph(e, which, [&](EnqCtx& x) { return enqueue_step(x, single_iteration(act, polyak)); }));
   e->qnet_updates = updates;
   e->cur_slot = 0;
-  e->slot_weighted = false; e->td_valid = true;      // (the fused paths draw their own sample and are never weighted)
+  e->slot_weighted = false; e->slot_nstep = false; e->td_valid = true;      // (the fused paths draw their own 1-step sample and are never weighted)
   e->grads_stale[0] = false;
   if (act) e->grads_stale[1] = false;
   return 0;
@@ -2267,7 +2276,7 @@ int sactd3_step_period(sactd3_engine* e) {
   // (the period's iterations run one behind the other, each writing e->q / e->y in its critic tail; what runs ahead inside the first one
   //  -- the later iterations' and the next period's opening passes -- goes through the actor only: cur_slot, e->q and e->y all belong to
   //  the period's last iteration)
-  e->slot_weighted = false; e->td_valid = true;
+  e->slot_weighted = false; e->slot_nstep = false; e->td_valid = true;
   return 0;
 }
 
@@ -2294,7 +2303,7 @@ int sactd3_step_prefix(sactd3_engine* e, int m) {
   RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](EnqCtx& x) { return enqueue_period(x, v, m); }));
   e->cur_slot = m - 1;
   e->qnet_updates += m;
-  e->slot_weighted = false; e->td_valid = true;      // (as sactd3_step_period)
+  e->slot_weighted = false; e->slot_nstep = false; e->td_valid = true;      // (as sactd3_step_period)
   return 0;
 }
 
@@ -2788,9 +2797,11 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
     // launches, batch slot 0 overwritten, the draw counter advanced) / the write-back kernel on batch_size rows, indices as for
     // "rows_to_fields", every priority 1 (those rows' priorities ARE overwritten)
     if (!strcmp(kernel, "prio_sample") || !strcmp(kernel, "prio_update")) return prio_time_body(e, kernel);
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update)");
+    // the n-step staging kernel on batch_size rows: steps 3, stride 1, indices as for "rows_to_fields", no weights, into batch slot 0
+    if (!strcmp(kernel, "batch_from_index_nstep")) return nstep_time_body(e);
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update | batch_from_index_nstep)");
   };
-  if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index") || !strcmp(kernel, "prio_update")) rc = time_rows_indices(e);
+  if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index") || !strcmp(kernel, "prio_update") || !strcmp(kernel, "batch_from_index_nstep")) rc = time_rows_indices(e);
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up
   if (rc == 0) {
     hipEventRecord(t0, e->stream);
@@ -3001,8 +3012,8 @@ static int prio_refresh(sactd3_engine* e, int64_t first, int64_t n) {
 static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n) {
   return (e->pt_on && n > 0) ? prio_refresh(e, first, n) : 0;
 }
-// the three launches of a prioritised sample: draw, weights (+ counter tick), staging
-static int prio_sample_launches(sactd3_engine* e, float beta) {
+// the three launches of a prioritised sample: draw, weights (+ counter tick) -- what the n-step form shares -- then staging
+static int prio_draw_launches(sactd3_engine* e, float beta) {
   PrioDrawArgs d{};
   d.leaf4 = (const float4*)e->pt_leaf; d.sums4 = (const float4*)e->pt_sums;
   d.ngroups = e->pt_groups; d.nch = (e->pt_groups + PRIO_G - 1) / PRIO_G; d.len = (int)e->rb_len;
@@ -3013,6 +3024,10 @@ static int prio_sample_launches(sactd3_engine* e, float beta) {
   const PrioWeightArgs w{e->pt_idx, e->pt_dleaf, e->pt_total, e->pt_w, e->B, (float)e->rb_len, beta, e->pt_inject ? nullptr : &e->pt_ctl->draw_ctr};
   hipLaunchKernelGGL(k_prio_weights, dim3(1), dim3(256), 0, e->stream, w);
   HIPCHK(hipGetLastError());
+  return 0;
+}
+static int prio_sample_launches(sactd3_engine* e, float beta) {
+  RCCHK(prio_draw_launches(e, beta));
   return launch_batch_index(e, e->pt_idx, 1, e->pt_w, 1);
 }
 static int launch_prio_update(sactd3_engine* e, PrioUpdateArgs g) {
@@ -3156,6 +3171,160 @@ int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]) {
     HIPCHK(hipMemcpy(&refused, &e->pt_ctl->refused, sizeof(int), hipMemcpyDeviceToHost));
   }
   out[0] = e->pt_host[0]; out[1] = e->pt_host[1]; out[2] = refused; out[3] = e->pt_host[2];
+  return 0;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop
+
+// ---- n-step returns staged from the ring (include/sactd3.h: sactd3_rb_sample_nstep*, sactd3_nstep_info_device, sactd3_nstep_stats).
+// Kernels, launches and entry points all stand here, behind everything that existed before (see launch_ctail_nn_w).
+#include "nstep_kernels.h"
+
+static int nstep_alloc(sactd3_engine* e) {
+  if (e->ns_ctr) return 0;
+  if (!e->ns_k) RCCHK(dalloc(e, &e->ns_k, (size_t)e->B));
+  if (!e->ns_last) RCCHK(dalloc(e, &e->ns_last, (size_t)e->B));
+  RCCHK(dalloc(e, &e->ns_ctr, 32));
+  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
+  return 0;
+}
+// idx == NULL: the uniform draw at the current sample counter; wdst: the slot's weight array, or NULL for a slot without weights
+static int launch_batch_nstep(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, float* wdst,
+                              int steps, int stride) {
+  const sactd3_engine::BatchSlot& S = e->bs[0];
+  NstepArgs g{};
+  g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.cx = e->cx; g.cn = e->cn; g.o = e->o; g.B = e->B;
+  g.len = (int)e->rb_len; g.cursor = (int)e->rb_cursor; g.cap = (int)e->cfg.rb_capacity;
+  g.steps = steps; g.stride = stride; g.gamma = e->cfg.gamma;
+  g.idx = idx; g.idx_ld = (long)idx_ld; g.w = w; g.w_ld = (long)w_ld; g.ctl = e->ctl;
+  g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.slot_idx = S.idx; g.wdst = wdst;
+  g.nk = e->ns_k; g.nlast = e->ns_last;
+  const long chunks = (long)e->B * e->rec4;      // (< 2^31: create_impl)
+  g.rec4_magic = magic_div((unsigned)e->rec4, (unsigned long long)chunks + 1);
+  // the gather's grid, with the span cut so that a block's rows fit its LDS tables: (cpb * 256) / rec4 + 2 <= NS_ROWS
+  const unsigned gb = gather_blocks(chunks);
+  const long cpb_g = (chunks + 256L * gb - 1) / (256L * gb), cpb_l = std::max(1L, (long)(NS_ROWS - 2) * e->rec4 / 256);
+  g.cpb = (int)std::min(cpb_g, cpb_l);
+  if ((256L * g.cpb) / e->rec4 + 2 > NS_ROWS) return e->fail(SACTD3_EINVAL, "n-step staging: the record is too short for the kernel's row tables");
+  const unsigned blocks = (unsigned)((chunks + 256L * g.cpb - 1) / (256L * g.cpb));
+  g.counters = e->ns_ctr;
+  hipLaunchKernelGGL(k_batch_from_index_nstep, dim3(blocks), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int nstep_args_check(sactd3_engine* e, int steps, int stride, const char* what) {
+  if (steps < 1 || steps > NS_MAX) { e->err = std::string(what) + ": steps must be in [1, 16]"; return SACTD3_EINVAL; }
+  if (stride < 1) { e->err = std::string(what) + ": stride must be at least 1"; return SACTD3_EINVAL; }
+  return 0;
+}
+static int nstep_time_body(sactd3_engine* e) {
+  RCCHK(nstep_alloc(e));
+  SLOT_REFILL(e);
+  e->cur_slot = 0;
+  RCCHK(launch_batch_nstep(e, e->time_idx, 1, nullptr, 1, nullptr, 3, 1));
+  e->slot_nstep = true;
+  return 0;
+}
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+// sactd3_rb_sample_indices_device with the chain: one k_batch_from_index_nstep launch.  No host wait, no copy command, no counter tick.
+int sactd3_rb_sample_nstep_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n, int steps,
+                                  int stride, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!idx) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: `idx` is NULL");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: unknown flag");
+  if (n != e->B) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: n must equal batch_size");
+  if (idx_ld < 1) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: row stride of `idx` is below its width");
+  if (w && w_ld < 1) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: row stride of `w` is below its width");
+  RCCHK(nstep_args_check(e, steps, stride, "rb_sample_nstep_device"));
+  RCCHK(device_ptr_check(e, idx, "rb_sample_nstep_device", "idx"));
+  if (w) RCCHK(device_ptr_check(e, w, "rb_sample_nstep_device", "w"));
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_nstep_device: buffer is empty");
+  CHAIN_BREAK(e);
+  RCCHK(slot_weights_alloc(e));
+  RCCHK(nstep_alloc(e));
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  SLOT_REFILL(e);
+  e->cur_slot = 0;
+  RCCHK(launch_batch_nstep(e, (const long long*)idx, idx_ld, w, w_ld, e->bs[0].w, steps, stride));
+  RCCHK(src_order_end(e, caller, flags));
+  e->slot_weighted = true; e->slot_nstep = true;
+  ++e->ns_host[0]; e->ns_host[1] += e->B;
+  return 0;
+}
+
+// sactd3_rb_sample with the chain: the start slots are the uniform draw at the current sample counter, which then advances once.
+int sactd3_rb_sample_nstep(sactd3_engine* e, int steps, int stride) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  RCCHK(nstep_args_check(e, steps, stride, "rb_sample_nstep"));
+  CHAIN_BREAK(e);
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_nstep: buffer is empty");
+  RCCHK(nstep_alloc(e));
+  SLOT_REFILL(e);
+  e->cur_slot = 0;
+  RCCHK(launch_batch_nstep(e, nullptr, 1, nullptr, 1, nullptr, steps, stride));
+  hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
+  HIPCHK(hipGetLastError());
+  e->slot_nstep = true;
+  ++e->ns_host[0]; e->ns_host[1] += e->B;
+  return 0;
+}
+
+// sactd3_rb_sample_prioritized with the chain: k_prio_draw, k_prio_weights, then the n-step staging kernel on the drawn slots.
+int sactd3_rb_sample_prioritized_nstep(sactd3_engine* e, float beta, int steps, int stride) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!(beta >= 0.f) || !std::isfinite(beta)) return e->fail(SACTD3_EINVAL, "rb_sample_prioritized_nstep: beta must be finite and >= 0");
+  RCCHK(nstep_args_check(e, steps, stride, "rb_sample_prioritized_nstep"));
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "rb_sample_prioritized_nstep: priorities are not enabled (sactd3_prio_enable)");
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_prioritized_nstep: buffer is empty");
+  CHAIN_BREAK(e);
+  RCCHK(nstep_alloc(e));
+  SLOT_REFILL(e);
+  e->cur_slot = 0;
+  RCCHK(prio_draw_launches(e, beta));
+  RCCHK(launch_batch_nstep(e, e->pt_idx, 1, e->pt_w, 1, e->bs[0].w, steps, stride));
+  e->slot_weighted = true; e->slot_nstep = true;
+  ++e->pt_host[0];
+  ++e->ns_host[0]; e->ns_host[1] += e->B;
+  return 0;
+}
+
+// k and the last ring slot of every row of an n-step slot, left in the caller's device arrays: one k_nstep_info launch on the learner
+// stream.  Reads the two per-slot arrays only; no CHAIN_BREAK.
+int sactd3_nstep_info_device(sactd3_engine* e, int32_t* k, int64_t k_ld, int32_t* last, int64_t last_ld, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!k && !last) return e->fail(SACTD3_EINVAL, "nstep_info_device: `k` and `last` are both NULL");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "nstep_info_device: unknown flag");
+  if ((k && k_ld < 1) || (last && last_ld < 1)) return e->fail(SACTD3_EINVAL, "nstep_info_device: a row stride is below 1");
+  if (k) RCCHK(device_ptr_check(e, k, "nstep_info_device", "k"));
+  if (last) RCCHK(device_ptr_check(e, last, "nstep_info_device", "last"));
+  if (!e->slot_nstep || e->cur_slot != 0) return e->fail(SACTD3_ESTATE, "nstep_info_device: the batch slot was not filled by an n-step staging call");
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  const NstepInfoArgs g{e->ns_k, e->ns_last, e->B, k, (long)k_ld, last, (long)last_ld};
+  hipLaunchKernelGGL(k_nstep_info, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  RCCHK(src_order_end(e, caller, flags));
+  return 0;
+}
+
+int sactd3_nstep_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int c[2] = {0, 0};
+  if (e->ns_ctr) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(c, e->ns_ctr, sizeof(c), hipMemcpyDeviceToHost));
+  }
+  out[0] = e->ns_host[0]; out[1] = e->ns_host[1]; out[2] = c[0]; out[3] = c[1];
   return 0;
 }
 

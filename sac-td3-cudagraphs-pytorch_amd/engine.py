@@ -497,6 +497,33 @@ class Engine:
         """counters of the engine-owned priorities (sactd3_prio_stats; waits for the engine's stream)"""
         return self._stats(self.lib.sactd3_prio_stats, ("samples", "write_backs", "rows_refused", "rows_entered_at_max"))
 
+    # -- n-step returns staged by the engine (include/sactd3.h: sactd3_rb_sample_nstep*)
+    def rb_sample_nstep_device(self, idx_ptr: int, idx_ld: int, w_ptr: int, w_ld: int, n: int, steps: int, stride: int, stream: int = 0,
+                               ordered: bool = True) -> None:
+        """sactd3_rb_sample_nstep_device: rb_sample_indices_device with the chain -- per row the batch slot gets [s|a] of the start
+        slot, the discounted return of up to `steps` consecutive rows of its env (`stride` = rows appended per env step), the s' of the
+        chain's last row and the mask 1 - (1 - d_last) gamma^(k-1), so that update_qnets() computes the k-step target.  One launch."""
+        self._ck(self.lib.sactd3_rb_sample_nstep_device(self._h, _vp(idx_ptr), int(idx_ld), _vp(w_ptr), int(w_ld), int(n), int(steps),
+                                                        int(stride), _vp(stream), _flag(_lib.SRC_ORDERED, ordered)))
+
+    def rb_sample_nstep(self, steps: int, stride: int) -> None:
+        """sactd3_rb_sample_nstep: rb_sample() with the chain (the same uniform draw, one counter tick, no weights)."""
+        self._ck(self.lib.sactd3_rb_sample_nstep(self._h, int(steps), int(stride)))
+
+    def rb_sample_prioritized_nstep(self, beta: float, steps: int, stride: int) -> None:
+        """sactd3_rb_sample_prioritized_nstep: rb_sample_prioritized() with the chain started at every drawn slot."""
+        self._ck(self.lib.sactd3_rb_sample_prioritized_nstep(self._h, float(beta), int(steps), int(stride)))
+
+    def nstep_info_device(self, k_ptr: int, k_ld: int, last_ptr: int, last_ld: int, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_nstep_info_device: the chain length k and the ring slot of the chain's last row of every row of an n-step batch slot,
+        to int32 arrays in this device's memory (address 0: not wanted).  EngineError (SACTD3_ESTATE) on a slot that is not n-step."""
+        self._ck(self.lib.sactd3_nstep_info_device(self._h, _vp(k_ptr), int(k_ld), _vp(last_ptr), int(last_ld), _vp(stream),
+                                                   _flag(_lib.DST_ORDERED, ordered)))
+
+    def nstep_stats(self) -> Dict[str, int]:
+        """counters of the n-step route (sactd3_nstep_stats; waits for the engine's stream: the last two live on the device)"""
+        return self._stats(self.lib.sactd3_nstep_stats, ("stagings", "rows_staged", "rows_cut_short", "rows_refused"))
+
     def acting_stats(self) -> Dict[str, int]:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
         return self._stats(self.lib.sactd3_acting_stats, ("begun", "begin_waited_for_learner", "learner_waited_for_acting", "ended_by_spin"))

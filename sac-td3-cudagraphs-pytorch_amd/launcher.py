@@ -203,7 +203,7 @@ def job_config(algo: str, env_id: str, seed: int, **over):
 
 
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
-            device_env: bool = False, prioritized: bool = False, **over):
+            device_env: bool = False, prioritized: bool = False, n_step: int = 1, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU."""
     import json
     import time
@@ -230,8 +230,9 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
     t0 = time.time()
     # --prioritized: the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4), call by call
-    metrics = loop.train(cfg, env, agent, fused=not prioritized, evaluator=ev, overlap=overlap_acting, device_env=device_env,
-                         prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None)
+    # --n_step N > 1: n-step returns chained by the engine, call by call as well
+    metrics = loop.train(cfg, env, agent, fused=not prioritized and n_step == 1, evaluator=ev, overlap=overlap_acting, device_env=device_env,
+                         prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -259,7 +260,8 @@ def _worker_main(args) -> int:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
                           eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity,
-                          overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized)
+                          overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized,
+                          n_step=args.n_step)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -291,6 +293,8 @@ def main(argv=None) -> int:
                     help="train on the GPU-resident synthetic vector env: observations and actions never leave the device (loop.train device_env=True)")
     ap.add_argument("--prioritized", action="store_true",
                     help="proportional prioritised replay kept by the engine (loop.train prioritized=...; the iteration is issued call by call)")
+    ap.add_argument("--n_step", type=int, default=1,
+                    help="train the critics on N-step returns chained by the engine (loop.train n_step=...; above 1 the iteration is issued call by call)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)

@@ -194,7 +194,8 @@ class ProportionalSampler:
 
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
           evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
-          sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None) -> Dict[str, float]:
+          sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
+          n_step: int = 1) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -209,7 +210,15 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     its TD errors (`agent.td_errors`) back into the sampler's priorities; the actor updates train on the same rows, unweighted.
     `prioritized` (dict(alpha=, beta=, eps=), any subset; needs `fused=False`, excludes `sampler`): the same iteration with the
     priorities kept by the ENGINE -- `rb.sample_prioritized` -> weighted critic update -> `rb.update_priorities()` -- with no torch
-    arithmetic in between and nothing to mirror on the host: the engine sees its own appends."""
+    arithmetic in between and nothing to mirror on the host: the engine sees its own appends.
+    `n_step` (1 to 16; above 1 it needs `fused=False`): the critic trains on n-step returns chained by the engine out of consecutive ring
+    rows of one env (`stride=cfg.num_envs`), cut at episode ends -- in the uniform, `sampler` and `prioritized` branches alike."""
+    n_step = int(n_step)
+    if not 1 <= n_step <= 16:
+        raise ValueError(f"n_step must be in [1, 16], got {n_step}")
+    if n_step > 1 and fused:
+        raise ValueError("n_step=... needs fused=False: the fused iteration samples single steps uniformly inside its graph")
+    chain = dict(n_step=n_step, stride=int(cfg.num_envs)) if n_step > 1 else {}
     if sampler is not None and fused:
         raise ValueError("sampler=... needs fused=False: the fused iteration samples uniformly inside its graph")
     if prioritized is not None:
@@ -244,12 +253,12 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
             agent.iteration(i)
         else:
             if prioritized is not None:
-                batch = agent.rb.sample_prioritized(cfg.batch_size, prio_beta)
+                batch = agent.rb.sample_prioritized(cfg.batch_size, prio_beta, **chain)
             elif sampler is None:
-                batch = agent.rb.sample(cfg.batch_size)
+                batch = agent.rb.sample(cfg.batch_size, **chain)
             else:
                 index, weights = sampler.sample(cfg.batch_size)
-                batch = agent.rb.sample_at(index, weights)
+                batch = agent.rb.sample_at(index, weights, **chain)
             tlog.update(agent.update_qnets(batch))
             if sampler is not None:
                 sampler.update(index, agent.td_errors())
