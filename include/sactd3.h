@@ -316,7 +316,8 @@ int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]);
  *   1 - (1 - d) gamma^(k-1) is non-zero for every chain longer than one row); the mask is exactly 1.0 iff the chain's last row terminated.
  * "Slot 0 is an n-step slot" is host state next to the weighted flag: the three staging calls set it; every other refill of the slot and
  *   every sactd3_step* clears it (the fused paths keep their own 1-step uniform gather inside their graphs: n-step there is out of
- *   scope).  The three calls break the run-ahead chain and make slot 0 current, exactly as their 1-step counterparts do. */
+ *   scope).  The three calls break the run-ahead chain and make slot 0 current, exactly as their 1-step counterparts do; a call of
+ *   these five that is refused (any SACTD3_EINVAL / SACTD3_ESTATE above) has changed nothing, the run-ahead chain included. */
 /* sactd3_rb_sample_indices_device with the chain: same pointer, stride, flag and error rules; in addition SACTD3_EINVAL for `steps`
  * outside [1, 16] or `stride` < 1.  One launch.  With steps == 1 it leaves, bit for bit, what sactd3_rb_sample_indices_device leaves. */
 int sactd3_rb_sample_nstep_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n, int steps,

@@ -381,6 +381,15 @@ class ReplayBuffer:
         h._n_step = n_step
         return h
 
+    def _staged(self, eng: Engine, n_step: int, stride: int, one_step: str, chained: str, *args, tail=()) -> BatchHandle:
+        """the one place a sampling call forks on n_step: the engine's 1-step call `one_step(*args, *tail)`, or its chained form
+        `chained(*args, n_step, stride, *tail)`; then the handle of the freshly filled slot"""
+        if n_step == 1:
+            getattr(eng, one_step)(*args, *tail)
+        else:
+            getattr(eng, chained)(*args, n_step, stride, *tail)
+        return self._new_handle(eng, n_step > 1)
+
     def extend(self, td: Mapping[str, Any]) -> None:
         """orchestrator.py:100-113: keys observations, next_observations, actions, rewards, terminations, dones."""
         done = td["dones"] if "dones" in td else td["terminations"]
@@ -401,11 +410,7 @@ class ReplayBuffer:
         n_step, stride = _n_step_args("sample", n_step, stride)
         eng = self._need()
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
-        if n_step == 1:
-            eng.rb_sample()
-            return self._new_handle(eng)
-        eng.rb_sample_nstep(n_step, stride)
-        return self._new_handle(eng, True)
+        return self._staged(eng, n_step, stride, "rb_sample", "rb_sample_nstep")
 
     def sample_at(self, index, weights=None, *, n_step: int = 1, stride: Optional[int] = None) -> BatchHandle:
         """sample() with the caller's rows: the ring records `index` names (batch_size ring slots: an int64 tensor on the engine's
@@ -424,12 +429,10 @@ class ReplayBuffer:
         if n != B:
             raise ValueError(f"sample_at: expected {B} indices (the engine is built for one batch size), got {n}")
         keep, w_ptr, w_ld = (None, 0, 1) if weights is None else _weight_field(eng, weights, B, "sample_at")
-        if n_step == 1:
-            eng.rb_sample_indices_device(ptr, ld, w_ptr, w_ld, n, _producer_stream(index, eng.cfg.device_id))
-        else:
-            eng.rb_sample_nstep_device(ptr, ld, w_ptr, w_ld, n, n_step, stride, _producer_stream(index, eng.cfg.device_id))
+        h = self._staged(eng, n_step, stride, "rb_sample_indices_device", "rb_sample_nstep_device", ptr, ld, w_ptr, w_ld, n,
+                         tail=(_producer_stream(index, eng.cfg.device_id),))
         del keep      # (the engine's read is ordered against the stream the allocator hands the block out on)
-        return self._new_handle(eng, n_step > 1)
+        return h
 
     def enable_priorities(self, alpha: float = 0.6, eps: float = 1e-6) -> None:
         """Proportional prioritised replay kept by the engine (include/sactd3.h: sactd3_prio_enable): one priority per ring slot in
@@ -452,11 +455,7 @@ class ReplayBuffer:
             raise RuntimeError("sample_prioritized: call enable_priorities() first")
         eng = self._need()
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
-        if n_step == 1:
-            eng.rb_sample_prioritized(beta)
-            return self._new_handle(eng)
-        eng.rb_sample_prioritized_nstep(beta, n_step, stride)
-        return self._new_handle(eng, True)
+        return self._staged(eng, n_step, stride, "rb_sample_prioritized", "rb_sample_prioritized_nstep", beta)
 
     def update_priorities(self, index=None, priorities=None) -> None:
         """The write-back.  No arguments: the rows of the batch slot get |TD error| (the larger of the twin critics') + eps of the

@@ -119,7 +119,12 @@ struct sactd3_engine {
   // does the same for the opening pair of the NEXT period's first iteration (next-action pass on s' and the first actor update's
   // policy pass on s), whose slot alternates between 0 and 3 from one period to the next (the running period still reads its own).
   struct BatchSlot { float *X, *Xn, *rew, *done, *logp_n, *eps_c; int* idx; float* w; } bs[4] = {};      // w: loss weights [B], slot 0 only, see below
-  int cur_slot = 0;              // the slot the most recent iteration trained on (what read_batch / read_noise / debug_read report)
+  // What the host knows about the slots.  cur: the slot the most recent update trained on, or 0 behind a refill (what read_batch /
+  // read_noise / debug_read / the TD write-back report).  weighted: slot 0 carries loss weights -> sactd3_update_qnets replays the weighted
+  // graph (G_QW).  nstep: slot 0 was filled by an n-step staging (ns_k / ns_last describe its rows).  td_valid: e->q / e->y belong to a
+  // critic update on the rows now in bs[cur] (sactd3_td_errors_device, sactd3_prio_update_from_td).  Written by the two transitions
+  // slot_refilled / slot_trained alone -- and by slot_set_weighted, for sactd3_batch_weights_device, which changes `weighted` only.
+  struct SlotState { int cur = 0; bool weighted = false, nstep = false, td_valid = false; } slot;
   // chain_ready = v (0 / 1): the previous sactd3_step_period left the opening pair of the next period precomputed in slot (v ? 3 : 0)
   // and nothing has touched the state it depends on since (parameters, ring length, counters, noise injection, the slots);
   // -1: not so -- the next period starts with the opening graph.  Every state-changing ABI call resets it (CHAIN_BREAK).
@@ -173,12 +178,8 @@ struct sactd3_engine {
   float *qs_hq = nullptr, *qs_hobs = nullptr, *qs_hact = nullptr;      // sactd3_qvalues (host arrays): device staging of one chunk
   int64_t q_stats[4] = {};
   // Training on caller-chosen rows with loss weights (sactd3_rb_sample_indices_device / sactd3_batch_weights_device): bs[0].w is made at
-  // the first staging call -- an engine that never stages weights holds nothing more than before.  slot_weighted: slot 0 carries
-  // weights -> sactd3_update_qnets replays the weighted graph (G_QW); set by the two staging calls, cleared by every other refill.
-  // td_valid: e->q / e->y belong to a critic update on the rows now in bs[cur_slot] (sactd3_td_errors_device): set by every critic
-  // update, cleared by every refill of a slot outside one.  prio_stats: {index stagings, weight stagings, td read-outs}; the fourth
-  // value of sactd3_priority_stats is DevCtl::priority_refused.
-  bool slot_weighted = false, td_valid = false;
+  // the first staging call -- an engine that never stages weights holds nothing more than before.  prio_stats: {index stagings, weight stagings,
+  // td read-outs}; the fourth value of sactd3_priority_stats is DevCtl::priority_refused.
   int64_t prio_stats[3] = {};
   // Proportional prioritised replay as engine state (sactd3_prio_enable; device code and table layout: prio_kernels.h).  Everything
   // below is made by sactd3_prio_enable -- an engine that never calls it holds nothing more and launches nothing more than before.
@@ -193,11 +194,9 @@ struct sactd3_engine {
   long long* pt_idx = nullptr;
   struct PrioCtl* pt_ctl = nullptr;
   int64_t pt_host[3] = {};
-  // N-step returns staged from the ring (sactd3_rb_sample_nstep*; device code: nstep_kernels.h).  slot_nstep: slot 0 was filled by an
-  // n-step staging and not refilled since (host state next to slot_weighted; SLOT_REFILL clears it).  ns_k / ns_last [B] and the two
-  // device counters ns_ctr {rows cut short, rows refused} are made at the first n-step call -- an engine that never makes one holds
-  // nothing more than before.  ns_host: {n-step stagings, rows staged}.
-  bool slot_nstep = false;
+  // N-step returns staged from the ring (sactd3_rb_sample_nstep*; device code: nstep_kernels.h).  ns_k / ns_last [B] and the two device
+  // counters ns_ctr {rows cut short, rows refused} are made at the first n-step call -- an engine that never makes one holds nothing
+  // more than before.  ns_host: {n-step stagings, rows staged}.
   int *ns_k = nullptr, *ns_last = nullptr, *ns_ctr = nullptr;
   int64_t ns_host[2] = {};
 
@@ -222,8 +221,18 @@ struct sactd3_engine {
   } while (0)
 // any call that changes what a precomputed opening pair depends on (see sactd3_engine::chain_ready)
 #define CHAIN_BREAK(e) do { (e)->chain_ready = -1; } while (0)
-// batch slot 0 is refilled outside an update: it carries no weights any more, and e->q / e->y are no longer its rows
-#define SLOT_REFILL(e) do { (e)->slot_weighted = false; (e)->td_valid = false; (e)->slot_nstep = false; } while (0)
+// The two transitions of sactd3_engine::slot.  slot_refilled: slot 0 was filled outside an update -- it is the current slot, e->q / e->y
+// are no longer its rows, and it carries weights / n-step chains only if this refill staged them.
+static inline void slot_refilled(sactd3_engine* e, bool weighted, bool nstep) { e->slot = {0, weighted, nstep, false}; }
+// slot_trained: a critic update ran on `slot`.  fused: it was part of an iteration that drew its own sample (sactd3_step and the period
+// graphs: a uniform 1-step draw, never weighted); otherwise (sactd3_update_qnets) the slot keeps what its refill staged.
+static inline void slot_trained(sactd3_engine* e, int slot, bool fused) {
+  e->slot.cur = slot; e->slot.td_valid = true;
+  if (fused) e->slot.weighted = e->slot.nstep = false;
+}
+static inline void slot_set_weighted(sactd3_engine* e, bool weighted) { e->slot.weighted = weighted; }
+// the batch slot that iteration i of a period (or cut-short period) of variant v trains on (see BatchSlot, enqueue_period)
+static inline int period_slot(bool pipelined, int v, int i) { return !pipelined ? 0 : i ? i : (v ? 3 : 0); }
 #define RCCHK(call)                    \
   do {                                 \
     int _rc = (call);                  \
@@ -1348,17 +1357,131 @@ static int publish_rb_state(sactd3_engine* e) {
   return 0;
 }
 
-// the launches of the prioritised route (defined at the end of this file, see launch_ctail_nn_w)
-static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld);
-static int launch_batch_weights(sactd3_engine* e, const float* w, int64_t w_ld);
-static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns);
-// ... and of the engine-owned priorities (prio_kernels.h; defined at the end of this file for the same reason).  prio_after_append:
-// rows [first, first + n) of the ring, wrapping at the capacity, have just been written -- nothing is launched while priorities are off.
-static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n);
-static int64_t prio_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats);
-static int prio_time_body(sactd3_engine* e, const char* kernel);
-// ... and of the n-step staging (nstep_kernels.h; again at the end of this file)
-static int nstep_time_body(sactd3_engine* e);
+// ------------------------------------------------------------------------------------------------ ring rows into batch slot 0: launches
+// Device code and launches of the staging calls (stage_ring_rows, in the replay-buffer part of the C ABI below) and of the engine-owned
+// priorities.  Plain kernels only: no template instance is first named here, so none moves in the code object.  All of it stands in
+// front of the extern "C" block, where a kernel keeps its C++ name and a helper may be a template.
+#include "prio_kernels.h"
+#include "nstep_kernels.h"
+
+static int slot_weights_alloc(sactd3_engine* e) {      // (never zeroed: every staging kernel writes all B entries before anything reads them)
+  return e->bs[0].w ? 0 : dalloc(e, &e->bs[0].w, (size_t)e->B, false);
+}
+static int nstep_alloc(sactd3_engine* e) {
+  if (e->ns_ctr) return 0;
+  if (!e->ns_k) RCCHK(dalloc(e, &e->ns_k, (size_t)e->B));
+  if (!e->ns_last) RCCHK(dalloc(e, &e->ns_last, (size_t)e->B));
+  RCCHK(dalloc(e, &e->ns_ctr, 32));
+  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
+  return 0;
+}
+// What k_batch_from_index and k_batch_from_index_nstep are both told (IndexBatchArgs and NstepArgs name these fields alike): the ring's
+// geometry, the index and weight sources, slot 0's arrays, the magic divisor.  Returns the gather's span: chunks per thread over
+// gather_blocks(B * rec4) blocks.
+template <class Args>
+static long ring_rows_args(sactd3_engine* e, Args& g, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, float* wdst) {
+  const sactd3_engine::BatchSlot& S = e->bs[0];
+  g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.cx = e->cx; g.cn = e->cn; g.B = e->B; g.len = (int)e->rb_len;
+  g.idx = idx; g.idx_ld = (long)idx_ld; g.w = w; g.w_ld = (long)w_ld;
+  g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.slot_idx = S.idx; g.wdst = wdst;
+  const long chunks = (long)e->B * e->rec4;      // (< 2^31: create_impl)
+  g.rec4_magic = magic_div((unsigned)e->rec4, (unsigned long long)chunks + 1);
+  const unsigned blocks = gather_blocks(chunks);
+  return (chunks + 256L * blocks - 1) / (256L * blocks);
+}
+// the 1-step kernel: it always writes the slot's weights (w == NULL: 1)
+static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld) {
+  IndexBatchArgs g{};
+  g.cpb = (int)ring_rows_args(e, g, idx, idx_ld, w, w_ld, e->bs[0].w);
+  g.refused = &e->ctl->priority_refused;
+  hipLaunchKernelGGL(k_batch_from_index, dim3(gather_blocks((long)e->B * e->rec4)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// idx == NULL: the uniform draw at the current sample counter; wdst: the slot's weight array, or NULL for a slot without weights
+static int launch_batch_nstep(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, float* wdst,
+                              int steps, int stride) {
+  NstepArgs g{};
+  const long cpb_g = ring_rows_args(e, g, idx, idx_ld, w, w_ld, wdst);
+  g.o = e->o; g.cursor = (int)e->rb_cursor; g.cap = (int)e->cfg.rb_capacity;
+  g.steps = steps; g.stride = stride; g.gamma = e->cfg.gamma; g.ctl = e->ctl;
+  g.nk = e->ns_k; g.nlast = e->ns_last;
+  // the gather's grid, with the span cut so that a block's rows fit its LDS tables: (cpb * 256) / rec4 + 2 <= NS_ROWS
+  const long chunks = (long)e->B * e->rec4, cpb_l = std::max(1L, (long)(NS_ROWS - 2) * e->rec4 / 256);
+  g.cpb = (int)std::min(cpb_g, cpb_l);
+  if ((256L * g.cpb) / e->rec4 + 2 > NS_ROWS) return e->fail(SACTD3_EINVAL, "n-step staging: the record is too short for the kernel's row tables");
+  const unsigned blocks = (unsigned)((chunks + 256L * g.cpb - 1) / (256L * g.cpb));
+  g.counters = e->ns_ctr;
+  hipLaunchKernelGGL(k_batch_from_index_nstep, dim3(blocks), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_batch_weights(sactd3_engine* e, const float* w, int64_t w_ld) {
+  const WeightArgs g{w, (long)w_ld, e->bs[0].idx, e->bs[0].w, e->B, &e->ctl->priority_refused};
+  hipLaunchKernelGGL(k_batch_weights, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns) {
+  const TdArgs g{e->q, e->y, e->B, td, (long)td_ld, (long)td_ns};
+  hipLaunchKernelGGL(k_td_to_field, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// rows [first, first + n) of the ring, wrapping at the capacity, have just been written: they enter at the maximum priority
+static int prio_refresh(sactd3_engine* e, int64_t first, int64_t n) {
+  const int64_t cap = e->cfg.rb_capacity;
+  PrioRefreshArgs g{};
+  g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.pc = e->pt_ctl; g.alpha = e->pt_alpha;
+  if (n >= cap) { first = 0; n = cap; }
+  g.lo0 = (int)first; g.hi0 = (int)std::min(first + n, cap);
+  g.lo1 = 0; g.hi1 = (int)std::max<int64_t>(first + n - cap, 0);
+  g.g0 = g.lo0 / PRIO_G; g.n0 = (g.hi0 - 1) / PRIO_G - g.g0 + 1;
+  g.g1 = 0;
+  const int n1 = g.hi1 > 0 ? (g.hi1 - 1) / PRIO_G + 1 : 0;
+  hipLaunchKernelGGL(k_prio_refresh, dim3((unsigned)(g.n0 + n1)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  e->pt_host[2] += n;
+  return 0;
+}
+// (nothing is launched while priorities are off)
+static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n) {
+  return (e->pt_on && n > 0) ? prio_refresh(e, first, n) : 0;
+}
+// the two launches of a prioritised draw: slots and leaves, then weights (+ counter tick); the staging kernel follows (stage_ring_rows)
+static int prio_draw_launches(sactd3_engine* e, float beta) {
+  PrioDrawArgs d{};
+  d.leaf4 = (const float4*)e->pt_leaf; d.sums4 = (const float4*)e->pt_sums;
+  d.ngroups = e->pt_groups; d.nch = (e->pt_groups + PRIO_G - 1) / PRIO_G; d.len = (int)e->rb_len;
+  d.u_inj = e->pt_inject ? e->pt_u : nullptr; d.ctl = e->ctl; d.pc = e->pt_ctl;
+  d.idx_out = e->pt_idx; d.leaf_out = e->pt_dleaf; d.total_out = e->pt_total;
+  hipLaunchKernelGGL(k_prio_draw, dim3((unsigned)e->B), dim3(256), 0, e->stream, d);
+  HIPCHK(hipGetLastError());
+  const PrioWeightArgs w{e->pt_idx, e->pt_dleaf, e->pt_total, e->pt_w, e->B, (float)e->rb_len, beta, e->pt_inject ? nullptr : &e->pt_ctl->draw_ctr};
+  hipLaunchKernelGGL(k_prio_weights, dim3(1), dim3(256), 0, e->stream, w);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_prio_update(sactd3_engine* e, PrioUpdateArgs g) {
+  g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.len = (int)e->rb_len; g.alpha = e->pt_alpha; g.eps = e->pt_eps; g.pc = e->pt_ctl;
+  hipLaunchKernelGGL(k_prio_update, dim3((unsigned)g.n), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int64_t prio_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
+  const float* src = nullptr; int64_t n = 0;
+  if (e->pt_on && !strcmp(name, "prio_leaf")) { src = e->pt_leaf; n = e->cfg.rb_capacity; }
+  else if (e->pt_on && !strcmp(name, "prio_sums")) { src = e->pt_sums; n = e->pt_groups; }      // (the one level above the leaves)
+  else if (e->pt_on && !strcmp(name, "prio_max")) { src = &e->pt_ctl->max_prio; n = 1; }
+  else if (e->pt_on && !strcmp(name, "prio_weights")) { src = e->bs[0].w; n = e->B; }           // (the loss weights batch slot 0 carries)
+  else if (!strcmp(name, "prio_leaf") || !strcmp(name, "prio_sums") || !strcmp(name, "prio_max") || !strcmp(name, "prio_weights")) return e->fail(SACTD3_ESTATE, "debug_read: priorities are not enabled");
+  else return e->fail(SACTD3_EINVAL, "debug_read: unknown buffer name");
+  if (!dst) return n;
+  if (max_floats < n) return e->fail(SACTD3_EINVAL, "debug_read: buffer too small");
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost));
+  return n;
+}
 
 // ------------------------------------------------------------------------------------------------ C ABI
 #pragma GCC visibility push(default)
@@ -1728,8 +1851,7 @@ int sactd3_rb_sample(sactd3_engine* e) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample: buffer is empty");
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
+  slot_refilled(e, false, false);
   RCCHK(gather_now(e, e->ring, -1));
   hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
   HIPCHK(hipGetLastError());
@@ -1748,8 +1870,7 @@ int sactd3_rb_sample_with_indices(sactd3_engine* e, const int64_t* idx, int n) {
   }
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipMemcpy(e->idx, h.data(), sizeof(int) * n, hipMemcpyHostToDevice));
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
+  slot_refilled(e, false, false);
   RCCHK(set_flag(e, &e->ctl->inject_idx, 1));
   RCCHK(gather_now(e, e->ring, -1));
   return set_flag(e, &e->ctl->inject_idx, 0);
@@ -1761,13 +1882,12 @@ int sactd3_load_batch(sactd3_engine* e, const float* obs, const float* act, cons
   CHAIN_BREAK(e);
   if (n != e->B) return e->fail(SACTD3_EINVAL, "load_batch: n must equal batch_size");
   HIPCHK(hipStreamSynchronize(e->stream));
-  SLOT_REFILL(e);
+  slot_refilled(e, false, false);
   std::vector<int> h(n);
   for (int i = 0; i < n; ++i) {
     pack_record(e, e->h_batch + (size_t)i * e->rec_f, obs + (size_t)i * e->o, act + (size_t)i * e->a, rew[i], nobs + (size_t)i * e->o, dones[i]);
     h[i] = i;
   }
-  e->cur_slot = 0;
   HIPCHK(hipMemcpy(e->stage_dev, e->h_batch, sizeof(float) * (size_t)n * e->rec_f, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(e->idx, h.data(), sizeof(int) * n, hipMemcpyHostToDevice));
   RCCHK(set_flag(e, &e->ctl->inject_idx, 1));
@@ -1901,8 +2021,7 @@ int sactd3_load_batch_device(sactd3_engine* e, const sactd3_device_fields* f, in
   RCCHK(fields_check(e, f, "load_batch_device"));
   const hipStream_t producer = (hipStream_t)producer_stream;
   RCCHK(src_order_begin(e, producer, flags));
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
+  slot_refilled(e, false, false);
   RCCHK(launch_batch_fields(e, field_src(e, f, 0)));
   RCCHK(src_order_end(e, producer, flags));
   ++e->bnd_stats[2];
@@ -1918,7 +2037,7 @@ int sactd3_read_batch(sactd3_engine* e, float* obs, float* act, float* rew, floa
   HIPCHK(hipStreamSynchronize(e->stream));
   std::vector<float> hx((size_t)B * e->ldc), hn((size_t)B * e->ldc), hr(B), hd(B);
   std::vector<int> hi(B);
-  const sactd3_engine::BatchSlot& S = e->bs[e->cur_slot];      // the slot of the most recent iteration
+  const sactd3_engine::BatchSlot& S = e->bs[e->slot.cur];      // the slot of the most recent iteration
   HIPCHK(hipMemcpy(hx.data(), S.X, sizeof(float) * hx.size(), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(hn.data(), S.Xn, sizeof(float) * hn.size(), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(hr.data(), S.rew, sizeof(float) * B, hipMemcpyDeviceToHost));
@@ -1953,7 +2072,7 @@ static FieldDst field_dst(const sactd3_engine* e, const sactd3_device_fields_out
   return d;
 }
 static int launch_batch_out(sactd3_engine* e, const FieldDst& dst) {
-  const sactd3_engine::BatchSlot& S = e->bs[e->cur_slot];      // the slot sactd3_read_batch reports
+  const sactd3_engine::BatchSlot& S = e->bs[e->slot.cur];      // the slot sactd3_read_batch reports
   const BatchOutArgs g{(const float4*)S.X, (const float4*)S.Xn, S.rew, S.done, S.idx, e->B};
   const long chunks = (long)e->B * (e->cx + e->cn + 1);      // (< B * rec4 < 2^31: create_impl)
   hipLaunchKernelGGL(k_batch_to_fields, dim3(cpt_blocks(chunks, TOFIELDS_CPT)), dim3(256), 0, e->stream, dst, g);
@@ -2019,37 +2138,116 @@ int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx
 
 int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]) { return stats_with_refused(e, &sactd3_engine::ro_stats, &DevCtl::readout_refused, out); }
 
-// ---- training on caller-chosen ring rows with loss weights, TD errors out (include/sactd3.h): what closes a prioritised sampler's loop
-// on the device.  (Its launches stand at the end of this file, see launch_ctail_nn_w.)
-static int slot_weights_alloc(sactd3_engine* e) {      // (never zeroed: both staging kernels write all B entries before anything reads them)
-  return e->bs[0].w ? 0 : dalloc(e, &e->bs[0].w, (size_t)e->B, false);
+// ---- ring rows into batch slot 0, all on the device (include/sactd3.h): the caller's rows or the engine's draw, one row each or chained
+// into n-step returns, with or without loss weights.  One request, one routine; the entry points below only fill the request in.
+enum { DRAW_NONE = 0, DRAW_UNIFORM = 1, DRAW_PRIO = 2 };
+struct StageReq {
+  const char* name;                            // the entry point's name, for messages
+  int draw = DRAW_NONE;                        // who chooses the rows: the caller (idx), the uniform draw at the sample counter (chained form only:
+                                               // the 1-step uniform sample is sactd3_rb_sample's gather), or the priority table (beta)
+  const long long* idx = nullptr; int64_t idx_ld = 1; const float* w = nullptr; int64_t w_ld = 1; int n = 0;      // DRAW_NONE: the caller's arrays
+  float beta = 0.f;                            // DRAW_PRIO: the exponent of the importance weights
+  bool chain = false; int steps = 0, stride = 0;      // chain: k_batch_from_index_nstep over (steps, stride); otherwise k_batch_from_index
+  bool weighted = false;                       // the slot carries loss weights behind this call
+  void* caller_stream = nullptr; int flags = 0;       // SACTD3_SRC_ORDERED and the stream it orders against
+  bool internal = false;                       // a timing body: the index array is the engine's own (no pointer check) and no host counter moves
+};
+// The whole protocol, always in this order:
+//   1. refusals, the first fault wins: `idx` NULL, unknown flag, n, stride of `idx`, stride of `w` (the caller's arrays); beta (priority
+//      draw); steps, stride (chained); `idx`, `w` not device memory of this device; priorities not enabled; ring empty.  A refused
+//      call has changed nothing -- a precomputed opening pair (chain_ready) stays valid across it
+//   2. CHAIN_BREAK                     3. allocations at first use (slot weights, n-step arrays)      4. src_order_begin
+//   5. the launches, on the learner stream: [k_prio_draw, k_prio_weights,] the staging kernel [, k_tick of the sample counter behind a uniform draw]
+//   6. src_order_end                   7. slot_refilled                                               8. the host counters
+static int stage_ring_rows(sactd3_engine* e, const StageReq& q) {
+  const auto refuse = [&](int code, const char* what) { e->err = std::string(q.name) + ": " + what; return code; };
+  const bool callers = q.draw == DRAW_NONE;
+  if (callers) {
+    if (!q.idx) return refuse(SACTD3_EINVAL, "`idx` is NULL");
+    if (q.flags & ~SACTD3_SRC_ORDERED) return refuse(SACTD3_EINVAL, "unknown flag");
+    if (q.n != e->B) return refuse(SACTD3_EINVAL, "n must equal batch_size");
+    if (q.idx_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `idx` is below its width");
+    if (q.w && q.w_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `w` is below its width");
+  }
+  if (q.draw == DRAW_PRIO && (!(q.beta >= 0.f) || !std::isfinite(q.beta))) return refuse(SACTD3_EINVAL, "beta must be finite and >= 0");
+  if (q.chain && (q.steps < 1 || q.steps > NS_MAX)) return refuse(SACTD3_EINVAL, "steps must be in [1, 16]");
+  if (q.chain && q.stride < 1) return refuse(SACTD3_EINVAL, "stride must be at least 1");
+  if (q.draw == DRAW_UNIFORM && !q.chain) return refuse(SACTD3_EINVAL, "the uniform 1-step sample is sactd3_rb_sample");      // (no entry point asks)
+  if (callers && !q.internal) {
+    RCCHK(device_ptr_check(e, q.idx, q.name, "idx"));
+    if (q.w) RCCHK(device_ptr_check(e, q.w, q.name, "w"));
+  }
+  if (q.draw == DRAW_PRIO && !e->pt_on) return refuse(SACTD3_ESTATE, "priorities are not enabled (sactd3_prio_enable)");
+  if (e->rb_len <= 0) return refuse(SACTD3_ESTATE, "buffer is empty");
+  CHAIN_BREAK(e);
+  if (q.weighted || !q.chain) RCCHK(slot_weights_alloc(e));      // (the 1-step kernel always writes the slot's weights)
+  if (q.chain) RCCHK(nstep_alloc(e));
+  const hipStream_t caller = (hipStream_t)q.caller_stream;
+  RCCHK(src_order_begin(e, caller, q.flags));
+  const bool prio = q.draw == DRAW_PRIO;      // the draw leaves slots and weights in pt_idx / pt_w
+  if (prio) RCCHK(prio_draw_launches(e, q.beta));
+  const long long* idx = prio ? e->pt_idx : q.idx;
+  const float* w = prio ? e->pt_w : q.w;
+  const int64_t idx_ld = prio ? 1 : q.idx_ld, w_ld = prio ? 1 : q.w_ld;
+  if (q.chain) RCCHK(launch_batch_nstep(e, idx, idx_ld, w, w_ld, q.weighted ? e->bs[0].w : nullptr, q.steps, q.stride));
+  else RCCHK(launch_batch_index(e, idx, idx_ld, w, w_ld));
+  if (q.draw == DRAW_UNIFORM) {
+    hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  RCCHK(src_order_end(e, caller, q.flags));
+  slot_refilled(e, q.weighted, q.chain);
+  if (q.internal) return 0;
+  if (q.chain) { ++e->ns_host[0]; e->ns_host[1] += e->B; }
+  if (prio) ++e->pt_host[0];
+  if (callers && !q.chain) ++e->prio_stats[0];
+  return 0;
 }
 
-// rb.sample() with the caller's indices and importance weights, all on the device: one k_batch_from_index launch fills slot 0 as the
-// index-injected gather of sactd3_rb_sample_with_indices does, plus the slot's w.  No host wait, no copy command, no sample-counter tick.
+// rb.sample() with the caller's indices and importance weights: one k_batch_from_index launch fills slot 0 as the index-injected gather
+// of sactd3_rb_sample_with_indices does, plus the slot's w.  No host wait, no copy command, no sample-counter tick.
 int sactd3_rb_sample_indices_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n,
                                     void* caller_stream, int flags) {
   if (!e) return SACTD3_EINVAL;
-  if (!idx) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: `idx` is NULL");
   USE_DEVICE(e);
-  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: unknown flag");
-  if (n != e->B) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: n must equal batch_size");
-  if (idx_ld < 1) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: row stride of `idx` is below its width");
-  if (w && w_ld < 1) return e->fail(SACTD3_EINVAL, "rb_sample_indices_device: row stride of `w` is below its width");
-  RCCHK(device_ptr_check(e, idx, "rb_sample_indices_device", "idx"));
-  if (w) RCCHK(device_ptr_check(e, w, "rb_sample_indices_device", "w"));
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_indices_device: buffer is empty");
-  CHAIN_BREAK(e);
-  RCCHK(slot_weights_alloc(e));
-  const hipStream_t caller = (hipStream_t)caller_stream;
-  RCCHK(src_order_begin(e, caller, flags));
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
-  RCCHK(launch_batch_index(e, (const long long*)idx, idx_ld, w, w_ld));
-  RCCHK(src_order_end(e, caller, flags));
-  e->slot_weighted = true;
-  ++e->prio_stats[0];
-  return 0;
+  StageReq q{"rb_sample_indices_device"};
+  q.idx = (const long long*)idx; q.idx_ld = idx_ld; q.w = w; q.w_ld = w_ld; q.n = n; q.weighted = true;
+  q.caller_stream = caller_stream; q.flags = flags;
+  return stage_ring_rows(e, q);
+}
+// ... with the chain: one k_batch_from_index_nstep launch
+int sactd3_rb_sample_nstep_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n, int steps,
+                                  int stride, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  StageReq q{"rb_sample_nstep_device"};
+  q.idx = (const long long*)idx; q.idx_ld = idx_ld; q.w = w; q.w_ld = w_ld; q.n = n; q.weighted = true;
+  q.chain = true; q.steps = steps; q.stride = stride; q.caller_stream = caller_stream; q.flags = flags;
+  return stage_ring_rows(e, q);
+}
+// sactd3_rb_sample with the chain: the start slots are the uniform draw at the current sample counter, which then advances once
+int sactd3_rb_sample_nstep(sactd3_engine* e, int steps, int stride) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  StageReq q{"rb_sample_nstep"};
+  q.draw = DRAW_UNIFORM; q.chain = true; q.steps = steps; q.stride = stride;
+  return stage_ring_rows(e, q);
+}
+// rb.sample by priority: k_prio_draw, k_prio_weights, k_batch_from_index.  The uniform sampler's counter is not touched.
+int sactd3_rb_sample_prioritized(sactd3_engine* e, float beta) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  StageReq q{"rb_sample_prioritized"};
+  q.draw = DRAW_PRIO; q.beta = beta; q.weighted = true;
+  return stage_ring_rows(e, q);
+}
+// ... with the chain: the n-step staging kernel on the drawn slots
+int sactd3_rb_sample_prioritized_nstep(sactd3_engine* e, float beta, int steps, int stride) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  StageReq q{"rb_sample_prioritized_nstep"};
+  q.draw = DRAW_PRIO; q.beta = beta; q.weighted = true; q.chain = true; q.steps = steps; q.stride = stride;
+  return stage_ring_rows(e, q);
 }
 
 // loss weights for whatever slot 0 holds (a caller-owned device batch, an index-staged one); NULL drops them
@@ -2058,7 +2256,7 @@ int sactd3_batch_weights_device(sactd3_engine* e, const float* w, int64_t w_ld, 
   USE_DEVICE(e);
   if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "batch_weights_device: unknown flag");
   if (n != e->B) return e->fail(SACTD3_EINVAL, "batch_weights_device: n must equal batch_size");
-  if (!w) { e->slot_weighted = false; return 0; }
+  if (!w) { slot_set_weighted(e, false); return 0; }
   if (w_ld < 1) return e->fail(SACTD3_EINVAL, "batch_weights_device: row stride of `w` is below its width");
   RCCHK(device_ptr_check(e, w, "batch_weights_device", "w"));
   CHAIN_BREAK(e);
@@ -2067,7 +2265,7 @@ int sactd3_batch_weights_device(sactd3_engine* e, const float* w, int64_t w_ld, 
   RCCHK(src_order_begin(e, caller, flags));
   RCCHK(launch_batch_weights(e, w, w_ld));
   RCCHK(src_order_end(e, caller, flags));
-  e->slot_weighted = true;
+  slot_set_weighted(e, true);
   ++e->prio_stats[1];
   return 0;
 }
@@ -2081,7 +2279,7 @@ int sactd3_td_errors_device(sactd3_engine* e, float* td, int64_t td_ld, int64_t 
   if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "td_errors_device: unknown flag");
   if (td_ld < 1 || td_ns < 1) return e->fail(SACTD3_EINVAL, "td_errors_device: a stride of `td` is below 1");
   RCCHK(device_ptr_check(e, td, "td_errors_device", "td"));
-  if (!e->td_valid) return e->fail(SACTD3_ESTATE, "td_errors_device: no critic update has run on the rows now in the batch slot");
+  if (!e->slot.td_valid) return e->fail(SACTD3_ESTATE, "td_errors_device: no critic update has run on the rows now in the batch slot");
   const hipStream_t caller = (hipStream_t)caller_stream;
   RCCHK(src_order_begin(e, caller, flags));
   RCCHK(launch_td_out(e, td, td_ld, td_ns));
@@ -2091,6 +2289,123 @@ int sactd3_td_errors_device(sactd3_engine* e, float* td, int64_t td_ld, int64_t 
 }
 
 int sactd3_priority_stats(sactd3_engine* e, int64_t out[4]) { return stats_with_refused(e, &sactd3_engine::prio_stats, &DevCtl::priority_refused, out); }
+
+// ---- proportional prioritised replay as engine state (include/sactd3.h: sactd3_prio_*; the sample itself: stage_ring_rows)
+// One leaf per ring slot plus the group sums, built for the rows the ring holds now (priority 1 = the starting maximum).
+int sactd3_prio_enable(sactd3_engine* e, float alpha, float eps) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!(alpha >= 0.f) || !std::isfinite(alpha)) return e->fail(SACTD3_EINVAL, "prio_enable: alpha must be finite and >= 0");
+  if (!(eps > 0.f) || !std::isfinite(eps)) return e->fail(SACTD3_EINVAL, "prio_enable: eps must be finite and > 0");
+  if (e->pt_on) return (alpha == e->pt_alpha && eps == e->pt_eps) ? 0 : e->fail(SACTD3_ESTATE, "prio_enable: already enabled with other values");
+  const int64_t groups = ((int64_t)e->cfg.rb_capacity + PRIO_G - 1) / PRIO_G, chunks = (groups + PRIO_G - 1) / PRIO_G;
+  if (!e->pt_leaf) {      // (a call that failed half way keeps what it had made)
+    RCCHK(dalloc(e, &e->pt_leaf, (size_t)groups * PRIO_G)); RCCHK(dalloc(e, &e->pt_sums, (size_t)chunks * PRIO_G));
+    RCCHK(dalloc(e, &e->pt_ctl, 1));
+    RCCHK(dalloc(e, &e->pt_idx, (size_t)e->B)); RCCHK(dalloc(e, &e->pt_dleaf, (size_t)e->B)); RCCHK(dalloc(e, &e->pt_w, (size_t)e->B));
+    RCCHK(dalloc(e, &e->pt_total, 4)); RCCHK(dalloc(e, &e->pt_u, (size_t)e->B));
+  }
+  RCCHK(slot_weights_alloc(e));
+  PrioCtl h{};
+  h.max_prio = 1.f;
+  HIPCHK(hipMemcpy(e->pt_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
+  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
+  e->pt_groups = (int)groups; e->pt_alpha = alpha; e->pt_eps = eps; e->pt_on = true;
+  return prio_after_append(e, 0, e->rb_len);
+}
+
+int sactd3_prio_set_uniforms(sactd3_engine* e, const float* u, int n) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_set_uniforms: priorities are not enabled (sactd3_prio_enable)");
+  if (!u) { e->pt_inject = false; return 0; }
+  if (n != e->B) return e->fail(SACTD3_EINVAL, "prio_set_uniforms: n must equal batch_size");
+  std::vector<float> h((size_t)n);
+  for (int i = 0; i < n; ++i) h[i] = u[i] >= 0.f ? std::min(u[i], 0x1.fffffep-1f) : 0.f;      // into [0, 1); NaN -> 0
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(e->pt_u, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
+  e->pt_inject = true;
+  return 0;
+}
+
+// The write-back from the critic update that just ran on the batch slot: one k_prio_update launch.  It reads e->q / e->y and the slot's
+// ring indices and writes the priority table only: no CHAIN_BREAK, a precomputed opening pair of sactd3_step_period stays valid.
+int sactd3_prio_update_from_td(sactd3_engine* e) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_from_td: priorities are not enabled (sactd3_prio_enable)");
+  if (!e->slot.td_valid) return e->fail(SACTD3_ESTATE, "prio_update_from_td: no critic update has run on the rows now in the batch slot");
+  PrioUpdateArgs g{};
+  g.n = e->B; g.slot_idx = e->bs[e->slot.cur].idx; g.q = e->q; g.y = e->y; g.B = e->B;
+  RCCHK(launch_prio_update(e, g));
+  ++e->pt_host[1];
+  return 0;
+}
+
+int sactd3_prio_update_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* prio, int64_t prio_ld, int n,
+                              void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!idx || !prio) return e->fail(SACTD3_EINVAL, "prio_update_device: `idx` or `prio` is NULL");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "prio_update_device: unknown flag");
+  if (n < 1) return e->fail(SACTD3_EINVAL, "prio_update_device: n must be at least 1");
+  if (idx_ld < 1 || prio_ld < 1) return e->fail(SACTD3_EINVAL, "prio_update_device: a row stride is below 1");
+  RCCHK(device_ptr_check(e, idx, "prio_update_device", "idx"));
+  RCCHK(device_ptr_check(e, prio, "prio_update_device", "prio"));
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_device: priorities are not enabled (sactd3_prio_enable)");
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  PrioUpdateArgs g{};
+  g.n = n; g.idx = (const long long*)idx; g.idx_ld = (long)idx_ld; g.prio = prio; g.prio_ld = (long)prio_ld;
+  RCCHK(launch_prio_update(e, g));
+  RCCHK(src_order_end(e, caller, flags));
+  ++e->pt_host[1];
+  return 0;
+}
+
+int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int refused = 0;
+  if (e->pt_on) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(&refused, &e->pt_ctl->refused, sizeof(int), hipMemcpyDeviceToHost));
+  }
+  out[0] = e->pt_host[0]; out[1] = e->pt_host[1]; out[2] = refused; out[3] = e->pt_host[2];
+  return 0;
+}
+
+// k and the last ring slot of every row of an n-step slot, left in the caller's device arrays: one k_nstep_info launch on the learner
+// stream.  Reads the two per-slot arrays only; no CHAIN_BREAK.
+int sactd3_nstep_info_device(sactd3_engine* e, int32_t* k, int64_t k_ld, int32_t* last, int64_t last_ld, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!k && !last) return e->fail(SACTD3_EINVAL, "nstep_info_device: `k` and `last` are both NULL");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "nstep_info_device: unknown flag");
+  if ((k && k_ld < 1) || (last && last_ld < 1)) return e->fail(SACTD3_EINVAL, "nstep_info_device: a row stride is below 1");
+  if (k) RCCHK(device_ptr_check(e, k, "nstep_info_device", "k"));
+  if (last) RCCHK(device_ptr_check(e, last, "nstep_info_device", "last"));
+  if (!e->slot.nstep || e->slot.cur != 0) return e->fail(SACTD3_ESTATE, "nstep_info_device: the batch slot was not filled by an n-step staging call");
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  const NstepInfoArgs g{e->ns_k, e->ns_last, e->B, k, (long)k_ld, last, (long)last_ld};
+  hipLaunchKernelGGL(k_nstep_info, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
+  HIPCHK(hipGetLastError());
+  RCCHK(src_order_end(e, caller, flags));
+  return 0;
+}
+
+int sactd3_nstep_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int c[2] = {0, 0};
+  if (e->ns_ctr) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(c, e->ns_ctr, sizeof(c), hipMemcpyDeviceToHost));
+  }
+  out[0] = e->ns_host[0]; out[1] = e->ns_host[1]; out[2] = c[0]; out[3] = c[1];
+  return 0;
+}
 
 int sactd3_rb_fill_synthetic(sactd3_engine* e, int64_t n, uint64_t seed) {
   if (!e) return SACTD3_EINVAL;
@@ -2138,7 +2453,7 @@ int sactd3_read_noise(sactd3_engine* e, int site, float* eps, int n) {
   USE_DEVICE(e);
   if (e->act_inflight && site == SACTD3_SITE_PREDICT) return e->fail(SACTD3_ESTATE, "read_noise: an acting call is in flight (sactd3_predict_end first)");
   HIPCHK(hipStreamSynchronize(e->stream));
-  const float* src = site == SACTD3_SITE_CRITIC ? e->bs[e->cur_slot].eps_c : e->eps[site];
+  const float* src = site == SACTD3_SITE_CRITIC ? e->bs[e->slot.cur].eps_c : e->eps[site];
   HIPCHK(hipMemcpy(eps, src, sizeof(float) * (size_t)n * e->a, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -2148,14 +2463,13 @@ int sactd3_update_qnets(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
-  e->cur_slot = 0;
-  if (e->slot_weighted) {      // the weighted form: the same sequence with the weighted critic tail, a graph of its own
+  if (e->slot.weighted) {      // the weighted form: the same sequence with the weighted critic tail, a graph of its own
     IterPlace it;
     it.weighted = true;
     RCCHK(run_graph(e, G_QW, [&](EnqCtx& x) { return enqueue_update_qnets(x, it, false); }));
   } else RCCHK(run_graph(e, G_Q, [&](EnqCtx& x) { return enqueue_update_qnets(x, IterPlace{}, false); }));
   e->grads_stale[0] = false;
-  e->td_valid = true;
+  slot_trained(e, 0, false);
   return 0;
 }
 int sactd3_update_actor(sactd3_engine* e) {
@@ -2188,8 +2502,7 @@ int sactd3_step(sactd3_engine* e, int do_actor) {
   if (act) RCCHK(actor_write_begin(e));      // (a critic-only iteration touches nothing the acting kernels read: no order with them)
   RCCHK(run_graph(e, which, [&](EnqCtx& x) { return enqueue_step(x, single_iteration(act, polyak)); }));
   e->qnet_updates = updates;
-  e->cur_slot = 0;
-  e->slot_weighted = false; e->slot_nstep = false; e->td_valid = true;      // (the fused paths draw their own 1-step sample and are never weighted)
+  slot_trained(e, 0, true);
   e->grads_stale[0] = false;
   if (act) e->grads_stale[1] = false;
   return 0;
@@ -2230,7 +2543,7 @@ static int enqueue_period(EnqCtx& x, int variant, int m) {
   for (int i = 0; i < m; ++i) {
     IterPlace it;
     it.actor = i == 0 && e->cfg.actor_update_delay > 0; it.targets = true; it.more = i + 1 < m;
-    if (pipelined) { it.slot = i ? i : (variant ? 3 : 0); it.pre_sampled = true; }
+    if (pipelined) { it.slot = period_slot(true, variant, i); it.pre_sampled = true; }
     if (pipelined && i == 0) { it.ahead = m - 1; it.chain_slot = whole ? (variant ? 0 : 3) : -1; }
     RCCHK(enqueue_step(x, it));
   }
@@ -2257,26 +2570,26 @@ int sactd3_step_period(sactd3_engine* e) {
   const int n = e->cfg.actor_update_delay + 1;
   RCCHK(actor_write_begin(e));
   mark_grads_stale(e);
-  if (!period_is_pipelined(e)) {
+  const bool pipelined = period_is_pipelined(e);
+  int v = 0;
+  if (!pipelined) {
     e->chain_ready = -1;
     RCCHK(run_graph(e, G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, 0, n); }));
-    e->cur_slot = 0;
   } else {
     // chained periods: this period's opening pair is either left over from the previous one (chain_ready names the variant) or is
     // produced now by the 2- / 3-node opening graph; the period graph then leaves the NEXT period's behind
-    const int v = e->chain_ready >= 0 ? e->chain_ready : 0;
+    v = e->chain_ready >= 0 ? e->chain_ready : 0;
     const bool have = e->chain_ready >= 0;
     e->chain_ready = -1;
     if (!have) RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }));
     RCCHK(run_graph(e, v ? G_PERIOD_B : G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, v, n); }));
     e->chain_ready = 1 - v;
-    e->cur_slot = n - 1;
   }
   e->qnet_updates += n;
   // (the period's iterations run one behind the other, each writing e->q / e->y in its critic tail; what runs ahead inside the first one
-  //  -- the later iterations' and the next period's opening passes -- goes through the actor only: cur_slot, e->q and e->y all belong to
-  //  the period's last iteration)
-  e->slot_weighted = false; e->slot_nstep = false; e->td_valid = true;
+  //  -- the later iterations' and the next period's opening passes -- goes through the actor only: the current slot, e->q and e->y all
+  //  belong to the period's last iteration)
+  slot_trained(e, period_slot(pipelined, v, n - 1), true);
   return 0;
 }
 
@@ -2301,9 +2614,8 @@ int sactd3_step_prefix(sactd3_engine* e, int m) {
   mark_grads_stale(e);
   if (!have) RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }));
   RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](EnqCtx& x) { return enqueue_period(x, v, m); }));
-  e->cur_slot = m - 1;
   e->qnet_updates += m;
-  e->slot_weighted = false; e->slot_nstep = false; e->td_valid = true;      // (as sactd3_step_period)
+  slot_trained(e, period_slot(true, v, m - 1), true);      // (as sactd3_step_period; m == 1 on variant 1: slot 3)
   return 0;
 }
 
@@ -2670,7 +2982,7 @@ int sactd3_sync(sactd3_engine* e) {
 struct DbgEntry { const char* name; const float* ptr; int64_t n; };
 static std::vector<DbgEntry> dbg_table(sactd3_engine* e) {
   const int64_t B = e->B, BH = B * HID;
-  const sactd3_engine::BatchSlot& S = e->bs[e->cur_slot];
+  const sactd3_engine::BatchSlot& S = e->bs[e->slot.cur];
   return {
       {"X", S.X, B * e->ldc}, {"Xn", S.Xn, B * e->ldc}, {"Xp", e->Xp, B * e->ldc}, {"rew", S.rew, B}, {"done", S.done, B},
       {"logp_next", S.logp_n, B}, {"logp_pi", e->logp_pi, B}, {"logp_alpha", e->logp_al, B},
@@ -2727,7 +3039,7 @@ static int time_rows_indices(sactd3_engine* e) {
   std::vector<int> h(e->B);
   std::vector<long long> w(e->B);
   HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(h.data(), e->bs[e->cur_slot].idx, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(h.data(), e->bs[e->slot.cur].idx, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
   for (int b = 0; b < e->B; ++b) w[b] = (long long)((h[b] < 0 ? 0 : h[b]) % e->rb_len);
   HIPCHK(hipMemcpy(e->time_idx, w.data(), sizeof(long long) * w.size(), hipMemcpyHostToDevice));
   return 0;
@@ -2742,9 +3054,9 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
   int rc = 0;
   auto body = [&]() -> int {
     EnqCtx x{e, e->stream};
-    // (SLOT_REFILL: only where the kernel being timed overwrites batch slot 0)
+    // (slot_refilled: only where the kernel being timed overwrites batch slot 0)
     if (!strcmp(kernel, "gather")) {   // a fresh index draw per launch (k_tick bumps the sample counter): rows come from HBM, not from the caches
-      SLOT_REFILL(e);
+      slot_refilled(e, false, false);
       RCCHK(enqueue_gather(x, e->ring, -1));
       hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
       HIPCHK(hipGetLastError());
@@ -2763,7 +3075,7 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
       f.dones = (const uint8_t*)(e->stage_dev + e->ldc + e->ldo + 1);
       f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f;
-      if (!strcmp(kernel, "batch_from_fields")) { SLOT_REFILL(e); e->cur_slot = 0; return launch_batch_fields(e, field_src(e, &f, 0)); }
+      if (!strcmp(kernel, "batch_from_fields")) { slot_refilled(e, false, false); return launch_batch_fields(e, field_src(e, &f, 0)); }
       return launch_ingest_fields(e, field_src(e, &f, 0), (int)std::min<int64_t>(std::min(e->maxn, e->B), e->cfg.rb_capacity));
     }
     // the pack / unpack kernels of sactd3_predict_device on max_envs rows: observations read from the ring's records (the s columns,
@@ -2789,16 +3101,35 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       if (!strcmp(kernel, "sa_from_fields")) return launch_sa_pack(e, e->ring, e->rec_f, e->ring + e->o, e->rec_f, m);
       return launch_q_head(e, e->Pc, m, e->qs_z1, 1, Q_CHUNK);
     }
-    // the staging and TD read-out kernels of the prioritised route on batch_size rows: indices from time_idx (as "rows_to_fields"), no
-    // weights, into batch slot 0 (overwritten); the TD errors of whatever e->q / e->y hold, written into the engine's own staging slab
-    if (!strcmp(kernel, "batch_from_index")) { RCCHK(slot_weights_alloc(e)); SLOT_REFILL(e); e->cur_slot = 0; return launch_batch_index(e, e->time_idx, 1, nullptr, 1); }
+    // the TD read-out kernel: the TD errors of whatever e->q / e->y hold, written into the engine's own staging slab
     if (!strcmp(kernel, "td_to_field")) return launch_td_out(e, e->stage_dev, 1, e->B);
-    // the engine-owned priorities (SACTD3_ESTATE before sactd3_prio_enable): one whole sactd3_rb_sample_prioritized (beta 0.4: three
-    // launches, batch slot 0 overwritten, the draw counter advanced) / the write-back kernel on batch_size rows, indices as for
-    // "rows_to_fields", every priority 1 (those rows' priorities ARE overwritten)
-    if (!strcmp(kernel, "prio_sample") || !strcmp(kernel, "prio_update")) return prio_time_body(e, kernel);
-    // the n-step staging kernel on batch_size rows: steps 3, stride 1, indices as for "rows_to_fields", no weights, into batch slot 0
-    if (!strcmp(kernel, "batch_from_index_nstep")) return nstep_time_body(e);
+    // the engine-owned priorities (SACTD3_ESTATE before sactd3_prio_enable): "prio_update" is the write-back kernel on batch_size rows,
+    // indices as for "rows_to_fields", every priority 1 (those rows' priorities ARE overwritten)
+    const bool prio_sample = !strcmp(kernel, "prio_sample"), prio_update = !strcmp(kernel, "prio_update");
+    if ((prio_sample || prio_update) && !e->pt_on) return e->fail(SACTD3_ESTATE, "time_kernel: priorities are not enabled");
+    if ((prio_sample || prio_update) && e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_kernel: buffer is empty");
+    if (prio_update) {
+      if (!e->pt_ones) {
+        RCCHK(dalloc(e, &e->pt_ones, (size_t)e->B, false));
+        const std::vector<float> one((size_t)e->B, 1.f);
+        HIPCHK(hipMemcpy(e->pt_ones, one.data(), sizeof(float) * one.size(), hipMemcpyHostToDevice));
+      }
+      PrioUpdateArgs g{};
+      g.n = e->B; g.idx = e->time_idx; g.idx_ld = 1; g.prio = e->pt_ones; g.prio_ld = 1;
+      return launch_prio_update(e, g);
+    }
+    // the staging calls, batch slot 0 overwritten: stage_ring_rows itself, without its counters.  "batch_from_index" / "_nstep" (steps 3,
+    // stride 1): the one staging kernel on batch_size rows, indices from time_idx (as "rows_to_fields"), no weights; "prio_sample": one
+    // whole sactd3_rb_sample_prioritized (beta 0.4: three launches, the draw counter advanced)
+    const bool one_step = !strcmp(kernel, "batch_from_index"), chain = !strcmp(kernel, "batch_from_index_nstep");
+    if (one_step || chain || prio_sample) {
+      StageReq q{"time_kernel"};
+      q.internal = true;
+      if (prio_sample) { q.draw = DRAW_PRIO; q.beta = 0.4f; q.weighted = true; }
+      else { q.idx = e->time_idx; q.n = e->B; }
+      if (chain) { q.chain = true; q.steps = 3; q.stride = 1; }
+      return stage_ring_rows(e, q);
+    }
     return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update | batch_from_index_nstep)");
   };
   if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index") || !strcmp(kernel, "prio_update") || !strcmp(kernel, "batch_from_index_nstep")) rc = time_rows_indices(e);
@@ -2826,7 +3157,7 @@ int sactd3_time_nodes(sactd3_engine* e, int do_actor, int iters, int max_nodes, 
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_nodes: buffer is empty");
-  SLOT_REFILL(e);
+  slot_refilled(e, false, false);
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
   const bool period = do_actor == 2 && e->cfg.actor_update_delay > 0 && (e->cfg.prefer_td3_over_sac || e->cfg.crit_targ_update_freq == 1);
   if (act || period) RCCHK(actor_write_begin(e));
@@ -2948,10 +3279,9 @@ extern "C" __attribute__((visibility("default"))) int sactd3_debug_phases(sactd3
 }
 #endif
 
-// ---- the launches of the prioritised route (sactd3_rb_sample_indices_device, sactd3_batch_weights_device, sactd3_td_errors_device and
-// the weighted form of sactd3_update_qnets).  They stand here, behind everything else, because the compiler emits kernel template
-// instances in the order this file first names them (see launch_tails): the instances that existed before keep their place, and with
-// it their machine code.
+// ---- the two launches of the weighted form of sactd3_update_qnets.  They stand here, behind everything else, because the compiler
+// emits kernel template instances in the order this file first names them (see launch_tails): the instances that existed before keep
+// their place, and with it their machine code.
 static int launch_ctail_nn_w(EnqCtx& x, const CtailNn& f, const float* w, double fl, double by, dim3 grid) {
   const CtailNnW g{f, w};
   LAUNCH("k_ctail_nn_w<2>", fl, by, k_ctail_nn_w<2>, grid, dim3(256), g);
@@ -2962,371 +3292,3 @@ static int launch_critic_tail_w(EnqCtx& x, const CriticTail& t, const float* w, 
   LAUNCH("k_critic_tail_w<16>", fl, by, k_critic_tail_w<16>, grid, dim3(256), g);
   return 0;
 }
-static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld) {
-  const sactd3_engine::BatchSlot& S = e->bs[0];
-  IndexBatchArgs g{};
-  g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.cx = e->cx; g.cn = e->cn; g.B = e->B; g.len = (int)e->rb_len;
-  g.idx = idx; g.idx_ld = (long)idx_ld; g.w = w; g.w_ld = (long)w_ld;
-  g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.slot_idx = S.idx; g.wdst = S.w;
-  const long chunks = (long)e->B * e->rec4;      // (< 2^31: create_impl)
-  g.rec4_magic = magic_div((unsigned)e->rec4, (unsigned long long)chunks + 1);
-  const unsigned blocks = gather_blocks(chunks);
-  g.cpb = (int)((chunks + 256L * blocks - 1) / (256L * blocks));
-  g.refused = &e->ctl->priority_refused;
-  hipLaunchKernelGGL(k_batch_from_index, dim3(blocks), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-static int launch_batch_weights(sactd3_engine* e, const float* w, int64_t w_ld) {
-  const WeightArgs g{w, (long)w_ld, e->bs[0].idx, e->bs[0].w, e->B, &e->ctl->priority_refused};
-  hipLaunchKernelGGL(k_batch_weights, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns) {
-  const TdArgs g{e->q, e->y, e->B, td, (long)td_ld, (long)td_ns};
-  hipLaunchKernelGGL(k_td_to_field, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// ---- proportional prioritised replay as engine state (include/sactd3.h: sactd3_prio_*, sactd3_rb_sample_prioritized).  Kernels, launches
-// and entry points all stand here, behind everything that existed before (see launch_ctail_nn_w).
-#include "prio_kernels.h"
-
-static int prio_refresh(sactd3_engine* e, int64_t first, int64_t n) {
-  const int64_t cap = e->cfg.rb_capacity;
-  PrioRefreshArgs g{};
-  g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.pc = e->pt_ctl; g.alpha = e->pt_alpha;
-  if (n >= cap) { first = 0; n = cap; }
-  g.lo0 = (int)first; g.hi0 = (int)std::min(first + n, cap);
-  g.lo1 = 0; g.hi1 = (int)std::max<int64_t>(first + n - cap, 0);
-  g.g0 = g.lo0 / PRIO_G; g.n0 = (g.hi0 - 1) / PRIO_G - g.g0 + 1;
-  g.g1 = 0;
-  const int n1 = g.hi1 > 0 ? (g.hi1 - 1) / PRIO_G + 1 : 0;
-  hipLaunchKernelGGL(k_prio_refresh, dim3((unsigned)(g.n0 + n1)), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
-  e->pt_host[2] += n;
-  return 0;
-}
-static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n) {
-  return (e->pt_on && n > 0) ? prio_refresh(e, first, n) : 0;
-}
-// the three launches of a prioritised sample: draw, weights (+ counter tick) -- what the n-step form shares -- then staging
-static int prio_draw_launches(sactd3_engine* e, float beta) {
-  PrioDrawArgs d{};
-  d.leaf4 = (const float4*)e->pt_leaf; d.sums4 = (const float4*)e->pt_sums;
-  d.ngroups = e->pt_groups; d.nch = (e->pt_groups + PRIO_G - 1) / PRIO_G; d.len = (int)e->rb_len;
-  d.u_inj = e->pt_inject ? e->pt_u : nullptr; d.ctl = e->ctl; d.pc = e->pt_ctl;
-  d.idx_out = e->pt_idx; d.leaf_out = e->pt_dleaf; d.total_out = e->pt_total;
-  hipLaunchKernelGGL(k_prio_draw, dim3((unsigned)e->B), dim3(256), 0, e->stream, d);
-  HIPCHK(hipGetLastError());
-  const PrioWeightArgs w{e->pt_idx, e->pt_dleaf, e->pt_total, e->pt_w, e->B, (float)e->rb_len, beta, e->pt_inject ? nullptr : &e->pt_ctl->draw_ctr};
-  hipLaunchKernelGGL(k_prio_weights, dim3(1), dim3(256), 0, e->stream, w);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-static int prio_sample_launches(sactd3_engine* e, float beta) {
-  RCCHK(prio_draw_launches(e, beta));
-  return launch_batch_index(e, e->pt_idx, 1, e->pt_w, 1);
-}
-static int launch_prio_update(sactd3_engine* e, PrioUpdateArgs g) {
-  g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.len = (int)e->rb_len; g.alpha = e->pt_alpha; g.eps = e->pt_eps; g.pc = e->pt_ctl;
-  hipLaunchKernelGGL(k_prio_update, dim3((unsigned)g.n), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-static int prio_time_body(sactd3_engine* e, const char* kernel) {
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "time_kernel: priorities are not enabled");
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_kernel: buffer is empty");
-  if (!strcmp(kernel, "prio_sample")) {
-    SLOT_REFILL(e);
-    e->cur_slot = 0;
-    RCCHK(prio_sample_launches(e, 0.4f));
-    e->slot_weighted = true;
-    return 0;
-  }
-  if (!e->pt_ones) {
-    RCCHK(dalloc(e, &e->pt_ones, (size_t)e->B, false));
-    const std::vector<float> one((size_t)e->B, 1.f);
-    HIPCHK(hipMemcpy(e->pt_ones, one.data(), sizeof(float) * one.size(), hipMemcpyHostToDevice));
-  }
-  PrioUpdateArgs g{};
-  g.n = e->B; g.idx = e->time_idx; g.idx_ld = 1; g.prio = e->pt_ones; g.prio_ld = 1;
-  return launch_prio_update(e, g);
-}
-static int64_t prio_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
-  const float* src = nullptr; int64_t n = 0;
-  if (e->pt_on && !strcmp(name, "prio_leaf")) { src = e->pt_leaf; n = e->cfg.rb_capacity; }
-  else if (e->pt_on && !strcmp(name, "prio_sums")) { src = e->pt_sums; n = e->pt_groups; }      // (the one level above the leaves)
-  else if (e->pt_on && !strcmp(name, "prio_max")) { src = &e->pt_ctl->max_prio; n = 1; }
-  else if (e->pt_on && !strcmp(name, "prio_weights")) { src = e->bs[0].w; n = e->B; }           // (the loss weights batch slot 0 carries)
-  else if (!strcmp(name, "prio_leaf") || !strcmp(name, "prio_sums") || !strcmp(name, "prio_max") || !strcmp(name, "prio_weights")) return e->fail(SACTD3_ESTATE, "debug_read: priorities are not enabled");
-  else return e->fail(SACTD3_EINVAL, "debug_read: unknown buffer name");
-  if (!dst) return n;
-  if (max_floats < n) return e->fail(SACTD3_EINVAL, "debug_read: buffer too small");
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost));
-  return n;
-}
-
-#pragma GCC visibility push(default)
-extern "C" {
-
-// One leaf per ring slot plus the group sums, built for the rows the ring holds now (priority 1 = the starting maximum).
-int sactd3_prio_enable(sactd3_engine* e, float alpha, float eps) {
-  if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  if (!(alpha >= 0.f) || !std::isfinite(alpha)) return e->fail(SACTD3_EINVAL, "prio_enable: alpha must be finite and >= 0");
-  if (!(eps > 0.f) || !std::isfinite(eps)) return e->fail(SACTD3_EINVAL, "prio_enable: eps must be finite and > 0");
-  if (e->pt_on) return (alpha == e->pt_alpha && eps == e->pt_eps) ? 0 : e->fail(SACTD3_ESTATE, "prio_enable: already enabled with other values");
-  const int64_t groups = ((int64_t)e->cfg.rb_capacity + PRIO_G - 1) / PRIO_G, chunks = (groups + PRIO_G - 1) / PRIO_G;
-  if (!e->pt_leaf) {      // (a call that failed half way keeps what it had made)
-    RCCHK(dalloc(e, &e->pt_leaf, (size_t)groups * PRIO_G)); RCCHK(dalloc(e, &e->pt_sums, (size_t)chunks * PRIO_G));
-    RCCHK(dalloc(e, &e->pt_ctl, 1));
-    RCCHK(dalloc(e, &e->pt_idx, (size_t)e->B)); RCCHK(dalloc(e, &e->pt_dleaf, (size_t)e->B)); RCCHK(dalloc(e, &e->pt_w, (size_t)e->B));
-    RCCHK(dalloc(e, &e->pt_total, 4)); RCCHK(dalloc(e, &e->pt_u, (size_t)e->B));
-  }
-  RCCHK(slot_weights_alloc(e));
-  PrioCtl h{};
-  h.max_prio = 1.f;
-  HIPCHK(hipMemcpy(e->pt_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
-  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
-  e->pt_groups = (int)groups; e->pt_alpha = alpha; e->pt_eps = eps; e->pt_on = true;
-  return prio_after_append(e, 0, e->rb_len);
-}
-
-// rb.sample by priority: three launches on the learner stream (k_prio_draw, k_prio_weights, k_batch_from_index), no copy command, no
-// host wait.  The uniform sampler's counter is not touched.
-int sactd3_rb_sample_prioritized(sactd3_engine* e, float beta) {
-  if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  if (!(beta >= 0.f) || !std::isfinite(beta)) return e->fail(SACTD3_EINVAL, "rb_sample_prioritized: beta must be finite and >= 0");
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "rb_sample_prioritized: priorities are not enabled (sactd3_prio_enable)");
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_prioritized: buffer is empty");
-  CHAIN_BREAK(e);
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
-  RCCHK(prio_sample_launches(e, beta));
-  e->slot_weighted = true;
-  ++e->pt_host[0];
-  return 0;
-}
-
-int sactd3_prio_set_uniforms(sactd3_engine* e, const float* u, int n) {
-  if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_set_uniforms: priorities are not enabled (sactd3_prio_enable)");
-  if (!u) { e->pt_inject = false; return 0; }
-  if (n != e->B) return e->fail(SACTD3_EINVAL, "prio_set_uniforms: n must equal batch_size");
-  std::vector<float> h((size_t)n);
-  for (int i = 0; i < n; ++i) h[i] = u[i] >= 0.f ? std::min(u[i], 0x1.fffffep-1f) : 0.f;      // into [0, 1); NaN -> 0
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(e->pt_u, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
-  e->pt_inject = true;
-  return 0;
-}
-
-// The write-back from the critic update that just ran on the batch slot: one k_prio_update launch.  It reads e->q / e->y and the slot's
-// ring indices and writes the priority table only: no CHAIN_BREAK, a precomputed opening pair of sactd3_step_period stays valid.
-int sactd3_prio_update_from_td(sactd3_engine* e) {
-  if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_from_td: priorities are not enabled (sactd3_prio_enable)");
-  if (!e->td_valid) return e->fail(SACTD3_ESTATE, "prio_update_from_td: no critic update has run on the rows now in the batch slot");
-  PrioUpdateArgs g{};
-  g.n = e->B; g.slot_idx = e->bs[e->cur_slot].idx; g.q = e->q; g.y = e->y; g.B = e->B;
-  RCCHK(launch_prio_update(e, g));
-  ++e->pt_host[1];
-  return 0;
-}
-
-int sactd3_prio_update_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* prio, int64_t prio_ld, int n,
-                              void* caller_stream, int flags) {
-  if (!e) return SACTD3_EINVAL;
-  if (!idx || !prio) return e->fail(SACTD3_EINVAL, "prio_update_device: `idx` or `prio` is NULL");
-  USE_DEVICE(e);
-  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "prio_update_device: unknown flag");
-  if (n < 1) return e->fail(SACTD3_EINVAL, "prio_update_device: n must be at least 1");
-  if (idx_ld < 1 || prio_ld < 1) return e->fail(SACTD3_EINVAL, "prio_update_device: a row stride is below 1");
-  RCCHK(device_ptr_check(e, idx, "prio_update_device", "idx"));
-  RCCHK(device_ptr_check(e, prio, "prio_update_device", "prio"));
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_device: priorities are not enabled (sactd3_prio_enable)");
-  const hipStream_t caller = (hipStream_t)caller_stream;
-  RCCHK(src_order_begin(e, caller, flags));
-  PrioUpdateArgs g{};
-  g.n = n; g.idx = (const long long*)idx; g.idx_ld = (long)idx_ld; g.prio = prio; g.prio_ld = (long)prio_ld;
-  RCCHK(launch_prio_update(e, g));
-  RCCHK(src_order_end(e, caller, flags));
-  ++e->pt_host[1];
-  return 0;
-}
-
-int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  int refused = 0;
-  if (e->pt_on) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(&refused, &e->pt_ctl->refused, sizeof(int), hipMemcpyDeviceToHost));
-  }
-  out[0] = e->pt_host[0]; out[1] = e->pt_host[1]; out[2] = refused; out[3] = e->pt_host[2];
-  return 0;
-}
-
-}  // extern "C"
-#pragma GCC visibility pop
-
-// ---- n-step returns staged from the ring (include/sactd3.h: sactd3_rb_sample_nstep*, sactd3_nstep_info_device, sactd3_nstep_stats).
-// Kernels, launches and entry points all stand here, behind everything that existed before (see launch_ctail_nn_w).
-#include "nstep_kernels.h"
-
-static int nstep_alloc(sactd3_engine* e) {
-  if (e->ns_ctr) return 0;
-  if (!e->ns_k) RCCHK(dalloc(e, &e->ns_k, (size_t)e->B));
-  if (!e->ns_last) RCCHK(dalloc(e, &e->ns_last, (size_t)e->B));
-  RCCHK(dalloc(e, &e->ns_ctr, 32));
-  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
-  return 0;
-}
-// idx == NULL: the uniform draw at the current sample counter; wdst: the slot's weight array, or NULL for a slot without weights
-static int launch_batch_nstep(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, float* wdst,
-                              int steps, int stride) {
-  const sactd3_engine::BatchSlot& S = e->bs[0];
-  NstepArgs g{};
-  g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.cx = e->cx; g.cn = e->cn; g.o = e->o; g.B = e->B;
-  g.len = (int)e->rb_len; g.cursor = (int)e->rb_cursor; g.cap = (int)e->cfg.rb_capacity;
-  g.steps = steps; g.stride = stride; g.gamma = e->cfg.gamma;
-  g.idx = idx; g.idx_ld = (long)idx_ld; g.w = w; g.w_ld = (long)w_ld; g.ctl = e->ctl;
-  g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.slot_idx = S.idx; g.wdst = wdst;
-  g.nk = e->ns_k; g.nlast = e->ns_last;
-  const long chunks = (long)e->B * e->rec4;      // (< 2^31: create_impl)
-  g.rec4_magic = magic_div((unsigned)e->rec4, (unsigned long long)chunks + 1);
-  // the gather's grid, with the span cut so that a block's rows fit its LDS tables: (cpb * 256) / rec4 + 2 <= NS_ROWS
-  const unsigned gb = gather_blocks(chunks);
-  const long cpb_g = (chunks + 256L * gb - 1) / (256L * gb), cpb_l = std::max(1L, (long)(NS_ROWS - 2) * e->rec4 / 256);
-  g.cpb = (int)std::min(cpb_g, cpb_l);
-  if ((256L * g.cpb) / e->rec4 + 2 > NS_ROWS) return e->fail(SACTD3_EINVAL, "n-step staging: the record is too short for the kernel's row tables");
-  const unsigned blocks = (unsigned)((chunks + 256L * g.cpb - 1) / (256L * g.cpb));
-  g.counters = e->ns_ctr;
-  hipLaunchKernelGGL(k_batch_from_index_nstep, dim3(blocks), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-static int nstep_args_check(sactd3_engine* e, int steps, int stride, const char* what) {
-  if (steps < 1 || steps > NS_MAX) { e->err = std::string(what) + ": steps must be in [1, 16]"; return SACTD3_EINVAL; }
-  if (stride < 1) { e->err = std::string(what) + ": stride must be at least 1"; return SACTD3_EINVAL; }
-  return 0;
-}
-static int nstep_time_body(sactd3_engine* e) {
-  RCCHK(nstep_alloc(e));
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
-  RCCHK(launch_batch_nstep(e, e->time_idx, 1, nullptr, 1, nullptr, 3, 1));
-  e->slot_nstep = true;
-  return 0;
-}
-
-#pragma GCC visibility push(default)
-extern "C" {
-
-// sactd3_rb_sample_indices_device with the chain: one k_batch_from_index_nstep launch.  No host wait, no copy command, no counter tick.
-int sactd3_rb_sample_nstep_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n, int steps,
-                                  int stride, void* caller_stream, int flags) {
-  if (!e) return SACTD3_EINVAL;
-  if (!idx) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: `idx` is NULL");
-  USE_DEVICE(e);
-  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: unknown flag");
-  if (n != e->B) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: n must equal batch_size");
-  if (idx_ld < 1) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: row stride of `idx` is below its width");
-  if (w && w_ld < 1) return e->fail(SACTD3_EINVAL, "rb_sample_nstep_device: row stride of `w` is below its width");
-  RCCHK(nstep_args_check(e, steps, stride, "rb_sample_nstep_device"));
-  RCCHK(device_ptr_check(e, idx, "rb_sample_nstep_device", "idx"));
-  if (w) RCCHK(device_ptr_check(e, w, "rb_sample_nstep_device", "w"));
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_nstep_device: buffer is empty");
-  CHAIN_BREAK(e);
-  RCCHK(slot_weights_alloc(e));
-  RCCHK(nstep_alloc(e));
-  const hipStream_t caller = (hipStream_t)caller_stream;
-  RCCHK(src_order_begin(e, caller, flags));
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
-  RCCHK(launch_batch_nstep(e, (const long long*)idx, idx_ld, w, w_ld, e->bs[0].w, steps, stride));
-  RCCHK(src_order_end(e, caller, flags));
-  e->slot_weighted = true; e->slot_nstep = true;
-  ++e->ns_host[0]; e->ns_host[1] += e->B;
-  return 0;
-}
-
-// sactd3_rb_sample with the chain: the start slots are the uniform draw at the current sample counter, which then advances once.
-int sactd3_rb_sample_nstep(sactd3_engine* e, int steps, int stride) {
-  if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  RCCHK(nstep_args_check(e, steps, stride, "rb_sample_nstep"));
-  CHAIN_BREAK(e);
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_nstep: buffer is empty");
-  RCCHK(nstep_alloc(e));
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
-  RCCHK(launch_batch_nstep(e, nullptr, 1, nullptr, 1, nullptr, steps, stride));
-  hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
-  HIPCHK(hipGetLastError());
-  e->slot_nstep = true;
-  ++e->ns_host[0]; e->ns_host[1] += e->B;
-  return 0;
-}
-
-// sactd3_rb_sample_prioritized with the chain: k_prio_draw, k_prio_weights, then the n-step staging kernel on the drawn slots.
-int sactd3_rb_sample_prioritized_nstep(sactd3_engine* e, float beta, int steps, int stride) {
-  if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  if (!(beta >= 0.f) || !std::isfinite(beta)) return e->fail(SACTD3_EINVAL, "rb_sample_prioritized_nstep: beta must be finite and >= 0");
-  RCCHK(nstep_args_check(e, steps, stride, "rb_sample_prioritized_nstep"));
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "rb_sample_prioritized_nstep: priorities are not enabled (sactd3_prio_enable)");
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample_prioritized_nstep: buffer is empty");
-  CHAIN_BREAK(e);
-  RCCHK(nstep_alloc(e));
-  SLOT_REFILL(e);
-  e->cur_slot = 0;
-  RCCHK(prio_draw_launches(e, beta));
-  RCCHK(launch_batch_nstep(e, e->pt_idx, 1, e->pt_w, 1, e->bs[0].w, steps, stride));
-  e->slot_weighted = true; e->slot_nstep = true;
-  ++e->pt_host[0];
-  ++e->ns_host[0]; e->ns_host[1] += e->B;
-  return 0;
-}
-
-// k and the last ring slot of every row of an n-step slot, left in the caller's device arrays: one k_nstep_info launch on the learner
-// stream.  Reads the two per-slot arrays only; no CHAIN_BREAK.
-int sactd3_nstep_info_device(sactd3_engine* e, int32_t* k, int64_t k_ld, int32_t* last, int64_t last_ld, void* caller_stream, int flags) {
-  if (!e) return SACTD3_EINVAL;
-  if (!k && !last) return e->fail(SACTD3_EINVAL, "nstep_info_device: `k` and `last` are both NULL");
-  USE_DEVICE(e);
-  if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "nstep_info_device: unknown flag");
-  if ((k && k_ld < 1) || (last && last_ld < 1)) return e->fail(SACTD3_EINVAL, "nstep_info_device: a row stride is below 1");
-  if (k) RCCHK(device_ptr_check(e, k, "nstep_info_device", "k"));
-  if (last) RCCHK(device_ptr_check(e, last, "nstep_info_device", "last"));
-  if (!e->slot_nstep || e->cur_slot != 0) return e->fail(SACTD3_ESTATE, "nstep_info_device: the batch slot was not filled by an n-step staging call");
-  const hipStream_t caller = (hipStream_t)caller_stream;
-  RCCHK(src_order_begin(e, caller, flags));
-  const NstepInfoArgs g{e->ns_k, e->ns_last, e->B, k, (long)k_ld, last, (long)last_ld};
-  hipLaunchKernelGGL(k_nstep_info, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
-  RCCHK(src_order_end(e, caller, flags));
-  return 0;
-}
-
-int sactd3_nstep_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  int c[2] = {0, 0};
-  if (e->ns_ctr) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(c, e->ns_ctr, sizeof(c), hipMemcpyDeviceToHost));
-  }
-  out[0] = e->ns_host[0]; out[1] = e->ns_host[1]; out[2] = c[0]; out[3] = c[1];
-  return 0;
-}
-
-}  // extern "C"
-#pragma GCC visibility pop

@@ -776,9 +776,10 @@ def test_period_graph_equals_single_iterations(algo, env, B, delay, span):
                 eng.step(i % (delay + 1) == 0)
         res.append([eng.get_params(_lib.ACTOR), eng.get_params(_lib.CRITICS), eng.get_params(_lib.CRITICS_TARGET), eng.get_params(_lib.ACTOR_TARGET),
                     eng.get_params(_lib.LOG_ALPHA), eng.get_adam_state(_lib.CRITICS)[2], eng.get_adam_state(_lib.ACTOR)[2]])
-        if span == (1, 10):
-            res[-1].append(eng.read_batch()["index"])
-        else:   # behind step_prefix(1) on the other slot the engine reports the wrong slot's batch: the metrics instead
+        # the batch the last iteration trained on and its critic-site draws: behind step_prefix(1) on the other slot (the (0, 4) spans)
+        # that is slot 3, not slot 0
+        res[-1] += [eng.read_batch()["index"], eng.read_noise(_lib.SITE_CRITIC)]
+        if span != (1, 10):
             res[-1].append(np.array(list(eng.read_metrics().values())))
     for x, y in zip(*res):
         assert np.array_equal(x, y)

@@ -436,6 +436,27 @@ def test_priorities_do_not_change_what_the_other_paths_compute():
     close_all(N, E)
 
 
+def test_write_back_behind_a_cut_short_period_goes_to_the_rows_it_trained_on():
+    """run_iterations(0, 4) at delay 2 is a period, then step_prefix(1) on the opening pair that period left in batch slot 3: the
+    write-back behind it takes that slot's ring rows, as behind four single steps -- not the stale rows of slot 0.  SAC Hopper, B = 64,
+    3000 rows held, native draws."""
+    _, (P4, S4), _ = q_build("sac-hopper", 2, B=64, cap=CAP)
+    for eng in (P4, S4):
+        eng.rb_extend(*[t.numpy() for t in ring_rows("sac-hopper", 3000)])
+        eng.prio_enable(1.0, 1e-6)
+    before = S4.debug_read("prio_leaf")
+    assert P4.run_iterations(0, 4) == 4
+    for i in range(4):
+        S4.step(i % 3 == 0)
+    for eng in (P4, S4):
+        eng.prio_update_from_td()
+    got, want, rows = P4.debug_read("prio_leaf"), S4.debug_read("prio_leaf"), S4.read_batch()["index"]
+    assert np.array_equal(np.flatnonzero(want.view(np.uint32) != before.view(np.uint32)), np.unique(rows))      # (|TD| + eps is never exactly 1)
+    assert same_bits(got, want), np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+    assert same_bits(P4.debug_read("prio_sums"), S4.debug_read("prio_sums")) and np.array_equal(P4.read_batch()["index"], rows)
+    close_all(P4, S4)
+
+
 def test_bad_arguments_are_refused_and_leave_the_engine_usable():
     (eng,), _, B = build("sac-hopper-64", 1, enable=None)
     lib, h = eng.lib, eng._h

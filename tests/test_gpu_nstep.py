@@ -435,6 +435,35 @@ def test_n_step_state_is_set_by_the_three_calls_and_cleared_by_every_other_refil
     close_all(A, T)
 
 
+def test_slot_state_through_a_sequence_of_refills_and_updates():
+    """what the host knows about batch slot 0 (n-step rows? loss weights? TD errors of its rows?) behind each call of a sequence that mixes
+    the staging calls, the API-path update and a fused iteration: the return codes of sactd3_nstep_info_device and
+    sactd3_td_errors_device, and the weighted graph (graph 8) captured by the first weighted update only.  SAC Hopper, B = 64."""
+    ring = ring_u("sac-hopper", False)
+    _, (eng,), _, B, _ = build("sac-hopper-64", 1, ring, prio=(0.6, 1e-6))
+    lib, h = eng.lib, eng._h
+    k, td = torch.zeros(B, dtype=torch.int32, device=DEV), torch.zeros(2, B, device=DEV)
+
+    def state():
+        """(nstep_info's code, td_errors' code, nodes of the weighted update graph)"""
+        return (lib.sactd3_nstep_info_device(h, k.data_ptr(), 1, None, 1, None, 0), lib.sactd3_td_errors_device(h, td.data_ptr(), 1, B, None, 0),
+                eng.graph_kernel_count(8))
+
+    OK, NO = 0, _lib.ESTATE
+    assert lib.sactd3_rb_sample_nstep(h, 3, STRIDE) == 0 and state() == (OK, NO, 0)           # an n-step slot; no update has seen its rows
+    assert lib.sactd3_update_qnets(h) == 0 and state() == (OK, OK, 0)                         # the update keeps what the refill staged
+    assert lib.sactd3_rb_sample_prioritized(h, 0.4) == 0 and state() == (NO, NO, 0)           # 1-step rows with weights
+    assert lib.sactd3_batch_weights_device(h, None, 1, B, None, 0) == 0 and state() == (NO, NO, 0)      # weights dropped, nothing else
+    assert lib.sactd3_update_qnets(h) == 0 and state() == (NO, OK, 0)                         # ... so this update was the unweighted one
+    assert lib.sactd3_step(h, 1) == 0 and state() == (NO, OK, 0)                              # fused: its own 1-step sample
+    assert lib.sactd3_rb_sample_prioritized(h, 0.4) == 0 and state() == (NO, NO, 0)
+    assert lib.sactd3_update_qnets(h) == 0
+    s = state()
+    assert s[:2] == (NO, OK) and s[2] > 0                                                     # the weighted graph, at its first use
+    torch.cuda.synchronize()
+    eng.close()
+
+
 # ------------------------------------------------------------------------------------------ 8. views and streams
 @pytest.mark.parametrize("case", ["sac-hopper-64", "sac-humanoid-64"])
 def test_strided_views_on_another_stream_give_the_same_bits(case):
