@@ -201,7 +201,8 @@ int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx
 int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]);
 /* ---- training on rows a sampler of the caller's own chose, with loss weights, and the TD errors back: what a prioritised replay
  * iteration needs to stay on the device end to end (index staging, a weighted critic loss, a TD read-out).  Nothing here changes what the
- * calls above and below compute; the fused sactd3_step* paths keep their own uniform sampler and are never weighted.
+ * calls above and below compute; the fused sactd3_step* paths keep their own uniform sampler and are never weighted (sactd3_step_sampled is
+ * the iteration that draws by priority inside its graph).
  * rb.sample() with the caller's indices: one kernel launch on the learner stream fills batch slot 0 (the rows, their ring slots) from the
  * ring -- bit for bit what sactd3_rb_sample_with_indices leaves for the same indices -- and the slot's per-row loss weights from `w`
  * (w[i * w_ld]; NULL: all 1).  `idx` (idx[i * idx_ld], the ring slot of row i) and `w` are DEVICE pointers in the memory of the engine's
@@ -315,8 +316,8 @@ int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]);
  *   the bootstrap state s' of slot_{k-1}, and dones = (mask != 0).  For k > 1 that `dones` is NOT the termination flag (the mask
  *   1 - (1 - d) gamma^(k-1) is non-zero for every chain longer than one row); the mask is exactly 1.0 iff the chain's last row terminated.
  * "Slot 0 is an n-step slot" is host state next to the weighted flag: the three staging calls set it; every other refill of the slot and
- *   every sactd3_step* clears it (the fused paths keep their own 1-step uniform gather inside their graphs: n-step there is out of
- *   scope).  The three calls break the run-ahead chain and make slot 0 current, exactly as their 1-step counterparts do; a call of
+ *   every sactd3_step* clears it (the fused paths keep their own 1-step uniform gather inside their graphs; sactd3_step_sampled with
+ *   n_step > 1 stages chains inside its graph and sets it).  The three calls break the run-ahead chain and make slot 0 current, exactly as their 1-step counterparts do; a call of
  *   these five that is refused (any SACTD3_EINVAL / SACTD3_ESTATE above) has changed nothing, the run-ahead chain included. */
 /* sactd3_rb_sample_indices_device with the chain: same pointer, stride, flag and error rules; in addition SACTD3_EINVAL for `steps`
  * outside [1, 16] or `stride` < 1.  One launch.  With steps == 1 it leaves, bit for bit, what sactd3_rb_sample_indices_device leaves. */
@@ -365,6 +366,29 @@ int sactd3_update_targ_nets(sactd3_engine* e, int64_t qnet_updates_so_far);
  * update, (if do_actor) actor_update_delay x actor(+alpha) updates on the same batch, Polyak
  * (subject to crit_targ_update_freq and the engine's own update counter). */
 int sactd3_step(sactd3_engine* e, int do_actor);
+/* The same iteration with a prioritised draw and / or n-step returns, as ONE graph launch: what the call sequence
+ *   sactd3_rb_sample_prioritized[_nstep] (or sactd3_rb_sample_nstep) -> sactd3_update_qnets -> sactd3_prio_update_from_td (prioritised
+ *   only) -> do_actor: actor_update_delay x sactd3_update_actor -> sactd3_update_targ_nets(the engine's own update counter + 1)
+ * computes, bit for bit, and every host counter and slot state that sequence leaves (sactd3_td_errors_device, sactd3_nstep_info_device,
+ * sactd3_read_batch, sactd3_prio_stats, sactd3_nstep_stats work behind it as behind the calls); the engine's update counter advances
+ * as in sactd3_step.  The graph is linear and holds, in order: the draw, the staging into batch slot 0, the critic update (weighted
+ * when the draw is prioritised), the TD write-back (prioritised only), the actor updates, the target update.  Its staging and
+ * priority kernels read the ring length, the cursor, `beta` and the injection switch of sactd3_prio_set_uniforms from device memory:
+ * a graph is captured once per (do_actor, target update) for the current (draw, n_step, stride) -- a change of those three drops the
+ * captured graphs -- and replayed while the ring grows and `beta` anneals; a changed `beta` or switch costs one single-thread launch
+ * in front of the graph.  Uniform with n_step == 1 is sactd3_step itself.  With use_graphs == 0 the same launches are issued eagerly.
+ * Refused, with nothing changed: NULL struct, unknown `draw`, n_step outside [1, 16], stride < 1 at n_step > 1, beta negative or
+ * not finite (SACTD3_EINVAL); a prioritised draw before sactd3_prio_enable, an empty ring (SACTD3_ESTATE). */
+enum { SACTD3_DRAW_UNIFORM = 0, SACTD3_DRAW_PRIORITIZED = 1 };
+typedef struct {
+  int32_t draw;      /* SACTD3_DRAW_UNIFORM | SACTD3_DRAW_PRIORITIZED */
+  int32_t n_step;    /* 1 .. 16 */
+  int32_t stride;    /* rows between two steps of one env; ignored at n_step == 1 */
+  float beta;        /* exponent of the importance weights; ignored by the uniform draw (but checked) */
+} sactd3_sampling;
+int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* sampling);
+/* out = {sactd3_step_sampled calls issued, graphs captured for them, 0, 0} */
+int sactd3_step_sampled_stats(sactd3_engine* e, int64_t out[4]);
 /* actor_update_delay + 1 consecutive iterations of orchestrator.py:337-352 -- the first with the actor updates, the others
  * critic-only: one period of the schedule of :345-349 -- as ONE graph launch.  Equal to that many sactd3_step calls, bit for
  * bit.  Needs TD3 or crit_targ_update_freq == 1 (else SACTD3_ESTATE: issue the iterations with sactd3_step).
@@ -490,7 +514,8 @@ int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_
 const char* sactd3_debug_names(void);
 /* number of kernel nodes in the instantiated graph of: 0 update_qnets, 1 update_actor, 2 step(do_actor=0), 3 step(do_actor=1), 4 step_period,
  * 5 the opening graph of a period that cannot use a precomputed opening pair, 6 / 7 step_prefix(1) / step_prefix(2),
- * 8 update_qnets in its weighted form (0 until its first use; the same count as 0) */
+ * 8 update_qnets in its weighted form (0 until its first use; the same count as 0),
+ * 16 + 2 do_actor + (1 with the target update): sactd3_step_sampled's graphs for its current (draw, n_step, stride), 0 until captured */
 int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
 /* average device time in microseconds of `iters` back-to-back launches of one kernel of the path,
  * measured with hipEvents on the engine's stream: "gather" (a fresh index draw per launch), "polyak", "trunk_critics" (the 4-net

@@ -18,6 +18,7 @@ SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device 
 DST_ORDERED = 1     # sactd3_read_batch_device / sactd3_rb_read_rows_device / sactd3_td_errors_device flags (the same bit, the same two events)
 Q_ONLINE, Q_TARGET = 0, 1   # sactd3_qvalues / sactd3_qvalues_device `which`
 ESTATE, EINVAL = -3, -1
+DRAW_UNIFORM, DRAW_PRIORITIZED = 0, 1   # sactd3_sampling.draw
 
 # every symbol include/sactd3.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -38,6 +39,7 @@ SYMBOLS = [
     "sactd3_prio_stats",
     "sactd3_rb_sample_nstep_device", "sactd3_rb_sample_nstep", "sactd3_rb_sample_prioritized_nstep", "sactd3_nstep_info_device",
     "sactd3_nstep_stats",
+    "sactd3_step_sampled", "sactd3_step_sampled_stats",
 ]
 
 
@@ -62,6 +64,11 @@ class CDeviceFields(C.Structure):
 class CDeviceFieldsOut(C.Structure):
     """sactd3_device_fields_out: six device pointers (None = field not wanted), each with its row stride in elements"""
     _fields_ = [(n, t) for f in ("obs", "actions", "rewards", "next_obs", "dones", "index") for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
+
+
+class CSampling(C.Structure):
+    """sactd3_sampling: how sactd3_step_sampled draws and stages its batch"""
+    _fields_ = [("draw", C.c_int32), ("n_step", C.c_int32), ("stride", C.c_int32), ("beta", C.c_float)]
 
 
 def library_path() -> str:
@@ -154,6 +161,8 @@ def load_library():
         "sactd3_rb_sample_prioritized_nstep": (C.c_int, [vp, C.c_float, C.c_int, C.c_int]),
         "sactd3_nstep_info_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int]),
         "sactd3_nstep_stats": (C.c_int, [vp, i64p]),
+        "sactd3_step_sampled": (C.c_int, [vp, C.c_int, C.POINTER(CSampling)]),
+        "sactd3_step_sampled_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

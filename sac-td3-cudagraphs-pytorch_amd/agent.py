@@ -713,11 +713,18 @@ class Agent:
     def update_targ_nets(self) -> None:
         self.engine.update_targ_nets(self.qnet_updates_so_far)
 
-    def iteration(self, i: int) -> None:
+    def iteration(self, i: int, *, beta: Optional[float] = None, n_step: int = 1, stride: Optional[int] = None) -> None:
         """orchestrator.py:337-352 as ONE graph launch (sample, critic, delayed actor x N, Polyak); keeps the
-        reference's counters."""
+        reference's counters.  `beta` (needs ReplayBuffer.enable_priorities): the sample is drawn by priority, the critic update is
+        weighted by the importance weights of exponent beta and its TD errors go back into the priorities; `n_step`, `stride`: as for
+        ReplayBuffer.sample -- all inside the same launch (include/sactd3.h: sactd3_step_sampled), equal to the call sequence
+        sample_prioritized / sample -> update_qnets -> update_priorities -> update_actor x N -> update_targ_nets bit for bit."""
         do_actor = i % (self.engine.cfg.actor_update_delay + 1) == 0
-        self.engine.step(do_actor)
+        if beta is None and n_step == 1 and stride is None:
+            self.engine.step(do_actor)
+        else:
+            n_step, stride = _n_step_args("iteration", n_step, stride)
+            self.engine.step_sampled(do_actor, beta=None if beta is None else float(beta), n_step=n_step, stride=stride)
         _bump_generation(self.engine)      # the fused step drew a new sample
         self.qnet_updates_so_far += 1
         if do_actor:

@@ -199,6 +199,14 @@ struct sactd3_engine {
   // more than before.  ns_host: {n-step stagings, rows staged}.
   int *ns_k = nullptr, *ns_last = nullptr, *ns_ctr = nullptr;
   int64_t ns_host[2] = {};
+  // The replay-aware iteration as one graph launch (sactd3_step_sampled): one executable graph per (do_actor, target update) for the
+  // current (draw, n_step, stride) -- a change of those three drops all four.  Their staging and priority launches are the graph forms
+  // (prio_kernels.h), which read the ring length, the cursor, beta and the injection switch from device memory: ss_beta_bits / ss_inject
+  // are what the host last published into PrioCtl (-1: nothing yet).  ss_stats: {launches, graph captures}.
+  hipGraphExec_t ss_graphs[4] = {}; int ss_nodes[4] = {};
+  int ss_key[3] = {0, 0, 0};
+  int64_t ss_beta_bits = -1; int ss_inject = -1;
+  int64_t ss_stats[2] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -1390,17 +1398,21 @@ static long ring_rows_args(sactd3_engine* e, Args& g, const long long* idx, int6
   return (chunks + 256L * blocks - 1) / (256L * blocks);
 }
 // the 1-step kernel: it always writes the slot's weights (w == NULL: 1)
-static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld) {
+// graph_form (here and in the launchers below): the launch is being captured into a graph that is replayed while the ring grows --
+// the kernel instance that reads what varies from device memory (prio_kernels.h: the graph forms)
+static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, bool graph_form = false) {
   IndexBatchArgs g{};
   g.cpb = (int)ring_rows_args(e, g, idx, idx_ld, w, w_ld, e->bs[0].w);
   g.refused = &e->ctl->priority_refused;
-  hipLaunchKernelGGL(k_batch_from_index, dim3(gather_blocks((long)e->B * e->rec4)), dim3(256), 0, e->stream, g);
+  const dim3 grid(gather_blocks((long)e->B * e->rec4));
+  if (graph_form) hipLaunchKernelGGL(k_batch_from_index_g, grid, dim3(256), 0, e->stream, IndexBatchArgsG{g, e->ctl, (int)e->cfg.rb_capacity});
+  else hipLaunchKernelGGL(k_batch_from_index, grid, dim3(256), 0, e->stream, g);
   HIPCHK(hipGetLastError());
   return 0;
 }
 // idx == NULL: the uniform draw at the current sample counter; wdst: the slot's weight array, or NULL for a slot without weights
 static int launch_batch_nstep(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, float* wdst,
-                              int steps, int stride) {
+                              int steps, int stride, bool graph_form = false) {
   NstepArgs g{};
   const long cpb_g = ring_rows_args(e, g, idx, idx_ld, w, w_ld, wdst);
   g.o = e->o; g.cursor = (int)e->rb_cursor; g.cap = (int)e->cfg.rb_capacity;
@@ -1412,7 +1424,8 @@ static int launch_batch_nstep(sactd3_engine* e, const long long* idx, int64_t id
   if ((256L * g.cpb) / e->rec4 + 2 > NS_ROWS) return e->fail(SACTD3_EINVAL, "n-step staging: the record is too short for the kernel's row tables");
   const unsigned blocks = (unsigned)((chunks + 256L * g.cpb - 1) / (256L * g.cpb));
   g.counters = e->ns_ctr;
-  hipLaunchKernelGGL(k_batch_from_index_nstep, dim3(blocks), dim3(256), 0, e->stream, g);
+  if (graph_form) hipLaunchKernelGGL(k_batch_from_index_nstep_g, dim3(blocks), dim3(256), 0, e->stream, g);
+  else hipLaunchKernelGGL(k_batch_from_index_nstep, dim3(blocks), dim3(256), 0, e->stream, g);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1449,25 +1462,62 @@ static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n) {
   return (e->pt_on && n > 0) ? prio_refresh(e, first, n) : 0;
 }
 // the two launches of a prioritised draw: slots and leaves, then weights (+ counter tick); the staging kernel follows (stage_ring_rows)
-static int prio_draw_launches(sactd3_engine* e, float beta) {
+static int prio_draw_launches(sactd3_engine* e, float beta, bool graph_form = false) {
   PrioDrawArgs d{};
   d.leaf4 = (const float4*)e->pt_leaf; d.sums4 = (const float4*)e->pt_sums;
   d.ngroups = e->pt_groups; d.nch = (e->pt_groups + PRIO_G - 1) / PRIO_G; d.len = (int)e->rb_len;
-  d.u_inj = e->pt_inject ? e->pt_u : nullptr; d.ctl = e->ctl; d.pc = e->pt_ctl;
+  d.u_inj = (graph_form || e->pt_inject) ? e->pt_u : nullptr; d.ctl = e->ctl; d.pc = e->pt_ctl;
   d.idx_out = e->pt_idx; d.leaf_out = e->pt_dleaf; d.total_out = e->pt_total;
-  hipLaunchKernelGGL(k_prio_draw, dim3((unsigned)e->B), dim3(256), 0, e->stream, d);
+  const int cap = (int)e->cfg.rb_capacity;
+  if (graph_form) hipLaunchKernelGGL(k_prio_draw_g, dim3((unsigned)e->B), dim3(256), 0, e->stream, PrioDrawArgsG{d, cap});
+  else hipLaunchKernelGGL(k_prio_draw, dim3((unsigned)e->B), dim3(256), 0, e->stream, d);
   HIPCHK(hipGetLastError());
   const PrioWeightArgs w{e->pt_idx, e->pt_dleaf, e->pt_total, e->pt_w, e->B, (float)e->rb_len, beta, e->pt_inject ? nullptr : &e->pt_ctl->draw_ctr};
-  hipLaunchKernelGGL(k_prio_weights, dim3(1), dim3(256), 0, e->stream, w);
+  if (graph_form) hipLaunchKernelGGL(k_prio_weights_g, dim3(1), dim3(256), 0, e->stream, PrioWeightArgsG{w, e->ctl, e->pt_ctl, cap});
+  else hipLaunchKernelGGL(k_prio_weights, dim3(1), dim3(256), 0, e->stream, w);
   HIPCHK(hipGetLastError());
   return 0;
 }
-static int launch_prio_update(sactd3_engine* e, PrioUpdateArgs g) {
+static int launch_prio_update(sactd3_engine* e, PrioUpdateArgs g, bool graph_form = false) {
   g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.len = (int)e->rb_len; g.alpha = e->pt_alpha; g.eps = e->pt_eps; g.pc = e->pt_ctl;
-  hipLaunchKernelGGL(k_prio_update, dim3((unsigned)g.n), dim3(256), 0, e->stream, g);
+  if (graph_form) hipLaunchKernelGGL(k_prio_update_g, dim3((unsigned)g.n), dim3(256), 0, e->stream, PrioUpdateArgsG{g, e->ctl, (int)e->cfg.rb_capacity});
+  else hipLaunchKernelGGL(k_prio_update, dim3((unsigned)g.n), dim3(256), 0, e->stream, g);
   HIPCHK(hipGetLastError());
   return 0;
 }
+// the TD form of the write-back: the rows of batch slot `slot` and the TD errors of the critic update that ran on them
+static PrioUpdateArgs prio_td_args(sactd3_engine* e, int slot) {
+  PrioUpdateArgs g{};
+  g.n = e->B; g.slot_idx = e->bs[slot].idx; g.q = e->q; g.y = e->y; g.B = e->B;
+  return g;
+}
+
+// The replay-aware iteration (sactd3_step_sampled) as one linear sequence: what the calls
+//   sactd3_rb_sample_prioritized[_nstep] | sactd3_rb_sample_nstep -> sactd3_update_qnets -> [sactd3_prio_update_from_td] ->
+//   [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets
+// launch, launch for launch, with the staging and priority kernels in their graph forms.  (The 1-step uniform iteration is sactd3_step.)
+struct SampledPlan { bool prio; int steps, stride; bool actor, targets; };
+static int enqueue_step_sampled(EnqCtx& x, const SampledPlan& sp) {
+  sactd3_engine* e = x.e;
+  if (sp.prio) RCCHK(prio_draw_launches(e, 0.f, true));
+  const long long* idx = sp.prio ? e->pt_idx : nullptr;
+  const float* w = sp.prio ? e->pt_w : nullptr;
+  if (sp.steps > 1) RCCHK(launch_batch_nstep(e, idx, 1, w, 1, sp.prio ? e->bs[0].w : nullptr, sp.steps, sp.stride, true));
+  else RCCHK(launch_batch_index(e, idx, 1, w, 1, true));
+  if (!sp.prio) {      // the uniform draw was made at the sample counter, which now advances
+    hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, x.s, &e->ctl->sample_ctr, (int*)nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  IterPlace it;
+  it.weighted = sp.prio;
+  RCCHK(enqueue_update_qnets(x, it, false));
+  if (sp.prio) RCCHK(launch_prio_update(e, prio_td_args(e, 0), true));
+  if (sp.actor)
+    for (int j = 0; j < e->cfg.actor_update_delay; ++j) RCCHK(enqueue_update_actor(x, IterPlace{}, 0, false));
+  if (sp.targets) RCCHK(enqueue_polyak(x, POLYAK_CRITICS | (e->cfg.prefer_td3_over_sac ? POLYAK_ACTOR : 0)));
+  return 0;
+}
+
 static int64_t prio_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
   const float* src = nullptr; int64_t n = 0;
   if (e->pt_on && !strcmp(name, "prio_leaf")) { src = e->pt_leaf; n = e->cfg.rb_capacity; }
@@ -1510,6 +1560,7 @@ void sactd3_destroy(sactd3_engine* e) {
   if (e->stream) hipStreamSynchronize(e->stream);
   if (e->act_stream) hipStreamSynchronize(e->act_stream);
   for (auto& g : e->graphs) if (g) hipGraphExecDestroy(g);
+  for (auto& g : e->ss_graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_dev_graphs) if (g) hipGraphExecDestroy(g);
   for (auto ev : e->events) hipEventDestroy(ev);
@@ -2335,9 +2386,7 @@ int sactd3_prio_update_from_td(sactd3_engine* e) {
   USE_DEVICE(e);
   if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_from_td: priorities are not enabled (sactd3_prio_enable)");
   if (!e->slot.td_valid) return e->fail(SACTD3_ESTATE, "prio_update_from_td: no critic update has run on the rows now in the batch slot");
-  PrioUpdateArgs g{};
-  g.n = e->B; g.slot_idx = e->bs[e->slot.cur].idx; g.q = e->q; g.y = e->y; g.B = e->B;
-  RCCHK(launch_prio_update(e, g));
+  RCCHK(launch_prio_update(e, prio_td_args(e, e->slot.cur)));
   ++e->pt_host[1];
   return 0;
 }
@@ -2505,6 +2554,73 @@ int sactd3_step(sactd3_engine* e, int do_actor) {
   slot_trained(e, 0, true);
   e->grads_stale[0] = false;
   if (act) e->grads_stale[1] = false;
+  return 0;
+}
+
+// The iteration with a prioritised draw and / or n-step returns as ONE graph launch (include/sactd3.h); preceded by one k_set_int2
+// launch only when beta or the injection switch differ from what PrioCtl holds.  Refusals first; a refused call has changed nothing.
+int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* sm) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!sm) return e->fail(SACTD3_EINVAL, "step_sampled: the sampling struct is NULL");
+  if (sm->draw != SACTD3_DRAW_UNIFORM && sm->draw != SACTD3_DRAW_PRIORITIZED) return e->fail(SACTD3_EINVAL, "step_sampled: unknown draw");
+  if (sm->n_step < 1 || sm->n_step > NS_MAX) return e->fail(SACTD3_EINVAL, "step_sampled: n_step must be in [1, 16]");
+  if (sm->n_step > 1 && sm->stride < 1) return e->fail(SACTD3_EINVAL, "step_sampled: stride must be at least 1");
+  const bool prio = sm->draw == SACTD3_DRAW_PRIORITIZED;
+  if (!(sm->beta >= 0.f) || !std::isfinite(sm->beta)) return e->fail(SACTD3_EINVAL, "step_sampled: beta must be finite and >= 0");
+  if (prio && !e->pt_on) return e->fail(SACTD3_ESTATE, "step_sampled: priorities are not enabled (sactd3_prio_enable)");
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step_sampled: buffer is empty");
+  if (!prio && sm->n_step == 1) { RCCHK(sactd3_step(e, do_actor)); ++e->ss_stats[0]; return 0; }
+  CHAIN_BREAK(e);
+  const bool chain = sm->n_step > 1;
+  const int stride = chain ? sm->stride : 1;
+  if (prio || !chain) RCCHK(slot_weights_alloc(e));
+  if (chain) RCCHK(nstep_alloc(e));
+  const int key[3] = {sm->draw, sm->n_step, stride};
+  if (memcmp(key, e->ss_key, sizeof(key)) != 0) {
+    bool any = false;
+    for (auto& g : e->ss_graphs) any = any || g;
+    if (any) HIPCHK(hipStreamSynchronize(e->stream));      // (an executable graph is not destroyed under its own replay)
+    for (int i = 0; i < 4; ++i) {
+      if (e->ss_graphs[i]) hipGraphExecDestroy(e->ss_graphs[i]);
+      e->ss_graphs[i] = nullptr; e->ss_nodes[i] = 0;
+    }
+    memcpy(e->ss_key, key, sizeof(key));
+  }
+  if (prio) {
+    int32_t bits;
+    memcpy(&bits, &sm->beta, sizeof(bits));
+    const int inject = e->pt_inject ? 1 : 0;
+    if ((int64_t)(uint32_t)bits != e->ss_beta_bits || inject != e->ss_inject) {
+      hipLaunchKernelGGL(k_set_int2, dim3(1), dim3(1), 0, e->stream, reinterpret_cast<int*>(&e->pt_ctl->beta), (int)bits, inject);
+      HIPCHK(hipGetLastError());
+      e->ss_beta_bits = (int64_t)(uint32_t)bits; e->ss_inject = inject;
+    }
+  }
+  const int64_t updates = e->qnet_updates + 1;
+  const bool polyak = e->cfg.prefer_td3_over_sac || (updates % e->cfg.crit_targ_update_freq == 0);
+  const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
+  const int which = (act ? 2 : 0) + (polyak ? 1 : 0);
+  if (act) RCCHK(actor_write_begin(e));
+  const bool capture = e->cfg.use_graphs && !e->ss_graphs[which];
+  const SampledPlan sp{prio, sm->n_step, stride, act, polyak};
+  RCCHK(run_graph_slot(e, &e->ss_graphs[which], &e->ss_nodes[which], [&](EnqCtx& x) { return enqueue_step_sampled(x, sp); }));
+  if (capture) ++e->ss_stats[1];
+  ++e->ss_stats[0];
+  // the host state, transition by transition as the call sequence makes them
+  slot_refilled(e, prio, chain);
+  if (chain) { ++e->ns_host[0]; e->ns_host[1] += e->B; }
+  if (prio) ++e->pt_host[0];
+  slot_trained(e, 0, false);
+  e->grads_stale[0] = false;
+  if (prio) ++e->pt_host[1];
+  if (act) e->grads_stale[1] = false;
+  e->qnet_updates = updates;
+  return 0;
+}
+int sactd3_step_sampled_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  out[0] = e->ss_stats[0]; out[1] = e->ss_stats[1]; out[2] = 0; out[3] = 0;
   return 0;
 }
 
@@ -3025,6 +3141,8 @@ int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_
 int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph) {
   if (!e) return SACTD3_EINVAL;
   static const int map[9] = {G_Q, G_A, G_STEP01, G_STEP11, G_PERIOD, G_OPENING, G_PREFIX, G_PREFIX + 2, G_QW};
+  // 16 + 2 do_actor + target update: the graphs of sactd3_step_sampled for its current (draw, n_step, stride); 0: not captured
+  if (which_graph >= 16 && which_graph < 20) return e->ss_nodes[which_graph - 16];
   if (which_graph < 0 || which_graph > 8) return SACTD3_EINVAL;
   int w = map[which_graph];
   if (!e->graphs[w] && (which_graph == 2 || which_graph == 3)) w -= 1;   // the no-Polyak variant, if that is the one in use

@@ -27,9 +27,24 @@ struct PrioCtl {
   float max_prio;     // running maximum of the unscaled priorities (starts at 1): what a freshly appended row gets
   int draw_ctr;       // counter word of the SACTD3_STREAM_PRIO draws, bumped once per native sactd3_rb_sample_prioritized
   int refused;        // rows a write-back refused (bad index, bad priority, non-finite TD error), once per row and call
-  int pad[29];
+  // what the graph forms below (k_*_g) read here instead of taking it by value -- a captured graph would freeze it.  Published by the
+  // host on the learner stream in front of the graph launch, and only when it differs from what was last published (two adjacent words)
+  float beta;         // the exponent of the importance weights
+  int inject;         // != 0: the draws use the injected uniforms (pt_u) and the draw counter stands still
+  int pad[27];
 };
 static_assert(sizeof(PrioCtl) == 128, "one line");
+
+// The graph forms (k_prio_draw_g, k_prio_weights_g, k_prio_update_g; nstep_kernels.h: k_batch_from_index_g, k_batch_from_index_nstep_g):
+// second instances of the bodies below for launches that live inside a captured graph (sactd3_step_sampled).  They take the same
+// argument struct and overwrite, before the body runs, the fields that change between two replays with what device memory holds: the
+// ring length and cursor from DevCtl (every append path publishes them on the learner stream), beta and the injection switch from
+// PrioCtl.  For the same values they leave the same bits as the by-value forms -- it is the same code.  What they read is bounded by
+// the capacity before anything is derived from it; a length of 0 selects nothing: every row is refused and counted, nothing faults.
+// A body is a __device__ function that takes the struct BY VALUE (by reference the by-value kernel's instructions come out in another
+// order), or, where it leaves early, a textual include (*_body.inc): either way the by-value kernels keep their machine code.
+__device__ __forceinline__ int dev_ring_len(const DevCtl* ctl, int cap) { return min(max(ctl->rb_len, 0), cap); }
+__device__ __forceinline__ int dev_ring_cursor(const DevCtl* ctl, int cap) { return min(max(ctl->rb_cursor, 0), max(cap - 1, 0)); }
 
 // Running sums of the block's 1024 values (thread t owns values 4t .. 4t+3, in v): returns the sum of everything in front of the
 // thread's first value, `tot` = the sum of all 1024.  Fixed order: four values sequentially per thread, a Kogge-Stone scan of the 64
@@ -99,7 +114,7 @@ struct PrioDrawArgs {
   const DevCtl* ctl; const PrioCtl* pc;
   long long* idx_out; float* leaf_out; float* total_out;
 };
-__global__ __launch_bounds__(256) void k_prio_draw(PrioDrawArgs p) {
+__device__ __forceinline__ void prio_draw_body(const PrioDrawArgs p) {
   __shared__ float ws[4];
   __shared__ int s_first, s_last;
   __shared__ float s_excl, s_val;
@@ -146,13 +161,22 @@ __global__ __launch_bounds__(256) void k_prio_draw(PrioDrawArgs p) {
     if (b == 0) p.total_out[0] = T;
   }
 }
+__global__ __launch_bounds__(256) void k_prio_draw(PrioDrawArgs p) { prio_draw_body(p); }
+// (graph form: u_inj always names pt_u; the switch decides)
+struct PrioDrawArgsG { PrioDrawArgs a; int cap; };
+__global__ __launch_bounds__(256) void k_prio_draw_g(PrioDrawArgsG q) {
+  PrioDrawArgs p = q.a;
+  p.len = dev_ring_len(p.ctl, q.cap);
+  if (!p.pc->inject) p.u_inj = nullptr;
+  prio_draw_body(p);
+}
 
 // ... launch 2 of 3, one workgroup: the importance weights w_b = (N leaf_b / T)^(-beta) over the batch's largest (the row that holds
 // the largest gets exactly 1: x / x), N = the ring length; beta == 0: exactly 1 everywhere; a row with nothing drawn: 0.  The raw
 // values are parked in w[] by the thread that reads them back.  Thread 0 then advances the draw counter (native draws only).
 // Launch 3 is k_batch_from_index on idx / w.
 struct PrioWeightArgs { const long long* idx; const float* leaf; const float* total; float* w; int B; float n_rows, beta; int* ctr; };
-__global__ __launch_bounds__(256) void k_prio_weights(PrioWeightArgs p) {
+__device__ __forceinline__ void prio_weights_body(const PrioWeightArgs p) {
   __shared__ int s_max;
   const int tid = threadIdx.x;
   if (tid == 0) s_max = 0;
@@ -176,6 +200,15 @@ __global__ __launch_bounds__(256) void k_prio_weights(PrioWeightArgs p) {
     p.w[b] = top > 0.f ? raw / top : 0.f;
   }
   if (tid == 0 && p.ctr) *p.ctr += 1;
+}
+__global__ __launch_bounds__(256) void k_prio_weights(PrioWeightArgs p) { prio_weights_body(p); }
+struct PrioWeightArgsG { PrioWeightArgs a; const DevCtl* ctl; PrioCtl* pc; int cap; };
+__global__ __launch_bounds__(256) void k_prio_weights_g(PrioWeightArgsG q) {
+  PrioWeightArgs p = q.a;
+  p.n_rows = (float)dev_ring_len(q.ctl, q.cap);
+  p.beta = q.pc->beta;
+  p.ctr = q.pc->inject ? nullptr : &q.pc->draw_ctr;
+  prio_weights_body(p);
 }
 
 // Rows the ring has just written (or, at sactd3_prio_enable, the rows it holds) enter at the current maximum priority: one workgroup
@@ -240,40 +273,13 @@ __device__ __forceinline__ bool prio_row(const PrioUpdateArgs& p, int j, int& sl
 __device__ __forceinline__ float prio_leaf_value(float pr, float alpha) {
   return pr == 0.f ? 0.f : (alpha == 1.f ? pr : powf(pr, alpha));
 }
+// (the body lives in prio_update_body.inc, shared with the graph form below)
 __global__ __launch_bounds__(256) void k_prio_update(PrioUpdateArgs p) {
-  __shared__ unsigned long long own[PRIO_G];
-  __shared__ float ws[4];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  int slot_b; float pr_b;
-  const bool ok_b = prio_row(p, b, slot_b, pr_b);
-  if (!ok_b) {                        // (block-uniform)
-    if (tid == 0) atomicAdd(&p.pc->refused, 1);
-    return;
-  }
-  const int g = slot_b / PRIO_G;
-  const float4 v = reinterpret_cast<const float4*>(p.leaf)[(long)g * 256 + tid];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) own[4 * tid + k] = 0ull;
-  __syncthreads();
-  for (int j = tid; j < p.n; j += 256) {
-    int s; float pr;
-    const bool ok = prio_row(p, j, s, pr);
-    if (ok && s / PRIO_G == g)
-      atomicMax(&own[s % PRIO_G], ((unsigned long long)(unsigned)(j + 1) << 32) | (unsigned long long)__float_as_uint(prio_leaf_value(pr, p.alpha)));
-  }
-  __syncthreads();
-  float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const unsigned long long o = own[4 * tid + k];
-    if (o) vv[k] = __uint_as_float((unsigned)o);
-  }
-  float tot;
-  prio_scan(make_float4(vv[0], vv[1], vv[2], vv[3]), ws, tot);
-  if (tid == 0) {
-    st1_wt(p.sums + g, tot);
-    const unsigned long long o = own[slot_b % PRIO_G];
-    if ((unsigned)(o >> 32) == (unsigned)(b + 1)) st1_wt(p.leaf + slot_b, __uint_as_float((unsigned)o));
-    atomicMax(reinterpret_cast<int*>(&p.pc->max_prio), __float_as_int(pr_b));
-  }
+#include "prio_update_body.inc"
+}
+struct PrioUpdateArgsG { PrioUpdateArgs a; const DevCtl* ctl; int cap; };
+__global__ __launch_bounds__(256) void k_prio_update_g(PrioUpdateArgsG q) {
+  PrioUpdateArgs p = q.a;
+  p.len = dev_ring_len(q.ctl, q.cap);
+#include "prio_update_body.inc"
 }

@@ -328,6 +328,19 @@ class Engine:
     def step(self, do_actor: bool) -> None:
         self._ck(self.lib.sactd3_step(self._h, int(bool(do_actor))))
 
+    def step_sampled(self, do_actor: bool, *, beta: Optional[float] = None, n_step: int = 1, stride: int = 1) -> None:
+        """sactd3_step_sampled: step() with a prioritised draw (`beta`: the exponent of the importance weights; None: the uniform
+        draw) and / or `n_step` returns chained at `stride` rows per env step -- sample, weighted critic update, priority write-back,
+        actor updates and target update as one graph launch, replayed while the ring grows and beta anneals."""
+        sm = _lib.CSampling(_lib.DRAW_UNIFORM if beta is None else _lib.DRAW_PRIORITIZED, int(n_step), int(stride),
+                            0.0 if beta is None else float(beta))
+        self._ck(self.lib.sactd3_step_sampled(self._h, int(bool(do_actor)), C.byref(sm)))
+
+    def step_sampled_stats(self) -> Dict[str, int]:
+        """host counters of step_sampled (sactd3_step_sampled_stats): calls issued, graphs captured for them"""
+        st = self._stats(self.lib.sactd3_step_sampled_stats, ("launches", "graph_captures", "reserved0", "reserved1"))
+        return {k: st[k] for k in ("launches", "graph_captures")}
+
     def step_prefix(self, m: int) -> None:
         """the first m iterations of a period (the one with the actor updates + m - 1 critic-only ones) in one graph launch"""
         self._ck(self.lib.sactd3_step_prefix(self._h, int(m)))

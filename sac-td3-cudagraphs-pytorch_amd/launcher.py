@@ -203,7 +203,7 @@ def job_config(algo: str, env_id: str, seed: int, **over):
 
 
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
-            device_env: bool = False, prioritized: bool = False, n_step: int = 1, **over):
+            device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU."""
     import json
     import time
@@ -231,8 +231,9 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     t0 = time.time()
     # --prioritized: the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4), call by call
     # --n_step N > 1: n-step returns chained by the engine, call by call as well
+    # --one_launch: either of them (or both) as one graph launch per iteration instead
     metrics = loop.train(cfg, env, agent, fused=not prioritized and n_step == 1, evaluator=ev, overlap=overlap_acting, device_env=device_env,
-                         prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step)
+                         prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -261,7 +262,7 @@ def _worker_main(args) -> int:
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
                           eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity,
                           overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized,
-                          n_step=args.n_step)
+                          n_step=args.n_step, one_launch=args.one_launch)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -293,6 +294,8 @@ def main(argv=None) -> int:
                     help="train on the GPU-resident synthetic vector env: observations and actions never leave the device (loop.train device_env=True)")
     ap.add_argument("--prioritized", action="store_true",
                     help="proportional prioritised replay kept by the engine (loop.train prioritized=...; the iteration is issued call by call)")
+    ap.add_argument("--one_launch", action="store_true",
+                    help="with --prioritized and / or --n_step N > 1: issue the iteration as one graph launch (loop.train one_launch=True)")
     ap.add_argument("--n_step", type=int, default=1,
                     help="train the critics on N-step returns chained by the engine (loop.train n_step=...; above 1 the iteration is issued call by call)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")

@@ -195,7 +195,7 @@ class ProportionalSampler:
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
           evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
           sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
-          n_step: int = 1) -> Dict[str, float]:
+          n_step: int = 1, one_launch: bool = False) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -205,14 +205,24 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     acting stream while this iteration's update runs; a pending action is collected before an evaluation acts with the agent.
     `device_env=True`: `env` lives on the GPU (device tensors in and out, e.g. SyntheticDeviceVecEnv) and is driven by `DeviceRollout`
     -- `agent.predict_device`, no host round trip per env step.  It acts on the learner stream, so it excludes `overlap`.
-    `sampler` (a ProportionalSampler; needs `fused=False`: the fused iteration owns its uniform sampler): prioritised replay, call
+    `sampler` (a ProportionalSampler; needs `fused=False`: `fused=True` is the uniform iteration): prioritised replay, call
     by call on the device -- the sampler's rows and importance weights through `rb.sample_at`, the critic update weighted by them,
     its TD errors (`agent.td_errors`) back into the sampler's priorities; the actor updates train on the same rows, unweighted.
     `prioritized` (dict(alpha=, beta=, eps=), any subset; needs `fused=False`, excludes `sampler`): the same iteration with the
     priorities kept by the ENGINE -- `rb.sample_prioritized` -> weighted critic update -> `rb.update_priorities()` -- with no torch
     arithmetic in between and nothing to mirror on the host: the engine sees its own appends.
     `n_step` (1 to 16; above 1 it needs `fused=False`): the critic trains on n-step returns chained by the engine out of consecutive ring
-    rows of one env (`stride=cfg.num_envs`), cut at episode ends -- in the uniform, `sampler` and `prioritized` branches alike."""
+    rows of one env (`stride=cfg.num_envs`), cut at episode ends -- in the uniform, `sampler` and `prioritized` branches alike.
+    `one_launch=True` (needs `fused=False` and `prioritized` and / or `n_step` > 1, excludes `sampler`): the `prioritized` / `n_step`
+    iteration is issued as one graph launch -- `agent.iteration(i, beta=, n_step=, stride=cfg.num_envs)` -- in place of the call
+    sequence, with the same results bit for bit and the same counters."""
+    if one_launch:
+        if fused:
+            raise ValueError("one_launch=True needs fused=False: fused=True is the uniform 1-step iteration, already one launch")
+        if sampler is not None:
+            raise ValueError("one_launch=True excludes sampler=...: a sampler outside the engine cannot be part of its graph")
+        if prioritized is None and int(n_step) <= 1:
+            raise ValueError("one_launch=True needs prioritized=... and / or n_step > 1: the uniform 1-step iteration is fused=True")
     n_step = int(n_step)
     if not 1 <= n_step <= 16:
         raise ValueError(f"n_step must be in [1, 16], got {n_step}")
@@ -251,6 +261,9 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
             continue
         if fused:
             agent.iteration(i)
+        elif one_launch:
+            agent.iteration(i, beta=prio_beta if prioritized is not None else None, n_step=n_step,
+                            stride=int(cfg.num_envs) if n_step > 1 else None)
         else:
             if prioritized is not None:
                 batch = agent.rb.sample_prioritized(cfg.batch_size, prio_beta, **chain)
