@@ -402,7 +402,20 @@ int sactd3_step_period(sactd3_engine* e);
  * iterations that is not a multiple of the period).  Equal to sactd3_step(e, 1) followed by m - 1 sactd3_step(e, 0), bit for bit.
  * Same preconditions as sactd3_step_period. */
 int sactd3_step_prefix(sactd3_engine* e, int m);
-/* Capture and instantiate the hipGraphs of sactd3_step / sactd3_step_period now rather than at their first use (the reference's
+/* k >= 1 whole periods: equal to k sactd3_step_period calls -- k * (actor_update_delay + 1) sactd3_step calls -- bit for bit, host
+ * state included.  Where the period graph has its pipelined form, runs of R consecutive periods go out as ONE graph launch (R: an even
+ * build constant, 2 as shipped, at most 8; the node sequence of a run is that of R period graphs one behind the other, no kernel and no launch
+ * argument differs), so the idle time between two graph replays is paid once per R periods; what is left of k below R goes out as
+ * single period graphs.  Elsewhere the call loops over sactd3_step_period; with use_graphs == 0 the same launches are issued eagerly.
+ * It writes the actor parameters (see sactd3_predict_begin), and it acts with the updated ones: a sactd3_predict or a
+ * sactd3_predict_begin behind it waits for every launch the call issued, a whole run of R periods at the least -- R times the acting
+ * latency behind one sactd3_step_period.  A loop that acts every iteration issues its iterations with sactd3_step, as before.
+ * SACTD3_EINVAL: k < 1.  SACTD3_ESTATE as for sactd3_step_period (empty buffer; SAC with crit_targ_update_freq != 1).  A refused
+ * call changes nothing. */
+int sactd3_step_periods(sactd3_engine* e, int k);
+/* out = {sactd3_step_periods calls, run-graph launches, single-period launches made inside those calls, run graphs captured} */
+int sactd3_step_periods_stats(sactd3_engine* e, int64_t out[4]);
+/* Capture and instantiate the hipGraphs of sactd3_step / sactd3_step_period / sactd3_step_periods now rather than at their first use (the reference's
  * CudaGraphModule captures after a warm-up inside the loop, orchestrator.py:313-315); nothing is launched, no state changes. */
 int sactd3_instantiate_graphs(sactd3_engine* e);
 /* Agent.predict (agents/agent.py:172-181): obs [n, ob_dim] host -> actions [n, ac_dim] host.  Stream-ordered behind whatever
@@ -420,15 +433,15 @@ int sactd3_predict(sactd3_engine* e, const float* obs, int n, int explore, float
  * Order between the two streams is decided on the host and kept with events, only where the acting kernels (which read the actor
  * parameters, the action bounds, their own scratch and their own control words) meet a learner call:
  *   learner -> acting: if a call that writes the actor parameters was issued on the learner stream since the acting stream last
- *     waited for it (sactd3_update_actor, sactd3_step with actor updates, sactd3_step_period, sactd3_step_prefix,
+ *     waited for it (sactd3_update_actor, sactd3_step with actor updates, sactd3_step_period, sactd3_step_periods, sactd3_step_prefix,
  *     sactd3_set_params(ACTOR), sactd3_time_nodes), or a sactd3_predict_device call (its queued kernels use the acting scratch), or if flags has SACTD3_ACT_AFTER_ALL, `begin` makes the acting stream wait for
  *     everything issued on the learner stream so far -- as sactd3_predict does.  Otherwise it waits for nothing: behind a
  *     critic-only iteration the action comes from the same parameters either way.
  *   acting -> learner: while a call is in flight (begun, not ended) the first of the calls above makes the learner stream wait for
  *     the acting kernels, so the actor is not overwritten under a running predict.  After `end` nothing is inserted.
  *   Critic-only sactd3_step, sactd3_update_qnets, sactd3_update_targ_nets, sactd3_rb_* neither wait nor are waited for.
- * A period graph (sactd3_step_period / _prefix) contains actor updates, so a `begin` behind one waits for all of it: the overlap
- * pays with single-iteration sactd3_step loops.
+ * A period graph (sactd3_step_period / _prefix) contains actor updates, so a `begin` behind one waits for all of it -- behind
+ * sactd3_step_periods for the whole run: the overlap pays with single-iteration sactd3_step loops.
  * One call in flight at most.  While one is, a second `begin`, sactd3_predict, and sactd3_set_noise / _clear_noise / _read_noise on
  * SACTD3_SITE_PREDICT return SACTD3_ESTATE; so does `end` without a `begin`.  sactd3_sync and sactd3_destroy drain the acting
  * stream too (after sactd3_sync the call is still to be collected with `end`). */
@@ -515,6 +528,7 @@ const char* sactd3_debug_names(void);
 /* number of kernel nodes in the instantiated graph of: 0 update_qnets, 1 update_actor, 2 step(do_actor=0), 3 step(do_actor=1), 4 step_period,
  * 5 the opening graph of a period that cannot use a precomputed opening pair, 6 / 7 step_prefix(1) / step_prefix(2),
  * 8 update_qnets in its weighted form (0 until its first use; the same count as 0),
+ * 10 the run graph of sactd3_step_periods (R times the count of 4; 0 until captured; 9 names no graph),
  * 16 + 2 do_actor + (1 with the target update): sactd3_step_sampled's graphs for its current (draw, n_step, stride), 0 until captured */
 int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
 /* average device time in microseconds of `iters` back-to-back launches of one kernel of the path,

@@ -40,6 +40,7 @@ SYMBOLS = [
     "sactd3_rb_sample_nstep_device", "sactd3_rb_sample_nstep", "sactd3_rb_sample_prioritized_nstep", "sactd3_nstep_info_device",
     "sactd3_nstep_stats",
     "sactd3_step_sampled", "sactd3_step_sampled_stats",
+    "sactd3_step_periods", "sactd3_step_periods_stats",
 ]
 
 
@@ -163,6 +164,8 @@ def load_library():
         "sactd3_nstep_stats": (C.c_int, [vp, i64p]),
         "sactd3_step_sampled": (C.c_int, [vp, C.c_int, C.POINTER(CSampling)]),
         "sactd3_step_sampled_stats": (C.c_int, [vp, i64p]),
+        "sactd3_step_periods": (C.c_int, [vp, C.c_int]),
+        "sactd3_step_periods_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -207,6 +207,11 @@ struct sactd3_engine {
   int ss_key[3] = {0, 0, 0};
   int64_t ss_beta_bits = -1; int ss_inject = -1;
   int64_t ss_stats[2] = {};
+  // Runs of whole periods as one graph launch (sactd3_step_periods): RUN_PERIODS consecutive pipelined periods, one executable graph
+  // per start variant (the run that starts on variant v leaves chain_ready == v behind: RUN_PERIODS is even).
+  // run_stats: {calls, run launches, single-period launches made inside those calls, run graphs captured}.
+  hipGraphExec_t run_graphs[2] = {}; int run_nodes[2] = {};
+  int64_t run_stats[4] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -1561,6 +1566,7 @@ void sactd3_destroy(sactd3_engine* e) {
   if (e->act_stream) hipStreamSynchronize(e->act_stream);
   for (auto& g : e->graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->ss_graphs) if (g) hipGraphExecDestroy(g);
+  for (auto& g : e->run_graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_dev_graphs) if (g) hipGraphExecDestroy(g);
   for (auto ev : e->events) hipEventDestroy(ev);
@@ -2735,6 +2741,71 @@ int sactd3_step_prefix(sactd3_engine* e, int m) {
   return 0;
 }
 
+// Runs of whole periods.  The device idles for a few microseconds between the last node of one graph replay and the first of the next
+// (DESIGN.md 8), so a loop of period graphs pays that once per period; a graph that holds RUN_PERIODS consecutive pipelined periods
+// pays it once per run.  RUN_PERIODS is even, so a run ends on the variant it started on, and at most 8 (make RUN=<R>).
+#ifndef SACTD3_RUN_PERIODS
+#define SACTD3_RUN_PERIODS 2
+#endif
+static const int RUN_PERIODS = SACTD3_RUN_PERIODS;
+static_assert(RUN_PERIODS >= 2 && RUN_PERIODS <= 8 && RUN_PERIODS % 2 == 0, "SACTD3_RUN_PERIODS: an even number of periods, 2 .. 8");
+// RUN_PERIODS pipelined periods from variant v on, as one sequence: what enqueue_period(x, v, n), enqueue_period(x, 1 - v, n), ...
+// issue one behind the other -- a period leaves nothing deferred behind, so the launches are those of the single periods, one for one
+static int enqueue_period_run(EnqCtx& x, int v) {
+  for (int r = 0; r < RUN_PERIODS; ++r) {
+    RCCHK(enqueue_period(x, (v + r) & 1, x.e->cfg.actor_update_delay + 1));
+    if (x.alpha_pending || x.alpha_tick_owed) return x.e->fail(SACTD3_ESTATE, "period run: a period left a deferred temperature step behind");
+  }
+  return 0;
+}
+static int run_period_graph(sactd3_engine* e, int v, bool launch) {
+  const bool had = e->run_graphs[v] != nullptr;
+  RCCHK(run_graph_slot(e, &e->run_graphs[v], &e->run_nodes[v], [&](EnqCtx& x) { return enqueue_period_run(x, v); }, launch));
+  if (!had && e->run_graphs[v]) ++e->run_stats[3];
+  return 0;
+}
+
+// k whole periods: equal to k sactd3_step_period calls, bit for bit, with the pipelined form's periods going out RUN_PERIODS to a
+// graph launch and what is left of k below that through the single-period graphs.  The host state moves launch by launch, so a
+// launch that fails leaves it where the launches that were issued put it.
+int sactd3_step_periods(sactd3_engine* e, int k) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (k < 1) return e->fail(SACTD3_EINVAL, "step_periods: k >= 1");
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step_periods: buffer is empty");
+  if (!e->cfg.prefer_td3_over_sac && e->cfg.crit_targ_update_freq != 1) return e->fail(SACTD3_ESTATE, "step_periods: needs crit_targ_update_freq == 1");
+  ++e->run_stats[0];
+  if (!period_is_pipelined(e)) {      // no chained form: the periods one by one
+    for (int i = 0; i < k; ++i) { RCCHK(sactd3_step_period(e)); ++e->run_stats[2]; }
+    return 0;
+  }
+  const int n = e->cfg.actor_update_delay + 1;
+  RCCHK(actor_write_begin(e));
+  mark_grads_stale(e);
+  int v = e->chain_ready >= 0 ? e->chain_ready : 0;
+  const bool have = e->chain_ready >= 0;
+  e->chain_ready = -1;
+  if (!have) RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }));
+  for (int left = k; left > 0;) {
+    const int periods = left >= RUN_PERIODS ? RUN_PERIODS : 1;
+    if (periods > 1) RCCHK(run_period_graph(e, v, true));
+    else RCCHK(run_graph(e, v ? G_PERIOD_B : G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, v, n); }));
+    ++e->run_stats[periods > 1 ? 1 : 2];
+    const int last = (v + periods - 1) & 1;      // the variant of the last period issued
+    v = 1 - last;
+    left -= periods;
+    e->qnet_updates += (int64_t)periods * n;
+    slot_trained(e, period_slot(true, last, n - 1), true);
+    e->chain_ready = left > 0 ? -1 : v;      // (named only once the call is through: a failure in between leaves no pair to rely on)
+  }
+  return 0;
+}
+int sactd3_step_periods_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = e->run_stats[i];
+  return 0;
+}
+
 // Capture + instantiate the graphs of sactd3_step (both schedules, with the target update) and sactd3_step_period now instead of
 // at their first use, without launching anything: a caller that times its first iterations (or must not stall in the loop) calls
 // this once after sactd3_create.  No-op with use_graphs == 0.
@@ -2755,6 +2826,7 @@ int sactd3_instantiate_graphs(sactd3_engine* e) {
       for (int m = 1; m <= e->cfg.actor_update_delay && m <= 2; ++m)
         for (int v = 0; v < 2; ++v)
           RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](EnqCtx& x) { return enqueue_period(x, v, m); }, false));
+      for (int v = 0; v < 2; ++v) RCCHK(run_period_graph(e, v, false));      // sactd3_step_periods: a run from either variant
     }
   }
   return 0;
@@ -3143,6 +3215,7 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph) {
   static const int map[9] = {G_Q, G_A, G_STEP01, G_STEP11, G_PERIOD, G_OPENING, G_PREFIX, G_PREFIX + 2, G_QW};
   // 16 + 2 do_actor + target update: the graphs of sactd3_step_sampled for its current (draw, n_step, stride); 0: not captured
   if (which_graph >= 16 && which_graph < 20) return e->ss_nodes[which_graph - 16];
+  if (which_graph == 10) return e->run_graphs[0] ? e->run_nodes[0] : e->run_nodes[1];      // the run graph of sactd3_step_periods; 0: not captured
   if (which_graph < 0 || which_graph > 8) return SACTD3_EINVAL;
   int w = map[which_graph];
   if (!e->graphs[w] && (which_graph == 2 || which_graph == 3)) w -= 1;   // the no-Polyak variant, if that is the one in use

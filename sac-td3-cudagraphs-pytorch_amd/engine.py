@@ -349,18 +349,32 @@ class Engine:
         """actor_update_delay + 1 iterations (actor updates in the first) as one graph launch."""
         self._ck(self.lib.sactd3_step_period(self._h))
 
+    def step_periods(self, k: int) -> None:
+        """sactd3_step_periods: k whole periods, bit for bit k step_period() calls; where the period graph is pipelined, runs of
+        several periods go out as one graph launch each."""
+        self._ck(self.lib.sactd3_step_periods(self._h, int(k)))
+
+    def step_periods_stats(self) -> Dict[str, int]:
+        """host counters of step_periods (sactd3_step_periods_stats)"""
+        return self._stats(self.lib.sactd3_step_periods_stats, ("calls", "run_launches", "single_period_launches", "run_graphs_captured"))
+
     def instantiate_graphs(self) -> None:
         """capture + instantiate the step / period graphs now instead of at their first use (nothing is launched)."""
         self._ck(self.lib.sactd3_instantiate_graphs(self._h))
 
     def run_iterations(self, i0: int, n: int) -> int:
         """iterations i0 .. i0 + n - 1 of the loop (orchestrator.py:337-352 schedule: actor updates when i % (delay + 1) == 0),
-        whole periods as one graph launch each, the rest one by one.  Returns i0 + n."""
+        whole periods as one graph launch each -- two or more of them in a row through step_periods(), where the engine has it --
+        the rest one by one.  Returns i0 + n."""
         period = self.cfg.actor_update_delay + 1
+        many = getattr(self, "step_periods", None)
         can = self.cfg.actor_update_delay > 0 and (self.cfg.prefer_td3_over_sac or self.cfg.crit_targ_update_freq == 1)
         i, end = i0, i0 + n
         while i < end:
-            if can and i % period == 0 and i + period <= end:
+            if can and i % period == 0 and i + 2 * period <= end and many is not None:
+                many((end - i) // period)
+                i += (end - i) // period * period
+            elif can and i % period == 0 and i + period <= end:
                 self.step_period()
                 i += period
             elif can and i % period == 0:          # what is left behind the last whole period: its first end - i iterations, one launch
