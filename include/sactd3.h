@@ -71,6 +71,8 @@ enum {
   SACTD3_M_ACTOR_LOSS = 1,
   SACTD3_M_ALPHA_LOSS = 2,
   SACTD3_M_ALPHA = 3,
+  SACTD3_M_BC_LOSS = 4,    /* TD3+BC only (sactd3_set_bc): the unweighted (1 / (B A)) sum (pi - a)^2 of the last actor update */
+  SACTD3_M_BC_LAMBDA = 5,  /* TD3+BC only: lambda = bc_alpha / max(mean |Q1(s, pi(s))|, 1e-8) of the last actor update       */
   SACTD3_NUM_METRICS = 8
 };
 
@@ -98,7 +100,7 @@ typedef struct sactd3_config {
   float clip_norm;                          /* sac.yml:34; <= 0 disables (agent.py:284) */
   float td3_std, td3_c, actor_noise_std;    /* td3.yml:45-48 */
   float adam_beta1, adam_beta2, adam_eps;   /* torch.optim.Adam defaults 0.9, 0.999, 1e-8 (agent.py:115-139) */
-  float reserved1;
+  float bc_alpha;               /* TD3+BC (sactd3_set_bc): > 0 turns the behaviour-cloning actor term on, for good; 0 (the default) = plain TD3 / SAC */
   uint64_t seed;                /* keys the engine's Philox4x32-10 streams (main.py:145-146 seeds torch instead) */
 } sactd3_config;
 
@@ -507,6 +509,29 @@ int sactd3_qvalues_device(sactd3_engine* e, const float* obs, int64_t obs_ld, co
 int sactd3_qvalues(sactd3_engine* e, const float* obs, const float* actions, int n, int which, float* q);
 /* host counters: out = {calls, rows, calls that inserted event waits, calls in the policy form (actions == NULL)} */
 int sactd3_qvalues_stats(const sactd3_engine* e, int64_t out[4]);
+
+/* ---- TD3+BC (Fujimoto & Gu 2021): the behaviour-cloning actor term that lets the TD3 engine train on a FIXED dataset -- the workload
+ * of the run-ahead modes (sactd3_step_period / sactd3_step_periods), which no ring append interrupts.  An engine created with
+ * sactd3_config::bc_alpha > 0 (TD3 only: SACTD3_EINVAL with prefer_td3_over_sac == 0; NaN, infinite or negative: SACTD3_EINVAL) runs
+ * sactd3_update_actor, in every entry point that contains it, on the loss
+ *     lambda  = bc_alpha / max(mean_b |q_b|, 1e-8)                   q_b = Q1(s_b, pi_b), online critic 1; lambda is a constant of the backward pass
+ *     bc      = (1 / (B A)) sum_b sum_j (pi_bj - a_bj)^2             pi = actor(s), a_b = the action stored in the batch slot, A = ac_dim
+ *     L_actor = -lambda mean_b q_b + bc_weight bc
+ *     dL/dpi_bj = lambda (-1/B) dq_b/da_j + bc_weight 2 (pi_bj - a_bj) / (B A)
+ * (bc_weight = 1 and bc_alpha = 2.5 are the paper's form.)  The 1e-8 floor is this engine's own guard, not the paper's: a batch whose
+ * q are all 0 must not poison a parameter.  Nothing else of the update changes: critic update, smoothing noise, Polyak, clip_norm, the
+ * loss weights (actor updates stay unweighted) and n-step staging are as before, and so is every graph's node count -- the term lives
+ * in BC forms of the head-backward launch and of the launch that finalises the actor loss; an engine with bc_alpha == 0 launches
+ * exactly the kernels it launched before.  Metrics: SACTD3_M_ACTOR_LOSS = L_actor, SACTD3_M_BC_LOSS = bc (unweighted),
+ * SACTD3_M_BC_LAMBDA = lambda; an engine without BC never writes the last two.  Normalising the dataset's states (the paper does) is
+ * the caller's business: the engine trains on the rows it is given.
+ * sactd3_set_bc: new (bc_alpha > 0, bc_weight >= 0), both finite, else SACTD3_EINVAL with nothing changed; SACTD3_ESTATE on an engine
+ * created with bc_alpha == 0 (the kernel forms are chosen at create).  Both values live in device memory beside the other control
+ * words and are read there by the kernels: a change costs one single-thread launch on the learner stream, never a graph capture, and
+ * does not break the run-ahead chain of sactd3_step_period(s) (nothing that ran ahead depends on them).  bc_weight starts at 1 and is
+ * run-time state: not part of sactd3_config. */
+int sactd3_set_bc(sactd3_engine* e, float bc_alpha, float bc_weight);
+int sactd3_get_bc(sactd3_engine* e, float out[2]);                         /* (bc_alpha, bc_weight) as the device holds them [sync] */
 
 int sactd3_read_metrics(sactd3_engine* e, float out[SACTD3_NUM_METRICS]);  /* [sync] */
 /* The engine's HIP stream (hipStream_t) and the DEVICE address of the metrics slots, for callers that want the values the

@@ -13,6 +13,7 @@ ABI_VERSION = 1
 ACTOR, CRITICS, ACTOR_TARGET, CRITICS_TARGET, LOG_ALPHA = range(5)
 SITE_CRITIC, SITE_ACTOR0, SITE_ACTOR1, SITE_ALPHA0, SITE_ALPHA1, SITE_PREDICT = range(6)
 NUM_METRICS = 8
+M_QF_LOSS, M_ACTOR_LOSS, M_ALPHA_LOSS, M_ALPHA, M_BC_LOSS, M_BC_LAMBDA = range(6)   # metrics slots (SACTD3_M_*); the last two: TD3+BC only
 ACT_AFTER_ALL = 1   # sactd3_predict_begin flags
 SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device / sactd3_predict_device / sactd3_qvalues_device / sactd3_rb_sample_indices_device / sactd3_batch_weights_device flags
 DST_ORDERED = 1     # sactd3_read_batch_device / sactd3_rb_read_rows_device / sactd3_td_errors_device flags (the same bit, the same two events)
@@ -41,6 +42,7 @@ SYMBOLS = [
     "sactd3_nstep_stats",
     "sactd3_step_sampled", "sactd3_step_sampled_stats",
     "sactd3_step_periods", "sactd3_step_periods_stats",
+    "sactd3_set_bc", "sactd3_get_bc",
 ]
 
 
@@ -54,7 +56,7 @@ class CConfig(C.Structure):
         "layer_norm", "autotune", "bcq_style_targ_mix", "targ_actor_smoothing", "actor_update_delay",
         "crit_targ_update_freq", "use_graphs", "device_id", "reserved0")] + [(n, C.c_float) for n in (
         "actor_lr", "qnets_lr", "log_alpha_lr", "gamma", "polyak", "alpha_init", "clip_norm", "td3_std", "td3_c",
-        "actor_noise_std", "adam_beta1", "adam_beta2", "adam_eps", "reserved1")] + [("seed", C.c_uint64)]
+        "actor_noise_std", "adam_beta1", "adam_beta2", "adam_eps", "bc_alpha")] + [("seed", C.c_uint64)]
 
 
 class CDeviceFields(C.Structure):
@@ -166,6 +168,8 @@ def load_library():
         "sactd3_step_sampled_stats": (C.c_int, [vp, i64p]),
         "sactd3_step_periods": (C.c_int, [vp, C.c_int]),
         "sactd3_step_periods_stats": (C.c_int, [vp, i64p]),
+        "sactd3_set_bc": (C.c_int, [vp, C.c_float, C.c_float]),
+        "sactd3_get_bc": (C.c_int, [vp, fp]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

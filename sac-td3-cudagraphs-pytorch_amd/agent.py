@@ -268,7 +268,8 @@ class _DeviceScalar:
         self.__cuda_array_interface__ = {"shape": (), "typestr": "<f4", "data": (int(ptr), False), "version": 3, "strides": None}
 
 
-_METRIC_SLOT = {"loss/qf_loss": 0, "loss/actor_loss": 1, "loss/alpha_loss": 2, "vitals/alpha": 3}   # SACTD3_M_*
+_METRIC_SLOT = {"loss/qf_loss": 0, "loss/actor_loss": 1, "loss/alpha_loss": 2, "vitals/alpha": 3,
+                "loss/bc_loss": 4, "vitals/bc_lambda": 5}   # SACTD3_M_* (the last two: written by a TD3+BC engine only)
 
 
 def _bump_generation(engine: Engine) -> int:
@@ -708,6 +709,8 @@ class Agent:
             if self.engine.cfg.autotune:
                 keys.append("loss/alpha_loss")
             keys.append("vitals/alpha")
+        if self.engine.cfg.bc_alpha > 0:      # TD3+BC (hps.bc_alpha): the unweighted BC term and lambda of this update
+            keys += ["loss/bc_loss", "vitals/bc_lambda"]
         return self._results(keys)
 
     def update_targ_nets(self) -> None:

@@ -212,6 +212,13 @@ struct sactd3_engine {
   // run_stats: {calls, run launches, single-period launches made inside those calls, run graphs captured}.
   hipGraphExec_t run_graphs[2] = {}; int run_nodes[2] = {};
   int64_t run_stats[4] = {};
+  // TD3+BC (sactd3_config::bc_alpha > 0 at create; kernels.h: BcArgs).  bc_on picks the BC forms of the head-backward launch and of the
+  // actor's weight-gradient launch, for good; bc_alpha / bc_weight mirror DevCtl::bc, which is what the kernels read (sactd3_set_bc
+  // republishes it with one launch: no captured graph holds a value).  bc_part [nblk4]: the head backward's partial sums of (pi - a)^2,
+  // made at create only when bc_on -- an engine without BC holds nothing more than before.
+  bool bc_on = false;
+  float bc_alpha = 0.f, bc_weight = 1.f;
+  float* bc_part = nullptr;
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -489,7 +496,7 @@ static AdamRedArgs adam_red_args(const TnArgs& g, int nets, long g_ns, int tick_
 }
 // Large batches: split-M GEMM into partial slabs (k_tn64) + slab sum / vector gradients / Adam / Polyak (k_adam_red).
 // (called by launch_tn, which has set g.keep_g)
-static int launch_tn64(EnqCtx& x, const char* name, const TnArgs& g, int nets, int tick_extra = 0) {
+static int launch_tn64(EnqCtx& x, const char* name, const TnArgs& g, int nets, int tick_extra = 0, const BcFin* bf = nullptr) {
   sactd3_engine* e = x.e;
   Tn64Args a{};
   a.nprob = g.nprob; a.M = g.M; a.nets = nets; a.Gp = e->Gp; a.g_ns = nets > 1 ? g.g_ns : (long)e->La.size;
@@ -523,7 +530,11 @@ static int launch_tn64(EnqCtx& x, const char* name, const TnArgs& g, int nets, i
   const dim3 grid((unsigned)((size / 4 + 255) / 256 + 4 * r.nvec + 1), (unsigned)nets);
   const char* rname = g.apply ? (g.T ? "k_adam_red.sum+adam+polyak" : "k_adam_red.sum+adam") : "k_adam_red.sum";
   const double rbytes = nets * (double)size * (4.0 * S + 4.0 + (g.apply ? 24.0 : 0.0) + (g.apply && g.T ? 8.0 : 0.0));
-  if (r.keep_g) LAUNCH(rname, 0.0, rbytes, k_adam_red<true>, grid, dim3(256), r);
+  if (bf) {      // TD3+BC: the instance whose last tail block finalises the BC loss
+    const char* bname = g.apply ? (g.T ? "k_adam_red_bc.sum+adam+polyak" : "k_adam_red_bc.sum+adam") : "k_adam_red_bc.sum";
+    if (r.keep_g) LAUNCH(bname, 0.0, rbytes, k_adam_red_bc<true>, grid, dim3(256), r, *bf);
+    else LAUNCH(bname, 0.0, rbytes, k_adam_red_bc<false>, grid, dim3(256), r, *bf);
+  } else if (r.keep_g) LAUNCH(rname, 0.0, rbytes, k_adam_red<true>, grid, dim3(256), r);
   else LAUNCH(rname, 0.0, rbytes, k_adam_red<false>, grid, dim3(256), r);
   (void)name;
   return 0;
@@ -535,7 +546,8 @@ static inline int tn_width(const TnProb& q) { return q.kw > 0 ? q.kw : q.ldw; }
 // vs 14.4 us)
 static bool tn_is_tiled64(const sactd3_engine* e, int M, int tiles64) { return M >= BIG_BATCH && e->Gp && tiles64 >= e->num_cus / 2; }
 static inline int tn64_tiles(int N, int ldw) { return ((N + TN64_N - 1) / TN64_N) * ((ldw + TN64_K - 1) / TN64_K); }
-static int launch_tn(EnqCtx& x, const char* name, TnArgs& g, int nets, int tick_extra = 0) {
+// bf != nullptr (TD3+BC actor launch): the k_tn_bc / k_adam_red_bc instances; g.loss_dst is NULL then, BcFin names the slots
+static int launch_tn(EnqCtx& x, const char* name, TnArgs& g, int nets, int tick_extra = 0, const BcFin* bf = nullptr) {
   sactd3_engine* e = x.e;
   const hipStream_t s = x.s;
   g.keep_g = !(x.lean_stores && g.apply);      // (see sactd3_engine::grads_stale)
@@ -543,7 +555,7 @@ static int launch_tn(EnqCtx& x, const char* name, TnArgs& g, int nets, int tick_
   {
     int tiles = 0;
     for (int i = 0; i < g.nprob; ++i) tiles += tn64_tiles(g.pr[i].N, g.pr[i].ldw);
-    if (tn_is_tiled64(e, g.M, tiles * nets)) return launch_tn64(x, name, g, nets, tick_extra);
+    if (tn_is_tiled64(e, g.M, tiles * nets)) return launch_tn64(x, name, g, nets, tick_extra, bf);
   }
   auto count = [&](int kt) {
     int tiles = 0;
@@ -570,14 +582,27 @@ static int launch_tn(EnqCtx& x, const char* name, TnArgs& g, int nets, int tick_
   bool fold = false;
   for (int i = 0; i < g.nprob; ++i) fold = fold || g.pr[i].fold;
   char inst[96];
-  snprintf(inst, sizeof(inst), fold ? "k_tn<%d,true>.%s" : "k_tn<%d>.%s", kt, name);
+  if (bf) snprintf(inst, sizeof(inst), fold ? "k_tn_bc<%d,true>.%s" : "k_tn_bc<%d>.%s", kt, name);
+  else snprintf(inst, sizeof(inst), fold ? "k_tn<%d,true>.%s" : "k_tn<%d>.%s", kt, name);
   g.tiles = tiles;
   if (g.pk_blocks) by += 12.0 * (g.pk.n0 + g.pk.n1);
   g.fin = adam_red_args(g, nets, g.g_ns, tick_extra);      // what is not a GEMM tile goes to riding blocks (see TnArgs::fin)
   g.fin_blocks = 4 * g.fin.nvec + 1;
   const dim3 grid((unsigned)((tiles + g.pk_blocks + g.fin_blocks + (nets > 1 ? 7 : 0)) & (nets > 1 ? ~7 : ~0)), 1, (unsigned)nets);
   if (!node_on(x, inst, fl, by, grid, dim3(256))) return 0;
-  if (g.keep_g) {
+  if (bf) {
+    if (g.keep_g) {
+      if (fold) {
+        if (kt == 2) launch_k_tn_bc<2, true, true>(grid, s, g, *bf);
+        else launch_k_tn_bc<1, true, true>(grid, s, g, *bf);
+      } else if (kt == 2) launch_k_tn_bc<2, false, true>(grid, s, g, *bf);
+      else launch_k_tn_bc<1, false, true>(grid, s, g, *bf);
+    } else if (fold) {
+      if (kt == 2) launch_k_tn_bc<2, true, false>(grid, s, g, *bf);
+      else launch_k_tn_bc<1, true, false>(grid, s, g, *bf);
+    } else if (kt == 2) launch_k_tn_bc<2, false, false>(grid, s, g, *bf);
+    else launch_k_tn_bc<1, false, false>(grid, s, g, *bf);
+  } else if (g.keep_g) {
     if (fold) {
       if (kt == 2) launch_k_tn<2, true, true>(grid, s, g);
       else launch_k_tn<1, true, true>(grid, s, g);
@@ -1144,6 +1169,12 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
     h.log_alpha = e->la; h.scale = e->scale; h.P = e->Pa; h.L = e->La; h.xh2 = e->a_xh2; h.rstd2 = e->a_rs2; h.h2 = e->a_h2;
     h.B = B; h.a = e->a; h.ln = ln; h.sac = !td3; h.du = e->a_du; h.ldu = e->ldu; h.dz2 = e->a_dz2;
     h.part = e->part;
+    // TD3+BC: the same launch in its BC form (kernels.h, BcArgs) -- the dataset action from the batch slot this iteration trains on
+    BcArgs bk{};
+    if (e->bc_on) {
+      bk.ctl = e->ctl->bc; bk.q = e->q_pi; bk.pi = e->Xp; bk.act = SX; bk.ld = e->ldc; bk.off = e->o;
+      bk.inv_ba = 1.0f / ((float)B * (float)e->a); bk.part = e->bc_part; bk.lam = &e->ctl->metrics[SACTD3_M_BC_LAMBDA];
+    }
     if (fused_head_nn) {   // column partials per 16-row block
       HeadBwdNn f{};
       f.c = h; f.Wt = e->Pa + e->La.W2; f.ldw = HID; f.dX = e->a_dh1;
@@ -1153,13 +1184,20 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
       }
       f.f.fold = fold_ln1; f.f.ln = ln; f.f.h1 = e->a_h1; f.f.xh1 = e->a_xh1; f.f.g1_off = e->La.g1; f.f.ps = e->a_ps; f.f.gsnap = e->a_ps + (long)B * PS_W;
       f.xr = pick_xr(e->nblk, HID / 16, 4.0 * 2 * B * HID, 4.0 * HID * HID);
-      LAUNCH("k_headbwd_nn", 2.0 * B * (double)HID * e->nh + 2.0 * (double)B * HID * HID,
-             4.0 * (3.0 * BH + (double)e->nh * HID + (double)B * (nq * e->a + 4 * e->a + e->nh)) + 4.0 * ((double)HID * HID + (double)B * HID),
-             k_headbwd_nn, dim3((unsigned)(e->nblk * (HID / 16))), dim3(256), f);
-    } else if (small_head) LAUNCH("k_actor_head_bwd_s<4>", 2.0 * B * (double)HID * e->nh, 4.0 * (3.0 * BH + (double)e->nh * HID + (double)B * (nq * e->a + 4 * e->a + e->nh)),
-                           k_actor_head_bwd_s<4>, dim3(e->nblk4), dim3(64), h);
-    else LAUNCH("k_actor_head_bwd", 2.0 * B * (double)HID * e->nh, 4.0 * (3.0 * BH + (double)e->nh * HID + (double)B * (nq * e->a + 4 * e->a + e->nh)),
-                k_actor_head_bwd, dim3(e->nblk), dim3(256), h);
+      const double fl = 2.0 * B * (double)HID * e->nh + 2.0 * (double)B * HID * HID;
+      const double by = 4.0 * (3.0 * BH + (double)e->nh * HID + (double)B * (nq * e->a + 4 * e->a + e->nh)) + 4.0 * ((double)HID * HID + (double)B * HID);
+      if (e->bc_on) LAUNCH("k_headbwd_nn_bc", fl, by + 4.0 * B * (2.0 * e->a + 1), k_headbwd_nn_bc, dim3((unsigned)(e->nblk * (HID / 16))), dim3(256), f, bk);
+      else LAUNCH("k_headbwd_nn", fl, by, k_headbwd_nn, dim3((unsigned)(e->nblk * (HID / 16))), dim3(256), f);
+    } else {
+      const double fl = 2.0 * B * (double)HID * e->nh, by = 4.0 * (3.0 * BH + (double)e->nh * HID + (double)B * (nq * e->a + 4 * e->a + e->nh));
+      if (small_head) {
+        // (the plain instance is named first: template instances are emitted in the order they are first named, and the helpers two
+        //  instances share are emitted with the first -- the other way round the plain kernel's machine code changed)
+        if (!e->bc_on) LAUNCH("k_actor_head_bwd_s<4>", fl, by, k_actor_head_bwd_s<4>, dim3(e->nblk4), dim3(64), h);
+        else LAUNCH("k_actor_head_bwd_s_bc<4>", fl, by + 4.0 * B * (2.0 * e->a + 1), k_actor_head_bwd_s_bc<4>, dim3(e->nblk4), dim3(64), h, bk);
+      } else if (e->bc_on) LAUNCH("k_actor_head_bwd_bc", fl, by + 4.0 * B * (2.0 * e->a + 1), k_actor_head_bwd_bc, dim3(e->nblk), dim3(256), h, bk);
+      else LAUNCH("k_actor_head_bwd", fl, by, k_actor_head_bwd, dim3(e->nblk), dim3(256), h);
+    }
   }
   if (!fused_head_nn) {
     NnArgs g{};
@@ -1193,7 +1231,15 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
     g.b1 = c.adam_beta1; g.b2 = c.adam_beta2; g.eps = c.adam_eps;
     g.loss_part = e->part_sa; g.loss_n = e->nblk4; g.loss_stride = 2; g.loss_off = 1; g.loss_scale = 1.0f / (float)B;
     g.loss_dst = &e->ctl->metrics[SACTD3_M_ACTOR_LOSS]; g.tick = (td3 && !clip) ? &e->ctl->noise_ctr : nullptr;
-    RCCHK(launch_tn(x, clip ? "dW" : (polyak_targ ? "dW+adam+polyak" : "dW+adam"), g, 1));
+    BcFin bf{};
+    if (e->bc_on) {      // the loss is finalised from the two kinds of partials and lambda (kernels.h, bc_loss_finish)
+      bf.q_part = e->part_sa; bf.q_n = e->nblk4; bf.bc_part = e->bc_part; bf.bc_n = e->nblk4;
+      bf.inv_b = 1.0f / (float)B; bf.inv_ba = 1.0f / ((float)B * (float)e->a);
+      bf.ctl = e->ctl->bc; bf.lam = &e->ctl->metrics[SACTD3_M_BC_LAMBDA];
+      bf.loss_dst = &e->ctl->metrics[SACTD3_M_ACTOR_LOSS]; bf.bc_dst = &e->ctl->metrics[SACTD3_M_BC_LOSS];
+      g.loss_dst = nullptr;
+    }
+    RCCHK(launch_tn(x, clip ? "dW" : (polyak_targ ? "dW+adam+polyak" : "dW+adam"), g, 1, 0, e->bc_on ? &bf : nullptr));
   }
   if (clip) {
     NormArgs n{e->Ga, (long)e->La.size, c.clip_norm, e->gscale};
@@ -1588,6 +1634,8 @@ static int create_impl(sactd3_engine* e, const float* min_ac, const float* max_a
   if (c.batch_size < 1 || c.rb_capacity < 1 || c.max_envs < 1) return e->fail(SACTD3_EINVAL, "batch_size, rb_capacity, max_envs must be positive");
   if (c.actor_update_delay < 0 || c.crit_targ_update_freq < 1) return e->fail(SACTD3_EINVAL, "actor_update_delay >= 0 and crit_targ_update_freq >= 1 required");
   if (!min_ac || !max_ac) return e->fail(SACTD3_EINVAL, "min_ac / max_ac required");
+  if (!(c.bc_alpha >= 0.f) || !std::isfinite(c.bc_alpha)) return e->fail(SACTD3_EINVAL, "bc_alpha must be finite and >= 0");
+  if (c.bc_alpha > 0.f && !c.prefer_td3_over_sac) return e->fail(SACTD3_EINVAL, "bc_alpha > 0 needs a TD3 engine (prefer_td3_over_sac): SAC has no behaviour-cloning form");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return e->fail(SACTD3_ENODEV, "no HIP device visible");
   if (c.device_id < 0 || c.device_id >= ndev) return e->fail(SACTD3_EINVAL, "device_id out of range");
@@ -1654,6 +1702,8 @@ static int create_impl(sactd3_engine* e, const float* min_ac, const float* max_a
     RCCHK(dalloc(e, &e->Gp, (size_t)e->gp_slabs * std::max<size_t>(2 * (size_t)e->Lc.size, e->La.size)));
   }
   RCCHK(dalloc(e, &e->part, 2 * (size_t)e->nblk4 * NSLOT * HID)); RCCHK(dalloc(e, &e->part_s, 2 * (size_t)e->nblk4 * 2)); RCCHK(dalloc(e, &e->part_sa, (size_t)e->nblk4 * 2));
+  e->bc_on = c.bc_alpha > 0.f; e->bc_alpha = c.bc_alpha; e->bc_weight = 1.f;
+  if (e->bc_on) RCCHK(dalloc(e, &e->bc_part, (size_t)e->nblk4));
   RCCHK(dalloc(e, &e->p_x, (size_t)e->maxn * e->ldo)); RCCHK(dalloc(e, &e->p_z1, (size_t)e->maxn * HID));
   RCCHK(dalloc(e, &e->p_z2, (size_t)e->maxn * HID)); RCCHK(dalloc(e, &e->p_act, (size_t)e->maxn * e->a4));
   RCCHK(halloc(e, &e->h_obs, (size_t)e->maxn * e->ldo)); RCCHK(halloc(e, &e->h_act, (size_t)e->maxn * e->a4));
@@ -1676,6 +1726,7 @@ static int create_impl(sactd3_engine* e, const float* min_ac, const float* max_a
   DevCtl hc{};
   hc.seed = c.seed;
   hc.pw_q[0] = hc.pw_q[1] = hc.pw_a[0] = hc.pw_a[1] = hc.pw_l[0] = hc.pw_l[1] = 1.0;
+  hc.bc[0] = e->bc_alpha; hc.bc[1] = e->bc_weight;
   HIPCHK(hipMemcpy(e->ctl, &hc, sizeof(hc), hipMemcpyHostToDevice));
   const float la0[4] = {logf(c.alpha_init), 0.f, 0.f, 0.f};   // agents/agent.py:128
   HIPCHK(hipMemcpy(e->la, la0, sizeof(la0), hipMemcpyHostToDevice));
@@ -3134,6 +3185,31 @@ int sactd3_read_metrics(sactd3_engine* e, float out[SACTD3_NUM_METRICS]) {
   USE_DEVICE(e);
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipMemcpy(out, e->ctl->metrics, sizeof(float) * SACTD3_NUM_METRICS, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// TD3+BC: republish (bc_alpha, bc_weight) -- DevCtl::bc, two adjacent words -- with one single-thread launch on the learner stream, as
+// `beta` of the prioritised draw is.  The kernels read the words there, no graph holds a value, and nothing that ran ahead (the opening
+// pair of the next period: a next-action pass and a policy pass) depends on them: no CHAIN_BREAK, no capture.
+int sactd3_set_bc(sactd3_engine* e, float bc_alpha, float bc_weight) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (!e->bc_on) return e->fail(SACTD3_ESTATE, "set_bc: the engine was created with bc_alpha == 0 (the kernel forms are chosen at create)");
+  if (!(bc_alpha > 0.f) || !std::isfinite(bc_alpha)) return e->fail(SACTD3_EINVAL, "set_bc: bc_alpha must be finite and > 0");
+  if (!(bc_weight >= 0.f) || !std::isfinite(bc_weight)) return e->fail(SACTD3_EINVAL, "set_bc: bc_weight must be finite and >= 0");
+  int bits[2];
+  memcpy(&bits[0], &bc_alpha, sizeof(int)); memcpy(&bits[1], &bc_weight, sizeof(int));
+  hipLaunchKernelGGL(k_set_int2, dim3(1), dim3(1), 0, e->stream, reinterpret_cast<int*>(e->ctl->bc), bits[0], bits[1]);
+  HIPCHK(hipGetLastError());
+  e->bc_alpha = bc_alpha; e->bc_weight = bc_weight;
+  return 0;
+}
+
+int sactd3_get_bc(sactd3_engine* e, float out[2]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(out, e->ctl->bc, sizeof(float) * 2, hipMemcpyDeviceToHost));
   return 0;
 }
 

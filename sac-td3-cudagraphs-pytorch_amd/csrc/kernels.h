@@ -22,6 +22,8 @@
 //   k_actorq_tail     twin Q(s, pi(s)) -> min -> actor loss -> dQ routing -> head bwd -> LN bwd
 //   k_actor_head_bwd(_s)  d(action), d(logp) -> tanh-Gaussian bwd -> head bwd (MFMA; _s: DPP broadcast + FMAs) -> LN bwd
 //   k_ln_bwd          LN+ReLU backward of hidden layer 1 (+ the dQ/da slice product of the actor update)
+//   k_headbwd_nn_bc / k_actor_head_bwd_bc / k_actor_head_bwd_s_bc / k_tn_bc / k_adam_red_bc   TD3+BC twins of the head-backward kernels and of
+//                     the launch that finalises the actor loss (BcArgs / BcFin below; one body file each with its plain kernel)
 //   k_ctail_nn / k_qtail_nn / k_headbwd_nn   (B < 1024) a row kernel AND the dh1 = dz2 W2 GEMM behind it in one launch: every column-tile
 //                     block redoes the tail of its 16 rows; the epilogues leave what the next launch needs of layer 1's LayerNorm
 //                     backward (NnFold -> k_tn<.., true>) and of dQ/da (QaFold: per-tile partial sums by MFMA, finished in k_headbwd_nn)
@@ -105,10 +107,15 @@ struct DevCtl {
   // is negative, NaN or infinite): behind everything else again, so no existing offset moves (sactd3_priority_stats)
   alignas(128) int priority_refused;
   int pad_priority[31];
+  // ... and the two TD3+BC words (sactd3_set_bc): (bc_alpha, bc_weight), read by the BC kernel forms, written by a single-thread launch on
+  // the learner stream only.  Behind everything else once more: no existing offset moves.
+  alignas(128) float bc[2];
+  int pad_bc[30];
 };
 static_assert(offsetof(DevCtl, predict_ctr) % 128 == 0 && sizeof(DevCtl) % 128 == 0, "acting words need a line of their own");
 static_assert(offsetof(DevCtl, readout_refused) % 128 == 0 && offsetof(DevCtl, readout_refused) == offsetof(DevCtl, predict_ctr) + 128, "the read-out word sits behind the existing ones");
 static_assert(offsetof(DevCtl, priority_refused) == offsetof(DevCtl, readout_refused) + 128, "the priority word sits behind the read-out word");
+static_assert(offsetof(DevCtl, bc) == offsetof(DevCtl, priority_refused) + 128, "the BC words sit behind the priority word");
 
 struct NetLayout {   // float offsets inside one net's parameter block (all multiples of 4)
   int K, ld1, nh;
@@ -200,6 +207,60 @@ __device__ __forceinline__ float wave_sum(float v) {
   return (lane_bcast(v, 0) + lane_bcast(v, 16)) + (lane_bcast(v, 32) + lane_bcast(v, 48));
 }
 __device__ __forceinline__ float sum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
+// ---- TD3+BC (Fujimoto & Gu 2021; include/sactd3.h, sactd3_set_bc): the actor loss of an engine created with bc_alpha > 0 is
+//     L = -lambda mean_b q_b + bc_weight (1 / (B A)) sum_bj (pi_bj - a_bj)^2,   lambda = bc_alpha / max(mean_b |q_b|, 1e-8) (a constant)
+// so that the head backward's upstream gradient dA_bj (= -(1/B) dq_b/da_j, as the critic tail leaves it) becomes
+//     lambda dA_bj + bc_weight 2 (pi_bj - a_bj) / (B A)
+// -- the one place the BC forms of the three head-backward kernels (k_*_bc, HB_BC in their body files) differ from the plain ones.
+// lambda: EVERY WAVE of every block sums |q_pi[0][0 .. B)| itself, lane l taking q[l], q[l + 64], ... in this order and wave_sum
+// finishing: one fixed tree, the same bits everywhere in a launch, no atomics, no extra launch (B floats from L2: 1 KB at B = 256).
+// The 1e-8 floor is this engine's own guard (not the paper's): a batch whose q are all 0 must not poison a parameter.
+struct BcArgs {
+  const float* ctl;                      // DevCtl::bc = (bc_alpha, bc_weight)
+  const float* q;                        // q_pi[0][0 .. B): Q1(s_b, pi_b), online critic 1
+  const float* pi; const float* act;     // Xp = [s | pi(s)] and the batch slot's X = [s | a], both [B][ld]; the action sits in columns off .. off + A - 1
+  int ld, off;
+  float inv_ba;                          // 1 / (B A)
+  float* part;                           // [row blocks] this launch's partial sums of (pi - a)^2 (finished by bc_loss_finish)
+  float* lam;                            // metrics slot SACTD3_M_BC_LAMBDA, written once per launch
+};
+__device__ __forceinline__ float bc_abs_partial(const float* q, int B, int lane) {
+  float s = 0.f;
+  for (int base = 0; base < B; base += 256) {      // 4 requests per trip, clamped and masked: they go out together
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = q[min(base + 64 * u + lane, B - 1)];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s += (base + 64 * u + lane < B) ? fabsf(v[u]) : 0.f;
+  }
+  return s;
+}
+__device__ __forceinline__ float bc_lambda(float bc_alpha, float abs_sum, int B) { return bc_alpha / fmaxf(abs_sum / (float)B, 1e-8f); }
+__device__ __forceinline__ float bc_mix(float lam, float dAj, float w, float inv_ba, float dif) { return lam * dAj + (2.0f * w * inv_ba) * dif; }
+// The loss finalisation of a BC actor update, by the riding block that finalises the plain one (k_tn_bc / k_adam_red_bc, whose
+// AdamRedArgs::loss_dst is then NULL): L as above from the critic tail's partials of sum -q, the head backward's of sum (pi - a)^2
+// and the lambda it published; the unweighted BC term goes to its own metrics slot.  One wave, fixed order.
+struct BcFin {
+  const float* q_part; int q_n;          // part_sa[k][1], k < q_n
+  const float* bc_part; int bc_n;        // BcArgs::part
+  float inv_b, inv_ba;
+  const float* ctl; const float* lam;    // DevCtl::bc; metrics slot SACTD3_M_BC_LAMBDA
+  float* loss_dst; float* bc_dst;        // metrics slots SACTD3_M_ACTOR_LOSS, SACTD3_M_BC_LOSS
+};
+__device__ __forceinline__ void bc_loss_finish(const BcFin& f) {
+  const int t = threadIdx.x;
+  if (t >= 64) return;
+  float s1 = 0.f, s2 = 0.f;
+  for (int k = t; k < f.q_n; k += 64) s1 += f.q_part[2 * (long)k + 1];
+  for (int k = t; k < f.bc_n; k += 64) s2 += f.bc_part[k];
+  const float lam = *f.lam, w = f.ctl[1];
+  s1 = wave_sum(s1); s2 = wave_sum(s2);
+  if (t == 0) {
+    const float bcl = s2 * f.inv_ba;
+    *f.loss_dst = lam * (s1 * f.inv_b) + w * bcl;
+    *f.bc_dst = bcl;
+  }
+}
 __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
@@ -358,7 +419,9 @@ __device__ __forceinline__ Row16 ln_bwd(const Row16& dy, const Row16& xh, float 
 }
 // Column sums over the RPB rows of a block (blockDim = 16 RPB) for `nslots` quantities; cs = __shared__ float[nslots][RPB][HID].
 // Column c of every slot is written to dst[slot][c].  Contains a barrier: every thread of the block calls it.
-template <int RPB>
+// (TAG: an instance of its own for a caller that asks for one -- k_actor_head_bwd_s_bc; sharing the RPB = 4 instance with its plain
+//  twin changed the twin's machine code)
+template <int RPB, int TAG = 0>
 __device__ __forceinline__ void block_colsum(float* cs, const Row16* vals, int nslots, int row, int sub, float* dst) {
   for (int s = 0; s < nslots; ++s) row_st(cs + (s * RPB + row) * HID, sub, vals[s]);
   __syncthreads();
@@ -1942,197 +2005,12 @@ __device__ __forceinline__ void adam_commit(const TnArgs& p, long off, float g, 
 // and wave 1 commit one each -- used when a launch would otherwise put more than two blocks on every CU.
 // FOLD: the instance whose layer-1 problem applies the LayerNorm backward itself (TnProb::fold); launches without such a problem
 // take the plain instance (the fold's operands cost registers: the actor's B = 1024 launch was 5 us slower through one kernel).
-template <int KT, bool FOLD = false, bool KEEP_G = true>
-__global__ __launch_bounds__(256) void k_tn(int h_tiles, int h_pk_blocks, int h_fin_blocks, int h_nprob, int h_tile1, int h_tile2, int h_tile3, int h_M, TnArgs p) {
-  __shared__ __attribute__((aligned(16))) float red[KT * 4 * 64 * 4];
-  __shared__ __attribute__((aligned(16))) float Ys[256 * YS];
-  __shared__ __attribute__((aligned(16))) float Xs[KT * 256 * YS];
-  __shared__ float cred[16 * 17];                        // bias gradient: [16 partial groups][16 columns]
-  __shared__ __attribute__((aligned(16))) float fsum[FOLD ? 16 * 4 * 8 : 4];   // folded LayerNorm backward: [wave x DPP row][column quad][dgamma 4 | dbeta 4]
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, net = blockIdx.z;
-  const int r = lane & 15, kq = lane >> 4;
-  BLK_MARK(0);
-  // role and problem from the launch header (HDR_TN): no load in front of the problem's own batch
-  const int tiles = HDR_TN ? h_tiles : p.tiles, pk_blocks = HDR_TN ? h_pk_blocks : p.pk_blocks, fin_blocks = HDR_TN ? h_fin_blocks : p.fin_blocks;
-  const int M = HDR_TN ? h_M : p.M;
-  if ((int)blockIdx.x >= tiles) {                           // (block-uniform) riding blocks
-    const int x = (int)blockIdx.x - tiles;
-    if (x < pk_blocks) { if (net == 0) polyak_body(p.pk, x, pk_blocks); }
-    else if (x - pk_blocks < fin_blocks) adam_red_tail_body<KEEP_G>(p.fin, x - pk_blocks, net);      // (behind them: padding up to a multiple of 8 blocks
-    BLK_MARK(1);                                                                                  //  per net, so that every net's tile ids keep their XCDs)
-    return;
-  }
-  const int nprob = HDR_TN ? h_nprob : p.nprob;
-  int pi = 0;
-  if (nprob > 1 && (int)blockIdx.x >= (HDR_TN ? h_tile1 : p.pr[1].tile0)) pi = 1;
-  if (nprob > 2 && (int)blockIdx.x >= (HDR_TN ? h_tile2 : p.pr[2].tile0)) pi = 2;
-  if (nprob > 3 && (int)blockIdx.x >= (HDR_TN ? h_tile3 : p.pr[3].tile0)) pi = 3;
-  const TnProb q = p.pr[pi];     // ONE batch of scalar loads for the whole problem (field-by-field they came in 3-4 dependent rounds)
-  int ldy = q.ldy, ldx = q.ldx;  // (left alone, the compiler fetches these two again in a round of their own, waited for in front of the first operand load)
-  // ... and with them what the requests BEHIND the operand batch need (the optimiser state of the block's elements): integers, and
-  // copies of the pointers' bits -- a pointer that went through a pin itself would no longer be known to be global (see k_nt)
-  long g_ns = p.g_ns;
-  int apply = p.apply;
-  unsigned long adam_bits = (unsigned long)p.adam, P_bits = (unsigned long)p.P, Mo_bits = (unsigned long)p.Mo, Vo_bits = (unsigned long)p.Vo, T_bits = (unsigned long)p.T;
-  if (HDR_TN) {
-    ldy = uni(ldy); ldx = uni(ldx); g_ns = uni(g_ns); apply = uni(apply);
-    adam_bits = (unsigned long)uni((long)adam_bits); P_bits = (unsigned long)uni((long)P_bits); Mo_bits = (unsigned long)uni((long)Mo_bits);
-    Vo_bits = (unsigned long)uni((long)Vo_bits); T_bits = (unsigned long)uni((long)T_bits);
-    asm volatile("" : "+s"(ldy), "+s"(ldx), "+s"(g_ns), "+s"(apply), "+s"(adam_bits), "+s"(P_bits), "+s"(Mo_bits), "+s"(Vo_bits), "+s"(T_bits));
-  }
-  const int local = blockIdx.x - q.tile0;
-  const int kw = q.kw > 0 ? q.kw : q.ldw;                 // columns of this problem's piece of dW
-  const int tiles_k = (((kw + 15) >> 4) + KT - 1) / KT;
-  int tn, tk;
-  xcd_tile(local, (q.N + 15) >> 4, tiles_k, q.xr, tn, tk);
-  const int n0 = tn * 16, k0 = tk * 16 * KT;
-  const long nbase = net * g_ns;
-  // the epilogue's elements: wave kt < KT, lane (j = lane & 15, rq = lane >> 4) owns rows n0 + 4 rq + i, column k0 + 16 kt + j
-  const int ecol = k0 + 16 * min(wave, KT - 1) + (lane & 15);
-  AdamState st[4], sv = {0.f, 0.f, 0.f, 0.f};
-  STAMP(0); BLK_PH(0);
-  // operand tiles are column slices ([M rows][16 floats]): fetched as float4 (64-byte pieces), transposed through LDS
-  const float* dYn = q.dY + net * q.dy_ns;
-  const float* Xn = q.X + net * q.x_ns;
-  const int Nr = (q.N + 3) & ~3, Kr = (q.K + 3) & ~3;     // rows hold at least round4(.) floats
-  f32x4 acc[KT];
-#pragma unroll
-  for (int kt = 0; kt < KT; ++kt) acc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float asum = 0.f;                                       // thread (col = t & 15, part = t >> 4): partial column sums of dY
-  float4 vy[4], vx[KT][4];
-  const bool fold = FOLD && q.fold != 0, fold_ln = fold && q.f_ln;   // (block-uniform)
-  float4 vxh[4], vp1[4], vp2[4], gq = f4(1.f), cg = f4(0.f), cb = f4(0.f);
-  float vrs[4];
-  auto fetch = [&](int mb) {                      // raw loads; masked when the slab is parked in LDS, a stage later (see ld4_raw)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = t + 256 * u, row = i >> 2, c4 = i & 3, m = mb + row, n = n0 + 4 * c4, k = k0 + 4 * c4;
-      const long mc = min(m, M - 1);
-      vy[u] = ld4_raw(dYn + mc * ldy, n, Nr);
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) vx[kt][u] = ld4_raw(Xn + mc * ldx, k + 16 * kt, Kr);
-      if (fold_ln) {
-        const long rn = (long)net * M + mc;
-        vxh[u] = ld4(q.f_xh + rn * HID + n);
-        vp1[u] = ld4(q.f_ps + rn * PS_W + 4 * c4);
-        vp2[u] = ld4(q.f_ps + rn * PS_W + 16 + 4 * c4);
-        vrs[u] = q.f_rstd[rn];
-      }
-    }
-  };
-  fetch(0);
-  if (fold_ln) gq = ld4(q.f_g + net * HID + n0 + 4 * (t & 3));
-  const float step = apply ? p.adam[0] : 0.f, sq2 = apply ? p.adam[1] : 1.f;
-  if (wave < KT) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {          // clamped, not predicated (the commit is predicated)
-      const int row = min(n0 + 4 * (lane >> 4) + i, q.N - 1);
-      st[i] = adam_fetch(p, nbase + q.w_off + (long)row * q.ldw + min(ecol, kw - 1));
-    }
-  }
-  // k-tile-0 blocks also produce the bias gradient of their 16 columns (column sums of dY, collected from the LDS tile in the
-  // main loop): wave 3, lanes 0 .. 15 commit it; its optimiser state is requested now
-  const int fcol = t & 15, fpart = t >> 4, fn = n0 + fcol;         // (column, partial-group) of this thread
-  const bool want_bias = tk == 0 && q.b_off >= 0;
-  AdamState fstate = sv;
-  long foff = -1;
-  if (want_bias && wave == 3 && lane < 16 && fn < q.N) { foff = nbase + q.b_off + fn; fstate = adam_fetch(p, foff); }
-  const bool fold_vec = fold_ln && tk == 0;                // dgamma1 / dbeta1 of the 16 columns: wave 3, lanes 16 .. 31 / 32 .. 47
-  if (fold_vec && wave == 3 && lane >= 16 && lane < 48) { foff = nbase + (lane < 32 ? q.f_g_off : q.f_be_off) + fn; fstate = adam_fetch(p, foff); }
-  for (int mb = 0; mb < M; mb += 256) {
-    if (mb) __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-    STAMP(1); BLK_PH(1);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = t + 256 * u, c4 = i & 3;
-      const bool row_ok = mb + (i >> 2) < M;
-      if (fold) {                                          // N = HID: no column mask
-        float4 dz = row_ok ? vy[u] : f4(0.f);
-        if (fold_ln) {
-          const float a1 = sum4(vp1[u]), a2 = sum4(vp2[u]);                       // 4 of the 16 tile partials each; the quad holds the row
-          const float s1 = (dpp_mov<0x00>(a1) + dpp_mov<0x55>(a1)) + (dpp_mov<0xAA>(a1) + dpp_mov<0xFF>(a1));   // quad_perm broadcasts
-          const float s2 = (dpp_mov<0x00>(a2) + dpp_mov<0x55>(a2)) + (dpp_mov<0xAA>(a2) + dpp_mov<0xFF>(a2));
-          const float m1 = s1 * (1.0f / HID), m2 = s2 * (1.0f / HID);
-          const float4 dy = dz;
-          cg = cg + dy * vxh[u]; cb = cb + dy;
-          dz = (dy * gq - f4(m1) - vxh[u] * m2) * vrs[u];                         // ln_bwd's expression
-          if (!row_ok) dz = f4(0.f);
-        }
-        st4(Ys + (i >> 2) * YS + 4 * c4, dz);
-        if (tk == 0 && row_ok && q.f_dz) st4(q.f_dz + ((long)net * M + mb + (i >> 2)) * HID + n0 + 4 * c4, dz);
-      } else
-      st4(Ys + (i >> 2) * YS + 4 * c4, mask4_cols(vy[u], n0 + 4 * c4, q.N, row_ok));
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) st4(Xs + kt * 256 * YS + (i >> 2) * YS + 4 * c4, mask4_cols(vx[kt][u], k0 + 4 * c4 + 16 * kt, q.K, row_ok));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if (mb + 256 < M) fetch(mb + 256);                   // the next slab's rows fly under this slab's MFMAs
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {                          // wave w: 16-row chunks w, w+4, w+8, w+12 of this slab
-      const float* y0 = Ys + (16 * (wave + 4 * u) + 4 * kq) * YS + r;
-      const float4 a = make_float4(y0[0], y0[YS], y0[2 * YS], y0[3 * YS]);
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) {
-        const float* x0 = Xs + kt * 256 * YS + (16 * (wave + 4 * u) + 4 * kq) * YS + r;
-        const float4 b = make_float4(x0[0], x0[YS], x0[2 * YS], x0[3 * YS]);
-        MFMA4(acc[kt], a, b);
-      }
-    }
-    if (want_bias) {
-      const int col = t & 15, part = t >> 4;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) asum += Ys[(part * 16 + i) * YS + col];
-    }
-  }
-  STAMP(2); BLK_PH(2);
-  // sum the 4 waves' accumulators of every tile (split-M); wave kt gets the total of tile kt
-#pragma unroll
-  for (int kt = 0; kt < KT; ++kt) st4(red + ((kt * 4 + wave) * 64 + lane) * 4, make_float4(acc[kt][0], acc[kt][1], acc[kt][2], acc[kt][3]));
-  if (want_bias) cred[fpart * 17 + fcol] = asum;
-  if (fold_vec) {                                          // lanes with equal (lane & 3) hold the same 4 columns: sum the 4 of a DPP row,
-    float v[8] = {cg.x, cg.y, cg.z, cg.w, cb.x, cb.y, cb.z, cb.w};     // then one partial per (wave, row) into LDS
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { v[j] += dpp_mov<0x124>(v[j]); v[j] += dpp_mov<0x128>(v[j]); }   // row_ror:4, row_ror:8
-    if ((lane & 15) < 4) {
-      float* d = fsum + ((wave * 4 + (lane >> 4)) * 4 + (lane & 3)) * 8;
-      st4(d, make_float4(v[0], v[1], v[2], v[3])); st4(d + 4, make_float4(v[4], v[5], v[6], v[7]));
-    }
-  }
-  __syncthreads();
-  STAMP(3); BLK_PH(3);
-  if (!KEEP_G) {          // (without the arena store in front of it, each row's branch below would be the first use of its optimiser
-#pragma unroll           //  state, and every group of stores would wait for the previous group's: PIN)
-    for (int i = 0; i < 4; ++i) { PIN(st[i].w); PIN(st[i].m); PIN(st[i].v); PIN(st[i].t); }
-    PIN(fstate.w); PIN(fstate.m); PIN(fstate.v); PIN(fstate.t);
-  }
-  if (wave < KT && ecol < kw) {
-    const float* rr = red + (wave * 4 * 64 + lane) * 4;
-    const float4 a = ld4(rr), b = ld4(rr + 256), c = ld4(rr + 512), d = ld4(rr + 768);
-    const float o[4] = {(a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w)};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = n0 + 4 * (lane >> 4) + i;
-      if (row < q.N) adam_commit<KEEP_G>(p, nbase + q.w_off + (long)row * q.ldw + ecol, ecol < q.K ? o[i] : 0.f, st[i], step, sq2);
-    }
-  }
-  if (foff >= 0) {
-    float v = 0.f;
-    if (lane < 16) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v += cred[i * 17 + fcol];
-    } else {
-      const float* f = fsum + (fcol >> 2) * 8 + (lane < 32 ? 0 : 4) + (fcol & 3);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v += f[i * 32];
-    }
-    adam_commit<KEEP_G>(p, foff, v, fstate, step, sq2);
-  }
-  STAMP(4); BLK_PH(4);
-  BLK_MARK(1);
-}
+#define FIN_BC 0
+#include "tn_body.inc"
+#undef FIN_BC
+#define FIN_BC 1
+#include "tn_body.inc"
+#undef FIN_BC
 
 // k_tn's launch header (SACTD3_HDR; host side): the words a block needs to find its role and its problem, taken from the very struct
 // that follows them -- a header cannot disagree with its struct
@@ -2140,6 +2018,11 @@ template <int KT, bool FOLD, bool KEEP_G>
 static inline void launch_k_tn(dim3 grid, hipStream_t s, const TnArgs& g) {
   hipLaunchKernelGGL((k_tn<KT, FOLD, KEEP_G>), grid, dim3(256), 0, s, g.tiles, g.pk_blocks, g.fin_blocks, g.nprob,
                      g.pr[1].tile0, g.pr[2].tile0, g.pr[3].tile0, g.M, g);
+}
+template <int KT, bool FOLD, bool KEEP_G>
+static inline void launch_k_tn_bc(dim3 grid, hipStream_t s, const TnArgs& g, const BcFin& bf) {
+  hipLaunchKernelGGL((k_tn_bc<KT, FOLD, KEEP_G>), grid, dim3(256), 0, s, g.tiles, g.pk_blocks, g.fin_blocks, g.nprob,
+                     g.pr[1].tile0, g.pr[2].tile0, g.pr[3].tile0, g.M, g, bf);
 }
 
 // ---- large-batch form of the weight gradients (M >= 1024).  k_tn's 16 x 16 tiles make every block re-read a [M][16]
@@ -2354,32 +2237,12 @@ __global__ __launch_bounds__(256) void k_tn64(Tn64Args p) {
 }
 
 // grid = (main blocks + 4 nvec vector blocks + 1 scalar block, nets); main blocks = ceil(g_ns / 1024)
-template <bool KEEP_G = true>
-__global__ __launch_bounds__(256) void k_adam_red(AdamRedArgs a) {
-  const int net = blockIdx.y, t = threadIdx.x;
-  const int main_blocks = (int)((a.g_ns / 4 + 255) / 256);
-  const int bx = blockIdx.x;
-  if (bx >= main_blocks) { adam_red_tail_body<KEEP_G>(a, bx - main_blocks, net); return; }
-  const float step = a.apply ? a.adam[0] : 0.f, sq2 = a.apply ? a.adam[1] : 1.f;
-  // slab-sourced elements: one float4 per thread (the vector ranges and the scalar's float4 belong to the tail blocks)
-  const long i = ((long)bx * 256 + t) * 4;
-  bool mine = i < a.g_ns && !(a.s_off >= 0 && i == a.s_off);
-#pragma unroll
-  for (int e = 0; e < 5; ++e)
-    if (e < a.nvec && i >= a.vec[e].off && i < a.vec[e].off + HID) mine = false;
-  if (mine) {
-    const long off = net * a.g_ns + i;
-    float4 w = f4(0.f), m = f4(0.f), v = f4(0.f), tt = f4(0.f);
-    if (a.apply) { w = ld4(a.P + off); m = ld4(a.Mo + off); v = ld4(a.Vo + off); if (a.T) tt = ld4(a.T + off); }
-    float4 gs[8];
-#pragma unroll
-    for (int sl = 0; sl < 8; ++sl) gs[sl] = ld4(a.Gp + ((long)min(sl, a.S - 1) * a.nets + net) * a.g_ns + i);   // all requests first
-    float4 g = gs[0];
-#pragma unroll
-    for (int sl = 1; sl < 8; ++sl) if (sl < a.S) g = g + gs[sl];
-    adam_red_commit<KEEP_G>(a, off, g, w, m, v, tt, step, sq2);
-  }
-}
+#define FIN_BC 0
+#include "adam_red_body.inc"
+#undef FIN_BC
+#define FIN_BC 1
+#include "adam_red_body.inc"
+#undef FIN_BC
 
 // ------------------------------------------------------------------------------------------------ row kernels
 struct ActorTail {
@@ -3259,172 +3122,23 @@ struct ActorHeadBwd {
   float* part;                           // [blocks][NSLOT][HID]
 };
 
-__global__ __launch_bounds__(256) void k_actor_head_bwd(ActorHeadBwd p) {
-  __shared__ __attribute__((aligned(16))) float cs[2 * 16 * HID];   // also holds dh2 [16][AS] before the column sums
-  __shared__ __attribute__((aligned(16))) float Du[16 * 68];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int row = t >> 4, sub = t & 15, r = lane & 15, kq = lane >> 4;
-  const int b = blockIdx.x * 16 + row, bc = min(b, p.B - 1);
-  const bool valid = b < p.B;
-  const int nh = p.L.nh, C = (nh + 15) >> 4;      // k chunks of the head-backward product (<= 4)
-  const float* Wh = p.P + p.L.Wh;
-  // loads first
-  const long ro = (long)bc * HID;
-  const Row16 hh = row_ld(p.h2 + ro, sub), xh = row_ld(p.xh2 + ro, sub);
-  Row16 g;
-  if (p.ln) g = row_ld(p.P + p.L.g2, sub);
-  const float rstd = p.ln ? p.rstd2[bc] : 1.f;
-  float4 wf[4][4];                       // B operand of dh2 = du Wh: Wh[k = 16c + 4kq + jj][n = (4*tt + wave)*16 + r]
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int n = (4 * tt + wave) * 16 + r, k = 16 * c + 4 * kq;
-      wf[tt][c] = f4(0.f);
-      if (c < C) {
-        if (k < nh) wf[tt][c].x = Wh[(long)k * HID + n];
-        if (k + 1 < nh) wf[tt][c].y = Wh[(long)(k + 1) * HID + n];
-        if (k + 2 < nh) wf[tt][c].z = Wh[(long)(k + 2) * HID + n];
-        if (k + 3 < nh) wf[tt][c].w = Wh[(long)(k + 3) * HID + n];
-      }
-    }
-  // operands of this thread's first head element (j = sub), requested with the rest (see k_actor_tail)
-  const int j0 = min(sub, p.a - 1);
-  const float* tgr = p.tg + (long)bc * 4 * p.a4;
-  float la = p.sac ? *p.log_alpha : 0.f;
-  float o_dA = p.dA[(long)bc * p.ldA + j0], o_dA1 = p.nq == 2 ? p.dA[p.dA_ns + (long)bc * p.ldA + j0] : 0.f;
-  float o_sc = p.scale[j0], o_t0 = tgr[j0];
-  float o_t1 = 0.f, o_t2 = 0.f, o_e = 0.f;
-  if (p.sac) { o_t1 = tgr[p.a4 + j0]; o_t2 = tgr[2 * p.a4 + j0]; o_e = p.eps[(long)bc * p.a + j0]; }
-  for (int j = sub; j < 64; j += 16) Du[row * 68 + j] = 0.f;
-  PIN(la); PIN(o_dA); PIN(o_dA1); PIN(o_sc); PIN(o_t0); PIN(o_t1); PIN(o_t2); PIN(o_e);
-  __syncthreads();
-  const float dlogp = p.sac ? expf(la) / (float)p.B : 0.f;
-  auto element = [&](int j, float dAj, float sc, float t0, float t1, float t2, float e) {
-    float g_mean, g_raw = 0.f;
-    if (p.sac) {
-      const float tt = t0, sd = t1, yt = t2;
-      const float omy2 = 1.0f - yt * yt;
-      const float g0 = dAj * sc * omy2 + dlogp * (2.0f * sc * yt * omy2) / (sc * omy2 + 1e-6f);
-      g_mean = g0;
-      g_raw = (g0 * e * sd - dlogp) * 3.5f * (1.0f - tt * tt);
-    } else {
-      const float th = t0;
-      g_mean = dAj * sc * (1.0f - th * th);
-    }
-    if (!valid) { g_mean = 0.f; g_raw = 0.f; }
-    Du[row * 68 + j] = g_mean;
-    if (p.sac) Du[row * 68 + p.a + j] = g_raw;
-    if (valid) {
-      p.du[(long)b * p.ldu + j] = g_mean;
-      if (p.sac) p.du[(long)b * p.ldu + p.a + j] = g_raw;
-    }
-  };
-  if (sub < p.a) element(sub, o_dA + o_dA1, o_sc, o_t0, o_t1, o_t2, o_e);
-  for (int j = sub + 16; j < p.a; j += 16) {            // ac_dim > 16 only
-    float dAj = p.dA[(long)bc * p.ldA + j];
-    if (p.nq == 2) dAj += p.dA[p.dA_ns + (long)bc * p.ldA + j];
-    element(j, dAj, p.scale[j], tgr[j], p.sac ? tgr[p.a4 + j] : 0.f, p.sac ? tgr[2 * p.a4 + j] : 0.f, p.sac ? p.eps[(long)bc * p.a + j] : 0.f);
-  }
-  __syncthreads();
-  // dh2[16][256] = du[16][nh] Wh[nh][256]; wave w owns column tiles w, w+4, w+8, w+12
-  float* DH = cs;
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (c < C) { const float4 av = ld4(Du + r * 68 + 16 * c + 4 * kq); MFMA4(acc, av, wf[tt][c]); }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) DH[(4 * kq + i) * AS + (4 * tt + wave) * 16 + r] = acc[i];
-  }
-  __syncthreads();
-  const Row16 dh = row_ld(DH + row * AS, sub);
-  __syncthreads();                       // DH is reused by the column sums below
-  Row16 dy, vals[2];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dy.v[q] = gate4(dh.v[q], hh.v[q]);
-  const Row16 dz = ln_bwd(dy, xh, rstd, g, p.ln);
-  if (valid) row_st(p.dz2 + (long)b * HID, sub, dz);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { vals[0].v[q] = dy.v[q] * xh.v[q]; vals[1].v[q] = dy.v[q]; }
-  block_colsum<16>(cs, vals, 2, row, sub, p.part + (long)blockIdx.x * NSLOT * HID);
-}
+#define HB_BC 0
+#include "actor_head_bwd_body.inc"
+#undef HB_BC
+#define HB_BC 1
+#include "actor_head_bwd_body.inc"
+#undef HB_BC
 
 // Narrow heads (nh <= 8), as k_actor_tail_s: a row lives in ONE wave (RPB rows x 16 threads = 64 threads per block).  Lane n of
 // a row computes head-output gradient du[n] itself (lanes a .. 2a-1 redo their element's arithmetic for the log-std half instead
 // of fetching it across lanes), du[n] reaches the row's other lanes by DPP row broadcast, dh2 = du Wh is nh FMAs per column on
 // the vector ALU, and the dgamma / dbeta partials are summed over the block's rows through wave-local LDS: no MFMA, no block barrier.
-template <int RPB>
-__global__ __launch_bounds__(16 * RPB) void k_actor_head_bwd_s(ActorHeadBwd p) {
-  __shared__ __attribute__((aligned(16))) float cs[2 * RPB * HID];
-  const int t = threadIdx.x, row = t >> 4, sub = t & 15;
-  const int b = blockIdx.x * RPB + row, bc = min(b, p.B - 1);
-  const bool valid = b < p.B;
-  const int nh = p.L.nh;                         // <= 8, and a <= 8
-  const float* Wh = p.P + p.L.Wh;
-  // loads first
-  const long ro = (long)bc * HID;
-  const Row16 hh = row_ld(p.h2 + ro, sub), xh = row_ld(p.xh2 + ro, sub);
-  Row16 g;
-  if (p.ln) g = row_ld(p.P + p.L.g2, sub);
-  const float rstd = p.ln ? p.rstd2[bc] : 1.f;
-  Row16 w[8];
-#pragma unroll
-  for (int n = 0; n < 8; ++n) w[n] = row_ld(Wh + (long)min(n, nh - 1) * HID, sub);   // unconditional, row clamped
-  // lane `sub` < nh owns head output n = sub: action element j = n (mean half) or n - a (log-std half, SAC)
-  const bool second = sub >= p.a;
-  const int j0 = min(second ? sub - p.a : sub, p.a - 1);
-  const float* tgr = p.tg + (long)bc * 4 * p.a4;
-  float la = p.sac ? *p.log_alpha : 0.f;
-  float o_dA = p.dA[(long)bc * p.ldA + j0], o_dA1 = p.nq == 2 ? p.dA[p.dA_ns + (long)bc * p.ldA + j0] : 0.f;
-  float o_sc = p.scale[j0], o_t0 = tgr[j0];
-  float o_t1 = 0.f, o_t2 = 0.f, o_e = 0.f;
-  if (p.sac) { o_t1 = tgr[p.a4 + j0]; o_t2 = tgr[2 * p.a4 + j0]; o_e = p.eps[(long)bc * p.a + j0]; }
-  PIN(la); PIN(o_dA); PIN(o_dA1); PIN(o_sc); PIN(o_t0); PIN(o_t1); PIN(o_t2); PIN(o_e);
-  const float dlogp = p.sac ? expf(la) / (float)p.B : 0.f;
-  float d;                                        // du[sub]
-  {
-    const float dAj = o_dA + o_dA1, sc = o_sc;
-    float g_mean, g_raw = 0.f;
-    if (p.sac) {
-      const float tt = o_t0, sd = o_t1, yt = o_t2;
-      const float omy2 = 1.0f - yt * yt;
-      const float g0 = dAj * sc * omy2 + dlogp * (2.0f * sc * yt * omy2) / (sc * omy2 + 1e-6f);
-      g_mean = g0;
-      g_raw = (g0 * o_e * sd - dlogp) * 3.5f * (1.0f - tt * tt);
-    } else {
-      g_mean = dAj * sc * (1.0f - o_t0 * o_t0);
-    }
-    d = second ? g_raw : g_mean;
-    if (!valid || sub >= nh) d = 0.f;
-  }
-  // dh2[c] = sum_n du[n] Wh[n][c]
-  Row16 dh;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dh.v[q] = f4(0.f);
-  auto add_n = [&](float dn, const Row16& wn) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dh.v[q] = dh.v[q] + wn.v[q] * dn;
-  };
-  row_pin(w[0]); add_n(dpp_mov<0x150>(d), w[0]);           // row_newbcast:n = lane n of every 16-lane row to all of its lanes
-  row_pin(w[1]); add_n(dpp_mov<0x151>(d), w[1]);
-  row_pin(w[2]); add_n(dpp_mov<0x152>(d), w[2]);
-  row_pin(w[3]); add_n(dpp_mov<0x153>(d), w[3]);
-  row_pin(w[4]); add_n(dpp_mov<0x154>(d), w[4]);
-  row_pin(w[5]); add_n(dpp_mov<0x155>(d), w[5]);
-  row_pin(w[6]); add_n(dpp_mov<0x156>(d), w[6]);
-  row_pin(w[7]); add_n(dpp_mov<0x157>(d), w[7]);           // (lanes >= nh hold d = 0: their clamped weight rows add nothing)
-  if (valid && sub < nh) p.du[(long)b * p.ldu + sub] = d;
-  Row16 dy, vals[2];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dy.v[q] = gate4(dh.v[q], hh.v[q]);
-  const Row16 dz = ln_bwd(dy, xh, rstd, g, p.ln);
-  if (valid) row_st(p.dz2 + (long)b * HID, sub, dz);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { vals[0].v[q] = dy.v[q] * xh.v[q]; vals[1].v[q] = dy.v[q]; }
-  block_colsum<RPB>(cs, vals, 2, row, sub, p.part + (long)blockIdx.x * NSLOT * HID);
-}
+#define HB_BC 0
+#include "actor_head_bwd_s_body.inc"
+#undef HB_BC
+#define HB_BC 1
+#include "actor_head_bwd_s_body.inc"
+#undef HB_BC
 
 // k_actor_head_bwd_s + k_nn in ONE launch (narrow heads, B < 1024), as k_ctail_nn: a block = 16 batch rows x 16 columns of the
 // actor's dh1 = dz2 W2.  Every block redoes the head backward of its 16 rows (k_actor_head_bwd_s's arithmetic: lane n of a row
@@ -3433,179 +3147,12 @@ __global__ __launch_bounds__(16 * RPB) void k_actor_head_bwd_s(ActorHeadBwd p) {
 // qa.on: dA is not read but finished here from k_qtail_nn's partials (QaFold): rstd = the critics' layer-1 rstd [nq][B]
 struct QaIn { int on, ln, a, pqw, ntile; const float* ps; const float* S; const float* rstd; float* dA; };
 struct HeadBwdNn { ActorHeadBwd c; const float* Wt; int ldw; float* dX; int xr; NnFold f; QaIn qa; };
-__global__ __launch_bounds__(256) void k_headbwd_nn(HeadBwdNn a) {
-  const ActorHeadBwd& p = a.c;
-  constexpr int CB = 16;
-  __shared__ __attribute__((aligned(16))) float Dz[16 * AS];
-  __shared__ __attribute__((aligned(16))) float cs[2 * 16 * CB];
-  __shared__ __attribute__((aligned(16))) float red[4 * 64 * 4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, row = t >> 4, sub = t & 15;
-  const int r = lane & 15, kq = lane >> 4;
-  int tm, tk;
-  xcd_tile(blockIdx.x, (p.B + 15) >> 4, HID / CB, a.xr, tm, tk);
-  const int b = tm * 16 + row, bc = min(b, p.B - 1), c_lo = tk * CB;
-  const bool valid = b < p.B;
-  const int nh = p.L.nh;                         // <= 8, and a <= 8
-  const float* Wh = p.P + p.L.Wh;
-  // ---- loads first (k_actor_head_bwd_s), then this block's W2 fragments (k_nn's B operand)
-  const long ro = (long)bc * HID;
-  const Row16 hh = row_ld(p.h2 + ro, sub), xh = row_ld(p.xh2 + ro, sub);
-  Row16 g;
-  if (p.ln) g = row_ld(p.P + p.L.g2, sub);
-  const float rstd = p.ln ? p.rstd2[bc] : 1.f;
-  Row16 w[8];
-#pragma unroll
-  for (int n = 0; n < 8; ++n) w[n] = row_ld(Wh + (long)min(n, nh - 1) * HID, sub);   // unconditional, row clamped
-  const bool second = sub >= p.a;
-  const int j0 = min(second ? sub - p.a : sub, p.a - 1);
-  const float* tgr = p.tg + (long)bc * 4 * p.a4;
-  float la = p.sac ? *p.log_alpha : 0.f;
-  float o_dA = 0.f, o_dA1 = 0.f;
-  // (qa.on) the row's partials: thread `sub` takes float4 #sub, #sub + 16, ... of the row's ntile x pqw floats of each critic
-  float4 qv[2] = {f4(0.f), f4(0.f)}, qs[2] = {f4(0.f), f4(0.f)};
-  float qrs[2] = {1.f, 1.f};
-  if (a.qa.on) {
-    const int n4 = a.qa.ntile * a.qa.pqw / 4, s4 = a.qa.ntile * 2;     // float4s per row / of a critic's S partials
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-      if (q < p.nq) {
-        const float* pr = a.qa.ps + ((long)q * p.B + bc) * (long)n4 * 4;
-        float4 v0 = ld4(pr + 4 * sub), v1 = f4(0.f), v2 = f4(0.f), v3 = f4(0.f);
-        if (n4 > 16) v1 = ld4(pr + 4 * (sub + 16));
-        if (n4 > 32) { v2 = ld4(pr + 4 * (sub + 32)); v3 = ld4(pr + 4 * (sub + 48)); }
-        qv[q] = (v0 + v1) + (v2 + v3);
-        const float* sr = a.qa.S + (long)q * s4 * 4;
-        float4 t0 = ld4(sr + 4 * sub), t1 = f4(0.f);
-        if (s4 > 16) t1 = ld4(sr + 4 * (sub + 16));
-        qs[q] = t0 + t1;
-        if (a.qa.ln) qrs[q] = a.qa.rstd[(long)q * p.B + bc];
-      }
-  } else {
-    o_dA = p.dA[(long)bc * p.ldA + j0]; o_dA1 = p.nq == 2 ? p.dA[p.dA_ns + (long)bc * p.ldA + j0] : 0.f;
-  }
-  float o_sc = p.scale[j0], o_t0 = tgr[j0];
-  float o_t1 = 0.f, o_t2 = 0.f, o_e = 0.f;
-  if (p.sac) { o_t1 = tgr[p.a4 + j0]; o_t2 = tgr[2 * p.a4 + j0]; o_e = p.eps[(long)bc * p.a + j0]; }
-  const int nb = 64 * wave + 4 * kq;
-  float4 bv[4];
-  {
-    const float* Wc = a.Wt + (long)nb * a.ldw + c_lo + r;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float* wp = Wc + (long)(16 * c) * a.ldw;
-      bv[c] = make_float4(wp[0], wp[a.ldw], wp[2 * (long)a.ldw], wp[3 * (long)a.ldw]);
-    }
-  }
-  float fh[4] = {1.f, 1.f, 1.f, 1.f}, fx[4] = {0.f, 0.f, 0.f, 0.f}, fg = 1.f;      // the epilogue's layer-1 operands (wave 0)
-  if (a.f.fold && wave == 0) {
-    const int col = c_lo + (lane & 15);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const long o = (long)min(tm * 16 + 4 * (lane >> 4) + i, p.B - 1) * HID + col;
-      fh[i] = a.f.h1[o]; if (a.f.ln) fx[i] = a.f.xh1[o];
-    }
-    if (a.f.ln) fg = p.P[a.f.g1_off + col];
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  if (a.qa.on) {
-    // sum the tiles: the float4s a thread took all hold the same part of a partial (16 is a multiple of pqw / 4), so lanes with equal
-    // sub mod (pqw / 4) add up (DPP row rotations); lane g < pqw / 4 then parks part g of the row's sums in LDS for the whole row to read
-    float* Vs = red + (row * 2) * 24;                       // [16 rows][2 critics][16 sums | 8 S]
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-      if (q < p.nq) {
-        float v[8] = {qv[q].x, qv[q].y, qv[q].z, qv[q].w, qs[q].x, qs[q].y, qs[q].z, qs[q].w};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          if (k >= 4 || a.qa.pqw == 8) v[k] += dpp_mov<0x122>(v[k]);     // row_ror:2 (S partials are 8 floats: parts 0, 1)
-          v[k] += dpp_mov<0x124>(v[k]); v[k] += dpp_mov<0x128>(v[k]);       // row_ror:4, row_ror:8
-        }
-        if (sub < a.qa.pqw / 4) st4(Vs + q * 24 + 4 * sub, make_float4(v[0], v[1], v[2], v[3]));
-        if (sub < 2) st4(Vs + q * 24 + 16 + 4 * sub, make_float4(v[4], v[5], v[6], v[7]));
-      }
-    const int na = a.qa.a;
-    float tot = 0.f;
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-      if (q < p.nq) {
-        const float* V = Vs + q * 24;
-        const float P = V[j0];
-        float dq = P;
-        if (a.qa.ln) dq = (P - V[na] * (1.0f / HID) * V[16 + j0] - V[2 * na + 1] * (1.0f / HID) * V[na + 1 + j0]) * qrs[q];
-        if (a.qa.dA && tk == 0 && valid && sub < na) a.qa.dA[((long)q * p.B + b) * p.ldA + sub] = dq;
-        tot += dq;
-      }
-    o_dA = tot; o_dA1 = 0.f;
-  }
-  PIN(la); PIN(o_dA); PIN(o_dA1); PIN(o_sc); PIN(o_t0); PIN(o_t1); PIN(o_t2); PIN(o_e);
-  const float dlogp = p.sac ? expf(la) / (float)p.B : 0.f;
-  float d;                                        // du[sub]
-  {
-    const float dAj = o_dA + o_dA1, sc = o_sc;
-    float g_mean, g_raw = 0.f;
-    if (p.sac) {
-      const float tt = o_t0, sd = o_t1, yt = o_t2;
-      const float omy2 = 1.0f - yt * yt;
-      const float g0 = dAj * sc * omy2 + dlogp * (2.0f * sc * yt * omy2) / (sc * omy2 + 1e-6f);
-      g_mean = g0;
-      g_raw = (g0 * o_e * sd - dlogp) * 3.5f * (1.0f - tt * tt);
-    } else {
-      g_mean = dAj * sc * (1.0f - o_t0 * o_t0);
-    }
-    d = second ? g_raw : g_mean;
-    if (!valid || sub >= nh) d = 0.f;
-  }
-  Row16 dh;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dh.v[q] = f4(0.f);
-  auto add_n = [&](float dn, const Row16& wn) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dh.v[q] = dh.v[q] + wn.v[q] * dn;
-  };
-  row_pin(w[0]); add_n(dpp_mov<0x150>(d), w[0]);           // row_newbcast:n = lane n of every 16-lane row to all of its lanes
-  row_pin(w[1]); add_n(dpp_mov<0x151>(d), w[1]);
-  row_pin(w[2]); add_n(dpp_mov<0x152>(d), w[2]);
-  row_pin(w[3]); add_n(dpp_mov<0x153>(d), w[3]);
-  row_pin(w[4]); add_n(dpp_mov<0x154>(d), w[4]);
-  row_pin(w[5]); add_n(dpp_mov<0x155>(d), w[5]);
-  row_pin(w[6]); add_n(dpp_mov<0x156>(d), w[6]);
-  row_pin(w[7]); add_n(dpp_mov<0x157>(d), w[7]);
-#pragma unroll
-  for (int c = 0; c < 4; ++c) { PIN(bv[c].x); PIN(bv[c].y); PIN(bv[c].z); PIN(bv[c].w); }
-  if (tk == 0 && valid && sub < nh) p.du[(long)b * p.ldu + sub] = d;
-  Row16 dy, vals[2];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dy.v[q] = gate4(dh.v[q], hh.v[q]);
-  const Row16 dz = ln_bwd(dy, xh, rstd, g, p.ln);           // (rows beyond the batch: d = 0 -> all zeros)
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { vals[0].v[q] = dy.v[q] * xh.v[q]; vals[1].v[q] = dy.v[q]; }
-  row_st(Dz + row * AS, sub, dz);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int col = 4 * sub + 64 * q;
-    if (col >= c_lo && col < c_lo + CB) {
-      if (valid) st4_pol<WT_DZ>(p.dz2, (long)b * HID + col, dz.v[q]);
-#pragma unroll
-      for (int sl = 0; sl < 2; ++sl) st4(cs + (sl * 16 + row) * CB + (col - c_lo), vals[sl].v[q]);
-    }
-  }
-  __syncthreads();
-  if (t < 2 * CB) {
-    const int sl = t / CB, c = t - sl * CB;
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sum += cs[(sl * 16 + i) * CB + c];
-    p.part[((long)tm * NSLOT + sl) * HID + c_lo + c] = sum;
-  }
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < 4; ++c) { const float4 av = ld4(Dz + r * AS + nb + 16 * c); MFMA4(acc, av, bv[c]); }
-  acc = splitk_reduce(red, acc, wave, lane);
-  if (wave == 0) {
-    const float o[4] = {acc[0], acc[1], acc[2], acc[3]};
-    nn_fold_store(a.f, o, fh, fx, fg, a.dX, a.f.ps, a.f.gsnap, tm * 16, p.B, c_lo + (lane & 15), lane);
-  }
-}
+#define HB_BC 0
+#include "headbwd_nn_body.inc"
+#undef HB_BC
+#define HB_BC 1
+#include "headbwd_nn_body.inc"
+#undef HB_BC
 
 // ------------------------------------------------------------------------------------------------ optimiser
 struct AdamArgs {

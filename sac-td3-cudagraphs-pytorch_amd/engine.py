@@ -63,6 +63,7 @@ class Config:
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_eps: float = 1e-8
+    bc_alpha: float = 0.0      # TD3+BC (include/sactd3.h: sactd3_set_bc): > 0 turns the behaviour-cloning actor term on; TD3 only
     seed: int = 0
 
     @staticmethod
@@ -82,7 +83,7 @@ class Config:
         for k in ("batch_size", "rb_capacity", "prefer_td3_over_sac", "layer_norm", "autotune", "bcq_style_targ_mix",
                   "targ_actor_smoothing", "actor_update_delay", "crit_targ_update_freq", "actor_lr", "qnets_lr",
                   "log_alpha_lr", "gamma", "polyak", "alpha_init", "clip_norm", "td3_std", "td3_c", "actor_noise_std",
-                  "seed"):
+                  "bc_alpha", "seed"):
             setattr(c, k, type(getattr(c, k))(get(k, getattr(c, k))))
         c.max_envs = max(int(get("num_envs", 4)), 1)
         # NOT hps.cudagraphs: INTEGRATION.md runs the reference loop with `cudagraphs: false` so that orchestrator.py:313-315
@@ -555,11 +556,26 @@ class Engine:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
         return self._stats(self.lib.sactd3_acting_stats, ("begun", "begin_waited_for_learner", "learner_waited_for_acting", "ended_by_spin"))
 
+    # -- TD3+BC (include/sactd3.h: sactd3_set_bc)
+    def set_bc(self, alpha: float, weight: float = 1.0) -> None:
+        """sactd3_set_bc: new (bc_alpha, bc_weight) of an engine created with cfg.bc_alpha > 0 -- one small launch on the engine's
+        stream, no graph capture, the run-ahead chain of step_period(s) stays intact.  bc_weight is run-time state: not saved."""
+        self._ck(self.lib.sactd3_set_bc(self._h, float(alpha), float(weight)))
+
+    def bc(self):
+        """sactd3_get_bc: (bc_alpha, bc_weight) as the device holds them (waits for the engine's stream)"""
+        out = np.empty(2, np.float32)
+        self._ck(self.lib.sactd3_get_bc(self._h, _fp(out)))
+        return float(out[0]), float(out[1])
+
     def read_metrics(self) -> Dict[str, float]:
         m = np.empty(_lib.NUM_METRICS, np.float32)
         self._ck(self.lib.sactd3_read_metrics(self._h, _fp(m)))
-        return {"loss/qf_loss": float(m[0]), "loss/actor_loss": float(m[1]), "loss/alpha_loss": float(m[2]),
-                "vitals/alpha": float(m[3])}
+        out = {"loss/qf_loss": float(m[0]), "loss/actor_loss": float(m[1]), "loss/alpha_loss": float(m[2]),
+               "vitals/alpha": float(m[3])}
+        if self.cfg.bc_alpha > 0:      # (an engine without BC never writes these two slots)
+            out["loss/bc_loss"], out["vitals/bc_lambda"] = float(m[_lib.M_BC_LOSS]), float(m[_lib.M_BC_LAMBDA])
+        return out
 
     def sync(self) -> None:
         self._ck(self.lib.sactd3_sync(self._h))

@@ -202,9 +202,38 @@ def job_config(algo: str, env_id: str, seed: int, **over):
     return SimpleNamespace(**cfg)
 
 
+def offline_plan(args):
+    """What --offline_dataset / --bc_alpha / --num_updates ask for, checked without touching a GPU.  -> None for an online run, else
+    dict(dataset=, num_updates=, bc_alpha=).  ValueError: --bc_alpha with --algo sac (the behaviour-cloning term exists in the TD3
+    engine only), a negative or non-finite --bc_alpha, --num_updates without a dataset or below 1, or an online-only switch
+    (--overlap_acting, --device_env, --prioritized, --n_step, --one_launch: they shape the env loop) beside a dataset.  A dataset
+    WITHOUT --bc_alpha is accepted for either algorithm -- plain TD3 / SAC on a fixed ring, the baseline that usually diverges -- and
+    flagged in the plan (`plain=True`) so that the caller can say so."""
+    import math
+    bc_alpha = 0.0 if args.bc_alpha is None else float(args.bc_alpha)
+    if not math.isfinite(bc_alpha) or bc_alpha < 0.0:
+        raise ValueError("--bc_alpha must be finite and >= 0")
+    if bc_alpha > 0.0 and args.algo != "td3":
+        raise ValueError("--bc_alpha needs --algo td3: the behaviour-cloning actor term (TD3+BC) exists in the TD3 engine only")
+    if args.offline_dataset is None:
+        if args.num_updates is not None:
+            raise ValueError("--num_updates needs --offline_dataset (an online run is sized by --num_timesteps)")
+        return None
+    online_only = [k for k in ("overlap_acting", "device_env", "prioritized", "one_launch") if getattr(args, k)] + (["n_step"] if args.n_step != 1 else [])
+    if online_only:
+        raise ValueError("--offline_dataset excludes " + ", ".join("--" + k for k in online_only) + ": there is no env loop to shape")
+    if args.num_updates is not None and args.num_updates < 1:
+        raise ValueError("--num_updates must be >= 1")
+    return dict(dataset=args.offline_dataset, num_updates=args.num_updates, bc_alpha=bc_alpha, plain=bc_alpha == 0.0)
+
+
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
-            device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False, **over):
-    """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU."""
+            device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
+            offline_dataset=None, num_updates=None, **over):
+    """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
+    `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
+    `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
+    `bc_alpha` in `over` turns the TD3+BC actor term on."""
     import json
     import time
     from pathlib import Path
@@ -232,8 +261,18 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     # --prioritized: the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4), call by call
     # --n_step N > 1: n-step returns chained by the engine, call by call as well
     # --one_launch: either of them (or both) as one graph launch per iteration instead
-    metrics = loop.train(cfg, env, agent, fused=not prioritized and n_step == 1, evaluator=ev, overlap=overlap_acting, device_env=device_env,
-                         prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch)
+    if offline_dataset is not None:
+        with np.load(offline_dataset) as z:
+            data = {k: z[k] for k in z.files}
+        if data["observations"].shape[1:] != (o,) or data["actions"].shape[1:] != (a,):
+            raise ValueError(f"{offline_dataset}: observations / actions are {data['observations'].shape[1:]} / {data['actions'].shape[1:]}, "
+                             f"{env_id} has ({o},) / ({a},)")
+        loop.load_dataset(agent, data)
+        metrics = loop.train_offline(cfg, agent, num_updates=int(num_updates if num_updates is not None else cfg.num_timesteps),
+                                     evaluator=ev, eval_every_updates=int(cfg.eval_every))
+    else:
+        metrics = loop.train(cfg, env, agent, fused=not prioritized and n_step == 1, evaluator=ev, overlap=overlap_acting, device_env=device_env,
+                             prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -250,6 +289,7 @@ def _worker_main(args) -> int:
     import importlib
     import json
     jobs = shard_jobs(sweep_jobs(args.env_bundle, args.num_seeds), args.world, args.rank)
+    plan = offline_plan(args) or {}
     factory = None
     if args.env_factory:
         mod, fn = args.env_factory.split(":")
@@ -262,7 +302,8 @@ def _worker_main(args) -> int:
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
                           eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity,
                           overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized,
-                          n_step=args.n_step, one_launch=args.one_launch)
+                          n_step=args.n_step, one_launch=args.one_launch, offline_dataset=plan.get("dataset"),
+                          num_updates=plan.get("num_updates"), bc_alpha=args.bc_alpha)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -298,13 +339,26 @@ def main(argv=None) -> int:
                     help="with --prioritized and / or --n_step N > 1: issue the iteration as one graph launch (loop.train one_launch=True)")
     ap.add_argument("--n_step", type=int, default=1,
                     help="train the critics on N-step returns chained by the engine (loop.train n_step=...; above 1 the iteration is issued call by call)")
+    ap.add_argument("--offline_dataset", default=None, metavar="FILE.npz",
+                    help="train on a fixed dataset instead of an env loop: an .npz with observations, actions, rewards, next_observations, "
+                         "terminations [, dones] of the job's env dims (loop.load_dataset + loop.train_offline); evaluated every --eval_every updates")
+    ap.add_argument("--bc_alpha", type=float, default=None,
+                    help="TD3+BC: the behaviour-cloning actor term with this alpha (2.5 in Fujimoto & Gu 2021); needs --algo td3")
+    ap.add_argument("--num_updates", type=int, default=None, help="with --offline_dataset: iterations to run (default: --num_timesteps)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--world", type=int, default=1, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    try:
+        plan = offline_plan(args)
+    except ValueError as ex:
+        ap.error(str(ex))
     if args.worker:
         return _worker_main(args)
+    if plan is not None and plan["plain"]:
+        print(f"launcher: --offline_dataset without --bc_alpha: plain {args.algo.upper()} on a fixed ring (no behaviour-cloning term; "
+              "--algo td3 --bc_alpha 2.5 is TD3+BC)", file=sys.stderr, flush=True)
     # parent: touches no GPU (no torch import, no HIP call); one fresh child per GPU
     jobs = sweep_jobs(args.env_bundle, args.num_seeds)
     world = max(1, min(args.gpus, len(jobs)))

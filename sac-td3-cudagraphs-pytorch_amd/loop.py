@@ -4,6 +4,8 @@ be driven end to end without tensordict / torchrl / gymnasium being importable:
   Rollout / segment()   the acting side + its generator  orchestrator.py:42-118   
   DeviceRollout         the same acting side for a vector env that lives on the GPU: every array a device tensor, no host wait
   train()       the training loop's control flow       orchestrator.py:317-352 (+ counters :326,342,349)
+  load_dataset() / train_offline()   training on a FIXED dataset (not in the reference): the ring filled once, then runs of whole
+                periods through Engine.run_iterations -- the workload of TD3+BC (hps.bc_alpha > 0)
   ProportionalSampler   proportional prioritised replay (not in the reference): a priority array on the device for train(sampler=...)
   episode()     evaluation-episode generator           orchestrator.py:121-246 (lengths / returns, trajectories with need_lists; no pixels)
   evaluate()    offline evaluation of a checkpoint     orchestrator.py:415-481 (trajectory files as .npz)
@@ -294,6 +296,70 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     if ro is not None:
         ro.resolve()                                                      # leave no acting call in flight behind the loop
     return agent.engine.read_metrics()
+
+
+_DATASET_KEYS = ("observations", "actions", "rewards", "next_observations", "terminations")
+
+
+def load_dataset(agent, data, chunk: int = 65536) -> int:
+    """Append a whole offline dataset to the agent's replay ring, `chunk` rows per `rb.extend` call, in order.  `data`: a mapping with
+    the keys of `rb.extend` -- observations [n, o], actions [n, a], rewards [n] or [n, 1], next_observations [n, o], terminations [n]
+    or [n, 1], optionally dones (default: terminations) -- whose values are numpy arrays or CUDA tensors (device tensors are appended
+    where they are, without a host round trip).  Raises ValueError if the rows do not fit into what is left of the ring's capacity:
+    the ring would wrap and silently drop the oldest rows.  Normalising the states (as the TD3+BC paper does) is the caller's
+    business, before this call: the engine trains on the rows it is given.  Returns the number of rows appended."""
+    missing = [k for k in _DATASET_KEYS if k not in data]
+    if missing:
+        raise ValueError(f"load_dataset: missing key(s) {missing}")
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"load_dataset: chunk must be >= 1, got {chunk}")
+    cols = {k: data[k] for k in _DATASET_KEYS}
+    cols["dones"] = data["dones"] if "dones" in data else data["terminations"]
+    rows = {k: int(v.shape[0]) for k, v in cols.items()}
+    n = rows["observations"]
+    if len(set(rows.values())) != 1:
+        raise ValueError(f"load_dataset: the fields disagree on the number of rows: {rows}")
+    room = int(agent.rb.capacity) - len(agent.rb)
+    if n > room:
+        raise ValueError(f"load_dataset: {n} rows do not fit into the replay ring ({room} of {int(agent.rb.capacity)} rows free): "
+                         "it would wrap and drop data; build the agent with a larger rb_capacity")
+    for lo in range(0, n, chunk):
+        agent.rb.extend({k: v[lo:lo + chunk] for k, v in cols.items()})
+    return n
+
+
+def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Evaluator"] = None,
+                  on_eval: Optional[Callable[[Any, int], None]] = None, eval_every_updates: Optional[int] = None) -> Dict[str, float]:
+    """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
+    between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
+    runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
+    `eval_every_updates` iterations; None: none before the end) and at `num_updates`.  `evaluator` and / or `on_eval(agent, updates
+    done)` run at those points.  Keeps `qnet_updates_so_far` and `actor_updates_so_far` as Agent.iteration does and leaves
+    `timesteps_so_far` alone (no env step was taken).  With plain TD3 or SAC this diverges on most datasets -- the actor climbs Q where
+    no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  Returns the last metrics."""
+    num_updates = int(num_updates)
+    if num_updates < 0:
+        raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
+    every = num_updates if eval_every_updates is None else int(eval_every_updates)
+    if eval_every_updates is not None and every < 1:
+        raise ValueError(f"train_offline: eval_every_updates must be >= 1, got {eval_every_updates}")
+    eng = agent.engine
+    period, delay = int(eng.cfg.actor_update_delay) + 1, int(eng.cfg.actor_update_delay)
+    i = 0
+    while i < num_updates:
+        end = min(num_updates, (i // every + 1) * every) if every > 0 else num_updates
+        eng.run_iterations(i, end - i)
+        eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1      # every iteration drew a new sample: older batch handles are stale
+        agent.qnet_updates_so_far += end - i
+        agent.actor_updates_so_far += delay * len(range(-(-i // period) * period, end, period))      # the iterations with i % period == 0
+        i = end
+        if i % every == 0 or i == num_updates:
+            if evaluator is not None:
+                evaluator(agent)
+            if on_eval is not None:
+                on_eval(agent, i)
+    return eng.read_metrics()
 
 
 class Tabular:
