@@ -544,6 +544,8 @@ int sactd3_sync(sactd3_engine* e);                                          /* [
 /* ---- introspection for tests / profiling (not part of the reference surface) ---- */
 /* copy a named internal device buffer to the host; returns the number of floats it holds (or < 0).
  * With dst == NULL only the size is returned. Names: see sactd3_debug_names(). [sync]
+ * "a_h2", "a_xh2" [B][256], "a_rs2" [B] and "a_tg" [B][4][a4] (a4 = ac_dim rounded up to 4; per row tanh(raw log-std), std and the
+ * squashed sample y at offsets 0, a4 and 2 a4; TD3: tanh(mean) at offset 0) are what the last policy pass stored for the head backward.
  * "grad_critics", "c_dz1", "grad_actor", "a_dz1": SACTD3_ESTATE while the family's last writer was a period / cut-short period
  * graph, which leaves them out (see sactd3_step_period) -- stale gradients are not handed out.
  * "prio_leaf" [rb_capacity], "prio_sums" (the level above the leaves: one sum per 1024 slots), "prio_max" [1] and "prio_weights"

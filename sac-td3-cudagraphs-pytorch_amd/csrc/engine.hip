@@ -3251,6 +3251,7 @@ static std::vector<DbgEntry> dbg_table(sactd3_engine* e) {
       {"X", S.X, B * e->ldc}, {"Xn", S.Xn, B * e->ldc}, {"Xp", e->Xp, B * e->ldc}, {"rew", S.rew, B}, {"done", S.done, B},
       {"logp_next", S.logp_n, B}, {"logp_pi", e->logp_pi, B}, {"logp_alpha", e->logp_al, B},
       {"a_xh1", e->a_xh1, BH}, {"a_h1", e->a_h1, BH}, {"a_z2", e->a_z2, BH}, {"a_h2", e->a_h2, BH}, {"a_du", e->a_du, B * e->ldu},
+      {"a_xh2", e->a_xh2, BH}, {"a_rs2", e->a_rs2, B}, {"a_tg", e->a_tg, B * 4 * e->a4},
       {"a_dz2", e->a_dz2, BH}, {"a_dh1", e->a_dh1, BH}, {"a_dz1", e->a_dz1, BH},
       {"c_xh1", e->c_xh1, 2 * BH}, {"c_h1", e->c_h1, 2 * BH}, {"c_z2", e->c_z2, 2 * BH}, {"c_dz2", e->c_dz2, 2 * BH},
       {"c_dh1", e->c_dh1, 2 * BH}, {"c_dz1", e->c_dz1, 2 * BH}, {"t_z2", e->t_z2, 2 * BH},
@@ -3258,7 +3259,7 @@ static std::vector<DbgEntry> dbg_table(sactd3_engine* e) {
   };
 }
 const char* sactd3_debug_names(void) {
-  return "X Xn Xp rew done logp_next logp_pi logp_alpha a_xh1 a_h1 a_z2 a_h2 a_du a_dz2 a_dh1 a_dz1 c_xh1 c_h1 c_z2 c_dz2 c_dh1 c_dz1 "
+  return "X Xn Xp rew done logp_next logp_pi logp_alpha a_xh1 a_h1 a_z2 a_h2 a_xh2 a_rs2 a_tg a_du a_dz2 a_dh1 a_dz1 c_xh1 c_h1 c_z2 c_dz2 c_dh1 c_dz1 "
          "t_z2 q q_target targ_q q_pi dA grad_actor grad_critics prio_leaf prio_sums prio_max prio_weights";
 }
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {

@@ -44,7 +44,10 @@ DIMS = {"hopper": (11, 3, 1.0), "halfcheetah": (17, 6, 1.0), "humanoid": (376, 1
         # action vector the folded dQ/da takes)
         "sac4": (9, 4, 1.0), "td3_2": (5, 2, 2.0), "td3_7": (13, 7, 1.0),
         # the widest head (nh = 64 under SAC) and odd widths on both sides of the fused first layer's 64 inputs, at large batch
-        "o3a32": (3, 32, 0.7), "o48a17": (48, 17, 0.7)}
+        "o3a32": (3, 32, 0.7), "o48a17": (48, 17, 0.7),
+        # tests/test_gpu_tail_edges.py: 5 actions under SAC (nh = 10: the general tail and head backward below the large-batch
+        # threshold); 8 actions under TD3 (the narrow head without the folded dQ/da)
+        "sac5": (7, 5, 1.0), "td3_8": (10, 8, 1.0)}
 
 
 def synth_transitions(n, o, a, bound, seed=0):

@@ -28,6 +28,15 @@ def test_library_exports_every_declared_symbol():
     assert pkg.load_library().sactd3_abi_version() == _lib.ABI_VERSION
 
 
+def test_debug_names_list_what_the_head_backward_reads():
+    """sactd3_debug_names: the policy pass's stores for the head backward are readable (tests/test_gpu_tail_edges.py reads them)"""
+    import sac_td3_cudagraphs_pytorch_amd as pkg
+    names = pkg.load_library().sactd3_debug_names().decode().split()
+    assert len(names) == len(set(names))
+    for name in ("a_h2", "a_xh2", "a_rs2", "a_tg", "a_du", "a_dz2", "dA", "q_pi", "t_z2"):
+        assert name in names, name
+
+
 def test_config_struct_layout_and_defaults():
     import sac_td3_cudagraphs_pytorch_amd as pkg
     from sac_td3_cudagraphs_pytorch_amd import _lib
