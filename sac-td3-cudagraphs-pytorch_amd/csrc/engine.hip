@@ -20,6 +20,12 @@
 
 #include "../../include/sactd3.h"
 #include "kernels.h"
+__global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v; }      // (set_flag)
+#include "prio_kernels.h"
+#include "nstep_kernels.h"
+// All device code stands above.  The order of the template instances in the code object is pinned by this list, not by where the
+// host code below names them: a new instance is appended there.
+#include "kernel_instances.inc"
 
 static thread_local std::string g_create_error;
 
@@ -644,6 +650,38 @@ static TnProb tn_cols(const TnProb& q, int k_lo, int k) {
   return r;
 }
 static void tn_fin(TnProb& q, int slot, int off, int nblk) { q.fin_slot[q.nfin] = slot; q.fin_off[q.nfin] = off; q.fin_nblk[q.nfin++] = nblk; }
+// The layer-1 problem with the layer's LayerNorm backward folded in (TnProb::fold): L = the net's layout, ps = the row-sum partials
+// that the launch in front left, with its gamma1 snapshot g behind them (fold_args); dz: where dz1 goes for inspection
+static void tn_fold(TnProb& q, int ln, const NetLayout& L, const float* xh, const float* rstd, const float* ps, float* dz, const float* g) {
+  q.fold = 1; q.f_ln = ln; q.f_g_off = L.g1; q.f_be_off = L.be1; q.f_xh = xh; q.f_rstd = rstd; q.f_ps = ps; q.f_dz = dz; q.f_g = g;
+}
+// ... and what the fused tail + dh1 launch in front of it is told (NnFold): the partials and the snapshot it leaves for tn_fold
+static NnFold fold_args(bool fold, int ln, const NetLayout& L, const float* h1, const float* xh1, float* ps, float* gsnap) {
+  NnFold f{};
+  f.fold = fold; f.ln = ln; f.h1 = h1; f.xh1 = xh1; f.g1_off = L.g1; f.ps = ps; f.gsnap = gsnap;
+  return f;
+}
+// dh1 = dz2 W2 of nets that lie ns floats apart in dz2 / dh1 and p_ns floats apart in the parameter arena holding W2
+static NnArgs dh1_args(const float* dz2, const float* W2, float* dh1, int M, long ns, long p_ns) {
+  NnArgs g{};
+  g.dY = dz2; g.dy_ns = ns; g.Wt = W2; g.ldw = HID; g.p_ns = p_ns; g.k_off = 0;
+  g.dX = dh1; g.ldx = HID; g.dx_ns = ns; g.M = M; g.Kout = HID;
+  return g;
+}
+// layer 1's LayerNorm backward as a launch of its own: dz1 from dh1 and the forward pass's stores (gamma: the first net's gamma1)
+static LnBwd ln_bwd_args(const sactd3_engine* e, const float* dh, const float* xh, const float* h, const float* rstd,
+                         const float* gamma, long p_ns, int want_part, float* dz) {
+  LnBwd l{};
+  l.dh = dh; l.xh = xh; l.h = h; l.rstd = rstd; l.gamma = gamma; l.p_ns = p_ns;
+  l.B = e->B; l.ln = e->cfg.layer_norm; l.want_part = want_part; l.dz = dz; l.part = e->part; l.pstride = e->nblk4;
+  return l;
+}
+// what the two launches around a folded dQ/da agree on (QaFold of k_qtail_nn, QaIn of k_headbwd_nn): the partials' shape and place
+template <class Qa>
+static void qa_fold_args(Qa& q, const sactd3_engine* e) {
+  q.on = 1; q.ln = e->cfg.layer_norm; q.a = e->a; q.pqw = e->a <= 3 ? 8 : 16; q.ntile = HID / (e->nq_actor == 2 ? 32 : 16);
+  q.ps = e->qa_ps; q.S = e->qa_S;
+}
 
 // The two hidden layers of MLP trunks: z2 = relu(LN(x W1^T + b1)) W2^T + b2 for up to two groups of nets
 // (a group = nets sharing an input and a parameter arena) in ONE launch.  One kernel when the input is narrow
@@ -770,9 +808,6 @@ static NoiseJob noise_job(sactd3_engine* e, int site_buf, unsigned site_code, in
 static int tail_rows_per_block(const ActorTail& t) { return (t.L.nh <= 8 && t.a <= 8) ? 4 : 16; }
 // The tails t[0 .. n) (all of B rows through the same head shape) as ONE launch of the kernel that holds `width` of them: 1; 2 (the
 // opening pair's target-action and policy tails); 5 (the run-ahead: n <= 5, blocks exist for n tails only).  4-row or 16-row form.
-// (The 5-tail form's launch stands behind enqueue_update_actor: the compiler emits kernel template instances in the order this file
-//  first names them, and k_ln_bwd<16> came out with other instructions when k_actor_tail_s5<4> was named here, ahead of it.)
-static int launch_tails5(EnqCtx& x, const ActorTail5& T, double fl, double by, dim3 grid, dim3 block);
 static int launch_tails(EnqCtx& x, int width, const ActorTail* t, int n) {
   const int B = t[0].B, nh = t[0].L.nh, a = t[0].a, o = t[0].o;
   const bool rows4 = tail_rows_per_block(t[0]) == 4;
@@ -792,7 +827,9 @@ static int launch_tails(EnqCtx& x, int width, const ActorTail* t, int n) {
     for (int i = 0; i < 5; ++i) T.t[i] = t[i < n ? i : 0];                               // (the copies never run: blocks exist for n tails only)
     T.nb = nb; T.n = n;
     // (a policy pass at the end -- the next period's -- also writes its backward stores and [s | pi(s)])
-    return launch_tails5(x, T, fl, 4.0 * n * ((double)B * HID + (double)nh * (HID + 1) + 2.0 * HID + (double)B * (3 * a + 2)) + (t[n - 1].train ? 8.0 * (double)B * (HID + o) : 0.0), grid, block);
+    const double by = 4.0 * n * ((double)B * HID + (double)nh * (HID + 1) + 2.0 * HID + (double)B * (3 * a + 2)) + (t[n - 1].train ? 8.0 * (double)B * (HID + o) : 0.0);
+    if (rows4) LAUNCH("k_actor_tail_s5<4>", fl, by, k_actor_tail_s5<4>, grid, block, T);
+    else LAUNCH("k_actor_tail5", fl, by, k_actor_tail5, grid, block, T);
   }
   return 0;
 }
@@ -922,11 +959,6 @@ static int enqueue_opening_pair(EnqCtx& x, const IterPlace& it, bool fused_sampl
   return launch_tails(x, 2, t, 2);
 }
 
-// The weighted critic tails (IterPlace::weighted) are launched from the end of this file: the compiler emits kernel template instances in
-// the order the file first names them (see launch_tails), and the new instances are named behind every existing one.
-static int launch_ctail_nn_w(EnqCtx& x, const CtailNn& f, const float* w, double fl, double by, dim3 grid);
-static int launch_critic_tail_w(EnqCtx& x, const CriticTail& t, const float* w, double fl, double by, dim3 grid);
-
 // agents/agent.py:183-242
 // fused_sample: see enqueue_opening_pair (false: the API path -- the batch slot was filled by the caller, no policy pass, no target update).
 // it.targets: with the target updates in the optimiser epilogue (see enqueue_step, actor_target_rides).
@@ -972,26 +1004,22 @@ static int enqueue_update_qnets(EnqCtx& x, const IterPlace& it, bool fused_sampl
     if (fused_tail_nn) {   // 16-row blocks x 32-column tiles
       CtailNn f{};
       f.c = t; f.c.pstride = e->nblk4; f.Wt = e->Pc + e->Lc.W2; f.ldw = HID; f.dX = e->c_dh1;
-      f.f.fold = fold_ln1; f.f.ln = ln; f.f.h1 = e->c_h1; f.f.xh1 = e->c_xh1; f.f.g1_off = e->Lc.g1; f.f.ps = e->c_ps; f.f.gsnap = e->c_ps + 2L * B * PS_W;
+      f.f = fold_args(fold_ln1, ln, e->Lc, e->c_h1, e->c_xh1, e->c_ps, e->c_ps + 2L * B * PS_W);
       f.xr = pick_xr(e->nblk, HID / 32, 4.0 * 3 * B * HID, 4.0 * HID * HID);
       const double fl = 2.0 * 4 * B * (double)HID + 2.0 * 2 * (double)B * HID * HID, by = 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B) + 4.0 * 2 * ((double)HID * HID + (double)B * HID);
       const dim3 grid((unsigned)(e->nblk * (HID / 32)), 1, 2);
-      if (it.weighted) RCCHK(launch_ctail_nn_w(x, f, S.w, fl, by + 4.0 * B, grid));
+      if (it.weighted) LAUNCH("k_ctail_nn_w<2>", fl, by + 4.0 * B, k_ctail_nn_w<2>, grid, dim3(256), (CtailNnW{f, S.w}));
       else LAUNCH("k_ctail_nn<2>", fl, by, k_ctail_nn<2>, grid, dim3(256), f);
-    } else if (it.weighted) RCCHK(launch_critic_tail_w(x, t, S.w, 2.0 * 4 * B * (double)HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 9.0 * B), dim3(e->nblk, 2)));
-    else LAUNCH("k_critic_tail<16>", 2.0 * 4 * B * (double)HID, 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B), k_critic_tail<16>, dim3(e->nblk, 2), dim3(256), t);
+    } else {
+      const double fl = 2.0 * 4 * B * (double)HID, by = 4.0 * (6.0 * BH + 4.0 * 4 * HID + 8.0 * B);
+      if (it.weighted) LAUNCH("k_critic_tail_w<16>", fl, by + 4.0 * B, k_critic_tail_w<16>, dim3(e->nblk, 2), dim3(256), (CriticTailW{t, S.w}));
+      else LAUNCH("k_critic_tail<16>", fl, by, k_critic_tail<16>, dim3(e->nblk, 2), dim3(256), t);
+    }
   }
-  if (!fused_tail_nn) {  // dh1 = dz2 W2
-    NnArgs g{};
-    g.dY = e->c_dz2; g.dy_ns = BH; g.Wt = e->Pc + e->Lc.W2; g.ldw = HID; g.p_ns = e->Lc.size; g.k_off = 0;
-    g.dX = e->c_dh1; g.ldx = HID; g.dx_ns = BH; g.M = B; g.Kout = HID;
-    RCCHK(launch_nn(x, "k_nn.dh1", g, 2));
-  }
+  if (!fused_tail_nn)  // dh1 = dz2 W2
+    RCCHK(launch_nn(x, "k_nn.dh1", dh1_args(e->c_dz2, e->Pc + e->Lc.W2, e->c_dh1, B, BH, e->Lc.size), 2));
   if (!fold_ln1) {
-    LnBwd l{};
-    l.dh = e->c_dh1; l.xh = e->c_xh1; l.h = e->c_h1; l.rstd = e->c_rs1;
-    l.gamma = e->Pc + e->Lc.g1; l.p_ns = e->Lc.size; l.B = B; l.ln = ln; l.want_part = ln;
-    l.dz = e->c_dz1; l.part = e->part; l.pstride = e->nblk4;
+    const LnBwd l = ln_bwd_args(e, e->c_dh1, e->c_xh1, e->c_h1, e->c_rs1, e->Pc + e->Lc.g1, e->Lc.size, ln, e->c_dz1);
     LAUNCH("k_ln_bwd<16>", 0.0, 4.0 * 2 * (4.0 * BH + B + HID), k_ln_bwd<16>, dim3(e->nblk, 2), dim3(256), l);
   }
   {  // every critic gradient + the Adam step (+ Polyak) in one launch:
@@ -1003,11 +1031,9 @@ static int enqueue_update_qnets(EnqCtx& x, const IterPlace& it, bool fused_sampl
     if (ln) { tn_fin(g.pr[i2], 0, e->Lc.g2, e->nblk); tn_fin(g.pr[i2], 1, e->Lc.be2, e->nblk); }
     tn_fin(g.pr[i2], 2, e->Lc.Wh, e->nblk); g.pr[i2].fin_s_off = e->Lc.bh; g.pr[i2].fin_s_nblk = e->nblk;
     g.pr[i1] = tn_prob(fold_ln1 ? e->c_dh1 : e->c_dz1, HID, BH, HID, S.X, e->ldc, 0, e->o + e->a, e->Lc.W1, e->Lc.ld1, e->Lc.b1);
+    if (!fold_ln1 && ln) { tn_fin(g.pr[i1], 3, e->Lc.g1, e->nblk); tn_fin(g.pr[i1], 4, e->Lc.be1, e->nblk); }
     if (fold_ln1) {
-      TnProb& q = g.pr[i1];
-      q.fold = 1; q.f_ln = ln; q.f_g_off = e->Lc.g1; q.f_be_off = e->Lc.be1; q.f_xh = e->c_xh1; q.f_rstd = e->c_rs1; q.f_ps = e->c_ps; q.f_dz = e->c_dz1; q.f_g = e->c_ps + 2L * B * PS_W;
-    } else if (ln) { tn_fin(g.pr[i1], 3, e->Lc.g1, e->nblk); tn_fin(g.pr[i1], 4, e->Lc.be1, e->nblk); }
-    if (fold_ln1) {
+      tn_fold(g.pr[i1], ln, e->Lc, e->c_xh1, e->c_rs1, e->c_ps, e->c_dz1, e->c_ps + 2L * B * PS_W);
       g.nprob = 3;
       g.pr[1] = tn_cols(g.pr[0], HID / 2, HID / 2); g.pr[0] = tn_cols(g.pr[0], 0, HID / 2); g.pr[0].xr_force = g.pr[1].xr_force = 8;
       std::swap(g.pr[1], g.pr[2]);
@@ -1123,7 +1149,6 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
   const bool fused_qtail_nn = B < BIG_BATCH;
   // dQ/da finished inside the two fused launches around it (QaFold): narrow heads, ac_dim <= 7
   const bool qa_fold = fused_qtail_nn && small_head && e->a <= 7;    // (small_head: k_headbwd_nn is the consumer)
-  const int qa_ntile = HID / (nq == 2 ? 32 : 16), qa_pqw = e->a <= 3 ? 8 : 16;
   {
     ActorQTail t{};
     t.z2c = e->c_z2; t.P = e->Pc; t.p_ns = e->Lc.size; t.L = e->Lc; t.logp = e->logp_pi; t.log_alpha = e->la;
@@ -1132,8 +1157,8 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
       QtailNn f{};
       f.c = t; f.Wt = e->Pc + e->Lc.W2; f.ldw = HID; f.dX = e->c_dh1;
       if (qa_fold) {
-        f.qa.on = 1; f.qa.ln = ln; f.qa.a = e->a; f.qa.pqw = qa_pqw; f.qa.ntile = qa_ntile; f.qa.h1 = e->c_h1; f.qa.xh1 = e->c_xh1;
-        f.qa.g1_off = e->Lc.g1; f.qa.w1_off = e->Lc.W1; f.qa.ld1 = e->Lc.ld1; f.qa.k_off = e->o; f.qa.ps = e->qa_ps; f.qa.S = e->qa_S;
+        qa_fold_args(f.qa, e);
+        f.qa.h1 = e->c_h1; f.qa.xh1 = e->c_xh1; f.qa.g1_off = e->Lc.g1; f.qa.w1_off = e->Lc.W1; f.qa.ld1 = e->Lc.ld1; f.qa.k_off = e->o;
       }
       const double fl = 2.0 * nq * B * (double)HID + 2.0 * nq * (double)B * HID * HID, by = 4.0 * nq * (2.0 * BH + 4.0 * HID + 2.0 * B) + 4.0 * nq * ((double)HID * HID + (double)B * HID);
       if (nq == 2) {
@@ -1145,17 +1170,9 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
       }
     } else LAUNCH("k_actorq_tail<4>", 2.0 * nq * B * (double)HID, 4.0 * nq * (2.0 * BH + 4.0 * HID + 2.0 * B), k_actorq_tail<4>, dim3(e->nblk4), dim3(64), t);
   }
-  if (!fused_qtail_nn) {
-    NnArgs g{};
-    g.dY = e->c_dz2; g.dy_ns = BH; g.Wt = e->Pc + e->Lc.W2; g.ldw = HID; g.p_ns = e->Lc.size; g.k_off = 0;
-    g.dX = e->c_dh1; g.ldx = HID; g.dx_ns = BH; g.M = B; g.Kout = HID;
-    RCCHK(launch_nn(x, "k_nn.dh1", g, nq));
-  }
+  if (!fused_qtail_nn) RCCHK(launch_nn(x, "k_nn.dh1", dh1_args(e->c_dz2, e->Pc + e->Lc.W2, e->c_dh1, B, BH, e->Lc.size), nq));
   if (!qa_fold) {
-    LnBwd l{};
-    l.dh = e->c_dh1; l.xh = e->c_xh1; l.h = e->c_h1; l.rstd = e->c_rs1;
-    l.gamma = e->Pc + e->Lc.g1; l.p_ns = e->Lc.size; l.B = B; l.ln = ln; l.want_part = 0;
-    l.dz = e->c_dz1; l.part = e->part; l.pstride = e->nblk4;
+    LnBwd l = ln_bwd_args(e, e->c_dh1, e->c_xh1, e->c_h1, e->c_rs1, e->Pc + e->Lc.g1, e->Lc.size, 0, e->c_dz1);
     // fused: dA_i = dz1_i W1_i[:, o:o+a]  (gradient of Q_i with respect to the action)
     l.W1 = e->Pc + e->Lc.W1; l.ldw1 = e->Lc.ld1; l.k_off = e->o; l.na = e->a; l.dA = e->dA; l.ldA = e->a4;
     LAUNCH("k_ln_bwd<16>.dQ/da", 2.0 * nq * B * (double)HID * e->a, 4.0 * nq * (4.0 * BH + B + HID + (double)HID * e->a + (double)B * e->a),
@@ -1178,11 +1195,8 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
     if (fused_head_nn) {   // column partials per 16-row block
       HeadBwdNn f{};
       f.c = h; f.Wt = e->Pa + e->La.W2; f.ldw = HID; f.dX = e->a_dh1;
-      if (qa_fold) {
-        f.qa.on = 1; f.qa.ln = ln; f.qa.a = e->a; f.qa.pqw = qa_pqw; f.qa.ntile = qa_ntile; f.qa.ps = e->qa_ps; f.qa.S = e->qa_S;
-        f.qa.rstd = e->c_rs1; f.qa.dA = e->dA;
-      }
-      f.f.fold = fold_ln1; f.f.ln = ln; f.f.h1 = e->a_h1; f.f.xh1 = e->a_xh1; f.f.g1_off = e->La.g1; f.f.ps = e->a_ps; f.f.gsnap = e->a_ps + (long)B * PS_W;
+      if (qa_fold) { qa_fold_args(f.qa, e); f.qa.rstd = e->c_rs1; f.qa.dA = e->dA; }
+      f.f = fold_args(fold_ln1, ln, e->La, e->a_h1, e->a_xh1, e->a_ps, e->a_ps + (long)B * PS_W);
       f.xr = pick_xr(e->nblk, HID / 16, 4.0 * 2 * B * HID, 4.0 * HID * HID);
       const double fl = 2.0 * B * (double)HID * e->nh + 2.0 * (double)B * HID * HID;
       const double by = 4.0 * (3.0 * BH + (double)e->nh * HID + (double)B * (nq * e->a + 4 * e->a + e->nh)) + 4.0 * ((double)HID * HID + (double)B * HID);
@@ -1191,23 +1205,15 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
     } else {
       const double fl = 2.0 * B * (double)HID * e->nh, by = 4.0 * (3.0 * BH + (double)e->nh * HID + (double)B * (nq * e->a + 4 * e->a + e->nh));
       if (small_head) {
-        // (the plain instance is named first: template instances are emitted in the order they are first named, and the helpers two
-        //  instances share are emitted with the first -- the other way round the plain kernel's machine code changed)
-        if (!e->bc_on) LAUNCH("k_actor_head_bwd_s<4>", fl, by, k_actor_head_bwd_s<4>, dim3(e->nblk4), dim3(64), h);
-        else LAUNCH("k_actor_head_bwd_s_bc<4>", fl, by + 4.0 * B * (2.0 * e->a + 1), k_actor_head_bwd_s_bc<4>, dim3(e->nblk4), dim3(64), h, bk);
+        if (e->bc_on) LAUNCH("k_actor_head_bwd_s_bc<4>", fl, by + 4.0 * B * (2.0 * e->a + 1), k_actor_head_bwd_s_bc<4>, dim3(e->nblk4), dim3(64), h, bk);
+        else LAUNCH("k_actor_head_bwd_s<4>", fl, by, k_actor_head_bwd_s<4>, dim3(e->nblk4), dim3(64), h);
       } else if (e->bc_on) LAUNCH("k_actor_head_bwd_bc", fl, by + 4.0 * B * (2.0 * e->a + 1), k_actor_head_bwd_bc, dim3(e->nblk), dim3(256), h, bk);
       else LAUNCH("k_actor_head_bwd", fl, by, k_actor_head_bwd, dim3(e->nblk), dim3(256), h);
     }
   }
-  if (!fused_head_nn) {
-    NnArgs g{};
-    g.dY = e->a_dz2; g.Wt = e->Pa + e->La.W2; g.ldw = HID; g.k_off = 0; g.dX = e->a_dh1; g.ldx = HID; g.M = B; g.Kout = HID;
-    RCCHK(launch_nn(x, "k_nn.dh1", g, 1));
-  }
+  if (!fused_head_nn) RCCHK(launch_nn(x, "k_nn.dh1", dh1_args(e->a_dz2, e->Pa + e->La.W2, e->a_dh1, B, 0, 0), 1));
   if (!fold_ln1) {
-    LnBwd l{};
-    l.dh = e->a_dh1; l.xh = e->a_xh1; l.h = e->a_h1; l.rstd = e->a_rs1; l.gamma = e->Pa + e->La.g1;
-    l.B = B; l.ln = ln; l.want_part = ln; l.dz = e->a_dz1; l.part = e->part; l.pstride = e->nblk4;
+    const LnBwd l = ln_bwd_args(e, e->a_dh1, e->a_xh1, e->a_h1, e->a_rs1, e->Pa + e->La.g1, 0, ln, e->a_dz1);
     LAUNCH("k_ln_bwd<16>", 0.0, 4.0 * (4.0 * BH + B + HID), k_ln_bwd<16>, dim3(e->nblk, 1), dim3(256), l);
   }
   {  // every actor gradient (+ Adam unless clip_grad_norm_ needs the global norm first) in one launch:
@@ -1220,11 +1226,11 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
     const int nb_head = (small_head && !fused_head_nn) ? e->nblk4 : e->nblk;      // row blocks that wrote the head backward's column partials
     if (ln) { tn_fin(g.pr[i2], 0, e->La.g2, nb_head); tn_fin(g.pr[i2], 1, e->La.be2, nb_head); }
     g.pr[i1] = tn_prob(fold_ln1 ? e->a_dh1 : e->a_dz1, HID, 0, HID, SX, e->ldc, 0, e->o, e->La.W1, e->La.ld1, e->La.b1);
+    if (!fold_ln1 && ln) { tn_fin(g.pr[i1], 3, e->La.g1, e->nblk); tn_fin(g.pr[i1], 4, e->La.be1, e->nblk); }
     if (fold_ln1) {
-      TnProb& q = g.pr[i1];
-      q.fold = 1; q.f_ln = ln; q.f_g_off = e->La.g1; q.f_be_off = e->La.be1; q.f_xh = e->a_xh1; q.f_rstd = e->a_rs1; q.f_ps = e->a_ps; q.f_dz = e->a_dz1; q.f_g = e->a_ps + (long)B * PS_W;
-    } else if (ln) { tn_fin(g.pr[i1], 3, e->La.g1, e->nblk); tn_fin(g.pr[i1], 4, e->La.be1, e->nblk); }
-    if (fold_ln1) { g.nprob = 4; g.pr[2] = tn_rows(g.pr[1], 48, HID - 48); g.pr[1] = tn_rows(g.pr[1], 0, 48); std::swap(g.pr[2], g.pr[3]); }
+      tn_fold(g.pr[i1], ln, e->La, e->a_xh1, e->a_rs1, e->a_ps, e->a_dz1, e->a_ps + (long)B * PS_W);
+      g.nprob = 4; g.pr[2] = tn_rows(g.pr[1], 48, HID - 48); g.pr[1] = tn_rows(g.pr[1], 0, 48); std::swap(g.pr[2], g.pr[3]);
+    }
     g.part = e->part; g.pstride = e->nblk4; g.part_s = e->part_s;
     g.apply = clip ? 0 : 1; g.P = e->Pa; g.Mo = e->Ma; g.Vo = e->Va; g.T = clip ? nullptr : polyak_targ; g.tau = c.polyak; g.adam = e->ctl->adam_a;
     if (td3 && g.T && (ahead > 0 || chain_slot >= 0)) { g.T2 = e->Ta2; g.T3 = e->Ta3; }   // the actor target of the next two Polyak updates, now
@@ -1320,12 +1326,6 @@ static int enqueue_update_actor(EnqCtx& x, const IterPlace& it, int j, bool fuse
   return 0;
 }
 
-static int launch_tails5(EnqCtx& x, const ActorTail5& T, double fl, double by, dim3 grid, dim3 block) {      // (see launch_tails)
-  if (block.x == 64) LAUNCH("k_actor_tail_s5<4>", fl, by, k_actor_tail_s5<4>, grid, block, T);
-  else LAUNCH("k_actor_tail5", fl, by, k_actor_tail5, grid, block, T);
-  return 0;
-}
-
 // agents/agent.py:328-331
 enum { POLYAK_CRITICS = 1, POLYAK_ACTOR = 2 };
 static int enqueue_polyak(EnqCtx& x, int which) {
@@ -1403,7 +1403,6 @@ static int actor_write_begin(sactd3_engine* e) {
   return 0;
 }
 
-__global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v; }
 static int set_flag(sactd3_engine* e, int* dst, int v) {
   hipLaunchKernelGGL(k_set_int1, dim3(1), dim3(1), 0, e->stream, dst, v);
   HIPCHK(hipGetLastError());
@@ -1417,12 +1416,8 @@ static int publish_rb_state(sactd3_engine* e) {
 }
 
 // ------------------------------------------------------------------------------------------------ ring rows into batch slot 0: launches
-// Device code and launches of the staging calls (stage_ring_rows, in the replay-buffer part of the C ABI below) and of the engine-owned
-// priorities.  Plain kernels only: no template instance is first named here, so none moves in the code object.  All of it stands in
-// front of the extern "C" block, where a kernel keeps its C++ name and a helper may be a template.
-#include "prio_kernels.h"
-#include "nstep_kernels.h"
-
+// Launches of the staging calls (stage_ring_rows, in the replay-buffer part of the C ABI below) and of the engine-owned priorities
+// (device code: prio_kernels.h, nstep_kernels.h).  They stand in front of the extern "C" block, where a helper may be a template.
 static int slot_weights_alloc(sactd3_engine* e) {      // (never zeroed: every staging kernel writes all B entries before anything reads them)
   return e->bs[0].w ? 0 : dalloc(e, &e->bs[0].w, (size_t)e->B, false);
 }
@@ -3320,6 +3315,12 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
   hipEvent_t t0, t1;
   HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1));
   int rc = 0;
+  // the engine's own staging slab as five strided fields, one record per row: [s | a] [s'] [r] [d, as the float's first byte]
+  auto slab_fields = [&](auto& f) {
+    f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
+    f.dones = (decltype(f.dones))(e->stage_dev + e->ldc + e->ldo + 1);
+    f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f;
+  };
   auto body = [&]() -> int {
     EnqCtx x{e, e->stream};
     // (slot_refilled: only where the kernel being timed overwrites batch slot 0)
@@ -3340,9 +3341,7 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       // the device-boundary pack kernels, fed from the engine's own staging slab read as five strided fields (batch_size rows into
       // the batch slot / an env step's max_envs rows into the ring: both are overwritten)
       sactd3_device_fields f{};
-      f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
-      f.dones = (const uint8_t*)(e->stage_dev + e->ldc + e->ldo + 1);
-      f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f;
+      slab_fields(f);
       if (!strcmp(kernel, "batch_from_fields")) { slot_refilled(e, false, false); return launch_batch_fields(e, field_src(e, &f, 0)); }
       return launch_ingest_fields(e, field_src(e, &f, 0), (int)std::min<int64_t>(std::min(e->maxn, e->B), e->cfg.rb_capacity));
     }
@@ -3355,9 +3354,8 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       // of the pack kernels' sources above; the index goes to the two pad floats behind [r, d], which are 8-byte aligned); the rows
       // kernel takes its indices from time_idx (the current slot's idx, widened: prepared below, before anything is timed)
       sactd3_device_fields_out f{};
-      f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
-      f.dones = (uint8_t*)(e->stage_dev + e->ldc + e->ldo + 1); f.index = (int64_t*)(e->stage_dev + e->ldc + e->ldo + 2);
-      f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f; f.index_ld = e->rec_f / 2;
+      slab_fields(f);
+      f.index = (int64_t*)(e->stage_dev + e->ldc + e->ldo + 2); f.index_ld = e->rec_f / 2;
       if (!strcmp(kernel, "batch_to_fields")) return launch_batch_out(e, field_dst(e, &f, 0));
       return launch_rows_out(e, field_dst(e, &f, 0), e->time_idx, 1, e->B, (int)e->rb_len);
     }
@@ -3546,17 +3544,3 @@ extern "C" __attribute__((visibility("default"))) int sactd3_debug_phases(sactd3
   return 0;
 }
 #endif
-
-// ---- the two launches of the weighted form of sactd3_update_qnets.  They stand here, behind everything else, because the compiler
-// emits kernel template instances in the order this file first names them (see launch_tails): the instances that existed before keep
-// their place, and with it their machine code.
-static int launch_ctail_nn_w(EnqCtx& x, const CtailNn& f, const float* w, double fl, double by, dim3 grid) {
-  const CtailNnW g{f, w};
-  LAUNCH("k_ctail_nn_w<2>", fl, by, k_ctail_nn_w<2>, grid, dim3(256), g);
-  return 0;
-}
-static int launch_critic_tail_w(EnqCtx& x, const CriticTail& t, const float* w, double fl, double by, dim3 grid) {
-  const CriticTailW g{t, w};
-  LAUNCH("k_critic_tail_w<16>", fl, by, k_critic_tail_w<16>, grid, dim3(256), g);
-  return 0;
-}

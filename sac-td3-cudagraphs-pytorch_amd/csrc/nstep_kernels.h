@@ -1,5 +1,5 @@
 // N-step returns staged from the ring (include/sactd3.h: sactd3_rb_sample_nstep*): device code.
-// Included behind prio_kernels.h: every kernel that existed before keeps its place in the code object, and with it its machine code.
+// Included by engine.hip behind prio_kernels.h (the graph form reads the ring's state through its helpers).
 //
 // k_batch_from_index_nstep is k_batch_from_index with a chain walk in front of the copy.  Per batch row with start slot i0:
 //   age(i)  = i while len < cap, else (i - cursor) mod cap            (rows the slot is behind the oldest one)

@@ -1,6 +1,5 @@
 // Proportional prioritised replay (Schaul et al. 2016, proportional variant, draws with replacement) as engine state: device code.
-// Included behind kernels.h and every kernel engine.hip itself defines: those keep their place in the code object, and with it their
-// machine code.
+// Included by engine.hip behind kernels.h (its structs and helpers are used here).
 //
 // Structure: a flat two-level table.  leaf[slot] = p^alpha of ring slot `slot` (0 for a slot the ring has not filled), in groups of
 // PRIO_G = 1024 consecutive slots; sums[g] = the sum of group g's leaves.  The top level is as wide as the ring needs (977 sums for a

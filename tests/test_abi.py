@@ -172,3 +172,28 @@ def test_fetch_width_table_matches_the_code_objects(engine_asm):
         seen.add(inst)
         assert (narrow / (wide + narrow) >= 0.3) == (pmc_summary.fetch_factor(inst) == 1.0), (inst, wide, narrow)
     assert set(pmc_summary.MIXED) <= seen and len(seen) >= 40
+
+
+def test_kernel_instance_manifest_matches_the_code_object(engine_asm):
+    """csrc/kernel_instances.inc pins the order in which the template instances are emitted (an instance's machine code has been
+    seen to change with that order), so that host code may stand anywhere in engine.hip.  Check it against the compiled gfx950 code:
+    the template instances of the code object are the manifest's lines -- the same instances, the same count, the same order -- and
+    all of them stand behind the plain kernels.  An instance that is launched but not listed is emitted behind the listed ones and
+    fails here.  And engine.hip includes the manifest once, in front of its first launch."""
+    import subprocess
+    csrc = os.path.join(ROOT, "sac-td3-cudagraphs-pytorch_amd", "csrc")
+    names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", engine_asm[1], re.M)
+    dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")[:len(names)]
+    is_inst = [d.startswith("void ") for d in dem]
+    first = is_inst.index(True)
+    assert all(is_inst[first:]), [d for d, t in zip(dem[first:], is_inst[first:]) if not t]      # no plain kernel behind an instance
+    listed = [line[len("template __global__ "):].rstrip().rstrip(";") for line in open(os.path.join(csrc, "kernel_instances.inc"))
+              if line.startswith("template __global__ ")]
+    blank = lambda s: re.sub(r"\s+", "", s)
+    assert [blank(d) for d in dem[first:]] == [blank(s) for s in listed]
+    assert len(listed) == len(set(listed)) >= 71
+    src = open(os.path.join(csrc, "engine.hip")).read()
+    inc = '#include "kernel_instances.inc"'
+    assert src.count(inc) == 1
+    launches = [i for i in (src.find("LAUNCH("), src.find("hipLaunchKernelGGL")) if i >= 0]
+    assert launches and src.index(inc) < min(launches)
