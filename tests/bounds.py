@@ -6,7 +6,7 @@ the only difference left is the engine's own fp32 rounding.  For that the classi
 summation order (sequential, blocked, split over slices, MFMA tiles): with u = 2^-24 and gamma(n) = n u / (1 - n u),
     sum_i a_i b_i  in fp32  differs from the exact value by at most  gamma(n) sum_i |a_i b_i|       (Higham, Thm. 3.5 / 4.4).
 The bounds below are that bound times SAFETY = 2, set before any run; none of them is taken from an observed error, and none
-allows a fraction of elements to be outside.
+allows a fraction of elements to be outside.  (prio_draw_tol is the plain worst case of its add count, without SAFETY: see there.)
 """
 import numpy as np
 
@@ -498,6 +498,53 @@ def clip_coef(G, clip):
     """coef = min(1, clip / (||G||_2 + 1e-6)) in float64 and the relative error of the engine's fp32 norm, gamma(n)"""
     G = f64(G)
     return min(1.0, float(clip) / (float(np.sqrt((G * G).sum())) + 1e-6)), gamma(G.size + 2)
+
+
+# ---------------------------------------------------------------------------------------------------- prioritised draw
+# (csrc/prio_kernels.h: prio_draw_body; tests/test_gpu_priorities_scale.py; checked on the CPU by tests/test_prio_model.py)
+
+# fp32 adds on the longest path to ...
+PRIO_ADDS_GROUP = 3 + 6 + 3         # a group sum: in the thread, the Kogge-Stone steps of a wave, the four wave sums
+PRIO_ADDS_LEAF = 16                 # a running sum inside a group: 3 + 6 + 2 (woff) + 1 (woff + before) + 3 (in the thread) + 1 (front + ...)
+
+
+def prio_draw_tol(T, nch):
+    """How far m may lie outside the float64 running-sum interval of the slot a draw selects.  The draw compares m with fp32
+    running sums of non-negative terms; a sum reached by n adds is within gamma(n) of the exact one, and none exceeds T.
+      top level: the group sums themselves (PRIO_ADDS_GROUP), the same depth again for the scan over them, nch carry adds, the
+                 carry + front add and up to 4 adds in the thread                                  -> 2 * 12 + nch + 1 + 4
+      residue:   m - excl, one subtract of two values below T                                      -> 1
+      leaves:    the running sums inside the chosen group                                          -> PRIO_ADDS_LEAF
+    The top level's error moves the group boundary m is compared with, the subtract and the leaf level move the boundary inside
+    the group: the three add up.  gamma(n) is already the worst case of every order of n adds, so no SAFETY factor is put on top;
+    the count is generous instead (the in-thread adds are counted in the scan depth and again)."""
+    return gamma(2 * PRIO_ADDS_GROUP + nch + 1 + 4 + 1 + PRIO_ADDS_LEAF) * float(T)
+
+
+def prio_draw_interval(name, leaf, length, slots, m, nch, C=None):
+    """Every drawn slot s with its m = fl32(u T), as the device or the fp32 model formed it from its own T, against the float64
+    inclusive running sums C of the leaves of [0, length):  C[s-1] - tol <= m <= C[s] + tol, tol = prio_draw_tol(C[-1], nch).
+    Refused outright: a slot outside [0, length), a slot whose leaf is not positive.  Returns the worst err / tol."""
+    leaf = f64(leaf)[:length]
+    C = np.cumsum(leaf) if C is None else C
+    slots, m = np.asarray(slots, np.int64).reshape(-1), f64(m).reshape(-1)
+    assert C.shape == (length,) and slots.shape == m.shape
+    bad = (slots < 0) | (slots >= length)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise Violation(f"{name}: draw {i} selected slot {int(slots[i])}, outside the {length} rows held")
+    zero = ~(leaf[slots] > 0)
+    if zero.any():
+        i = int(np.flatnonzero(zero)[0])
+        raise Violation(f"{name}: draw {i} selected slot {int(slots[i])}, whose leaf is {leaf[slots[i]]!r}")
+    tol = prio_draw_tol(C[-1], nch)
+    lo = np.where(slots > 0, C[np.maximum(slots - 1, 0)], 0.0)
+    err = np.maximum(np.maximum(lo - m, m - C[slots]), 0.0)
+    if (err > tol).any():
+        i = int(np.argmax(err))
+        raise Violation(f"{name}: {int((err > tol).sum())} of {err.size} draws outside their interval; worst draw {i}: slot {int(slots[i])}, "
+                        f"m {m[i]!r} against [{lo[i]!r}, {C[slots[i]]!r}], err {err[i]:.3e} tol {tol:.3e}")
+    return float((err / tol).max()) if err.size else 0.0
 
 
 # ---------------------------------------------------------------------------------------------------- inputs
