@@ -339,6 +339,45 @@ int sactd3_nstep_info_device(sactd3_engine* e, int32_t* k, int64_t k_ld, int32_t
 /* [sync] out = {n-step stagings, rows staged, rows cut short (k < steps), rows refused}; the last two are counted on the device */
 int sactd3_nstep_stats(sactd3_engine* e, int64_t out[4]);
 
+/* ---- prior data under an online run (RLPD, Ball et al. 2023: a fixed share of every batch from a dataset that is never evicted, LayerNorm
+ * critics, several updates per env step).  Not in the reference.  Two pieces: a pinned prefix of the ring, and a draw that takes m batch
+ * rows from it and B - m from the rows behind it.  Nothing above changes: an engine that never pins or mixes holds nothing more and
+ * launches nothing more than before.
+ * sactd3_rb_pin: slots [0, n) become rows no append overwrites.  Allowed while the ring has never overwritten a row (host state),
+ * 0 <= n <= sactd3_rb_len and n < rb_capacity; it may be called again under the same conditions, n == 0 unpins.  Refused with nothing
+ * changed: SACTD3_EINVAL for n out of range; SACTD3_ESTATE once the ring has wrapped (the live region included), and while priorities
+ * are enabled.  With P = the pinned count > 0 every append path (sactd3_rb_extend, _extend_device, _extend_fields_device) goes
+ * round-robin over [P, cap): the cursor wraps to P, not to 0; sactd3_rb_len still saturates at cap; an append of more than cap - P rows
+ * keeps the last cap - P (as one of cap or more rows keeps the last cap today).  The ingest kernels are the same: they are told the ring
+ * advanced by P records, the cursor less P and the capacity cap - P.  The device's ring length and cursor keep their absolute meaning.
+ * Unchanged on a pinned ring: sactd3_rb_sample, sactd3_step*, sactd3_rb_sample_with_indices, the read-outs, sactd3_qvalues* -- every
+ * slot below sactd3_rb_len holds a row, and they draw over all of them.
+ * Out of scope for now, SACTD3_ESTATE while P > 0: sactd3_prio_enable, the three n-step staging calls (sactd3_rb_sample_nstep_device,
+ * _nstep, _prioritized_nstep), sactd3_step_sampled with n_step > 1, sactd3_rb_fill_synthetic.  The n-step age formula and the priority
+ * refresh assume ONE wrap point, at slot 0; their two-region forms are a later change.
+ * Pinning is run-time state: it is not part of a checkpoint. */
+int sactd3_rb_pin(sactd3_engine* e, int64_t n);
+int64_t sactd3_rb_pinned(const sactd3_engine* e);                          /* the current P */
+/* m = `prior_rows`: how many rows of a mixed batch come from the pinned rows.  Host state next to P; the device's copy of both lives in a
+ * small struct made at the first mixed draw, and a changed m or P costs one single-thread launch in front of the next graph that reads
+ * them (as a changed beta does), never a graph capture.  SACTD3_EINVAL for prior_rows outside [0, batch_size]; whether the ring can
+ * serve m is checked where a draw is asked for. */
+int sactd3_rb_set_mix(sactd3_engine* e, int prior_rows);
+/* rb.sample(batch_size) with a fixed share of prior data.  With w_b the 32-bit Philox word philox_index(seed, sample_ctr, b, .) selects
+ * for batch row b (the stream of sactd3_rb_sample: counter words (sample counter, 0, 0x100, b >> 2), word b & 3), len = sactd3_rb_len:
+ *     b <  m:  slot = (w_b * P) >> 32                   (a pinned row)
+ *     b >= m:  slot = P + ((w_b * (len - P)) >> 32)     (a live row)
+ * The sample counter advances once, as in sactd3_rb_sample; with P == 0 and m == 0 the slots ARE those of sactd3_rb_sample, bit for
+ * bit.  Batch slot 0 receives the rows and their ring slots, bit for bit what sactd3_rb_sample_indices_device leaves for the same
+ * indices; the slot carries no loss weights and sactd3_update_qnets behind it is the unweighted one.  Two launches: the draw (one
+ * workgroup; it ticks the counter itself) and k_batch_from_index on an engine-owned int64 index array.  No copy command, no host wait.
+ * SACTD3_ESTATE, checked on the host, nothing changed (the run-ahead chain of sactd3_step_period included): an empty ring; m > 0 with
+ * P == 0; m < batch_size with no live row (sactd3_rb_len == P).  An accepted call breaks the run-ahead chain and makes slot 0 current. */
+int sactd3_rb_sample_mixed(sactd3_engine* e);
+/* host counters: out = {mixed draws (sactd3_step_sampled's included), prior rows drawn, live rows drawn, appends that wrapped at the
+ * pinned boundary (the cursor came back to P)} */
+int sactd3_mix_stats(sactd3_engine* e, int64_t out[4]);
+
 /* rb.sample(batch_size) (orchestrator.py:338): uniform-with-replacement indices from the engine's
  * Philox stream + gather into the engine-owned batch slot. */
 int sactd3_rb_sample(sactd3_engine* e);
@@ -380,10 +419,17 @@ int sactd3_step(sactd3_engine* e, int do_actor);
  * captured graphs -- and replayed while the ring grows and `beta` anneals; a changed `beta` or switch costs one single-thread launch
  * in front of the graph.  Uniform with n_step == 1 is sactd3_step itself.  With use_graphs == 0 the same launches are issued eagerly.
  * Refused, with nothing changed: NULL struct, unknown `draw`, n_step outside [1, 16], stride < 1 at n_step > 1, beta negative or
- * not finite (SACTD3_EINVAL); a prioritised draw before sactd3_prio_enable, an empty ring (SACTD3_ESTATE). */
-enum { SACTD3_DRAW_UNIFORM = 0, SACTD3_DRAW_PRIORITIZED = 1 };
+ * not finite (SACTD3_EINVAL); a prioritised draw before sactd3_prio_enable, an empty ring (SACTD3_ESTATE).
+ * SACTD3_DRAW_MIXED: the mixed draw of sactd3_rb_sample_mixed (below: prior data under an online run) in place of the uniform one, with
+ * the current sactd3_rb_set_mix / sactd3_rb_pin values.  The graph holds, in order: the draw (graph form: it reads the ring length, P
+ * and m from device memory, and ticks the sample counter), k_batch_from_index_g, the UNWEIGHTED critic update, the actor updates, the
+ * target update; no priority write-back.  Bit for bit, host state included, the call sequence sactd3_rb_sample_mixed ->
+ * sactd3_update_qnets -> [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets.  Captured under the same
+ * (draw, n_step, stride) key and replayed while the ring grows, the live region wraps and m and P change (a changed m or P costs one
+ * single-thread launch in front of the graph).  n_step must be 1 (SACTD3_EINVAL); the refusals of sactd3_rb_sample_mixed apply. */
+enum { SACTD3_DRAW_UNIFORM = 0, SACTD3_DRAW_PRIORITIZED = 1, SACTD3_DRAW_MIXED = 2 };
 typedef struct {
-  int32_t draw;      /* SACTD3_DRAW_UNIFORM | SACTD3_DRAW_PRIORITIZED */
+  int32_t draw;      /* SACTD3_DRAW_UNIFORM | SACTD3_DRAW_PRIORITIZED | SACTD3_DRAW_MIXED */
   int32_t n_step;    /* 1 .. 16 */
   int32_t stride;    /* rows between two steps of one env; ignored at n_step == 1 */
   float beta;        /* exponent of the importance weights; ignored by the uniform draw (but checked) */
@@ -572,7 +618,8 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
  * sactd3_rb_sample_prioritized with beta 0.4 -- its three launches, the batch slot overwritten, the draw counter advanced -- / the
  * write-back kernel on batch_size rows, indices as for "rows_to_fields", every priority 1: those rows' priorities are overwritten),
  * "batch_from_index_nstep" (the staging kernel of sactd3_rb_sample_nstep_device on batch_size rows with steps = 3, stride = 1: indices
- * as for "rows_to_fields", no weights, into the batch slot). [sync] */
+ * as for "rows_to_fields", no weights, into the batch slot), "mix_draw" (the draw kernel of sactd3_rb_sample_mixed alone, with the current
+ * P and m: the sample counter advances, the batch slot stays; SACTD3_ESTATE where sactd3_rb_sample_mixed is refused). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

@@ -20,6 +20,7 @@ DST_ORDERED = 1     # sactd3_read_batch_device / sactd3_rb_read_rows_device / sa
 Q_ONLINE, Q_TARGET = 0, 1   # sactd3_qvalues / sactd3_qvalues_device `which`
 ESTATE, EINVAL = -3, -1
 DRAW_UNIFORM, DRAW_PRIORITIZED = 0, 1   # sactd3_sampling.draw
+DRAW_MIXED = 2                          # ... the mixed draw over pinned and live rows (sactd3_rb_pin / sactd3_rb_set_mix)
 
 # every symbol include/sactd3.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -43,6 +44,7 @@ SYMBOLS = [
     "sactd3_step_sampled", "sactd3_step_sampled_stats",
     "sactd3_step_periods", "sactd3_step_periods_stats",
     "sactd3_set_bc", "sactd3_get_bc",
+    "sactd3_rb_pin", "sactd3_rb_pinned", "sactd3_rb_set_mix", "sactd3_rb_sample_mixed", "sactd3_mix_stats",
 ]
 
 
@@ -170,6 +172,11 @@ def load_library():
         "sactd3_step_periods_stats": (C.c_int, [vp, i64p]),
         "sactd3_set_bc": (C.c_int, [vp, C.c_float, C.c_float]),
         "sactd3_get_bc": (C.c_int, [vp, fp]),
+        "sactd3_rb_pin": (C.c_int, [vp, C.c_int64]),
+        "sactd3_rb_pinned": (C.c_int64, [vp]),
+        "sactd3_rb_set_mix": (C.c_int, [vp, C.c_int]),
+        "sactd3_rb_sample_mixed": (C.c_int, [vp]),
+        "sactd3_mix_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -458,6 +458,27 @@ class ReplayBuffer:
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
         return self._staged(eng, n_step, stride, "rb_sample_prioritized", "rb_sample_prioritized_nstep", beta)
 
+    def pin(self, n: Optional[int] = None) -> None:
+        """Protect the first `n` rows (None: every row held now) from eviction: a dataset loaded before the online run starts
+        (include/sactd3.h: sactd3_rb_pin).  extend() then goes round-robin over the slots behind them.  Allowed before the buffer has
+        wrapped; pin(0) unpins.  Excludes enable_priorities() and n_step > 1 for now.  Not saved in checkpoints."""
+        eng = self._need()
+        eng.rb_pin(eng.rb_len() if n is None else int(n))
+
+    @property
+    def pinned(self) -> int:
+        return 0 if self._engine is None else self._engine.rb_pinned()
+
+    def sample_mixed(self, batch_size: int, prior_rows: int) -> BatchHandle:
+        """sample() with a fixed share of prior data: the first `prior_rows` rows of the batch are drawn from the pinned rows, the
+        others from the rows behind them (sactd3_rb_sample_mixed) -- the index stream of sample(), one counter tick, no weights.  The
+        handle is a sample()'s in every respect: older handles go stale."""
+        eng = self._need()
+        assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
+        if int(prior_rows) != getattr(eng, "_mix_rows", None):
+            eng.rb_set_mix(int(prior_rows))
+        return self._staged(eng, 1, 1, "rb_sample_mixed", "rb_sample_mixed")
+
     def update_priorities(self, index=None, priorities=None) -> None:
         """The write-back.  No arguments: the rows of the batch slot get |TD error| (the larger of the twin critics') + eps of the
         critic update that just ran on them (sactd3_prio_update_from_td).  Both arguments: ring slots (int64, as for rows()) and their
@@ -716,14 +737,21 @@ class Agent:
     def update_targ_nets(self) -> None:
         self.engine.update_targ_nets(self.qnet_updates_so_far)
 
-    def iteration(self, i: int, *, beta: Optional[float] = None, n_step: int = 1, stride: Optional[int] = None) -> None:
+    def iteration(self, i: int, *, beta: Optional[float] = None, n_step: int = 1, stride: Optional[int] = None,
+                  prior_rows: Optional[int] = None) -> None:
         """orchestrator.py:337-352 as ONE graph launch (sample, critic, delayed actor x N, Polyak); keeps the
         reference's counters.  `beta` (needs ReplayBuffer.enable_priorities): the sample is drawn by priority, the critic update is
         weighted by the importance weights of exponent beta and its TD errors go back into the priorities; `n_step`, `stride`: as for
         ReplayBuffer.sample -- all inside the same launch (include/sactd3.h: sactd3_step_sampled), equal to the call sequence
-        sample_prioritized / sample -> update_qnets -> update_priorities -> update_actor x N -> update_targ_nets bit for bit."""
+        sample_prioritized / sample -> update_qnets -> update_priorities -> update_actor x N -> update_targ_nets bit for bit.
+        `prior_rows` (needs ReplayBuffer.pin): the sample is ReplayBuffer.sample_mixed's, inside the same launch; it excludes
+        `beta` and n_step > 1."""
         do_actor = i % (self.engine.cfg.actor_update_delay + 1) == 0
-        if beta is None and n_step == 1 and stride is None:
+        if prior_rows is not None:
+            if beta is not None or n_step != 1:
+                raise ValueError("iteration: prior_rows (the mixed draw) excludes beta and n_step > 1")
+            self.engine.step_sampled(do_actor, prior_rows=int(prior_rows))
+        elif beta is None and n_step == 1 and stride is None:
             self.engine.step(do_actor)
         else:
             n_step, stride = _n_step_args("iteration", n_step, stride)

@@ -23,6 +23,7 @@
 __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v; }      // (set_flag)
 #include "prio_kernels.h"
 #include "nstep_kernels.h"
+#include "mix_kernels.h"
 // All device code stands above.  The order of the template instances in the code object is pinned by this list, not by where the
 // host code below names them: a new instance is appended there.
 #include "kernel_instances.inc"
@@ -225,6 +226,17 @@ struct sactd3_engine {
   bool bc_on = false;
   float bc_alpha = 0.f, bc_weight = 1.f;
   float* bc_part = nullptr;
+  // Prior data under an online run (sactd3_rb_pin / sactd3_rb_set_mix; device code: mix_kernels.h).  rb_pinned = P: appends go round
+  // [P, cap) and never write slots [0, P) (ring_append, the one place that moves the cursor).  rb_wrapped: an append has overwritten a
+  // row -- pinning is allowed before that only.  Run-time state, not part of a checkpoint.  mix_m: batch rows a mixed draw takes from
+  // the pinned rows.  mix_ctl (the device's P and m, read by the graph form of the draw) and mix_idx (the drawn slots, int64
+  // [B rounded up to 4]) are made at the first mixed draw -- an engine that never mixes holds nothing more than before; mix_pub: what
+  // the host last published into mix_ctl (-1: nothing yet).  mix_stats: sactd3_mix_stats.
+  int64_t rb_pinned = 0; bool rb_wrapped = false;
+  int mix_m = 0;
+  struct MixCtl* mix_ctl = nullptr; long long* mix_idx = nullptr;
+  int64_t mix_pub[2] = {-1, -1};
+  int64_t mix_stats[4] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -1414,6 +1426,24 @@ static int publish_rb_state(sactd3_engine* e) {
   HIPCHK(hipGetLastError());
   return 0;
 }
+// THE cursor arithmetic of every append path (sactd3_rb_extend, _extend_device, _extend_fields_device).  With P = rb_pinned the
+// appends go round-robin over [P, cap): the ingest kernels take (ring, cursor, cap) as launch arguments and are told the ring advanced
+// by P records, the cursor relative to P and the region's size cap - P -- with P == 0 exactly what they were told before.
+// ring_region: the most rows one launch may append.  ring_append: moves the host's cursor and length over `chunk` <= ring_region rows
+// and returns what the launch is told; new_len / new_cursor (what the kernel publishes into DevCtl) keep their absolute meaning.
+struct RingSpan { float4* ring; int cursor, cap; int first /* absolute slot of the first row written */, new_len, new_cursor; };
+static inline int64_t ring_region(const sactd3_engine* e) { return (int64_t)e->cfg.rb_capacity - e->rb_pinned; }
+static RingSpan ring_append(sactd3_engine* e, int chunk) {
+  const int64_t cap = e->cfg.rb_capacity, P = e->rb_pinned, region = cap - P, rel = e->rb_cursor - P;
+  RingSpan s{};
+  s.ring = (float4*)e->ring + (size_t)P * e->rec4; s.cursor = (int)rel; s.cap = (int)region; s.first = (int)e->rb_cursor;
+  if (e->rb_len + chunk > cap) e->rb_wrapped = true;             // a row is being overwritten
+  if (P > 0 && rel + chunk >= region) ++e->mix_stats[3];         // the cursor comes back to P, not to 0
+  e->rb_cursor = P + (rel + chunk) % region;
+  e->rb_len = std::min<int64_t>(cap, e->rb_len + chunk);
+  s.new_len = (int)e->rb_len; s.new_cursor = (int)e->rb_cursor;
+  return s;
+}
 
 // ------------------------------------------------------------------------------------------------ ring rows into batch slot 0: launches
 // Launches of the staging calls (stage_ring_rows, in the replay-buffer part of the C ABI below) and of the engine-owned priorities
@@ -1542,15 +1572,53 @@ static PrioUpdateArgs prio_td_args(sactd3_engine* e, int slot) {
 //   sactd3_rb_sample_prioritized[_nstep] | sactd3_rb_sample_nstep -> sactd3_update_qnets -> [sactd3_prio_update_from_td] ->
 //   [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets
 // launch, launch for launch, with the staging and priority kernels in their graph forms.  (The 1-step uniform iteration is sactd3_step.)
-struct SampledPlan { bool prio; int steps, stride; bool actor, targets; };
+// ---- the mixed draw (device code: mix_kernels.h)
+static int mix_alloc(sactd3_engine* e) {
+  if (e->mix_ctl && e->mix_idx) return 0;
+  if (!e->mix_idx) RCCHK(dalloc(e, &e->mix_idx, (size_t)round_up(e->B, 4)));
+  if (!e->mix_ctl) RCCHK(dalloc(e, &e->mix_ctl, 1));
+  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
+  return 0;
+}
+// what a mixed draw needs of the ring, checked on the host, which knows len, P and m (NULL: nothing to refuse)
+static const char* mix_refusal(const sactd3_engine* e) {
+  if (e->rb_len <= 0) return "buffer is empty";
+  if (e->mix_m > 0 && e->rb_pinned == 0) return "prior rows were asked for (sactd3_rb_set_mix) but no row is pinned (sactd3_rb_pin)";
+  if (e->mix_m < e->B && e->rb_len == e->rb_pinned) return "live rows were asked for but every row of the ring is pinned";
+  return nullptr;
+}
+// the device's copy of P and m, for the graph form: one single-thread launch, and only when a value changed
+static int mix_publish(sactd3_engine* e) {
+  if (e->mix_pub[0] == e->rb_pinned && e->mix_pub[1] == e->mix_m) return 0;
+  hipLaunchKernelGGL(k_set_int2, dim3(1), dim3(1), 0, e->stream, &e->mix_ctl->pinned, (int)e->rb_pinned, e->mix_m);
+  HIPCHK(hipGetLastError());
+  e->mix_pub[0] = e->rb_pinned; e->mix_pub[1] = e->mix_m;
+  return 0;
+}
+// the draw (it advances the sample counter itself) and the staging of the drawn slots: the two launches in front of the critic update
+static int launch_mix_draw(sactd3_engine* e, bool graph_form) {
+  const MixDrawArgs d{e->ctl, e->mix_idx, e->B, (int)e->rb_len, (int)e->rb_pinned, e->mix_m};
+  if (graph_form) hipLaunchKernelGGL(k_mix_draw<true>, dim3(1), dim3(256), 0, e->stream, d, (const MixCtl*)e->mix_ctl, (int)e->cfg.rb_capacity);
+  else hipLaunchKernelGGL(k_mix_draw<false>, dim3(1), dim3(256), 0, e->stream, d, (const MixCtl*)nullptr, 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int mix_draw_launches(sactd3_engine* e, bool graph_form = false) {
+  RCCHK(launch_mix_draw(e, graph_form));
+  return launch_batch_index(e, e->mix_idx, 1, nullptr, 1, graph_form);
+}
+static inline void mix_count(sactd3_engine* e) { ++e->mix_stats[0]; e->mix_stats[1] += e->mix_m; e->mix_stats[2] += e->B - e->mix_m; }
+
+struct SampledPlan { bool prio; int steps, stride; bool actor, targets; bool mixed = false; };
 static int enqueue_step_sampled(EnqCtx& x, const SampledPlan& sp) {
   sactd3_engine* e = x.e;
   if (sp.prio) RCCHK(prio_draw_launches(e, 0.f, true));
   const long long* idx = sp.prio ? e->pt_idx : nullptr;
   const float* w = sp.prio ? e->pt_w : nullptr;
-  if (sp.steps > 1) RCCHK(launch_batch_nstep(e, idx, 1, w, 1, sp.prio ? e->bs[0].w : nullptr, sp.steps, sp.stride, true));
+  if (sp.mixed) RCCHK(mix_draw_launches(e, true));      // (unweighted, no chain; the draw kernel has advanced the sample counter)
+  else if (sp.steps > 1) RCCHK(launch_batch_nstep(e, idx, 1, w, 1, sp.prio ? e->bs[0].w : nullptr, sp.steps, sp.stride, true));
   else RCCHK(launch_batch_index(e, idx, 1, w, 1, true));
-  if (!sp.prio) {      // the uniform draw was made at the sample counter, which now advances
+  if (!sp.prio && !sp.mixed) {      // the uniform draw was made at the sample counter, which now advances
     hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, x.s, &e->ctl->sample_ctr, (int*)nullptr);
     HIPCHK(hipGetLastError());
   }
@@ -1882,10 +1950,9 @@ int sactd3_rb_extend(sactd3_engine* e, const float* obs, const float* act, const
   if (!e || !obs || !act || !rew || !nobs || !dones || n < 0) return e ? e->fail(SACTD3_EINVAL, "rb_extend: bad argument") : SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
-  const int64_t cap = e->cfg.rb_capacity;
   int done_rows = 0;
   while (done_rows < n) {
-    const int chunk = (int)std::min<int64_t>(std::min(n - done_rows, e->stage_rows), cap);
+    const int chunk = (int)std::min<int64_t>(std::min(n - done_rows, e->stage_rows), ring_region(e));
     // staging slots are reused round-robin; one stream sync per lap of the ring of slots guarantees that the copy
     // that last read a slot has completed (events / device-written flags cost more per call than this amortised sync)
     if (++e->stage_used == NSTAGE) { HIPCHK(hipStreamSynchronize(e->stream)); e->stage_used = 1; }
@@ -1898,14 +1965,13 @@ int sactd3_rb_extend(sactd3_engine* e, const float* obs, const float* act, const
     // one launch: the kernel reads the staged rows from pinned host memory, writes them round-robin into the ring
     // (wrapping at capacity) and publishes the new length / cursor
     IngestArgs g{};
-    g.src = (const float4*)st; g.ring = (float4*)e->ring; g.rec4 = e->rec4; g.n = chunk; g.cursor = (int)e->rb_cursor; g.cap = (int)cap;
-    e->rb_cursor = (e->rb_cursor + chunk) % cap;
-    e->rb_len = std::min<int64_t>(cap, e->rb_len + chunk);
-    g.len_cursor = &e->ctl->rb_len; g.new_len = (int)e->rb_len; g.new_cursor = (int)e->rb_cursor;
+    const RingSpan sp = ring_append(e, chunk);
+    g.src = (const float4*)st; g.ring = sp.ring; g.rec4 = e->rec4; g.n = chunk; g.cursor = sp.cursor; g.cap = sp.cap;
+    g.len_cursor = &e->ctl->rb_len; g.new_len = sp.new_len; g.new_cursor = sp.new_cursor;
     const int blocks = (int)std::min<long>(256, ((long)chunk * e->rec4 + 255) / 256);
     hipLaunchKernelGGL(k_rb_ingest, dim3(std::max(blocks, 1)), dim3(256), 0, e->stream, g);
     HIPCHK(hipGetLastError());
-    RCCHK(prio_after_append(e, g.cursor, chunk));
+    RCCHK(prio_after_append(e, sp.first, chunk));
     done_rows += chunk;
   }
   return 0;
@@ -1928,20 +1994,18 @@ int sactd3_rb_extend_device(sactd3_engine* e, const float* records, int n) {
     (void)hipGetLastError();
     return e->fail(SACTD3_EINVAL, "rb_extend_device: `records` is not a device pointer");
   }
-  const int64_t cap = e->cfg.rb_capacity;
   int done_rows = 0;
   while (done_rows < n) {
-    const int chunk = (int)std::min<int64_t>(n - done_rows, cap);
+    const int chunk = (int)std::min<int64_t>(n - done_rows, ring_region(e));
     IngestArgs g{};
-    g.src = (const float4*)(records + (size_t)done_rows * e->rec_f); g.ring = (float4*)e->ring; g.rec4 = e->rec4; g.n = chunk;
-    g.cursor = (int)e->rb_cursor; g.cap = (int)cap;
-    e->rb_cursor = (e->rb_cursor + chunk) % cap;
-    e->rb_len = std::min<int64_t>(cap, e->rb_len + chunk);
-    g.len_cursor = &e->ctl->rb_len; g.new_len = (int)e->rb_len; g.new_cursor = (int)e->rb_cursor;
+    const RingSpan sp = ring_append(e, chunk);
+    g.src = (const float4*)(records + (size_t)done_rows * e->rec_f); g.ring = sp.ring; g.rec4 = e->rec4; g.n = chunk;
+    g.cursor = sp.cursor; g.cap = sp.cap;
+    g.len_cursor = &e->ctl->rb_len; g.new_len = sp.new_len; g.new_cursor = sp.new_cursor;
     const int blocks = (int)std::min<long>(1024, ((long)chunk * e->rec4 + 255) / 256);
     hipLaunchKernelGGL(k_rb_ingest, dim3(std::max(blocks, 1)), dim3(256), 0, e->stream, g);
     HIPCHK(hipGetLastError());
-    RCCHK(prio_after_append(e, g.cursor, chunk));
+    RCCHK(prio_after_append(e, sp.first, chunk));
     done_rows += chunk;
   }
   return 0;
@@ -2071,16 +2135,14 @@ static int src_order_end(sactd3_engine* e, hipStream_t producer, int flags) {
   return 0;
 }
 static int launch_ingest_fields(sactd3_engine* e, const FieldSrc& src, int chunk) {
-  const int64_t cap = e->cfg.rb_capacity;
   IngestFieldsArgs g{};
-  g.ring = (float4*)e->ring; g.rec4 = e->rec4; g.n = chunk; g.cursor = (int)e->rb_cursor; g.cap = (int)cap;
-  e->rb_cursor = (e->rb_cursor + chunk) % cap;
-  e->rb_len = std::min<int64_t>(cap, e->rb_len + chunk);
-  g.len_cursor = &e->ctl->rb_len; g.new_len = (int)e->rb_len; g.new_cursor = (int)e->rb_cursor;
+  const RingSpan sp = ring_append(e, chunk);
+  g.ring = sp.ring; g.rec4 = e->rec4; g.n = chunk; g.cursor = sp.cursor; g.cap = sp.cap;
+  g.len_cursor = &e->ctl->rb_len; g.new_len = sp.new_len; g.new_cursor = sp.new_cursor;
   const long chunks = (long)chunk * e->rec4;
   hipLaunchKernelGGL(k_rb_ingest_fields, dim3(cpt_blocks(chunks, FIELDS_CPT)), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
   HIPCHK(hipGetLastError());
-  return prio_after_append(e, g.cursor, chunk);
+  return prio_after_append(e, sp.first, chunk);
 }
 static int launch_batch_fields(sactd3_engine* e, const FieldSrc& src) {
   const sactd3_engine::BatchSlot& S = e->bs[0];
@@ -2101,7 +2163,7 @@ int sactd3_rb_extend_fields_device(sactd3_engine* e, const sactd3_device_fields*
   CHAIN_BREAK(e);
   RCCHK(fields_check(e, f, "rb_extend_fields_device"));
   const hipStream_t producer = (hipStream_t)producer_stream;
-  const int64_t per_launch = std::min<int64_t>(e->cfg.rb_capacity, ((1ll << 31) - 1) / e->rec4);
+  const int64_t per_launch = std::min<int64_t>(ring_region(e), ((1ll << 31) - 1) / e->rec4);
   if (n > 0) RCCHK(src_order_begin(e, producer, flags));
   for (int done_rows = 0; done_rows < n;) {
     const int chunk = (int)std::min<int64_t>(n - done_rows, per_launch);
@@ -2281,6 +2343,7 @@ static int stage_ring_rows(sactd3_engine* e, const StageReq& q) {
     if (q.w) RCCHK(device_ptr_check(e, q.w, q.name, "w"));
   }
   if (q.draw == DRAW_PRIO && !e->pt_on) return refuse(SACTD3_ESTATE, "priorities are not enabled (sactd3_prio_enable)");
+  if (q.chain && e->rb_pinned > 0) return refuse(SACTD3_ESTATE, "rows are pinned (sactd3_rb_pin): the n-step age formula assumes one wrap point, at slot 0");
   if (e->rb_len <= 0) return refuse(SACTD3_ESTATE, "buffer is empty");
   CHAIN_BREAK(e);
   if (q.weighted || !q.chain) RCCHK(slot_weights_alloc(e));      // (the 1-step kernel always writes the slot's weights)
@@ -2353,6 +2416,55 @@ int sactd3_rb_sample_prioritized_nstep(sactd3_engine* e, float beta, int steps, 
   return stage_ring_rows(e, q);
 }
 
+// ---- prior data under an online run (include/sactd3.h): pinned rows and the mixed draw
+// Slots [0, n) become rows no append overwrites.  Host state only: nothing is launched unless the cursor has to leave the pinned rows
+// (a ring that is exactly full and has not wrapped stands at cursor 0), which republishes the ring state.
+int sactd3_rb_pin(sactd3_engine* e, int64_t n) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  const int64_t cap = e->cfg.rb_capacity;
+  if (n < 0 || n > e->rb_len || n >= cap) return e->fail(SACTD3_EINVAL, "rb_pin: 0 <= n <= rb_len and n < rb_capacity required");
+  if (e->pt_on) return e->fail(SACTD3_ESTATE, "rb_pin: priorities are enabled (a pinned ring has no priority table yet)");
+  // where the cursor of a ring that has never overwritten a row stands: behind its rows, or, exactly full, at the first live slot.
+  // (Elsewhere: sactd3_rb_fill_synthetic below rows an append wrote -- the order of the rows is gone.)
+  const int64_t unwrapped_cursor = e->rb_len < cap ? e->rb_len : e->rb_pinned;
+  if (e->rb_wrapped || e->rb_cursor != unwrapped_cursor)
+    return e->fail(SACTD3_ESTATE, "rb_pin: the ring has wrapped: the oldest rows are no longer the first ones");
+  CHAIN_BREAK(e);
+  e->rb_pinned = n;
+  if (e->rb_len == cap && e->rb_cursor != n) {      // full, never wrapped: the next append overwrites the oldest LIVE row
+    e->rb_cursor = n;
+    RCCHK(publish_rb_state(e));
+  }
+  return 0;
+}
+int64_t sactd3_rb_pinned(const sactd3_engine* e) { return e ? e->rb_pinned : SACTD3_EINVAL; }
+
+// m of the mixed draw: host state; the device's copy is published in front of the next launch that reads it (mix_publish)
+int sactd3_rb_set_mix(sactd3_engine* e, int prior_rows) {
+  if (!e) return SACTD3_EINVAL;
+  if (prior_rows < 0 || prior_rows > e->cfg.batch_size) return e->fail(SACTD3_EINVAL, "rb_set_mix: prior_rows must be in [0, batch_size]");
+  e->mix_m = prior_rows;
+  return 0;
+}
+
+// rb.sample(batch_size) with m rows from the pinned rows and B - m from the live ones: k_mix_draw (which ticks the sample counter),
+// then k_batch_from_index on the drawn slots.  Refusals first; a refused call has changed nothing.
+int sactd3_rb_sample_mixed(sactd3_engine* e) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (const char* why = mix_refusal(e)) { e->err = std::string("rb_sample_mixed: ") + why; return SACTD3_ESTATE; }
+  CHAIN_BREAK(e);
+  RCCHK(slot_weights_alloc(e));      // (the staging kernel always writes the slot's weights: all 1, and the slot does not carry them)
+  RCCHK(mix_alloc(e));
+  RCCHK(mix_draw_launches(e));
+  slot_refilled(e, false, false);
+  mix_count(e);
+  return 0;
+}
+
+int sactd3_mix_stats(sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::mix_stats, out); }
+
 // loss weights for whatever slot 0 holds (a caller-owned device batch, an index-staged one); NULL drops them
 int sactd3_batch_weights_device(sactd3_engine* e, const float* w, int64_t w_ld, int n, void* caller_stream, int flags) {
   if (!e) return SACTD3_EINVAL;
@@ -2401,6 +2513,7 @@ int sactd3_prio_enable(sactd3_engine* e, float alpha, float eps) {
   if (!(alpha >= 0.f) || !std::isfinite(alpha)) return e->fail(SACTD3_EINVAL, "prio_enable: alpha must be finite and >= 0");
   if (!(eps > 0.f) || !std::isfinite(eps)) return e->fail(SACTD3_EINVAL, "prio_enable: eps must be finite and > 0");
   if (e->pt_on) return (alpha == e->pt_alpha && eps == e->pt_eps) ? 0 : e->fail(SACTD3_ESTATE, "prio_enable: already enabled with other values");
+  if (e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "prio_enable: rows are pinned (sactd3_rb_pin): the priority refresh assumes one wrap point, at slot 0");
   const int64_t groups = ((int64_t)e->cfg.rb_capacity + PRIO_G - 1) / PRIO_G, chunks = (groups + PRIO_G - 1) / PRIO_G;
   if (!e->pt_leaf) {      // (a call that failed half way keeps what it had made)
     RCCHK(dalloc(e, &e->pt_leaf, (size_t)groups * PRIO_G)); RCCHK(dalloc(e, &e->pt_sums, (size_t)chunks * PRIO_G));
@@ -2513,6 +2626,7 @@ int sactd3_rb_fill_synthetic(sactd3_engine* e, int64_t n, uint64_t seed) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   if (n < 1 || n > e->cfg.rb_capacity) return e->fail(SACTD3_EINVAL, "rb_fill_synthetic: 1 <= n <= rb_capacity");
+  if (e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "rb_fill_synthetic: rows are pinned (sactd3_rb_pin): the fill writes from slot 0");
   FillArgs f{(float4*)e->ring, e->rec4, e->cx, e->cn, e->o, e->a, (long)n, seed, e->min_ac, e->max_ac};
   const long threads = (long)n * e->rec4;
   hipLaunchKernelGGL(k_rb_fill, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream, f);
@@ -2615,19 +2729,24 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   if (!sm) return e->fail(SACTD3_EINVAL, "step_sampled: the sampling struct is NULL");
-  if (sm->draw != SACTD3_DRAW_UNIFORM && sm->draw != SACTD3_DRAW_PRIORITIZED) return e->fail(SACTD3_EINVAL, "step_sampled: unknown draw");
+  if (sm->draw != SACTD3_DRAW_UNIFORM && sm->draw != SACTD3_DRAW_PRIORITIZED && sm->draw != SACTD3_DRAW_MIXED) return e->fail(SACTD3_EINVAL, "step_sampled: unknown draw");
   if (sm->n_step < 1 || sm->n_step > NS_MAX) return e->fail(SACTD3_EINVAL, "step_sampled: n_step must be in [1, 16]");
   if (sm->n_step > 1 && sm->stride < 1) return e->fail(SACTD3_EINVAL, "step_sampled: stride must be at least 1");
-  const bool prio = sm->draw == SACTD3_DRAW_PRIORITIZED;
+  const bool prio = sm->draw == SACTD3_DRAW_PRIORITIZED, mixed = sm->draw == SACTD3_DRAW_MIXED;
+  if (mixed && sm->n_step != 1) return e->fail(SACTD3_EINVAL, "step_sampled: the mixed draw has no n-step form: n_step must be 1");
   if (!(sm->beta >= 0.f) || !std::isfinite(sm->beta)) return e->fail(SACTD3_EINVAL, "step_sampled: beta must be finite and >= 0");
   if (prio && !e->pt_on) return e->fail(SACTD3_ESTATE, "step_sampled: priorities are not enabled (sactd3_prio_enable)");
+  if (sm->n_step > 1 && e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "step_sampled: rows are pinned (sactd3_rb_pin): the n-step age formula assumes one wrap point, at slot 0");
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step_sampled: buffer is empty");
-  if (!prio && sm->n_step == 1) { RCCHK(sactd3_step(e, do_actor)); ++e->ss_stats[0]; return 0; }
+  if (mixed)
+    if (const char* why = mix_refusal(e)) { e->err = std::string("step_sampled: ") + why; return SACTD3_ESTATE; }
+  if (!prio && !mixed && sm->n_step == 1) { RCCHK(sactd3_step(e, do_actor)); ++e->ss_stats[0]; return 0; }
   CHAIN_BREAK(e);
   const bool chain = sm->n_step > 1;
   const int stride = chain ? sm->stride : 1;
   if (prio || !chain) RCCHK(slot_weights_alloc(e));
   if (chain) RCCHK(nstep_alloc(e));
+  if (mixed) RCCHK(mix_alloc(e));
   const int key[3] = {sm->draw, sm->n_step, stride};
   if (memcmp(key, e->ss_key, sizeof(key)) != 0) {
     bool any = false;
@@ -2649,13 +2768,14 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
       e->ss_beta_bits = (int64_t)(uint32_t)bits; e->ss_inject = inject;
     }
   }
+  if (mixed) RCCHK(mix_publish(e));      // (P and m as the graph's draw reads them: a launch only when one of them changed)
   const int64_t updates = e->qnet_updates + 1;
   const bool polyak = e->cfg.prefer_td3_over_sac || (updates % e->cfg.crit_targ_update_freq == 0);
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
   const int which = (act ? 2 : 0) + (polyak ? 1 : 0);
   if (act) RCCHK(actor_write_begin(e));
   const bool capture = e->cfg.use_graphs && !e->ss_graphs[which];
-  const SampledPlan sp{prio, sm->n_step, stride, act, polyak};
+  const SampledPlan sp{prio, sm->n_step, stride, act, polyak, mixed};
   RCCHK(run_graph_slot(e, &e->ss_graphs[which], &e->ss_nodes[which], [&](EnqCtx& x) { return enqueue_step_sampled(x, sp); }));
   if (capture) ++e->ss_stats[1];
   ++e->ss_stats[0];
@@ -2663,6 +2783,7 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
   slot_refilled(e, prio, chain);
   if (chain) { ++e->ns_host[0]; e->ns_host[1] += e->B; }
   if (prio) ++e->pt_host[0];
+  if (mixed) mix_count(e);
   slot_trained(e, 0, false);
   e->grads_stale[0] = false;
   if (prio) ++e->pt_host[1];
@@ -3343,7 +3464,7 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       sactd3_device_fields f{};
       slab_fields(f);
       if (!strcmp(kernel, "batch_from_fields")) { slot_refilled(e, false, false); return launch_batch_fields(e, field_src(e, &f, 0)); }
-      return launch_ingest_fields(e, field_src(e, &f, 0), (int)std::min<int64_t>(std::min(e->maxn, e->B), e->cfg.rb_capacity));
+      return launch_ingest_fields(e, field_src(e, &f, 0), (int)std::min<int64_t>(std::min(e->maxn, e->B), ring_region(e)));
     }
     // the pack / unpack kernels of sactd3_predict_device on max_envs rows: observations read from the ring's records (the s columns,
     // row stride = the record), actions written to the acting scratch p_z1 (row stride = its 256 columns; the next trunk overwrites it)
@@ -3369,6 +3490,12 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
     }
     // the TD read-out kernel: the TD errors of whatever e->q / e->y hold, written into the engine's own staging slab
     if (!strcmp(kernel, "td_to_field")) return launch_td_out(e, e->stage_dev, 1, e->B);
+    // the draw kernel of sactd3_rb_sample_mixed alone (call form, the current P and m; the sample counter advances, the slot stays)
+    if (!strcmp(kernel, "mix_draw")) {
+      if (const char* why = mix_refusal(e)) { e->err = std::string("time_kernel: ") + why; return SACTD3_ESTATE; }
+      RCCHK(mix_alloc(e));
+      return launch_mix_draw(e, false);
+    }
     // the engine-owned priorities (SACTD3_ESTATE before sactd3_prio_enable): "prio_update" is the write-back kernel on batch_size rows,
     // indices as for "rows_to_fields", every priority 1 (those rows' priorities ARE overwritten)
     const bool prio_sample = !strcmp(kernel, "prio_sample"), prio_update = !strcmp(kernel, "prio_update");
@@ -3396,7 +3523,7 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       if (chain) { q.chain = true; q.steps = 3; q.stride = 1; }
       return stage_ring_rows(e, q);
     }
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update | batch_from_index_nstep)");
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update | batch_from_index_nstep | mix_draw)");
   };
   if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index") || !strcmp(kernel, "prio_update") || !strcmp(kernel, "batch_from_index_nstep")) rc = time_rows_indices(e);
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up

@@ -78,3 +78,5 @@ template __global__ void k_actor_tail_s5<4>(ActorTail5);
 template __global__ void k_q_head<4>(QHead);
 template __global__ void k_ctail_nn_w<2>(CtailNnW);
 template __global__ void k_critic_tail_w<16>(CriticTailW);
+template __global__ void k_mix_draw<false>(MixDrawArgs, MixCtl const*, int);
+template __global__ void k_mix_draw<true>(MixDrawArgs, MixCtl const*, int);

@@ -329,12 +329,22 @@ class Engine:
     def step(self, do_actor: bool) -> None:
         self._ck(self.lib.sactd3_step(self._h, int(bool(do_actor))))
 
-    def step_sampled(self, do_actor: bool, *, beta: Optional[float] = None, n_step: int = 1, stride: int = 1) -> None:
+    def step_sampled(self, do_actor: bool, *, beta: Optional[float] = None, n_step: int = 1, stride: int = 1,
+                     prior_rows: Optional[int] = None) -> None:
         """sactd3_step_sampled: step() with a prioritised draw (`beta`: the exponent of the importance weights; None: the uniform
         draw) and / or `n_step` returns chained at `stride` rows per env step -- sample, weighted critic update, priority write-back,
-        actor updates and target update as one graph launch, replayed while the ring grows and beta anneals."""
-        sm = _lib.CSampling(_lib.DRAW_UNIFORM if beta is None else _lib.DRAW_PRIORITIZED, int(n_step), int(stride),
-                            0.0 if beta is None else float(beta))
+        actor updates and target update as one graph launch, replayed while the ring grows and beta anneals.
+        `prior_rows`: the mixed draw instead -- that many batch rows from the pinned rows (rb_pin), the others from the live rows;
+        rb_set_mix is issued only when the value changed.  It has no prioritised and no n-step form."""
+        if prior_rows is not None:
+            if beta is not None or int(n_step) != 1:
+                raise ValueError("prior_rows (the mixed draw) excludes beta and n_step > 1")
+            if int(prior_rows) != getattr(self, "_mix_rows", None):
+                self.rb_set_mix(int(prior_rows))
+            sm = _lib.CSampling(_lib.DRAW_MIXED, 1, 1, 0.0)
+        else:
+            sm = _lib.CSampling(_lib.DRAW_UNIFORM if beta is None else _lib.DRAW_PRIORITIZED, int(n_step), int(stride),
+                                0.0 if beta is None else float(beta))
         self._ck(self.lib.sactd3_step_sampled(self._h, int(bool(do_actor)), C.byref(sm)))
 
     def step_sampled_stats(self) -> Dict[str, int]:
@@ -551,6 +561,29 @@ class Engine:
     def nstep_stats(self) -> Dict[str, int]:
         """counters of the n-step route (sactd3_nstep_stats; waits for the engine's stream: the last two live on the device)"""
         return self._stats(self.lib.sactd3_nstep_stats, ("stagings", "rows_staged", "rows_cut_short", "rows_refused"))
+
+    # -- prior data under an online run (include/sactd3.h: sactd3_rb_pin, sactd3_rb_set_mix, sactd3_rb_sample_mixed)
+    def rb_pin(self, n: int) -> None:
+        """sactd3_rb_pin: ring slots [0, n) become rows no append overwrites; appends go round-robin over the slots behind them.
+        Allowed before the ring has wrapped; 0 unpins.  Not saved in checkpoints."""
+        self._ck(self.lib.sactd3_rb_pin(self._h, int(n)))
+
+    def rb_pinned(self) -> int:
+        return int(self._ck(self.lib.sactd3_rb_pinned(self._h)))
+
+    def rb_set_mix(self, prior_rows: int) -> None:
+        """sactd3_rb_set_mix: how many rows of a mixed batch come from the pinned rows (0 .. batch_size)."""
+        self._ck(self.lib.sactd3_rb_set_mix(self._h, int(prior_rows)))
+        self._mix_rows = int(prior_rows)
+
+    def rb_sample_mixed(self) -> None:
+        """sactd3_rb_sample_mixed: the batch slot filled with rb_set_mix's share of pinned rows and live rows for the rest -- the
+        index stream of rb_sample(), one counter tick, two launches, no weights."""
+        self._ck(self.lib.sactd3_rb_sample_mixed(self._h))
+
+    def mix_stats(self) -> Dict[str, int]:
+        """host counters of the mixed draw and the pinned ring (sactd3_mix_stats)"""
+        return self._stats(self.lib.sactd3_mix_stats, ("mixed_draws", "prior_rows_drawn", "live_rows_drawn", "pinned_wraps"))
 
     def acting_stats(self) -> Dict[str, int]:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""

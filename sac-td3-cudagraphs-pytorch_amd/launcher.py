@@ -215,10 +215,29 @@ def offline_plan(args):
         raise ValueError("--bc_alpha must be finite and >= 0")
     if bc_alpha > 0.0 and args.algo != "td3":
         raise ValueError("--bc_alpha needs --algo td3: the behaviour-cloning actor term (TD3+BC) exists in the TD3 engine only")
+    # --prior_fraction F beside a dataset: an ONLINE run on top of the pinned dataset (load, pin, loop.train) -- the plan says so with
+    # two more keys; --updates_per_step G: any online run.  Without the two flags the plan is what it always was.
+    prior, utd = getattr(args, "prior_fraction", None), getattr(args, "updates_per_step", None)
+    if utd is not None and int(utd) < 1:
+        raise ValueError("--updates_per_step must be >= 1")
+    if prior is not None and not 0.0 <= float(prior) <= 1.0:                               # (false for NaN)
+        raise ValueError("--prior_fraction must be in [0, 1]")
     if args.offline_dataset is None:
         if args.num_updates is not None:
             raise ValueError("--num_updates needs --offline_dataset (an online run is sized by --num_timesteps)")
+        if prior is not None:
+            raise ValueError("--prior_fraction needs --offline_dataset: the prior data the batches take their share from")
         return None
+    if prior is not None:
+        excluded = (["prioritized"] if args.prioritized else []) + (["n_step"] if args.n_step != 1 else []) + \
+                   (["num_updates"] if args.num_updates is not None else [])
+        if excluded:
+            raise ValueError("--prior_fraction excludes " + ", ".join("--" + k for k in excluded) +
+                             ": a pinned ring has no priorities and no n-step chains yet, and the run is sized by --num_timesteps")
+        return dict(dataset=args.offline_dataset, num_updates=None, bc_alpha=bc_alpha, plain=bc_alpha == 0.0,
+                    prior_fraction=float(prior), updates_per_step=1 if utd is None else int(utd))
+    if utd is not None:
+        raise ValueError("--updates_per_step needs an env loop: with --offline_dataset add --prior_fraction (the number of updates is --num_updates)")
     online_only = [k for k in ("overlap_acting", "device_env", "prioritized", "one_launch") if getattr(args, k)] + (["n_step"] if args.n_step != 1 else [])
     if online_only:
         raise ValueError("--offline_dataset excludes " + ", ".join("--" + k for k in online_only) + ": there is no env loop to shape")
@@ -229,11 +248,14 @@ def offline_plan(args):
 
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
-            offline_dataset=None, num_updates=None, **over):
+            offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
-    `bc_alpha` in `over` turns the TD3+BC actor term on."""
+    `bc_alpha` in `over` turns the TD3+BC actor term on.
+    `prior_fraction` beside `offline_dataset`: an online run on top of the dataset instead -- the ring is filled and its rows pinned
+    (loop.load_dataset(pin=True)), then loop.train draws that share of every batch from them; `updates_per_step`: updates per
+    segment of any online run."""
     import json
     import time
     from pathlib import Path
@@ -267,12 +289,17 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
         if data["observations"].shape[1:] != (o,) or data["actions"].shape[1:] != (a,):
             raise ValueError(f"{offline_dataset}: observations / actions are {data['observations'].shape[1:]} / {data['actions'].shape[1:]}, "
                              f"{env_id} has ({o},) / ({a},)")
-        loop.load_dataset(agent, data)
+        loop.load_dataset(agent, data, **(dict(pin=True) if prior_fraction is not None else {}))
+    utd = dict(updates_per_step=int(updates_per_step)) if int(updates_per_step) != 1 else {}      # (a keyword only when it is used)
+    if offline_dataset is not None and prior_fraction is not None:
+        metrics = loop.train(cfg, env, agent, fused=False, evaluator=ev, overlap=overlap_acting, device_env=device_env,
+                             one_launch=one_launch, prior_fraction=float(prior_fraction), **utd)
+    elif offline_dataset is not None:
         metrics = loop.train_offline(cfg, agent, num_updates=int(num_updates if num_updates is not None else cfg.num_timesteps),
                                      evaluator=ev, eval_every_updates=int(cfg.eval_every))
     else:
         metrics = loop.train(cfg, env, agent, fused=not prioritized and n_step == 1, evaluator=ev, overlap=overlap_acting, device_env=device_env,
-                             prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch)
+                             prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch, **utd)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -303,7 +330,8 @@ def _worker_main(args) -> int:
                           eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity,
                           overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized,
                           n_step=args.n_step, one_launch=args.one_launch, offline_dataset=plan.get("dataset"),
-                          num_updates=plan.get("num_updates"), bc_alpha=args.bc_alpha)
+                          num_updates=plan.get("num_updates"), bc_alpha=args.bc_alpha, prior_fraction=plan.get("prior_fraction"),
+                          updates_per_step=args.updates_per_step or 1)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -345,6 +373,11 @@ def main(argv=None) -> int:
     ap.add_argument("--bc_alpha", type=float, default=None,
                     help="TD3+BC: the behaviour-cloning actor term with this alpha (2.5 in Fujimoto & Gu 2021); needs --algo td3")
     ap.add_argument("--num_updates", type=int, default=None, help="with --offline_dataset: iterations to run (default: --num_timesteps)")
+    ap.add_argument("--prior_fraction", type=float, default=None, metavar="F",
+                    help="with --offline_dataset: an ONLINE run on top of the dataset -- its rows are pinned in the ring and every batch takes "
+                         "round(F * batch_size) rows from them, the others from the rows the run appends (loop.train prior_fraction=...)")
+    ap.add_argument("--updates_per_step", type=int, default=None, metavar="G",
+                    help="any online run: G updates after each segment instead of one (loop.train updates_per_step=...)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)

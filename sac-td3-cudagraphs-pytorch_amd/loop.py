@@ -197,7 +197,8 @@ class ProportionalSampler:
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
           evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
           sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
-          n_step: int = 1, one_launch: bool = False) -> Dict[str, float]:
+          n_step: int = 1, one_launch: bool = False, prior_fraction: Optional[float] = None,
+          updates_per_step: int = 1) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -217,13 +218,34 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     rows of one env (`stride=cfg.num_envs`), cut at episode ends -- in the uniform, `sampler` and `prioritized` branches alike.
     `one_launch=True` (needs `fused=False` and `prioritized` and / or `n_step` > 1, excludes `sampler`): the `prioritized` / `n_step`
     iteration is issued as one graph launch -- `agent.iteration(i, beta=, n_step=, stride=cfg.num_envs)` -- in place of the call
-    sequence, with the same results bit for bit and the same counters."""
+    sequence, with the same results bit for bit and the same counters.
+    `prior_fraction` (in [0, 1]; needs `fused=False`, excludes `sampler`, `prioritized` and `n_step` > 1): learning online from prior
+    data -- every batch takes round(prior_fraction * batch_size) rows from the rows `agent.rb.pin()` protects (`load_dataset(...,
+    pin=True)`) and the others from the rows the run appends (`rb.sample_mixed`); it counts as a reason for `one_launch=True`.
+    `updates_per_step` (>= 1, every branch): the update-to-data ratio -- after each segment the update block runs that many times,
+    `i` and the update counters advancing per update; 1 is the reference's loop."""
+    updates_per_step = int(updates_per_step)
+    if updates_per_step < 1:
+        raise ValueError(f"updates_per_step must be >= 1, got {updates_per_step}")
+    prior_rows = None
+    if prior_fraction is not None:
+        if not 0.0 <= float(prior_fraction) <= 1.0:
+            raise ValueError(f"prior_fraction must be in [0, 1], got {prior_fraction}")
+        if fused:
+            raise ValueError("prior_fraction=... needs fused=False: the fused iteration samples uniformly inside its graph")
+        if sampler is not None:
+            raise ValueError("prior_fraction=... and sampler=... exclude each other: the mixed draw is the engine's own")
+        if prioritized is not None:
+            raise ValueError("prior_fraction=... and prioritized=... exclude each other: a pinned ring has no priority table yet")
+        if int(n_step) > 1:
+            raise ValueError("prior_fraction=... excludes n_step > 1: a pinned ring has no n-step chains yet")
+        prior_rows = int(round(float(prior_fraction) * int(cfg.batch_size)))
     if one_launch:
         if fused:
             raise ValueError("one_launch=True needs fused=False: fused=True is the uniform 1-step iteration, already one launch")
         if sampler is not None:
             raise ValueError("one_launch=True excludes sampler=...: a sampler outside the engine cannot be part of its graph")
-        if prioritized is None and int(n_step) <= 1:
+        if prioritized is None and int(n_step) <= 1 and prior_rows is None:
             raise ValueError("one_launch=True needs prioritized=... and / or n_step > 1: the uniform 1-step iteration is fused=True")
     n_step = int(n_step)
     if not 1 <= n_step <= 16:
@@ -261,30 +283,36 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
         if agent.timesteps_so_far <= cfg.learning_starts:
             i += 1
             continue
-        if fused:
-            agent.iteration(i)
-        elif one_launch:
-            agent.iteration(i, beta=prio_beta if prioritized is not None else None, n_step=n_step,
-                            stride=int(cfg.num_envs) if n_step > 1 else None)
-        else:
-            if prioritized is not None:
-                batch = agent.rb.sample_prioritized(cfg.batch_size, prio_beta, **chain)
-            elif sampler is None:
-                batch = agent.rb.sample(cfg.batch_size, **chain)
+        for _update in range(updates_per_step):                          # (1: the reference's one update per segment)
+            if fused:
+                agent.iteration(i)
+            elif one_launch and prior_rows is not None:                   # (a keyword the older signature lacks: only when used)
+                agent.iteration(i, prior_rows=prior_rows)
+            elif one_launch:
+                agent.iteration(i, beta=prio_beta if prioritized is not None else None, n_step=n_step,
+                                stride=int(cfg.num_envs) if n_step > 1 else None)
             else:
-                index, weights = sampler.sample(cfg.batch_size)
-                batch = agent.rb.sample_at(index, weights, **chain)
-            tlog.update(agent.update_qnets(batch))
-            if sampler is not None:
-                sampler.update(index, agent.td_errors())
-            if prioritized is not None:
-                agent.rb.update_priorities()
-            agent.qnet_updates_so_far += 1
-            if i % (cfg.actor_update_delay + 1) == 0:
-                for _ in range(cfg.actor_update_delay):
-                    tlog.update(agent.update_actor(batch))
-                    agent.actor_updates_so_far += 1
-            agent.update_targ_nets()
+                if prior_rows is not None:
+                    batch = agent.rb.sample_mixed(cfg.batch_size, prior_rows)
+                elif prioritized is not None:
+                    batch = agent.rb.sample_prioritized(cfg.batch_size, prio_beta, **chain)
+                elif sampler is None:
+                    batch = agent.rb.sample(cfg.batch_size, **chain)
+                else:
+                    index, weights = sampler.sample(cfg.batch_size)
+                    batch = agent.rb.sample_at(index, weights, **chain)
+                tlog.update(agent.update_qnets(batch))
+                if sampler is not None:
+                    sampler.update(index, agent.td_errors())
+                if prioritized is not None:
+                    agent.rb.update_priorities()
+                agent.qnet_updates_so_far += 1
+                if i % (cfg.actor_update_delay + 1) == 0:
+                    for _ in range(cfg.actor_update_delay):
+                        tlog.update(agent.update_actor(batch))
+                        agent.actor_updates_so_far += 1
+                agent.update_targ_nets()
+            i += 1
         if agent.timesteps_so_far % cfg.eval_every == 0:
             if ro is not None:
                 ro.resolve()                                              # the evaluator / on_eval act (or load) with the same agent
@@ -292,7 +320,6 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
                 evaluator(agent)
             if on_eval is not None:
                 on_eval(agent, agent.timesteps_so_far)
-        i += 1
     if ro is not None:
         ro.resolve()                                                      # leave no acting call in flight behind the loop
     return agent.engine.read_metrics()
@@ -301,13 +328,15 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
 _DATASET_KEYS = ("observations", "actions", "rewards", "next_observations", "terminations")
 
 
-def load_dataset(agent, data, chunk: int = 65536) -> int:
+def load_dataset(agent, data, chunk: int = 65536, pin: bool = False) -> int:
     """Append a whole offline dataset to the agent's replay ring, `chunk` rows per `rb.extend` call, in order.  `data`: a mapping with
     the keys of `rb.extend` -- observations [n, o], actions [n, a], rewards [n] or [n, 1], next_observations [n, o], terminations [n]
     or [n, 1], optionally dones (default: terminations) -- whose values are numpy arrays or CUDA tensors (device tensors are appended
     where they are, without a host round trip).  Raises ValueError if the rows do not fit into what is left of the ring's capacity:
     the ring would wrap and silently drop the oldest rows.  Normalising the states (as the TD3+BC paper does) is the caller's
-    business, before this call: the engine trains on the rows it is given.  Returns the number of rows appended."""
+    business, before this call: the engine trains on the rows it is given.  `pin=True`: the rows the ring then holds are pinned
+    (`agent.rb.pin()`) -- an online run on top appends behind them and never evicts them (train(prior_fraction=...)).  Returns the
+    number of rows appended."""
     missing = [k for k in _DATASET_KEYS if k not in data]
     if missing:
         raise ValueError(f"load_dataset: missing key(s) {missing}")
@@ -326,6 +355,8 @@ def load_dataset(agent, data, chunk: int = 65536) -> int:
                          "it would wrap and drop data; build the agent with a larger rb_capacity")
     for lo in range(0, n, chunk):
         agent.rb.extend({k: v[lo:lo + chunk] for k, v in cols.items()})
+    if pin:
+        agent.rb.pin()
     return n
 
 
