@@ -454,7 +454,7 @@ int sactd3_step_prefix(sactd3_engine* e, int m);
  * state included.  Where the period graph has its pipelined form, runs of R consecutive periods go out as ONE graph launch (R: an even
  * build constant, 2 as shipped, at most 8; the node sequence of a run is that of R period graphs one behind the other, no kernel and no launch
  * argument differs), so the idle time between two graph replays is paid once per R periods; what is left of k below R goes out as
- * single period graphs.  Elsewhere the call loops over sactd3_step_period; with use_graphs == 0 the same launches are issued eagerly.
+ * single period graphs.  Elsewhere the k periods go out as k plain period graphs; with use_graphs == 0 the same launches are issued eagerly.
  * It writes the actor parameters (see sactd3_predict_begin), and it acts with the updated ones: a sactd3_predict or a
  * sactd3_predict_begin behind it waits for every launch the call issued, a whole run of R periods at the least -- R times the acting
  * latency behind one sactd3_step_period.  A loop that acts every iteration issues its iterations with sactd3_step, as before.

@@ -83,7 +83,8 @@ static void unpack_net(const NetLayout& L, int ln, const float* src, float* dst)
 static const int BIG_BATCH = 1024;   // from here on the hidden layers run as 64 x 64-tiled GEMMs + a LayerNorm row kernel
 enum { G_Q = 0, G_A = 1, G_STEP00 = 2, G_STEP01 = 3, G_STEP10 = 4, G_STEP11 = 5, G_PERIOD = 6, G_PERIOD_B = 7, G_OPENING = 8,
        G_PREFIX = 9 /* + 2 (m - 1) + variant, m = 1, 2: the first m iterations of a period (sactd3_step_prefix) */,
-       G_QW = 13 /* update_qnets in its weighted form: captured at its first use only */, G_COUNT = 14 };
+       G_QW = 13 /* update_qnets in its weighted form: captured at its first use only */,
+       G_RUN = 14 /* + start variant (sactd3_step_periods) */, G_SAMPLED = 16 /* + 2 do_actor + target update (sactd3_step_sampled) */, G_COUNT = 20 };
 static const int NSTAGE = 32;
 
 struct NodeInfo { std::string name; double flops; double bytes; long threads; };
@@ -153,7 +154,7 @@ struct sactd3_engine {
   float* h_batch = nullptr;                      // pinned [B][rec_f]
 
   int64_t rb_len = 0, rb_cursor = 0, qnet_updates = 0;
-  hipGraphExec_t graphs[G_COUNT] = {}; int graph_nodes[G_COUNT] = {};
+  hipGraphExec_t graphs[G_COUNT] = {}; int graph_nodes[G_COUNT] = {};      // every learner graph, by its G_* id (enqueue_graph says what each holds)
   std::vector<hipGraphExec_t> predict_graphs;   // [explore][n]: the two launches of sactd3_predict, captured per row count
   // Acting on a stream of its own (sactd3_predict_begin / _end), created at the first begin.  Order between the two streams is kept
   // by the host, with events, only where the acting kernels and a learner call touch the same memory -- the actor parameters:
@@ -206,18 +207,16 @@ struct sactd3_engine {
   // more than before.  ns_host: {n-step stagings, rows staged}.
   int *ns_k = nullptr, *ns_last = nullptr, *ns_ctr = nullptr;
   int64_t ns_host[2] = {};
-  // The replay-aware iteration as one graph launch (sactd3_step_sampled): one executable graph per (do_actor, target update) for the
-  // current (draw, n_step, stride) -- a change of those three drops all four.  Their staging and priority launches are the graph forms
-  // (prio_kernels.h), which read the ring length, the cursor, beta and the injection switch from device memory: ss_beta_bits / ss_inject
-  // are what the host last published into PrioCtl (-1: nothing yet).  ss_stats: {launches, graph captures}.
-  hipGraphExec_t ss_graphs[4] = {}; int ss_nodes[4] = {};
+  // The replay-aware iteration as one graph launch (sactd3_step_sampled): one executable graph per (do_actor, target update), G_SAMPLED + k,
+  // for the current ss_key = (draw, n_step, stride) -- a change of those three drops all four.  Their staging and priority launches are the
+  // graph forms (prio_kernels.h), which read the ring length, the cursor, beta and the injection switch from device memory: ss_beta_bits /
+  // ss_inject are what the host last published into PrioCtl (-1: nothing yet).  ss_stats: {launches, graph captures, 0, 0}.
   int ss_key[3] = {0, 0, 0};
   int64_t ss_beta_bits = -1; int ss_inject = -1;
-  int64_t ss_stats[2] = {};
+  int64_t ss_stats[4] = {};
   // Runs of whole periods as one graph launch (sactd3_step_periods): RUN_PERIODS consecutive pipelined periods, one executable graph
-  // per start variant (the run that starts on variant v leaves chain_ready == v behind: RUN_PERIODS is even).
+  // per start variant, G_RUN + v (the run that starts on variant v leaves chain_ready == v behind: RUN_PERIODS is even).
   // run_stats: {calls, run launches, single-period launches made inside those calls, run graphs captured}.
-  hipGraphExec_t run_graphs[2] = {}; int run_nodes[2] = {};
   int64_t run_stats[4] = {};
   // TD3+BC (sactd3_config::bc_alpha > 0 at create; kernels.h: BcArgs).  bc_on picks the BC forms of the head-backward launch and of the
   // actor's weight-gradient launch, for good; bc_alpha / bc_weight mirror DevCtl::bc, which is what the kernels read (sactd3_set_bc
@@ -1397,9 +1396,25 @@ static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&
   if (launch) HIPCHK(hipGraphLaunch(*slot, st));
   return 0;
 }
-template <class F>
-static int run_graph(sactd3_engine* e, int which, F&& enqueue, bool launch = true) {
-  return run_graph_slot(e, &e->graphs[which], &e->graph_nodes[which], enqueue, launch);
+// The learner graphs live in one table, sactd3_engine::graphs, keyed by the G_* ids; enqueue_graph (below the sequences it names) is
+// the one place that says which sequence an id holds, so an id cannot be captured with one sequence here and another there.
+static int enqueue_graph(EnqCtx& x, int which);
+static int run_graph(sactd3_engine* e, int which, bool launch = true) {
+  const bool had = e->graphs[which] != nullptr;
+  RCCHK(run_graph_slot(e, &e->graphs[which], &e->graph_nodes[which], [which](EnqCtx& x) { return enqueue_graph(x, which); }, launch));
+  // whoever needs a graph first captures it (its entry point, sactd3_instantiate_graphs): the two capture counters are kept here
+  if (!had && e->graphs[which] && which >= G_RUN) ++(which >= G_SAMPLED ? e->ss_stats[1] : e->run_stats[3]);
+  return 0;
+}
+// drop the graphs [first, first + count) of the table (an executable graph is not destroyed under its own replay: the stream drains first)
+static int drop_graphs(sactd3_engine* e, int first, int count) {
+  hipGraphExec_t* g = &e->graphs[first];
+  if (std::count(g, g + count, nullptr) < count) HIPCHK(hipStreamSynchronize(e->stream));
+  for (int i = 0; i < count; ++i) {
+    if (g[i]) hipGraphExecDestroy(g[i]);
+    g[i] = nullptr; e->graph_nodes[first + i] = 0;
+  }
+  return 0;
 }
 
 // A learner-stream call that writes the actor parameters (what the acting kernels read through that stream) is about to be issued:
@@ -1609,26 +1624,27 @@ static int mix_draw_launches(sactd3_engine* e, bool graph_form = false) {
 }
 static inline void mix_count(sactd3_engine* e) { ++e->mix_stats[0]; e->mix_stats[1] += e->mix_m; e->mix_stats[2] += e->B - e->mix_m; }
 
-struct SampledPlan { bool prio; int steps, stride; bool actor, targets; bool mixed = false; };
-static int enqueue_step_sampled(EnqCtx& x, const SampledPlan& sp) {
+static int enqueue_step_sampled(EnqCtx& x, bool actor, bool targets) {
   sactd3_engine* e = x.e;
-  if (sp.prio) RCCHK(prio_draw_launches(e, 0.f, true));
-  const long long* idx = sp.prio ? e->pt_idx : nullptr;
-  const float* w = sp.prio ? e->pt_w : nullptr;
-  if (sp.mixed) RCCHK(mix_draw_launches(e, true));      // (unweighted, no chain; the draw kernel has advanced the sample counter)
-  else if (sp.steps > 1) RCCHK(launch_batch_nstep(e, idx, 1, w, 1, sp.prio ? e->bs[0].w : nullptr, sp.steps, sp.stride, true));
+  const bool prio = e->ss_key[0] == SACTD3_DRAW_PRIORITIZED, mixed = e->ss_key[0] == SACTD3_DRAW_MIXED;
+  const int steps = e->ss_key[1], stride = e->ss_key[2];
+  if (prio) RCCHK(prio_draw_launches(e, 0.f, true));
+  const long long* idx = prio ? e->pt_idx : nullptr;
+  const float* w = prio ? e->pt_w : nullptr;
+  if (mixed) RCCHK(mix_draw_launches(e, true));      // (unweighted, no chain; the draw kernel has advanced the sample counter)
+  else if (steps > 1) RCCHK(launch_batch_nstep(e, idx, 1, w, 1, prio ? e->bs[0].w : nullptr, steps, stride, true));
   else RCCHK(launch_batch_index(e, idx, 1, w, 1, true));
-  if (!sp.prio && !sp.mixed) {      // the uniform draw was made at the sample counter, which now advances
+  if (!prio && !mixed) {      // the uniform draw was made at the sample counter, which now advances
     hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, x.s, &e->ctl->sample_ctr, (int*)nullptr);
     HIPCHK(hipGetLastError());
   }
   IterPlace it;
-  it.weighted = sp.prio;
+  it.weighted = prio;
   RCCHK(enqueue_update_qnets(x, it, false));
-  if (sp.prio) RCCHK(launch_prio_update(e, prio_td_args(e, 0), true));
-  if (sp.actor)
+  if (prio) RCCHK(launch_prio_update(e, prio_td_args(e, 0), true));
+  if (actor)
     for (int j = 0; j < e->cfg.actor_update_delay; ++j) RCCHK(enqueue_update_actor(x, IterPlace{}, 0, false));
-  if (sp.targets) RCCHK(enqueue_polyak(x, POLYAK_CRITICS | (e->cfg.prefer_td3_over_sac ? POLYAK_ACTOR : 0)));
+  if (targets) RCCHK(enqueue_polyak(x, POLYAK_CRITICS | (e->cfg.prefer_td3_over_sac ? POLYAK_ACTOR : 0)));
   return 0;
 }
 
@@ -1673,9 +1689,7 @@ void sactd3_destroy(sactd3_engine* e) {
   if (e->stream) (void)hipSetDevice(e->cfg.device_id);   // (a failed create may carry a device_id that was never valid)
   if (e->stream) hipStreamSynchronize(e->stream);
   if (e->act_stream) hipStreamSynchronize(e->act_stream);
-  for (auto& g : e->graphs) if (g) hipGraphExecDestroy(g);
-  for (auto& g : e->ss_graphs) if (g) hipGraphExecDestroy(g);
-  for (auto& g : e->run_graphs) if (g) hipGraphExecDestroy(g);
+  (void)drop_graphs(e, 0, G_COUNT);
   for (auto& g : e->predict_graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_dev_graphs) if (g) hipGraphExecDestroy(g);
   for (auto ev : e->events) hipEventDestroy(ev);
@@ -2678,11 +2692,7 @@ int sactd3_update_qnets(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
-  if (e->slot.weighted) {      // the weighted form: the same sequence with the weighted critic tail, a graph of its own
-    IterPlace it;
-    it.weighted = true;
-    RCCHK(run_graph(e, G_QW, [&](EnqCtx& x) { return enqueue_update_qnets(x, it, false); }));
-  } else RCCHK(run_graph(e, G_Q, [&](EnqCtx& x) { return enqueue_update_qnets(x, IterPlace{}, false); }));
+  RCCHK(run_graph(e, e->slot.weighted ? G_QW : G_Q));      // the weighted form: the same sequence with the weighted critic tail, a graph of its own
   e->grads_stale[0] = false;
   slot_trained(e, 0, false);
   return 0;
@@ -2692,7 +2702,7 @@ int sactd3_update_actor(sactd3_engine* e) {
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   RCCHK(actor_write_begin(e));
-  RCCHK(run_graph(e, G_A, [&](EnqCtx& x) { return enqueue_update_actor(x, IterPlace{}, 0, false); }));
+  RCCHK(run_graph(e, G_A));
   e->grads_stale[1] = false;
   return 0;
 }
@@ -2705,21 +2715,31 @@ int sactd3_update_targ_nets(sactd3_engine* e, int64_t qnet_updates_so_far) {
   if (td3 || qnet_updates_so_far % e->cfg.crit_targ_update_freq == 0) return enqueue_polyak(x, POLYAK_CRITICS | (td3 ? POLYAK_ACTOR : 0));
   return 0;
 }
+// The schedule of the iteration that brings the critics to their `updates`-th update (orchestrator.py:337-352): does it run the actor
+// updates, does it update the targets, and k = 2 act + polyak, its place among the four graphs of G_STEP00 + k / G_SAMPLED + k.
+struct IterSchedule { bool act, polyak; int k; };
+static IterSchedule iteration_schedule(const sactd3_engine* e, int do_actor, int64_t updates) {
+  const bool polyak = e->cfg.prefer_td3_over_sac || (updates % e->cfg.crit_targ_update_freq == 0);
+  const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
+  return {act, polyak, (act ? 2 : 0) + (polyak ? 1 : 0)};
+}
+// the next iteration as graph `first` + k (G_STEP00, G_SAMPLED), and what it does to the counter and to grads_stale
+static int issue_iteration(sactd3_engine* e, int do_actor, int first) {
+  const IterSchedule s = iteration_schedule(e, do_actor, e->qnet_updates + 1);
+  if (s.act) RCCHK(actor_write_begin(e));      // (a critic-only iteration touches nothing the acting kernels read: no order with them)
+  RCCHK(run_graph(e, first + s.k));
+  ++e->qnet_updates;      // (the engine's own counter advances only once the iteration has been launched)
+  e->grads_stale[0] = false;
+  if (s.act) e->grads_stale[1] = false;
+  return 0;
+}
 int sactd3_step(sactd3_engine* e, int do_actor) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step: buffer is empty");
-  const int64_t updates = e->qnet_updates + 1;     // (the engine's own counter advances only once the iteration has been launched)
-  const bool polyak = e->cfg.prefer_td3_over_sac || (updates % e->cfg.crit_targ_update_freq == 0);
-  const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
-  const int which = G_STEP00 + (act ? 2 : 0) + (polyak ? 1 : 0);
-  if (act) RCCHK(actor_write_begin(e));      // (a critic-only iteration touches nothing the acting kernels read: no order with them)
-  RCCHK(run_graph(e, which, [&](EnqCtx& x) { return enqueue_step(x, single_iteration(act, polyak)); }));
-  e->qnet_updates = updates;
+  RCCHK(issue_iteration(e, do_actor, G_STEP00));
   slot_trained(e, 0, true);
-  e->grads_stale[0] = false;
-  if (act) e->grads_stale[1] = false;
   return 0;
 }
 
@@ -2749,13 +2769,7 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
   if (mixed) RCCHK(mix_alloc(e));
   const int key[3] = {sm->draw, sm->n_step, stride};
   if (memcmp(key, e->ss_key, sizeof(key)) != 0) {
-    bool any = false;
-    for (auto& g : e->ss_graphs) any = any || g;
-    if (any) HIPCHK(hipStreamSynchronize(e->stream));      // (an executable graph is not destroyed under its own replay)
-    for (int i = 0; i < 4; ++i) {
-      if (e->ss_graphs[i]) hipGraphExecDestroy(e->ss_graphs[i]);
-      e->ss_graphs[i] = nullptr; e->ss_nodes[i] = 0;
-    }
+    RCCHK(drop_graphs(e, G_SAMPLED, 4));
     memcpy(e->ss_key, key, sizeof(key));
   }
   if (prio) {
@@ -2769,33 +2783,18 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
     }
   }
   if (mixed) RCCHK(mix_publish(e));      // (P and m as the graph's draw reads them: a launch only when one of them changed)
-  const int64_t updates = e->qnet_updates + 1;
-  const bool polyak = e->cfg.prefer_td3_over_sac || (updates % e->cfg.crit_targ_update_freq == 0);
-  const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
-  const int which = (act ? 2 : 0) + (polyak ? 1 : 0);
-  if (act) RCCHK(actor_write_begin(e));
-  const bool capture = e->cfg.use_graphs && !e->ss_graphs[which];
-  const SampledPlan sp{prio, sm->n_step, stride, act, polyak, mixed};
-  RCCHK(run_graph_slot(e, &e->ss_graphs[which], &e->ss_nodes[which], [&](EnqCtx& x) { return enqueue_step_sampled(x, sp); }));
-  if (capture) ++e->ss_stats[1];
+  RCCHK(issue_iteration(e, do_actor, G_SAMPLED));
   ++e->ss_stats[0];
-  // the host state, transition by transition as the call sequence makes them
+  // the rest of the host state, transition by transition as the call sequence makes them
   slot_refilled(e, prio, chain);
   if (chain) { ++e->ns_host[0]; e->ns_host[1] += e->B; }
   if (prio) ++e->pt_host[0];
   if (mixed) mix_count(e);
   slot_trained(e, 0, false);
-  e->grads_stale[0] = false;
   if (prio) ++e->pt_host[1];
-  if (act) e->grads_stale[1] = false;
-  e->qnet_updates = updates;
   return 0;
 }
-int sactd3_step_sampled_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  out[0] = e->ss_stats[0]; out[1] = e->ss_stats[1]; out[2] = 0; out[3] = 0;
-  return 0;
-}
+int sactd3_step_sampled_stats(sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::ss_stats, out); }
 
 // Is the period graph built in its pipelined form (see BatchSlot)?  One or two critic-only iterations behind the one with the actor
 // updates, and an opening trunk that reads ring rows itself (narrow observations below the large-batch threshold, wide ones at large batch).
@@ -2824,7 +2823,7 @@ static void mark_grads_stale(sactd3_engine* e) {
 // (and, the whole period, the next period's opening pair into the other slot); then those iterations on slots 1 .. m - 1.
 // variant (pipelined form only): which batch slot the period's first iteration trains on (0: slot 0, 1: slot 3) -- the other one
 // receives the opening pair of the NEXT period, so consecutive periods alternate (chain_ready).  The pipelined form assumes its own
-// opening pair is already in place: sactd3_step_period runs the opening graph first when it is not.
+// opening pair is already in place: take_opening runs the opening graph first when it is not.
 static int enqueue_period(EnqCtx& x, int variant, int m) {
   sactd3_engine* e = x.e;
   const bool pipelined = period_is_pipelined(e), whole = m == e->cfg.actor_update_delay + 1;
@@ -2846,68 +2845,6 @@ static int enqueue_opening(EnqCtx& x) {
   return enqueue_opening_pair(x, it, true);
 }
 
-// One period of the actor schedule (orchestrator.py:345-349: iteration i with i % (delay + 1) == 0 runs the actor updates,
-// the next `delay` iterations are critic-only) as ONE graph launch: delay + 1 iterations back to back, no host call and no
-// inter-replay gap in between.  Only when every iteration takes the same target-update branch (TD3, or crit_targ_update_freq
-// == 1); otherwise the caller gets SACTD3_ESTATE and issues the iterations one by one.
-int sactd3_step_period(sactd3_engine* e) {
-  if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step_period: buffer is empty");
-  const bool td3 = e->cfg.prefer_td3_over_sac;
-  if (!td3 && e->cfg.crit_targ_update_freq != 1) return e->fail(SACTD3_ESTATE, "step_period: needs crit_targ_update_freq == 1");
-  const int n = e->cfg.actor_update_delay + 1;
-  RCCHK(actor_write_begin(e));
-  mark_grads_stale(e);
-  const bool pipelined = period_is_pipelined(e);
-  int v = 0;
-  if (!pipelined) {
-    e->chain_ready = -1;
-    RCCHK(run_graph(e, G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, 0, n); }));
-  } else {
-    // chained periods: this period's opening pair is either left over from the previous one (chain_ready names the variant) or is
-    // produced now by the 2- / 3-node opening graph; the period graph then leaves the NEXT period's behind
-    v = e->chain_ready >= 0 ? e->chain_ready : 0;
-    const bool have = e->chain_ready >= 0;
-    e->chain_ready = -1;
-    if (!have) RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }));
-    RCCHK(run_graph(e, v ? G_PERIOD_B : G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, v, n); }));
-    e->chain_ready = 1 - v;
-  }
-  e->qnet_updates += n;
-  // (the period's iterations run one behind the other, each writing e->q / e->y in its critic tail; what runs ahead inside the first one
-  //  -- the later iterations' and the next period's opening passes -- goes through the actor only: the current slot, e->q and e->y all
-  //  belong to the period's last iteration)
-  slot_trained(e, period_slot(pipelined, v, n - 1), true);
-  return 0;
-}
-
-// The first m iterations of a period (1 <= m <= actor_update_delay) as ONE graph launch: what is left of a run of iterations behind
-// its last whole period (orchestrator.py:337-352 for a number of iterations that is not a multiple of the period).  Equal to
-// sactd3_step(1) followed by m - 1 sactd3_step(0), bit for bit; in the pipelined form it uses the opening pair the previous period
-// left behind (or runs the opening graph) exactly as sactd3_step_period does.  Same preconditions as sactd3_step_period.
-int sactd3_step_prefix(sactd3_engine* e, int m) {
-  if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  if (m < 1 || m > e->cfg.actor_update_delay) return e->fail(SACTD3_EINVAL, "step_prefix: 1 <= m <= actor_update_delay");
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step_prefix: buffer is empty");
-  if (!e->cfg.prefer_td3_over_sac && e->cfg.crit_targ_update_freq != 1) return e->fail(SACTD3_ESTATE, "step_prefix: needs crit_targ_update_freq == 1");
-  if (!period_is_pipelined(e) || m > 2) {      // no cut-short form: the iterations one by one
-    for (int i = 0; i < m; ++i) RCCHK(sactd3_step(e, i == 0));
-    return 0;
-  }
-  const int v = e->chain_ready >= 0 ? e->chain_ready : 0;
-  const bool have = e->chain_ready >= 0;
-  e->chain_ready = -1;
-  RCCHK(actor_write_begin(e));
-  mark_grads_stale(e);
-  if (!have) RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }));
-  RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](EnqCtx& x) { return enqueue_period(x, v, m); }));
-  e->qnet_updates += m;
-  slot_trained(e, period_slot(true, v, m - 1), true);      // (as sactd3_step_period; m == 1 on variant 1: slot 3)
-  return 0;
-}
-
 // Runs of whole periods.  The device idles for a few microseconds between the last node of one graph replay and the first of the next
 // (DESIGN.md 8), so a loop of period graphs pays that once per period; a graph that holds RUN_PERIODS consecutive pipelined periods
 // pays it once per run.  RUN_PERIODS is even, so a run ends on the variant it started on, and at most 8 (make RUN=<R>).
@@ -2925,77 +2862,138 @@ static int enqueue_period_run(EnqCtx& x, int v) {
   }
   return 0;
 }
-static int run_period_graph(sactd3_engine* e, int v, bool launch) {
-  const bool had = e->run_graphs[v] != nullptr;
-  RCCHK(run_graph_slot(e, &e->run_graphs[v], &e->run_nodes[v], [&](EnqCtx& x) { return enqueue_period_run(x, v); }, launch));
-  if (!had && e->run_graphs[v]) ++e->run_stats[3];
+// What each learner graph holds (see run_graph): one definition for whoever captures it -- its entry point at the first use,
+// sactd3_instantiate_graphs ahead of that -- and whoever walks its sequence without a graph (use_graphs == 0, sactd3_time_nodes).
+static int enqueue_graph(EnqCtx& x, int which) {
+  sactd3_engine* e = x.e;
+  IterPlace api;      // (the API path's updates: no place in a fused iteration)
+  api.weighted = which == G_QW;
+  switch (which) {
+    case G_Q: case G_QW: return enqueue_update_qnets(x, api, false);
+    case G_A: return enqueue_update_actor(x, api, 0, false);
+    case G_STEP00: case G_STEP01: case G_STEP10: case G_STEP11:      // + IterSchedule::k
+      return enqueue_step(x, single_iteration(((which - G_STEP00) & 2) != 0, ((which - G_STEP00) & 1) != 0));
+    case G_PERIOD: case G_PERIOD_B: return enqueue_period(x, which - G_PERIOD, e->cfg.actor_update_delay + 1);
+    case G_OPENING: return enqueue_opening(x);
+    case G_PREFIX: case G_PREFIX + 1: case G_PREFIX + 2: case G_PREFIX + 3: return enqueue_period(x, (which - G_PREFIX) & 1, (which - G_PREFIX) / 2 + 1);
+    case G_RUN: case G_RUN + 1: return enqueue_period_run(x, which - G_RUN);
+    case G_SAMPLED: case G_SAMPLED + 1: case G_SAMPLED + 2: case G_SAMPLED + 3:      // + IterSchedule::k
+      return enqueue_step_sampled(x, ((which - G_SAMPLED) & 2) != 0, ((which - G_SAMPLED) & 1) != 0);
+  }
+  return e->fail(SACTD3_EINVAL, "enqueue_graph: no such graph");
+}
+
+// what the period graphs need: every iteration takes the same target-update branch (TD3, or a target update with every critic update)
+static bool same_target_branch(const sactd3_engine* e) { return e->cfg.prefer_td3_over_sac || e->cfg.crit_targ_update_freq == 1; }
+// the preconditions the period entry points share; `who` is the entry point, for the message
+static int period_refusal(sactd3_engine* e, const char* who) {
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, (std::string(who) + ": buffer is empty").c_str());
+  if (!same_target_branch(e)) return e->fail(SACTD3_ESTATE, (std::string(who) + ": needs crit_targ_update_freq == 1").c_str());
+  return 0;
+}
+// Chained periods: the opening pair of a pipelined (cut-short) period is either left over from the previous one (chain_ready names the
+// variant, *v) or is produced now by the 2- / 3-node opening graph; taken either way -- a failure further on leaves no pair to rely on.
+// A period that is not pipelined has no pair: variant 0, and nothing to rely on behind it either.
+static int take_opening(sactd3_engine* e, bool pipelined, int* v) {
+  const bool have = pipelined && e->chain_ready >= 0;
+  *v = have ? e->chain_ready : 0;
+  e->chain_ready = -1;
+  if (pipelined && !have) RCCHK(run_graph(e, G_OPENING));
+  return 0;
+}
+// what the host knows behind a launch of `periods` periods, the last of them m iterations long on variant v
+// (a period's iterations run one behind the other, each writing e->q / e->y in its critic tail; what runs ahead inside the first one
+//  -- the later iterations' and the next period's opening passes -- goes through the actor only: the current slot, e->q and e->y all
+//  belong to the last iteration issued; m == 1 on variant 1: slot 3)
+static void periods_issued(sactd3_engine* e, bool pipelined, int v, int m, int periods = 1) {
+  e->qnet_updates += (int64_t)periods * m;
+  slot_trained(e, period_slot(pipelined, v, m - 1), true);
+}
+// k whole periods.  Pipelined: RUN_PERIODS to a graph launch, what is left of k below that through the single-period graphs, each period
+// graph leaving the NEXT period's opening pair behind; otherwise G_PERIOD k times.  The host state moves launch by launch, so a launch that
+// fails leaves it where the launches that were issued put it.  launches: {run launches, single-period launches}, counted as they go out.
+static int issue_periods(sactd3_engine* e, int k, int64_t launches[2]) {
+  const bool pipelined = period_is_pipelined(e);
+  const int n = e->cfg.actor_update_delay + 1;
+  RCCHK(actor_write_begin(e));
+  mark_grads_stale(e);
+  int v = 0;
+  RCCHK(take_opening(e, pipelined, &v));
+  for (int left = k; left > 0;) {
+    const int periods = pipelined && left >= RUN_PERIODS ? RUN_PERIODS : 1;
+    RCCHK(run_graph(e, periods > 1 ? G_RUN + v : G_PERIOD + v));
+    ++launches[periods > 1 ? 0 : 1];
+    const int last = (v + periods - 1) & 1;      // the variant of the last period issued
+    v = pipelined ? 1 - last : 0;
+    left -= periods;
+    periods_issued(e, pipelined, last, n, periods);
+    e->chain_ready = pipelined && left == 0 ? v : -1;      // (named only once the call is through)
+  }
   return 0;
 }
 
-// k whole periods: equal to k sactd3_step_period calls, bit for bit, with the pipelined form's periods going out RUN_PERIODS to a
-// graph launch and what is left of k below that through the single-period graphs.  The host state moves launch by launch, so a
-// launch that fails leaves it where the launches that were issued put it.
+// One period of the actor schedule (orchestrator.py:345-349: iteration i with i % (delay + 1) == 0 runs the actor updates,
+// the next `delay` iterations are critic-only) as ONE graph launch: delay + 1 iterations back to back, no host call and no
+// inter-replay gap in between.  Only when every iteration takes the same target-update branch (same_target_branch); otherwise the
+// caller gets SACTD3_ESTATE and issues the iterations one by one.
+int sactd3_step_period(sactd3_engine* e) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  RCCHK(period_refusal(e, "step_period"));
+  int64_t uncounted[2] = {};      // (run_stats counts what sactd3_step_periods issues)
+  return issue_periods(e, 1, uncounted);
+}
+
+// The first m iterations of a period (1 <= m <= actor_update_delay) as ONE graph launch: what is left of a run of iterations behind
+// its last whole period (orchestrator.py:337-352 for a number of iterations that is not a multiple of the period).  Equal to
+// sactd3_step(1) followed by m - 1 sactd3_step(0), bit for bit; in the pipelined form it takes the opening pair exactly as a whole
+// period does, and leaves none behind.  Same preconditions as sactd3_step_period.
+int sactd3_step_prefix(sactd3_engine* e, int m) {
+  if (!e) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  if (m < 1 || m > e->cfg.actor_update_delay) return e->fail(SACTD3_EINVAL, "step_prefix: 1 <= m <= actor_update_delay");
+  RCCHK(period_refusal(e, "step_prefix"));
+  if (!period_is_pipelined(e) || m > 2) {      // no cut-short form: the iterations one by one
+    for (int i = 0; i < m; ++i) RCCHK(sactd3_step(e, i == 0));
+    return 0;
+  }
+  RCCHK(actor_write_begin(e));
+  mark_grads_stale(e);
+  int v = 0;
+  RCCHK(take_opening(e, true, &v));
+  RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v));
+  periods_issued(e, true, v, m);
+  return 0;
+}
+
+// k whole periods: equal to k sactd3_step_period calls, bit for bit (issue_periods; sactd3_step_period is its k == 1).
 int sactd3_step_periods(sactd3_engine* e, int k) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   if (k < 1) return e->fail(SACTD3_EINVAL, "step_periods: k >= 1");
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step_periods: buffer is empty");
-  if (!e->cfg.prefer_td3_over_sac && e->cfg.crit_targ_update_freq != 1) return e->fail(SACTD3_ESTATE, "step_periods: needs crit_targ_update_freq == 1");
+  RCCHK(period_refusal(e, "step_periods"));
   ++e->run_stats[0];
-  if (!period_is_pipelined(e)) {      // no chained form: the periods one by one
-    for (int i = 0; i < k; ++i) { RCCHK(sactd3_step_period(e)); ++e->run_stats[2]; }
-    return 0;
-  }
-  const int n = e->cfg.actor_update_delay + 1;
-  RCCHK(actor_write_begin(e));
-  mark_grads_stale(e);
-  int v = e->chain_ready >= 0 ? e->chain_ready : 0;
-  const bool have = e->chain_ready >= 0;
-  e->chain_ready = -1;
-  if (!have) RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }));
-  for (int left = k; left > 0;) {
-    const int periods = left >= RUN_PERIODS ? RUN_PERIODS : 1;
-    if (periods > 1) RCCHK(run_period_graph(e, v, true));
-    else RCCHK(run_graph(e, v ? G_PERIOD_B : G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, v, n); }));
-    ++e->run_stats[periods > 1 ? 1 : 2];
-    const int last = (v + periods - 1) & 1;      // the variant of the last period issued
-    v = 1 - last;
-    left -= periods;
-    e->qnet_updates += (int64_t)periods * n;
-    slot_trained(e, period_slot(true, last, n - 1), true);
-    e->chain_ready = left > 0 ? -1 : v;      // (named only once the call is through: a failure in between leaves no pair to rely on)
-  }
-  return 0;
+  return issue_periods(e, k, &e->run_stats[1]);
 }
-int sactd3_step_periods_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  for (int i = 0; i < 4; ++i) out[i] = e->run_stats[i];
-  return 0;
-}
+int sactd3_step_periods_stats(sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::run_stats, out); }
 
-// Capture + instantiate the graphs of sactd3_step (both schedules, with the target update) and sactd3_step_period now instead of
-// at their first use, without launching anything: a caller that times its first iterations (or must not stall in the loop) calls
-// this once after sactd3_create.  No-op with use_graphs == 0.
+// Capture + instantiate the graphs of sactd3_step (both schedules, with the target update) and of sactd3_step_period / _prefix /
+// _periods now instead of at their first use, without launching anything: a caller that times its first iterations (or must not
+// stall in the loop) calls this once after sactd3_create.  No-op with use_graphs == 0.
 int sactd3_instantiate_graphs(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
-  const bool same_branch = e->cfg.prefer_td3_over_sac || e->cfg.crit_targ_update_freq == 1;
-  for (int act = 0; act < 2; ++act)
-    for (int pol = same_branch ? 1 : 0; pol < 2; ++pol) {      // (the variants without the target update exist only when it is gated)
-      const bool a = act != 0 && e->cfg.actor_update_delay > 0, py = pol != 0;
-      RCCHK(run_graph(e, G_STEP00 + (a ? 2 : 0) + (py ? 1 : 0), [&](EnqCtx& x) { return enqueue_step(x, single_iteration(a, py)); }, false));
-    }
-  if (same_branch && e->cfg.actor_update_delay > 0) {
-    RCCHK(run_graph(e, G_PERIOD, [&](EnqCtx& x) { return enqueue_period(x, 0, e->cfg.actor_update_delay + 1); }, false));
-    if (period_is_pipelined(e)) {
-      RCCHK(run_graph(e, G_PERIOD_B, [&](EnqCtx& x) { return enqueue_period(x, 1, e->cfg.actor_update_delay + 1); }, false));
-      RCCHK(run_graph(e, G_OPENING, [&](EnqCtx& x) { return enqueue_opening(x); }, false));
-      for (int m = 1; m <= e->cfg.actor_update_delay && m <= 2; ++m)
-        for (int v = 0; v < 2; ++v)
-          RCCHK(run_graph(e, G_PREFIX + 2 * (m - 1) + v, [&](EnqCtx& x) { return enqueue_period(x, v, m); }, false));
-      for (int v = 0; v < 2; ++v) RCCHK(run_period_graph(e, v, false));      // sactd3_step_periods: a run from either variant
-    }
+  for (int act = 0; act < 2; ++act) {      // the schedules of the first update and of one with a target update: the same unless that is gated
+    RCCHK(run_graph(e, G_STEP00 + iteration_schedule(e, act, 1).k, false));
+    RCCHK(run_graph(e, G_STEP00 + iteration_schedule(e, act, e->cfg.crit_targ_update_freq).k, false));
   }
+  if (!same_target_branch(e) || e->cfg.actor_update_delay <= 0) return 0;
+  RCCHK(run_graph(e, G_PERIOD, false));
+  if (!period_is_pipelined(e)) return 0;
+  // the other variant, the opening graph, a run from either variant (sactd3_step_periods), and the cut-short periods of m = 1 (, 2)
+  const int pipelined_ids[] = {G_PERIOD_B, G_OPENING, G_RUN, G_RUN + 1};
+  for (int id : pipelined_ids) RCCHK(run_graph(e, id, false));
+  for (int id = G_PREFIX; id < G_PREFIX + 2 * std::min(e->cfg.actor_update_delay, 2); ++id) RCCHK(run_graph(e, id, false));
   return 0;
 }
 
@@ -3407,8 +3405,8 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph) {
   if (!e) return SACTD3_EINVAL;
   static const int map[9] = {G_Q, G_A, G_STEP01, G_STEP11, G_PERIOD, G_OPENING, G_PREFIX, G_PREFIX + 2, G_QW};
   // 16 + 2 do_actor + target update: the graphs of sactd3_step_sampled for its current (draw, n_step, stride); 0: not captured
-  if (which_graph >= 16 && which_graph < 20) return e->ss_nodes[which_graph - 16];
-  if (which_graph == 10) return e->run_graphs[0] ? e->run_nodes[0] : e->run_nodes[1];      // the run graph of sactd3_step_periods; 0: not captured
+  if (which_graph >= 16 && which_graph < 20) return e->graph_nodes[G_SAMPLED + which_graph - 16];
+  if (which_graph == 10) return e->graph_nodes[e->graphs[G_RUN] ? G_RUN : G_RUN + 1];      // the run graph of sactd3_step_periods; 0: not captured
   if (which_graph < 0 || which_graph > 8) return SACTD3_EINVAL;
   int w = map[which_graph];
   if (!e->graphs[w] && (which_graph == 2 || which_graph == 3)) w -= 1;   // the no-Polyak variant, if that is the one in use
@@ -3552,14 +3550,14 @@ int sactd3_time_nodes(sactd3_engine* e, int do_actor, int iters, int max_nodes, 
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_nodes: buffer is empty");
   slot_refilled(e, false, false);
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
-  const bool period = do_actor == 2 && e->cfg.actor_update_delay > 0 && (e->cfg.prefer_td3_over_sac || e->cfg.crit_targ_update_freq == 1);
+  const bool period = do_actor == 2 && e->cfg.actor_update_delay > 0 && same_target_branch(e);
   if (act || period) RCCHK(actor_write_begin(e));
   if (period) mark_grads_stale(e);
   std::vector<NodeInfo> log;
   auto seq = [&](int only, std::vector<NodeInfo>* into = nullptr) -> int {      // the sequence with launch `only` alone issued (-1: all of them)
     EnqCtx x{e, e->stream};
     x.node_only = only; x.node_log = into;
-    return enqueue_end(x, period ? enqueue_period(x, 0, e->cfg.actor_update_delay + 1) : enqueue_step(x, single_iteration(act, true)));
+    return enqueue_end(x, enqueue_graph(x, period ? G_PERIOD : act ? G_STEP11 : G_STEP01));
   };
   int rc = seq(1 << 30, &log);               // list only, launch nothing
   if (rc != 0) return rc;

@@ -856,6 +856,26 @@ def test_graphs_can_be_instantiated_ahead_of_the_first_step():
         res.append((eng.get_params(_lib.ACTOR), eng.get_params(_lib.CRITICS), eng.get_params(_lib.LOG_ALPHA), eng.read_batch()["index"]))
     for x, y in zip(*res):
         assert np.array_equal(x, y)
+    # delay 1: the pipelined period with one iteration run ahead; delay 3: the period that is not pipelined.  The entry points find the
+    # graphs instantiate_graphs made -- none is captured again under another id: every public id (0..8, 10, 16..19) the lazily capturing
+    # twin has used holds the same node count ahead, and the iterations capture no further run graph (2 where pipelined, else 0)
+    for delay, run_graphs in ((1, 2), (3, 0)):
+        res, counts = [], []
+        for ahead in (True, False):
+            ref, eng, (o, a, bound) = make_pair("sac", "hopper", 64, seed=9, actor_update_delay=delay)
+            eng.rb_extend(*[t.numpy() for t in synth_transitions(300, o, a, bound, seed=2)])
+            if ahead:
+                eng.instantiate_graphs()
+                assert eng.step_periods_stats()["run_graphs_captured"] == run_graphs
+            eng.run_iterations(0, 12)
+            if ahead:
+                assert eng.step_periods_stats()["run_graphs_captured"] == run_graphs
+            counts.append({i: eng.graph_kernel_count(i) for i in (*range(9), 10, *range(16, 20))})
+            res.append((eng.get_params(_lib.ACTOR), eng.get_params(_lib.CRITICS), eng.get_params(_lib.LOG_ALPHA), eng.read_batch()["index"]))
+        used = {i: n for i, n in counts[1].items() if n}
+        assert used and {i: counts[0][i] for i in used} == used, (delay, counts)
+        for x, y in zip(*res):
+            assert np.array_equal(x, y), delay
     # a gated target update (crit_targ_update_freq = 2): both variants of the step graphs are captured, no period graph
     res = []
     for ahead in (True, False):
