@@ -104,6 +104,29 @@ def ln_rstd(X, W1, b1, eps=1e-5):
     return 1.0 / np.sqrt(var + eps), rho
 
 
+def ln_xhat(X, W1, b1, eps=1e-5):
+    """xhat1 = (z - mean z) rstd of the layer-1 LayerNorm, z = X W1^T + b1, in float64 from the layer's input rows X -- what ties the
+    stored xhat1 (every later check's input) to the batch rows: a first-layer tile masked one column short or a row block reading
+    another block's rows moves z by whole terms.  First-order bound, every kernel form computing (z - mean) * rstd:
+      z     within dz, the GEMM bound (gemm, without SAFETY);
+      mean  within dm = mean(dz) + gamma(H + 2) (mean |z| + mean(dz)): the shift of its terms, then its own rounding in any order
+            (sequential, or a mean of partial means);
+      d = z - mean  within dd = dz + dm + u (|d| + dz + dm);
+      rstd  within the relative rho of ln_rstd;
+      the product adds u:   |xhat - xhat64| <= rstd (1 + rho) dd + |xhat64| (rho + u)."""
+    z, dz = gemm(X, W1, b1)
+    dz = dz / SAFETY
+    H = z.shape[1]
+    rstd, rho = ln_rstd(X, W1, b1, eps)
+    mu = z.mean(1, keepdims=True)
+    d = z - mu
+    mdz = dz.mean(1, keepdims=True)
+    dm = mdz + gamma(H + 2) * (np.abs(z).mean(1, keepdims=True) + mdz)
+    dd = dz + dm + U * (np.abs(d) + dz + dm)
+    xhat = d * rstd
+    return xhat, SAFETY * (rstd * (1.0 + rho) * dd + np.abs(xhat) * (rho + U))
+
+
 def ln_bwd(dh, h, xhat, g, rstd, rho):
     """dz = rstd (dxh - mean(dxh) - xhat mean(dxh xhat)), dxh = relu'(y) dh g, from the engine's dh, h (ReLU mask), xhat, with the
     float64 rstd of ln_rstd.  First-order bound: the rounding of dxh, of the two row means (gamma(H + 2), gamma(H + 3)), of the

@@ -12,7 +12,9 @@ nodes of each form the fused iteration graphs hold, derived from those rules (tr
 quietly empty the table.
 
 Every case then runs update_qnets, update_actor and update_targ_nets through the API and checks (tests/bounds.py):
-  * each stage whose inputs can be read back, recomputed in float64 from those inputs, against an a-priori rounding bound;
+  * each stage whose inputs can be read back, recomputed in float64 from those inputs, against an a-priori rounding bound -- the
+    critics' and the actor's trunk forward and backward, and the forward pass of the online critics over [s | pi(s)] that
+    update_actor leaves in the critics' buffers (a 2-net launch under SAC, a 1-net one under TD3);
   * every element of the Adam moments, the parameters, the Polyak targets and the temperature from the engine's own gradient;
   * the existing per-intermediate / per-key assertions of tests/test_gpu_engine.py at the new shapes.
 No tolerance here is taken from an observed error and none allows a fraction of bad elements; the worst |err| / bound per stage is
@@ -241,8 +243,11 @@ def check_trunk_backward(rec, who, X, p, h1, xh1, dz2, dh1, dz1, grads, ln, B, g
 
 
 def check_trunk_forward(rec, who, X, p, h1, xh1, z2, ln):
-    """h1 (LayerNorm affine + ReLU from the engine's xhat1; without LayerNorm relu(X W1^T + b1)) and z2 = h1 W2^T + b2 (K = 256)"""
+    """xhat1 from the input rows X (LayerNorm), h1 (LayerNorm affine + ReLU from the engine's xhat1; without LayerNorm
+    relu(X W1^T + b1)) and z2 = h1 W2^T + b2 (K = 256)"""
     if ln:
+        want, bound = bd.ln_xhat(X, p[f"{K1}.fc.weight"], p[f"{K1}.fc.bias"])
+        observe(rec, f"{who} xhat1: err / bound", bd.check(f"{who} xhat1", xh1, want, bound))
         want, y, bound = bd.ln_affine_relu(xh1, p[f"{K1}.ln.weight"], p[f"{K1}.ln.bias"])
     else:
         y, bound = bd.gemm(X, p[f"{K1}.fc.weight"], p[f"{K1}.fc.bias"])
@@ -310,6 +315,14 @@ def run_one_iteration(algo, env, B, ln, rec, adam_step=1000, stages=True, **hp):
         check_trunk_backward(rec, "actor", Xo, p, rd["a_h1"], rd["a_xh1"], rd["a_dz2"], rd["a_dh1"], rd["a_dz1"], gr, ln, B, gated_dh1=B < 1024)
         for key, (want, bnd) in (("head.weight", bd.batch_wgrad(du, rd["a_h2"])), ("head.bias", bd.batch_sum(du))):
             observe(rec, f"actor grad {key}: err / bound", bd.check(f"actor grad {key}", gr[key], want, bnd))
+        # the Q(s, pi) pass: the nq online critics (SAC 2, TD3 1), as stepped above, over Xp = [s | pi(s)] -- a launch of its own shape
+        # (2 or 1 nets), whose xhat1, h1 and z2 stay in the critics' buffers
+        Xp = eng.debug_read("Xp").reshape(B, ldc)[:, :o + a]
+        assert np.array_equal(Xp[:, :o], obs.numpy())
+        pq = eng.get_params(_lib.CRITICS).reshape(2, -1)
+        rq = {k: eng.debug_read(k).reshape(2, B, H) for k in ("c_xh1", "c_h1", "c_z2")}
+        for i in range(2 if sac else 1):
+            check_trunk_forward(rec, f"Q(s, pi) critic{i}", Xp, _nd(pq[i], o + a, 1, ln), rq["c_h1"][i], rq["c_xh1"][i], rq["c_z2"][i], ln)
     if eng.cfg.clip_norm > 0:      # k_adam: the stored gradient is the unclipped G, scaled by the coefficient of its fp32 norm
         coef, rel = bd.clip_coef(Ga, eng.cfg.clip_norm)
         check_adam(rec, "actor (clipped)", eng, _lib.ACTOR, pre[_lib.ACTOR], Ga, eng.cfg.actor_lr, coef=coef, coef_rel=rel)
@@ -328,9 +341,16 @@ def run_one_iteration(algo, env, B, ln, rec, adam_step=1000, stages=True, **hp):
     eng.close()
 
 
-def run_fused_critic_iteration(algo, env, B, ln, rec, adam_step=1000):
+def _same_bits(got, want):
+    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def run_fused_critic_iteration(algo, env, B, ln, rec, adam_step=1000, stages=False):
     """one fused critic-only iteration (sactd3_step): the critic targets lerped in the weight-gradient launch's Adam epilogue (k_tn /
-    k_adam_red) and, TD3, the actor target as riding blocks of that launch -- from the engine's own gradient and parameters"""
+    k_adam_red) and, TD3, the actor target as riding blocks of that launch -- from the engine's own gradient and parameters.
+    stages: also the batch slot against the ring rows of the sample it reports, bit for bit, and the critics' trunk forward and
+    backward stages from the parameters before the step -- the launches whose opening trunk reads ring rows and carries the gather"""
     o, a, bound = DIMS[env]
     ref, eng, _ = make_pair(algo, env, B, ln, rb_capacity=2 * B)
     rows = [t.numpy() for t in synth_transitions(2 * B, o, a, bound, seed=7)]
@@ -339,6 +359,20 @@ def run_fused_critic_iteration(algo, env, B, ln, rec, adam_step=1000):
     evolve_adam(eng, _lib.CRITICS, adam_step, 12)
     pre = {w: snapshot(eng, w) for w in (_lib.CRITICS, _lib.CRITICS_TARGET, _lib.ACTOR, _lib.ACTOR_TARGET)}
     eng.step(False)
+    if stages:
+        idx = eng.read_batch()["index"]
+        assert idx.shape == (B,) and idx.min() >= 0 and idx.max() < 2 * B, (idx.min(), idx.max())
+        X = eng.debug_read("X").reshape(B, (o + a + 3) // 4 * 4)[:, :o + a]
+        assert _same_bits(X[:, :o], rows[0][idx]) and _same_bits(X[:, o:], rows[1][idx]), "batch slot [s | a] != the sampled ring rows"
+        assert _same_bits(eng.debug_read("rew"), rows[2][idx]), "batch slot rewards != the sampled ring rows"
+        assert _same_bits(eng.debug_read("done"), rows[4][idx].astype(np.float32)), "batch slot done flags != the sampled ring rows"
+        rd = {k: eng.debug_read(k).reshape(2, B, H) for k in ("c_xh1", "c_h1", "c_z2", "c_dz2", "c_dh1", "c_dz1")}
+        pc, Gc = pre[_lib.CRITICS]["p"].reshape(2, -1), eng.debug_read("grad_critics").reshape(2, -1)
+        for i in range(2):
+            p, who = _nd(pc[i], o + a, 1, ln), f"fused critic{i}"
+            check_trunk_forward(rec, who, X, p, rd["c_h1"][i], rd["c_xh1"][i], rd["c_z2"][i], ln)
+            check_trunk_backward(rec, who, X, p, rd["c_h1"][i], rd["c_xh1"][i], rd["c_dz2"][i], rd["c_dh1"][i], rd["c_dz1"][i],
+                                 _nd(Gc[i], o + a, 1, ln), ln, B, gated_dh1=B < 1024)
     check_adam(rec, "critics (fused step)", eng, _lib.CRITICS, pre[_lib.CRITICS], eng.debug_read("grad_critics"), eng.cfg.qnets_lr)
     check_polyak(rec, "critic targets (Adam epilogue)", eng, _lib.CRITICS_TARGET, _lib.CRITICS, pre[_lib.CRITICS_TARGET]["p"])
     assert np.array_equal(eng.get_params(_lib.ACTOR), pre[_lib.ACTOR]["p"])

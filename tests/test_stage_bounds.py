@@ -1,6 +1,8 @@
-"""The checker of tests/test_gpu_large_batch.py on the CPU: the a-priori bounds of tests/bounds.py accept correct fp32 computations
-in every summation order the engine uses (torch's matmul, a sequential reversed sum, 64-row chunks dealt unevenly over slices as
-k_tn64 + k_adam_red do) and reject each defect listed below.  The bounds are worst-case, so the outcome does not depend on the CPU."""
+"""The checker of tests/test_gpu_large_batch.py and tests/test_gpu_small_batch.py on the CPU: the a-priori bounds of tests/bounds.py
+accept correct fp32 computations in every summation order the engine uses (torch's matmul, a sequential reversed sum, 64-row chunks
+dealt unevenly over slices as k_tn64 + k_adam_red do, 256-row slabs of four interleaved chunk groups as k_tn does, a K split into 4 or
+2 parts as k_nt does) and reject each defect listed below, at large batch sizes and at the small ones where a switch of the
+small-batch dispatch leaves a one-row block (17, 113, 257).  The bounds are worst-case, so the outcome does not depend on the CPU."""
 import numpy as np
 import pytest
 import torch
@@ -49,37 +51,104 @@ def _blocked_slices(dY, X, S=3):
     return w, b
 
 
+def _slab_groups(dY, X):
+    """k_tn's order below B = 1024: the rows in 256-row slabs, summed slab after slab; inside a slab the 16-row chunks (each an fp32
+    product) are dealt round-robin over four groups that accumulate separately and are summed as (a + b) + (c + d).  The bias: 16
+    partials (row r in partial r mod 16, each summed in order), then the partials in order."""
+    B = dY.shape[0]
+    w = np.zeros((dY.shape[1], X.shape[1]), F32)
+    for s in range(0, B, 256):
+        grp = [np.zeros_like(w) for _ in range(4)]
+        for j, c in enumerate(range(s, min(s + 256, B), 16)):
+            grp[j % 4] = grp[j % 4] + _torch_wgrad(dY[c:c + 16], X[c:c + 16])[0]
+        w = w + ((grp[0] + grp[1]) + (grp[2] + grp[3]))
+    b = np.zeros(dY.shape[1], F32)
+    for p in range(16):
+        part = np.zeros(dY.shape[1], F32)
+        for r in range(p, B, 16):
+            part = part + dY[r]
+        b = b + part
+    return w, b
+
+
+def _split_k(A, W, b, parts):
+    """k_nt's order: K in `parts` (4, 2) contiguous parts, each summed in order in fp32, the parts combined as a tree, then the bias"""
+    K = A.shape[1]
+    acc = []
+    for q in range(parts):
+        y = np.zeros((A.shape[0], W.shape[0]), F32)
+        for k in range(q * K // parts, (q + 1) * K // parts):
+            y = y + A[:, k:k + 1] * W[None, :, k]
+        acc.append(y)
+    while len(acc) > 1:
+        acc = [acc[i] + acc[i + 1] for i in range(0, len(acc), 2)]
+    return acc[0] + b
+
+
+ORDERS = {"torch": _torch_wgrad, "sequential_reversed": _sequential_reversed, "blocked_slices": _blocked_slices, "slab_groups": _slab_groups}
+BATCHES = [17, 113, 257, 1025, 4095]
+
+
 def _check_wgrad(dY, X, got_w, got_b):
     ww, bw = bd.batch_wgrad(dY, X)
     wb, bb = bd.batch_sum(dY)
     return max(bd.check("dW", got_w, ww, bw), bd.check("db", got_b, wb, bb))
 
 
-@pytest.mark.parametrize("B", [1025, 4095])
-@pytest.mark.parametrize("order", ["torch", "sequential_reversed", "blocked_slices"])
+@pytest.mark.parametrize("B", BATCHES)
+@pytest.mark.parametrize("order", list(ORDERS))
 def test_weight_gradient_bounds_accept_every_summation_order(B, order):
     dY, X = _data(B)
-    w, b = {"torch": _torch_wgrad, "sequential_reversed": _sequential_reversed, "blocked_slices": _blocked_slices}[order](dY, X)
+    w, b = ORDERS[order](dY, X)
     assert _check_wgrad(dY, X, w, b) <= 1.0
 
 
-@pytest.mark.parametrize("B", [1025, 4095])
-@pytest.mark.parametrize("defect", ["last_row_dropped", "row_counted_twice", "chunk_dropped"])
+def _defective_wgrad(dY, X, defect, order):
+    B = dY.shape[0]
+    if defect == "last_row_dropped":
+        return ORDERS[order](dY[:-1], X[:-1])
+    if defect == "row_counted_twice":
+        return ORDERS[order](np.concatenate([dY, dY[-1:]]), np.concatenate([X, X[-1:]]))
+    c = (B // 64) // 2                                      # chunk_dropped: one 64-row chunk of ordinary (not loud) rows
+    keep = np.r_[0:64 * c, 64 * (c + 1):B]
+    return ORDERS[order](dY[keep], X[keep])
+
+
+# (B = 17 has fewer than two 64-row chunks: no chunk of ordinary rows to drop)
+DEFECTS = [pytest.param(B, d, id=f"{d}-{B}") for B in BATCHES for d in ("last_row_dropped", "row_counted_twice", "chunk_dropped")
+           if not (d == "chunk_dropped" and B < 64)]
+
+
+@pytest.mark.parametrize("B,defect", DEFECTS)
 def test_weight_gradient_bounds_catch_lost_or_repeated_rows(B, defect):
     dY, X = _data(B)
-    if defect == "last_row_dropped":
-        w, b = _torch_wgrad(dY[:-1], X[:-1])
-    elif defect == "row_counted_twice":
-        w, b = _torch_wgrad(np.concatenate([dY, dY[-1:]]), np.concatenate([X, X[-1:]]))
-    else:                                                   # one 64-row chunk of ordinary (not loud) rows
-        c = (B // 64) // 2
-        keep = np.r_[0:64 * c, 64 * (c + 1):B]
-        w, b = _torch_wgrad(dY[keep], X[keep])
     with pytest.raises(bd.Violation):
-        _check_wgrad(dY, X, w, b)
+        _check_wgrad(dY, X, *_defective_wgrad(dY, X, defect, "torch"))
 
 
-@pytest.mark.parametrize("B", [1025, 4095])
+@pytest.mark.parametrize("B,defect", DEFECTS)
+def test_weight_gradient_bounds_catch_lost_or_repeated_rows_in_the_slab_order(B, defect):
+    """the same defects in k_tn's small-batch summation order"""
+    dY, X = _data(B)
+    with pytest.raises(bd.Violation):
+        _check_wgrad(dY, X, *_defective_wgrad(dY, X, defect, "slab_groups"))
+
+
+@pytest.mark.parametrize("B", [17, 113, 257])
+@pytest.mark.parametrize("parts", [4, 2])
+def test_gemm_bound_accepts_a_split_k_and_catches_a_lost_part(B, parts):
+    """z2 = h1 W2^T + b2 over K = 256 in k_nt's KS = 4 and KS = 2 orders; a defect: the last sixteenth of K left out"""
+    rng = np.random.default_rng(B + parts)
+    K = N = 256
+    A = np.maximum(rng.standard_normal((B, K)), 0.0).astype(F32)
+    W, b = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(F32), (0.1 * rng.standard_normal(N)).astype(F32)
+    want, bound = bd.gemm(A, W, b)
+    assert bd.check("z2", _split_k(A, W, b, parts), want, bound) <= 1.0
+    with pytest.raises(bd.Violation):
+        bd.check("z2", _split_k(A[:, :K - 16], W[:, :K - 16], b, parts), want, bound)
+
+
+@pytest.mark.parametrize("B", BATCHES)
 def test_gemm_and_layernorm_forward_bounds_accept_fp32(B):
     rng = np.random.default_rng(B)
     K, H = 40, 256
@@ -91,10 +160,51 @@ def test_gemm_and_layernorm_forward_bounds_accept_fp32(B):
     zt = torch.from_numpy(z)
     mu = zt.mean(1, keepdim=True)
     xhat = ((zt - mu) * torch.rsqrt(((zt - mu) ** 2).mean(1, keepdim=True) + 1e-5)).numpy()
+    want, bound = bd.ln_xhat(X, W1, b1)
+    assert bd.check("xhat1", xhat, want, bound) <= 1.0
     g, be = (1 + 0.1 * rng.standard_normal(H)).astype(F32), (0.1 * rng.standard_normal(H)).astype(F32)
     h = np.maximum(xhat * g + be, F32(0))
     want, y, bound = bd.ln_affine_relu(xhat, g, be)
     assert bd.check("h1", h, want, bound, accept=bd.relu_accept(h, y, bound)) <= 1.0
+
+
+def _xhat_partials(X, W1, b1, parts=16):
+    """k_nt's LayerNorm prologue in fp32: z in k order, (mean, M2) per group of 256 / parts columns, the mean of the partial means,
+    M2 combined as Chan et al. do, xhat = (z - mean) * rstd"""
+    z = _split_k(X, W1, b1, 1)
+    H = z.shape[1]
+    n = H // parts
+    zp = z.reshape(z.shape[0], parts, n)
+    ml = zp.sum(2, dtype=F32) * F32(1.0 / n)
+    m2 = ((zp - ml[:, :, None]) ** 2).sum(2, dtype=F32)
+    mean = ml.sum(1, dtype=F32, keepdims=True) * F32(1.0 / parts)
+    M2 = (m2 + F32(n) * (ml - mean) ** 2).sum(1, dtype=F32, keepdims=True)
+    rstd = F32(1) / np.sqrt(M2 * F32(1.0 / H) + F32(1e-5))
+    return ((z - mean) * rstd).astype(F32)
+
+
+@pytest.mark.parametrize("B", [17, 113, 257])
+@pytest.mark.parametrize("K", [3, 14, 48, 65])
+def test_xhat_bound_ties_the_stored_rows_to_the_input_rows(B, K):
+    """bounds.ln_xhat accepts the fp32 prologue of the fused trunk form and rejects a first layer that leaves out the last input
+    column (a mask one short), one whose last row read the row in front of it, and a mean taken over 255 of the 256 columns"""
+    rng = np.random.default_rng(100 * B + K)
+    X = rng.standard_normal((B, K)).astype(F32)
+    W1, b1 = (rng.standard_normal((256, K)) / np.sqrt(K)).astype(F32), (0.1 * rng.standard_normal(256)).astype(F32)
+    want, bound = bd.ln_xhat(X, W1, b1)
+    assert bd.check("xhat1", _xhat_partials(X, W1, b1), want, bound) <= 1.0
+    masked = X.copy()
+    masked[:, -1] = 0
+    shifted = X.copy()
+    shifted[-1] = X[-2]
+    for what, bad in (("column", _xhat_partials(masked, W1, b1)), ("row", _xhat_partials(shifted, W1, b1))):
+        with pytest.raises(bd.Violation):
+            bd.check(f"xhat1 ({what})", bad, want, bound)
+    z = _split_k(X, W1, b1, 1)
+    mean = z[:, :255].mean(1, keepdims=True, dtype=F32)
+    rstd = F32(1) / np.sqrt(((z - mean) ** 2).mean(1, keepdims=True, dtype=F32) + F32(1e-5))
+    with pytest.raises(bd.Violation):
+        bd.check("xhat1 (mean)", (z - mean) * rstd, want, bound)
 
 
 def _ln_case(seed=3, B=96, K=40, H=256):
@@ -213,7 +323,7 @@ def test_polyak_bound(twice):
         assert bd.check("target", t, want, bound) <= 1.0
 
 
-@pytest.mark.parametrize("B", [1025, 4095])
+@pytest.mark.parametrize("B", BATCHES)
 def test_alpha_gradient_bound(B):
     rng = np.random.default_rng(B)
     logp = (rng.standard_normal(B) * 3).astype(F32)
