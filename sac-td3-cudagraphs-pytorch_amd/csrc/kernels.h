@@ -1981,21 +1981,65 @@ __device__ __forceinline__ AdamState adam_fetch(const TnArgs& p, long off) {
   if (p.apply) { s.w = p.P[off]; s.m = p.Mo[off]; s.v = p.Vo[off]; if (p.T) s.t = p.T[off]; }
   return s;
 }
+// one element's step, IN PLACE (s becomes the new w, m, v); the 4-byte and the 16-byte commit share these expressions
+__device__ __forceinline__ void adam_step(const TnArgs& p, float g, AdamState& s, float step, float sq2) {
+  const float m = s.m + (g - s.m) * (1.0f - p.b1);
+  const float v = s.v * p.b2 + g * g * (1.0f - p.b2);
+  const float w = s.w - step * (m / (sqrtf(v) / sq2 + p.eps));
+  s.m = m; s.v = v; s.w = w;
+}
+__device__ __forceinline__ float polyak_step(const TnArgs& p, float t, float w) { return t + (w - t) * p.tau; }
 template <bool KEEP_G>
 __device__ __forceinline__ void adam_commit(const TnArgs& p, long off, float g, AdamState s, float step, float sq2) {
   if (KEEP_G) p.G[off] = g;
   if (p.apply) {
-    const float m = s.m + (g - s.m) * (1.0f - p.b1);
-    const float v = s.v * p.b2 + g * g * (1.0f - p.b2);
-    const float w = s.w - step * (m / (sqrtf(v) / sq2 + p.eps));
-    p.Mo[off] = m; p.Vo[off] = v; p.P[off] = w;
+    adam_step(p, g, s, step, sq2);
+    p.Mo[off] = s.m; p.Vo[off] = s.v; p.P[off] = s.w;
     if (p.T) {
-      const float t1 = s.t + (w - s.t) * p.tau;
+      const float t1 = polyak_step(p, s.t, s.w);
       p.T[off] = t1;
       if (p.T2) {
-        const float t2 = t1 + (w - t1) * p.tau;
+        const float t2 = polyak_step(p, t1, s.w);
         p.T2[off] = t2;
-        if (p.T3) p.T3[off] = t2 + (w - t2) * p.tau;
+        if (p.T3) p.T3[off] = polyak_step(p, t2, s.w);
+      }
+    }
+  }
+}
+// The same for 4 consecutive elements of one weight row (off is a multiple of 4: every arena row is float4 aligned): one 16-byte
+// request per array where the 4-byte form issues four.  Component i is element off + i.
+struct AdamState4 { float4 w, m, v, t; };
+__device__ __forceinline__ float& f4r(float4& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }   // (i is a constant after unrolling)
+__device__ __forceinline__ AdamState4 adam_fetch4(const TnArgs& p, long off) {
+  AdamState4 s{f4(0.f), f4(0.f), f4(0.f), f4(0.f)};
+  if (p.apply) { s.w = ld4(p.P + off); s.m = ld4(p.Mo + off); s.v = ld4(p.Vo + off); if (p.T) s.t = ld4(p.T + off); }
+  return s;
+}
+__device__ __forceinline__ AdamState adam_pick(const AdamState4& s, int i) { return AdamState{f4c(s.w, i), f4c(s.m, i), f4c(s.v, i), f4c(s.t, i)}; }
+template <bool KEEP_G>
+__device__ __forceinline__ void adam_commit4(const TnArgs& p, long off, float4 g, AdamState4 s, float step, float sq2) {
+  if (KEEP_G) st4(p.G + off, g);
+  if (p.apply) {
+    AdamState e[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { e[i] = adam_pick(s, i); adam_step(p, f4c(g, i), e[i], step, sq2); }
+    st4(p.Mo + off, make_float4(e[0].m, e[1].m, e[2].m, e[3].m));
+    st4(p.Vo + off, make_float4(e[0].v, e[1].v, e[2].v, e[3].v));
+    st4(p.P + off, make_float4(e[0].w, e[1].w, e[2].w, e[3].w));
+    if (p.T) {
+      float t[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) t[i] = polyak_step(p, e[i].t, e[i].w);
+      st4(p.T + off, make_float4(t[0], t[1], t[2], t[3]));
+      if (p.T2) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t[i] = polyak_step(p, t[i], e[i].w);
+        st4(p.T2 + off, make_float4(t[0], t[1], t[2], t[3]));
+        if (p.T3) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) t[i] = polyak_step(p, t[i], e[i].w);
+          st4(p.T3 + off, make_float4(t[0], t[1], t[2], t[3]));
+        }
       }
     }
   }

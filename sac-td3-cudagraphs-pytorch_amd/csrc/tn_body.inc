@@ -55,9 +55,13 @@ __global__ __launch_bounds__(256) void k_tn(int h_tiles, int h_pk_blocks, int h_
   xcd_tile(local, (q.N + 15) >> 4, tiles_k, q.xr, tn, tk);
   const int n0 = tn * 16, k0 = tk * 16 * KT;
   const long nbase = net * g_ns;
-  // the epilogue's elements: wave kt < KT, lane (j = lane & 15, rq = lane >> 4) owns rows n0 + 4 rq + i, column k0 + 16 kt + j
-  const int ecol = k0 + 16 * min(wave, KT - 1) + (lane & 15);
-  AdamState st[4], sv = {0.f, 0.f, 0.f, 0.f};
+  // the epilogue's elements: wave kt < KT, lane (j = lane & 15, cq = lane >> 4) owns row n0 + j, columns k0 + 16 kt + 4 cq + i: 16
+  // bytes of one weight row (the MFMAs below take X as their A operand, so the accumulator holds the tile transposed), one request
+  // per array instead of four.  A piece whose width, row stride or offset is no multiple of 4 takes them one by one (block-uniform)
+  const int erow = n0 + (lane & 15), ecol = k0 + 16 * min(wave, KT - 1) + 4 * (lane >> 4);
+  const bool vec4 = uni(((kw | q.ldw | q.w_off) & 3) | (int)(g_ns & 3)) == 0;
+  AdamState4 st{f4(0.f), f4(0.f), f4(0.f), f4(0.f)};
+  const AdamState sv = {0.f, 0.f, 0.f, 0.f};
   STAMP(0); BLK_PH(0);
   // operand tiles are column slices ([M rows][16 floats]): fetched as float4 (64-byte pieces), transposed through LDS
   const float* dYn = q.dY + net * q.dy_ns;
@@ -91,13 +95,9 @@ __global__ __launch_bounds__(256) void k_tn(int h_tiles, int h_pk_blocks, int h_
   fetch(0);
   if (fold_ln) gq = ld4(q.f_g + net * HID + n0 + 4 * (t & 3));
   const float step = apply ? p.adam[0] : 0.f, sq2 = apply ? p.adam[1] : 1.f;
-  if (wave < KT) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {          // clamped, not predicated (the commit is predicated)
-      const int row = min(n0 + 4 * (lane >> 4) + i, q.N - 1);
-      st[i] = adam_fetch(p, nbase + q.w_off + (long)row * q.ldw + min(ecol, kw - 1));
-    }
-  }
+  // clamped, not predicated (the commit is predicated).  Only the 16-byte form asks here: a second form of this request, joined
+  // with it, made the compiler wait for the whole operand batch in front of both (the 4-byte form fetches where it commits)
+  if (wave < KT && vec4) st = adam_fetch4(p, nbase + q.w_off + (long)min(erow, q.N - 1) * q.ldw + min(ecol, kw - 4));
   // k-tile-0 blocks also produce the bias gradient of their 16 columns (column sums of dY, collected from the LDS tile in the
   // main loop): wave 3, lanes 0 .. 15 commit it; its optimiser state is requested now
   const int fcol = t & 15, fpart = t >> 4, fn = n0 + fcol;         // (column, partial-group) of this thread
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void k_tn(int h_tiles, int h_pk_blocks, int h_
       for (int kt = 0; kt < KT; ++kt) {
         const float* x0 = Xs + kt * 256 * YS + (16 * (wave + 4 * u) + 4 * kq) * YS + r;
         const float4 b = make_float4(x0[0], x0[YS], x0[2 * YS], x0[3 * YS]);
-        MFMA4(acc[kt], a, b);
+        MFMA4(acc[kt], b, a);                                // D[k][n]: the same products in the same order as D[n][k] of (a, b)
       }
     }
     if (want_bias) {
@@ -173,17 +173,21 @@ __global__ __launch_bounds__(256) void k_tn(int h_tiles, int h_pk_blocks, int h_
   STAMP(3); BLK_PH(3);
   if (!KEEP_G) {          // (without the arena store in front of it, each row's branch below would be the first use of its optimiser
 #pragma unroll           //  state, and every group of stores would wait for the previous group's: PIN)
-    for (int i = 0; i < 4; ++i) { PIN(st[i].w); PIN(st[i].m); PIN(st[i].v); PIN(st[i].t); }
+    for (int i = 0; i < 4; ++i) { PIN(f4r(st.w, i)); PIN(f4r(st.m, i)); PIN(f4r(st.v, i)); PIN(f4r(st.t, i)); }
     PIN(fstate.w); PIN(fstate.m); PIN(fstate.v); PIN(fstate.t);
   }
-  if (wave < KT && ecol < kw) {
+  if (wave < KT && ecol < kw && erow < q.N) {
     const float* rr = red + (wave * 4 * 64 + lane) * 4;
     const float4 a = ld4(rr), b = ld4(rr + 256), c = ld4(rr + 512), d = ld4(rr + 768);
     const float o[4] = {(a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w)};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = n0 + 4 * (lane >> 4) + i;
-      if (row < q.N) adam_commit<KEEP_G>(p, nbase + q.w_off + (long)row * q.ldw + ecol, ecol < q.K ? o[i] : 0.f, st[i], step, sq2);
+    const float4 g = make_float4(ecol < q.K ? o[0] : 0.f, ecol + 1 < q.K ? o[1] : 0.f, ecol + 2 < q.K ? o[2] : 0.f, ecol + 3 < q.K ? o[3] : 0.f);
+    const long off = nbase + q.w_off + (long)erow * q.ldw + ecol;
+    if (vec4) adam_commit4<KEEP_G>(p, off, g, st, step, sq2);       // (ecol < kw, both multiples of 4: all 4 columns are the piece's)
+    else {                                                          // (no layout the engine builds comes here: rolled, a round trip per element)
+#pragma unroll 1
+      for (int i = 0; i < 4; ++i) {
+        if (ecol + i < kw) adam_commit<KEEP_G>(p, off + i, f4c(g, i), adam_fetch(p, off + i), step, sq2);
+      }
     }
   }
   if (foff >= 0) {
