@@ -556,6 +556,54 @@ int sactd3_qvalues(sactd3_engine* e, const float* obs, const float* actions, int
 /* host counters: out = {calls, rows, calls that inserted event waits, calls in the policy form (actions == NULL)} */
 int sactd3_qvalues_stats(const sactd3_engine* e, int64_t out[4]);
 
+/* ---- querying the policy on the device: the actor as a read path, beside ring rows (sactd3_rb_read_rows_device), Q-values
+ * (sactd3_qvalues_device) and TD errors (sactd3_td_errors_device).  For n >= 1 rows of observations the caller supplies, any n (worked
+ * through 1024 rows at a time on the learner stream: pack, the actor trunk in the pinned launch shape of sactd3_qvalues_device, one head
+ * kernel), whichever of these the caller asks for (float32, one rounding per written operation; sc / bi = action scale / bias):
+ *   mode         SAC tanh(mean) sc + bi, TD3 actor(s) -- the exploit action, the bits sactd3_predict(explore = 0) computes from the same
+ *                trunk output; any n, not only max_envs
+ *   mean, log_std   the pre-squash mean and log_std = -5 + 3.5 (tanh(raw) + 1) of the SAC head
+ *   sample, sample_logp   y sc + bi with y = tanh(mean + e exp(log_std)) and its log-density, e from `eps`, or -- eps == NULL -- from a
+ *                Philox stream of the call's own: counter words (policy_ctr, 0, 0x400, element >> 2), element = row a + j,
+ *                philox_normal's construction; policy_ctr is a device word of this feature that advances once per call that draws
+ *                natively.  No training or acting counter moves.  eps_out receives the draws used.
+ *   action_logp  log pi(actions_i | obs_i) through the inverse squash: v = (g - bi) / sc, c = clamp(v, -M, M), M = float32(1 - 1e-6),
+ *                x = 0.5 (logf(1 + c) - logf(1 - c)), sum_j [-(x - mean)^2 / (2 sd^2) - logf(sd) - 0.9189385 - logf(sc (1 - c c) + 1e-6)].
+ *                A row with a component outside [-M, M] is clamped and counted; a row with a NaN component gets a quiet NaN and is
+ *                counted; neither is an error and neither touches another output or row.
+ * Every pointer of sactd3_policy_io is a DEVICE pointer in the memory of the engine's device with a row stride in elements (>= the
+ * width), a contiguous inner dimension and 4-byte alignment; NULL = not given / not wanted, and a NULL output costs no store.  Each
+ * output is written inside its [n, width] window only.  TD3 knows `mode` alone (every other field NULL), from the online actor or
+ * -- SACTD3_PI_TARGET -- the target actor.
+ * Launch semantics are those of sactd3_qvalues_device: eager launches on the learner stream, ordered behind every update issued before
+ * the call, no copy command and no host wait; flags & SACTD3_SRC_ORDERED orders every given array against `caller_stream` in both
+ * directions.  A row's outputs are the same bits whatever n is.  The call is invisible to training and acting: scratch and control
+ * words of its own (made at the first call), no batch slot, no noise buffer, no acting scratch, no sample / noise / predict counter;
+ * a precomputed opening pair of sactd3_step_period stays valid, and the call is allowed while a sactd3_predict_begin call is in flight.
+ * SACTD3_EINVAL, before anything is launched and with the engine left usable: NULL `obs` or `io`, n < 1, no output set, action_logp
+ * without actions, eps or eps_out while neither sample nor sample_logp is wanted, a stride below the width, a pointer that is not memory
+ * of the engine's device, an unknown flag, `which` outside the two values, SACTD3_PI_TARGET on SAC, a SAC-only field on TD3. */
+#define SACTD3_PI_ONLINE 0
+#define SACTD3_PI_TARGET 1            /* TD3 only */
+typedef struct sactd3_policy_io {     /* device pointers; NULL = not given / not wanted; *_ld = row stride in elements */
+  const float* actions; int64_t actions_ld;   /* in : [n, a] actions to score            (SAC)            */
+  const float* eps;     int64_t eps_ld;       /* in : [n, a] standard normals for `sample` (SAC; NULL: native) */
+  float* mode;        int64_t mode_ld;        /* out: [n, a]                                               */
+  float* mean;        int64_t mean_ld;        /* out: [n, a] pre-squash mean               (SAC)           */
+  float* log_std;     int64_t log_std_ld;     /* out: [n, a]                               (SAC)           */
+  float* sample;      int64_t sample_ld;      /* out: [n, a]                               (SAC)           */
+  float* sample_logp; int64_t sample_logp_ld; /* out: [n]                                  (SAC)           */
+  float* action_logp; int64_t action_logp_ld; /* out: [n], needs `actions`                 (SAC)           */
+  float* eps_out;     int64_t eps_out_ld;     /* out: [n, a] the draws `sample` used       (SAC)           */
+} sactd3_policy_io;
+int sactd3_policy_device(sactd3_engine* e, const float* obs, int64_t obs_ld, int n, int which,
+                         const sactd3_policy_io* io, void* caller_stream, int flags /* SACTD3_SRC_ORDERED */);
+/* The same for host arrays, all contiguous ([n, a] / [n]; the *_ld fields are not read), staged a chunk at a time through device
+ * buffers of the engine's own; bit for bit the values of the device call.  [sync] */
+int sactd3_policy(sactd3_engine* e, const float* obs, int n, int which, const sactd3_policy_io* host_io);
+/* out = {calls, rows, rows clamped, rows with a NaN action}; the last two are counted on the device.  [sync] */
+int sactd3_policy_stats(sactd3_engine* e, int64_t out[4]);
+
 /* ---- TD3+BC (Fujimoto & Gu 2021): the behaviour-cloning actor term that lets the TD3 engine train on a FIXED dataset -- the workload
  * of the run-ahead modes (sactd3_step_period / sactd3_step_periods), which no ring append interrupts.  An engine created with
  * sactd3_config::bc_alpha > 0 (TD3 only: SACTD3_EINVAL with prefer_td3_over_sac == 0; NaN, infinite or negative: SACTD3_EINVAL) runs
@@ -595,7 +643,9 @@ int sactd3_sync(sactd3_engine* e);                                          /* [
  * "grad_critics", "c_dz1", "grad_actor", "a_dz1": SACTD3_ESTATE while the family's last writer was a period / cut-short period
  * graph, which leaves them out (see sactd3_step_period) -- stale gradients are not handed out.
  * "prio_leaf" [rb_capacity], "prio_sums" (the level above the leaves: one sum per 1024 slots), "prio_max" [1] and "prio_weights"
- * [batch_size] (the loss weights batch slot 0 carries, whichever call staged them): SACTD3_ESTATE before sactd3_prio_enable. */
+ * [batch_size] (the loss weights batch slot 0 carries, whichever call staged them): SACTD3_ESTATE before sactd3_prio_enable.
+ * "pi_z2" [m][256]: the actor trunk's output for the last chunk (m <= 1024 rows) of the last sactd3_policy* call, what its head kernel
+ * read; SACTD3_ESTATE before the first such call. */
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats);
 const char* sactd3_debug_names(void);
 /* number of kernel nodes in the instantiated graph of: 0 update_qnets, 1 update_actor, 2 step(do_actor=0), 3 step(do_actor=1), 4 step_period,
@@ -619,7 +669,9 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph);
  * write-back kernel on batch_size rows, indices as for "rows_to_fields", every priority 1: those rows' priorities are overwritten),
  * "batch_from_index_nstep" (the staging kernel of sactd3_rb_sample_nstep_device on batch_size rows with steps = 3, stride = 1: indices
  * as for "rows_to_fields", no weights, into the batch slot), "mix_draw" (the draw kernel of sactd3_rb_sample_mixed alone, with the current
- * P and m: the sample counter advances, the batch slot stays; SACTD3_ESTATE where sactd3_rb_sample_mixed is refused). [sync] */
+ * P and m: the sample counter advances, the batch slot stays; SACTD3_ESTATE where sactd3_rb_sample_mixed is refused), "pi_head" (the head
+ * kernel of sactd3_policy_device alone on 1024 rows of that call's scratch, every output wanted and written to the scratch, native
+ * draws; its counters are not touched). [sync] */
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec);
 /* Per-node device time of one fused iteration (sactd3_step with this do_actor; do_actor == 2: of one whole period as
  * sactd3_step_period captures it): every kernel launch of the sequence

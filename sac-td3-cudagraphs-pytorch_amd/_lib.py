@@ -18,6 +18,7 @@ ACT_AFTER_ALL = 1   # sactd3_predict_begin flags
 SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device / sactd3_predict_device / sactd3_qvalues_device / sactd3_rb_sample_indices_device / sactd3_batch_weights_device flags
 DST_ORDERED = 1     # sactd3_read_batch_device / sactd3_rb_read_rows_device / sactd3_td_errors_device flags (the same bit, the same two events)
 Q_ONLINE, Q_TARGET = 0, 1   # sactd3_qvalues / sactd3_qvalues_device `which`
+PI_ONLINE, PI_TARGET = 0, 1   # sactd3_policy / sactd3_policy_device `which` (the target actor: TD3 only)
 ESTATE, EINVAL = -3, -1
 DRAW_UNIFORM, DRAW_PRIORITIZED = 0, 1   # sactd3_sampling.draw
 DRAW_MIXED = 2                          # ... the mixed draw over pinned and live rows (sactd3_rb_pin / sactd3_rb_set_mix)
@@ -45,6 +46,7 @@ SYMBOLS = [
     "sactd3_step_periods", "sactd3_step_periods_stats",
     "sactd3_set_bc", "sactd3_get_bc",
     "sactd3_rb_pin", "sactd3_rb_pinned", "sactd3_rb_set_mix", "sactd3_rb_sample_mixed", "sactd3_mix_stats",
+    "sactd3_policy_device", "sactd3_policy", "sactd3_policy_stats",
 ]
 
 
@@ -74,6 +76,16 @@ class CDeviceFieldsOut(C.Structure):
 class CSampling(C.Structure):
     """sactd3_sampling: how sactd3_step_sampled draws and stages its batch"""
     _fields_ = [("draw", C.c_int32), ("n_step", C.c_int32), ("stride", C.c_int32), ("beta", C.c_float)]
+
+
+# the fields of sactd3_policy_io, in the header's order: two inputs, seven outputs; (name, width: "a" = ac_dim)
+POLICY_IO_FIELDS = (("actions", "a"), ("eps", "a"), ("mode", "a"), ("mean", "a"), ("log_std", "a"), ("sample", "a"),
+                    ("sample_logp", 1), ("action_logp", 1), ("eps_out", "a"))
+
+
+class CPolicyIO(C.Structure):
+    """sactd3_policy_io: nine pointers (None = not given / not wanted), each with its row stride in elements"""
+    _fields_ = [(n, t) for f, _ in POLICY_IO_FIELDS for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
 
 
 def library_path() -> str:
@@ -177,6 +189,9 @@ def load_library():
         "sactd3_rb_set_mix": (C.c_int, [vp, C.c_int]),
         "sactd3_rb_sample_mixed": (C.c_int, [vp]),
         "sactd3_mix_stats": (C.c_int, [vp, i64p]),
+        "sactd3_policy_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, C.POINTER(CPolicyIO), vp, C.c_int]),
+        "sactd3_policy": (C.c_int, [vp, fp, C.c_int, C.c_int, C.POINTER(CPolicyIO)]),
+        "sactd3_policy_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -677,6 +677,66 @@ class Agent:
         eng.q_values_device(obs_ptr, obs_ld, act_ptr, act_ld, n, target, q_ptr, q_ld, q_ns, _producer_stream(keep, eng.cfg.device_id))
         return out[:, :n] if out_rows > n else out
 
+    # Agent.policy's keys and the sactd3_policy_io outputs they are: (key, field, width: "a" = ac_dim)
+    _POLICY_KEYS = (("mode", "mode", "a"), ("mean", "mean", "a"), ("log_std", "log_std", "a"), ("sample", "sample", "a"),
+                    ("sample_log_prob", "sample_logp", 1), ("eps", "eps_out", "a"), ("log_prob", "action_logp", 1))
+
+    def policy(self, in_td: Mapping[str, Any], *, sample: bool = False, target: bool = False, eps: Any = None, out: Any = None) -> Dict[str, Any]:
+        """What the actor thinks of these rows (include/sactd3.h: sactd3_policy_device), any n, computed by the engine's own kernels
+        on `observations` [n, ob_dim] -> a dict of float32 arrays:
+            mode [n, ac_dim]                      the exploit action (what predict(explore=False) computes), always
+            mean, log_std [n, ac_dim]             the SAC head's pre-squash mean and log-std (SAC)
+            sample [n, ac_dim], sample_log_prob [n, 1], eps [n, ac_dim]
+                                                  with `sample=True` or `eps`: a sample, its log-density and the draws it used -- the
+                                                  given `eps`, or a stream of the query's own that no training or acting draw shares
+            log_prob [n, 1]                       with an `actions` key in `in_td`: log pi(a | s) of those actions under the policy
+        `target`: TD3's target actor.  Routed by where the data lives, as q_values is: arrays in the memory of the engine's device give
+        tensors on that device, nothing is copied and the host does not wait (ordered on the GPU against the caller's current stream);
+        host arrays give numpy arrays; a mix is a TypeError.  `out`: a mapping of preallocated float32 arrays or views of that device
+        under the keys above (the log-probs as [n, 1] or [n]).  Training and acting do not see the call."""
+        eng = self.engine
+        o, a = eng.cfg.ob_dim, eng.cfg.ac_dim
+        given = [("observations", in_td["observations"], o)] + ([("actions", in_td["actions"], a)] if "actions" in in_td else [])
+        given += [("eps", eps, a)] if eps is not None else []
+        given = [(k, _detached(x), w) for k, x, w in given]
+        names = {k for k, _, _ in given}
+        fields = eng.policy_outputs(bool(sample) or "eps" in names, "actions" in names)
+        keys = [(key, f, a if w == "a" else 1) for key, f, w in self._POLICY_KEYS if f in fields]
+        cais = [_cai(x) for _, x, _ in given]
+        if all(c is None for c in cais):                     # host data: numpy out
+            if out is not None:
+                raise TypeError("policy: `out` is for arrays in the memory of the engine's device (host arrays return numpy arrays)")
+            host = {k: _np(x) for k, x, _ in given}
+            got = eng.policy(host["observations"], host.get("actions"), host.get("eps"), sample, target)
+            return {key: got[f].reshape(-1, w) for key, f, w in keys}
+        if any(c is None for c in cais):
+            raise TypeError("policy: observations, actions and eps must all be host arrays or all be arrays in the memory of the engine's device")
+        if not getattr(eng, "device_inputs", False):
+            raise TypeError("policy: engine.device_inputs is off (pass host arrays)")
+        got = {}
+        for (key, x, width), cai in zip(given, cais):
+            if not _on_engine_device(eng, x):
+                raise TypeError(f"policy: `{key}` is not an array in the memory of the engine's device")
+            got[key] = _read_input(eng, x, width, "f4", cai)
+        rows = [g[2] for g in got.values()]
+        if len(set(rows)) != 1:
+            raise ValueError(f"policy: observations, actions and eps disagree on the number of rows: {rows}")
+        n = rows[0]
+        out = dict(out) if out else {}
+        if set(out) - {k for k, _, _ in keys}:
+            raise ValueError(f"policy: unknown output key(s) {sorted(set(out) - {k for k, _, _ in keys})}: this call fills {[k for k, _, _ in keys]}")
+        io = {k: (got[k][1], got[k][3]) for k in ("actions", "eps") if k in got}
+        res = {}
+        for key, f, w in keys:
+            x = out.get(key)
+            if x is None:
+                x = _torch_alloc(eng, "policy")((n, w), "f4")
+            ptr, _, ld = _read_output(eng, x, w, "f4", f"policy: `{key}`", n)
+            io[f], res[key] = (ptr, ld), x
+        keep = got["observations"][0]
+        eng.policy_device(got["observations"][1], got["observations"][3], n, io, target, _producer_stream(keep, eng.cfg.device_id))
+        return res
+
     def td_errors(self, out: Any = None):
         """The per-row TD errors of the most recent critic update (include/sactd3.h: sactd3_td_errors_device): Q_k(s_i, a_i) - y_i as
         the update itself computed them (its Bellman target, its policy draw), signed, per critic -> [2, batch_size, 1] float32 on

@@ -24,6 +24,7 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 #include "prio_kernels.h"
 #include "nstep_kernels.h"
 #include "mix_kernels.h"
+#include "policy_kernels.h"
 // All device code stands above.  The order of the template instances in the code object is pinned by this list, not by where the
 // host code below names them: a new instance is appended there.
 #include "kernel_instances.inc"
@@ -185,6 +186,17 @@ struct sactd3_engine {
   float *qs_x = nullptr, *qs_az1 = nullptr, *qs_az2 = nullptr, *qs_act = nullptr;
   float *qs_hq = nullptr, *qs_hobs = nullptr, *qs_hact = nullptr;      // sactd3_qvalues (host arrays): device staging of one chunk
   int64_t q_stats[4] = {};
+  // Querying the policy on caller-supplied rows (sactd3_policy_device; device code: policy_kernels.h).  Everything below is made at the
+  // first call -- an engine that never asks holds nothing more and launches nothing more than before.  pi_x / pi_z1 / pi_z2: packed
+  // observations and the actor trunk's two outputs for Q_CHUNK rows; pi_ctl[0]: the native draws' counter and the two row counters,
+  // pi_ctl[1]: the same words for sactd3_time_kernel("pi_head"), so that a timing run counts nothing; pi_h*: device staging of the host
+  // form; pi_time: the outputs of the timing run.  pi_rows: rows of the last chunk (what "pi_z2" holds; 0: no call yet).
+  // pi_stats: {calls, rows}.
+  float *pi_x = nullptr, *pi_z1 = nullptr, *pi_z2 = nullptr;
+  struct PiCtl* pi_ctl = nullptr;
+  float *pi_hobs = nullptr, *pi_hio = nullptr, *pi_time = nullptr;
+  int pi_rows = 0;
+  int64_t pi_stats[2] = {};
   // Training on caller-chosen rows with loss weights (sactd3_rb_sample_indices_device / sactd3_batch_weights_device): bs[0].w is made at
   // the first staging call -- an engine that never stages weights holds nothing more than before.  prio_stats: {index stagings, weight stagings,
   // td read-outs}; the fourth value of sactd3_priority_stats is DevCtl::priority_refused.
@@ -3292,6 +3304,168 @@ int sactd3_qvalues(sactd3_engine* e, const float* obs, const float* actions, int
 
 int sactd3_qvalues_stats(const sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::q_stats, out); }
 
+// ---- querying the policy on caller-supplied rows: the actor as a read path (include/sactd3.h; device code: policy_kernels.h).
+// Q_CHUNK rows at a time, three eager launches per chunk on the learner stream: pack -> actor trunk (pinned launch shape) -> k_pi_head,
+// which stores straight into the caller's arrays; a call that drew natively ends with one k_tick of the feature's own counter.  Like a
+// scoring call it writes its own scratch and its own words only: no CHAIN_BREAK, actor_dirty untouched, no batch slot / noise buffer /
+// p_* use, no sample / noise / predict counter.
+static int pi_scratch(sactd3_engine* e) {
+  if (e->pi_ctl) return 0;
+  RCCHK(dalloc(e, &e->pi_x, (size_t)Q_CHUNK * e->ldo));
+  RCCHK(dalloc(e, &e->pi_z1, (size_t)Q_CHUNK * HID));
+  RCCHK(dalloc(e, &e->pi_z2, (size_t)Q_CHUNK * HID));
+  RCCHK(dalloc(e, &e->pi_ctl, 2));
+  return 0;
+}
+// the head of a (narrow: see tail_rows_per_block) actor, in the form of the acting tail of the same head shape
+static int launch_pi_head(sactd3_engine* e, const PiHead& h) {
+  if (e->La.nh <= 8 && e->a <= 8) hipLaunchKernelGGL(k_pi_head_s, dim3((unsigned)((h.n + 3) / 4)), dim3(64), 0, e->stream, h);
+  else hipLaunchKernelGGL(k_pi_head, dim3((unsigned)((h.n + 15) / 16)), dim3(256), 0, e->stream, h);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// m rows from row `row0` of the arrays in `io`; `draw_row`: the row of the CALL that one is (it numbers the native draws)
+static PiHead pi_head_args(sactd3_engine* e, const float* P, PiCtl* pc, int m, int64_t row0, int64_t draw_row, const sactd3_policy_io& io) {
+  PiHead h{};
+  h.z2 = e->pi_z2; h.P = P; h.L = e->La; h.n = m; h.a = e->a; h.ln = e->cfg.layer_norm; h.sac = !e->cfg.prefer_td3_over_sac;
+  h.draw = (io.sample || io.sample_logp || io.eps_out) ? 1 : 0;
+  h.scale = e->scale; h.bias = e->bias; h.ctl = e->ctl; h.pc = pc; h.row0 = (long)draw_row;
+  auto at = [&](auto* p, int64_t ld) { return p ? p + row0 * ld : p; };
+  h.actions = at(io.actions, io.actions_ld); h.actions_ld = (long)io.actions_ld;
+  h.eps = at(io.eps, io.eps_ld); h.eps_ld = (long)io.eps_ld;
+  h.mode = at(io.mode, io.mode_ld); h.mode_ld = (long)io.mode_ld;
+  h.mean = at(io.mean, io.mean_ld); h.mean_ld = (long)io.mean_ld;
+  h.log_std = at(io.log_std, io.log_std_ld); h.log_std_ld = (long)io.log_std_ld;
+  h.sample = at(io.sample, io.sample_ld); h.sample_ld = (long)io.sample_ld;
+  h.sample_logp = at(io.sample_logp, io.sample_logp_ld); h.sample_logp_ld = (long)io.sample_logp_ld;
+  h.action_logp = at(io.action_logp, io.action_logp_ld); h.action_logp_ld = (long)io.action_logp_ld;
+  h.eps_out = at(io.eps_out, io.eps_out_ld); h.eps_out_ld = (long)io.eps_out_ld;
+  return h;
+}
+// n rows of `obs` and of every array of `io`; their row 0 is row `first` of the call (the host form hands over a chunk at a time)
+static int enqueue_policy(sactd3_engine* e, const float* obs, int64_t obs_ld, int64_t first, int n, int which, const sactd3_policy_io& io) {
+  EnqCtx x{e, e->stream};
+  TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
+  tk.pin_shape = true;
+  const float* P = which == SACTD3_PI_TARGET ? e->Ta : e->Pa;
+  for (int64_t r0 = 0; r0 < n; r0 += Q_CHUNK) {
+    const int m = (int)std::min<int64_t>(Q_CHUNK, n - r0);
+    RCCHK(launch_obs_pack(e, obs + r0 * obs_ld, obs_ld, e->pi_x, m));
+    const TrunkGrp ga{e->pi_x, P, e->pi_z1, e->pi_z2, nullptr, nullptr, nullptr};
+    RCCHK(enqueue_trunk(x, e->ldo, e->o, m, e->La, 0, 1, 1, &ga, tk));
+    RCCHK(launch_pi_head(e, pi_head_args(e, P, e->pi_ctl, m, r0, first + r0, io)));
+    e->pi_rows = m;
+  }
+  return 0;
+}
+static int pi_tick(sactd3_engine* e, const sactd3_policy_io& io) {      // behind the last chunk of a call that drew natively
+  if (!(io.sample || io.sample_logp || io.eps_out) || io.eps) return 0;
+  hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->pi_ctl->policy_ctr, (int*)nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// what both forms refuse, pointers aside
+static int policy_args(sactd3_engine* e, const char* what, int n, int which, const sactd3_policy_io& io) {
+  auto bad = [&](const char* why) { e->err = std::string(what) + ": " + why; return SACTD3_EINVAL; };
+  const bool td3 = e->cfg.prefer_td3_over_sac != 0;
+  if (n < 1) return bad("n >= 1");
+  if (which != SACTD3_PI_ONLINE && which != SACTD3_PI_TARGET) return bad("`which` is SACTD3_PI_ONLINE or SACTD3_PI_TARGET");
+  if (which == SACTD3_PI_TARGET && !td3) return bad("SAC has no target actor (SACTD3_PI_TARGET is TD3 only)");
+  if (!(io.mode || io.mean || io.log_std || io.sample || io.sample_logp || io.action_logp || io.eps_out)) return bad("no output is set");
+  if (td3 && (io.actions || io.eps || io.mean || io.log_std || io.sample || io.sample_logp || io.action_logp || io.eps_out))
+    return bad("TD3 has `mode` only (every other field must be NULL)");
+  if (io.action_logp && !io.actions) return bad("`action_logp` needs `actions`");
+  if ((io.eps || io.eps_out) && !(io.sample || io.sample_logp)) return bad("`eps` / `eps_out` without `sample` or `sample_logp`");
+  return 0;
+}
+
+int sactd3_policy_device(sactd3_engine* e, const float* obs, int64_t obs_ld, int n, int which, const sactd3_policy_io* io,
+                         void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!obs || !io) return e->fail(SACTD3_EINVAL, "policy_device: null argument");
+  USE_DEVICE(e);
+  RCCHK(policy_args(e, "policy_device", n, which, *io));
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "policy_device: unknown flag");
+  if (obs_ld < e->o) return e->fail(SACTD3_EINVAL, "policy_device: row stride of `obs` is below its width");
+  const FieldRow rows[9] = {
+      {io->actions, io->actions_ld, e->a, "actions"}, {io->eps, io->eps_ld, e->a, "eps"}, {io->mode, io->mode_ld, e->a, "mode"},
+      {io->mean, io->mean_ld, e->a, "mean"}, {io->log_std, io->log_std_ld, e->a, "log_std"}, {io->sample, io->sample_ld, e->a, "sample"},
+      {io->sample_logp, io->sample_logp_ld, 1, "sample_logp"}, {io->action_logp, io->action_logp_ld, 1, "action_logp"},
+      {io->eps_out, io->eps_out_ld, e->a, "eps_out"}};
+  RCCHK(device_ptr_check(e, obs, "policy_device", "obs"));
+  for (const FieldRow& r : rows) {
+    if (!r.p) continue;
+    if (r.ld < r.width) { e->err = std::string("policy_device: row stride of `") + r.name + "` is below its width"; return SACTD3_EINVAL; }
+    RCCHK(device_ptr_check(e, r.p, "policy_device", r.name));
+  }
+  RCCHK(pi_scratch(e));
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  RCCHK(enqueue_policy(e, obs, obs_ld, 0, n, which, *io));
+  RCCHK(pi_tick(e, *io));
+  RCCHK(src_order_end(e, caller, flags));
+  ++e->pi_stats[0]; e->pi_stats[1] += n;
+  return 0;
+}
+
+// the same for host arrays: a chunk at a time through device staging of the engine's own (made at the first call); the chunk's rows keep
+// their row numbers of the call, so the native draws are those of the device call
+int sactd3_policy(sactd3_engine* e, const float* obs, int n, int which, const sactd3_policy_io* hio) {
+  if (!e) return SACTD3_EINVAL;
+  if (!obs || !hio) return e->fail(SACTD3_EINVAL, "policy: null argument");
+  USE_DEVICE(e);
+  RCCHK(policy_args(e, "policy", n, which, *hio));
+  RCCHK(pi_scratch(e));
+  const int a = e->a;
+  if (!e->pi_hobs) {
+    RCCHK(dalloc(e, &e->pi_hobs, (size_t)Q_CHUNK * e->o, false));
+    RCCHK(dalloc(e, &e->pi_hio, (size_t)Q_CHUNK * (7 * a + 2), false));
+  }
+  // device staging of one chunk: [actions | eps | mode | mean | log_std | sample | eps_out] each [Q_CHUNK, a], then the two [Q_CHUNK] columns
+  float* const base = e->pi_hio;
+  auto slab = [&](int k) { return base + (size_t)k * Q_CHUNK * a; };
+  float* const lp_s = slab(7), * const lp_a = slab(7) + Q_CHUNK;
+  for (int64_t row0 = 0; row0 < n; row0 += Q_CHUNK) {
+    const int m = (int)std::min<int64_t>(Q_CHUNK, n - row0);
+    const size_t wide = sizeof(float) * (size_t)m * a;
+    HIPCHK(hipMemcpy(e->pi_hobs, obs + row0 * e->o, sizeof(float) * (size_t)m * e->o, hipMemcpyHostToDevice));
+    if (hio->actions) HIPCHK(hipMemcpy(slab(0), hio->actions + row0 * a, wide, hipMemcpyHostToDevice));
+    if (hio->eps) HIPCHK(hipMemcpy(slab(1), hio->eps + row0 * a, wide, hipMemcpyHostToDevice));
+    sactd3_policy_io d{};      // the chunk's staging, for the fields the caller gave / wants
+    auto staged = [](float* p, const void* wanted) -> float* { return wanted ? p : nullptr; };
+    d.actions = staged(slab(0), hio->actions); d.eps = staged(slab(1), hio->eps);
+    d.mode = staged(slab(2), hio->mode); d.mean = staged(slab(3), hio->mean);
+    d.log_std = staged(slab(4), hio->log_std); d.sample = staged(slab(5), hio->sample);
+    d.eps_out = staged(slab(6), hio->eps_out);
+    d.sample_logp = staged(lp_s, hio->sample_logp); d.action_logp = staged(lp_a, hio->action_logp);
+    d.actions_ld = d.eps_ld = d.mode_ld = d.mean_ld = d.log_std_ld = d.sample_ld = d.eps_out_ld = a;
+    d.sample_logp_ld = d.action_logp_ld = 1;
+    RCCHK(enqueue_policy(e, e->pi_hobs, e->o, row0, m, which, d));
+    if (row0 + m >= n) RCCHK(pi_tick(e, *hio));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    auto back = [&](float* dst, const float* src, int width) -> hipError_t {
+      return dst ? hipMemcpy(dst + row0 * width, src, sizeof(float) * (size_t)m * width, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIPCHK(back(hio->mode, slab(2), a)); HIPCHK(back(hio->mean, slab(3), a)); HIPCHK(back(hio->log_std, slab(4), a));
+    HIPCHK(back(hio->sample, slab(5), a)); HIPCHK(back(hio->eps_out, slab(6), a));
+    HIPCHK(back(hio->sample_logp, lp_s, 1)); HIPCHK(back(hio->action_logp, lp_a, 1));
+  }
+  ++e->pi_stats[0]; e->pi_stats[1] += n;
+  return 0;
+}
+
+int sactd3_policy_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int words[3] = {0, 0, 0};
+  if (e->pi_ctl) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(words, e->pi_ctl, sizeof(words), hipMemcpyDeviceToHost));
+  }
+  out[0] = e->pi_stats[0]; out[1] = e->pi_stats[1]; out[2] = words[1]; out[3] = words[2];
+  return 0;
+}
+
 int sactd3_acting_stats(const sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::act_stats, out); }
 
 int sactd3_read_metrics(sactd3_engine* e, float out[SACTD3_NUM_METRICS]) {
@@ -3374,7 +3548,7 @@ static std::vector<DbgEntry> dbg_table(sactd3_engine* e) {
 }
 const char* sactd3_debug_names(void) {
   return "X Xn Xp rew done logp_next logp_pi logp_alpha a_xh1 a_h1 a_z2 a_h2 a_xh2 a_rs2 a_tg a_du a_dz2 a_dh1 a_dz1 c_xh1 c_h1 c_z2 c_dz2 c_dh1 c_dz1 "
-         "t_z2 q q_target targ_q q_pi dA grad_actor grad_critics prio_leaf prio_sums prio_max prio_weights";
+         "t_z2 q q_target targ_q q_pi dA grad_actor grad_critics prio_leaf prio_sums prio_max prio_weights pi_z2";
 }
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
   if (!e || !name) return SACTD3_EINVAL;
@@ -3390,6 +3564,15 @@ int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_
     return n;
   }
   if (!strncmp(name, "prio_", 5)) return prio_debug_read(e, name, dst, max_floats);
+  if (!strcmp(name, "pi_z2")) {      // the last chunk of the last policy query
+    if (!e->pi_rows) return e->fail(SACTD3_ESTATE, "debug_read: no policy query has run (sactd3_policy_device first)");
+    const int64_t n = (int64_t)e->pi_rows * HID;
+    if (!dst) return n;
+    if (max_floats < n) return e->fail(SACTD3_EINVAL, "debug_read: buffer too small");
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(dst, e->pi_z2, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return n;
+  }
   for (const DbgEntry& d : dbg_table(e)) {
     if (strcmp(d.name, name)) continue;
     if (!dst) return d.n;
@@ -3486,6 +3669,22 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       if (!strcmp(kernel, "sa_from_fields")) return launch_sa_pack(e, e->ring, e->rec_f, e->ring + e->o, e->rec_f, m);
       return launch_q_head(e, e->Pc, m, e->qs_z1, 1, Q_CHUNK);
     }
+    // the head kernel of sactd3_policy_device alone on Q_CHUNK rows of its scratch: whatever z2 holds (zeros before the first call), the
+    // given actions zeros, native draws, every output into a scratch of this timing's own; its row counters are a second PiCtl's
+    if (!strcmp(kernel, "pi_head")) {
+      RCCHK(pi_scratch(e));
+      const int a = e->a;
+      if (!e->pi_time) RCCHK(dalloc(e, &e->pi_time, (size_t)Q_CHUNK * (6 * a + 2)));
+      auto slab = [&](int k) { return e->pi_time + (size_t)k * Q_CHUNK * a; };
+      sactd3_policy_io io{};
+      io.mode = slab(1); io.mode_ld = a;
+      if (!e->cfg.prefer_td3_over_sac) {
+        io.actions = slab(0); io.mean = slab(2); io.log_std = slab(3); io.sample = slab(4); io.eps_out = slab(5);
+        io.sample_logp = slab(6); io.action_logp = slab(6) + Q_CHUNK;
+        io.actions_ld = io.mean_ld = io.log_std_ld = io.sample_ld = io.eps_out_ld = a; io.sample_logp_ld = io.action_logp_ld = 1;
+      }
+      return launch_pi_head(e, pi_head_args(e, e->Pa, e->pi_ctl + 1, Q_CHUNK, 0, 0, io));
+    }
     // the TD read-out kernel: the TD errors of whatever e->q / e->y hold, written into the engine's own staging slab
     if (!strcmp(kernel, "td_to_field")) return launch_td_out(e, e->stage_dev, 1, e->B);
     // the draw kernel of sactd3_rb_sample_mixed alone (call form, the current P and m; the sample counter advances, the slot stays)
@@ -3521,7 +3720,7 @@ int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* u
       if (chain) { q.chain = true; q.steps = 3; q.stride = 1; }
       return stage_ring_rows(e, q);
     }
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update | batch_from_index_nstep | mix_draw)");
+    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update | batch_from_index_nstep | mix_draw | pi_head)");
   };
   if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index") || !strcmp(kernel, "prio_update") || !strcmp(kernel, "batch_from_index_nstep")) rc = time_rows_indices(e);
   for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up

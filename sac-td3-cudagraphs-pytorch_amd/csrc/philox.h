@@ -35,6 +35,7 @@ SACTD3_HD Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t 
 #define SACTD3_STREAM_FILL    0x200u   // synthetic buffer fill
 #define SACTD3_STREAM_NOISE   0x000u   // + site code
 #define SACTD3_STREAM_PRIO    0x300u   // prioritised replay draws (sactd3_rb_sample_prioritized)
+#define SACTD3_STREAM_POLICY  0x400u   // the samples of a policy query (sactd3_policy_device): a stream and a counter of its own
 
 // uniform index in [0, len): Lemire multiply-shift on one 32-bit word (bias <= len / 2^32)
 SACTD3_HD uint32_t philox_index(uint64_t seed, uint32_t ctr, uint32_t b, uint32_t len) {

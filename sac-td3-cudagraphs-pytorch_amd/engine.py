@@ -479,6 +479,57 @@ class Engine:
         """host counters of the scoring route (sactd3_qvalues_stats)"""
         return self._stats(self.lib.sactd3_qvalues_stats, ("calls", "rows", "ordered_calls", "policy_calls"))
 
+    def policy_outputs(self, sample: bool = False, actions: bool = False):
+        """the outputs of sactd3_policy_io a query of this engine's policy fills: `mode`; SAC also `mean`, `log_std`; with a sample
+        `sample`, `sample_logp`, `eps_out`; with given actions `action_logp`"""
+        if self.cfg.prefer_td3_over_sac:
+            return ("mode",)
+        return ("mode", "mean", "log_std") + (("sample", "sample_logp", "eps_out") if sample else ()) + (("action_logp",) if actions else ())
+
+    def policy_device(self, obs_ptr: int, obs_ld: int, n: int, fields, target: bool = False, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_policy_device: ask the actor about n observation rows that live in this device's memory.  `fields`: {name of a
+        sactd3_policy_io field: (device address, row stride in elements)} -- the inputs `actions` / `eps` and whichever outputs are
+        wanted (`mode`, `mean`, `log_std`, `sample`, `sample_logp`, `action_logp`, `eps_out`); a field left out is NULL.  `target`: the
+        target actor (TD3).  Asynchronous on the engine's stream behind the updates issued so far, no host wait, invisible to training
+        and acting.  `ordered` / `stream` as for q_values_device."""
+        io = _lib.CPolicyIO()
+        names = {f for f, _ in _lib.POLICY_IO_FIELDS}
+        for name, (ptr, ld) in dict(fields).items():
+            if name not in names:
+                raise ValueError(f"policy_device: unknown field `{name}` (expected a subset of {sorted(names)})")
+            setattr(io, name, int(ptr) or None)
+            setattr(io, name + "_ld", int(ld))
+        self._ck(self.lib.sactd3_policy_device(self._h, _vp(obs_ptr), int(obs_ld), int(n), _lib.PI_TARGET if target else _lib.PI_ONLINE,
+                                               C.byref(io), _vp(stream), _flag(_lib.SRC_ORDERED, ordered)))
+
+    def policy(self, obs, actions=None, eps=None, sample: bool = False, target: bool = False) -> Dict[str, np.ndarray]:
+        """sactd3_policy: the same for host rows -> {output name: float32 array}, [n, ac_dim] or [n] (the log-probs) -- the outputs
+        policy_outputs(sample or eps given, actions given) names.  Waits for the result; bit for bit what policy_device() leaves on
+        the device."""
+        obs = _f32(obs).reshape(-1, self.cfg.ob_dim)
+        n, a = obs.shape[0], self.cfg.ac_dim
+        io, keep = _lib.CPolicyIO(), {}
+        for name, x in (("actions", actions), ("eps", eps)):
+            if x is None:
+                continue
+            x = _f32(x).reshape(-1, a)
+            if x.shape[0] != n:
+                raise ValueError(f"observations and {name} disagree on the number of rows: {n}, {x.shape[0]}")
+            keep[name] = x
+            setattr(io, name, x.ctypes.data)
+            setattr(io, name + "_ld", a)
+        out = {}
+        for name in self.policy_outputs(bool(sample) or eps is not None, actions is not None):
+            out[name] = np.empty((n,) if name.endswith("_logp") else (n, a), np.float32)
+            setattr(io, name, out[name].ctypes.data)
+            setattr(io, name + "_ld", 1 if name.endswith("_logp") else a)
+        self._ck(self.lib.sactd3_policy(self._h, _fp(obs), n, _lib.PI_TARGET if target else _lib.PI_ONLINE, C.byref(io)))
+        return out
+
+    def policy_stats(self) -> Dict[str, int]:
+        """counters of the policy queries (sactd3_policy_stats); the last two are counted on the device: the call waits"""
+        return self._stats(self.lib.sactd3_policy_stats, ("calls", "rows", "rows_clamped", "rows_nan"))
+
     def rb_sample_indices_device(self, idx_ptr: int, idx_ld: int, w_ptr: int, w_ld: int, n: int, stream: int = 0, ordered: bool = True) -> None:
         """sactd3_rb_sample_indices_device: fill the batch slot with the ring records a device int64 array names (`idx_ptr`, stride
         `idx_ld` elements; n == batch_size) and the slot's loss weights from a device float32 array (`w_ptr`, `w_ld`; address 0: all 1).

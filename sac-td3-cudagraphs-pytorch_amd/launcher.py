@@ -246,16 +246,27 @@ def offline_plan(args):
     return dict(dataset=args.offline_dataset, num_updates=args.num_updates, bc_alpha=bc_alpha, plain=bc_alpha == 0.0)
 
 
+def policy_stats_plan(args) -> int:
+    """What --policy_stats N asks for, checked without touching a GPU.  -> N (0: off).  ValueError: a negative N, or N > 0 with --algo td3
+    (there is no SAC policy to ask: TD3's actor has no log-probability, entropy or log-std)."""
+    n = int(getattr(args, "policy_stats", 0) or 0)
+    if n < 0:
+        raise ValueError("--policy_stats must be >= 0")
+    if n > 0 and args.algo != "sac":
+        raise ValueError("--policy_stats needs --algo sac: TD3's deterministic actor has no log-probability, entropy or log-std to report")
+    return n
+
+
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
-            offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, **over):
+            offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
     `bc_alpha` in `over` turns the TD3+BC actor term on.
     `prior_fraction` beside `offline_dataset`: an online run on top of the dataset instead -- the ring is filled and its rows pinned
     (loop.load_dataset(pin=True)), then loop.train draws that share of every batch from them; `updates_per_step`: updates per
-    segment of any online run."""
+    segment of any online run; `policy_stats`: rows put to the policy at every evaluation (loop.PolicyStats; SAC only)."""
     import json
     import time
     from pathlib import Path
@@ -263,6 +274,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     import torch
     from . import loop
     from .agent import Agent, ReplayBuffer
+    if int(policy_stats) and algo != "sac":      # (before anything is built)
+        raise ValueError("policy_stats needs algo sac: TD3's deterministic actor has no log-probability, entropy or log-std to report")
     cfg = job_config(algo, env_id, seed, **over)
     o, a, bound = ENV_DIMS[env_id]
     if env_factory is None:   # no simulator in this image: the synthetic vector env has the task's shapes and the gymnasium protocol
@@ -291,12 +304,15 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
                              f"{env_id} has ({o},) / ({a},)")
         loop.load_dataset(agent, data, **(dict(pin=True) if prior_fraction is not None else {}))
     utd = dict(updates_per_step=int(updates_per_step)) if int(updates_per_step) != 1 else {}      # (a keyword only when it is used)
+    if int(policy_stats):
+        utd["policy_stats"] = int(policy_stats)
     if offline_dataset is not None and prior_fraction is not None:
         metrics = loop.train(cfg, env, agent, fused=False, evaluator=ev, overlap=overlap_acting, device_env=device_env,
                              one_launch=one_launch, prior_fraction=float(prior_fraction), **utd)
     elif offline_dataset is not None:
         metrics = loop.train_offline(cfg, agent, num_updates=int(num_updates if num_updates is not None else cfg.num_timesteps),
-                                     evaluator=ev, eval_every_updates=int(cfg.eval_every))
+                                     evaluator=ev, eval_every_updates=int(cfg.eval_every),
+                                     **(dict(policy_stats=int(policy_stats)) if int(policy_stats) else {}))
     else:
         metrics = loop.train(cfg, env, agent, fused=not prioritized and n_step == 1, evaluator=ev, overlap=overlap_acting, device_env=device_env,
                              prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch, **utd)
@@ -331,7 +347,7 @@ def _worker_main(args) -> int:
                           overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized,
                           n_step=args.n_step, one_launch=args.one_launch, offline_dataset=plan.get("dataset"),
                           num_updates=plan.get("num_updates"), bc_alpha=args.bc_alpha, prior_fraction=plan.get("prior_fraction"),
-                          updates_per_step=args.updates_per_step or 1)
+                          updates_per_step=args.updates_per_step or 1, policy_stats=policy_stats_plan(args))
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -378,6 +394,9 @@ def main(argv=None) -> int:
                          "round(F * batch_size) rows from them, the others from the rows the run appends (loop.train prior_fraction=...)")
     ap.add_argument("--updates_per_step", type=int, default=None, metavar="G",
                     help="any online run: G updates after each segment instead of one (loop.train updates_per_step=...)")
+    ap.add_argument("--policy_stats", type=int, default=0, metavar="N",
+                    help="SAC: at every evaluation put N ring rows to the policy and record vitals/replay_log_prob, vitals/policy_entropy "
+                         "and vitals/log_std_mean (loop.train policy_stats=...)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
@@ -385,6 +404,7 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     try:
         plan = offline_plan(args)
+        policy_stats_plan(args)
     except ValueError as ex:
         ap.error(str(ex))
     if args.worker:

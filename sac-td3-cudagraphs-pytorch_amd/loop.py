@@ -194,11 +194,42 @@ class ProportionalSampler:
         self.max_priority = self._torch.maximum(self.max_priority, new.max())
 
 
+class PolicyStats:
+    """`policy_stats=N` of train / train_offline: at every evaluation point N ring rows -- host-drawn slots from a generator of this
+    object's own, read where they are (`rb.rows`) -- are put to the policy with their stored actions and a native sample
+    (`agent.policy`).  -> vitals/replay_log_prob (mean log pi(a|s) of the stored actions: the behaviour-cloning diagnostic of a run on
+    prior data), vitals/policy_entropy (mean -log pi of fresh samples) and vitals/log_std_mean.  SAC only: ValueError otherwise, at
+    construction.  The query has a stream, a counter and a scratch of its own: the run's parameters, optimiser state, losses and
+    counters are bit for bit those of the run without it."""
+    KEYS = ("vitals/replay_log_prob", "vitals/policy_entropy", "vitals/log_std_mean")
+
+    def __init__(self, agent, n: int, seed: int = 0):
+        self.n = int(n)
+        if self.n < 0:
+            raise ValueError(f"policy_stats must be >= 0, got {n}")
+        if self.n and bool(agent.engine.cfg.prefer_td3_over_sac):
+            raise ValueError("policy_stats=... needs SAC: TD3's deterministic actor has no log-probability, entropy or log-std to report")
+        self.agent, self.rng, self.last = agent, np.random.default_rng([int(seed), 0x706F6C]), {}
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        rows = len(self.agent.rb) if self.n else 0
+        if rows == 0:
+            return {}
+        at = self.agent.rb.rows(self.rng.integers(0, rows, size=self.n, dtype=np.int64))
+        got = self.agent.policy({"observations": at["observations"], "actions": at["actions"]}, sample=True)
+        self.last = {"vitals/replay_log_prob": float(got["log_prob"].mean()), "vitals/policy_entropy": float(-got["sample_log_prob"].mean()),
+                     "vitals/log_std_mean": float(got["log_std"].mean())}
+        if tabular is not None:
+            for k, v in self.last.items():
+                tabular.record(k, v)
+        return self.last
+
+
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
           evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
           sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
           n_step: int = 1, one_launch: bool = False, prior_fraction: Optional[float] = None,
-          updates_per_step: int = 1) -> Dict[str, float]:
+          updates_per_step: int = 1, policy_stats: int = 0) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -223,7 +254,11 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     data -- every batch takes round(prior_fraction * batch_size) rows from the rows `agent.rb.pin()` protects (`load_dataset(...,
     pin=True)`) and the others from the rows the run appends (`rb.sample_mixed`); it counts as a reason for `one_launch=True`.
     `updates_per_step` (>= 1, every branch): the update-to-data ratio -- after each segment the update block runs that many times,
-    `i` and the update counters advancing per update; 1 is the reference's loop."""
+    `i` and the update counters advancing per update; 1 is the reference's loop.
+    `policy_stats=N` (default 0: off, and no call is made; SAC only): at every evaluation point N ring rows are put to the policy
+    (PolicyStats) and vitals/replay_log_prob, vitals/policy_entropy and vitals/log_std_mean are recorded with the evaluator's table
+    and returned with the last metrics; the run itself is bit for bit the run without it."""
+    pstats = PolicyStats(agent, policy_stats, cfg.seed) if policy_stats else None
     updates_per_step = int(updates_per_step)
     if updates_per_step < 1:
         raise ValueError(f"updates_per_step must be >= 1, got {updates_per_step}")
@@ -316,13 +351,15 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
         if agent.timesteps_so_far % cfg.eval_every == 0:
             if ro is not None:
                 ro.resolve()                                              # the evaluator / on_eval act (or load) with the same agent
+            if pstats is not None:
+                pstats(getattr(evaluator, "tabular", None))
             if evaluator is not None:
                 evaluator(agent)
             if on_eval is not None:
                 on_eval(agent, agent.timesteps_so_far)
     if ro is not None:
         ro.resolve()                                                      # leave no acting call in flight behind the loop
-    return agent.engine.read_metrics()
+    return dict(agent.engine.read_metrics(), **(pstats.last if pstats is not None else {}))
 
 
 _DATASET_KEYS = ("observations", "actions", "rewards", "next_observations", "terminations")
@@ -361,14 +398,17 @@ def load_dataset(agent, data, chunk: int = 65536, pin: bool = False) -> int:
 
 
 def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Evaluator"] = None,
-                  on_eval: Optional[Callable[[Any, int], None]] = None, eval_every_updates: Optional[int] = None) -> Dict[str, float]:
+                  on_eval: Optional[Callable[[Any, int], None]] = None, eval_every_updates: Optional[int] = None,
+                  policy_stats: int = 0) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
     `eval_every_updates` iterations; None: none before the end) and at `num_updates`.  `evaluator` and / or `on_eval(agent, updates
     done)` run at those points.  Keeps `qnet_updates_so_far` and `actor_updates_so_far` as Agent.iteration does and leaves
     `timesteps_so_far` alone (no env step was taken).  With plain TD3 or SAC this diverges on most datasets -- the actor climbs Q where
-    no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  Returns the last metrics."""
+    no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
+    only).  Returns the last metrics."""
+    pstats = PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0)) if policy_stats else None
     num_updates = int(num_updates)
     if num_updates < 0:
         raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
@@ -386,11 +426,13 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
         agent.actor_updates_so_far += delay * len(range(-(-i // period) * period, end, period))      # the iterations with i % period == 0
         i = end
         if i % every == 0 or i == num_updates:
+            if pstats is not None:
+                pstats(getattr(evaluator, "tabular", None))
             if evaluator is not None:
                 evaluator(agent)
             if on_eval is not None:
                 on_eval(agent, i)
-    return eng.read_metrics()
+    return dict(eng.read_metrics(), **(pstats.last if pstats is not None else {}))
 
 
 class Tabular:
