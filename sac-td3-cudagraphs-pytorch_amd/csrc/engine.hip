@@ -297,6 +297,20 @@ static int dalloc(sactd3_engine* e, T** p, size_t count, bool zero = true) {
   *p = (T*)v;
   return 0;
 }
+// THE allocation of state made after sactd3_create, at a feature's first use: nothing if *p exists (a call that failed half way keeps
+// what it had made), and a zero fill goes onto the learner stream -- a non-blocking one, which a null-stream fill is not ordered with --
+// so it stands in front of that stream's next launch.  Every caller runs in front of run_graph, never between the begin and the end
+// of a capture (the fill would become a node of the graph): keep it that way.
+template <class T>
+static int first_use_alloc(sactd3_engine* e, T** p, size_t count, bool zero = true) {
+  if (*p) return 0;
+  void* v = nullptr;
+  HIPCHK(hipMalloc(&v, std::max<size_t>(count, 4) * sizeof(T)));
+  e->dev_allocs.push_back(v);
+  if (zero) HIPCHK(hipMemsetAsync(v, 0, std::max<size_t>(count, 4) * sizeof(T), e->stream));
+  *p = (T*)v;
+  return 0;
+}
 template <class T>
 static int halloc(sactd3_engine* e, T** p, size_t count) {
   void* v = nullptr;
@@ -314,6 +328,9 @@ struct EnqCtx {
   sactd3_engine* e; hipStream_t s;
   const char* role = "";          // which part of the iteration is being enqueued (names the nodes)
   bool lean_stores = false;       // leave out the stores that only inspection reads (see sactd3_engine::grads_stale)
+  // The sequence is replayed as a graph while the ring grows (set by enqueue_graph for G_SAMPLED, nowhere else): the staging and priority
+  // launchers take the kernel instances that read what varies from device memory (prio_kernels.h: the graph forms)
+  bool graph_form = false;
   // a temperature step deferred into the next update's trunk launch ...
   AlphaArgs alpha{}; bool alpha_pending = false;
   bool alpha_tick_owed = false;   // ... across an ITERATION boundary (period graphs): its counter tick is owed until the next critic update's last kernel
@@ -343,14 +360,28 @@ static inline bool node_on(EnqCtx& x, const char* name, double flops, double byt
   }
   return x.node_only < 0 || x.node_only == k;
 }
+// THE launch: on the sequence's stream, with the one error check.  Every launch of the file goes through it (the launch_nt_* / launch_k_*
+// helpers aside, which are handed x.s) -- the feature layer plainly: its launches are not nodes of the registry ...
+#define LAUNCH_ON(kernel, grid, block, ...)                                 \
+  do {                                                                      \
+    hipLaunchKernelGGL(kernel, grid, block, 0, x.s, __VA_ARGS__);           \
+    const hipError_t _he = hipGetLastError();                               \
+    if (_he != hipSuccess) return x.e->fail(SACTD3_EHIP, "hipGetLastError()", _he); \
+  } while (0)
+// ... and the update path as a numbered node
 #define LAUNCH(name, flops, bytes, kernel, grid, block, ...)                 \
   do {                                                                      \
-    if (node_on(x, name, flops, bytes, grid, block)) {                      \
-      hipLaunchKernelGGL(kernel, grid, block, 0, x.s, __VA_ARGS__);         \
-      const hipError_t _he = hipGetLastError();                             \
-      if (_he != hipSuccess) return x.e->fail(SACTD3_EHIP, "hipGetLastError()", _he); \
-    }                                                                       \
+    if (node_on(x, name, flops, bytes, grid, block)) LAUNCH_ON(kernel, grid, block, __VA_ARGS__); \
   } while (0)
+// the two single-thread launches that many sequences end or begin with: a counter tick, two adjacent device words set
+static int launch_tick(EnqCtx& x, int* ctr) {
+  LAUNCH_ON(k_tick, dim3(1), dim3(1), ctr, (int*)nullptr);
+  return 0;
+}
+static int launch_set_int2(EnqCtx& x, int* dst, int v0, int v1) {
+  LAUNCH_ON(k_set_int2, dim3(1), dim3(1), dst, v0, v1);
+  return 0;
+}
 
 static inline dim3 tile_grid(int tiles, int nets) { return dim3((unsigned)((tiles + 3) / 4), 1, (unsigned)nets); }
 // blocks of 256 threads at `cpt` chunks per thread
@@ -428,8 +459,7 @@ static int launch_nt(EnqCtx& x, const char* name, int pro, bool fuse1, const NtA
   if (g.gblocks) by += (g.gblocks / std::max(g.gb_each, 1)) * 8.0 * (double)g.ga[0].B * 4 * (g.ga[0].cx + g.ga[0].cn + 1);
   if (pro == 0) {
     const dim3 grid((unsigned)(tiles_m * tiles_n), 1, (unsigned)nets);
-    if (!node_on(x, "k_nt_wide.layer1", fl, by, grid, dim3(256))) return 0;
-    hipLaunchKernelGGL(k_nt_wide, grid, dim3(256), 0, s, g);
+    LAUNCH("k_nt_wide.layer1", fl, by, k_nt_wide, grid, dim3(256), g);
   } else {
     const int tiles = tiles_m * tiles_n * nets;
     int ks = tiles >= 2 * e->num_cus ? 2 : 4;   // measured on 256 .. 4096-tile launches (KS = 1 never won)
@@ -864,10 +894,6 @@ static int enqueue_gather(EnqCtx& x, const float* ring, int identity_len) {
   // 2 B T + 4 B, T = 4 (2o + a + 1) + 1
   LAUNCH("k_gather", 0.0, 2.0 * e->B * (4.0 * (2 * e->o + e->a + 1) + 1.0) + 4.0 * e->B, k_gather, dim3(gather_blocks((long)e->B * e->rec4)), dim3(256), g);
   return 0;
-}
-static int gather_now(sactd3_engine* e, const float* ring, int identity_len) {      // (the API path: a sequence of this one launch)
-  EnqCtx x{e, e->stream};
-  return enqueue_gather(x, ring, identity_len);
 }
 
 static AdamArgs adam_args(sactd3_engine* e, float* p, const float* g, float* m, float* v, long n, const float* adam) {
@@ -1442,17 +1468,12 @@ static int actor_write_begin(sactd3_engine* e) {
   return 0;
 }
 
-static int set_flag(sactd3_engine* e, int* dst, int v) {
-  hipLaunchKernelGGL(k_set_int1, dim3(1), dim3(1), 0, e->stream, dst, v);
-  HIPCHK(hipGetLastError());
+static int set_flag(EnqCtx& x, int* dst, int v) {
+  LAUNCH_ON(k_set_int1, dim3(1), dim3(1), dst, v);
   return 0;
 }
 // ctl->rb_len and ctl->rb_cursor are adjacent ints
-static int publish_rb_state(sactd3_engine* e) {
-  hipLaunchKernelGGL(k_set_int2, dim3(1), dim3(1), 0, e->stream, &e->ctl->rb_len, (int)e->rb_len, (int)e->rb_cursor);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
+static int publish_rb_state(EnqCtx& x) { return launch_set_int2(x, &x.e->ctl->rb_len, (int)x.e->rb_len, (int)x.e->rb_cursor); }
 // THE cursor arithmetic of every append path (sactd3_rb_extend, _extend_device, _extend_fields_device).  With P = rb_pinned the
 // appends go round-robin over [P, cap): the ingest kernels take (ring, cursor, cap) as launch arguments and are told the ring advanced
 // by P records, the cursor relative to P and the region's size cap - P -- with P == 0 exactly what they were told before.
@@ -1476,15 +1497,12 @@ static RingSpan ring_append(sactd3_engine* e, int chunk) {
 // Launches of the staging calls (stage_ring_rows, in the replay-buffer part of the C ABI below) and of the engine-owned priorities
 // (device code: prio_kernels.h, nstep_kernels.h).  They stand in front of the extern "C" block, where a helper may be a template.
 static int slot_weights_alloc(sactd3_engine* e) {      // (never zeroed: every staging kernel writes all B entries before anything reads them)
-  return e->bs[0].w ? 0 : dalloc(e, &e->bs[0].w, (size_t)e->B, false);
+  return first_use_alloc(e, &e->bs[0].w, (size_t)e->B, false);
 }
 static int nstep_alloc(sactd3_engine* e) {
-  if (e->ns_ctr) return 0;
-  if (!e->ns_k) RCCHK(dalloc(e, &e->ns_k, (size_t)e->B));
-  if (!e->ns_last) RCCHK(dalloc(e, &e->ns_last, (size_t)e->B));
-  RCCHK(dalloc(e, &e->ns_ctr, 32));
-  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
-  return 0;
+  RCCHK(first_use_alloc(e, &e->ns_k, (size_t)e->B));
+  RCCHK(first_use_alloc(e, &e->ns_last, (size_t)e->B));
+  return first_use_alloc(e, &e->ns_ctr, 32);
 }
 // What k_batch_from_index and k_batch_from_index_nstep are both told (IndexBatchArgs and NstepArgs name these fields alike): the ring's
 // geometry, the index and weight sources, slot 0's arrays, the magic divisor.  Returns the gather's span: chunks per thread over
@@ -1500,22 +1518,21 @@ static long ring_rows_args(sactd3_engine* e, Args& g, const long long* idx, int6
   const unsigned blocks = gather_blocks(chunks);
   return (chunks + 256L * blocks - 1) / (256L * blocks);
 }
-// the 1-step kernel: it always writes the slot's weights (w == NULL: 1)
-// graph_form (here and in the launchers below): the launch is being captured into a graph that is replayed while the ring grows --
-// the kernel instance that reads what varies from device memory (prio_kernels.h: the graph forms)
-static int launch_batch_index(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, bool graph_form = false) {
+// the 1-step kernel: it always writes the slot's weights (w == NULL: 1).  (Here and in the launchers below: EnqCtx::graph_form picks
+// the kernel instance.)
+static int launch_batch_index(EnqCtx& x, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld) {
+  sactd3_engine* e = x.e;
   IndexBatchArgs g{};
   g.cpb = (int)ring_rows_args(e, g, idx, idx_ld, w, w_ld, e->bs[0].w);
   g.refused = &e->ctl->priority_refused;
   const dim3 grid(gather_blocks((long)e->B * e->rec4));
-  if (graph_form) hipLaunchKernelGGL(k_batch_from_index_g, grid, dim3(256), 0, e->stream, IndexBatchArgsG{g, e->ctl, (int)e->cfg.rb_capacity});
-  else hipLaunchKernelGGL(k_batch_from_index, grid, dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
+  if (x.graph_form) LAUNCH_ON(k_batch_from_index_g, grid, dim3(256), IndexBatchArgsG{g, e->ctl, (int)e->cfg.rb_capacity});
+  else LAUNCH_ON(k_batch_from_index, grid, dim3(256), g);
   return 0;
 }
 // idx == NULL: the uniform draw at the current sample counter; wdst: the slot's weight array, or NULL for a slot without weights
-static int launch_batch_nstep(sactd3_engine* e, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, float* wdst,
-                              int steps, int stride, bool graph_form = false) {
+static int launch_batch_nstep(EnqCtx& x, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld, float* wdst, int steps, int stride) {
+  sactd3_engine* e = x.e;
   NstepArgs g{};
   const long cpb_g = ring_rows_args(e, g, idx, idx_ld, w, w_ld, wdst);
   g.o = e->o; g.cursor = (int)e->rb_cursor; g.cap = (int)e->cfg.rb_capacity;
@@ -1527,25 +1544,25 @@ static int launch_batch_nstep(sactd3_engine* e, const long long* idx, int64_t id
   if ((256L * g.cpb) / e->rec4 + 2 > NS_ROWS) return e->fail(SACTD3_EINVAL, "n-step staging: the record is too short for the kernel's row tables");
   const unsigned blocks = (unsigned)((chunks + 256L * g.cpb - 1) / (256L * g.cpb));
   g.counters = e->ns_ctr;
-  if (graph_form) hipLaunchKernelGGL(k_batch_from_index_nstep_g, dim3(blocks), dim3(256), 0, e->stream, g);
-  else hipLaunchKernelGGL(k_batch_from_index_nstep, dim3(blocks), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
+  if (x.graph_form) LAUNCH_ON(k_batch_from_index_nstep_g, dim3(blocks), dim3(256), g);
+  else LAUNCH_ON(k_batch_from_index_nstep, dim3(blocks), dim3(256), g);
   return 0;
 }
-static int launch_batch_weights(sactd3_engine* e, const float* w, int64_t w_ld) {
+static int launch_batch_weights(EnqCtx& x, const float* w, int64_t w_ld) {
+  sactd3_engine* e = x.e;
   const WeightArgs g{w, (long)w_ld, e->bs[0].idx, e->bs[0].w, e->B, &e->ctl->priority_refused};
-  hipLaunchKernelGGL(k_batch_weights, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_batch_weights, dim3((unsigned)((e->B + 255) / 256)), dim3(256), g);
   return 0;
 }
-static int launch_td_out(sactd3_engine* e, float* td, int64_t td_ld, int64_t td_ns) {
+static int launch_td_out(EnqCtx& x, float* td, int64_t td_ld, int64_t td_ns) {
+  sactd3_engine* e = x.e;
   const TdArgs g{e->q, e->y, e->B, td, (long)td_ld, (long)td_ns};
-  hipLaunchKernelGGL(k_td_to_field, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_td_to_field, dim3((unsigned)((e->B + 255) / 256)), dim3(256), g);
   return 0;
 }
 // rows [first, first + n) of the ring, wrapping at the capacity, have just been written: they enter at the maximum priority
-static int prio_refresh(sactd3_engine* e, int64_t first, int64_t n) {
+static int prio_refresh(EnqCtx& x, int64_t first, int64_t n) {
+  sactd3_engine* e = x.e;
   const int64_t cap = e->cfg.rb_capacity;
   PrioRefreshArgs g{};
   g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.pc = e->pt_ctl; g.alpha = e->pt_alpha;
@@ -1555,37 +1572,35 @@ static int prio_refresh(sactd3_engine* e, int64_t first, int64_t n) {
   g.g0 = g.lo0 / PRIO_G; g.n0 = (g.hi0 - 1) / PRIO_G - g.g0 + 1;
   g.g1 = 0;
   const int n1 = g.hi1 > 0 ? (g.hi1 - 1) / PRIO_G + 1 : 0;
-  hipLaunchKernelGGL(k_prio_refresh, dim3((unsigned)(g.n0 + n1)), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_prio_refresh, dim3((unsigned)(g.n0 + n1)), dim3(256), g);
   e->pt_host[2] += n;
   return 0;
 }
 // (nothing is launched while priorities are off)
-static int prio_after_append(sactd3_engine* e, int64_t first, int64_t n) {
-  return (e->pt_on && n > 0) ? prio_refresh(e, first, n) : 0;
+static int prio_after_append(EnqCtx& x, int64_t first, int64_t n) {
+  return (x.e->pt_on && n > 0) ? prio_refresh(x, first, n) : 0;
 }
 // the two launches of a prioritised draw: slots and leaves, then weights (+ counter tick); the staging kernel follows (stage_ring_rows)
-static int prio_draw_launches(sactd3_engine* e, float beta, bool graph_form = false) {
+static int prio_draw_launches(EnqCtx& x, float beta) {
+  sactd3_engine* e = x.e;
   PrioDrawArgs d{};
   d.leaf4 = (const float4*)e->pt_leaf; d.sums4 = (const float4*)e->pt_sums;
   d.ngroups = e->pt_groups; d.nch = (e->pt_groups + PRIO_G - 1) / PRIO_G; d.len = (int)e->rb_len;
-  d.u_inj = (graph_form || e->pt_inject) ? e->pt_u : nullptr; d.ctl = e->ctl; d.pc = e->pt_ctl;
+  d.u_inj = (x.graph_form || e->pt_inject) ? e->pt_u : nullptr; d.ctl = e->ctl; d.pc = e->pt_ctl;
   d.idx_out = e->pt_idx; d.leaf_out = e->pt_dleaf; d.total_out = e->pt_total;
   const int cap = (int)e->cfg.rb_capacity;
-  if (graph_form) hipLaunchKernelGGL(k_prio_draw_g, dim3((unsigned)e->B), dim3(256), 0, e->stream, PrioDrawArgsG{d, cap});
-  else hipLaunchKernelGGL(k_prio_draw, dim3((unsigned)e->B), dim3(256), 0, e->stream, d);
-  HIPCHK(hipGetLastError());
+  if (x.graph_form) LAUNCH_ON(k_prio_draw_g, dim3((unsigned)e->B), dim3(256), PrioDrawArgsG{d, cap});
+  else LAUNCH_ON(k_prio_draw, dim3((unsigned)e->B), dim3(256), d);
   const PrioWeightArgs w{e->pt_idx, e->pt_dleaf, e->pt_total, e->pt_w, e->B, (float)e->rb_len, beta, e->pt_inject ? nullptr : &e->pt_ctl->draw_ctr};
-  if (graph_form) hipLaunchKernelGGL(k_prio_weights_g, dim3(1), dim3(256), 0, e->stream, PrioWeightArgsG{w, e->ctl, e->pt_ctl, cap});
-  else hipLaunchKernelGGL(k_prio_weights, dim3(1), dim3(256), 0, e->stream, w);
-  HIPCHK(hipGetLastError());
+  if (x.graph_form) LAUNCH_ON(k_prio_weights_g, dim3(1), dim3(256), PrioWeightArgsG{w, e->ctl, e->pt_ctl, cap});
+  else LAUNCH_ON(k_prio_weights, dim3(1), dim3(256), w);
   return 0;
 }
-static int launch_prio_update(sactd3_engine* e, PrioUpdateArgs g, bool graph_form = false) {
+static int launch_prio_update(EnqCtx& x, PrioUpdateArgs g) {
+  sactd3_engine* e = x.e;
   g.leaf = e->pt_leaf; g.sums = e->pt_sums; g.len = (int)e->rb_len; g.alpha = e->pt_alpha; g.eps = e->pt_eps; g.pc = e->pt_ctl;
-  if (graph_form) hipLaunchKernelGGL(k_prio_update_g, dim3((unsigned)g.n), dim3(256), 0, e->stream, PrioUpdateArgsG{g, e->ctl, (int)e->cfg.rb_capacity});
-  else hipLaunchKernelGGL(k_prio_update, dim3((unsigned)g.n), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
+  if (x.graph_form) LAUNCH_ON(k_prio_update_g, dim3((unsigned)g.n), dim3(256), PrioUpdateArgsG{g, e->ctl, (int)e->cfg.rb_capacity});
+  else LAUNCH_ON(k_prio_update, dim3((unsigned)g.n), dim3(256), g);
   return 0;
 }
 // the TD form of the write-back: the rows of batch slot `slot` and the TD errors of the critic update that ran on them
@@ -1595,17 +1610,10 @@ static PrioUpdateArgs prio_td_args(sactd3_engine* e, int slot) {
   return g;
 }
 
-// The replay-aware iteration (sactd3_step_sampled) as one linear sequence: what the calls
-//   sactd3_rb_sample_prioritized[_nstep] | sactd3_rb_sample_nstep -> sactd3_update_qnets -> [sactd3_prio_update_from_td] ->
-//   [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets
-// launch, launch for launch, with the staging and priority kernels in their graph forms.  (The 1-step uniform iteration is sactd3_step.)
 // ---- the mixed draw (device code: mix_kernels.h)
 static int mix_alloc(sactd3_engine* e) {
-  if (e->mix_ctl && e->mix_idx) return 0;
-  if (!e->mix_idx) RCCHK(dalloc(e, &e->mix_idx, (size_t)round_up(e->B, 4)));
-  if (!e->mix_ctl) RCCHK(dalloc(e, &e->mix_ctl, 1));
-  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
-  return 0;
+  RCCHK(first_use_alloc(e, &e->mix_idx, (size_t)round_up(e->B, 4)));
+  return first_use_alloc(e, &e->mix_ctl, 1);
 }
 // what a mixed draw needs of the ring, checked on the host, which knows len, P and m (NULL: nothing to refuse)
 static const char* mix_refusal(const sactd3_engine* e) {
@@ -1615,64 +1623,50 @@ static const char* mix_refusal(const sactd3_engine* e) {
   return nullptr;
 }
 // the device's copy of P and m, for the graph form: one single-thread launch, and only when a value changed
-static int mix_publish(sactd3_engine* e) {
+static int mix_publish(EnqCtx& x) {
+  sactd3_engine* e = x.e;
   if (e->mix_pub[0] == e->rb_pinned && e->mix_pub[1] == e->mix_m) return 0;
-  hipLaunchKernelGGL(k_set_int2, dim3(1), dim3(1), 0, e->stream, &e->mix_ctl->pinned, (int)e->rb_pinned, e->mix_m);
-  HIPCHK(hipGetLastError());
+  RCCHK(launch_set_int2(x, &e->mix_ctl->pinned, (int)e->rb_pinned, e->mix_m));
   e->mix_pub[0] = e->rb_pinned; e->mix_pub[1] = e->mix_m;
   return 0;
 }
 // the draw (it advances the sample counter itself) and the staging of the drawn slots: the two launches in front of the critic update
-static int launch_mix_draw(sactd3_engine* e, bool graph_form) {
+static int launch_mix_draw(EnqCtx& x) {
+  sactd3_engine* e = x.e;
   const MixDrawArgs d{e->ctl, e->mix_idx, e->B, (int)e->rb_len, (int)e->rb_pinned, e->mix_m};
-  if (graph_form) hipLaunchKernelGGL(k_mix_draw<true>, dim3(1), dim3(256), 0, e->stream, d, (const MixCtl*)e->mix_ctl, (int)e->cfg.rb_capacity);
-  else hipLaunchKernelGGL(k_mix_draw<false>, dim3(1), dim3(256), 0, e->stream, d, (const MixCtl*)nullptr, 0);
-  HIPCHK(hipGetLastError());
+  if (x.graph_form) LAUNCH_ON(k_mix_draw<true>, dim3(1), dim3(256), d, (const MixCtl*)e->mix_ctl, (int)e->cfg.rb_capacity);
+  else LAUNCH_ON(k_mix_draw<false>, dim3(1), dim3(256), d, (const MixCtl*)nullptr, 0);
   return 0;
 }
-static int mix_draw_launches(sactd3_engine* e, bool graph_form = false) {
-  RCCHK(launch_mix_draw(e, graph_form));
-  return launch_batch_index(e, e->mix_idx, 1, nullptr, 1, graph_form);
+static int mix_draw_launches(EnqCtx& x) {
+  RCCHK(launch_mix_draw(x));
+  return launch_batch_index(x, x.e->mix_idx, 1, nullptr, 1);
 }
 static inline void mix_count(sactd3_engine* e) { ++e->mix_stats[0]; e->mix_stats[1] += e->mix_m; e->mix_stats[2] += e->B - e->mix_m; }
 
+// The replay-aware iteration (sactd3_step_sampled) as one linear sequence: what the calls
+//   sactd3_rb_sample_prioritized[_nstep] | sactd3_rb_sample_nstep | sactd3_rb_sample_mixed -> sactd3_update_qnets ->
+//   [sactd3_prio_update_from_td] -> [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets
+// launch, launch for launch, with the staging and priority kernels in their graph forms.  (The 1-step uniform iteration is sactd3_step.)
 static int enqueue_step_sampled(EnqCtx& x, bool actor, bool targets) {
   sactd3_engine* e = x.e;
   const bool prio = e->ss_key[0] == SACTD3_DRAW_PRIORITIZED, mixed = e->ss_key[0] == SACTD3_DRAW_MIXED;
   const int steps = e->ss_key[1], stride = e->ss_key[2];
-  if (prio) RCCHK(prio_draw_launches(e, 0.f, true));
+  if (prio) RCCHK(prio_draw_launches(x, 0.f));
   const long long* idx = prio ? e->pt_idx : nullptr;
   const float* w = prio ? e->pt_w : nullptr;
-  if (mixed) RCCHK(mix_draw_launches(e, true));      // (unweighted, no chain; the draw kernel has advanced the sample counter)
-  else if (steps > 1) RCCHK(launch_batch_nstep(e, idx, 1, w, 1, prio ? e->bs[0].w : nullptr, steps, stride, true));
-  else RCCHK(launch_batch_index(e, idx, 1, w, 1, true));
-  if (!prio && !mixed) {      // the uniform draw was made at the sample counter, which now advances
-    hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, x.s, &e->ctl->sample_ctr, (int*)nullptr);
-    HIPCHK(hipGetLastError());
-  }
+  if (mixed) RCCHK(mix_draw_launches(x));      // (unweighted, no chain; the draw kernel has advanced the sample counter)
+  else if (steps > 1) RCCHK(launch_batch_nstep(x, idx, 1, w, 1, prio ? e->bs[0].w : nullptr, steps, stride));
+  else RCCHK(launch_batch_index(x, idx, 1, w, 1));
+  if (!prio && !mixed) RCCHK(launch_tick(x, &e->ctl->sample_ctr));      // the uniform draw was made at the sample counter, which now advances
   IterPlace it;
   it.weighted = prio;
   RCCHK(enqueue_update_qnets(x, it, false));
-  if (prio) RCCHK(launch_prio_update(e, prio_td_args(e, 0), true));
+  if (prio) RCCHK(launch_prio_update(x, prio_td_args(e, 0)));
   if (actor)
     for (int j = 0; j < e->cfg.actor_update_delay; ++j) RCCHK(enqueue_update_actor(x, IterPlace{}, 0, false));
   if (targets) RCCHK(enqueue_polyak(x, POLYAK_CRITICS | (e->cfg.prefer_td3_over_sac ? POLYAK_ACTOR : 0)));
   return 0;
-}
-
-static int64_t prio_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
-  const float* src = nullptr; int64_t n = 0;
-  if (e->pt_on && !strcmp(name, "prio_leaf")) { src = e->pt_leaf; n = e->cfg.rb_capacity; }
-  else if (e->pt_on && !strcmp(name, "prio_sums")) { src = e->pt_sums; n = e->pt_groups; }      // (the one level above the leaves)
-  else if (e->pt_on && !strcmp(name, "prio_max")) { src = &e->pt_ctl->max_prio; n = 1; }
-  else if (e->pt_on && !strcmp(name, "prio_weights")) { src = e->bs[0].w; n = e->B; }           // (the loss weights batch slot 0 carries)
-  else if (!strcmp(name, "prio_leaf") || !strcmp(name, "prio_sums") || !strcmp(name, "prio_max") || !strcmp(name, "prio_weights")) return e->fail(SACTD3_ESTATE, "debug_read: priorities are not enabled");
-  else return e->fail(SACTD3_EINVAL, "debug_read: unknown buffer name");
-  if (!dst) return n;
-  if (max_floats < n) return e->fail(SACTD3_EINVAL, "debug_read: buffer too small");
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost));
-  return n;
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
@@ -1971,11 +1965,24 @@ static void pack_record(const sactd3_engine* e, float* rec, const float* ob, con
   rec[e->ldc + e->ldo] = rw;
   rec[e->ldc + e->ldo + 1] = dn ? 1.f : 0.f;
 }
+// `chunk` packed records at `src` (pinned host memory or device memory) into the ring: one k_rb_ingest launch of at most max_blocks
+// blocks, which writes them round-robin (wrapping at capacity) and publishes the new length / cursor
+static int launch_ingest(EnqCtx& x, const float* src, int chunk, long max_blocks) {
+  sactd3_engine* e = x.e;
+  IngestArgs g{};
+  const RingSpan sp = ring_append(e, chunk);
+  g.src = (const float4*)src; g.ring = sp.ring; g.rec4 = e->rec4; g.n = chunk; g.cursor = sp.cursor; g.cap = sp.cap;
+  g.len_cursor = &e->ctl->rb_len; g.new_len = sp.new_len; g.new_cursor = sp.new_cursor;
+  const int blocks = (int)std::min<long>(max_blocks, ((long)chunk * e->rec4 + 255) / 256);
+  LAUNCH_ON(k_rb_ingest, dim3(std::max(blocks, 1)), dim3(256), g);
+  return prio_after_append(x, sp.first, chunk);
+}
 
 int sactd3_rb_extend(sactd3_engine* e, const float* obs, const float* act, const float* rew, const float* nobs, const uint8_t* dones, int n) {
   if (!e || !obs || !act || !rew || !nobs || !dones || n < 0) return e ? e->fail(SACTD3_EINVAL, "rb_extend: bad argument") : SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
+  EnqCtx x{e, e->stream};
   int done_rows = 0;
   while (done_rows < n) {
     const int chunk = (int)std::min<int64_t>(std::min(n - done_rows, e->stage_rows), ring_region(e));
@@ -1988,16 +1995,7 @@ int sactd3_rb_extend(sactd3_engine* e, const float* obs, const float* act, const
       const int r = done_rows + i;
       pack_record(e, st + (size_t)i * e->rec_f, obs + (size_t)r * e->o, act + (size_t)r * e->a, rew[r], nobs + (size_t)r * e->o, dones[r]);
     }
-    // one launch: the kernel reads the staged rows from pinned host memory, writes them round-robin into the ring
-    // (wrapping at capacity) and publishes the new length / cursor
-    IngestArgs g{};
-    const RingSpan sp = ring_append(e, chunk);
-    g.src = (const float4*)st; g.ring = sp.ring; g.rec4 = e->rec4; g.n = chunk; g.cursor = sp.cursor; g.cap = sp.cap;
-    g.len_cursor = &e->ctl->rb_len; g.new_len = sp.new_len; g.new_cursor = sp.new_cursor;
-    const int blocks = (int)std::min<long>(256, ((long)chunk * e->rec4 + 255) / 256);
-    hipLaunchKernelGGL(k_rb_ingest, dim3(std::max(blocks, 1)), dim3(256), 0, e->stream, g);
-    HIPCHK(hipGetLastError());
-    RCCHK(prio_after_append(e, sp.first, chunk));
+    RCCHK(launch_ingest(x, st, chunk, 256));      // (the kernel reads the staged rows from pinned host memory)
     done_rows += chunk;
   }
   return 0;
@@ -2020,18 +2018,11 @@ int sactd3_rb_extend_device(sactd3_engine* e, const float* records, int n) {
     (void)hipGetLastError();
     return e->fail(SACTD3_EINVAL, "rb_extend_device: `records` is not a device pointer");
   }
+  EnqCtx x{e, e->stream};
   int done_rows = 0;
   while (done_rows < n) {
     const int chunk = (int)std::min<int64_t>(n - done_rows, ring_region(e));
-    IngestArgs g{};
-    const RingSpan sp = ring_append(e, chunk);
-    g.src = (const float4*)(records + (size_t)done_rows * e->rec_f); g.ring = sp.ring; g.rec4 = e->rec4; g.n = chunk;
-    g.cursor = sp.cursor; g.cap = sp.cap;
-    g.len_cursor = &e->ctl->rb_len; g.new_len = sp.new_len; g.new_cursor = sp.new_cursor;
-    const int blocks = (int)std::min<long>(1024, ((long)chunk * e->rec4 + 255) / 256);
-    hipLaunchKernelGGL(k_rb_ingest, dim3(std::max(blocks, 1)), dim3(256), 0, e->stream, g);
-    HIPCHK(hipGetLastError());
-    RCCHK(prio_after_append(e, sp.first, chunk));
+    RCCHK(launch_ingest(x, records + (size_t)done_rows * e->rec_f, chunk, 1024));
     done_rows += chunk;
   }
   return 0;
@@ -2045,10 +2036,9 @@ int sactd3_rb_sample(sactd3_engine* e) {
   CHAIN_BREAK(e);
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_sample: buffer is empty");
   slot_refilled(e, false, false);
-  RCCHK(gather_now(e, e->ring, -1));
-  hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
-  HIPCHK(hipGetLastError());
-  return 0;
+  EnqCtx x{e, e->stream};
+  RCCHK(enqueue_gather(x, e->ring, -1));
+  return launch_tick(x, &e->ctl->sample_ctr);
 }
 
 int sactd3_rb_sample_with_indices(sactd3_engine* e, const int64_t* idx, int n) {
@@ -2064,9 +2054,10 @@ int sactd3_rb_sample_with_indices(sactd3_engine* e, const int64_t* idx, int n) {
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipMemcpy(e->idx, h.data(), sizeof(int) * n, hipMemcpyHostToDevice));
   slot_refilled(e, false, false);
-  RCCHK(set_flag(e, &e->ctl->inject_idx, 1));
-  RCCHK(gather_now(e, e->ring, -1));
-  return set_flag(e, &e->ctl->inject_idx, 0);
+  EnqCtx x{e, e->stream};
+  RCCHK(set_flag(x, &e->ctl->inject_idx, 1));
+  RCCHK(enqueue_gather(x, e->ring, -1));
+  return set_flag(x, &e->ctl->inject_idx, 0);
 }
 
 int sactd3_load_batch(sactd3_engine* e, const float* obs, const float* act, const float* rew, const float* nobs, const uint8_t* dones, int n) {
@@ -2083,9 +2074,10 @@ int sactd3_load_batch(sactd3_engine* e, const float* obs, const float* act, cons
   }
   HIPCHK(hipMemcpy(e->stage_dev, e->h_batch, sizeof(float) * (size_t)n * e->rec_f, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(e->idx, h.data(), sizeof(int) * n, hipMemcpyHostToDevice));
-  RCCHK(set_flag(e, &e->ctl->inject_idx, 1));
-  RCCHK(gather_now(e, e->stage_dev, n));
-  return set_flag(e, &e->ctl->inject_idx, 0);
+  EnqCtx x{e, e->stream};
+  RCCHK(set_flag(x, &e->ctl->inject_idx, 1));
+  RCCHK(enqueue_gather(x, e->stage_dev, n));
+  return set_flag(x, &e->ctl->inject_idx, 0);
 }
 
 // ---- the device boundary: the caller's five arrays are already in this device's memory (include/sactd3.h)
@@ -2101,7 +2093,8 @@ static int device_ptr_check(sactd3_engine* e, const void* p, const char* what, c
 }
 // one row per field of a caller's field block.  Inputs (`required`): a NULL pointer is refused; outputs: it is a field not wanted
 struct FieldRow { const void* p; int64_t ld; int width; const char* name; };
-static int field_rows_check(sactd3_engine* e, const FieldRow* rows, int count, bool required, const char* what) {
+// none_wanted: the refusal when every pointer of an output block is NULL (NULL: the caller has its own rule for that)
+static int field_rows_check(sactd3_engine* e, const FieldRow* rows, int count, bool required, const char* what, const char* none_wanted) {
   int wanted = 0;
   for (const FieldRow* x = rows; x != rows + count; ++x) {
     if (!x->p && !required) continue;
@@ -2110,29 +2103,31 @@ static int field_rows_check(sactd3_engine* e, const FieldRow* rows, int count, b
     if (x->ld < x->width) { e->err = std::string(what) + ": row stride of `" + x->name + "` is below its width"; return SACTD3_EINVAL; }
     RCCHK(device_ptr_check(e, x->p, what, x->name));
   }
-  if (!wanted) { e->err = std::string(what) + ": all six destinations (obs, actions, rewards, next_obs, dones, index) are NULL"; return SACTD3_EINVAL; }
+  if (!wanted && none_wanted) { e->err = std::string(what) + ": " + none_wanted; return SACTD3_EINVAL; }
   return 0;
 }
 static int fields_check(sactd3_engine* e, const sactd3_device_fields* f, const char* what) {
   const FieldRow rows[5] = {
       {f->obs, f->obs_ld, e->o, "obs"}, {f->actions, f->actions_ld, e->a, "actions"}, {f->rewards, f->rewards_ld, 1, "rewards"},
       {f->next_obs, f->next_obs_ld, e->o, "next_obs"}, {f->dones, f->dones_ld, 1, "dones"}};
-  return field_rows_check(e, rows, 5, true, what);
+  return field_rows_check(e, rows, 5, true, what, nullptr);
 }
-// the *_stats getters: four host counters; or three and one the kernels keep on the device, read behind a stream sync
+// the *_stats getters: four host counters; or host counters and words the kernels keep on the device (stats_with_words)
 static int host_stats(const sactd3_engine* e, int64_t (sactd3_engine::*stats)[4], int64_t out[4]) {
   if (!e || !out) return SACTD3_EINVAL;
   for (int i = 0; i < 4; ++i) out[i] = (e->*stats)[i];
   return 0;
 }
-static int stats_with_refused(sactd3_engine* e, int64_t (sactd3_engine::*stats)[3], int DevCtl::*refused_word, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
+// out[at, at + nw) = the nw adjacent device words at `words`, read behind a stream sync -- or 0 where the feature's state does not exist
+// yet (words == NULL); the other entries = the 4 - nw host counters, in their order
+static int stats_with_words(sactd3_engine* e, const int64_t* host, const int* words, int nw, int at, int64_t out[4]) {
   USE_DEVICE(e);
-  int refused = 0;
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(&refused, &(e->ctl->*refused_word), sizeof(int), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 3; ++i) out[i] = (e->*stats)[i];
-  out[3] = refused;
+  int w[4] = {0, 0, 0, 0};
+  if (words) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(w, words, sizeof(int) * nw, hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 4; ++i) out[i] = (i >= at && i < at + nw) ? w[i - at] : *host++;
   return 0;
 }
 static FieldSrc field_src(const sactd3_engine* e, const sactd3_device_fields* f, int64_t row0) {
@@ -2160,23 +2155,23 @@ static int src_order_end(sactd3_engine* e, hipStream_t producer, int flags) {
   ++e->bnd_stats[3];
   return 0;
 }
-static int launch_ingest_fields(sactd3_engine* e, const FieldSrc& src, int chunk) {
+static int launch_ingest_fields(EnqCtx& x, const FieldSrc& src, int chunk) {
+  sactd3_engine* e = x.e;
   IngestFieldsArgs g{};
   const RingSpan sp = ring_append(e, chunk);
   g.ring = sp.ring; g.rec4 = e->rec4; g.n = chunk; g.cursor = sp.cursor; g.cap = sp.cap;
   g.len_cursor = &e->ctl->rb_len; g.new_len = sp.new_len; g.new_cursor = sp.new_cursor;
   const long chunks = (long)chunk * e->rec4;
-  hipLaunchKernelGGL(k_rb_ingest_fields, dim3(cpt_blocks(chunks, FIELDS_CPT)), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
-  HIPCHK(hipGetLastError());
-  return prio_after_append(e, sp.first, chunk);
+  LAUNCH_ON(k_rb_ingest_fields, dim3(cpt_blocks(chunks, FIELDS_CPT)), dim3(256), FIELD_ARGS(src), g);
+  return prio_after_append(x, sp.first, chunk);
 }
-static int launch_batch_fields(sactd3_engine* e, const FieldSrc& src) {
+static int launch_batch_fields(EnqCtx& x, const FieldSrc& src) {
+  sactd3_engine* e = x.e;
   const sactd3_engine::BatchSlot& S = e->bs[0];
   BatchFieldsArgs g{};
   g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.idx = S.idx; g.B = e->B;
   const long chunks = (long)e->B * (e->cx + e->cn + 1);      // (< B * rec4 < 2^31: create_impl)
-  hipLaunchKernelGGL(k_batch_from_fields, dim3(cpt_blocks(chunks, FIELDS_CPT)), dim3(256), 0, e->stream, FIELD_ARGS(src), g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_batch_from_fields, dim3(cpt_blocks(chunks, FIELDS_CPT)), dim3(256), FIELD_ARGS(src), g);
   return 0;
 }
 
@@ -2190,10 +2185,11 @@ int sactd3_rb_extend_fields_device(sactd3_engine* e, const sactd3_device_fields*
   RCCHK(fields_check(e, f, "rb_extend_fields_device"));
   const hipStream_t producer = (hipStream_t)producer_stream;
   const int64_t per_launch = std::min<int64_t>(ring_region(e), ((1ll << 31) - 1) / e->rec4);
+  EnqCtx x{e, e->stream};
   if (n > 0) RCCHK(src_order_begin(e, producer, flags));
   for (int done_rows = 0; done_rows < n;) {
     const int chunk = (int)std::min<int64_t>(n - done_rows, per_launch);
-    RCCHK(launch_ingest_fields(e, field_src(e, f, done_rows), chunk));
+    RCCHK(launch_ingest_fields(x, field_src(e, f, done_rows), chunk));
     done_rows += chunk;
   }
   if (n > 0) RCCHK(src_order_end(e, producer, flags));
@@ -2213,7 +2209,8 @@ int sactd3_load_batch_device(sactd3_engine* e, const sactd3_device_fields* f, in
   const hipStream_t producer = (hipStream_t)producer_stream;
   RCCHK(src_order_begin(e, producer, flags));
   slot_refilled(e, false, false);
-  RCCHK(launch_batch_fields(e, field_src(e, f, 0)));
+  EnqCtx x{e, e->stream};
+  RCCHK(launch_batch_fields(x, field_src(e, f, 0)));
   RCCHK(src_order_end(e, producer, flags));
   ++e->bnd_stats[2];
   return 0;
@@ -2250,7 +2247,7 @@ static int fields_out_check(sactd3_engine* e, const sactd3_device_fields_out* f,
   const FieldRow rows[6] = {
       {f->obs, f->obs_ld, e->o, "obs"}, {f->actions, f->actions_ld, e->a, "actions"}, {f->rewards, f->rewards_ld, 1, "rewards"},
       {f->next_obs, f->next_obs_ld, e->o, "next_obs"}, {f->dones, f->dones_ld, 1, "dones"}, {f->index, f->index_ld, 1, "index"}};
-  return field_rows_check(e, rows, 6, false, what);
+  return field_rows_check(e, rows, 6, false, what, "all six destinations (obs, actions, rewards, next_obs, dones, index) are NULL");
 }
 static FieldDst field_dst(const sactd3_engine* e, const sactd3_device_fields_out* f, int64_t row0) {
   FieldDst d{};
@@ -2262,16 +2259,17 @@ static FieldDst field_dst(const sactd3_engine* e, const sactd3_device_fields_out
   d.o = e->o; d.a = e->a; d.cx = e->cx; d.cn = e->cn;
   return d;
 }
-static int launch_batch_out(sactd3_engine* e, const FieldDst& dst) {
+static int launch_batch_out(EnqCtx& x, const FieldDst& dst) {
+  sactd3_engine* e = x.e;
   const sactd3_engine::BatchSlot& S = e->bs[e->slot.cur];      // the slot sactd3_read_batch reports
   const BatchOutArgs g{(const float4*)S.X, (const float4*)S.Xn, S.rew, S.done, S.idx, e->B};
   const long chunks = (long)e->B * (e->cx + e->cn + 1);      // (< B * rec4 < 2^31: create_impl)
-  hipLaunchKernelGGL(k_batch_to_fields, dim3(cpt_blocks(chunks, TOFIELDS_CPT)), dim3(256), 0, e->stream, dst, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_batch_to_fields, dim3(cpt_blocks(chunks, TOFIELDS_CPT)), dim3(256), dst, g);
   return 0;
 }
 // rows [0, n) of `idx` (n * rec4 < 2^31), `len` = the ring length the indices are checked against
-static int launch_rows_out(sactd3_engine* e, const FieldDst& dst, const long long* idx, int64_t idx_ld, int n, int len) {
+static int launch_rows_out(EnqCtx& x, const FieldDst& dst, const long long* idx, int64_t idx_ld, int n, int len) {
+  sactd3_engine* e = x.e;
   RowsOutArgs g{};
   g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.n = n; g.len = len; g.idx = idx; g.idx_ld = (long)idx_ld;
   const long chunks = (long)n * e->rec4;
@@ -2279,8 +2277,7 @@ static int launch_rows_out(sactd3_engine* e, const FieldDst& dst, const long lon
   const unsigned blocks = gather_blocks(chunks);
   g.cpb = (int)((chunks + 256L * blocks - 1) / (256L * blocks));
   g.refused = &e->ctl->readout_refused;
-  hipLaunchKernelGGL(k_rows_to_fields, dim3(blocks), dim3(256), 0, e->stream, dst, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_rows_to_fields, dim3(blocks), dim3(256), dst, g);
   return 0;
 }
 
@@ -2294,8 +2291,9 @@ int sactd3_read_batch_device(sactd3_engine* e, const sactd3_device_fields_out* f
   if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "read_batch_device: unknown flag");
   RCCHK(fields_out_check(e, f, "read_batch_device"));
   const hipStream_t consumer = (hipStream_t)consumer_stream;
+  EnqCtx x{e, e->stream};
   RCCHK(src_order_begin(e, consumer, flags));
-  RCCHK(launch_batch_out(e, field_dst(e, f, 0)));
+  RCCHK(launch_batch_out(x, field_dst(e, f, 0)));
   RCCHK(src_order_end(e, consumer, flags));
   ++e->ro_stats[0];
   return 0;
@@ -2316,10 +2314,11 @@ int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "rb_read_rows_device: buffer is empty");
   const hipStream_t consumer = (hipStream_t)consumer_stream;
   const int64_t per_launch = ((1ll << 31) - 1) / e->rec4;
+  EnqCtx x{e, e->stream};
   RCCHK(src_order_begin(e, consumer, flags));
   for (int done_rows = 0; done_rows < n;) {
     const int chunk = (int)std::min<int64_t>(n - done_rows, per_launch);
-    RCCHK(launch_rows_out(e, field_dst(e, f, done_rows), (const long long*)idx + (int64_t)done_rows * idx_ld, idx_ld, chunk, (int)e->rb_len));
+    RCCHK(launch_rows_out(x, field_dst(e, f, done_rows), (const long long*)idx + (int64_t)done_rows * idx_ld, idx_ld, chunk, (int)e->rb_len));
     done_rows += chunk;
   }
   RCCHK(src_order_end(e, consumer, flags));
@@ -2327,7 +2326,7 @@ int sactd3_rb_read_rows_device(sactd3_engine* e, const int64_t* idx, int64_t idx
   return 0;
 }
 
-int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]) { return stats_with_refused(e, &sactd3_engine::ro_stats, &DevCtl::readout_refused, out); }
+int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]) { return (!e || !out) ? SACTD3_EINVAL : stats_with_words(e, e->ro_stats, &e->ctl->readout_refused, 1, 3, out); }
 
 // ---- ring rows into batch slot 0, all on the device (include/sactd3.h): the caller's rows or the engine's draw, one row each or chained
 // into n-step returns, with or without loss weights.  One request, one routine; the entry points below only fill the request in.
@@ -2350,7 +2349,8 @@ struct StageReq {
 //   2. CHAIN_BREAK                     3. allocations at first use (slot weights, n-step arrays)      4. src_order_begin
 //   5. the launches, on the learner stream: [k_prio_draw, k_prio_weights,] the staging kernel [, k_tick of the sample counter behind a uniform draw]
 //   6. src_order_end                   7. slot_refilled                                               8. the host counters
-static int stage_ring_rows(sactd3_engine* e, const StageReq& q) {
+static int stage_ring_rows(EnqCtx& x, const StageReq& q) {
+  sactd3_engine* e = x.e;
   const auto refuse = [&](int code, const char* what) { e->err = std::string(q.name) + ": " + what; return code; };
   const bool callers = q.draw == DRAW_NONE;
   if (callers) {
@@ -2377,16 +2377,13 @@ static int stage_ring_rows(sactd3_engine* e, const StageReq& q) {
   const hipStream_t caller = (hipStream_t)q.caller_stream;
   RCCHK(src_order_begin(e, caller, q.flags));
   const bool prio = q.draw == DRAW_PRIO;      // the draw leaves slots and weights in pt_idx / pt_w
-  if (prio) RCCHK(prio_draw_launches(e, q.beta));
+  if (prio) RCCHK(prio_draw_launches(x, q.beta));
   const long long* idx = prio ? e->pt_idx : q.idx;
   const float* w = prio ? e->pt_w : q.w;
   const int64_t idx_ld = prio ? 1 : q.idx_ld, w_ld = prio ? 1 : q.w_ld;
-  if (q.chain) RCCHK(launch_batch_nstep(e, idx, idx_ld, w, w_ld, q.weighted ? e->bs[0].w : nullptr, q.steps, q.stride));
-  else RCCHK(launch_batch_index(e, idx, idx_ld, w, w_ld));
-  if (q.draw == DRAW_UNIFORM) {
-    hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
-    HIPCHK(hipGetLastError());
-  }
+  if (q.chain) RCCHK(launch_batch_nstep(x, idx, idx_ld, w, w_ld, q.weighted ? e->bs[0].w : nullptr, q.steps, q.stride));
+  else RCCHK(launch_batch_index(x, idx, idx_ld, w, w_ld));
+  if (q.draw == DRAW_UNIFORM) RCCHK(launch_tick(x, &e->ctl->sample_ctr));
   RCCHK(src_order_end(e, caller, q.flags));
   slot_refilled(e, q.weighted, q.chain);
   if (q.internal) return 0;
@@ -2396,50 +2393,50 @@ static int stage_ring_rows(sactd3_engine* e, const StageReq& q) {
   return 0;
 }
 
+static int stage_call(sactd3_engine* e, const StageReq& q) {      // what the entry points below end with
+  USE_DEVICE(e);
+  EnqCtx x{e, e->stream};
+  return stage_ring_rows(x, q);
+}
 // rb.sample() with the caller's indices and importance weights: one k_batch_from_index launch fills slot 0 as the index-injected gather
 // of sactd3_rb_sample_with_indices does, plus the slot's w.  No host wait, no copy command, no sample-counter tick.
 int sactd3_rb_sample_indices_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n,
                                     void* caller_stream, int flags) {
   if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
   StageReq q{"rb_sample_indices_device"};
   q.idx = (const long long*)idx; q.idx_ld = idx_ld; q.w = w; q.w_ld = w_ld; q.n = n; q.weighted = true;
   q.caller_stream = caller_stream; q.flags = flags;
-  return stage_ring_rows(e, q);
+  return stage_call(e, q);
 }
 // ... with the chain: one k_batch_from_index_nstep launch
 int sactd3_rb_sample_nstep_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const float* w, int64_t w_ld, int n, int steps,
                                   int stride, void* caller_stream, int flags) {
   if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
   StageReq q{"rb_sample_nstep_device"};
   q.idx = (const long long*)idx; q.idx_ld = idx_ld; q.w = w; q.w_ld = w_ld; q.n = n; q.weighted = true;
   q.chain = true; q.steps = steps; q.stride = stride; q.caller_stream = caller_stream; q.flags = flags;
-  return stage_ring_rows(e, q);
+  return stage_call(e, q);
 }
 // sactd3_rb_sample with the chain: the start slots are the uniform draw at the current sample counter, which then advances once
 int sactd3_rb_sample_nstep(sactd3_engine* e, int steps, int stride) {
   if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
   StageReq q{"rb_sample_nstep"};
   q.draw = DRAW_UNIFORM; q.chain = true; q.steps = steps; q.stride = stride;
-  return stage_ring_rows(e, q);
+  return stage_call(e, q);
 }
 // rb.sample by priority: k_prio_draw, k_prio_weights, k_batch_from_index.  The uniform sampler's counter is not touched.
 int sactd3_rb_sample_prioritized(sactd3_engine* e, float beta) {
   if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
   StageReq q{"rb_sample_prioritized"};
   q.draw = DRAW_PRIO; q.beta = beta; q.weighted = true;
-  return stage_ring_rows(e, q);
+  return stage_call(e, q);
 }
 // ... with the chain: the n-step staging kernel on the drawn slots
 int sactd3_rb_sample_prioritized_nstep(sactd3_engine* e, float beta, int steps, int stride) {
   if (!e) return SACTD3_EINVAL;
-  USE_DEVICE(e);
   StageReq q{"rb_sample_prioritized_nstep"};
   q.draw = DRAW_PRIO; q.beta = beta; q.weighted = true; q.chain = true; q.steps = steps; q.stride = stride;
-  return stage_ring_rows(e, q);
+  return stage_call(e, q);
 }
 
 // ---- prior data under an online run (include/sactd3.h): pinned rows and the mixed draw
@@ -2460,7 +2457,8 @@ int sactd3_rb_pin(sactd3_engine* e, int64_t n) {
   e->rb_pinned = n;
   if (e->rb_len == cap && e->rb_cursor != n) {      // full, never wrapped: the next append overwrites the oldest LIVE row
     e->rb_cursor = n;
-    RCCHK(publish_rb_state(e));
+    EnqCtx x{e, e->stream};
+    RCCHK(publish_rb_state(x));
   }
   return 0;
 }
@@ -2483,7 +2481,8 @@ int sactd3_rb_sample_mixed(sactd3_engine* e) {
   CHAIN_BREAK(e);
   RCCHK(slot_weights_alloc(e));      // (the staging kernel always writes the slot's weights: all 1, and the slot does not carry them)
   RCCHK(mix_alloc(e));
-  RCCHK(mix_draw_launches(e));
+  EnqCtx x{e, e->stream};
+  RCCHK(mix_draw_launches(x));
   slot_refilled(e, false, false);
   mix_count(e);
   return 0;
@@ -2503,8 +2502,9 @@ int sactd3_batch_weights_device(sactd3_engine* e, const float* w, int64_t w_ld, 
   CHAIN_BREAK(e);
   RCCHK(slot_weights_alloc(e));
   const hipStream_t caller = (hipStream_t)caller_stream;
+  EnqCtx x{e, e->stream};
   RCCHK(src_order_begin(e, caller, flags));
-  RCCHK(launch_batch_weights(e, w, w_ld));
+  RCCHK(launch_batch_weights(x, w, w_ld));
   RCCHK(src_order_end(e, caller, flags));
   slot_set_weighted(e, true);
   ++e->prio_stats[1];
@@ -2522,14 +2522,15 @@ int sactd3_td_errors_device(sactd3_engine* e, float* td, int64_t td_ld, int64_t 
   RCCHK(device_ptr_check(e, td, "td_errors_device", "td"));
   if (!e->slot.td_valid) return e->fail(SACTD3_ESTATE, "td_errors_device: no critic update has run on the rows now in the batch slot");
   const hipStream_t caller = (hipStream_t)caller_stream;
+  EnqCtx x{e, e->stream};
   RCCHK(src_order_begin(e, caller, flags));
-  RCCHK(launch_td_out(e, td, td_ld, td_ns));
+  RCCHK(launch_td_out(x, td, td_ld, td_ns));
   RCCHK(src_order_end(e, caller, flags));
   ++e->prio_stats[2];
   return 0;
 }
 
-int sactd3_priority_stats(sactd3_engine* e, int64_t out[4]) { return stats_with_refused(e, &sactd3_engine::prio_stats, &DevCtl::priority_refused, out); }
+int sactd3_priority_stats(sactd3_engine* e, int64_t out[4]) { return (!e || !out) ? SACTD3_EINVAL : stats_with_words(e, e->prio_stats, &e->ctl->priority_refused, 1, 3, out); }
 
 // ---- proportional prioritised replay as engine state (include/sactd3.h: sactd3_prio_*; the sample itself: stage_ring_rows)
 // One leaf per ring slot plus the group sums, built for the rows the ring holds now (priority 1 = the starting maximum).
@@ -2541,19 +2542,17 @@ int sactd3_prio_enable(sactd3_engine* e, float alpha, float eps) {
   if (e->pt_on) return (alpha == e->pt_alpha && eps == e->pt_eps) ? 0 : e->fail(SACTD3_ESTATE, "prio_enable: already enabled with other values");
   if (e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "prio_enable: rows are pinned (sactd3_rb_pin): the priority refresh assumes one wrap point, at slot 0");
   const int64_t groups = ((int64_t)e->cfg.rb_capacity + PRIO_G - 1) / PRIO_G, chunks = (groups + PRIO_G - 1) / PRIO_G;
-  if (!e->pt_leaf) {      // (a call that failed half way keeps what it had made)
-    RCCHK(dalloc(e, &e->pt_leaf, (size_t)groups * PRIO_G)); RCCHK(dalloc(e, &e->pt_sums, (size_t)chunks * PRIO_G));
-    RCCHK(dalloc(e, &e->pt_ctl, 1));
-    RCCHK(dalloc(e, &e->pt_idx, (size_t)e->B)); RCCHK(dalloc(e, &e->pt_dleaf, (size_t)e->B)); RCCHK(dalloc(e, &e->pt_w, (size_t)e->B));
-    RCCHK(dalloc(e, &e->pt_total, 4)); RCCHK(dalloc(e, &e->pt_u, (size_t)e->B));
-  }
+  RCCHK(first_use_alloc(e, &e->pt_leaf, (size_t)groups * PRIO_G)); RCCHK(first_use_alloc(e, &e->pt_sums, (size_t)chunks * PRIO_G));
+  RCCHK(first_use_alloc(e, &e->pt_ctl, 1, false));      // (never zeroed: the copy below, done when it returns, writes all of it)
+  RCCHK(first_use_alloc(e, &e->pt_idx, (size_t)e->B)); RCCHK(first_use_alloc(e, &e->pt_dleaf, (size_t)e->B)); RCCHK(first_use_alloc(e, &e->pt_w, (size_t)e->B));
+  RCCHK(first_use_alloc(e, &e->pt_total, 4)); RCCHK(first_use_alloc(e, &e->pt_u, (size_t)e->B));
   RCCHK(slot_weights_alloc(e));
   PrioCtl h{};
   h.max_prio = 1.f;
   HIPCHK(hipMemcpy(e->pt_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
-  HIPCHK(hipDeviceSynchronize());      // (the zero fills above are not ordered with the learner stream by themselves)
   e->pt_groups = (int)groups; e->pt_alpha = alpha; e->pt_eps = eps; e->pt_on = true;
-  return prio_after_append(e, 0, e->rb_len);
+  EnqCtx x{e, e->stream};
+  return prio_after_append(x, 0, e->rb_len);
 }
 
 int sactd3_prio_set_uniforms(sactd3_engine* e, const float* u, int n) {
@@ -2577,7 +2576,8 @@ int sactd3_prio_update_from_td(sactd3_engine* e) {
   USE_DEVICE(e);
   if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_from_td: priorities are not enabled (sactd3_prio_enable)");
   if (!e->slot.td_valid) return e->fail(SACTD3_ESTATE, "prio_update_from_td: no critic update has run on the rows now in the batch slot");
-  RCCHK(launch_prio_update(e, prio_td_args(e, e->slot.cur)));
+  EnqCtx x{e, e->stream};
+  RCCHK(launch_prio_update(x, prio_td_args(e, e->slot.cur)));
   ++e->pt_host[1];
   return 0;
 }
@@ -2594,25 +2594,18 @@ int sactd3_prio_update_device(sactd3_engine* e, const int64_t* idx, int64_t idx_
   RCCHK(device_ptr_check(e, prio, "prio_update_device", "prio"));
   if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_device: priorities are not enabled (sactd3_prio_enable)");
   const hipStream_t caller = (hipStream_t)caller_stream;
+  EnqCtx x{e, e->stream};
   RCCHK(src_order_begin(e, caller, flags));
   PrioUpdateArgs g{};
   g.n = n; g.idx = (const long long*)idx; g.idx_ld = (long)idx_ld; g.prio = prio; g.prio_ld = (long)prio_ld;
-  RCCHK(launch_prio_update(e, g));
+  RCCHK(launch_prio_update(x, g));
   RCCHK(src_order_end(e, caller, flags));
   ++e->pt_host[1];
   return 0;
 }
 
-int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  int refused = 0;
-  if (e->pt_on) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(&refused, &e->pt_ctl->refused, sizeof(int), hipMemcpyDeviceToHost));
-  }
-  out[0] = e->pt_host[0]; out[1] = e->pt_host[1]; out[2] = refused; out[3] = e->pt_host[2];
-  return 0;
+int sactd3_prio_stats(sactd3_engine* e, int64_t out[4]) {      // (the device word stands third)
+  return (!e || !out) ? SACTD3_EINVAL : stats_with_words(e, e->pt_host, e->pt_on ? &e->pt_ctl->refused : nullptr, 1, 2, out);
 }
 
 // k and the last ring slot of every row of an n-step slot, left in the caller's device arrays: one k_nstep_info launch on the learner
@@ -2629,22 +2622,14 @@ int sactd3_nstep_info_device(sactd3_engine* e, int32_t* k, int64_t k_ld, int32_t
   const hipStream_t caller = (hipStream_t)caller_stream;
   RCCHK(src_order_begin(e, caller, flags));
   const NstepInfoArgs g{e->ns_k, e->ns_last, e->B, k, (long)k_ld, last, (long)last_ld};
-  hipLaunchKernelGGL(k_nstep_info, dim3((unsigned)((e->B + 255) / 256)), dim3(256), 0, e->stream, g);
-  HIPCHK(hipGetLastError());
+  EnqCtx x{e, e->stream};
+  LAUNCH_ON(k_nstep_info, dim3((unsigned)((e->B + 255) / 256)), dim3(256), g);
   RCCHK(src_order_end(e, caller, flags));
   return 0;
 }
 
 int sactd3_nstep_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  int c[2] = {0, 0};
-  if (e->ns_ctr) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(c, e->ns_ctr, sizeof(c), hipMemcpyDeviceToHost));
-  }
-  out[0] = e->ns_host[0]; out[1] = e->ns_host[1]; out[2] = c[0]; out[3] = c[1];
-  return 0;
+  return (!e || !out) ? SACTD3_EINVAL : stats_with_words(e, e->ns_host, e->ns_ctr, 2, 2, out);
 }
 
 int sactd3_rb_fill_synthetic(sactd3_engine* e, int64_t n, uint64_t seed) {
@@ -2655,12 +2640,12 @@ int sactd3_rb_fill_synthetic(sactd3_engine* e, int64_t n, uint64_t seed) {
   if (e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "rb_fill_synthetic: rows are pinned (sactd3_rb_pin): the fill writes from slot 0");
   FillArgs f{(float4*)e->ring, e->rec4, e->cx, e->cn, e->o, e->a, (long)n, seed, e->min_ac, e->max_ac};
   const long threads = (long)n * e->rec4;
-  hipLaunchKernelGGL(k_rb_fill, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream, f);
-  HIPCHK(hipGetLastError());
+  EnqCtx x{e, e->stream};
+  LAUNCH_ON(k_rb_fill, dim3((unsigned)((threads + 255) / 256)), dim3(256), f);
   e->rb_len = std::max<int64_t>(e->rb_len, n);
   e->rb_cursor = n % e->cfg.rb_capacity;
-  RCCHK(publish_rb_state(e));
-  return prio_after_append(e, 0, n);
+  RCCHK(publish_rb_state(x));
+  return prio_after_append(x, 0, n);
 }
 
 // ---- noise
@@ -2780,6 +2765,7 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
   if (chain) RCCHK(nstep_alloc(e));
   if (mixed) RCCHK(mix_alloc(e));
   const int key[3] = {sm->draw, sm->n_step, stride};
+  EnqCtx x{e, e->stream};      // (the eager launches in front of the graph)
   if (memcmp(key, e->ss_key, sizeof(key)) != 0) {
     RCCHK(drop_graphs(e, G_SAMPLED, 4));
     memcpy(e->ss_key, key, sizeof(key));
@@ -2789,12 +2775,11 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
     memcpy(&bits, &sm->beta, sizeof(bits));
     const int inject = e->pt_inject ? 1 : 0;
     if ((int64_t)(uint32_t)bits != e->ss_beta_bits || inject != e->ss_inject) {
-      hipLaunchKernelGGL(k_set_int2, dim3(1), dim3(1), 0, e->stream, reinterpret_cast<int*>(&e->pt_ctl->beta), (int)bits, inject);
-      HIPCHK(hipGetLastError());
+      RCCHK(launch_set_int2(x, reinterpret_cast<int*>(&e->pt_ctl->beta), (int)bits, inject));
       e->ss_beta_bits = (int64_t)(uint32_t)bits; e->ss_inject = inject;
     }
   }
-  if (mixed) RCCHK(mix_publish(e));      // (P and m as the graph's draw reads them: a launch only when one of them changed)
+  if (mixed) RCCHK(mix_publish(x));      // (P and m as the graph's draw reads them: a launch only when one of them changed)
   RCCHK(issue_iteration(e, do_actor, G_SAMPLED));
   ++e->ss_stats[0];
   // the rest of the host state, transition by transition as the call sequence makes them
@@ -2890,6 +2875,7 @@ static int enqueue_graph(EnqCtx& x, int which) {
     case G_PREFIX: case G_PREFIX + 1: case G_PREFIX + 2: case G_PREFIX + 3: return enqueue_period(x, (which - G_PREFIX) & 1, (which - G_PREFIX) / 2 + 1);
     case G_RUN: case G_RUN + 1: return enqueue_period_run(x, which - G_RUN);
     case G_SAMPLED: case G_SAMPLED + 1: case G_SAMPLED + 2: case G_SAMPLED + 3:      // + IterSchedule::k
+      x.graph_form = true;
       return enqueue_step_sampled(x, ((which - G_SAMPLED) & 2) != 0, ((which - G_SAMPLED) & 1) != 0);
   }
   return e->fail(SACTD3_EINVAL, "enqueue_graph: no such graph");
@@ -3038,10 +3024,7 @@ static int enqueue_predict(EnqCtx& x, int n, int explore, bool on_device = false
   if (explore && one_block) t.tick = &e->ctl->predict_ctr;
   if (one_block && !on_device) { t.seq = &e->ctl->predict_seq; t.done_flag = e->h_done; }
   RCCHK(launch_tail(x, t));
-  if (explore && !one_block) {
-    hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, x.s, &e->ctl->predict_ctr, (int*)nullptr);
-    HIPCHK(hipGetLastError());
-  }
+  if (explore && !one_block) RCCHK(launch_tick(x, &e->ctl->predict_ctr));
   return 0;
 }
 static void predict_stage_obs(sactd3_engine* e, const float* obs, int n) {
@@ -3136,18 +3119,16 @@ int sactd3_predict_end(sactd3_engine* e, float* actions) {
   return 0;
 }
 
-static int launch_obs_pack(sactd3_engine* e, const float* obs, int64_t obs_ld, float* x, int n) {      // x: n packed rows at ldo
-  const ObsFieldArgs g{(float4*)x, n, e->ldo / 4};
+static int launch_obs_pack(EnqCtx& x, const float* obs, int64_t obs_ld, float* rows, int n) {      // rows: n packed rows at ldo
+  const ObsFieldArgs g{(float4*)rows, n, x.e->ldo / 4};
   const long chunks = (long)n * g.c4;
-  hipLaunchKernelGGL(k_obs_from_field, dim3(cpt_blocks(chunks, OBS_CPT)), dim3(256), 0, e->stream, obs, (long)obs_ld, e->o, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_obs_from_field, dim3(cpt_blocks(chunks, OBS_CPT)), dim3(256), obs, (long)obs_ld, x.e->o, g);
   return 0;
 }
-static int launch_act_unpack(sactd3_engine* e, float* actions, int64_t actions_ld, int n) {
-  const ActFieldArgs g{(const float4*)e->p_act, n, e->a4 / 4, e->a};
+static int launch_act_unpack(EnqCtx& x, float* actions, int64_t actions_ld, int n) {
+  const ActFieldArgs g{(const float4*)x.e->p_act, n, x.e->a4 / 4, x.e->a};
   const long chunks = (long)n * g.c4;
-  hipLaunchKernelGGL(k_act_to_field, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, e->stream, actions, (long)actions_ld, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_act_to_field, dim3((unsigned)((chunks + 255) / 256)), dim3(256), actions, (long)actions_ld, g);
   return 0;
 }
 
@@ -3170,12 +3151,13 @@ int sactd3_predict_device(sactd3_engine* e, const float* obs, int64_t obs_ld, in
   // (it shares predict_ctr and eps[SITE_PREDICT] with a call on the acting stream)
   if (e->act_inflight) return e->fail(SACTD3_ESTATE, "predict_device: an acting call is in flight (sactd3_predict_end first)");
   const hipStream_t caller = (hipStream_t)caller_stream;
+  EnqCtx x{e, e->stream};      // (the two eager launches around the pair's graph)
   RCCHK(src_order_begin(e, caller, flags));
-  RCCHK(launch_obs_pack(e, obs, obs_ld, e->p_x, n));
+  RCCHK(launch_obs_pack(x, obs, obs_ld, e->p_x, n));
   if (e->predict_dev_graphs.empty()) e->predict_dev_graphs.assign(2 * (size_t)(e->maxn + 1), nullptr);
   RCCHK(run_graph_slot(e, &e->predict_dev_graphs[(size_t)(explore ? 1 : 0) * (e->maxn + 1) + n], nullptr,
-                       [&](EnqCtx& x) { return enqueue_predict(x, n, explore, true); }));
-  RCCHK(launch_act_unpack(e, actions, actions_ld, n));
+                       [&](EnqCtx& xg) { return enqueue_predict(xg, n, explore, true); }));
+  RCCHK(launch_act_unpack(x, actions, actions_ld, n));
   RCCHK(src_order_end(e, caller, flags));
   // The call returns with its kernels still queued, and they use the scratch, the draw buffer and the counter that an acting-stream
   // call uses too: the next sactd3_predict_begin has to wait for the learner stream, exactly as behind a write of the actor.
@@ -3195,38 +3177,32 @@ int sactd3_predict_device_stats(const sactd3_engine* e, int64_t out[4]) { return
 // scratch and its own counters only: no CHAIN_BREAK, no counter tick, actor_dirty untouched, no batch slot / noise buffer / p_* use.
 static const int Q_CHUNK = 1024;      // rows per pass: what the scoring scratch is sized for
 static int q_scratch(sactd3_engine* e, bool policy) {      // (never zeroed: every float a launch reads was written by the one before it)
-  if (!e->qs_sa) {
-    RCCHK(dalloc(e, &e->qs_z1, (size_t)2 * Q_CHUNK * HID, false));
-    RCCHK(dalloc(e, &e->qs_z2, (size_t)2 * Q_CHUNK * HID, false));
-    RCCHK(dalloc(e, &e->qs_sa, (size_t)Q_CHUNK * e->ldc, false));
-  }
-  if (policy && !e->qs_act) {
-    RCCHK(dalloc(e, &e->qs_x, (size_t)Q_CHUNK * e->ldo, false));
-    RCCHK(dalloc(e, &e->qs_az1, (size_t)Q_CHUNK * HID, false));
-    RCCHK(dalloc(e, &e->qs_az2, (size_t)Q_CHUNK * HID, false));
-    RCCHK(dalloc(e, &e->qs_act, (size_t)Q_CHUNK * e->a4, false));
-  }
-  return 0;
+  RCCHK(first_use_alloc(e, &e->qs_z1, (size_t)2 * Q_CHUNK * HID, false));
+  RCCHK(first_use_alloc(e, &e->qs_z2, (size_t)2 * Q_CHUNK * HID, false));
+  RCCHK(first_use_alloc(e, &e->qs_sa, (size_t)Q_CHUNK * e->ldc, false));
+  if (!policy) return 0;
+  RCCHK(first_use_alloc(e, &e->qs_x, (size_t)Q_CHUNK * e->ldo, false));
+  RCCHK(first_use_alloc(e, &e->qs_az1, (size_t)Q_CHUNK * HID, false));
+  RCCHK(first_use_alloc(e, &e->qs_az2, (size_t)Q_CHUNK * HID, false));
+  return first_use_alloc(e, &e->qs_act, (size_t)Q_CHUNK * e->a4, false);
 }
-static int launch_sa_pack(sactd3_engine* e, const float* obs, int64_t obs_ld, const float* act, int64_t act_ld, int m) {
-  const SaFieldArgs g{(float4*)e->qs_sa, m, e->ldc / 4};
+static int launch_sa_pack(EnqCtx& x, const float* obs, int64_t obs_ld, const float* act, int64_t act_ld, int m) {
+  const SaFieldArgs g{(float4*)x.e->qs_sa, m, x.e->ldc / 4};
   const long chunks = (long)m * g.c4;
-  hipLaunchKernelGGL(k_sa_from_fields, dim3(cpt_blocks(chunks, SA_CPT)), dim3(256), 0, e->stream,
-                     obs, (long)obs_ld, act, (long)act_ld, e->o, e->a, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_sa_from_fields, dim3(cpt_blocks(chunks, SA_CPT)), dim3(256), obs, (long)obs_ld, act, (long)act_ld, x.e->o, x.e->a, g);
   return 0;
 }
-static int launch_q_head(sactd3_engine* e, const float* P, int m, float* q, int64_t q_ld, int64_t q_ns) {
+static int launch_q_head(EnqCtx& x, const float* P, int m, float* q, int64_t q_ld, int64_t q_ns) {
+  sactd3_engine* e = x.e;
   QHead h{};
   h.z2 = e->qs_z2; h.P = P; h.p_ns = e->Lc.size; h.L = e->Lc; h.n = m; h.ln = e->cfg.layer_norm; h.q = q; h.q_ld = (long)q_ld; h.q_ns = (long)q_ns;
-  hipLaunchKernelGGL(k_q_head<4>, dim3((unsigned)((m + 3) / 4), 2), dim3(64), 0, e->stream, h);
-  HIPCHK(hipGetLastError());
+  LAUNCH_ON(k_q_head<4>, dim3((unsigned)((m + 3) / 4), 2), dim3(64), h);
   return 0;
 }
-static int enqueue_qvalues(sactd3_engine* e, const float* obs, int64_t obs_ld, const float* act, int64_t act_ld, int n, int which,
+static int enqueue_qvalues(EnqCtx& x, const float* obs, int64_t obs_ld, const float* act, int64_t act_ld, int n, int which,
                            float* q, int64_t q_ld, int64_t q_ns) {
+  sactd3_engine* e = x.e;
   RCCHK(q_scratch(e, act == nullptr));
-  EnqCtx x{e, e->stream};
   TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
   tk.pin_shape = true;
   const float* P = which == SACTD3_Q_TARGET ? e->Tc : e->Pc;
@@ -3234,17 +3210,17 @@ static int enqueue_qvalues(sactd3_engine* e, const float* obs, int64_t obs_ld, c
     const int m = (int)std::min<int64_t>(Q_CHUNK, n - row0);
     const float* obs_c = obs + row0 * obs_ld;
     if (!act) {      // pi(s): the online actor's exploit action, what sactd3_predict(explore = 0) returns
-      RCCHK(launch_obs_pack(e, obs_c, obs_ld, e->qs_x, m));
+      RCCHK(launch_obs_pack(x, obs_c, obs_ld, e->qs_x, m));
       const TrunkGrp ga{e->qs_x, e->Pa, e->qs_az1, e->qs_az2, nullptr, nullptr, nullptr};
       RCCHK(enqueue_trunk(x, e->ldo, e->o, m, e->La, 0, 1, 1, &ga, tk));
       // (exploit mode draws nothing: the tail reads neither the draw buffer nor -- for its result -- the counter, and ticks nothing)
       const ActorTail t = tail_args(e, e->qs_az2, e->Pa, m, e->cfg.prefer_td3_over_sac ? 0 : 1, 0, SACTD3_SITE_PREDICT, 48u, e->qs_act, e->a4, 0, nullptr);
       RCCHK(launch_tail(x, t));
-      RCCHK(launch_sa_pack(e, obs_c, obs_ld, e->qs_act, e->a4, m));
-    } else RCCHK(launch_sa_pack(e, obs_c, obs_ld, act + row0 * act_ld, act_ld, m));
+      RCCHK(launch_sa_pack(x, obs_c, obs_ld, e->qs_act, e->a4, m));
+    } else RCCHK(launch_sa_pack(x, obs_c, obs_ld, act + row0 * act_ld, act_ld, m));
     const TrunkGrp gc{e->qs_sa, P, e->qs_z1, e->qs_z2, nullptr, nullptr, nullptr};
     RCCHK(enqueue_trunk(x, e->ldc, e->o + e->a, m, e->Lc, e->Lc.size, 1, 2, &gc, tk));
-    RCCHK(launch_q_head(e, P, m, q + row0 * q_ld, q_ld, q_ns));
+    RCCHK(launch_q_head(x, P, m, q + row0 * q_ld, q_ld, q_ns));
   }
   return 0;
 }
@@ -3268,8 +3244,9 @@ int sactd3_qvalues_device(sactd3_engine* e, const float* obs, int64_t obs_ld, co
   if (actions) RCCHK(device_ptr_check(e, actions, "qvalues_device", "actions"));      // (NULL: the policy form)
   RCCHK(device_ptr_check(e, q, "qvalues_device", "q"));
   const hipStream_t caller = (hipStream_t)caller_stream;
+  EnqCtx x{e, e->stream};
   RCCHK(src_order_begin(e, caller, flags));
-  RCCHK(enqueue_qvalues(e, obs, obs_ld, actions, actions_ld, n, which, q, q_ld, q_ns));
+  RCCHK(enqueue_qvalues(x, obs, obs_ld, actions, actions_ld, n, which, q, q_ld, q_ns));
   RCCHK(src_order_end(e, caller, flags));
   ++e->q_stats[0]; e->q_stats[1] += n;
   if (flags & SACTD3_SRC_ORDERED) ++e->q_stats[2];
@@ -3283,16 +3260,15 @@ int sactd3_qvalues(sactd3_engine* e, const float* obs, const float* actions, int
   if (!obs || !q) return e->fail(SACTD3_EINVAL, "qvalues: null argument");
   USE_DEVICE(e);
   RCCHK(qvalues_args(e, "qvalues", n, which));
-  if (!e->qs_hq) {
-    RCCHK(dalloc(e, &e->qs_hq, (size_t)2 * Q_CHUNK, false));
-    RCCHK(dalloc(e, &e->qs_hobs, (size_t)Q_CHUNK * e->o, false));
-    RCCHK(dalloc(e, &e->qs_hact, (size_t)Q_CHUNK * e->a, false));
-  }
+  RCCHK(first_use_alloc(e, &e->qs_hq, (size_t)2 * Q_CHUNK, false));
+  RCCHK(first_use_alloc(e, &e->qs_hobs, (size_t)Q_CHUNK * e->o, false));
+  RCCHK(first_use_alloc(e, &e->qs_hact, (size_t)Q_CHUNK * e->a, false));
+  EnqCtx x{e, e->stream};
   for (int64_t row0 = 0; row0 < n; row0 += Q_CHUNK) {
     const int m = (int)std::min<int64_t>(Q_CHUNK, n - row0);
     HIPCHK(hipMemcpy(e->qs_hobs, obs + row0 * e->o, sizeof(float) * (size_t)m * e->o, hipMemcpyHostToDevice));
     if (actions) HIPCHK(hipMemcpy(e->qs_hact, actions + row0 * e->a, sizeof(float) * (size_t)m * e->a, hipMemcpyHostToDevice));
-    RCCHK(enqueue_qvalues(e, e->qs_hobs, e->o, actions ? e->qs_hact : nullptr, e->a, m, which, e->qs_hq, 1, Q_CHUNK));
+    RCCHK(enqueue_qvalues(x, e->qs_hobs, e->o, actions ? e->qs_hact : nullptr, e->a, m, which, e->qs_hq, 1, Q_CHUNK));
     HIPCHK(hipStreamSynchronize(e->stream));
     for (int k = 0; k < 2; ++k)
       HIPCHK(hipMemcpy(q + (int64_t)k * n + row0, e->qs_hq + (size_t)k * Q_CHUNK, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost));
@@ -3310,18 +3286,15 @@ int sactd3_qvalues_stats(const sactd3_engine* e, int64_t out[4]) { return host_s
 // scoring call it writes its own scratch and its own words only: no CHAIN_BREAK, actor_dirty untouched, no batch slot / noise buffer /
 // p_* use, no sample / noise / predict counter.
 static int pi_scratch(sactd3_engine* e) {
-  if (e->pi_ctl) return 0;
-  RCCHK(dalloc(e, &e->pi_x, (size_t)Q_CHUNK * e->ldo));
-  RCCHK(dalloc(e, &e->pi_z1, (size_t)Q_CHUNK * HID));
-  RCCHK(dalloc(e, &e->pi_z2, (size_t)Q_CHUNK * HID));
-  RCCHK(dalloc(e, &e->pi_ctl, 2));
-  return 0;
+  RCCHK(first_use_alloc(e, &e->pi_x, (size_t)Q_CHUNK * e->ldo));
+  RCCHK(first_use_alloc(e, &e->pi_z1, (size_t)Q_CHUNK * HID));
+  RCCHK(first_use_alloc(e, &e->pi_z2, (size_t)Q_CHUNK * HID));
+  return first_use_alloc(e, &e->pi_ctl, 2);
 }
 // the head of a (narrow: see tail_rows_per_block) actor, in the form of the acting tail of the same head shape
-static int launch_pi_head(sactd3_engine* e, const PiHead& h) {
-  if (e->La.nh <= 8 && e->a <= 8) hipLaunchKernelGGL(k_pi_head_s, dim3((unsigned)((h.n + 3) / 4)), dim3(64), 0, e->stream, h);
-  else hipLaunchKernelGGL(k_pi_head, dim3((unsigned)((h.n + 15) / 16)), dim3(256), 0, e->stream, h);
-  HIPCHK(hipGetLastError());
+static int launch_pi_head(EnqCtx& x, const PiHead& h) {
+  if (x.e->La.nh <= 8 && x.e->a <= 8) LAUNCH_ON(k_pi_head_s, dim3((unsigned)((h.n + 3) / 4)), dim3(64), h);
+  else LAUNCH_ON(k_pi_head, dim3((unsigned)((h.n + 15) / 16)), dim3(256), h);
   return 0;
 }
 // m rows from row `row0` of the arrays in `io`; `draw_row`: the row of the CALL that one is (it numbers the native draws)
@@ -3343,26 +3316,24 @@ static PiHead pi_head_args(sactd3_engine* e, const float* P, PiCtl* pc, int m, i
   return h;
 }
 // n rows of `obs` and of every array of `io`; their row 0 is row `first` of the call (the host form hands over a chunk at a time)
-static int enqueue_policy(sactd3_engine* e, const float* obs, int64_t obs_ld, int64_t first, int n, int which, const sactd3_policy_io& io) {
-  EnqCtx x{e, e->stream};
+static int enqueue_policy(EnqCtx& x, const float* obs, int64_t obs_ld, int64_t first, int n, int which, const sactd3_policy_io& io) {
+  sactd3_engine* e = x.e;
   TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
   tk.pin_shape = true;
   const float* P = which == SACTD3_PI_TARGET ? e->Ta : e->Pa;
   for (int64_t r0 = 0; r0 < n; r0 += Q_CHUNK) {
     const int m = (int)std::min<int64_t>(Q_CHUNK, n - r0);
-    RCCHK(launch_obs_pack(e, obs + r0 * obs_ld, obs_ld, e->pi_x, m));
+    RCCHK(launch_obs_pack(x, obs + r0 * obs_ld, obs_ld, e->pi_x, m));
     const TrunkGrp ga{e->pi_x, P, e->pi_z1, e->pi_z2, nullptr, nullptr, nullptr};
     RCCHK(enqueue_trunk(x, e->ldo, e->o, m, e->La, 0, 1, 1, &ga, tk));
-    RCCHK(launch_pi_head(e, pi_head_args(e, P, e->pi_ctl, m, r0, first + r0, io)));
+    RCCHK(launch_pi_head(x, pi_head_args(e, P, e->pi_ctl, m, r0, first + r0, io)));
     e->pi_rows = m;
   }
   return 0;
 }
-static int pi_tick(sactd3_engine* e, const sactd3_policy_io& io) {      // behind the last chunk of a call that drew natively
+static int pi_tick(EnqCtx& x, const sactd3_policy_io& io) {      // behind the last chunk of a call that drew natively
   if (!(io.sample || io.sample_logp || io.eps_out) || io.eps) return 0;
-  hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->pi_ctl->policy_ctr, (int*)nullptr);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_tick(x, &x.e->pi_ctl->policy_ctr);
 }
 // what both forms refuse, pointers aside
 static int policy_args(sactd3_engine* e, const char* what, int n, int which, const sactd3_policy_io& io) {
@@ -3393,16 +3364,13 @@ int sactd3_policy_device(sactd3_engine* e, const float* obs, int64_t obs_ld, int
       {io->sample_logp, io->sample_logp_ld, 1, "sample_logp"}, {io->action_logp, io->action_logp_ld, 1, "action_logp"},
       {io->eps_out, io->eps_out_ld, e->a, "eps_out"}};
   RCCHK(device_ptr_check(e, obs, "policy_device", "obs"));
-  for (const FieldRow& r : rows) {
-    if (!r.p) continue;
-    if (r.ld < r.width) { e->err = std::string("policy_device: row stride of `") + r.name + "` is below its width"; return SACTD3_EINVAL; }
-    RCCHK(device_ptr_check(e, r.p, "policy_device", r.name));
-  }
+  RCCHK(field_rows_check(e, rows, 9, false, "policy_device", nullptr));      // (policy_args has refused "no output is set")
   RCCHK(pi_scratch(e));
   const hipStream_t caller = (hipStream_t)caller_stream;
+  EnqCtx x{e, e->stream};
   RCCHK(src_order_begin(e, caller, flags));
-  RCCHK(enqueue_policy(e, obs, obs_ld, 0, n, which, *io));
-  RCCHK(pi_tick(e, *io));
+  RCCHK(enqueue_policy(x, obs, obs_ld, 0, n, which, *io));
+  RCCHK(pi_tick(x, *io));
   RCCHK(src_order_end(e, caller, flags));
   ++e->pi_stats[0]; e->pi_stats[1] += n;
   return 0;
@@ -3417,10 +3385,9 @@ int sactd3_policy(sactd3_engine* e, const float* obs, int n, int which, const sa
   RCCHK(policy_args(e, "policy", n, which, *hio));
   RCCHK(pi_scratch(e));
   const int a = e->a;
-  if (!e->pi_hobs) {
-    RCCHK(dalloc(e, &e->pi_hobs, (size_t)Q_CHUNK * e->o, false));
-    RCCHK(dalloc(e, &e->pi_hio, (size_t)Q_CHUNK * (7 * a + 2), false));
-  }
+  RCCHK(first_use_alloc(e, &e->pi_hobs, (size_t)Q_CHUNK * e->o, false));
+  RCCHK(first_use_alloc(e, &e->pi_hio, (size_t)Q_CHUNK * (7 * a + 2), false));
+  EnqCtx x{e, e->stream};
   // device staging of one chunk: [actions | eps | mode | mean | log_std | sample | eps_out] each [Q_CHUNK, a], then the two [Q_CHUNK] columns
   float* const base = e->pi_hio;
   auto slab = [&](int k) { return base + (size_t)k * Q_CHUNK * a; };
@@ -3440,8 +3407,8 @@ int sactd3_policy(sactd3_engine* e, const float* obs, int n, int which, const sa
     d.sample_logp = staged(lp_s, hio->sample_logp); d.action_logp = staged(lp_a, hio->action_logp);
     d.actions_ld = d.eps_ld = d.mode_ld = d.mean_ld = d.log_std_ld = d.sample_ld = d.eps_out_ld = a;
     d.sample_logp_ld = d.action_logp_ld = 1;
-    RCCHK(enqueue_policy(e, e->pi_hobs, e->o, row0, m, which, d));
-    if (row0 + m >= n) RCCHK(pi_tick(e, *hio));
+    RCCHK(enqueue_policy(x, e->pi_hobs, e->o, row0, m, which, d));
+    if (row0 + m >= n) RCCHK(pi_tick(x, *hio));
     HIPCHK(hipStreamSynchronize(e->stream));
     auto back = [&](float* dst, const float* src, int width) -> hipError_t {
       return dst ? hipMemcpy(dst + row0 * width, src, sizeof(float) * (size_t)m * width, hipMemcpyDeviceToHost) : hipSuccess;
@@ -3454,16 +3421,8 @@ int sactd3_policy(sactd3_engine* e, const float* obs, int n, int which, const sa
   return 0;
 }
 
-int sactd3_policy_stats(sactd3_engine* e, int64_t out[4]) {
-  if (!e || !out) return SACTD3_EINVAL;
-  USE_DEVICE(e);
-  int words[3] = {0, 0, 0};
-  if (e->pi_ctl) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(words, e->pi_ctl, sizeof(words), hipMemcpyDeviceToHost));
-  }
-  out[0] = e->pi_stats[0]; out[1] = e->pi_stats[1]; out[2] = words[1]; out[3] = words[2];
-  return 0;
+int sactd3_policy_stats(sactd3_engine* e, int64_t out[4]) {      // (PiCtl::clamped and ::nan_rows are adjacent)
+  return (!e || !out) ? SACTD3_EINVAL : stats_with_words(e, e->pi_stats, e->pi_ctl ? &e->pi_ctl->clamped : nullptr, 2, 2, out);
 }
 
 int sactd3_acting_stats(const sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::act_stats, out); }
@@ -3487,8 +3446,8 @@ int sactd3_set_bc(sactd3_engine* e, float bc_alpha, float bc_weight) {
   if (!(bc_weight >= 0.f) || !std::isfinite(bc_weight)) return e->fail(SACTD3_EINVAL, "set_bc: bc_weight must be finite and >= 0");
   int bits[2];
   memcpy(&bits[0], &bc_alpha, sizeof(int)); memcpy(&bits[1], &bc_weight, sizeof(int));
-  hipLaunchKernelGGL(k_set_int2, dim3(1), dim3(1), 0, e->stream, reinterpret_cast<int*>(e->ctl->bc), bits[0], bits[1]);
-  HIPCHK(hipGetLastError());
+  EnqCtx x{e, e->stream};
+  RCCHK(launch_set_int2(x, reinterpret_cast<int*>(e->ctl->bc), bits[0], bits[1]));
   e->bc_alpha = bc_alpha; e->bc_weight = bc_weight;
   return 0;
 }
@@ -3531,52 +3490,53 @@ int sactd3_sync(sactd3_engine* e) {
 }
 
 // ---- introspection
-struct DbgEntry { const char* name; const float* ptr; int64_t n; };
-static std::vector<DbgEntry> dbg_table(sactd3_engine* e) {
+// THE list of what sactd3_debug_read hands out, in the order sactd3_debug_names spells it.  A name carries its kind -- a plain buffer, a
+// gradient arena (read in the reference's unpadded layout), a word of the priority table (refused until sactd3_prio_enable), the policy
+// query's last chunk (refused until a query has run) -- and `stale`: the grads_stale family it belongs to, or -1.  dbg_table(e) is that
+// list for an engine; on an engine that holds nothing it still names everything, which is what sactd3_debug_names reads.
+enum { DBG_PLAIN, DBG_GRAD, DBG_PRIO, DBG_PI_Z2 };
+struct DbgEntry { const char* name; const float* ptr; int64_t n; int kind = DBG_PLAIN; int stale = -1; };
+static std::vector<DbgEntry> dbg_table(const sactd3_engine* e) {
   const int64_t B = e->B, BH = B * HID;
   const sactd3_engine::BatchSlot& S = e->bs[e->slot.cur];
   return {
       {"X", S.X, B * e->ldc}, {"Xn", S.Xn, B * e->ldc}, {"Xp", e->Xp, B * e->ldc}, {"rew", S.rew, B}, {"done", S.done, B},
       {"logp_next", S.logp_n, B}, {"logp_pi", e->logp_pi, B}, {"logp_alpha", e->logp_al, B},
-      {"a_xh1", e->a_xh1, BH}, {"a_h1", e->a_h1, BH}, {"a_z2", e->a_z2, BH}, {"a_h2", e->a_h2, BH}, {"a_du", e->a_du, B * e->ldu},
-      {"a_xh2", e->a_xh2, BH}, {"a_rs2", e->a_rs2, B}, {"a_tg", e->a_tg, B * 4 * e->a4},
-      {"a_dz2", e->a_dz2, BH}, {"a_dh1", e->a_dh1, BH}, {"a_dz1", e->a_dz1, BH},
+      {"a_xh1", e->a_xh1, BH}, {"a_h1", e->a_h1, BH}, {"a_z2", e->a_z2, BH}, {"a_h2", e->a_h2, BH},
+      {"a_xh2", e->a_xh2, BH}, {"a_rs2", e->a_rs2, B}, {"a_tg", e->a_tg, B * 4 * e->a4}, {"a_du", e->a_du, B * e->ldu},
+      {"a_dz2", e->a_dz2, BH}, {"a_dh1", e->a_dh1, BH}, {"a_dz1", e->a_dz1, BH, DBG_PLAIN, 1},
       {"c_xh1", e->c_xh1, 2 * BH}, {"c_h1", e->c_h1, 2 * BH}, {"c_z2", e->c_z2, 2 * BH}, {"c_dz2", e->c_dz2, 2 * BH},
-      {"c_dh1", e->c_dh1, 2 * BH}, {"c_dz1", e->c_dz1, 2 * BH}, {"t_z2", e->t_z2, 2 * BH},
+      {"c_dh1", e->c_dh1, 2 * BH}, {"c_dz1", e->c_dz1, 2 * BH, DBG_PLAIN, 0}, {"t_z2", e->t_z2, 2 * BH},
       {"q", e->q, 2 * B}, {"q_target", e->qt, 2 * B}, {"targ_q", e->y, B}, {"q_pi", e->q_pi, 2 * B}, {"dA", e->dA, 2 * B * e->a4},
+      {"grad_actor", e->Ga, ref_count(e->La, e->cfg.layer_norm), DBG_GRAD, 1},
+      {"grad_critics", e->Gc, 2 * ref_count(e->Lc, e->cfg.layer_norm), DBG_GRAD, 0},
+      {"prio_leaf", e->pt_leaf, e->cfg.rb_capacity, DBG_PRIO}, {"prio_sums", e->pt_sums, e->pt_groups, DBG_PRIO},      // (the one level above the leaves)
+      {"prio_max", e->pt_ctl ? &e->pt_ctl->max_prio : nullptr, 1, DBG_PRIO},
+      {"prio_weights", e->bs[0].w, B, DBG_PRIO},      // (the loss weights batch slot 0 carries)
+      {"pi_z2", e->pi_z2, (int64_t)e->pi_rows * HID, DBG_PI_Z2},      // the last chunk of the last policy query
   };
 }
 const char* sactd3_debug_names(void) {
-  return "X Xn Xp rew done logp_next logp_pi logp_alpha a_xh1 a_h1 a_z2 a_h2 a_xh2 a_rs2 a_tg a_du a_dz2 a_dh1 a_dz1 c_xh1 c_h1 c_z2 c_dz2 c_dh1 c_dz1 "
-         "t_z2 q q_target targ_q q_pi dA grad_actor grad_critics prio_leaf prio_sums prio_max prio_weights pi_z2";
+  static const std::string names = [] {
+    const sactd3_engine none;
+    std::string s;
+    for (const DbgEntry& d : dbg_table(&none)) s += (s.empty() ? "" : " ") + std::string(d.name);
+    return s;
+  }();
+  return names.c_str();
 }
 int64_t sactd3_debug_read(sactd3_engine* e, const char* name, float* dst, int64_t max_floats) {
   if (!e || !name) return SACTD3_EINVAL;
   USE_DEVICE(e);
-  if (((!strcmp(name, "grad_critics") || !strcmp(name, "c_dz1")) && e->grads_stale[0]) || ((!strcmp(name, "grad_actor") || !strcmp(name, "a_dz1")) && e->grads_stale[1]))
-    return e->fail(SACTD3_ESTATE, "debug_read: period graphs do not store this buffer; run an API-path update or sactd3_step first");
-  if (!strcmp(name, "grad_actor") || !strcmp(name, "grad_critics")) {   // reference (unpadded) layout
-    const bool act = !strcmp(name, "grad_actor");
-    const int64_t n = sactd3_param_count(e, act ? SACTD3_ACTOR : SACTD3_CRITICS);
-    if (!dst) return n;
-    if (max_floats < n) return e->fail(SACTD3_EINVAL, "debug_read: buffer too small");
-    RCCHK(read_arena(e, act ? e->Ga : e->Gc, act ? e->La : e->Lc, act ? 1 : 2, dst));
-    return n;
-  }
-  if (!strncmp(name, "prio_", 5)) return prio_debug_read(e, name, dst, max_floats);
-  if (!strcmp(name, "pi_z2")) {      // the last chunk of the last policy query
-    if (!e->pi_rows) return e->fail(SACTD3_ESTATE, "debug_read: no policy query has run (sactd3_policy_device first)");
-    const int64_t n = (int64_t)e->pi_rows * HID;
-    if (!dst) return n;
-    if (max_floats < n) return e->fail(SACTD3_EINVAL, "debug_read: buffer too small");
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(dst, e->pi_z2, sizeof(float) * n, hipMemcpyDeviceToHost));
-    return n;
-  }
   for (const DbgEntry& d : dbg_table(e)) {
     if (strcmp(d.name, name)) continue;
+    if (d.stale >= 0 && e->grads_stale[d.stale])
+      return e->fail(SACTD3_ESTATE, "debug_read: period graphs do not store this buffer; run an API-path update or sactd3_step first");
+    if (d.kind == DBG_PRIO && !e->pt_on) return e->fail(SACTD3_ESTATE, "debug_read: priorities are not enabled");
+    if (d.kind == DBG_PI_Z2 && !e->pi_rows) return e->fail(SACTD3_ESTATE, "debug_read: no policy query has run (sactd3_policy_device first)");
     if (!dst) return d.n;
     if (max_floats < d.n) return e->fail(SACTD3_EINVAL, "debug_read: buffer too small");
+    if (d.kind == DBG_GRAD) { RCCHK(read_arena(e, d.ptr, d.stale ? e->La : e->Lc, d.stale ? 1 : 2, dst)); return d.n; }
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(dst, d.ptr, sizeof(float) * d.n, hipMemcpyDeviceToHost));
     return d.n;
@@ -3600,7 +3560,7 @@ int sactd3_graph_kernel_count(sactd3_engine* e, int which_graph) {
 // first use), folded into [0, rb_len) so that a slot filled by sactd3_load_batch on a short ring does not count as refused rows
 static int time_rows_indices(sactd3_engine* e) {
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_kernel: buffer is empty");
-  if (!e->time_idx) RCCHK(dalloc(e, &e->time_idx, (size_t)e->B));
+  RCCHK(first_use_alloc(e, &e->time_idx, (size_t)e->B));
   std::vector<int> h(e->B);
   std::vector<long long> w(e->B);
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -3610,123 +3570,147 @@ static int time_rows_indices(sactd3_engine* e) {
   return 0;
 }
 
+// ---- sactd3_time_kernel: the bodies, one launch sequence each, and the table that names them
+// (slot_refilled: only where the kernel being timed overwrites batch slot 0)
+static int time_gather(EnqCtx& x) {   // a fresh index draw per launch (k_tick bumps the sample counter): rows come from HBM, not from the caches
+  slot_refilled(x.e, false, false);
+  RCCHK(enqueue_gather(x, x.e->ring, -1));
+  return launch_tick(x, &x.e->ctl->sample_ctr);
+}
+static int time_polyak(EnqCtx& x) { return enqueue_polyak(x, POLYAK_CRITICS | (x.e->cfg.prefer_td3_over_sac ? POLYAK_ACTOR : 0)); }
+static int time_trunk_critics(EnqCtx& x) {   // the 4-net hidden-layer launch of update_qnets (no state is modified)
+  sactd3_engine* e = x.e;
+  const TrunkGrp g[2] = {{e->Xn, e->Tc, e->t_z1, e->t_z2, nullptr, nullptr, nullptr},
+                         {e->X, e->Pc, e->c_z1, e->c_z2, e->c_xh1, e->c_h1, e->c_rs1}};
+  return enqueue_trunk(x, e->ldc, e->o + e->a, e->B, e->Lc, e->Lc.size, 2, 2, g, TrunkTicks{nullptr, nullptr, nullptr, nullptr, 0.f});
+}
+// the engine's own staging slab as six strided fields, one record per row: [s | a] [s'] [r] [d, as the float's first byte] and the index
+// in the two pad floats behind [r, d], which are 8-byte aligned
+static sactd3_device_fields_out slab_fields(const sactd3_engine* e) {
+  sactd3_device_fields_out f{};
+  f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
+  f.dones = (uint8_t*)(e->stage_dev + e->ldc + e->ldo + 1);
+  f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f;
+  f.index = (int64_t*)(e->stage_dev + e->ldc + e->ldo + 2); f.index_ld = e->rec_f / 2;
+  return f;
+}
+// the device-boundary pack kernels, fed from the slab read as five strided fields (batch_size rows into the batch slot / an env step's
+// max_envs rows into the ring: both are overwritten)
+static FieldSrc slab_src(const sactd3_engine* e) {
+  const sactd3_device_fields_out o = slab_fields(e);
+  const sactd3_device_fields f{o.obs, o.obs_ld, o.actions, o.actions_ld, o.rewards, o.rewards_ld, o.next_obs, o.next_obs_ld, o.dones, o.dones_ld};
+  return field_src(e, &f, 0);
+}
+static int time_batch_from_fields(EnqCtx& x) { slot_refilled(x.e, false, false); return launch_batch_fields(x, slab_src(x.e)); }
+static int time_rb_ingest_fields(EnqCtx& x) {
+  return launch_ingest_fields(x, slab_src(x.e), (int)std::min<int64_t>(std::min(x.e->maxn, x.e->B), ring_region(x.e)));
+}
+// the pack / unpack kernels of sactd3_predict_device on max_envs rows: observations read from the ring's records (the s columns,
+// row stride = the record), actions written to the acting scratch p_z1 (row stride = its 256 columns; the next trunk overwrites it)
+static int time_obs_from_field(EnqCtx& x) {
+  return launch_obs_pack(x, x.e->ring, x.e->rec_f, x.e->p_x, (int)std::min<int64_t>(x.e->maxn, x.e->cfg.rb_capacity));
+}
+static int time_act_to_field(EnqCtx& x) { return launch_act_unpack(x, x.e->p_z1, HID, x.e->maxn); }
+// the read-out kernels on batch_size rows, written into the slab as six strided fields (the mirror image of the pack kernels' sources);
+// the rows kernel takes its indices from time_idx (the current slot's idx, widened: prepared before anything is timed)
+static FieldDst slab_dst(const sactd3_engine* e) { const sactd3_device_fields_out f = slab_fields(e); return field_dst(e, &f, 0); }
+static int time_batch_to_fields(EnqCtx& x) { return launch_batch_out(x, slab_dst(x.e)); }
+static int time_rows_to_fields(EnqCtx& x) { return launch_rows_out(x, slab_dst(x.e), x.e->time_idx, 1, x.e->B, (int)x.e->rb_len); }
+// the pack / head kernels of sactd3_qvalues_device on Q_CHUNK rows of the scoring scratch: [s | a] read from the ring's records (row
+// stride = the record); the head on whatever the scratch's z2 holds, its values written over the scratch's z1
+static int time_q_kernels(EnqCtx& x, bool head) {
+  sactd3_engine* e = x.e;
+  RCCHK(q_scratch(e, false));
+  const int m = (int)std::min<int64_t>(Q_CHUNK, e->cfg.rb_capacity);
+  return head ? launch_q_head(x, e->Pc, m, e->qs_z1, 1, Q_CHUNK) : launch_sa_pack(x, e->ring, e->rec_f, e->ring + e->o, e->rec_f, m);
+}
+// the head kernel of sactd3_policy_device alone on Q_CHUNK rows of its scratch: whatever z2 holds (zeros before the first call), the
+// given actions zeros, native draws, every output into a scratch of this timing's own; its row counters are a second PiCtl's
+static int time_pi_head(EnqCtx& x) {
+  sactd3_engine* e = x.e;
+  RCCHK(pi_scratch(e));
+  const int a = e->a;
+  RCCHK(first_use_alloc(e, &e->pi_time, (size_t)Q_CHUNK * (6 * a + 2)));
+  auto slab = [&](int k) { return e->pi_time + (size_t)k * Q_CHUNK * a; };
+  sactd3_policy_io io{};
+  io.mode = slab(1); io.mode_ld = a;
+  if (!e->cfg.prefer_td3_over_sac) {
+    io.actions = slab(0); io.mean = slab(2); io.log_std = slab(3); io.sample = slab(4); io.eps_out = slab(5);
+    io.sample_logp = slab(6); io.action_logp = slab(6) + Q_CHUNK;
+    io.actions_ld = io.mean_ld = io.log_std_ld = io.sample_ld = io.eps_out_ld = a; io.sample_logp_ld = io.action_logp_ld = 1;
+  }
+  return launch_pi_head(x, pi_head_args(e, e->Pa, e->pi_ctl + 1, Q_CHUNK, 0, 0, io));
+}
+// the TD read-out kernel: the TD errors of whatever e->q / e->y hold, written into the engine's own staging slab
+static int time_td_to_field(EnqCtx& x) { return launch_td_out(x, x.e->stage_dev, 1, x.e->B); }
+// the draw kernel of sactd3_rb_sample_mixed alone (call form, the current P and m; the sample counter advances, the slot stays)
+static int time_mix_draw(EnqCtx& x) {
+  if (const char* why = mix_refusal(x.e)) { x.e->err = std::string("time_kernel: ") + why; return SACTD3_ESTATE; }
+  RCCHK(mix_alloc(x.e));
+  return launch_mix_draw(x);
+}
+// the engine-owned priorities (SACTD3_ESTATE before sactd3_prio_enable)
+static int time_prio_refusal(sactd3_engine* e) {
+  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "time_kernel: priorities are not enabled");
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_kernel: buffer is empty");
+  return 0;
+}
+// "prio_update": the write-back kernel on batch_size rows, indices as for "rows_to_fields", every priority 1 (those rows' priorities ARE overwritten)
+static int time_prio_update(EnqCtx& x) {
+  sactd3_engine* e = x.e;
+  RCCHK(time_prio_refusal(e));
+  if (!e->pt_ones) {
+    RCCHK(first_use_alloc(e, &e->pt_ones, (size_t)e->B, false));
+    const std::vector<float> one((size_t)e->B, 1.f);
+    HIPCHK(hipMemcpy(e->pt_ones, one.data(), sizeof(float) * one.size(), hipMemcpyHostToDevice));
+  }
+  PrioUpdateArgs g{};
+  g.n = e->B; g.idx = e->time_idx; g.idx_ld = 1; g.prio = e->pt_ones; g.prio_ld = 1;
+  return launch_prio_update(x, g);
+}
+// the staging calls, batch slot 0 overwritten: stage_ring_rows itself, without its counters.  "batch_from_index" / "_nstep" (steps 3,
+// stride 1): the one staging kernel on batch_size rows, indices from time_idx (as "rows_to_fields"), no weights; "prio_sample": one
+// whole sactd3_rb_sample_prioritized (beta 0.4: three launches, the draw counter advanced)
+static int time_stage(EnqCtx& x, bool prio_sample, bool chain) {
+  StageReq q{"time_kernel"};
+  q.internal = true;
+  if (prio_sample) { RCCHK(time_prio_refusal(x.e)); q.draw = DRAW_PRIO; q.beta = 0.4f; q.weighted = true; }
+  else { q.idx = x.e->time_idx; q.n = x.e->B; }
+  if (chain) { q.chain = true; q.steps = 3; q.stride = 1; }
+  return stage_ring_rows(x, q);
+}
+// needs_row_indices: time_rows_indices runs once in front of the warm-up
+struct TimedKernel { const char* name; bool needs_row_indices; int (*body)(EnqCtx&); };
+static const TimedKernel TIMED_KERNELS[] = {
+    {"gather", false, time_gather}, {"polyak", false, time_polyak}, {"trunk_critics", false, time_trunk_critics},
+    {"batch_from_fields", false, time_batch_from_fields}, {"rb_ingest_fields", false, time_rb_ingest_fields},
+    {"obs_from_field", false, time_obs_from_field}, {"act_to_field", false, time_act_to_field},
+    {"batch_to_fields", false, time_batch_to_fields}, {"rows_to_fields", true, time_rows_to_fields},
+    {"sa_from_fields", false, [](EnqCtx& x) { return time_q_kernels(x, false); }}, {"q_head", false, [](EnqCtx& x) { return time_q_kernels(x, true); }},
+    {"batch_from_index", true, [](EnqCtx& x) { return time_stage(x, false, false); }}, {"td_to_field", false, time_td_to_field},
+    {"prio_sample", false, [](EnqCtx& x) { return time_stage(x, true, false); }}, {"prio_update", true, time_prio_update},
+    {"batch_from_index_nstep", true, [](EnqCtx& x) { return time_stage(x, false, true); }}, {"mix_draw", false, time_mix_draw},
+    {"pi_head", false, time_pi_head},
+};
+
 int sactd3_time_kernel(sactd3_engine* e, const char* kernel, int iters, float* usec) {
   if (!e || !kernel || !usec || iters < 1) return SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
+  const TimedKernel* k = std::find_if(std::begin(TIMED_KERNELS), std::end(TIMED_KERNELS), [&](const TimedKernel& t) { return !strcmp(t.name, kernel); });
+  if (k == std::end(TIMED_KERNELS)) {
+    std::string names;
+    for (const TimedKernel& t : TIMED_KERNELS) names += (names.empty() ? "" : " | ") + std::string(t.name);
+    return e->fail(SACTD3_EINVAL, ("time_kernel: unknown kernel (" + names + ")").c_str());
+  }
   hipEvent_t t0, t1;
   HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1));
-  int rc = 0;
-  // the engine's own staging slab as five strided fields, one record per row: [s | a] [s'] [r] [d, as the float's first byte]
-  auto slab_fields = [&](auto& f) {
-    f.obs = e->stage_dev; f.actions = e->stage_dev + e->o; f.next_obs = e->stage_dev + e->ldc; f.rewards = e->stage_dev + e->ldc + e->ldo;
-    f.dones = (decltype(f.dones))(e->stage_dev + e->ldc + e->ldo + 1);
-    f.obs_ld = f.actions_ld = f.next_obs_ld = f.rewards_ld = e->rec_f; f.dones_ld = 4 * (int64_t)e->rec_f;
-  };
-  auto body = [&]() -> int {
-    EnqCtx x{e, e->stream};
-    // (slot_refilled: only where the kernel being timed overwrites batch slot 0)
-    if (!strcmp(kernel, "gather")) {   // a fresh index draw per launch (k_tick bumps the sample counter): rows come from HBM, not from the caches
-      slot_refilled(e, false, false);
-      RCCHK(enqueue_gather(x, e->ring, -1));
-      hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    if (!strcmp(kernel, "polyak")) return enqueue_polyak(x, POLYAK_CRITICS | (e->cfg.prefer_td3_over_sac ? POLYAK_ACTOR : 0));
-    if (!strcmp(kernel, "trunk_critics")) {   // the 4-net hidden-layer launch of update_qnets (no state is modified)
-      const TrunkGrp g[2] = {{e->Xn, e->Tc, e->t_z1, e->t_z2, nullptr, nullptr, nullptr},
-                             {e->X, e->Pc, e->c_z1, e->c_z2, e->c_xh1, e->c_h1, e->c_rs1}};
-      return enqueue_trunk(x, e->ldc, e->o + e->a, e->B, e->Lc, e->Lc.size, 2, 2, g, TrunkTicks{nullptr, nullptr, nullptr, nullptr, 0.f});
-    }
-    if (!strcmp(kernel, "batch_from_fields") || !strcmp(kernel, "rb_ingest_fields")) {
-      // the device-boundary pack kernels, fed from the engine's own staging slab read as five strided fields (batch_size rows into
-      // the batch slot / an env step's max_envs rows into the ring: both are overwritten)
-      sactd3_device_fields f{};
-      slab_fields(f);
-      if (!strcmp(kernel, "batch_from_fields")) { slot_refilled(e, false, false); return launch_batch_fields(e, field_src(e, &f, 0)); }
-      return launch_ingest_fields(e, field_src(e, &f, 0), (int)std::min<int64_t>(std::min(e->maxn, e->B), ring_region(e)));
-    }
-    // the pack / unpack kernels of sactd3_predict_device on max_envs rows: observations read from the ring's records (the s columns,
-    // row stride = the record), actions written to the acting scratch p_z1 (row stride = its 256 columns; the next trunk overwrites it)
-    if (!strcmp(kernel, "obs_from_field")) return launch_obs_pack(e, e->ring, e->rec_f, e->p_x, (int)std::min<int64_t>(e->maxn, e->cfg.rb_capacity));
-    if (!strcmp(kernel, "act_to_field")) return launch_act_unpack(e, e->p_z1, HID, e->maxn);
-    if (!strcmp(kernel, "batch_to_fields") || !strcmp(kernel, "rows_to_fields")) {
-      // the read-out kernels on batch_size rows, written into the engine's own staging slab as six strided fields (the mirror image
-      // of the pack kernels' sources above; the index goes to the two pad floats behind [r, d], which are 8-byte aligned); the rows
-      // kernel takes its indices from time_idx (the current slot's idx, widened: prepared below, before anything is timed)
-      sactd3_device_fields_out f{};
-      slab_fields(f);
-      f.index = (int64_t*)(e->stage_dev + e->ldc + e->ldo + 2); f.index_ld = e->rec_f / 2;
-      if (!strcmp(kernel, "batch_to_fields")) return launch_batch_out(e, field_dst(e, &f, 0));
-      return launch_rows_out(e, field_dst(e, &f, 0), e->time_idx, 1, e->B, (int)e->rb_len);
-    }
-    // the pack / head kernels of sactd3_qvalues_device on Q_CHUNK rows of the scoring scratch: [s | a] read from the ring's records (row
-    // stride = the record); the head on whatever the scratch's z2 holds, its values written over the scratch's z1
-    if (!strcmp(kernel, "sa_from_fields") || !strcmp(kernel, "q_head")) {
-      RCCHK(q_scratch(e, false));
-      const int m = (int)std::min<int64_t>(Q_CHUNK, e->cfg.rb_capacity);
-      if (!strcmp(kernel, "sa_from_fields")) return launch_sa_pack(e, e->ring, e->rec_f, e->ring + e->o, e->rec_f, m);
-      return launch_q_head(e, e->Pc, m, e->qs_z1, 1, Q_CHUNK);
-    }
-    // the head kernel of sactd3_policy_device alone on Q_CHUNK rows of its scratch: whatever z2 holds (zeros before the first call), the
-    // given actions zeros, native draws, every output into a scratch of this timing's own; its row counters are a second PiCtl's
-    if (!strcmp(kernel, "pi_head")) {
-      RCCHK(pi_scratch(e));
-      const int a = e->a;
-      if (!e->pi_time) RCCHK(dalloc(e, &e->pi_time, (size_t)Q_CHUNK * (6 * a + 2)));
-      auto slab = [&](int k) { return e->pi_time + (size_t)k * Q_CHUNK * a; };
-      sactd3_policy_io io{};
-      io.mode = slab(1); io.mode_ld = a;
-      if (!e->cfg.prefer_td3_over_sac) {
-        io.actions = slab(0); io.mean = slab(2); io.log_std = slab(3); io.sample = slab(4); io.eps_out = slab(5);
-        io.sample_logp = slab(6); io.action_logp = slab(6) + Q_CHUNK;
-        io.actions_ld = io.mean_ld = io.log_std_ld = io.sample_ld = io.eps_out_ld = a; io.sample_logp_ld = io.action_logp_ld = 1;
-      }
-      return launch_pi_head(e, pi_head_args(e, e->Pa, e->pi_ctl + 1, Q_CHUNK, 0, 0, io));
-    }
-    // the TD read-out kernel: the TD errors of whatever e->q / e->y hold, written into the engine's own staging slab
-    if (!strcmp(kernel, "td_to_field")) return launch_td_out(e, e->stage_dev, 1, e->B);
-    // the draw kernel of sactd3_rb_sample_mixed alone (call form, the current P and m; the sample counter advances, the slot stays)
-    if (!strcmp(kernel, "mix_draw")) {
-      if (const char* why = mix_refusal(e)) { e->err = std::string("time_kernel: ") + why; return SACTD3_ESTATE; }
-      RCCHK(mix_alloc(e));
-      return launch_mix_draw(e, false);
-    }
-    // the engine-owned priorities (SACTD3_ESTATE before sactd3_prio_enable): "prio_update" is the write-back kernel on batch_size rows,
-    // indices as for "rows_to_fields", every priority 1 (those rows' priorities ARE overwritten)
-    const bool prio_sample = !strcmp(kernel, "prio_sample"), prio_update = !strcmp(kernel, "prio_update");
-    if ((prio_sample || prio_update) && !e->pt_on) return e->fail(SACTD3_ESTATE, "time_kernel: priorities are not enabled");
-    if ((prio_sample || prio_update) && e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "time_kernel: buffer is empty");
-    if (prio_update) {
-      if (!e->pt_ones) {
-        RCCHK(dalloc(e, &e->pt_ones, (size_t)e->B, false));
-        const std::vector<float> one((size_t)e->B, 1.f);
-        HIPCHK(hipMemcpy(e->pt_ones, one.data(), sizeof(float) * one.size(), hipMemcpyHostToDevice));
-      }
-      PrioUpdateArgs g{};
-      g.n = e->B; g.idx = e->time_idx; g.idx_ld = 1; g.prio = e->pt_ones; g.prio_ld = 1;
-      return launch_prio_update(e, g);
-    }
-    // the staging calls, batch slot 0 overwritten: stage_ring_rows itself, without its counters.  "batch_from_index" / "_nstep" (steps 3,
-    // stride 1): the one staging kernel on batch_size rows, indices from time_idx (as "rows_to_fields"), no weights; "prio_sample": one
-    // whole sactd3_rb_sample_prioritized (beta 0.4: three launches, the draw counter advanced)
-    const bool one_step = !strcmp(kernel, "batch_from_index"), chain = !strcmp(kernel, "batch_from_index_nstep");
-    if (one_step || chain || prio_sample) {
-      StageReq q{"time_kernel"};
-      q.internal = true;
-      if (prio_sample) { q.draw = DRAW_PRIO; q.beta = 0.4f; q.weighted = true; }
-      else { q.idx = e->time_idx; q.n = e->B; }
-      if (chain) { q.chain = true; q.steps = 3; q.stride = 1; }
-      return stage_ring_rows(e, q);
-    }
-    return e->fail(SACTD3_EINVAL, "time_kernel: unknown kernel (gather | polyak | trunk_critics | batch_from_fields | rb_ingest_fields | obs_from_field | act_to_field | batch_to_fields | rows_to_fields | sa_from_fields | q_head | batch_from_index | td_to_field | prio_sample | prio_update | batch_from_index_nstep | mix_draw | pi_head)");
-  };
-  if (!strcmp(kernel, "rows_to_fields") || !strcmp(kernel, "batch_from_index") || !strcmp(kernel, "prio_update") || !strcmp(kernel, "batch_from_index_nstep")) rc = time_rows_indices(e);
-  for (int i = 0; i < 3 && rc == 0; ++i) rc = body();   // warm-up
+  EnqCtx x{e, e->stream};
+  int rc = k->needs_row_indices ? time_rows_indices(e) : 0;
+  for (int i = 0; i < 3 && rc == 0; ++i) rc = k->body(x);   // warm-up
   if (rc == 0) {
     hipEventRecord(t0, e->stream);
-    for (int i = 0; i < iters && rc == 0; ++i) rc = body();
+    for (int i = 0; i < iters && rc == 0; ++i) rc = k->body(x);
     hipEventRecord(t1, e->stream);
     hipEventSynchronize(t1);
     float ms = 0.f;
@@ -3818,19 +3802,21 @@ int sactd3_time_gather_sweep(sactd3_engine* e, int batch, int iters, float* usec
     g.cpb = (int)(((long)batch * e->rec4 + 256L * grid.x - 1) / (256L * grid.x));
     hipEvent_t t0, t1;
     hipEventCreate(&t0); hipEventCreate(&t1);
-    for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(k_gather, grid, dim3(256), 0, e->stream, g);
+    EnqCtx x{e, e->stream};
+    const auto gather = [&](bool tick) -> int {
+      LAUNCH_ON(k_gather, grid, dim3(256), g);
+      return tick ? launch_tick(x, &e->ctl->sample_ctr) : 0;
+    };
+    for (int i = 0; i < 2 && rc == 0; ++i) rc = gather(false);
     hipEventRecord(t0, e->stream);
-    for (int i = 0; i < iters; ++i) {
-      hipLaunchKernelGGL(k_gather, grid, dim3(256), 0, e->stream, g);
-      hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, e->stream, &e->ctl->sample_ctr, (int*)nullptr);
-    }
+    for (int i = 0; i < iters && rc == 0; ++i) rc = gather(true);
     hipEventRecord(t1, e->stream);
     he = hipEventSynchronize(t1);
     float ms = 0.f;
     hipEventElapsedTime(&ms, t0, t1);
     *usec = ms * 1000.f / (float)iters;
     hipEventDestroy(t0); hipEventDestroy(t1);
-    if (he != hipSuccess) rc = e->fail(SACTD3_EHIP, "gather sweep", he);
+    if (rc == 0 && he != hipSuccess) rc = e->fail(SACTD3_EHIP, "gather sweep", he);
     // 2*B*T + 4*B with T = 4*(2o+a+1)+1 bytes
     if (algo_bytes) *algo_bytes = 2.0 * batch * (4.0 * (2 * e->o + e->a + 1) + 1.0) + 4.0 * batch;
   }

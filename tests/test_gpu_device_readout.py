@@ -3,6 +3,7 @@ read-back it stands beside.  Everything here is an equality at small shapes: wha
 bit for bit, what sactd3_read_batch returns for the same slot or the same ring rows; nothing outside the destinations' windows is
 written; a read-out is invisible to training; and the counters follow from the calls, not from timing."""
 import ctypes as C
+import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -459,3 +460,58 @@ def test_time_kernel_knows_the_readout_kernels(env):
     eng.step(True)
     eng.sync()
     eng.close()
+
+
+# ------------------------------------------------------------------------------------------ 11. the name tables cannot drift
+STATE_REFUSALS = r"error -3.*(priorities are not enabled|no row is pinned|rows are pinned)"
+
+
+def test_every_timing_and_debug_name_is_served_on_some_engine():
+    """Every name sactd3_time_kernel lists in its own refusal, and every word of sactd3_debug_names(), is served by at least one of two
+    tiny engines whose states exclude each other (priorities enabled / rows pinned with a mixed draw); the other engine serves it too
+    or refuses it for its STATE -- never as an unknown name.  (Besides the two refusals a name can meet for a state it lacks,
+    "priorities are not enabled" and "no row is pinned", the pinned engine has a third: "batch_from_index_nstep" stages chains, which
+    a pinned ring refuses with "rows are pinned".)"""
+    o, a, bound = DIMS["hopper"]
+
+    def tiny(prepare):
+        cfg = P.Config(ob_dim=o, ac_dim=a, batch_size=32, rb_capacity=256, max_envs=4, seed=0)
+        eng = P.Engine(cfg, [-bound] * a, [bound] * a)
+        torch.manual_seed(0)
+        actor, critics = P.schema.reference_initial_params(o, a, False, True)
+        for which, flat in ((_lib.ACTOR, actor), (_lib.ACTOR_TARGET, actor), (_lib.CRITICS, critics), (_lib.CRITICS_TARGET, critics)):
+            eng.set_params(which, flat)
+        eng.rb_fill_synthetic(64, seed=0)
+        prepare(eng)
+        eng.step(True)                                            # q, y and the slot exist
+        eng.policy(np.zeros((4, o), np.float32))                  # ... and pi_z2
+        return eng
+
+    def pin_and_mix(eng):
+        eng.rb_pin(16)
+        eng.rb_set_mix(8)
+
+    engines = [tiny(lambda eng: eng.prio_enable()), tiny(pin_and_mix)]
+    with pytest.raises(P.EngineError, match=r"error -1.*time_kernel: unknown kernel \(") as refusal:
+        engines[0].time_kernel("no_such_kernel", 1)
+    kernels = str(refusal.value).split("(")[-1].split(")")[0].split(" | ")
+    assert len(kernels) >= 18 and "gather" in kernels and "pi_head" in kernels, kernels
+
+    def served(call, names, unknown):
+        for name in names:
+            ok = 0
+            for eng in engines:
+                try:
+                    ok += bool(call(eng, name))
+                except P.EngineError as err:
+                    assert unknown not in str(err), (name, str(err))
+                    assert re.search(STATE_REFUSALS, str(err)), (name, str(err))
+            assert ok >= 1, name
+
+    served(lambda eng, name: eng.time_kernel(name, 2) > 0.0, kernels, "unknown kernel")
+    words = engines[0].lib.sactd3_debug_names().decode().split()
+    assert len(words) >= 38 and len(set(words)) == len(words), words
+    served(lambda eng, name: eng.debug_read(name).size > 0, words, "unknown buffer name")
+    for eng in engines:
+        eng.sync()
+        eng.close()
