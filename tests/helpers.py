@@ -1,5 +1,6 @@
 """Shared synthetic-data helpers for the tests (shapes from SURVEY.md section 8d)."""
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -75,6 +76,46 @@ def randomize_ln(agent, seed=1):
         for net in [agent.actor_target, *agent.qnets_target]:
             for p in net.parameters():
                 p.add_(0.01 * torch.randn(p.shape, generator=g))
+
+
+class FakeDeviceArray:
+    """a stand-in for a device array on the CPU -- what the mirror's routing helper may rely on: __cuda_array_interface__
+    (version 3), detach(), and the array library's own conversions"""
+    _next = 0x7F0000000000
+
+    def __init__(self, shape, typestr="<f4", strides=None, device_index=0, log=None):
+        FakeDeviceArray._next += 1 << 20
+        self.ptr, self.shape, self.typestr, self.strides = FakeDeviceArray._next, tuple(shape), typestr, strides
+        self.device = SimpleNamespace(index=device_index)
+        self.log = [] if log is None else log
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": self.shape, "typestr": self.typestr, "data": (self.ptr, False), "version": 3, "strides": self.strides}
+
+    def detach(self):
+        return self
+
+    def to(self, dtype):
+        return FakeDeviceArray(self.shape, "<f4", None, self.device.index, self.log + [("to", str(dtype))])
+
+    def contiguous(self):
+        return FakeDeviceArray(self.shape, self.typestr, None, self.device.index, self.log + ["contiguous"])
+
+    def __ne__(self, other):
+        assert other == 0
+        return FakeDeviceArray(self.shape, "|b1", None, self.device.index, self.log + ["!= 0"])
+
+    def cpu(self):
+        raise AssertionError("the device route must not copy to the host")
+
+
+def five(n=8, o=11, a=3, **over):
+    """[obs, act, rew, nobs, done] as FakeDeviceArrays of n rows; `over` replaces fields by name"""
+    d = dict(obs=FakeDeviceArray((n, o)), act=FakeDeviceArray((n, a)), rew=FakeDeviceArray((n,)), nobs=FakeDeviceArray((n, o)),
+             done=FakeDeviceArray((n,), "|b1"))
+    d.update(over)
+    return [d[k] for k in ("obs", "act", "rew", "nobs", "done")]
 
 
 # ---- observed parity deltas: tests report what they measured, the session writes it out (tests/conftest.py), and the

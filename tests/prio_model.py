@@ -18,6 +18,8 @@ tests/test_prio_model.py checks this file on the CPU: against tests/bounds.py:pr
 copy of this source with one line changed (its DEFECTS) is told apart."""
 from __future__ import annotations
 
+import functools
+from types import SimpleNamespace
 from typing import NamedTuple
 
 import numpy as np
@@ -205,3 +207,121 @@ def write_back(t, length, idx, prio):
     for s, p in zip(idx[ok], prio[ok]):
         leaf[s] = p
     return resum(t._replace(leaf=leaf), idx[ok] // G), int((~ok).sum())
+
+
+# ------------------------------------------------------------------------------------------ the case table
+# rings, leaves, directed uniforms and the model's draws of them: tests/test_prio_model.py checks them on the CPU,
+# tests/test_gpu_priorities_scale.py holds the device to the same cases
+FILLS = ["uniform", "wide", "zero-groups", "spike"]
+NAMED_GROUPS = (0, 1, 511, 975, 976, 1022, 1023, 1024, 1025)
+# how many seeds fallback_seed tries: 400 where a ring costs microseconds, 40 where it costs 20 ms
+SEEDS = {1024: 400, 1025: 400, 1000: 400, 5000: 400, 1_000_000: 40, 1_050_076: 40, 1_100_000: 40}
+
+
+def case_id(c):
+    return f"{c[0]}-{c[1]}-{c[2]}"
+
+
+def uniform_leaves(held, seed):
+    return np.random.default_rng(seed).uniform(0.05, 3.0, held).astype(F32)
+
+
+@functools.lru_cache(maxsize=None)
+def fallback_seed(cap, held):
+    """the first seed of SEEDS[cap] whose uniform(0.05, 3) ring falls back at u = 1 - 2^-24: at the group stage where the ring has
+    more than eight groups, at the leaf stage below.  -> (seed, found); seed 0 where none does"""
+    want_group = cap > 8 * G
+    for seed in range(SEEDS[cap]):
+        path = draw(table(uniform_leaves(held, seed), cap), held, U_MAX)[3]
+        if path.group_fallback if want_group else (path.leaf_fallback and not path.group_fallback):
+            return seed, True
+    return 0, False
+
+
+def leaves(cap, held, fill):
+    """the leaves of rows [0, held) of one case"""
+    if fill == "uniform":
+        return uniform_leaves(held, fallback_seed(cap, held)[0])
+    rng = np.random.default_rng(1000 + held % 997)
+    last_group = (held - 1) // G
+    if fill == "wide":                        # exp(N(0, 1.5))^0.6 with exact zeros: 5000 in a million, the ends and group edges among them
+        lf = (np.exp(rng.normal(0.0, 1.5, held)) ** 0.6).astype(F32)
+        lf[rng.choice(held, max(held * 5000 // 1_050_039, 24), replace=False)] = 0.0
+        edges = [0, held - 1, held - 2] + [s for g in NAMED_GROUPS[1:] for s in (g * G - 1, g * G, g * G + 4) if s < held]
+        lf[edges] = 0.0
+        return lf
+    if fill == "zero-groups":                 # whole groups without mass: 1022, 1023, 1024 (around the chunk boundary) and the last
+        lf = rng.uniform(0.05, 3.0, held).astype(F32)
+        for g in (1022, 1023, 1024, last_group):
+            if g * G < held and last_group > 0:
+                lf[g * G:(g + 1) * G] = 0.0
+        if last_group == 0:                   # (one group: its second half)
+            lf[held // 2:] = 0.0
+        return lf
+    lf = np.full(held, 1e-3, F32)             # spike: one leaf of 1e6 among leaves of 1e-3
+    lf[(2 * held) // 3] = 1e6
+    return lf
+
+
+def aim(T, target):
+    """a float32 u <= U_MAX with fl32(u T) == target exactly, or None"""
+    u = F32(np.float64(target) / np.float64(T))
+    cand = [u]
+    lo = hi = u
+    for _ in range(4):
+        lo, hi = np.nextafter(lo, F32(-1)), np.nextafter(hi, F32(2))
+        cand += [lo, hi]
+    for c in cand:
+        if 0 <= c <= U_MAX and F32(c * T) == F32(target):
+            return c
+    return None
+
+
+def directed(t, held, C):
+    """the uniforms of one case -> (u float32 [n], exact): 0 and the largest; the centre and both edges of the first and last
+    positive slot and of the slots on both sides of every named group boundary (the chunk boundary is group 1024's); the edges and
+    centres of the named groups; 32 random ones; and `exact`, {index into u: (level, position)} for the uniforms whose m equals one of
+    the model's own inclusive running sums -- at the top level (of a named group) and at the leaf level (inside group 0)."""
+    leaf = t.leaf[:held]
+    T64, T = C[-1], draw(t, held, 0.0)[1]
+    live = np.flatnonzero(leaf > 0)
+    slots = {int(live[0]), int(live[-1]), held - 1}
+    groups = [g for g in NAMED_GROUPS if g * G < held] + [(held - 1) // G]
+    for g in groups:
+        slots.update(s for s in (g * G - 1, g * G, (g + 1) * G - 1, (g + 1) * G) if 0 <= s < held)
+    us = [0.0, float(U_MAX)]
+    for s in sorted(slots):
+        lo, hi = (C[s - 1] if s else 0.0), C[s]
+        us += [lo / T64, 0.5 * (lo + hi) / T64, hi / T64]
+    for g in groups:
+        lo, hi = (C[g * G - 1] if g else 0.0), C[min((g + 1) * G, held) - 1]
+        us += [lo / T64, 0.5 * (lo + hi) / T64, hi / T64]
+    us += list(np.random.default_rng(7).random(32))
+    us = [min(max(F32(u), F32(0)), U_MAX) for u in us]
+    exact = {}
+    top = top_running(t)
+    for g in groups:
+        u = aim(T, top[g]) if t.sums[g] > 0 else None
+        if u is not None:
+            exact[len(us)] = ("top", g)
+            us.append(u)
+    inc0 = leaf_running(t, 0)
+    for s in [s for s in (0, 1, 2, 5, 6, 254, 257, 258, 509, 510, 513, 769, 770, 1021, 1022) if s < held and leaf[s] > 0]:
+        u = aim(T, inc0[s])
+        if u is not None:
+            exact[len(us)] = ("leaf", s)
+            us.append(u)
+    return np.array(us, F32), exact
+
+
+@functools.lru_cache(maxsize=None)
+def case(cap, held, fill):
+    """one case, computed once and never written: leaves, table, float64 running sums, directed uniforms, the model's draws"""
+    leaf = leaves(cap, held, fill)
+    t = table(leaf, cap)
+    C = np.cumsum(leaf.astype(np.float64))
+    u, exact = directed(t, held, C)
+    slots, T, m, paths = draws(t, held, u)
+    for a in (leaf, t.leaf, t.sums, C, u, slots, m):
+        a.setflags(write=False)
+    return SimpleNamespace(cap=cap, held=held, fill=fill, leaf=leaf, table=t, C=C, u=u, exact=exact, slots=slots, T=T, m=m, paths=paths)

@@ -15,7 +15,7 @@ from tests.helpers import DIMS, observe
 
 H = 256
 F32 = np.float32
-K2 = "fc_stack.fc_block_2"
+K1, K2 = "fc_stack.fc_block_1", "fc_stack.fc_block_2"
 MEAN_OFFSETS = (0.0, 3.0, -3.0, 6.0, -9.0, 12.0)
 LOGSTD_OFFSETS = (0.0, 4.0, -4.0, 9.0, -9.0)
 MAX_UNDECIDED = 3
@@ -375,3 +375,98 @@ def check_head_bwd(rec, R, c, log_alpha, bc=None):
         _chk(rec, f"actor grad {K2}.ln.bias", R["grads"][f"{K2}.ln.bias"], *bd.tail_colsums(dy, edy))
     _chk(rec, "actor grad head.weight", R["grads"]["head.weight"], *bd.batch_wgrad(R["a_du"], R["a_h2"]))
     _chk(rec, "actor grad head.bias", R["grads"]["head.bias"], *bd.batch_sum(R["a_du"]))
+
+
+# ------------------------------------------------------------------------------------------ fp32 building blocks
+# the kernels' summation orders in numpy float32, for the CPU emulations of tests/test_tail_bounds.py and tests/test_policy_bounds.py
+
+def lanes(x):
+    """[B, 256] -> [B, 16 lanes, 4 q, 4]: lane `sub` holds columns 4 sub + 64 q .. + 3 (Row16)"""
+    return x.reshape(x.shape[0], 4, 16, 4).transpose(0, 2, 1, 3)
+
+
+def tree16(v):
+    """row16_sum: xor 1, xor 2, half mirror, mirror"""
+    i = np.arange(16)
+    for perm in (i ^ 1, i ^ 2, (i & 8) | (7 - (i & 7)), 15 - i):
+        v = v + v[:, perm]
+    return v[:, 0]
+
+
+def sum4(v):
+    return (v[..., 0] + v[..., 1]) + (v[..., 2] + v[..., 3])
+
+
+def row_total(x):
+    s = sum4(lanes(x))
+    return tree16((s[..., 0] + s[..., 1]) + (s[..., 2] + s[..., 3]))
+
+
+def row_dot(a, b):
+    p = lanes(a) * lanes(b)
+    d = ((p[..., 0] + p[..., 1]) + p[..., 2]) + p[..., 3]
+    return tree16((d[..., 0] + d[..., 1]) + (d[..., 2] + d[..., 3]))
+
+
+def ln_fwd(z, g, be, ln, eps_outside=False):
+    if not ln:
+        return z, z, np.ones(z.shape[0], F32)
+    mean = row_total(z) * F32(1.0 / H)
+    d = z - mean[:, None]
+    var = row_dot(d, d) * F32(1.0 / H)
+    rstd = F32(1) / (np.sqrt(var) + F32(1e-5)) if eps_outside else F32(1) / np.sqrt(var + F32(1e-5))
+    xh = d * rstd[:, None]
+    return xh, xh * g + be, rstd.astype(F32)
+
+
+def ln_bwd(dy, xh, rstd, g, ln):
+    if not ln:
+        return dy
+    dxh = dy * g
+    m1 = row_total(dxh) * F32(1.0 / H)
+    m2 = row_dot(dxh, xh) * F32(1.0 / H)
+    return (dxh - m1[:, None] - xh * m2[:, None]) * rstd[:, None]
+
+
+def block_colsum(vals, rpb, drop_last_group=False):
+    """column sums per rpb-row block (rows in order), then over the blocks in order"""
+    B = vals.shape[0]
+    if drop_last_group:
+        B = 4 * ((B - 1) // 4)
+    tot = np.zeros(vals.shape[1:], F32)
+    for b0 in range(0, B, rpb):
+        acc = np.zeros(vals.shape[1:], F32)
+        for r in range(b0, min(b0 + rpb, B)):
+            acc = acc + vals[r]
+        tot = tot + acc
+    return tot
+
+
+def ln_of(p, ln):
+    return (p[f"{K2}.ln.weight"], p[f"{K2}.ln.bias"]) if ln else (None, None)
+
+
+def trunk(p, X, ln, stores=False):
+    """z2 of a net on rows X (torch-free fp32: the trunk GEMMs have their own tests); stores: also h1, xhat1, rstd1"""
+    z1 = (X @ p[f"{K1}.fc.weight"].T + p[f"{K1}.fc.bias"]).astype(F32)
+    xh1, rs1 = z1, np.ones(len(X), F32)
+    if ln:
+        mu = z1.mean(1, keepdims=True)
+        rs1 = (F32(1) / np.sqrt(((z1 - mu) ** 2).mean(1, keepdims=True) + F32(1e-5))).astype(F32)
+        xh1 = ((z1 - mu) * rs1).astype(F32)
+        z1, rs1 = (xh1 * p[f"{K1}.ln.weight"] + p[f"{K1}.ln.bias"]).astype(F32), rs1[:, 0]
+    h1 = np.maximum(z1, F32(0))
+    z2 = (h1 @ p[f"{K2}.fc.weight"].T + p[f"{K2}.fc.bias"]).astype(F32)
+    return (z2, h1, xh1, rs1) if stores else z2
+
+
+def head(h, Wh, bh, narrow):
+    if narrow:        # one dot product per output, reduced over the row's 16 lanes
+        return np.stack([row_dot(h, np.broadcast_to(Wh[n], h.shape)) for n in range(Wh.shape[0])], 1) + bh
+    part = []         # K split over 4 waves of 64 columns, each accumulated in order; then ((p0 + p1) + (p2 + p3)) + bh
+    for w in range(4):
+        acc = np.zeros((h.shape[0], Wh.shape[0]), F32)
+        for k in range(64 * w, 64 * w + 64):
+            acc = acc + h[:, k:k + 1] * Wh[None, :, k]
+        part.append(acc)
+    return ((part[0] + part[1]) + (part[2] + part[3])) + bh

@@ -9,47 +9,10 @@ import pytest
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod
+from tests.helpers import FakeDeviceArray, five
 
 O, A = 11, 3
 ENGINE = SimpleNamespace(device_inputs=True, cfg=SimpleNamespace(ob_dim=O, ac_dim=A, device_id=0))
-
-
-class FakeDeviceArray:
-    """what the helper may rely on: __cuda_array_interface__ (version 3), detach(), and the array library's own conversions"""
-    _next = 0x7F0000000000
-
-    def __init__(self, shape, typestr="<f4", strides=None, device_index=0, log=None):
-        FakeDeviceArray._next += 1 << 20
-        self.ptr, self.shape, self.typestr, self.strides = FakeDeviceArray._next, tuple(shape), typestr, strides
-        self.device = SimpleNamespace(index=device_index)
-        self.log = [] if log is None else log
-
-    @property
-    def __cuda_array_interface__(self):
-        return {"shape": self.shape, "typestr": self.typestr, "data": (self.ptr, False), "version": 3, "strides": self.strides}
-
-    def detach(self):
-        return self
-
-    def to(self, dtype):
-        return FakeDeviceArray(self.shape, "<f4", None, self.device.index, self.log + [("to", str(dtype))])
-
-    def contiguous(self):
-        return FakeDeviceArray(self.shape, self.typestr, None, self.device.index, self.log + ["contiguous"])
-
-    def __ne__(self, other):
-        assert other == 0
-        return FakeDeviceArray(self.shape, "|b1", None, self.device.index, self.log + ["!= 0"])
-
-    def cpu(self):
-        raise AssertionError("the device route must not copy to the host")
-
-
-def five(n=8, **over):
-    d = dict(obs=FakeDeviceArray((n, O)), act=FakeDeviceArray((n, A)), rew=FakeDeviceArray((n,)), nobs=FakeDeviceArray((n, O)),
-             done=FakeDeviceArray((n,), "|b1"))
-    d.update(over)
-    return [d[k] for k in ("obs", "act", "rew", "nobs", "done")]
 
 
 def test_contiguous_fields_go_to_the_device_as_they_are():

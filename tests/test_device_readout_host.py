@@ -10,7 +10,7 @@ import pytest
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod
-from tests.test_device_boundary_host import FakeDeviceArray
+from tests.helpers import FakeDeviceArray
 
 O, A, N = 11, 3, 8
 ENGINE = SimpleNamespace(device_inputs=True, cfg=SimpleNamespace(ob_dim=O, ac_dim=A, device_id=0, batch_size=N))

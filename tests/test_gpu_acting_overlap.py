@@ -10,16 +10,12 @@ import pytest
 import torch
 
 from oracle.sac_td3_ref import Hps, RefAgent
+from tests.gpu_support import P, _lib, assert_same_state, close, close_engines, loop, make_pair, push_params, track  # noqa: F401
 from tests.helpers import DIMS, synth_transitions
-from tests.test_gpu_engine import close, make_pair, push_params
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, loop  # noqa: E402
-
 WORKLOADS = [("sac", "hopper"), ("td3", "halfcheetah"), ("sac", "humanoid")]
-SETS = (_lib.ACTOR, _lib.CRITICS, _lib.ACTOR_TARGET, _lib.CRITICS_TARGET, _lib.LOG_ALPHA)
 
 
 def two_engines(algo, env, B, **kw):
@@ -61,7 +57,6 @@ def test_begin_end_returns_what_predict_returns(algo, env):
     # the two entry points share the counter: a serial call on B continues the stream where its begun calls left it
     obs = torch.randn(4, o, generator=torch.Generator().manual_seed(77))
     assert np.array_equal(A.predict(obs, explore=True), B.predict(obs, explore=True))
-    A.close(); B.close()
 
 
 def test_begin_end_with_a_multi_block_tail():
@@ -71,7 +66,8 @@ def test_begin_end_with_a_multi_block_tail():
     hps = Hps.sac(batch_size=32)
     torch.manual_seed(0)
     ref = RefAgent(o, a, [-bound] * a, [bound] * a, hps)
-    A, B = [P.Engine(P.Config.from_hps(hps, o, a, rb_capacity=256, max_envs=48, seed=7), [-bound] * a, [bound] * a) for _ in range(2)]
+    A, B = [track(P.Engine(P.Config.from_hps(hps, o, a, rb_capacity=256, max_envs=48, seed=7), [-bound] * a, [bound] * a))
+            for _ in range(2)]
     for e in (A, B):
         push_params(e, ref)
     obs = torch.randn(40, o, generator=torch.Generator().manual_seed(3))
@@ -82,7 +78,6 @@ def test_begin_end_with_a_multi_block_tail():
         assert np.array_equal(A.predict(obs, explore=True), begin_end(B, obs, True)), k
         assert np.array_equal(A.read_noise(_lib.SITE_PREDICT, 40), B.read_noise(_lib.SITE_PREDICT, 40))
     assert B.acting_stats()["begun"] == 4 and B.acting_stats()["ended_by_spin"] == 0
-    A.close(); B.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. / 3. the loop
@@ -109,22 +104,6 @@ def acting_loop(eng, dims, n_iter, overlapped, after_all=False, rows=4, prefill=
     return acts
 
 
-def assert_same_state(A, B, n_iter, rows=4, prefill=256):
-    for which in SETS:
-        assert np.array_equal(A.get_params(which), B.get_params(which)), ("params", which)
-    for which in (_lib.ACTOR, _lib.CRITICS, _lib.LOG_ALPHA):
-        (m1, v1, t1), (m2, v2, t2) = A.get_adam_state(which), B.get_adam_state(which)
-        assert t1 == t2 and np.array_equal(m1, m2) and np.array_equal(v1, v2), ("adam", which)
-    assert A.read_metrics() == B.read_metrics()
-    assert A.rb_len() == B.rb_len() == prefill + rows * n_iter
-    idx = prefill + np.arange(A.cfg.batch_size) % (rows * n_iter)                     # the rows the loop wrote
-    for e in (A, B):
-        e.rb_sample_with_indices(idx)
-    x, y = A.read_batch(), B.read_batch()
-    for k in x:
-        assert np.array_equal(x[k], y[k]), ("batch", k)
-
-
 LOOPS = [
     ("sac", "hopper", 256, 90, dict(use_graphs=True), False),
     ("sac", "hopper", 256, 90, dict(use_graphs=False), False),
@@ -145,8 +124,8 @@ def test_overlapped_loop_is_the_serial_loop_bit_for_bit(algo, env, B, n_iter, kw
     for i, (x, y) in enumerate(zip(want, got)):
         assert np.array_equal(x, y), ("actions of iteration", i)
     assert not np.array_equal(want[0], want[-1])
-    assert_same_state(A, Bn, n_iter)
-    A.close(); Bn.close()
+    assert_same_state(A, Bn, "ring")                             # every ring row: the prefill and the rows the loop wrote
+    assert A.rb_len() == Bn.rb_len() == 256 + 4 * n_iter
 
 
 @pytest.mark.parametrize("after_all,want_waits", [(False, 30), (True, 90)])
@@ -165,7 +144,6 @@ def test_the_ordering_policy_engaged(after_all, want_waits):
     assert d["begin_waited_for_learner"] == want_waits
     assert d["learner_waited_for_acting"] == 30
     assert 0 <= d["ended_by_spin"] <= 90
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 4. write after read
@@ -190,7 +168,6 @@ def test_actor_writes_wait_for_the_call_in_flight():
     assert np.array_equal(B.predict(obs, False), want[0])        # (40 rounds: p0 is in place again)
     assert np.array_equal(begin_end(B, obs, False), want[0])
     assert B.acting_stats()["learner_waited_for_acting"] - s0["learner_waited_for_acting"] >= 40
-    A.close(); B.close()
 
 
 # ------------------------------------------------------------------------------------------ 5. state errors
@@ -218,7 +195,6 @@ def test_state_errors_leave_the_engine_usable():
     assert np.array_equal(begin_end(B, obs, True), A.predict(obs, True))
     B.predict_begin(obs, True)
     B.close()                                                     # with a call in flight: returns
-    A.close()
 
 
 def test_null_arguments_through_the_raw_abi():
@@ -237,7 +213,6 @@ def test_null_arguments_through_the_raw_abi():
     assert lib.sactd3_predict_end(h, None) == _lib.EINVAL                                      # ... and does not end the call
     assert lib.sactd3_predict_end(h, out.ctypes.data_as(fp)) == 0
     assert np.array_equal(out, eng.predict(obs, False))
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 6. end to end
@@ -262,7 +237,7 @@ def test_train_loop_with_overlap_equals_the_serial_train_loop(tmp_path):
         assert evals == [800, 1600, 2400] and all(np.isfinite(v) for v in m.values())
         stats = agent.engine.acting_stats()
         assert (stats["begun"] > 0) == overlap
-        logs.append(dict(metrics=m, actor=agent.engine.get_params(_lib.ACTOR), critics=agent.engine.get_params(_lib.CRITICS),
+        logs.append(dict(metrics=m, actor=track(agent.engine).get_params(_lib.ACTOR), critics=agent.engine.get_params(_lib.CRITICS),
                          counters=(agent.timesteps_so_far, agent.qnet_updates_so_far, agent.actor_updates_so_far), rb=len(agent.rb),
                          history=[(h["timestep"], h["length"], h["return"]) for h in ev.history],
                          next_action=agent.predict({"observations": np.ones((n, o), np.float32)}, explore=True)))

@@ -10,52 +10,16 @@ import pytest
 import torch
 
 from oracle.sac_td3_ref import Hps
+from tests.gpu_support import (DEV, PACK_SHAPES, P, _lib, agent_mod, assert_same_state, close_engines, cuda, extend_device, load_device,  # noqa: F401
+                               make_pair, rows, track)
 from tests.helpers import DIMS, synth_transitions
-from tests.test_gpu_engine import make_pair
 
 pytestmark = pytest.mark.gpu
-
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod  # noqa: E402
-
-SETS = (_lib.ACTOR, _lib.CRITICS, _lib.ACTOR_TARGET, _lib.CRITICS_TARGET, _lib.LOG_ALPHA)
-# shapes for the places a pack kernel can go wrong: o % 4 = 1 and a one-line record; o % 4 = 3 with s|a ending inside a chunk;
-# o % 4 = 0 with an odd a; an action wider than the observation; 196 chunks per record
-PACK_SHAPES = ["td3_2", "hopper", "o48a17", "o3a32", "humanoid"]
-DEV = "cuda:0"
-
-
-def fields_of(eng, five):
-    """(fields, n, keep) of five CUDA tensors, through the mirror's own routing helper"""
-    got = agent_mod._device_route(eng, *five)
-    assert got is not None, "the routing helper sent CUDA tensors down the host route"
-    return got
 
 
 def raw_fields(five):
     """contiguous CUDA tensors -> [(address, row stride in elements)]"""
     return [(t.data_ptr(), t.shape[1] if t.dim() == 2 else 1) for t in five]
-
-
-def extend_device(eng, five):
-    fields, n, keep = fields_of(eng, five)
-    eng.rb_extend_fields_device(fields, n, torch.cuda.current_stream().cuda_stream)
-
-
-def load_device(eng, five):
-    fields, n, keep = fields_of(eng, five)
-    eng.load_batch_device(fields, n, torch.cuda.current_stream().cuda_stream)
-
-
-def rows(n, o, a, bound, seed, first=0):
-    """n transitions whose every 7th flag (counted from row `first` of the run) is done"""
-    obs, act, rew, nobs, _ = synth_transitions(n, o, a, bound, seed=seed)
-    done = (torch.arange(first, first + n) % 7) == 0
-    return obs, act, rew, nobs, done
-
-
-def cuda(five):
-    return tuple(t.to(DEV) for t in five)
 
 
 def strided(five):
@@ -68,15 +32,6 @@ def strided(five):
     flags = torch.ones((n, 3), dtype=torch.bool, device=DEV)
     flags[:, 1] = done.to(DEV)
     return wide[:, 1:1 + o], wide[:, 2 + o:2 + o + a], wide[:, 4 + 2 * o + a:5 + 2 * o + a], wide[:, 3 + o + a:3 + 2 * o + a], flags[:, 1:2]
-
-
-def assert_same_state(A, B):
-    for which in SETS:
-        assert np.array_equal(A.get_params(which), B.get_params(which)), ("params", which)
-    for which in (_lib.ACTOR, _lib.CRITICS, _lib.LOG_ALPHA):
-        (m1, v1, t1), (m2, v2, t2) = A.get_adam_state(which), B.get_adam_state(which)
-        assert t1 == t2 and np.array_equal(m1, m2) and np.array_equal(v1, v2), ("adam", which)
-    assert A.read_metrics() == B.read_metrics()
 
 
 def assert_same_ring(A, B):
@@ -96,7 +51,8 @@ def assert_same_ring(A, B):
 @pytest.mark.parametrize("env", PACK_SHAPES)
 def test_ring_from_device_fields_equals_ring_from_host_arrays(env, layout):
     o, a, bound = DIMS[env]
-    H, D = [P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=64, rb_capacity=1000, max_envs=8), [-bound] * a, [bound] * a) for _ in range(2)]
+    H, D = [track(P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=64, rb_capacity=1000, max_envs=8), [-bound] * a, [bound] * a))
+            for _ in range(2)]
     first = 0
     for k, n in enumerate((1, 4, 4, 8, 300, 683, 300)):          # 1300 rows into 1000: one wrap, inside the 300-row push
         five = rows(n, o, a, bound, seed=k, first=first)
@@ -108,7 +64,6 @@ def test_ring_from_device_fields_equals_ring_from_host_arrays(env, layout):
     s = D.boundary_stats()
     assert (s["device_extends"], s["device_rows"], s["device_batches"], s["ordered_calls"]) == (7, 1300, 0, 7)
     assert list(H.boundary_stats().values()) == [0, 0, 0, 0]
-    H.close(); D.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. the batch slot
@@ -133,7 +88,6 @@ def test_batch_slot_from_device_fields_equals_load_batch(algo, env, B):
             e.update_targ_nets(rnd + 1)
         assert_same_state(H, D)
     assert D.boundary_stats()["device_batches"] == 2 and H.boundary_stats()["device_batches"] == 0
-    H.close(); D.close()
 
 
 # ------------------------------------------------------------------------------------------ 3. the mirror, as the reference's loop drives it
@@ -145,7 +99,7 @@ def mirror_run(device_inputs, as_numpy=False):
     torch.manual_seed(0)
     ag = P.Agent({"ob_shape": (n, o), "ac_shape": (n, a)}, np.full(a, -1.0, np.float32), np.full(a, 1.0, np.float32),
                  torch.device(DEV), cfg, P.ReplayBuffer(cfg.rb_capacity))
-    ag.engine.device_inputs = device_inputs
+    track(ag.engine).device_inputs = device_inputs
     put = (lambda t: t.numpy()) if as_numpy else (lambda t: t.to(DEV))
 
     def td(five):
@@ -182,8 +136,6 @@ def test_mirror_keeps_device_tensors_on_the_device():
         for k in x:
             assert np.array_equal(x[k], y[k]), ("ring", k)
         assert D.engine._batch_generation == other.engine._batch_generation == 20      # (StaleBatchError behaviour: same generations)
-    for ag in (D, H, N):
-        ag.engine.close()
 
 
 # ------------------------------------------------------------------------------------------ 4. stream order, both directions
@@ -192,7 +144,7 @@ def test_reads_are_ordered_against_the_producer_stream():
     call: the engine must read after the write and before the zeroing.  (A missing wait reads stale or zeroed values; nothing faults.)"""
     o, a, bound = DIMS["hopper"]
     B = 64
-    eng = P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=256, max_envs=8), [-bound] * a, [bound] * a)
+    eng = track(P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=256, max_envs=8), [-bound] * a, [bound] * a))
     want = rows(B, o, a, bound, seed=3)
     real = cuda(want)
     src = tuple(torch.full_like(t, True if t.dtype == torch.bool else 5.0) for t in real)
@@ -219,7 +171,6 @@ def test_reads_are_ordered_against_the_producer_stream():
             s_.fill_(True if s_.dtype == torch.bool else 5.0)
         torch.cuda.synchronize()
     assert eng.boundary_stats()["ordered_calls"] == 2
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 5. a precomputed opening pair is dropped
@@ -236,17 +187,16 @@ def test_device_extend_breaks_the_period_chain():
         if i == 3:
             Bn.rb_extend(*[t.numpy() for t in new])
         Bn.step(i % 3 == 0)
-    assert_same_state(A, Bn)
-    assert np.array_equal(A.read_batch()["index"], Bn.read_batch()["index"])
+    assert_same_state(A, Bn, "index")
     assert A.rb_len() == Bn.rb_len() == 516
-    A.close(); Bn.close()
 
 
 # ------------------------------------------------------------------------------------------ 6. errors
 def test_bad_arguments_are_refused_and_leave_the_engine_usable():
     o, a, bound = DIMS["hopper"]
     B = 32
-    H, D = [P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=256, max_envs=8), [-bound] * a, [bound] * a) for _ in range(2)]
+    H, D = [track(P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=256, max_envs=8), [-bound] * a, [bound] * a))
+            for _ in range(2)]
     want = rows(B, o, a, bound, seed=4)
     five = cuda(want)
     good = raw_fields(five)
@@ -285,7 +235,6 @@ def test_bad_arguments_are_refused_and_leave_the_engine_usable():
         assert np.array_equal(x[k], y[k]), k
     s = D.boundary_stats()
     assert (s["device_extends"], s["device_rows"], s["device_batches"]) == (2, B, 1)
-    H.close(); D.close()
 
 
 def test_a_tensor_of_another_gpu_is_refused():
@@ -293,7 +242,7 @@ def test_a_tensor_of_another_gpu_is_refused():
         pytest.skip("one device")
     o, a, bound = DIMS["hopper"]
     B = 32
-    eng = P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=256, max_envs=8), [-bound] * a, [bound] * a)
+    eng = track(P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=256, max_envs=8), [-bound] * a, [bound] * a))
     here = cuda(rows(B, o, a, bound, seed=4))
     there = tuple(t.to("cuda:1") for t in here)
     assert agent_mod._device_route(eng, *there) is None and agent_mod._device_route(eng, *(here[:1] + there[1:])) is None
@@ -302,7 +251,6 @@ def test_a_tensor_of_another_gpu_is_refused():
             call(raw_fields(here[:2] + there[2:3] + here[3:]), B)
     eng.load_batch_device(raw_fields(here), B)
     assert np.array_equal(eng.read_batch()["observations"], here[0].cpu().numpy())
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 7. acting overlap
@@ -318,4 +266,3 @@ def test_device_extend_does_not_meet_an_acting_call_in_flight():
     assert Bn.acting_stats() == s0 and s0["begun"] == 1
     assert np.array_equal(Bn.predict_end(), want)
     assert Bn.rb_len() == 4 and Bn.boundary_stats()["device_extends"] == 1
-    A.close(); Bn.close()

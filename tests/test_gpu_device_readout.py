@@ -11,16 +11,12 @@ import pytest
 import torch
 
 from oracle.sac_td3_ref import Hps
+from tests.gpu_support import (DEV, PACK_SHAPES, P, _lib, assert_same_state, close_engines, fields_of, make_pair, new_engine,  # noqa: F401
+                               rows, stream, track)
 from tests.helpers import DIMS
-from tests.test_gpu_device_boundary import PACK_SHAPES, assert_same_state, fields_of, rows
-from tests.test_gpu_engine import make_pair
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod  # noqa: E402
-
-DEV = "cuda:0"
 KEYS = ("observations", "actions", "rewards", "next_observations", "dones", "index")
 B, CAP = 64, 1000
 
@@ -28,9 +24,7 @@ B, CAP = 64, 1000
 def engine(env, td3=False, cap=CAP, seed=0):
     """an engine with the reference's initial parameters (so that it can step), batch_size 64"""
     o, a, bound = DIMS[env]
-    cfg = P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=cap, max_envs=8, prefer_td3_over_sac=td3, bcq_style_targ_mix=td3,
-                   qnets_lr=3e-4 if td3 else 1e-3, seed=seed)
-    eng = P.Engine(cfg, [-bound] * a, [bound] * a)
+    eng = new_engine((Hps.td3 if td3 else Hps.sac)(batch_size=B), DIMS[env], rb_capacity=cap, max_envs=8, seed=seed)
     torch.manual_seed(seed)
     actor, critics = P.schema.reference_initial_params(o, a, td3, True)
     for which, flat in ((_lib.ACTOR, actor), (_lib.ACTOR_TARGET, actor), (_lib.CRITICS, critics), (_lib.CRITICS_TARGET, critics)):
@@ -59,10 +53,6 @@ def outs(n, o, a, fill_value=None):
 def fields(ts, drop=()):
     """[(address, row stride in elements)] in the order of sactd3_device_fields_out; a dropped key is a NULL destination"""
     return [(0, 0) if k in drop else (ts[k].data_ptr(), ts[k].stride(0) if ts[k].shape[0] > 1 else (ts[k].shape[1] if ts[k].dim() == 2 else 1)) for k in KEYS]
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def host(ts):
@@ -122,7 +112,6 @@ def test_batch_readout_equals_read_batch(env):
     assert_equals_host(batch_out(eng, dims), eng.read_batch(), "step(1)")
     s = eng.readout_stats()
     assert (s["batch_readouts"], s["row_readouts"], s["rows_requested"], s["rows_refused"]) == (4, 0, 0, 0)
-    eng.close()
 
 
 @pytest.mark.parametrize("td3,env", [(False, "hopper"), (True, "td3_2")])
@@ -135,7 +124,6 @@ def test_batch_readout_after_a_period_reads_the_last_slot(td3, env):
         got, want = batch_out(eng, dims), eng.read_batch()
         assert_equals_host(got, want, "step_period")
         assert_equals_host(batch_out(eng, dims), want, "step_period, again")
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. strided, unaligned destinations
@@ -190,7 +178,6 @@ def test_strided_unaligned_destinations_and_nothing_else_written(env):
         made = slabs(150, o, a)
         eng.rb_read_rows_device(idx.data_ptr(), 1, 150, fields(made[0], drop), stream())
         check_slabs(made, want_rows, drop, ("rows", drop))
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 3. ring rows
@@ -218,7 +205,6 @@ def test_ring_rows_equal_the_host_read_back(env):
             calls += 1
     s = eng.readout_stats()
     assert (s["row_readouts"], s["rows_requested"], s["rows_refused"]) == (calls, 3 * (1 + 5 + 64 + 300 + 1000), 0)
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 4. indices outside the ring
@@ -246,7 +232,6 @@ def test_out_of_range_indices_read_zero_rows_and_are_counted():
     eng.step(True)                                               # the engine goes on
     eng.sync()
     assert eng.readout_stats()["rows_refused"] == refused and eng.rb_len() == 500
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 5. a sampler of the caller's own
@@ -271,7 +256,6 @@ def test_external_sampler_round_trip_trains_like_the_engines_own_gather(algo, en
             e.update_actor()
             e.update_targ_nets(rnd + 1)
         assert_same_state(D, H)
-    D.close(); H.close()
 
 
 # ------------------------------------------------------------------------------------------ 6. read-outs are invisible to training
@@ -306,7 +290,6 @@ def test_readouts_between_chained_periods_change_nothing(algo, env):
     assert gr == gn and sum(gr) > 0                              # the same graphs were instantiated: no chain break, no counter consumed
     assert R.readout_stats()["batch_readouts"] == 7 and N.readout_stats()["batch_readouts"] == 0
     assert R.boundary_stats()["ordered_calls"] == 14 and N.boundary_stats()["ordered_calls"] == 0
-    R.close(); N.close()
 
 
 # ------------------------------------------------------------------------------------------ 7. stream order, both directions
@@ -338,7 +321,6 @@ def test_readouts_are_ordered_against_the_consumer_stream():
         assert eng.boundary_stats()["ordered_calls"] == before + rep + 1
         want = eng.read_batch()
         assert_equals_host({k: kept[-1][k].cpu().numpy() for k in KEYS}, want, rep)
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 8. errors
@@ -403,7 +385,6 @@ def test_bad_arguments_are_refused_and_leave_the_engine_usable():
     eng.read_batch_device(good, 0, ordered=False)               # without the flag nothing is inserted
     eng.sync()
     assert eng.boundary_stats()["ordered_calls"] == 2
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 9. the mirror
@@ -413,7 +394,7 @@ def test_mirror_hands_out_device_batches_like_the_reference():
     torch.manual_seed(0)
     ag = P.Agent({"ob_shape": (n, o), "ac_shape": (n, a)}, np.full(a, -1.0, np.float32), np.full(a, 1.0, np.float32),
                  torch.device(DEV), cfg, P.ReplayBuffer(cfg.rb_capacity, device_batches=True))
-    eng = ag.engine
+    eng = track(ag.engine)
     fill(eng, (o, a, 1.0), 200)
     first = ag.rb.sample(B)                                      # never looked at
     batch = ag.rb.sample(B)
@@ -444,7 +425,6 @@ def test_mirror_hands_out_device_batches_like_the_reference():
     with pytest.raises(P.StaleBatchError):
         ag.update_qnets(batch)
     ag.update_qnets(later)
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 10. timing names
@@ -459,7 +439,6 @@ def test_time_kernel_knows_the_readout_kernels(env):
     assert eng.readout_stats()["rows_refused"] == 0
     eng.step(True)
     eng.sync()
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 11. the name tables cannot drift
@@ -476,7 +455,7 @@ def test_every_timing_and_debug_name_is_served_on_some_engine():
 
     def tiny(prepare):
         cfg = P.Config(ob_dim=o, ac_dim=a, batch_size=32, rb_capacity=256, max_envs=4, seed=0)
-        eng = P.Engine(cfg, [-bound] * a, [bound] * a)
+        eng = track(P.Engine(cfg, [-bound] * a, [bound] * a))
         torch.manual_seed(0)
         actor, critics = P.schema.reference_initial_params(o, a, False, True)
         for which, flat in ((_lib.ACTOR, actor), (_lib.ACTOR_TARGET, actor), (_lib.CRITICS, critics), (_lib.CRITICS_TARGET, critics)):
@@ -514,4 +493,3 @@ def test_every_timing_and_debug_name_is_served_on_some_engine():
     served(lambda eng, name: eng.debug_read(name).size > 0, words, "unknown buffer name")
     for eng in engines:
         eng.sync()
-        eng.close()

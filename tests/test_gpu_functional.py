@@ -7,10 +7,10 @@ import pytest
 import torch
 
 from oracle.sac_td3_ref import DetPolicy, Hps, QNet, RefAgent, SquashedGaussPolicy
+from tests.gpu_support import P, _lib, close_engines, flat_actor, flat_critics, track  # noqa: F401
+from tests.helpers import assert_params_close
 
 pytestmark = pytest.mark.gpu
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib  # noqa: E402
 
 
 def _agent(algo="sac", B=256, cap=20000, seed=0, **kw):
@@ -18,8 +18,10 @@ def _agent(algo="sac", B=256, cap=20000, seed=0, **kw):
     base = (Hps.td3 if algo == "td3" else Hps.sac)(batch_size=B, **kw)
     hps = SimpleNamespace(**{**base.__dict__, "cudagraphs": True, "rb_capacity": cap, "seed": seed})
     torch.manual_seed(seed)
-    return P.Agent({"ob_shape": (4, o), "ac_shape": (4, a)}, np.full(a, -1.0, np.float32), np.full(a, 1.0, np.float32),
-                   torch.device("cuda:0"), hps, P.ReplayBuffer(cap)), o, a
+    agent = P.Agent({"ob_shape": (4, o), "ac_shape": (4, a)}, np.full(a, -1.0, np.float32), np.full(a, 1.0, np.float32),
+                    torch.device("cuda:0"), hps, P.ReplayBuffer(cap))
+    track(agent.engine)
+    return agent, o, a
 
 
 @pytest.mark.parametrize("algo", ["sac", "td3"])
@@ -146,7 +148,6 @@ def test_checkpoint_carries_the_reference_optimizer_keys(tmp_path, algo):
     eps = torch.randn(64, a, generator=g)
     ex = ck["engine_resume"]
     ref.qnets_target.load_state_dict(ref.qnets.state_dict())
-    from tests.test_gpu_engine import flat_critics, flat_actor
     eng = agent.engine
     eng.set_params(_lib.CRITICS_TARGET, flat_critics(ref, ref.qnets))            # both sides: targets := online critics
     if algo == "td3":
@@ -158,7 +159,6 @@ def test_checkpoint_carries_the_reference_optimizer_keys(tmp_path, algo):
     eng.update_qnets()
     out = ref.update_qnets(ref.to_batch(b["observations"], b["actions"], b["rewards"], b["next_observations"], b["dones"]), eps)
     np.testing.assert_allclose(eng.read_metrics()["loss/qf_loss"], float(out["loss/qf_loss"]), rtol=1e-5, atol=1e-5)
-    from tests.helpers import assert_params_close
     assert_params_close(eng.get_params(_lib.CRITICS), flat_critics(ref, ref.qnets), hps.qnets_lr, 1, "critics after the 7th Adam step (moments from the checkpoint)")
     # (iii) the reference's keys alone restore the optimiser moments in a fresh engine
     ref_only = {k: v for k, v in ck.items() if k != "engine_resume"}
@@ -235,7 +235,7 @@ def test_shared_replay_device_path_equals_the_host_path():
     rows["terminations"] = rows["dones"]
     rings = []
     for device_path in (True, False):
-        eng = P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=cap, max_envs=4), [-1] * a, [1] * a)
+        eng = track(P.Engine(P.Config(ob_dim=o, ac_dim=a, batch_size=B, rb_capacity=cap, max_envs=4), [-1] * a, [1] * a))
         rb = P.ReplayBuffer(cap)
         rb._bind(eng)
         shared = launcher.SharedReplay(None, rb, device=torch.device("cuda:0"), every=3, force_device_path=device_path)
@@ -300,7 +300,7 @@ def test_bench_dump_is_the_state_after_warmup_plus_timed_steps(workload, tmp_pat
     assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
     sys.path.insert(0, root)
     import bench
-    eng = bench.make_engine(bench.WORKLOADS[workload], seed=0, device_id=0)
+    eng = track(bench.make_engine(bench.WORKLOADS[workload], seed=0, device_id=0))
     assert bench.run_steps(eng, (-warmup) % (bench.DELAY + 1), warmup + steps) == (-warmup) % (bench.DELAY + 1) + warmup + steps
     eng.sync()
     for k, v in eng.read_metrics().items():
@@ -308,7 +308,6 @@ def test_bench_dump_is_the_state_after_warmup_plus_timed_steps(workload, tmp_pat
     for name, which in bench.PARAM_GROUPS:
         got = np.load(tmp_path / f"params_{name}.npy")
         assert got.dtype == np.float32 and np.array_equal(got, eng.get_params(which)), name
-    eng.close()
 
 
 def test_plain_bench_run_reports_the_headline_only():

@@ -24,37 +24,18 @@ Loud rows: the critic cases add 30 to the rewards of the last 64-row tile (which
 errors dominate dW and db: a dropped or doubled row there exceeds the bound many times over.  The actor has no such lever: at
 B >~ 2900 one lost ordinary row (about 1 / B of sum |terms|) is below 2 gamma(B) and only the critics' loud rows can reveal it.
 """
-import numpy as np
 import pytest
 import torch
 
-from tests import bounds as bd
-from tests.helpers import DIMS, observe, synth_transitions
-from tests.test_gpu_engine import P, _lib, check_update_actor_intermediates, check_update_qnets_intermediates, make_pair, schema
+from tests.gpu_stage_checks import (LARGE_BATCH_CASES as CASES, H, check_update_actor_intermediates, check_update_qnets_intermediates,
+                                    run_fused_critic_iteration, run_one_iteration)
+from tests.gpu_support import close_engines, make_pair  # noqa: F401
+from tests.helpers import DIMS
 
 pytestmark = pytest.mark.gpu
 
-K1, K2 = "fc_stack.fc_block_1", "fc_stack.fc_block_2"
-H = 256
 NUM_CUS = 256
 
-# (algo, env, B, layer_norm): why
-CASES = [
-    ("sac", "hopper", 1023, True),        # the largest small-batch shape: 4 slabs, last row block of 15 rows (Adam from step 0)
-    ("sac", "humanoid", 1025, True),      # one row into the 17th 64-row tile; split-M with uneven slices
-    ("td3", "halfcheetah", 1025, True),   # narrow input at a ragged large B
-    ("sac", "humanoid", 1472, True),      # below the 2-net tiling switch and the opening trunk's alpha / gather switch
-    ("sac", "humanoid", 1473, True),      # past both
-    ("td3", "humanoid", 1473, True),      # TD3 past the 2-net switch: target-actor next-action pass, actor-target Polyak
-    ("sac", "humanoid", 2048, False),     # k_nt64_ln's ReLU-only prologue in the 64 x 64 form
-    ("sac", "hopper", 3008, True),        # below the 1-net switch (fused k_nt, K = 11)
-    ("sac", "hopper", 3009, True),        # past it: the tiled pair with K = 11
-    ("sac", "humanoid", 3009, True),      # every trunk tiled
-    ("td3", "halfcheetah", 4095, True),   # ragged at the top of the scope
-    ("sac", "humanoid", 4096, True),      # the top of the scope, wide
-    ("sac", "o3a32", 1030, True),         # the widest head (nh = 64) at a large B
-    ("td3", "o48a17", 1041, True),        # odd widths at a large B
-]
 IDS = [f"{a}-{e}-{b}-{'ln' if ln else 'noln'}" for a, e, b, ln in CASES]
 
 
@@ -163,222 +144,6 @@ def test_switch_points_move_launches_to_the_tiled_form(algo, env, lo, hi):
         assert l0.get("k_gather", 0) == 0 and l1.get("k_gather", 0) == 0 and h0.get("k_gather", 0) == 1 and h1.get("k_gather", 0) == 1
     else:
         assert h0.get("k_nt64<4,2,2>/layer1", 0) == 2 and l0.get("k_nt64<4,2,2>/layer1", 0) == 1
-
-
-# ------------------------------------------------------------------------------------------ optimiser, targets, temperature
-
-def evolve_adam(eng, which, step, seed):
-    """non-trivial Adam state: m ~ 1e-3 N(0, 1), v = (1e-3 N(0, 1))^2 + 1e-7 > 0 at `step` (0: zero moments)"""
-    n = eng.param_count(which)
-    if step == 0:
-        eng.set_adam_state(which, np.zeros(n, np.float32), np.zeros(n, np.float32), 0)
-        return
-    rng = np.random.default_rng(seed)
-    eng.set_adam_state(which, (1e-3 * rng.standard_normal(n)).astype(np.float32),
-                       ((1e-3 * rng.standard_normal(n)) ** 2 + 1e-7).astype(np.float32), step)
-
-
-def snapshot(eng, which):
-    p = eng.get_params(which)
-    try:
-        m, v, t = eng.get_adam_state(which)
-    except P.EngineError:
-        m = v = t = None
-    return dict(p=p, m=m, v=v, t=t)
-
-
-def check_adam(rec, what, eng, which, pre, G, lr, coef=1.0, coef_rel=0.0):
-    """every element of m, v, p after one Adam step from `pre` with the engine's own gradient G (tests/bounds.py:adam_expected)"""
-    m, v, t = eng.get_adam_state(which)
-    p = eng.get_params(which)
-    assert t == pre["t"] + 1, (what, t, pre["t"])
-    cfg = eng.cfg
-    ex = bd.adam_expected(pre["p"], pre["m"], pre["v"], pre["t"], G, lr, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_eps, m_got=m, v_got=v,
-                          coef=coef, coef_rel=coef_rel)
-    for k, got in (("m", m), ("v", v), ("p", p)):
-        observe(rec, f"{what} Adam {k}: err / bound", bd.check(f"{what} Adam {k}", got, *ex[k]))
-
-
-def check_polyak(rec, what, eng, which_t, which_w, t0):
-    want, bound = bd.polyak_expected(t0, eng.get_params(which_w), eng.cfg.polyak)
-    observe(rec, f"{what} Polyak: err / bound", bd.check(f"{what} Polyak", eng.get_params(which_t), want, bound))
-
-
-def check_alpha(rec, eng, pre, B):
-    """the temperature step: its gradient (the alpha loss the engine reports) from the engine's own log-probs, then Adam"""
-    g_eng = eng.read_metrics()["loss/alpha_loss"]
-    want, bound = bd.alpha_grad_expected(eng.debug_read("logp_alpha"), pre["p"][0], -eng.cfg.ac_dim)
-    observe(rec, "alpha gradient: err / bound", bd.check("alpha gradient", np.float32(g_eng), want, bound))
-    check_adam(rec, "log_alpha", eng, _lib.LOG_ALPHA, pre, np.array([g_eng], np.float32), eng.cfg.log_alpha_lr)
-
-
-# ------------------------------------------------------------------------------------------ stages
-
-def _nd(flat, in_dim, nh, ln):
-    return {k: np.asarray(v, np.float64) for k, v in schema.flat_to_dict(flat, in_dim, nh, ln).items()}
-
-
-def check_trunk_backward(rec, who, X, p, h1, xh1, dz2, dh1, dz1, grads, ln, B, gated_dh1):
-    """dh1 = dz2 W2 (GEMM, K = 256), dz1 (LayerNorm backward, or the ReLU gate), and the layer-1 / layer-2 weight, bias and LayerNorm-affine
-    gradients (reductions over the batch) from the engine's own dz2, h1, xhat1, dh1, dz1 and its batch rows X"""
-    mask = h1 > 0
-    want, bound = bd.gemm(dz2, p[f"{K2}.fc.weight"].T)
-    got = np.asarray(dh1, np.float64)
-    if gated_dh1:      # (below B = 1024 the critics' dh1 GEMM epilogue applies the ReLU gate: compare where the gate lets dh1 through)
-        got, want, bound = got * mask, want * mask, bound * mask
-    observe(rec, f"{who} dh1: err / bound", bd.check(f"{who} dh1", got, want, bound))
-    if ln:
-        rstd, rho = bd.ln_rstd(X, p[f"{K1}.fc.weight"], p[f"{K1}.fc.bias"])
-        want, bound = bd.ln_bwd(dh1, h1, xh1, p[f"{K1}.ln.weight"], rstd, rho)
-    else:
-        want, bound = np.asarray(dh1, np.float64) * mask, 0.0
-    observe(rec, f"{who} dz1: err / bound", bd.check(f"{who} dz1", dz1, want, bound))
-    for key, (want, bound) in ((f"{K2}.fc.weight", bd.batch_wgrad(dz2, h1)), (f"{K2}.fc.bias", bd.batch_sum(dz2)),
-                               (f"{K1}.fc.weight", bd.batch_wgrad(dz1, X)), (f"{K1}.fc.bias", bd.batch_sum(dz1))):
-        observe(rec, f"{who} grad {key}: err / bound", bd.check(f"{who} grad {key}", grads[key], want, bound))
-    if ln:
-        (wg, bg), (wb, bb) = bd.ln_affine_grads(dh1, h1, xh1)
-        observe(rec, f"{who} grad {K1}.ln.weight: err / bound", bd.check(f"{who} grad {K1}.ln.weight", grads[f"{K1}.ln.weight"], wg, bg))
-        observe(rec, f"{who} grad {K1}.ln.bias: err / bound", bd.check(f"{who} grad {K1}.ln.bias", grads[f"{K1}.ln.bias"], wb, bb))
-
-
-def check_trunk_forward(rec, who, X, p, h1, xh1, z2, ln):
-    """xhat1 from the input rows X (LayerNorm), h1 (LayerNorm affine + ReLU from the engine's xhat1; without LayerNorm
-    relu(X W1^T + b1)) and z2 = h1 W2^T + b2 (K = 256)"""
-    if ln:
-        want, bound = bd.ln_xhat(X, p[f"{K1}.fc.weight"], p[f"{K1}.fc.bias"])
-        observe(rec, f"{who} xhat1: err / bound", bd.check(f"{who} xhat1", xh1, want, bound))
-        want, y, bound = bd.ln_affine_relu(xh1, p[f"{K1}.ln.weight"], p[f"{K1}.ln.bias"])
-    else:
-        y, bound = bd.gemm(X, p[f"{K1}.fc.weight"], p[f"{K1}.fc.bias"])
-        want = np.maximum(y, 0.0)
-    observe(rec, f"{who} h1: err / bound", bd.check(f"{who} h1", h1, want, bound, accept=bd.relu_accept(h1, y, bound)))
-    if z2 is not None:
-        want, bound = bd.gemm(h1, p[f"{K2}.fc.weight"], p[f"{K2}.fc.bias"])
-        observe(rec, f"{who} z2: err / bound", bd.check(f"{who} z2", z2, want, bound))
-
-
-def run_one_iteration(algo, env, B, ln, rec, adam_step=1000, stages=True, **hp):
-    """update_qnets, update_actor, update_targ_nets through the API from an evolved optimiser state, on a batch with loud rows; after each
-    update every checkable stage (stages=True) and every optimiser / target / temperature output against float64"""
-    o, a, bound = DIMS[env]
-    ref, eng, _ = make_pair(algo, env, B, ln, rb_capacity=max(4096, B), **hp)
-    sac = algo == "sac"
-    nh = 2 * a if sac else a
-    obs, act, rew, nobs, done = synth_transitions(B, o, a, bound, seed=3)
-    done[::5] = True
-    rew = bd.make_loud(rew.numpy(), B)
-    g = torch.Generator().manual_seed(4)
-    eps_c, eps_a, eps_l = (torch.randn(B, a, generator=g) for _ in range(3))
-    for i, which in enumerate((_lib.CRITICS, _lib.ACTOR)):
-        evolve_adam(eng, which, adam_step, 10 + i)
-    if sac:
-        eng.set_adam_state(_lib.LOG_ALPHA, np.array([0.0 if adam_step == 0 else 0.02], np.float32),
-                           np.array([0.0 if adam_step == 0 else 4e-4], np.float32), adam_step)
-    pre = {w: snapshot(eng, w) for w in (_lib.CRITICS, _lib.CRITICS_TARGET, _lib.ACTOR, _lib.ACTOR_TARGET) + ((_lib.LOG_ALPHA,) if sac else ())}
-
-    # ---- critics
-    eng.load_batch(obs, act, rew, nobs, done)
-    eng.set_noise(_lib.SITE_CRITIC, eps_c)
-    eng.update_qnets()
-    ldc = (o + a + 3) // 4 * 4
-    X = eng.debug_read("X").reshape(B, ldc)[:, :o + a]
-    assert np.array_equal(X[:, :o], obs.numpy()) and np.array_equal(X[:, o:], act.numpy()) and np.array_equal(eng.debug_read("rew"), rew)
-    Gc = eng.debug_read("grad_critics").reshape(2, -1)
-    if stages:
-        rd = {k: eng.debug_read(k).reshape(2, B, H) for k in ("c_xh1", "c_h1", "c_z2", "c_dz2", "c_dh1", "c_dz1")}
-        pc = pre[_lib.CRITICS]["p"].reshape(2, -1)
-        for i in range(2):
-            p = _nd(pc[i], o + a, 1, ln)
-            gr = _nd(Gc[i], o + a, 1, ln)
-            who = f"critic{i}"
-            check_trunk_forward(rec, who, X, p, rd["c_h1"][i], rd["c_xh1"][i], rd["c_z2"][i], ln)
-            check_trunk_backward(rec, who, X, p, rd["c_h1"][i], rd["c_xh1"][i], rd["c_dz2"][i], rd["c_dh1"][i], rd["c_dz1"][i], gr, ln, B,
-                                 gated_dh1=B < 1024)
-    check_adam(rec, "critics", eng, _lib.CRITICS, pre[_lib.CRITICS], Gc.reshape(-1), eng.cfg.qnets_lr)
-
-    # ---- actor (+ temperature)
-    eng.set_noise(_lib.SITE_ACTOR0, eps_a)
-    eng.set_noise(_lib.SITE_ALPHA0, eps_l)
-    eng.update_actor()
-    Ga = eng.debug_read("grad_actor")
-    if stages:
-        p = _nd(pre[_lib.ACTOR]["p"], o, nh, ln)
-        gr = _nd(Ga, o, nh, ln)
-        Xo = X[:, :o]
-        rd = {k: eng.debug_read(k).reshape(B, H) for k in ("a_xh1", "a_h1", "a_z2", "a_h2", "a_dz2", "a_dh1", "a_dz1")}
-        ldu = (nh + 3) // 4 * 4
-        du = eng.debug_read("a_du").reshape(B, ldu)[:, :nh]
-        # (SAC: a_z2 afterwards holds the temperature pass's pre-activation through the stepped actor, whose h1 is not kept: z2 is
-        #  checked for TD3 only)
-        check_trunk_forward(rec, "actor", Xo, p, rd["a_h1"], rd["a_xh1"], None if sac else rd["a_z2"], ln)
-        check_trunk_backward(rec, "actor", Xo, p, rd["a_h1"], rd["a_xh1"], rd["a_dz2"], rd["a_dh1"], rd["a_dz1"], gr, ln, B, gated_dh1=B < 1024)
-        for key, (want, bnd) in (("head.weight", bd.batch_wgrad(du, rd["a_h2"])), ("head.bias", bd.batch_sum(du))):
-            observe(rec, f"actor grad {key}: err / bound", bd.check(f"actor grad {key}", gr[key], want, bnd))
-        # the Q(s, pi) pass: the nq online critics (SAC 2, TD3 1), as stepped above, over Xp = [s | pi(s)] -- a launch of its own shape
-        # (2 or 1 nets), whose xhat1, h1 and z2 stay in the critics' buffers
-        Xp = eng.debug_read("Xp").reshape(B, ldc)[:, :o + a]
-        assert np.array_equal(Xp[:, :o], obs.numpy())
-        pq = eng.get_params(_lib.CRITICS).reshape(2, -1)
-        rq = {k: eng.debug_read(k).reshape(2, B, H) for k in ("c_xh1", "c_h1", "c_z2")}
-        for i in range(2 if sac else 1):
-            check_trunk_forward(rec, f"Q(s, pi) critic{i}", Xp, _nd(pq[i], o + a, 1, ln), rq["c_h1"][i], rq["c_xh1"][i], rq["c_z2"][i], ln)
-    if eng.cfg.clip_norm > 0:      # k_adam: the stored gradient is the unclipped G, scaled by the coefficient of its fp32 norm
-        coef, rel = bd.clip_coef(Ga, eng.cfg.clip_norm)
-        check_adam(rec, "actor (clipped)", eng, _lib.ACTOR, pre[_lib.ACTOR], Ga, eng.cfg.actor_lr, coef=coef, coef_rel=rel)
-    else:
-        check_adam(rec, "actor", eng, _lib.ACTOR, pre[_lib.ACTOR], Ga, eng.cfg.actor_lr)
-    if sac:
-        check_alpha(rec, eng, pre[_lib.LOG_ALPHA], B)
-
-    # ---- targets (k_polyak)
-    eng.update_targ_nets(1)
-    check_polyak(rec, "critic targets (k_polyak)", eng, _lib.CRITICS_TARGET, _lib.CRITICS, pre[_lib.CRITICS_TARGET]["p"])
-    if not sac:
-        check_polyak(rec, "actor target (k_polyak)", eng, _lib.ACTOR_TARGET, _lib.ACTOR, pre[_lib.ACTOR_TARGET]["p"])
-    else:
-        assert np.array_equal(eng.get_params(_lib.ACTOR_TARGET), pre[_lib.ACTOR_TARGET]["p"])
-    eng.close()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
-    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-
-
-def run_fused_critic_iteration(algo, env, B, ln, rec, adam_step=1000, stages=False):
-    """one fused critic-only iteration (sactd3_step): the critic targets lerped in the weight-gradient launch's Adam epilogue (k_tn /
-    k_adam_red) and, TD3, the actor target as riding blocks of that launch -- from the engine's own gradient and parameters.
-    stages: also the batch slot against the ring rows of the sample it reports, bit for bit, and the critics' trunk forward and
-    backward stages from the parameters before the step -- the launches whose opening trunk reads ring rows and carries the gather"""
-    o, a, bound = DIMS[env]
-    ref, eng, _ = make_pair(algo, env, B, ln, rb_capacity=2 * B)
-    rows = [t.numpy() for t in synth_transitions(2 * B, o, a, bound, seed=7)]
-    rows[2] = bd.make_loud(rows[2], 2 * B)
-    eng.rb_extend(*rows)
-    evolve_adam(eng, _lib.CRITICS, adam_step, 12)
-    pre = {w: snapshot(eng, w) for w in (_lib.CRITICS, _lib.CRITICS_TARGET, _lib.ACTOR, _lib.ACTOR_TARGET)}
-    eng.step(False)
-    if stages:
-        idx = eng.read_batch()["index"]
-        assert idx.shape == (B,) and idx.min() >= 0 and idx.max() < 2 * B, (idx.min(), idx.max())
-        X = eng.debug_read("X").reshape(B, (o + a + 3) // 4 * 4)[:, :o + a]
-        assert _same_bits(X[:, :o], rows[0][idx]) and _same_bits(X[:, o:], rows[1][idx]), "batch slot [s | a] != the sampled ring rows"
-        assert _same_bits(eng.debug_read("rew"), rows[2][idx]), "batch slot rewards != the sampled ring rows"
-        assert _same_bits(eng.debug_read("done"), rows[4][idx].astype(np.float32)), "batch slot done flags != the sampled ring rows"
-        rd = {k: eng.debug_read(k).reshape(2, B, H) for k in ("c_xh1", "c_h1", "c_z2", "c_dz2", "c_dh1", "c_dz1")}
-        pc, Gc = pre[_lib.CRITICS]["p"].reshape(2, -1), eng.debug_read("grad_critics").reshape(2, -1)
-        for i in range(2):
-            p, who = _nd(pc[i], o + a, 1, ln), f"fused critic{i}"
-            check_trunk_forward(rec, who, X, p, rd["c_h1"][i], rd["c_xh1"][i], rd["c_z2"][i], ln)
-            check_trunk_backward(rec, who, X, p, rd["c_h1"][i], rd["c_xh1"][i], rd["c_dz2"][i], rd["c_dh1"][i], rd["c_dz1"][i],
-                                 _nd(Gc[i], o + a, 1, ln), ln, B, gated_dh1=B < 1024)
-    check_adam(rec, "critics (fused step)", eng, _lib.CRITICS, pre[_lib.CRITICS], eng.debug_read("grad_critics"), eng.cfg.qnets_lr)
-    check_polyak(rec, "critic targets (Adam epilogue)", eng, _lib.CRITICS_TARGET, _lib.CRITICS, pre[_lib.CRITICS_TARGET]["p"])
-    assert np.array_equal(eng.get_params(_lib.ACTOR), pre[_lib.ACTOR]["p"])
-    if algo == "td3":
-        check_polyak(rec, "actor target (riding blocks)", eng, _lib.ACTOR_TARGET, _lib.ACTOR, pre[_lib.ACTOR_TARGET]["p"])
-    eng.close()
 
 
 @pytest.mark.parametrize("algo,env,B,ln", CASES, ids=IDS)

@@ -14,32 +14,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_support import DEV, _lib, assert_same_bits, assert_same_state, close_engines, engine_state, make_pair, stream  # noqa: F401
 from tests.helpers import synth_transitions
-from tests.test_gpu_engine import make_pair
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib  # noqa: E402
-
 SHAPES = [("sac", "hopper"), ("td3", "halfcheetah")]
 BATCHES = [40, 64, 256]
-
-
-def full_state(eng):
-    """parameters, targets, log alpha, Adam state of both optimisers, metrics, the last sample's indices"""
-    out = {f"params{w}": eng.get_params(w) for w in (_lib.ACTOR, _lib.CRITICS, _lib.ACTOR_TARGET, _lib.CRITICS_TARGET, _lib.LOG_ALPHA)}
-    for name, which in (("critics", _lib.CRITICS), ("actor", _lib.ACTOR)):
-        m, v, t = eng.get_adam_state(which)
-        out[f"adam_m_{name}"], out[f"adam_v_{name}"], out[f"adam_t_{name}"] = m, v, np.float64(t)
-    out["metrics"] = np.array(list(eng.read_metrics().values()), np.float32)
-    out["index"] = eng.read_batch()["index"]
-    return out
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes()
 
 
 def engine(algo, env, B, use_graphs):
@@ -59,17 +40,16 @@ def test_graphs_launch_sequences_and_single_steps_leave_the_same_bits(algo, env,
     for key, use_graphs in (("graphs", True), ("launches", False)):
         eng = engine(algo, env, B, use_graphs)
         assert eng.run_iterations(1, 10) == 11 and eng.run_iterations(11, 4) == 15
-        states[key] = full_state(eng)
+        states[key] = engine_state(eng, "index")
         eng.close()
     eng = engine(algo, env, B, True)
     for i in range(1, 15):
         eng.step(i % 3 == 0)
-    states["single"] = full_state(eng)
-    eng.close()
+    states["single"] = engine_state(eng, "index")
     for key in ("launches", "single"):
-        for k, v in states["graphs"].items():
-            assert same_bits(v, states[key][k]), (key, k)
-    assert np.isfinite(states["graphs"]["metrics"]).all() and states["graphs"]["adam_t_critics"] == 14
+        assert_same_state(states["graphs"], states[key], what=key)
+    assert all(np.isfinite(v).all() for k, v in states["graphs"].items() if k.startswith("metrics."))
+    assert states["graphs"]["adam_t.critics"] == 14
 
 
 @pytest.mark.parametrize("B", [40, 256])
@@ -85,8 +65,8 @@ def test_weighted_critic_update_with_unit_weights(algo, env, B):
         eps = torch.randn(B, eng.cfg.ac_dim, generator=torch.Generator().manual_seed(4))
         eng.set_noise(_lib.SITE_CRITIC, eps)
         if weighted:
-            di, dw = torch.as_tensor(idx, device="cuda:0"), torch.ones(B, device="cuda:0")
-            eng.rb_sample_indices_device(di.data_ptr(), 1, dw.data_ptr(), 1, B, torch.cuda.current_stream().cuda_stream)
+            di, dw = torch.as_tensor(idx, device=DEV), torch.ones(B, device=DEV)
+            eng.rb_sample_indices_device(di.data_ptr(), 1, dw.data_ptr(), 1, B, stream())
         else:
             eng.rb_sample_with_indices(idx)
         eng.update_qnets()
@@ -94,5 +74,4 @@ def test_weighted_critic_update_with_unit_weights(algo, env, B):
         out.append(dict(params=eng.get_params(_lib.CRITICS), m=m, v=v, t=np.float64(t), grad=eng.debug_read("grad_critics"),
                         loss=np.float32(eng.read_metrics()["loss/qf_loss"])))
         eng.close()
-    for k, v in out[0].items():
-        assert same_bits(v, out[1][k]), k
+    assert_same_bits(out[0], out[1], what="weights of 1.0 against the plain update")

@@ -2,11 +2,10 @@
 sactd3_prio_set_uniforms, sactd3_prio_update_from_td, sactd3_prio_update_device, sactd3_prio_stats) against the numpy restatement of
 tests/priorities_ref.py and against twin engines.
 
-Engines are the small ones of tests/test_gpu_prioritized.py (the oracle's perturbed parameters, the critic site's noise injected) with a
+Engines are shape_engines() of tests/gpu_support.py (the oracle's perturbed parameters), the critic site's noise injected, with a
 5000-slot ring that holds 2500 rows: two whole groups of 1024 leaves, a partial third, unfilled slots behind it, two empty groups.
 Shapes: SAC Hopper at B = 64 and B = 40, TD3 HalfCheetah at B = 64, SAC Hopper at B = 1024 (the weights kernel's loop, 1024 draw and
 write-back workgroups)."""
-import functools
 from types import SimpleNamespace
 
 import numpy as np
@@ -15,40 +14,22 @@ import torch
 
 from oracle.sac_td3_ref import Hps
 from tests import priorities_ref as pref
-from tests.helpers import observe, synth_transitions
-from tests.test_gpu_device_boundary import assert_same_state, cuda, extend_device
-from tests.test_gpu_prioritized import assert_same_bits, close_all, slot, stage, stream, td_of
-from tests.test_gpu_qvalues import SHAPES, build as q_build, same_bits
+from tests.gpu_support import (BOUND_REL, CAP, DEV, HELD, PRIO_CASES as CASES, SEED, P, _lib, assert_same_bits, assert_same_state,  # noqa: F401
+                               boundary_uniforms, close_engines, cuda, extend_device, integer_priorities, loop, ring_rows, same_bits, shape_engines,
+                               slot, stage, td_of, track, upload_priorities)
+from tests.helpers import observe
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, loop  # noqa: E402
-
-DEV = "cuda:0"
-CAP, HELD, SEED = 5000, 2500, 3          # (SEED: the engines' Philox key, tests/test_gpu_qvalues.py build())
-CASES = {"sac-hopper-64": ("sac-hopper", 64), "sac-hopper-40": ("sac-hopper", 40), "td3-halfcheetah-64": ("td3-halfcheetah", 64),
-         "sac-hopper-1024": ("sac-hopper", 1024)}
 ALL = list(CASES)
 U24 = 2.0 ** -24
-# Tests 4 and 6: the largest relative difference between the device's float32 weights / leaves and the float64 restatement, measured on
-# an MI355X over every case of the two tests, and the bound the tests apply: 8 x the measured value, never above 1e-4.
-MEASURED_REL = {"weights": 2.215e-7, "leaves": 1.293e-7}      # (both at sac-hopper-1024; bounds 1.77e-6 and 1.03e-6)
-BOUND_REL = {k: min(8.0 * v, 1e-4) for k, v in MEASURED_REL.items()}
-
-
-@functools.lru_cache(maxsize=None)
-def ring_rows(shape, n=HELD, seed=9):
-    """the transitions every engine's ring holds: computed once per shape, never written"""
-    _, (o, a, bound), _ = SHAPES[shape]
-    return synth_transitions(n, o, a, bound, seed=seed)
 
 
 def build(case, count, enable=(1.0, 1e-6)):
     """`count` twin engines: same parameters, the same 2500 rows in a 5000-slot ring, the same injected critic noise; priorities
     enabled with `enable` = (alpha, eps) unless None"""
     shape, B = CASES[case]
-    _, engs, (o, a, bound) = q_build(shape, count, B=B, cap=CAP)
+    _, engs, (o, a, bound) = shape_engines(shape, count, B=B, cap=CAP)
     eps = torch.randn(B, a, generator=torch.Generator().manual_seed(4))
     for eng in engs:
         eng.rb_extend(*[t.numpy() for t in ring_rows(shape)])
@@ -56,36 +37,6 @@ def build(case, count, enable=(1.0, 1e-6)):
         if enable is not None:
             eng.prio_enable(*enable)
     return engs, (o, a, bound), B
-
-
-def write(eng, idx, prio):
-    """sactd3_prio_update_device on host arrays (uploaded first)"""
-    i = torch.as_tensor(np.asarray(idx, np.int64), device=DEV)
-    p = torch.as_tensor(np.asarray(prio, np.float32), device=DEV)
-    eng.prio_update_device(i.data_ptr(), 1, p.data_ptr(), 1, i.shape[0], stream())
-    return i, p
-
-
-def integer_priorities():
-    """2500 priorities from {0, 1, 2}: 100 zeros (the ring's first and last rows and both sides of a group boundary among them), 160 twos,
-    ones elsewhere -- T = 2560 = 5 * 2^9, so u = k / 4096 with 8 | k puts u * T exactly on a running-sum boundary"""
-    rng = np.random.default_rng(11)
-    p = np.ones(HELD, np.float32)
-    fixed_zero, fixed_two = [0, 1023, 1024, HELD - 1], [1, 1022, 1025, 2047, 2048, HELD - 2]
-    rest = rng.permutation(np.setdiff1d(np.arange(HELD), fixed_zero + fixed_two))
-    p[fixed_zero + list(rest[:96])] = 0.0
-    p[fixed_two + list(rest[96:96 + 154])] = 2.0
-    assert p.sum() == 2560.0
-    return p
-
-
-def boundary_uniforms(B):
-    """k / 4096: 0, the largest, and multiples of 8 (mass exactly on a boundary) among arbitrary k"""
-    rng = np.random.default_rng(12)
-    k = rng.integers(0, 4096, B)
-    k[:8] = [0, 4095, 8, 16, 4088, 2048, 1024, 3072]
-    k[8:B // 2] = 8 * rng.integers(0, 512, B // 2 - 8)
-    return (k / 4096.0).astype(np.float32)
 
 
 def drawn(eng):
@@ -107,7 +58,7 @@ def assert_sums_consistent(eng, what=""):
 def test_injected_uniforms_select_exactly_the_restatements_slots(case):
     (eng,), _, B = build(case, 1)
     prio = integer_priorities()
-    keep = write(eng, np.arange(HELD), prio)
+    keep = upload_priorities(eng, np.arange(HELD), prio)
     leaf = eng.debug_read("prio_leaf")
     assert np.array_equal(leaf[:HELD], prio) and not leaf[HELD:].any()          # alpha == 1: the priority itself
     T = float(leaf.sum())
@@ -123,7 +74,6 @@ def test_injected_uniforms_select_exactly_the_restatements_slots(case):
     eng.prio_set_uniforms(None)
     assert eng.prio_stats() == dict(samples=1, write_backs=1, rows_refused=0, rows_entered_at_max=HELD)
     del keep
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. exact selection, native draws
@@ -131,7 +81,7 @@ def test_injected_uniforms_select_exactly_the_restatements_slots(case):
 def test_native_draws_follow_the_philox_stream_and_leave_the_uniform_sampler_alone(case):
     (A, Bt, N), _, B = build(case, 3)
     prio = integer_priorities()
-    keep = [write(e, np.arange(HELD), prio) for e in (A, Bt)]
+    keep = [upload_priorities(e, np.arange(HELD), prio) for e in (A, Bt)]
     leaf = A.debug_read("prio_leaf")
     for ctr in range(3):                                            # the draw counter advances once per call
         A.rb_sample_prioritized(0.4)
@@ -143,14 +93,13 @@ def test_native_draws_follow_the_philox_stream_and_leave_the_uniform_sampler_alo
     N.rb_sample()
     assert_same_bits(slot(A), slot(N), what="uniform sample behind three prioritised ones")
     del keep
-    close_all(A, Bt, N)
 
 
 # ------------------------------------------------------------------------------------------ 3. the slot is what index staging leaves
 @pytest.mark.parametrize("case", ALL)
 def test_the_slot_is_what_index_staging_leaves(case):
     (D, H), _, B = build(case, 2)
-    keep = write(D, np.arange(HELD), integer_priorities())
+    keep = upload_priorities(D, np.arange(HELD), integer_priorities())
     D.rb_sample_prioritized(0.4)
     idx = drawn(D)
     keep2 = stage(H, idx)
@@ -160,7 +109,6 @@ def test_the_slot_is_what_index_staging_leaves(case):
     H.update_qnets()
     assert D.graph_kernel_count(8) == H.graph_kernel_count(0) > 0 and D.graph_kernel_count(0) == 0      # the weighted graph, the plain count
     del keep, keep2
-    close_all(D, H)
 
 
 # ------------------------------------------------------------------------------------------ 4. weights
@@ -173,7 +121,7 @@ def test_importance_weights(case):
     """general float priorities, alpha = 0.6; beta 0: all exactly 1; every batch's largest weight exactly 1; otherwise the float64
     restatement on the leaves read back and the slots actually drawn, within BOUND_REL["weights"]"""
     (eng,), _, B = build(case, 1, enable=(0.6, 1e-6))
-    keep = write(eng, np.arange(HELD), float_priorities())
+    keep = upload_priorities(eng, np.arange(HELD), float_priorities())
     leaf = eng.debug_read("prio_leaf")
     worst = 0.0
     for beta in (0.0, 0.4, 1.0):
@@ -191,7 +139,6 @@ def test_importance_weights(case):
         observe("native_priorities_weights", f"{case} beta {beta}: max relative delta", rel)
         assert rel <= BOUND_REL["weights"], (beta, rel)
     del keep
-    eng.close()
 
 
 def weights_of(eng, B):
@@ -209,7 +156,7 @@ def test_draws_follow_the_priorities():
     the host); the run is deterministic."""
     (eng,), _, B = build("sac-hopper-64", 1, enable=(0.6, 1e-6))
     cls = np.arange(HELD) % 16
-    keep = write(eng, np.arange(HELD), (0.2 + 0.1 * cls).astype(np.float32))
+    keep = upload_priorities(eng, np.arange(HELD), (0.2 + 0.1 * cls).astype(np.float32))
     leaf = eng.debug_read("prio_leaf")
     mass = np.array([leaf[:HELD][cls == c].astype(np.float64).sum() for c in range(16)])
     calls = 200
@@ -228,7 +175,6 @@ def test_draws_follow_the_priorities():
     assert chi_ref < crit and chi_dev < crit, (chi_dev, chi_ref, crit)
     assert eng.prio_stats()["samples"] == calls
     del keep
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 6. write-back from the TD errors
@@ -270,7 +216,6 @@ def test_write_back_from_td_errors(case):
         with pytest.raises(P.EngineError, match="-3"):
             eng.prio_update_from_td()
         assert eng.prio_stats() == dict(samples=1, write_backs=1, rows_refused=0, rows_entered_at_max=HELD)
-    close_all(E1, E6)
 
 
 # ------------------------------------------------------------------------------------------ 7. duplicates and refused rows
@@ -282,7 +227,7 @@ def test_duplicates_resolve_by_batch_position_and_bad_rows_are_refused():
     idx[[3, 10, 50]] = 7                                            # one slot at three positions with three priorities
     idx[[0, 63]] = 1030                                             # ... and one at both ends of the batch
     prio[[3, 10, 50]] = [0.5, 1.75, 0.25]
-    keeps = [write(e, idx, prio) for e in engs]
+    keeps = [upload_priorities(e, idx, prio) for e in engs]
     leaves = [e.debug_read("prio_leaf") for e in engs]
     sums = [e.debug_read("prio_sums") for e in engs]
     for k in (1, 2):
@@ -296,7 +241,7 @@ def test_duplicates_resolve_by_batch_position_and_bad_rows_are_refused():
     # refused rows between good ones: bad priorities on valid slots, good priorities on bad slots
     bad_idx = np.array([100, 101, 102, -1, HELD, 2 ** 40, 200, 201], np.int64)
     bad_prio = np.array([-1.0, np.nan, np.inf, 0.5, 0.5, 0.5, 0.75, 0.0], np.float32)
-    keep = write(E, bad_idx, bad_prio)
+    keep = upload_priorities(E, bad_idx, bad_prio)
     leaf = E.debug_read("prio_leaf")
     want = before.copy()
     want[200], want[201] = np.float32(0.75) ** np.float32(0.6), 0.0                    # (0 excludes the row)
@@ -314,19 +259,17 @@ def test_duplicates_resolve_by_batch_position_and_bad_rows_are_refused():
     assert np.isfinite(list(E.read_metrics().values())).all() and np.isfinite(E.debug_read("prio_leaf")).all()
     assert E.priority_stats()["rows_refused"] == 0
     del keeps, keep
-    close_all(*engs)
 
 
 def test_nothing_to_draw_from_is_refused_rows_not_a_fault():
     (eng,), _, B = build("sac-hopper-64", 1)
-    keep = write(eng, np.arange(HELD), np.zeros(HELD, np.float32))
+    keep = upload_priorities(eng, np.arange(HELD), np.zeros(HELD, np.float32))
     eng.rb_sample_prioritized(0.4)
     assert (drawn(eng) == -1).all() and not eng.debug_read("X").any()
     assert eng.priority_stats()["rows_refused"] == B                # stored as refused rows by the staging kernel, and counted
     eng.update_qnets()
     assert np.isfinite(list(eng.read_metrics().values())).all()
     del keep
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 8. the sums never drift
@@ -338,18 +281,17 @@ def test_sums_depend_on_the_leaves_not_on_the_history():
     for k in range(20):                                             # 20 overlapping write-backs of 64 rows over 400 slots around a group boundary
         idx = rng.integers(800, 1200, 64)
         prio = rng.uniform(0.05, 3.0, 64).astype(np.float32)
-        keep.append(write(A, idx, prio))
+        keep.append(upload_priorities(A, idx, prio))
         for s, p in zip(idx, prio):
             final[int(s)] = p
     slots = np.array(sorted(final), np.int64)
-    keep.append(write(Bt, slots, np.array([final[int(s)] for s in slots], np.float32)))      # ... and the same leaves in one
+    keep.append(upload_priorities(Bt, slots, np.array([final[int(s)] for s in slots], np.float32)))      # ... and the same leaves in one
     la, lb = A.debug_read("prio_leaf"), Bt.debug_read("prio_leaf")
     assert same_bits(la, lb) and len(slots) > 300
     assert same_bits(A.debug_read("prio_sums"), Bt.debug_read("prio_sums"))
     assert_sums_consistent(A)
     assert A.prio_stats()["write_backs"] == 20 and Bt.prio_stats()["write_backs"] == 1
     del keep
-    close_all(A, Bt)
 
 
 # ------------------------------------------------------------------------------------------ 9. appends
@@ -361,7 +303,7 @@ def test_every_append_path_enters_rows_at_the_maximum_priority():
     assert (leaf[:HELD] == 1.0).all() and not leaf[HELD:].any() and eng.prio_stats()["rows_entered_at_max"] == HELD
     p0 = np.zeros(HELD, np.float32)
     p0[0] = 3.0                                                     # the running maximum becomes 3; nothing else can be drawn
-    keep = [write(eng, np.arange(HELD), p0)]
+    keep = [upload_priorities(eng, np.arange(HELD), p0)]
     fresh = float(np.float32(3.0) ** np.float32(0.6))
     entered, length = HELD, HELD
 
@@ -400,7 +342,6 @@ def test_every_append_path_enters_rows_at_the_maximum_priority():
     leaf = check(0, 1300, "rb_fill_synthetic")
     assert not leaf[1300:HELD].any() and (leaf[HELD:] == leaf[0]).all()
     del keep, rec
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 10. invisible when off, harmless when on
@@ -417,7 +358,7 @@ def test_priorities_do_not_change_what_the_other_paths_compute():
         eng.step(False)
         it = eng.run_iterations(0, 3)
         if eng is E:                                                # behind a period that left the next one's opening pair precomputed
-            keep.append(write(E, np.arange(64), np.linspace(0.1, 2.0, 64)))
+            keep.append(upload_priorities(E, np.arange(64), np.linspace(0.1, 2.0, 64)))
         it = eng.run_iterations(it, 3)
         samples = eng.read_batch()["index"]
         eng.rb_sample()
@@ -433,14 +374,13 @@ def test_priorities_do_not_change_what_the_other_paths_compute():
     with pytest.raises(P.EngineError, match="-3"):
         N.debug_read("prio_leaf")
     del keep
-    close_all(N, E)
 
 
 def test_write_back_behind_a_cut_short_period_goes_to_the_rows_it_trained_on():
     """run_iterations(0, 4) at delay 2 is a period, then step_prefix(1) on the opening pair that period left in batch slot 3: the
     write-back behind it takes that slot's ring rows, as behind four single steps -- not the stale rows of slot 0.  SAC Hopper, B = 64,
     3000 rows held, native draws."""
-    _, (P4, S4), _ = q_build("sac-hopper", 2, B=64, cap=CAP)
+    _, (P4, S4), _ = shape_engines("sac-hopper", 2, B=64, cap=CAP)
     for eng in (P4, S4):
         eng.rb_extend(*[t.numpy() for t in ring_rows("sac-hopper", 3000)])
         eng.prio_enable(1.0, 1e-6)
@@ -454,7 +394,6 @@ def test_write_back_behind_a_cut_short_period_goes_to_the_rows_it_trained_on():
     assert np.array_equal(np.flatnonzero(want.view(np.uint32) != before.view(np.uint32)), np.unique(rows))      # (|TD| + eps is never exactly 1)
     assert same_bits(got, want), np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
     assert same_bits(P4.debug_read("prio_sums"), S4.debug_read("prio_sums")) and np.array_equal(P4.read_batch()["index"], rows)
-    close_all(P4, S4)
 
 
 def test_bad_arguments_are_refused_and_leave_the_engine_usable():
@@ -485,7 +424,6 @@ def test_bad_arguments_are_refused_and_leave_the_engine_usable():
     eng.prio_update_from_td()
     assert eng.prio_stats() == dict(samples=1, write_backs=2, rows_refused=0, rows_entered_at_max=HELD)
     assert eng.time_kernel("prio_sample", 5) > 0 and eng.time_kernel("prio_update", 5) > 0
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 11. end to end
@@ -503,7 +441,7 @@ def test_train_with_engine_owned_priorities():
     with pytest.raises(ValueError, match="fused=False"):
         loop.train(cfg, env, agent, fused=True, prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6))
     metrics = loop.train(cfg, env, agent, fused=False, prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6))
-    eng = agent.engine
+    eng = track(agent.engine)
     assert all(np.isfinite(v) for v in metrics.values()), metrics
     updates = agent.qnet_updates_so_far
     assert updates >= iters
@@ -513,4 +451,3 @@ def test_train_with_engine_owned_priorities():
     leaf = eng.debug_read("prio_leaf")
     assert (leaf[:held] > 0).all() and np.isfinite(leaf).all() and not leaf[held:].any()
     assert eng.debug_read("prio_max")[0] >= 1.0 and len(np.unique(leaf[:held])) > iters      # the write-backs moved them
-    eng.close()

@@ -2,11 +2,11 @@
 sactd3_rb_sample_prioritized_nstep, sactd3_nstep_info_device, sactd3_nstep_stats) against the numpy restatement of tests/nstep_ref.py
 and against twin engines.
 
-Engines are those of tests/test_gpu_qvalues.py build() (the oracle's perturbed parameters) with the critic site's noise injected as in
+Engines are shape_engines() of tests/gpu_support.py (the oracle's perturbed parameters) with the critic site's noise injected as in
 tests/test_gpu_native_priorities.py.  Shapes: SAC Hopper at B = 64 and B = 40 (o % 4 = 3), TD3 HalfCheetah at B = 64 (o % 4 = 1), SAC
 Humanoid at B = 64 (o % 4 = 0, 196 chunks per record: a block's span holds a handful of rows), SAC Hopper at B = 1024 (many blocks).
 
-Ring U: 5000 slots, 2400 rows = 600 env steps of 4 envs, chained trajectories built on the host.  Episode lengths cycle through
+Ring U: 5000 slots, 2400 rows = 600 env steps of 4 envs, chained trajectories built on the host (gpu_support.trajectories).  Episode lengths cycle through
 1, 2, 3, 4, 5, 6, 15, 16, 17 (steps - 1, steps, steps + 1 for the step counts in use); episodes end by termination or, alternately, by a
 fresh s without a flag.  Planted: (a) a successor whose s differs from s' in element ob_dim - 1 only, (b) a -0.0 / +0.0 pair, (c) a pair
 of equal NaN patterns (the link holds), (d) the newest step's s' zeroed and unflagged, so that only the length rule cuts it off from the
@@ -21,53 +21,17 @@ import torch
 
 from oracle.sac_td3_ref import Hps
 from tests import nstep_ref as nref
-from tests.test_gpu_device_boundary import assert_same_state
-from tests.test_gpu_engine import push_params
-from tests.test_gpu_prioritized import assert_same_bits, close_all, slot, stage, stream
-from tests.test_gpu_qvalues import MAXN, SHAPES, build as q_build, same_bits
+from tests.gpu_support import (DEV, MAXN, NSTEP_STRIDE as STRIDE, SEED, SHAPES, P, _lib, assert_same_bits, assert_same_state, close_engines,  # noqa: F401
+                               info, loop, push_params, same_bits, shape_engines, slot, stage, stream, track, trajectories)
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, loop  # noqa: E402
-
-DEV = "cuda:0"
-SEED = 3                                  # the engines' Philox key (tests/test_gpu_qvalues.py build())
-STRIDE = 4
 CASES = {"sac-hopper-64": ("sac-hopper", 64), "sac-hopper-40": ("sac-hopper", 40), "td3-halfcheetah-64": ("td3-halfcheetah", 64),
          "sac-humanoid-64": ("sac-humanoid", 64), "sac-hopper-1024": ("sac-hopper", 1024)}
 ALL = list(CASES)
 STEPS = (1, 2, 3, 5, 16)
-LENGTHS = (1, 2, 3, 4, 5, 6, 15, 16, 17)
 U_CAP, U_ROWS = 5000, 2400
 W_CAP, W_ROWS = 1001, 1400
-SENTINEL = -77
-
-
-def trajectories(o, a, n_rows, seed):
-    """n_rows / STRIDE env steps of STRIDE envs in append order: within an episode row t+1 of an env starts at the s' of row t"""
-    rng = np.random.default_rng(seed)
-    T = n_rows // STRIDE
-    obs, nobs = np.zeros((T, STRIDE, o), np.float32), np.zeros((T, STRIDE, o), np.float32)
-    done = np.zeros((T, STRIDE), np.float32)
-    for e in range(STRIDE):
-        t, ep = 0, e                                                   # (each env starts at another place of the cycle)
-        while t < T:
-            n = LENGTHS[ep % len(LENGTHS)]
-            s = rng.standard_normal(o).astype(np.float32)
-            for j in range(n):
-                if t >= T:
-                    break
-                obs[t, e] = s
-                s = rng.standard_normal(o).astype(np.float32)
-                nobs[t, e] = s
-                if j == n - 1 and (ep // len(LENGTHS) + ep) % 2 == 0:
-                    done[t, e] = 1.0                                   # ends by termination; otherwise by a fresh s without a flag
-                t += 1
-            ep += 1
-    act = rng.uniform(-1, 1, (T, STRIDE, a)).astype(np.float32)
-    rew = rng.standard_normal((T, STRIDE)).astype(np.float32)
-    return [obs.reshape(-1, o), act.reshape(-1, a), rew.reshape(-1), nobs.reshape(-1, o), done.reshape(-1)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -119,7 +83,7 @@ def fill(eng, ring):
 def build(case, count, ring, prio=None):
     """`count` twin engines holding `ring`, the same critic noise injected"""
     shape, B = CASES[case]
-    ref, engs, (o, a, bound) = q_build(shape, count, B=B, cap=ring["cap"])
+    ref, engs, (o, a, bound) = shape_engines(shape, count, B=B, cap=ring["cap"])
     eps = torch.randn(B, a, generator=torch.Generator().manual_seed(4))
     for eng in engs:
         fill(eng, ring)
@@ -136,17 +100,6 @@ def stage_n(eng, idx, w, steps, stride=STRIDE):
     eng.rb_sample_nstep_device(idx.data_ptr(), max(idx.stride(0), 1), 0 if w is None else w.data_ptr(), 1 if w is None else max(w.stride(0), 1),
                                idx.shape[0], steps, stride, stream())
     return idx, w
-
-
-def info(eng):
-    """sactd3_nstep_info_device -> (k, last) on the host; a sentinel on either side of both arrays must survive"""
-    B = eng.cfg.batch_size
-    k = torch.full((B + 2,), SENTINEL, dtype=torch.int32, device=DEV)
-    last = torch.full((B + 2,), SENTINEL, dtype=torch.int32, device=DEV)
-    eng.nstep_info_device(k[1:].data_ptr(), 1, last[1:].data_ptr(), 1, stream())
-    k, last = k.cpu().numpy(), last.cpu().numpy()
-    assert k[0] == k[-1] == last[0] == last[-1] == SENTINEL
-    return k[1:-1], last[1:-1]
 
 
 def expected(eng, ring, idx, steps):
@@ -237,7 +190,6 @@ def test_staging_equals_the_restatement_bit_for_bit(case, which):
         if steps == 16:
             assert (want["k"] == 16).any() and (want["k"] == 1).any()
     assert refused > 0 and cut > 0
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. steps == 1 is the 1-step staging
@@ -259,7 +211,6 @@ def test_one_step_staging_is_the_index_staging_bit_for_bit(case):
     assert_same_state(A, T)
     assert same_bits(A.debug_read("targ_q"), T.debug_read("targ_q"))
     del keep
-    close_all(A, T)
 
 
 # ------------------------------------------------------------------------------------------ 3. bad indices, bad weights
@@ -294,7 +245,6 @@ def test_bad_indices_and_weights_are_neutralised_and_counted(case):
     T.update_qnets()
     assert_same_state(A, T)
     del keep
-    close_all(A, T)
 
 
 # ------------------------------------------------------------------------------------------ 4. the engine's own uniform draw
@@ -319,7 +269,6 @@ def test_native_draw_starts_where_rb_sample_draws(case):
     A.update_qnets()                                                   # no weights: the unweighted critic graph
     assert A.graph_kernel_count(8) == 0
     del keep
-    close_all(A, T, Cn)
 
 
 # ------------------------------------------------------------------------------------------ 5. prioritised
@@ -355,7 +304,6 @@ def test_prioritised_nstep_draws_weights_and_writes_back_like_the_one_step_call(
     assert len(changed) > 0 and np.isin(changed, idx).all()            # the start slots only
     assert A.prio_stats()["samples"] == 1 and A.nstep_stats()["stagings"] == 1
     del keep
-    close_all(A, T, Cn)
 
 
 # ------------------------------------------------------------------------------------------ 6. the target is the n-step target
@@ -372,7 +320,7 @@ def test_the_critic_target_is_the_n_step_target(case, steps):
     gk = float(np.float32(np.float64(g32) ** steps))
     algo, _, ln = SHAPES[shape]
     hps = (Hps.td3 if algo == "td3" else Hps.sac)(layer_norm=ln, batch_size=B)
-    T = P.Engine(P.Config.from_hps(hps, o, a, rb_capacity=ring["cap"], max_envs=MAXN, seed=SEED, gamma=gk), [-bound] * a, [bound] * a)
+    T = track(P.Engine(P.Config.from_hps(hps, o, a, rb_capacity=ring["cap"], max_envs=MAXN, seed=SEED, gamma=gk), [-bound] * a, [bound] * a))
     push_params(T, ref)
     T.set_noise(_lib.SITE_CRITIC, eps)
     obs, act, rew, nobs, done = ring["fields"]
@@ -399,7 +347,6 @@ def test_the_critic_target_is_the_n_step_target(case, steps):
           f"largest ratio = {(err / bound_b)[~ended].max():.3f}")
     assert (err[~ended] <= bound_b[~ended]).all(), np.flatnonzero(err > bound_b)
     del keep
-    close_all(A, T)
 
 
 # ------------------------------------------------------------------------------------------ 7. host state
@@ -432,7 +379,6 @@ def test_n_step_state_is_set_by_the_three_calls_and_cleared_by_every_other_refil
     assert np.array_equal(res[0], res[1])
     assert_same_state(A, T)
     del keep
-    close_all(A, T)
 
 
 def test_slot_state_through_a_sequence_of_refills_and_updates():
@@ -461,7 +407,6 @@ def test_slot_state_through_a_sequence_of_refills_and_updates():
     s = state()
     assert s[:2] == (NO, OK) and s[2] > 0                                                     # the weighted graph, at its first use
     torch.cuda.synchronize()
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 8. views and streams
@@ -484,7 +429,6 @@ def test_strided_views_on_another_stream_give_the_same_bits(case):
     assert_slot_is(read_slot(V), read_slot(A), case)
     assert same_bits(V.debug_read("prio_weights"), A.debug_read("prio_weights"))
     del keep
-    close_all(A, V)
 
 
 # ------------------------------------------------------------------------------------------ 9. loop.train
@@ -501,7 +445,6 @@ def test_train_runs_with_n_step_returns(prioritized):
                     torch.device(DEV), cfg, P.ReplayBuffer(cfg.rb_capacity))
     metrics = loop.train(cfg, env, agent, fused=False, prioritized=prioritized, n_step=3)
     assert all(np.isfinite(v) for v in metrics.values()), metrics
-    st = agent.engine.nstep_stats()
+    st = track(agent.engine).nstep_stats()
     assert st["stagings"] == agent.qnet_updates_so_far > 100 and st["rows_staged"] == 64 * st["stagings"]
     assert st["rows_cut_short"] > 0 and st["rows_refused"] == 0
-    agent.engine.close()

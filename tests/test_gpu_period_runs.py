@@ -10,61 +10,40 @@ import functools
 
 import numpy as np
 import pytest
-import torch
 
-from oracle.sac_td3_ref import Hps, RefAgent
-from tests.helpers import DIMS, randomize_ln, synth_transitions
-from tests.test_gpu_engine import flat_actor, flat_critics
-from tests.test_gpu_prioritized import td_of
+from oracle.sac_td3_ref import Hps
+from tests.gpu_support import (P, _lib, assert_same_state, build_engines, close_engines, engine_state, flat_actor, flat_critics,  # noqa: F401
+                               new_engine)
+from tests.helpers import DIMS, synth_transitions
 
 pytestmark = pytest.mark.gpu
 
-import sac_td3_cudagraphs_pytorch_amd as P  # noqa: E402
-from sac_td3_cudagraphs_pytorch_amd import _lib  # noqa: E402
-
-SETS = (_lib.ACTOR, _lib.CRITICS, _lib.ACTOR_TARGET, _lib.CRITICS_TARGET, _lib.LOG_ALPHA)
 # (algo, env, B, the period graph is pipelined)
 CASES = {"sac-hopper-64": ("sac", "hopper", 64, True), "td3-halfcheetah-64": ("td3", "halfcheetah", 64, True),
          "sac-humanoid-1024": ("sac", "humanoid", 1024, True), "sac-humanoid-64": ("sac", "humanoid", 64, False)}
 PERIOD = 3      # actor_update_delay 2 (the default of both algorithms)
 ROWS = 3000
+PARTS = ("index", "noise", "td")      # what a sequence of iterations leaves behind, beside parameters, optimisers and metrics
 
 
 @functools.lru_cache(maxsize=None)
 def material(case):
     """(hps, dims, the oracle's perturbed initial parameters, the ring's rows): computed once per case, never written"""
     algo, env, B, _ = CASES[case]
-    o, a, bound = DIMS[env]
-    hps = (Hps.td3 if algo == "td3" else Hps.sac)(batch_size=B)
-    torch.manual_seed(5)
-    ref = RefAgent(o, a, [-bound] * a, [bound] * a, hps)
-    randomize_ln(ref)
+    ref, _, (o, a, bound) = build_engines(algo, DIMS[env], B, count=0, seed=5)
     params = {_lib.ACTOR: flat_actor(ref, ref.actor), _lib.ACTOR_TARGET: flat_actor(ref, ref.actor_target),
               _lib.CRITICS: flat_critics(ref, ref.qnets), _lib.CRITICS_TARGET: flat_critics(ref, ref.qnets_target)}
     rows = [t.numpy() for t in synth_transitions(ROWS + 400, o, a, bound, seed=31)]
-    return hps, (o, a, bound), params, rows
+    return ref.hps, (o, a, bound), params, rows
 
 
-_OPEN = []      # the engines of the running test
-
-
-@pytest.fixture(autouse=True)
-def close_engines():
-    """every engine a test made is destroyed when the test ends, passed or not"""
-    yield
-    for eng in _OPEN:
-        eng.close()
-    _OPEN.clear()
-
-
-def engine(hps, o, a, bound, **cfg):
-    _OPEN.append(P.Engine(P.Config.from_hps(hps, o, a, max_envs=8, seed=5, **cfg), [-bound] * a, [bound] * a))
-    return _OPEN[-1]
+def engine(hps, dims, **cfg):
+    return new_engine(hps, dims, max_envs=8, seed=5, **cfg)
 
 
 def build(case, use_graphs=True, cap=4096):
-    hps, (o, a, bound), params, rows = material(case)
-    eng = engine(hps, o, a, bound, rb_capacity=cap, use_graphs=use_graphs)
+    hps, dims, params, rows = material(case)
+    eng = engine(hps, dims, rb_capacity=cap, use_graphs=use_graphs)
     for which, flat in params.items():
         eng.set_params(which, flat)
     eng.rb_extend(*[r[:ROWS] for r in rows])
@@ -90,22 +69,6 @@ def singles(eng, it, n):
     return it + n
 
 
-def snapshot(eng):
-    """everything a sequence of iterations leaves behind"""
-    out = [eng.get_params(which) for which in SETS]
-    for which in (_lib.ACTOR, _lib.CRITICS, _lib.LOG_ALPHA):
-        m, v, t = eng.get_adam_state(which)
-        out += [np.asarray(m), np.asarray(v), np.array(t)]
-    out += [np.array(list(eng.read_metrics().values())), eng.read_batch()["index"], eng.read_noise(_lib.SITE_CRITIC), td_of(eng)]
-    return out
-
-
-def assert_same(A, B, what=""):
-    a, b = snapshot(A), snapshot(B)
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(x, y), (what, i)
-
-
 # ------------------------------------------------------------------------------------------ 1. bit equality
 @pytest.mark.parametrize("started", [False, True], ids=["fresh", "behind-a-period"])
 @pytest.mark.parametrize("case", list(CASES))
@@ -123,8 +86,8 @@ def test_step_periods_equals_periods_and_single_iterations(case, started):
         for _ in range(k):
             engs[1].step_period()
         singles(engs[2], 0, PERIOD * k)
-        assert_same(engs[0], engs[1], f"k={k}: runs vs periods")
-        assert_same(engs[0], engs[2], f"k={k}: runs vs single iterations")
+        assert_same_state(engs[0], engs[1], *PARTS, what=f"k={k}: runs vs periods")
+        assert_same_state(engs[0], engs[2], *PARTS, what=f"k={k}: runs vs single iterations")
         assert engs[0].get_adam_state(_lib.CRITICS)[2] == PERIOD * (k + started)
         st = engs[0].step_periods_stats()
         if CASES[case][3]:
@@ -162,10 +125,9 @@ def test_state_changes_between_runs_equal_single_iterations(case):
         run(R)
         eng.step(False)                                            # a single critic-only iteration
         run(R)
-        res.append(snapshot(eng) + [acted])
+        res.append(engine_state(eng, *PARTS, extra={"acted": acted}))
         eng.close()
-    for i, (x, y) in enumerate(zip(*res)):
-        assert np.array_equal(x, y), i
+    assert_same_state(*res, what="runs vs single iterations")
 
 
 # ------------------------------------------------------------------------------------------ 3. node counts and counters
@@ -185,17 +147,16 @@ def test_run_graph_node_count_and_counters():
     st = eng.step_periods_stats()
     assert st == {"calls": 1, "run_launches": 2, "single_period_launches": 1, "run_graphs_captured": 2}
     # the refusals: nothing changes
-    before = snapshot(eng)
+    before = engine_state(eng, *PARTS)
     with pytest.raises(P.EngineError, match="-1"):
         eng.step_periods(0)
     assert eng.step_periods_stats() == st
-    for x, y in zip(before, snapshot(eng)):
-        assert np.array_equal(x, y)
-    hps, (o, a, bound), _, _ = material("sac-hopper-64")
-    empty = engine(hps, o, a, bound, rb_capacity=256)
+    assert_same_state(before, engine_state(eng, *PARTS), what="a refused step_periods")
+    hps, dims, _, _ = material("sac-hopper-64")
+    empty = engine(hps, dims, rb_capacity=256)
     with pytest.raises(P.EngineError, match="-3"):
         empty.step_periods(2)
-    gated = engine(Hps.sac(batch_size=64, crit_targ_update_freq=2), o, a, bound, rb_capacity=256)
+    gated = engine(Hps.sac(batch_size=64, crit_targ_update_freq=2), dims, rb_capacity=256)
     gated.rb_fill_synthetic(200)
     with pytest.raises(P.EngineError, match="-3"):
         gated.step_periods(2)
@@ -215,7 +176,7 @@ def test_eager_launches_equal_the_run_graphs(case):
     for e in engs:
         e.step_periods(R + 1)
         e.step_periods(R)
-    assert_same(*engs)
+    assert_same_state(*engs, *PARTS)
     assert engs[1].graph_kernel_count(10) == 0 and engs[1].step_periods_stats()["run_graphs_captured"] == 0
 
 
@@ -226,11 +187,7 @@ def test_reads_behind_a_run_report_its_last_iteration(case):
     A, B = build(case), build(case)
     A.step_periods(R)
     singles(B, 0, PERIOD * R)
-    assert np.array_equal(td_of(A), td_of(B))
-    x, y = A.read_batch(), B.read_batch()
-    for k in x:
-        assert np.array_equal(x[k], y[k]), k
-    assert np.array_equal(A.read_noise(_lib.SITE_CRITIC), B.read_noise(_lib.SITE_CRITIC))
+    assert_same_state(A, B, "slot", "noise", "td", what="reads behind a run")
     for name in ("grad_critics", "c_dz1", "grad_actor", "a_dz1"):
         with pytest.raises(P.EngineError, match="-3"):
             A.debug_read(name)
@@ -251,7 +208,7 @@ def test_a_run_behind_predict_begin_leaves_the_action_of_the_serial_order(case):
     want = B.predict(rows[0][:4], True)
     B.step_periods(R)
     assert np.array_equal(got, want)
-    assert_same(A, B)
+    assert_same_state(A, B, *PARTS)
     assert np.array_equal(A.predict(rows[0][4:8], True), B.predict(rows[0][4:8], True))      # the exploration stream stands where it should
     assert A.acting_stats()["learner_waited_for_acting"] == 1
 
@@ -267,7 +224,7 @@ def test_run_iterations_through_runs_equals_single_iterations(case):
     it = A.run_iterations(1, n)
     it = A.run_iterations(it, 1 + PERIOD)
     assert it == singles(B, 1, n + 1 + PERIOD)
-    assert_same(A, B)
+    assert_same_state(A, B, *PARTS)
     st = A.step_periods_stats()
     want = (2, 1) if CASES[case][3] else (0, 2 * R + 1)
     assert (st["calls"], st["run_launches"], st["single_period_launches"]) == (1,) + want

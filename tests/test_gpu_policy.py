@@ -5,7 +5,7 @@ equality: the mode is the exploit action the scoring route's policy form compute
 asked with it, views change nothing, the native draws follow their own Philox stream, and training and acting cannot tell whether a
 call was made.
 
-Shapes (tests/test_gpu_qvalues.py: SHAPES / build): SAC Hopper (a = 3: the narrow head form), SAC Humanoid (o = 376, a = 17: the MFMA
+Shapes (tests/gpu_support.py: SHAPES / shape_engines): SAC Hopper (a = 3: the narrow head form), SAC Humanoid (o = 376, a = 17: the MFMA
 form, a second element per lane, wide observations), SAC Hopper without LayerNorm, TD3 HalfCheetah.  Row counts 1, 67 and 1041 = a
 chunk of 1024 rows and one of 17."""
 import copy
@@ -21,16 +21,11 @@ from oracle import replay_ref
 from oracle.sac_td3_ref import Hps
 from tests import policy_checks as pc
 from tests import tail_checks as tc
+from tests.gpu_support import (DEV, NROWS, SENTINEL, SHAPES, P, _lib, assert_same_state, close, close_engines, data, loop, make_engine,  # noqa: F401
+                               same_bits, score, shape_engines, stream, track)
 from tests.helpers import synth_transitions
-from tests.test_gpu_device_boundary import assert_same_state
-from tests.test_gpu_engine import close
-from tests.test_gpu_qvalues import DEV, NROWS, SENTINEL, SHAPES, build, data, same_bits, score, stream
-from tests.test_gpu_tail_edges import make_engine
 
 pytestmark = pytest.mark.gpu
-
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, loop  # noqa: E402
 
 F32 = np.float32
 ALL = ["sac-hopper", "sac-humanoid", "sac-hopper-noln", "td3-halfcheetah"]
@@ -88,7 +83,6 @@ def test_every_output_lies_in_its_float64_interval(shape, degenerate):
                 lo = n - z2.shape[0]
                 assert z2.shape[0] == (n - 1) % 1024 + 1
                 pc.check_policy_outputs(f"policy_intervals[{shape}]", z2, params, c, {"mode": got["mode"][lo:]})
-        eng.close()
         return
     own = ask(eng, obs, eps=eps, want=("sample",))["sample"]
     g = c["act"].copy()
@@ -111,7 +105,6 @@ def test_every_output_lies_in_its_float64_interval(shape, degenerate):
     if degenerate:          # (the 1041 rows) tanh(raw) == +-1 <=> log_std is exactly 2 or -5; y == +-1 <=> sample == bi +- sc
         assert np.isin(got["log_std"], (F32(2), F32(-5))).any(), "tanh(raw log-std) did not saturate"
         assert ((got["sample"] == c["bias"] + c["scale"]) | (got["sample"] == c["bias"] - c["scale"])).any(), "y did not saturate"
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. against the oracle
@@ -119,7 +112,7 @@ def test_every_output_lies_in_its_float64_interval(shape, degenerate):
 def test_mode_and_sample_match_the_oracles_actor(shape):
     """the oracle's actor on the same rows, injected draws: rtol 1e-5 + atol 1e-5, what
     tests/test_gpu_qvalues.py::test_scores_match_the_oracles_twin_critics applies to a forward pass at these shapes and this data"""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     obs_h = data(shape)[0]
     obs = obs_h.to(DEV)
     if SHAPES[shape][0] == "td3":
@@ -130,7 +123,6 @@ def test_mode_and_sample_match_the_oracles_actor(shape):
                 got = ask(eng, obs[:n], target=target)["mode"]
                 print(shape, target, n, "max |d mode|", float(np.abs(got - want[:n]).max()))
                 close(got, want[:n], rtol=1e-5, atol=1e-5, name=f"{shape} mode target={target} n={n}")
-        eng.close()
         return
     eps_h = draws(shape)
     with torch.no_grad():
@@ -158,7 +150,6 @@ def test_mode_and_sample_match_the_oracles_actor(shape):
         if rows.size:
             print(shape, n, "sample_logp", rows.size, "rows, max |d|", float(np.abs(got["sample_logp"][rows] - w32[rows]).max()))
             close(got["sample_logp"][rows], w32[rows], rtol=1e-5, atol=1e-5, name=f"{shape} sample_logp n={n}")
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 3. bit-for-bit ties to existing paths
@@ -166,7 +157,7 @@ def test_mode_and_sample_match_the_oracles_actor(shape):
 def test_bit_for_bit_ties(shape):
     """q_values(obs, actions=mode) == q_values(obs), the scoring route's policy form (online critics); sample with eps = 0 == mode; a
     row's outputs are the same bits alone, inside 67 rows and inside 1041 rows; the host call gives the device call's bits"""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     sac = SHAPES[shape][0] == "sac"
     obs_h, act_h = data(shape)
     obs, act = obs_h.to(DEV), act_h.to(DEV)
@@ -188,7 +179,6 @@ def test_bit_for_bit_ties(shape):
     else:
         host = eng.policy(obs_h.numpy())
     assert same(host, full)
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 4. native draws
@@ -197,7 +187,7 @@ def test_native_draws_follow_their_own_philox_stream_and_move_no_other_counter()
     stream 0x400 and the counter at 0, then 1; a call with `eps` given leaves the counter alone (the next native call draws with 2);
     the host call draws from the same stream.  A twin engine that asks nothing has the same noise buffers at every site and returns
     the same exploring action."""
-    ref, (R, N), (o, a, bound) = build("sac-humanoid", count=2)
+    ref, (R, N), (o, a, bound) = shape_engines("sac-humanoid", count=2)
     obs_h = data("sac-humanoid")[0]
     obs = obs_h.to(DEV)
     want = lambda ctr, n: replay_ref.normals(3, ctr, 0x400, n * a).reshape(n, a)
@@ -223,13 +213,12 @@ def test_native_draws_follow_their_own_philox_stream_and_move_no_other_counter()
     for site in range(6):
         assert np.array_equal(R.read_noise(site), N.read_noise(site)), site
     assert N.policy_stats() == dict(calls=0, rows=0, rows_clamped=0, rows_nan=0) and R.policy_stats()["calls"] == 10
-    R.close(); N.close()
 
 
 # ------------------------------------------------------------------------------------------ 5. edge actions
 @pytest.mark.parametrize("shape", ["sac-hopper", "sac-humanoid"])
 def test_edge_actions_clamp_count_and_stay_in_their_row(shape):
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     obs = data(shape)[0][:12].to(DEV)
     g = data(shape)[1][:12].numpy().copy()
     base = ask(eng, obs, dev(g), want=("action_logp", "mode"))
@@ -256,7 +245,6 @@ def test_edge_actions_clamp_count_and_stay_in_their_row(shape):
     f = g.copy()
     f[3, 0] = bound                               # ... and beyond the bound is the bound
     assert same_bits(ask(eng, obs[3:4], dev(f[3:4]), want=("action_logp",))["action_logp"], lp[3:4])
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 6. views
@@ -265,7 +253,7 @@ def test_views_in_and_out_from_another_stream(shape):
     """obs / actions / eps = strided, 4-byte-aligned views; outputs = windows at odd offsets of sentinel-filled tensors, a subset of
     them NULL; issued from another torch stream with SACTD3_SRC_ORDERED: the bits of the contiguous call, nothing outside the windows
     touched, the sources unchanged"""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     sac = SHAPES[shape][0] == "sac"
     ag = P.Agent.__new__(P.Agent)
     ag.engine = eng
@@ -313,7 +301,6 @@ def test_views_in_and_out_from_another_stream(shape):
         assert all(same_bits(v.reshape(want[names[k]].shape), want[names[k]]) for k, v in res.items())
     with pytest.raises(TypeError):
         ag.policy({"observations": obs_h[:4].to(DEV), "actions": act_h[:4].numpy()})
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 7. invisible to training
@@ -322,7 +309,7 @@ def test_asking_between_chained_periods_changes_nothing(shape):
     """two engines, one asks (native and injected draws, given actions; 67 rows) between rb_extend and the periods, between two
     back-to-back periods, around single steps and inside predict_begin / predict_end: same parameters, Adam state, metrics, sampled
     indices, TD errors, actions, graphs and every counter but the feature's own"""
-    _, (R, N), (o, a, bound) = build(shape, count=2, cap=1000)
+    _, (R, N), (o, a, bound) = shape_engines(shape, count=2, cap=1000)
     sac = SHAPES[shape][0] == "sac"
     obs, act = [t[:67].to(DEV) for t in data(shape)]
     eps = draws("sac-hopper")[:67].to(DEV)
@@ -378,14 +365,13 @@ def test_asking_between_chained_periods_changes_nothing(shape):
     calls = 12 * (3 if sac else 2)
     assert R.policy_stats() == dict(calls=calls, rows=calls * 67, rows_clamped=0, rows_nan=0)
     assert N.policy_stats() == dict(calls=0, rows=0, rows_clamped=0, rows_nan=0)
-    R.close(); N.close()
 
 
 # ------------------------------------------------------------------------------------------ 8. follows the parameters
 @pytest.mark.parametrize("shape", ["sac-hopper", "td3-halfcheetah"])
 def test_outputs_follow_the_parameters(shape):
     """after update_actor the outputs change; after set_params(ACTOR, old) they are the old bits; TD3's target form follows ACTOR_TARGET"""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     sac = SHAPES[shape][0] == "sac"
     obs, act = [t[:67].to(DEV) for t in data(shape)]
     kw = dict(actions=act, eps=draws(shape)[:67].to(DEV)) if sac else {}
@@ -406,14 +392,13 @@ def test_outputs_follow_the_parameters(shape):
         assert same_bits(ask(eng, obs, target=True)["mode"], after["mode"])
     eng.set_params(_lib.ACTOR, old)
     assert same(ask(eng, obs, **kw), before)
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 9. refusals
 def test_refusals_launch_nothing_and_leave_the_engine_usable():
     lib, ORD, vp = None, _lib.SRC_ORDERED, C.c_void_p
     for shape in ("sac-hopper", "td3-halfcheetah"):
-        ref, (eng,), (o, a, bound) = build(shape)
+        ref, (eng,), (o, a, bound) = shape_engines(shape)
         sac = SHAPES[shape][0] == "sac"
         lib, h = eng.lib, eng._h
         obs, act = [t[:8].to(DEV) for t in data(shape)]
@@ -505,7 +490,7 @@ def test_the_loop_records_the_policys_vitals_and_trains_the_same_bits(tmp_path):
         ev = loop.Evaluator(cfg, loop.SyntheticVecEnv(o, a, 1, horizon=20), agent, tab)
         m = loop.train(cfg, env, agent, evaluator=ev, policy_stats=stats)
         tab.close()
-        eng = agent.engine
+        eng = track(agent.engine)
         runs.append((m, [eng.get_params(w) for w in range(5)], [eng.get_adam_state(w) for w in (_lib.ACTOR, _lib.CRITICS, _lib.LOG_ALPHA)],
                      (agent.qnet_updates_so_far, agent.actor_updates_so_far, agent.timesteps_so_far), eng.policy_stats(),
                      (tmp_path / str(stats) / "progress.csv").read_text().splitlines()[0]))

@@ -13,35 +13,21 @@ import numpy as np
 import pytest
 import torch
 
-from oracle.sac_td3_ref import Hps, RefAgent
-from tests.helpers import DIMS, randomize_ln, synth_transitions
-from tests.test_gpu_engine import push_params
+from oracle.sac_td3_ref import Hps
+from tests.gpu_support import (DEV, MAXN, SENTINEL, SETS, P, _lib, assert_same_state, build_engines, close_engines, loop, stream,  # noqa: F401
+                               track)
+from tests.helpers import DIMS, synth_transitions
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, loop  # noqa: E402
-
-DEV = "cuda:0"
 SHAPES = [("sac", "hopper"), ("td3", "halfcheetah"), ("sac", "humanoid")]
 ROWS = (1, 4, 5, 16, 17, 67)
-MAXN = 96
-SETS = (_lib.ACTOR, _lib.CRITICS, _lib.ACTOR_TARGET, _lib.CRITICS_TARGET, _lib.LOG_ALPHA)
 
 
 def twins(algo, env, count=2, B=64, use_graphs=True, seed=3):
     """`count` engines with the same seed and the same (perturbed, so that every parameter matters) parameters"""
-    o, a, bound = DIMS[env]
-    hps = (Hps.td3 if algo == "td3" else Hps.sac)(layer_norm=True, batch_size=B)
-    torch.manual_seed(seed)
-    ref = RefAgent(o, a, [-bound] * a, [bound] * a, hps)
-    randomize_ln(ref)
-    engs = []
-    for _ in range(count):
-        eng = P.Engine(P.Config.from_hps(hps, o, a, rb_capacity=2048, max_envs=MAXN, seed=seed, use_graphs=use_graphs), [-bound] * a, [bound] * a)
-        push_params(eng, ref)
-        engs.append(eng)
-    return engs, (o, a, bound)
+    _, engs, dims = build_engines(algo, DIMS[env], B, count=count, seed=seed, cap=2048, max_envs=MAXN, use_graphs=use_graphs)
+    return engs, dims
 
 
 def obs_rows(n, o, seed):
@@ -52,8 +38,7 @@ def device_call(eng, obs, explore, out=None, ordered=True):
     """predict_device on a CUDA tensor `obs` [n, o] (any row stride) -> the actions as a host array"""
     n, a = obs.shape[0], eng.cfg.ac_dim
     out = torch.empty(n, a, device=DEV) if out is None else out
-    eng.predict_device(obs.data_ptr(), obs.stride(0), n, explore, out.data_ptr(), out.stride(0),
-                       torch.cuda.current_stream().cuda_stream, ordered)
+    eng.predict_device(obs.data_ptr(), obs.stride(0), n, explore, out.data_ptr(), out.stride(0), stream(), ordered)
     return out.cpu().numpy()            # (on the current stream, which the call made wait for the engine's)
 
 
@@ -77,7 +62,6 @@ def test_device_calls_equal_host_calls(algo, env, explore):
     if explore:                                                      # (the draws are in use: another call, other actions)
         obs = obs_rows(5, o, seed=1)
         assert not np.array_equal(device_call(D, obs.to(DEV), True), device_call(D, obs.to(DEV), True))
-    H.close(); D.close()
 
 
 @pytest.mark.parametrize("algo,env", SHAPES)
@@ -91,7 +75,6 @@ def test_host_and_device_calls_share_one_noise_stream(algo, env):
             got = device_call(M, obs.to(DEV), True) if on_device else M.predict(obs.numpy(), True)
             assert np.array_equal(want, got), (n, k)
         assert np.array_equal(H.read_noise(_lib.SITE_PREDICT, n), M.read_noise(_lib.SITE_PREDICT, n))
-    H.close(); M.close()
 
 
 def test_eager_sequence_equals_host_calls():
@@ -101,13 +84,9 @@ def test_eager_sequence_equals_host_calls():
             obs = obs_rows(n, o, seed=n + k)
             assert np.array_equal(H.predict(obs.numpy(), True), device_call(D, obs.to(DEV), True)), (n, k)
     assert np.array_equal(H.read_noise(_lib.SITE_PREDICT, 17), D.read_noise(_lib.SITE_PREDICT, 17))
-    H.close(); D.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. views
-SENTINEL = -12345.678
-
-
 @pytest.mark.parametrize("algo,env", SHAPES)
 def test_views_in_and_out(algo, env):
     """obs = big[:, 1:1+o] (rows 4-byte aligned only, stride above the width), out = wide[:, 2:2+a] of a sentinel-filled tensor with
@@ -145,7 +124,6 @@ def test_views_in_and_out(algo, env):
     assert (wide == SENTINEL).all()
     with pytest.raises(TypeError):
         ag.predict_device({"observations": obs_rows(4, o, 0)}, explore=False)      # host data: predict() takes it
-    H.close(); D.close()
 
 
 # ------------------------------------------------------------------------------------------ 3. ordering without synchronisation
@@ -177,21 +155,9 @@ def test_ordered_against_the_callers_stream_without_a_sync():
     side.synchronize()
     assert np.array_equal(result.cpu().numpy(), want)
     assert torch.isnan(obs).all()
-    T.close(); D.close()
 
 
 # ------------------------------------------------------------------------------------------ 4. neutral to the learner
-def learner_state(eng):
-    out = [eng.get_params(w) for w in SETS]
-    for w in (_lib.ACTOR, _lib.CRITICS, _lib.LOG_ALPHA):
-        m, v, t = eng.get_adam_state(w)
-        out += [m, v, np.asarray([t])]
-    met = eng.read_metrics()
-    out.append(np.asarray([met[k] for k in sorted(met)], np.float32))
-    out.append(eng.read_batch()["index"])
-    return out
-
-
 @pytest.mark.parametrize("algo,env", [("sac", "hopper"), ("td3", "halfcheetah")])
 def test_device_acting_between_periods_leaves_the_learner_alone(algo, env):
     """4 periods through run_iterations with an acting call between them: predict on one engine, predict_device on its twin.
@@ -208,10 +174,8 @@ def test_device_acting_between_periods_leaves_the_learner_alone(algo, env):
         for e in (H, D):
             assert e.run_iterations(3 * p, 3) == 3 * p + 3
         assert np.array_equal(H.predict(obs.numpy(), True), device_call(D, obs.to(DEV), True)), p
-    for x, y in zip(learner_state(H), learner_state(D)):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
+    assert_same_state(H, D, "index")
     assert D.graph_kernel_count(4) == H.graph_kernel_count(4) == nodes
-    H.close(); D.close()
 
 
 # ------------------------------------------------------------------------------------------ 5. the loop
@@ -239,7 +203,7 @@ def test_train_on_a_device_env_equals_train_on_the_host_env():
         agent = P.Agent({"ob_shape": (n, o), "ac_shape": (n, a)}, np.full(a, -1.0, np.float32), np.full(a, 1.0, np.float32),
                         torch.device(DEV), cfg, P.ReplayBuffer(cfg.rb_capacity))
         m = loop.train(cfg, env, agent, fused=True, device_env=device_env)
-        eng = agent.engine
+        eng = track(agent.engine)
         st = eng.predict_device_stats()
         assert (st["calls"] > 0) == device_env and (eng.boundary_stats()["device_extends"] > 0) == device_env
         ring = []
@@ -295,7 +259,6 @@ def test_bad_arguments_and_the_acting_call_in_flight():
     got = out.cpu().numpy()
     assert np.isfinite(got[:4]).all() and not np.array_equal(got[:4], first) and (got[4:] == np.float32(SENTINEL)).all()
     assert lib.sactd3_predict_device_stats(h, st) == 0 and list(st) == [1, 4, 1, 0]
-    eng.close()
 
 
 @pytest.mark.parametrize("algo,env", [("sac", "hopper"), ("td3", "halfcheetah")])
@@ -329,7 +292,6 @@ def test_predict_begin_behind_a_device_call_waits_for_it(algo, env):
         assert np.array_equal(out.cpu().numpy(), want[0]) and np.array_equal(got_small, want[1]), (k, n)
         assert np.array_equal(H.read_noise(_lib.SITE_PREDICT, 4), D.read_noise(_lib.SITE_PREDICT, 4))
     assert D.acting_stats()["begin_waited_for_learner"] == 5 and H.acting_stats()["begin_waited_for_learner"] == 1
-    H.close(); D.close()
 
 
 def test_device_env_on_the_gpu_equals_the_host_env_across_pool_refreshes():

@@ -5,7 +5,6 @@ notice a pinned ring; the loop.
 
 Shapes: SAC Hopper dims at B = 64 and B = 40 (a ragged last block in the staging) and TD3 HalfCheetah dims at B = 64; rings of 38 to
 64 slots with 37 pinned rows."""
-import ctypes as C
 import functools
 from types import SimpleNamespace
 
@@ -16,29 +15,22 @@ import torch
 from oracle.replay_ref import sample_indices
 from oracle.sac_td3_ref import Hps
 from tests import mix_ref
-from tests.test_gpu_device_boundary import assert_same_state, fields_of, rows
-from tests.test_gpu_engine import push_params
-from tests.test_gpu_prioritized import assert_same_bits, close_all, td_of
-from tests.test_gpu_qvalues import SHAPES, build as q_build, same_bits
+from tests.gpu_support import (DEV, MAXN, SEED, SHAPES, P, _lib, agent_mod, assert_same_bits, assert_same_state, call_sequence,  # noqa: F401
+                               close_engines, engine_state, fields_of, iteration_state, loop, new_engine, raw_step, rows, same_bits,
+                               shape_engines, stream, track)
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, loop  # noqa: E402
-
-DEV = "cuda:0"
-SEED = 3                                          # the engines' Philox key (tests/test_gpu_qvalues.py build())
 PIN = 37
 CASES = {"sac-hopper-64": ("sac-hopper", 64), "sac-hopper-40": ("sac-hopper", 40), "td3-halfcheetah-64": ("td3-halfcheetah", 64)}
-SETS = (_lib.ACTOR, _lib.CRITICS, _lib.ACTOR_TARGET, _lib.CRITICS_TARGET, _lib.LOG_ALPHA)
 E, S = _lib.EINVAL, _lib.ESTATE
 
 
 def bare_engine(shape, B, cap, **cfg):
     """an engine whose parameters nobody reads: rings and draws only"""
-    algo, (o, a, bound), ln = SHAPES[shape]
+    algo, dims, ln = SHAPES[shape]
     hps = (Hps.td3 if algo == "td3" else Hps.sac)(layer_norm=ln, batch_size=B)
-    return P.Engine(P.Config.from_hps(hps, o, a, rb_capacity=cap, max_envs=96, seed=SEED, **cfg), [-bound] * a, [bound] * a)
+    return new_engine(hps, dims, rb_capacity=cap, max_envs=MAXN, seed=SEED, **cfg)
 
 
 @functools.lru_cache(maxsize=None)
@@ -75,7 +67,7 @@ def append(eng, path, five, keep):
     else:                                         # five device fields (sactd3_rb_extend_fields_device)
         dev = tuple(t.to(DEV) for t in five)
         fields, n, hold = fields_of(eng, dev)
-        eng.rb_extend_fields_device(fields, n, torch.cuda.current_stream().cuda_stream)
+        eng.rb_extend_fields_device(fields, n, stream())
         keep.append((dev, hold))
 
 
@@ -123,7 +115,6 @@ def test_pinned_appends_follow_the_cursor_model(path, cap):
     assert st["pinned_wraps"] == model.wraps > 1 and st["mixed_draws"] == 0
     eng.sync()
     del keep
-    eng.close()
 
 
 def test_pin_on_an_exactly_full_ring_and_unpin():
@@ -151,7 +142,6 @@ def test_pin_on_an_exactly_full_ring_and_unpin():
     assert eng.rb_len() == 48 and eng.mix_stats()["pinned_wraps"] == 0
     eng.rb_extend(*five)
     assert same_bits(ring_flat(eng, 48)[:4], flat(five))
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. the exact draw
@@ -175,7 +165,6 @@ def test_mixed_draw_is_the_slot_formula_and_ticks_the_counter_once(case, live):
         eng.rb_sample()
     assert_same_bits(A.read_batch(), T.read_batch(), what="the uniform sample behind five draws")      # the counter moved once per draw
     assert np.array_equal(A.read_batch()["index"], sample_indices(SEED, 5, B, length))
-    close_all(A, T)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -188,7 +177,6 @@ def test_mixed_draw_without_pinned_rows_is_rb_sample(case):
         A.rb_sample_mixed()                       # P = 0, m = 0
         T.rb_sample()
         assert_same_bits(A.read_batch(), T.read_batch(), what="P = 0, m = 0")
-    close_all(A, T)
 
 
 def test_every_row_pinned_and_every_batch_row_prior():
@@ -197,42 +185,26 @@ def test_every_row_pinned_and_every_batch_row_prior():
     eng.rb_set_mix(B)
     eng.rb_sample_mixed()
     assert np.array_equal(eng.read_batch()["index"], mix_ref.mixed_indices(SEED, 0, B, B, PIN, PIN))
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 3. one launch equals the call sequence
+def mixed_draw(m):
+    """the mixed draw with m prior rows, as call_sequence takes it (the mix is set only when it changes)"""
+    def draw(eng):
+        if eng.mix_rows != m:
+            eng.rb_set_mix(m)
+            eng.mix_rows = m
+        eng.rb_sample_mixed()
+    return draw
+
+
 def twins(case, cap, use_graphs=(True, True)):
     shape, B = CASES[case]
-    algo, (o, a, bound), ln = SHAPES[shape]
-    ref, engs, _ = q_build(shape, 0, B=B, cap=cap)
-    hps = (Hps.td3 if algo == "td3" else Hps.sac)(layer_norm=ln, batch_size=B)
-    for g in use_graphs:
-        eng = P.Engine(P.Config.from_hps(hps, o, a, rb_capacity=cap, max_envs=96, seed=SEED, use_graphs=g), [-bound] * a, [bound] * a)
-        push_params(eng, ref)
+    _, engs, _ = shape_engines(shape, B=B, cap=cap, use_graphs=use_graphs)
+    for eng in engs:
         eng.rb_extend(*some_rows(shape, PIN, 1))
         eng.rb_pin(PIN)
-        engs.append(eng)
     return engs, shape, B
-
-
-def call_sequence(eng, do_actor, m, updates):
-    """the iteration call by call: what sactd3_step_sampled with the mixed draw has to equal"""
-    if eng.mix_rows != m:
-        eng.rb_set_mix(m)
-        eng.mix_rows = m
-    eng.rb_sample_mixed()
-    eng.update_qnets()
-    if do_actor:
-        for _ in range(eng.cfg.actor_update_delay):
-            eng.update_actor()
-    eng.update_targ_nets(updates)
-
-
-def iteration_state(eng):
-    d = dict(eng.read_batch())
-    d["td"] = td_of(eng)
-    d["metrics"] = np.float32(list(eng.read_metrics().values()))
-    return d
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -246,7 +218,7 @@ def test_one_launch_equals_the_call_sequence(case):
         for eng in (A, Bt):
             eng.rb_extend(*some_rows(shape, 4, 200 + i, 4 * i))
         m = B // 2 if i < 3 else B // 4
-        call_sequence(A, i % 3 == 0, m, i + 1)
+        call_sequence(A, i % 3 == 0, mixed_draw(m), i + 1)
         Bt.step_sampled(i % 3 == 0, prior_rows=m)
         assert_same_bits(iteration_state(A), iteration_state(Bt), what=f"iteration {i}")
         idx = Bt.read_batch()["index"]
@@ -261,7 +233,6 @@ def test_one_launch_equals_the_call_sequence(case):
     assert Bt.step_sampled_stats() == dict(launches=7, graph_captures=2) and A.step_sampled_stats()["launches"] == 0
     nodes = [Bt.graph_kernel_count(16 + k) for k in range(4)]
     assert nodes[0] == nodes[2] == 0 and nodes[3] > nodes[1] > 4
-    close_all(A, Bt)
 
 
 # ------------------------------------------------------------------------------------------ 4. the eager form
@@ -276,20 +247,13 @@ def test_eager_form_equals_the_graph():
     assert_same_state(G, Eg)
     assert Eg.step_sampled_stats() == dict(launches=6, graph_captures=0) and G.step_sampled_stats()["graph_captures"] == 2
     assert G.mix_stats() == Eg.mix_stats()
-    close_all(G, Eg)
 
 
 # ------------------------------------------------------------------------------------------ 5. refusals
-def raw_step(eng, do_actor, draw, n_step, stride, beta):
-    sm = _lib.CSampling(draw, n_step, stride, beta)
-    return eng.lib.sactd3_step_sampled(eng._h, do_actor, C.byref(sm))
-
-
-def snapshot(eng):
-    d = {f"params{w}": eng.get_params(w) for w in SETS}
-    d["ring"] = ring_flat(eng, eng.rb_len()) if eng.rb_len() else np.zeros(1, np.float32)
-    d["stats"] = np.float32(list(eng.mix_stats().values()) + [eng.rb_len(), eng.rb_pinned()])
-    return d
+def ring_and_counters(eng):
+    """what a pinned ring adds to an engine's state: every held row, the mix counters, the length and the pinned rows"""
+    return dict(ring_flat=ring_flat(eng, eng.rb_len()) if eng.rb_len() else np.zeros(1, np.float32),
+                mix_stats=np.float32(list(eng.mix_stats().values()) + [eng.rb_len(), eng.rb_pinned()]))
 
 
 def test_refusals_change_nothing_and_leave_the_engine_usable():
@@ -297,7 +261,7 @@ def test_refusals_change_nothing_and_leave_the_engine_usable():
     eng.rb_extend(*some_rows(shape, 8, 2))        # 37 pinned + 8 live
     lib, h = eng.lib, eng._h
     M, U = _lib.DRAW_MIXED, _lib.DRAW_UNIFORM
-    before = snapshot(eng)
+    before = engine_state(eng, extra=ring_and_counters(eng))
     # sactd3_rb_pin: n out of range
     for n in (-1, PIN + 9, PIN + 20, 10 ** 12):
         assert lib.sactd3_rb_pin(h, n) == E, n
@@ -313,7 +277,7 @@ def test_refusals_change_nothing_and_leave_the_engine_usable():
     assert raw_step(eng, 1, U, 3, 4, 0.0) == S and lib.sactd3_rb_fill_synthetic(h, 16, 0) == S
     # the mixed draw inside the one launch: n_step must be 1; beta is still checked
     assert raw_step(eng, 1, M, 2, 4, 0.0) == E and raw_step(eng, 1, M, 16, 1, 0.0) == E and raw_step(eng, 1, M, 1, 1, -1.0) == E
-    assert_same_bits(before, snapshot(eng), what="refused calls on a pinned ring")
+    assert_same_state(before, engine_state(eng, extra=ring_and_counters(eng)), what="refused calls on a pinned ring")
     # no live row: m < B is refused, by the call and by the one launch
     full = pinned_engine(shape, B, 64, 0)
     full.rb_set_mix(B - 1)
@@ -336,9 +300,8 @@ def test_refusals_change_nothing_and_leave_the_engine_usable():
     # ... and the refused engine runs a normal iteration, and a mixed one
     eng.step(True)
     eng.step_sampled(True, prior_rows=B // 2)
-    assert not same_bits(eng.get_params(_lib.CRITICS), before[f"params{_lib.CRITICS}"])
+    assert not same_bits(eng.get_params(_lib.CRITICS), before["params.critics"])
     assert eng.mix_stats()["mixed_draws"] == 1 and eng.step_sampled_stats()["graph_captures"] == 1
-    close_all(eng, full, plain, empty, wrapped, prio)
 
 
 # ------------------------------------------------------------------------------------------ 6. the untouched paths
@@ -361,7 +324,6 @@ def test_the_uniform_paths_do_not_notice_a_pinned_ring():
     eng.rb_sample_with_indices(np.arange(B) % length)
     assert np.array_equal(eng.read_batch()["index"], np.arange(B) % length)
     assert eng.mix_stats()["mixed_draws"] == 0
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 7. the loop
@@ -383,13 +345,13 @@ def test_train_one_launch_equals_the_call_by_call_loop():
                         torch.device(DEV), cfg, P.ReplayBuffer(cfg.rb_capacity))
         assert loop.load_dataset(agent, data, pin=True) == 40 and agent.rb.pinned == 40
         loop.train(cfg, env, agent, fused=False, prior_fraction=0.5, updates_per_step=2, one_launch=one_launch)
-        eng = agent.engine
-        res.append(dict({f"params{w}": eng.get_params(w) for w in SETS}, ring=ring_flat(eng, 64),
-                        counters=np.float32([agent.qnet_updates_so_far, agent.actor_updates_so_far, agent.timesteps_so_far, len(agent.rb)]),
-                        mix=np.float32(list(eng.mix_stats().values()))))
+        eng = track(agent.engine)
+        res.append(engine_state(eng, extra=dict(
+            ring_and_counters(eng),
+            counters=np.float32([agent.qnet_updates_so_far, agent.actor_updates_so_far, agent.timesteps_so_far, len(agent.rb)]))))
         assert agent.qnet_updates_so_far == 20 and len(agent.rb) == 64 and agent.rb.pinned == 40
         assert eng.mix_stats() == dict(mixed_draws=20, prior_rows_drawn=20 * 32, live_rows_drawn=20 * 32, pinned_wraps=2)
         launches = eng.step_sampled_stats()
         assert launches["launches"] == (20 if one_launch else 0) and launches["graph_captures"] <= 2
         eng.close()
-    assert_same_bits(res[0], res[1], what="one_launch against the call sequence")
+    assert_same_state(res[0], res[1], what="one_launch against the call sequence")

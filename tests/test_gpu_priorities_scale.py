@@ -3,7 +3,7 @@ numpy float32 -- bit for bit: group sums, drawn slots, leaves and sums behind ap
 model, every drawn slot against the a-priori float64 interval of tests/bounds.py:prio_draw_interval.  Both are kept: a reading
 of the kernel that model and test share cannot hide a draw from the wrong group from the float64 running sums.
 
-Rings, leaves and uniforms are those of tests/test_prio_model.py (which shows on the CPU that they take the leaf fall-back, the
+Rings, leaves and uniforms are the case table of tests/prio_model.py (tests/test_prio_model.py shows on the CPU that they take the leaf fall-back, the
 group fall-back in either chunk, the second top-level chunk and uniforms whose m is a running sum): one group; one group and a
 leaf; the reference's 1 000 000 slots (977 groups); 1 050 076 slots with 1 050 039 held (1026 groups: two chunks, the last group
 partly filled); 1 100 000 slots (1075 groups: the group fall-back inside the second chunk).  SAC Hopper, B = 64; the rings are
@@ -21,31 +21,22 @@ import torch
 from tests import bounds
 from tests import priorities_ref as pref
 from tests import prio_model as pm
-from tests import test_prio_model as cpu
+from tests.gpu_support import (BOUND_REL, DEV, SEED, SHAPES, _lib, call_sequence, close_engines, cuda, extend_device, same_bits,  # noqa: F401
+                               sampled_draw, shape_engines, stream, td_of)
 from tests.helpers import observe, synth_transitions
-from tests.test_gpu_device_boundary import cuda, extend_device
-from tests.test_gpu_native_priorities import BOUND_REL
-from tests.test_gpu_prioritized import close_all, stream, td_of
-from tests.test_gpu_qvalues import SHAPES, build as q_build, same_bits
-from tests.test_gpu_step_sampled import call_sequence
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib  # noqa: E402
-
-DEV = "cuda:0"
 SHAPE, B, EPS, BETA = "sac-hopper", 64, 1e-6, 0.4
 CALL_ROWS = 8192
 F32, G = np.float32, pm.G
 BIG = (1_050_076, 1_050_039)
-RINGS = [r + (fill,) for r in ((1024, 1024), (1025, 1025), (1_000_000, 1_000_000), BIG) for fill in cpu.FILLS]
+RINGS = [r + (fill,) for r in ((1024, 1024), (1025, 1025), (1_000_000, 1_000_000), BIG) for fill in pm.FILLS]
 RINGS += [(1_100_000, 1_100_000, "uniform"), (1_100_000, 1_100_000, "spike")]
-SEED = 3                            # the engines' Philox key (tests/test_gpu_qvalues.py build())
 GROUPS = {1024: 1, 1025: 2, 1_000_000: 977, 1_050_076: 1026, 1_100_000: 1075}
 
 
-def write(eng, idx, prio):
+def write_chunked(eng, idx, prio):
     """prio_update_device on device tensors, at most CALL_ROWS rows a call (one workgroup per row walks all rows of its call)"""
     for lo in range(0, idx.shape[0], CALL_ROWS):
         n = min(CALL_ROWS, idx.shape[0] - lo)
@@ -55,8 +46,8 @@ def write(eng, idx, prio):
 def ring(cap, held, fill, count=1, alpha=1.0):
     """`count` twin engines whose ring holds `held` synthetic rows and whose priorities are the leaves of the CPU case (alpha == 1: its
     leaves); -> (engines, case, the model's table for the leaves read back)"""
-    k = cpu.case(cap, held, fill)
-    _, engs, (o, a, bound) = q_build(SHAPE, count, B=B, cap=cap)
+    k = pm.case(cap, held, fill)
+    _, engs, (o, a, bound) = shape_engines(SHAPE, count, B=B, cap=cap)
     noise = torch.randn(B, a, generator=torch.Generator().manual_seed(4))
     idx, prio = torch.arange(held, device=DEV), torch.as_tensor(k.leaf.copy(), device=DEV)
     for eng in engs:
@@ -65,7 +56,7 @@ def ring(cap, held, fill, count=1, alpha=1.0):
         eng.prio_enable(alpha, EPS)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        write(eng, idx, prio)
+        write_chunked(eng, idx, prio)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         print(f"{cap}-{held}-{fill}: {(held + CALL_ROWS - 1) // CALL_ROWS} prio_update_device calls wrote {held} leaves in {dt:.4f} s")
@@ -116,7 +107,7 @@ def into_groups(t, C, groups, n=B):
 
 
 # ------------------------------------------------------------------------------------------ 1. sums, draws, weights per ring
-@pytest.mark.parametrize("cap,held,fill", RINGS, ids=[cpu.case_id(r) for r in RINGS])
+@pytest.mark.parametrize("cap,held,fill", RINGS, ids=[pm.case_id(r) for r in RINGS])
 def test_sums_and_draws_have_the_models_bits_and_lie_in_the_float64_interval(cap, held, fill):
     """prio_sums equal the model's sums of the leaves read back as uint32; the CPU case's directed uniforms, 64 a call, and one native
     call draw exactly the model's slots; each slot lies in its float64 interval for m = fl32(u T), T the total the model predicts (the
@@ -129,7 +120,7 @@ def test_sums_and_draws_have_the_models_bits_and_lie_in_the_float64_interval(cap
     worst_iv = worst_w = 0.0
     slots, T, m, paths = pm.draws(t, held, k.u)
     assert np.array_equal(slots, k.slots)                                    # (the CPU case: its fall-back draws are among these)
-    observe("prio_draw_interval_model", cpu.case_id((cap, held, fill)), bounds.prio_draw_interval("model", t.leaf, held, slots, m, t.nch, C))
+    observe("prio_draw_interval_model", pm.case_id((cap, held, fill)), bounds.prio_draw_interval("model", t.leaf, held, slots, m, t.nch, C))
     for j, u in enumerate(batches(k.u)):
         want, _, m, _ = pm.draws(t, held, u)
         got = draw(eng, u)
@@ -150,11 +141,10 @@ def test_sums_and_draws_have_the_models_bits_and_lie_in_the_float64_interval(cap
     worst_iv = max(worst_iv, bounds.prio_draw_interval(f"{cap}-{held}-{fill} native", t.leaf, held, got, m, t.nch, C))
     print(f"{cap}-{held}-{fill}: {len(k.u)} directed draws, worst interval err / tol {worst_iv:.4f}, worst weight delta {worst_w:.3e}, "
           f"fall-backs: group {sum(p.group_fallback for p in paths)}, leaf {sum(p.leaf_fallback for p in paths)}, chunk 1: {sum(p.chunk == 1 for p in paths)}")
-    observe("prio_draw_interval_device", cpu.case_id((cap, held, fill)), worst_iv)
-    observe("prio_scale_weights", cpu.case_id((cap, held, fill)) + ": max relative delta", worst_w)
+    observe("prio_draw_interval_device", pm.case_id((cap, held, fill)), worst_iv)
+    observe("prio_scale_weights", pm.case_id((cap, held, fill)) + ": max relative delta", worst_w)
     st = eng.prio_stats()
     assert st["rows_refused"] == 0 and st["samples"] == len(batches(k.u)) + 1 and eng.priority_stats()["rows_refused"] == 0
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. appends at scale
@@ -176,7 +166,6 @@ def test_appends_in_the_second_chunk_and_across_the_wrap_leave_the_models_table(
     assert eng.prio_stats() == dict(samples=0, write_backs=(held + CALL_ROWS - 1) // CALL_ROWS, rows_refused=0, rows_entered_at_max=held + 2000 + 1_049_000)
     u = into_groups(t, np.cumsum(t.leaf[:cap].astype(np.float64)), [1023, 1024, 1025, 0])
     assert np.array_equal(draw(eng, u), pm.draws(t, cap, u)[0])              # ... and the table draws like the model's
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 3. write-backs in the second chunk
@@ -187,7 +176,7 @@ def test_write_backs_in_the_second_chunk_leave_the_models_table():
     idx = np.array([1_048_574, 1_048_575, 1_048_576, 1_048_577, 1_048_575, 1_050_038, 1_048_576, 1_049_600, 1_048_575], np.int64)
     prio = np.array([0.5, 0.25, 4.0, 0.0, 1.5, 2.0, 0.125, 3.0, 0.75], F32)
     keep = torch.as_tensor(idx, device=DEV), torch.as_tensor(prio, device=DEV)
-    write(eng, *keep)
+    write_chunked(eng, *keep)
     t1, refused = pm.write_back(t, held, idx, prio)
     assert refused == 0 and t1.leaf[1_048_575] == 0.75 and t1.leaf[1_048_576] == 0.125 and t1.leaf[1_048_577] == 0.0
     assert_table(eng, t1, "prio_update_device across the chunk boundary")
@@ -210,7 +199,6 @@ def test_write_backs_in_the_second_chunk_leave_the_models_table():
         assert t2.leaf[rows[b]] == p32[np.flatnonzero(rows == rows[b])[-1]]
     assert eng.prio_stats()["rows_refused"] == 0
     del keep
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 4. the graph forms at nch = 2
@@ -225,7 +213,7 @@ def test_the_graph_forms_draw_and_write_back_like_the_call_sequence_at_two_chunk
     u[:2] = [0.0, pm.U_MAX]
     for eng in (A, Bt):
         eng.prio_set_uniforms(u)
-    call_sequence(A, False, BETA, 1, 1, 1)
+    call_sequence(A, False, sampled_draw(BETA), 1, write_back=True)
     Bt.step_sampled(False, beta=BETA)
     want, T, m, paths = pm.draws(t, held, u)
     rows = Bt.read_batch()["index"]
@@ -240,7 +228,6 @@ def test_the_graph_forms_draw_and_write_back_like_the_call_sequence_at_two_chunk
     assert_table(Bt, t2, "step_sampled")
     assert same_bits(A.debug_read("prio_max"), Bt.debug_read("prio_max"))
     assert A.prio_stats() == Bt.prio_stats() and Bt.prio_stats()["rows_refused"] == 0 and Bt.step_sampled_stats()["launches"] == 1
-    close_all(A, Bt)
 
 
 # ------------------------------------------------------------------------------------------ 5. alpha != 1
@@ -263,4 +250,3 @@ def test_behind_a_power_the_sums_and_draws_are_still_the_models():
         assert np.array_equal(got, slots), np.flatnonzero(got != slots)
         bounds.prio_draw_interval("alpha 0.6", t.leaf, held, got, m, t.nch, C)
     assert eng.prio_stats()["rows_refused"] == 0
-    eng.close()

@@ -2,7 +2,7 @@
 sactd3_batch_weights_device, sactd3_td_errors_device, the weighted form of sactd3_update_qnets; include/sactd3.h).  Against the oracle
 at the tolerances the suite applies to the unweighted critic update; everything else is an equality of bits against a twin engine.
 
-Engines are built like build() of tests/test_gpu_qvalues.py (the oracle's perturbed parameters), with a 2048-row ring of
+Engines are shape_engines() of tests/gpu_support.py (the oracle's perturbed parameters), with a 2048-row ring of
 synth_transitions (every 5th row done) and the critic site's noise injected.  Shapes: SAC Hopper at B = 64; at B = 40 (ends in a
 partial 16-row tile: the clamped rows meet the weight); TD3 HalfCheetah at B = 64; SAC Hopper without LayerNorm at B = 64; SAC Hopper at
 B = 1024 (k_critic_tail_w<16> instead of k_ctail_nn_w<2>)."""
@@ -15,20 +15,14 @@ import pytest
 import torch
 
 from oracle.sac_td3_ref import Hps
+from tests.gpu_support import (DEV, SENTINEL, SHAPES, P, _lib, assert_same_bits, assert_same_state, close, close_engines, crit_layout, cuda,  # noqa: F401
+                               flat_critics, gclose, load_device, loop, same_bits, schema, shape_engines, slot, stage, stream, td_of, track)
 from tests.helpers import assert_params_close, observe, synth_transitions
-from tests.test_gpu_device_boundary import assert_same_state, cuda, load_device
-from tests.test_gpu_engine import close, crit_layout, flat_critics, gclose
-from tests.test_gpu_qvalues import SHAPES, build as q_build, same_bits
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, loop, schema  # noqa: E402
-
-DEV = "cuda:0"
 RING = 2048
-SENTINEL = -12345.678
-# name -> (shape of tests/test_gpu_qvalues.py, batch size)
+# name -> (shape of gpu_support.SHAPES, batch size)
 CASES = {"sac-hopper-64": ("sac-hopper", 64), "sac-hopper-40": ("sac-hopper", 40), "td3-halfcheetah-64": ("td3-halfcheetah", 64),
          "sac-hopper-noln-64": ("sac-hopper-noln", 64), "sac-hopper-1024": ("sac-hopper", 1024)}
 ALL = list(CASES)
@@ -47,7 +41,7 @@ def ring_rows(shape):
 def build(case, count):
     """the oracle and `count` twin engines: same parameters, same ring, same injected critic noise"""
     shape, B = CASES[case]
-    ref, engs, (o, a, bound) = q_build(shape, count, B=B, cap=RING)
+    ref, engs, (o, a, bound) = shape_engines(shape, count, B=B, cap=RING)
     eps = torch.randn(B, a, generator=torch.Generator().manual_seed(4))
     for eng in engs:
         eng.rb_extend(*[t.numpy() for t in ring_rows(shape)])
@@ -70,37 +64,10 @@ def weights_u02(B, seed=1):
     return w
 
 
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def stage(eng, idx, w=None):
-    """sactd3_rb_sample_indices_device on CUDA tensors (any stride); -> what has to stay alive"""
-    idx = idx if torch.is_tensor(idx) else torch.as_tensor(idx, device=DEV)
-    w = w.to(DEV) if torch.is_tensor(w) and not w.is_cuda else w
-    eng.rb_sample_indices_device(idx.data_ptr(), max(idx.stride(0), 1), 0 if w is None else w.data_ptr(), 1 if w is None else max(w.stride(0), 1),
-                                 idx.shape[0], stream())
-    return idx, w
-
-
 def attach(eng, w):
     w = w.to(DEV) if not w.is_cuda else w
     eng.batch_weights_device(w.data_ptr(), max(w.stride(0), 1), w.shape[0], stream())
     return w
-
-
-def td_of(eng):
-    """sactd3_td_errors_device -> [2, B] on the host"""
-    B = eng.cfg.batch_size
-    out = torch.full((2, B), SENTINEL, device=DEV)
-    eng.td_errors_device(out.data_ptr(), 1, B, stream())
-    return out.cpu().numpy()
-
-
-def slot(eng):
-    d = {k: eng.debug_read(k) for k in ("X", "Xn", "rew", "done")}
-    d["index"] = eng.read_batch()["index"]
-    return d
 
 
 def critic_update_state(eng):
@@ -108,16 +75,6 @@ def critic_update_state(eng):
     m, v, t = eng.get_adam_state(_lib.CRITICS)
     return dict(grad=eng.debug_read("grad_critics"), dz2=eng.debug_read("c_dz2"), q=eng.debug_read("q"), y=eng.debug_read("targ_q"),
                 loss=np.float32(eng.read_metrics()["loss/qf_loss"]), params=eng.get_params(_lib.CRITICS), m=m, v=v, t=np.float32(t))
-
-
-def assert_same_bits(x, y, keys=None, what=""):
-    for k in keys or x:
-        assert same_bits(np.asarray(x[k]), np.asarray(y[k])), (what, k)
-
-
-def close_all(*engs):
-    for e in engs:
-        e.close()
 
 
 # ------------------------------------------------------------------------------------------ 1. staging equals the host route
@@ -144,7 +101,6 @@ def test_index_staging_leaves_what_the_host_route_leaves(case):
     H.rb_sample()
     assert_same_bits(slot(D), slot(H), what="native sample behind the stagings")
     del keep
-    close_all(D, H)
 
 
 # ------------------------------------------------------------------------------------------ 2. weights of 1 change nothing
@@ -163,7 +119,6 @@ def test_unit_weights_equal_the_plain_update(case):
         del keep
     assert D.graph_kernel_count(8) == H.graph_kernel_count(0) > 0 and H.graph_kernel_count(8) == 0 and D.graph_kernel_count(0) == 0
     assert_same_state(D, H)
-    close_all(D, H)
 
 
 # ------------------------------------------------------------------------------------------ 3. powers of two scale exactly
@@ -187,7 +142,6 @@ def test_power_of_two_weights_scale_gradients_and_loss_exactly(case):
         assert same_bits(g["dz2"], one["dz2"] * s), scale
         assert same_bits(np.asarray(g["loss"]), np.asarray(one["loss"] * s)), (scale, g["loss"], one["loss"])
         assert_same_bits(g, one, ("q", "y"), what=scale)
-    close_all(*engs)
 
 
 # ------------------------------------------------------------------------------------------ 4. a row of weight 0 is invisible
@@ -213,7 +167,6 @@ def test_a_row_of_weight_zero_is_invisible(case):
     assert_same_bits(x, y, ("grad", "loss", "params", "m", "v", "t"))
     assert not same_bits(x["y"], y["y"])                                      # the rows did differ
     assert D.priority_stats()["weight_stagings"] == 1
-    close_all(D, T)
 
 
 # ------------------------------------------------------------------------------------------ 5. against the oracle
@@ -276,7 +229,6 @@ def test_weighted_update_against_the_oracle(case):
     assert_params_close(eng.get_params(_lib.CRITICS), flat_critics(ref, ref.qnets), ref.hps.qnets_lr, 1, "critics after Adam",
                         layout=crit_layout(ref), record=f"weighted_update_against_oracle[{case}]")
     del keep
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 6. refusals
@@ -338,7 +290,6 @@ def test_bad_indices_and_bad_weights_are_neutralised_and_counted(case):
     D.update_qnets()
     assert np.isfinite(D.read_metrics()["loss/qf_loss"])
     del keep
-    close_all(D, T)
 
 
 def test_bad_arguments_are_refused_and_leave_the_engine_usable():
@@ -366,14 +317,12 @@ def test_bad_arguments_are_refused_and_leave_the_engine_usable():
     assert lib.sactd3_td_errors_device(h, C.c_void_p(host.ctypes.data), 1, B, None, 1) == E
     assert lib.sactd3_priority_stats(h, None) == E
     assert D.priority_stats() == dict(index_stagings=0, weight_stagings=0, td_readouts=0, rows_refused=0)
-    empty = P.Engine(D.cfg, [-1.0] * D.cfg.ac_dim, [1.0] * D.cfg.ac_dim)
+    empty = track(P.Engine(D.cfg, [-1.0] * D.cfg.ac_dim, [1.0] * D.cfg.ac_dim))
     with pytest.raises(P.EngineError, match="-3.*empty"):
         stage(empty, idx, w)
-    empty.close()
     stage(D, idx, w)                                                         # ... and the engine takes a good call
     D.update_qnets()
     assert np.isfinite(td_of(D)).all()
-    D.close()
 
 
 # ------------------------------------------------------------------------------------------ 7. TD errors
@@ -431,7 +380,6 @@ def test_td_errors_are_the_last_critic_updates(case):
     assert_same_state(D, T)
     assert D.priority_stats()["td_readouts"] >= 8 and T.priority_stats()["td_readouts"] == 0
     del keep
-    close_all(D, T)
 
 
 # ------------------------------------------------------------------------------------------ 8. lifetime of the weights
@@ -463,7 +411,6 @@ def test_weights_do_not_outlive_their_batch(refill):
     assert_same_bits(slot(D), slot(T), what=refill)
     assert D.graph_kernel_count(8) == 0 and D.graph_kernel_count(0) > 0      # the weighted graph was never needed
     del keep
-    close_all(D, T)
 
 
 def test_actor_update_is_never_weighted():
@@ -488,7 +435,6 @@ def test_actor_update_is_never_weighted():
     D.update_qnets()
     assert D.graph_kernel_count(8) == D.graph_kernel_count(0) > 0
     del keep
-    close_all(D, T)
 
 
 # ------------------------------------------------------------------------------------------ 9. the loop
@@ -515,7 +461,7 @@ def test_train_with_a_proportional_sampler_stays_on_the_device():
     with pytest.raises(ValueError, match="fused=False"):
         loop.train(cfg, env, agent, fused=True, device_env=True, sampler=sampler)
     metrics = loop.train(cfg, env, agent, fused=False, device_env=True, sampler=sampler)
-    eng = agent.engine
+    eng = track(agent.engine)
     assert all(np.isfinite(v) for v in metrics.values()), metrics
     assert len(seen) == agent.qnet_updates_so_far >= iters and sampler.len == eng.rb_len() == len(agent.rb)
     ps, bs, pd, ro = eng.priority_stats(), eng.boundary_stats(), eng.predict_device_stats(), eng.readout_stats()
@@ -537,4 +483,3 @@ def test_train_with_a_proportional_sampler_stays_on_the_device():
     assert once.sum() > B // 2 and same_bits(sampler.priorities[index].cpu().numpy()[once], want[once])
     pri = sampler.priorities[:sampler.len].cpu().numpy()
     assert (pri > 0).all() and np.isfinite(pri).all() and float(sampler.max_priority) >= pri.max() > 0
-    eng.close()

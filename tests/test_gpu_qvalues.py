@@ -2,60 +2,25 @@
 twin critics at the suite's Q-value tolerance; everything else is an equality: a row's values are the same bits whatever rows are
 scored with it, the policy form is its own composition, views change nothing, and training cannot tell whether a call was made.
 
-Engines are built like twins() of tests/test_gpu_predict_device.py (B = 64, a 2048-row ring, the oracle's perturbed parameters);
-the rows are synth_transitions(1041, seed 5).  Shapes: SAC Hopper (K = o + a = 14: fused first layer), TD3 HalfCheetah (K = 23), SAC
+Engines come from shape_engines() of tests/gpu_support.py (B = 64, a 2048-row ring, the oracle's perturbed parameters); the rows are
+its data(): synth_transitions(1041, seed 5).  Shapes: SAC Hopper (K = o + a = 14: fused first layer), TD3 HalfCheetah (K = 23), SAC
 Humanoid (K = 393: k_nt_wide + the unfused layer 2), SAC Hopper without LayerNorm, and K = 64 / 65, the two sides of the fused first
 layer's limit.  Row counts 1, 5, 16, 17, 67: one row, a partial tile, a whole one, a whole one and a row, several blocks; 1041 crosses
 the 1024-row chunk and ends in a partial tile."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 import torch
 
-from oracle.sac_td3_ref import Hps, RefAgent
-from tests.helpers import DIMS, observe, randomize_ln, synth_transitions
-from tests.test_gpu_device_boundary import assert_same_state
-from tests.test_gpu_engine import close, push_params
+from oracle.sac_td3_ref import RefAgent
+from tests.gpu_support import (DEV, MAXN, NROWS, SENTINEL, P, _lib, assert_same_state, close, close_engines, data, same_bits, score,  # noqa: F401
+                               shape_engines, stream)
+from tests.helpers import observe, synth_transitions
 
 pytestmark = pytest.mark.gpu
 
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib  # noqa: E402
-
-DEV = "cuda:0"
-MAXN = 96
-NROWS = 1041
 ROWS = (1, 5, 16, 17, 67)
-SENTINEL = -12345.678
-# name -> (algo, (o, a, bound), layer_norm)
-SHAPES = {"sac-hopper": ("sac", DIMS["hopper"], True), "td3-halfcheetah": ("td3", DIMS["halfcheetah"], True),
-          "sac-humanoid": ("sac", DIMS["humanoid"], True), "sac-hopper-noln": ("sac", DIMS["hopper"], False),
-          "sac-k64": ("sac", (47, 17, 0.7), True), "sac-k65": ("sac", (48, 17, 0.7), True), "td3-td3_2": ("td3", DIMS["td3_2"], True)}
-
-
-def build(shape, count=1, B=64, seed=3, cap=2048):
-    """the oracle and `count` engines with its (perturbed, so that every parameter matters) parameters"""
-    algo, (o, a, bound), ln = SHAPES[shape]
-    hps = (Hps.td3 if algo == "td3" else Hps.sac)(layer_norm=ln, batch_size=B)
-    torch.manual_seed(seed)
-    ref = RefAgent(o, a, [-bound] * a, [bound] * a, hps)
-    randomize_ln(ref)
-    engs = []
-    for _ in range(count):
-        eng = P.Engine(P.Config.from_hps(hps, o, a, rb_capacity=cap, max_envs=MAXN, seed=seed), [-bound] * a, [bound] * a)
-        push_params(eng, ref)
-        engs.append(eng)
-    return ref, engs, (o, a, bound)
-
-
-@functools.lru_cache(maxsize=None)
-def data(shape):
-    """(obs, act) [1041, .] on the host: computed once per shape, never written"""
-    _, (o, a, bound), _ = SHAPES[shape]
-    obs, act = synth_transitions(NROWS, o, a, bound, seed=5)[:2]
-    return obs, act
 
 
 def oracle_q(ref, obs, act, target):
@@ -66,34 +31,13 @@ def oracle_q(ref, obs, act, target):
         return RefAgent._twin(ref.qnets_target if target else ref.qnets, obs, act).squeeze(-1).numpy()
 
 
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def score(eng, obs, act=None, target=False):
-    """q_values_device on CUDA tensors -> [2, n] on the host (read on the current stream, which the call made wait)"""
-    n = obs.shape[0]
-    out = torch.empty(2, n, device=DEV)
-    eng.q_values_device(obs.data_ptr(), max(obs.stride(0), obs.shape[1]), 0 if act is None else act.data_ptr(),
-                        eng.cfg.ac_dim if act is None else max(act.stride(0), act.shape[1]), n, target, out.data_ptr(), 1, n, stream())
-    return out.cpu().numpy()
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
-def same_bits(x, y):
-    return x.shape == y.shape and np.array_equal(bits(x), bits(y))
-
-
 # ------------------------------------------------------------------------------------------ 1. against the oracle
 @pytest.mark.parametrize("shape", ["sac-hopper", "td3-halfcheetah", "sac-humanoid", "sac-hopper-noln", "sac-k64", "sac-k65"])
 def test_scores_match_the_oracles_twin_critics(shape):
     """RefAgent._twin on the same rows, online and target, explicit actions and pi(s) = ref.predict(explore=False): rtol 1e-5 +
     atol 1e-5, what the suite applies to debug_read("q") / "q_target" / "q_pi" at these shapes and this data distribution (the float32
     oracle sits within 7 % of that of its float64 self on exactly these inputs: 1.0e-6 at |Q| <= 3.3)."""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     obs, act = data(shape)
     obs_d, act_d = obs.to(DEV), act.to(DEV)
     for target in (False, True):
@@ -108,7 +52,6 @@ def test_scores_match_the_oracles_twin_critics(shape):
                 print(shape, "target" if target else "online", "policy" if policy else "explicit", n, "max |dq|", float(np.abs(got - w).max()))
                 close(got, w, rtol=1e-5, atol=1e-5, name=f"{shape} target={target} policy={policy} n={n}")
     assert eng.qvalues_stats() == dict(calls=20, rows=4 * sum(ROWS), ordered_calls=20, policy_calls=10)
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. a row's bits do not depend on its company
@@ -116,7 +59,7 @@ def test_scores_match_the_oracles_twin_critics(shape):
 def test_a_rows_values_do_not_depend_on_the_rows_scored_with_it(shape):
     """row i alone, inside 67 rows and inside 1041 rows (two chunks: 1024 rows in the launch shape of many tiles, then 17): the same
     bits, explicit and policy actions, online and target"""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     obs, act = [t.to(DEV) for t in data(shape)]
     for policy in (False, True):
         for target in (False, True):
@@ -129,13 +72,12 @@ def test_a_rows_values_do_not_depend_on_the_rows_scored_with_it(shape):
                 assert same_bits(one, full[:, i:i + 1]), (policy, target, i)
             tail = score(eng, obs[1000:], None if policy else act[1000:], target)      # 41 rows, another position in the chunk
             assert same_bits(tail, full[:, 1000:]), (policy, target)
-    eng.close()
 
 
 def test_a_call_of_batch_size_rows_takes_no_large_batch_form():
     """Humanoid, B = 1024: the trunk's 64 x 64 / 32 x 32 forms belong to M == B >= 1024 -- 1024 scored rows must not take them:
     the same bits as the same rows scored 16 at a time, explicit and policy actions"""
-    ref, (eng,), (o, a, bound) = build("sac-humanoid", B=1024)
+    ref, (eng,), (o, a, bound) = shape_engines("sac-humanoid", B=1024)
     obs, act = [t.to(DEV)[:1024] for t in data("sac-humanoid")]
     for policy in (False, True):
         full = score(eng, obs, None if policy else act)
@@ -143,20 +85,18 @@ def test_a_call_of_batch_size_rows_takes_no_large_batch_form():
         assert same_bits(full, np.concatenate(parts, axis=1)), policy
     want = oracle_q(ref, data("sac-humanoid")[0][:1024], data("sac-humanoid")[1][:1024], False)
     close(score(eng, obs, act), want, rtol=1e-5, atol=1e-5, name="humanoid B=1024")
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 3. the policy form is its composition
 @pytest.mark.parametrize("shape", ["sac-hopper", "td3-halfcheetah", "sac-humanoid"])
 def test_policy_form_equals_scoring_the_exploit_action(shape):
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     obs = data(shape)[0].to(DEV)
     for n in (1, 5, 17, 67, MAXN):
         pi = torch.empty(n, a, device=DEV)
         eng.predict_device(obs[:n].data_ptr(), o, n, False, pi.data_ptr(), a, stream())
         for target in (False, True):
             assert same_bits(score(eng, obs[:n], None, target), score(eng, obs[:n], pi, target)), (n, target)
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 4. views, and the host call
@@ -165,7 +105,7 @@ def test_views_in_and_out_and_the_host_call(shape):
     """obs = big[:, 1:1+o], actions = wide[:, 3:3+a] (rows 4-byte aligned only, strides above the widths), out = a [2, n + 2, 1] view
     at an odd offset of a sentinel-filled tensor: the bits of the contiguous call, nothing outside [2, n] touched, sources unchanged;
     Engine.q_values and Agent.q_values on host arrays give the same bits as numpy"""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     ag = P.Agent.__new__(P.Agent)                                    # the mirror's method on an engine of this test
     ag.engine = eng
     obs_h, act_h = data(shape)
@@ -205,7 +145,6 @@ def test_views_in_and_out_and_the_host_call(shape):
         ag.q_values({"observations": obs_h[:4].to(DEV), "actions": act_h[:4].numpy()})
     # more rows than a chunk through the host call: the bits of the device call
     assert same_bits(eng.q_values(obs_h.numpy(), act_h.numpy()), score(eng, obs_h.to(DEV), act_h.to(DEV)))
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 5. invisible to training
@@ -215,7 +154,7 @@ def test_scoring_between_chained_periods_changes_nothing(shape):
     periods -- the second starts from the opening pair the first precomputed, if the chain holds: same parameters, Adam state, metrics,
     sampled indices and graphs; the counters count what was called.  Then a score inside predict_begin / predict_end: the action and
     the exploration draw of the twin that did not score."""
-    _, (R, N), (o, a, bound) = build(shape, count=2, cap=1000)
+    _, (R, N), (o, a, bound) = shape_engines(shape, count=2, cap=1000)
     obs, act = [t[:67].to(DEV) for t in data(shape)]
     res = []
     for eng, scores in ((R, True), (N, False)):
@@ -255,7 +194,6 @@ def test_scoring_between_chained_periods_changes_nothing(shape):
         assert np.array_equal(R.read_noise(_lib.SITE_PREDICT, n), N.read_noise(_lib.SITE_PREDICT, n))
     ra, na = R.acting_stats(), N.acting_stats()                       # (how a call's wait ended is timing, not schedule)
     assert all(ra[k] == na[k] for k in ("begun", "begin_waited_for_learner", "learner_waited_for_acting")) and ra["begun"] == 2
-    R.close(); N.close()
 
 
 # ------------------------------------------------------------------------------------------ 6. follows the parameters
@@ -263,7 +201,7 @@ def test_scoring_between_chained_periods_changes_nothing(shape):
 def test_scores_follow_the_parameters(shape):
     """one critic update + Polyak step with an injected draw, on the engine and on the oracle: the online and the target scores of
     fixed rows both change, and meet the oracle's new ones at the tolerance of test 1"""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     obs_h, act_h = [t[:67] for t in data(shape)]
     obs, act = obs_h.to(DEV), act_h.to(DEV)
     before = [score(eng, obs, act), score(eng, obs, act, True), score(eng, obs)]
@@ -283,25 +221,23 @@ def test_scores_follow_the_parameters(shape):
         observe(f"qvalues_follow_the_parameters[{shape}]", f"{name}: max |dq| / (1e-5 + 1e-5 |q|)", float((np.abs(x - w) / (1e-5 + 1e-5 * np.abs(w))).max()))
         print(shape, name, "max |dq|", float(np.abs(x - w).max()), "moved by", float(np.abs(x - b).max()))
         close(x, w, rtol=1e-5, atol=1e-5, name=f"{shape} {name} after the update")
-    eng.close()
 
 
 @pytest.mark.parametrize("shape", ["sac-hopper", "td3-halfcheetah", "sac-humanoid"])
 def test_a_scored_row_has_the_bits_the_critic_update_computes(shape):
     """the batch's (s, a) rows scored with the online critics, then update_qnets on that batch: debug_read("q") -- the Q-values the
     update computed from the same parameters, in the B < 1024 kernels' K split -- holds the same bits"""
-    ref, (eng,), (o, a, bound) = build(shape)
+    ref, (eng,), (o, a, bound) = shape_engines(shape)
     batch = synth_transitions(64, o, a, bound, seed=11)
     eng.load_batch(*[t.numpy() for t in batch])
     got = score(eng, batch[0].to(DEV), batch[1].to(DEV))
     eng.update_qnets()
     assert same_bits(got, eng.debug_read("q").reshape(2, 64))
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 7. refusals
 def test_refusals_launch_nothing_and_leave_the_engine_usable():
-    ref, (eng,), (o, a, bound) = build("sac-hopper")
+    ref, (eng,), (o, a, bound) = shape_engines("sac-hopper")
     lib, h, ORD, vp = eng.lib, eng._h, _lib.SRC_ORDERED, C.c_void_p
     obs, act = [t[:8].to(DEV) for t in data("sac-hopper")]
     out = torch.full((2, 8), SENTINEL, device=DEV)
@@ -343,4 +279,3 @@ def test_refusals_launch_nothing_and_leave_the_engine_usable():
     assert call(po, o, pa, a, 8, 0, pq, 1, 8, None, ORD) == 0                                # ... and the engine is as usable as before
     eng.sync()
     assert same_bits(out.cpu().numpy(), good)
-    eng.close()

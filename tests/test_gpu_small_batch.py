@@ -1,6 +1,7 @@
 """The small-batch kernel forms (B < 1024) at their switch points, checked stage by stage in float64 from the engine's own inputs --
-the path every published number takes (B = 256), with the checker and the a-priori bounds of tests/test_gpu_large_batch.py and
-tests/bounds.py (checked on the CPU by tests/test_stage_bounds.py at these batch sizes and in these kernels' summation orders).
+the path every published number takes (B = 256), with the checker of tests/test_gpu_large_batch.py (tests/gpu_stage_checks.py) and the
+a-priori bounds of tests/bounds.py (checked on the CPU by tests/test_stage_bounds.py at these batch sizes and in these kernels'
+summation orders).
 
 Below B = 1024 csrc/engine.hip runs a trunk as the fused k_nt<pro,true,KS,c1,nt> (inputs of at most 64 columns: the first layer is
 recomputed per output tile) or as k_nt_wide + k_nt<pro,false,KS,0,nt>, and every weight gradient, with the optimiser step and the
@@ -41,9 +42,9 @@ import re
 import pytest
 import torch
 
+from tests.gpu_stage_checks import run_fused_critic_iteration, run_one_iteration
+from tests.gpu_support import close_engines, make_pair  # noqa: F401
 from tests.helpers import DIMS
-from tests.test_gpu_engine import make_pair
-from tests.test_gpu_large_batch import run_fused_critic_iteration, run_one_iteration
 
 pytestmark = pytest.mark.gpu
 

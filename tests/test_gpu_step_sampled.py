@@ -2,10 +2,10 @@
 the call sequence it replaces, for equal bits throughout -- that sequence is pinned against the numpy restatements and the oracle by
 tests/test_gpu_native_priorities.py and tests/test_gpu_nstep.py.
 
-Engines are the twin small ones of tests/test_gpu_native_priorities.py (the oracle's perturbed parameters, the critic site's noise
-injected): a 5000-slot ring that holds 2500 rows, or a 2504-slot one that the appends of the test wrap.  The chained cases hold the
-trajectories of tests/test_gpu_nstep.py (4 envs, so stride 4) -- on independent rows every chain would be cut at its first link."""
-import ctypes as C
+Engines are the twin small ones of tests/test_gpu_native_priorities.py (tests/gpu_support.py: PRIO_CASES, shape_engines; the oracle's
+perturbed parameters, the critic site's noise injected): a 5000-slot ring that holds 2500 rows, or a 2504-slot one that the appends of
+the test wrap.  The chained cases hold gpu_support.trajectories, the rows of tests/test_gpu_nstep.py (4 envs, so stride 4) -- on
+independent rows every chain would be cut at its first link."""
 import functools
 from types import SimpleNamespace
 
@@ -15,21 +15,12 @@ import torch
 
 from oracle.sac_td3_ref import Hps
 from tests import priorities_ref as pref
-from tests.test_gpu_device_boundary import assert_same_state
-from tests.test_gpu_engine import push_params
-from tests.test_gpu_native_priorities import CAP, CASES, HELD, SEED, boundary_uniforms, integer_priorities, ring_rows, write
-from tests.test_gpu_nstep import info, trajectories
-from tests.test_gpu_prioritized import assert_same_bits, close_all, td_of
-from tests.test_gpu_qvalues import SHAPES, build as q_build, same_bits
+from tests.gpu_support import (CAP, DEV, HELD, NSTEP_STRIDE as STRIDE, PRIO_CASES as CASES, SEED, SHAPES, P, _lib, assert_same_bits,  # noqa: F401
+                               assert_same_state, boundary_uniforms, call_sequence, close_engines, engine_state, info, integer_priorities,
+                               iteration_state, loop, raw_step, ring_rows, same_bits, sampled_draw, shape_engines, td_of, track, trajectories,
+                               upload_priorities)
 
 pytestmark = pytest.mark.gpu
-
-P = pytest.importorskip("sac_td3_cudagraphs_pytorch_amd")
-from sac_td3_cudagraphs_pytorch_amd import _lib, loop  # noqa: E402
-
-DEV = "cuda:0"
-STRIDE = 4
-SETS = (_lib.ACTOR, _lib.CRITICS, _lib.ACTOR_TARGET, _lib.CRITICS_TARGET, _lib.LOG_ALPHA)
 
 
 @functools.lru_cache(maxsize=None)
@@ -52,7 +43,7 @@ def fresh_rows(shape, chained, i):
 
 def twins(case, count, chained=False, cap=CAP, enable=(0.6, 1e-6), held=True):
     shape, B = CASES[case]
-    _, engs, (o, a, bound) = q_build(shape, count, B=B, cap=cap)
+    _, engs, (o, a, bound) = shape_engines(shape, count, B=B, cap=cap)
     eps = torch.randn(B, a, generator=torch.Generator().manual_seed(4))
     for eng in engs:
         if held:
@@ -63,54 +54,8 @@ def twins(case, count, chained=False, cap=CAP, enable=(0.6, 1e-6), held=True):
     return engs, shape, B
 
 
-def call_sequence(eng, do_actor, beta, n_step, stride, updates):
-    """the iteration call by call: what sactd3_step_sampled has to equal"""
-    if beta is None:
-        eng.rb_sample_nstep(n_step, stride)
-    elif n_step == 1:
-        eng.rb_sample_prioritized(beta)
-    else:
-        eng.rb_sample_prioritized_nstep(beta, n_step, stride)
-    eng.update_qnets()
-    if beta is not None:
-        eng.prio_update_from_td()
-    if do_actor:
-        for _ in range(eng.cfg.actor_update_delay):
-            eng.update_actor()
-    eng.update_targ_nets(updates)
-
-
-def iteration_state(eng, prio):
-    d = dict(eng.read_batch())
-    d["td"] = td_of(eng)
-    d["metrics"] = np.float32(list(eng.read_metrics().values()))
-    if prio:
-        for k in ("prio_weights", "prio_leaf", "prio_sums", "prio_max"):
-            d[k] = eng.debug_read(k)
-    return d
-
-
-def assert_same_iteration(A, B, prio, what):
-    x, y = iteration_state(A, prio), iteration_state(B, prio)
-    for k in x:
-        assert same_bits(np.asarray(x[k], np.float32), np.asarray(y[k], np.float32)) if x[k].dtype.kind == "f" else np.array_equal(x[k], y[k]), (what, k)
-
-
 def betas(n):
     return [float(b) for b in np.linspace(0.4, 1.0, n)]
-
-
-def raw_step(eng, do_actor, draw, n_step, stride, beta):
-    sm = _lib.CSampling(draw, n_step, stride, beta)
-    return eng.lib.sactd3_step_sampled(eng._h, do_actor, C.byref(sm))
-
-
-def snapshot(eng, prio=True):
-    d = {f"params{w}": eng.get_params(w) for w in SETS}
-    if prio:
-        d["leaf"], d["sums"], d["max"] = eng.debug_read("prio_leaf"), eng.debug_read("prio_sums"), eng.debug_read("prio_max")
-        d["stats"] = np.float32(list(eng.prio_stats().values()))
-    return d
 
 
 # ------------------------------------------------------------------------------------------ 1. one launch equals the call sequence
@@ -130,9 +75,9 @@ def test_one_launch_equals_the_call_sequence(case, prio, n_step, cap):
     for i, beta in enumerate(betas(7)):
         for eng in (A, Bt):
             eng.rb_extend(*fresh_rows(shape, chained, i))
-        call_sequence(A, i % 3 == 0, beta if prio else None, n_step, STRIDE, i + 1)
+        call_sequence(A, i % 3 == 0, sampled_draw(beta if prio else None, n_step, STRIDE), i + 1, write_back=prio)
         Bt.step_sampled(i % 3 == 0, beta=beta if prio else None, n_step=n_step, stride=STRIDE)
-        assert_same_iteration(A, Bt, prio, f"iteration {i}")
+        assert_same_bits(iteration_state(A, prio), iteration_state(Bt, prio), what=f"iteration {i}")
         if chained:
             (ka, la), (kb, lb) = info(A), info(Bt)
             assert np.array_equal(ka, kb) and np.array_equal(la, lb), f"chains of iteration {i}"
@@ -153,17 +98,12 @@ def test_one_launch_equals_the_call_sequence(case, prio, n_step, cap):
         eng.rb_sample()
     assert_same_bits(A.read_batch(), Bt.read_batch(), what="a further uniform sample")
     assert Bt.step_sampled_stats()["launches"] == 7
-    close_all(A, Bt)
 
 
 def test_eager_form_equals_the_graph():
     """use_graphs = 0: the same launches issued one by one"""
     shape, B = CASES["sac-hopper-64"]
-    _, (o, a, bound), ln = SHAPES[shape]
-    ref, (G,), _ = q_build(shape, 1, B=B, cap=CAP)
-    E = P.Engine(P.Config.from_hps(Hps.sac(layer_norm=ln, batch_size=B), o, a, rb_capacity=CAP, max_envs=96, seed=SEED, use_graphs=False),
-                 [-bound] * a, [bound] * a)
-    push_params(E, ref)
+    _, (G, E), (o, a, bound) = shape_engines(shape, B=B, cap=CAP, use_graphs=(True, False))
     eps = torch.randn(B, a, generator=torch.Generator().manual_seed(4))
     for eng in (G, E):
         eng.rb_extend(*held_rows(shape, True))
@@ -172,10 +112,9 @@ def test_eager_form_equals_the_graph():
     for i, beta in enumerate(betas(4)):
         for eng in (G, E):
             eng.step_sampled(i % 3 == 0, beta=beta, n_step=3, stride=STRIDE)
-        assert_same_iteration(G, E, True, f"iteration {i}")
+        assert_same_bits(iteration_state(G, True), iteration_state(E, True), what=f"iteration {i}")
     assert_same_state(G, E)
     assert E.step_sampled_stats() == dict(launches=4, graph_captures=0) and G.step_sampled_stats()["graph_captures"] == 2
-    close_all(G, E)
 
 
 # ------------------------------------------------------------------------------------------ 2. replayed, not re-captured
@@ -193,7 +132,7 @@ def test_graphs_are_replayed_while_beta_moves_and_the_ring_grows():
     assert length == HELD + 48
     prio = np.ones(length, np.float32)
     prio[:HELD] = integer_priorities()
-    keep = write(eng, np.arange(length), prio)
+    keep = upload_priorities(eng, np.arange(length), prio)
     leaf = eng.debug_read("prio_leaf")
     assert np.array_equal(leaf[:length], prio) and float(leaf.sum()) < 4096
     u = boundary_uniforms(B)
@@ -202,7 +141,7 @@ def test_graphs_are_replayed_while_beta_moves_and_the_ring_grows():
     got, want = eng.read_batch()["index"], pref.select(leaf, length, u)
     assert np.array_equal(got, want), np.flatnonzero(got != want)
     eng.prio_set_uniforms(None)
-    keep2 = write(eng, np.arange(length), prio)                     # (the write-back moved the drawn rows' leaves)
+    keep2 = upload_priorities(eng, np.arange(length), prio)                     # (the write-back moved the drawn rows' leaves)
     eng.step_sampled(False, beta=0.4)                               # native again: draw 12 of the Philox stream
     want = pref.select(leaf, length, pref.native_uniforms(SEED, 12, B))
     assert np.array_equal(eng.read_batch()["index"], want)
@@ -211,14 +150,13 @@ def test_graphs_are_replayed_while_beta_moves_and_the_ring_grows():
     assert eng.step_sampled_stats() == dict(launches=15, graph_captures=3)
     assert eng.graph_kernel_count(16 + 3) == 0 and eng.graph_kernel_count(16 + 1) > 0
     del keep, keep2
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------ 3. refusals
 def test_refusals_change_nothing_and_leave_the_engine_usable():
     (eng, N), shape, B = twins("sac-hopper-64", 2, chained=True)
     (empty,), _, _ = twins("sac-hopper-64", 1, held=False)
-    before = snapshot(eng)
+    before = engine_state(eng, "prio")
     U, PR, E, S = _lib.DRAW_UNIFORM, _lib.DRAW_PRIORITIZED, _lib.EINVAL, _lib.ESTATE
     assert eng.lib.sactd3_step_sampled(eng._h, 1, None) == E
     assert eng.lib.sactd3_step_sampled(None, 1, None) == E and eng.lib.sactd3_step_sampled_stats(None, None) == E
@@ -230,11 +168,10 @@ def test_refusals_change_nothing_and_leave_the_engine_usable():
     N2 = twins("sac-hopper-64", 1, chained=True, enable=None)[0][0]
     assert raw_step(N2, 1, PR, 1, 1, 0.4) == S                     # priorities not enabled
     assert raw_step(empty, 1, PR, 1, 1, 0.4) == S and raw_step(empty, 0, U, 3, 4, 0.0) == S      # empty ring
-    after = snapshot(eng)
-    assert_same_bits(before, after, what="refused calls")
+    assert_same_state(before, engine_state(eng, "prio"), what="refused calls")
     assert eng.step_sampled_stats() == dict(launches=0, graph_captures=0)
     # nothing to draw from: zero-weight rows, refused counts, unchanged parameters (a fresh Adam state: a zero gradient moves nothing)
-    keep = write(N, np.arange(HELD), np.zeros(HELD, np.float32))
+    keep = upload_priorities(N, np.arange(HELD), np.zeros(HELD, np.float32))
     pa, pc = N.get_params(_lib.ACTOR), N.get_params(_lib.CRITICS)
     N.step_sampled(False, beta=0.4, n_step=3, stride=STRIDE)
     assert not N.debug_read("prio_weights").any() and (N.read_batch()["index"] == -1).all()
@@ -243,24 +180,23 @@ def test_refusals_change_nothing_and_leave_the_engine_usable():
     # ... and the refused engine runs a normal iteration
     eng.step_sampled(True, beta=0.4, n_step=3, stride=STRIDE)
     assert eng.step_sampled_stats() == dict(launches=1, graph_captures=1)
-    assert not same_bits(eng.get_params(_lib.CRITICS), before[f"params{_lib.CRITICS}"])
+    assert not same_bits(eng.get_params(_lib.CRITICS), before["params.critics"])
     assert eng.prio_stats() == dict(samples=1, write_backs=1, rows_refused=0, rows_entered_at_max=HELD)
     del keep
-    close_all(eng, N, N2, empty)
 
 
 # ------------------------------------------------------------------------------------------ 4. nothing else moved
 def test_the_other_entry_points_agree_behind_it():
     (A, Bt), shape, B = twins("sac-hopper-64", 2, chained=True)
     for i, beta in enumerate(betas(4)):
-        call_sequence(A, i % 3 == 0, beta, 3, STRIDE, i + 1)
+        call_sequence(A, i % 3 == 0, sampled_draw(beta, 3, STRIDE), i + 1, write_back=True)
         Bt.step_sampled(i % 3 == 0, beta=beta, n_step=3, stride=STRIDE)
     # the slot behind the one-launch iteration serves the read-outs and the caller's write-back
     assert same_bits(td_of(A), td_of(Bt))
     (ka, la), (kb, lb) = info(A), info(Bt)
     assert np.array_equal(ka, kb) and np.array_equal(la, lb) and (kb >= 1).all()
     idx = Bt.read_batch()["index"]
-    keep = [write(e, idx, np.linspace(0.5, 2.0, B)) for e in (A, Bt)]
+    keep = [upload_priorities(e, idx, np.linspace(0.5, 2.0, B)) for e in (A, Bt)]
     assert same_bits(A.debug_read("prio_leaf"), Bt.debug_read("prio_leaf")) and same_bits(A.debug_read("prio_sums"), Bt.debug_read("prio_sums"))
     for eng in (A, Bt):
         for i in range(3):
@@ -269,7 +205,6 @@ def test_the_other_entry_points_agree_behind_it():
     assert_same_state(A, Bt)
     assert_same_bits(A.read_batch(), Bt.read_batch(), what="the slot behind step and step_period")
     del keep
-    close_all(A, Bt)
 
 
 # ------------------------------------------------------------------------------------------ 5. acting overlap
@@ -287,7 +222,6 @@ def test_acting_overlaps_with_the_one_launch_iteration():
         assert same_bits(want, got), f"actions of iteration {i}"
     assert_same_state(S, O)
     assert O.acting_stats()["learner_waited_for_acting"] + O.acting_stats()["begin_waited_for_learner"] > 0
-    close_all(S, O)
 
 
 # ------------------------------------------------------------------------------------------ 6. the loop
@@ -304,11 +238,12 @@ def test_train_one_launch_equals_the_call_by_call_loop():
         agent = P.Agent({"ob_shape": (n, o), "ac_shape": (n, a)}, np.full(a, -1.0, np.float32), np.full(a, 1.0, np.float32),
                         torch.device(DEV), cfg, P.ReplayBuffer(cfg.rb_capacity))
         loop.train(cfg, env, agent, fused=False, prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6), n_step=3, one_launch=one_launch)
-        eng = agent.engine
-        res.append(dict(snapshot(eng), nstep=np.float32(list(eng.nstep_stats().values())),
-                        counters=np.float32([agent.qnet_updates_so_far, agent.actor_updates_so_far, agent.timesteps_so_far, len(agent.rb)])))
+        eng = track(agent.engine)
+        res.append(engine_state(eng, "prio", extra=dict(
+            nstep=np.float32(list(eng.nstep_stats().values())),
+            counters=np.float32([agent.qnet_updates_so_far, agent.actor_updates_so_far, agent.timesteps_so_far, len(agent.rb)]))))
         launches = eng.step_sampled_stats()
         assert launches["launches"] == (agent.qnet_updates_so_far if one_launch else 0) and launches["graph_captures"] <= 2
         assert agent.qnet_updates_so_far >= iters
         eng.close()
-    assert_same_bits(res[0], res[1], what="one_launch against the call sequence")
+    assert_same_state(res[0], res[1], what="one_launch against the call sequence")

@@ -30,28 +30,12 @@ import pytest
 import torch
 
 from tests import tail_checks as tc
-from tests.test_gpu_engine import P, _lib, schema
+from tests.gpu_support import _lib, close_engines, make_engine, schema  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 H = 256
 IDS = [f"{al}-{env}-{B}-{'ln' if ln else 'noln'}" for al, env, B, ln in tc.CASE_TABLE]
-
-
-def make_engine(c, log_alpha=None, bcq=None, rb_capacity=None, bc_alpha=0.0):
-    sac = c["sac"]
-    cfg = P.Config(ob_dim=c["o"], ac_dim=c["a"], batch_size=c["B"], rb_capacity=rb_capacity or max(4096, c["B"]), max_envs=8,
-                   prefer_td3_over_sac=not sac, layer_norm=c["ln"], bcq_style_targ_mix=(not sac) if bcq is None else bcq,
-                   qnets_lr=1e-3 if sac else 3e-4, bc_alpha=bc_alpha, seed=0)
-    eng = P.Engine(cfg, c["lo"], c["hi"])
-    flat = lambda p, i, n: schema.dict_to_flat(p, i, n, c["ln"])
-    eng.set_params(_lib.ACTOR, flat(c["actor"], c["o"], c["nh"]))
-    eng.set_params(_lib.ACTOR_TARGET, flat(c["actor_t"], c["o"], c["nh"]))
-    eng.set_params(_lib.CRITICS, np.concatenate([flat(p, c["o"] + c["a"], 1) for p in c["critics"]]))
-    eng.set_params(_lib.CRITICS_TARGET, np.concatenate([flat(p, c["o"] + c["a"], 1) for p in c["critics_t"]]))
-    if sac and log_alpha is not None:
-        eng.set_params(_lib.LOG_ALPHA, np.array([log_alpha], np.float32))
-    return eng
 
 
 def expected_kernels(c):

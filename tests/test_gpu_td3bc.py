@@ -8,11 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-from oracle.sac_td3_ref import Hps, RefAgent
+from oracle.sac_td3_ref import Hps
 from tests import bounds as bd
 from tests import td3bc_ref as R
-from tests.helpers import DIMS, assert_params_close, observe, randomize_ln, synth_transitions
-from tests.test_gpu_engine import P, _lib, actor_layout, flat_actor, flat_critics, gclose, push_params, schema
+from tests.gpu_support import (P, _lib, actor_layout, assert_same_state, build_engines, close_engines, engine_state, flat_actor,  # noqa: F401
+                               flat_critics, gclose, push_params, schema, track)
+from tests.helpers import DIMS, assert_params_close, observe, synth_transitions
 
 pytestmark = pytest.mark.gpu
 
@@ -22,16 +23,9 @@ SHAPES = dict(DIMS, o10a8=(10, 8, 1.0))      # tests/helpers.DIMS has no 8-actio
 
 def make_bc_pair(shape, B, ln=True, seed=0, use_graphs=True, bc_alpha=2.5, rb_capacity=4096, max_envs=8, randomize=True, **hp):
     """the oracle's TD3 agent (its modules carry the parameters) and an engine with the same parameters; bc_alpha = 0: plain TD3"""
-    o, a, bound = SHAPES[shape]
-    hps = Hps.td3(layer_norm=ln, batch_size=B, **hp)
-    torch.manual_seed(seed)
-    ref = RefAgent(o, a, [-bound] * a, [bound] * a, hps)
-    if randomize:
-        randomize_ln(ref)
-    cfg = P.Config.from_hps(hps, o, a, rb_capacity=rb_capacity, max_envs=max_envs, seed=seed, use_graphs=use_graphs, bc_alpha=bc_alpha)
-    eng = P.Engine(cfg, [-bound] * a, [bound] * a)
-    push_params(eng, ref)
-    return ref, eng, (o, a, bound)
+    ref, (eng,), dims = build_engines("td3", SHAPES[shape], B, ln=ln, seed=seed, cap=rb_capacity, max_envs=max_envs, use_graphs=use_graphs,
+                                      randomize=randomize, bc_alpha=bc_alpha, **hp)
+    return ref, eng, dims
 
 
 # ------------------------------------------------------------------------------------------ 1. stages against float64
@@ -152,13 +146,6 @@ def test_stages_against_float64(shape, B, ln, clip, w):
 
 # ------------------------------------------------------------------------------------------ 2. one computation, every route
 
-def snapshot(eng):
-    return (eng.get_params(_lib.ACTOR), eng.get_params(_lib.CRITICS), eng.get_params(_lib.ACTOR_TARGET), eng.get_params(_lib.CRITICS_TARGET),
-            *eng.get_adam_state(_lib.ACTOR)[:2], *eng.get_adam_state(_lib.CRITICS)[:2],
-            np.array([eng.get_adam_state(_lib.ACTOR)[2], eng.get_adam_state(_lib.CRITICS)[2]]), np.array(list(eng.read_metrics().values())),
-            eng.read_batch()["index"])
-
-
 def issue(eng, route, i0, n, agent=None):
     """iterations i0 .. i0 + n - 1 (actor updates at the multiples of 3) through one route"""
     if route == "periods":
@@ -193,7 +180,7 @@ def test_every_route_computes_the_same_bits(shape, B):
             agent = Agent({"ob_shape": (o,), "ac_shape": (a,)}, np.full(a, -bound, np.float32), np.full(a, bound, np.float32),
                           torch.device("cuda", 0), hps, ReplayBuffer(4096), seed=4)
             ref, _, _ = make_bc_pair(shape, B, seed=4)
-            eng = agent.engine
+            eng = track(agent.engine)
             push_params(eng, ref)
             assert eng.cfg.bc_alpha == 2.5
         else:
@@ -201,11 +188,12 @@ def test_every_route_computes_the_same_bits(shape, B):
             _, eng, _ = make_bc_pair(shape, B, seed=4, use_graphs=route != "eager")
         eng.rb_extend(*rows)
         assert issue(eng, route, 0, 6, agent) == 6
-        res[route], engines[route] = snapshot(eng), (eng, agent)
+        res[route], engines[route] = engine_state(eng, "index"), (eng, agent)
     for route in ("agent", "periods", "eager"):
-        for k, (x, y) in enumerate(zip(res["calls"], res[route])):
-            assert np.array_equal(x, y), (route, k)
-    assert res["calls"][8].tolist() == [4, 6] and np.isfinite(res["calls"][9]).all() and res["calls"][9][4] > 0 and res["calls"][9][5] > 0
+        assert_same_state(res["calls"], res[route], what=route)
+    met = {k[len("metrics."):]: float(v[0]) for k, v in res["calls"].items() if k.startswith("metrics.")}
+    assert [int(res["calls"][f"adam_t.{k}"][0]) for k in ("actor", "critics")] == [4, 6] and np.isfinite(list(met.values())).all()
+    assert met["loss/bc_loss"] > 0 and met["vitals/bc_lambda"] > 0
     assert engines["agent"][1].qnet_updates_so_far == 6 and engines["agent"][1].actor_updates_so_far == 4
     st0 = engines["periods"][0].step_periods_stats()
     pipelined = B < 1024      # (where the period graph has its pipelined form two periods go out as one run graph; elsewhere one by one)
@@ -218,11 +206,10 @@ def test_every_route_computes_the_same_bits(shape, B):
         eng.set_bc(1.5, 0.25)                             # ... new values between two periods ...
         issue(eng, route, 9, 9, agent)                    # ... a two-period run and a period on the chained opening pair
         assert eng.bc() == (1.5, 0.25)
-        after[route] = snapshot(eng)
+        after[route] = engine_state(eng, "index")
     for route in ("calls", "eager"):
-        for k, (x, y) in enumerate(zip(after["periods"], after[route])):
-            assert np.array_equal(x, y), (route, k)
-    assert not np.array_equal(after["periods"][0], res["periods"][0])
+        assert_same_state(after["periods"], after[route], what=f"{route} behind set_bc")
+    assert not np.array_equal(after["periods"]["params.actor"], res["periods"]["params.actor"])
     st1 = engines["periods"][0].step_periods_stats()
     assert st1["run_graphs_captured"] <= 2      # (at most the other start variant; test_set_bc_between_periods_captures_nothing is the strict form)
     assert engines["periods"][0].graph_kernel_count(10) == run_nodes and (run_nodes > 0) == pipelined
@@ -230,7 +217,7 @@ def test_every_route_computes_the_same_bits(shape, B):
     _, other, _ = make_bc_pair(shape, B, seed=4)
     other.rb_extend(*rows)
     other.run_iterations(0, 18)
-    assert not np.array_equal(other.get_params(_lib.ACTOR), after["periods"][0])
+    assert not np.array_equal(other.get_params(_lib.ACTOR), after["periods"]["params.actor"])
     # Agent.update_actor hands the two BC metrics out as zero-copy tensors beside the loss
     eng, agent = engines["agent"]
     out = agent.update_actor(agent.rb.sample(B))
@@ -281,10 +268,10 @@ def test_bc_adds_no_graph_node(shape, B):
 def test_boundaries():
     o, a, bound = DIMS["halfcheetah"]
     with pytest.raises(P.EngineError, match="bc_alpha"):      # SAC has no BC form; the message names the field
-        P.Engine(P.Config(ob_dim=o, ac_dim=a, bc_alpha=2.5), -1.0, 1.0)
+        track(P.Engine(P.Config(ob_dim=o, ac_dim=a, bc_alpha=2.5), -1.0, 1.0))
     for bad in (-1.0, float("nan"), float("inf")):
         with pytest.raises(P.EngineError, match=r"\(-1\).*bc_alpha"):
-            P.Engine(P.Config(ob_dim=o, ac_dim=a, prefer_td3_over_sac=True, bc_alpha=bad), -1.0, 1.0)
+            track(P.Engine(P.Config(ob_dim=o, ac_dim=a, prefer_td3_over_sac=True, bc_alpha=bad), -1.0, 1.0))
     _, plain, _ = make_bc_pair("halfcheetah", 64, bc_alpha=0.0)
     with pytest.raises(P.EngineError, match="-3"):            # SACTD3_ESTATE: the kernel forms are chosen at create
         plain.set_bc(2.5, 1.0)

@@ -136,3 +136,48 @@ def test_run_iterations_splits_a_run_into_periods_a_cut_short_period_and_single_
                 assert sum(c[0] == "period" for c in calls) == max(0, (i0 + n) // period - (i0 + period - 1) // period)      # every whole period inside the run
             else:
                 assert all(c[0] == "step" for c in calls)
+
+
+# ------------------------------------------------------------------------------------------ the test suite's own plumbing
+def test_no_test_module_imports_another_test_module():
+    """helpers shared by test modules live in modules that are not tests (tests/helpers.py, tests/gpu_support.py, ...): an import of a
+    module whose last component starts with `test_` makes one test file a library of another"""
+    import ast
+    import glob
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    found = []
+    for path in sorted(glob.glob(os.path.join(here, "*.py"))):
+        with open(path) as f:
+            tree = ast.parse(f.read(), path)
+        for node in ast.walk(tree):
+            names = []
+            if isinstance(node, ast.Import):
+                names = [a.name for a in node.names]
+            elif isinstance(node, ast.ImportFrom):
+                names = [node.module or ""] + [f"{node.module or ''}.{a.name}" for a in node.names]
+            found += [f"{os.path.basename(path)}:{node.lineno}: {n}" for n in names if n.rsplit(".", 1)[-1].startswith("test_")]
+    assert not found, found
+
+
+def test_same_bits_compares_shape_dtype_and_bytes():
+    from tests.gpu_support import same_bits
+    nan = np.array([np.nan, 1.0], np.float32)
+    assert not same_bits(np.float32([-0.0]), np.float32([0.0]))                      # -0.0 is not +0.0
+    assert same_bits(nan, nan.copy())                                                # a NaN equals the same NaN pattern
+    assert not same_bits(np.float32([1.0, 2.0]), np.float64([1.0, 2.0]))             # float32 is not float64 of the same values
+
+
+def test_engines_of_a_test_are_closed_when_it_ends():
+    """the autouse fixture of tests/gpu_support.py, as pytest drives it: whatever the registry holds when the test body is left --
+    by a return or by an exception -- is closed, and the registry is empty for the next test"""
+    import inspect
+    from tests import gpu_support
+    closed = []
+    fixture = inspect.unwrap(gpu_support.close_engines)()
+    next(fixture)                                                                    # set-up; the test body would run here
+    stub = gpu_support.track(SimpleNamespace(close=lambda: closed.append("stub")))
+    assert gpu_support._OPEN[-1] is stub
+    with pytest.raises(StopIteration):                                               # tear-down, which pytest runs whether the body raised or not
+        next(fixture)
+    assert closed == ["stub"] and not gpu_support._OPEN

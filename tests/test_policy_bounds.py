@@ -1,5 +1,5 @@
 """The checker of tests/test_gpu_policy.py on the CPU.  k_pi_head (csrc/policy_kernels.h) is restated here in fp32 numpy in its
-documented order of operations -- ln_fwd, the head product in the form of the acting tail of the same head shape (tests/test_tail_bounds.py:
+documented order of operations -- ln_fwd, the head product in the form of the acting tail of the same head shape (tests/tail_checks.py:
 head), the squash, the inverse squash with its clamp at M = float32(1 - 1e-6), the row sums as a 16-lane tree -- on the edge inputs of
 tail_checks.make_case (saturating head-bias offsets, per-dimension asymmetric action bounds) at the GPU test's shapes, with benign and
 with degenerate nets.  policy_checks.check_policy_outputs must accept every one of them and raise bounds.Violation for each defect of
@@ -13,7 +13,7 @@ from tests import bounds as bd
 from tests import policy_checks as pc
 from tests import tail_checks as tc
 from tests.helpers import DIMS
-from tests.test_tail_bounds import head, ln_fwd, ln_of, tree16, trunk
+from tests.tail_checks import head, ln_fwd, ln_of, tree16, trunk
 
 F32 = np.float32
 N = 67

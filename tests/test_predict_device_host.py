@@ -10,7 +10,7 @@ import torch
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, loop
-from tests.test_device_boundary_host import FakeDeviceArray
+from tests.helpers import FakeDeviceArray
 
 O, A = 11, 3
 

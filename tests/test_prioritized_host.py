@@ -13,7 +13,7 @@ import torch
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, loop
-from tests.test_device_boundary_host import FakeDeviceArray, five
+from tests.helpers import FakeDeviceArray, five
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 O, A, B = 11, 3, 8

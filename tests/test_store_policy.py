@@ -91,17 +91,6 @@ def test_write_through_sites_compile_to_sc1_vector_stores(tmp_path_factory, whic
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
 
-def _state(eng, _lib):
-    out = [eng.get_params(w) for w in (_lib.ACTOR, _lib.CRITICS, _lib.CRITICS_TARGET, _lib.ACTOR_TARGET, _lib.LOG_ALPHA)]
-    for w in (_lib.ACTOR, _lib.CRITICS):
-        m, v, t = eng.get_adam_state(w)
-        out += [m, v, np.asarray([t])]
-    met = eng.read_metrics()
-    out.append(np.asarray([met[k] for k in sorted(met)], np.float32))
-    out.append(eng.read_batch()["index"])
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("algo,env,B", [("sac", "hopper", 256), ("td3", "halfcheetah", 256)])
 def test_period_graphs_without_inspection_stores_equal_single_iterations(algo, env, B):
@@ -109,8 +98,8 @@ def test_period_graphs_without_inspection_stores_equal_single_iterations(algo, e
     them, so 4 whole periods + a cut-short one through run_iterations leave parameters, targets, log alpha, Adam state, metrics
     and the sampled indices bit-identical to the same iterations issued singly; debug_read of the gradients raises behind a period
     call and, behind a following single iteration, returns the bits of an engine that only ever stepped singly."""
+    from tests.gpu_support import P, _lib, assert_same_state, engine_state, make_pair
     from tests.helpers import synth_transitions
-    from tests.test_gpu_engine import P, _lib, make_pair
     res, grads = [], []
     for mode in ("period", "single"):
         ref, eng, (o, a, bound) = make_pair(algo, env, B, seed=9)
@@ -124,7 +113,7 @@ def test_period_graphs_without_inspection_stores_equal_single_iterations(algo, e
         else:
             for i in range(n):
                 eng.step(i % 3 == 0)
-        res.append(_state(eng, _lib))
+        res.append(engine_state(eng, "index"))
         eng.step(False)                                      # iteration 14: rewrites the critics' arenas in full
         grads.append((eng.debug_read("grad_critics"), eng.debug_read("c_dz1")))
         if mode == "period":
@@ -132,7 +121,7 @@ def test_period_graphs_without_inspection_stores_equal_single_iterations(algo, e
                 eng.debug_read("grad_actor")
             eng.update_actor()
             assert eng.debug_read("grad_actor").size == eng.param_count(_lib.ACTOR) and eng.debug_read("a_dz1").size == B * 256
-    for x, y in zip(*res):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
+        eng.close()
+    assert_same_state(*res, what="periods against single iterations")
     for x, y in zip(*grads):
         assert np.array_equal(x, y) and np.isfinite(x).all() and np.abs(x).max() > 0

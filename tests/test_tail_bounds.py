@@ -1,7 +1,7 @@
 """The checker of tests/test_gpu_tail_edges.py on the CPU.  The row-local kernels (csrc/kernels.h: ln_fwd, ln_bwd, actor_tail_body,
 actor_tail_s_body, critic_tail_body.inc, k_actorq_tail, actor_head_bwd*_body.inc) are restated here in fp32 numpy in the summation
-orders they use -- a 16-lane tree per row over per-lane partial sums, the general tail's head dot product split over four waves,
-column sums per 4-row or 16-row block and then over the blocks -- on the edge inputs of tests/tail_checks.py:make_case with the GPU
+orders they use (the building blocks at the end of tests/tail_checks.py) -- a 16-lane tree per row over per-lane partial sums, the
+general tail's head dot product split over four waves, column sums per 4-row or 16-row block and then over the blocks -- on the edge inputs of tests/tail_checks.py:make_case with the GPU
 cases' own seeds.  The checks of tests/tail_checks.py (bounds from tests/bounds.py) must accept every one of them and raise
 bounds.Violation for each defect of DEFECTS, one at a time, on the same inputs.  They also show that no row of any case comes near
 the limit of three undecided layer-2 ReLU gates."""
@@ -10,109 +10,16 @@ import pytest
 
 from tests import bounds as bd
 from tests import tail_checks as tc
+from tests.tail_checks import block_colsum, head, ln_bwd, ln_fwd, ln_of, row_dot, tree16, trunk
 
 F32 = tc.F32
 H = tc.H
-K1, K2 = "fc_stack.fc_block_1", "fc_stack.fc_block_2"
+K1, K2 = tc.K1, tc.K2
 
 CASES, case_seed = tc.CASES, tc.case_seed      # (algo, o, a, B, layer_norm): the table of tests/test_gpu_tail_edges.py
 
 DEFECTS = ["eps_outside_log", "scale_missing", "logstd_3_0", "ln_eps_outside_sqrt", "done_dropped", "tie_to_critic_1", "gate_ge_0",
            "dlogp_sign", "ragged_group_dropped", "weight_not_on_loss", "clip_before_noise"]
-
-
-# ------------------------------------------------------------------------------------------ fp32 building blocks
-
-def lanes(x):
-    """[B, 256] -> [B, 16 lanes, 4 q, 4]: lane `sub` holds columns 4 sub + 64 q .. + 3 (Row16)"""
-    return x.reshape(x.shape[0], 4, 16, 4).transpose(0, 2, 1, 3)
-
-
-def tree16(v):
-    """row16_sum: xor 1, xor 2, half mirror, mirror"""
-    i = np.arange(16)
-    for perm in (i ^ 1, i ^ 2, (i & 8) | (7 - (i & 7)), 15 - i):
-        v = v + v[:, perm]
-    return v[:, 0]
-
-
-def sum4(v):
-    return (v[..., 0] + v[..., 1]) + (v[..., 2] + v[..., 3])
-
-
-def row_total(x):
-    s = sum4(lanes(x))
-    return tree16((s[..., 0] + s[..., 1]) + (s[..., 2] + s[..., 3]))
-
-
-def row_dot(a, b):
-    p = lanes(a) * lanes(b)
-    d = ((p[..., 0] + p[..., 1]) + p[..., 2]) + p[..., 3]
-    return tree16((d[..., 0] + d[..., 1]) + (d[..., 2] + d[..., 3]))
-
-
-def ln_fwd(z, g, be, ln, eps_outside=False):
-    if not ln:
-        return z, z, np.ones(z.shape[0], F32)
-    mean = row_total(z) * F32(1.0 / H)
-    d = z - mean[:, None]
-    var = row_dot(d, d) * F32(1.0 / H)
-    rstd = F32(1) / (np.sqrt(var) + F32(1e-5)) if eps_outside else F32(1) / np.sqrt(var + F32(1e-5))
-    xh = d * rstd[:, None]
-    return xh, xh * g + be, rstd.astype(F32)
-
-
-def ln_bwd(dy, xh, rstd, g, ln):
-    if not ln:
-        return dy
-    dxh = dy * g
-    m1 = row_total(dxh) * F32(1.0 / H)
-    m2 = row_dot(dxh, xh) * F32(1.0 / H)
-    return (dxh - m1[:, None] - xh * m2[:, None]) * rstd[:, None]
-
-
-def block_colsum(vals, rpb, drop_last_group=False):
-    """column sums per rpb-row block (rows in order), then over the blocks in order"""
-    B = vals.shape[0]
-    if drop_last_group:
-        B = 4 * ((B - 1) // 4)
-    tot = np.zeros(vals.shape[1:], F32)
-    for b0 in range(0, B, rpb):
-        acc = np.zeros(vals.shape[1:], F32)
-        for r in range(b0, min(b0 + rpb, B)):
-            acc = acc + vals[r]
-        tot = tot + acc
-    return tot
-
-
-def ln_of(p, ln):
-    return (p[f"{K2}.ln.weight"], p[f"{K2}.ln.bias"]) if ln else (None, None)
-
-
-def trunk(p, X, ln, stores=False):
-    """z2 of a net on rows X (torch-free fp32: the trunk GEMMs have their own tests); stores: also h1, xhat1, rstd1"""
-    z1 = (X @ p[f"{K1}.fc.weight"].T + p[f"{K1}.fc.bias"]).astype(F32)
-    xh1, rs1 = z1, np.ones(len(X), F32)
-    if ln:
-        mu = z1.mean(1, keepdims=True)
-        rs1 = (F32(1) / np.sqrt(((z1 - mu) ** 2).mean(1, keepdims=True) + F32(1e-5))).astype(F32)
-        xh1 = ((z1 - mu) * rs1).astype(F32)
-        z1, rs1 = (xh1 * p[f"{K1}.ln.weight"] + p[f"{K1}.ln.bias"]).astype(F32), rs1[:, 0]
-    h1 = np.maximum(z1, F32(0))
-    z2 = (h1 @ p[f"{K2}.fc.weight"].T + p[f"{K2}.fc.bias"]).astype(F32)
-    return (z2, h1, xh1, rs1) if stores else z2
-
-
-def head(h, Wh, bh, narrow):
-    if narrow:        # one dot product per output, reduced over the row's 16 lanes
-        return np.stack([row_dot(h, np.broadcast_to(Wh[n], h.shape)) for n in range(Wh.shape[0])], 1) + bh
-    part = []         # K split over 4 waves of 64 columns, each accumulated in order; then ((p0 + p1) + (p2 + p3)) + bh
-    for w in range(4):
-        acc = np.zeros((h.shape[0], Wh.shape[0]), F32)
-        for k in range(64 * w, 64 * w + 64):
-            acc = acc + h[:, k:k + 1] * Wh[None, :, k]
-        part.append(acc)
-    return ((part[0] + part[1]) + (part[2] + part[3])) + bh
 
 
 def actor_tail(z2, p, eps, c, mode, cfg, defect=None):
