@@ -162,6 +162,15 @@ def ln_affine_grads(dh, h, xhat):
 # rounding of that comparison itself.
 LIBM_ULP = {"tanhf": 3, "expf": 2, "logf": 4}
 ULP = 2.0 * U                 # the float32 spacing at v is at most 2^-23 |v|
+# The pieces of the engine's normal draws, measured EXHAUSTIVELY over the 2^24 arguments of philox_u01 against float64
+# (profiles/libm_ulp.json under "noise", tools/libm_ulp.py on an MI355X), each rounded up to the next power of two -- the margin covers
+# only the rounding of the comparison itself.  tests/test_noise_model.py ties the record to these constants.
+#   rad_rel       sqrtf(-2 ln2 v_log_f32(u)), relative to sqrt(-2 ln u)                    measured 1.278e-7  (> 2^-23)
+#   trig_rev_abs  v_sin_f32(u) / v_cos_f32(u), absolute against sin / cos(2 pi u)          measured 1.253e-7 both  (> 2^-23)
+#   rad_libm_rel  sqrtf(-2.f logf(u)) of k_rb_fill, relative                               measured 1.500e-7
+#   sinf_abs, cosf_abs   the library's sinf / cosf at t = fl32(2 pi_f32 u), absolute against float64 at that t    6.29e-8, 7.03e-8
+# logf over the same 2^24 arguments (down to 2^-25, below the 1e-6 where the entry above starts): 2.14 ulp, under LIBM_ULP["logf"].
+NOISE = {"rad_rel": 2.0 ** -22, "trig_rev_abs": 2.0 ** -22, "rad_libm_rel": 2.0 ** -22, "sinf_abs": 2.0 ** -23, "cosf_abs": 2.0 ** -23}
 LN_EPS = float(np.float32(1e-5))
 LOGP_CONST = float(np.float32(0.9189385332046727))
 TANH_EPS = float(np.float32(1e-6))

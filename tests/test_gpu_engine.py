@@ -12,6 +12,7 @@ import torch
 
 from oracle import replay_ref
 from oracle.sac_td3_ref import Hps, RefAgent
+from tests import noise_model
 from tests.gpu_stage_checks import check_update_actor_intermediates, check_update_qnets_intermediates
 from tests.gpu_support import (P, _lib, actor_layout, close, close_engines, crit_layout, flat_actor, flat_critics, gclose, logp_close,  # noqa: F401
                                make_pair, push_params, schema, track)
@@ -730,11 +731,11 @@ def test_native_noise_stream_matches_philox_oracle():
     eng.load_batch(obs, act, rew, nobs, done)
     eng.update_qnets()
     got = eng.read_noise(_lib.SITE_CRITIC)
-    want = replay_ref.normals(77, 0, 0, 256 * a).reshape(256, a)
-    np.testing.assert_allclose(got, want, rtol=1e-4, atol=2e-5)
+    # every element inside the a-priori bound of the float64 model (tests/noise_model.py: measured unit errors, nothing observed here)
+    observe("test_native_noise_stream_matches_philox_oracle", "worst |err| / bound", noise_model.check("counter 0", got, 77, 0, 0))
     eng.update_qnets()   # the graph bumped the device-side counter itself: fresh draws
     got2 = eng.read_noise(_lib.SITE_CRITIC)
-    np.testing.assert_allclose(got2, replay_ref.normals(77, 1, 0, 256 * a).reshape(256, a), rtol=1e-4, atol=2e-5)
+    observe("test_native_noise_stream_matches_philox_oracle", "worst |err| / bound", noise_model.check("counter 1", got2, 77, 1, 0))
     assert not np.allclose(got, got2)
 
 

@@ -17,8 +17,8 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import replay_ref
 from oracle.sac_td3_ref import Hps
+from tests import noise_model
 from tests import policy_checks as pc
 from tests import tail_checks as tc
 from tests.gpu_support import (DEV, NROWS, SENTINEL, SHAPES, P, _lib, assert_same_state, close, close_engines, data, loop, make_engine,  # noqa: F401
@@ -183,26 +183,29 @@ def test_bit_for_bit_ties(shape):
 
 # ------------------------------------------------------------------------------------------ 4. native draws
 def test_native_draws_follow_their_own_philox_stream_and_move_no_other_counter():
-    """eps_out of two consecutive native calls == the Philox restatement of the noise tests (oracle/replay_ref.py: normals) with
-    stream 0x400 and the counter at 0, then 1; a call with `eps` given leaves the counter alone (the next native call draws with 2);
+    """eps_out of two consecutive native calls lies, element by element, inside the a-priori bound of the float64 Philox model of the
+    noise tests (tests/noise_model.py) with stream 0x400 and the counter at 0, then 1; a call with `eps` given leaves the counter alone (the next native call draws with 2);
     the host call draws from the same stream.  A twin engine that asks nothing has the same noise buffers at every site and returns
     the same exploring action."""
     ref, (R, N), (o, a, bound) = shape_engines("sac-humanoid", count=2)
     obs_h = data("sac-humanoid")[0]
     obs = obs_h.to(DEV)
-    want = lambda ctr, n: replay_ref.normals(3, ctr, 0x400, n * a).reshape(n, a)
+    # every element inside the a-priori bound of the float64 model (tests/noise_model.py) at stream word 0x400
+    on_stream = lambda got, ctr: noise_model.check(f"policy draw {ctr}", got, 3, ctr, noise_model.STREAM_POLICY)
     for ctr, n in ((0, NROWS), (1, 67)):
         got = ask(R, obs[:n], sample=True)
-        np.testing.assert_allclose(got["eps_out"], want(ctr, n), rtol=1e-4, atol=2e-5)
+        assert got["eps_out"].shape == (n, a)
+        on_stream(got["eps_out"], ctr)
         again = ask(R, obs[:n], eps=dev(got["eps_out"]))                     # its sample is the sample of those draws; no tick
         assert same_bits(again["sample"], got["sample"]) and same_bits(again["sample_logp"], got["sample_logp"])
     got = R.policy(obs_h[:67].numpy(), sample=True)
-    np.testing.assert_allclose(got["eps_out"], want(2, 67), rtol=1e-4, atol=2e-5)
+    assert got["eps_out"].shape == (67, a)
+    on_stream(got["eps_out"], 2)
     got = ask(R, obs[:5], want=("sample_logp",))                             # (sample_logp alone draws too)
     assert np.isfinite(got["sample_logp"]).all()
-    np.testing.assert_allclose(ask(R, obs[:5], want=("eps_out", "sample"))["eps_out"], want(4, 5), rtol=1e-4, atol=2e-5)
+    on_stream(ask(R, obs[:5], want=("eps_out", "sample"))["eps_out"], 4)
     ask(R, obs[:5])                                                          # no sample wanted: no tick
-    np.testing.assert_allclose(ask(R, obs[:5], sample=True)["eps_out"], want(5, 5), rtol=1e-4, atol=2e-5)
+    on_stream(ask(R, obs[:5], sample=True)["eps_out"], 5)
     for eng in (R, N):
         eng.rb_extend(*[t.numpy() for t in synth_transitions(300, o, a, bound, seed=31)])
         eng.run_iterations(0, 3)

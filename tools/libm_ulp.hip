@@ -5,7 +5,20 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/libm_ulp.hip -o tools/libm_ulp       (the engine Makefile's flags: no fast-math)
 //   tools/libm_ulp <out.bin>
 // File: int32 count n, then per function (tanh, exp, log) n arguments and n results.
+//
+// Behind them, the pieces of the engine's normal draws, EXHAUSTIVELY: philox_u01 (csrc/philox.h, included here) has only 2^24
+// possible arguments x >> 8, so every piece is evaluated at u = philox_u01(i << 8), i = 0 .. 2^24 - 1.  The three arithmetic lines
+// of philox_normal4 (csrc/kernels.h) are RESTATED here, not included -- kernels.h is the whole engine:
+//     rad = sqrtf(-2.0f * 0.6931471805599453f * __builtin_amdgcn_logf(u))      (v_log_f32: log2)
+//     __builtin_amdgcn_sinf(u), __builtin_amdgcn_cosf(u)                       (v_sin_f32 / v_cos_f32: argument in revolutions)
+// and so are those of k_rb_fill, which uses the library instead:  t = 6.283185307179586f * u, sinf(t), cosf(t), logf(u),
+// sqrtf(-2.f * logf(u)).
+// File, continued: int32 count m = 2^24, then m results each of NOISE_FNS functions in the order of enum NoiseFn; for FN_T the
+// result is t itself (the float64 reference is taken at that same fp32 t).  The arguments are not written: tools/libm_ulp.py
+// recomputes philox_u01 in numpy float32, and FN_U carries the device's own u to check that against.
 #include <hip/hip_runtime.h>
+
+#include "../sac-td3-cudagraphs-pytorch_amd/csrc/philox.h"
 
 #include <cmath>
 #include <cstdio>
@@ -26,6 +39,28 @@ __global__ __launch_bounds__(256) void k_eval(const float* x, float* y, int n, i
   if (i >= n) return;
   const float v = x[i];
   y[i] = fn == 0 ? tanhf(v) : (fn == 1 ? expf(v) : logf(v));
+}
+
+enum NoiseFn { FN_U = 0, FN_RAD, FN_SINREV, FN_COSREV, FN_T, FN_SINF, FN_COSF, FN_LOGF, FN_RAD_LIBM, NOISE_FNS };
+
+__global__ __launch_bounds__(256) void k_noise(float* y, int m, int fn) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  const float u = philox_u01((uint32_t)i << 8);
+  const float t = 6.283185307179586f * u;
+  float r;
+  switch (fn) {
+    case FN_U: r = u; break;
+    case FN_RAD: r = sqrtf(-2.0f * 0.6931471805599453f * __builtin_amdgcn_logf(u)); break;
+    case FN_SINREV: r = __builtin_amdgcn_sinf(u); break;
+    case FN_COSREV: r = __builtin_amdgcn_cosf(u); break;
+    case FN_T: r = t; break;
+    case FN_SINF: r = sinf(t); break;
+    case FN_COSF: r = cosf(t); break;
+    case FN_LOGF: r = logf(u); break;
+    default: r = sqrtf(-2.f * logf(u)); break;
+  }
+  y[i] = r;
 }
 
 int main(int argc, char** argv) {
@@ -58,6 +93,17 @@ int main(int argc, char** argv) {
   }
   CHECK(hipFree(dx));
   CHECK(hipFree(dy));
+  const int m = 1 << 24;
+  std::vector<float> z((size_t)NOISE_FNS * m);
+  float* dz = nullptr;
+  CHECK(hipMalloc(&dz, sizeof(float) * m));
+  for (int fn = 0; fn < NOISE_FNS; ++fn) {
+    hipLaunchKernelGGL(k_noise, dim3((m + 255) / 256), dim3(256), 0, 0, dz, m, fn);
+    CHECK(hipGetLastError());
+    CHECK(hipDeviceSynchronize());
+    CHECK(hipMemcpy(z.data() + (size_t)fn * m, dz, sizeof(float) * m, hipMemcpyDeviceToHost));
+  }
+  CHECK(hipFree(dz));
   FILE* f = fopen(argv[1], "wb");
   if (!f) {
     perror(argv[1]);
@@ -66,11 +112,12 @@ int main(int argc, char** argv) {
   bool ok = fwrite(&n, sizeof(int), 1, f) == 1;
   for (int fn = 0; fn < 3 && ok; ++fn)
     ok = fwrite(x.data() + (size_t)fn * n, sizeof(float), n, f) == (size_t)n && fwrite(y.data() + (size_t)fn * n, sizeof(float), n, f) == (size_t)n;
+  ok = ok && fwrite(&m, sizeof(int), 1, f) == 1 && fwrite(z.data(), sizeof(float), z.size(), f) == z.size();
   ok = (fclose(f) == 0) && ok;
   if (!ok) {
     fprintf(stderr, "short write to %s\n", argv[1]);
     return 1;
   }
-  printf("wrote %d points per function to %s\n", n, argv[1]);
+  printf("wrote %d points per library function and %d per noise piece to %s\n", n, m, argv[1]);
   return 0;
 }
