@@ -49,6 +49,14 @@ SYMBOLS = [
     "sactd3_policy_device", "sactd3_policy", "sactd3_policy_stats",
 ]
 
+# every symbol include/sactd3_env.h declares (tests/test_env_host.py checks the header against this list)
+ENV_SYMBOLS = [
+    "sactd3_env_create", "sactd3_env_destroy", "sactd3_env_last_error", "sactd3_env_spec", "sactd3_env_reset", "sactd3_env_step",
+    "sactd3_env_sample_actions", "sactd3_env_episode_stats", "sactd3_env_get_state", "sactd3_env_set_state",
+]
+ENV_PENDULUM, ENV_CARTPOLE = 0, 1   # sactd3_env_config.kind
+ENV_STATE_DIM = 4                   # SACTD3_ENV_STATE_DIM
+
 
 class EngineError(RuntimeError):
     pass
@@ -86,6 +94,33 @@ POLICY_IO_FIELDS = (("actions", "a"), ("eps", "a"), ("mode", "a"), ("mean", "a")
 class CPolicyIO(C.Structure):
     """sactd3_policy_io: nine pointers (None = not given / not wanted), each with its row stride in elements"""
     _fields_ = [(n, t) for f, _ in POLICY_IO_FIELDS for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
+
+
+class CEnvConfig(C.Structure):
+    """sactd3_env_config"""
+    _fields_ = [("kind", C.c_int32), ("num_envs", C.c_int32), ("horizon", C.c_int32), ("device_id", C.c_int32), ("seed", C.c_uint64)]
+
+
+class CEnvInfo(C.Structure):
+    """sactd3_env_info"""
+    _fields_ = [("ob_dim", C.c_int32), ("ac_dim", C.c_int32), ("horizon", C.c_int32), ("num_envs", C.c_int32), ("min_ac", C.c_float), ("max_ac", C.c_float)]
+
+
+class CEnvOut(C.Structure):
+    """sactd3_env_out: six device pointers (None = not wanted; obs is required), each with its row stride in elements"""
+    _fields_ = [(n, t) for f in ("obs", "final_obs", "reward", "terminated", "truncated", "ended") for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
+
+
+class CEnvState(C.Structure):
+    """sactd3_env_state: five host arrays (None = skipped)"""
+    _fields_ = [(n, C.c_void_p) for n in ("phys", "steps", "episode", "returns", "draws")]
+
+
+class CEnvStats(C.Structure):
+    """sactd3_env_stats: four totals, five per-env host arrays (None = not wanted)"""
+    _fields_ = [("episodes", C.c_int64), ("return_sum", C.c_double), ("length_sum", C.c_int64), ("bad_actions", C.c_int64),
+                ("last_return", C.c_void_p), ("last_length", C.c_void_p), ("env_episodes", C.c_void_p),
+                ("first_return", C.c_void_p), ("first_length", C.c_void_p)]
 
 
 def library_path() -> str:
@@ -203,6 +238,20 @@ def load_library():
         "sactd3_time_nodes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, fp, C.POINTER(C.c_double), C.POINTER(C.c_double), i64p]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
+    env_sig = {
+        "sactd3_env_create": (C.c_int, [C.POINTER(CEnvConfig), C.POINTER(vp)]),
+        "sactd3_env_destroy": (None, [vp]),
+        "sactd3_env_last_error": (C.c_char_p, [vp]),
+        "sactd3_env_spec": (C.c_int, [vp, C.POINTER(CEnvInfo)]),
+        "sactd3_env_reset": (C.c_int, [vp, C.c_uint64, vp, C.c_int64, vp]),
+        "sactd3_env_step": (C.c_int, [vp, vp, C.c_int64, C.POINTER(CEnvOut), vp]),
+        "sactd3_env_sample_actions": (C.c_int, [vp, vp, C.c_int64, vp]),
+        "sactd3_env_episode_stats": (C.c_int, [vp, C.POINTER(CEnvStats), vp]),
+        "sactd3_env_get_state": (C.c_int, [vp, C.POINTER(CEnvState), vp]),
+        "sactd3_env_set_state": (C.c_int, [vp, C.POINTER(CEnvState), vp]),
+    }
+    assert sorted(env_sig) == sorted(ENV_SYMBOLS)
+    sig.update(env_sig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the .so does not export what the header declares
         fn.restype, fn.argtypes = res, args

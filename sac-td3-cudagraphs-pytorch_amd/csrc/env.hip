@@ -1,0 +1,339 @@
+// Host side of include/sactd3_env.h: the handle, its one device allocation, and one launch per call (csrc/env_kernels.h).
+// A translation unit of its own inside libsactd3_hip.so: it shares philox.h with engine.hip and nothing else.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/sactd3.h"
+#include "../../include/sactd3_env.h"
+#include "env_kernels.h"
+
+#define ENV_API extern "C" __attribute__((visibility("default")))
+
+static thread_local std::string g_env_create_error;
+
+struct sactd3_env {
+  sactd3_env_config cfg{};
+  sactd3_env_info info{};
+  EnvDev d{};
+  void* mem = nullptr;
+  std::string err;
+
+  int fail(int code, const char* what, hipError_t he = hipSuccess) {
+    err = what;
+    if (he != hipSuccess) err += std::string(": ") + hipGetErrorString(he);
+    return code;
+  }
+};
+
+#define ENV_HIP(e, call)                                                \
+  do {                                                                  \
+    hipError_t he_ = (call);                                            \
+    if (he_ != hipSuccess) return (e)->fail(SACTD3_EHIP, #call, he_);   \
+  } while (0)
+
+static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline unsigned env_blocks(int n) { return (unsigned)((n + 255) / 256); }
+
+static int env_alloc(sactd3_env* e) {
+  const size_t n = (size_t)e->cfg.num_envs;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
+  const size_t phys = take(4 * n * 4), steps = take(n * 4), episode = take(n * 4), ret = take(n * 4), draws = take(n * 4),
+               done_count = take(n * 4), ret_sum = take(n * 8), len_sum = take(n * 8), last_ret = take(n * 4), last_len = take(n * 4),
+               first_ret = take(n * 4), first_len = take(n * 4), bad = take(n * 4);
+  ENV_HIP(e, hipMalloc(&e->mem, off));
+  ENV_HIP(e, hipMemset(e->mem, 0, off));
+  char* base = (char*)e->mem;
+  e->d.phys = (float*)(base + phys);
+  e->d.steps = (int32_t*)(base + steps);
+  e->d.episode = (uint32_t*)(base + episode);
+  e->d.ret = (float*)(base + ret);
+  e->d.draws = (uint32_t*)(base + draws);
+  e->d.done_count = (uint32_t*)(base + done_count);
+  e->d.ret_sum = (double*)(base + ret_sum);
+  e->d.len_sum = (unsigned long long*)(base + len_sum);
+  e->d.last_ret = (float*)(base + last_ret);
+  e->d.last_len = (int32_t*)(base + last_len);
+  e->d.first_ret = (float*)(base + first_ret);
+  e->d.first_len = (int32_t*)(base + first_len);
+  e->d.bad = (uint32_t*)(base + bad);
+  e->d.n = (int)n;
+  return SACTD3_OK;
+}
+
+static int env_init(sactd3_env* e, const sactd3_env_config* cfg) {
+  e->cfg = *cfg;
+  if (cfg->kind < 0 || cfg->kind >= SACTD3_ENV_NUM_KINDS) return e->fail(SACTD3_EINVAL, "kind must be SACTD3_ENV_PENDULUM or SACTD3_ENV_CARTPOLE");
+  if (cfg->num_envs < 1 || cfg->num_envs > (1 << 24)) return e->fail(SACTD3_EINVAL, "num_envs must be in [1, 2^24]");
+  if (cfg->horizon < 0) return e->fail(SACTD3_EINVAL, "horizon must be >= 0 (0: the task's default)");
+  const bool pend = cfg->kind == SACTD3_ENV_PENDULUM;
+  e->info.ob_dim = pend ? EnvTask<ENV_PENDULUM>::OB : EnvTask<ENV_CARTPOLE>::OB;
+  e->info.ac_dim = 1;
+  e->info.horizon = cfg->horizon ? cfg->horizon : 200;
+  e->info.num_envs = cfg->num_envs;
+  e->info.max_ac = pend ? EnvTask<ENV_PENDULUM>::BOUND : EnvTask<ENV_CARTPOLE>::BOUND;
+  e->info.min_ac = -e->info.max_ac;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return e->fail(SACTD3_ENODEV, "no HIP device visible");
+  if (cfg->device_id < 0 || cfg->device_id >= ndev) return e->fail(SACTD3_EINVAL, "device_id is not a visible device");
+  ENV_HIP(e, hipSetDevice(cfg->device_id));
+  hipDeviceProp_t prop;
+  ENV_HIP(e, hipGetDeviceProperties(&prop, cfg->device_id));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return e->fail(SACTD3_ENODEV, "device is not gfx950 (this library carries gfx950 code objects only)");
+  return env_alloc(e);
+}
+
+static int env_create_body(const sactd3_env_config* cfg, sactd3_env** out);
+ENV_API int sactd3_env_create(const sactd3_env_config* cfg, sactd3_env** out) {
+  try {
+    return env_create_body(cfg, out);
+  } catch (...) {      // (the error text is a std::string)
+    return SACTD3_EHIP;
+  }
+}
+
+static int env_create_body(const sactd3_env_config* cfg, sactd3_env** out) {
+  if (out) *out = nullptr;
+  if (!cfg || !out) {
+    g_env_create_error = "sactd3_env_create: NULL argument";
+    return SACTD3_EINVAL;
+  }
+  sactd3_env* e = new (std::nothrow) sactd3_env();
+  if (!e) {
+    g_env_create_error = "sactd3_env_create: out of host memory";
+    return SACTD3_EHIP;
+  }
+  int rc;
+  try {
+    rc = env_init(e, cfg);
+    if (rc != SACTD3_OK) g_env_create_error = e->err;
+  } catch (...) {      // (nothing is leaked on the way out)
+    rc = SACTD3_EHIP;
+  }
+  if (rc != SACTD3_OK) {
+    if (e->mem) (void)hipFree(e->mem);
+    delete e;
+    return rc;
+  }
+  *out = e;
+  return SACTD3_OK;
+}
+
+ENV_API void sactd3_env_destroy(sactd3_env* e) {
+  if (!e) return;
+  if (e->mem) {
+    (void)hipSetDevice(e->cfg.device_id);
+    (void)hipFree(e->mem);      // (waits for the device: no kernel of this env is in flight behind it)
+  }
+  delete e;
+}
+
+ENV_API const char* sactd3_env_last_error(const sactd3_env* e) { return e ? e->err.c_str() : g_env_create_error.c_str(); }
+
+ENV_API int sactd3_env_spec(const sactd3_env* e, sactd3_env_info* out) {
+  if (!e || !out) return SACTD3_EINVAL;
+  *out = e->info;
+  return SACTD3_OK;
+}
+
+static int env_reset_body(sactd3_env* e, uint64_t seed, float* obs, int64_t obs_ld, void* stream);
+ENV_API int sactd3_env_reset(sactd3_env* e, uint64_t seed, float* obs, int64_t obs_ld, void* stream) {
+  try {
+    return env_reset_body(e, seed, obs, obs_ld, stream);
+  } catch (...) {      // (the error text is a std::string)
+    return SACTD3_EHIP;
+  }
+}
+
+static int env_reset_body(sactd3_env* e, uint64_t seed, float* obs, int64_t obs_ld, void* stream) {
+  if (!e) return SACTD3_EINVAL;
+  if (obs && obs_ld < e->info.ob_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_reset: obs_ld is below ob_dim");
+  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+  e->cfg.seed = seed;
+  hipStream_t st = (hipStream_t)stream;
+  if (e->cfg.kind == SACTD3_ENV_PENDULUM)
+    hipLaunchKernelGGL(k_env_reset<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, obs, (long long)obs_ld, seed);
+  else
+    hipLaunchKernelGGL(k_env_reset<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, obs, (long long)obs_ld, seed);
+  ENV_HIP(e, hipGetLastError());
+  return SACTD3_OK;
+}
+
+static int env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_env_out* out, void* stream);
+ENV_API int sactd3_env_step(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_env_out* out, void* stream) {
+  try {
+    return env_step_body(e, actions, act_ld, out, stream);
+  } catch (...) {      // (the error text is a std::string)
+    return SACTD3_EHIP;
+  }
+}
+
+static int env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_env_out* out, void* stream) {
+  if (!e) return SACTD3_EINVAL;
+  if (!actions || !out || !out->obs) return e->fail(SACTD3_EINVAL, "sactd3_env_step: actions, out and out->obs must not be NULL");
+  const int o = e->info.ob_dim;
+  if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_step: act_ld is below ac_dim");
+  if (out->obs_ld < o || (out->final_obs && out->final_obs_ld < o)) return e->fail(SACTD3_EINVAL, "sactd3_env_step: an observation stride is below ob_dim");
+  if ((out->reward && out->reward_ld < 1) || (out->terminated && out->terminated_ld < 1) || (out->truncated && out->truncated_ld < 1) ||
+      (out->ended && out->ended_ld < 1))
+    return e->fail(SACTD3_EINVAL, "sactd3_env_step: a per-env output needs a stride of at least 1");
+  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+  EnvOut k;
+  k.obs = out->obs; k.obs_ld = out->obs_ld;
+  k.final_obs = out->final_obs; k.final_obs_ld = out->final_obs_ld;
+  k.reward = out->reward; k.reward_ld = out->reward_ld;
+  k.terminated = out->terminated; k.terminated_ld = out->terminated_ld;
+  k.truncated = out->truncated; k.truncated_ld = out->truncated_ld;
+  k.ended = out->ended; k.ended_ld = out->ended_ld;
+  hipStream_t st = (hipStream_t)stream;
+  if (e->cfg.kind == SACTD3_ENV_PENDULUM)
+    hipLaunchKernelGGL(k_env_step<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, e->info.horizon,
+                       e->cfg.seed);
+  else
+    hipLaunchKernelGGL(k_env_step<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, e->info.horizon,
+                       e->cfg.seed);
+  ENV_HIP(e, hipGetLastError());
+  return SACTD3_OK;
+}
+
+static int env_sample_actions_body(sactd3_env* e, float* actions, int64_t act_ld, void* stream);
+ENV_API int sactd3_env_sample_actions(sactd3_env* e, float* actions, int64_t act_ld, void* stream) {
+  try {
+    return env_sample_actions_body(e, actions, act_ld, stream);
+  } catch (...) {      // (the error text is a std::string)
+    return SACTD3_EHIP;
+  }
+}
+
+static int env_sample_actions_body(sactd3_env* e, float* actions, int64_t act_ld, void* stream) {
+  if (!e) return SACTD3_EINVAL;
+  if (!actions) return e->fail(SACTD3_EINVAL, "sactd3_env_sample_actions: actions must not be NULL");
+  if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_sample_actions: act_ld is below ac_dim");
+  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+  hipLaunchKernelGGL(k_env_sample_actions, dim3(env_blocks(e->d.n)), dim3(256), 0, (hipStream_t)stream, e->d, actions, (long long)act_ld,
+                     e->info.ac_dim, e->info.min_ac, e->info.max_ac - e->info.min_ac, e->cfg.seed);
+  ENV_HIP(e, hipGetLastError());
+  return SACTD3_OK;
+}
+
+// device -> host of one per-env array, behind what the stream has queued
+template <class T>
+static int env_pull(sactd3_env* e, std::vector<T>& host, const T* dev, size_t count, hipStream_t st) {
+  host.resize(count);
+  ENV_HIP(e, hipMemcpyAsync(host.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost, st));
+  return SACTD3_OK;
+}
+
+static int env_episode_stats_body(sactd3_env* e, sactd3_env_stats* out, void* stream);
+ENV_API int sactd3_env_episode_stats(sactd3_env* e, sactd3_env_stats* out, void* stream) {
+  try {
+    return env_episode_stats_body(e, out, stream);
+  } catch (...) {      // (the host staging vectors, the error text: std::bad_alloc never crosses the C boundary)
+    return SACTD3_EHIP;
+  }
+}
+
+static int env_episode_stats_body(sactd3_env* e, sactd3_env_stats* out, void* stream) {
+  if (!e) return SACTD3_EINVAL;
+  if (!out) return e->fail(SACTD3_EINVAL, "sactd3_env_episode_stats: out must not be NULL");
+  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)e->d.n;
+  std::vector<uint32_t> done, bad;
+  std::vector<double> rs;
+  std::vector<unsigned long long> ls;
+  std::vector<float> lr, fr;
+  std::vector<int32_t> ll, fl;
+  int rc;
+  if ((rc = env_pull(e, done, e->d.done_count, n, st)) || (rc = env_pull(e, bad, e->d.bad, n, st)) || (rc = env_pull(e, rs, e->d.ret_sum, n, st)) ||
+      (rc = env_pull(e, ls, e->d.len_sum, n, st)) || (rc = env_pull(e, lr, e->d.last_ret, n, st)) || (rc = env_pull(e, ll, e->d.last_len, n, st)) ||
+      (rc = env_pull(e, fr, e->d.first_ret, n, st)) || (rc = env_pull(e, fl, e->d.first_len, n, st)))
+    return rc;
+  ENV_HIP(e, hipStreamSynchronize(st));
+  out->episodes = 0; out->return_sum = 0.0; out->length_sum = 0; out->bad_actions = 0;
+  for (size_t i = 0; i < n; ++i) {      // the only sums over envs, in env order, on the host
+    out->episodes += done[i];
+    out->return_sum += rs[i];
+    out->length_sum += (int64_t)ls[i];
+    out->bad_actions += bad[i];
+    if (out->last_return) out->last_return[i] = lr[i];
+    if (out->last_length) out->last_length[i] = ll[i];
+    if (out->env_episodes) out->env_episodes[i] = done[i];
+    if (out->first_return) out->first_return[i] = fr[i];
+    if (out->first_length) out->first_length[i] = fl[i];
+  }
+  return SACTD3_OK;
+}
+
+static int env_get_state_body(sactd3_env* e, const sactd3_env_state* out, void* stream);
+ENV_API int sactd3_env_get_state(sactd3_env* e, const sactd3_env_state* out, void* stream) {
+  try {
+    return env_get_state_body(e, out, stream);
+  } catch (...) {      // (the host staging vectors, the error text: std::bad_alloc never crosses the C boundary)
+    return SACTD3_EHIP;
+  }
+}
+
+static int env_get_state_body(sactd3_env* e, const sactd3_env_state* out, void* stream) {
+  if (!e) return SACTD3_EINVAL;
+  if (!out) return e->fail(SACTD3_EINVAL, "sactd3_env_get_state: out must not be NULL");
+  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)e->d.n;
+  std::vector<float> phys;
+  if (out->phys) {
+    const int rc = env_pull(e, phys, e->d.phys, 4 * n, st);
+    if (rc) return rc;
+  }
+  if (out->steps) ENV_HIP(e, hipMemcpyAsync(out->steps, e->d.steps, n * 4, hipMemcpyDeviceToHost, st));
+  if (out->episode) ENV_HIP(e, hipMemcpyAsync(out->episode, e->d.episode, n * 4, hipMemcpyDeviceToHost, st));
+  if (out->returns) ENV_HIP(e, hipMemcpyAsync(out->returns, e->d.ret, n * 4, hipMemcpyDeviceToHost, st));
+  if (out->draws) ENV_HIP(e, hipMemcpyAsync(out->draws, e->d.draws, n * 4, hipMemcpyDeviceToHost, st));
+  ENV_HIP(e, hipStreamSynchronize(st));
+  if (out->phys)
+    for (size_t i = 0; i < n; ++i)
+      for (int j = 0; j < 4; ++j) out->phys[i * 4 + j] = phys[j * n + i];      // component-major on the device, env-major for the caller
+  return SACTD3_OK;
+}
+
+static int env_set_state_body(sactd3_env* e, const sactd3_env_state* in, void* stream);
+ENV_API int sactd3_env_set_state(sactd3_env* e, const sactd3_env_state* in, void* stream) {
+  try {
+    return env_set_state_body(e, in, stream);
+  } catch (...) {      // (the host staging vectors, the error text: std::bad_alloc never crosses the C boundary)
+    return SACTD3_EHIP;
+  }
+}
+
+static int env_set_state_body(sactd3_env* e, const sactd3_env_state* in, void* stream) {
+  if (!e) return SACTD3_EINVAL;
+  if (!in) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: in must not be NULL");
+  const size_t n = (size_t)e->d.n;
+  if (in->phys)
+    for (size_t k = 0; k < 4 * n; ++k)
+      if (!std::isfinite(in->phys[k])) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: a physical state is not finite");
+  if (in->steps)
+    for (size_t i = 0; i < n; ++i)
+      if (in->steps[i] < 0) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: a step count is negative");
+  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<float> phys;
+  if (in->phys) {
+    phys.resize(4 * n);
+    for (size_t i = 0; i < n; ++i)
+      for (int j = 0; j < 4; ++j) phys[j * n + i] = in->phys[i * 4 + j];
+    ENV_HIP(e, hipMemcpyAsync(e->d.phys, phys.data(), 4 * n * 4, hipMemcpyHostToDevice, st));
+  }
+  if (in->steps) ENV_HIP(e, hipMemcpyAsync(e->d.steps, in->steps, n * 4, hipMemcpyHostToDevice, st));
+  if (in->episode) ENV_HIP(e, hipMemcpyAsync(e->d.episode, in->episode, n * 4, hipMemcpyHostToDevice, st));
+  if (in->returns) ENV_HIP(e, hipMemcpyAsync(e->d.ret, in->returns, n * 4, hipMemcpyHostToDevice, st));
+  if (in->draws) ENV_HIP(e, hipMemcpyAsync(e->d.draws, in->draws, n * 4, hipMemcpyHostToDevice, st));
+  ENV_HIP(e, hipStreamSynchronize(st));      // the host arrays (and `phys` above) are free again when the call returns
+  return SACTD3_OK;
+}

@@ -1,0 +1,194 @@
+// The GPU-resident vector environments (include/sactd3_env.h): k_env_step<KIND>, k_env_reset<KIND>, k_env_sample_actions.
+// One thread per env, 256-thread blocks, plain C++ with vector stores.  No workgroup reads what another stores and there is
+// no global counter: every counter is a per-env word, so a step is exactly one launch and the kernels are launch-bound by
+// construction.
+//
+// Arithmetic: fp32, contraction off, ONE operation order -- the order of the expressions below, every product and sum
+// parenthesised as written.  envs.py (HostVecEnv) restates these lines in numpy float32 and tests/env_model.py in float64.
+// The physics is the textbook's: the torque-limited pendulum swing-up, and the cart-pole of Barto, Sutton & Anderson (1983)
+// with a continuous force.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "philox.h"
+
+#define SACTD3_STREAM_ENV 0x500u   // third counter word of every env draw; fourth word: 0 = episode start, 1 = random action
+
+#define ENV_PENDULUM 0
+#define ENV_CARTPOLE 1
+
+// per-env words, struct of arrays: element i belongs to env i
+struct EnvDev {
+  float* phys;                  // [4][n] physical state, component-major
+  int32_t* steps;               // steps taken in the running episode
+  uint32_t* episode;            // index of the running episode
+  float* ret;                   // running return
+  uint32_t* draws;              // random actions drawn
+  uint32_t* done_count;         // episodes finished
+  double* ret_sum;              // sum of their returns
+  unsigned long long* len_sum;  // sum of their lengths
+  float* last_ret;              // the last finished episode
+  int32_t* last_len;
+  float* first_ret;             // the first episode finished since the reset
+  int32_t* first_len;
+  uint32_t* bad;                // non-finite actions replaced
+  int n;
+};
+
+struct EnvOut {   // sactd3_env_out with the strides checked
+  float* obs; long long obs_ld;
+  float* final_obs; long long final_obs_ld;
+  float* reward; long long reward_ld;
+  uint8_t* terminated; long long terminated_ld;
+  uint8_t* truncated; long long truncated_ld;
+  uint8_t* ended; long long ended_ld;
+};
+
+template <int KIND> struct EnvTask;
+template <> struct EnvTask<ENV_PENDULUM> { static constexpr int OB = 3, AC = 1, NS = 2; static constexpr float BOUND = 2.0f; };
+template <> struct EnvTask<ENV_CARTPOLE> { static constexpr int OB = 4, AC = 1, NS = 4; static constexpr float BOUND = 1.0f; };
+
+#define ENV_PI      3.14159274f     // fl32(pi)
+#define ENV_TWO_PI  6.28318548f     // fl32(2 pi)
+#define ENV_INV_2PI 0.159154937f    // fl32(1 / (2 pi))
+
+#pragma clang fp contract(off)
+
+// x - 2 pi floor((x + pi) / (2 pi)): [-pi, pi) up to the roundings of its three operations; x unchanged (exactly) where the floor is 0
+__device__ __forceinline__ float env_angnorm(float x) {
+  const float k = floorf((x + ENV_PI) * ENV_INV_2PI);
+  return x - ENV_TWO_PI * k;
+}
+
+__device__ __forceinline__ float env_clamp(float x, float b) { return fminf(fmaxf(x, -b), b); }
+
+// the first state of episode `ep` of env i
+template <int KIND>
+__device__ __forceinline__ void env_first_state(uint64_t seed, uint32_t i, uint32_t ep, float s[4]) {
+  const Philox4 r = philox4x32_10(ep, i, SACTD3_STREAM_ENV, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const float u0 = philox_u01(r.v[0]), u1 = philox_u01(r.v[1]), u2 = philox_u01(r.v[2]), u3 = philox_u01(r.v[3]);
+  if (KIND == ENV_PENDULUM) {
+    s[0] = -ENV_PI + ENV_TWO_PI * u0;   // theta ~ U(-pi, pi)
+    s[1] = -1.0f + 2.0f * u1;           // omega ~ U(-1, 1)
+    s[2] = 0.0f; s[3] = 0.0f;
+  } else {
+    s[0] = -0.05f + 0.1f * u0; s[1] = -0.05f + 0.1f * u1; s[2] = -0.05f + 0.1f * u2; s[3] = -0.05f + 0.1f * u3;
+  }
+}
+
+template <int KIND>
+__device__ __forceinline__ void env_observe(const float s[4], float* row) {
+  if (KIND == ENV_PENDULUM) {
+    row[0] = cosf(s[0]); row[1] = sinf(s[0]); row[2] = s[1];
+  } else {
+    row[0] = s[0]; row[1] = s[1]; row[2] = s[2]; row[3] = s[3];
+  }
+}
+
+// one step of the physics: s -> s2, the reward, and whether s2 is terminal; `u` is the clamped, finite action
+template <int KIND>
+__device__ __forceinline__ void env_physics(const float s[4], float u, float s2[4], float& reward, bool& terminal) {
+  if (KIND == ENV_PENDULUM) {
+    const float th = s[0], w = s[1];
+    const float thn = env_angnorm(th);
+    const float cost = ((thn * thn) + (0.1f * (w * w))) + (0.001f * (u * u));
+    const float acc = (15.0f * sinf(th)) + (3.0f * u);
+    const float w2 = env_clamp(w + (acc * 0.05f), 8.0f);
+    s2[0] = env_angnorm(th + (0.05f * w2));
+    s2[1] = w2; s2[2] = 0.0f; s2[3] = 0.0f;
+    reward = -cost;
+    terminal = false;
+  } else {
+    const float x = s[0], xd = s[1], th = s[2], thd = s[3];
+    const float f = 10.0f * u;
+    const float c = cosf(th), sn = sinf(th);
+    const float temp = (f + ((0.05f * (thd * thd)) * sn)) / 1.1f;                 // (F + m l thd^2 sin) / (M + m)
+    const float den = 0.5f * (1.33333337f - ((0.1f * (c * c)) / 1.1f));           // l (4/3 - m cos^2 / (M + m))
+    const float thacc = ((9.8f * sn) - (c * temp)) / den;
+    const float xacc = temp - (((0.05f * thacc) * c) / 1.1f);
+    s2[0] = x + (0.02f * xd);
+    s2[1] = xd + (0.02f * xacc);
+    s2[2] = th + (0.02f * thd);
+    s2[3] = thd + (0.02f * thacc);
+    reward = 1.0f;
+    terminal = (fabsf(s2[0]) > 2.4f) || (fabsf(s2[2]) > 0.20943951f);
+  }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restrict__ actions, long long act_ld, EnvOut o, int horizon,
+                                                  uint64_t seed) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.n) return;
+  const size_t n = (size_t)d.n;
+  float a = actions[(size_t)i * act_ld];
+  const bool bad = !(fabsf(a) <= 3.40282347e38f);      // NaN or infinite (every finite float passes): never reaches the state
+  if (bad) a = 0.0f;
+  const float u = env_clamp(a, EnvTask<KIND>::BOUND);
+  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4];
+#pragma unroll
+  for (int j = 0; j < EnvTask<KIND>::NS; ++j) s[j] = d.phys[j * n + i];
+  float reward;
+  bool terminal;
+  env_physics<KIND>(s, u, s2, reward, terminal);
+  const int t = d.steps[i] + 1;
+  const float ret = d.ret[i] + reward;
+  const bool truncated = !terminal && t >= horizon;
+  const bool ended = terminal || truncated;
+  if (o.final_obs) env_observe<KIND>(s2, o.final_obs + (size_t)i * o.final_obs_ld);
+  if (o.reward) o.reward[(size_t)i * o.reward_ld] = reward;
+  if (o.terminated) o.terminated[(size_t)i * o.terminated_ld] = terminal ? 1 : 0;
+  if (o.truncated) o.truncated[(size_t)i * o.truncated_ld] = truncated ? 1 : 0;
+  if (o.ended) o.ended[(size_t)i * o.ended_ld] = ended ? 1 : 0;
+  if (bad) d.bad[i] += 1u;
+  if (ended) {
+    const uint32_t ep = d.episode[i] + 1u;
+    const uint32_t done = d.done_count[i];
+    if (done == 0u) { d.first_ret[i] = ret; d.first_len[i] = t; }
+    d.done_count[i] = done + 1u;
+    d.ret_sum[i] += (double)ret;
+    d.len_sum[i] += (unsigned long long)t;
+    d.last_ret[i] = ret;
+    d.last_len[i] = t;
+    d.episode[i] = ep;
+    env_first_state<KIND>(seed, (uint32_t)i, ep, s2);
+    d.steps[i] = 0;
+    d.ret[i] = 0.0f;
+  } else {
+    d.steps[i] = t;
+    d.ret[i] = ret;
+  }
+#pragma unroll
+  for (int j = 0; j < EnvTask<KIND>::NS; ++j) d.phys[j * n + i] = s2[j];
+  env_observe<KIND>(s2, o.obs + (size_t)i * o.obs_ld);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_env_reset(EnvDev d, float* __restrict__ obs, long long obs_ld, uint64_t seed) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.n) return;
+  const size_t n = (size_t)d.n;
+  float s[4];
+  env_first_state<KIND>(seed, (uint32_t)i, 0u, s);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) d.phys[j * n + i] = s[j];
+  d.steps[i] = 0; d.episode[i] = 0u; d.ret[i] = 0.0f; d.draws[i] = 0u;
+  d.done_count[i] = 0u; d.ret_sum[i] = 0.0; d.len_sum[i] = 0ull; d.last_ret[i] = 0.0f; d.last_len[i] = 0; d.first_ret[i] = 0.0f; d.first_len[i] = 0; d.bad[i] = 0u;
+  if (obs) env_observe<KIND>(s, obs + (size_t)i * obs_ld);
+}
+
+// ac_dim <= 4: dimension j of the draw takes word j
+__global__ __launch_bounds__(256) void k_env_sample_actions(EnvDev d, float* __restrict__ actions, long long act_ld, int ac_dim, float lo,
+                                                            float span, uint64_t seed) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.n) return;
+  const uint32_t j = d.draws[i];
+  const Philox4 r = philox4x32_10(j, (uint32_t)i, SACTD3_STREAM_ENV, 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
+  float* row = actions + (size_t)i * act_ld;
+  row[0] = lo + span * philox_u01(r.v[0]);
+  if (ac_dim > 1) row[1] = lo + span * philox_u01(r.v[1]);
+  if (ac_dim > 2) row[2] = lo + span * philox_u01(r.v[2]);
+  if (ac_dim > 3) row[3] = lo + span * philox_u01(r.v[3]);
+  d.draws[i] = j + 1u;
+}

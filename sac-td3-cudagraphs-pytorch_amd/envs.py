@@ -1,0 +1,406 @@
+"""Two real continuous-control tasks for the engine to train on, on the GPU and on the host (include/sactd3_env.h):
+
+  NativeVecEnv    the vector env that lives on the GPU (csrc/env_kernels.h): `step` is ONE kernel launch on the current torch stream,
+                  every array a device tensor, no host draw, no host wait, no torch arithmetic -- the protocol `loop.DeviceRollout`
+                  consumes (`loop.train(device_env=True)`)
+  HostVecEnv      the same two tasks in numpy float32, in the kernel's operation order and with the same Philox resets, with the
+                  gymnasium-0.29 protocol of `loop.SyntheticVecEnv` -- for `loop.Rollout`, `loop.Evaluator` and `loop.evaluate`
+  greedy_returns  evaluation with one host wait: a vector env stepped in lock-step with the agent's greedy action for one horizon
+  device_episodes the same as an episode generator, to stand in for `loop.Evaluator.ep_gen`
+
+The tasks (textbook physics: the torque-limited pendulum swing-up; the cart-pole of Barto, Sutton & Anderson 1983 with a continuous
+force) and the random streams are stated in include/sactd3_env.h.  The host twin computes, bit for bit, what the kernel computes
+except through sin / cos: the reset states, the random actions, the flags' rules and the fp32 accumulation of the returns are the
+same bits."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Dict, Generator, Optional
+
+import numpy as np
+
+from . import _lib
+
+KINDS = {"pendulum": _lib.ENV_PENDULUM, "cartpole": _lib.ENV_CARTPOLE}
+#        kind -> (ob_dim, ac_dim, action bound, default horizon, floats of physical state)
+SPECS = {_lib.ENV_PENDULUM: (3, 1, 2.0, 200, 2), _lib.ENV_CARTPOLE: (4, 1, 1.0, 200, 4)}
+STREAM_ENV = 0x500          # csrc/env_kernels.h: SACTD3_STREAM_ENV
+F = np.float32
+PI, TWO_PI, INV_2PI = F(3.14159274), F(6.28318548), F(0.159154937)       # csrc/env_kernels.h: ENV_PI, ENV_TWO_PI, ENV_INV_2PI
+X_LIMIT, THETA_LIMIT = F(2.4), F(0.20943951)
+
+
+def kind_of(kind) -> int:
+    if isinstance(kind, str):
+        if kind.lower() not in KINDS:
+            raise ValueError(f"unknown env kind {kind!r} (one of {sorted(KINDS)})")
+        return KINDS[kind.lower()]
+    if int(kind) not in SPECS:
+        raise ValueError(f"unknown env kind {kind!r}")
+    return int(kind)
+
+
+# ---------------------------------------------------------------------------------------------------- Philox4x32-10 in numpy
+def philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
+    """csrc/philox.h: philox4x32_10, vectorised over the counter words -> four uint32 arrays"""
+    m = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(x, np.uint64) & m for x in np.broadcast_arrays(c0, c1, c2, c3)]
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        n0 = (p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0)
+        n2 = (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1)
+        c = [n0, p1 & m, n2, p0 & m]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return [x.astype(np.uint32) for x in c]
+
+
+def u01(x):
+    """csrc/philox.h: philox_u01 in numpy float32"""
+    return ((np.asarray(x, np.uint32) >> np.uint32(8)).astype(F) + F(0.5)) * F(1.0 / 16777216.0)
+
+
+def _words(seed: int, first, env_index, which: int):
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return philox4x32_10(first, env_index, STREAM_ENV, which, seed & 0xFFFFFFFF, seed >> 32)
+
+
+def first_states(kind: int, seed: int, env_index, episode) -> np.ndarray:
+    """[n, 4] float32: the state in which episode `episode[k]` of env `env_index[k]` starts -- a pure function of (seed, env, episode)"""
+    u = np.stack([u01(w) for w in _words(seed, np.asarray(episode), np.asarray(env_index), 0)], 1)
+    s = np.zeros(u.shape, F)
+    if kind == _lib.ENV_PENDULUM:
+        s[:, 0] = -PI + TWO_PI * u[:, 0]
+        s[:, 1] = F(-1.0) + F(2.0) * u[:, 1]
+    else:
+        s[:] = F(-0.05) + F(0.1) * u
+    return s
+
+
+def random_actions(kind: int, seed: int, env_index, draw) -> np.ndarray:
+    """[n, 1] float32: random action number `draw[k]` of env `env_index[k]`, uniform inside the bounds"""
+    bound = F(SPECS[kind][2])
+    w = _words(seed, np.asarray(draw), np.asarray(env_index), 1)
+    return (-bound + (bound - (-bound)) * u01(w[0])).astype(F).reshape(-1, 1)
+
+
+# ---------------------------------------------------------------------------------------------------- the physics, float32
+def _angnorm(x):
+    return x - TWO_PI * np.floor((x + PI) * INV_2PI)
+
+
+def physics(kind: int, s: np.ndarray, u: np.ndarray):
+    """csrc/env_kernels.h: env_physics line for line in numpy float32.  s [n, 4], u [n] clamped and finite -> (s2 [n, 4], reward [n],
+    terminal [n])"""
+    assert s.dtype == F and u.dtype == F
+    s2 = np.zeros_like(s)
+    if kind == _lib.ENV_PENDULUM:
+        th, w = s[:, 0], s[:, 1]
+        thn = _angnorm(th)
+        cost = ((thn * thn) + (F(0.1) * (w * w))) + (F(0.001) * (u * u))
+        acc = (F(15.0) * np.sin(th)) + (F(3.0) * u)
+        w2 = np.minimum(np.maximum(w + (acc * F(0.05)), F(-8.0)), F(8.0))
+        s2[:, 0] = _angnorm(th + (F(0.05) * w2))
+        s2[:, 1] = w2
+        return s2, -cost, np.zeros(len(u), bool)
+    x, xd, th, thd = s[:, 0], s[:, 1], s[:, 2], s[:, 3]
+    f = F(10.0) * u
+    c, sn = np.cos(th), np.sin(th)
+    temp = (f + ((F(0.05) * (thd * thd)) * sn)) / F(1.1)
+    den = F(0.5) * (F(1.33333337) - ((F(0.1) * (c * c)) / F(1.1)))
+    thacc = ((F(9.8) * sn) - (c * temp)) / den
+    xacc = temp - (((F(0.05) * thacc) * c) / F(1.1))
+    s2[:, 0] = x + (F(0.02) * xd)
+    s2[:, 1] = xd + (F(0.02) * xacc)
+    s2[:, 2] = th + (F(0.02) * thd)
+    s2[:, 3] = thd + (F(0.02) * thacc)
+    assert s2.dtype == F
+    return s2, np.ones(len(u), F), (np.abs(s2[:, 0]) > X_LIMIT) | (np.abs(s2[:, 2]) > THETA_LIMIT)
+
+
+def observe(kind: int, s: np.ndarray) -> np.ndarray:
+    if kind == _lib.ENV_PENDULUM:
+        return np.stack([np.cos(s[:, 0]), np.sin(s[:, 0]), s[:, 1]], 1).astype(F)
+    return s.astype(F).copy()
+
+
+def clean_actions(kind: int, actions, n: int):
+    """-> (u [n] float32 clamped, bad [n] bool): a NaN or infinite action is replaced by 0"""
+    a = np.asarray(actions, F).reshape(n, -1)[:, 0]
+    bad = ~np.isfinite(a)
+    bound = F(SPECS[kind][2])
+    return np.minimum(np.maximum(np.where(bad, F(0.0), a), -bound), bound).astype(F), bad
+
+
+# ---------------------------------------------------------------------------------------------------- the host twin
+class _HostBox:
+    def __init__(self, env):
+        self._env = env
+        bound = SPECS[env.kind][2]
+        self.low, self.high = np.full(SPECS[env.kind][1], -bound, F), np.full(SPECS[env.kind][1], bound, F)
+
+    def sample(self):
+        e = self._env
+        out = random_actions(e.kind, e.seed, np.arange(e.n), e.draws)
+        e.draws = e.draws + np.uint32(1)
+        return out
+
+
+class HostVecEnv:
+    """The two tasks on the host, float32 numpy in the kernel's operation order, with gymnasium-0.29 autoreset semantics as
+    `loop.SyntheticVecEnv` has them: on termination or truncation `infos["final_observation"][k]` (an object array) holds the
+    observation the step arrived at, `infos["final_info"][k]["episode"]` its length `l` and return `r`, and the returned observation
+    is the next episode's first one.  Episode k of env i starts where it starts on the GPU (the same Philox draw)."""
+
+    def __init__(self, kind, num_envs: int, seed: int = 0, horizon: Optional[int] = None):
+        self.kind = kind_of(kind)
+        self.o, self.a, self.bound, default_horizon, _ = SPECS[self.kind]
+        self.n = self.num_envs = int(num_envs)
+        if self.n < 1:
+            raise ValueError("num_envs must be >= 1")
+        self.horizon = int(horizon) if horizon else default_horizon
+        self.seed = int(seed)
+        self.action_space = _HostBox(self)
+        self.reset(seed=self.seed)
+
+    def reset(self, seed=None):
+        if seed is not None:
+            self.seed = int(seed)
+        n = self.n
+        self.s = first_states(self.kind, self.seed, np.arange(n), np.zeros(n, np.uint32))
+        self.t = np.zeros(n, np.int32)
+        self.ep = np.zeros(n, np.uint32)
+        self.ret = np.zeros(n, F)
+        self.draws = np.zeros(n, np.uint32)
+        self._done, self._bad = np.zeros(n, np.int64), 0
+        self._ret_sum, self._len_sum = 0.0, 0
+        self._last_ret, self._last_len = np.zeros(n, F), np.zeros(n, np.int32)
+        self._first_ret, self._first_len = np.zeros(n, F), np.zeros(n, np.int32)
+        return observe(self.kind, self.s), {}
+
+    def step(self, actions):
+        n = self.n
+        u, bad = clean_actions(self.kind, actions, n)
+        self._bad += int(bad.sum())
+        s2, rew, term = physics(self.kind, self.s, u)
+        self.t = self.t + np.int32(1)
+        self.ret = (self.ret + rew).astype(F)
+        trunc = (self.t >= self.horizon) & ~term
+        ended = term | trunc
+        infos: Dict[str, Any] = {}
+        if ended.any():
+            final = observe(self.kind, s2)
+            infos["final_observation"] = np.array([final[k].copy() if ended[k] else None for k in range(n)], dtype=object)
+            infos["final_info"] = np.array([{"episode": {"l": np.array([self.t[k]]), "r": np.array([self.ret[k]])}} if ended[k] else None
+                                            for k in range(n)], dtype=object)
+            at = np.flatnonzero(ended)
+            new = at[self._done[at] == 0]                     # the first episode an env finishes since the reset
+            self._first_ret[new], self._first_len[new] = self.ret[new], self.t[new]
+            self._done[at] += 1
+            self._ret_sum += float(self.ret[at].astype(np.float64).sum())
+            self._len_sum += int(self.t[at].sum())
+            self._last_ret[at], self._last_len[at] = self.ret[at], self.t[at]
+            self.ep[at] += np.uint32(1)
+            s2[at] = first_states(self.kind, self.seed, at, self.ep[at])
+            self.t[at] = 0
+            self.ret[at] = 0.0
+        self.s = s2
+        return observe(self.kind, self.s), rew.astype(F), term, trunc, infos
+
+    def episode_stats(self) -> Dict[str, Any]:
+        return {"episodes": int(self._done.sum()), "return_sum": self._ret_sum, "length_sum": self._len_sum, "bad_actions": self._bad,
+                "last_return": self._last_ret.copy(), "last_length": self._last_len.copy(), "env_episodes": self._done.copy(),
+                "first_return": self._first_ret.copy(), "first_length": self._first_len.copy()}
+
+    def state(self) -> Dict[str, np.ndarray]:
+        return {"phys": self.s.copy(), "steps": self.t.copy(), "episode": self.ep.copy(), "returns": self.ret.copy(), "draws": self.draws.copy()}
+
+    def set_state(self, state) -> None:
+        _check_state(state, self.n)
+        for key, name, dt in (("phys", "s", F), ("steps", "t", np.int32), ("episode", "ep", np.uint32), ("returns", "ret", F), ("draws", "draws", np.uint32)):
+            if key in state:
+                setattr(self, name, np.array(state[key], dt).reshape(getattr(self, name).shape))
+
+
+_STATE_KEYS = {"phys": (F, _lib.ENV_STATE_DIM), "steps": (np.int32, 1), "episode": (np.uint32, 1), "returns": (F, 1), "draws": (np.uint32, 1)}
+
+
+def _check_state(state, n: int) -> None:
+    unknown = set(state) - set(_STATE_KEYS)
+    if unknown:
+        raise ValueError(f"set_state: unknown keys {sorted(unknown)}")
+    for k, v in state.items():
+        if np.asarray(v).size != n * _STATE_KEYS[k][1]:
+            raise ValueError(f"set_state: {k} must have {n} x {_STATE_KEYS[k][1]} elements")
+    if "phys" in state and not np.isfinite(np.asarray(state["phys"], np.float64)).all():
+        raise ValueError("set_state: a physical state is not finite")
+    if "steps" in state and (np.asarray(state["steps"]) < 0).any():
+        raise ValueError("set_state: a step count is negative")
+
+
+# ---------------------------------------------------------------------------------------------------- the env on the GPU
+class _DeviceBox:
+    def __init__(self, env):
+        self._env = env
+        self.low, self.high = np.full(env.a, -env.bound, F), np.full(env.a, env.bound, F)
+
+    def sample(self):
+        """[n, ac_dim] device tensor drawn by the device (sactd3_env_sample_actions): no host draw, no upload"""
+        e = self._env
+        out = e._empty((e.n, e.a), e._t.float32)
+        e._call("sactd3_env_sample_actions", out.data_ptr(), out.stride(0), e._stream())
+        return out
+
+
+class NativeVecEnv:
+    """The vector env on the GPU (include/sactd3_env.h), with the protocol `loop.DeviceRollout` consumes:
+      reset(seed) -> (obs [n, o], {});   step(actions [n, a]) -> (obs, rewards [n], terminations [n], truncations [n], infos)
+      infos["final_observation"]: [n, o], what the step arrived at BEFORE any reset, for every env; infos["_final_observation"]: [n]
+      bool, the envs that ended;   action_space.sample() -> [n, a] drawn on the device.
+    A step is one kernel launch on the current torch stream of the env's device.  Its outputs are FRESH tensors of torch's caching
+    allocator on that stream -- never a buffer an earlier step handed out: `DeviceRollout.advance` still holds the previous
+    observations while the next step runs and `rb.extend` reads them afterwards.  Nothing here reads a device value on the host;
+    `episode_stats()`, `state()` and `set_state()` do, and wait."""
+
+    def __init__(self, kind, num_envs: int, seed: int = 0, device: Any = None, horizon: Optional[int] = None):
+        import torch
+        self._t = torch
+        self.kind = kind_of(kind)
+        self.n = self.num_envs = int(num_envs)
+        self.seed = int(seed)
+        self.lib = _lib.load_library()
+        if device is not None:
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise ValueError(f"NativeVecEnv lives on a GPU, not on {self.device} (HostVecEnv is the host twin)")
+            if self.device.index is None:
+                self.device = torch.device("cuda", torch.cuda.current_device())
+        else:
+            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        cfg = _lib.CEnvConfig(self.kind, self.n, int(horizon or 0), int(self.device.index), self.seed & 0xFFFFFFFFFFFFFFFF)
+        h = C.c_void_p()
+        rc = self.lib.sactd3_env_create(C.byref(cfg), C.byref(h))
+        if rc != 0:
+            raise _lib.EngineError(f"sactd3_env_create failed ({rc}): {self.lib.sactd3_env_last_error(None).decode()}")
+        self._h = h
+        info = _lib.CEnvInfo()
+        self._call("sactd3_env_spec", C.byref(info))
+        self.o, self.a, self.horizon, self.bound = int(info.ob_dim), int(info.ac_dim), int(info.horizon), float(info.max_ac)
+        self.action_space = _DeviceBox(self)
+
+    # -- plumbing
+    def _call(self, name, *args):
+        if self._h is None:
+            raise _lib.EngineError(f"{name}: the env is closed")
+        rc = getattr(self.lib, name)(self._h, *args)
+        if rc != 0:
+            raise _lib.EngineError(f"{name} failed ({rc}): {self.lib.sactd3_env_last_error(self._h).decode()}")
+
+    def _stream(self) -> int:
+        return int(self._t.cuda.current_stream(self.device).cuda_stream)
+
+    def _empty(self, shape, dtype):
+        return self._t.empty(shape, dtype=dtype, device=self.device)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            self.lib.sactd3_env_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    # -- the protocol
+    def reset(self, seed=None):
+        if seed is not None:
+            self.seed = int(seed)
+        obs = self._empty((self.n, self.o), self._t.float32)
+        self._call("sactd3_env_reset", self.seed & 0xFFFFFFFFFFFFFFFF, obs.data_ptr(), obs.stride(0), self._stream())
+        return obs, {}
+
+    def step(self, actions):
+        t, n = self._t, self.n
+        a = actions
+        if not (t.is_tensor(a) and a.device == self.device and a.dtype == t.float32 and a.dim() == 2 and a.shape == (n, self.a)
+                and a.stride(1) == 1 and a.stride(0) >= self.a):
+            a = t.as_tensor(a, dtype=t.float32, device=self.device).reshape(n, self.a).contiguous()
+        obs, final = self._empty((n, self.o), t.float32), self._empty((n, self.o), t.float32)
+        rew = self._empty((n,), t.float32)
+        flags = self._empty((3, n), t.bool)                   # one byte each: the kernel writes 0 / 1
+        out = _lib.CEnvOut(obs.data_ptr(), obs.stride(0), final.data_ptr(), final.stride(0), rew.data_ptr(), 1,
+                           flags[0].data_ptr(), 1, flags[1].data_ptr(), 1, flags[2].data_ptr(), 1)
+        self._call("sactd3_env_step", a.data_ptr(), a.stride(0), C.byref(out), self._stream())
+        return obs, rew, flags[0], flags[1], {"final_observation": final, "_final_observation": flags[2]}
+
+    # -- bookkeeping: these wait for the device
+    def episode_stats(self) -> Dict[str, Any]:
+        last_ret, last_len, eps = np.zeros(self.n, F), np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
+        first_ret, first_len = np.zeros(self.n, F), np.zeros(self.n, np.int32)
+        st = _lib.CEnvStats(0, 0.0, 0, 0, last_ret.ctypes.data, last_len.ctypes.data, eps.ctypes.data, first_ret.ctypes.data, first_len.ctypes.data)
+        self._call("sactd3_env_episode_stats", C.byref(st), self._stream())
+        return {"episodes": int(st.episodes), "return_sum": float(st.return_sum), "length_sum": int(st.length_sum),
+                "bad_actions": int(st.bad_actions), "last_return": last_ret, "last_length": last_len, "env_episodes": eps,
+                "first_return": first_ret, "first_length": first_len}
+
+    def state(self) -> Dict[str, np.ndarray]:
+        out = {k: np.zeros((self.n, w) if w > 1 else self.n, dt) for k, (dt, w) in _STATE_KEYS.items()}
+        st = _lib.CEnvState(*[out[k].ctypes.data for k in ("phys", "steps", "episode", "returns", "draws")])
+        self._call("sactd3_env_get_state", C.byref(st), self._stream())
+        return out
+
+    def set_state(self, state) -> None:
+        _check_state(state, self.n)
+        keep = {k: np.ascontiguousarray(np.asarray(v, _STATE_KEYS[k][0]).reshape(-1)) for k, v in state.items()}
+        st = _lib.CEnvState(*[keep[k].ctypes.data if k in keep else None for k in ("phys", "steps", "episode", "returns", "draws")])
+        self._call("sactd3_env_set_state", C.byref(st), self._stream())
+
+
+# ---------------------------------------------------------------------------------------------------- evaluation with one host wait
+def _greedy_actions(env, agent, obs):
+    """the agent's greedy action for every row of `obs`, in calls of at most the engine's max_envs rows"""
+    n = env.num_envs
+    limit = int(getattr(getattr(getattr(agent, "engine", None), "cfg", None), "max_envs", n)) or n
+    if isinstance(env, NativeVecEnv):
+        if n <= limit:
+            return agent.predict_device({"observations": obs}, explore=False)
+        out = env._empty((n, env.a), env._t.float32)
+        for lo in range(0, n, limit):
+            agent.predict_device({"observations": obs[lo:lo + limit]}, explore=False, out=out[lo:lo + limit])
+        return out
+    return np.concatenate([np.asarray(agent.predict({"observations": obs[lo:lo + limit]}, explore=False), F).reshape(-1, env.a)
+                           for lo in range(0, n, limit)])
+
+
+def greedy_returns(env, agent, episodes: int, seed: Optional[int] = None) -> Dict[str, Any]:
+    """Greedy evaluation on `episodes` envs in lock-step: `env` (a NativeVecEnv or a HostVecEnv with num_envs == episodes) is reset
+    (`seed`: its own if None) and stepped for one horizon with `agent.predict_device(explore=False)` (`agent.predict` on the host
+    twin); `episode_stats()` is read once at the end -- on the GPU that is the evaluation's only host wait.  Every env finishes its
+    FIRST episode inside that window (the time limit at the latest), and that one counts: one episode per env, whatever their lengths,
+    which is the statistic `loop.episode` reports one env at a time.  An env that terminates early goes on with further episodes;
+    they are not counted.
+    -> {"return", "length": the means over the envs' first episodes (float64 of the fp32 figures, in env order), "episodes": how many,
+    "returns", "lengths": per env, "bad_actions"}"""
+    if int(episodes) != env.num_envs:
+        raise ValueError(f"greedy_returns: the env has {env.num_envs} envs, {episodes} episodes were asked for")
+    obs, _ = env.reset(seed=env.seed if seed is None else seed)
+    for _ in range(env.horizon):
+        obs = env.step(_greedy_actions(env, agent, obs))[0]
+    st = env.episode_stats()
+    if not (st["env_episodes"] >= 1).all():
+        raise RuntimeError("greedy_returns: an env finished no episode within one horizon")      # (the time limit makes this impossible)
+    return {"return": float(st["first_return"].astype(np.float64).mean()), "length": float(st["first_length"].astype(np.float64).mean()),
+            "episodes": env.num_envs, "returns": st["first_return"], "lengths": st["first_length"], "bad_actions": st["bad_actions"]}
+
+
+def device_episodes(env, agent, seed: int) -> Generator[Dict[str, np.ndarray], None, None]:
+    """An episode generator with the yield of `loop.episode` ({"length", "return"} per `next()`), served by `greedy_returns`: one
+    window of env.num_envs episodes per refill, re-seeded as `loop.episode` re-seeds.  Assign it to `loop.Evaluator.ep_gen` (sized
+    num_envs == cfg.eval_steps: one window per evaluation) to evaluate without a host env step."""
+    rng = np.random.default_rng(seed)
+    while True:
+        got = greedy_returns(env, agent, env.num_envs, seed=seed + rng.integers(2 ** 32 - 1, size=1).item())
+        for k in range(env.num_envs):
+            yield {"length": np.array(float(got["lengths"][k])), "return": np.array(float(got["returns"][k]))}

@@ -30,7 +30,9 @@ ENV_BUNDLES = {
     "low": ["Hopper-v4", "Pusher-v4"],
     "medium": ["HalfCheetah-v4", "Walker2d-v4", "Ant-v4"],
     "high": ["Humanoid-v4", "HumanoidStandup-v4"],
+    "native": ["Pendulum-native", "CartPole-native"],      # the two tasks this package simulates itself (envs.py)
 }
+NATIVE_ENVS = {"Pendulum-native": "pendulum", "CartPole-native": "cartpole"}      # env id -> envs.py kind
 
 
 def sweep_jobs(env_bundle: str, num_seeds: int) -> List[Tuple[str, int]]:
@@ -181,7 +183,19 @@ def _host(x):
 ENV_DIMS = {   # (ob_dim, ac_dim, action bound) of the Gymnasium MuJoCo -v4 tasks named by the bundles (public task specs)
     "Hopper-v4": (11, 3, 1.0), "Pusher-v4": (23, 7, 2.0), "HalfCheetah-v4": (17, 6, 1.0), "Walker2d-v4": (17, 6, 1.0),
     "Ant-v4": (27, 8, 1.0), "Humanoid-v4": (376, 17, 0.4), "HumanoidStandup-v4": (376, 17, 0.4),
+    "Pendulum-native": (3, 1, 2.0), "CartPole-native": (4, 1, 1.0),      # include/sactd3_env.h
 }
+
+
+def env_plan(env_id: str, device_env: bool, has_factory: bool = False):
+    """Which env classes a job uses, decided without touching a GPU: -> dict(train=, eval=) of class names.  The -native ids are
+    simulated by this package: `envs.HostVecEnv` trains and evaluates on the host, and with --device_env `envs.NativeVecEnv` does both
+    on the GPU (evaluation through `envs.device_episodes`: no host env step anywhere in the job).  Every other id is what it was: the
+    caller's factory or the synthetic stand-in, and the synthetic device env for training with --device_env."""
+    if env_id in NATIVE_ENVS and not has_factory:
+        return dict(train="NativeVecEnv", eval="NativeVecEnv") if device_env else dict(train="HostVecEnv", eval="HostVecEnv")
+    base = "factory" if has_factory else "SyntheticVecEnv"
+    return dict(train="SyntheticDeviceVecEnv" if device_env else base, eval=base)
 DEFAULTS = {   # tasks/defaults/sac.yml:1-48 (td3.yml differs in the keys listed under "td3")
     "sac": dict(num_envs=4, action_repeat=1, measure_burnin=3, num_timesteps=10_000_000, learning_starts=5000, eval_steps=10,
                 eval_every=10_000, layer_norm=True, actor_lr=3e-4, qnets_lr=1e-3, clip_norm=0.0, segment_len=1, batch_size=256,
@@ -278,13 +292,22 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
         raise ValueError("policy_stats needs algo sac: TD3's deterministic actor has no log-probability, entropy or log-std to report")
     cfg = job_config(algo, env_id, seed, **over)
     o, a, bound = ENV_DIMS[env_id]
-    if env_factory is None:   # no simulator in this image: the synthetic vector env has the task's shapes and the gymnasium protocol
+    native = env_id in NATIVE_ENVS and env_factory is None      # the two tasks this package simulates itself (env_plan)
+    on_gpu = native and device_env                              # ... with --device_env on the GPU, training AND evaluation: no host env
+    dev = torch.device("cuda", device_index)
+    if native:
+        from . import envs
+        make = lambda n: envs.HostVecEnv(NATIVE_ENVS[env_id], n, seed=seed)      # the numpy twin on the host
+    elif env_factory is None:   # no MuJoCo in this image: the synthetic vector env has the task's shapes and the gymnasium protocol
         make = lambda n: loop.SyntheticVecEnv(o, a, n, horizon=200, term_at=6.0, bound=bound)
     else:
         make = lambda n: env_factory(env_id, n, seed)
-    env, eval_env = make(cfg.num_envs), make(1)
-    if device_env:            # the training env lives on the GPU (loop.DeviceRollout); evaluation keeps its host env and predict()
-        env = loop.SyntheticDeviceVecEnv(o, a, cfg.num_envs, horizon=200, term_at=6.0, bound=bound, device=torch.device("cuda", device_index))
+    if on_gpu:
+        env, eval_env = envs.NativeVecEnv(NATIVE_ENVS[env_id], cfg.num_envs, seed=seed, device=dev), None
+    else:
+        env, eval_env = make(cfg.num_envs), make(1)
+    if device_env and not native:   # the training env lives on the GPU (loop.DeviceRollout); evaluation keeps its host env and predict()
+        env = loop.SyntheticDeviceVecEnv(o, a, cfg.num_envs, horizon=200, term_at=6.0, bound=bound, device=dev)
     torch.manual_seed(seed)                                           # main.py:145-146
     rb = ReplayBuffer(cfg.rb_capacity)
     agent = Agent({"ob_shape": (o,), "ac_shape": (a,)}, np.full(a, -bound, np.float32), np.full(a, bound, np.float32),
@@ -292,6 +315,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     run_dir = Path(out_dir) / f"{env_id}__{algo}__seed{seed:02d}"
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
+    if on_gpu:                # cfg.eval_steps greedy episodes per evaluation, in lock-step on the GPU, read with one host wait
+        ev.ep_gen = envs.device_episodes(envs.NativeVecEnv(NATIVE_ENVS[env_id], cfg.eval_steps, seed=seed, device=dev), agent, seed)
     t0 = time.time()
     # --prioritized: the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4), call by call
     # --n_step N > 1: n-step returns chained by the engine, call by call as well
@@ -376,7 +401,8 @@ def main(argv=None) -> int:
     ap.add_argument("--overlap_acting", action="store_true",
                     help="compute the next action on the engine's acting stream while the iteration's update runs (loop.train overlap=True)")
     ap.add_argument("--device_env", action="store_true",
-                    help="train on the GPU-resident synthetic vector env: observations and actions never leave the device (loop.train device_env=True)")
+                    help="train on the GPU-resident vector env (the synthetic one; for the -native ids envs.NativeVecEnv, which also evaluates "
+                         "there): observations and actions never leave the device (loop.train device_env=True)")
     ap.add_argument("--prioritized", action="store_true",
                     help="proportional prioritised replay kept by the engine (loop.train prioritized=...; the iteration is issued call by call)")
     ap.add_argument("--one_launch", action="store_true",
