@@ -116,6 +116,8 @@ int sactd3_create(const sactd3_config* cfg, const float* min_ac, const float* ma
 void sactd3_destroy(sactd3_engine* e);
 const char* sactd3_last_error(const sactd3_engine* e);
 int sactd3_abi_version(void);
+/* the configuration the engine was created with (dims, max_envs, device_id, ...): for code that is handed an engine it did not make */
+int sactd3_get_config(const sactd3_engine* e, sactd3_config* out);
 
 /* ---- parameters / optimiser state: Agent.save / load_from_disk (agents/agent.py:333-371) ---- */
 int64_t sactd3_param_count(const sactd3_engine* e, int which);            /* floats exchanged for `which` */
@@ -159,6 +161,13 @@ typedef struct sactd3_device_fields {     /* device pointers; *_ld = row stride 
 #define SACTD3_SRC_ORDERED 1
 /* rb.extend (orchestrator.py:100-113) of n >= 0 rows from device fields: same ring state as sactd3_rb_extend of the same rows. */
 int sactd3_rb_extend_fields_device(sactd3_engine* e, const sactd3_device_fields* f, int n, void* producer_stream, int flags);
+/* sactd3_rb_extend_device for a slab whose PRODUCER is still running: n >= 0 records already packed (sactd3_rb_layout) in the memory of
+ * the engine's device, 16-byte aligned -- what a GPU-resident env writes per step (include/sactd3_rollout.h).  The same launches, the
+ * same ring-region chunking, the same ring state (pinned prefix, priorities) as sactd3_rb_extend_device of the same records; flags &
+ * SACTD3_SRC_ORDERED brackets them with the two events described above, so the caller neither synchronises nor keeps the slab beyond
+ * its own stream's order.  n == 0 is a no-op and inserts no events.  SACTD3_EINVAL: a NULL or misaligned pointer, one that is not
+ * memory of the engine's device, n < 0, an unknown flag; nothing is launched then. */
+int sactd3_rb_extend_records_device(sactd3_engine* e, const float* records, int n, void* producer_stream, int flags /* SACTD3_SRC_ORDERED */);
 /* a caller-owned device batch (agents/agent.py:183,245), n == batch_size: same batch slot, bit for bit, as sactd3_load_batch. */
 int sactd3_load_batch_device(sactd3_engine* e, const sactd3_device_fields* f, int n, void* producer_stream, int flags);
 /* Both: SACTD3_EINVAL for a NULL field, a stride below the field's width, a pointer that is not memory of the engine's device, n out

@@ -15,7 +15,7 @@ SITE_CRITIC, SITE_ACTOR0, SITE_ACTOR1, SITE_ALPHA0, SITE_ALPHA1, SITE_PREDICT = 
 NUM_METRICS = 8
 M_QF_LOSS, M_ACTOR_LOSS, M_ALPHA_LOSS, M_ALPHA, M_BC_LOSS, M_BC_LAMBDA = range(6)   # metrics slots (SACTD3_M_*); the last two: TD3+BC only
 ACT_AFTER_ALL = 1   # sactd3_predict_begin flags
-SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_load_batch_device / sactd3_predict_device / sactd3_qvalues_device / sactd3_rb_sample_indices_device / sactd3_batch_weights_device flags
+SRC_ORDERED = 1     # sactd3_rb_extend_fields_device / sactd3_rb_extend_records_device / sactd3_load_batch_device / sactd3_predict_device / sactd3_qvalues_device / sactd3_rb_sample_indices_device / sactd3_batch_weights_device flags
 DST_ORDERED = 1     # sactd3_read_batch_device / sactd3_rb_read_rows_device / sactd3_td_errors_device flags (the same bit, the same two events)
 Q_ONLINE, Q_TARGET = 0, 1   # sactd3_qvalues / sactd3_qvalues_device `which`
 PI_ONLINE, PI_TARGET = 0, 1   # sactd3_policy / sactd3_policy_device `which` (the target actor: TD3 only)
@@ -47,6 +47,7 @@ SYMBOLS = [
     "sactd3_set_bc", "sactd3_get_bc",
     "sactd3_rb_pin", "sactd3_rb_pinned", "sactd3_rb_set_mix", "sactd3_rb_sample_mixed", "sactd3_mix_stats",
     "sactd3_policy_device", "sactd3_policy", "sactd3_policy_stats",
+    "sactd3_get_config", "sactd3_rb_extend_records_device",
 ]
 
 # every symbol include/sactd3_env.h declares (tests/test_env_host.py checks the header against this list)
@@ -56,6 +57,13 @@ ENV_SYMBOLS = [
 ]
 ENV_PENDULUM, ENV_CARTPOLE = 0, 1   # sactd3_env_config.kind
 ENV_STATE_DIM = 4                   # SACTD3_ENV_STATE_DIM
+
+# every symbol include/sactd3_rollout.h declares (tests/test_native_rollout_host.py checks the header against this list)
+ROLLOUT_SYMBOLS = [
+    "sactd3_rollout_env_step", "sactd3_rollout_create", "sactd3_rollout_destroy", "sactd3_rollout_last_error", "sactd3_rollout_reset",
+    "sactd3_rollout_choose", "sactd3_rollout_advance", "sactd3_rollout_stats",
+]
+ROLLOUT_RANDOM, ROLLOUT_EXPLORE, ROLLOUT_EXPLOIT, ROLLOUT_REPEAT = range(4)   # sactd3_rollout_choose `mode` (SACTD3_ROLLOUT_*)
 
 
 class EngineError(RuntimeError):
@@ -121,6 +129,16 @@ class CEnvStats(C.Structure):
     _fields_ = [("episodes", C.c_int64), ("return_sum", C.c_double), ("length_sum", C.c_int64), ("bad_actions", C.c_int64),
                 ("last_return", C.c_void_p), ("last_length", C.c_void_p), ("env_episodes", C.c_void_p),
                 ("first_return", C.c_void_p), ("first_length", C.c_void_p)]
+
+
+class CRecordLayout(C.Structure):
+    """sactd3_record_layout: the first three values of sactd3_rb_layout"""
+    _fields_ = [("record_len", C.c_int32), ("next_off", C.c_int32), ("next_width", C.c_int32)]
+
+
+class CRolloutBuffers(C.Structure):
+    """sactd3_rollout_buffers: obs and actions with their row strides in elements, the contiguous record slab"""
+    _fields_ = [("obs", C.c_void_p), ("obs_ld", C.c_int64), ("actions", C.c_void_p), ("actions_ld", C.c_int64), ("records", C.c_void_p)]
 
 
 def library_path() -> str:
@@ -227,6 +245,8 @@ def load_library():
         "sactd3_policy_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, C.POINTER(CPolicyIO), vp, C.c_int]),
         "sactd3_policy": (C.c_int, [vp, fp, C.c_int, C.c_int, C.POINTER(CPolicyIO)]),
         "sactd3_policy_stats": (C.c_int, [vp, i64p]),
+        "sactd3_get_config": (C.c_int, [vp, C.POINTER(CConfig)]),
+        "sactd3_rb_extend_records_device": (C.c_int, [vp, vp, C.c_int, vp, C.c_int]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
@@ -252,6 +272,18 @@ def load_library():
     }
     assert sorted(env_sig) == sorted(ENV_SYMBOLS)
     sig.update(env_sig)
+    rollout_sig = {
+        "sactd3_rollout_env_step": (C.c_int, [vp, vp, C.c_int64, C.POINTER(CRecordLayout), vp, vp, C.c_int64, vp]),
+        "sactd3_rollout_create": (C.c_int, [vp, vp, C.POINTER(CRolloutBuffers), vp, C.POINTER(vp)]),
+        "sactd3_rollout_destroy": (None, [vp]),
+        "sactd3_rollout_last_error": (C.c_char_p, [vp]),
+        "sactd3_rollout_reset": (C.c_int, [vp, C.c_uint64]),
+        "sactd3_rollout_choose": (C.c_int, [vp, C.c_int]),
+        "sactd3_rollout_advance": (C.c_int, [vp]),
+        "sactd3_rollout_stats": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(rollout_sig) == sorted(ROLLOUT_SYMBOLS)
+    sig.update(rollout_sig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the .so does not export what the header declares
         fn.restype, fn.argtypes = res, args

@@ -402,6 +402,24 @@ class ReplayBuffer:
             return
         eng.rb_extend(*[_np(x) for x in five])
 
+    def extend_records(self, records) -> None:
+        """extend() with rows that are ALREADY ring records: a float32 [n, record_floats] array in the memory of the engine's device,
+        contiguous and 16-byte aligned, in the layout of Engine.rb_layout() -- what `envs.NativeVecEnv.step_records` writes
+        (`envs.pack_records` states the layout).  One ingest launch per ring region, ordered on the GPU behind what torch's current
+        stream has queued (the producer of the slab) and in front of what it queues next: the caller neither waits nor keeps the slab
+        untouched (include/sactd3.h: sactd3_rb_extend_records_device).  The ring, its length, a pinned prefix and the priorities end
+        as extend() of the same rows leaves them."""
+        eng = self._need()
+        width = eng.rb_layout()["record_floats"]
+        x = _detached(records)
+        cai = _cai(x)
+        if cai is None or not _on_engine_device(eng, x):
+            raise TypeError("extend_records: `records` must be an array in the memory of the engine's device (extend() takes host rows)")
+        got = _cai_field(cai, width, 4) if _is_kind(cai["typestr"], "f4") else None      # (nothing is converted: a copy would not be the slab)
+        if got is None or got[2] != width:
+            raise ValueError(f"extend_records: `records` must be float32 [n, {width}] with contiguous rows")
+        eng.rb_extend_records_device(got[0], got[1], _producer_stream(records, eng.cfg.device_id))
+
     def sample(self, batch_size: int, *, n_step: int = 1, stride: Optional[int] = None) -> BatchHandle:
         """`n_step` > 1: every drawn row starts a chain of up to n_step consecutive rows of its env (`stride` = the rows appended per
         env step, i.e. the env count), cut where an episode ends or the ring does; the slot holds the discounted return, the last

@@ -1675,6 +1675,12 @@ extern "C" {
 
 int sactd3_abi_version(void) { return SACTD3_ABI_VERSION; }
 
+int sactd3_get_config(const sactd3_engine* e, sactd3_config* out) {
+  if (!e || !out) return SACTD3_EINVAL;
+  *out = e->cfg;
+  return 0;
+}
+
 void sactd3_default_config(sactd3_config* c, int td3) {
   memset(c, 0, sizeof(*c));
   c->abi_version = SACTD3_ABI_VERSION;
@@ -2194,6 +2200,30 @@ int sactd3_rb_extend_fields_device(sactd3_engine* e, const sactd3_device_fields*
   }
   if (n > 0) RCCHK(src_order_end(e, producer, flags));
   ++e->bnd_stats[0]; e->bnd_stats[1] += n;
+  return 0;
+}
+
+// sactd3_rb_extend_device for a slab a producer stream is still writing (a GPU-resident env's step, include/sactd3_rollout.h): the same
+// launch_ingest per ring region, bracketed by the two events of SACTD3_SRC_ORDERED.  Every refusal comes before the first side effect.
+int sactd3_rb_extend_records_device(sactd3_engine* e, const float* records, int n, void* producer_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!records || n < 0) return e->fail(SACTD3_EINVAL, "rb_extend_records_device: bad argument");
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "rb_extend_records_device: unknown flag");
+  if ((uintptr_t)records % 16) return e->fail(SACTD3_EINVAL, "rb_extend_records_device: `records` is not 16-byte aligned");
+  USE_DEVICE(e);
+  RCCHK(device_ptr_check(e, records, "rb_extend_records_device", "records"));
+  if (n == 0) return 0;
+  CHAIN_BREAK(e);
+  const hipStream_t producer = (hipStream_t)producer_stream;
+  const int64_t int_rows = ((1ll << 31) - 1) / e->rec4;      // (k_rb_ingest counts float4 chunks in an int)
+  EnqCtx x{e, e->stream};
+  RCCHK(src_order_begin(e, producer, flags));
+  for (int done_rows = 0; done_rows < n;) {
+    const int chunk = (int)std::min<int64_t>(std::min<int64_t>(n - done_rows, int_rows), ring_region(e));
+    RCCHK(launch_ingest(x, records + (size_t)done_rows * e->rec_f, chunk, 1024));
+    done_rows += chunk;
+  }
+  RCCHK(src_order_end(e, producer, flags));
   return 0;
 }
 

@@ -1,5 +1,7 @@
 // Host side of include/sactd3_env.h: the handle, its one device allocation, and one launch per call (csrc/env_kernels.h).
 // A translation unit of its own inside libsactd3_hip.so: it shares philox.h with engine.hip and nothing else.
+// Behind it, the host side of include/sactd3_rollout.h: the record-emitting env step and the rollout handle, which reaches the
+// engine through its public ABI (include/sactd3.h) only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -10,6 +12,7 @@
 
 #include "../../include/sactd3.h"
 #include "../../include/sactd3_env.h"
+#include "../../include/sactd3_rollout.h"
 #include "env_kernels.h"
 
 #define ENV_API extern "C" __attribute__((visibility("default")))
@@ -335,5 +338,192 @@ static int env_set_state_body(sactd3_env* e, const sactd3_env_state* in, void* s
   if (in->returns) ENV_HIP(e, hipMemcpyAsync(e->d.ret, in->returns, n * 4, hipMemcpyHostToDevice, st));
   if (in->draws) ENV_HIP(e, hipMemcpyAsync(e->d.draws, in->draws, n * 4, hipMemcpyHostToDevice, st));
   ENV_HIP(e, hipStreamSynchronize(st));      // the host arrays (and `phys` above) are free again when the call returns
+  return SACTD3_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- include/sactd3_rollout.h
+static thread_local std::string g_rollout_create_error;
+
+// device memory of device `dev`?  (the engine's rule for a caller's pointer, csrc/engine.hip: device_ptr_check)
+static bool on_device(const void* p, int dev) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != dev) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
+}
+
+// the refusals of a record layout for an env of (o, a): NULL = accepted
+static const char* layout_refusal(const sactd3_record_layout* L, int o, int a) {
+  if (L->record_len % 4 || L->next_off % 4 || L->next_width % 4) return "record_len, next_off and next_width must be multiples of 4";
+  if (L->next_off < o + a) return "next_off is below ob_dim + ac_dim";
+  if (L->next_width < o) return "next_width is below ob_dim";
+  if ((int64_t)L->record_len < (int64_t)L->next_off + L->next_width + 2) return "record_len is below next_off + next_width + 2";
+  return nullptr;
+}
+
+// the one launch of k_env_step_rec: every argument has been checked
+static int launch_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
+                           int64_t obs_ld, hipStream_t st) {
+  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+  const EnvRec k{L->record_len, L->next_off, L->next_width};
+  if (e->cfg.kind == SACTD3_ENV_PENDULUM)
+    hipLaunchKernelGGL(k_env_step_rec<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
+                       (long long)obs_ld, e->info.horizon, e->cfg.seed);
+  else
+    hipLaunchKernelGGL(k_env_step_rec<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
+                       (long long)obs_ld, e->info.horizon, e->cfg.seed);
+  ENV_HIP(e, hipGetLastError());
+  return SACTD3_OK;
+}
+
+static int rollout_env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
+                                 int64_t obs_ld, void* stream);
+ENV_API int sactd3_rollout_env_step(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records,
+                                    float* obs, int64_t obs_ld, void* stream) {
+  try {
+    return rollout_env_step_body(e, actions, act_ld, L, records, obs, obs_ld, stream);
+  } catch (...) {      // (the error text is a std::string)
+    return SACTD3_EHIP;
+  }
+}
+
+static int rollout_env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
+                                 int64_t obs_ld, void* stream) {
+  if (!e) return SACTD3_EINVAL;
+  if (!actions || !L || !records || !obs) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: actions, layout, records and obs must not be NULL");
+  if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: act_ld is below ac_dim");
+  if (obs_ld < e->info.ob_dim) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: obs_ld is below ob_dim");
+  if (const char* why = layout_refusal(L, e->info.ob_dim, e->info.ac_dim)) return e->fail(SACTD3_EINVAL, (std::string("sactd3_rollout_env_step: ") + why).c_str());
+  if ((uintptr_t)records % 16) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: `records` is not 16-byte aligned");
+  if (!on_device(records, e->cfg.device_id)) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: `records` is not device memory of the env's device");
+  return launch_step_rec(e, actions, act_ld, L, records, obs, obs_ld, (hipStream_t)stream);
+}
+
+struct sactd3_rollout {
+  sactd3_engine* eng = nullptr;
+  sactd3_env* env = nullptr;
+  sactd3_rollout_buffers buf{};
+  sactd3_record_layout lay{};
+  hipStream_t stream = nullptr;
+  int n = 0;
+  int64_t stats[4] = {0, 0, 0, 0};      // random choices, policy choices, steps, rows appended
+  std::string err;
+
+  int fail(int code, const std::string& what) {
+    err = what;
+    return code;
+  }
+  // a failed call of the env's / the engine's ABI: its code, its text
+  int from_env(int rc, const char* call) { return rc ? fail(rc, std::string(call) + ": " + sactd3_env_last_error(env)) : 0; }
+  int from_engine(int rc, const char* call) {
+    if (!rc) return 0;
+    const char* text = sactd3_last_error(eng);
+    return fail(rc, std::string(call) + ": " + (text ? text : "?"));
+  }
+};
+
+static int rollout_create_body(sactd3_engine* eng, sactd3_env* env, const sactd3_rollout_buffers* b, void* stream, sactd3_rollout** out) {
+  if (out) *out = nullptr;
+  auto refuse = [](const std::string& what) {
+    g_rollout_create_error = "sactd3_rollout_create: " + what;
+    return SACTD3_EINVAL;
+  };
+  if (!eng || !env || !b || !out) return refuse("NULL argument");
+  if (!b->obs || !b->actions || !b->records) return refuse("a buffer is NULL");
+  sactd3_config cfg;
+  int32_t lay[4];
+  if (sactd3_get_config(eng, &cfg) != SACTD3_OK || sactd3_rb_layout(eng, lay) != SACTD3_OK) return refuse("the engine gave no configuration");
+  const sactd3_env_info& info = env->info;
+  if (info.ob_dim != cfg.ob_dim || info.ac_dim != cfg.ac_dim)
+    return refuse("the env's ob_dim / ac_dim (" + std::to_string(info.ob_dim) + ", " + std::to_string(info.ac_dim) + ") differ from the engine's (" +
+                  std::to_string(cfg.ob_dim) + ", " + std::to_string(cfg.ac_dim) + ")");
+  if (env->cfg.device_id != cfg.device_id) return refuse("the env and the engine are on different devices");
+  if (info.num_envs > cfg.max_envs)
+    return refuse("num_envs (" + std::to_string(info.num_envs) + ") is above the engine's max_envs (" + std::to_string(cfg.max_envs) + ")");
+  if (b->obs_ld < info.ob_dim || b->actions_ld < info.ac_dim) return refuse("a row stride is below its width");
+  const sactd3_record_layout L{lay[0], lay[1], lay[2]};
+  if (const char* why = layout_refusal(&L, info.ob_dim, info.ac_dim)) return refuse(why);
+  if ((uintptr_t)b->records % 16) return refuse("`records` is not 16-byte aligned");
+  if (!on_device(b->obs, cfg.device_id) || !on_device(b->actions, cfg.device_id) || !on_device(b->records, cfg.device_id))
+    return refuse("a buffer is not device memory of the handles' device");
+  sactd3_rollout* r = new (std::nothrow) sactd3_rollout();
+  if (!r) {
+    g_rollout_create_error = "sactd3_rollout_create: out of host memory";
+    return SACTD3_EHIP;
+  }
+  r->eng = eng; r->env = env; r->buf = *b; r->lay = L; r->stream = (hipStream_t)stream; r->n = info.num_envs;
+  *out = r;
+  return SACTD3_OK;
+}
+
+ENV_API int sactd3_rollout_create(sactd3_engine* eng, sactd3_env* env, const sactd3_rollout_buffers* b, void* stream, sactd3_rollout** out) {
+  try {
+    return rollout_create_body(eng, env, b, stream, out);
+  } catch (...) {      // (the error text is a std::string)
+    return SACTD3_EHIP;
+  }
+}
+
+ENV_API void sactd3_rollout_destroy(sactd3_rollout* r) { delete r; }      // (neither handle nor any buffer is the rollout's)
+
+ENV_API const char* sactd3_rollout_last_error(const sactd3_rollout* r) { return r ? r->err.c_str() : g_rollout_create_error.c_str(); }
+
+ENV_API int sactd3_rollout_reset(sactd3_rollout* r, uint64_t seed) {
+  if (!r) return SACTD3_EINVAL;
+  try {
+    return r->from_env(sactd3_env_reset(r->env, seed, r->buf.obs, r->buf.obs_ld, r->stream), "sactd3_env_reset");
+  } catch (...) {
+    return SACTD3_EHIP;
+  }
+}
+
+ENV_API int sactd3_rollout_choose(sactd3_rollout* r, int mode) {
+  if (!r) return SACTD3_EINVAL;
+  try {
+    const sactd3_rollout_buffers& b = r->buf;
+    int rc;
+    switch (mode) {
+      case SACTD3_ROLLOUT_REPEAT:
+        return SACTD3_OK;
+      case SACTD3_ROLLOUT_RANDOM:
+        if ((rc = r->from_env(sactd3_env_sample_actions(r->env, b.actions, b.actions_ld, r->stream), "sactd3_env_sample_actions"))) return rc;
+        ++r->stats[0];
+        return SACTD3_OK;
+      case SACTD3_ROLLOUT_EXPLORE:
+      case SACTD3_ROLLOUT_EXPLOIT:
+        rc = sactd3_predict_device(r->eng, b.obs, b.obs_ld, r->n, mode == SACTD3_ROLLOUT_EXPLORE ? 1 : 0, b.actions, b.actions_ld, r->stream,
+                                   SACTD3_SRC_ORDERED);
+        if ((rc = r->from_engine(rc, "sactd3_predict_device"))) return rc;
+        ++r->stats[1];
+        return SACTD3_OK;
+      default:
+        return r->fail(SACTD3_EINVAL, "sactd3_rollout_choose: mode must be one of SACTD3_ROLLOUT_*");
+    }
+  } catch (...) {
+    return SACTD3_EHIP;
+  }
+}
+
+ENV_API int sactd3_rollout_advance(sactd3_rollout* r) {
+  if (!r) return SACTD3_EINVAL;
+  try {
+    const sactd3_rollout_buffers& b = r->buf;
+    int rc = launch_step_rec(r->env, b.actions, b.actions_ld, &r->lay, b.records, b.obs, b.obs_ld, r->stream);
+    if ((rc = r->from_env(rc, "k_env_step_rec"))) return rc;
+    ++r->stats[2];
+    rc = sactd3_rb_extend_records_device(r->eng, b.records, r->n, r->stream, SACTD3_SRC_ORDERED);
+    if ((rc = r->from_engine(rc, "sactd3_rb_extend_records_device"))) return rc;
+    r->stats[3] += r->n;
+    return SACTD3_OK;
+  } catch (...) {
+    return SACTD3_EHIP;
+  }
+}
+
+ENV_API int sactd3_rollout_stats(const sactd3_rollout* r, int64_t out[4]) {
+  if (!r || !out) return SACTD3_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = r->stats[i];
   return SACTD3_OK;
 }

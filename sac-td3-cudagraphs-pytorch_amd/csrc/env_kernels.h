@@ -164,6 +164,92 @@ __global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restr
   env_observe<KIND>(s2, o.obs + (size_t)i * o.obs_ld);
 }
 
+// k_env_step that also emits env i's transition as record i of a caller slab in the engine's ring layout (include/sactd3.h:
+// sactd3_rb_layout; include/sactd3_rollout.h):
+//   [s (OB) | a (AC) | 0-pad to next_off][s'_stored (OB) | 0-pad to next_width][r, d][0-pad to record_len]
+// s is env_observe of the state BEFORE the step (recomputed from phys: the caller's observation buffer is not read), a the action
+// as given (its bits, not the clamped one), s'_stored the arrival observation where the step was truncated and otherwise the
+// observation the caller acts on next (behind a termination: the auto-reset one), d = 1 iff terminated.  State, books, counters and
+// `obs` are those of k_env_step, statement for statement.  One thread writes its whole record with 16-byte stores: the host side
+// guarantees a 16-byte aligned slab and lengths that are multiples of four, and next_off >= OB + AC, next_width >= OB,
+// record_len >= next_off + next_width + 2.
+struct EnvRec { int record_len, next_off, next_width; };
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_env_step_rec(EnvDev d, const float* __restrict__ actions, long long act_ld, EnvRec L,
+                                                      float* __restrict__ records, float* __restrict__ obs, long long obs_ld, int horizon,
+                                                      uint64_t seed) {
+  constexpr int OB = EnvTask<KIND>::OB, AC = EnvTask<KIND>::AC;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.n) return;
+  const size_t n = (size_t)d.n;
+  uint32_t araw[AC];
+#pragma unroll
+  for (int j = 0; j < AC; ++j) araw[j] = __float_as_uint(actions[(size_t)i * act_ld + j]);
+  float a = __uint_as_float(araw[0]);
+  const bool bad = !(fabsf(a) <= 3.40282347e38f);      // NaN or infinite (every finite float passes): never reaches the state
+  if (bad) a = 0.0f;
+  const float u = env_clamp(a, EnvTask<KIND>::BOUND);
+  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4];
+#pragma unroll
+  for (int j = 0; j < EnvTask<KIND>::NS; ++j) s[j] = d.phys[j * n + i];
+  float reward;
+  bool terminal;
+  env_physics<KIND>(s, u, s2, reward, terminal);
+  const int t = d.steps[i] + 1;
+  const float ret = d.ret[i] + reward;
+  const bool truncated = !terminal && t >= horizon;
+  const bool ended = terminal || truncated;
+  float so[OB], fin[OB], nx[OB];
+  env_observe<KIND>(s, so);
+  env_observe<KIND>(s2, fin);
+  if (bad) d.bad[i] += 1u;
+  if (ended) {
+    const uint32_t ep = d.episode[i] + 1u;
+    const uint32_t done = d.done_count[i];
+    if (done == 0u) { d.first_ret[i] = ret; d.first_len[i] = t; }
+    d.done_count[i] = done + 1u;
+    d.ret_sum[i] += (double)ret;
+    d.len_sum[i] += (unsigned long long)t;
+    d.last_ret[i] = ret;
+    d.last_len[i] = t;
+    d.episode[i] = ep;
+    env_first_state<KIND>(seed, (uint32_t)i, ep, s2);
+    d.steps[i] = 0;
+    d.ret[i] = 0.0f;
+  } else {
+    d.steps[i] = t;
+    d.ret[i] = ret;
+  }
+#pragma unroll
+  for (int j = 0; j < EnvTask<KIND>::NS; ++j) d.phys[j * n + i] = s2[j];
+  env_observe<KIND>(s2, nx);
+#pragma unroll
+  for (int j = 0; j < OB; ++j) obs[(size_t)i * obs_ld + j] = nx[j];
+  // the record, element by element through selects (no indexed local array), four elements per store
+  const int tail = L.next_off + L.next_width;
+  const uint32_t rbits = __float_as_uint(reward), dbits = __float_as_uint(terminal ? 1.0f : 0.0f);
+  uint4* __restrict__ rec = (uint4*)(records + (size_t)i * (size_t)L.record_len);
+  for (int c = 0; c < L.record_len / 4; ++c) {
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int e = 4 * c + k;
+      uint32_t v = 0u;
+#pragma unroll
+      for (int j = 0; j < OB; ++j) v = (e == j) ? __float_as_uint(so[j]) : v;
+#pragma unroll
+      for (int j = 0; j < AC; ++j) v = (e == OB + j) ? araw[j] : v;
+#pragma unroll
+      for (int j = 0; j < OB; ++j) v = (e == L.next_off + j) ? __float_as_uint(truncated ? fin[j] : nx[j]) : v;
+      v = (e == tail) ? rbits : v;
+      v = (e == tail + 1) ? dbits : v;
+      w[k] = v;
+    }
+    rec[c] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
 template <int KIND>
 __global__ __launch_bounds__(256) void k_env_reset(EnvDev d, float* __restrict__ obs, long long obs_ld, uint64_t seed) {
   const int i = blockIdx.x * 256 + threadIdx.x;

@@ -227,6 +227,12 @@ class Engine:
         """append n packed records that already live in device memory (kept alive by the caller until sync())."""
         self._ck(self.lib.sactd3_rb_extend_device(self._h, C.c_void_p(int(device_ptr)), int(n)))
 
+    def rb_extend_records_device(self, device_ptr: int, n: int, producer_stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_rb_extend_records_device: rb_extend_device for a 16-byte aligned slab of n packed records that `producer_stream` (a
+        hipStream_t as an integer; 0 = the default stream) may still be writing.  `ordered`: the engine orders its read behind that
+        stream and the stream's next write behind the read, on the GPU; otherwise as rb_extend_device."""
+        self._ck(self.lib.sactd3_rb_extend_records_device(self._h, _vp(device_ptr), int(n), _vp(producer_stream), _flag(_lib.SRC_ORDERED, ordered)))
+
     def _fields(self, fields):
         df = self._df
         (df.obs, df.obs_ld), (df.actions, df.actions_ld), (df.rewards, df.rewards_ld), (df.next_obs, df.next_obs_ld), (df.dones, df.dones_ld) = fields

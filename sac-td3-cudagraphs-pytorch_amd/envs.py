@@ -2,7 +2,9 @@
 
   NativeVecEnv    the vector env that lives on the GPU (csrc/env_kernels.h): `step` is ONE kernel launch on the current torch stream,
                   every array a device tensor, no host draw, no host wait, no torch arithmetic -- the protocol `loop.DeviceRollout`
-                  consumes (`loop.train(device_env=True)`)
+                  consumes (`loop.train(device_env=True)`); `step_records` is the same step writing its transitions as ring records
+                  into the caller's slab (include/sactd3_rollout.h), which `loop.NativeRollout` drives (`native_rollout=True`)
+  pack_records    the ring's record layout in numpy: what `step_records` writes, for the host twin's users and for tests
   HostVecEnv      the same two tasks in numpy float32, in the kernel's operation order and with the same Philox resets, with the
                   gymnasium-0.29 protocol of `loop.SyntheticVecEnv` -- for `loop.Rollout`, `loop.Evaluator` and `loop.evaluate`
   greedy_returns  evaluation with one host wait: a vector env stepped in lock-step with the agent's greedy action for one horizon
@@ -238,6 +240,36 @@ def _check_state(state, n: int) -> None:
         raise ValueError("set_state: a step count is negative")
 
 
+# ---------------------------------------------------------------------------------------------------- transitions as ring records
+def _layout_triple(layout):
+    """(record_floats, next_obs_offset, next_obs_width) of Engine.rb_layout()'s dict, or of a triple given as such"""
+    if isinstance(layout, dict):
+        return int(layout["record_floats"]), int(layout["next_obs_offset"]), int(layout["next_obs_width"])
+    rec, off, width = layout
+    return int(rec), int(off), int(width)
+
+
+def pack_records(layout, obs, actions, rewards, next_obs, dones) -> np.ndarray:
+    """[n, record_floats] float32: n transitions as records of the engine's replay ring (include/sactd3.h: sactd3_rb_layout) --
+        [s (ob_dim) | a (ac_dim) | 0-pad to next_obs_offset][s' (ob_dim) | 0-pad to next_obs_width][r, d (0 / 1)][0-pad]
+    every value copied bit for bit, every pad float +0.  `next_obs` is the STORED next observation: for a `HostVecEnv` step the
+    arrival observation where the step was truncated (infos["final_observation"]), otherwise the one returned -- which is what
+    `NativeVecEnv.step_records` writes on the device.  With a host env, `agent.rb.extend_records(torch.as_tensor(rows, device=...))`
+    appends the rows."""
+    rec, off, width = _layout_triple(layout)
+    obs, next_obs = np.asarray(obs, F), np.asarray(next_obs, F)
+    n = obs.shape[0]
+    obs, next_obs, actions = obs.reshape(n, -1), next_obs.reshape(n, -1), np.asarray(actions, F).reshape(n, -1)
+    o, a = obs.shape[1], actions.shape[1]
+    if off < o + a or width < o or rec < off + width + 2 or next_obs.shape != obs.shape:
+        raise ValueError(f"pack_records: layout {(rec, off, width)} does not hold observations [{n}, {o}] and actions [{n}, {a}]")
+    out = np.zeros((n, rec), F)
+    out[:, :o], out[:, o:o + a], out[:, off:off + o] = obs, actions, next_obs
+    out[:, off + width] = np.asarray(rewards, F).reshape(n)
+    out[:, off + width + 1] = (np.asarray(dones).reshape(n) != 0).astype(F)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- the env on the GPU
 class _DeviceBox:
     def __init__(self, env):
@@ -334,6 +366,16 @@ class NativeVecEnv:
                            flags[0].data_ptr(), 1, flags[1].data_ptr(), 1, flags[2].data_ptr(), 1)
         self._call("sactd3_env_step", a.data_ptr(), a.stride(0), C.byref(out), self._stream())
         return obs, rew, flags[0], flags[1], {"final_observation": final, "_final_observation": flags[2]}
+
+    def step_records(self, actions, layout, records, obs) -> None:
+        """One vector step that writes env i's transition as row i of `records`, in the engine's ring layout, and the observations to
+        act on next into `obs` -- both the CALLER's tensors, nothing is allocated (include/sactd3_rollout.h: sactd3_rollout_env_step;
+        one launch of k_env_step_rec on the current torch stream).  State, books and `obs` are those of step().  `layout`:
+        Engine.rb_layout() (or a (record_floats, next_obs_offset, next_obs_width) triple); `records`: float32 [n, record_floats],
+        contiguous, 16-byte aligned -- what `ReplayBuffer.extend_records` appends; `pack_records` states what a row holds."""
+        lay = _lib.CRecordLayout(*_layout_triple(layout))
+        self._call("sactd3_rollout_env_step", actions.data_ptr(), actions.stride(0), C.byref(lay), records.data_ptr(), obs.data_ptr(),
+                   obs.stride(0), self._stream())
 
     # -- bookkeeping: these wait for the device
     def episode_stats(self) -> Dict[str, Any]:

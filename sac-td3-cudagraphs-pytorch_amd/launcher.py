@@ -7,7 +7,7 @@ the timings, never on the data path.
 from __future__ import annotations
 
 import os
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 
 def rank_info() -> Tuple[int, int, int]:
@@ -187,15 +187,27 @@ ENV_DIMS = {   # (ob_dim, ac_dim, action bound) of the Gymnasium MuJoCo -v4 task
 }
 
 
-def env_plan(env_id: str, device_env: bool, has_factory: bool = False):
+def env_plan(env_id: str, device_env: bool, has_factory: bool = False, native_rollout: Optional[bool] = None):
     """Which env classes a job uses, decided without touching a GPU: -> dict(train=, eval=) of class names.  The -native ids are
     simulated by this package: `envs.HostVecEnv` trains and evaluates on the host, and with --device_env `envs.NativeVecEnv` does both
     on the GPU (evaluation through `envs.device_episodes`: no host env step anywhere in the job).  Every other id is what it was: the
-    caller's factory or the synthetic stand-in, and the synthetic device env for training with --device_env."""
+    caller's factory or the synthetic stand-in, and the synthetic device env for training with --device_env.
+    `native_rollout` (True / False; None: the question is not asked and the plan has no such key) adds rollout=: the class of `loop`
+    that drives the training env -- "NativeRollout" with --native_rollout, which needs --device_env and a -native id without a
+    factory (ValueError otherwise), else "DeviceRollout" with --device_env and "Rollout" without."""
     if env_id in NATIVE_ENVS and not has_factory:
-        return dict(train="NativeVecEnv", eval="NativeVecEnv") if device_env else dict(train="HostVecEnv", eval="HostVecEnv")
-    base = "factory" if has_factory else "SyntheticVecEnv"
-    return dict(train="SyntheticDeviceVecEnv" if device_env else base, eval=base)
+        plan = dict(train="NativeVecEnv", eval="NativeVecEnv") if device_env else dict(train="HostVecEnv", eval="HostVecEnv")
+    else:
+        base = "factory" if has_factory else "SyntheticVecEnv"
+        plan = dict(train="SyntheticDeviceVecEnv" if device_env else base, eval=base)
+    if native_rollout is not None:
+        if native_rollout and not device_env:
+            raise ValueError("--native_rollout needs --device_env: it drives an env that lives on the GPU")
+        if native_rollout and plan["train"] != "NativeVecEnv":
+            raise ValueError(f"--native_rollout needs a -native env id ({', '.join(NATIVE_ENVS)}) without --env_factory: {env_id} "
+                             "has no env that emits ring records")
+        plan["rollout"] = "NativeRollout" if native_rollout else ("DeviceRollout" if device_env else "Rollout")
+    return plan
 DEFAULTS = {   # tasks/defaults/sac.yml:1-48 (td3.yml differs in the keys listed under "td3")
     "sac": dict(num_envs=4, action_repeat=1, measure_burnin=3, num_timesteps=10_000_000, learning_starts=5000, eval_steps=10,
                 eval_every=10_000, layer_norm=True, actor_lr=3e-4, qnets_lr=1e-3, clip_norm=0.0, segment_len=1, batch_size=256,
@@ -273,14 +285,16 @@ def policy_stats_plan(args) -> int:
 
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
-            offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0, **over):
+            offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
+            native_rollout: bool = False, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
     `bc_alpha` in `over` turns the TD3+BC actor term on.
     `prior_fraction` beside `offline_dataset`: an online run on top of the dataset instead -- the ring is filled and its rows pinned
     (loop.load_dataset(pin=True)), then loop.train draws that share of every batch from them; `updates_per_step`: updates per
-    segment of any online run; `policy_stats`: rows put to the policy at every evaluation (loop.PolicyStats; SAC only)."""
+    segment of any online run; `policy_stats`: rows put to the policy at every evaluation (loop.PolicyStats; SAC only);
+    `native_rollout`: the env loop through loop.NativeRollout (needs `device_env` and a -native id: env_plan refuses otherwise)."""
     import json
     import time
     from pathlib import Path
@@ -290,6 +304,13 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     from .agent import Agent, ReplayBuffer
     if int(policy_stats) and algo != "sac":      # (before anything is built)
         raise ValueError("policy_stats needs algo sac: TD3's deterministic actor has no log-probability, entropy or log-std to report")
+    if native_rollout:                           # (before anything is built)
+        env_plan(env_id, device_env, env_factory is not None, native_rollout=True)
+        if offline_dataset is not None or overlap_acting:
+            raise ValueError("native_rollout excludes offline_dataset and overlap_acting")
+        utd_native = dict(native_rollout=True)
+    else:
+        utd_native = {}
     cfg = job_config(algo, env_id, seed, **over)
     o, a, bound = ENV_DIMS[env_id]
     native = env_id in NATIVE_ENVS and env_factory is None      # the two tasks this package simulates itself (env_plan)
@@ -331,6 +352,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     utd = dict(updates_per_step=int(updates_per_step)) if int(updates_per_step) != 1 else {}      # (a keyword only when it is used)
     if int(policy_stats):
         utd["policy_stats"] = int(policy_stats)
+    utd.update(utd_native)
     if offline_dataset is not None and prior_fraction is not None:
         metrics = loop.train(cfg, env, agent, fused=False, evaluator=ev, overlap=overlap_acting, device_env=device_env,
                              one_launch=one_launch, prior_fraction=float(prior_fraction), **utd)
@@ -364,7 +386,8 @@ def _worker_main(args) -> int:
         factory = getattr(importlib.import_module(mod), fn)
     for env_id, seed in jobs:
         if args.dry_run:
-            out = {"env_id": env_id, "algo": args.algo, "seed": seed, "gpu": args.rank, "dry_run": True}
+            out = {"env_id": env_id, "algo": args.algo, "seed": seed, "gpu": args.rank, "dry_run": True,
+                   "rollout": env_plan(env_id, args.device_env, factory is not None, native_rollout=args.native_rollout)["rollout"]}
         else:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
@@ -372,7 +395,8 @@ def _worker_main(args) -> int:
                           overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized,
                           n_step=args.n_step, one_launch=args.one_launch, offline_dataset=plan.get("dataset"),
                           num_updates=plan.get("num_updates"), bc_alpha=args.bc_alpha, prior_fraction=plan.get("prior_fraction"),
-                          updates_per_step=args.updates_per_step or 1, policy_stats=policy_stats_plan(args))
+                          updates_per_step=args.updates_per_step or 1, policy_stats=policy_stats_plan(args),
+                          native_rollout=args.native_rollout)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -403,6 +427,9 @@ def main(argv=None) -> int:
     ap.add_argument("--device_env", action="store_true",
                     help="train on the GPU-resident vector env (the synthetic one; for the -native ids envs.NativeVecEnv, which also evaluates "
                          "there): observations and actions never leave the device (loop.train device_env=True)")
+    ap.add_argument("--native_rollout", action="store_true",
+                    help="with --device_env and a -native env bundle: the env step writes ring records and choose / advance are one library "
+                         "call each (loop.train native_rollout=True); the default stays loop.DeviceRollout")
     ap.add_argument("--prioritized", action="store_true",
                     help="proportional prioritised replay kept by the engine (loop.train prioritized=...; the iteration is issued call by call)")
     ap.add_argument("--one_launch", action="store_true",
@@ -431,6 +458,11 @@ def main(argv=None) -> int:
     try:
         plan = offline_plan(args)
         policy_stats_plan(args)
+        if args.native_rollout:                  # every job of the sweep, before a worker starts
+            if args.offline_dataset is not None or args.overlap_acting:
+                raise ValueError("--native_rollout excludes --offline_dataset and --overlap_acting")
+            for env_id in ENV_BUNDLES[args.env_bundle]:
+                env_plan(env_id, args.device_env, bool(args.env_factory), native_rollout=True)
     except ValueError as ex:
         ap.error(str(ex))
     if args.worker:

@@ -3,6 +3,7 @@ be driven end to end without tensordict / torchrl / gymnasium being importable:
 
   Rollout / segment()   the acting side + its generator  orchestrator.py:42-118   
   DeviceRollout         the same acting side for a vector env that lives on the GPU: every array a device tensor, no host wait
+  NativeRollout         ... for an env that emits ring records itself (envs.NativeVecEnv): choose / advance are one library call each
   train()       the training loop's control flow       orchestrator.py:317-352 (+ counters :326,342,349)
   load_dataset() / train_offline()   training on a FIXED dataset (not in the reference): the ring filled once, then runs of whole
                 periods through Engine.run_iterations -- the workload of TD3+BC (hps.bc_alpha > 0)
@@ -139,6 +140,86 @@ class DeviceRollout:
         self.steps += 1
 
 
+class NativeRollout:
+    """`DeviceRollout` for an env that writes its transitions as ring records itself (`env.step_records`: envs.NativeVecEnv), through
+    one handle of the library that knows the env and the engine (include/sactd3_rollout.h).  Three tensors -- `.obs` [n, o], `.actions`
+    [n, a] and the record slab [n, record_floats] -- are allocated here, once; after that `choose()` and `advance()` are ONE ctypes
+    call each and allocate nothing: the env's draw or the acting kernels write `.actions`, one launch of the env steps, writes the
+    slab and overwrites `.obs`, one ingest launch appends the slab, all ordered on the GPU.  The kernels of the env run on the torch
+    stream that is current at construction.  Same two half-steps and the same reference behaviour as `Rollout`
+    (orchestrator.py:42-118); what stays in Python is what is host state: random or exploring actions by
+    `agent.timesteps_so_far < learning_starts`, and `action_repeat`.  The ring, the env and the engine end bit for bit as
+    `DeviceRollout` leaves them.  `.obs` and `.actions` are VIEWS of the bound buffers: the next call overwrites them."""
+
+    def __init__(self, env, agent, seed: int, learning_starts: int, action_repeat: int):
+        assert agent.rb is not None
+        if not callable(getattr(env, "step_records", None)):
+            raise TypeError(f"native_rollout=True needs an env with step_records(); {type(env).__name__} has none")
+        import ctypes as C
+        import torch
+        from . import _lib
+        eng = agent.engine
+        self.env, self.agent = env, agent
+        self.learning_starts, self.action_repeat = learning_starts, action_repeat
+        dev = torch.device("cuda", int(eng.cfg.device_id))
+        self.obs = torch.zeros((env.num_envs, eng.cfg.ob_dim), dtype=torch.float32, device=dev)
+        self.actions = torch.zeros((env.num_envs, eng.cfg.ac_dim), dtype=torch.float32, device=dev)
+        self.records = torch.zeros((env.num_envs, eng.rb_layout()["record_floats"]), dtype=torch.float32, device=dev)
+        self._lib, self._error = eng.lib, _lib.EngineError
+        buffers = _lib.CRolloutBuffers(self.obs.data_ptr(), self.obs.stride(0), self.actions.data_ptr(), self.actions.stride(0),
+                                       self.records.data_ptr())
+        self._h = C.c_void_p()
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self._lib.sactd3_rollout_create(eng._h, env._h, C.byref(buffers), C.c_void_p(stream or None), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise self._error(f"sactd3_rollout_create failed ({rc}): {self._lib.sactd3_rollout_last_error(None).decode()}")
+        self._choose, self._advance = self._lib.sactd3_rollout_choose, self._lib.sactd3_rollout_advance
+        self._random, self._explore = _lib.ROLLOUT_RANDOM, _lib.ROLLOUT_EXPLORE
+        env.seed = int(seed)
+        self._ck(self._lib.sactd3_rollout_reset(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self.steps = 0
+
+    def _ck(self, rc: int) -> None:
+        if rc != 0:
+            raise self._error(f"native rollout call failed ({rc}): {self._lib.sactd3_rollout_last_error(self._h).decode()}")
+
+    def close(self) -> None:
+        """drop the handle (before the env or the engine is closed); the tensors stay the caller's"""
+        if getattr(self, "_h", None):
+            self._lib.sactd3_rollout_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def stats(self) -> Dict[str, int]:
+        """host counters of the handle (sactd3_rollout_stats)"""
+        import ctypes as C
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.sactd3_rollout_stats(self._h, out))
+        return dict(zip(("random_choices", "policy_choices", "steps", "rows_appended"), (int(v) for v in out)))
+
+    def choose(self) -> None:
+        if self.steps % self.action_repeat:
+            return                                                   # the action in force is repeated
+        rc = self._choose(self._h, self._random if self.agent.timesteps_so_far < self.learning_starts else self._explore)
+        if rc:
+            self._ck(rc)
+
+    def resolve(self) -> None:
+        """nothing is ever pending here (the protocol of `Rollout`, for `segment` / `train`)"""
+
+    def advance(self) -> None:
+        rc = self._advance(self._h)
+        if rc:
+            self._ck(rc)
+        self.steps += 1
+
+
 def segment(env, agent, seed: int, segment_len: int, learning_starts: int, action_repeat: int, overlap: bool = False,
             rollout: Optional[Rollout] = None) -> Generator[None, None, None]:
     """orchestrator.py:42-118 as a generator over `Rollout`: control goes back to the caller every `segment_len` env steps, AFTER
@@ -229,7 +310,7 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
           sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
           n_step: int = 1, one_launch: bool = False, prior_fraction: Optional[float] = None,
-          updates_per_step: int = 1, policy_stats: int = 0) -> Dict[str, float]:
+          updates_per_step: int = 1, policy_stats: int = 0, native_rollout: bool = False) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -239,6 +320,9 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     acting stream while this iteration's update runs; a pending action is collected before an evaluation acts with the agent.
     `device_env=True`: `env` lives on the GPU (device tensors in and out, e.g. SyntheticDeviceVecEnv) and is driven by `DeviceRollout`
     -- `agent.predict_device`, no host round trip per env step.  It acts on the learner stream, so it excludes `overlap`.
+    `native_rollout=True` (needs `device_env=True` and an env with `step_records`, e.g. envs.NativeVecEnv; excludes `overlap`): the
+    env is driven by `NativeRollout` instead -- the env step writes the transitions as ring records and choose / advance are one
+    library call each, with the ring, the env and the engine bit for bit as `DeviceRollout` leaves them.  Off by default.
     `sampler` (a ProportionalSampler; needs `fused=False`: `fused=True` is the uniform iteration): prioritised replay, call
     by call on the device -- the sampler's rows and importance weights through `rb.sample_at`, the critic update weighted by them,
     its TD errors (`agent.td_errors`) back into the sampler's priorities; the actor updates train on the same rows, unweighted.
@@ -300,11 +384,17 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
             raise ValueError(f"prioritized: unknown keys {sorted(unknown)}")
         prio_beta = float(prioritized.get("beta", 0.4))
         agent.rb.enable_priorities(alpha=float(prioritized.get("alpha", 0.6)), eps=float(prioritized.get("eps", 1e-6)))
+    if native_rollout and overlap:
+        raise ValueError("native_rollout=True and overlap=True exclude each other: the native rollout acts on the learner stream")
+    if native_rollout and not device_env:
+        raise ValueError("native_rollout=True needs device_env=True: it drives an env that lives on the GPU")
+    if native_rollout and not callable(getattr(env, "step_records", None)):
+        raise TypeError(f"native_rollout=True needs an env with step_records(); {type(env).__name__} has none")
     if overlap and device_env:
         raise ValueError("overlap=True and device_env=True exclude each other: predict_device acts on the learner stream")
     ro = Rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat, overlap=True) if overlap else None
     if device_env:
-        ro = DeviceRollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat)
+        ro = (NativeRollout if native_rollout else DeviceRollout)(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat)
     seg_gen = segment(env, agent, cfg.seed, cfg.segment_len, cfg.learning_starts, cfg.action_repeat, rollout=ro)
     i = 0
     tlog: Dict[str, Any] = {}

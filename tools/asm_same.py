@@ -9,9 +9,15 @@ or, with two outputs already made,
     make -C sac-td3-cudagraphs-pytorch_amd/csrc asm ASM_OUT=/tmp/b.s      (at another)
     python tools/asm_same.py /tmp/a.s /tmp/b.s
 
+or, to renew the record the suite holds `make asm` to (tests/test_native_rollout_host.py) in a change that means to alter a kernel,
+
+    python tools/asm_same.py --record /tmp/b.s     (-> tests/golden/engine_kernels_sha256.json: the SHA-256 of every body)
+
 A body is the text between `<symbol>:` and its `.Lfunc_end`, without comments and without the labels' numbering (a label number is
 global to the file and moves when a kernel is added in front).  Prints the symbols only one side has and those whose bodies differ,
 and whether the symbols both sides have stand in the same order; exit status 1 if a symbol present in both differs.  Needs no GPU."""
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -20,6 +26,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "sac-td3-cudagraphs-pytorch_amd/csrc"
+RECORD = os.path.join(ROOT, "tests", "golden", "engine_kernels_sha256.json")
 
 
 def bodies(path):
@@ -41,6 +48,21 @@ def bodies(path):
         body = re.sub(r"\.Ltmp\d+", ".Ltmp", body)
         out[name] = body
     return out
+
+
+def digests(path):
+    """{symbol: SHA-256 of its body}"""
+    return {name: hashlib.sha256(body.encode()).hexdigest() for name, body in bodies(path).items()}
+
+
+def record(path):
+    got = digests(path)
+    with open(RECORD, "w") as f:
+        json.dump({"what": "SHA-256 of every kernel body of `make asm` (csrc/engine.hip, gfx950) as tools/asm_same.py reads it", "kernels": got},
+                  f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(f"{len(got)} symbols -> {RECORD}")
+    return 0
 
 
 def compare(path_a, path_b):
@@ -77,6 +99,8 @@ def main():
     args = sys.argv[1:]
     if len(args) == 2 and args[0] == "--rev":
         return compare_rev(args[1])
+    if len(args) == 2 and args[0] == "--record":
+        return record(args[1])
     if len(args) == 2 and not args[0].startswith("-"):
         return compare(args[0], args[1])
     print(__doc__)
