@@ -134,6 +134,12 @@ int sactd3_set_adam_state(sactd3_engine* e, int which, const float* exp_avg, con
 int sactd3_rb_extend(sactd3_engine* e, const float* obs, const float* actions, const float* rewards,
                      const float* next_obs, const uint8_t* dones, int n);
 int64_t sactd3_rb_len(const sactd3_engine* e);                             /* len(rb) (orchestrator.py:385) */
+/* the generation of the batch slot: it strictly increases with every accepted call that changes the rows sactd3_read_batch reports
+ * (the sactd3_rb_sample* and sactd3_load_batch* calls, sactd3_step*, the refilling kernels of sactd3_time_kernel / _time_nodes), by no
+ * promised amount, and no other call changes it: not an update on the rows already there (sactd3_update_*), not a read-out, not an
+ * append, and not a refused call, which changed nothing.  Whoever holds a name for the slot, not a copy of its rows, remembers the
+ * value and compares.  Host state: no launch, no wait. */
+int64_t sactd3_batch_generation(const sactd3_engine* e);
 /* layout of one ring record, in floats: out = {record length, offset of s' (= padded width of [s | a]), padded width of s',
  * rb_capacity}; record = [s (ob_dim) | a (ac_dim) | 0-pad][s' (ob_dim) | 0-pad][r, d (0/1)][0-pad to a 64-byte multiple] */
 int sactd3_rb_layout(const sactd3_engine* e, int32_t out[4]);

@@ -47,7 +47,7 @@ SYMBOLS = [
     "sactd3_set_bc", "sactd3_get_bc",
     "sactd3_rb_pin", "sactd3_rb_pinned", "sactd3_rb_set_mix", "sactd3_rb_sample_mixed", "sactd3_mix_stats",
     "sactd3_policy_device", "sactd3_policy", "sactd3_policy_stats",
-    "sactd3_get_config", "sactd3_rb_extend_records_device",
+    "sactd3_get_config", "sactd3_rb_extend_records_device", "sactd3_batch_generation",
 ]
 
 # every symbol include/sactd3_env.h declares (tests/test_env_host.py checks the header against this list)
@@ -184,6 +184,7 @@ def load_library():
         "sactd3_set_adam_state": (C.c_int, [vp, C.c_int, fp, fp, C.c_int64]),
         "sactd3_rb_extend": (C.c_int, [vp, fp, fp, fp, fp, u8p, C.c_int]),
         "sactd3_rb_len": (C.c_int64, [vp]),
+        "sactd3_batch_generation": (C.c_int64, [vp]),
         "sactd3_rb_layout": (C.c_int, [vp, C.POINTER(C.c_int32)]),
         "sactd3_rb_extend_device": (C.c_int, [vp, C.c_void_p, C.c_int]),
         "sactd3_rb_sample": (C.c_int, [vp]),

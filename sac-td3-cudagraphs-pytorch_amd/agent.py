@@ -272,15 +272,9 @@ _METRIC_SLOT = {"loss/qf_loss": 0, "loss/actor_loss": 1, "loss/alpha_loss": 2, "
                 "loss/bc_loss": 4, "vitals/bc_lambda": 5}   # SACTD3_M_* (the last two: written by a TD3+BC engine only)
 
 
-def _bump_generation(engine: Engine) -> int:
-    """the engine's batch slot has new rows: handles made for the old ones go stale (see StaleBatchError)"""
-    engine._batch_generation = getattr(engine, "_batch_generation", 0) + 1
-    return engine._batch_generation
-
-
 class StaleBatchError(RuntimeError):
-    """A BatchHandle names THE batch slot of the engine, not a copy: once a later `rb.sample()` (or a caller-owned batch) has
-    refilled the slot, an older handle no longer stands for the rows it was made for.  The reference's loop never keeps one
+    """A BatchHandle names THE batch slot of the engine, not a copy: once any later engine call has refilled the slot (the engine
+    counts them: Engine.batch_generation), an older handle no longer stands for the rows it was made for.  The reference's loop never keeps one
     (orchestrator.py:338-348 samples, updates, drops); a caller that does gets this error instead of a silent update on the
     newest sample."""
 
@@ -294,12 +288,12 @@ class BatchHandle(dict):
     def __init__(self, engine: Engine, generation: int = 0, device: bool = False):
         super().__init__()
         self._engine = engine
-        self._generation = generation      # which rb.sample() filled the batch slot when this handle was made (see StaleBatchError)
+        self._generation = generation      # Engine.batch_generation() when this handle was made (see StaleBatchError)
         self._device = device              # key access: device tensors (one read-out launch, cached) instead of numpy arrays
         self._cache: Optional[Dict[str, Any]] = None
 
     def _is_current(self) -> bool:
-        return getattr(self._engine, "_batch_generation", 0) == self._generation
+        return self._engine.batch_generation() == self._generation
 
     def on_device(self, out: Optional[Mapping[str, Any]] = None) -> Dict[str, Any]:
         """The batch as a dict of tensors on the engine's device (include/sactd3.h: sactd3_read_batch_device), all keys filled by ONE
@@ -378,7 +372,7 @@ class ReplayBuffer:
         return self._engine
 
     def _new_handle(self, eng: Engine, n_step: bool = False) -> BatchHandle:
-        h = BatchHandle(eng, _bump_generation(eng), device=self.device_batches)
+        h = BatchHandle(eng, eng.batch_generation(), device=self.device_batches)      # read behind the call that filled the slot
         h._n_step = n_step
         return h
 
@@ -619,13 +613,12 @@ class Agent:
                 raise StaleBatchError("update called with an old batch handle: the engine's batch slot holds a later sample "
                                       "(keep the rows, e.g. dict(handle), to train on them again)")
             return  # already in the engine's batch slot (a device-backed handle too: its tensors are copies OF the slot)
-        _bump_generation(self.engine)      # a caller-owned batch replaces the slot
         five = (batch["observations"], batch["actions"], batch["rewards"], batch["next_observations"], batch["dones"])
         dev = _device_route(self.engine, *five)
         if dev is not None:
             self.engine.load_batch_device(dev[0], dev[1], _producer_stream(five[0], self.engine.cfg.device_id))
             return
-        self.engine.load_batch(*[_np(x) for x in five])
+        self.engine.load_batch(*[_np(x) for x in five])      # (either call replaces the slot's rows: older handles go stale)
 
     def predict(self, in_td: Mapping[str, Any], *, explore: bool) -> np.ndarray:
         """agents/agent.py:172-181 -> np.ndarray[n, ac_dim] float32 on the host."""
@@ -834,7 +827,6 @@ class Agent:
         else:
             n_step, stride = _n_step_args("iteration", n_step, stride)
             self.engine.step_sampled(do_actor, beta=None if beta is None else float(beta), n_step=n_step, stride=stride)
-        _bump_generation(self.engine)      # the fused step drew a new sample
         self.qnet_updates_so_far += 1
         if do_actor:
             self.actor_updates_so_far += self.engine.cfg.actor_update_delay

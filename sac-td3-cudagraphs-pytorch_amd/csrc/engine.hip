@@ -133,7 +133,8 @@ struct sactd3_engine {
   // graph (G_QW).  nstep: slot 0 was filled by an n-step staging (ns_k / ns_last describe its rows).  td_valid: e->q / e->y belong to a
   // critic update on the rows now in bs[cur] (sactd3_td_errors_device, sactd3_prio_update_from_td).  Written by the two transitions
   // slot_refilled / slot_trained alone -- and by slot_set_weighted, for sactd3_batch_weights_device, which changes `weighted` only.
-  struct SlotState { int cur = 0; bool weighted = false, nstep = false, td_valid = false; } slot;
+  // generation: how often the rows that read_batch reports were replaced (sactd3_batch_generation); it only ever grows.
+  struct SlotState { int cur = 0; bool weighted = false, nstep = false, td_valid = false; int64_t generation = 0; } slot;
   // chain_ready = v (0 / 1): the previous sactd3_step_period left the opening pair of the next period precomputed in slot (v ? 3 : 0)
   // and nothing has touched the state it depends on since (parameters, ring length, counters, noise injection, the slots);
   // -1: not so -- the next period starts with the opening graph.  Every state-changing ABI call resets it (CHAIN_BREAK).
@@ -272,12 +273,14 @@ struct sactd3_engine {
 #define CHAIN_BREAK(e) do { (e)->chain_ready = -1; } while (0)
 // The two transitions of sactd3_engine::slot.  slot_refilled: slot 0 was filled outside an update -- it is the current slot, e->q / e->y
 // are no longer its rows, and it carries weights / n-step chains only if this refill staged them.
-static inline void slot_refilled(sactd3_engine* e, bool weighted, bool nstep) { e->slot = {0, weighted, nstep, false}; }
+// The generation counts new rows: a refill is one; so is a fused update, which drew its own sample; an update on the rows a refill left
+// (sactd3_update_qnets, the tail of sactd3_step_sampled) is none.  These two are its only writers.
+static inline void slot_refilled(sactd3_engine* e, bool weighted, bool nstep) { e->slot = {0, weighted, nstep, false, e->slot.generation + 1}; }
 // slot_trained: a critic update ran on `slot`.  fused: it was part of an iteration that drew its own sample (sactd3_step and the period
 // graphs: a uniform 1-step draw, never weighted); otherwise (sactd3_update_qnets) the slot keeps what its refill staged.
 static inline void slot_trained(sactd3_engine* e, int slot, bool fused) {
   e->slot.cur = slot; e->slot.td_valid = true;
-  if (fused) e->slot.weighted = e->slot.nstep = false;
+  if (fused) { e->slot.weighted = e->slot.nstep = false; ++e->slot.generation; }
 }
 static inline void slot_set_weighted(sactd3_engine* e, bool weighted) { e->slot.weighted = weighted; }
 // the batch slot that iteration i of a period (or cut-short period) of variant v trains on (see BatchSlot, enqueue_period)
@@ -2035,6 +2038,7 @@ int sactd3_rb_extend_device(sactd3_engine* e, const float* records, int n) {
 }
 
 int64_t sactd3_rb_len(const sactd3_engine* e) { return e ? e->rb_len : SACTD3_EINVAL; }
+int64_t sactd3_batch_generation(const sactd3_engine* e) { return e ? e->slot.generation : SACTD3_EINVAL; }
 
 int sactd3_rb_sample(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;

@@ -281,6 +281,10 @@ class Engine:
     def rb_len(self) -> int:
         return int(self._ck(self.lib.sactd3_rb_len(self._h)))
 
+    def batch_generation(self) -> int:
+        """sactd3_batch_generation: grows with every call that puts new rows into the batch slot; the engine is its only writer"""
+        return int(self._ck(self.lib.sactd3_batch_generation(self._h)))
+
     def rb_sample(self) -> None:
         self._ck(self.lib.sactd3_rb_sample(self._h))
 

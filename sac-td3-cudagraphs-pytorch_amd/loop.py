@@ -511,7 +511,6 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     while i < num_updates:
         end = min(num_updates, (i // every + 1) * every) if every > 0 else num_updates
         eng.run_iterations(i, end - i)
-        eng._batch_generation = getattr(eng, "_batch_generation", 0) + 1      # every iteration drew a new sample: older batch handles are stale
         agent.qnet_updates_so_far += end - i
         agent.actor_updates_so_far += delay * len(range(-(-i // period) * period, end, period))      # the iterations with i % period == 0
         i = end

@@ -118,6 +118,18 @@ def five(n=8, o=11, a=3, **over):
     return [d[k] for k in ("obs", "act", "rew", "nobs", "done")]
 
 
+class SlotGeneration:
+    """a fake engine's share of the engine's rule (include/sactd3.h: sactd3_batch_generation): it calls slot_refilled() from every
+    method that puts new rows into the batch slot, and from no other"""
+    _generation = 5
+
+    def batch_generation(self):
+        return self._generation
+
+    def slot_refilled(self):
+        self._generation += 1
+
+
 # ---- observed parity deltas: tests report what they measured, the session writes it out (tests/conftest.py), and the
 # tolerances in the tests are set from these records (<= 2x the observed value, never above north_star's 1e-5 per step)
 OBSERVED = {}

@@ -10,7 +10,7 @@ import pytest
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod
-from tests.helpers import FakeDeviceArray
+from tests.helpers import FakeDeviceArray, SlotGeneration
 
 O, A, N = 11, 3, 8
 ENGINE = SimpleNamespace(device_inputs=True, cfg=SimpleNamespace(ob_dim=O, ac_dim=A, device_id=0, batch_size=N))
@@ -104,7 +104,7 @@ def test_wrong_dtypes_and_places_are_a_type_error():
             agent_mod._device_outputs(ENGINE, N, {key: bad}, alloc=fake_alloc)
 
 
-class StubEngine:
+class StubEngine(SlotGeneration):
     """the engine as the mirror's replay buffer sees it; the device read-out raises"""
 
     def __init__(self):
@@ -113,6 +113,7 @@ class StubEngine:
 
     def rb_sample(self):
         self.calls.append("rb_sample")
+        self.slot_refilled()
 
     def read_batch(self):
         self.calls.append("read_batch")
@@ -135,7 +136,7 @@ def test_default_replay_buffer_reads_back_to_numpy_and_never_calls_the_device_en
     assert np.array_equal(batch["terminations"], batch["dones"]) and np.array_equal(batch["index"], np.arange(N))
     assert eng.calls == ["rb_sample", "read_batch"]                        # one read-back, cached
     with pytest.raises(AssertionError, match="device read-out"):          # ... and the stub does notice a device read-out
-        pkg.BatchHandle(eng, eng._batch_generation).on_device(out={k: fake_alloc((N,) if k == "index" else (N, w), kind)
+        pkg.BatchHandle(eng, eng.batch_generation()).on_device(out={k: fake_alloc((N,) if k == "index" else (N, w), kind)
                                                                    for k, w, kind in (("observations", O, "f4"), ("actions", A, "f4"), ("rewards", 1, "f4"),
                                                                                       ("next_observations", O, "f4"), ("dones", 1, "b1"), ("index", 1, "i8"))})
 
@@ -146,14 +147,13 @@ def test_device_backed_handle_asks_for_one_readout_and_goes_stale_like_the_host_
             self.calls.append(("read_batch_device", len(fields), consumer_stream, ordered))
 
     eng = Recorder()
-    eng._batch_generation = 3
     outs = {k: fake_alloc((N,) if k == "index" else (N, w), kind) for k, w, kind in
             (("observations", O, "f4"), ("actions", A, "f4"), ("rewards", 1, "f4"), ("next_observations", O, "f4"), ("dones", 1, "b1"), ("index", 1, "i8"))}
-    h = pkg.BatchHandle(eng, 3, device=True)
+    h = pkg.BatchHandle(eng, eng.batch_generation(), device=True)
     got = h.on_device(out=outs)
     assert got["observations"] is outs["observations"] and got["terminations"] is outs["dones"]
     assert eng.calls == [("read_batch_device", 6, 0, True)]               # one launch for all keys; not torch: the default stream
-    eng._batch_generation = 4
+    eng.slot_refilled()                                                    # a later refill of the slot
     with pytest.raises(pkg.StaleBatchError):
         h.on_device(out=outs)
     with pytest.raises(pkg.StaleBatchError):

@@ -93,7 +93,8 @@ def test_batch_slot_from_device_fields_equals_load_batch(algo, env, B):
 # ------------------------------------------------------------------------------------------ 3. the mirror, as the reference's loop drives it
 def mirror_run(device_inputs, as_numpy=False):
     """12 iterations of orchestrator.py:317-352 on Agent + ReplayBuffer: rb.extend with a dict of CUDA tensors (:100-113), update_qnets /
-    update_actor with a dict of CUDA tensors (:338-348), update_targ_nets."""
+    update_actor with a dict of CUDA tensors (:338-348), update_targ_nets.  `slot_refills` on the agent returned: how far the run moved
+    the engine's batch generation."""
     o, a, n, B = 11, 3, 4, 64
     cfg = SimpleNamespace(**{**Hps.sac(batch_size=B).__dict__, "seed": 0, "num_envs": n, "rb_capacity": 500})
     torch.manual_seed(0)
@@ -101,6 +102,7 @@ def mirror_run(device_inputs, as_numpy=False):
                  torch.device(DEV), cfg, P.ReplayBuffer(cfg.rb_capacity))
     track(ag.engine).device_inputs = device_inputs
     put = (lambda t: t.numpy()) if as_numpy else (lambda t: t.to(DEV))
+    before = ag.engine.batch_generation()
 
     def td(five):
         obs, act, rew, nobs, done = five
@@ -117,6 +119,7 @@ def mirror_run(device_inputs, as_numpy=False):
                 ag.update_actor(batch)
                 ag.actor_updates_so_far += 1
         ag.update_targ_nets()
+    ag.slot_refills = ag.engine.batch_generation() - before
     return ag
 
 
@@ -126,16 +129,18 @@ def test_mirror_keeps_device_tensors_on_the_device():
     assert (s["device_extends"], s["device_rows"], s["device_batches"], s["ordered_calls"]) == (12, 48, 20, 32)
     assert list(H.engine.boundary_stats().values()) == [0, 0, 0, 0]
     assert list(N.engine.boundary_stats().values()) == [0, 0, 0, 0]      # numpy never takes the device route
+    assert D.slot_refills == H.slot_refills == N.slot_refills == 12 + 8      # (StaleBatchError behaviour: a generation per staged caller-owned batch, on every route)
     for other in (H, N):
         assert_same_state(D.engine, other.engine)
         assert len(D.rb) == len(other.rb) == 48
         idx = np.arange(64) % 48
-        D.engine.rb_sample_with_indices(idx)
-        other.engine.rb_sample_with_indices(idx)
+        for eng in (D.engine, other.engine):
+            gen = eng.batch_generation()
+            eng.rb_sample_with_indices(idx)
+            assert eng.batch_generation() == gen + 1                    # a direct refill counts, exactly once
         x, y = D.engine.read_batch(), other.engine.read_batch()
         for k in x:
             assert np.array_equal(x[k], y[k]), ("ring", k)
-        assert D.engine._batch_generation == other.engine._batch_generation == 20      # (StaleBatchError behaviour: same generations)
 
 
 # ------------------------------------------------------------------------------------------ 4. stream order, both directions

@@ -404,7 +404,7 @@ def test_mirror_hands_out_device_batches_like_the_reference():
     assert tuple(batch["rewards"].shape) == (B, 1) and tuple(batch["actions"].shape) == (B, a) and tuple(batch["next_observations"].shape) == (B, o)
     assert batch["index"].dtype == torch.int64 and tuple(batch["index"].shape) == (B,)
     assert batch["observations"] is obs and eng.readout_stats()["batch_readouts"] == 1      # one launch filled every key; cached
-    want = P.BatchHandle(eng, eng._batch_generation)             # a default handle on the same slot: numpy through read_batch
+    want = P.BatchHandle(eng, eng.batch_generation())            # a default handle on the same slot: numpy through read_batch
     for k in KEYS + ("terminations",):
         assert isinstance(want[k], np.ndarray) and np.array_equal(batch[k].cpu().numpy(), want[k]), k
     with pytest.raises(P.StaleBatchError):

@@ -122,9 +122,9 @@ def test_views_in_and_out_and_the_host_call(shape):
                 base = torch.full((2, n + 3, 3), SENTINEL, device=DEV)
                 view = base[:, 1:, 1:2]
                 td = {"observations": big[:, 1:1 + o]} if policy else {"observations": big[:, 1:1 + o], "actions": wide[:, 3:3 + a]}
-                gen = getattr(eng, "_batch_generation", 0)
+                gen = eng.batch_generation()
                 got = ag.q_values(td, target=target, out=view)
-                assert getattr(eng, "_batch_generation", 0) == gen
+                assert eng.batch_generation() == gen
                 assert tuple(got.shape) == (2, n, 1) and got.data_ptr() == view.data_ptr()
                 host = base.cpu().numpy()
                 assert same_bits(host[:, 1:1 + n, 1], want), (n, target, policy)

@@ -9,6 +9,7 @@ import torch
 import sac_td3_cudagraphs_pytorch_amd as P
 from sac_td3_cudagraphs_pytorch_amd import schema
 from oracle.sac_td3_ref import DetPolicy, QNet, SquashedGaussPolicy
+from tests.helpers import SlotGeneration
 
 
 @pytest.mark.parametrize("o,a,ln", [(11, 3, True), (17, 6, False), (376, 17, True)])
@@ -75,13 +76,14 @@ def test_compare_hps_reports_added_removed_changed_like_the_reference():
 def test_batch_handle_goes_stale_when_the_slot_is_refilled():
     """A BatchHandle names the engine's ONE batch slot: after a later rb.sample() an older handle is refused (StaleBatchError)
     instead of silently standing for the newest sample.  (Host logic only: a stub engine counts the calls.)"""
-    class StubEngine:
+    class StubEngine(SlotGeneration):
         def __init__(self):
             self.cfg = SimpleNamespace(batch_size=4)
             self.samples = 0
 
         def rb_sample(self):
             self.samples += 1
+            self.slot_refilled()
 
         def rb_len(self):
             return 10

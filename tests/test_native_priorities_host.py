@@ -12,6 +12,7 @@ import torch
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, loop
 from tests import priorities_ref as pref
+from tests.helpers import SlotGeneration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sactd3_prio_enable", "sactd3_rb_sample_prioritized", "sactd3_prio_set_uniforms", "sactd3_prio_update_from_td",
@@ -81,17 +82,17 @@ def test_train_rejects_prioritized_with_the_fused_iteration_or_a_sampler():
         loop.train(cfg, None, None, fused=False, prioritized=dict(gamma=1.0))
 
 
-class RecordingEngine:
+class RecordingEngine(SlotGeneration):
     def __init__(self):
         self.cfg = SimpleNamespace(batch_size=8, device_id=0)
         self.calls = []
-        self._batch_generation = 5
 
     def prio_enable(self, alpha, eps):
         self.calls.append(("enable", alpha, eps))
 
     def rb_sample_prioritized(self, beta):
         self.calls.append(("sample", beta))
+        self.slot_refilled()
 
     def prio_update_from_td(self):
         self.calls.append(("from_td",))
@@ -110,7 +111,7 @@ def test_replay_buffer_wants_enable_priorities_first_and_bumps_the_generation():
     rb._bind(eng)
     assert eng.calls == [("enable", 0.7, 1e-3)]
     h = rb.sample_prioritized(8, 0.5)
-    assert eng.calls[-1] == ("sample", 0.5) and eng._batch_generation == 6 and h._is_current()      # as sample_at does
+    assert eng.calls[-1] == ("sample", 0.5) and eng.batch_generation() == 6 and h._is_current()      # as sample_at does
     rb.update_priorities()
     assert eng.calls[-1] == ("from_td",)
     with pytest.raises(ValueError, match="both"):

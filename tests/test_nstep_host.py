@@ -13,6 +13,7 @@ import pytest
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, loop
 from tests import nstep_ref as nref
+from tests.helpers import SlotGeneration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sactd3_rb_sample_nstep_device", "sactd3_rb_sample_nstep", "sactd3_rb_sample_prioritized_nstep", "sactd3_nstep_info_device",
@@ -142,26 +143,29 @@ def test_null_engine_is_an_error_code_not_a_crash():
     assert lib.sactd3_nstep_stats(None, out) == _lib.EINVAL
 
 
-class RecordingEngine:
+class RecordingEngine(SlotGeneration):
     def __init__(self):
         self.cfg = SimpleNamespace(batch_size=8, device_id=0)
         self.calls = []
-        self._batch_generation = 5
 
     def prio_enable(self, alpha, eps):
         self.calls.append(("enable", alpha, eps))
 
     def rb_sample(self):
         self.calls.append(("sample",))
+        self.slot_refilled()
 
     def rb_sample_nstep(self, steps, stride):
         self.calls.append(("sample_nstep", steps, stride))
+        self.slot_refilled()
 
     def rb_sample_prioritized(self, beta):
         self.calls.append(("prio", beta))
+        self.slot_refilled()
 
     def rb_sample_prioritized_nstep(self, beta, steps, stride):
         self.calls.append(("prio_nstep", beta, steps, stride))
+        self.slot_refilled()
 
 
 def test_replay_buffer_refuses_bad_n_step_before_it_touches_the_engine():
@@ -184,7 +188,7 @@ def test_replay_buffer_refuses_bad_n_step_before_it_touches_the_engine():
     assert rb.sample(8, n_step=1, stride=4) is not None and eng.calls[-1] == ("sample",)
     h3 = rb.sample(8, n_step=3, stride=4)
     assert eng.calls[-1] == ("sample_nstep", 3, 4) and h3._n_step and h3._is_current() and not h1._is_current()
-    assert eng._batch_generation == 8                                  # bumped once per sampling call
+    assert eng.batch_generation() == 8                                  # bumped once per sampling call
     rb.sample_prioritized(8, 0.5)
     assert eng.calls[-1] == ("prio", 0.5)
     hp = rb.sample_prioritized(8, 0.5, n_step=16, stride=2)

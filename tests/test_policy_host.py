@@ -14,7 +14,7 @@ import torch
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, engine as engine_mod, launcher, loop
-from tests.helpers import FakeDeviceArray
+from tests.helpers import FakeDeviceArray, SlotGeneration
 
 O, A = 11, 3
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sactd3.h")
@@ -127,14 +127,13 @@ def test_engine_policy_asks_for_the_outputs_the_arguments_imply():
 
 
 # ------------------------------------------------------------------------------------------ Agent.policy against a recording engine
-class RecordingEngine:
+class RecordingEngine(SlotGeneration):
     device_inputs = True
     policy_outputs = engine_mod.Engine.policy_outputs
 
     def __init__(self, td3=False):
         self.cfg = SimpleNamespace(ob_dim=O, ac_dim=A, device_id=0, prefer_td3_over_sac=td3)
         self.calls, self.host_calls = [], []
-        self._batch_generation = 5
 
     def policy_device(self, *args):
         self.calls.append(args)
@@ -166,7 +165,7 @@ def test_device_rows_go_to_the_engine_where_they_are():
     assert (optr, old, n, target, stream) == (obs.ptr, O + 5, 8, False, 0)
     assert io == {"actions": (act.ptr, A), "mode": (out["mode"].ptr, A + 4), "mean": (out["mean"].ptr, A), "log_std": (out["log_std"].ptr, A),
                   "action_logp": (out["log_prob"].ptr, 1)}
-    assert ag.engine.host_calls == [] and ag.engine._batch_generation == 5 and obs.log == []
+    assert ag.engine.host_calls == [] and ag.engine.batch_generation() == 5 and obs.log == []
 
 
 def test_sample_and_eps_name_the_sample_keys():
@@ -220,7 +219,7 @@ def test_host_rows_take_the_host_call_and_come_back_as_numpy():
     assert (got["sample_log_prob"] == 4).all() and (got["eps"] == 5).all() and (got["log_prob"] == 6).all()
     (o_, a_, e_, sample, target), = ag.engine.host_calls
     assert np.array_equal(o_, obs) and np.array_equal(a_, act.numpy()) and e_ is None and sample is True and target is False
-    assert ag.engine.calls == [] and ag.engine._batch_generation == 5
+    assert ag.engine.calls == [] and ag.engine.batch_generation() == 5
 
 
 # ------------------------------------------------------------------------------------------ loop, launcher

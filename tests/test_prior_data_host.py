@@ -14,6 +14,7 @@ import sac_td3_cudagraphs_pytorch_amd as pkg
 from oracle.replay_ref import sample_indices
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, engine as engine_mod, launcher, loop
 from tests import mix_ref
+from tests.helpers import SlotGeneration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sactd3_rb_pin", "sactd3_rb_pinned", "sactd3_rb_set_mix", "sactd3_rb_sample_mixed", "sactd3_mix_stats")
@@ -204,19 +205,20 @@ def test_engine_pin_and_stats_bindings():
 
 
 # ------------------------------------------------------------------------------------------ Agent.iteration, ReplayBuffer, loop.train
-class RecordingEngine:
+class RecordingEngine(SlotGeneration):
     """today's stub signatures plus the new calls; step_sampled takes prior_rows"""
 
     def __init__(self, delay=2, held=40):
         self.cfg = SimpleNamespace(batch_size=8, device_id=0, actor_update_delay=delay, bc_alpha=0.0, autotune=0)
         self.calls, self.held = [], held
-        self._batch_generation = 5
 
     def step(self, do_actor):
         self.calls.append(("step", do_actor))
+        self.slot_refilled()
 
     def step_sampled(self, do_actor, *, beta=None, n_step=1, stride=1, prior_rows=None):
         self.calls.append(("step_sampled", do_actor, beta, n_step, stride, prior_rows))
+        self.slot_refilled()
 
     def rb_len(self):
         return self.held
@@ -233,9 +235,11 @@ class RecordingEngine:
 
     def rb_sample_mixed(self):
         self.calls.append(("sample_mixed",))
+        self.slot_refilled()
 
     def rb_sample(self):
         self.calls.append(("sample",))
+        self.slot_refilled()
 
     def update_qnets(self):
         self.calls.append(("qnets",))
@@ -255,6 +259,7 @@ class OldSignatureEngine(RecordingEngine):
 
     def step_sampled(self, do_actor, *, beta=None, n_step=1, stride=1):
         self.calls.append(("step_sampled", do_actor, beta, n_step, stride))
+        self.slot_refilled()
 
 
 def stub_agent(delay=2, engine=RecordingEngine):
@@ -274,7 +279,8 @@ def test_agent_iteration_passes_prior_rows_only_when_used():
     ag.iteration(0, prior_rows=4)
     ag.iteration(1, prior_rows=0)
     assert ag.engine.calls == [("step_sampled", True, None, 1, 1, 4), ("step_sampled", False, None, 1, 1, 0)]
-    assert (ag.qnet_updates_so_far, ag.actor_updates_so_far) == (2, 2) and ag.engine._batch_generation == 7
+    assert (ag.qnet_updates_so_far, ag.actor_updates_so_far) == (2, 2)
+    assert ag.engine.batch_generation() == 7                           # step_sampled itself counts the new rows, not Agent.iteration
     for kw in (dict(beta=0.4), dict(n_step=3, stride=4)):
         with pytest.raises(ValueError, match="prior_rows"):
             ag.iteration(2, prior_rows=4, **kw)

@@ -13,24 +13,24 @@ import torch
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, loop
-from tests.helpers import FakeDeviceArray, five
+from tests.helpers import FakeDeviceArray, SlotGeneration, five
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 O, A, B = 11, 3, 8
 NEW = ("sactd3_rb_sample_indices_device", "sactd3_batch_weights_device", "sactd3_td_errors_device", "sactd3_priority_stats")
 
 
-class RecordingEngine:
+class RecordingEngine(SlotGeneration):
     """what the three methods need of an engine; records what it is handed, in order"""
     device_inputs = True
 
     def __init__(self):
         self.cfg = SimpleNamespace(ob_dim=O, ac_dim=A, device_id=0, batch_size=B)
         self.calls = []
-        self._batch_generation = 5
 
     def rb_sample_indices_device(self, *args):
         self.calls.append(("index",) + args)
+        self.slot_refilled()
 
     def batch_weights_device(self, *args):
         self.calls.append(("weights",) + args)
@@ -40,6 +40,7 @@ class RecordingEngine:
 
     def load_batch_device(self, fields, n, stream):
         self.calls.append(("load", n))
+        self.slot_refilled()
 
     def update_qnets(self):
         self.calls.append(("update_qnets",))
@@ -72,9 +73,10 @@ def test_header_declares_and_the_binding_covers_the_four_entry_points():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sactd3.h")).read(), flags=re.S)
     declared = set(re.findall(r"\b(sactd3_[a-z0-9_]+)\s*\(", src))
     lib = pkg.load_library()
-    for name in NEW:
+    for name in NEW + ("sactd3_batch_generation",):
         assert name in declared and name in _lib.SYMBOLS, name
         assert getattr(lib, name).argtypes is not None, name
+    assert lib.sactd3_batch_generation.restype is C.c_int64
     assert "#define SACTD3_ABI_VERSION 1" in src and lib.sactd3_abi_version() == 1
 
 
@@ -85,6 +87,7 @@ def test_null_engine_is_refused_without_a_device():
     assert lib.sactd3_batch_weights_device(None, C.c_void_p(8192), 1, B, None, _lib.SRC_ORDERED) == _lib.EINVAL
     assert lib.sactd3_td_errors_device(None, C.c_void_p(4096), 1, B, None, _lib.DST_ORDERED) == _lib.EINVAL
     assert lib.sactd3_priority_stats(None, st) == _lib.EINVAL
+    assert lib.sactd3_batch_generation(None) == _lib.EINVAL
 
 
 # ------------------------------------------------------------------------------------------ ReplayBuffer.sample_at
@@ -142,7 +145,7 @@ def test_sample_at_refusals():
     for n in (B - 1, B + 1):
         with pytest.raises(ValueError, match="expected 8 indices"):
             buffer(eng).sample_at(index(n))
-    assert eng.calls == [] and eng._batch_generation == 5                                              # nothing reached the engine
+    assert eng.calls == [] and eng.batch_generation() == 5                                              # nothing reached the engine
     with pytest.raises(AssertionError, match="attached"):
         agent_mod.ReplayBuffer(64).sample_at(index())
 
@@ -151,9 +154,9 @@ def test_sample_at_bumps_the_generation_and_older_handles_go_stale():
     eng = RecordingEngine()
     rb, ag = buffer(eng), mirror(eng)
     first = rb.sample_at(index(), FakeDeviceArray((B,)))
-    assert eng._batch_generation == 6 and first._is_current()
+    assert eng.batch_generation() == 6 and first._is_current()
     second = rb.sample_at(index())
-    assert eng._batch_generation == 7 and second._is_current() and not first._is_current()
+    assert eng.batch_generation() == 7 and second._is_current() and not first._is_current()
     with pytest.raises(agent_mod.StaleBatchError):
         ag.update_qnets(first)
     with pytest.raises(agent_mod.StaleBatchError):
@@ -173,7 +176,7 @@ def test_update_qnets_stages_weight_key_behind_the_batch():
         ag, w = mirror(), FakeDeviceArray(wshape, strides=strides)
         got = ag.update_qnets(batch_of(_weight=w))
         assert ag.engine.calls == [("load", B), ("weights", w.ptr, ld, B, 0), ("update_qnets",)] and list(got) == ["loss/qf_loss"]
-        assert ag.engine._batch_generation == 6                              # a caller-owned batch replaces the slot
+        assert ag.engine.batch_generation() == 6                              # a caller-owned batch replaces the slot
     ag = mirror()
     ag.update_qnets(batch_of())                                              # no key: as before
     ag.update_qnets(None)
@@ -216,7 +219,7 @@ def test_td_errors_addresses_out_like_q_values():
     ag, out = mirror(), Sliceable((2, B + 4, 1))                             # more rows than the batch: the first B are returned
     assert ag.td_errors(out=out) == ("rows", (slice(None), slice(None, B)))
     assert ag.engine.calls == [("td", out.ptr, 1, B + 4, 0)]
-    assert ag.engine._batch_generation == 5                                  # a read-out: handles stay current
+    assert ag.engine.batch_generation() == 5                                  # a read-out: handles stay current
 
 
 def test_td_errors_refusals():

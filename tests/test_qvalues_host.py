@@ -10,19 +10,18 @@ import torch
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod
-from tests.helpers import FakeDeviceArray
+from tests.helpers import FakeDeviceArray, SlotGeneration
 
 O, A = 11, 3
 
 
-class RecordingEngine:
+class RecordingEngine(SlotGeneration):
     """what Agent.q_values needs of an engine; records what it is handed"""
     device_inputs = True
 
     def __init__(self):
         self.cfg = SimpleNamespace(ob_dim=O, ac_dim=A, device_id=0)
         self.calls, self.host_calls = [], []
-        self._batch_generation = 5
 
     def q_values_device(self, *args):
         self.calls.append(args)
@@ -49,7 +48,7 @@ def test_contiguous_fields_and_out_go_to_the_engine_as_they_are():
     assert ag.q_values({"observations": obs, "actions": act}, target=True, out=out) is out
     # (pointer, row stride) of obs and actions, n, target, then `out`: pointer, row stride, net stride; not a torch array: the default stream
     assert ag.engine.calls == [(obs.ptr, O, act.ptr, A, 8, False, out.ptr, 1, 8, 0), (obs.ptr, O, act.ptr, A, 8, True, out.ptr, 1, 8, 0)]
-    assert ag.engine.host_calls == [] and ag.engine._batch_generation == 5
+    assert ag.engine.host_calls == [] and ag.engine.batch_generation() == 5
 
 
 def test_a_missing_actions_key_is_the_policy_form():
@@ -156,12 +155,12 @@ def test_host_arrays_take_the_host_call_and_come_back_as_numpy():
     (o_, a_, target), = ag.engine.host_calls
     assert target is True and np.array_equal(o_, obs) and np.array_equal(a_, act.numpy())
     ag.q_values({"observations": obs})
-    assert ag.engine.host_calls[1][1] is None and ag.engine.calls == [] and ag.engine._batch_generation == 5
+    assert ag.engine.host_calls[1][1] is None and ag.engine.calls == [] and ag.engine.batch_generation() == 5
 
 
 def test_a_batch_handle_stays_current_across_a_score():
     eng = RecordingEngine()
-    handle = agent_mod.BatchHandle(eng, eng._batch_generation)
+    handle = agent_mod.BatchHandle(eng, eng.batch_generation())
     ag = mirror(eng)
     ag.q_values({"observations": FakeDeviceArray((8, O)), "actions": FakeDeviceArray((8, A))}, out=FakeDeviceArray((2, 8, 1)))
     ag.q_values({"observations": np.zeros((8, O), np.float32)})

@@ -10,6 +10,7 @@ import pytest
 
 import sac_td3_cudagraphs_pytorch_amd as pkg
 from sac_td3_cudagraphs_pytorch_amd import _lib, agent as agent_mod, engine as engine_mod, loop
+from tests.helpers import SlotGeneration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sactd3_step_sampled", "sactd3_step_sampled_stats")
@@ -67,23 +68,25 @@ def test_engine_step_sampled_fills_the_struct():
     eng._h = None                                                      # (nothing for __del__ to destroy)
 
 
-class RecordingEngine:
+class RecordingEngine(SlotGeneration):
     def __init__(self, delay=2):
         self.cfg = SimpleNamespace(batch_size=8, device_id=0, actor_update_delay=delay)
         self.calls = []
-        self._batch_generation = 5
 
     def step(self, do_actor):
         self.calls.append(("step", do_actor))
+        self.slot_refilled()
 
     def step_sampled(self, do_actor, *, beta=None, n_step=1, stride=1):
         self.calls.append(("step_sampled", do_actor, beta, n_step, stride))
+        self.slot_refilled()
 
     def prio_enable(self, alpha, eps):
         self.calls.append(("enable", alpha, eps))
 
     def rb_sample_prioritized(self, beta):
         self.calls.append(("prio", beta))
+        self.slot_refilled()
 
     def read_metrics(self):
         return {"loss/qf_loss": 0.0}
@@ -108,7 +111,7 @@ def test_agent_iteration_maps_its_keywords_and_keeps_the_counters():
     ag.iteration(3, beta=0.7, n_step=3, stride=4)
     ag.iteration(4, n_step=2, stride=8)
     assert eng.calls[2:] == [("step_sampled", False, 0.4, 1, 1), ("step_sampled", True, 0.7, 3, 4), ("step_sampled", False, None, 2, 8)]
-    assert (ag.qnet_updates_so_far, ag.actor_updates_so_far) == (5, 4) and eng._batch_generation == 10
+    assert (ag.qnet_updates_so_far, ag.actor_updates_so_far) == (5, 4) and eng.batch_generation() == 10
     n = len(eng.calls)
     with pytest.raises(ValueError, match="stride"):
         ag.iteration(5, n_step=3)                                      # as ReplayBuffer.sample
@@ -119,7 +122,7 @@ def test_agent_iteration_maps_its_keywords_and_keeps_the_counters():
             ag.iteration(5, n_step=bad, stride=4)
     with pytest.raises(TypeError):
         ag.iteration(5, 0.4)                                           # keyword-only
-    assert len(eng.calls) == n and ag.qnet_updates_so_far == 5 and eng._batch_generation == 10      # refused before the engine is touched
+    assert len(eng.calls) == n and ag.qnet_updates_so_far == 5 and eng.batch_generation() == 10      # refused before the engine is touched
 
 
 def test_an_old_batch_handle_is_stale_behind_a_prioritised_iteration():

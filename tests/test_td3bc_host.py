@@ -14,6 +14,7 @@ import sac_td3_cudagraphs_pytorch_amd as P
 from sac_td3_cudagraphs_pytorch_amd import _lib, launcher, loop
 from sac_td3_cudagraphs_pytorch_amd.engine import Engine
 from tests import td3bc_ref as R
+from tests.helpers import SlotGeneration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -147,7 +148,7 @@ def test_load_dataset_keeps_dones_apart_and_refuses_what_does_not_fit():
 
 # ------------------------------------------------------------------------------------------ train_offline
 
-class FakeEngine:
+class FakeEngine(SlotGeneration):
     """records run_iterations calls and expands them with Engine.run_iterations' own routing"""
 
     def __init__(self, delay=2, td3=True):
@@ -161,6 +162,7 @@ class FakeEngine:
 
     def run_iterations(self, i0, n):
         self.runs.append((i0, n))
+        self.slot_refilled()
         return Engine.run_iterations(self, i0, n)
 
     def read_metrics(self):
@@ -188,6 +190,7 @@ def test_train_offline_cuts_runs_at_evaluation_points_and_keeps_the_counters(del
     assert agent.qnet_updates_so_far == num
     assert agent.actor_updates_so_far == delay * len([i for i in range(num) if i % period == 0])      # as Agent.iteration counts
     assert agent.timesteps_so_far == 123                        # no env step was taken
+    assert agent.engine.batch_generation() == 5 + len(runs)     # run_iterations itself counts the new rows, not the loop
     assert out == {"loss/qf_loss": 1.0, "n": len(runs)}
     # the iterations issued are exactly 0 .. num - 1 with the actor updates at the multiples of the period
     i = 0
