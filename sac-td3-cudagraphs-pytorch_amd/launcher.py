@@ -9,6 +9,8 @@ from __future__ import annotations
 import os
 from typing import List, Optional, Tuple
 
+from . import loop      # (numpy only: the parent process still opens no GPU)
+
 
 def rank_info() -> Tuple[int, int, int]:
     """(rank, world_size, local_rank) from the torch.distributed.run environment (1 process: 0, 1, 0)."""
@@ -283,6 +285,35 @@ def policy_stats_plan(args) -> int:
     return n
 
 
+def native_rollout_plan(env_ids, device_env: bool, has_factory: bool, offline: bool, overlap_acting: bool) -> None:
+    """What --native_rollout excludes, checked without touching a GPU for every env id it is asked for: ValueError with a dataset or
+    --overlap_acting beside it, and whatever env_plan refuses."""
+    if offline or overlap_acting:
+        raise ValueError("--native_rollout excludes --offline_dataset and --overlap_acting")
+    for env_id in env_ids:
+        env_plan(env_id, device_env, has_factory, native_rollout=True)
+
+
+def mode_flags(args, plan) -> dict:
+    """the flags that shape the env loop, under the names run_job and train_keywords take them by (`plan`: offline_plan(args) or {})"""
+    return dict(prioritized=args.prioritized, n_step=args.n_step, one_launch=args.one_launch, prior_fraction=plan.get("prior_fraction"),
+                updates_per_step=args.updates_per_step or 1, overlap_acting=args.overlap_acting, device_env=args.device_env,
+                native_rollout=args.native_rollout, policy_stats=policy_stats_plan(args))
+
+
+def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, prior_fraction, updates_per_step, overlap_acting: bool,
+                   device_env: bool, native_rollout: bool, policy_stats: int) -> dict:
+    """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
+    job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
+    before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
+    --n_step N > 1 and --prior_fraction are issued call by call (fused=False), or with --one_launch as one graph launch per iteration."""
+    update = dict(fused=not prioritized and n_step == 1 and prior_fraction is None,
+                  prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch,
+                  prior_fraction=None if prior_fraction is None else float(prior_fraction), updates_per_step=int(updates_per_step))
+    loop.update_plan(cfg, sampler=None, **update)
+    return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats))
+
+
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
@@ -300,17 +331,11 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     from pathlib import Path
     import numpy as np
     import torch
-    from . import loop
     from .agent import Agent, ReplayBuffer
     if int(policy_stats) and algo != "sac":      # (before anything is built)
         raise ValueError("policy_stats needs algo sac: TD3's deterministic actor has no log-probability, entropy or log-std to report")
     if native_rollout:                           # (before anything is built)
-        env_plan(env_id, device_env, env_factory is not None, native_rollout=True)
-        if offline_dataset is not None or overlap_acting:
-            raise ValueError("native_rollout excludes offline_dataset and overlap_acting")
-        utd_native = dict(native_rollout=True)
-    else:
-        utd_native = {}
+        native_rollout_plan([env_id], device_env, env_factory is not None, offline_dataset is not None, overlap_acting)
     cfg = job_config(algo, env_id, seed, **over)
     o, a, bound = ENV_DIMS[env_id]
     native = env_id in NATIVE_ENVS and env_factory is None      # the two tasks this package simulates itself (env_plan)
@@ -339,30 +364,21 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     if on_gpu:                # cfg.eval_steps greedy episodes per evaluation, in lock-step on the GPU, read with one host wait
         ev.ep_gen = envs.device_episodes(envs.NativeVecEnv(NATIVE_ENVS[env_id], cfg.eval_steps, seed=seed, device=dev), agent, seed)
     t0 = time.time()
-    # --prioritized: the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4), call by call
-    # --n_step N > 1: n-step returns chained by the engine, call by call as well
-    # --one_launch: either of them (or both) as one graph launch per iteration instead
     if offline_dataset is not None:
         with np.load(offline_dataset) as z:
             data = {k: z[k] for k in z.files}
         if data["observations"].shape[1:] != (o,) or data["actions"].shape[1:] != (a,):
             raise ValueError(f"{offline_dataset}: observations / actions are {data['observations'].shape[1:]} / {data['actions'].shape[1:]}, "
                              f"{env_id} has ({o},) / ({a},)")
-        loop.load_dataset(agent, data, **(dict(pin=True) if prior_fraction is not None else {}))
-    utd = dict(updates_per_step=int(updates_per_step)) if int(updates_per_step) != 1 else {}      # (a keyword only when it is used)
-    if int(policy_stats):
-        utd["policy_stats"] = int(policy_stats)
-    utd.update(utd_native)
-    if offline_dataset is not None and prior_fraction is not None:
-        metrics = loop.train(cfg, env, agent, fused=False, evaluator=ev, overlap=overlap_acting, device_env=device_env,
-                             one_launch=one_launch, prior_fraction=float(prior_fraction), **utd)
-    elif offline_dataset is not None:
+        loop.load_dataset(agent, data, pin=prior_fraction is not None)
+    if offline_dataset is not None and prior_fraction is None:
         metrics = loop.train_offline(cfg, agent, num_updates=int(num_updates if num_updates is not None else cfg.num_timesteps),
-                                     evaluator=ev, eval_every_updates=int(cfg.eval_every),
-                                     **(dict(policy_stats=int(policy_stats)) if int(policy_stats) else {}))
+                                     evaluator=ev, eval_every_updates=int(cfg.eval_every), policy_stats=int(policy_stats))
     else:
-        metrics = loop.train(cfg, env, agent, fused=not prioritized and n_step == 1, evaluator=ev, overlap=overlap_acting, device_env=device_env,
-                             prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch, **utd)
+        kw = train_keywords(cfg, prioritized=prioritized, n_step=n_step, one_launch=one_launch, prior_fraction=prior_fraction,
+                            updates_per_step=updates_per_step, overlap_acting=overlap_acting, device_env=device_env,
+                            native_rollout=native_rollout, policy_stats=policy_stats)
+        metrics = loop.train(cfg, env, agent, evaluator=ev, **kw)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -375,11 +391,10 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     return out
 
 
-def _worker_main(args) -> int:
+def _worker_main(args, plan, flags) -> int:
     import importlib
     import json
     jobs = shard_jobs(sweep_jobs(args.env_bundle, args.num_seeds), args.world, args.rank)
-    plan = offline_plan(args) or {}
     factory = None
     if args.env_factory:
         mod, fn = args.env_factory.split(":")
@@ -392,11 +407,7 @@ def _worker_main(args) -> int:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
                           eval_steps=args.eval_steps, batch_size=args.batch_size, rb_capacity=args.rb_capacity,
-                          overlap_acting=args.overlap_acting, device_env=args.device_env, prioritized=args.prioritized,
-                          n_step=args.n_step, one_launch=args.one_launch, offline_dataset=plan.get("dataset"),
-                          num_updates=plan.get("num_updates"), bc_alpha=args.bc_alpha, prior_fraction=plan.get("prior_fraction"),
-                          updates_per_step=args.updates_per_step or 1, policy_stats=policy_stats_plan(args),
-                          native_rollout=args.native_rollout)
+                          offline_dataset=plan.get("dataset"), num_updates=plan.get("num_updates"), bc_alpha=args.bc_alpha, **flags)
         print("JOB " + json.dumps(out), flush=True)
     return 0
 
@@ -457,16 +468,16 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     try:
         plan = offline_plan(args)
-        policy_stats_plan(args)
+        flags = mode_flags(args, plan or {})     # (policy_stats_plan is asked in there)
         if args.native_rollout:                  # every job of the sweep, before a worker starts
-            if args.offline_dataset is not None or args.overlap_acting:
-                raise ValueError("--native_rollout excludes --offline_dataset and --overlap_acting")
-            for env_id in ENV_BUNDLES[args.env_bundle]:
-                env_plan(env_id, args.device_env, bool(args.env_factory), native_rollout=True)
+            native_rollout_plan(ENV_BUNDLES[args.env_bundle], args.device_env, bool(args.env_factory), args.offline_dataset is not None,
+                                args.overlap_acting)
+        # what loop.train would refuse is refused here, with no worker started (no env loop: offline_plan left no flag for it to mind)
+        train_keywords(job_config(args.algo, None, 0, batch_size=args.batch_size), **flags)
     except ValueError as ex:
         ap.error(str(ex))
     if args.worker:
-        return _worker_main(args)
+        return _worker_main(args, plan or {}, flags)
     if plan is not None and plan["plain"]:
         print(f"launcher: --offline_dataset without --bc_alpha: plain {args.algo.upper()} on a fixed ring (no behaviour-cloning term; "
               "--algo td3 --bc_alpha 2.5 is TD3+BC)", file=sys.stderr, flush=True)

@@ -5,6 +5,8 @@ be driven end to end without tensordict / torchrl / gymnasium being importable:
   DeviceRollout         the same acting side for a vector env that lives on the GPU: every array a device tensor, no host wait
   NativeRollout         ... for an env that emits ring records itself (envs.NativeVecEnv): choose / advance are one library call each
   train()       the training loop's control flow       orchestrator.py:317-352 (+ counters :326,342,349)
+  update_plan() / rollout_for()   what train() decides ONCE before its loop: which update it issues (and every rule about the update
+                keywords), which rollout drives the env -- both without touching an agent or a GPU
   load_dataset() / train_offline()   training on a FIXED dataset (not in the reference): the ring filled once, then runs of whole
                 periods through Engine.run_iterations -- the workload of TD3+BC (hps.bc_alpha > 0)
   ProportionalSampler   proportional prioritised replay (not in the reference): a priority array on the device for train(sampler=...)
@@ -26,6 +28,7 @@ import json
 import time
 from collections import deque
 from pathlib import Path
+from types import SimpleNamespace
 from typing import Any, Callable, Dict, Generator, Optional, TextIO
 
 import numpy as np
@@ -234,6 +237,24 @@ def segment(env, agent, seed: int, segment_len: int, learning_starts: int, actio
         ro.advance()
 
 
+def rollout_for(env, *, overlap: bool, device_env: bool, native_rollout: bool):
+    """Which of the three classes above drives `env` for train(): refuses what excludes each other, constructs nothing.  -> None for the
+    plain host case (segment() makes its own `Rollout`), else what to call with (env, agent, seed, learning_starts, action_repeat).
+    Both device rollouts act on the learner stream, so neither goes with `overlap`; the native one needs an env on the GPU that emits
+    ring records (`step_records`: envs.NativeVecEnv)."""
+    if native_rollout and overlap:
+        raise ValueError("native_rollout=True and overlap=True exclude each other: the native rollout acts on the learner stream")
+    if native_rollout and not device_env:
+        raise ValueError("native_rollout=True needs device_env=True: it drives an env that lives on the GPU")
+    if native_rollout and not callable(getattr(env, "step_records", None)):
+        raise TypeError(f"native_rollout=True needs an env with step_records(); {type(env).__name__} has none")
+    if overlap and device_env:
+        raise ValueError("overlap=True and device_env=True exclude each other: predict_device acts on the learner stream")
+    if device_env:
+        return NativeRollout if native_rollout else DeviceRollout
+    return (lambda *to: Rollout(*to, overlap=True)) if overlap else None
+
+
 class ProportionalSampler:
     """Proportional prioritised replay (Schaul et al. 2016) as a sampler the engine does not own: one float32 priority per ring slot in
     a torch tensor on `device`, nothing else -- no tree, no storage (the rows stay in the engine's ring).  Every method is torch ops on
@@ -306,6 +327,99 @@ class PolicyStats:
         return self.last
 
 
+def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler], prioritized: Optional[Dict[str, float]], n_step: int,
+                one_launch: bool, prior_fraction: Optional[float], updates_per_step: int) -> SimpleNamespace:
+    """What train() does with one update, decided once from its keywords: touches no agent, env or GPU and imports nothing, so a process
+    that never opens a GPU can ask whether a run would be refused.  `cfg` needs `batch_size` (with `prior_fraction`, and when an update is
+    issued call by call), `num_envs` (with `n_step` > 1) and `actor_update_delay` (call by call).  Which keywords need or exclude each
+    other is the table `refusals` below, one row per rule with its reason, the first row that applies raising ValueError: a new mode
+    adds its rows there.  `prior_fraction` counts as a reason for `one_launch`.
+    -> a namespace of
+      updates_per_step  as an int
+      priorities        None, or dict(alpha=, eps=) for `agent.rb.enable_priorities` -- train() enables them once, before its loop
+      update            `update(agent, i, tlog)`: iteration i, in ONE of three forms chosen here --
+                          fused        agent.iteration(i)
+                          one launch   agent.iteration(i, prior_rows=) or agent.iteration(i, beta=, n_step=, stride=), the values fixed here
+                          call by call one draw (uniform `rb.sample`, `sampler` + `rb.sample_at`, `rb.sample_prioritized`, `rb.sample_mixed`) ->
+                                       update_qnets -> its write-back (`sampler.update` / `rb.update_priorities`) -> counters -> every
+                                       delay + 1 iterations delay x update_actor -> update_targ_nets; losses go into `tlog`"""
+    updates_per_step, n_step = int(updates_per_step), int(n_step)
+    prior, prio, outside = prior_fraction is not None, prioritized is not None, sampler is not None
+    unknown = sorted(set(prioritized or ()) - {"alpha", "beta", "eps"})
+    refusals = (
+        (updates_per_step < 1, f"updates_per_step must be >= 1, got {updates_per_step}"),
+        (prior and not 0.0 <= float(prior_fraction) <= 1.0, f"prior_fraction must be in [0, 1], got {prior_fraction}"),
+        (prior and fused, "prior_fraction=... needs fused=False: the fused iteration samples uniformly inside its graph"),
+        (prior and outside, "prior_fraction=... and sampler=... exclude each other: the mixed draw is the engine's own"),
+        (prior and prio, "prior_fraction=... and prioritized=... exclude each other: a pinned ring has no priority table yet"),
+        (prior and n_step > 1, "prior_fraction=... excludes n_step > 1: a pinned ring has no n-step chains yet"),
+        (one_launch and fused, "one_launch=True needs fused=False: fused=True is the uniform 1-step iteration, already one launch"),
+        (one_launch and outside, "one_launch=True excludes sampler=...: a sampler outside the engine cannot be part of its graph"),
+        (one_launch and not (prio or n_step > 1 or prior),
+         "one_launch=True needs prioritized=... and / or n_step > 1: the uniform 1-step iteration is fused=True"),
+        (not 1 <= n_step <= 16, f"n_step must be in [1, 16], got {n_step}"),
+        (n_step > 1 and fused, "n_step=... needs fused=False: the fused iteration samples single steps uniformly inside its graph"),
+        (outside and fused, "sampler=... needs fused=False: the fused iteration samples uniformly inside its graph"),
+        (prio and fused, "prioritized=... needs fused=False: the fused iteration samples uniformly inside its graph"),
+        (prio and outside, "prioritized=... and sampler=... exclude each other: one owner for the priorities"),
+        (bool(unknown), f"prioritized: unknown keys {unknown}"),
+    )
+    for applies, why in refusals:
+        if applies:
+            raise ValueError(why)
+    prior_rows = int(round(float(prior_fraction) * int(cfg.batch_size))) if prior else None
+    chain = dict(n_step=n_step, stride=int(cfg.num_envs)) if n_step > 1 else {}
+    beta = float(prioritized.get("beta", 0.4)) if prio else None
+    priorities = dict(alpha=float(prioritized.get("alpha", 0.6)), eps=float(prioritized.get("eps", 1e-6))) if prio else None
+    if fused:
+        update = lambda agent, i, tlog: agent.iteration(i)
+    elif one_launch and prior:                                           # (a keyword the older signature lacks: only when used)
+        update = lambda agent, i, tlog: agent.iteration(i, prior_rows=prior_rows)
+    elif one_launch:
+        stride = chain.get("stride")
+        update = lambda agent, i, tlog: agent.iteration(i, beta=beta, n_step=n_step, stride=stride)
+    else:
+        write_back = lambda agent, index: None                           # the uniform and the mixed draw keep no priorities
+        if prior:
+            draw = lambda agent: (agent.rb.sample_mixed(cfg.batch_size, prior_rows), None)
+        elif prio:
+            draw = lambda agent: (agent.rb.sample_prioritized(cfg.batch_size, beta, **chain), None)
+            write_back = lambda agent, index: agent.rb.update_priorities()
+        elif not outside:
+            draw = lambda agent: (agent.rb.sample(cfg.batch_size, **chain), None)
+        else:
+            def draw(agent):
+                index, weights = sampler.sample(cfg.batch_size)
+                return agent.rb.sample_at(index, weights, **chain), index
+            write_back = lambda agent, index: sampler.update(index, agent.td_errors())
+
+        def update(agent, i, tlog):
+            batch, index = draw(agent)
+            tlog.update(agent.update_qnets(batch))
+            write_back(agent, index)
+            agent.qnet_updates_so_far += 1
+            if i % (cfg.actor_update_delay + 1) == 0:
+                for _ in range(cfg.actor_update_delay):
+                    tlog.update(agent.update_actor(batch))
+                    agent.actor_updates_so_far += 1
+            agent.update_targ_nets()
+    return SimpleNamespace(updates_per_step=updates_per_step, priorities=priorities, update=update)
+
+
+def _eval_point(agent, pstats: Optional[PolicyStats], evaluator: Optional["Evaluator"], on_eval, count: int) -> None:
+    """the evaluation point of train / train_offline: policy stats, then the evaluator, then on_eval(agent, count)"""
+    if pstats is not None:
+        pstats(getattr(evaluator, "tabular", None))
+    if evaluator is not None:
+        evaluator(agent)
+    if on_eval is not None:
+        on_eval(agent, count)
+
+
+def _last_metrics(agent, pstats: Optional[PolicyStats]) -> Dict[str, float]:
+    return dict(agent.engine.read_metrics(), **(pstats.last if pstats is not None else {}))
+
+
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
           evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
           sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
@@ -316,85 +430,42 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
     launch (Agent.iteration); `fused=False` makes the reference's individual calls.  Every `eval_every` timesteps
     `evaluator` (the reference's eval block, :354-403) and/or `on_eval` run.  Returns the last metrics.
+    Which of the update keywords need or exclude each other is stated once, at `update_plan`; which rollout keywords do, at
+    `rollout_for`.  Both are asked before anything else happens: a call that either refuses has not touched the agent -- in
+    particular it has not enabled priorities in the engine, as a call refused for its rollout keywords once had.
     `overlap=True` (an agent with predict_begin / predict_end): the action that opens the next segment is computed on the engine's
     acting stream while this iteration's update runs; a pending action is collected before an evaluation acts with the agent.
     `device_env=True`: `env` lives on the GPU (device tensors in and out, e.g. SyntheticDeviceVecEnv) and is driven by `DeviceRollout`
-    -- `agent.predict_device`, no host round trip per env step.  It acts on the learner stream, so it excludes `overlap`.
-    `native_rollout=True` (needs `device_env=True` and an env with `step_records`, e.g. envs.NativeVecEnv; excludes `overlap`): the
-    env is driven by `NativeRollout` instead -- the env step writes the transitions as ring records and choose / advance are one
-    library call each, with the ring, the env and the engine bit for bit as `DeviceRollout` leaves them.  Off by default.
-    `sampler` (a ProportionalSampler; needs `fused=False`: `fused=True` is the uniform iteration): prioritised replay, call
-    by call on the device -- the sampler's rows and importance weights through `rb.sample_at`, the critic update weighted by them,
-    its TD errors (`agent.td_errors`) back into the sampler's priorities; the actor updates train on the same rows, unweighted.
-    `prioritized` (dict(alpha=, beta=, eps=), any subset; needs `fused=False`, excludes `sampler`): the same iteration with the
-    priorities kept by the ENGINE -- `rb.sample_prioritized` -> weighted critic update -> `rb.update_priorities()` -- with no torch
-    arithmetic in between and nothing to mirror on the host: the engine sees its own appends.
-    `n_step` (1 to 16; above 1 it needs `fused=False`): the critic trains on n-step returns chained by the engine out of consecutive ring
-    rows of one env (`stride=cfg.num_envs`), cut at episode ends -- in the uniform, `sampler` and `prioritized` branches alike.
-    `one_launch=True` (needs `fused=False` and `prioritized` and / or `n_step` > 1, excludes `sampler`): the `prioritized` / `n_step`
-    iteration is issued as one graph launch -- `agent.iteration(i, beta=, n_step=, stride=cfg.num_envs)` -- in place of the call
-    sequence, with the same results bit for bit and the same counters.
-    `prior_fraction` (in [0, 1]; needs `fused=False`, excludes `sampler`, `prioritized` and `n_step` > 1): learning online from prior
-    data -- every batch takes round(prior_fraction * batch_size) rows from the rows `agent.rb.pin()` protects (`load_dataset(...,
-    pin=True)`) and the others from the rows the run appends (`rb.sample_mixed`); it counts as a reason for `one_launch=True`.
-    `updates_per_step` (>= 1, every branch): the update-to-data ratio -- after each segment the update block runs that many times,
-    `i` and the update counters advancing per update; 1 is the reference's loop.
+    -- `agent.predict_device`, no host round trip per env step.
+    `native_rollout=True` (an env with `step_records`, e.g. envs.NativeVecEnv): the env is driven by `NativeRollout` instead -- the env
+    step writes the transitions as ring records and choose / advance are one library call each, with the ring, the env and the engine
+    bit for bit as `DeviceRollout` leaves them.  Off by default.
+    `sampler` (a ProportionalSampler): prioritised replay, call by call on the device -- the sampler's rows and importance weights
+    through `rb.sample_at`, the critic update weighted by them, its TD errors (`agent.td_errors`) back into the sampler's priorities;
+    the actor updates train on the same rows, unweighted.
+    `prioritized` (dict(alpha=, beta=, eps=), any subset): the same iteration with the priorities kept by the ENGINE --
+    `rb.sample_prioritized` -> weighted critic update -> `rb.update_priorities()` -- with no torch arithmetic in between and nothing to
+    mirror on the host: the engine sees its own appends.
+    `n_step` (1 to 16): the critic trains on n-step returns chained by the engine out of consecutive ring rows of one env
+    (`stride=cfg.num_envs`), cut at episode ends -- with the uniform, the `sampler` and the `prioritized` draw alike.
+    `one_launch=True`: the `prioritized` / `n_step` / `prior_fraction` iteration is issued as one graph launch --
+    `agent.iteration(i, beta=, n_step=, stride=cfg.num_envs)` or `agent.iteration(i, prior_rows=)` -- in place of the call sequence,
+    with the same results bit for bit and the same counters.
+    `prior_fraction` (in [0, 1]): learning online from prior data -- every batch takes round(prior_fraction * batch_size) rows from
+    the rows `agent.rb.pin()` protects (`load_dataset(..., pin=True)`) and the others from the rows the run appends (`rb.sample_mixed`).
+    `updates_per_step` (>= 1, every mode): the update-to-data ratio -- after each segment the update runs that many times, `i` and the
+    update counters advancing per update; 1 is the reference's loop.
     `policy_stats=N` (default 0: off, and no call is made; SAC only): at every evaluation point N ring rows are put to the policy
     (PolicyStats) and vitals/replay_log_prob, vitals/policy_entropy and vitals/log_std_mean are recorded with the evaluator's table
     and returned with the last metrics; the run itself is bit for bit the run without it."""
     pstats = PolicyStats(agent, policy_stats, cfg.seed) if policy_stats else None
-    updates_per_step = int(updates_per_step)
-    if updates_per_step < 1:
-        raise ValueError(f"updates_per_step must be >= 1, got {updates_per_step}")
-    prior_rows = None
-    if prior_fraction is not None:
-        if not 0.0 <= float(prior_fraction) <= 1.0:
-            raise ValueError(f"prior_fraction must be in [0, 1], got {prior_fraction}")
-        if fused:
-            raise ValueError("prior_fraction=... needs fused=False: the fused iteration samples uniformly inside its graph")
-        if sampler is not None:
-            raise ValueError("prior_fraction=... and sampler=... exclude each other: the mixed draw is the engine's own")
-        if prioritized is not None:
-            raise ValueError("prior_fraction=... and prioritized=... exclude each other: a pinned ring has no priority table yet")
-        if int(n_step) > 1:
-            raise ValueError("prior_fraction=... excludes n_step > 1: a pinned ring has no n-step chains yet")
-        prior_rows = int(round(float(prior_fraction) * int(cfg.batch_size)))
-    if one_launch:
-        if fused:
-            raise ValueError("one_launch=True needs fused=False: fused=True is the uniform 1-step iteration, already one launch")
-        if sampler is not None:
-            raise ValueError("one_launch=True excludes sampler=...: a sampler outside the engine cannot be part of its graph")
-        if prioritized is None and int(n_step) <= 1 and prior_rows is None:
-            raise ValueError("one_launch=True needs prioritized=... and / or n_step > 1: the uniform 1-step iteration is fused=True")
-    n_step = int(n_step)
-    if not 1 <= n_step <= 16:
-        raise ValueError(f"n_step must be in [1, 16], got {n_step}")
-    if n_step > 1 and fused:
-        raise ValueError("n_step=... needs fused=False: the fused iteration samples single steps uniformly inside its graph")
-    chain = dict(n_step=n_step, stride=int(cfg.num_envs)) if n_step > 1 else {}
-    if sampler is not None and fused:
-        raise ValueError("sampler=... needs fused=False: the fused iteration samples uniformly inside its graph")
-    if prioritized is not None:
-        if fused:
-            raise ValueError("prioritized=... needs fused=False: the fused iteration samples uniformly inside its graph")
-        if sampler is not None:
-            raise ValueError("prioritized=... and sampler=... exclude each other: one owner for the priorities")
-        unknown = set(prioritized) - {"alpha", "beta", "eps"}
-        if unknown:
-            raise ValueError(f"prioritized: unknown keys {sorted(unknown)}")
-        prio_beta = float(prioritized.get("beta", 0.4))
-        agent.rb.enable_priorities(alpha=float(prioritized.get("alpha", 0.6)), eps=float(prioritized.get("eps", 1e-6)))
-    if native_rollout and overlap:
-        raise ValueError("native_rollout=True and overlap=True exclude each other: the native rollout acts on the learner stream")
-    if native_rollout and not device_env:
-        raise ValueError("native_rollout=True needs device_env=True: it drives an env that lives on the GPU")
-    if native_rollout and not callable(getattr(env, "step_records", None)):
-        raise TypeError(f"native_rollout=True needs an env with step_records(); {type(env).__name__} has none")
-    if overlap and device_env:
-        raise ValueError("overlap=True and device_env=True exclude each other: predict_device acts on the learner stream")
-    ro = Rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat, overlap=True) if overlap else None
-    if device_env:
-        ro = (NativeRollout if native_rollout else DeviceRollout)(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat)
+    plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
+                       prior_fraction=prior_fraction, updates_per_step=updates_per_step)
+    make_rollout = rollout_for(env, overlap=overlap, device_env=device_env, native_rollout=native_rollout)
+    if plan.priorities is not None:                                       # (nothing above touched the agent's engine)
+        agent.rb.enable_priorities(**plan.priorities)
+    ro = make_rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat) if make_rollout is not None else None
+    resolve = ro.resolve if ro is not None else (lambda: None)            # (segment()'s own host rollout never has an action pending)
     seg_gen = segment(env, agent, cfg.seed, cfg.segment_len, cfg.learning_starts, cfg.action_repeat, rollout=ro)
     i = 0
     tlog: Dict[str, Any] = {}
@@ -408,48 +479,14 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
         if agent.timesteps_so_far <= cfg.learning_starts:
             i += 1
             continue
-        for _update in range(updates_per_step):                          # (1: the reference's one update per segment)
-            if fused:
-                agent.iteration(i)
-            elif one_launch and prior_rows is not None:                   # (a keyword the older signature lacks: only when used)
-                agent.iteration(i, prior_rows=prior_rows)
-            elif one_launch:
-                agent.iteration(i, beta=prio_beta if prioritized is not None else None, n_step=n_step,
-                                stride=int(cfg.num_envs) if n_step > 1 else None)
-            else:
-                if prior_rows is not None:
-                    batch = agent.rb.sample_mixed(cfg.batch_size, prior_rows)
-                elif prioritized is not None:
-                    batch = agent.rb.sample_prioritized(cfg.batch_size, prio_beta, **chain)
-                elif sampler is None:
-                    batch = agent.rb.sample(cfg.batch_size, **chain)
-                else:
-                    index, weights = sampler.sample(cfg.batch_size)
-                    batch = agent.rb.sample_at(index, weights, **chain)
-                tlog.update(agent.update_qnets(batch))
-                if sampler is not None:
-                    sampler.update(index, agent.td_errors())
-                if prioritized is not None:
-                    agent.rb.update_priorities()
-                agent.qnet_updates_so_far += 1
-                if i % (cfg.actor_update_delay + 1) == 0:
-                    for _ in range(cfg.actor_update_delay):
-                        tlog.update(agent.update_actor(batch))
-                        agent.actor_updates_so_far += 1
-                agent.update_targ_nets()
+        for _ in range(plan.updates_per_step):                           # (1: the reference's one update per segment)
+            plan.update(agent, i, tlog)
             i += 1
         if agent.timesteps_so_far % cfg.eval_every == 0:
-            if ro is not None:
-                ro.resolve()                                              # the evaluator / on_eval act (or load) with the same agent
-            if pstats is not None:
-                pstats(getattr(evaluator, "tabular", None))
-            if evaluator is not None:
-                evaluator(agent)
-            if on_eval is not None:
-                on_eval(agent, agent.timesteps_so_far)
-    if ro is not None:
-        ro.resolve()                                                      # leave no acting call in flight behind the loop
-    return dict(agent.engine.read_metrics(), **(pstats.last if pstats is not None else {}))
+            resolve()                                                     # the evaluator / on_eval act (or load) with the same agent
+            _eval_point(agent, pstats, evaluator, on_eval, agent.timesteps_so_far)
+    resolve()                                                             # leave no acting call in flight behind the loop
+    return _last_metrics(agent, pstats)
 
 
 _DATASET_KEYS = ("observations", "actions", "rewards", "next_observations", "terminations")
@@ -515,13 +552,8 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
         agent.actor_updates_so_far += delay * len(range(-(-i // period) * period, end, period))      # the iterations with i % period == 0
         i = end
         if i % every == 0 or i == num_updates:
-            if pstats is not None:
-                pstats(getattr(evaluator, "tabular", None))
-            if evaluator is not None:
-                evaluator(agent)
-            if on_eval is not None:
-                on_eval(agent, i)
-    return dict(eng.read_metrics(), **(pstats.last if pstats is not None else {}))
+            _eval_point(agent, pstats, evaluator, on_eval, i)
+    return _last_metrics(agent, pstats)
 
 
 class Tabular:
