@@ -393,6 +393,56 @@ int sactd3_rb_sample_mixed(sactd3_engine* e);
  * pinned boundary (the cursor came back to P)} */
 int sactd3_mix_stats(sactd3_engine* e, int64_t out[4]);
 
+/* ---- hindsight relabelling at staging (hindsight experience replay, Andrychowicz et al. 2017, the "future" strategy): the batch slot
+ * receives ring rows whose desired goal was replaced by a goal the same episode achieved at or after the row, with the reward that goal
+ * pays -- ONE launch (k_hindsight_stage, csrc/hindsight_kernels.h) in place of a read-out, torch arithmetic and a
+ * sactd3_load_batch_device.  The ring needs no episode field: the chain rule of the n-step staging above says where an episode goes on.
+ * Config (sactd3_hindsight_configure, host state): the achieved goal is floats [ag_off, ag_off + goal_dim) of an observation, the desired
+ *   goal floats [dg_off, dg_off + goal_dim); `window` in [1, 64] rows a goal may lie ahead (the env's horizon); `stride` >= 1 the rows
+ *   appended per env step; `threshold` thr; `ratio` in [0, 1] the share of rows relabelled.
+ * Rule for batch row b with start slot i0 (age, slot_j, "exists" and "link j -> j+1 holds" exactly as for the n-step staging):
+ *   1. accepted iff 0 <= i0 < len; otherwise refused as k_batch_from_index refuses: a zero record, slot index -1, counted, never an address.
+ *   2. L = 1 + the number of leading links that hold among links 0 .. window - 2, so 1 <= L <= window.
+ *   3. the draw: Philox counter words (hctr, 0, 0x600, b) keyed by the engine's seed -- stream SACTD3_STREAM_HINDSIGHT, hctr = the native
+ *      draws made so far (out[0] of sactd3_hindsight_stats).  Relabelled iff philox_u01(v0) < ratio (philox_u01 lies in (0, 1): ratio 0
+ *      relabels nothing, ratio 1 every accepted row); j = (v1 * L) >> 32.  With `choice` given: choice[b] < 0 not relabelled, otherwise
+ *      relabelled with j = min(choice[b], L - 1); no draw is made and hctr does not move.
+ *   4. the goal = floats [ag_off, ag_off + goal_dim) of the s' field of slot_j, as bits (an intermediate goal is a bit copy; j = 0 is
+ *      the row's own arrival, whose reward is 0).
+ *   5. staged: X = [s|a] of slot_0 with floats [dg_off, dg_off + goal_dim) of s replaced, Xn = s' of slot_0 with the same floats
+ *      replaced, done = the stored flag (not recomputed), slot index = i0, rew = (acc <= thr * thr) ? 0 : -1 with acc the sum over c in
+ *      index order of (ag'_c - g_c) * (ag'_c - g_c), ag' the achieved goal in slot_0's own s' -- each operation one fp32 rounding, no
+ *      contraction.  A row that is not relabelled receives its record's bits: what k_batch_from_index leaves, reward included.  The
+ *      slot carries no weights.
+ *   6. two per-slot int32 arrays, made at the first staging call: the offset j (-1: not relabelled or refused) and the goal's ring slot
+ *      (-1); read with sactd3_hindsight_info_device.
+ *   7. three device counters, one atomic per counted row: rows relabelled, rows refused, rows whose relabelled reward is 0.
+ * Out of scope: a graph form (sactd3_step_sampled and the fused graphs know no hindsight), priorities, n-step chains or pinned rows beside
+ *   it, strategies other than "future", recomputing the flag on success, other reward functions, the config in checkpoints. */
+typedef struct sactd3_hindsight_config {
+  int32_t ag_off, dg_off, goal_dim, window, stride;
+  float threshold, ratio;
+} sactd3_hindsight_config;
+/* SACTD3_EINVAL: goal_dim outside [1, 8]; a goal range outside [0, ob_dim) or overlapping the other; window outside [1, 64]; stride < 1;
+ * threshold negative or not finite; ratio outside [0, 1] or NaN.  Host state only: no launch, the run-ahead chain stays intact. */
+int sactd3_hindsight_configure(sactd3_engine* e, const sactd3_hindsight_config* cfg);
+/* The engine's own uniform draw (k_mix_draw with nothing pinned: the slots sactd3_rb_sample would draw; the sample counter advances
+ * once), then the staging launch.  SACTD3_ESTATE: hindsight not configured, rows pinned (the age formula assumes one wrap point), ring
+ * empty.  Breaks the run-ahead chain and makes slot 0 current; a refused call has changed nothing. */
+int sactd3_rb_sample_hindsight(sactd3_engine* e);
+/* ... with the caller's start slots (idx[b * idx_ld], DEVICE int64, n == batch_size) and, optionally, the caller's choices
+ * (choice[b * choice_ld], DEVICE int32, NULL: the native draw).  Pointer, stride, flag and error rules of sactd3_rb_sample_indices_device. */
+int sactd3_rb_sample_hindsight_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const int32_t* choice, int64_t choice_ld, int n,
+                                      void* caller_stream, int flags /* SACTD3_SRC_ORDERED */);
+/* offset[b * offset_ld] = j or -1, goal_slot[b * goal_slot_ld] = the goal's ring slot or -1: DEVICE int32 arrays, either may be NULL, not
+ * both.  One launch on the learner stream, ordered as sactd3_nstep_info_device orders.  SACTD3_ESTATE unless batch slot 0 was filled by a
+ * hindsight staging call and not refilled since. */
+int sactd3_hindsight_info_device(sactd3_engine* e, int32_t* offset, int64_t offset_ld, int32_t* goal_slot, int64_t goal_slot_ld,
+                                 void* caller_stream, int flags /* SACTD3_DST_ORDERED */);
+/* [sync] out = {native draws made (staging calls without `choice`), rows relabelled, rows refused, rows whose relabelled reward is 0};
+ * the last three are counted on the device */
+int sactd3_hindsight_stats(sactd3_engine* e, int64_t out[4]);
+
 /* rb.sample(batch_size) (orchestrator.py:338): uniform-with-replacement indices from the engine's
  * Philox stream + gather into the engine-owned batch slot. */
 int sactd3_rb_sample(sactd3_engine* e);

@@ -33,8 +33,14 @@
  *       force = 10 clamp(a, +-1); g 9.8, cart mass 1.0, pole mass 0.1, half-length 0.5, Euler step 0.02 (Barto, Sutton &
  *       Anderson 1983); terminates when |x'| > 2.4 or |theta'| > 0.20943951 (strictly); reward 1 on every step, the terminating
  *       one included.  Reset: U(-0.05, 0.05)^4.
- *   Both: truncated when the episode's step count reaches the horizon and the step did not terminate (termination wins).
- *   A NaN or infinite action is replaced by 0 and counted; it never reaches the state.
+ *   SACTD3_ENV_POINTGOAL  ob_dim 6, ac_dim 2, bounds +-1, horizon 50, never terminates.  State (x, y, vx, vy): a point mass
+ *       that has to reach a goal drawn per episode.  The goal (gx, gy) is not state: for episode k of env i it is
+ *       -1 + 2 philox_u01(w) of words 0 and 1 of counter words (k, i, 0x500, 2).  Per dimension c: u_c = clamp(a_c, +-1);
+ *       v_c' = 0.8 v_c + 0.2 u_c; p_c' = clamp(p_c + 0.1 v_c', +-1).  obs = (x, y, vx, vy, gx, gy): the achieved goal is
+ *       elements 0-1, the desired goal elements 4-5.  reward = 0 if (x'-gx)^2 + (y'-gy)^2 <= 0.1f * 0.1f else -1, of the
+ *       ARRIVAL state against the running episode's goal.  Reset: x, y ~ U(-1, 1), at rest.
+ *   All: truncated when the episode's step count reaches the horizon and the step did not terminate (termination wins).
+ *   A NaN or infinite action component is replaced by 0; a step with any such component is counted once; none reaches the state.
  */
 #ifndef SACTD3_ENV_H
 #define SACTD3_ENV_H
@@ -49,7 +55,8 @@ extern "C" {
 enum {
   SACTD3_ENV_PENDULUM = 0,
   SACTD3_ENV_CARTPOLE = 1,
-  SACTD3_ENV_NUM_KINDS = 2
+  SACTD3_ENV_POINTGOAL = 2,
+  SACTD3_ENV_NUM_KINDS = 3
 };
 
 #define SACTD3_ENV_STATE_DIM 4   /* floats of physical state per env in sactd3_env_state.phys (the pendulum uses two, the rest is 0) */
@@ -57,7 +64,7 @@ enum {
 typedef struct sactd3_env_config {
   int32_t kind;       /* SACTD3_ENV_* */
   int32_t num_envs;   /* >= 1 */
-  int32_t horizon;    /* steps to the time limit; 0 = the task's default (200) */
+  int32_t horizon;    /* steps to the time limit; 0 = the task's default (200; the point mass: 50) */
   int32_t device_id;  /* HIP device ordinal */
   uint64_t seed;      /* Philox key; sactd3_env_reset replaces it */
 } sactd3_env_config;

@@ -48,6 +48,8 @@ SYMBOLS = [
     "sactd3_rb_pin", "sactd3_rb_pinned", "sactd3_rb_set_mix", "sactd3_rb_sample_mixed", "sactd3_mix_stats",
     "sactd3_policy_device", "sactd3_policy", "sactd3_policy_stats",
     "sactd3_get_config", "sactd3_rb_extend_records_device", "sactd3_batch_generation",
+    "sactd3_hindsight_configure", "sactd3_rb_sample_hindsight", "sactd3_rb_sample_hindsight_device", "sactd3_hindsight_info_device",
+    "sactd3_hindsight_stats",
 ]
 
 # every symbol include/sactd3_env.h declares (tests/test_env_host.py checks the header against this list)
@@ -55,7 +57,7 @@ ENV_SYMBOLS = [
     "sactd3_env_create", "sactd3_env_destroy", "sactd3_env_last_error", "sactd3_env_spec", "sactd3_env_reset", "sactd3_env_step",
     "sactd3_env_sample_actions", "sactd3_env_episode_stats", "sactd3_env_get_state", "sactd3_env_set_state",
 ]
-ENV_PENDULUM, ENV_CARTPOLE = 0, 1   # sactd3_env_config.kind
+ENV_PENDULUM, ENV_CARTPOLE, ENV_POINTGOAL = 0, 1, 2   # sactd3_env_config.kind
 ENV_STATE_DIM = 4                   # SACTD3_ENV_STATE_DIM
 
 # every symbol include/sactd3_rollout.h declares (tests/test_native_rollout_host.py checks the header against this list)
@@ -102,6 +104,11 @@ POLICY_IO_FIELDS = (("actions", "a"), ("eps", "a"), ("mode", "a"), ("mean", "a")
 class CPolicyIO(C.Structure):
     """sactd3_policy_io: nine pointers (None = not given / not wanted), each with its row stride in elements"""
     _fields_ = [(n, t) for f, _ in POLICY_IO_FIELDS for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
+
+
+class CHindsightConfig(C.Structure):
+    """sactd3_hindsight_config"""
+    _fields_ = [(n, C.c_int32) for n in ("ag_off", "dg_off", "goal_dim", "window", "stride")] + [("threshold", C.c_float), ("ratio", C.c_float)]
 
 
 class CEnvConfig(C.Structure):
@@ -248,6 +255,11 @@ def load_library():
         "sactd3_policy_stats": (C.c_int, [vp, i64p]),
         "sactd3_get_config": (C.c_int, [vp, C.POINTER(CConfig)]),
         "sactd3_rb_extend_records_device": (C.c_int, [vp, vp, C.c_int, vp, C.c_int]),
+        "sactd3_hindsight_configure": (C.c_int, [vp, C.POINTER(CHindsightConfig)]),
+        "sactd3_rb_sample_hindsight": (C.c_int, [vp]),
+        "sactd3_rb_sample_hindsight_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int]),
+        "sactd3_hindsight_info_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int]),
+        "sactd3_hindsight_stats": (C.c_int, [vp, i64p]),
         "sactd3_read_metrics": (C.c_int, [vp, fp]),
         "sactd3_sync": (C.c_int, [vp]),
         "sactd3_device_handles": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

@@ -338,6 +338,25 @@ class BatchHandle(dict):
         eng.nstep_info_device(steps.data_ptr(), 1, last.data_ptr(), 1, _producer_stream(steps, eng.cfg.device_id))
         return {"steps": steps, "last_index": last}
 
+    def hindsight_info(self) -> Dict[str, Any]:
+        """{"offset": int32 [B], "goal_index": int32 [B]} on the engine's device, for a handle made by sample_hindsight /
+        sample_hindsight_at: how many env steps behind the row its new goal was achieved (0: the row's own arrival; -1: the row was not
+        relabelled, or refused) and the ring slot the goal was taken from (-1), written by one launch ordered against torch's current
+        stream (include/sactd3.h: sactd3_hindsight_info_device).  On such a handle the desired goal inside `observations` and
+        `next_observations` and the `rewards` of the relabelled rows are the relabelled ones; `dones` is the stored flag.
+        StaleBatchError when the handle is not current, RuntimeError on a handle that is not a hindsight one."""
+        if not self._is_current():
+            raise StaleBatchError("this batch handle is older than the engine's batch slot: a later rb.sample() / staged batch replaced its rows")
+        if not getattr(self, "_hindsight", False):
+            raise RuntimeError("hindsight_info: this batch was not sampled with sample_hindsight / sample_hindsight_at")
+        import torch
+        eng = self._engine
+        dev = torch.device("cuda", int(eng.cfg.device_id))
+        offset = torch.empty(int(eng.cfg.batch_size), dtype=torch.int32, device=dev)
+        goal = torch.empty_like(offset)
+        eng.hindsight_info_device(offset.data_ptr(), 1, goal.data_ptr(), 1, _producer_stream(offset, eng.cfg.device_id))
+        return {"offset": offset, "goal_index": goal}
+
 
 def _n_step_args(what: str, n_step, stride) -> Tuple[int, int]:
     """(steps, stride) of a sampling call, checked before the engine is touched"""
@@ -361,11 +380,14 @@ class ReplayBuffer:
         self.capacity, self.device, self.device_batches = int(capacity), device, bool(device_batches)
         self._engine: Optional[Engine] = None
         self._priorities: Optional[Dict[str, float]] = None      # enable_priorities' arguments, once it was called
+        self._hindsight: Optional[Dict[str, Any]] = None         # configure_hindsight's arguments, once it was called
 
     def _bind(self, engine: Engine):
         self._engine = engine
         if self._priorities is not None:      # enabled before the agent existed: the engine learns it now
             engine.prio_enable(**self._priorities)
+        if self._hindsight is not None:
+            engine.hindsight_configure(**self._hindsight)
 
     def _need(self) -> Engine:
         assert self._engine is not None, "replay buffer is not attached to an Agent yet"
@@ -469,6 +491,66 @@ class ReplayBuffer:
         eng = self._need()
         assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
         return self._staged(eng, n_step, stride, "rb_sample_prioritized", "rb_sample_prioritized_nstep", beta)
+
+    def configure_hindsight(self, *, achieved: int, desired: int, dim: int, threshold: float, ratio: float = 0.8, window: int = 50,
+                            stride: Optional[int] = None) -> None:
+        """Hindsight relabelling kept by the engine (hindsight experience replay, the "future" strategy; include/sactd3.h:
+        sactd3_hindsight_configure).  `achieved`, `desired`, `dim`: floats [achieved, achieved + dim) of an observation are the goal it
+        has reached, floats [desired, desired + dim) the goal it is after (envs.NativeVecEnv.goal_layout names them for a native task);
+        `threshold`: a goal counts as reached, and pays 0 instead of -1, within this distance; `ratio`: the share of a batch's rows
+        that get a goal their own episode reached at or after the row; `window`: how many env steps ahead that goal may lie (the env's
+        horizon); `stride`: the rows appended per env step, i.e. the env count (None: the engine's max_envs).  Host state only.  Before
+        the buffer is attached to an Agent the call is remembered and made then.  Not saved in checkpoints."""
+        args = dict(achieved=int(achieved), desired=int(desired), dim=int(dim), threshold=float(threshold), ratio=float(ratio), window=int(window),
+                    stride=None if stride is None else int(stride))
+        if self._engine is not None:
+            if args["stride"] is None:
+                args["stride"] = int(self._engine.cfg.max_envs)
+            self._engine.hindsight_configure(**args)
+        elif args["stride"] is None:
+            raise ValueError("configure_hindsight: before the buffer is attached to an Agent `stride` (the env count) must be given")
+        self._hindsight = args
+
+    def _hindsight_handle(self, eng: Engine) -> BatchHandle:
+        h = self._new_handle(eng)
+        h._hindsight = True
+        return h
+
+    def sample_hindsight(self, batch_size: int) -> BatchHandle:
+        """sample() with goals relabelled while the rows are staged (sactd3_rb_sample_hindsight): the start rows are those sample() would
+        draw (one counter tick); a `ratio` share of them receives, in place of its desired goal, a goal achieved later in its own
+        episode, with the reward that goal pays -- two launches, no torch arithmetic, no copy out and back in.  The handle is a
+        sample()'s in every other respect; BatchHandle.hindsight_info() says which rows were relabelled and from where.  Needs
+        configure_hindsight(); excludes priorities, n-step chains and pinned rows."""
+        if self._hindsight is None:
+            raise RuntimeError("sample_hindsight: call configure_hindsight() first")
+        eng = self._need()
+        assert batch_size == eng.cfg.batch_size, "the engine is built for one batch size (hps.batch_size)"
+        eng.rb_sample_hindsight()
+        return self._hindsight_handle(eng)
+
+    def sample_hindsight_at(self, index, choice=None) -> BatchHandle:
+        """sample_hindsight() with the caller's start rows (`index`: batch_size ring slots, as for sample_at) and, optionally, the
+        caller's choices (`choice`: int32 [batch_size]; below 0: the row keeps its goal; otherwise the number of env steps behind the
+        row its new goal is taken from, cut to what is left of the episode).  None: the engine draws (sactd3_rb_sample_hindsight_device).
+        A slot outside [0, len(rb)) becomes a zero record with index -1."""
+        if self._hindsight is None:
+            raise RuntimeError("sample_hindsight_at: call configure_hindsight() first")
+        eng = self._need()
+        B = int(eng.cfg.batch_size)
+        index, ptr, n, ld = _index_field(eng, index)
+        if n != B:
+            raise ValueError(f"sample_hindsight_at: expected {B} indices (the engine is built for one batch size), got {n}")
+        c_ptr = 0
+        if choice is not None:
+            import torch
+            choice = torch.as_tensor(choice, dtype=torch.int32).to(torch.device("cuda", int(eng.cfg.device_id))).reshape(-1).contiguous()
+            if choice.numel() != B:
+                raise ValueError(f"sample_hindsight_at: expected {B} choices (one per batch row), got {choice.numel()}")
+            c_ptr = choice.data_ptr()
+        eng.rb_sample_hindsight_device(ptr, ld, c_ptr, 1, n, _producer_stream(index, eng.cfg.device_id))
+        del choice      # (the engine's read is ordered against the stream the allocator hands the block out on)
+        return self._hindsight_handle(eng)
 
     def pin(self, n: Optional[int] = None) -> None:
         """Protect the first `n` rows (None: every row held now) from eviction: a dataset loaded before the online run starts

@@ -28,6 +28,8 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 // All device code stands above.  The order of the template instances in the code object is pinned by this list, not by where the
 // host code below names them: a new instance is appended there.
 #include "kernel_instances.inc"
+// the hindsight staging kernel is a translation unit of its own (hindsight.hip): only its argument struct and launcher are known here
+#include "hindsight.h"
 
 static thread_local std::string g_create_error;
 
@@ -134,7 +136,8 @@ struct sactd3_engine {
   // critic update on the rows now in bs[cur] (sactd3_td_errors_device, sactd3_prio_update_from_td).  Written by the two transitions
   // slot_refilled / slot_trained alone -- and by slot_set_weighted, for sactd3_batch_weights_device, which changes `weighted` only.
   // generation: how often the rows that read_batch reports were replaced (sactd3_batch_generation); it only ever grows.
-  struct SlotState { int cur = 0; bool weighted = false, nstep = false, td_valid = false; int64_t generation = 0; } slot;
+  // hindsight: slot 0 was filled by a hindsight staging (hs_off / hs_gs describe its rows); every other refill and every fused update clears it.
+  struct SlotState { int cur = 0; bool weighted = false, nstep = false, td_valid = false; int64_t generation = 0; bool hindsight = false; } slot;
   // chain_ready = v (0 / 1): the previous sactd3_step_period left the opening pair of the next period precomputed in slot (v ? 3 : 0)
   // and nothing has touched the state it depends on since (parameters, ring length, counters, noise injection, the slots);
   // -1: not so -- the next period starts with the opening graph.  Every state-changing ABI call resets it (CHAIN_BREAK).
@@ -249,6 +252,15 @@ struct sactd3_engine {
   struct MixCtl* mix_ctl = nullptr; long long* mix_idx = nullptr;
   int64_t mix_pub[2] = {-1, -1};
   int64_t mix_stats[4] = {};
+  // Hindsight relabelling at staging (sactd3_hindsight_configure, sactd3_rb_sample_hindsight*; device code: hindsight_kernels.h, a
+  // translation unit of its own).  hs_on / hs_cfg: host state, set by the configure call.  hs_off / hs_gs [B] (per batch row: the offset j
+  // and the goal's ring slot) and the device counters hs_ctr {rows relabelled, rows refused, rows whose relabelled reward is 0} are made at
+  // the first staging call -- an engine that never makes one holds nothing more than before.  hs_calls: native draws made so far, the
+  // first counter word of the next one.  Run-time state, not part of a checkpoint.
+  bool hs_on = false;
+  sactd3_hindsight_config hs_cfg{};
+  int *hs_off = nullptr, *hs_gs = nullptr, *hs_ctr = nullptr;
+  int64_t hs_calls = 0;
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -280,7 +292,7 @@ static inline void slot_refilled(sactd3_engine* e, bool weighted, bool nstep) { 
 // graphs: a uniform 1-step draw, never weighted); otherwise (sactd3_update_qnets) the slot keeps what its refill staged.
 static inline void slot_trained(sactd3_engine* e, int slot, bool fused) {
   e->slot.cur = slot; e->slot.td_valid = true;
-  if (fused) { e->slot.weighted = e->slot.nstep = false; ++e->slot.generation; }
+  if (fused) { e->slot.weighted = e->slot.nstep = e->slot.hindsight = false; ++e->slot.generation; }
 }
 static inline void slot_set_weighted(sactd3_engine* e, bool weighted) { e->slot.weighted = weighted; }
 // the batch slot that iteration i of a period (or cut-short period) of variant v trains on (see BatchSlot, enqueue_period)
@@ -1647,6 +1659,37 @@ static int mix_draw_launches(EnqCtx& x) {
 }
 static inline void mix_count(sactd3_engine* e) { ++e->mix_stats[0]; e->mix_stats[1] += e->mix_m; e->mix_stats[2] += e->B - e->mix_m; }
 
+// ---- hindsight relabelling (device code: hindsight_kernels.h, through the launcher of hindsight.h)
+static int hindsight_alloc(sactd3_engine* e) {
+  RCCHK(first_use_alloc(e, &e->hs_off, (size_t)e->B));
+  RCCHK(first_use_alloc(e, &e->hs_gs, (size_t)e->B));
+  return first_use_alloc(e, &e->hs_ctr, 32);
+}
+// the one launch of k_hindsight_stage into batch slot 0: the ring's geometry as ring_rows_args states it, everything else by value
+static int launch_hindsight(EnqCtx& x, const long long* idx, int64_t idx_ld, const int* choice, int64_t choice_ld, unsigned hctr) {
+  sactd3_engine* e = x.e;
+  const sactd3_engine::BatchSlot& S = e->bs[0];
+  const sactd3_hindsight_config& c = e->hs_cfg;
+  HindsightArgs g{};
+  g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.cx = e->cx; g.cn = e->cn; g.o = e->o;
+  g.B = e->B; g.len = (int)e->rb_len; g.cursor = (int)e->rb_cursor; g.cap = (int)e->cfg.rb_capacity;
+  g.ag_off = c.ag_off; g.dg_off = c.dg_off; g.G = c.goal_dim; g.thr = c.threshold; g.ratio = c.ratio; g.window = c.window; g.stride = c.stride;
+  g.seed = e->cfg.seed; g.hctr = hctr;
+  g.idx = idx; g.idx_ld = (long)idx_ld; g.choice = choice; g.choice_ld = (long)choice_ld;
+  g.X = (float4*)S.X; g.Xn = (float4*)S.Xn; g.rew = S.rew; g.done = S.done; g.slot_idx = S.idx;
+  g.offset = e->hs_off; g.goal_slot = e->hs_gs; g.counters = e->hs_ctr;
+  const long chunks = (long)e->B * e->rec4;      // (< 2^31: create_impl)
+  g.rec4_magic = magic_div((unsigned)e->rec4, (unsigned long long)chunks + 1);
+  // the gather's grid, with the span cut so that a block's rows fit the kernel's LDS tables: (cpb * 256) / rec4 + 2 <= HS_ROWS
+  const unsigned blocks_g = gather_blocks(chunks);
+  const long cpb_g = (chunks + 256L * blocks_g - 1) / (256L * blocks_g), cpb_l = std::max(1L, (long)(HS_ROWS - 2) * e->rec4 / 256);
+  g.cpb = (int)std::min(std::min(cpb_g, cpb_l), (long)HS_CPT);
+  const unsigned blocks = (unsigned)((chunks + 256L * g.cpb - 1) / (256L * g.cpb));
+  const hipError_t he = hindsight_stage_launch(g, blocks, x.s);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "hindsight_stage_launch", he);
+  return 0;
+}
+
 // The replay-aware iteration (sactd3_step_sampled) as one linear sequence: what the calls
 //   sactd3_rb_sample_prioritized[_nstep] | sactd3_rb_sample_nstep | sactd3_rb_sample_mixed -> sactd3_update_qnets ->
 //   [sactd3_prio_update_from_td] -> [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets
@@ -2523,6 +2566,98 @@ int sactd3_rb_sample_mixed(sactd3_engine* e) {
 }
 
 int sactd3_mix_stats(sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::mix_stats, out); }
+
+// ---- hindsight relabelling at staging (include/sactd3.h)
+// Host state only: no launch, and a precomputed opening pair stays valid across it (nothing it depends on changes).
+int sactd3_hindsight_configure(sactd3_engine* e, const sactd3_hindsight_config* c) {
+  if (!e) return SACTD3_EINVAL;
+  if (!c) return e->fail(SACTD3_EINVAL, "hindsight_configure: the config is NULL");
+  if (c->goal_dim < 1 || c->goal_dim > HS_MAX_GOAL) return e->fail(SACTD3_EINVAL, "hindsight_configure: goal_dim must be in [1, 8]");
+  const int o = e->o, G = c->goal_dim;
+  if (c->ag_off < 0 || c->ag_off > o - G || c->dg_off < 0 || c->dg_off > o - G)
+    return e->fail(SACTD3_EINVAL, "hindsight_configure: a goal range lies outside [0, ob_dim)");
+  if (c->ag_off < c->dg_off + G && c->dg_off < c->ag_off + G)
+    return e->fail(SACTD3_EINVAL, "hindsight_configure: the achieved and the desired goal overlap");
+  if (c->window < 1 || c->window > HS_MAX_WINDOW) return e->fail(SACTD3_EINVAL, "hindsight_configure: window must be in [1, 64]");
+  if (c->stride < 1) return e->fail(SACTD3_EINVAL, "hindsight_configure: stride must be at least 1");
+  if (!(c->threshold >= 0.f) || !std::isfinite(c->threshold)) return e->fail(SACTD3_EINVAL, "hindsight_configure: threshold must be finite and >= 0");
+  if (!(c->ratio >= 0.f && c->ratio <= 1.f)) return e->fail(SACTD3_EINVAL, "hindsight_configure: ratio must be in [0, 1]");
+  e->hs_cfg = *c;
+  e->hs_on = true;
+  return 0;
+}
+
+// The protocol of stage_ring_rows, in its order: refusals (a refused call has changed nothing), CHAIN_BREAK, allocations at first use,
+// src_order_begin, the launches ([k_mix_draw, which ticks the sample counter,] k_hindsight_stage), src_order_end, slot_refilled, counters.
+// idx == NULL: the uniform draw, with nothing pinned the slots of sactd3_rb_sample.
+static int hindsight_stage(sactd3_engine* e, const char* name, const long long* idx, int64_t idx_ld, const int* choice, int64_t choice_ld, int n,
+                           bool callers, void* caller_stream, int flags) {
+  USE_DEVICE(e);
+  const auto refuse = [&](int code, const char* what) { e->err = std::string(name) + ": " + what; return code; };
+  if (callers) {
+    if (!idx) return refuse(SACTD3_EINVAL, "`idx` is NULL");
+    if (flags & ~SACTD3_SRC_ORDERED) return refuse(SACTD3_EINVAL, "unknown flag");
+    if (n != e->B) return refuse(SACTD3_EINVAL, "n must equal batch_size");
+    if (idx_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `idx` is below its width");
+    if (choice && choice_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `choice` is below its width");
+    RCCHK(device_ptr_check(e, idx, name, "idx"));
+    if (choice) RCCHK(device_ptr_check(e, choice, name, "choice"));
+  }
+  if (!e->hs_on) return refuse(SACTD3_ESTATE, "hindsight is not configured (sactd3_hindsight_configure)");
+  if (e->rb_pinned > 0) return refuse(SACTD3_ESTATE, "rows are pinned (sactd3_rb_pin): the chain's age formula assumes one wrap point, at slot 0");
+  if (e->rb_len <= 0) return refuse(SACTD3_ESTATE, "buffer is empty");
+  CHAIN_BREAK(e);
+  RCCHK(hindsight_alloc(e));
+  if (!callers) RCCHK(mix_alloc(e));
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  EnqCtx x{e, e->stream};
+  if (!callers) {      // the uniform draw: no pinned row, no prior share
+    const MixDrawArgs d{e->ctl, e->mix_idx, e->B, (int)e->rb_len, 0, 0};
+    LAUNCH_ON(k_mix_draw<false>, dim3(1), dim3(256), d, (const MixCtl*)nullptr, 0);
+    idx = e->mix_idx; idx_ld = 1;
+  }
+  RCCHK(launch_hindsight(x, idx, idx_ld, choice, choice_ld, (unsigned)e->hs_calls));
+  RCCHK(src_order_end(e, caller, flags));
+  slot_refilled(e, false, false);
+  e->slot.hindsight = true;
+  if (!choice) ++e->hs_calls;      // a native draw was made at this counter
+  return 0;
+}
+int sactd3_rb_sample_hindsight(sactd3_engine* e) {
+  if (!e) return SACTD3_EINVAL;
+  return hindsight_stage(e, "rb_sample_hindsight", nullptr, 1, nullptr, 1, e->B, false, nullptr, 0);
+}
+int sactd3_rb_sample_hindsight_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const int32_t* choice, int64_t choice_ld, int n,
+                                      void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  return hindsight_stage(e, "rb_sample_hindsight_device", (const long long*)idx, idx_ld, (const int*)choice, choice_ld, n, true, caller_stream, flags);
+}
+// the offset and the goal's ring slot of every row of a hindsight slot, left in the caller's device arrays: one k_nstep_info launch (the
+// kernel copies two per-row int32 arrays, whatever they mean) on the learner stream.  No CHAIN_BREAK.
+int sactd3_hindsight_info_device(sactd3_engine* e, int32_t* offset, int64_t offset_ld, int32_t* goal_slot, int64_t goal_slot_ld, void* caller_stream,
+                                 int flags) {
+  if (!e) return SACTD3_EINVAL;
+  if (!offset && !goal_slot) return e->fail(SACTD3_EINVAL, "hindsight_info_device: `offset` and `goal_slot` are both NULL");
+  USE_DEVICE(e);
+  if (flags & ~SACTD3_DST_ORDERED) return e->fail(SACTD3_EINVAL, "hindsight_info_device: unknown flag");
+  if ((offset && offset_ld < 1) || (goal_slot && goal_slot_ld < 1)) return e->fail(SACTD3_EINVAL, "hindsight_info_device: a row stride is below 1");
+  if (offset) RCCHK(device_ptr_check(e, offset, "hindsight_info_device", "offset"));
+  if (goal_slot) RCCHK(device_ptr_check(e, goal_slot, "hindsight_info_device", "goal_slot"));
+  if (!e->slot.hindsight || e->slot.cur != 0)
+    return e->fail(SACTD3_ESTATE, "hindsight_info_device: the batch slot was not filled by a hindsight staging call");
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  const NstepInfoArgs g{e->hs_off, e->hs_gs, e->B, offset, (long)offset_ld, goal_slot, (long)goal_slot_ld};
+  EnqCtx x{e, e->stream};
+  LAUNCH_ON(k_nstep_info, dim3((unsigned)((e->B + 255) / 256)), dim3(256), g);
+  RCCHK(src_order_end(e, caller, flags));
+  return 0;
+}
+// {native draws, rows relabelled, rows refused, rows whose relabelled reward is 0}: the last three are device words
+int sactd3_hindsight_stats(sactd3_engine* e, int64_t out[4]) {
+  return (!e || !out) ? SACTD3_EINVAL : stats_with_words(e, &e->hs_calls, e->hs_ctr, 3, 1, out);
+}
 
 // loss weights for whatever slot 0 holds (a caller-owned device batch, an index-staged one); NULL drops them
 int sactd3_batch_weights_device(sactd3_engine* e, const float* w, int64_t w_ld, int n, void* caller_stream, int flags) {

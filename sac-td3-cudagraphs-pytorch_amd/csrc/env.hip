@@ -71,15 +71,23 @@ static int env_alloc(sactd3_env* e) {
 
 static int env_init(sactd3_env* e, const sactd3_env_config* cfg) {
   e->cfg = *cfg;
-  if (cfg->kind < 0 || cfg->kind >= SACTD3_ENV_NUM_KINDS) return e->fail(SACTD3_EINVAL, "kind must be SACTD3_ENV_PENDULUM or SACTD3_ENV_CARTPOLE");
+  if (cfg->kind < 0 || cfg->kind >= SACTD3_ENV_NUM_KINDS) return e->fail(SACTD3_EINVAL, "kind must be SACTD3_ENV_PENDULUM, SACTD3_ENV_CARTPOLE or SACTD3_ENV_POINTGOAL");
   if (cfg->num_envs < 1 || cfg->num_envs > (1 << 24)) return e->fail(SACTD3_EINVAL, "num_envs must be in [1, 2^24]");
   if (cfg->horizon < 0) return e->fail(SACTD3_EINVAL, "horizon must be >= 0 (0: the task's default)");
-  const bool pend = cfg->kind == SACTD3_ENV_PENDULUM;
-  e->info.ob_dim = pend ? EnvTask<ENV_PENDULUM>::OB : EnvTask<ENV_CARTPOLE>::OB;
-  e->info.ac_dim = 1;
-  e->info.horizon = cfg->horizon ? cfg->horizon : 200;
+  int default_horizon = 200;
+  switch (cfg->kind) {
+    case SACTD3_ENV_PENDULUM:
+      e->info.ob_dim = EnvTask<ENV_PENDULUM>::OB; e->info.ac_dim = EnvTask<ENV_PENDULUM>::AC; e->info.max_ac = EnvTask<ENV_PENDULUM>::BOUND;
+      break;
+    case SACTD3_ENV_CARTPOLE:
+      e->info.ob_dim = EnvTask<ENV_CARTPOLE>::OB; e->info.ac_dim = EnvTask<ENV_CARTPOLE>::AC; e->info.max_ac = EnvTask<ENV_CARTPOLE>::BOUND;
+      break;
+    default:
+      e->info.ob_dim = EnvTask<ENV_POINTGOAL>::OB; e->info.ac_dim = EnvTask<ENV_POINTGOAL>::AC; e->info.max_ac = EnvTask<ENV_POINTGOAL>::BOUND;
+      default_horizon = 50;
+  }
+  e->info.horizon = cfg->horizon ? cfg->horizon : default_horizon;
   e->info.num_envs = cfg->num_envs;
-  e->info.max_ac = pend ? EnvTask<ENV_PENDULUM>::BOUND : EnvTask<ENV_CARTPOLE>::BOUND;
   e->info.min_ac = -e->info.max_ac;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return e->fail(SACTD3_ENODEV, "no HIP device visible");
@@ -162,8 +170,10 @@ static int env_reset_body(sactd3_env* e, uint64_t seed, float* obs, int64_t obs_
   hipStream_t st = (hipStream_t)stream;
   if (e->cfg.kind == SACTD3_ENV_PENDULUM)
     hipLaunchKernelGGL(k_env_reset<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, obs, (long long)obs_ld, seed);
-  else
+  else if (e->cfg.kind == SACTD3_ENV_CARTPOLE)
     hipLaunchKernelGGL(k_env_reset<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, obs, (long long)obs_ld, seed);
+  else
+    hipLaunchKernelGGL(k_env_reset<ENV_POINTGOAL>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, obs, (long long)obs_ld, seed);
   ENV_HIP(e, hipGetLastError());
   return SACTD3_OK;
 }
@@ -198,8 +208,11 @@ static int env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, co
   if (e->cfg.kind == SACTD3_ENV_PENDULUM)
     hipLaunchKernelGGL(k_env_step<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, e->info.horizon,
                        e->cfg.seed);
-  else
+  else if (e->cfg.kind == SACTD3_ENV_CARTPOLE)
     hipLaunchKernelGGL(k_env_step<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, e->info.horizon,
+                       e->cfg.seed);
+  else
+    hipLaunchKernelGGL(k_env_step<ENV_POINTGOAL>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, e->info.horizon,
                        e->cfg.seed);
   ENV_HIP(e, hipGetLastError());
   return SACTD3_OK;
@@ -371,8 +384,11 @@ static int launch_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, 
   if (e->cfg.kind == SACTD3_ENV_PENDULUM)
     hipLaunchKernelGGL(k_env_step_rec<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
                        (long long)obs_ld, e->info.horizon, e->cfg.seed);
-  else
+  else if (e->cfg.kind == SACTD3_ENV_CARTPOLE)
     hipLaunchKernelGGL(k_env_step_rec<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
+                       (long long)obs_ld, e->info.horizon, e->cfg.seed);
+  else
+    hipLaunchKernelGGL(k_env_step_rec<ENV_POINTGOAL>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
                        (long long)obs_ld, e->info.horizon, e->cfg.seed);
   ENV_HIP(e, hipGetLastError());
   return SACTD3_OK;

@@ -6,17 +6,18 @@
 // Arithmetic: fp32, contraction off, ONE operation order -- the order of the expressions below, every product and sum
 // parenthesised as written.  envs.py (HostVecEnv) restates these lines in numpy float32 and tests/env_model.py in float64.
 // The physics is the textbook's: the torque-limited pendulum swing-up, and the cart-pole of Barto, Sutton & Anderson (1983)
-// with a continuous force.
+// with a continuous force; and a 2-D point mass that has to reach a goal drawn per episode, paid -1 per step off the goal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "philox.h"
 
-#define SACTD3_STREAM_ENV 0x500u   // third counter word of every env draw; fourth word: 0 = episode start, 1 = random action
+#define SACTD3_STREAM_ENV 0x500u   // third counter word of every env draw; fourth word: 0 = episode start, 1 = random action, 2 = goal
 
 #define ENV_PENDULUM 0
 #define ENV_CARTPOLE 1
+#define ENV_POINTGOAL 2
 
 // per-env words, struct of arrays: element i belongs to env i
 struct EnvDev {
@@ -48,10 +49,12 @@ struct EnvOut {   // sactd3_env_out with the strides checked
 template <int KIND> struct EnvTask;
 template <> struct EnvTask<ENV_PENDULUM> { static constexpr int OB = 3, AC = 1, NS = 2; static constexpr float BOUND = 2.0f; };
 template <> struct EnvTask<ENV_CARTPOLE> { static constexpr int OB = 4, AC = 1, NS = 4; static constexpr float BOUND = 1.0f; };
+template <> struct EnvTask<ENV_POINTGOAL> { static constexpr int OB = 6, AC = 2, NS = 4; static constexpr float BOUND = 1.0f; };
 
 #define ENV_PI      3.14159274f     // fl32(pi)
 #define ENV_TWO_PI  6.28318548f     // fl32(2 pi)
 #define ENV_INV_2PI 0.159154937f    // fl32(1 / (2 pi))
+#define ENV_GOAL_THR 0.1f           // the point mass is on its goal within this distance (compared squared: one fp32 product)
 
 #pragma clang fp contract(off)
 
@@ -72,23 +75,46 @@ __device__ __forceinline__ void env_first_state(uint64_t seed, uint32_t i, uint3
     s[0] = -ENV_PI + ENV_TWO_PI * u0;   // theta ~ U(-pi, pi)
     s[1] = -1.0f + 2.0f * u1;           // omega ~ U(-1, 1)
     s[2] = 0.0f; s[3] = 0.0f;
-  } else {
+  } else if (KIND == ENV_CARTPOLE) {
     s[0] = -0.05f + 0.1f * u0; s[1] = -0.05f + 0.1f * u1; s[2] = -0.05f + 0.1f * u2; s[3] = -0.05f + 0.1f * u3;
+  } else {
+    s[0] = -1.0f + 2.0f * u0; s[1] = -1.0f + 2.0f * u1;   // x, y ~ U(-1, 1), at rest
+    s[2] = 0.0f; s[3] = 0.0f;
   }
 }
 
+// the goal of episode `ep` of env i: not state, a pure function of (seed, i, ep).  (0, 0) for a task without one.
 template <int KIND>
-__device__ __forceinline__ void env_observe(const float s[4], float* row) {
+__device__ __forceinline__ void env_goal(uint64_t seed, uint32_t i, uint32_t ep, float g[2]) {
+  g[0] = 0.0f; g[1] = 0.0f;
+  if (KIND == ENV_POINTGOAL) {
+    const Philox4 r = philox4x32_10(ep, i, SACTD3_STREAM_ENV, 2u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    g[0] = -1.0f + 2.0f * philox_u01(r.v[0]);
+    g[1] = -1.0f + 2.0f * philox_u01(r.v[1]);
+  }
+}
+
+// the thresholded squared distance of an achieved goal from a desired one: 0 on the goal, -1 off it
+__device__ __forceinline__ float env_goal_reward(float ax, float ay, float gx, float gy) {
+  const float d2 = ((ax - gx) * (ax - gx)) + ((ay - gy) * (ay - gy));
+  return (d2 <= (ENV_GOAL_THR * ENV_GOAL_THR)) ? 0.0f : -1.0f;
+}
+
+template <int KIND>
+__device__ __forceinline__ void env_observe(const float s[4], const float g[2], float* row) {
   if (KIND == ENV_PENDULUM) {
     row[0] = cosf(s[0]); row[1] = sinf(s[0]); row[2] = s[1];
   } else {
     row[0] = s[0]; row[1] = s[1]; row[2] = s[2]; row[3] = s[3];
+    if (KIND == ENV_POINTGOAL) { row[4] = g[0]; row[5] = g[1]; }   // achieved goal: elements 0-1, desired goal: elements 4-5
   }
 }
 
-// one step of the physics: s -> s2, the reward, and whether s2 is terminal; `u` is the clamped, finite action
+// one step of the physics: s -> s2, the reward, and whether s2 is terminal; `ua` is the clamped, finite action, `g` the running
+// episode's goal
 template <int KIND>
-__device__ __forceinline__ void env_physics(const float s[4], float u, float s2[4], float& reward, bool& terminal) {
+__device__ __forceinline__ void env_physics(const float s[4], const float* ua, const float g[2], float s2[4], float& reward, bool& terminal) {
+  const float u = ua[0];
   if (KIND == ENV_PENDULUM) {
     const float th = s[0], w = s[1];
     const float thn = env_angnorm(th);
@@ -98,6 +124,14 @@ __device__ __forceinline__ void env_physics(const float s[4], float u, float s2[
     s2[0] = env_angnorm(th + (0.05f * w2));
     s2[1] = w2; s2[2] = 0.0f; s2[3] = 0.0f;
     reward = -cost;
+    terminal = false;
+  } else if (KIND == ENV_POINTGOAL) {
+    const float vx = (0.8f * s[2]) + (0.2f * ua[0]);
+    const float vy = (0.8f * s[3]) + (0.2f * ua[EnvTask<KIND>::AC - 1]);
+    s2[0] = env_clamp(s[0] + (0.1f * vx), 1.0f);
+    s2[1] = env_clamp(s[1] + (0.1f * vy), 1.0f);
+    s2[2] = vx; s2[3] = vy;
+    reward = env_goal_reward(s2[0], s2[1], g[0], g[1]);   // of the arrival state, against the running episode's goal
     terminal = false;
   } else {
     const float x = s[0], xd = s[1], th = s[2], thd = s[3];
@@ -116,27 +150,44 @@ __device__ __forceinline__ void env_physics(const float s[4], float u, float s2[
   }
 }
 
+// the action as the physics takes it: a NaN or infinite component (every finite float passes) is replaced by 0 and never reaches
+// the state, every component clamped to the bounds -> whether any component was replaced
+template <int KIND>
+__device__ __forceinline__ bool env_clean_action(const float* a, float* u) {
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < EnvTask<KIND>::AC; ++j) {
+    float x = a[j];
+    const bool b = !(fabsf(x) <= 3.40282347e38f);
+    if (b) x = 0.0f;
+    bad = bad || b;
+    u[j] = env_clamp(x, EnvTask<KIND>::BOUND);
+  }
+  return bad;
+}
+
 template <int KIND>
 __global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restrict__ actions, long long act_ld, EnvOut o, int horizon,
                                                   uint64_t seed) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= d.n) return;
   const size_t n = (size_t)d.n;
-  float a = actions[(size_t)i * act_ld];
-  const bool bad = !(fabsf(a) <= 3.40282347e38f);      // NaN or infinite (every finite float passes): never reaches the state
-  if (bad) a = 0.0f;
-  const float u = env_clamp(a, EnvTask<KIND>::BOUND);
-  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4];
+  float a[EnvTask<KIND>::AC], u[EnvTask<KIND>::AC];
+#pragma unroll
+  for (int j = 0; j < EnvTask<KIND>::AC; ++j) a[j] = actions[(size_t)i * act_ld + j];
+  const bool bad = env_clean_action<KIND>(a, u);
+  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4], g[2];
 #pragma unroll
   for (int j = 0; j < EnvTask<KIND>::NS; ++j) s[j] = d.phys[j * n + i];
+  env_goal<KIND>(seed, (uint32_t)i, d.episode[i], g);
   float reward;
   bool terminal;
-  env_physics<KIND>(s, u, s2, reward, terminal);
+  env_physics<KIND>(s, u, g, s2, reward, terminal);
   const int t = d.steps[i] + 1;
   const float ret = d.ret[i] + reward;
   const bool truncated = !terminal && t >= horizon;
   const bool ended = terminal || truncated;
-  if (o.final_obs) env_observe<KIND>(s2, o.final_obs + (size_t)i * o.final_obs_ld);
+  if (o.final_obs) env_observe<KIND>(s2, g, o.final_obs + (size_t)i * o.final_obs_ld);
   if (o.reward) o.reward[(size_t)i * o.reward_ld] = reward;
   if (o.terminated) o.terminated[(size_t)i * o.terminated_ld] = terminal ? 1 : 0;
   if (o.truncated) o.truncated[(size_t)i * o.truncated_ld] = truncated ? 1 : 0;
@@ -153,6 +204,7 @@ __global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restr
     d.last_len[i] = t;
     d.episode[i] = ep;
     env_first_state<KIND>(seed, (uint32_t)i, ep, s2);
+    env_goal<KIND>(seed, (uint32_t)i, ep, g);
     d.steps[i] = 0;
     d.ret[i] = 0.0f;
   } else {
@@ -161,7 +213,7 @@ __global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restr
   }
 #pragma unroll
   for (int j = 0; j < EnvTask<KIND>::NS; ++j) d.phys[j * n + i] = s2[j];
-  env_observe<KIND>(s2, o.obs + (size_t)i * o.obs_ld);
+  env_observe<KIND>(s2, g, o.obs + (size_t)i * o.obs_ld);
 }
 
 // k_env_step that also emits env i's transition as record i of a caller slab in the engine's ring layout (include/sactd3.h:
@@ -186,23 +238,24 @@ __global__ __launch_bounds__(256) void k_env_step_rec(EnvDev d, const float* __r
   uint32_t araw[AC];
 #pragma unroll
   for (int j = 0; j < AC; ++j) araw[j] = __float_as_uint(actions[(size_t)i * act_ld + j]);
-  float a = __uint_as_float(araw[0]);
-  const bool bad = !(fabsf(a) <= 3.40282347e38f);      // NaN or infinite (every finite float passes): never reaches the state
-  if (bad) a = 0.0f;
-  const float u = env_clamp(a, EnvTask<KIND>::BOUND);
-  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4];
+  float a[AC], u[AC];
+#pragma unroll
+  for (int j = 0; j < AC; ++j) a[j] = __uint_as_float(araw[j]);
+  const bool bad = env_clean_action<KIND>(a, u);
+  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4], g[2];
 #pragma unroll
   for (int j = 0; j < EnvTask<KIND>::NS; ++j) s[j] = d.phys[j * n + i];
+  env_goal<KIND>(seed, (uint32_t)i, d.episode[i], g);
   float reward;
   bool terminal;
-  env_physics<KIND>(s, u, s2, reward, terminal);
+  env_physics<KIND>(s, u, g, s2, reward, terminal);
   const int t = d.steps[i] + 1;
   const float ret = d.ret[i] + reward;
   const bool truncated = !terminal && t >= horizon;
   const bool ended = terminal || truncated;
   float so[OB], fin[OB], nx[OB];
-  env_observe<KIND>(s, so);
-  env_observe<KIND>(s2, fin);
+  env_observe<KIND>(s, g, so);
+  env_observe<KIND>(s2, g, fin);
   if (bad) d.bad[i] += 1u;
   if (ended) {
     const uint32_t ep = d.episode[i] + 1u;
@@ -215,6 +268,7 @@ __global__ __launch_bounds__(256) void k_env_step_rec(EnvDev d, const float* __r
     d.last_len[i] = t;
     d.episode[i] = ep;
     env_first_state<KIND>(seed, (uint32_t)i, ep, s2);
+    env_goal<KIND>(seed, (uint32_t)i, ep, g);
     d.steps[i] = 0;
     d.ret[i] = 0.0f;
   } else {
@@ -223,7 +277,7 @@ __global__ __launch_bounds__(256) void k_env_step_rec(EnvDev d, const float* __r
   }
 #pragma unroll
   for (int j = 0; j < EnvTask<KIND>::NS; ++j) d.phys[j * n + i] = s2[j];
-  env_observe<KIND>(s2, nx);
+  env_observe<KIND>(s2, g, nx);
 #pragma unroll
   for (int j = 0; j < OB; ++j) obs[(size_t)i * obs_ld + j] = nx[j];
   // the record, element by element through selects (no indexed local array), four elements per store
@@ -255,13 +309,14 @@ __global__ __launch_bounds__(256) void k_env_reset(EnvDev d, float* __restrict__
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= d.n) return;
   const size_t n = (size_t)d.n;
-  float s[4];
+  float s[4], g[2];
   env_first_state<KIND>(seed, (uint32_t)i, 0u, s);
+  env_goal<KIND>(seed, (uint32_t)i, 0u, g);
 #pragma unroll
   for (int j = 0; j < 4; ++j) d.phys[j * n + i] = s[j];
   d.steps[i] = 0; d.episode[i] = 0u; d.ret[i] = 0.0f; d.draws[i] = 0u;
   d.done_count[i] = 0u; d.ret_sum[i] = 0.0; d.len_sum[i] = 0ull; d.last_ret[i] = 0.0f; d.last_len[i] = 0; d.first_ret[i] = 0.0f; d.first_len[i] = 0; d.bad[i] = 0u;
-  if (obs) env_observe<KIND>(s, obs + (size_t)i * obs_ld);
+  if (obs) env_observe<KIND>(s, g, obs + (size_t)i * obs_ld);
 }
 
 // ac_dim <= 4: dimension j of the draw takes word j

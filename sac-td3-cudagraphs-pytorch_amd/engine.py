@@ -646,6 +646,34 @@ class Engine:
         """host counters of the mixed draw and the pinned ring (sactd3_mix_stats)"""
         return self._stats(self.lib.sactd3_mix_stats, ("mixed_draws", "prior_rows_drawn", "live_rows_drawn", "pinned_wraps"))
 
+    # -- hindsight relabelling at staging (include/sactd3.h: sactd3_hindsight_configure, sactd3_rb_sample_hindsight*)
+    def hindsight_configure(self, achieved: int, desired: int, dim: int, threshold: float, ratio: float, window: int, stride: int) -> None:
+        """sactd3_hindsight_configure: where an observation keeps its achieved and its desired goal, when a goal counts as reached, the
+        share of rows relabelled, how many rows ahead a goal may lie and the rows appended per env step.  Host state: no launch."""
+        cfg = _lib.CHindsightConfig(int(achieved), int(desired), int(dim), int(window), int(stride), float(threshold), float(ratio))
+        self._ck(self.lib.sactd3_hindsight_configure(self._h, C.byref(cfg)))
+
+    def rb_sample_hindsight(self) -> None:
+        """sactd3_rb_sample_hindsight: rb_sample()'s draw (one counter tick), then one launch that relabels goals while it stages."""
+        self._ck(self.lib.sactd3_rb_sample_hindsight(self._h))
+
+    def rb_sample_hindsight_device(self, idx_ptr: int, idx_ld: int, choice_ptr: int, choice_ld: int, n: int, stream: int = 0,
+                                   ordered: bool = True) -> None:
+        """sactd3_rb_sample_hindsight_device: the caller's start slots (int64) and, optionally, its choices (int32; address 0: the
+        native draw) -- below 0 not relabelled, otherwise the offset of the goal's row, cut to the episode's rest.  One launch."""
+        self._ck(self.lib.sactd3_rb_sample_hindsight_device(self._h, _vp(idx_ptr), int(idx_ld), _vp(choice_ptr), int(choice_ld), int(n),
+                                                            _vp(stream), _flag(_lib.SRC_ORDERED, ordered)))
+
+    def hindsight_info_device(self, offset_ptr: int, offset_ld: int, slot_ptr: int, slot_ld: int, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_hindsight_info_device: per row of a hindsight batch slot the offset j (-1: not relabelled or refused) and the goal's ring
+        slot (-1), to int32 arrays in this device's memory (address 0: not wanted).  EngineError (SACTD3_ESTATE) on any other slot."""
+        self._ck(self.lib.sactd3_hindsight_info_device(self._h, _vp(offset_ptr), int(offset_ld), _vp(slot_ptr), int(slot_ld), _vp(stream),
+                                                       _flag(_lib.DST_ORDERED, ordered)))
+
+    def hindsight_stats(self) -> Dict[str, int]:
+        """counters of the hindsight route (sactd3_hindsight_stats; waits for the engine's stream: the last three live on the device)"""
+        return self._stats(self.lib.sactd3_hindsight_stats, ("native_draws", "rows_relabelled", "rows_refused", "rows_reward_zero"))
+
     def acting_stats(self) -> Dict[str, int]:
         """host counters of the two-stream ordering policy (sactd3_acting_stats)"""
         return self._stats(self.lib.sactd3_acting_stats, ("begun", "begin_waited_for_learner", "learner_waited_for_acting", "ended_by_spin"))

@@ -1,19 +1,20 @@
-"""Two real continuous-control tasks for the engine to train on, on the GPU and on the host (include/sactd3_env.h):
+"""Three real continuous-control tasks for the engine to train on, on the GPU and on the host (include/sactd3_env.h):
 
   NativeVecEnv    the vector env that lives on the GPU (csrc/env_kernels.h): `step` is ONE kernel launch on the current torch stream,
                   every array a device tensor, no host draw, no host wait, no torch arithmetic -- the protocol `loop.DeviceRollout`
                   consumes (`loop.train(device_env=True)`); `step_records` is the same step writing its transitions as ring records
                   into the caller's slab (include/sactd3_rollout.h), which `loop.NativeRollout` drives (`native_rollout=True`)
   pack_records    the ring's record layout in numpy: what `step_records` writes, for the host twin's users and for tests
-  HostVecEnv      the same two tasks in numpy float32, in the kernel's operation order and with the same Philox resets, with the
+  HostVecEnv      the same tasks in numpy float32, in the kernel's operation order and with the same Philox resets, with the
                   gymnasium-0.29 protocol of `loop.SyntheticVecEnv` -- for `loop.Rollout`, `loop.Evaluator` and `loop.evaluate`
   greedy_returns  evaluation with one host wait: a vector env stepped in lock-step with the agent's greedy action for one horizon
   device_episodes the same as an episode generator, to stand in for `loop.Evaluator.ep_gen`
 
 The tasks (textbook physics: the torque-limited pendulum swing-up; the cart-pole of Barto, Sutton & Anderson 1983 with a continuous
-force) and the random streams are stated in include/sactd3_env.h.  The host twin computes, bit for bit, what the kernel computes
-except through sin / cos: the reset states, the random actions, the flags' rules and the fp32 accumulation of the returns are the
-same bits."""
+force; a 2-D point mass that has to reach a goal drawn per episode, with a sparse reward) and the random streams are stated in
+include/sactd3_env.h.  The host twin computes, bit for bit, what the kernel computes except through sin / cos: the reset states, the
+random actions, the flags' rules and the fp32 accumulation of the returns are the same bits -- and the point mass, which calls no
+libm function, is the same bits throughout."""
 from __future__ import annotations
 
 import ctypes as C
@@ -23,11 +24,14 @@ import numpy as np
 
 from . import _lib
 
-KINDS = {"pendulum": _lib.ENV_PENDULUM, "cartpole": _lib.ENV_CARTPOLE}
+KINDS = {"pendulum": _lib.ENV_PENDULUM, "cartpole": _lib.ENV_CARTPOLE, "pointgoal": _lib.ENV_POINTGOAL}
 #        kind -> (ob_dim, ac_dim, action bound, default horizon, floats of physical state)
-SPECS = {_lib.ENV_PENDULUM: (3, 1, 2.0, 200, 2), _lib.ENV_CARTPOLE: (4, 1, 1.0, 200, 4)}
+SPECS = {_lib.ENV_PENDULUM: (3, 1, 2.0, 200, 2), _lib.ENV_CARTPOLE: (4, 1, 1.0, 200, 4), _lib.ENV_POINTGOAL: (6, 2, 1.0, 50, 4)}
+# where a goal-conditioned task keeps its goals in an observation, and when it counts as reached (include/sactd3_env.h)
+GOAL_LAYOUTS = {_lib.ENV_POINTGOAL: dict(achieved=0, desired=4, dim=2, threshold=0.1)}
 STREAM_ENV = 0x500          # csrc/env_kernels.h: SACTD3_STREAM_ENV
 F = np.float32
+GOAL_THR = F(0.1)           # csrc/env_kernels.h: ENV_GOAL_THR
 PI, TWO_PI, INV_2PI = F(3.14159274), F(6.28318548), F(0.159154937)       # csrc/env_kernels.h: ENV_PI, ENV_TWO_PI, ENV_INV_2PI
 X_LIMIT, THETA_LIMIT = F(2.4), F(0.20943951)
 
@@ -74,16 +78,27 @@ def first_states(kind: int, seed: int, env_index, episode) -> np.ndarray:
     if kind == _lib.ENV_PENDULUM:
         s[:, 0] = -PI + TWO_PI * u[:, 0]
         s[:, 1] = F(-1.0) + F(2.0) * u[:, 1]
-    else:
+    elif kind == _lib.ENV_CARTPOLE:
         s[:] = F(-0.05) + F(0.1) * u
+    else:
+        s[:, :2] = F(-1.0) + F(2.0) * u[:, :2]
     return s
 
 
+def goals(kind: int, seed: int, env_index, episode) -> np.ndarray:
+    """[n, 2] float32: the goal of episode `episode[k]` of env `env_index[k]` -- a pure function of (seed, env, episode); zeros for a
+    task without one"""
+    w = _words(seed, np.asarray(episode), np.asarray(env_index), 2)
+    if kind != _lib.ENV_POINTGOAL:
+        return np.zeros((len(w[0]), 2), F)
+    return np.stack([F(-1.0) + F(2.0) * u01(w[0]), F(-1.0) + F(2.0) * u01(w[1])], 1).astype(F)
+
+
 def random_actions(kind: int, seed: int, env_index, draw) -> np.ndarray:
-    """[n, 1] float32: random action number `draw[k]` of env `env_index[k]`, uniform inside the bounds"""
+    """[n, ac_dim] float32: random action number `draw[k]` of env `env_index[k]`, uniform inside the bounds; dimension j takes word j"""
     bound = F(SPECS[kind][2])
     w = _words(seed, np.asarray(draw), np.asarray(env_index), 1)
-    return (-bound + (bound - (-bound)) * u01(w[0])).astype(F).reshape(-1, 1)
+    return np.stack([(-bound + (bound - (-bound)) * u01(w[j])).astype(F) for j in range(SPECS[kind][1])], 1)
 
 
 # ---------------------------------------------------------------------------------------------------- the physics, float32
@@ -91,11 +106,25 @@ def _angnorm(x):
     return x - TWO_PI * np.floor((x + PI) * INV_2PI)
 
 
-def physics(kind: int, s: np.ndarray, u: np.ndarray):
-    """csrc/env_kernels.h: env_physics line for line in numpy float32.  s [n, 4], u [n] clamped and finite -> (s2 [n, 4], reward [n],
-    terminal [n])"""
+def goal_reward(achieved: np.ndarray, goal: np.ndarray) -> np.ndarray:
+    """csrc/env_kernels.h: env_goal_reward in numpy float32: [n, 2] against [n, 2] -> [n], 0 on the goal and -1 off it"""
+    assert achieved.dtype == F and goal.dtype == F
+    dx, dy = achieved[:, 0] - goal[:, 0], achieved[:, 1] - goal[:, 1]
+    d2 = (dx * dx) + (dy * dy)
+    return np.where(d2 <= (GOAL_THR * GOAL_THR), F(0.0), F(-1.0)).astype(F)
+
+
+def physics(kind: int, s: np.ndarray, u: np.ndarray, goal: Optional[np.ndarray] = None):
+    """csrc/env_kernels.h: env_physics line for line in numpy float32.  s [n, 4], u [n] ([n, 2] for the point mass) clamped and finite,
+    goal [n, 2] of the running episodes (the point mass only) -> (s2 [n, 4], reward [n], terminal [n])"""
     assert s.dtype == F and u.dtype == F
     s2 = np.zeros_like(s)
+    if kind == _lib.ENV_POINTGOAL:
+        v = (F(0.8) * s[:, 2:4]) + (F(0.2) * u)
+        s2[:, 0:2] = np.minimum(np.maximum(s[:, 0:2] + (F(0.1) * v), F(-1.0)), F(1.0))
+        s2[:, 2:4] = v
+        assert s2.dtype == F
+        return s2, goal_reward(s2[:, 0:2], np.asarray(goal, F)), np.zeros(len(s), bool)
     if kind == _lib.ENV_PENDULUM:
         th, w = s[:, 0], s[:, 1]
         thn = _angnorm(th)
@@ -120,18 +149,23 @@ def physics(kind: int, s: np.ndarray, u: np.ndarray):
     return s2, np.ones(len(u), F), (np.abs(s2[:, 0]) > X_LIMIT) | (np.abs(s2[:, 2]) > THETA_LIMIT)
 
 
-def observe(kind: int, s: np.ndarray) -> np.ndarray:
+def observe(kind: int, s: np.ndarray, goal: Optional[np.ndarray] = None) -> np.ndarray:
     if kind == _lib.ENV_PENDULUM:
         return np.stack([np.cos(s[:, 0]), np.sin(s[:, 0]), s[:, 1]], 1).astype(F)
+    if kind == _lib.ENV_POINTGOAL:
+        return np.concatenate([s.astype(F), np.asarray(goal, F)], 1)
     return s.astype(F).copy()
 
 
 def clean_actions(kind: int, actions, n: int):
-    """-> (u [n] float32 clamped, bad [n] bool): a NaN or infinite action is replaced by 0"""
-    a = np.asarray(actions, F).reshape(n, -1)[:, 0]
-    bad = ~np.isfinite(a)
+    """-> (u [n] float32 clamped ([n, ac_dim] where ac_dim > 1), bad [n] bool): a NaN or infinite action component is replaced by 0;
+    `bad` marks the steps with any such component"""
+    ac = SPECS[kind][1]
+    a = np.asarray(actions, F).reshape(n, -1)[:, :ac]
+    nonfinite = ~np.isfinite(a)
     bound = F(SPECS[kind][2])
-    return np.minimum(np.maximum(np.where(bad, F(0.0), a), -bound), bound).astype(F), bad
+    u = np.minimum(np.maximum(np.where(nonfinite, F(0.0), a), -bound), bound).astype(F)
+    return (u[:, 0] if ac == 1 else u), nonfinite.any(1)
 
 
 # ---------------------------------------------------------------------------------------------------- the host twin
@@ -149,7 +183,7 @@ class _HostBox:
 
 
 class HostVecEnv:
-    """The two tasks on the host, float32 numpy in the kernel's operation order, with gymnasium-0.29 autoreset semantics as
+    """The tasks on the host, float32 numpy in the kernel's operation order, with gymnasium-0.29 autoreset semantics as
     `loop.SyntheticVecEnv` has them: on termination or truncation `infos["final_observation"][k]` (an object array) holds the
     observation the step arrived at, `infos["final_info"][k]["episode"]` its length `l` and return `r`, and the returned observation
     is the next episode's first one.  Episode k of env i starts where it starts on the GPU (the same Philox draw)."""
@@ -157,6 +191,7 @@ class HostVecEnv:
     def __init__(self, kind, num_envs: int, seed: int = 0, horizon: Optional[int] = None):
         self.kind = kind_of(kind)
         self.o, self.a, self.bound, default_horizon, _ = SPECS[self.kind]
+        self.goal_layout = dict(GOAL_LAYOUTS[self.kind]) if self.kind in GOAL_LAYOUTS else None
         self.n = self.num_envs = int(num_envs)
         if self.n < 1:
             raise ValueError("num_envs must be >= 1")
@@ -170,6 +205,7 @@ class HostVecEnv:
             self.seed = int(seed)
         n = self.n
         self.s = first_states(self.kind, self.seed, np.arange(n), np.zeros(n, np.uint32))
+        self.goal = goals(self.kind, self.seed, np.arange(n), np.zeros(n, np.uint32))
         self.t = np.zeros(n, np.int32)
         self.ep = np.zeros(n, np.uint32)
         self.ret = np.zeros(n, F)
@@ -178,20 +214,20 @@ class HostVecEnv:
         self._ret_sum, self._len_sum = 0.0, 0
         self._last_ret, self._last_len = np.zeros(n, F), np.zeros(n, np.int32)
         self._first_ret, self._first_len = np.zeros(n, F), np.zeros(n, np.int32)
-        return observe(self.kind, self.s), {}
+        return observe(self.kind, self.s, self.goal), {}
 
     def step(self, actions):
         n = self.n
         u, bad = clean_actions(self.kind, actions, n)
         self._bad += int(bad.sum())
-        s2, rew, term = physics(self.kind, self.s, u)
+        s2, rew, term = physics(self.kind, self.s, u, self.goal)
         self.t = self.t + np.int32(1)
         self.ret = (self.ret + rew).astype(F)
         trunc = (self.t >= self.horizon) & ~term
         ended = term | trunc
         infos: Dict[str, Any] = {}
         if ended.any():
-            final = observe(self.kind, s2)
+            final = observe(self.kind, s2, self.goal)      # (against the goal of the episode that ends)
             infos["final_observation"] = np.array([final[k].copy() if ended[k] else None for k in range(n)], dtype=object)
             infos["final_info"] = np.array([{"episode": {"l": np.array([self.t[k]]), "r": np.array([self.ret[k]])}} if ended[k] else None
                                             for k in range(n)], dtype=object)
@@ -204,10 +240,11 @@ class HostVecEnv:
             self._last_ret[at], self._last_len[at] = self.ret[at], self.t[at]
             self.ep[at] += np.uint32(1)
             s2[at] = first_states(self.kind, self.seed, at, self.ep[at])
+            self.goal[at] = goals(self.kind, self.seed, at, self.ep[at])
             self.t[at] = 0
             self.ret[at] = 0.0
         self.s = s2
-        return observe(self.kind, self.s), rew.astype(F), term, trunc, infos
+        return observe(self.kind, self.s, self.goal), rew.astype(F), term, trunc, infos
 
     def episode_stats(self) -> Dict[str, Any]:
         return {"episodes": int(self._done.sum()), "return_sum": self._ret_sum, "length_sum": self._len_sum, "bad_actions": self._bad,
@@ -222,6 +259,7 @@ class HostVecEnv:
         for key, name, dt in (("phys", "s", F), ("steps", "t", np.int32), ("episode", "ep", np.uint32), ("returns", "ret", F), ("draws", "draws", np.uint32)):
             if key in state:
                 setattr(self, name, np.array(state[key], dt).reshape(getattr(self, name).shape))
+        self.goal = goals(self.kind, self.seed, np.arange(self.n), self.ep)      # (not state: a function of the episode index)
 
 
 _STATE_KEYS = {"phys": (F, _lib.ENV_STATE_DIM), "steps": (np.int32, 1), "episode": (np.uint32, 1), "returns": (F, 1), "draws": (np.uint32, 1)}
@@ -318,6 +356,7 @@ class NativeVecEnv:
         info = _lib.CEnvInfo()
         self._call("sactd3_env_spec", C.byref(info))
         self.o, self.a, self.horizon, self.bound = int(info.ob_dim), int(info.ac_dim), int(info.horizon), float(info.max_ac)
+        self.goal_layout = dict(GOAL_LAYOUTS[self.kind]) if self.kind in GOAL_LAYOUTS else None
         self.action_space = _DeviceBox(self)
 
     # -- plumbing

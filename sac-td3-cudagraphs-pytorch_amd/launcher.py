@@ -32,9 +32,10 @@ ENV_BUNDLES = {
     "low": ["Hopper-v4", "Pusher-v4"],
     "medium": ["HalfCheetah-v4", "Walker2d-v4", "Ant-v4"],
     "high": ["Humanoid-v4", "HumanoidStandup-v4"],
-    "native": ["Pendulum-native", "CartPole-native"],      # the two tasks this package simulates itself (envs.py)
+    "native": ["Pendulum-native", "CartPole-native"],      # the two dense-reward tasks this package simulates itself (envs.py)
+    "native_goal": ["PointGoal-native"],                   # ... and its goal-conditioned, sparse-reward one
 }
-NATIVE_ENVS = {"Pendulum-native": "pendulum", "CartPole-native": "cartpole"}      # env id -> envs.py kind
+NATIVE_ENVS = {"Pendulum-native": "pendulum", "CartPole-native": "cartpole", "PointGoal-native": "pointgoal"}      # env id -> envs.py kind
 
 
 def sweep_jobs(env_bundle: str, num_seeds: int) -> List[Tuple[str, int]]:
@@ -185,7 +186,7 @@ def _host(x):
 ENV_DIMS = {   # (ob_dim, ac_dim, action bound) of the Gymnasium MuJoCo -v4 tasks named by the bundles (public task specs)
     "Hopper-v4": (11, 3, 1.0), "Pusher-v4": (23, 7, 2.0), "HalfCheetah-v4": (17, 6, 1.0), "Walker2d-v4": (17, 6, 1.0),
     "Ant-v4": (27, 8, 1.0), "Humanoid-v4": (376, 17, 0.4), "HumanoidStandup-v4": (376, 17, 0.4),
-    "Pendulum-native": (3, 1, 2.0), "CartPole-native": (4, 1, 1.0),      # include/sactd3_env.h
+    "Pendulum-native": (3, 1, 2.0), "CartPole-native": (4, 1, 1.0), "PointGoal-native": (6, 2, 1.0),      # include/sactd3_env.h
 }
 
 
@@ -294,22 +295,60 @@ def native_rollout_plan(env_ids, device_env: bool, has_factory: bool, offline: b
         env_plan(env_id, device_env, has_factory, native_rollout=True)
 
 
+def goal_layout_of(env_id: str, has_factory: bool = False) -> Optional[dict]:
+    """dict(achieved=, desired=, dim=, threshold=, horizon=) of a -native env id whose task has a goal (envs.GOAL_LAYOUTS), else None;
+    decided without touching a GPU"""
+    if env_id not in NATIVE_ENVS or has_factory:
+        return None
+    from . import envs      # (numpy and ctypes only)
+    kind = envs.kind_of(NATIVE_ENVS[env_id])
+    if kind not in envs.GOAL_LAYOUTS:
+        return None
+    return dict(envs.GOAL_LAYOUTS[kind], horizon=envs.SPECS[kind][3])
+
+
+def hindsight_plan(env_ids, has_factory: bool, offline: bool) -> None:
+    """What --hindsight needs, checked without touching a GPU for every env id it is asked for: ValueError for an env without a goal
+    layout, and beside a dataset"""
+    if offline:
+        raise ValueError("--hindsight excludes --offline_dataset: there is no env loop whose episodes could be relabelled")
+    for env_id in env_ids:
+        if goal_layout_of(env_id, has_factory) is None:
+            with_goal = [k for k in NATIVE_ENVS if goal_layout_of(k) is not None]
+            raise ValueError(f"--hindsight needs an env with a goal layout ({', '.join(with_goal)}) without --env_factory: {env_id} has none")
+
+
+def hindsight_keywords(env_id: str, num_envs: int) -> dict:
+    """loop.train's hindsight=dict(...) for a goal env id: its layout, window = its horizon, stride = the env count"""
+    lay = goal_layout_of(env_id)
+    return dict(achieved=lay["achieved"], desired=lay["desired"], dim=lay["dim"], threshold=lay["threshold"], window=lay["horizon"],
+                stride=int(num_envs))
+
+
 def mode_flags(args, plan) -> dict:
-    """the flags that shape the env loop, under the names run_job and train_keywords take them by (`plan`: offline_plan(args) or {})"""
-    return dict(prioritized=args.prioritized, n_step=args.n_step, one_launch=args.one_launch, prior_fraction=plan.get("prior_fraction"),
-                updates_per_step=args.updates_per_step or 1, overlap_acting=args.overlap_acting, device_env=args.device_env,
-                native_rollout=args.native_rollout, policy_stats=policy_stats_plan(args))
+    """the flags that shape the env loop, under the names run_job and train_keywords take them by (`plan`: offline_plan(args) or {});
+    `hindsight` is among them only when --hindsight was given"""
+    flags = dict(prioritized=args.prioritized, n_step=args.n_step, one_launch=args.one_launch, prior_fraction=plan.get("prior_fraction"),
+                 updates_per_step=args.updates_per_step or 1, overlap_acting=args.overlap_acting, device_env=args.device_env,
+                 native_rollout=args.native_rollout, policy_stats=policy_stats_plan(args))
+    if getattr(args, "hindsight", False):
+        flags["hindsight"] = True
+    return flags
 
 
 def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, prior_fraction, updates_per_step, overlap_acting: bool,
-                   device_env: bool, native_rollout: bool, policy_stats: int) -> dict:
+                   device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
-    --n_step N > 1 and --prior_fraction are issued call by call (fused=False), or with --one_launch as one graph launch per iteration."""
-    update = dict(fused=not prioritized and n_step == 1 and prior_fraction is None,
+    --n_step N > 1 and --prior_fraction are issued call by call (fused=False), or with --one_launch as one graph launch per iteration.
+    `hindsight` (--hindsight: the dict of hindsight_keywords for the job's env): call by call as well; the key is in the result only
+    when it was given."""
+    update = dict(fused=not prioritized and n_step == 1 and prior_fraction is None and not hindsight,
                   prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch,
                   prior_fraction=None if prior_fraction is None else float(prior_fraction), updates_per_step=int(updates_per_step))
+    if hindsight:
+        update["hindsight"] = dict(hindsight)
     loop.update_plan(cfg, sampler=None, **update)
     return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats))
 
@@ -317,7 +356,7 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
-            native_rollout: bool = False, **over):
+            native_rollout: bool = False, hindsight: bool = False, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -325,7 +364,9 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     `prior_fraction` beside `offline_dataset`: an online run on top of the dataset instead -- the ring is filled and its rows pinned
     (loop.load_dataset(pin=True)), then loop.train draws that share of every batch from them; `updates_per_step`: updates per
     segment of any online run; `policy_stats`: rows put to the policy at every evaluation (loop.PolicyStats; SAC only);
-    `native_rollout`: the env loop through loop.NativeRollout (needs `device_env` and a -native id: env_plan refuses otherwise)."""
+    `native_rollout`: the env loop through loop.NativeRollout (needs `device_env` and a -native id: env_plan refuses otherwise);
+    `hindsight`: the engine relabels goals while it stages each batch (loop.train hindsight=...; needs an env id with a goal layout:
+    hindsight_plan refuses otherwise)."""
     import json
     import time
     from pathlib import Path
@@ -336,9 +377,11 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
         raise ValueError("policy_stats needs algo sac: TD3's deterministic actor has no log-probability, entropy or log-std to report")
     if native_rollout:                           # (before anything is built)
         native_rollout_plan([env_id], device_env, env_factory is not None, offline_dataset is not None, overlap_acting)
+    if hindsight:                                # (before anything is built)
+        hindsight_plan([env_id], env_factory is not None, offline_dataset is not None)
     cfg = job_config(algo, env_id, seed, **over)
     o, a, bound = ENV_DIMS[env_id]
-    native = env_id in NATIVE_ENVS and env_factory is None      # the two tasks this package simulates itself (env_plan)
+    native = env_id in NATIVE_ENVS and env_factory is None      # the tasks this package simulates itself (env_plan)
     on_gpu = native and device_env                              # ... with --device_env on the GPU, training AND evaluation: no host env
     dev = torch.device("cuda", device_index)
     if native:
@@ -377,7 +420,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     else:
         kw = train_keywords(cfg, prioritized=prioritized, n_step=n_step, one_launch=one_launch, prior_fraction=prior_fraction,
                             updates_per_step=updates_per_step, overlap_acting=overlap_acting, device_env=device_env,
-                            native_rollout=native_rollout, policy_stats=policy_stats)
+                            native_rollout=native_rollout, policy_stats=policy_stats,
+                            **(dict(hindsight=hindsight_keywords(env_id, cfg.num_envs)) if hindsight else {}))
         metrics = loop.train(cfg, env, agent, evaluator=ev, **kw)
     agent.engine.sync()
     dt = time.time() - t0
@@ -403,6 +447,8 @@ def _worker_main(args, plan, flags) -> int:
         if args.dry_run:
             out = {"env_id": env_id, "algo": args.algo, "seed": seed, "gpu": args.rank, "dry_run": True,
                    "rollout": env_plan(env_id, args.device_env, factory is not None, native_rollout=args.native_rollout)["rollout"]}
+            if args.hindsight:                   # (the key is there only when the flag was given)
+                out["hindsight"] = hindsight_keywords(env_id, job_config(args.algo, env_id, seed).num_envs)
         else:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
@@ -441,6 +487,10 @@ def main(argv=None) -> int:
     ap.add_argument("--native_rollout", action="store_true",
                     help="with --device_env and a -native env bundle: the env step writes ring records and choose / advance are one library "
                          "call each (loop.train native_rollout=True); the default stays loop.DeviceRollout")
+    ap.add_argument("--hindsight", action="store_true",
+                    help="with an env bundle whose tasks have a goal (native_goal): the engine relabels goals while it stages each batch -- "
+                         "hindsight experience replay, the future strategy, window = the task's horizon (loop.train hindsight=...; the "
+                         "iteration is issued call by call)")
     ap.add_argument("--prioritized", action="store_true",
                     help="proportional prioritised replay kept by the engine (loop.train prioritized=...; the iteration is issued call by call)")
     ap.add_argument("--one_launch", action="store_true",
@@ -472,8 +522,13 @@ def main(argv=None) -> int:
         if args.native_rollout:                  # every job of the sweep, before a worker starts
             native_rollout_plan(ENV_BUNDLES[args.env_bundle], args.device_env, bool(args.env_factory), args.offline_dataset is not None,
                                 args.overlap_acting)
+        if args.hindsight:                       # every job of the sweep, before a worker starts
+            hindsight_plan(ENV_BUNDLES[args.env_bundle], bool(args.env_factory), args.offline_dataset is not None)
         # what loop.train would refuse is refused here, with no worker started (no env loop: offline_plan left no flag for it to mind)
-        train_keywords(job_config(args.algo, None, 0, batch_size=args.batch_size), **flags)
+        facts = {k: v for k, v in flags.items() if k != "hindsight"}
+        for env_id in (ENV_BUNDLES[args.env_bundle] if args.hindsight else [None]):      # (with --hindsight: each job's own layout)
+            cfg0 = job_config(args.algo, env_id, 0, batch_size=args.batch_size)
+            train_keywords(cfg0, **facts, **(dict(hindsight=hindsight_keywords(env_id, cfg0.num_envs)) if args.hindsight else {}))
     except ValueError as ex:
         ap.error(str(ex))
     if args.worker:

@@ -328,7 +328,8 @@ class PolicyStats:
 
 
 def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler], prioritized: Optional[Dict[str, float]], n_step: int,
-                one_launch: bool, prior_fraction: Optional[float], updates_per_step: int) -> SimpleNamespace:
+                one_launch: bool, prior_fraction: Optional[float], updates_per_step: int,
+                hindsight: Optional[Dict[str, Any]] = None) -> SimpleNamespace:
     """What train() does with one update, decided once from its keywords: touches no agent, env or GPU and imports nothing, so a process
     that never opens a GPU can ask whether a run would be refused.  `cfg` needs `batch_size` (with `prior_fraction`, and when an update is
     issued call by call), `num_envs` (with `n_step` > 1) and `actor_update_delay` (call by call).  Which keywords need or exclude each
@@ -337,15 +338,21 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
     -> a namespace of
       updates_per_step  as an int
       priorities        None, or dict(alpha=, eps=) for `agent.rb.enable_priorities` -- train() enables them once, before its loop
+      hindsight         None, or the keywords of `agent.rb.configure_hindsight` (`hindsight` as given, `stride` defaulting to
+                        cfg.num_envs) -- train() configures the buffer once, in the same place
       update            `update(agent, i, tlog)`: iteration i, in ONE of three forms chosen here --
                           fused        agent.iteration(i)
                           one launch   agent.iteration(i, prior_rows=) or agent.iteration(i, beta=, n_step=, stride=), the values fixed here
-                          call by call one draw (uniform `rb.sample`, `sampler` + `rb.sample_at`, `rb.sample_prioritized`, `rb.sample_mixed`) ->
+                          call by call one draw (uniform `rb.sample`, `sampler` + `rb.sample_at`, `rb.sample_prioritized`, `rb.sample_mixed`,
+                                       `rb.sample_hindsight`) ->
                                        update_qnets -> its write-back (`sampler.update` / `rb.update_priorities`) -> counters -> every
                                        delay + 1 iterations delay x update_actor -> update_targ_nets; losses go into `tlog`"""
     updates_per_step, n_step = int(updates_per_step), int(n_step)
     prior, prio, outside = prior_fraction is not None, prioritized is not None, sampler is not None
     unknown = sorted(set(prioritized or ()) - {"alpha", "beta", "eps"})
+    hind = hindsight is not None
+    hs_unknown = sorted(set(hindsight or ()) - {"achieved", "desired", "dim", "threshold", "ratio", "window", "stride"})
+    hs_missing = sorted({"achieved", "desired", "dim", "threshold"} - set(hindsight or ())) if hind else []
     refusals = (
         (updates_per_step < 1, f"updates_per_step must be >= 1, got {updates_per_step}"),
         (prior and not 0.0 <= float(prior_fraction) <= 1.0, f"prior_fraction must be in [0, 1], got {prior_fraction}"),
@@ -363,6 +370,14 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
         (prio and fused, "prioritized=... needs fused=False: the fused iteration samples uniformly inside its graph"),
         (prio and outside, "prioritized=... and sampler=... exclude each other: one owner for the priorities"),
         (bool(unknown), f"prioritized: unknown keys {unknown}"),
+        (hind and fused, "hindsight=... needs fused=False: the fused iteration samples uniformly inside its graph and relabels nothing"),
+        (hind and outside, "hindsight=... and sampler=... exclude each other: the engine relabels the rows of its own draw"),
+        (hind and prio, "hindsight=... and prioritized=... exclude each other: a relabelled row's TD error is not its record's priority"),
+        (hind and n_step > 1, "hindsight=... excludes n_step > 1: a relabelled reward is a single step's, the chain's return is not"),
+        (hind and prior, "hindsight=... and prior_fraction=... exclude each other: a pinned ring has no episode chains yet"),
+        (hind and one_launch, "hindsight=... excludes one_launch=True: the hindsight staging has no graph form"),
+        (bool(hs_unknown), f"hindsight: unknown keys {hs_unknown}"),
+        (bool(hs_missing), f"hindsight: missing keys {hs_missing}"),
     )
     for applies, why in refusals:
         if applies:
@@ -371,6 +386,7 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
     chain = dict(n_step=n_step, stride=int(cfg.num_envs)) if n_step > 1 else {}
     beta = float(prioritized.get("beta", 0.4)) if prio else None
     priorities = dict(alpha=float(prioritized.get("alpha", 0.6)), eps=float(prioritized.get("eps", 1e-6))) if prio else None
+    hs_config = dict(hindsight, stride=int(hindsight["stride"]) if hindsight.get("stride") is not None else int(cfg.num_envs)) if hind else None
     if fused:
         update = lambda agent, i, tlog: agent.iteration(i)
     elif one_launch and prior:                                           # (a keyword the older signature lacks: only when used)
@@ -385,6 +401,8 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
         elif prio:
             draw = lambda agent: (agent.rb.sample_prioritized(cfg.batch_size, beta, **chain), None)
             write_back = lambda agent, index: agent.rb.update_priorities()
+        elif hind:
+            draw = lambda agent: (agent.rb.sample_hindsight(cfg.batch_size), None)
         elif not outside:
             draw = lambda agent: (agent.rb.sample(cfg.batch_size, **chain), None)
         else:
@@ -403,7 +421,7 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
                     tlog.update(agent.update_actor(batch))
                     agent.actor_updates_so_far += 1
             agent.update_targ_nets()
-    return SimpleNamespace(updates_per_step=updates_per_step, priorities=priorities, update=update)
+    return SimpleNamespace(updates_per_step=updates_per_step, priorities=priorities, hindsight=hs_config, update=update)
 
 
 def _eval_point(agent, pstats: Optional[PolicyStats], evaluator: Optional["Evaluator"], on_eval, count: int) -> None:
@@ -424,7 +442,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           evaluator: Optional["Evaluator"] = None, overlap: bool = False, device_env: bool = False,
           sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
           n_step: int = 1, one_launch: bool = False, prior_fraction: Optional[float] = None,
-          updates_per_step: int = 1, policy_stats: int = 0, native_rollout: bool = False) -> Dict[str, float]:
+          updates_per_step: int = 1, policy_stats: int = 0, native_rollout: bool = False,
+          hindsight: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -453,6 +472,10 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     with the same results bit for bit and the same counters.
     `prior_fraction` (in [0, 1]): learning online from prior data -- every batch takes round(prior_fraction * batch_size) rows from
     the rows `agent.rb.pin()` protects (`load_dataset(..., pin=True)`) and the others from the rows the run appends (`rb.sample_mixed`).
+    `hindsight` (dict(achieved=, desired=, dim=, threshold= [, ratio=, window=, stride=]): the keywords of `rb.configure_hindsight`,
+    `stride` defaulting to cfg.num_envs): a goal-conditioned task with a sparse reward -- every batch is drawn as `rb.sample` draws it
+    and a `ratio` share of its rows is relabelled by the engine while it is staged, with a goal the row's own episode reached later
+    (`rb.sample_hindsight`; call by call, fused=False).  `envs.NativeVecEnv.goal_layout` gives the first four keys for a native task.
     `updates_per_step` (>= 1, every mode): the update-to-data ratio -- after each segment the update runs that many times, `i` and the
     update counters advancing per update; 1 is the reference's loop.
     `policy_stats=N` (default 0: off, and no call is made; SAC only): at every evaluation point N ring rows are put to the policy
@@ -460,10 +483,12 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     and returned with the last metrics; the run itself is bit for bit the run without it."""
     pstats = PolicyStats(agent, policy_stats, cfg.seed) if policy_stats else None
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
-                       prior_fraction=prior_fraction, updates_per_step=updates_per_step)
+                       prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight)
     make_rollout = rollout_for(env, overlap=overlap, device_env=device_env, native_rollout=native_rollout)
     if plan.priorities is not None:                                       # (nothing above touched the agent's engine)
         agent.rb.enable_priorities(**plan.priorities)
+    if plan.hindsight is not None:
+        agent.rb.configure_hindsight(**plan.hindsight)
     ro = make_rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat) if make_rollout is not None else None
     resolve = ro.resolve if ro is not None else (lambda: None)            # (segment()'s own host rollout never has an action pending)
     seg_gen = segment(env, agent, cfg.seed, cfg.segment_len, cfg.learning_starts, cfg.action_repeat, rollout=ro)
