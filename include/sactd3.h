@@ -417,14 +417,17 @@ int sactd3_mix_stats(sactd3_engine* e, int64_t out[4]);
  *   6. two per-slot int32 arrays, made at the first staging call: the offset j (-1: not relabelled or refused) and the goal's ring slot
  *      (-1); read with sactd3_hindsight_info_device.
  *   7. three device counters, one atomic per counted row: rows relabelled, rows refused, rows whose relabelled reward is 0.
- * Out of scope: a graph form (sactd3_step_sampled and the fused graphs know no hindsight), priorities, n-step chains or pinned rows beside
- *   it, strategies other than "future", recomputing the flag on success, other reward functions, the config in checkpoints. */
+ * The graph form: sactd3_step_sampled with SACTD3_DRAW_HINDSIGHT holds the native draw and this staging in the iteration's one graph.
+ * Out of scope: hindsight inside the fused graphs (sactd3_step, the period graphs), injected choices inside a graph, priorities, n-step
+ *   chains or pinned rows beside it, strategies other than "future", recomputing the flag on success, other reward functions, the
+ *   config in checkpoints. */
 typedef struct sactd3_hindsight_config {
   int32_t ag_off, dg_off, goal_dim, window, stride;
   float threshold, ratio;
 } sactd3_hindsight_config;
 /* SACTD3_EINVAL: goal_dim outside [1, 8]; a goal range outside [0, ob_dim) or overlapping the other; window outside [1, 64]; stride < 1;
- * threshold negative or not finite; ratio outside [0, 1] or NaN.  Host state only: no launch, the run-ahead chain stays intact. */
+ * threshold negative or not finite; ratio outside [0, 1] or NaN.  Host state only: no launch, the run-ahead chain stays intact.  A
+ * changed config drops the graphs sactd3_step_sampled captured for SACTD3_DRAW_HINDSIGHT (they hold the config by value). */
 int sactd3_hindsight_configure(sactd3_engine* e, const sactd3_hindsight_config* cfg);
 /* The engine's own uniform draw (k_mix_draw with nothing pinned: the slots sactd3_rb_sample would draw; the sample counter advances
  * once), then the staging launch.  SACTD3_ESTATE: hindsight not configured, rows pinned (the age formula assumes one wrap point), ring
@@ -491,10 +494,21 @@ int sactd3_step(sactd3_engine* e, int do_actor);
  * target update; no priority write-back.  Bit for bit, host state included, the call sequence sactd3_rb_sample_mixed ->
  * sactd3_update_qnets -> [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets.  Captured under the same
  * (draw, n_step, stride) key and replayed while the ring grows, the live region wraps and m and P change (a changed m or P costs one
- * single-thread launch in front of the graph).  n_step must be 1 (SACTD3_EINVAL); the refusals of sactd3_rb_sample_mixed apply. */
-enum { SACTD3_DRAW_UNIFORM = 0, SACTD3_DRAW_PRIORITIZED = 1, SACTD3_DRAW_MIXED = 2 };
+ * single-thread launch in front of the graph).  n_step must be 1 (SACTD3_EINVAL); the refusals of sactd3_rb_sample_mixed apply.
+ * SACTD3_DRAW_HINDSIGHT: the native draw and the relabelling of sactd3_rb_sample_hindsight (above) with the current
+ * sactd3_hindsight_configure values.  The graph holds, in order: k_hindsight_draw_g (the uniform draw; it reads the ring length from
+ * device memory, ticks the sample counter and carries the count of native hindsight draws: a device word it advances and whose old
+ * value it leaves for the staging), k_hindsight_stage_g (ring length, cursor and that count from device memory, the config by value),
+ * the UNWEIGHTED critic update, the actor updates, the target update; no tick launch, no priority write-back: as many nodes as the
+ * SACTD3_DRAW_MIXED graph.  Bit for bit, host state included (the slot is a hindsight slot: sactd3_hindsight_info_device and
+ * sactd3_hindsight_stats work behind it), the call sequence sactd3_rb_sample_hindsight -> sactd3_update_qnets -> [sactd3_update_actor x
+ * actor_update_delay] -> sactd3_update_targ_nets.  Captured under the same (draw, n_step, stride) key and replayed while the ring grows,
+ * fills and wraps; sactd3_hindsight_configure with a CHANGED config drops the captured graphs (the same config again drops nothing); a
+ * call-form native draw between two graph launches costs one single-thread launch in front of the next graph.  `beta` is checked and
+ * otherwise ignored.  n_step must be 1 (SACTD3_EINVAL); SACTD3_ESTATE: hindsight not configured, rows pinned, an empty ring. */
+enum { SACTD3_DRAW_UNIFORM = 0, SACTD3_DRAW_PRIORITIZED = 1, SACTD3_DRAW_MIXED = 2, SACTD3_DRAW_HINDSIGHT = 3 };
 typedef struct {
-  int32_t draw;      /* SACTD3_DRAW_UNIFORM | SACTD3_DRAW_PRIORITIZED | SACTD3_DRAW_MIXED */
+  int32_t draw;      /* SACTD3_DRAW_UNIFORM | SACTD3_DRAW_PRIORITIZED | SACTD3_DRAW_MIXED | SACTD3_DRAW_HINDSIGHT */
   int32_t n_step;    /* 1 .. 16 */
   int32_t stride;    /* rows between two steps of one env; ignored at n_step == 1 */
   float beta;        /* exponent of the importance weights; ignored by the uniform draw (but checked) */

@@ -22,6 +22,7 @@ PI_ONLINE, PI_TARGET = 0, 1   # sactd3_policy / sactd3_policy_device `which` (th
 ESTATE, EINVAL = -3, -1
 DRAW_UNIFORM, DRAW_PRIORITIZED = 0, 1   # sactd3_sampling.draw
 DRAW_MIXED = 2                          # ... the mixed draw over pinned and live rows (sactd3_rb_pin / sactd3_rb_set_mix)
+DRAW_HINDSIGHT = 3                      # ... the uniform draw with goals relabelled while the rows are staged (sactd3_hindsight_configure)
 
 # every symbol include/sactd3.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [

@@ -891,16 +891,22 @@ class Agent:
         self.engine.update_targ_nets(self.qnet_updates_so_far)
 
     def iteration(self, i: int, *, beta: Optional[float] = None, n_step: int = 1, stride: Optional[int] = None,
-                  prior_rows: Optional[int] = None) -> None:
+                  prior_rows: Optional[int] = None, hindsight: bool = False) -> None:
         """orchestrator.py:337-352 as ONE graph launch (sample, critic, delayed actor x N, Polyak); keeps the
         reference's counters.  `beta` (needs ReplayBuffer.enable_priorities): the sample is drawn by priority, the critic update is
         weighted by the importance weights of exponent beta and its TD errors go back into the priorities; `n_step`, `stride`: as for
         ReplayBuffer.sample -- all inside the same launch (include/sactd3.h: sactd3_step_sampled), equal to the call sequence
         sample_prioritized / sample -> update_qnets -> update_priorities -> update_actor x N -> update_targ_nets bit for bit.
         `prior_rows` (needs ReplayBuffer.pin): the sample is ReplayBuffer.sample_mixed's, inside the same launch; it excludes
-        `beta` and n_step > 1."""
+        `beta` and n_step > 1.
+        `hindsight=True` (needs ReplayBuffer.configure_hindsight): the sample is ReplayBuffer.sample_hindsight's, drawn and relabelled
+        inside the same launch; it excludes `beta`, n_step > 1 and `prior_rows`."""
         do_actor = i % (self.engine.cfg.actor_update_delay + 1) == 0
-        if prior_rows is not None:
+        if hindsight:
+            if beta is not None or n_step != 1 or prior_rows is not None:
+                raise ValueError("iteration: hindsight (the relabelling draw) excludes beta, n_step > 1 and prior_rows")
+            self.engine.step_sampled(do_actor, hindsight=True)
+        elif prior_rows is not None:
             if beta is not None or n_step != 1:
                 raise ValueError("iteration: prior_rows (the mixed draw) excludes beta and n_step > 1")
             self.engine.step_sampled(do_actor, prior_rows=int(prior_rows))

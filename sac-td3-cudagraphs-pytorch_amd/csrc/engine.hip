@@ -28,7 +28,7 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 // All device code stands above.  The order of the template instances in the code object is pinned by this list, not by where the
 // host code below names them: a new instance is appended there.
 #include "kernel_instances.inc"
-// the hindsight staging kernel is a translation unit of its own (hindsight.hip): only its argument struct and launcher are known here
+// the hindsight kernels are a translation unit of their own (hindsight.hip): only their argument structs and launchers are known here
 #include "hindsight.h"
 
 static thread_local std::string g_create_error;
@@ -257,10 +257,13 @@ struct sactd3_engine {
   // and the goal's ring slot) and the device counters hs_ctr {rows relabelled, rows refused, rows whose relabelled reward is 0} are made at
   // the first staging call -- an engine that never makes one holds nothing more than before.  hs_calls: native draws made so far, the
   // first counter word of the next one.  Run-time state, not part of a checkpoint.
+  // The graph form (sactd3_step_sampled, SACTD3_DRAW_HINDSIGHT) counts the draws on the device as well: hs_ctr[HS_WORD_MASTER], which its
+  // draw kernel advances.  hs_pub: what the host knows that word to hold (-1: nothing yet); hs_calls is published in front of a graph
+  // launch only when the two differ (a call-form native draw in between), as mix_publish does for P and m.
   bool hs_on = false;
   sactd3_hindsight_config hs_cfg{};
   int *hs_off = nullptr, *hs_gs = nullptr, *hs_ctr = nullptr;
-  int64_t hs_calls = 0;
+  int64_t hs_calls = 0, hs_pub = -1;
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -1663,14 +1666,14 @@ static inline void mix_count(sactd3_engine* e) { ++e->mix_stats[0]; e->mix_stats
 static int hindsight_alloc(sactd3_engine* e) {
   RCCHK(first_use_alloc(e, &e->hs_off, (size_t)e->B));
   RCCHK(first_use_alloc(e, &e->hs_gs, (size_t)e->B));
-  return first_use_alloc(e, &e->hs_ctr, 32);
+  return first_use_alloc(e, &e->hs_ctr, HS_WORDS);
 }
-// the one launch of k_hindsight_stage into batch slot 0: the ring's geometry as ring_rows_args states it, everything else by value
-static int launch_hindsight(EnqCtx& x, const long long* idx, int64_t idx_ld, const int* choice, int64_t choice_ld, unsigned hctr) {
-  sactd3_engine* e = x.e;
+// what both forms of the staging kernel are told: the ring's geometry as ring_rows_args states it, everything else by value.  Returns
+// the grid.
+static unsigned hindsight_args(sactd3_engine* e, HindsightArgs& g, const long long* idx, int64_t idx_ld, const int* choice, int64_t choice_ld,
+                               unsigned hctr) {
   const sactd3_engine::BatchSlot& S = e->bs[0];
   const sactd3_hindsight_config& c = e->hs_cfg;
-  HindsightArgs g{};
   g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.cx = e->cx; g.cn = e->cn; g.o = e->o;
   g.B = e->B; g.len = (int)e->rb_len; g.cursor = (int)e->rb_cursor; g.cap = (int)e->cfg.rb_capacity;
   g.ag_off = c.ag_off; g.dg_off = c.dg_off; g.G = c.goal_dim; g.thr = c.threshold; g.ratio = c.ratio; g.window = c.window; g.stride = c.stride;
@@ -1684,27 +1687,60 @@ static int launch_hindsight(EnqCtx& x, const long long* idx, int64_t idx_ld, con
   const unsigned blocks_g = gather_blocks(chunks);
   const long cpb_g = (chunks + 256L * blocks_g - 1) / (256L * blocks_g), cpb_l = std::max(1L, (long)(HS_ROWS - 2) * e->rec4 / 256);
   g.cpb = (int)std::min(std::min(cpb_g, cpb_l), (long)HS_CPT);
-  const unsigned blocks = (unsigned)((chunks + 256L * g.cpb - 1) / (256L * g.cpb));
+  return (unsigned)((chunks + 256L * g.cpb - 1) / (256L * g.cpb));
+}
+// the one launch of k_hindsight_stage into batch slot 0
+static int launch_hindsight(EnqCtx& x, const long long* idx, int64_t idx_ld, const int* choice, int64_t choice_ld, unsigned hctr) {
+  sactd3_engine* e = x.e;
+  HindsightArgs g{};
+  const unsigned blocks = hindsight_args(e, g, idx, idx_ld, choice, choice_ld, hctr);
   const hipError_t he = hindsight_stage_launch(g, blocks, x.s);
   if (he != hipSuccess) return e->fail(SACTD3_EHIP, "hindsight_stage_launch", he);
   return 0;
 }
+// The graph forms (hindsight_kernels.h): the draw into mix_idx, which ticks the sample counter and the device's draw counter itself,
+// then the staging of the drawn slots.  Ring length, cursor and draw counter are read on the device through the pointers given here;
+// the config travels by value (sactd3_hindsight_configure drops the graphs that hold an earlier one).
+static int hindsight_draw_launches_g(EnqCtx& x) {
+  sactd3_engine* e = x.e;
+  const HindsightDrawArgs d{&e->ctl->seed, &e->ctl->sample_ctr, &e->ctl->rb_len, e->hs_ctr, e->mix_idx, e->B, (int)e->cfg.rb_capacity};
+  hipError_t he = hindsight_draw_g_launch(d, x.s);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "hindsight_draw_g_launch", he);
+  HindsightArgsG g{};
+  const unsigned blocks = hindsight_args(e, g.a, e->mix_idx, 1, nullptr, 0, 0u);
+  g.a.len = g.a.cursor = 0;      // (the device's, read by the kernel)
+  g.ring_words = &e->ctl->rb_len; g.hs_words = e->hs_ctr;
+  he = hindsight_stage_g_launch(g, blocks, x.s);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "hindsight_stage_g_launch", he);
+  return 0;
+}
+// the device's draw counter, for the graph form: one single-thread launch, and only when the host's count is not what the word holds
+static int hindsight_publish(EnqCtx& x) {
+  sactd3_engine* e = x.e;
+  if (e->hs_pub == e->hs_calls) return 0;
+  static_assert(HS_WORD_SNAPSHOT == HS_WORD_MASTER + 1, "the two words are set by one k_set_int2");
+  RCCHK(launch_set_int2(x, e->hs_ctr + HS_WORD_MASTER, (int)e->hs_calls, (int)e->hs_calls));
+  e->hs_pub = e->hs_calls;
+  return 0;
+}
 
 // The replay-aware iteration (sactd3_step_sampled) as one linear sequence: what the calls
-//   sactd3_rb_sample_prioritized[_nstep] | sactd3_rb_sample_nstep | sactd3_rb_sample_mixed -> sactd3_update_qnets ->
+//   sactd3_rb_sample_prioritized[_nstep] | sactd3_rb_sample_nstep | sactd3_rb_sample_mixed | sactd3_rb_sample_hindsight -> sactd3_update_qnets ->
 //   [sactd3_prio_update_from_td] -> [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets
 // launch, launch for launch, with the staging and priority kernels in their graph forms.  (The 1-step uniform iteration is sactd3_step.)
 static int enqueue_step_sampled(EnqCtx& x, bool actor, bool targets) {
   sactd3_engine* e = x.e;
   const bool prio = e->ss_key[0] == SACTD3_DRAW_PRIORITIZED, mixed = e->ss_key[0] == SACTD3_DRAW_MIXED;
+  const bool hind = e->ss_key[0] == SACTD3_DRAW_HINDSIGHT;
   const int steps = e->ss_key[1], stride = e->ss_key[2];
   if (prio) RCCHK(prio_draw_launches(x, 0.f));
   const long long* idx = prio ? e->pt_idx : nullptr;
   const float* w = prio ? e->pt_w : nullptr;
   if (mixed) RCCHK(mix_draw_launches(x));      // (unweighted, no chain; the draw kernel has advanced the sample counter)
+  else if (hind) RCCHK(hindsight_draw_launches_g(x));      // (the same, and the draw kernel has advanced the hindsight draw counter too)
   else if (steps > 1) RCCHK(launch_batch_nstep(x, idx, 1, w, 1, prio ? e->bs[0].w : nullptr, steps, stride));
   else RCCHK(launch_batch_index(x, idx, 1, w, 1));
-  if (!prio && !mixed) RCCHK(launch_tick(x, &e->ctl->sample_ctr));      // the uniform draw was made at the sample counter, which now advances
+  if (!prio && !mixed && !hind) RCCHK(launch_tick(x, &e->ctl->sample_ctr));      // the uniform draw was made at the sample counter, which now advances
   IterPlace it;
   it.weighted = prio;
   RCCHK(enqueue_update_qnets(x, it, false));
@@ -2568,7 +2604,9 @@ int sactd3_rb_sample_mixed(sactd3_engine* e) {
 int sactd3_mix_stats(sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::mix_stats, out); }
 
 // ---- hindsight relabelling at staging (include/sactd3.h)
-// Host state only: no launch, and a precomputed opening pair stays valid across it (nothing it depends on changes).
+// Host state only: no launch, and a precomputed opening pair stays valid across it (nothing it depends on changes).  A CHANGED config
+// drops the four graphs of sactd3_step_sampled when they were captured for SACTD3_DRAW_HINDSIGHT (the stream drains first); the same
+// config again drops nothing.
 int sactd3_hindsight_configure(sactd3_engine* e, const sactd3_hindsight_config* c) {
   if (!e) return SACTD3_EINVAL;
   if (!c) return e->fail(SACTD3_EINVAL, "hindsight_configure: the config is NULL");
@@ -2582,6 +2620,14 @@ int sactd3_hindsight_configure(sactd3_engine* e, const sactd3_hindsight_config* 
   if (c->stride < 1) return e->fail(SACTD3_EINVAL, "hindsight_configure: stride must be at least 1");
   if (!(c->threshold >= 0.f) || !std::isfinite(c->threshold)) return e->fail(SACTD3_EINVAL, "hindsight_configure: threshold must be finite and >= 0");
   if (!(c->ratio >= 0.f && c->ratio <= 1.f)) return e->fail(SACTD3_EINVAL, "hindsight_configure: ratio must be in [0, 1]");
+  // the graph forms hold the config by value: graphs captured for the hindsight draw under another config are dropped
+  const sactd3_hindsight_config& h = e->hs_cfg;
+  const bool same = e->hs_on && h.ag_off == c->ag_off && h.dg_off == c->dg_off && h.goal_dim == c->goal_dim && h.window == c->window &&
+                    h.stride == c->stride && memcmp(&h.threshold, &c->threshold, sizeof(float)) == 0 && memcmp(&h.ratio, &c->ratio, sizeof(float)) == 0;
+  if (!same && e->ss_key[0] == SACTD3_DRAW_HINDSIGHT) {
+    USE_DEVICE(e);
+    RCCHK(drop_graphs(e, G_SAMPLED, 4));
+  }
   e->hs_cfg = *c;
   e->hs_on = true;
   return 0;
@@ -2915,24 +2961,29 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   if (!sm) return e->fail(SACTD3_EINVAL, "step_sampled: the sampling struct is NULL");
-  if (sm->draw != SACTD3_DRAW_UNIFORM && sm->draw != SACTD3_DRAW_PRIORITIZED && sm->draw != SACTD3_DRAW_MIXED) return e->fail(SACTD3_EINVAL, "step_sampled: unknown draw");
+  if (sm->draw != SACTD3_DRAW_UNIFORM && sm->draw != SACTD3_DRAW_PRIORITIZED && sm->draw != SACTD3_DRAW_MIXED && sm->draw != SACTD3_DRAW_HINDSIGHT)
+    return e->fail(SACTD3_EINVAL, "step_sampled: unknown draw");
   if (sm->n_step < 1 || sm->n_step > NS_MAX) return e->fail(SACTD3_EINVAL, "step_sampled: n_step must be in [1, 16]");
   if (sm->n_step > 1 && sm->stride < 1) return e->fail(SACTD3_EINVAL, "step_sampled: stride must be at least 1");
-  const bool prio = sm->draw == SACTD3_DRAW_PRIORITIZED, mixed = sm->draw == SACTD3_DRAW_MIXED;
+  const bool prio = sm->draw == SACTD3_DRAW_PRIORITIZED, mixed = sm->draw == SACTD3_DRAW_MIXED, hind = sm->draw == SACTD3_DRAW_HINDSIGHT;
   if (mixed && sm->n_step != 1) return e->fail(SACTD3_EINVAL, "step_sampled: the mixed draw has no n-step form: n_step must be 1");
+  if (hind && sm->n_step != 1) return e->fail(SACTD3_EINVAL, "step_sampled: the hindsight draw has no n-step form: n_step must be 1");
   if (!(sm->beta >= 0.f) || !std::isfinite(sm->beta)) return e->fail(SACTD3_EINVAL, "step_sampled: beta must be finite and >= 0");
   if (prio && !e->pt_on) return e->fail(SACTD3_ESTATE, "step_sampled: priorities are not enabled (sactd3_prio_enable)");
   if (sm->n_step > 1 && e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "step_sampled: rows are pinned (sactd3_rb_pin): the n-step age formula assumes one wrap point, at slot 0");
+  if (hind && !e->hs_on) return e->fail(SACTD3_ESTATE, "step_sampled: hindsight is not configured (sactd3_hindsight_configure)");
+  if (hind && e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "step_sampled: rows are pinned (sactd3_rb_pin): the chain's age formula assumes one wrap point, at slot 0");
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step_sampled: buffer is empty");
   if (mixed)
     if (const char* why = mix_refusal(e)) { e->err = std::string("step_sampled: ") + why; return SACTD3_ESTATE; }
-  if (!prio && !mixed && sm->n_step == 1) { RCCHK(sactd3_step(e, do_actor)); ++e->ss_stats[0]; return 0; }
+  if (!prio && !mixed && !hind && sm->n_step == 1) { RCCHK(sactd3_step(e, do_actor)); ++e->ss_stats[0]; return 0; }
   CHAIN_BREAK(e);
   const bool chain = sm->n_step > 1;
   const int stride = chain ? sm->stride : 1;
-  if (prio || !chain) RCCHK(slot_weights_alloc(e));
+  if (prio || (!chain && !hind)) RCCHK(slot_weights_alloc(e));      // (the hindsight staging writes no weights: its slot carries none)
   if (chain) RCCHK(nstep_alloc(e));
-  if (mixed) RCCHK(mix_alloc(e));
+  if (mixed || hind) RCCHK(mix_alloc(e));
+  if (hind) RCCHK(hindsight_alloc(e));
   const int key[3] = {sm->draw, sm->n_step, stride};
   EnqCtx x{e, e->stream};      // (the eager launches in front of the graph)
   if (memcmp(key, e->ss_key, sizeof(key)) != 0) {
@@ -2949,6 +3000,7 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
     }
   }
   if (mixed) RCCHK(mix_publish(x));      // (P and m as the graph's draw reads them: a launch only when one of them changed)
+  if (hind) RCCHK(hindsight_publish(x));      // (the draw counter as the graph's draw reads it: a launch only behind a call-form native draw)
   RCCHK(issue_iteration(e, do_actor, G_SAMPLED));
   ++e->ss_stats[0];
   // the rest of the host state, transition by transition as the call sequence makes them
@@ -2956,6 +3008,7 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
   if (chain) { ++e->ns_host[0]; e->ns_host[1] += e->B; }
   if (prio) ++e->pt_host[0];
   if (mixed) mix_count(e);
+  if (hind) { e->slot.hindsight = true; ++e->hs_calls; ++e->hs_pub; }      // (the draw kernel advanced the device's word as well)
   slot_trained(e, 0, false);
   if (prio) ++e->pt_host[1];
   return 0;

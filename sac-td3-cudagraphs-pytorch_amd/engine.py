@@ -340,13 +340,19 @@ class Engine:
         self._ck(self.lib.sactd3_step(self._h, int(bool(do_actor))))
 
     def step_sampled(self, do_actor: bool, *, beta: Optional[float] = None, n_step: int = 1, stride: int = 1,
-                     prior_rows: Optional[int] = None) -> None:
+                     prior_rows: Optional[int] = None, hindsight: bool = False) -> None:
         """sactd3_step_sampled: step() with a prioritised draw (`beta`: the exponent of the importance weights; None: the uniform
         draw) and / or `n_step` returns chained at `stride` rows per env step -- sample, weighted critic update, priority write-back,
         actor updates and target update as one graph launch, replayed while the ring grows and beta anneals.
         `prior_rows`: the mixed draw instead -- that many batch rows from the pinned rows (rb_pin), the others from the live rows;
-        rb_set_mix is issued only when the value changed.  It has no prioritised and no n-step form."""
-        if prior_rows is not None:
+        rb_set_mix is issued only when the value changed.  It has no prioritised and no n-step form.
+        `hindsight=True`: rb_sample_hindsight's draw and relabelling instead (needs hindsight_configure), inside the same launch.  It
+        excludes `beta`, n_step > 1 and `prior_rows`."""
+        if hindsight:
+            if beta is not None or int(n_step) != 1 or prior_rows is not None:
+                raise ValueError("hindsight (the relabelling draw) excludes beta, n_step > 1 and prior_rows")
+            sm = _lib.CSampling(_lib.DRAW_HINDSIGHT, 1, 1, 0.0)
+        elif prior_rows is not None:
             if beta is not None or int(n_step) != 1:
                 raise ValueError("prior_rows (the mixed draw) excludes beta and n_step > 1")
             if int(prior_rows) != getattr(self, "_mix_rows", None):

@@ -342,8 +342,8 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
     --n_step N > 1 and --prior_fraction are issued call by call (fused=False), or with --one_launch as one graph launch per iteration.
-    `hindsight` (--hindsight: the dict of hindsight_keywords for the job's env): call by call as well; the key is in the result only
-    when it was given."""
+    `hindsight` (--hindsight: the dict of hindsight_keywords for the job's env): call by call as well, or with --one_launch as one
+    graph launch; the key is in the result only when it was given."""
     update = dict(fused=not prioritized and n_step == 1 and prior_fraction is None and not hindsight,
                   prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch,
                   prior_fraction=None if prior_fraction is None else float(prior_fraction), updates_per_step=int(updates_per_step))
@@ -366,7 +366,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     segment of any online run; `policy_stats`: rows put to the policy at every evaluation (loop.PolicyStats; SAC only);
     `native_rollout`: the env loop through loop.NativeRollout (needs `device_env` and a -native id: env_plan refuses otherwise);
     `hindsight`: the engine relabels goals while it stages each batch (loop.train hindsight=...; needs an env id with a goal layout:
-    hindsight_plan refuses otherwise)."""
+    hindsight_plan refuses otherwise); with `one_launch` the draw and the relabelling are part of the iteration's one graph."""
     import json
     import time
     from pathlib import Path
@@ -449,6 +449,8 @@ def _worker_main(args, plan, flags) -> int:
                    "rollout": env_plan(env_id, args.device_env, factory is not None, native_rollout=args.native_rollout)["rollout"]}
             if args.hindsight:                   # (the key is there only when the flag was given)
                 out["hindsight"] = hindsight_keywords(env_id, job_config(args.algo, env_id, seed).num_envs)
+                if args.one_launch:              # (... and the one-launch form of its iteration beside it)
+                    out["one_launch"] = True
         else:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
@@ -490,11 +492,12 @@ def main(argv=None) -> int:
     ap.add_argument("--hindsight", action="store_true",
                     help="with an env bundle whose tasks have a goal (native_goal): the engine relabels goals while it stages each batch -- "
                          "hindsight experience replay, the future strategy, window = the task's horizon (loop.train hindsight=...; the "
-                         "iteration is issued call by call)")
+                         "iteration is issued call by call, or with --one_launch as one graph launch)")
     ap.add_argument("--prioritized", action="store_true",
                     help="proportional prioritised replay kept by the engine (loop.train prioritized=...; the iteration is issued call by call)")
     ap.add_argument("--one_launch", action="store_true",
-                    help="with --prioritized and / or --n_step N > 1: issue the iteration as one graph launch (loop.train one_launch=True)")
+                    help="with --prioritized, --n_step N > 1, --prior_fraction and / or --hindsight: issue the iteration as one graph launch "
+                         "(loop.train one_launch=True)")
     ap.add_argument("--n_step", type=int, default=1,
                     help="train the critics on N-step returns chained by the engine (loop.train n_step=...; above 1 the iteration is issued call by call)")
     ap.add_argument("--offline_dataset", default=None, metavar="FILE.npz",

@@ -334,7 +334,7 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
     that never opens a GPU can ask whether a run would be refused.  `cfg` needs `batch_size` (with `prior_fraction`, and when an update is
     issued call by call), `num_envs` (with `n_step` > 1) and `actor_update_delay` (call by call).  Which keywords need or exclude each
     other is the table `refusals` below, one row per rule with its reason, the first row that applies raising ValueError: a new mode
-    adds its rows there.  `prior_fraction` counts as a reason for `one_launch`.
+    adds its rows there.  `prior_fraction` and `hindsight` count as reasons for `one_launch`.
     -> a namespace of
       updates_per_step  as an int
       priorities        None, or dict(alpha=, eps=) for `agent.rb.enable_priorities` -- train() enables them once, before its loop
@@ -342,7 +342,8 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
                         cfg.num_envs) -- train() configures the buffer once, in the same place
       update            `update(agent, i, tlog)`: iteration i, in ONE of three forms chosen here --
                           fused        agent.iteration(i)
-                          one launch   agent.iteration(i, prior_rows=) or agent.iteration(i, beta=, n_step=, stride=), the values fixed here
+                          one launch   agent.iteration(i, prior_rows=), agent.iteration(i, hindsight=True) or
+                                       agent.iteration(i, beta=, n_step=, stride=), the values fixed here
                           call by call one draw (uniform `rb.sample`, `sampler` + `rb.sample_at`, `rb.sample_prioritized`, `rb.sample_mixed`,
                                        `rb.sample_hindsight`) ->
                                        update_qnets -> its write-back (`sampler.update` / `rb.update_priorities`) -> counters -> every
@@ -362,7 +363,7 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
         (prior and n_step > 1, "prior_fraction=... excludes n_step > 1: a pinned ring has no n-step chains yet"),
         (one_launch and fused, "one_launch=True needs fused=False: fused=True is the uniform 1-step iteration, already one launch"),
         (one_launch and outside, "one_launch=True excludes sampler=...: a sampler outside the engine cannot be part of its graph"),
-        (one_launch and not (prio or n_step > 1 or prior),
+        (one_launch and not (prio or n_step > 1 or prior or hind),
          "one_launch=True needs prioritized=... and / or n_step > 1: the uniform 1-step iteration is fused=True"),
         (not 1 <= n_step <= 16, f"n_step must be in [1, 16], got {n_step}"),
         (n_step > 1 and fused, "n_step=... needs fused=False: the fused iteration samples single steps uniformly inside its graph"),
@@ -375,7 +376,6 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
         (hind and prio, "hindsight=... and prioritized=... exclude each other: a relabelled row's TD error is not its record's priority"),
         (hind and n_step > 1, "hindsight=... excludes n_step > 1: a relabelled reward is a single step's, the chain's return is not"),
         (hind and prior, "hindsight=... and prior_fraction=... exclude each other: a pinned ring has no episode chains yet"),
-        (hind and one_launch, "hindsight=... excludes one_launch=True: the hindsight staging has no graph form"),
         (bool(hs_unknown), f"hindsight: unknown keys {hs_unknown}"),
         (bool(hs_missing), f"hindsight: missing keys {hs_missing}"),
     )
@@ -391,6 +391,8 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
         update = lambda agent, i, tlog: agent.iteration(i)
     elif one_launch and prior:                                           # (a keyword the older signature lacks: only when used)
         update = lambda agent, i, tlog: agent.iteration(i, prior_rows=prior_rows)
+    elif one_launch and hind:                                            # (the same: a keyword only when used)
+        update = lambda agent, i, tlog: agent.iteration(i, hindsight=True)
     elif one_launch:
         stride = chain.get("stride")
         update = lambda agent, i, tlog: agent.iteration(i, beta=beta, n_step=n_step, stride=stride)
@@ -467,15 +469,16 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     mirror on the host: the engine sees its own appends.
     `n_step` (1 to 16): the critic trains on n-step returns chained by the engine out of consecutive ring rows of one env
     (`stride=cfg.num_envs`), cut at episode ends -- with the uniform, the `sampler` and the `prioritized` draw alike.
-    `one_launch=True`: the `prioritized` / `n_step` / `prior_fraction` iteration is issued as one graph launch --
-    `agent.iteration(i, beta=, n_step=, stride=cfg.num_envs)` or `agent.iteration(i, prior_rows=)` -- in place of the call sequence,
+    `one_launch=True`: the `prioritized` / `n_step` / `prior_fraction` / `hindsight` iteration is issued as one graph launch --
+    `agent.iteration(i, beta=, n_step=, stride=cfg.num_envs)`, `agent.iteration(i, prior_rows=)` or
+    `agent.iteration(i, hindsight=True)` -- in place of the call sequence,
     with the same results bit for bit and the same counters.
     `prior_fraction` (in [0, 1]): learning online from prior data -- every batch takes round(prior_fraction * batch_size) rows from
     the rows `agent.rb.pin()` protects (`load_dataset(..., pin=True)`) and the others from the rows the run appends (`rb.sample_mixed`).
     `hindsight` (dict(achieved=, desired=, dim=, threshold= [, ratio=, window=, stride=]): the keywords of `rb.configure_hindsight`,
     `stride` defaulting to cfg.num_envs): a goal-conditioned task with a sparse reward -- every batch is drawn as `rb.sample` draws it
     and a `ratio` share of its rows is relabelled by the engine while it is staged, with a goal the row's own episode reached later
-    (`rb.sample_hindsight`; call by call, fused=False).  `envs.NativeVecEnv.goal_layout` gives the first four keys for a native task.
+    (`rb.sample_hindsight`; fused=False: call by call, or with one_launch=True as one graph launch).  `envs.NativeVecEnv.goal_layout` gives the first four keys for a native task.
     `updates_per_step` (>= 1, every mode): the update-to-data ratio -- after each segment the update runs that many times, `i` and the
     update counters advancing per update; 1 is the reference's loop.
     `policy_stats=N` (default 0: off, and no call is made; SAC only): at every evaluation point N ring rows are put to the policy

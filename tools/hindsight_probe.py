@@ -11,7 +11,19 @@ tests/test_gpu_hindsight.py takes its learning test's budget and the oracle's fi
                                                  #            window 1, 16 and 50 against k_batch_from_index and the n-step kernel (3 steps)
                                                  #   "loop":  loop.train(device_env=True, fused=False) iterations/s with and without hindsight
                                                  #   "gpu_learning": the learning test's run with and without hindsight (recorded, not asserted)
-Each mode rewrites its own entries of the record and leaves the others."""
+
+    python tools/hindsight_probe.py --one-launch [--parent-library PATH]
+                                                 # GPU -> profiles/hindsight_one_launch.json (a file of its own: hindsight.json stays):
+                                                 #   "loop":  the hindsight loop of the shape above, iterations/s, as one graph launch per
+                                                 #            iteration (one_launch=True), call by call with this build and, with PATH (a
+                                                 #            libsactd3_hip.so built from the parent commit), call by call with that build --
+                                                 #            alternating child processes, 5 runs each, median and range, and the ratios
+    python tools/hindsight_probe.py --kernel-stats STATS.csv
+                                                 # -> "kernel_us" of the same file: the per-launch device time of the two kernels the graph
+                                                 #    adds, read from the kernel statistics of a profiled run of the one-launch loop,
+                                                 #      rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- \
+                                                 #          python tools/hindsight_probe.py --child loop 1 1
+Each mode rewrites its own entries of its record and leaves the others."""
 import argparse
 import json
 import os
@@ -25,6 +37,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "profiles", "hindsight.json")
+ONE_LAUNCH_OUT = os.path.join(ROOT, "profiles", "hindsight_one_launch.json")
 SEEDS = (0, 1, 2)
 EPISODES = 16
 KIND = "pointgoal"
@@ -198,7 +211,7 @@ def child_stage(which):
     return (time.perf_counter() - t0) / STAGE_CALLS
 
 
-def child_loop(hindsight):
+def child_loop(hindsight, one_launch=False):
     """iterations per second of loop.train(device_env=True, fused=False) on the goal env, behind a warm-up run"""
     import torch
     from sac_td3_cudagraphs_pytorch_amd import envs, loop
@@ -206,7 +219,7 @@ def child_loop(hindsight):
     cfg, warm = learning_cfg(0, budget), learning_cfg(0, dict(budget, updates=200))
     agent = gpu_agent(cfg, 0)
     env = envs.NativeVecEnv(KIND, 4, seed=0, device=torch.device("cuda", 0))
-    kw = dict(hindsight=hindsight_kw(env, 4)) if hindsight else {}
+    kw = dict(hindsight=hindsight_kw(env, 4), one_launch=bool(one_launch)) if hindsight else {}
     loop.train(warm, env, agent, device_env=True, fused=False, **kw)
     agent.engine.sync()
     done = agent.qnet_updates_so_far
@@ -231,8 +244,26 @@ def child_learn(seed, hindsight):
     return {"seed": seed, "hindsight": bool(hindsight), "untrained": float(before), "trained": float(after), "updates": agent.qnet_updates_so_far}
 
 
-def run_child(*argv):
+def kernel_stats_mode(path):
+    """the rows of a rocprofv3 kernel-statistics file that name a hindsight kernel or the draw it replaces -> the "kernel_us" entry"""
+    import csv
+    with open(path, newline="") as f:
+        rows = [r for r in csv.DictReader(f) if "hindsight" in r["Name"] or "k_mix_draw" in r["Name"]]
+    rec = {r["Name"].split("(")[0].replace("void ", ""): {"calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
+                                                          "min_us": round(float(r["MinNs"]) / 1e3, 2), "max_us": round(float(r["MaxNs"]) / 1e3, 2)}
+           for r in rows}
+    rec["what"] = ("device time per launch from the kernel statistics of a profiled one-launch hindsight loop (PointGoal-native, 4 envs, B = 256, "
+                   "window 50, the ring growing from 1000 rows): every launch of the run, warm-up included")
+    global OUT
+    OUT = ONE_LAUNCH_OUT
+    merge({"kernel_us": rec})
+    print(json.dumps({"kernel_us": rec}), flush=True)
+
+
+def run_child(*argv, library=None):
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    if library:                                                           # (another build of the library: _lib.library_path)
+        env["SACTD3_LIBRARY"] = os.path.abspath(library)
     out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + [str(a) for a in argv], capture_output=True, text=True, env=env,
                          cwd=ROOT, timeout=600)
     if out.returncode != 0:
@@ -259,19 +290,51 @@ def gpu_mode():
                       "gpu_learning": learn}), flush=True)
 
 
+def one_launch_mode(parent_library):
+    kinds = {"one_launch": ("loop", 1, 1), "call_by_call": ("loop", 1, 0)}
+    loops = {k: [] for k in list(kinds) + (["call_by_call_parent"] if parent_library else [])}
+    for _ in range(RUNS):                                                 # alternating: every kind once per round
+        for k, argv in kinds.items():
+            loops[k].append(run_child(*argv))
+        if parent_library:
+            loops["call_by_call_parent"].append(run_child("loop", 1, 0, library=parent_library))
+    rec = {k: spread(v) for k, v in loops.items()}
+    base = rec.get("call_by_call_parent", rec["call_by_call"])
+    rec["what"] = ("iterations/s of loop.train(device_env=True, fused=False, hindsight=...) on PointGoal-native, 4 envs, B = 256, 3000 updates behind "
+                   "a warm-up: one_launch=True, call by call with this build, call by call with the parent commit's build")
+    rec["ratio_to_parent_median"] = rec["one_launch"]["median"] / base["median"]
+    rec["parent_spread"] = (base["max"] - base["min"]) / base["median"]
+    rec["one_launch_median_clears_parent_best"] = bool(rec["one_launch"]["median"] > base["max"])
+    out = {"loop": rec}
+    global OUT
+    OUT = ONE_LAUNCH_OUT
+    merge(out)
+    print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--oracle-child", nargs=2, type=int, metavar=("SEED", "HINDSIGHT"))
     ap.add_argument("--child", nargs="+", metavar="WHAT")
+    ap.add_argument("--one-launch", action="store_true")
+    ap.add_argument("--parent-library", default=None, metavar="PATH")
+    ap.add_argument("--kernel-stats", default=None, metavar="STATS.csv")
     args = ap.parse_args()
     if args.oracle_child:
         print(json.dumps(oracle_run(args.oracle_child[0], bool(args.oracle_child[1]))), flush=True)
     elif args.child:
         what, rest = args.child[0], args.child[1:]
-        got = child_stage(rest[0]) if what == "stage" else child_loop(bool(int(rest[0]))) if what == "loop" else child_learn(int(rest[0]), bool(int(rest[1])))
+        if what == "loop":
+            got = child_loop(bool(int(rest[0])), bool(int(rest[1])) if len(rest) > 1 else False)
+        else:
+            got = child_stage(rest[0]) if what == "stage" else child_learn(int(rest[0]), bool(int(rest[1])))
         print(json.dumps(got), flush=True)
     elif args.oracle:
         oracle_mode()
+    elif args.one_launch:
+        one_launch_mode(args.parent_library)
+    elif args.kernel_stats:
+        kernel_stats_mode(args.kernel_stats)
     else:
         gpu_mode()
