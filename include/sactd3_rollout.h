@@ -93,4 +93,8 @@ int sactd3_rollout_stats(const sactd3_rollout* r, int64_t out[4]);
 #ifdef __cplusplus
 }
 #endif
+
+/* advance, choose and the engine's update as ONE graph launch per env step: declared in a header of its own, which needs the types above */
+#include "sactd3_rollout_cycle.h"
+
 #endif /* SACTD3_ROLLOUT_H */

@@ -67,6 +67,9 @@ ROLLOUT_SYMBOLS = [
     "sactd3_rollout_choose", "sactd3_rollout_advance", "sactd3_rollout_stats",
 ]
 ROLLOUT_RANDOM, ROLLOUT_EXPLORE, ROLLOUT_EXPLOIT, ROLLOUT_REPEAT = range(4)   # sactd3_rollout_choose `mode` (SACTD3_ROLLOUT_*)
+# every symbol include/sactd3_rollout_cycle.h declares -- the header sactd3_rollout.h ends with (tests/test_rollout_cycle_host.py checks it
+# against this list)
+ROLLOUT_CYCLE_SYMBOLS = ["sactd3_rollout_cycle", "sactd3_rollout_cycle_stats", "sactd3_rollout_cycle_clamped"]
 
 
 class EngineError(RuntimeError):
@@ -298,6 +301,13 @@ def load_library():
     }
     assert sorted(rollout_sig) == sorted(ROLLOUT_SYMBOLS)
     sig.update(rollout_sig)
+    cycle_sig = {
+        "sactd3_rollout_cycle": (C.c_int, [vp, C.c_int, C.c_int]),
+        "sactd3_rollout_cycle_stats": (C.c_int, [vp, i64p]),
+        "sactd3_rollout_cycle_clamped": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(cycle_sig) == sorted(ROLLOUT_CYCLE_SYMBOLS)
+    sig.update(cycle_sig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the .so does not export what the header declares
         fn.restype, fn.argtypes = res, args

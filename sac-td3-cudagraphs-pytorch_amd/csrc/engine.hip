@@ -30,6 +30,8 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 #include "kernel_instances.inc"
 // the hindsight kernels are a translation unit of their own (hindsight.hip): only their argument structs and launchers are known here
 #include "hindsight.h"
+// ... and so is the graph form of the ring append (rollout_cycle.hip); the same header is how the rollout handle (env.hip) asks for a cycle
+#include "rollout_cycle.h"
 
 static thread_local std::string g_create_error;
 
@@ -264,6 +266,15 @@ struct sactd3_engine {
   sactd3_hindsight_config hs_cfg{};
   int *hs_off = nullptr, *hs_gs = nullptr, *hs_ctr = nullptr;
   int64_t hs_calls = 0, hs_pub = -1;
+  // One env step of a native rollout as one graph launch (sactd3_rollout_cycle; engine_rollout_cycle at the end of this file): env step,
+  // ring append in its graph form, acting pair, uniform iteration.  One executable graph per (mode, IterSchedule::k), 4 exploit + k, for
+  // the rollout handle cyc_owner, whose three buffers and env-step launcher its nodes hold by value: a cycle of another handle, and
+  // that handle's destruction, drop all eight.  cyc_ctr: the device word the append counts a clamped cursor / length in; made at
+  // the first cycle -- an engine that never cycles holds nothing more than before.  Not in the table of learner graphs: they need a
+  // rollout to be built from (sactd3_instantiate_graphs has none), and the existing ids keep their numbers.
+  const void* cyc_owner = nullptr;
+  hipGraphExec_t cyc_graphs[8] = {}; int cyc_nodes[8] = {};
+  int* cyc_ctr = nullptr;
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -1786,6 +1797,7 @@ void sactd3_destroy(sactd3_engine* e) {
   (void)drop_graphs(e, 0, G_COUNT);
   for (auto& g : e->predict_graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_dev_graphs) if (g) hipGraphExecDestroy(g);
+  for (auto& g : e->cyc_graphs) if (g) hipGraphExecDestroy(g);
   for (auto ev : e->events) hipEventDestroy(ev);
   for (void* p : e->dev_allocs) hipFree(p);
   for (void* p : e->host_allocs) hipHostFree(p);
@@ -4048,6 +4060,101 @@ int sactd3_time_gather_sweep(sactd3_engine* e, int batch, int iters, float* usec
 
 }  // extern "C"
 #pragma GCC visibility pop
+
+// ------------------------------------------------------------------------------------------------ the rollout cycle (rollout_cycle.h)
+// Not part of the C ABI of this file: include/sactd3_rollout_cycle.h is the rollout handle's (env.hip), which calls in here.
+// THE sequence of a cycle, for the graph and for use_graphs == 0 alike: what sactd3_rollout_advance, sactd3_rollout_choose and
+// sactd3_step launch, in their order, on one stream -- with the append in the form that reads its cursor on the device.
+static_assert(offsetof(DevCtl, rb_len) % 8 == 0 && offsetof(DevCtl, rb_cursor) == offsetof(DevCtl, rb_len) + 4,
+              "k_rb_ingest_g reads {rb_len, rb_cursor} as one 8-byte word");
+static int launch_ingest_g(EnqCtx& x, const float* records, int n) {
+  sactd3_engine* e = x.e;
+  IngestArgsG g{};
+  g.src = (const float4*)records; g.ring = (float4*)e->ring; g.rec4 = e->rec4; g.n = n; g.cap = e->cfg.rb_capacity;
+  g.ring_words = &e->ctl->rb_len; g.clamped = e->cyc_ctr;
+  const unsigned blocks = std::min(1024u, ingest_g_blocks(n, e->rec4));      // (k_rb_ingest's bound for a device slab)
+  g.publish = blocks == 1 ? 1 : 0;
+  hipError_t he = rb_ingest_g_launch(g, blocks, x.s);
+  if (he == hipSuccess && !g.publish) he = rb_publish_g_launch(g, x.s);
+  return he == hipSuccess ? 0 : e->fail(SACTD3_EHIP, "rollout cycle: k_rb_ingest_g", he);
+}
+static int enqueue_cycle(EnqCtx& x, const CycleBinding& b, int explore, const IterSchedule& s) {
+  sactd3_engine* e = x.e;
+  if (const int he = b.env_step(b.ctx, x.s)) return e->fail(SACTD3_EHIP, "rollout cycle: k_env_step_rec", (hipError_t)he);
+  RCCHK(launch_ingest_g(x, b.records, b.n));
+  RCCHK(launch_obs_pack(x, b.obs, b.obs_ld, e->p_x, b.n));
+  RCCHK(enqueue_predict(x, b.n, explore, true));
+  RCCHK(launch_act_unpack(x, b.actions, b.actions_ld, b.n));
+  return enqueue_step(x, single_iteration(s.act, s.polyak));
+}
+static int drop_cycle_graphs(sactd3_engine* e) {
+  hipGraphExec_t* g = e->cyc_graphs;
+  if (std::count(g, g + 8, nullptr) < 8) HIPCHK(hipStreamSynchronize(e->stream));      // (not under its own replay)
+  for (int i = 0; i < 8; ++i) {
+    if (g[i]) hipGraphExecDestroy(g[i]);
+    g[i] = nullptr; e->cyc_nodes[i] = 0;
+  }
+  return 0;
+}
+
+int engine_rollout_cycle(sactd3_engine* e, const CycleBinding& b, int explore, int do_actor) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first (the mode's came in front of the call): a refused call has changed nothing, on either side
+  if (b.n < 1 || b.n > e->maxn) return e->fail(SACTD3_EINVAL, "rollout_cycle: 1 <= num_envs <= max_envs");
+  if (b.n > e->cfg.rb_capacity) return e->fail(SACTD3_EINVAL, "rollout_cycle: num_envs is above rb_capacity (one append launch holds the slab)");
+  if ((int64_t)b.n * std::max(std::max(e->ldo, e->a4) / 4, e->rec4) >= (1ll << 31)) return e->fail(SACTD3_EINVAL, "rollout_cycle: too many rows for one launch");
+  if (e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "rollout_cycle: rows are pinned (sactd3_rb_pin): the append's graph form goes round the whole ring");
+  if (e->pt_on) return e->fail(SACTD3_ESTATE, "rollout_cycle: priorities are enabled (sactd3_prio_enable): the append would owe their launches");
+  if (e->act_inflight) return e->fail(SACTD3_ESTATE, "rollout_cycle: an acting call is in flight (sactd3_predict_end first)");
+  USE_DEVICE(e);
+  if (e->cyc_owner != b.owner) {      // the nodes hold the other binding's buffers
+    RCCHK(drop_cycle_graphs(e));
+    e->cyc_owner = b.owner;
+  }
+  RCCHK(first_use_alloc(e, &e->cyc_ctr, 4));      // (in front of the capture: first_use_alloc)
+  explore = explore ? 1 : 0;
+  const IterSchedule s = iteration_schedule(e, do_actor, e->qnet_updates + 1);
+  const int id = (explore ? 0 : 4) + s.k;
+  auto sequence = [&](EnqCtx& x) { return enqueue_cycle(x, b, explore, s); };
+  const bool had = e->cyc_graphs[id] != nullptr;
+  RCCHK(run_graph_slot(e, &e->cyc_graphs[id], &e->cyc_nodes[id], sequence, false));      // capture at the first use; nothing is launched yet
+  if (!had && e->cyc_graphs[id]) ++b.stats[1];
+  // The rollout's stream around the cycle, once (the pair of SACTD3_SRC_ORDERED): the cycle behind what that stream holds -- a reset, a
+  // write of the buffers -- and whatever that stream is given next -- env calls, reads of the buffers -- behind the cycle.
+  RCCHK(src_order_begin(e, b.stream, SACTD3_SRC_ORDERED));
+  // the host state, transition by transition as the three calls make them
+  CHAIN_BREAK(e);                                     // sactd3_rb_extend_records_device
+  (void)ring_append(e, b.n);                          // ... rb_len, the cursor, rb_wrapped
+  e->actor_dirty = true;                              // sactd3_predict_device: its kernels use the acting scratch, draw buffer and counter
+  ++e->pdev_stats[0]; e->pdev_stats[1] += b.n; ++e->pdev_stats[2];
+  if (!predict_one_block(e, b.n)) ++e->pdev_stats[3];
+  if (s.act) RCCHK(actor_write_begin(e));             // sactd3_step (issue_iteration)
+  RCCHK(run_graph_slot(e, &e->cyc_graphs[id], &e->cyc_nodes[id], sequence, true));      // THE launch (use_graphs == 0: the sequence itself)
+  ++e->qnet_updates;
+  e->grads_stale[0] = false;
+  if (s.act) e->grads_stale[1] = false;
+  slot_trained(e, 0, true);
+  RCCHK(src_order_end(e, b.stream, SACTD3_SRC_ORDERED));
+  ++b.stats[0];
+  b.stats[2] = e->cyc_nodes[id];
+  if (!e->cfg.use_graphs) ++b.stats[3];
+  return 0;
+}
+
+void engine_rollout_cycle_release(sactd3_engine* e, const void* owner) {
+  if (!e || e->cyc_owner != owner) return;
+  if (hipSetDevice(e->cfg.device_id) == hipSuccess) (void)drop_cycle_graphs(e);
+  e->cyc_owner = nullptr;
+}
+
+int engine_rollout_cycle_clamped(sactd3_engine* e, int64_t* out) {
+  if (!e || !out) return SACTD3_EINVAL;
+  const int64_t none[4] = {0, 0, 0, 0};
+  int64_t got[4];
+  RCCHK(stats_with_words(e, none, e->cyc_ctr, 1, 0, got));      // (0 where no cycle was ever issued)
+  *out = got[0];
+  return 0;
+}
 
 #ifdef SACTD3_STAMPS
 // diagnostic builds only (make stamps; tools/blocks_probe.py): the per-block begin / end stamps of the last stamped launch

@@ -1,7 +1,7 @@
 // Host side of include/sactd3_env.h: the handle, its one device allocation, and one launch per call (csrc/env_kernels.h).
 // A translation unit of its own inside libsactd3_hip.so: it shares philox.h with engine.hip and nothing else.
 // Behind it, the host side of include/sactd3_rollout.h: the record-emitting env step and the rollout handle, which reaches the
-// engine through its public ABI (include/sactd3.h) only.
+// engine through its public ABI (include/sactd3.h) only -- and, for sactd3_rollout_cycle alone, through the one entry of rollout_cycle.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,6 +14,7 @@
 #include "../../include/sactd3_env.h"
 #include "../../include/sactd3_rollout.h"
 #include "env_kernels.h"
+#include "rollout_cycle.h"
 
 #define ENV_API extern "C" __attribute__((visibility("default")))
 
@@ -376,10 +377,10 @@ static const char* layout_refusal(const sactd3_record_layout* L, int o, int a) {
   return nullptr;
 }
 
-// the one launch of k_env_step_rec: every argument has been checked
-static int launch_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
-                           int64_t obs_ld, hipStream_t st) {
-  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+// the one launch of k_env_step_rec: every argument has been checked.  issue_step_rec: the launch alone, on the current device -- what a
+// stream capture may hold (the cycle's graph, below); launch_step_rec: on the env's device, with the error text
+static hipError_t issue_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
+                                 int64_t obs_ld, hipStream_t st) {
   const EnvRec k{L->record_len, L->next_off, L->next_width};
   if (e->cfg.kind == SACTD3_ENV_PENDULUM)
     hipLaunchKernelGGL(k_env_step_rec<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
@@ -390,7 +391,12 @@ static int launch_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, 
   else
     hipLaunchKernelGGL(k_env_step_rec<ENV_POINTGOAL>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
                        (long long)obs_ld, e->info.horizon, e->cfg.seed);
-  ENV_HIP(e, hipGetLastError());
+  return hipGetLastError();
+}
+static int launch_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
+                           int64_t obs_ld, hipStream_t st) {
+  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+  ENV_HIP(e, issue_step_rec(e, actions, act_ld, L, records, obs, obs_ld, st));
   return SACTD3_OK;
 }
 
@@ -425,6 +431,8 @@ struct sactd3_rollout {
   hipStream_t stream = nullptr;
   int n = 0;
   int64_t stats[4] = {0, 0, 0, 0};      // random choices, policy choices, steps, rows appended
+  int64_t cycle_stats[4] = {0, 0, 0, 0};      // cycles issued, graphs captured, nodes of the last graph launched, cycles issued eagerly
+  bool cycled = false;                  // a cycle reached the engine: it may hold graphs of this binding (sactd3_rollout_destroy)
   std::string err;
 
   int fail(int code, const std::string& what) {
@@ -482,7 +490,11 @@ ENV_API int sactd3_rollout_create(sactd3_engine* eng, sactd3_env* env, const sac
   }
 }
 
-ENV_API void sactd3_rollout_destroy(sactd3_rollout* r) { delete r; }      // (neither handle nor any buffer is the rollout's)
+// (neither handle nor any buffer is the rollout's; the cycle graphs of its binding, which the engine keeps, go with it)
+ENV_API void sactd3_rollout_destroy(sactd3_rollout* r) {
+  if (r && r->cycled) engine_rollout_cycle_release(r->eng, r);
+  delete r;
+}
 
 ENV_API const char* sactd3_rollout_last_error(const sactd3_rollout* r) { return r ? r->err.c_str() : g_rollout_create_error.c_str(); }
 
@@ -542,4 +554,47 @@ ENV_API int sactd3_rollout_stats(const sactd3_rollout* r, int64_t out[4]) {
   if (!r || !out) return SACTD3_EINVAL;
   for (int i = 0; i < 4; ++i) out[i] = r->stats[i];
   return SACTD3_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- include/sactd3_rollout_cycle.h
+// What the engine is handed for the env step: this launcher and the rollout as its context -- no field of either handle.  (The device is
+// the engine's, which is the env's: sactd3_rollout_create.  Nothing but the launch, so that the engine's capture may hold it.)
+static int cycle_env_step(void* ctx, hipStream_t s) {
+  sactd3_rollout* r = (sactd3_rollout*)ctx;
+  const sactd3_rollout_buffers& b = r->buf;
+  return (int)issue_step_rec(r->env, b.actions, b.actions_ld, &r->lay, b.records, b.obs, b.obs_ld, s);
+}
+
+ENV_API int sactd3_rollout_cycle(sactd3_rollout* r, int mode, int do_actor) {
+  if (!r) return SACTD3_EINVAL;
+  try {
+    if (mode != SACTD3_ROLLOUT_EXPLORE && mode != SACTD3_ROLLOUT_EXPLOIT)
+      return r->fail(SACTD3_EINVAL, "sactd3_rollout_cycle: mode must be SACTD3_ROLLOUT_EXPLORE or SACTD3_ROLLOUT_EXPLOIT (a random or repeated choice "
+                                    "runs no update: sactd3_rollout_advance / _choose)");
+    const sactd3_rollout_buffers& b = r->buf;
+    const CycleBinding bind{r, cycle_env_step, r, b.obs, b.obs_ld, b.actions, b.actions_ld, b.records, r->n, r->stream, r->cycle_stats};
+    const int64_t had = r->cycle_stats[0] + r->cycle_stats[1];
+    int rc = engine_rollout_cycle(r->eng, bind, mode == SACTD3_ROLLOUT_EXPLORE ? 1 : 0, do_actor);
+    if (r->cycle_stats[0] + r->cycle_stats[1] != had) r->cycled = true;      // (a capture counts: the engine holds a graph of ours)
+    if ((rc = r->from_engine(rc, "sactd3_rollout_cycle"))) return rc;
+    ++r->stats[1]; ++r->stats[2]; r->stats[3] += r->n;      // a policy choice, a step, its rows
+    return SACTD3_OK;
+  } catch (...) {
+    return SACTD3_EHIP;
+  }
+}
+
+ENV_API int sactd3_rollout_cycle_stats(const sactd3_rollout* r, int64_t out[4]) {
+  if (!r || !out) return SACTD3_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = r->cycle_stats[i];
+  return SACTD3_OK;
+}
+
+ENV_API int sactd3_rollout_cycle_clamped(sactd3_rollout* r, int64_t* out) {
+  if (!r || !out) return SACTD3_EINVAL;
+  try {
+    return r->from_engine(engine_rollout_cycle_clamped(r->eng, out), "sactd3_rollout_cycle_clamped");
+  } catch (...) {
+    return SACTD3_EHIP;
+  }
 }

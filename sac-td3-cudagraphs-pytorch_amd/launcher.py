@@ -333,22 +333,30 @@ def mode_flags(args, plan) -> dict:
                  native_rollout=args.native_rollout, policy_stats=policy_stats_plan(args))
     if getattr(args, "hindsight", False):
         flags["hindsight"] = True
+    if getattr(args, "fused_rollout", False):    # (the same: the key is there only when the flag was given)
+        flags["fused_rollout"] = True
     return flags
 
 
 def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, prior_fraction, updates_per_step, overlap_acting: bool,
-                   device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None) -> dict:
+                   device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
     --n_step N > 1 and --prior_fraction are issued call by call (fused=False), or with --one_launch as one graph launch per iteration.
     `hindsight` (--hindsight: the dict of hindsight_keywords for the job's env): call by call as well, or with --one_launch as one
-    graph launch; the key is in the result only when it was given."""
+    graph launch; the key is in the result only when it was given.
+    `fused_rollout` (--fused_rollout: a loop body as one graph launch, loop.NativeRollout.cycle): asked of loop.rollout_for's own rules
+    and of loop.update_plan beside the other keywords; the key is in the result only when it was given."""
+    if fused_rollout and not (native_rollout and not overlap_acting):      # (its two rules stand in front of the env's: no env is looked at)
+        loop.rollout_for(None, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, fused_rollout=True)
     update = dict(fused=not prioritized and n_step == 1 and prior_fraction is None and not hindsight,
                   prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch,
                   prior_fraction=None if prior_fraction is None else float(prior_fraction), updates_per_step=int(updates_per_step))
     if hindsight:
         update["hindsight"] = dict(hindsight)
+    if fused_rollout:
+        update["fused_rollout"] = True
     loop.update_plan(cfg, sampler=None, **update)
     return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats))
 
@@ -356,7 +364,7 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
-            native_rollout: bool = False, hindsight: bool = False, **over):
+            native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -366,7 +374,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     segment of any online run; `policy_stats`: rows put to the policy at every evaluation (loop.PolicyStats; SAC only);
     `native_rollout`: the env loop through loop.NativeRollout (needs `device_env` and a -native id: env_plan refuses otherwise);
     `hindsight`: the engine relabels goals while it stages each batch (loop.train hindsight=...; needs an env id with a goal layout:
-    hindsight_plan refuses otherwise); with `one_launch` the draw and the relabelling are part of the iteration's one graph."""
+    hindsight_plan refuses otherwise); with `one_launch` the draw and the relabelling are part of the iteration's one graph.
+    `fused_rollout`: with `native_rollout`, a loop body past learning_starts as one graph launch (loop.train fused_rollout=True)."""
     import json
     import time
     from pathlib import Path
@@ -421,7 +430,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
         kw = train_keywords(cfg, prioritized=prioritized, n_step=n_step, one_launch=one_launch, prior_fraction=prior_fraction,
                             updates_per_step=updates_per_step, overlap_acting=overlap_acting, device_env=device_env,
                             native_rollout=native_rollout, policy_stats=policy_stats,
-                            **(dict(hindsight=hindsight_keywords(env_id, cfg.num_envs)) if hindsight else {}))
+                            **(dict(hindsight=hindsight_keywords(env_id, cfg.num_envs)) if hindsight else {}),
+                            **(dict(fused_rollout=True) if fused_rollout else {}))
         metrics = loop.train(cfg, env, agent, evaluator=ev, **kw)
     agent.engine.sync()
     dt = time.time() - t0
@@ -451,6 +461,8 @@ def _worker_main(args, plan, flags) -> int:
                 out["hindsight"] = hindsight_keywords(env_id, job_config(args.algo, env_id, seed).num_envs)
                 if args.one_launch:              # (... and the one-launch form of its iteration beside it)
                     out["one_launch"] = True
+            if args.fused_rollout:               # (the same: a key only when the flag was given)
+                out["fused_rollout"] = True
         else:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
@@ -489,6 +501,9 @@ def main(argv=None) -> int:
     ap.add_argument("--native_rollout", action="store_true",
                     help="with --device_env and a -native env bundle: the env step writes ring records and choose / advance are one library "
                          "call each (loop.train native_rollout=True); the default stays loop.DeviceRollout")
+    ap.add_argument("--fused_rollout", action="store_true",
+                    help="with --device_env --native_rollout: past learning_starts a loop body -- env step, ring append, next action, update -- "
+                         "is one library call and one graph launch (loop.train fused_rollout=True); excludes the other draws")
     ap.add_argument("--hindsight", action="store_true",
                     help="with an env bundle whose tasks have a goal (native_goal): the engine relabels goals while it stages each batch -- "
                          "hindsight experience replay, the future strategy, window = the task's horizon (loop.train hindsight=...; the "

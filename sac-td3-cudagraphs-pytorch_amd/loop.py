@@ -190,7 +190,10 @@ class NativeRollout:
     def close(self) -> None:
         """drop the handle (before the env or the engine is closed); the tensors stay the caller's"""
         if getattr(self, "_h", None):
-            self._lib.sactd3_rollout_destroy(self._h)
+            # (an engine closed first is gone: the handle's destroy would give it back the cycle graphs it no longer holds -- the few
+            # bytes of the handle are left behind instead; the order the header asks for is rollout first)
+            if getattr(self.agent.engine, "_h", None):
+                self._lib.sactd3_rollout_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -222,6 +225,32 @@ class NativeRollout:
             self._ck(rc)
         self.steps += 1
 
+    def cycle(self, i: int) -> None:
+        """`advance()`, `choose()` with the exploring policy and `agent.iteration(i)` as ONE ctypes call and one graph launch
+        (include/sactd3_rollout_cycle.h: sactd3_rollout_cycle), with the counters the three keep: `steps`, the agent's
+        `qnet_updates_so_far` / `actor_updates_so_far` (the actor updates run when i % (delay + 1) == 0); the batch generation is the
+        engine's own.  Bit for bit the three calls.  For a body of the loop past `learning_starts` with `action_repeat` 1: the caller
+        decides that (train(fused_rollout=True)); the engine refuses pinned rows, engine-owned priorities and an acting call in flight."""
+        agent = self.agent
+        delay = agent.engine.cfg.actor_update_delay
+        do_actor = i % (delay + 1) == 0
+        rc = self._lib.sactd3_rollout_cycle(self._h, self._explore, 1 if do_actor else 0)
+        if rc:
+            self._ck(rc)
+        self.steps += 1
+        agent.qnet_updates_so_far += 1
+        if do_actor:
+            agent.actor_updates_so_far += delay
+
+    def cycle_stats(self) -> Dict[str, int]:
+        """host counters of the handle's cycles (sactd3_rollout_cycle_stats), and `clamped`: appends that found a ring length or cursor
+        outside the ring in device memory (sactd3_rollout_cycle_clamped: 0 in every sound run; waits for the engine's stream)"""
+        import ctypes as C
+        out, clamped = (C.c_int64 * 4)(), C.c_int64()
+        self._ck(self._lib.sactd3_rollout_cycle_stats(self._h, out))
+        self._ck(self._lib.sactd3_rollout_cycle_clamped(self._h, C.byref(clamped)))
+        return dict(zip(("cycles", "graphs_captured", "graph_nodes", "eager_cycles"), (int(v) for v in out)), clamped=int(clamped.value))
+
 
 def segment(env, agent, seed: int, segment_len: int, learning_starts: int, action_repeat: int, overlap: bool = False,
             rollout: Optional[Rollout] = None) -> Generator[None, None, None]:
@@ -237,11 +266,16 @@ def segment(env, agent, seed: int, segment_len: int, learning_starts: int, actio
         ro.advance()
 
 
-def rollout_for(env, *, overlap: bool, device_env: bool, native_rollout: bool):
+def rollout_for(env, *, overlap: bool, device_env: bool, native_rollout: bool, fused_rollout: bool = False):
     """Which of the three classes above drives `env` for train(): refuses what excludes each other, constructs nothing.  -> None for the
     plain host case (segment() makes its own `Rollout`), else what to call with (env, agent, seed, learning_starts, action_repeat).
     Both device rollouts act on the learner stream, so neither goes with `overlap`; the native one needs an env on the GPU that emits
-    ring records (`step_records`: envs.NativeVecEnv)."""
+    ring records (`step_records`: envs.NativeVecEnv).  `fused_rollout` (a loop body as one `NativeRollout.cycle`) needs the native
+    rollout -- its two rules come first, before `env` is looked at; what it needs of the update keywords is `update_plan`'s."""
+    if fused_rollout and not native_rollout:
+        raise ValueError("fused_rollout=True needs native_rollout=True: the cycle is a call of the native rollout's handle")
+    if fused_rollout and overlap:
+        raise ValueError("fused_rollout=True and overlap=True exclude each other: the cycle acts inside its own graph, on the learner stream")
     if native_rollout and overlap:
         raise ValueError("native_rollout=True and overlap=True exclude each other: the native rollout acts on the learner stream")
     if native_rollout and not device_env:
@@ -329,12 +363,14 @@ class PolicyStats:
 
 def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler], prioritized: Optional[Dict[str, float]], n_step: int,
                 one_launch: bool, prior_fraction: Optional[float], updates_per_step: int,
-                hindsight: Optional[Dict[str, Any]] = None) -> SimpleNamespace:
+                hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False) -> SimpleNamespace:
     """What train() does with one update, decided once from its keywords: touches no agent, env or GPU and imports nothing, so a process
     that never opens a GPU can ask whether a run would be refused.  `cfg` needs `batch_size` (with `prior_fraction`, and when an update is
     issued call by call), `num_envs` (with `n_step` > 1) and `actor_update_delay` (call by call).  Which keywords need or exclude each
     other is the table `refusals` below, one row per rule with its reason, the first row that applies raising ValueError: a new mode
     adds its rows there.  `prior_fraction` and `hindsight` count as reasons for `one_launch`.
+    `fused_rollout` (train's keyword: a loop body as one `NativeRollout.cycle`, whose update is the fused uniform iteration) needs
+    `fused` and excludes every other draw; `cfg` then needs `segment_len` and `action_repeat`, which must both be 1.  Its rows stand first.
     -> a namespace of
       updates_per_step  as an int
       priorities        None, or dict(alpha=, eps=) for `agent.rb.enable_priorities` -- train() enables them once, before its loop
@@ -354,7 +390,17 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
     hind = hindsight is not None
     hs_unknown = sorted(set(hindsight or ()) - {"achieved", "desired", "dim", "threshold", "ratio", "window", "stride"})
     hs_missing = sorted({"achieved", "desired", "dim", "threshold"} - set(hindsight or ())) if hind else []
+    fr = bool(fused_rollout)
     refusals = (
+        (fr and not fused, "fused_rollout=True needs fused=True: the update inside the cycle is the fused uniform iteration"),
+        (fr and outside, "fused_rollout=True excludes sampler=...: the cycle draws uniformly inside its graph"),
+        (fr and prio, "fused_rollout=True excludes prioritized=...: the cycle's append owes the priorities no launch, its draw is uniform"),
+        (fr and n_step > 1, "fused_rollout=True excludes n_step > 1: the cycle's iteration samples single steps"),
+        (fr and prior, "fused_rollout=True excludes prior_fraction=...: the cycle's append goes round the whole ring, pinned rows included"),
+        (fr and hind, "fused_rollout=True excludes hindsight=...: the cycle's iteration relabels nothing"),
+        (fr and one_launch, "fused_rollout=True excludes one_launch=True: that is the one-launch form of the other draws"),
+        (fr and int(cfg.segment_len) != 1, "fused_rollout=True needs segment_len == 1: a cycle is one env step and one update"),
+        (fr and int(cfg.action_repeat) != 1, "fused_rollout=True needs action_repeat == 1: a cycle chooses an action with every step"),
         (updates_per_step < 1, f"updates_per_step must be >= 1, got {updates_per_step}"),
         (prior and not 0.0 <= float(prior_fraction) <= 1.0, f"prior_fraction must be in [0, 1], got {prior_fraction}"),
         (prior and fused, "prior_fraction=... needs fused=False: the fused iteration samples uniformly inside its graph"),
@@ -445,7 +491,7 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
           n_step: int = 1, one_launch: bool = False, prior_fraction: Optional[float] = None,
           updates_per_step: int = 1, policy_stats: int = 0, native_rollout: bool = False,
-          hindsight: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+          hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -461,6 +507,11 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     `native_rollout=True` (an env with `step_records`, e.g. envs.NativeVecEnv): the env is driven by `NativeRollout` instead -- the env
     step writes the transitions as ring records and choose / advance are one library call each, with the ring, the env and the engine
     bit for bit as `DeviceRollout` leaves them.  Off by default.
+    `fused_rollout=True` (needs native_rollout=True and fused=True, segment_len == 1 and action_repeat == 1; excludes every other draw):
+    a loop body -- env step, ring append, next action, update -- is ONE library call and one graph launch (`NativeRollout.cycle`)
+    wherever the step count in front of it is at or past `learning_starts`, so that its choice is an exploring one and an update
+    follows; every other body -- the random phase, the step that crosses `learning_starts` -- goes through the call sequence, and
+    with `updates_per_step` > 1 the further updates do.  The run ends bit for bit as the native_rollout=True run does.  Off by default.
     `sampler` (a ProportionalSampler): prioritised replay, call by call on the device -- the sampler's rows and importance weights
     through `rb.sample_at`, the critic update weighted by them, its TD errors (`agent.td_errors`) back into the sampler's priorities;
     the actor updates train on the same rows, unweighted.
@@ -486,8 +537,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     and returned with the last metrics; the run itself is bit for bit the run without it."""
     pstats = PolicyStats(agent, policy_stats, cfg.seed) if policy_stats else None
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
-                       prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight)
-    make_rollout = rollout_for(env, overlap=overlap, device_env=device_env, native_rollout=native_rollout)
+                       prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout)
+    make_rollout = rollout_for(env, overlap=overlap, device_env=device_env, native_rollout=native_rollout, fused_rollout=fused_rollout)
     if plan.priorities is not None:                                       # (nothing above touched the agent's engine)
         agent.rb.enable_priorities(**plan.priorities)
     if plan.hindsight is not None:
@@ -497,22 +548,34 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     seg_gen = segment(env, agent, cfg.seed, cfg.segment_len, cfg.learning_starts, cfg.action_repeat, rollout=ro)
     i = 0
     tlog: Dict[str, Any] = {}
-    while agent.timesteps_so_far <= cfg.num_timesteps:
-        if evaluator is not None:
-            evaluator.maybe_start_clock(agent.timesteps_so_far)           # orchestrator.py:319-322
-        next(seg_gen)
-        agent.timesteps_so_far += cfg.segment_len * cfg.num_envs
-        if sampler is not None:
-            sampler.extend(cfg.segment_len * cfg.num_envs)                # the rows the segment just appended
-        if agent.timesteps_so_far <= cfg.learning_starts:
-            i += 1
-            continue
-        for _ in range(plan.updates_per_step):                           # (1: the reference's one update per segment)
-            plan.update(agent, i, tlog)
-            i += 1
-        if agent.timesteps_so_far % cfg.eval_every == 0:
-            resolve()                                                     # the evaluator / on_eval act (or load) with the same agent
-            _eval_point(agent, pstats, evaluator, on_eval, agent.timesteps_so_far)
+    step_rows = cfg.segment_len * cfg.num_envs
+    try:
+        while agent.timesteps_so_far <= cfg.num_timesteps:
+            if evaluator is not None:
+                evaluator.maybe_start_clock(agent.timesteps_so_far)       # orchestrator.py:319-322
+            # a body past learning_starts chooses by the policy and is followed by an update: advance, choose and that update as one
+            # call.  (ro.steps > 0: the generator has made the choice that opens the rollout, and waits between a choose and an advance.)
+            cycled = fused_rollout and ro.steps > 0 and agent.timesteps_so_far >= cfg.learning_starts
+            if cycled:
+                ro.cycle(i)
+                i += 1
+            else:
+                next(seg_gen)
+            agent.timesteps_so_far += step_rows
+            if sampler is not None:
+                sampler.extend(step_rows)                                 # the rows the segment just appended
+            if agent.timesteps_so_far <= cfg.learning_starts:
+                i += 1
+                continue
+            for _ in range(plan.updates_per_step - (1 if cycled else 0)):   # (1: the reference's one update per segment)
+                plan.update(agent, i, tlog)
+                i += 1
+            if agent.timesteps_so_far % cfg.eval_every == 0:
+                resolve()                                                 # the evaluator / on_eval act (or load) with the same agent
+                _eval_point(agent, pstats, evaluator, on_eval, agent.timesteps_so_far)
+    finally:
+        if fused_rollout and ro is not None:
+            ro.close()                                                    # the engine holds graphs of this binding: dropped with it, here
     resolve()                                                             # leave no acting call in flight behind the loop
     return _last_metrics(agent, pstats)
 
