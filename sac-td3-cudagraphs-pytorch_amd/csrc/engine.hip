@@ -89,11 +89,28 @@ static const int BIG_BATCH = 1024;   // from here on the hidden layers run as 64
 enum { G_Q = 0, G_A = 1, G_STEP00 = 2, G_STEP01 = 3, G_STEP10 = 4, G_STEP11 = 5, G_PERIOD = 6, G_PERIOD_B = 7, G_OPENING = 8,
        G_PREFIX = 9 /* + 2 (m - 1) + variant, m = 1, 2: the first m iterations of a period (sactd3_step_prefix) */,
        G_QW = 13 /* update_qnets in its weighted form: captured at its first use only */,
-       G_RUN = 14 /* + start variant (sactd3_step_periods) */, G_SAMPLED = 16 /* + 2 do_actor + target update (sactd3_step_sampled) */, G_COUNT = 20 };
+       G_RUN = 14 /* + start variant (sactd3_step_periods) */, G_SAMPLED = 16 /* + 2 do_actor + target update (sactd3_step_sampled) */,
+       G_CYCLE = 20 /* + (explore ? 0 : 4) + IterSchedule::k (sactd3_rollout_cycle) */, G_COUNT = 28 };
 static const int NSTAGE = 32;
 
 struct NodeInfo { std::string name; double flops; double bytes; long threads; };
-
+// Ring rows into batch slot 0, described once for a call form (sactd3_rb_sample_*) and for a place in a captured iteration
+// (sactd3_step_sampled): what such a draw refuses, allocates, launches and leaves in the host state stands in draw_state_refusal,
+// draw_alloc, draw_launches and draw_issued, and nowhere else.  kind: SACTD3_DRAW_*; beta: the importance exponent of a prioritised draw;
+// steps == 0: one ring row per batch row (k_batch_from_index), steps >= 1: rows chained into n-step returns over (steps, stride) by
+// k_batch_from_index_nstep (sactd3_rb_sample_nstep takes it at steps == 1 too).  rows: the caller chose them and nothing is drawn --
+// kind then names the staging kernel alone: SACTD3_DRAW_UNIFORM the two above, SACTD3_DRAW_HINDSIGHT k_hindsight_stage.
+struct CallerRows {
+  const long long* idx = nullptr; int64_t idx_ld = 1; const float* w = nullptr; int64_t w_ld = 1;      // ring slots [, loss weights]
+  const int* choice = nullptr; int64_t choice_ld = 1;      // hindsight: the relabelling choices (NULL: the kernel draws them)
+  bool weighted = false;                                   // the slot carries loss weights behind the call
+};
+struct Draw {
+  int kind = SACTD3_DRAW_UNIFORM; float beta = 0.f; int steps = 0, stride = 0; const CallerRows* rows = nullptr;
+  bool chain() const { return steps > 0; }
+  bool weighted() const { return rows ? rows->weighted : kind == SACTD3_DRAW_PRIORITIZED; }
+  bool same_graphs(const Draw& d) const { return kind == d.kind && steps == d.steps && stride == d.stride; }      // (beta is read on the device)
+};
 struct sactd3_engine {
   sactd3_config cfg{};
   std::string err;
@@ -161,7 +178,7 @@ struct sactd3_engine {
   float* h_batch = nullptr;                      // pinned [B][rec_f]
 
   int64_t rb_len = 0, rb_cursor = 0, qnet_updates = 0;
-  hipGraphExec_t graphs[G_COUNT] = {}; int graph_nodes[G_COUNT] = {};      // every learner graph, by its G_* id (enqueue_graph says what each holds)
+  hipGraphExec_t graphs[G_COUNT] = {}; int graph_nodes[G_COUNT] = {};      // every learner and cycle graph, by its G_* id (enqueue_graph says what each holds)
   std::vector<hipGraphExec_t> predict_graphs;   // [explore][n]: the two launches of sactd3_predict, captured per row count
   // Acting on a stream of its own (sactd3_predict_begin / _end), created at the first begin.  Order between the two streams is kept
   // by the host, with events, only where the acting kernels and a learner call touch the same memory -- the actor parameters:
@@ -226,10 +243,10 @@ struct sactd3_engine {
   int *ns_k = nullptr, *ns_last = nullptr, *ns_ctr = nullptr;
   int64_t ns_host[2] = {};
   // The replay-aware iteration as one graph launch (sactd3_step_sampled): one executable graph per (do_actor, target update), G_SAMPLED + k,
-  // for the current ss_key = (draw, n_step, stride) -- a change of those three drops all four.  Their staging and priority launches are the
+  // for the current ss_draw (kind, steps, stride) -- a change of those three drops all four.  Their staging and priority launches are the
   // graph forms (prio_kernels.h), which read the ring length, the cursor, beta and the injection switch from device memory: ss_beta_bits /
   // ss_inject are what the host last published into PrioCtl (-1: nothing yet).  ss_stats: {launches, graph captures, 0, 0}.
-  int ss_key[3] = {0, 0, 0};
+  Draw ss_draw;
   int64_t ss_beta_bits = -1; int ss_inject = -1;
   int64_t ss_stats[4] = {};
   // Runs of whole periods as one graph launch (sactd3_step_periods): RUN_PERIODS consecutive pipelined periods, one executable graph
@@ -267,13 +284,12 @@ struct sactd3_engine {
   int *hs_off = nullptr, *hs_gs = nullptr, *hs_ctr = nullptr;
   int64_t hs_calls = 0, hs_pub = -1;
   // One env step of a native rollout as one graph launch (sactd3_rollout_cycle; engine_rollout_cycle at the end of this file): env step,
-  // ring append in its graph form, acting pair, uniform iteration.  One executable graph per (mode, IterSchedule::k), 4 exploit + k, for
-  // the rollout handle cyc_owner, whose three buffers and env-step launcher its nodes hold by value: a cycle of another handle, and
-  // that handle's destruction, drop all eight.  cyc_ctr: the device word the append counts a clamped cursor / length in; made at
-  // the first cycle -- an engine that never cycles holds nothing more than before.  Not in the table of learner graphs: they need a
-  // rollout to be built from (sactd3_instantiate_graphs has none), and the existing ids keep their numbers.
-  const void* cyc_owner = nullptr;
-  hipGraphExec_t cyc_graphs[8] = {}; int cyc_nodes[8] = {};
+  // ring append in its graph form, acting pair, uniform iteration.  One executable graph per (mode, IterSchedule::k), G_CYCLE + 4 exploit + k,
+  // for the rollout handle cyc.owner, whose three buffers and env-step launcher its nodes hold by value -- cyc is the binding they were
+  // captured from (enqueue_graph reads it): a cycle of another handle, and that handle's destruction, drop all eight.  cyc_ctr: the
+  // device word the append counts a clamped cursor / length in; made at the first cycle -- an engine that never cycles holds nothing
+  // more than before.  sactd3_instantiate_graphs has no rollout to build them from and leaves these ids alone.
+  CycleBinding cyc{};
   int* cyc_ctr = nullptr;
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
@@ -1463,14 +1479,14 @@ static int run_graph_slot(sactd3_engine* e, hipGraphExec_t* slot, int* nodes, F&
   if (launch) HIPCHK(hipGraphLaunch(*slot, st));
   return 0;
 }
-// The learner graphs live in one table, sactd3_engine::graphs, keyed by the G_* ids; enqueue_graph (below the sequences it names) is
+// The learner graphs and the rollout cycle's live in one table, sactd3_engine::graphs, keyed by the G_* ids; enqueue_graph (below the sequences it names) is
 // the one place that says which sequence an id holds, so an id cannot be captured with one sequence here and another there.
 static int enqueue_graph(EnqCtx& x, int which);
 static int run_graph(sactd3_engine* e, int which, bool launch = true) {
   const bool had = e->graphs[which] != nullptr;
   RCCHK(run_graph_slot(e, &e->graphs[which], &e->graph_nodes[which], [which](EnqCtx& x) { return enqueue_graph(x, which); }, launch));
-  // whoever needs a graph first captures it (its entry point, sactd3_instantiate_graphs): the two capture counters are kept here
-  if (!had && e->graphs[which] && which >= G_RUN) ++(which >= G_SAMPLED ? e->ss_stats[1] : e->run_stats[3]);
+  // whoever needs a graph first captures it (its entry point, sactd3_instantiate_graphs): the capture counters are kept here
+  if (!had && e->graphs[which] && which >= G_RUN) ++*(which >= G_CYCLE ? &e->cyc.stats[1] : which >= G_SAMPLED ? &e->ss_stats[1] : &e->run_stats[3]);
   return 0;
 }
 // drop the graphs [first, first + count) of the table (an executable graph is not destroyed under its own replay: the stream drains first)
@@ -1609,9 +1625,10 @@ static int prio_refresh(EnqCtx& x, int64_t first, int64_t n) {
 static int prio_after_append(EnqCtx& x, int64_t first, int64_t n) {
   return (x.e->pt_on && n > 0) ? prio_refresh(x, first, n) : 0;
 }
-// the two launches of a prioritised draw: slots and leaves, then weights (+ counter tick); the staging kernel follows (stage_ring_rows)
+// the two launches of a prioritised draw: slots and leaves, then weights (+ counter tick); the staging kernel follows (draw_launches)
 static int prio_draw_launches(EnqCtx& x, float beta) {
   sactd3_engine* e = x.e;
+  if (x.graph_form) beta = 0.f;      // (read from PrioCtl on the device: a captured node holds no value of it)
   PrioDrawArgs d{};
   d.leaf4 = (const float4*)e->pt_leaf; d.sums4 = (const float4*)e->pt_sums;
   d.ngroups = e->pt_groups; d.nch = (e->pt_groups + PRIO_G - 1) / PRIO_G; d.len = (int)e->rb_len;
@@ -1659,19 +1676,15 @@ static int mix_publish(EnqCtx& x) {
   e->mix_pub[0] = e->rb_pinned; e->mix_pub[1] = e->mix_m;
   return 0;
 }
-// the draw (it advances the sample counter itself) and the staging of the drawn slots: the two launches in front of the critic update
-static int launch_mix_draw(EnqCtx& x) {
+// the draw of B slots into mix_idx, m of them from the P pinned rows (it advances the sample counter itself); P = m = 0: the uniform
+// draw of sactd3_rb_sample.  The graph form reads P and m from mix_ctl.
+static int launch_mix_draw(EnqCtx& x, int64_t P, int m) {
   sactd3_engine* e = x.e;
-  const MixDrawArgs d{e->ctl, e->mix_idx, e->B, (int)e->rb_len, (int)e->rb_pinned, e->mix_m};
+  const MixDrawArgs d{e->ctl, e->mix_idx, e->B, (int)e->rb_len, (int)P, m};
   if (x.graph_form) LAUNCH_ON(k_mix_draw<true>, dim3(1), dim3(256), d, (const MixCtl*)e->mix_ctl, (int)e->cfg.rb_capacity);
   else LAUNCH_ON(k_mix_draw<false>, dim3(1), dim3(256), d, (const MixCtl*)nullptr, 0);
   return 0;
 }
-static int mix_draw_launches(EnqCtx& x) {
-  RCCHK(launch_mix_draw(x));
-  return launch_batch_index(x, x.e->mix_idx, 1, nullptr, 1);
-}
-static inline void mix_count(sactd3_engine* e) { ++e->mix_stats[0]; e->mix_stats[1] += e->mix_m; e->mix_stats[2] += e->B - e->mix_m; }
 
 // ---- hindsight relabelling (device code: hindsight_kernels.h, through the launcher of hindsight.h)
 static int hindsight_alloc(sactd3_engine* e) {
@@ -1735,23 +1748,76 @@ static int hindsight_publish(EnqCtx& x) {
   return 0;
 }
 
+// ---- struct Draw, each part said once: the call forms (stage_ring_rows, sactd3_rb_sample_mixed) and the captured iteration
+// (sactd3_step_sampled, enqueue_step_sampled) are these four routines, in the protocol order of stage_ring_rows.
+// What a draw needs of the ring and of the engine's features, checked on the host (NULL: nothing to refuse); the caller puts its own
+// name in front (state_refusal).
+static const char* const PRIO_OFF = "priorities are not enabled (sactd3_prio_enable)";
+static const char* draw_state_refusal(const sactd3_engine* e, const Draw& d) {
+  const bool hind = d.kind == SACTD3_DRAW_HINDSIGHT;
+  if (d.kind == SACTD3_DRAW_PRIORITIZED && !e->pt_on) return PRIO_OFF;
+  if (d.chain() && e->rb_pinned > 0) return "rows are pinned (sactd3_rb_pin): the n-step age formula assumes one wrap point, at slot 0";
+  if (hind && !e->hs_on) return "hindsight is not configured (sactd3_hindsight_configure)";
+  if (hind && e->rb_pinned > 0) return "rows are pinned (sactd3_rb_pin): the chain's age formula assumes one wrap point, at slot 0";
+  if (e->rb_len <= 0) return "buffer is empty";
+  return d.kind == SACTD3_DRAW_MIXED ? mix_refusal(e) : nullptr;
+}
+static int state_refusal(sactd3_engine* e, const char* who, const char* why) { e->err = std::string(who) + ": " + why; return SACTD3_ESTATE; }
+// first-use allocations: an engine that never uses a feature holds nothing for it
+static int draw_alloc(sactd3_engine* e, const Draw& d) {
+  const bool hind = d.kind == SACTD3_DRAW_HINDSIGHT;
+  if (!hind && (d.weighted() || !d.chain())) RCCHK(slot_weights_alloc(e));      // (the 1-step kernel always writes the slot's weights, the hindsight kernel none)
+  if (d.chain()) RCCHK(nstep_alloc(e));
+  if (!d.rows && (hind || d.kind == SACTD3_DRAW_MIXED)) RCCHK(mix_alloc(e));      // (where the draw kernel leaves the slots)
+  return hind ? hindsight_alloc(e) : 0;
+}
+// the staging kernel on the rows `idx` [with the weights `w`]: one row each, or chained
+static int launch_staging(EnqCtx& x, const Draw& d, const long long* idx, int64_t idx_ld, const float* w, int64_t w_ld) {
+  if (d.chain()) return launch_batch_nstep(x, idx, idx_ld, w, w_ld, d.weighted() ? x.e->bs[0].w : nullptr, d.steps, d.stride);
+  return launch_batch_index(x, idx, idx_ld, w, w_ld);
+}
+// The launches, in the call form or, with x.graph_form, the form a captured graph holds: the draw's own, then the staging of the drawn
+// slots.  The mixed and hindsight draw kernels advance the sample counter themselves (the hindsight graph form its draw counter too); a
+// uniform draw is made by the staging kernel at the sample counter, which a tick then advances.
+static int draw_launches(EnqCtx& x, const Draw& d) {
+  sactd3_engine* e = x.e;
+  const bool hind = d.kind == SACTD3_DRAW_HINDSIGHT;
+  if (const CallerRows* r = d.rows)
+    return hind ? launch_hindsight(x, r->idx, r->idx_ld, r->choice, r->choice_ld, (unsigned)e->hs_calls) : launch_staging(x, d, r->idx, r->idx_ld, r->w, r->w_ld);
+  if (d.kind == SACTD3_DRAW_PRIORITIZED) {      // the draw leaves slots and weights in pt_idx / pt_w
+    RCCHK(prio_draw_launches(x, d.beta));
+    return launch_staging(x, d, e->pt_idx, 1, e->pt_w, 1);
+  }
+  if (hind && x.graph_form) return hindsight_draw_launches_g(x);
+  if (hind || d.kind == SACTD3_DRAW_MIXED) {      // hindsight: the uniform draw -- no pinned row, no prior share -- relabelled at the draw counter
+    RCCHK(launch_mix_draw(x, hind ? 0 : e->rb_pinned, hind ? 0 : e->mix_m));
+    return hind ? launch_hindsight(x, e->mix_idx, 1, nullptr, 1, (unsigned)e->hs_calls) : launch_batch_index(x, e->mix_idx, 1, nullptr, 1);
+  }
+  RCCHK(launch_staging(x, d, nullptr, 1, nullptr, 1));
+  return launch_tick(x, &e->ctl->sample_ctr);
+}
+// The host state behind the launches: the slot, then each feature's counters (ns_host: {n-step stagings, rows staged}; hs_calls: where
+// the kernel drew its own choices -- only the graph form's draw kernel has advanced the device's word as well, hs_pub; prio_stats[0]:
+// index stagings of the caller's rows).
+static void draw_issued(sactd3_engine* e, const Draw& d, bool graph_form) {
+  const bool hind = d.kind == SACTD3_DRAW_HINDSIGHT;
+  slot_refilled(e, d.weighted(), d.chain());
+  e->slot.hindsight = hind;
+  if (hind && !(d.rows && d.rows->choice)) { ++e->hs_calls; if (graph_form) ++e->hs_pub; }
+  if (d.chain()) { ++e->ns_host[0]; e->ns_host[1] += e->B; }
+  if (d.kind == SACTD3_DRAW_PRIORITIZED) ++e->pt_host[0];
+  if (d.kind == SACTD3_DRAW_MIXED) { ++e->mix_stats[0]; e->mix_stats[1] += e->mix_m; e->mix_stats[2] += e->B - e->mix_m; }
+  if (d.rows && !hind && !d.chain()) ++e->prio_stats[0];
+}
+
 // The replay-aware iteration (sactd3_step_sampled) as one linear sequence: what the calls
 //   sactd3_rb_sample_prioritized[_nstep] | sactd3_rb_sample_nstep | sactd3_rb_sample_mixed | sactd3_rb_sample_hindsight -> sactd3_update_qnets ->
 //   [sactd3_prio_update_from_td] -> [sactd3_update_actor x actor_update_delay] -> sactd3_update_targ_nets
 // launch, launch for launch, with the staging and priority kernels in their graph forms.  (The 1-step uniform iteration is sactd3_step.)
 static int enqueue_step_sampled(EnqCtx& x, bool actor, bool targets) {
   sactd3_engine* e = x.e;
-  const bool prio = e->ss_key[0] == SACTD3_DRAW_PRIORITIZED, mixed = e->ss_key[0] == SACTD3_DRAW_MIXED;
-  const bool hind = e->ss_key[0] == SACTD3_DRAW_HINDSIGHT;
-  const int steps = e->ss_key[1], stride = e->ss_key[2];
-  if (prio) RCCHK(prio_draw_launches(x, 0.f));
-  const long long* idx = prio ? e->pt_idx : nullptr;
-  const float* w = prio ? e->pt_w : nullptr;
-  if (mixed) RCCHK(mix_draw_launches(x));      // (unweighted, no chain; the draw kernel has advanced the sample counter)
-  else if (hind) RCCHK(hindsight_draw_launches_g(x));      // (the same, and the draw kernel has advanced the hindsight draw counter too)
-  else if (steps > 1) RCCHK(launch_batch_nstep(x, idx, 1, w, 1, prio ? e->bs[0].w : nullptr, steps, stride));
-  else RCCHK(launch_batch_index(x, idx, 1, w, 1));
-  if (!prio && !mixed && !hind) RCCHK(launch_tick(x, &e->ctl->sample_ctr));      // the uniform draw was made at the sample counter, which now advances
+  const bool prio = e->ss_draw.kind == SACTD3_DRAW_PRIORITIZED;
+  RCCHK(draw_launches(x, e->ss_draw));
   IterPlace it;
   it.weighted = prio;
   RCCHK(enqueue_update_qnets(x, it, false));
@@ -1797,7 +1863,6 @@ void sactd3_destroy(sactd3_engine* e) {
   (void)drop_graphs(e, 0, G_COUNT);
   for (auto& g : e->predict_graphs) if (g) hipGraphExecDestroy(g);
   for (auto& g : e->predict_dev_graphs) if (g) hipGraphExecDestroy(g);
-  for (auto& g : e->cyc_graphs) if (g) hipGraphExecDestroy(g);
   for (auto ev : e->events) hipEventDestroy(ev);
   for (void* p : e->dev_allocs) hipFree(p);
   for (void* p : e->host_allocs) hipHostFree(p);
@@ -2455,66 +2520,56 @@ int sactd3_readout_stats(sactd3_engine* e, int64_t out[4]) { return (!e || !out)
 
 // ---- ring rows into batch slot 0, all on the device (include/sactd3.h): the caller's rows or the engine's draw, one row each or chained
 // into n-step returns, with or without loss weights.  One request, one routine; the entry points below only fill the request in.
-enum { DRAW_NONE = 0, DRAW_UNIFORM = 1, DRAW_PRIO = 2 };
 struct StageReq {
   const char* name;                            // the entry point's name, for messages
-  int draw = DRAW_NONE;                        // who chooses the rows: the caller (idx), the uniform draw at the sample counter (chained form only:
-                                               // the 1-step uniform sample is sactd3_rb_sample's gather), or the priority table (beta)
-  const long long* idx = nullptr; int64_t idx_ld = 1; const float* w = nullptr; int64_t w_ld = 1; int n = 0;      // DRAW_NONE: the caller's arrays
-  float beta = 0.f;                            // DRAW_PRIO: the exponent of the importance weights
+  int kind = SACTD3_DRAW_UNIFORM;              // the engine's draw: uniform at the sample counter (chained or hindsight form only: the 1-step
+                                               // uniform sample is sactd3_rb_sample's gather), or by the priority table (beta) ...
+  bool callers = false; CallerRows rows; int n = 0;      // ... or none: the caller's n rows, staged plainly (kind uniform) or relabelled (hindsight)
+  float beta = 0.f;                            // SACTD3_DRAW_PRIORITIZED: the exponent of the importance weights
   bool chain = false; int steps = 0, stride = 0;      // chain: k_batch_from_index_nstep over (steps, stride); otherwise k_batch_from_index
-  bool weighted = false;                       // the slot carries loss weights behind this call
   void* caller_stream = nullptr; int flags = 0;       // SACTD3_SRC_ORDERED and the stream it orders against
   bool internal = false;                       // a timing body: the index array is the engine's own (no pointer check) and no host counter moves
 };
 // The whole protocol, always in this order:
-//   1. refusals, the first fault wins: `idx` NULL, unknown flag, n, stride of `idx`, stride of `w` (the caller's arrays); beta (priority
-//      draw); steps, stride (chained); `idx`, `w` not device memory of this device; priorities not enabled; ring empty.  A refused
-//      call has changed nothing -- a precomputed opening pair (chain_ready) stays valid across it
-//   2. CHAIN_BREAK                     3. allocations at first use (slot weights, n-step arrays)      4. src_order_begin
-//   5. the launches, on the learner stream: [k_prio_draw, k_prio_weights,] the staging kernel [, k_tick of the sample counter behind a uniform draw]
-//   6. src_order_end                   7. slot_refilled                                               8. the host counters
+//   1. refusals, the first fault wins: `idx` NULL, unknown flag, n, stride of `idx`, of `w`, of `choice` (the caller's arrays); beta
+//      (priority draw); steps, stride (chained); `idx`, `w`, `choice` not device memory of this device; then the ring's state
+//      (draw_state_refusal: priorities not enabled; a chain over pinned rows; hindsight not configured, or over pinned rows; ring empty).
+//      A refused call has changed nothing -- a precomputed opening pair (chain_ready) stays valid across it
+//   2. CHAIN_BREAK                     3. allocations at first use (draw_alloc)                       4. src_order_begin
+//   5. the launches, on the learner stream (draw_launches): [k_prio_draw, k_prio_weights, or k_mix_draw, which ticks the sample counter,]
+//      the staging kernel [, k_tick of the sample counter behind a uniform draw it made itself]
+//   6. src_order_end                   7. slot_refilled                                               8. the host counters (7, 8: draw_issued)
 static int stage_ring_rows(EnqCtx& x, const StageReq& q) {
   sactd3_engine* e = x.e;
   const auto refuse = [&](int code, const char* what) { e->err = std::string(q.name) + ": " + what; return code; };
-  const bool callers = q.draw == DRAW_NONE;
-  if (callers) {
-    if (!q.idx) return refuse(SACTD3_EINVAL, "`idx` is NULL");
+  const CallerRows& r = q.rows;
+  if (q.callers) {
+    if (!r.idx) return refuse(SACTD3_EINVAL, "`idx` is NULL");
     if (q.flags & ~SACTD3_SRC_ORDERED) return refuse(SACTD3_EINVAL, "unknown flag");
     if (q.n != e->B) return refuse(SACTD3_EINVAL, "n must equal batch_size");
-    if (q.idx_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `idx` is below its width");
-    if (q.w && q.w_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `w` is below its width");
+    if (r.idx_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `idx` is below its width");
+    if (r.w && r.w_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `w` is below its width");
+    if (r.choice && r.choice_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `choice` is below its width");
   }
-  if (q.draw == DRAW_PRIO && (!(q.beta >= 0.f) || !std::isfinite(q.beta))) return refuse(SACTD3_EINVAL, "beta must be finite and >= 0");
+  if (q.kind == SACTD3_DRAW_PRIORITIZED && (!(q.beta >= 0.f) || !std::isfinite(q.beta))) return refuse(SACTD3_EINVAL, "beta must be finite and >= 0");
   if (q.chain && (q.steps < 1 || q.steps > NS_MAX)) return refuse(SACTD3_EINVAL, "steps must be in [1, 16]");
   if (q.chain && q.stride < 1) return refuse(SACTD3_EINVAL, "stride must be at least 1");
-  if (q.draw == DRAW_UNIFORM && !q.chain) return refuse(SACTD3_EINVAL, "the uniform 1-step sample is sactd3_rb_sample");      // (no entry point asks)
-  if (callers && !q.internal) {
-    RCCHK(device_ptr_check(e, q.idx, q.name, "idx"));
-    if (q.w) RCCHK(device_ptr_check(e, q.w, q.name, "w"));
+  if (q.kind == SACTD3_DRAW_UNIFORM && !q.callers && !q.chain) return refuse(SACTD3_EINVAL, "the uniform 1-step sample is sactd3_rb_sample");      // (no entry point asks)
+  if (q.callers && !q.internal) {
+    RCCHK(device_ptr_check(e, r.idx, q.name, "idx"));
+    if (r.w) RCCHK(device_ptr_check(e, r.w, q.name, "w"));
+    if (r.choice) RCCHK(device_ptr_check(e, r.choice, q.name, "choice"));
   }
-  if (q.draw == DRAW_PRIO && !e->pt_on) return refuse(SACTD3_ESTATE, "priorities are not enabled (sactd3_prio_enable)");
-  if (q.chain && e->rb_pinned > 0) return refuse(SACTD3_ESTATE, "rows are pinned (sactd3_rb_pin): the n-step age formula assumes one wrap point, at slot 0");
-  if (e->rb_len <= 0) return refuse(SACTD3_ESTATE, "buffer is empty");
+  const Draw d{q.kind, q.beta, q.chain ? q.steps : 0, q.chain ? q.stride : 0, q.callers ? &r : nullptr};      // the arguments hold
+  if (const char* why = draw_state_refusal(e, d)) return refuse(SACTD3_ESTATE, why);
   CHAIN_BREAK(e);
-  if (q.weighted || !q.chain) RCCHK(slot_weights_alloc(e));      // (the 1-step kernel always writes the slot's weights)
-  if (q.chain) RCCHK(nstep_alloc(e));
+  RCCHK(draw_alloc(e, d));
   const hipStream_t caller = (hipStream_t)q.caller_stream;
   RCCHK(src_order_begin(e, caller, q.flags));
-  const bool prio = q.draw == DRAW_PRIO;      // the draw leaves slots and weights in pt_idx / pt_w
-  if (prio) RCCHK(prio_draw_launches(x, q.beta));
-  const long long* idx = prio ? e->pt_idx : q.idx;
-  const float* w = prio ? e->pt_w : q.w;
-  const int64_t idx_ld = prio ? 1 : q.idx_ld, w_ld = prio ? 1 : q.w_ld;
-  if (q.chain) RCCHK(launch_batch_nstep(x, idx, idx_ld, w, w_ld, q.weighted ? e->bs[0].w : nullptr, q.steps, q.stride));
-  else RCCHK(launch_batch_index(x, idx, idx_ld, w, w_ld));
-  if (q.draw == DRAW_UNIFORM) RCCHK(launch_tick(x, &e->ctl->sample_ctr));
+  RCCHK(draw_launches(x, d));
   RCCHK(src_order_end(e, caller, q.flags));
-  slot_refilled(e, q.weighted, q.chain);
-  if (q.internal) return 0;
-  if (q.chain) { ++e->ns_host[0]; e->ns_host[1] += e->B; }
-  if (prio) ++e->pt_host[0];
-  if (callers && !q.chain) ++e->prio_stats[0];
+  if (q.internal) slot_refilled(e, d.weighted(), d.chain());      // (a timing body moves no counter)
+  else draw_issued(e, d, false);
   return 0;
 }
 
@@ -2529,7 +2584,7 @@ int sactd3_rb_sample_indices_device(sactd3_engine* e, const int64_t* idx, int64_
                                     void* caller_stream, int flags) {
   if (!e) return SACTD3_EINVAL;
   StageReq q{"rb_sample_indices_device"};
-  q.idx = (const long long*)idx; q.idx_ld = idx_ld; q.w = w; q.w_ld = w_ld; q.n = n; q.weighted = true;
+  q.callers = true; q.rows = {(const long long*)idx, idx_ld, w, w_ld, nullptr, 1, true}; q.n = n;
   q.caller_stream = caller_stream; q.flags = flags;
   return stage_call(e, q);
 }
@@ -2538,7 +2593,7 @@ int sactd3_rb_sample_nstep_device(sactd3_engine* e, const int64_t* idx, int64_t 
                                   int stride, void* caller_stream, int flags) {
   if (!e) return SACTD3_EINVAL;
   StageReq q{"rb_sample_nstep_device"};
-  q.idx = (const long long*)idx; q.idx_ld = idx_ld; q.w = w; q.w_ld = w_ld; q.n = n; q.weighted = true;
+  q.callers = true; q.rows = {(const long long*)idx, idx_ld, w, w_ld, nullptr, 1, true}; q.n = n;
   q.chain = true; q.steps = steps; q.stride = stride; q.caller_stream = caller_stream; q.flags = flags;
   return stage_call(e, q);
 }
@@ -2546,21 +2601,21 @@ int sactd3_rb_sample_nstep_device(sactd3_engine* e, const int64_t* idx, int64_t 
 int sactd3_rb_sample_nstep(sactd3_engine* e, int steps, int stride) {
   if (!e) return SACTD3_EINVAL;
   StageReq q{"rb_sample_nstep"};
-  q.draw = DRAW_UNIFORM; q.chain = true; q.steps = steps; q.stride = stride;
+  q.chain = true; q.steps = steps; q.stride = stride;
   return stage_call(e, q);
 }
 // rb.sample by priority: k_prio_draw, k_prio_weights, k_batch_from_index.  The uniform sampler's counter is not touched.
 int sactd3_rb_sample_prioritized(sactd3_engine* e, float beta) {
   if (!e) return SACTD3_EINVAL;
   StageReq q{"rb_sample_prioritized"};
-  q.draw = DRAW_PRIO; q.beta = beta; q.weighted = true;
+  q.kind = SACTD3_DRAW_PRIORITIZED; q.beta = beta;
   return stage_call(e, q);
 }
 // ... with the chain: the n-step staging kernel on the drawn slots
 int sactd3_rb_sample_prioritized_nstep(sactd3_engine* e, float beta, int steps, int stride) {
   if (!e) return SACTD3_EINVAL;
   StageReq q{"rb_sample_prioritized_nstep"};
-  q.draw = DRAW_PRIO; q.beta = beta; q.weighted = true; q.chain = true; q.steps = steps; q.stride = stride;
+  q.kind = SACTD3_DRAW_PRIORITIZED; q.beta = beta; q.chain = true; q.steps = steps; q.stride = stride;
   return stage_call(e, q);
 }
 
@@ -2602,14 +2657,13 @@ int sactd3_rb_set_mix(sactd3_engine* e, int prior_rows) {
 int sactd3_rb_sample_mixed(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
-  if (const char* why = mix_refusal(e)) { e->err = std::string("rb_sample_mixed: ") + why; return SACTD3_ESTATE; }
+  const Draw d{SACTD3_DRAW_MIXED};
+  if (const char* why = draw_state_refusal(e, d)) return state_refusal(e, "rb_sample_mixed", why);
   CHAIN_BREAK(e);
-  RCCHK(slot_weights_alloc(e));      // (the staging kernel always writes the slot's weights: all 1, and the slot does not carry them)
-  RCCHK(mix_alloc(e));
+  RCCHK(draw_alloc(e, d));      // (the staging kernel always writes the slot's weights: all 1, and the slot does not carry them)
   EnqCtx x{e, e->stream};
-  RCCHK(mix_draw_launches(x));
-  slot_refilled(e, false, false);
-  mix_count(e);
+  RCCHK(draw_launches(x, d));
+  draw_issued(e, d, false);
   return 0;
 }
 
@@ -2636,7 +2690,7 @@ int sactd3_hindsight_configure(sactd3_engine* e, const sactd3_hindsight_config* 
   const sactd3_hindsight_config& h = e->hs_cfg;
   const bool same = e->hs_on && h.ag_off == c->ag_off && h.dg_off == c->dg_off && h.goal_dim == c->goal_dim && h.window == c->window &&
                     h.stride == c->stride && memcmp(&h.threshold, &c->threshold, sizeof(float)) == 0 && memcmp(&h.ratio, &c->ratio, sizeof(float)) == 0;
-  if (!same && e->ss_key[0] == SACTD3_DRAW_HINDSIGHT) {
+  if (!same && e->ss_draw.kind == SACTD3_DRAW_HINDSIGHT) {
     USE_DEVICE(e);
     RCCHK(drop_graphs(e, G_SAMPLED, 4));
   }
@@ -2645,51 +2699,21 @@ int sactd3_hindsight_configure(sactd3_engine* e, const sactd3_hindsight_config* 
   return 0;
 }
 
-// The protocol of stage_ring_rows, in its order: refusals (a refused call has changed nothing), CHAIN_BREAK, allocations at first use,
-// src_order_begin, the launches ([k_mix_draw, which ticks the sample counter,] k_hindsight_stage), src_order_end, slot_refilled, counters.
-// idx == NULL: the uniform draw, with nothing pinned the slots of sactd3_rb_sample.
-static int hindsight_stage(sactd3_engine* e, const char* name, const long long* idx, int64_t idx_ld, const int* choice, int64_t choice_ld, int n,
-                           bool callers, void* caller_stream, int flags) {
-  USE_DEVICE(e);
-  const auto refuse = [&](int code, const char* what) { e->err = std::string(name) + ": " + what; return code; };
-  if (callers) {
-    if (!idx) return refuse(SACTD3_EINVAL, "`idx` is NULL");
-    if (flags & ~SACTD3_SRC_ORDERED) return refuse(SACTD3_EINVAL, "unknown flag");
-    if (n != e->B) return refuse(SACTD3_EINVAL, "n must equal batch_size");
-    if (idx_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `idx` is below its width");
-    if (choice && choice_ld < 1) return refuse(SACTD3_EINVAL, "row stride of `choice` is below its width");
-    RCCHK(device_ptr_check(e, idx, name, "idx"));
-    if (choice) RCCHK(device_ptr_check(e, choice, name, "choice"));
-  }
-  if (!e->hs_on) return refuse(SACTD3_ESTATE, "hindsight is not configured (sactd3_hindsight_configure)");
-  if (e->rb_pinned > 0) return refuse(SACTD3_ESTATE, "rows are pinned (sactd3_rb_pin): the chain's age formula assumes one wrap point, at slot 0");
-  if (e->rb_len <= 0) return refuse(SACTD3_ESTATE, "buffer is empty");
-  CHAIN_BREAK(e);
-  RCCHK(hindsight_alloc(e));
-  if (!callers) RCCHK(mix_alloc(e));
-  const hipStream_t caller = (hipStream_t)caller_stream;
-  RCCHK(src_order_begin(e, caller, flags));
-  EnqCtx x{e, e->stream};
-  if (!callers) {      // the uniform draw: no pinned row, no prior share
-    const MixDrawArgs d{e->ctl, e->mix_idx, e->B, (int)e->rb_len, 0, 0};
-    LAUNCH_ON(k_mix_draw<false>, dim3(1), dim3(256), d, (const MixCtl*)nullptr, 0);
-    idx = e->mix_idx; idx_ld = 1;
-  }
-  RCCHK(launch_hindsight(x, idx, idx_ld, choice, choice_ld, (unsigned)e->hs_calls));
-  RCCHK(src_order_end(e, caller, flags));
-  slot_refilled(e, false, false);
-  e->slot.hindsight = true;
-  if (!choice) ++e->hs_calls;      // a native draw was made at this counter
-  return 0;
-}
+// Both are stage_ring_rows: the uniform draw (with nothing pinned the slots of sactd3_rb_sample) relabelled by k_hindsight_stage, or the
+// caller's rows and, with them, the caller's choices.
 int sactd3_rb_sample_hindsight(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
-  return hindsight_stage(e, "rb_sample_hindsight", nullptr, 1, nullptr, 1, e->B, false, nullptr, 0);
+  StageReq q{"rb_sample_hindsight"};
+  q.kind = SACTD3_DRAW_HINDSIGHT;
+  return stage_call(e, q);
 }
 int sactd3_rb_sample_hindsight_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, const int32_t* choice, int64_t choice_ld, int n,
                                       void* caller_stream, int flags) {
   if (!e) return SACTD3_EINVAL;
-  return hindsight_stage(e, "rb_sample_hindsight_device", (const long long*)idx, idx_ld, (const int*)choice, choice_ld, n, true, caller_stream, flags);
+  StageReq q{"rb_sample_hindsight_device"};
+  q.kind = SACTD3_DRAW_HINDSIGHT; q.callers = true; q.rows = {(const long long*)idx, idx_ld, nullptr, 1, (const int*)choice, choice_ld, false}; q.n = n;
+  q.caller_stream = caller_stream; q.flags = flags;
+  return stage_call(e, q);
 }
 // the offset and the goal's ring slot of every row of a hindsight slot, left in the caller's device arrays: one k_nstep_info launch (the
 // kernel copies two per-row int32 arrays, whatever they mean) on the learner stream.  No CHAIN_BREAK.
@@ -2785,7 +2809,7 @@ int sactd3_prio_enable(sactd3_engine* e, float alpha, float eps) {
 int sactd3_prio_set_uniforms(sactd3_engine* e, const float* u, int n) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_set_uniforms: priorities are not enabled (sactd3_prio_enable)");
+  if (!e->pt_on) return state_refusal(e, "prio_set_uniforms", PRIO_OFF);
   if (!u) { e->pt_inject = false; return 0; }
   if (n != e->B) return e->fail(SACTD3_EINVAL, "prio_set_uniforms: n must equal batch_size");
   std::vector<float> h((size_t)n);
@@ -2796,16 +2820,17 @@ int sactd3_prio_set_uniforms(sactd3_engine* e, const float* u, int n) {
   return 0;
 }
 
+static inline void prio_update_issued(sactd3_engine* e) { ++e->pt_host[1]; }      // a write-back was launched (pt_host: {samples, write-backs, ..})
 // The write-back from the critic update that just ran on the batch slot: one k_prio_update launch.  It reads e->q / e->y and the slot's
 // ring indices and writes the priority table only: no CHAIN_BREAK, a precomputed opening pair of sactd3_step_period stays valid.
 int sactd3_prio_update_from_td(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_from_td: priorities are not enabled (sactd3_prio_enable)");
+  if (!e->pt_on) return state_refusal(e, "prio_update_from_td", PRIO_OFF);
   if (!e->slot.td_valid) return e->fail(SACTD3_ESTATE, "prio_update_from_td: no critic update has run on the rows now in the batch slot");
   EnqCtx x{e, e->stream};
   RCCHK(launch_prio_update(x, prio_td_args(e, e->slot.cur)));
-  ++e->pt_host[1];
+  prio_update_issued(e);
   return 0;
 }
 
@@ -2819,7 +2844,7 @@ int sactd3_prio_update_device(sactd3_engine* e, const int64_t* idx, int64_t idx_
   if (idx_ld < 1 || prio_ld < 1) return e->fail(SACTD3_EINVAL, "prio_update_device: a row stride is below 1");
   RCCHK(device_ptr_check(e, idx, "prio_update_device", "idx"));
   RCCHK(device_ptr_check(e, prio, "prio_update_device", "prio"));
-  if (!e->pt_on) return e->fail(SACTD3_ESTATE, "prio_update_device: priorities are not enabled (sactd3_prio_enable)");
+  if (!e->pt_on) return state_refusal(e, "prio_update_device", PRIO_OFF);
   const hipStream_t caller = (hipStream_t)caller_stream;
   EnqCtx x{e, e->stream};
   RCCHK(src_order_begin(e, caller, flags));
@@ -2827,7 +2852,7 @@ int sactd3_prio_update_device(sactd3_engine* e, const int64_t* idx, int64_t idx_
   g.n = n; g.idx = (const long long*)idx; g.idx_ld = (long)idx_ld; g.prio = prio; g.prio_ld = (long)prio_ld;
   RCCHK(launch_prio_update(x, g));
   RCCHK(src_order_end(e, caller, flags));
-  ++e->pt_host[1];
+  prio_update_issued(e);
   return 0;
 }
 
@@ -2912,13 +2937,14 @@ int sactd3_read_noise(sactd3_engine* e, int site, float* eps, int n) {
 }
 
 // ---- updates
+// a critic update on the rows a refill left in slot 0 was launched: the critics' gradient arenas were written in full (grads_stale)
+static inline void update_qnets_issued(sactd3_engine* e) { e->grads_stale[0] = false; slot_trained(e, 0, false); }
 int sactd3_update_qnets(sactd3_engine* e) {
   if (!e) return SACTD3_EINVAL;
   USE_DEVICE(e);
   CHAIN_BREAK(e);
   RCCHK(run_graph(e, e->slot.weighted ? G_QW : G_Q));      // the weighted form: the same sequence with the weighted critic tail, a graph of its own
-  e->grads_stale[0] = false;
-  slot_trained(e, 0, false);
+  update_qnets_issued(e);
   return 0;
 }
 int sactd3_update_actor(sactd3_engine* e) {
@@ -2947,7 +2973,7 @@ static IterSchedule iteration_schedule(const sactd3_engine* e, int do_actor, int
   const bool act = do_actor != 0 && e->cfg.actor_update_delay > 0;
   return {act, polyak, (act ? 2 : 0) + (polyak ? 1 : 0)};
 }
-// the next iteration as graph `first` + k (G_STEP00, G_SAMPLED), and what it does to the counter and to grads_stale
+// the next iteration as graph `first` + k (G_STEP00, G_SAMPLED, G_CYCLE + 4 exploit), and what it does to the counter and to grads_stale
 static int issue_iteration(sactd3_engine* e, int do_actor, int first) {
   const IterSchedule s = iteration_schedule(e, do_actor, e->qnet_updates + 1);
   if (s.act) RCCHK(actor_write_begin(e));      // (a critic-only iteration touches nothing the acting kernels read: no order with them)
@@ -2981,27 +3007,15 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
   if (mixed && sm->n_step != 1) return e->fail(SACTD3_EINVAL, "step_sampled: the mixed draw has no n-step form: n_step must be 1");
   if (hind && sm->n_step != 1) return e->fail(SACTD3_EINVAL, "step_sampled: the hindsight draw has no n-step form: n_step must be 1");
   if (!(sm->beta >= 0.f) || !std::isfinite(sm->beta)) return e->fail(SACTD3_EINVAL, "step_sampled: beta must be finite and >= 0");
-  if (prio && !e->pt_on) return e->fail(SACTD3_ESTATE, "step_sampled: priorities are not enabled (sactd3_prio_enable)");
-  if (sm->n_step > 1 && e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "step_sampled: rows are pinned (sactd3_rb_pin): the n-step age formula assumes one wrap point, at slot 0");
-  if (hind && !e->hs_on) return e->fail(SACTD3_ESTATE, "step_sampled: hindsight is not configured (sactd3_hindsight_configure)");
-  if (hind && e->rb_pinned > 0) return e->fail(SACTD3_ESTATE, "step_sampled: rows are pinned (sactd3_rb_pin): the chain's age formula assumes one wrap point, at slot 0");
-  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "step_sampled: buffer is empty");
-  if (mixed)
-    if (const char* why = mix_refusal(e)) { e->err = std::string("step_sampled: ") + why; return SACTD3_ESTATE; }
-  if (!prio && !mixed && !hind && sm->n_step == 1) { RCCHK(sactd3_step(e, do_actor)); ++e->ss_stats[0]; return 0; }
-  CHAIN_BREAK(e);
   const bool chain = sm->n_step > 1;
-  const int stride = chain ? sm->stride : 1;
-  if (prio || (!chain && !hind)) RCCHK(slot_weights_alloc(e));      // (the hindsight staging writes no weights: its slot carries none)
-  if (chain) RCCHK(nstep_alloc(e));
-  if (mixed || hind) RCCHK(mix_alloc(e));
-  if (hind) RCCHK(hindsight_alloc(e));
-  const int key[3] = {sm->draw, sm->n_step, stride};
+  const Draw d{sm->draw, sm->beta, chain ? sm->n_step : 0, chain ? sm->stride : 0};
+  if (const char* why = draw_state_refusal(e, d)) return state_refusal(e, "step_sampled", why);
+  if (!prio && !mixed && !hind && !chain) { RCCHK(sactd3_step(e, do_actor)); ++e->ss_stats[0]; return 0; }
+  CHAIN_BREAK(e);
+  RCCHK(draw_alloc(e, d));
   EnqCtx x{e, e->stream};      // (the eager launches in front of the graph)
-  if (memcmp(key, e->ss_key, sizeof(key)) != 0) {
-    RCCHK(drop_graphs(e, G_SAMPLED, 4));
-    memcpy(e->ss_key, key, sizeof(key));
-  }
+  if (!d.same_graphs(e->ss_draw)) RCCHK(drop_graphs(e, G_SAMPLED, 4));
+  e->ss_draw = d;
   if (prio) {
     int32_t bits;
     memcpy(&bits, &sm->beta, sizeof(bits));
@@ -3015,14 +3029,10 @@ int sactd3_step_sampled(sactd3_engine* e, int do_actor, const sactd3_sampling* s
   if (hind) RCCHK(hindsight_publish(x));      // (the draw counter as the graph's draw reads it: a launch only behind a call-form native draw)
   RCCHK(issue_iteration(e, do_actor, G_SAMPLED));
   ++e->ss_stats[0];
-  // the rest of the host state, transition by transition as the call sequence makes them
-  slot_refilled(e, prio, chain);
-  if (chain) { ++e->ns_host[0]; e->ns_host[1] += e->B; }
-  if (prio) ++e->pt_host[0];
-  if (mixed) mix_count(e);
-  if (hind) { e->slot.hindsight = true; ++e->hs_calls; ++e->hs_pub; }      // (the draw kernel advanced the device's word as well)
-  slot_trained(e, 0, false);
-  if (prio) ++e->pt_host[1];
+  // the rest of the host state: what the calls of the sequence leave, by their own routines
+  draw_issued(e, d, true);
+  update_qnets_issued(e);
+  if (prio) prio_update_issued(e);
   return 0;
 }
 int sactd3_step_sampled_stats(sactd3_engine* e, int64_t out[4]) { return host_stats(e, &sactd3_engine::ss_stats, out); }
@@ -3095,6 +3105,7 @@ static int enqueue_period_run(EnqCtx& x, int v) {
 }
 // What each learner graph holds (see run_graph): one definition for whoever captures it -- its entry point at the first use,
 // sactd3_instantiate_graphs ahead of that -- and whoever walks its sequence without a graph (use_graphs == 0, sactd3_time_nodes).
+static int enqueue_cycle(EnqCtx& x, const CycleBinding& b, bool explore, bool act, bool polyak);      // (the rollout cycle, at the end of this file)
 static int enqueue_graph(EnqCtx& x, int which) {
   sactd3_engine* e = x.e;
   IterPlace api;      // (the API path's updates: no place in a fused iteration)
@@ -3112,6 +3123,8 @@ static int enqueue_graph(EnqCtx& x, int which) {
       x.graph_form = true;
       return enqueue_step_sampled(x, ((which - G_SAMPLED) & 2) != 0, ((which - G_SAMPLED) & 1) != 0);
   }
+  if (which >= G_CYCLE && which < G_CYCLE + 8)      // + (explore ? 0 : 4) + IterSchedule::k, for the binding the engine holds
+    return enqueue_cycle(x, e->cyc, which - G_CYCLE < 4, ((which - G_CYCLE) & 2) != 0, ((which - G_CYCLE) & 1) != 0);
   return e->fail(SACTD3_EINVAL, "enqueue_graph: no such graph");
 }
 
@@ -3366,6 +3379,15 @@ static int launch_act_unpack(EnqCtx& x, float* actions, int64_t actions_ld, int 
   return 0;
 }
 
+// The acting pair on n rows of p_x was queued on the learner stream.  The call returns with its kernels still queued, and they use the
+// scratch, the draw buffer and the counter that an acting-stream call uses too: the next sactd3_predict_begin has to wait for the
+// learner stream, exactly as behind a write of the actor.  pdev_stats: {calls, rows, ordered calls, calls with a multi-block tail}.
+static void predict_device_issued(sactd3_engine* e, int n, bool ordered) {
+  e->actor_dirty = true;
+  ++e->pdev_stats[0]; e->pdev_stats[1] += n;
+  if (ordered) ++e->pdev_stats[2];
+  if (!predict_one_block(e, n)) ++e->pdev_stats[3];
+}
 // Agent.predict for observations that are ALREADY in this device's memory, actions left there: include/sactd3.h.  Four launches on
 // the learner stream -- pack, the acting pair of sactd3_predict on p_x / p_act (its own (explore, n) graph, or the eager sequence),
 // unpack -- five behind an exploring multi-block tail (the counter kernel is part of the pair); the caller's pointers travel by value
@@ -3393,12 +3415,7 @@ int sactd3_predict_device(sactd3_engine* e, const float* obs, int64_t obs_ld, in
                        [&](EnqCtx& xg) { return enqueue_predict(xg, n, explore, true); }));
   RCCHK(launch_act_unpack(x, actions, actions_ld, n));
   RCCHK(src_order_end(e, caller, flags));
-  // The call returns with its kernels still queued, and they use the scratch, the draw buffer and the counter that an acting-stream
-  // call uses too: the next sactd3_predict_begin has to wait for the learner stream, exactly as behind a write of the actor.
-  e->actor_dirty = true;
-  ++e->pdev_stats[0]; e->pdev_stats[1] += n;
-  if (flags & SACTD3_SRC_ORDERED) ++e->pdev_stats[2];
-  if (!predict_one_block(e, n)) ++e->pdev_stats[3];
+  predict_device_issued(e, n, (flags & SACTD3_SRC_ORDERED) != 0);
   return 0;
 }
 
@@ -3881,7 +3898,7 @@ static int time_td_to_field(EnqCtx& x) { return launch_td_out(x, x.e->stage_dev,
 static int time_mix_draw(EnqCtx& x) {
   if (const char* why = mix_refusal(x.e)) { x.e->err = std::string("time_kernel: ") + why; return SACTD3_ESTATE; }
   RCCHK(mix_alloc(x.e));
-  return launch_mix_draw(x);
+  return launch_mix_draw(x, x.e->rb_pinned, x.e->mix_m);
 }
 // the engine-owned priorities (SACTD3_ESTATE before sactd3_prio_enable)
 static int time_prio_refusal(sactd3_engine* e) {
@@ -3908,8 +3925,8 @@ static int time_prio_update(EnqCtx& x) {
 static int time_stage(EnqCtx& x, bool prio_sample, bool chain) {
   StageReq q{"time_kernel"};
   q.internal = true;
-  if (prio_sample) { RCCHK(time_prio_refusal(x.e)); q.draw = DRAW_PRIO; q.beta = 0.4f; q.weighted = true; }
-  else { q.idx = x.e->time_idx; q.n = x.e->B; }
+  if (prio_sample) { RCCHK(time_prio_refusal(x.e)); q.kind = SACTD3_DRAW_PRIORITIZED; q.beta = 0.4f; }
+  else { q.callers = true; q.rows.idx = x.e->time_idx; q.n = x.e->B; }
   if (chain) { q.chain = true; q.steps = 3; q.stride = 1; }
   return stage_ring_rows(x, q);
 }
@@ -4078,23 +4095,14 @@ static int launch_ingest_g(EnqCtx& x, const float* records, int n) {
   if (he == hipSuccess && !g.publish) he = rb_publish_g_launch(g, x.s);
   return he == hipSuccess ? 0 : e->fail(SACTD3_EHIP, "rollout cycle: k_rb_ingest_g", he);
 }
-static int enqueue_cycle(EnqCtx& x, const CycleBinding& b, int explore, const IterSchedule& s) {
+static int enqueue_cycle(EnqCtx& x, const CycleBinding& b, bool explore, bool act, bool polyak) {
   sactd3_engine* e = x.e;
   if (const int he = b.env_step(b.ctx, x.s)) return e->fail(SACTD3_EHIP, "rollout cycle: k_env_step_rec", (hipError_t)he);
   RCCHK(launch_ingest_g(x, b.records, b.n));
   RCCHK(launch_obs_pack(x, b.obs, b.obs_ld, e->p_x, b.n));
-  RCCHK(enqueue_predict(x, b.n, explore, true));
+  RCCHK(enqueue_predict(x, b.n, explore ? 1 : 0, true));
   RCCHK(launch_act_unpack(x, b.actions, b.actions_ld, b.n));
-  return enqueue_step(x, single_iteration(s.act, s.polyak));
-}
-static int drop_cycle_graphs(sactd3_engine* e) {
-  hipGraphExec_t* g = e->cyc_graphs;
-  if (std::count(g, g + 8, nullptr) < 8) HIPCHK(hipStreamSynchronize(e->stream));      // (not under its own replay)
-  for (int i = 0; i < 8; ++i) {
-    if (g[i]) hipGraphExecDestroy(g[i]);
-    g[i] = nullptr; e->cyc_nodes[i] = 0;
-  }
-  return 0;
+  return enqueue_step(x, single_iteration(act, polyak));
 }
 
 int engine_rollout_cycle(sactd3_engine* e, const CycleBinding& b, int explore, int do_actor) {
@@ -4107,44 +4115,30 @@ int engine_rollout_cycle(sactd3_engine* e, const CycleBinding& b, int explore, i
   if (e->pt_on) return e->fail(SACTD3_ESTATE, "rollout_cycle: priorities are enabled (sactd3_prio_enable): the append would owe their launches");
   if (e->act_inflight) return e->fail(SACTD3_ESTATE, "rollout_cycle: an acting call is in flight (sactd3_predict_end first)");
   USE_DEVICE(e);
-  if (e->cyc_owner != b.owner) {      // the nodes hold the other binding's buffers
-    RCCHK(drop_cycle_graphs(e));
-    e->cyc_owner = b.owner;
-  }
+  if (e->cyc.owner != b.owner) RCCHK(drop_graphs(e, G_CYCLE, 8));      // the nodes hold the other binding's buffers
+  e->cyc = b;      // (a dozen words, every call: the sequence is always enqueued from the binding of the call that asks for it)
   RCCHK(first_use_alloc(e, &e->cyc_ctr, 4));      // (in front of the capture: first_use_alloc)
-  explore = explore ? 1 : 0;
-  const IterSchedule s = iteration_schedule(e, do_actor, e->qnet_updates + 1);
-  const int id = (explore ? 0 : 4) + s.k;
-  auto sequence = [&](EnqCtx& x) { return enqueue_cycle(x, b, explore, s); };
-  const bool had = e->cyc_graphs[id] != nullptr;
-  RCCHK(run_graph_slot(e, &e->cyc_graphs[id], &e->cyc_nodes[id], sequence, false));      // capture at the first use; nothing is launched yet
-  if (!had && e->cyc_graphs[id]) ++b.stats[1];
+  const int first = G_CYCLE + (explore ? 0 : 4), id = first + iteration_schedule(e, do_actor, e->qnet_updates + 1).k;
+  RCCHK(run_graph(e, id, false));      // capture at the first use (counted in b.stats[1]); nothing is launched yet
   // The rollout's stream around the cycle, once (the pair of SACTD3_SRC_ORDERED): the cycle behind what that stream holds -- a reset, a
   // write of the buffers -- and whatever that stream is given next -- env calls, reads of the buffers -- behind the cycle.
   RCCHK(src_order_begin(e, b.stream, SACTD3_SRC_ORDERED));
-  // the host state, transition by transition as the three calls make them
-  CHAIN_BREAK(e);                                     // sactd3_rb_extend_records_device
+  CHAIN_BREAK(e);                                     // the host state of the three calls, by their own routines: sactd3_rb_extend_records_device
   (void)ring_append(e, b.n);                          // ... rb_len, the cursor, rb_wrapped
-  e->actor_dirty = true;                              // sactd3_predict_device: its kernels use the acting scratch, draw buffer and counter
-  ++e->pdev_stats[0]; e->pdev_stats[1] += b.n; ++e->pdev_stats[2];
-  if (!predict_one_block(e, b.n)) ++e->pdev_stats[3];
-  if (s.act) RCCHK(actor_write_begin(e));             // sactd3_step (issue_iteration)
-  RCCHK(run_graph_slot(e, &e->cyc_graphs[id], &e->cyc_nodes[id], sequence, true));      // THE launch (use_graphs == 0: the sequence itself)
-  ++e->qnet_updates;
-  e->grads_stale[0] = false;
-  if (s.act) e->grads_stale[1] = false;
+  predict_device_issued(e, b.n, true);                // sactd3_predict_device
+  RCCHK(issue_iteration(e, do_actor, first));         // sactd3_step: THE launch of graph `id` (use_graphs == 0: the sequence itself)
   slot_trained(e, 0, true);
   RCCHK(src_order_end(e, b.stream, SACTD3_SRC_ORDERED));
   ++b.stats[0];
-  b.stats[2] = e->cyc_nodes[id];
+  b.stats[2] = e->graph_nodes[id];
   if (!e->cfg.use_graphs) ++b.stats[3];
   return 0;
 }
 
 void engine_rollout_cycle_release(sactd3_engine* e, const void* owner) {
-  if (!e || e->cyc_owner != owner) return;
-  if (hipSetDevice(e->cfg.device_id) == hipSuccess) (void)drop_cycle_graphs(e);
-  e->cyc_owner = nullptr;
+  if (!e || e->cyc.owner != owner) return;
+  if (hipSetDevice(e->cfg.device_id) == hipSuccess) (void)drop_graphs(e, G_CYCLE, 8);
+  e->cyc = CycleBinding{};
 }
 
 int engine_rollout_cycle_clamped(sactd3_engine* e, int64_t* out) {
