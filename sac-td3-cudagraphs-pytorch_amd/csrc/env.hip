@@ -2,12 +2,15 @@
 // A translation unit of its own inside libsactd3_hip.so: it shares philox.h with engine.hip and nothing else.
 // Behind it, the host side of include/sactd3_rollout.h: the record-emitting env step and the rollout handle, which reaches the
 // engine through its public ABI (include/sactd3.h) only -- and, for sactd3_rollout_cycle alone, through the one entry of rollout_cycle.h.
+// Two things are written once for all of it: guarded(), the C boundary of every entry point, and with_kind(), the way from a handle's
+// run-time kind to the task table and the kernel instances of env_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sactd3.h"
@@ -17,6 +20,27 @@
 #include "rollout_cycle.h"
 
 #define ENV_API extern "C" __attribute__((visibility("default")))
+
+// The C boundary: no exception crosses it (the error texts are std::strings, the getters stage in std::vectors: std::bad_alloc).
+// Every entry point that can throw is `return guarded([&]() -> int { ... });`
+template <class F>
+static int guarded(F&& body) {
+  try {
+    return body();
+  } catch (...) {
+    return SACTD3_EHIP;
+  }
+}
+
+// The run-time kind as a compile-time one: f(std::integral_constant<int, KIND>) -> f's result.  The only switch over the tasks here.
+template <class F>
+static auto with_kind(int kind, F&& f) {
+  switch (kind) {
+    case SACTD3_ENV_PENDULUM: return f(std::integral_constant<int, ENV_PENDULUM>{});
+    case SACTD3_ENV_CARTPOLE: return f(std::integral_constant<int, ENV_CARTPOLE>{});
+    default: return f(std::integral_constant<int, ENV_POINTGOAL>{});
+  }
+}
 
 static thread_local std::string g_env_create_error;
 
@@ -41,31 +65,26 @@ struct sactd3_env {
   } while (0)
 
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline unsigned env_blocks(int n) { return (unsigned)((n + 255) / 256); }
+static inline dim3 env_grid(const sactd3_env* e) { return dim3((unsigned)((e->d.n + 255) / 256)); }
+
+// The per-env arrays of `d` for n envs, each named once, every one on a 256-byte boundary: -> the bytes they take together; with
+// `base` they are placed there, in this order (phys stays component-major: tools/ and the state getters rely on it).
+static size_t env_place(EnvDev& d, size_t n, char* base) {
+  size_t off = 0;
+  auto take = [&](auto*& p, size_t count) {
+    if (base) p = (std::remove_reference_t<decltype(p)>)(base + off);
+    off += up256(count * sizeof(*p));
+  };
+  take(d.phys, 4 * n); take(d.steps, n); take(d.episode, n); take(d.ret, n); take(d.draws, n); take(d.done_count, n); take(d.ret_sum, n);
+  take(d.len_sum, n); take(d.last_ret, n); take(d.last_len, n); take(d.first_ret, n); take(d.first_len, n); take(d.bad, n);
+  return off;
+}
 
 static int env_alloc(sactd3_env* e) {
-  const size_t n = (size_t)e->cfg.num_envs;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
-  const size_t phys = take(4 * n * 4), steps = take(n * 4), episode = take(n * 4), ret = take(n * 4), draws = take(n * 4),
-               done_count = take(n * 4), ret_sum = take(n * 8), len_sum = take(n * 8), last_ret = take(n * 4), last_len = take(n * 4),
-               first_ret = take(n * 4), first_len = take(n * 4), bad = take(n * 4);
-  ENV_HIP(e, hipMalloc(&e->mem, off));
-  ENV_HIP(e, hipMemset(e->mem, 0, off));
-  char* base = (char*)e->mem;
-  e->d.phys = (float*)(base + phys);
-  e->d.steps = (int32_t*)(base + steps);
-  e->d.episode = (uint32_t*)(base + episode);
-  e->d.ret = (float*)(base + ret);
-  e->d.draws = (uint32_t*)(base + draws);
-  e->d.done_count = (uint32_t*)(base + done_count);
-  e->d.ret_sum = (double*)(base + ret_sum);
-  e->d.len_sum = (unsigned long long*)(base + len_sum);
-  e->d.last_ret = (float*)(base + last_ret);
-  e->d.last_len = (int32_t*)(base + last_len);
-  e->d.first_ret = (float*)(base + first_ret);
-  e->d.first_len = (int32_t*)(base + first_len);
-  e->d.bad = (uint32_t*)(base + bad);
+  const size_t n = (size_t)e->cfg.num_envs, bytes = env_place(e->d, n, nullptr);
+  ENV_HIP(e, hipMalloc(&e->mem, bytes));
+  ENV_HIP(e, hipMemset(e->mem, 0, bytes));
+  env_place(e->d, n, (char*)e->mem);
   e->d.n = (int)n;
   return SACTD3_OK;
 }
@@ -75,19 +94,11 @@ static int env_init(sactd3_env* e, const sactd3_env_config* cfg) {
   if (cfg->kind < 0 || cfg->kind >= SACTD3_ENV_NUM_KINDS) return e->fail(SACTD3_EINVAL, "kind must be SACTD3_ENV_PENDULUM, SACTD3_ENV_CARTPOLE or SACTD3_ENV_POINTGOAL");
   if (cfg->num_envs < 1 || cfg->num_envs > (1 << 24)) return e->fail(SACTD3_EINVAL, "num_envs must be in [1, 2^24]");
   if (cfg->horizon < 0) return e->fail(SACTD3_EINVAL, "horizon must be >= 0 (0: the task's default)");
-  int default_horizon = 200;
-  switch (cfg->kind) {
-    case SACTD3_ENV_PENDULUM:
-      e->info.ob_dim = EnvTask<ENV_PENDULUM>::OB; e->info.ac_dim = EnvTask<ENV_PENDULUM>::AC; e->info.max_ac = EnvTask<ENV_PENDULUM>::BOUND;
-      break;
-    case SACTD3_ENV_CARTPOLE:
-      e->info.ob_dim = EnvTask<ENV_CARTPOLE>::OB; e->info.ac_dim = EnvTask<ENV_CARTPOLE>::AC; e->info.max_ac = EnvTask<ENV_CARTPOLE>::BOUND;
-      break;
-    default:
-      e->info.ob_dim = EnvTask<ENV_POINTGOAL>::OB; e->info.ac_dim = EnvTask<ENV_POINTGOAL>::AC; e->info.max_ac = EnvTask<ENV_POINTGOAL>::BOUND;
-      default_horizon = 50;
-  }
-  e->info.horizon = cfg->horizon ? cfg->horizon : default_horizon;
+  with_kind(cfg->kind, [&](auto K) {
+    using T = EnvTask<decltype(K)::value>;
+    e->info.ob_dim = T::OB; e->info.ac_dim = T::AC; e->info.max_ac = T::BOUND;
+    e->info.horizon = cfg->horizon ? cfg->horizon : T::HORIZON;
+  });
   e->info.num_envs = cfg->num_envs;
   e->info.min_ac = -e->info.max_ac;
   int ndev = 0;
@@ -101,40 +112,31 @@ static int env_init(sactd3_env* e, const sactd3_env_config* cfg) {
   return env_alloc(e);
 }
 
-static int env_create_body(const sactd3_env_config* cfg, sactd3_env** out);
 ENV_API int sactd3_env_create(const sactd3_env_config* cfg, sactd3_env** out) {
-  try {
-    return env_create_body(cfg, out);
-  } catch (...) {      // (the error text is a std::string)
-    return SACTD3_EHIP;
-  }
-}
-
-static int env_create_body(const sactd3_env_config* cfg, sactd3_env** out) {
-  if (out) *out = nullptr;
-  if (!cfg || !out) {
-    g_env_create_error = "sactd3_env_create: NULL argument";
-    return SACTD3_EINVAL;
-  }
-  sactd3_env* e = new (std::nothrow) sactd3_env();
-  if (!e) {
-    g_env_create_error = "sactd3_env_create: out of host memory";
-    return SACTD3_EHIP;
-  }
-  int rc;
-  try {
-    rc = env_init(e, cfg);
-    if (rc != SACTD3_OK) g_env_create_error = e->err;
-  } catch (...) {      // (nothing is leaked on the way out)
-    rc = SACTD3_EHIP;
-  }
-  if (rc != SACTD3_OK) {
-    if (e->mem) (void)hipFree(e->mem);
-    delete e;
-    return rc;
-  }
-  *out = e;
-  return SACTD3_OK;
+  return guarded([&]() -> int {
+    if (out) *out = nullptr;
+    if (!cfg || !out) {
+      g_env_create_error = "sactd3_env_create: NULL argument";
+      return SACTD3_EINVAL;
+    }
+    sactd3_env* e = new (std::nothrow) sactd3_env();
+    if (!e) {
+      g_env_create_error = "sactd3_env_create: out of host memory";
+      return SACTD3_EHIP;
+    }
+    const int rc = guarded([&]() -> int {      // (of its own: nothing is leaked on the way out)
+      const int rc = env_init(e, cfg);
+      if (rc != SACTD3_OK) g_env_create_error = e->err;
+      return rc;
+    });
+    if (rc != SACTD3_OK) {
+      if (e->mem) (void)hipFree(e->mem);
+      delete e;
+      return rc;
+    }
+    *out = e;
+    return SACTD3_OK;
+  });
 }
 
 ENV_API void sactd3_env_destroy(sactd3_env* e) {
@@ -154,89 +156,58 @@ ENV_API int sactd3_env_spec(const sactd3_env* e, sactd3_env_info* out) {
   return SACTD3_OK;
 }
 
-static int env_reset_body(sactd3_env* e, uint64_t seed, float* obs, int64_t obs_ld, void* stream);
 ENV_API int sactd3_env_reset(sactd3_env* e, uint64_t seed, float* obs, int64_t obs_ld, void* stream) {
-  try {
-    return env_reset_body(e, seed, obs, obs_ld, stream);
-  } catch (...) {      // (the error text is a std::string)
-    return SACTD3_EHIP;
-  }
+  return guarded([&]() -> int {
+    if (!e) return SACTD3_EINVAL;
+    if (obs && obs_ld < e->info.ob_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_reset: obs_ld is below ob_dim");
+    ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+    e->cfg.seed = seed;
+    with_kind(e->cfg.kind, [&](auto K) {
+      hipLaunchKernelGGL(k_env_reset<decltype(K)::value>, env_grid(e), dim3(256), 0, (hipStream_t)stream, e->d, obs, (long long)obs_ld, seed);
+    });
+    ENV_HIP(e, hipGetLastError());
+    return SACTD3_OK;
+  });
 }
 
-static int env_reset_body(sactd3_env* e, uint64_t seed, float* obs, int64_t obs_ld, void* stream) {
-  if (!e) return SACTD3_EINVAL;
-  if (obs && obs_ld < e->info.ob_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_reset: obs_ld is below ob_dim");
-  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
-  e->cfg.seed = seed;
-  hipStream_t st = (hipStream_t)stream;
-  if (e->cfg.kind == SACTD3_ENV_PENDULUM)
-    hipLaunchKernelGGL(k_env_reset<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, obs, (long long)obs_ld, seed);
-  else if (e->cfg.kind == SACTD3_ENV_CARTPOLE)
-    hipLaunchKernelGGL(k_env_reset<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, obs, (long long)obs_ld, seed);
-  else
-    hipLaunchKernelGGL(k_env_reset<ENV_POINTGOAL>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, obs, (long long)obs_ld, seed);
-  ENV_HIP(e, hipGetLastError());
-  return SACTD3_OK;
-}
-
-static int env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_env_out* out, void* stream);
 ENV_API int sactd3_env_step(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_env_out* out, void* stream) {
-  try {
-    return env_step_body(e, actions, act_ld, out, stream);
-  } catch (...) {      // (the error text is a std::string)
-    return SACTD3_EHIP;
-  }
+  return guarded([&]() -> int {
+    if (!e) return SACTD3_EINVAL;
+    if (!actions || !out || !out->obs) return e->fail(SACTD3_EINVAL, "sactd3_env_step: actions, out and out->obs must not be NULL");
+    const int o = e->info.ob_dim;
+    if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_step: act_ld is below ac_dim");
+    if (out->obs_ld < o || (out->final_obs && out->final_obs_ld < o)) return e->fail(SACTD3_EINVAL, "sactd3_env_step: an observation stride is below ob_dim");
+    if ((out->reward && out->reward_ld < 1) || (out->terminated && out->terminated_ld < 1) || (out->truncated && out->truncated_ld < 1) ||
+        (out->ended && out->ended_ld < 1))
+      return e->fail(SACTD3_EINVAL, "sactd3_env_step: a per-env output needs a stride of at least 1");
+    ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+    EnvOut k;
+    k.obs = out->obs; k.obs_ld = out->obs_ld;
+    k.final_obs = out->final_obs; k.final_obs_ld = out->final_obs_ld;
+    k.reward = out->reward; k.reward_ld = out->reward_ld;
+    k.terminated = out->terminated; k.terminated_ld = out->terminated_ld;
+    k.truncated = out->truncated; k.truncated_ld = out->truncated_ld;
+    k.ended = out->ended; k.ended_ld = out->ended_ld;
+    with_kind(e->cfg.kind, [&](auto K) {
+      hipLaunchKernelGGL(k_env_step<decltype(K)::value>, env_grid(e), dim3(256), 0, (hipStream_t)stream, e->d, actions, (long long)act_ld, k,
+                         e->info.horizon, e->cfg.seed);
+    });
+    ENV_HIP(e, hipGetLastError());
+    return SACTD3_OK;
+  });
 }
 
-static int env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_env_out* out, void* stream) {
-  if (!e) return SACTD3_EINVAL;
-  if (!actions || !out || !out->obs) return e->fail(SACTD3_EINVAL, "sactd3_env_step: actions, out and out->obs must not be NULL");
-  const int o = e->info.ob_dim;
-  if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_step: act_ld is below ac_dim");
-  if (out->obs_ld < o || (out->final_obs && out->final_obs_ld < o)) return e->fail(SACTD3_EINVAL, "sactd3_env_step: an observation stride is below ob_dim");
-  if ((out->reward && out->reward_ld < 1) || (out->terminated && out->terminated_ld < 1) || (out->truncated && out->truncated_ld < 1) ||
-      (out->ended && out->ended_ld < 1))
-    return e->fail(SACTD3_EINVAL, "sactd3_env_step: a per-env output needs a stride of at least 1");
-  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
-  EnvOut k;
-  k.obs = out->obs; k.obs_ld = out->obs_ld;
-  k.final_obs = out->final_obs; k.final_obs_ld = out->final_obs_ld;
-  k.reward = out->reward; k.reward_ld = out->reward_ld;
-  k.terminated = out->terminated; k.terminated_ld = out->terminated_ld;
-  k.truncated = out->truncated; k.truncated_ld = out->truncated_ld;
-  k.ended = out->ended; k.ended_ld = out->ended_ld;
-  hipStream_t st = (hipStream_t)stream;
-  if (e->cfg.kind == SACTD3_ENV_PENDULUM)
-    hipLaunchKernelGGL(k_env_step<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, e->info.horizon,
-                       e->cfg.seed);
-  else if (e->cfg.kind == SACTD3_ENV_CARTPOLE)
-    hipLaunchKernelGGL(k_env_step<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, e->info.horizon,
-                       e->cfg.seed);
-  else
-    hipLaunchKernelGGL(k_env_step<ENV_POINTGOAL>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, e->info.horizon,
-                       e->cfg.seed);
-  ENV_HIP(e, hipGetLastError());
-  return SACTD3_OK;
-}
-
-static int env_sample_actions_body(sactd3_env* e, float* actions, int64_t act_ld, void* stream);
 ENV_API int sactd3_env_sample_actions(sactd3_env* e, float* actions, int64_t act_ld, void* stream) {
-  try {
-    return env_sample_actions_body(e, actions, act_ld, stream);
-  } catch (...) {      // (the error text is a std::string)
-    return SACTD3_EHIP;
-  }
-}
-
-static int env_sample_actions_body(sactd3_env* e, float* actions, int64_t act_ld, void* stream) {
-  if (!e) return SACTD3_EINVAL;
-  if (!actions) return e->fail(SACTD3_EINVAL, "sactd3_env_sample_actions: actions must not be NULL");
-  if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_sample_actions: act_ld is below ac_dim");
-  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
-  hipLaunchKernelGGL(k_env_sample_actions, dim3(env_blocks(e->d.n)), dim3(256), 0, (hipStream_t)stream, e->d, actions, (long long)act_ld,
-                     e->info.ac_dim, e->info.min_ac, e->info.max_ac - e->info.min_ac, e->cfg.seed);
-  ENV_HIP(e, hipGetLastError());
-  return SACTD3_OK;
+  return guarded([&]() -> int {
+    if (!e) return SACTD3_EINVAL;
+    if (!actions) return e->fail(SACTD3_EINVAL, "sactd3_env_sample_actions: actions must not be NULL");
+    if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_env_sample_actions: act_ld is below ac_dim");
+    ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+    hipLaunchKernelGGL(k_env_sample_actions, env_grid(e), dim3(256), 0, (hipStream_t)stream, e->d, actions, (long long)act_ld, e->info.ac_dim,
+                       e->info.min_ac, e->info.max_ac - e->info.min_ac, e->cfg.seed);
+    ENV_HIP(e, hipGetLastError());
+    return SACTD3_OK;
+  });
 }
 
 // device -> host of one per-env array, behind what the stream has queued
@@ -247,112 +218,91 @@ static int env_pull(sactd3_env* e, std::vector<T>& host, const T* dev, size_t co
   return SACTD3_OK;
 }
 
-static int env_episode_stats_body(sactd3_env* e, sactd3_env_stats* out, void* stream);
 ENV_API int sactd3_env_episode_stats(sactd3_env* e, sactd3_env_stats* out, void* stream) {
-  try {
-    return env_episode_stats_body(e, out, stream);
-  } catch (...) {      // (the host staging vectors, the error text: std::bad_alloc never crosses the C boundary)
-    return SACTD3_EHIP;
-  }
+  return guarded([&]() -> int {
+    if (!e) return SACTD3_EINVAL;
+    if (!out) return e->fail(SACTD3_EINVAL, "sactd3_env_episode_stats: out must not be NULL");
+    ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)e->d.n;
+    std::vector<uint32_t> done, bad;
+    std::vector<double> rs;
+    std::vector<unsigned long long> ls;
+    std::vector<float> lr, fr;
+    std::vector<int32_t> ll, fl;
+    int rc;
+    if ((rc = env_pull(e, done, e->d.done_count, n, st)) || (rc = env_pull(e, bad, e->d.bad, n, st)) || (rc = env_pull(e, rs, e->d.ret_sum, n, st)) ||
+        (rc = env_pull(e, ls, e->d.len_sum, n, st)) || (rc = env_pull(e, lr, e->d.last_ret, n, st)) || (rc = env_pull(e, ll, e->d.last_len, n, st)) ||
+        (rc = env_pull(e, fr, e->d.first_ret, n, st)) || (rc = env_pull(e, fl, e->d.first_len, n, st)))
+      return rc;
+    ENV_HIP(e, hipStreamSynchronize(st));
+    out->episodes = 0; out->return_sum = 0.0; out->length_sum = 0; out->bad_actions = 0;
+    for (size_t i = 0; i < n; ++i) {      // the only sums over envs, in env order, on the host
+      out->episodes += done[i];
+      out->return_sum += rs[i];
+      out->length_sum += (int64_t)ls[i];
+      out->bad_actions += bad[i];
+      if (out->last_return) out->last_return[i] = lr[i];
+      if (out->last_length) out->last_length[i] = ll[i];
+      if (out->env_episodes) out->env_episodes[i] = done[i];
+      if (out->first_return) out->first_return[i] = fr[i];
+      if (out->first_length) out->first_length[i] = fl[i];
+    }
+    return SACTD3_OK;
+  });
 }
 
-static int env_episode_stats_body(sactd3_env* e, sactd3_env_stats* out, void* stream) {
-  if (!e) return SACTD3_EINVAL;
-  if (!out) return e->fail(SACTD3_EINVAL, "sactd3_env_episode_stats: out must not be NULL");
-  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t n = (size_t)e->d.n;
-  std::vector<uint32_t> done, bad;
-  std::vector<double> rs;
-  std::vector<unsigned long long> ls;
-  std::vector<float> lr, fr;
-  std::vector<int32_t> ll, fl;
-  int rc;
-  if ((rc = env_pull(e, done, e->d.done_count, n, st)) || (rc = env_pull(e, bad, e->d.bad, n, st)) || (rc = env_pull(e, rs, e->d.ret_sum, n, st)) ||
-      (rc = env_pull(e, ls, e->d.len_sum, n, st)) || (rc = env_pull(e, lr, e->d.last_ret, n, st)) || (rc = env_pull(e, ll, e->d.last_len, n, st)) ||
-      (rc = env_pull(e, fr, e->d.first_ret, n, st)) || (rc = env_pull(e, fl, e->d.first_len, n, st)))
-    return rc;
-  ENV_HIP(e, hipStreamSynchronize(st));
-  out->episodes = 0; out->return_sum = 0.0; out->length_sum = 0; out->bad_actions = 0;
-  for (size_t i = 0; i < n; ++i) {      // the only sums over envs, in env order, on the host
-    out->episodes += done[i];
-    out->return_sum += rs[i];
-    out->length_sum += (int64_t)ls[i];
-    out->bad_actions += bad[i];
-    if (out->last_return) out->last_return[i] = lr[i];
-    if (out->last_length) out->last_length[i] = ll[i];
-    if (out->env_episodes) out->env_episodes[i] = done[i];
-    if (out->first_return) out->first_return[i] = fr[i];
-    if (out->first_length) out->first_length[i] = fl[i];
-  }
-  return SACTD3_OK;
-}
-
-static int env_get_state_body(sactd3_env* e, const sactd3_env_state* out, void* stream);
 ENV_API int sactd3_env_get_state(sactd3_env* e, const sactd3_env_state* out, void* stream) {
-  try {
-    return env_get_state_body(e, out, stream);
-  } catch (...) {      // (the host staging vectors, the error text: std::bad_alloc never crosses the C boundary)
-    return SACTD3_EHIP;
-  }
+  return guarded([&]() -> int {
+    if (!e) return SACTD3_EINVAL;
+    if (!out) return e->fail(SACTD3_EINVAL, "sactd3_env_get_state: out must not be NULL");
+    ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)e->d.n;
+    std::vector<float> phys;
+    if (out->phys) {
+      const int rc = env_pull(e, phys, e->d.phys, 4 * n, st);
+      if (rc) return rc;
+    }
+    if (out->steps) ENV_HIP(e, hipMemcpyAsync(out->steps, e->d.steps, n * 4, hipMemcpyDeviceToHost, st));
+    if (out->episode) ENV_HIP(e, hipMemcpyAsync(out->episode, e->d.episode, n * 4, hipMemcpyDeviceToHost, st));
+    if (out->returns) ENV_HIP(e, hipMemcpyAsync(out->returns, e->d.ret, n * 4, hipMemcpyDeviceToHost, st));
+    if (out->draws) ENV_HIP(e, hipMemcpyAsync(out->draws, e->d.draws, n * 4, hipMemcpyDeviceToHost, st));
+    ENV_HIP(e, hipStreamSynchronize(st));
+    if (out->phys)
+      for (size_t i = 0; i < n; ++i)
+        for (int j = 0; j < 4; ++j) out->phys[i * 4 + j] = phys[j * n + i];      // component-major on the device, env-major for the caller
+    return SACTD3_OK;
+  });
 }
 
-static int env_get_state_body(sactd3_env* e, const sactd3_env_state* out, void* stream) {
-  if (!e) return SACTD3_EINVAL;
-  if (!out) return e->fail(SACTD3_EINVAL, "sactd3_env_get_state: out must not be NULL");
-  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t n = (size_t)e->d.n;
-  std::vector<float> phys;
-  if (out->phys) {
-    const int rc = env_pull(e, phys, e->d.phys, 4 * n, st);
-    if (rc) return rc;
-  }
-  if (out->steps) ENV_HIP(e, hipMemcpyAsync(out->steps, e->d.steps, n * 4, hipMemcpyDeviceToHost, st));
-  if (out->episode) ENV_HIP(e, hipMemcpyAsync(out->episode, e->d.episode, n * 4, hipMemcpyDeviceToHost, st));
-  if (out->returns) ENV_HIP(e, hipMemcpyAsync(out->returns, e->d.ret, n * 4, hipMemcpyDeviceToHost, st));
-  if (out->draws) ENV_HIP(e, hipMemcpyAsync(out->draws, e->d.draws, n * 4, hipMemcpyDeviceToHost, st));
-  ENV_HIP(e, hipStreamSynchronize(st));
-  if (out->phys)
-    for (size_t i = 0; i < n; ++i)
-      for (int j = 0; j < 4; ++j) out->phys[i * 4 + j] = phys[j * n + i];      // component-major on the device, env-major for the caller
-  return SACTD3_OK;
-}
-
-static int env_set_state_body(sactd3_env* e, const sactd3_env_state* in, void* stream);
 ENV_API int sactd3_env_set_state(sactd3_env* e, const sactd3_env_state* in, void* stream) {
-  try {
-    return env_set_state_body(e, in, stream);
-  } catch (...) {      // (the host staging vectors, the error text: std::bad_alloc never crosses the C boundary)
-    return SACTD3_EHIP;
-  }
-}
-
-static int env_set_state_body(sactd3_env* e, const sactd3_env_state* in, void* stream) {
-  if (!e) return SACTD3_EINVAL;
-  if (!in) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: in must not be NULL");
-  const size_t n = (size_t)e->d.n;
-  if (in->phys)
-    for (size_t k = 0; k < 4 * n; ++k)
-      if (!std::isfinite(in->phys[k])) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: a physical state is not finite");
-  if (in->steps)
-    for (size_t i = 0; i < n; ++i)
-      if (in->steps[i] < 0) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: a step count is negative");
-  ENV_HIP(e, hipSetDevice(e->cfg.device_id));
-  hipStream_t st = (hipStream_t)stream;
-  std::vector<float> phys;
-  if (in->phys) {
-    phys.resize(4 * n);
-    for (size_t i = 0; i < n; ++i)
-      for (int j = 0; j < 4; ++j) phys[j * n + i] = in->phys[i * 4 + j];
-    ENV_HIP(e, hipMemcpyAsync(e->d.phys, phys.data(), 4 * n * 4, hipMemcpyHostToDevice, st));
-  }
-  if (in->steps) ENV_HIP(e, hipMemcpyAsync(e->d.steps, in->steps, n * 4, hipMemcpyHostToDevice, st));
-  if (in->episode) ENV_HIP(e, hipMemcpyAsync(e->d.episode, in->episode, n * 4, hipMemcpyHostToDevice, st));
-  if (in->returns) ENV_HIP(e, hipMemcpyAsync(e->d.ret, in->returns, n * 4, hipMemcpyHostToDevice, st));
-  if (in->draws) ENV_HIP(e, hipMemcpyAsync(e->d.draws, in->draws, n * 4, hipMemcpyHostToDevice, st));
-  ENV_HIP(e, hipStreamSynchronize(st));      // the host arrays (and `phys` above) are free again when the call returns
-  return SACTD3_OK;
+  return guarded([&]() -> int {
+    if (!e) return SACTD3_EINVAL;
+    if (!in) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: in must not be NULL");
+    const size_t n = (size_t)e->d.n;
+    if (in->phys)
+      for (size_t k = 0; k < 4 * n; ++k)
+        if (!std::isfinite(in->phys[k])) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: a physical state is not finite");
+    if (in->steps)
+      for (size_t i = 0; i < n; ++i)
+        if (in->steps[i] < 0) return e->fail(SACTD3_EINVAL, "sactd3_env_set_state: a step count is negative");
+    ENV_HIP(e, hipSetDevice(e->cfg.device_id));
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float> phys;
+    if (in->phys) {
+      phys.resize(4 * n);
+      for (size_t i = 0; i < n; ++i)
+        for (int j = 0; j < 4; ++j) phys[j * n + i] = in->phys[i * 4 + j];
+      ENV_HIP(e, hipMemcpyAsync(e->d.phys, phys.data(), 4 * n * 4, hipMemcpyHostToDevice, st));
+    }
+    if (in->steps) ENV_HIP(e, hipMemcpyAsync(e->d.steps, in->steps, n * 4, hipMemcpyHostToDevice, st));
+    if (in->episode) ENV_HIP(e, hipMemcpyAsync(e->d.episode, in->episode, n * 4, hipMemcpyHostToDevice, st));
+    if (in->returns) ENV_HIP(e, hipMemcpyAsync(e->d.ret, in->returns, n * 4, hipMemcpyHostToDevice, st));
+    if (in->draws) ENV_HIP(e, hipMemcpyAsync(e->d.draws, in->draws, n * 4, hipMemcpyHostToDevice, st));
+    ENV_HIP(e, hipStreamSynchronize(st));      // the host arrays (and `phys` above) are free again when the call returns
+    return SACTD3_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------- include/sactd3_rollout.h
@@ -382,15 +332,10 @@ static const char* layout_refusal(const sactd3_record_layout* L, int o, int a) {
 static hipError_t issue_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
                                  int64_t obs_ld, hipStream_t st) {
   const EnvRec k{L->record_len, L->next_off, L->next_width};
-  if (e->cfg.kind == SACTD3_ENV_PENDULUM)
-    hipLaunchKernelGGL(k_env_step_rec<ENV_PENDULUM>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
+  with_kind(e->cfg.kind, [&](auto K) {
+    hipLaunchKernelGGL(k_env_step_rec<decltype(K)::value>, env_grid(e), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
                        (long long)obs_ld, e->info.horizon, e->cfg.seed);
-  else if (e->cfg.kind == SACTD3_ENV_CARTPOLE)
-    hipLaunchKernelGGL(k_env_step_rec<ENV_CARTPOLE>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
-                       (long long)obs_ld, e->info.horizon, e->cfg.seed);
-  else
-    hipLaunchKernelGGL(k_env_step_rec<ENV_POINTGOAL>, dim3(env_blocks(e->d.n)), dim3(256), 0, st, e->d, actions, (long long)act_ld, k, records, obs,
-                       (long long)obs_ld, e->info.horizon, e->cfg.seed);
+  });
   return hipGetLastError();
 }
 static int launch_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
@@ -400,28 +345,24 @@ static int launch_step_rec(sactd3_env* e, const float* actions, int64_t act_ld, 
   return SACTD3_OK;
 }
 
-static int rollout_env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
-                                 int64_t obs_ld, void* stream);
 ENV_API int sactd3_rollout_env_step(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records,
                                     float* obs, int64_t obs_ld, void* stream) {
-  try {
-    return rollout_env_step_body(e, actions, act_ld, L, records, obs, obs_ld, stream);
-  } catch (...) {      // (the error text is a std::string)
-    return SACTD3_EHIP;
-  }
+  return guarded([&]() -> int {
+    if (!e) return SACTD3_EINVAL;
+    if (!actions || !L || !records || !obs) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: actions, layout, records and obs must not be NULL");
+    if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: act_ld is below ac_dim");
+    if (obs_ld < e->info.ob_dim) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: obs_ld is below ob_dim");
+    if (const char* why = layout_refusal(L, e->info.ob_dim, e->info.ac_dim)) return e->fail(SACTD3_EINVAL, (std::string("sactd3_rollout_env_step: ") + why).c_str());
+    if ((uintptr_t)records % 16) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: `records` is not 16-byte aligned");
+    if (!on_device(records, e->cfg.device_id)) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: `records` is not device memory of the env's device");
+    return launch_step_rec(e, actions, act_ld, L, records, obs, obs_ld, (hipStream_t)stream);
+  });
 }
 
-static int rollout_env_step_body(sactd3_env* e, const float* actions, int64_t act_ld, const sactd3_record_layout* L, float* records, float* obs,
-                                 int64_t obs_ld, void* stream) {
-  if (!e) return SACTD3_EINVAL;
-  if (!actions || !L || !records || !obs) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: actions, layout, records and obs must not be NULL");
-  if (act_ld < e->info.ac_dim) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: act_ld is below ac_dim");
-  if (obs_ld < e->info.ob_dim) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: obs_ld is below ob_dim");
-  if (const char* why = layout_refusal(L, e->info.ob_dim, e->info.ac_dim)) return e->fail(SACTD3_EINVAL, (std::string("sactd3_rollout_env_step: ") + why).c_str());
-  if ((uintptr_t)records % 16) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: `records` is not 16-byte aligned");
-  if (!on_device(records, e->cfg.device_id)) return e->fail(SACTD3_EINVAL, "sactd3_rollout_env_step: `records` is not device memory of the env's device");
-  return launch_step_rec(e, actions, act_ld, L, records, obs, obs_ld, (hipStream_t)stream);
-}
+// the host counters, in the order sactd3_rollout_stats and sactd3_rollout_cycle_stats give them out
+enum { ROLLOUT_RANDOM_CHOICES, ROLLOUT_POLICY_CHOICES, ROLLOUT_STEPS, ROLLOUT_ROWS, ROLLOUT_NUM_STATS };
+enum { CYCLE_ISSUED, CYCLE_CAPTURED, CYCLE_GRAPH_NODES, CYCLE_EAGER, CYCLE_NUM_STATS };
+static_assert(ROLLOUT_NUM_STATS == 4 && CYCLE_NUM_STATS == 4, "int64_t out[4] of include/sactd3_rollout.h and sactd3_rollout_cycle.h");
 
 struct sactd3_rollout {
   sactd3_engine* eng = nullptr;
@@ -430,8 +371,8 @@ struct sactd3_rollout {
   sactd3_record_layout lay{};
   hipStream_t stream = nullptr;
   int n = 0;
-  int64_t stats[4] = {0, 0, 0, 0};      // random choices, policy choices, steps, rows appended
-  int64_t cycle_stats[4] = {0, 0, 0, 0};      // cycles issued, graphs captured, nodes of the last graph launched, cycles issued eagerly
+  int64_t stats[ROLLOUT_NUM_STATS] = {};
+  int64_t cycle_stats[CYCLE_NUM_STATS] = {};      // (the engine counts in them: CycleBinding::stats)
   bool cycled = false;                  // a cycle reached the engine: it may hold graphs of this binding (sactd3_rollout_destroy)
   std::string err;
 
@@ -448,46 +389,40 @@ struct sactd3_rollout {
   }
 };
 
-static int rollout_create_body(sactd3_engine* eng, sactd3_env* env, const sactd3_rollout_buffers* b, void* stream, sactd3_rollout** out) {
-  if (out) *out = nullptr;
-  auto refuse = [](const std::string& what) {
-    g_rollout_create_error = "sactd3_rollout_create: " + what;
-    return SACTD3_EINVAL;
-  };
-  if (!eng || !env || !b || !out) return refuse("NULL argument");
-  if (!b->obs || !b->actions || !b->records) return refuse("a buffer is NULL");
-  sactd3_config cfg;
-  int32_t lay[4];
-  if (sactd3_get_config(eng, &cfg) != SACTD3_OK || sactd3_rb_layout(eng, lay) != SACTD3_OK) return refuse("the engine gave no configuration");
-  const sactd3_env_info& info = env->info;
-  if (info.ob_dim != cfg.ob_dim || info.ac_dim != cfg.ac_dim)
-    return refuse("the env's ob_dim / ac_dim (" + std::to_string(info.ob_dim) + ", " + std::to_string(info.ac_dim) + ") differ from the engine's (" +
-                  std::to_string(cfg.ob_dim) + ", " + std::to_string(cfg.ac_dim) + ")");
-  if (env->cfg.device_id != cfg.device_id) return refuse("the env and the engine are on different devices");
-  if (info.num_envs > cfg.max_envs)
-    return refuse("num_envs (" + std::to_string(info.num_envs) + ") is above the engine's max_envs (" + std::to_string(cfg.max_envs) + ")");
-  if (b->obs_ld < info.ob_dim || b->actions_ld < info.ac_dim) return refuse("a row stride is below its width");
-  const sactd3_record_layout L{lay[0], lay[1], lay[2]};
-  if (const char* why = layout_refusal(&L, info.ob_dim, info.ac_dim)) return refuse(why);
-  if ((uintptr_t)b->records % 16) return refuse("`records` is not 16-byte aligned");
-  if (!on_device(b->obs, cfg.device_id) || !on_device(b->actions, cfg.device_id) || !on_device(b->records, cfg.device_id))
-    return refuse("a buffer is not device memory of the handles' device");
-  sactd3_rollout* r = new (std::nothrow) sactd3_rollout();
-  if (!r) {
-    g_rollout_create_error = "sactd3_rollout_create: out of host memory";
-    return SACTD3_EHIP;
-  }
-  r->eng = eng; r->env = env; r->buf = *b; r->lay = L; r->stream = (hipStream_t)stream; r->n = info.num_envs;
-  *out = r;
-  return SACTD3_OK;
-}
-
 ENV_API int sactd3_rollout_create(sactd3_engine* eng, sactd3_env* env, const sactd3_rollout_buffers* b, void* stream, sactd3_rollout** out) {
-  try {
-    return rollout_create_body(eng, env, b, stream, out);
-  } catch (...) {      // (the error text is a std::string)
-    return SACTD3_EHIP;
-  }
+  return guarded([&]() -> int {
+    if (out) *out = nullptr;
+    auto refuse = [](const std::string& what) {
+      g_rollout_create_error = "sactd3_rollout_create: " + what;
+      return (int)SACTD3_EINVAL;
+    };
+    if (!eng || !env || !b || !out) return refuse("NULL argument");
+    if (!b->obs || !b->actions || !b->records) return refuse("a buffer is NULL");
+    sactd3_config cfg;
+    int32_t lay[4];
+    if (sactd3_get_config(eng, &cfg) != SACTD3_OK || sactd3_rb_layout(eng, lay) != SACTD3_OK) return refuse("the engine gave no configuration");
+    const sactd3_env_info& info = env->info;
+    if (info.ob_dim != cfg.ob_dim || info.ac_dim != cfg.ac_dim)
+      return refuse("the env's ob_dim / ac_dim (" + std::to_string(info.ob_dim) + ", " + std::to_string(info.ac_dim) + ") differ from the engine's (" +
+                    std::to_string(cfg.ob_dim) + ", " + std::to_string(cfg.ac_dim) + ")");
+    if (env->cfg.device_id != cfg.device_id) return refuse("the env and the engine are on different devices");
+    if (info.num_envs > cfg.max_envs)
+      return refuse("num_envs (" + std::to_string(info.num_envs) + ") is above the engine's max_envs (" + std::to_string(cfg.max_envs) + ")");
+    if (b->obs_ld < info.ob_dim || b->actions_ld < info.ac_dim) return refuse("a row stride is below its width");
+    const sactd3_record_layout L{lay[0], lay[1], lay[2]};
+    if (const char* why = layout_refusal(&L, info.ob_dim, info.ac_dim)) return refuse(why);
+    if ((uintptr_t)b->records % 16) return refuse("`records` is not 16-byte aligned");
+    if (!on_device(b->obs, cfg.device_id) || !on_device(b->actions, cfg.device_id) || !on_device(b->records, cfg.device_id))
+      return refuse("a buffer is not device memory of the handles' device");
+    sactd3_rollout* r = new (std::nothrow) sactd3_rollout();
+    if (!r) {
+      g_rollout_create_error = "sactd3_rollout_create: out of host memory";
+      return SACTD3_EHIP;
+    }
+    r->eng = eng; r->env = env; r->buf = *b; r->lay = L; r->stream = (hipStream_t)stream; r->n = info.num_envs;
+    *out = r;
+    return SACTD3_OK;
+  });
 }
 
 // (neither handle nor any buffer is the rollout's; the cycle graphs of its binding, which the engine keeps, go with it)
@@ -499,17 +434,15 @@ ENV_API void sactd3_rollout_destroy(sactd3_rollout* r) {
 ENV_API const char* sactd3_rollout_last_error(const sactd3_rollout* r) { return r ? r->err.c_str() : g_rollout_create_error.c_str(); }
 
 ENV_API int sactd3_rollout_reset(sactd3_rollout* r, uint64_t seed) {
-  if (!r) return SACTD3_EINVAL;
-  try {
+  return guarded([&]() -> int {
+    if (!r) return SACTD3_EINVAL;
     return r->from_env(sactd3_env_reset(r->env, seed, r->buf.obs, r->buf.obs_ld, r->stream), "sactd3_env_reset");
-  } catch (...) {
-    return SACTD3_EHIP;
-  }
+  });
 }
 
 ENV_API int sactd3_rollout_choose(sactd3_rollout* r, int mode) {
-  if (!r) return SACTD3_EINVAL;
-  try {
+  return guarded([&]() -> int {
+    if (!r) return SACTD3_EINVAL;
     const sactd3_rollout_buffers& b = r->buf;
     int rc;
     switch (mode) {
@@ -517,42 +450,38 @@ ENV_API int sactd3_rollout_choose(sactd3_rollout* r, int mode) {
         return SACTD3_OK;
       case SACTD3_ROLLOUT_RANDOM:
         if ((rc = r->from_env(sactd3_env_sample_actions(r->env, b.actions, b.actions_ld, r->stream), "sactd3_env_sample_actions"))) return rc;
-        ++r->stats[0];
+        ++r->stats[ROLLOUT_RANDOM_CHOICES];
         return SACTD3_OK;
       case SACTD3_ROLLOUT_EXPLORE:
       case SACTD3_ROLLOUT_EXPLOIT:
         rc = sactd3_predict_device(r->eng, b.obs, b.obs_ld, r->n, mode == SACTD3_ROLLOUT_EXPLORE ? 1 : 0, b.actions, b.actions_ld, r->stream,
                                    SACTD3_SRC_ORDERED);
         if ((rc = r->from_engine(rc, "sactd3_predict_device"))) return rc;
-        ++r->stats[1];
+        ++r->stats[ROLLOUT_POLICY_CHOICES];
         return SACTD3_OK;
       default:
         return r->fail(SACTD3_EINVAL, "sactd3_rollout_choose: mode must be one of SACTD3_ROLLOUT_*");
     }
-  } catch (...) {
-    return SACTD3_EHIP;
-  }
+  });
 }
 
 ENV_API int sactd3_rollout_advance(sactd3_rollout* r) {
-  if (!r) return SACTD3_EINVAL;
-  try {
+  return guarded([&]() -> int {
+    if (!r) return SACTD3_EINVAL;
     const sactd3_rollout_buffers& b = r->buf;
     int rc = launch_step_rec(r->env, b.actions, b.actions_ld, &r->lay, b.records, b.obs, b.obs_ld, r->stream);
     if ((rc = r->from_env(rc, "k_env_step_rec"))) return rc;
-    ++r->stats[2];
+    ++r->stats[ROLLOUT_STEPS];
     rc = sactd3_rb_extend_records_device(r->eng, b.records, r->n, r->stream, SACTD3_SRC_ORDERED);
     if ((rc = r->from_engine(rc, "sactd3_rb_extend_records_device"))) return rc;
-    r->stats[3] += r->n;
+    r->stats[ROLLOUT_ROWS] += r->n;
     return SACTD3_OK;
-  } catch (...) {
-    return SACTD3_EHIP;
-  }
+  });
 }
 
 ENV_API int sactd3_rollout_stats(const sactd3_rollout* r, int64_t out[4]) {
   if (!r || !out) return SACTD3_EINVAL;
-  for (int i = 0; i < 4; ++i) out[i] = r->stats[i];
+  for (int i = 0; i < ROLLOUT_NUM_STATS; ++i) out[i] = r->stats[i];
   return SACTD3_OK;
 }
 
@@ -566,35 +495,31 @@ static int cycle_env_step(void* ctx, hipStream_t s) {
 }
 
 ENV_API int sactd3_rollout_cycle(sactd3_rollout* r, int mode, int do_actor) {
-  if (!r) return SACTD3_EINVAL;
-  try {
+  return guarded([&]() -> int {
+    if (!r) return SACTD3_EINVAL;
     if (mode != SACTD3_ROLLOUT_EXPLORE && mode != SACTD3_ROLLOUT_EXPLOIT)
       return r->fail(SACTD3_EINVAL, "sactd3_rollout_cycle: mode must be SACTD3_ROLLOUT_EXPLORE or SACTD3_ROLLOUT_EXPLOIT (a random or repeated choice "
                                     "runs no update: sactd3_rollout_advance / _choose)");
     const sactd3_rollout_buffers& b = r->buf;
     const CycleBinding bind{r, cycle_env_step, r, b.obs, b.obs_ld, b.actions, b.actions_ld, b.records, r->n, r->stream, r->cycle_stats};
-    const int64_t had = r->cycle_stats[0] + r->cycle_stats[1];
+    const int64_t had = r->cycle_stats[CYCLE_ISSUED] + r->cycle_stats[CYCLE_CAPTURED];
     int rc = engine_rollout_cycle(r->eng, bind, mode == SACTD3_ROLLOUT_EXPLORE ? 1 : 0, do_actor);
-    if (r->cycle_stats[0] + r->cycle_stats[1] != had) r->cycled = true;      // (a capture counts: the engine holds a graph of ours)
+    if (r->cycle_stats[CYCLE_ISSUED] + r->cycle_stats[CYCLE_CAPTURED] != had) r->cycled = true;      // (a capture counts: the engine holds a graph of ours)
     if ((rc = r->from_engine(rc, "sactd3_rollout_cycle"))) return rc;
-    ++r->stats[1]; ++r->stats[2]; r->stats[3] += r->n;      // a policy choice, a step, its rows
+    ++r->stats[ROLLOUT_POLICY_CHOICES]; ++r->stats[ROLLOUT_STEPS]; r->stats[ROLLOUT_ROWS] += r->n;
     return SACTD3_OK;
-  } catch (...) {
-    return SACTD3_EHIP;
-  }
+  });
 }
 
 ENV_API int sactd3_rollout_cycle_stats(const sactd3_rollout* r, int64_t out[4]) {
   if (!r || !out) return SACTD3_EINVAL;
-  for (int i = 0; i < 4; ++i) out[i] = r->cycle_stats[i];
+  for (int i = 0; i < CYCLE_NUM_STATS; ++i) out[i] = r->cycle_stats[i];
   return SACTD3_OK;
 }
 
 ENV_API int sactd3_rollout_cycle_clamped(sactd3_rollout* r, int64_t* out) {
-  if (!r || !out) return SACTD3_EINVAL;
-  try {
+  return guarded([&]() -> int {
+    if (!r || !out) return SACTD3_EINVAL;
     return r->from_engine(engine_rollout_cycle_clamped(r->eng, out), "sactd3_rollout_cycle_clamped");
-  } catch (...) {
-    return SACTD3_EHIP;
-  }
+  });
 }

@@ -1,4 +1,5 @@
-// The GPU-resident vector environments (include/sactd3_env.h): k_env_step<KIND>, k_env_reset<KIND>, k_env_sample_actions.
+// The GPU-resident vector environments (include/sactd3_env.h): k_env_step<KIND>, k_env_step_rec<KIND> (both around the one env_step_body<KIND>),
+// k_env_reset<KIND>, k_env_sample_actions.
 // One thread per env, 256-thread blocks, plain C++ with vector stores.  No workgroup reads what another stores and there is
 // no global counter: every counter is a per-env word, so a step is exactly one launch and the kernels are launch-bound by
 // construction.
@@ -46,10 +47,12 @@ struct EnvOut {   // sactd3_env_out with the strides checked
   uint8_t* ended; long long ended_ld;
 };
 
+// The task table, one line per task: observation and action widths, physical state words, the action bound, the default horizon.
+// A new task is a line here, its KIND branches in the functions below and a case of env.hip's with_kind.
 template <int KIND> struct EnvTask;
-template <> struct EnvTask<ENV_PENDULUM> { static constexpr int OB = 3, AC = 1, NS = 2; static constexpr float BOUND = 2.0f; };
-template <> struct EnvTask<ENV_CARTPOLE> { static constexpr int OB = 4, AC = 1, NS = 4; static constexpr float BOUND = 1.0f; };
-template <> struct EnvTask<ENV_POINTGOAL> { static constexpr int OB = 6, AC = 2, NS = 4; static constexpr float BOUND = 1.0f; };
+template <> struct EnvTask<ENV_PENDULUM> { static constexpr int OB = 3, AC = 1, NS = 2, HORIZON = 200; static constexpr float BOUND = 2.0f; };
+template <> struct EnvTask<ENV_CARTPOLE> { static constexpr int OB = 4, AC = 1, NS = 4, HORIZON = 200; static constexpr float BOUND = 1.0f; };
+template <> struct EnvTask<ENV_POINTGOAL> { static constexpr int OB = 6, AC = 2, NS = 4, HORIZON = 50; static constexpr float BOUND = 1.0f; };
 
 #define ENV_PI      3.14159274f     // fl32(pi)
 #define ENV_TWO_PI  6.28318548f     // fl32(2 pi)
@@ -166,34 +169,38 @@ __device__ __forceinline__ bool env_clean_action(const float* a, float* u) {
   return bad;
 }
 
-template <int KIND>
-__global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restrict__ actions, long long act_ld, EnvOut o, int horizon,
-                                                  uint64_t seed) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= d.n) return;
-  const size_t n = (size_t)d.n;
-  float a[EnvTask<KIND>::AC], u[EnvTask<KIND>::AC];
-#pragma unroll
-  for (int j = 0; j < EnvTask<KIND>::AC; ++j) a[j] = actions[(size_t)i * act_ld + j];
-  const bool bad = env_clean_action<KIND>(a, u);
-  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4], g[2];
-#pragma unroll
-  for (int j = 0; j < EnvTask<KIND>::NS; ++j) s[j] = d.phys[j * n + i];
-  env_goal<KIND>(seed, (uint32_t)i, d.episode[i], g);
+// What one step of env i leaves for its kernel to write out.  The arrival state belongs to the goal the step started from.
+struct EnvStepped {
+  float s[4], g0[2];   // the state and the goal the step started from
+  float fin[4];        // the arrival state
+  float nx[4], g[2];   // the state the caller acts on next and its goal: the arrival, or behind an ended episode the next one's first
   float reward;
-  bool terminal;
-  env_physics<KIND>(s, u, g, s2, reward, terminal);
+  bool terminal, truncated, ended;
+};
+
+// One step of env i, everything but the caller's outputs: the action cleaned, the physics, the flags, the episode books, the auto-reset
+// and the new physical state.  `a`: the action as given.  The ONE statement of a step: both step kernels below are this plus their writes.
+template <int KIND>
+__device__ __forceinline__ EnvStepped env_step_body(const EnvDev& d, int i, const float* a, int horizon, uint64_t seed) {
+  const size_t n = (size_t)d.n;
+  EnvStepped r;
+  float u[EnvTask<KIND>::AC];
+  const bool bad = env_clean_action<KIND>(a, u);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r.s[j] = 0.0f;
+#pragma unroll
+  for (int j = 0; j < EnvTask<KIND>::NS; ++j) r.s[j] = d.phys[j * n + i];
+  env_goal<KIND>(seed, (uint32_t)i, d.episode[i], r.g0);
+  env_physics<KIND>(r.s, u, r.g0, r.fin, r.reward, r.terminal);
   const int t = d.steps[i] + 1;
-  const float ret = d.ret[i] + reward;
-  const bool truncated = !terminal && t >= horizon;
-  const bool ended = terminal || truncated;
-  if (o.final_obs) env_observe<KIND>(s2, g, o.final_obs + (size_t)i * o.final_obs_ld);
-  if (o.reward) o.reward[(size_t)i * o.reward_ld] = reward;
-  if (o.terminated) o.terminated[(size_t)i * o.terminated_ld] = terminal ? 1 : 0;
-  if (o.truncated) o.truncated[(size_t)i * o.truncated_ld] = truncated ? 1 : 0;
-  if (o.ended) o.ended[(size_t)i * o.ended_ld] = ended ? 1 : 0;
+  const float ret = d.ret[i] + r.reward;
+  r.truncated = !r.terminal && t >= horizon;
+  r.ended = r.terminal || r.truncated;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r.nx[j] = r.fin[j];
+  r.g[0] = r.g0[0]; r.g[1] = r.g0[1];
   if (bad) d.bad[i] += 1u;
-  if (ended) {
+  if (r.ended) {
     const uint32_t ep = d.episode[i] + 1u;
     const uint32_t done = d.done_count[i];
     if (done == 0u) { d.first_ret[i] = ret; d.first_len[i] = t; }
@@ -203,8 +210,8 @@ __global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restr
     d.last_ret[i] = ret;
     d.last_len[i] = t;
     d.episode[i] = ep;
-    env_first_state<KIND>(seed, (uint32_t)i, ep, s2);
-    env_goal<KIND>(seed, (uint32_t)i, ep, g);
+    env_first_state<KIND>(seed, (uint32_t)i, ep, r.nx);
+    env_goal<KIND>(seed, (uint32_t)i, ep, r.g);
     d.steps[i] = 0;
     d.ret[i] = 0.0f;
   } else {
@@ -212,8 +219,26 @@ __global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restr
     d.ret[i] = ret;
   }
 #pragma unroll
-  for (int j = 0; j < EnvTask<KIND>::NS; ++j) d.phys[j * n + i] = s2[j];
-  env_observe<KIND>(s2, g, o.obs + (size_t)i * o.obs_ld);
+  for (int j = 0; j < EnvTask<KIND>::NS; ++j) d.phys[j * n + i] = r.nx[j];
+  return r;
+}
+
+// `final_obs` is written before `obs`: a caller that hands one buffer for both finds `obs` in it
+template <int KIND>
+__global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restrict__ actions, long long act_ld, EnvOut o, int horizon,
+                                                  uint64_t seed) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.n) return;
+  float a[EnvTask<KIND>::AC];
+#pragma unroll
+  for (int j = 0; j < EnvTask<KIND>::AC; ++j) a[j] = actions[(size_t)i * act_ld + j];
+  const EnvStepped r = env_step_body<KIND>(d, i, a, horizon, seed);
+  if (o.final_obs) env_observe<KIND>(r.fin, r.g0, o.final_obs + (size_t)i * o.final_obs_ld);
+  if (o.reward) o.reward[(size_t)i * o.reward_ld] = r.reward;
+  if (o.terminated) o.terminated[(size_t)i * o.terminated_ld] = r.terminal ? 1 : 0;
+  if (o.truncated) o.truncated[(size_t)i * o.truncated_ld] = r.truncated ? 1 : 0;
+  if (o.ended) o.ended[(size_t)i * o.ended_ld] = r.ended ? 1 : 0;
+  env_observe<KIND>(r.nx, r.g, o.obs + (size_t)i * o.obs_ld);
 }
 
 // k_env_step that also emits env i's transition as record i of a caller slab in the engine's ring layout (include/sactd3.h:
@@ -222,7 +247,7 @@ __global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restr
 // s is env_observe of the state BEFORE the step (recomputed from phys: the caller's observation buffer is not read), a the action
 // as given (its bits, not the clamped one), s'_stored the arrival observation where the step was truncated and otherwise the
 // observation the caller acts on next (behind a termination: the auto-reset one), d = 1 iff terminated.  State, books, counters and
-// `obs` are those of k_env_step, statement for statement.  One thread writes its whole record with 16-byte stores: the host side
+// `obs` are those of k_env_step: the same env_step_body.  One thread writes its whole record with 16-byte stores: the host side
 // guarantees a 16-byte aligned slab and lengths that are multiples of four, and next_off >= OB + AC, next_width >= OB,
 // record_len >= next_off + next_width + 2.
 struct EnvRec { int record_len, next_off, next_width; };
@@ -234,50 +259,19 @@ __global__ __launch_bounds__(256) void k_env_step_rec(EnvDev d, const float* __r
   constexpr int OB = EnvTask<KIND>::OB, AC = EnvTask<KIND>::AC;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= d.n) return;
-  const size_t n = (size_t)d.n;
   uint32_t araw[AC];
 #pragma unroll
   for (int j = 0; j < AC; ++j) araw[j] = __float_as_uint(actions[(size_t)i * act_ld + j]);
-  float a[AC], u[AC];
+  float a[AC];
 #pragma unroll
   for (int j = 0; j < AC; ++j) a[j] = __uint_as_float(araw[j]);
-  const bool bad = env_clean_action<KIND>(a, u);
-  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4], g[2];
-#pragma unroll
-  for (int j = 0; j < EnvTask<KIND>::NS; ++j) s[j] = d.phys[j * n + i];
-  env_goal<KIND>(seed, (uint32_t)i, d.episode[i], g);
-  float reward;
-  bool terminal;
-  env_physics<KIND>(s, u, g, s2, reward, terminal);
-  const int t = d.steps[i] + 1;
-  const float ret = d.ret[i] + reward;
-  const bool truncated = !terminal && t >= horizon;
-  const bool ended = terminal || truncated;
+  const EnvStepped r = env_step_body<KIND>(d, i, a, horizon, seed);
+  const float reward = r.reward;
+  const bool terminal = r.terminal, truncated = r.truncated;
   float so[OB], fin[OB], nx[OB];
-  env_observe<KIND>(s, g, so);
-  env_observe<KIND>(s2, g, fin);
-  if (bad) d.bad[i] += 1u;
-  if (ended) {
-    const uint32_t ep = d.episode[i] + 1u;
-    const uint32_t done = d.done_count[i];
-    if (done == 0u) { d.first_ret[i] = ret; d.first_len[i] = t; }
-    d.done_count[i] = done + 1u;
-    d.ret_sum[i] += (double)ret;
-    d.len_sum[i] += (unsigned long long)t;
-    d.last_ret[i] = ret;
-    d.last_len[i] = t;
-    d.episode[i] = ep;
-    env_first_state<KIND>(seed, (uint32_t)i, ep, s2);
-    env_goal<KIND>(seed, (uint32_t)i, ep, g);
-    d.steps[i] = 0;
-    d.ret[i] = 0.0f;
-  } else {
-    d.steps[i] = t;
-    d.ret[i] = ret;
-  }
-#pragma unroll
-  for (int j = 0; j < EnvTask<KIND>::NS; ++j) d.phys[j * n + i] = s2[j];
-  env_observe<KIND>(s2, g, nx);
+  env_observe<KIND>(r.s, r.g0, so);
+  env_observe<KIND>(r.fin, r.g0, fin);
+  env_observe<KIND>(r.nx, r.g, nx);
 #pragma unroll
   for (int j = 0; j < OB; ++j) obs[(size_t)i * obs_ld + j] = nx[j];
   // the record, element by element through selects (no indexed local array), four elements per store

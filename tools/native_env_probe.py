@@ -11,6 +11,15 @@ is a pass / fail bar of this tool; tests/test_gpu_native_env.py takes the learni
                                                        #   "eval":  envs.greedy_returns on the GPU against loop.evaluate on the host twin
     python tools/native_env_probe.py --bench TREE      # GPU: this checkout's bench.py against the bench.py of another, built checkout
                                                        # (the parent commit's), alternating, 5 runs each -> "bench"
+    python tools/native_env_probe.py --step TREE       # GPU: the "step" figures on this build and on TREE's, alternating -> "step_vs_parent"
+    python tools/native_env_probe.py --digest TREE     # GPU: do the env kernels of this build and of TREE's compute the same bits?  One
+                                                       # child process per side runs pendulum, cartpole and pointgoal at n = 1, 4, 257
+                                                       # (one thread, a partial wavefront, a ragged second block) through step and
+                                                       # step_records and hashes every output, then state() and episode_stats().  The
+                                                       # tool asserts that each run met 2 bad actions, a truncation and, on the cart-pole,
+                                                       # a termination.  -> "digest"; exit status 1 if any of the 18 pairs differs.  (Not
+                                                       # a committed expectation: the digests of the trigonometric tasks belong to one
+                                                       # ROCm's sinf / cosf.)
 Each mode rewrites its own entries of the record and leaves the others."""
 import argparse
 import json
@@ -28,6 +37,10 @@ OUT = os.path.join(ROOT, "profiles", "native_env.json")
 RUNS = 5
 SEEDS = (0, 1, 2)
 EPISODES = 16
+# the digest's fixed inputs
+DIGEST_KINDS = ("pendulum", "cartpole", "pointgoal")
+DIGEST_NS = (1, 4, 257)
+DIGEST_HORIZON, DIGEST_SEED, DIGEST_STEPS = 10, 11, 60
 # the learning tests' budget: SAC, default hyper-parameters, 4 envs, one iteration per vector step
 LEARNING = {"pendulum": dict(num_envs=4, learning_starts=1000, updates=3500, batch_size=256),
             "cartpole": dict(num_envs=4, learning_starts=1000, updates=2000, batch_size=256)}
@@ -209,14 +222,73 @@ def child_bench(tree):
     return json.loads(line)
 
 
-CHILDREN = {"train": child_train, "step": child_step, "eval": child_eval}
+def digest_actions(kind_index, n, ac_dim, bound):
+    """[DIGEST_STEPS, n, ac_dim] float32, made on the host: 30 steps of large pushes with the sign of the env's parity (the cart-pole
+    falls, the point mass runs into its wall), 30 small ones; one NaN and one +inf component"""
+    rng = np.random.default_rng([n, kind_index])
+    half = DIGEST_STEPS // 2
+    sign = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)[None, :, None]
+    act = np.concatenate([sign * rng.uniform(0.5, 1.5, (half, n, ac_dim)) * bound, rng.uniform(-0.2, 0.2, (half, n, ac_dim)) * bound]).astype(np.float32)
+    act[3, 0, 0] = np.nan
+    act[5, n - 1, ac_dim - 1] = np.inf
+    return act
 
 
-def run_child(*argv, timeout=300):
-    """a fresh process per measurement; -> its JSON.  A child that fails ends the whole probe: nothing more is started on the GPU."""
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", *map(str, argv)], capture_output=True, text=True, timeout=timeout)
+def child_digest():
+    """every (kind, n, form) of the digest on the package this process imported: -> {"library", "runs": {"kind-n-form": {"sha256",
+    "terminations", "truncations", "bad_actions"}}}"""
+    import hashlib
+    import torch
+    import sac_td3_cudagraphs_pytorch_amd as pkg
+    from sac_td3_cudagraphs_pytorch_amd import envs
+    dev = torch.device("cuda", 0)
+    runs = {}
+    for kind in DIGEST_KINDS:
+        k = envs.kind_of(kind)
+        o, a, bound = envs.SPECS[k][:3]
+        eng = pkg.Engine(pkg.Config(ob_dim=o, ac_dim=a, batch_size=64, rb_capacity=256, max_envs=4, seed=0), [-bound] * a, [bound] * a)
+        layout = eng.rb_layout()
+        done_at = layout["next_obs_offset"] + layout["next_obs_width"] + 1
+        for n in DIGEST_NS:
+            actions = torch.as_tensor(digest_actions(k, n, a, bound), device=dev)
+            for form in ("step", "step_records"):
+                env = envs.NativeVecEnv(kind, n, seed=DIGEST_SEED, device=dev, horizon=DIGEST_HORIZON)
+                obs, _ = env.reset()
+                rec = torch.zeros((n, layout["record_floats"]), device=dev)
+                h, term, trunc = hashlib.sha256(), 0, 0
+                for t in range(DIGEST_STEPS):
+                    if form == "step":
+                        obs, rew, terminated, truncated, infos = env.step(actions[t])
+                        outs = (obs, infos["final_observation"], rew, terminated, truncated, infos["_final_observation"])
+                        term, trunc = term + int(terminated.sum()), trunc + int(truncated.sum())
+                    else:
+                        env.step_records(actions[t], layout, rec, obs)
+                        outs = (rec, obs)
+                        term += int((rec[:, done_at] != 0).sum())
+                    for x in outs:
+                        h.update(x.cpu().numpy().tobytes())
+                state, stats = env.state(), env.episode_stats()
+                for book in (state, stats):
+                    for key in sorted(book):
+                        h.update(np.asarray(book[key]).tobytes())
+                if form == "step_records":
+                    trunc = stats["episodes"] - term
+                runs[f"{kind}-{n}-{form}"] = {"sha256": h.hexdigest(), "terminations": term, "truncations": trunc, "bad_actions": stats["bad_actions"]}
+                env.close()
+        eng.close()
+    return {"library": os.path.realpath(pkg.library_path()), "runs": runs}
+
+
+CHILDREN = {"train": child_train, "step": child_step, "eval": child_eval, "digest": child_digest}
+
+
+def run_child(*argv, timeout=300, tree=ROOT):
+    """a fresh process per measurement, importing the package of `tree`; -> its JSON.  A child that fails ends the whole probe: nothing
+    more is started on the GPU."""
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--tree", tree, "--child", *map(str, argv)], capture_output=True, text=True,
+                         timeout=timeout)
     if out.returncode != 0:
-        raise SystemExit(f"child {argv} failed ({out.returncode}):\n{out.stdout[-2000:]}\n{out.stderr[-4000:]}")
+        raise SystemExit(f"child {argv} in {tree} failed ({out.returncode}):\n{out.stdout[-2000:]}\n{out.stderr[-4000:]}")
     return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
 
 
@@ -245,6 +317,54 @@ def gpu_mode(runs):
     merge(rec)
 
 
+def commit_of(tree):
+    """the commit a tree is a checkout of: git's word where the tree is a repository of its own, else its COMMIT_ID file, else None"""
+    top = subprocess.run(["git", "-C", tree, "rev-parse", "--show-toplevel", "HEAD"], capture_output=True, text=True)
+    if top.returncode == 0 and os.path.realpath(top.stdout.split()[0]) == os.path.realpath(tree):
+        dirty = subprocess.run(["git", "-C", tree, "status", "--porcelain", "-uno"], capture_output=True, text=True).stdout.strip()
+        return top.stdout.split()[1] + (" + uncommitted changes" if dirty else "")
+    if os.path.exists(os.path.join(tree, "COMMIT_ID")):
+        with open(os.path.join(tree, "COMMIT_ID")) as f:
+            return f.read().strip()
+    return None
+
+
+def digest_mode(parent):
+    """bit comparison of the env kernels against another build: one child per side, each on its own package and library"""
+    sides = {"this": run_child("digest", tree=ROOT, timeout=600), "parent": run_child("digest", tree=parent, timeout=600)}
+    for side, tree in (("this", ROOT), ("parent", parent)):
+        assert os.path.dirname(sides[side]["library"]) == os.path.realpath(os.path.join(tree, "sac-td3-cudagraphs-pytorch_amd")), (side, sides[side]["library"])
+        for name, run in sides[side]["runs"].items():      # a digest of a run that never resets would prove little
+            assert run["bad_actions"] == 2 and run["truncations"] >= 1, (side, name, run)
+            assert run["terminations"] >= 1 or not name.startswith("cartpole"), (side, name, run)
+    names = sorted(sides["this"]["runs"])
+    assert names == sorted(sides["parent"]["runs"]) and len(names) == len(DIGEST_KINDS) * len(DIGEST_NS) * 2
+    differ = [name for name in names if sides["this"]["runs"][name]["sha256"] != sides["parent"]["runs"][name]["sha256"]]
+    merge({"digest": {"what": f"SHA-256 over every output of {DIGEST_STEPS} steps (step: obs, final_obs, reward, the three flags; step_records: the "
+                              f"record slab, obs), then state() and episode_stats(): horizon {DIGEST_HORIZON}, env seed {DIGEST_SEED}, host-made "
+                              "actions with a NaN and a +inf, on this build and on the parent commit's, one process each",
+                      "commits": {"this": commit_of(ROOT), "parent": commit_of(parent)}, "equal": not differ, "differ": differ,
+                      **{side: got["runs"] for side, got in sides.items()}}})
+    print(json.dumps({"pairs": len(names), "equal": not differ, "differ": differ}), flush=True)
+    return 1 if differ else 0
+
+
+def step_mode(parent, runs):
+    """the "step" figures of this build and of the parent commit's, alternating"""
+    rec = {}
+    for kind in DIGEST_KINDS:
+        for n in (4, 4096):
+            got = {"this": [], "parent": []}
+            for _ in range(runs):
+                for side, tree in (("this", ROOT), ("parent", parent)):
+                    got[side].append(run_child("step", kind, n, tree=tree))
+            rec[f"{kind}-{n}"] = {side: {f"{name}.{fig}": spread([r[name][fig] for r in rs]) for name in ("launch_only", "env_step")
+                                         for fig in ("device_us_per_step", "host_issue_us_per_step")} for side, rs in got.items()}
+            print("step", kind, n, json.dumps(rec[f"{kind}-{n}"]), flush=True)
+    merge({"step_vs_parent": {"what": "the \"step\" figures (2000 steps behind 200: the launch alone into fixed buffers, and NativeVecEnv.step) on "
+                                      "this build and on the parent commit's, alternating fresh processes", **rec}})
+
+
 def bench_mode(other, runs):
     got = {"this": [], "other": []}
     for _ in range(runs):
@@ -260,14 +380,22 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--bench", default=None, metavar="TREE")
+    ap.add_argument("--digest", default=None, metavar="TREE")
+    ap.add_argument("--step", default=None, metavar="TREE")
     ap.add_argument("--runs", type=int, default=RUNS)
+    ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--child", nargs="+", default=None)
     args = ap.parse_args()
     if args.child:
+        sys.path.insert(0, os.path.abspath(args.tree))
         kind_args = [int(x) if x.isdigit() else x for x in args.child[1:]]
         print("RESULT " + json.dumps(CHILDREN[args.child[0]](*kind_args)), flush=True)
     elif args.oracle:
         oracle_mode()
+    elif args.digest:
+        return digest_mode(os.path.abspath(args.digest))
+    elif args.step:
+        step_mode(os.path.abspath(args.step), args.runs)
     elif args.bench:
         bench_mode(os.path.abspath(args.bench), args.runs)
     else:
