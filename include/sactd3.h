@@ -111,7 +111,8 @@ void sactd3_default_config(sactd3_config* cfg, int td3);
 
 /* Agent.__init__ (agents/agent.py:24-144).  min_ac/max_ac: [ac_dim] action bounds (agent.py:35-36).
  * Parameters start at zero weights / LN gamma=1: the caller supplies the reference's orthogonal
- * init through sactd3_set_params (the Python mirror does, with torch's own orthogonal_). */
+ * init through sactd3_set_params (the Python mirror does, with torch's own orthogonal_) -- or asks the
+ * engine for its own, on the device and without torch: sactd3_init_params (sactd3_init.h). */
 int sactd3_create(const sactd3_config* cfg, const float* min_ac, const float* max_ac, sactd3_engine** out);
 void sactd3_destroy(sactd3_engine* e);
 const char* sactd3_last_error(const sactd3_engine* e);

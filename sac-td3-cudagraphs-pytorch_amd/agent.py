@@ -606,19 +606,45 @@ class ReplayBuffer:
         return 0 if self._engine is None else self._engine.rb_len()
 
 
+RESET_NAMES = {"actor": _lib.INIT_ACTOR, "critics": _lib.INIT_CRITICS, "alpha": _lib.INIT_ALPHA}
+
+
+def _init_what(what, td3: bool) -> int:
+    """names of RESET_NAMES (a sequence, or one comma-separated string) -> the bits of sactd3_init_params; TD3 drops "alpha";
+    ValueError for an unknown name or nothing left to initialise"""
+    names = [w.strip() for w in what.split(",")] if isinstance(what, str) else list(what)
+    bad = [w for w in names if w not in RESET_NAMES]
+    if bad or not names:
+        raise ValueError(f"networks to initialise: a non-empty choice of {sorted(RESET_NAMES)}, got {what!r}")
+    bits = 0
+    for w in names:
+        if not (td3 and w == "alpha"):
+            bits |= RESET_NAMES[w]
+    if not bits:
+        raise ValueError("a TD3 agent has no temperature: nothing left to initialise")
+    return bits
+
+
 class Agent:
     """agents/agent.py:Agent, MI355X-native."""
 
     def __init__(self, net_shapes: Dict[str, tuple], min_ac: np.ndarray, max_ac: np.ndarray, device: Any,
                  hps: Any, rb: Optional[ReplayBuffer] = None, *, seed: Optional[int] = None,
-                 init_params: bool = True, use_graphs: Optional[bool] = None, metrics: str = "tensor"):
-        """`use_graphs`: None = the engine's own hipGraphs ON (whatever `hps.cudagraphs` says: that key steers the reference
+                 init_params: bool = True, use_graphs: Optional[bool] = None, metrics: str = "tensor", init: str = "torch"):
+        """`init`: who produces the initial parameters (with `init_params`).  "torch" (the default): the reference's own, torch's
+        orthogonal_ on the host under the caller's torch seed, installed through set_params.  "engine": the engine's, on the device
+        (include/sactd3_init.h) -- a pure function of the engine's seed, no torch, no copy; not torch's stream, so not the
+        reference's values.
+        `use_graphs`: None = the engine's own hipGraphs ON (whatever `hps.cudagraphs` says: that key steers the reference
         loop's CudaGraphModule wrappers, orchestrator.py:313-315, which must stay off around these methods).
         `metrics`: "tensor" = update_* return 0-dim float32 CUDA tensors that alias the engine's metrics slots (zero copy; what
         `tlog.update(...)` of orchestrator.py:302,341,348 expects -- a TensorDict takes them as is, and they are only read at
         evaluation time, :383); "lazy" = host-side LazyMetric handles (no torch needed)."""
+        if init not in ("torch", "engine"):
+            raise ValueError(f'init is "torch" or "engine", not {init!r}')
         ob_dim, ac_dim = int(net_shapes["ob_shape"][-1]), int(net_shapes["ac_shape"][-1])
         self.device, self.hps = device, hps
+        self.resets_so_far = 0      # reset_networks() calls: run-time state, not part of a checkpoint
         self.min_ac, self.max_ac = np.asarray(min_ac, np.float32), np.asarray(max_ac, np.float32)
         self.timesteps_so_far = 0
         self.actor_updates_so_far = 0
@@ -651,9 +677,23 @@ class Agent:
         self.rb = rb
         if rb is not None:
             rb._bind(self.engine)
-        if init_params:  # agents/nets.py:34-49 under the caller's torch seed (main.py:146)
+        if init_params and init == "engine":
+            self.engine.init_params(_init_what(("actor", "critics", "alpha"), self.td3), epoch=0)
+        elif init_params:  # agents/nets.py:34-49 under the caller's torch seed (main.py:146)
             actor, critics = schema.reference_initial_params(ob_dim, ac_dim, self.td3, self.ln)
             self.load_flat(actor, critics)
+
+    def reset_networks(self, what=("actor", "critics", "alpha")) -> int:
+        """Start the networks `what` names over and keep the replay ring (Nikishin et al. 2022; D'Oro et al. 2023): the engine's own
+        initialiser at epoch resets_so_far + 1 under the engine's seed -- fresh orthogonal weights, targets a copy, optimiser state
+        cleared; "alpha" puts the temperature back to alpha_init (a TD3 agent has none: the name is dropped silently).  One call on
+        the engine's stream; nothing waits, no captured graph is dropped.  -> resets_so_far, which counts these calls.  Like the
+        pinned rows of a replay buffer, resets_so_far is run-time state and is NOT saved in a checkpoint: a resumed run starts its
+        epochs at 1 again."""
+        bits = _init_what(what, self.td3)
+        self.engine.init_params(bits, epoch=self.resets_so_far + 1)
+        self.resets_so_far += 1
+        return self.resets_so_far
 
     # -- parameters
     def load_flat(self, actor: np.ndarray, critics: np.ndarray, also_targets: bool = True) -> None:

@@ -32,6 +32,9 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 #include "hindsight.h"
 // ... and so is the graph form of the ring append (rollout_cycle.hip); the same header is how the rollout handle (env.hip) asks for a cycle
 #include "rollout_cycle.h"
+// ... and the parameter initialiser (param_init.hip; its C ABI is include/sactd3_init.h, defined at the end of the extern "C" block below)
+#include "param_init.h"
+#include "../../include/sactd3_init.h"
 
 static thread_local std::string g_create_error;
 
@@ -291,6 +294,13 @@ struct sactd3_engine {
   // more than before.  sactd3_instantiate_graphs has no rollout to build them from and leaves these ids alone.
   CycleBinding cyc{};
   int* cyc_ctr = nullptr;
+  // Initialising / resetting the networks on the device (sactd3_init_params; device code: param_init_kernels.h, a translation unit of its
+  // own).  init_scratch: the Gaussian matrices of all nine weights, each at a fixed offset (init_mats); init_redrawn: the device word that
+  // counts redrawn columns.  Both are made at the first call -- an engine that never calls holds nothing more than before.
+  // init_host: {calls accepted, weight matrices of the last call}.
+  float* init_scratch = nullptr;
+  int* init_redrawn = nullptr;
+  int64_t init_host[2] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -4073,6 +4083,71 @@ int sactd3_time_gather_sweep(sactd3_engine* e, int batch, int iters, float* usec
   }
   hipFree(X); hipFree(Xn); hipFree(rw); hipFree(dn); hipFree(ix);
   return rc;
+}
+
+// ---- initialise / reset the networks on the device (include/sactd3_init.h)
+// the weight matrices of `what`, each with its id and its fixed place in the scratch buffer (whatever else the call holds); -> floats of
+// scratch all nine need
+static long init_mats(sactd3_engine* e, uint32_t what, InitMat* out, int* count) {
+  long off = 0; int n = 0;
+  for (int net = 0; net < 3; ++net) {      // 0: the actor; 1, 2: the critics
+    const NetLayout& L = net ? e->Lc : e->La;
+    float* P = net ? e->Pc + (size_t)(net - 1) * L.size : e->Pa;
+    const int woff[3] = {L.W1, L.W2, L.Wh}, ld[3] = {L.ld1, HID, HID}, rows[3] = {HID, HID, L.nh}, cols[3] = {L.K, HID, HID};
+    for (int l = 0; l < 3; ++l) {
+      if (what & (net ? SACTD3_INIT_CRITICS : SACTD3_INIT_ACTOR)) out[n++] = InitMat{P + woff[l], ld[l], rows[l], cols[l], 3 * net + l, off};
+      off += (long)rows[l] * cols[l];
+    }
+  }
+  *count = n;
+  return off;
+}
+static InitFanFam init_family(sactd3_engine* e, bool actor) {
+  const NetLayout& L = actor ? e->La : e->Lc;
+  InitFanFam f{};
+  f.P = actor ? e->Pa : e->Pc; f.T = actor ? e->Ta : e->Tc; f.T2 = actor ? e->Ta2 : nullptr; f.T3 = actor ? e->Ta3 : nullptr;
+  f.M = actor ? e->Ma : e->Mc; f.V = actor ? e->Va : e->Vc; f.nets = actor ? 1 : 2;
+  f.size = L.size; f.b1 = L.b1; f.g1 = L.g1; f.W2 = L.W2; f.b2 = L.b2; f.g2 = L.g2; f.Wh = L.Wh; f.bh = L.bh;
+  f.t = actor ? &e->ctl->t_a : &e->ctl->t_q; f.pw = actor ? e->ctl->pw_a : e->ctl->pw_q;
+  return f;
+}
+
+int sactd3_init_params(sactd3_engine* e, uint32_t what, uint64_t seed, uint32_t epoch) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first: a refused call has launched, allocated, counted and marked nothing
+  const uint32_t known = SACTD3_INIT_ACTOR | SACTD3_INIT_CRITICS | SACTD3_INIT_ALPHA;
+  if (what == 0 || (what & ~known)) return e->fail(SACTD3_EINVAL, "init_params: `what` is a non-empty sum of SACTD3_INIT_ACTOR, _CRITICS, _ALPHA");
+  if ((what & SACTD3_INIT_ALPHA) && e->cfg.prefer_td3_over_sac) return e->fail(SACTD3_EINVAL, "init_params: a TD3 engine has no temperature (SACTD3_INIT_ALPHA)");
+  if (std::max(e->o + e->a, HID) > PI_MAX_TALL) return e->fail(SACTD3_EINVAL, "init_params: ob_dim + ac_dim is above what one workgroup orthogonalises");
+  if (e->act_inflight) return e->fail(SACTD3_ESTATE, "init_params: an acting call is in flight (sactd3_predict_end first)");
+  USE_DEVICE(e);
+  InitOrthArgs g{};
+  const long scratch = init_mats(e, what, g.m, &g.n);
+  RCCHK(first_use_alloc(e, &e->init_scratch, (size_t)scratch, false));      // (never zeroed: a call draws every G it reads)
+  RCCHK(first_use_alloc(e, &e->init_redrawn, 4));
+  CHAIN_BREAK(e);
+  if (what & SACTD3_INIT_ACTOR) RCCHK(actor_write_begin(e));                // the next acting call waits for this one
+  if (what & SACTD3_INIT_CRITICS) e->grads_stale[0] = true;                 // the gradient arenas no longer belong to these parameters
+  if (what & SACTD3_INIT_ACTOR) e->grads_stale[1] = true;
+  g.seed = seed; g.epoch = epoch; g.scratch = e->init_scratch; g.redrawn = e->init_redrawn;
+  if (g.n > 0) {
+    const hipError_t he = param_init_orth_launch(g, e->stream);
+    if (he != hipSuccess) return e->fail(SACTD3_EHIP, "init_params: k_init_orth", he);
+  }
+  InitFanArgs f{};
+  if (what & SACTD3_INIT_ACTOR) f.f[f.nf++] = init_family(e, true);
+  if (what & SACTD3_INIT_CRITICS) f.f[f.nf++] = init_family(e, false);
+  if (what & SACTD3_INIT_ALPHA) { f.la = e->la; f.la0 = logf(e->cfg.alpha_init); f.t_l = &e->ctl->t_l; f.pw_l = e->ctl->pw_l; }      // (sactd3_create's value)
+  const hipError_t he = param_init_fanout_launch(f, e->stream);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "init_params: k_init_fanout", he);
+  ++e->init_host[0]; e->init_host[1] = g.n;
+  return 0;
+}
+
+int sactd3_init_stats(sactd3_engine* e, int64_t out[4]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  const int64_t host[3] = {e->init_host[0], e->init_host[1], 0};
+  return stats_with_words(e, host, e->init_redrawn, 1, 2, out);
 }
 
 }  // extern "C"

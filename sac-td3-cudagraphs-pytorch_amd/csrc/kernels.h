@@ -345,11 +345,7 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 
 // all four normals of Philox block q (elements 4q .. 4q + 3): identical to philox_normal(seed, ctr, site, 4q + k), k = 0..3
 __device__ __forceinline__ float4 philox_normal4(unsigned long long seed, unsigned ctr, unsigned site, unsigned q) {
-  const Philox4 r = philox4x32_10(ctr, 0u, SACTD3_STREAM_NOISE + site, q, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const float ua = philox_u01(r.v[0]), ub = philox_u01(r.v[1]), uc = philox_u01(r.v[2]), ud = philox_u01(r.v[3]);
-  const float r0 = sqrtf(-2.0f * 0.6931471805599453f * __builtin_amdgcn_logf(ua));
-  const float r1 = sqrtf(-2.0f * 0.6931471805599453f * __builtin_amdgcn_logf(uc));
-  return make_float4(r0 * __builtin_amdgcn_cosf(ub), r0 * __builtin_amdgcn_sinf(ub), r1 * __builtin_amdgcn_cosf(ud), r1 * __builtin_amdgcn_sinf(ud));
+  return philox_box_muller4(philox4x32_10(ctr, 0u, SACTD3_STREAM_NOISE + site, q, (uint32_t)seed, (uint32_t)(seed >> 32)));      // (philox.h)
 }
 // The N(0,1) draws of one noise site, produced AHEAD of the kernel that consumes them: the actor tail sits on the critical
 // path and Philox + Box-Muller is ~1500 cycles behind its first memory round trip (the stream counter), while the trunk

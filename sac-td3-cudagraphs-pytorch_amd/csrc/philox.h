@@ -48,3 +48,16 @@ SACTD3_HD uint32_t philox_index(uint64_t seed, uint32_t ctr, uint32_t b, uint32_
 SACTD3_HD float philox_u01(uint32_t x) {  // (0,1), 24 random bits
   return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f);
 }
+
+#if defined(__HIPCC__)
+// THE Box-Muller of every normal the library draws on the device: the four N(0,1) values of one Philox block, two pairs (v0, v1) and
+// (v2, v3), cosine first.  v_log_f32 / v_sin_f32 / v_cos_f32: the trig units take their argument in revolutions, so sin(2 pi u) is one
+// instruction.  Who calls it chooses the counter words; what comes out of a block is the same everywhere (kernels.h: philox_normal4,
+// param_init_kernels.h: the Gaussian matrices), so the error figures measured for it (profiles/libm_ulp.json) hold for every caller.
+__device__ __forceinline__ float4 philox_box_muller4(const Philox4& r) {
+  const float ua = philox_u01(r.v[0]), ub = philox_u01(r.v[1]), uc = philox_u01(r.v[2]), ud = philox_u01(r.v[3]);
+  const float r0 = sqrtf(-2.0f * 0.6931471805599453f * __builtin_amdgcn_logf(ua));
+  const float r1 = sqrtf(-2.0f * 0.6931471805599453f * __builtin_amdgcn_logf(uc));
+  return make_float4(r0 * __builtin_amdgcn_cosf(ub), r0 * __builtin_amdgcn_sinf(ub), r1 * __builtin_amdgcn_cosf(ud), r1 * __builtin_amdgcn_sinf(ud));
+}
+#endif

@@ -181,6 +181,19 @@ class Engine:
             raise ValueError(f"expected {n} floats of exp_avg / exp_avg_sq, got {m.size} / {v.size}")
         self._ck(self.lib.sactd3_set_adam_state(self._h, which, _fp(m), _fp(v), int(step)))
 
+    # -- initialise / reset the networks on the device (include/sactd3_init.h)
+    def init_params(self, what: int, seed: Optional[int] = None, epoch: int = 0) -> None:
+        """sactd3_init_params: orthogonal weights, zero biases, LayerNorm ones / zeros for the networks `what` names (a sum of
+        _lib.INIT_ACTOR / INIT_CRITICS / INIT_ALPHA), their targets a copy, their optimiser state cleared -- a pure function of
+        (seed, epoch); seed None: the engine's configured seed.  Enqueued on the engine's stream: no wait, no copy."""
+        seed = self.cfg.seed if seed is None else seed
+        self._ck(self.lib.sactd3_init_params(self._h, int(what), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch)))
+
+    def init_stats(self) -> Dict[str, int]:
+        """counters of init_params (sactd3_init_stats; waits for the engine's stream: the third lives on the device)"""
+        st = self._stats(self.lib.sactd3_init_stats, ("calls", "matrices", "columns_redrawn", "reserved0"))
+        return {k: st[k] for k in ("calls", "matrices", "columns_redrawn")}
+
     # -- replay
     def _rows(self, obs, act, rew, nobs, done):
         o, a = self.cfg.ob_dim, self.cfg.ac_dim

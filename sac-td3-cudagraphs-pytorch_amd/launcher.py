@@ -335,11 +335,24 @@ def mode_flags(args, plan) -> dict:
         flags["hindsight"] = True
     if getattr(args, "fused_rollout", False):    # (the same: the key is there only when the flag was given)
         flags["fused_rollout"] = True
+    if getattr(args, "reset_every", None) is not None:      # (the same)
+        flags["reset_every"] = int(args.reset_every)
+        flags["reset_what"] = reset_names(getattr(args, "reset_what", None))
+    elif getattr(args, "reset_what", None) is not None:
+        raise ValueError("--reset_what needs --reset_every N: it names the networks that rule resets")
+    if getattr(args, "init", "torch") != "torch":           # (the same)
+        flags["init"] = args.init
     return flags
 
 
+def reset_names(text=None) -> tuple:
+    """--reset_what 'actor,critics,alpha' -> the names as loop.train takes them (None: all three)"""
+    return tuple(loop.RESET_ALL) if text is None else tuple(w.strip() for w in str(text).split(","))
+
+
 def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, prior_fraction, updates_per_step, overlap_acting: bool,
-                   device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False) -> dict:
+                   device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False,
+                   reset_every=None, reset_what=None, init: str = "torch", num_updates=None) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
@@ -347,7 +360,13 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     `hindsight` (--hindsight: the dict of hindsight_keywords for the job's env): call by call as well, or with --one_launch as one
     graph launch; the key is in the result only when it was given.
     `fused_rollout` (--fused_rollout: a loop body as one graph launch, loop.NativeRollout.cycle): asked of loop.rollout_for's own rules
-    and of loop.update_plan beside the other keywords; the key is in the result only when it was given."""
+    and of loop.update_plan beside the other keywords; the key is in the result only when it was given.
+    `reset_every` / `reset_what` (--reset_every N [--reset_what actor,critics,alpha]: periodic resets of the networks on the kept ring,
+    loop.train reset_every=...): asked of loop.update_plan's table as well -- with `num_updates`, the length of an offline plan, which
+    has to reach N; the keys are in the result only when --reset_every was given.  `init` (--init: who makes the initial parameters)
+    is the Agent's keyword, not loop.train's: checked here, never in the result."""
+    if init not in ("torch", "engine"):
+        raise ValueError(f'--init is "torch" or "engine", not {init!r}')
     if fused_rollout and not (native_rollout and not overlap_acting):      # (its two rules stand in front of the env's: no env is looked at)
         loop.rollout_for(None, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, fused_rollout=True)
     update = dict(fused=not prioritized and n_step == 1 and prior_fraction is None and not hindsight,
@@ -357,14 +376,17 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
         update["hindsight"] = dict(hindsight)
     if fused_rollout:
         update["fused_rollout"] = True
-    loop.update_plan(cfg, sampler=None, **update)
+    if reset_every is not None:
+        update["reset_every"], update["reset_what"] = int(reset_every), tuple(reset_what if reset_what is not None else loop.RESET_ALL)
+    loop.update_plan(cfg, sampler=None, **update, **(dict(num_updates=int(num_updates)) if num_updates is not None else {}))
     return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats))
 
 
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
-            native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, **over):
+            native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, init: str = "torch",
+            reset_every=None, reset_what=None, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -375,7 +397,10 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     `native_rollout`: the env loop through loop.NativeRollout (needs `device_env` and a -native id: env_plan refuses otherwise);
     `hindsight`: the engine relabels goals while it stages each batch (loop.train hindsight=...; needs an env id with a goal layout:
     hindsight_plan refuses otherwise); with `one_launch` the draw and the relabelling are part of the iteration's one graph.
-    `fused_rollout`: with `native_rollout`, a loop body past learning_starts as one graph launch (loop.train fused_rollout=True)."""
+    `fused_rollout`: with `native_rollout`, a loop body past learning_starts as one graph launch (loop.train fused_rollout=True).
+    `init`: "engine" = the initial parameters come from the engine's own initialiser under the job's seed (Agent init="engine"), not
+    from torch's; `reset_every` [, `reset_what`]: periodic resets of the networks on the kept ring (loop.train / loop.train_offline
+    reset_every=...)."""
     import json
     import time
     from pathlib import Path
@@ -409,7 +434,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     torch.manual_seed(seed)                                           # main.py:145-146
     rb = ReplayBuffer(cfg.rb_capacity)
     agent = Agent({"ob_shape": (o,), "ac_shape": (a,)}, np.full(a, -bound, np.float32), np.full(a, bound, np.float32),
-                  torch.device("cuda", device_index), cfg, rb, seed=seed)
+                  torch.device("cuda", device_index), cfg, rb, seed=seed, **(dict(init=init) if init != "torch" else {}))
+    resets = dict(reset_every=reset_every, reset_what=reset_what) if reset_every is not None else {}
     run_dir = Path(out_dir) / f"{env_id}__{algo}__seed{seed:02d}"
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
@@ -425,13 +451,14 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
         loop.load_dataset(agent, data, pin=prior_fraction is not None)
     if offline_dataset is not None and prior_fraction is None:
         metrics = loop.train_offline(cfg, agent, num_updates=int(num_updates if num_updates is not None else cfg.num_timesteps),
-                                     evaluator=ev, eval_every_updates=int(cfg.eval_every), policy_stats=int(policy_stats))
+                                     evaluator=ev, eval_every_updates=int(cfg.eval_every), policy_stats=int(policy_stats),
+                                     **({k: v for k, v in resets.items() if v is not None}))
     else:
         kw = train_keywords(cfg, prioritized=prioritized, n_step=n_step, one_launch=one_launch, prior_fraction=prior_fraction,
                             updates_per_step=updates_per_step, overlap_acting=overlap_acting, device_env=device_env,
                             native_rollout=native_rollout, policy_stats=policy_stats,
                             **(dict(hindsight=hindsight_keywords(env_id, cfg.num_envs)) if hindsight else {}),
-                            **(dict(fused_rollout=True) if fused_rollout else {}))
+                            **(dict(fused_rollout=True) if fused_rollout else {}), **resets)
         metrics = loop.train(cfg, env, agent, evaluator=ev, **kw)
     agent.engine.sync()
     dt = time.time() - t0
@@ -463,6 +490,9 @@ def _worker_main(args, plan, flags) -> int:
                     out["one_launch"] = True
             if args.fused_rollout:               # (the same: a key only when the flag was given)
                 out["fused_rollout"] = True
+            for k in ("init", "reset_every", "reset_what"):      # (the same)
+                if k in flags:
+                    out[k] = flags[k]
         else:
             out = run_job(args.algo, env_id, seed, args.device if args.device >= 0 else args.rank, args.out, factory,
                           num_timesteps=args.num_timesteps, learning_starts=args.learning_starts, eval_every=args.eval_every,
@@ -526,6 +556,14 @@ def main(argv=None) -> int:
                          "round(F * batch_size) rows from them, the others from the rows the run appends (loop.train prior_fraction=...)")
     ap.add_argument("--updates_per_step", type=int, default=None, metavar="G",
                     help="any online run: G updates after each segment instead of one (loop.train updates_per_step=...)")
+    ap.add_argument("--init", default="torch", choices=["torch", "engine"],
+                    help="who makes the initial parameters: torch's orthogonal_ on the host under torch's seed (the reference's values), or "
+                         "the engine's own initialiser on the device under the job's seed (Agent init=...)")
+    ap.add_argument("--reset_every", type=int, default=None, metavar="N",
+                    help="reset the networks on the kept replay ring whenever the update count reaches a multiple of N (loop.train "
+                         "reset_every=...): the companion of a high --updates_per_step")
+    ap.add_argument("--reset_what", default=None, metavar="actor,critics,alpha",
+                    help="with --reset_every: the networks a reset starts over (default: all three; TD3 has no alpha)")
     ap.add_argument("--policy_stats", type=int, default=0, metavar="N",
                     help="SAC: at every evaluation put N ring rows to the policy and record vitals/replay_log_prob, vitals/policy_entropy "
                          "and vitals/log_std_mean (loop.train policy_stats=...)")
@@ -544,6 +582,8 @@ def main(argv=None) -> int:
             hindsight_plan(ENV_BUNDLES[args.env_bundle], bool(args.env_factory), args.offline_dataset is not None)
         # what loop.train would refuse is refused here, with no worker started (no env loop: offline_plan left no flag for it to mind)
         facts = {k: v for k, v in flags.items() if k != "hindsight"}
+        if plan is not None and plan.get("prior_fraction") is None and "reset_every" in flags:      # an offline plan: nothing but updates
+            facts["num_updates"] = plan["num_updates"] if plan["num_updates"] is not None else job_config(args.algo, None, 0).num_timesteps
         for env_id in (ENV_BUNDLES[args.env_bundle] if args.hindsight else [None]):      # (with --hindsight: each job's own layout)
             cfg0 = job_config(args.algo, env_id, 0, batch_size=args.batch_size)
             train_keywords(cfg0, **facts, **(dict(hindsight=hindsight_keywords(env_id, cfg0.num_envs)) if args.hindsight else {}))

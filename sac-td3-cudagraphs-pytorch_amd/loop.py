@@ -361,14 +361,22 @@ class PolicyStats:
         return self.last
 
 
+RESET_ALL = ("actor", "critics", "alpha")      # the networks reset_networks / reset_every may name (a TD3 agent drops "alpha")
+
+
 def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler], prioritized: Optional[Dict[str, float]], n_step: int,
                 one_launch: bool, prior_fraction: Optional[float], updates_per_step: int,
-                hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False) -> SimpleNamespace:
+                hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False,
+                reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, num_updates: Optional[int] = None) -> SimpleNamespace:
     """What train() does with one update, decided once from its keywords: touches no agent, env or GPU and imports nothing, so a process
     that never opens a GPU can ask whether a run would be refused.  `cfg` needs `batch_size` (with `prior_fraction`, and when an update is
     issued call by call), `num_envs` (with `n_step` > 1) and `actor_update_delay` (call by call).  Which keywords need or exclude each
     other is the table `refusals` below, one row per rule with its reason, the first row that applies raising ValueError: a new mode
     adds its rows there.  `prior_fraction` and `hindsight` count as reasons for `one_launch`.
+    `reset_every` (None: never): the networks `reset_what` names (any of "actor", "critics", "alpha"; a sequence or one comma-separated
+    string) start over, on the kept ring, whenever the update count reaches a multiple of it -- a call between two loop bodies, so it
+    goes with every update form and every rollout.  `num_updates`: the length of a plan that is nothing but updates (train_offline); a
+    `reset_every` above it would never be reached and is refused.
     `fused_rollout` (train's keyword: a loop body as one `NativeRollout.cycle`, whose update is the fused uniform iteration) needs
     `fused` and excludes every other draw; `cfg` then needs `segment_len` and `action_repeat`, which must both be 1.  Its rows stand first.
     -> a namespace of
@@ -376,6 +384,9 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
       priorities        None, or dict(alpha=, eps=) for `agent.rb.enable_priorities` -- train() enables them once, before its loop
       hindsight         None, or the keywords of `agent.rb.configure_hindsight` (`hindsight` as given, `stride` defaulting to
                         cfg.num_envs) -- train() configures the buffer once, in the same place
+      reset             None, or `reset(agent, before, first=None)`: to be called between two loop bodies with the update count the
+                        previous call saw -- if the count has reached a further multiple of reset_every since then, `first()` and
+                        `agent.reset_networks(reset_what)`, once; -> the count now
       update            `update(agent, i, tlog)`: iteration i, in ONE of three forms chosen here --
                           fused        agent.iteration(i)
                           one launch   agent.iteration(i, prior_rows=), agent.iteration(i, hindsight=True) or
@@ -391,7 +402,15 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
     hs_unknown = sorted(set(hindsight or ()) - {"achieved", "desired", "dim", "threshold", "ratio", "window", "stride"})
     hs_missing = sorted({"achieved", "desired", "dim", "threshold"} - set(hindsight or ())) if hind else []
     fr = bool(fused_rollout)
+    rs = reset_every is not None
+    rs_names = [w.strip() for w in reset_what.split(",")] if isinstance(reset_what, str) else list(reset_what)
+    rs_unknown = sorted(set(rs_names) - set(RESET_ALL))
     refusals = (
+        (rs and int(reset_every) < 1, f"reset_every must be >= 1, got {reset_every}"),
+        (rs and bool(rs_unknown), f"reset_what: unknown networks {rs_unknown} (a choice of {list(RESET_ALL)})"),
+        (rs and not rs_names, "reset_what names no network"),
+        (rs and num_updates is not None and int(reset_every) > int(num_updates),
+         f"reset_every={reset_every} is never reached by a plan of {num_updates} updates"),
         (fr and not fused, "fused_rollout=True needs fused=True: the update inside the cycle is the fused uniform iteration"),
         (fr and outside, "fused_rollout=True excludes sampler=...: the cycle draws uniformly inside its graph"),
         (fr and prio, "fused_rollout=True excludes prioritized=...: the cycle's append owes the priorities no launch, its draw is uniform"),
@@ -469,21 +488,38 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
                     tlog.update(agent.update_actor(batch))
                     agent.actor_updates_so_far += 1
             agent.update_targ_nets()
-    return SimpleNamespace(updates_per_step=updates_per_step, priorities=priorities, hindsight=hs_config, update=update)
+    reset = None
+    if rs:
+        every, names = int(reset_every), tuple(rs_names)
+
+        def reset(agent, before, first=None):
+            now = int(agent.qnet_updates_so_far)
+            if now // every > before // every:
+                if first is not None:
+                    first()
+                agent.reset_networks(names)
+            return now
+    return SimpleNamespace(updates_per_step=updates_per_step, priorities=priorities, hindsight=hs_config, update=update, reset=reset)
 
 
-def _eval_point(agent, pstats: Optional[PolicyStats], evaluator: Optional["Evaluator"], on_eval, count: int) -> None:
-    """the evaluation point of train / train_offline: policy stats, then the evaluator, then on_eval(agent, count)"""
+def _eval_point(agent, pstats: Optional[PolicyStats], evaluator: Optional["Evaluator"], on_eval, count: int, resets: bool = False) -> None:
+    """the evaluation point of train / train_offline: policy stats, then the evaluator, then on_eval(agent, count); resets: the run
+    resets its networks, and vitals/resets goes into the evaluator's table with them"""
     if pstats is not None:
         pstats(getattr(evaluator, "tabular", None))
+    if resets and getattr(evaluator, "tabular", None) is not None:
+        evaluator.tabular.record("vitals/resets", int(agent.resets_so_far))
     if evaluator is not None:
         evaluator(agent)
     if on_eval is not None:
         on_eval(agent, count)
 
 
-def _last_metrics(agent, pstats: Optional[PolicyStats]) -> Dict[str, float]:
-    return dict(agent.engine.read_metrics(), **(pstats.last if pstats is not None else {}))
+def _last_metrics(agent, pstats: Optional[PolicyStats], resets: bool = False) -> Dict[str, float]:
+    out = dict(agent.engine.read_metrics(), **(pstats.last if pstats is not None else {}))
+    if resets:
+        out["vitals/resets"] = int(agent.resets_so_far)
+    return out
 
 
 def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callable[[Any, int], None]] = None,
@@ -491,7 +527,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           sampler: Optional[ProportionalSampler] = None, prioritized: Optional[Dict[str, float]] = None,
           n_step: int = 1, one_launch: bool = False, prior_fraction: Optional[float] = None,
           updates_per_step: int = 1, policy_stats: int = 0, native_rollout: bool = False,
-          hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False) -> Dict[str, float]:
+          hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False,
+          reset_every: Optional[int] = None, reset_what: Any = RESET_ALL) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -534,10 +571,17 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     update counters advancing per update; 1 is the reference's loop.
     `policy_stats=N` (default 0: off, and no call is made; SAC only): at every evaluation point N ring rows are put to the policy
     (PolicyStats) and vitals/replay_log_prob, vitals/policy_entropy and vitals/log_std_mean are recorded with the evaluator's table
-    and returned with the last metrics; the run itself is bit for bit the run without it."""
+    and returned with the last metrics; the run itself is bit for bit the run without it.
+    `reset_every=N` (default None: never; `reset_what`: any of "actor", "critics", "alpha", default all): the periodic reset of high
+    update-to-data training -- whenever `agent.qnet_updates_so_far` reaches a multiple of N, `agent.reset_networks(reset_what)` is
+    issued between two loop bodies (behind the body's evaluation point): fresh networks from the engine's own initialiser, the replay
+    ring kept.  One call on the engine's stream in every update form and every rollout, fused_rollout=True included: no graph is
+    dropped.  vitals/resets (`agent.resets_so_far`) is recorded with the evaluator's table and returned with the last metrics."""
     pstats = PolicyStats(agent, policy_stats, cfg.seed) if policy_stats else None
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
-                       prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout)
+                       prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
+                       reset_every=reset_every, reset_what=reset_what)
+    resets = plan.reset is not None
     make_rollout = rollout_for(env, overlap=overlap, device_env=device_env, native_rollout=native_rollout, fused_rollout=fused_rollout)
     if plan.priorities is not None:                                       # (nothing above touched the agent's engine)
         agent.rb.enable_priorities(**plan.priorities)
@@ -549,6 +593,7 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     i = 0
     tlog: Dict[str, Any] = {}
     step_rows = cfg.segment_len * cfg.num_envs
+    seen = int(agent.qnet_updates_so_far) if resets else 0               # the update count the reset rule last looked at
     try:
         while agent.timesteps_so_far <= cfg.num_timesteps:
             if evaluator is not None:
@@ -572,12 +617,14 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
                 i += 1
             if agent.timesteps_so_far % cfg.eval_every == 0:
                 resolve()                                                 # the evaluator / on_eval act (or load) with the same agent
-                _eval_point(agent, pstats, evaluator, on_eval, agent.timesteps_so_far)
+                _eval_point(agent, pstats, evaluator, on_eval, agent.timesteps_so_far, resets)
+            if resets:                                                    # between two bodies, whatever form they take; resolve: the
+                seen = plan.reset(agent, seen, resolve)                   # engine refuses a reset under an acting call in flight
     finally:
         if fused_rollout and ro is not None:
             ro.close()                                                    # the engine holds graphs of this binding: dropped with it, here
     resolve()                                                             # leave no acting call in flight behind the loop
-    return _last_metrics(agent, pstats)
+    return _last_metrics(agent, pstats, resets)
 
 
 _DATASET_KEYS = ("observations", "actions", "rewards", "next_observations", "terminations")
@@ -617,7 +664,7 @@ def load_dataset(agent, data, chunk: int = 65536, pin: bool = False) -> int:
 
 def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Evaluator"] = None,
                   on_eval: Optional[Callable[[Any, int], None]] = None, eval_every_updates: Optional[int] = None,
-                  policy_stats: int = 0) -> Dict[str, float]:
+                  policy_stats: int = 0, reset_every: Optional[int] = None, reset_what: Any = RESET_ALL) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
@@ -625,26 +672,36 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     done)` run at those points.  Keeps `qnet_updates_so_far` and `actor_updates_so_far` as Agent.iteration does and leaves
     `timesteps_so_far` alone (no env step was taken).  With plain TD3 or SAC this diverges on most datasets -- the actor climbs Q where
     no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
-    only).  Returns the last metrics."""
-    pstats = PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0)) if policy_stats else None
+    only).  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
+    is refused (update_plan's table).  Returns the last metrics."""
     num_updates = int(num_updates)
     if num_updates < 0:
         raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
+    reset = None
+    if reset_every is not None:                                           # (before the agent is touched)
+        reset = update_plan(cfg, fused=True, sampler=None, prioritized=None, n_step=1, one_launch=False, prior_fraction=None,
+                            updates_per_step=1, reset_every=reset_every, reset_what=reset_what, num_updates=num_updates).reset
+    pstats = PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0)) if policy_stats else None
     every = num_updates if eval_every_updates is None else int(eval_every_updates)
     if eval_every_updates is not None and every < 1:
         raise ValueError(f"train_offline: eval_every_updates must be >= 1, got {eval_every_updates}")
     eng = agent.engine
     period, delay = int(eng.cfg.actor_update_delay) + 1, int(eng.cfg.actor_update_delay)
     i = 0
+    seen = int(agent.qnet_updates_so_far) if reset is not None else 0      # the update count the reset rule last looked at
     while i < num_updates:
         end = min(num_updates, (i // every + 1) * every) if every > 0 else num_updates
+        if reset is not None:                                             # ... and where the update count reaches a multiple of reset_every
+            end = min(end, i + int(reset_every) - seen % int(reset_every))
         eng.run_iterations(i, end - i)
         agent.qnet_updates_so_far += end - i
         agent.actor_updates_so_far += delay * len(range(-(-i // period) * period, end, period))      # the iterations with i % period == 0
         i = end
         if i % every == 0 or i == num_updates:
-            _eval_point(agent, pstats, evaluator, on_eval, i)
-    return _last_metrics(agent, pstats)
+            _eval_point(agent, pstats, evaluator, on_eval, i, reset is not None)
+        if reset is not None:
+            seen = reset(agent, seen)
+    return _last_metrics(agent, pstats, reset is not None)
 
 
 class Tabular:
