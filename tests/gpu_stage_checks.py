@@ -183,6 +183,18 @@ def check_alpha(rec, eng, pre, B):
     check_adam(rec, "log_alpha", eng, _lib.LOG_ALPHA, pre, np.array([g_eng], np.float32), eng.cfg.log_alpha_lr)
 
 
+def check_fixed_alpha(rec, eng, pre):
+    """autotune = 0: no temperature step -- log_alpha and its Adam words stay bit for bit what they were before the update, and the
+    reported alpha is expf(log_alpha): one fp32 rounding of the float64 value plus the device's measured expf error (bounds.LIBM_ULP)"""
+    post = pre_step_state(eng, _lib.LOG_ALPHA)
+    for k in ("p", "m", "v"):
+        assert same_bits(post[k], pre[k]), (rec, f"fixed temperature: log_alpha's {k} moved", post[k], pre[k])
+    assert post["t"] == pre["t"], (rec, "fixed temperature: log_alpha's Adam step count moved", post["t"], pre["t"])
+    want = float(np.exp(np.float64(pre["p"][0])))
+    bound = (bd.U + bd.LIBM_ULP["expf"] * bd.ULP) * want
+    observe(rec, "fixed alpha: err / bound", bd.check("vitals/alpha", np.float32(eng.read_metrics()["vitals/alpha"]), want, bound))
+
+
 # ------------------------------------------------------------------------------------------ stages
 
 def _nd(flat, in_dim, nh, ln):
@@ -231,7 +243,8 @@ def check_trunk_forward(rec, who, X, p, h1, xh1, z2, ln):
 
 def run_one_iteration(algo, env, B, ln, rec, adam_step=1000, stages=True, **hp):
     """update_qnets, update_actor, update_targ_nets through the API from an evolved optimiser state, on a batch with loud rows; after each
-    update every checkable stage (stages=True) and every optimiser / target / temperature output against float64"""
+    update every checkable stage (stages=True) and every optimiser / target / temperature output against float64.  `hp`: further Hps
+    fields -- clip_norm (the clipped Adam step), autotune=False (the fixed temperature: check_fixed_alpha)"""
     o, a, bound = DIMS[env]
     ref, eng, _ = make_pair(algo, env, B, ln, rb_capacity=max(4096, B), **hp)
     sac = algo == "sac"
@@ -300,8 +313,10 @@ def run_one_iteration(algo, env, B, ln, rec, adam_step=1000, stages=True, **hp):
         check_adam(rec, "actor (clipped)", eng, _lib.ACTOR, pre[_lib.ACTOR], Ga, eng.cfg.actor_lr, coef=coef, coef_rel=rel)
     else:
         check_adam(rec, "actor", eng, _lib.ACTOR, pre[_lib.ACTOR], Ga, eng.cfg.actor_lr)
-    if sac:
+    if sac and eng.cfg.autotune:
         check_alpha(rec, eng, pre[_lib.LOG_ALPHA], B)
+    elif sac:
+        check_fixed_alpha(rec, eng, pre[_lib.LOG_ALPHA])
 
     # ---- targets (k_polyak)
     eng.update_targ_nets(1)

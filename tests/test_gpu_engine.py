@@ -950,6 +950,11 @@ CORNER_TOL = 1e-5
     ("sac", "humanoid", 1024, dict(ln=False)),                          # k_nt64_ln's ReLU-only prologue
     ("sac", "hopper", 4096, dict()),                                    # largest batch of the scope (batch <= 4096)
     ("sac", "hopper", 1, dict()),                                       # degenerate batch
+    # the same four options in the large-batch kernel forms (k_critic_tail<16>, k_actor_tail(2), k_tn64 + k_adam_red)
+    ("sac", "hopper", 1024, dict(autotune=False)),
+    ("sac", "hopper", 1024, dict(bcq_style_targ_mix=True)),
+    ("td3", "halfcheetah", 1024, dict(targ_actor_smoothing=False)),
+    ("td3", "halfcheetah", 1024, dict(bcq_style_targ_mix=False)),
 ])
 def test_one_iteration_config_corners(algo, env, B, hp):
     """one whole iteration (critic update, two actor updates on top of each other, Polyak) from the oracle's state, call by call"""
