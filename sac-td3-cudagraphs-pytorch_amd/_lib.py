@@ -74,6 +74,15 @@ ROLLOUT_CYCLE_SYMBOLS = ["sactd3_rollout_cycle", "sactd3_rollout_cycle_stats", "
 INIT_SYMBOLS = ["sactd3_init_params", "sactd3_init_stats"]
 INIT_ACTOR, INIT_CRITICS, INIT_ALPHA = 1, 2, 4   # sactd3_init_params `what` (SACTD3_INIT_*)
 INIT_ALL = INIT_ACTOR | INIT_CRITICS | INIT_ALPHA
+# every symbol include/sactd3_eval.h declares (tests/test_eval_rollout_host.py checks the header against this list)
+EVAL_SYMBOLS = ["sactd3_eval_rollout", "sactd3_eval_stats"]
+EVAL_GREEDY, EVAL_SAMPLE = 0, 1     # sactd3_eval_config.mode (SACTD3_EVAL_*)
+EVAL_MAX_STEPS = 4096               # SACTD3_EVAL_MAX_STEPS
+STREAM_EVAL = 0x800                 # csrc/eval_kernels.h: SACTD3_STREAM_EVAL
+# the outputs of sactd3_eval_out, in the header's order: (name, width: "o" = ob_dim, "a" = ac_dim; rows: "T" = [T][n], "n" = [n], 1 = one word; dtype)
+EVAL_OUT_FIELDS = (("obs", "o", "T", "float32"), ("actions", "a", "T", "float32"), ("eps", "a", "T", "float32"), ("reward", 1, "T", "float32"),
+                   ("logp", 1, "T", "float32"), ("rtg", 1, "T", "float32"), ("live", 1, "T", "uint8"), ("ep_return", 1, "n", "float32"),
+                   ("ep_length", 1, "n", "int32"), ("ep_terminated", 1, "n", "uint8"), ("g0", 1, "n", "float32"), ("alpha", 1, 1, "float32"))
 
 
 class EngineError(RuntimeError):
@@ -154,6 +163,16 @@ class CRecordLayout(C.Structure):
 class CRolloutBuffers(C.Structure):
     """sactd3_rollout_buffers: obs and actions with their row strides in elements, the contiguous record slab"""
     _fields_ = [("obs", C.c_void_p), ("obs_ld", C.c_int64), ("actions", C.c_void_p), ("actions_ld", C.c_int64), ("records", C.c_void_p)]
+
+
+class CEvalConfig(C.Structure):
+    """sactd3_eval_config"""
+    _fields_ = [("steps", C.c_int32), ("mode", C.c_int32), ("reset", C.c_int32), ("soft", C.c_int32), ("gamma", C.c_float), ("seed", C.c_uint64)]
+
+
+class CEvalOut(C.Structure):
+    """sactd3_eval_out: twelve device pointers (None = not wanted)"""
+    _fields_ = [(f[0], C.c_void_p) for f in EVAL_OUT_FIELDS]
 
 
 def library_path() -> str:
@@ -318,6 +337,12 @@ def load_library():
     }
     assert sorted(init_sig) == sorted(INIT_SYMBOLS)
     sig.update(init_sig)
+    eval_sig = {
+        "sactd3_eval_rollout": (C.c_int, [vp, vp, C.POINTER(CEvalConfig), C.POINTER(CEvalOut), vp, C.c_int]),
+        "sactd3_eval_stats": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(eval_sig) == sorted(EVAL_SYMBOLS)
+    sig.update(eval_sig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the .so does not export what the header declares
         fn.restype, fn.argtypes = res, args

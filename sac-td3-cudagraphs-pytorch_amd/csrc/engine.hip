@@ -35,6 +35,8 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 // ... and the parameter initialiser (param_init.hip; its C ABI is include/sactd3_init.h, defined at the end of the extern "C" block below)
 #include "param_init.h"
 #include "../../include/sactd3_init.h"
+// ... and the evaluation rollout, whose kernel is compiled with the env kernels (env.hip): host code only here, at the end of this file
+#include "eval_rollout.h"
 
 static thread_local std::string g_create_error;
 
@@ -301,6 +303,15 @@ struct sactd3_engine {
   float* init_scratch = nullptr;
   int* init_redrawn = nullptr;
   int64_t init_host[2] = {};
+  // On-policy evaluation in one launch (sactd3_eval_rollout; include/sactd3_eval.h; the kernel: eval_kernels.h, compiled in env.hip).
+  // ev_ctr: the device word that numbers the feature's draws (stream 0x800); ev_rew / ev_lp: [T][n] rewards and log-probs of the running
+  // call, which wait there for its backward pass -- ev_rows floats each, made at the first call; a call that needs more than any before it
+  // makes larger ones (the old pair stays until sactd3_destroy: a queued launch may still use it).  An engine that never evaluates holds
+  // nothing more than before.  ev_stats: {calls, env steps rolled, calls that drew}.
+  int* ev_ctr = nullptr;
+  float *ev_rew = nullptr, *ev_lp = nullptr;
+  int64_t ev_rows = 0;
+  int64_t ev_stats[3] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -4223,6 +4234,49 @@ int engine_rollout_cycle_clamped(sactd3_engine* e, int64_t* out) {
   RCCHK(stats_with_words(e, none, e->cyc_ctr, 1, 0, got));      // (0 where no cycle was ever issued)
   *out = got[0];
   return 0;
+}
+
+// ---- the evaluation rollout (include/sactd3_eval.h), the engine's half: eval_rollout.h.  Like a scoring call it writes its own scratch and
+// its own words only: no CHAIN_BREAK, actor_dirty untouched, no batch slot / noise buffer / p_* use, no sample / noise / predict / policy
+// counter.  The kernel reads the online actor on the learner stream, behind every update issued so far.
+int engine_eval_fail(sactd3_engine* e, int code, const char* what) { return e ? e->fail(code, what) : code; }
+
+int engine_eval_open(sactd3_engine* e, int ob, int ac, int device, int sample, int soft, int64_t rows, void* caller_stream, int flags, EvalActor* out) {
+  if (!e) return SACTD3_EINVAL;
+  if (!out || ob != e->o || ac != e->a || device != e->cfg.device_id) return e->fail(SACTD3_EINVAL, "eval_rollout: the env does not match the engine");
+  if (e->cfg.prefer_td3_over_sac && (sample || soft)) return e->fail(SACTD3_EINVAL, "eval_rollout: SACTD3_EVAL_SAMPLE and soft are SAC only");
+  if (rows < 1) return e->fail(SACTD3_EINVAL, "eval_rollout: nothing to roll");
+  USE_DEVICE(e);
+  RCCHK(first_use_alloc(e, &e->ev_ctr, 32));
+  if (rows > e->ev_rows) {      // (never zeroed: the backward pass reads what the forward loop of the same launch wrote)
+    float *rew = nullptr, *lp = nullptr;
+    RCCHK(first_use_alloc(e, &rew, (size_t)rows, false));
+    RCCHK(first_use_alloc(e, &lp, (size_t)rows, false));
+    e->ev_rew = rew; e->ev_lp = lp; e->ev_rows = rows;
+  }
+  RCCHK(src_order_begin(e, (hipStream_t)caller_stream, flags & SACTD3_SRC_ORDERED));
+  const NetLayout& L = e->La;
+  EvalActor A{};
+  A.P = e->Pa; A.ld1 = L.ld1; A.W1 = L.W1; A.b1 = L.b1; A.g1 = L.g1; A.be1 = L.be1; A.W2 = L.W2; A.b2 = L.b2; A.g2 = L.g2; A.be2 = L.be2;
+  A.Wh = L.Wh; A.bh = L.bh; A.ln = e->cfg.layer_norm; A.sac = !e->cfg.prefer_td3_over_sac;
+  A.scale = e->scale; A.bias = e->bias; A.log_alpha = A.sac ? e->la : nullptr;
+  A.seed = &e->ctl->seed; A.eval_ctr = e->ev_ctr; A.rew = e->ev_rew; A.lp = e->ev_lp; A.stream = e->stream;
+  *out = A;
+  return 0;
+}
+
+int engine_eval_close(sactd3_engine* e, int drew, int64_t rows, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  EnqCtx x{e, e->stream};
+  if (drew) RCCHK(launch_tick(x, e->ev_ctr));
+  RCCHK(src_order_end(e, (hipStream_t)caller_stream, flags & SACTD3_SRC_ORDERED));
+  ++e->ev_stats[0]; e->ev_stats[1] += rows;
+  if (drew) ++e->ev_stats[2];
+  return 0;
+}
+
+int engine_eval_stats(sactd3_engine* e, int64_t out[4]) {
+  return (!e || !out) ? SACTD3_EINVAL : stats_with_words(e, e->ev_stats, e->ev_ctr, 1, 3, out);
 }
 
 #ifdef SACTD3_STAMPS

@@ -2,6 +2,8 @@
 // A translation unit of its own inside libsactd3_hip.so: it shares philox.h with engine.hip and nothing else.
 // Behind it, the host side of include/sactd3_rollout.h: the record-emitting env step and the rollout handle, which reaches the
 // engine through its public ABI (include/sactd3.h) only -- and, for sactd3_rollout_cycle alone, through the one entry of rollout_cycle.h.
+// Behind that, the host side of include/sactd3_eval.h: the evaluation rollout's kernel steps the envs with env_step_body, so it is compiled
+// here (eval_kernels.h); it reaches the engine through eval_rollout.h alone.
 // Two things are written once for all of it: guarded(), the C boundary of every entry point, and with_kind(), the way from a handle's
 // run-time kind to the task table and the kernel instances of env_kernels.h.
 #include <hip/hip_runtime.h>
@@ -16,7 +18,9 @@
 #include "../../include/sactd3.h"
 #include "../../include/sactd3_env.h"
 #include "../../include/sactd3_rollout.h"
+#include "../../include/sactd3_eval.h"
 #include "env_kernels.h"
+#include "eval_kernels.h"
 #include "rollout_cycle.h"
 
 #define ENV_API extern "C" __attribute__((visibility("default")))
@@ -522,4 +526,62 @@ ENV_API int sactd3_rollout_cycle_clamped(sactd3_rollout* r, int64_t* out) {
     if (!r || !out) return SACTD3_EINVAL;
     return r->from_engine(engine_rollout_cycle_clamped(r->eng, out), "sactd3_rollout_cycle_clamped");
   });
+}
+
+// ---------------------------------------------------------------------------------------------------- include/sactd3_eval.h
+// Every refusal stands in front of the first side effect: the env's words, the engine's state and both streams are untouched by a refused call.
+ENV_API int sactd3_eval_rollout(sactd3_engine* eng, sactd3_env* e, const sactd3_eval_config* cfg, const sactd3_eval_out* out, void* caller_stream,
+                                int flags) {
+  return guarded([&]() -> int {
+    if (!eng) return SACTD3_EINVAL;
+    auto refuse = [&](const std::string& what) { return engine_eval_fail(eng, SACTD3_EINVAL, ("eval_rollout: " + what).c_str()); };
+    if (!e || !cfg || !out) return refuse("NULL argument");
+    sactd3_config ec;
+    if (sactd3_get_config(eng, &ec) != SACTD3_OK) return refuse("the engine gave no configuration");
+    const sactd3_env_info& info = e->info;
+    if (info.ob_dim != ec.ob_dim || info.ac_dim != ec.ac_dim)
+      return refuse("the env's ob_dim / ac_dim (" + std::to_string(info.ob_dim) + ", " + std::to_string(info.ac_dim) + ") differ from the engine's (" +
+                    std::to_string(ec.ob_dim) + ", " + std::to_string(ec.ac_dim) + ")");
+    if (e->cfg.device_id != ec.device_id) return refuse("the env and the engine are on different devices");
+    if (flags & ~(SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) return refuse("unknown flag");
+    if (cfg->steps < 0 || cfg->steps > SACTD3_EVAL_MAX_STEPS) return refuse("steps must be in [1, 4096] (0: the env's horizon)");
+    const int T = cfg->steps ? cfg->steps : info.horizon;
+    if (T < 1 || T > SACTD3_EVAL_MAX_STEPS) return refuse("the env's horizon is above 4096 steps: name `steps`");
+    if (!(cfg->gamma >= 0.0f && cfg->gamma <= 1.0f)) return refuse("gamma must be in [0, 1]");
+    if (cfg->mode != SACTD3_EVAL_GREEDY && cfg->mode != SACTD3_EVAL_SAMPLE) return refuse("mode must be SACTD3_EVAL_GREEDY or SACTD3_EVAL_SAMPLE");
+    if (cfg->reset != 0 && cfg->reset != 1) return refuse("reset must be 0 or 1");
+    if (cfg->soft != 0 && cfg->soft != 1) return refuse("soft must be 0 or 1");
+    const bool sample = cfg->mode == SACTD3_EVAL_SAMPLE;
+    if (ec.prefer_td3_over_sac && (sample || cfg->soft)) return refuse("SACTD3_EVAL_SAMPLE and soft are SAC only");
+    if (cfg->soft && !sample) return refuse("soft needs SACTD3_EVAL_SAMPLE (a greedy action has no log-probability)");
+    const void* outs[12] = {out->obs, out->actions, out->eps, out->reward, out->logp, out->rtg, out->live, out->ep_return, out->ep_length,
+                            out->ep_terminated, out->g0, out->alpha};
+    static const char* const names[12] = {"obs", "actions", "eps", "reward", "logp", "rtg", "live", "ep_return", "ep_length", "ep_terminated", "g0", "alpha"};
+    for (int k = 0; k < 12; ++k)
+      if (outs[k] && !on_device(outs[k], ec.device_id)) return refuse(std::string("`") + names[k] + "` is not device memory of the handles' device");
+    const int64_t rows = (int64_t)T * info.num_envs;
+    EvalActor A{};
+    int rc = engine_eval_open(eng, info.ob_dim, info.ac_dim, e->cfg.device_id, sample ? 1 : 0, cfg->soft, rows, caller_stream, flags, &A);
+    if (rc) return rc;
+    // ---- no refusal behind this point
+    if (cfg->reset) {
+      e->cfg.seed = cfg->seed;
+      with_kind(e->cfg.kind, [&](auto K) {
+        hipLaunchKernelGGL(k_env_reset<decltype(K)::value>, env_grid(e), dim3(256), 0, A.stream, e->d, (float*)nullptr, 0ll, cfg->seed);
+      });
+      if (const hipError_t he = hipGetLastError()) return engine_eval_fail(eng, SACTD3_EHIP, (std::string("eval_rollout: k_env_reset: ") + hipGetErrorString(he)).c_str());
+    }
+    EvalLaunch p{};
+    p.A = A; p.T = T; p.horizon = info.horizon; p.sample = sample ? 1 : 0; p.soft = cfg->soft; p.gamma = cfg->gamma; p.env_seed = e->cfg.seed;
+    p.obs = out->obs; p.actions = out->actions; p.eps = out->eps; p.reward = out->reward; p.logp = out->logp; p.rtg = out->rtg; p.live = out->live;
+    p.ep_return = out->ep_return; p.ep_length = out->ep_length; p.ep_terminated = out->ep_terminated; p.g0 = out->g0; p.alpha = out->alpha;
+    const dim3 grid((unsigned)((e->d.n + EV_TILE - 1) / EV_TILE));
+    with_kind(e->cfg.kind, [&](auto K) { hipLaunchKernelGGL(k_eval_rollout<decltype(K)::value>, grid, dim3(256), 0, A.stream, e->d, p); });
+    if (const hipError_t he = hipGetLastError()) return engine_eval_fail(eng, SACTD3_EHIP, (std::string("eval_rollout: k_eval_rollout: ") + hipGetErrorString(he)).c_str());
+    return engine_eval_close(eng, sample ? 1 : 0, rows, caller_stream, flags);
+  });
+}
+
+ENV_API int sactd3_eval_stats(sactd3_engine* eng, int64_t out[4]) {
+  return guarded([&]() -> int { return engine_eval_stats(eng, out); });
 }

@@ -559,6 +559,28 @@ class Engine:
         """counters of the policy queries (sactd3_policy_stats); the last two are counted on the device: the call waits"""
         return self._stats(self.lib.sactd3_policy_stats, ("calls", "rows", "rows_clamped", "rows_nan"))
 
+    def eval_rollout(self, env_handle, outputs, *, steps: int = 0, sample: bool = False, reset: bool = True, soft: bool = False,
+                     gamma: Optional[float] = None, seed: int = 0, stream: int = 0, ordered: bool = True) -> None:
+        """sactd3_eval_rollout (include/sactd3_eval.h): roll the envs of a native env (`env_handle`: its sactd3_env*) for `steps` steps
+        (0: its horizon) under the online actor in ONE kernel launch on the engine's stream -- greedy actions, or (`sample`, SAC) sampled
+        ones with their log-probs -- and leave the trajectory, the returns-to-go and the per-env summary in device memory.  `outputs`:
+        {name of a sactd3_eval_out field: device address}, a field left out is NULL; every array time-major and contiguous.  `reset`:
+        sactd3_env_reset(seed) first.  `soft`: entropy terms in the returns-to-go.  `gamma` None: the engine's.  No host wait; invisible
+        to training and acting.  `ordered` / `stream` as for q_values_device."""
+        cfg = _lib.CEvalConfig(int(steps), _lib.EVAL_SAMPLE if sample else _lib.EVAL_GREEDY, 1 if reset else 0, 1 if soft else 0,
+                               float(self.cfg.gamma if gamma is None else gamma), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        out = _lib.CEvalOut()
+        names = {f[0] for f in _lib.EVAL_OUT_FIELDS}
+        for name, ptr in dict(outputs).items():
+            if name not in names:
+                raise ValueError(f"eval_rollout: unknown output `{name}` (expected a subset of {sorted(names)})")
+            setattr(out, name, int(ptr) or None)
+        self._ck(self.lib.sactd3_eval_rollout(self._h, env_handle, C.byref(cfg), C.byref(out), _vp(stream), _flag(_lib.SRC_ORDERED, ordered)))
+
+    def eval_stats(self) -> Dict[str, int]:
+        """counters of eval_rollout (sactd3_eval_stats); the last one is the device word that numbers its draws: the call waits"""
+        return self._stats(self.lib.sactd3_eval_stats, ("calls", "env_steps", "calls_that_drew", "eval_ctr"))
+
     def rb_sample_indices_device(self, idx_ptr: int, idx_ld: int, w_ptr: int, w_ld: int, n: int, stream: int = 0, ordered: bool = True) -> None:
         """sactd3_rb_sample_indices_device: fill the batch slot with the ring records a device int64 array names (`idx_ptr`, stride
         `idx_ld` elements; n == batch_size) and the slot's loss weights from a device float32 array (`w_ptr`, `w_ld`; address 0: all 1).

@@ -9,6 +9,9 @@
                   gymnasium-0.29 protocol of `loop.SyntheticVecEnv` -- for `loop.Rollout`, `loop.Evaluator` and `loop.evaluate`
   greedy_returns  evaluation with one host wait: a vector env stepped in lock-step with the agent's greedy action for one horizon
   device_episodes the same as an episode generator, to stand in for `loop.Evaluator.ep_gen`
+  policy_rollout  on-policy episodes of a NativeVecEnv in ONE kernel launch (include/sactd3_eval.h): summaries, and on request the
+                  trajectories with their returns-to-go; `greedy_returns(one_launch=True)` goes through the same launch
+  q_bias          the normalised Q-bias of the current policy: Q(s, a) against its Monte-Carlo return on fresh episodes
 
 The tasks (textbook physics: the torque-limited pendulum swing-up; the cart-pole of Barto, Sutton & Anderson 1983 with a continuous
 force; a 2-D point mass that has to reach a goal drawn per episode, with a sparse reward) and the random streams are stated in
@@ -455,20 +458,126 @@ def _greedy_actions(env, agent, obs):
                            for lo in range(0, n, limit)])
 
 
-def greedy_returns(env, agent, episodes: int, seed: Optional[int] = None) -> Dict[str, Any]:
+def _native_for_rollout(env, agent, what: str):
+    """the engine of `agent`, after the refusals of everything that goes through sactd3_eval_rollout"""
+    if not isinstance(env, NativeVecEnv):
+        raise TypeError(f"{what}: the one-launch rollout needs a NativeVecEnv -- the env's physics runs inside the kernel; a host env "
+                        f"({type(env).__name__}) is stepped by greedy_returns' default loop")
+    eng = getattr(agent, "engine", None)
+    if eng is None or not hasattr(eng, "eval_rollout"):
+        raise TypeError(f"{what}: the agent has no engine to roll the env with")
+    return eng
+
+
+def _rollout_launch(env, agent, what: str, steps, mode, seed, gamma, soft, trajectories, reset):
+    """the launch of policy_rollout, nothing read: -> (T, summary: one uint8 device buffer, its views {name: tensor}, trajectories {name: tensor})"""
+    eng = _native_for_rollout(env, agent, what)
+    if mode not in ("greedy", "sample"):
+        raise ValueError(f"{what}: mode must be 'greedy' or 'sample', not {mode!r}")
+    t, n = env._t, env.n
+    T = int(env.horizon if steps is None else steps)
+    if not 1 <= T <= _lib.EVAL_MAX_STEPS:
+        raise ValueError(f"{what}: steps must be in [1, {_lib.EVAL_MAX_STEPS}], not {T}")
+    if seed is not None and not reset:
+        raise ValueError(f"{what}: a seed is for reset=True")
+    # the summary as ONE device buffer, so that one copy reads it: three [n] word arrays, alpha, then the [n] bytes
+    summary = env._empty((4 * (3 * n + 1) + n,), t.uint8)
+    words = summary[:4 * (3 * n + 1)]
+    views = {"ep_return": words[:4 * n].view(t.float32), "g0": words[4 * n:8 * n].view(t.float32), "ep_length": words[8 * n:12 * n].view(t.int32),
+             "alpha": words[12 * n:].view(t.float32), "ep_terminated": summary[4 * (3 * n + 1):]}
+    traj = {}
+    if trajectories:
+        traj = {"obs": env._empty((T, n, env.o), t.float32), "actions": env._empty((T, n, env.a), t.float32),
+                "eps": env._empty((T, n, env.a), t.float32), "reward": env._empty((T, n), t.float32), "logp": env._empty((T, n), t.float32),
+                "rtg": env._empty((T, n), t.float32), "live": env._empty((T, n), t.uint8)}
+    if reset and seed is not None:
+        env.seed = int(seed)
+    eng.eval_rollout(env._h, {k: v.data_ptr() for k, v in {**views, **traj}.items()}, steps=T, sample=mode == "sample", reset=reset, soft=soft,
+                     gamma=gamma, seed=env.seed & 0xFFFFFFFFFFFFFFFF, stream=env._stream())
+    return T, summary, views, traj
+
+
+def policy_rollout(env, agent, *, steps: Optional[int] = None, mode: str = "greedy", seed: Optional[int] = None, gamma: Optional[float] = None,
+                   soft: bool = False, trajectories: bool = False, reset: bool = True) -> Dict[str, Any]:
+    """On-policy episodes in ONE kernel launch (include/sactd3_eval.h): the envs of a NativeVecEnv rolled for `steps` steps (None: one
+    horizon) under the agent's online actor -- `mode` "greedy" (the exploit action) or "sample" (SAC: a sampled action with its
+    log-prob) -- on the engine's stream, ordered against the current torch stream on the GPU.  `reset`: the env is reset first (`seed`:
+    its own if None); otherwise it goes on from where it is.  `gamma` None: the engine's.  `soft`: entropy terms in the returns-to-go.
+    -> {"ep_return", "ep_length", "ep_terminated", "g0": numpy [n], about the episode each env was in at the call's first step (length 0:
+    still open at the end); "alpha"; "steps"} -- read with one host wait; with `trajectories` also the device tensors "obs" [T, n, o],
+    "actions", "eps" [T, n, a], "reward", "logp", "rtg" [T, n] float32 and "live" [T, n] uint8, which that wait covers too."""
+    T, summary, _, traj = _rollout_launch(env, agent, "policy_rollout", steps, mode, seed, gamma, soft, trajectories, reset)
+    n = env.n
+    host = summary.cpu().numpy()                              # the call's one host wait
+    w = host[:4 * (3 * n + 1)]
+    out = {"ep_return": w[:4 * n].view(F).copy(), "g0": w[4 * n:8 * n].view(F).copy(), "ep_length": w[8 * n:12 * n].view(np.int32).copy(),
+           "alpha": float(w[12 * n:].view(F)[0]), "ep_terminated": host[4 * (3 * n + 1):].astype(bool), "steps": T}
+    out.update(traj)
+    return out
+
+
+def q_bias(env, agent, *, seed: int, gamma: Optional[float] = None, mode: Optional[str] = None, tail_tol: float = 0.05) -> Dict[str, Any]:
+    """The normalised Q-bias of the REDQ / DroQ / reset papers: Q(s, a) against the discounted Monte-Carlo return of the CURRENT policy
+    from (s, a), on fresh on-policy episodes.  One policy_rollout with trajectories (reset to `seed`, one horizon), then agent.q_values
+    on the recorded (o_t, a_t) rows; nothing leaves the device until the final statistics.  q_t = min_k Q_k, bias_t = q_t - G_t.
+    Rows counted: every live row of an episode that terminated; of a truncated episode only those with gamma^(L - t) <= tail_tol,
+    because its return lacks the tail behind the time limit.  `mode` None: "sample" with entropy terms for SAC (the soft return the
+    critics are trained towards), "greedy" for TD3.
+    -> {"mean", "std": of bias / |mean G| over the counted rows, "bias_mean", "bias_std", "return_mean", "rows"}"""
+    eng = _native_for_rollout(env, agent, "q_bias")
+    t = env._t
+    sac = not bool(eng.cfg.prefer_td3_over_sac)
+    mode = ("sample" if sac else "greedy") if mode is None else mode
+    g = float(np.float32(eng.cfg.gamma if gamma is None else gamma))
+    if not 0.0 < float(tail_tol) <= 1.0:
+        raise ValueError("q_bias: tail_tol must be in (0, 1]")
+    T, _, views, got = _rollout_launch(env, agent, "q_bias", None, mode, seed, g, sac and mode == "sample", True, True)
+    n = env.n
+    q = agent.q_values({"observations": got["obs"].view(T * n, env.o), "actions": got["actions"].view(T * n, env.a)})
+    qmin = q.view(2, T, n).min(0).values.double()
+    G = got["rtg"].double()
+    L, terminated = views["ep_length"].long(), views["ep_terminated"] != 0
+    left = (L.view(1, n) - t.arange(T, device=env.device).view(T, 1)).clamp(min=0).double()      # L - t of every row
+    counted = (got["live"] != 0) & (L.view(1, n) > 0) & (terminated.view(1, n) | (t.full_like(left, g) ** left <= float(tail_tol)))
+    m = counted.double()
+    bias = (qmin - G) * m
+    sums = t.stack([m.sum(), bias.sum(), (bias * bias).sum(), (G * m).sum()]).cpu().numpy()      # the final statistics: the one transfer
+    rows = int(sums[0])
+    if rows == 0:
+        raise ValueError(f"q_bias: no row counts -- no episode terminated and none is long enough for gamma^(L - t) <= {tail_tol} "
+                         f"(gamma {g}, horizon {env.horizon}): use an eval env with a longer horizon")
+    mean, g_mean = sums[1] / rows, sums[3] / rows
+    std = float(np.sqrt(max(sums[2] / rows - mean * mean, 0.0)))
+    scale = abs(g_mean)
+    return {"mean": float(mean / scale) if scale > 0 else float("nan"), "std": std / scale if scale > 0 else float("nan"),
+            "bias_mean": float(mean), "bias_std": std, "return_mean": float(g_mean), "rows": rows}
+
+
+def greedy_returns(env, agent, episodes: int, seed: Optional[int] = None, one_launch: bool = False) -> Dict[str, Any]:
     """Greedy evaluation on `episodes` envs in lock-step: `env` (a NativeVecEnv or a HostVecEnv with num_envs == episodes) is reset
     (`seed`: its own if None) and stepped for one horizon with `agent.predict_device(explore=False)` (`agent.predict` on the host
     twin); `episode_stats()` is read once at the end -- on the GPU that is the evaluation's only host wait.  Every env finishes its
     FIRST episode inside that window (the time limit at the latest), and that one counts: one episode per env, whatever their lengths,
     which is the statistic `loop.episode` reports one env at a time.  An env that terminates early goes on with further episodes;
     they are not counted.
+    `one_launch` (a NativeVecEnv only): the reset and the whole horizon are ONE kernel launch (include/sactd3_eval.h) instead of one loop
+    body per step; the env's books are read the same way afterwards, so the keys and their meaning are the same.  The actions are the
+    actor's greedy ones in another summation order: float32-close to the loop's, not its bits.
     -> {"return", "length": the means over the envs' first episodes (float64 of the fp32 figures, in env order), "episodes": how many,
     "returns", "lengths": per env, "bad_actions"}"""
     if int(episodes) != env.num_envs:
         raise ValueError(f"greedy_returns: the env has {env.num_envs} envs, {episodes} episodes were asked for")
-    obs, _ = env.reset(seed=env.seed if seed is None else seed)
-    for _ in range(env.horizon):
-        obs = env.step(_greedy_actions(env, agent, obs))[0]
+    if one_launch:
+        eng = _native_for_rollout(env, agent, "greedy_returns(one_launch=True)")
+        if env.horizon > _lib.EVAL_MAX_STEPS:
+            raise ValueError(f"greedy_returns(one_launch=True): the horizon ({env.horizon}) is above {_lib.EVAL_MAX_STEPS} steps")
+        if seed is not None:
+            env.seed = int(seed)
+        eng.eval_rollout(env._h, {}, steps=env.horizon, reset=True, seed=env.seed & 0xFFFFFFFFFFFFFFFF, stream=env._stream())
+    else:
+        obs, _ = env.reset(seed=env.seed if seed is None else seed)
+        for _ in range(env.horizon):
+            obs = env.step(_greedy_actions(env, agent, obs))[0]
     st = env.episode_stats()
     if not (st["env_episodes"] >= 1).all():
         raise RuntimeError("greedy_returns: an env finished no episode within one horizon")      # (the time limit makes this impossible)
@@ -476,12 +585,14 @@ def greedy_returns(env, agent, episodes: int, seed: Optional[int] = None) -> Dic
             "episodes": env.num_envs, "returns": st["first_return"], "lengths": st["first_length"], "bad_actions": st["bad_actions"]}
 
 
-def device_episodes(env, agent, seed: int) -> Generator[Dict[str, np.ndarray], None, None]:
+def device_episodes(env, agent, seed: int, one_launch: bool = False) -> Generator[Dict[str, np.ndarray], None, None]:
     """An episode generator with the yield of `loop.episode` ({"length", "return"} per `next()`), served by `greedy_returns`: one
     window of env.num_envs episodes per refill, re-seeded as `loop.episode` re-seeds.  Assign it to `loop.Evaluator.ep_gen` (sized
-    num_envs == cfg.eval_steps: one window per evaluation) to evaluate without a host env step."""
+    num_envs == cfg.eval_steps: one window per evaluation) to evaluate without a host env step.  `one_launch`: as for greedy_returns."""
+    if one_launch:
+        _native_for_rollout(env, agent, "device_episodes(one_launch=True)")      # (refused here, not at the first next())
     rng = np.random.default_rng(seed)
     while True:
-        got = greedy_returns(env, agent, env.num_envs, seed=seed + rng.integers(2 ** 32 - 1, size=1).item())
+        got = greedy_returns(env, agent, env.num_envs, seed=seed + rng.integers(2 ** 32 - 1, size=1).item(), one_launch=one_launch)
         for k in range(env.num_envs):
             yield {"length": np.array(float(got["lengths"][k])), "return": np.array(float(got["returns"][k]))}

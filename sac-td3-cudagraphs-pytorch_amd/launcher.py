@@ -286,6 +286,22 @@ def policy_stats_plan(args) -> int:
     return n
 
 
+def eval_plan(args, env_ids, has_factory: bool) -> dict:
+    """What --eval_one_launch and --q_bias N ask for, checked in the parent without touching a GPU, for every env id of the sweep: both go
+    through the one-launch rollout (envs.policy_rollout), whose env physics runs inside the kernel -- so they need --device_env and a
+    native env bundle without --env_factory.  -> the keys run_job takes, each only when its flag was given.  ValueError otherwise."""
+    one, n = bool(getattr(args, "eval_one_launch", False)), int(getattr(args, "q_bias", 0) or 0)
+    if n < 0:
+        raise ValueError("--q_bias must be >= 0")
+    if one or n:
+        which = " and ".join(w for w, on in (("--eval_one_launch", one), ("--q_bias", n)) if on)
+        foreign = [e for e in env_ids if e not in NATIVE_ENVS]
+        if not args.device_env or has_factory or foreign:
+            raise ValueError(f"{which} need(s) --device_env and a native env bundle without --env_factory: the evaluation episodes run "
+                             "inside one kernel, with the env's physics" + (f" ({', '.join(foreign)} is simulated elsewhere)" if foreign else ""))
+    return dict(**(dict(eval_one_launch=True) if one else {}), **(dict(q_bias=n) if n else {}))
+
+
 def native_rollout_plan(env_ids, device_env: bool, has_factory: bool, offline: bool, overlap_acting: bool) -> None:
     """What --native_rollout excludes, checked without touching a GPU for every env id it is asked for: ValueError with a dataset or
     --overlap_acting beside it, and whatever env_plan refuses."""
@@ -342,6 +358,8 @@ def mode_flags(args, plan) -> dict:
         raise ValueError("--reset_what needs --reset_every N: it names the networks that rule resets")
     if getattr(args, "init", "torch") != "torch":           # (the same)
         flags["init"] = args.init
+    if getattr(args, "eval_one_launch", False) or getattr(args, "q_bias", 0):      # (the same: keys only when a flag was given; every job
+        flags.update(eval_plan(args, ENV_BUNDLES[args.env_bundle], bool(args.env_factory)))      # of the sweep is asked, in the parent)
     return flags
 
 
@@ -386,7 +404,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
             native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, init: str = "torch",
-            reset_every=None, reset_what=None, **over):
+            reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -400,7 +418,10 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     `fused_rollout`: with `native_rollout`, a loop body past learning_starts as one graph launch (loop.train fused_rollout=True).
     `init`: "engine" = the initial parameters come from the engine's own initialiser under the job's seed (Agent init="engine"), not
     from torch's; `reset_every` [, `reset_what`]: periodic resets of the networks on the kept ring (loop.train / loop.train_offline
-    reset_every=...)."""
+    reset_every=...).
+    `eval_one_launch`: with `device_env` on a native id, every evaluation window is one kernel launch (envs.device_episodes
+    one_launch=True); `q_bias` = N > 0: N further evaluation envs, and at every evaluation the normalised Q-bias of the current policy on
+    fresh episodes of them (loop.train q_bias=dict(env=, seed=)); both need what eval_plan states."""
     import json
     import time
     from pathlib import Path
@@ -413,6 +434,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
         native_rollout_plan([env_id], device_env, env_factory is not None, offline_dataset is not None, overlap_acting)
     if hindsight:                                # (before anything is built)
         hindsight_plan([env_id], env_factory is not None, offline_dataset is not None)
+    if (eval_one_launch or int(q_bias)) and not (device_env and env_id in NATIVE_ENVS and env_factory is None):      # (before anything is built)
+        raise ValueError("eval_one_launch / q_bias need device_env and a native env id without an env factory")
     cfg = job_config(algo, env_id, seed, **over)
     o, a, bound = ENV_DIMS[env_id]
     native = env_id in NATIVE_ENVS and env_factory is None      # the tasks this package simulates itself (env_plan)
@@ -440,7 +463,14 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
     if on_gpu:                # cfg.eval_steps greedy episodes per evaluation, in lock-step on the GPU, read with one host wait
-        ev.ep_gen = envs.device_episodes(envs.NativeVecEnv(NATIVE_ENVS[env_id], cfg.eval_steps, seed=seed, device=dev), agent, seed)
+        ev.ep_gen = envs.device_episodes(envs.NativeVecEnv(NATIVE_ENVS[env_id], cfg.eval_steps, seed=seed, device=dev), agent, seed,
+                                         **(dict(one_launch=True) if eval_one_launch else {}))
+    bias = {}
+    if int(q_bias):           # a horizon of its own: the task's plus the steps gamma needs to fall to q_bias' tail_tol, so that a time-limited
+        g = float(getattr(cfg, "gamma", 0.99))                            # task (the pendulum) has rows whose return is complete enough to count
+        tail = int(np.ceil(np.log(0.05) / np.log(g))) if 0.0 < g < 1.0 else 0
+        horizon = min(envs.SPECS[envs.kind_of(NATIVE_ENVS[env_id])][3] + tail, 4096)
+        bias = dict(q_bias=dict(env=envs.NativeVecEnv(NATIVE_ENVS[env_id], int(q_bias), seed=seed, device=dev, horizon=horizon), seed=seed))
     t0 = time.time()
     if offline_dataset is not None:
         with np.load(offline_dataset) as z:
@@ -452,14 +482,14 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     if offline_dataset is not None and prior_fraction is None:
         metrics = loop.train_offline(cfg, agent, num_updates=int(num_updates if num_updates is not None else cfg.num_timesteps),
                                      evaluator=ev, eval_every_updates=int(cfg.eval_every), policy_stats=int(policy_stats),
-                                     **({k: v for k, v in resets.items() if v is not None}))
+                                     **({k: v for k, v in resets.items() if v is not None}), **bias)
     else:
         kw = train_keywords(cfg, prioritized=prioritized, n_step=n_step, one_launch=one_launch, prior_fraction=prior_fraction,
                             updates_per_step=updates_per_step, overlap_acting=overlap_acting, device_env=device_env,
                             native_rollout=native_rollout, policy_stats=policy_stats,
                             **(dict(hindsight=hindsight_keywords(env_id, cfg.num_envs)) if hindsight else {}),
                             **(dict(fused_rollout=True) if fused_rollout else {}), **resets)
-        metrics = loop.train(cfg, env, agent, evaluator=ev, **kw)
+        metrics = loop.train(cfg, env, agent, evaluator=ev, **kw, **bias)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -490,7 +520,7 @@ def _worker_main(args, plan, flags) -> int:
                     out["one_launch"] = True
             if args.fused_rollout:               # (the same: a key only when the flag was given)
                 out["fused_rollout"] = True
-            for k in ("init", "reset_every", "reset_what"):      # (the same)
+            for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias"):      # (the same)
                 if k in flags:
                     out[k] = flags[k]
         else:
@@ -567,6 +597,12 @@ def main(argv=None) -> int:
     ap.add_argument("--policy_stats", type=int, default=0, metavar="N",
                     help="SAC: at every evaluation put N ring rows to the policy and record vitals/replay_log_prob, vitals/policy_entropy "
                          "and vitals/log_std_mean (loop.train policy_stats=...)")
+    ap.add_argument("--eval_one_launch", action="store_true",
+                    help="with --device_env and a native env bundle: every evaluation window -- reset, one horizon of greedy steps -- is one "
+                         "kernel launch (envs.greedy_returns one_launch=True) instead of one loop body per step")
+    ap.add_argument("--q_bias", type=int, default=0, metavar="N",
+                    help="with --device_env and a native env bundle: at every evaluation roll N fresh on-policy episodes in one launch and record "
+                         "the normalised Q-bias of the critics, vitals/q_bias_mean, vitals/q_bias_std, vitals/q_bias_rows (loop.train q_bias=...)")
     ap.add_argument("--dry-run", action="store_true", help="enumerate and shard the jobs, start the workers, run nothing on a GPU")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
@@ -581,7 +617,7 @@ def main(argv=None) -> int:
         if args.hindsight:                       # every job of the sweep, before a worker starts
             hindsight_plan(ENV_BUNDLES[args.env_bundle], bool(args.env_factory), args.offline_dataset is not None)
         # what loop.train would refuse is refused here, with no worker started (no env loop: offline_plan left no flag for it to mind)
-        facts = {k: v for k, v in flags.items() if k != "hindsight"}
+        facts = {k: v for k, v in flags.items() if k not in ("hindsight", "eval_one_launch", "q_bias")}
         if plan is not None and plan.get("prior_fraction") is None and "reset_every" in flags:      # an offline plan: nothing but updates
             facts["num_updates"] = plan["num_updates"] if plan["num_updates"] is not None else job_config(args.algo, None, 0).num_timesteps
         for env_id in (ENV_BUNDLES[args.env_bundle] if args.hindsight else [None]):      # (with --hindsight: each job's own layout)

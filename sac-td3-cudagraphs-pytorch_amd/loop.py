@@ -361,6 +361,57 @@ class PolicyStats:
         return self.last
 
 
+class QBias:
+    """`q_bias=dict(env=, seed= [, gamma=, mode=, tail_tol=])` of train / train_offline: at every evaluation point `envs.q_bias` -- fresh
+    on-policy episodes of `env` (an envs.NativeVecEnv of its own: never the training env, whose episodes it would cut) in one kernel
+    launch, the critics' values of the recorded pairs against the Monte-Carlo returns.  -> vitals/q_bias_mean, vitals/q_bias_std (both
+    divided by |mean return|: the REDQ definition) and vitals/q_bias_rows.  The rollout and the scoring have scratch and counters of their
+    own: the run's parameters, optimiser state, losses and counters are bit for bit those of the run without it."""
+    KEYS = ("vitals/q_bias_mean", "vitals/q_bias_std", "vitals/q_bias_rows")
+
+    def __init__(self, agent, spec):
+        from . import envs
+        if not isinstance(spec, dict) or "env" not in spec or "seed" not in spec:
+            raise ValueError("q_bias must be a dict with `env` (an evaluation envs.NativeVecEnv) and `seed`")
+        unknown = set(spec) - {"env", "seed", "gamma", "mode", "tail_tol"}
+        if unknown:
+            raise ValueError(f"q_bias: unknown keys {sorted(unknown)}")
+        envs._native_for_rollout(spec["env"], agent, "q_bias")             # (a host env, an agent without an engine: TypeError, before the run)
+        self.agent, self.env, self.last = agent, spec["env"], {}
+        self.kw = {k: v for k, v in spec.items() if k != "env"}
+        self._q_bias = envs.q_bias
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        got = self._q_bias(self.env, self.agent, **self.kw)
+        self.last = {"vitals/q_bias_mean": got["mean"], "vitals/q_bias_std": got["std"], "vitals/q_bias_rows": got["rows"]}
+        if tabular is not None:
+            for k, v in self.last.items():
+                tabular.record(k, v)
+        return self.last
+
+
+class _Vitals:
+    """the diagnostics of an evaluation point, in order, as one: what _eval_point calls and _last_metrics reads"""
+
+    def __init__(self, parts):
+        self.parts = parts
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        for part in self.parts:
+            part(tabular)
+        return self.last
+
+    @property
+    def last(self) -> Dict[str, float]:
+        return {k: v for part in self.parts for k, v in part.last.items()}
+
+
+def _vitals(agent, policy_stats: int, q_bias, cfg: Any):
+    """PolicyStats and / or QBias as train / train_offline were asked for them; None: neither (and no call is made, no field of cfg read)"""
+    parts = ([PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0))] if policy_stats else []) + ([QBias(agent, q_bias)] if q_bias is not None else [])
+    return None if not parts else parts[0] if len(parts) == 1 else _Vitals(parts)
+
+
 RESET_ALL = ("actor", "critics", "alpha")      # the networks reset_networks / reset_every may name (a TD3 agent drops "alpha")
 
 
@@ -502,7 +553,7 @@ def update_plan(cfg: Any, *, fused: bool, sampler: Optional[ProportionalSampler]
     return SimpleNamespace(updates_per_step=updates_per_step, priorities=priorities, hindsight=hs_config, update=update, reset=reset)
 
 
-def _eval_point(agent, pstats: Optional[PolicyStats], evaluator: Optional["Evaluator"], on_eval, count: int, resets: bool = False) -> None:
+def _eval_point(agent, pstats: Optional[Any], evaluator: Optional["Evaluator"], on_eval, count: int, resets: bool = False) -> None:
     """the evaluation point of train / train_offline: policy stats, then the evaluator, then on_eval(agent, count); resets: the run
     resets its networks, and vitals/resets goes into the evaluator's table with them"""
     if pstats is not None:
@@ -515,7 +566,7 @@ def _eval_point(agent, pstats: Optional[PolicyStats], evaluator: Optional["Evalu
         on_eval(agent, count)
 
 
-def _last_metrics(agent, pstats: Optional[PolicyStats], resets: bool = False) -> Dict[str, float]:
+def _last_metrics(agent, pstats: Optional[Any], resets: bool = False) -> Dict[str, float]:
     out = dict(agent.engine.read_metrics(), **(pstats.last if pstats is not None else {}))
     if resets:
         out["vitals/resets"] = int(agent.resets_so_far)
@@ -528,7 +579,7 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           n_step: int = 1, one_launch: bool = False, prior_fraction: Optional[float] = None,
           updates_per_step: int = 1, policy_stats: int = 0, native_rollout: bool = False,
           hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False,
-          reset_every: Optional[int] = None, reset_what: Any = RESET_ALL) -> Dict[str, float]:
+          reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, q_bias: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -576,8 +627,11 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     update-to-data training -- whenever `agent.qnet_updates_so_far` reaches a multiple of N, `agent.reset_networks(reset_what)` is
     issued between two loop bodies (behind the body's evaluation point): fresh networks from the engine's own initialiser, the replay
     ring kept.  One call on the engine's stream in every update form and every rollout, fused_rollout=True included: no graph is
-    dropped.  vitals/resets (`agent.resets_so_far`) is recorded with the evaluator's table and returned with the last metrics."""
-    pstats = PolicyStats(agent, policy_stats, cfg.seed) if policy_stats else None
+    dropped.  vitals/resets (`agent.resets_so_far`) is recorded with the evaluator's table and returned with the last metrics.
+    `q_bias=dict(env=, seed=)` (default None: off, and no call is made): at every evaluation point the normalised Q-bias of the current
+    policy on fresh episodes of `env` (QBias; an envs.NativeVecEnv of its own) -- vitals/q_bias_mean, vitals/q_bias_std and
+    vitals/q_bias_rows, recorded and returned like the policy stats; the run itself is bit for bit the run without it."""
+    pstats = _vitals(agent, policy_stats, q_bias, cfg)
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
                        prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
                        reset_every=reset_every, reset_what=reset_what)
@@ -664,7 +718,8 @@ def load_dataset(agent, data, chunk: int = 65536, pin: bool = False) -> int:
 
 def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Evaluator"] = None,
                   on_eval: Optional[Callable[[Any, int], None]] = None, eval_every_updates: Optional[int] = None,
-                  policy_stats: int = 0, reset_every: Optional[int] = None, reset_what: Any = RESET_ALL) -> Dict[str, float]:
+                  policy_stats: int = 0, reset_every: Optional[int] = None, reset_what: Any = RESET_ALL,
+                  q_bias: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
@@ -672,7 +727,7 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     done)` run at those points.  Keeps `qnet_updates_so_far` and `actor_updates_so_far` as Agent.iteration does and leaves
     `timesteps_so_far` alone (no env step was taken).  With plain TD3 or SAC this diverges on most datasets -- the actor climbs Q where
     no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
-    only).  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
+    only), `q_bias=dict(env=, seed=)` as for train.  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
     is refused (update_plan's table).  Returns the last metrics."""
     num_updates = int(num_updates)
     if num_updates < 0:
@@ -681,7 +736,7 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     if reset_every is not None:                                           # (before the agent is touched)
         reset = update_plan(cfg, fused=True, sampler=None, prioritized=None, n_step=1, one_launch=False, prior_fraction=None,
                             updates_per_step=1, reset_every=reset_every, reset_what=reset_what, num_updates=num_updates).reset
-    pstats = PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0)) if policy_stats else None
+    pstats = _vitals(agent, policy_stats, q_bias, cfg)
     every = num_updates if eval_every_updates is None else int(eval_every_updates)
     if eval_every_updates is not None and every < 1:
         raise ValueError(f"train_offline: eval_every_updates must be >= 1, got {eval_every_updates}")
