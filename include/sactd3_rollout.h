@@ -96,5 +96,7 @@ int sactd3_rollout_stats(const sactd3_rollout* r, int64_t out[4]);
 
 /* advance, choose and the engine's update as ONE graph launch per env step: declared in a header of its own, which needs the types above */
 #include "sactd3_rollout_cycle.h"
+/* a whole segment of T env steps, records and append as ONE call: likewise */
+#include "sactd3_rollout_collect.h"
 
 #endif /* SACTD3_ROLLOUT_H */

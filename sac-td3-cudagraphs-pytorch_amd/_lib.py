@@ -70,6 +70,10 @@ ROLLOUT_RANDOM, ROLLOUT_EXPLORE, ROLLOUT_EXPLOIT, ROLLOUT_REPEAT = range(4)   # 
 # every symbol include/sactd3_rollout_cycle.h declares -- the header sactd3_rollout.h ends with (tests/test_rollout_cycle_host.py checks it
 # against this list)
 ROLLOUT_CYCLE_SYMBOLS = ["sactd3_rollout_cycle", "sactd3_rollout_cycle_stats", "sactd3_rollout_cycle_clamped"]
+# every symbol include/sactd3_rollout_collect.h declares -- the header behind it (tests/test_collect_host.py checks it against this list)
+ROLLOUT_COLLECT_SYMBOLS = ["sactd3_rollout_collect", "sactd3_rollout_collect_stats"]
+COLLECT_MAX_STEPS = 4096            # SACTD3_COLLECT_MAX_STEPS
+STREAM_COLLECT = 0x900              # csrc/collect_kernels.h: SACTD3_STREAM_COLLECT
 # every symbol include/sactd3_init.h declares (tests/test_param_init_host.py checks the header against this list)
 INIT_SYMBOLS = ["sactd3_init_params", "sactd3_init_stats"]
 INIT_ACTOR, INIT_CRITICS, INIT_ALPHA = 1, 2, 4   # sactd3_init_params `what` (SACTD3_INIT_*)
@@ -331,6 +335,12 @@ def load_library():
     }
     assert sorted(cycle_sig) == sorted(ROLLOUT_CYCLE_SYMBOLS)
     sig.update(cycle_sig)
+    collect_sig = {
+        "sactd3_rollout_collect": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+        "sactd3_rollout_collect_stats": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(collect_sig) == sorted(ROLLOUT_COLLECT_SYMBOLS)
+    sig.update(collect_sig)
     init_sig = {
         "sactd3_init_params": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_uint32]),
         "sactd3_init_stats": (C.c_int, [vp, i64p]),

@@ -37,6 +37,8 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 #include "../../include/sactd3_init.h"
 // ... and the evaluation rollout, whose kernel is compiled with the env kernels (env.hip): host code only here, at the end of this file
 #include "eval_rollout.h"
+// ... and the collected rollout segment, split the same way (collect_rollout.h)
+#include "collect_rollout.h"
 
 static thread_local std::string g_create_error;
 
@@ -312,6 +314,9 @@ struct sactd3_engine {
   float *ev_rew = nullptr, *ev_lp = nullptr;
   int64_t ev_rows = 0;
   int64_t ev_stats[3] = {};
+  // A training segment in one launch (sactd3_rollout_collect; include/sactd3_rollout_collect.h; the kernel: collect_kernels.h, compiled
+  // in env.hip).  cl_ctr: the device word that numbers the feature's draws (stream 0x900), made at the first call.
+  int* cl_ctr = nullptr;
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -4277,6 +4282,42 @@ int engine_eval_close(sactd3_engine* e, int drew, int64_t rows, void* caller_str
 
 int engine_eval_stats(sactd3_engine* e, int64_t out[4]) {
   return (!e || !out) ? SACTD3_EINVAL : stats_with_words(e, e->ev_stats, e->ev_ctr, 1, 3, out);
+}
+
+// ---- the collected rollout segment (include/sactd3_rollout_collect.h), the engine's half: collect_rollout.h.  The launch reads the online
+// actor on the learner stream, behind every update issued so far, and writes the caller's slab; the append that follows is the public
+// sactd3_rb_extend_records_device on the same stream (which breaks the run-ahead chain, as every append does).  No sample, noise, predict or
+// policy counter moves: the draws are numbered by cl_ctr alone.
+int engine_collect_open(sactd3_engine* e, int ob, int ac, int device, int64_t rows, void* rollout_stream, CollectActor* out) {
+  if (!e) return SACTD3_EINVAL;
+  if (!out || ob != e->o || ac != e->a || device != e->cfg.device_id) return e->fail(SACTD3_EINVAL, "rollout_collect: the env does not match the engine");
+  if (rows < 1) return e->fail(SACTD3_EINVAL, "rollout_collect: nothing to roll");
+  if (rows > ring_region(e))
+    return e->fail(SACTD3_EINVAL, "rollout_collect: steps * num_envs is above the ring slots an append may use (rb_capacity minus the pinned rows)");
+  if (e->act_inflight) return e->fail(SACTD3_ESTATE, "rollout_collect: an acting call is in flight (sactd3_predict_end first)");
+  USE_DEVICE(e);
+  RCCHK(first_use_alloc(e, &e->cl_ctr, 32));
+  RCCHK(src_order_begin(e, (hipStream_t)rollout_stream, SACTD3_SRC_ORDERED));
+  const NetLayout& L = e->La;
+  EvalActor A{};
+  A.P = e->Pa; A.ld1 = L.ld1; A.W1 = L.W1; A.b1 = L.b1; A.g1 = L.g1; A.be1 = L.be1; A.W2 = L.W2; A.b2 = L.b2; A.g2 = L.g2; A.be2 = L.be2;
+  A.Wh = L.Wh; A.bh = L.bh; A.ln = e->cfg.layer_norm; A.sac = !e->cfg.prefer_td3_over_sac;
+  A.scale = e->scale; A.bias = e->bias; A.log_alpha = nullptr;
+  A.seed = &e->ctl->seed; A.eval_ctr = e->cl_ctr; A.rew = nullptr; A.lp = nullptr; A.stream = e->stream;
+  out->A = A;
+  out->noise_std = e->cfg.actor_noise_std;
+  return 0;
+}
+
+int engine_collect_close(sactd3_engine* e, int drew, void* rollout_stream) {
+  if (!e) return SACTD3_EINVAL;
+  EnqCtx x{e, e->stream};
+  if (drew) RCCHK(launch_tick(x, e->cl_ctr));
+  return src_order_end(e, (hipStream_t)rollout_stream, SACTD3_SRC_ORDERED);
+}
+
+int engine_collect_stats(sactd3_engine* e, const int64_t host[3], int64_t out[4]) {
+  return (!e || !host || !out) ? SACTD3_EINVAL : stats_with_words(e, host, e->cl_ctr, 1, 3, out);
 }
 
 #ifdef SACTD3_STAMPS

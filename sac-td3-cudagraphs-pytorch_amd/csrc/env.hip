@@ -3,7 +3,8 @@
 // Behind it, the host side of include/sactd3_rollout.h: the record-emitting env step and the rollout handle, which reaches the
 // engine through its public ABI (include/sactd3.h) only -- and, for sactd3_rollout_cycle alone, through the one entry of rollout_cycle.h.
 // Behind that, the host side of include/sactd3_eval.h: the evaluation rollout's kernel steps the envs with env_step_body, so it is compiled
-// here (eval_kernels.h); it reaches the engine through eval_rollout.h alone.
+// here (eval_kernels.h); it reaches the engine through eval_rollout.h alone.  The same holds for the collected segment of
+// include/sactd3_rollout_collect.h: collect_kernels.h, collect_rollout.h.
 // Two things are written once for all of it: guarded(), the C boundary of every entry point, and with_kind(), the way from a handle's
 // run-time kind to the task table and the kernel instances of env_kernels.h.
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include "../../include/sactd3_eval.h"
 #include "env_kernels.h"
 #include "eval_kernels.h"
+#include "collect_kernels.h"
 #include "rollout_cycle.h"
 
 #define ENV_API extern "C" __attribute__((visibility("default")))
@@ -377,6 +379,7 @@ struct sactd3_rollout {
   int n = 0;
   int64_t stats[ROLLOUT_NUM_STATS] = {};
   int64_t cycle_stats[CYCLE_NUM_STATS] = {};      // (the engine counts in them: CycleBinding::stats)
+  int64_t collect_stats[3] = {};        // sactd3_rollout_collect: {calls, env steps, calls that drew}
   bool cycled = false;                  // a cycle reached the engine: it may hold graphs of this binding (sactd3_rollout_destroy)
   std::string err;
 
@@ -525,6 +528,65 @@ ENV_API int sactd3_rollout_cycle_clamped(sactd3_rollout* r, int64_t* out) {
   return guarded([&]() -> int {
     if (!r || !out) return SACTD3_EINVAL;
     return r->from_engine(engine_rollout_cycle_clamped(r->eng, out), "sactd3_rollout_cycle_clamped");
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------- include/sactd3_rollout_collect.h
+// Every refusal stands in front of the first side effect.  The launches, all on the engine's learner stream between ONE pair of events
+// against the rollout's: k_collect_rollout, the append of its slab (flags 0: the slab was written on the stream that reads it), the
+// counter tick of a call that drew.
+ENV_API int sactd3_rollout_collect(sactd3_rollout* r, int mode, int steps, float* records, float* eps) {
+  return guarded([&]() -> int {
+    if (!r) return SACTD3_EINVAL;
+    sactd3_env* e = r->env;
+    const int dev = e->cfg.device_id;
+    if (!records) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: `records` must not be NULL");
+    if ((uintptr_t)records % 16) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: `records` is not 16-byte aligned");
+    if (mode != SACTD3_ROLLOUT_RANDOM && mode != SACTD3_ROLLOUT_EXPLORE && mode != SACTD3_ROLLOUT_EXPLOIT)
+      return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: mode must be SACTD3_ROLLOUT_RANDOM, SACTD3_ROLLOUT_EXPLORE or SACTD3_ROLLOUT_EXPLOIT");
+    if (steps < 1 || steps > SACTD3_COLLECT_MAX_STEPS) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: steps must be in [1, 4096]");
+    if (!on_device(records, dev)) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: `records` is not device memory of the handles' device");
+    if (eps && !on_device(eps, dev)) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: `eps` is not device memory of the handles' device");
+    const int64_t rows = (int64_t)steps * r->n;
+    CollectActor ca{};
+    int rc = engine_collect_open(r->eng, e->info.ob_dim, e->info.ac_dim, dev, rows, r->stream, &ca);
+    if ((rc = r->from_engine(rc, "sactd3_rollout_collect"))) return rc;
+    // ---- no refusal behind this point
+    const sactd3_rollout_buffers& b = r->buf;
+    CollectLaunch p{};
+    p.A = ca.A; p.T = steps; p.horizon = e->info.horizon; p.mode = mode; p.noise_std = ca.noise_std;
+    p.lo = e->info.min_ac; p.span = e->info.max_ac - e->info.min_ac; p.env_seed = e->cfg.seed;
+    p.L = EnvRec{r->lay.record_len, r->lay.next_off, r->lay.next_width};
+    p.records = records; p.eps = eps; p.obs = b.obs; p.obs_ld = (long long)b.obs_ld; p.actions = b.actions; p.actions_ld = (long long)b.actions_ld;
+    const dim3 grid((unsigned)((e->d.n + EV_TILE - 1) / EV_TILE));
+    with_kind(e->cfg.kind, [&](auto K) { hipLaunchKernelGGL(k_collect_rollout<decltype(K)::value>, grid, dim3(256), 0, ca.A.stream, e->d, p); });
+    // a HIP error behind the opening half of the event pair: the pair is closed (no tick), so that the rollout's stream still stands
+    // behind whatever the learner stream was given, and the call's own error is what is reported
+    auto broken = [&](int code) {
+      (void)engine_collect_close(r->eng, 0, r->stream);
+      return code;
+    };
+    if (const hipError_t he = hipGetLastError())
+      return broken(r->fail(SACTD3_EHIP, std::string("sactd3_rollout_collect: k_collect_rollout: ") + hipGetErrorString(he)));
+    rc = sactd3_rb_extend_records_device(r->eng, records, (int)rows, nullptr, 0);
+    if ((rc = r->from_engine(rc, "sactd3_rb_extend_records_device"))) return broken(rc);
+    const bool drew = mode == SACTD3_ROLLOUT_EXPLORE;
+    rc = engine_collect_close(r->eng, drew ? 1 : 0, r->stream);
+    if ((rc = r->from_engine(rc, "sactd3_rollout_collect"))) return rc;
+    // the counters of `steps` choose + advance calls, and the feature's own
+    r->stats[mode == SACTD3_ROLLOUT_RANDOM ? ROLLOUT_RANDOM_CHOICES : ROLLOUT_POLICY_CHOICES] += steps;
+    r->stats[ROLLOUT_STEPS] += steps;
+    r->stats[ROLLOUT_ROWS] += rows;
+    ++r->collect_stats[0]; r->collect_stats[1] += steps;
+    if (drew) ++r->collect_stats[2];
+    return SACTD3_OK;
+  });
+}
+
+ENV_API int sactd3_rollout_collect_stats(sactd3_rollout* r, int64_t out[4]) {
+  return guarded([&]() -> int {
+    if (!r || !out) return SACTD3_EINVAL;
+    return r->from_engine(engine_collect_stats(r->eng, r->collect_stats, out), "sactd3_rollout_collect_stats");
   });
 }
 

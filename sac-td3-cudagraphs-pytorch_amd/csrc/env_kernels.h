@@ -252,32 +252,21 @@ __global__ __launch_bounds__(256) void k_env_step(EnvDev d, const float* __restr
 // record_len >= next_off + next_width + 2.
 struct EnvRec { int record_len, next_off, next_width; };
 
+// THE record of one step: what env_step_body left (`r`) and the action's bits as given (`araw`) -> the record at `row` (16-byte aligned,
+// record_len floats), by the rule above, element by element through selects (no indexed local array), four elements per store.
+// -> nx: the observation the caller acts on next.  Both kernels that emit records -- k_env_step_rec below, k_collect_rollout
+// (collect_kernels.h) -- are env_step_body plus this.
 template <int KIND>
-__global__ __launch_bounds__(256) void k_env_step_rec(EnvDev d, const float* __restrict__ actions, long long act_ld, EnvRec L,
-                                                      float* __restrict__ records, float* __restrict__ obs, long long obs_ld, int horizon,
-                                                      uint64_t seed) {
+__device__ __forceinline__ void env_write_record(const EnvStepped& r, const uint32_t* araw, const EnvRec& L, float* __restrict__ row, float* nx) {
   constexpr int OB = EnvTask<KIND>::OB, AC = EnvTask<KIND>::AC;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= d.n) return;
-  uint32_t araw[AC];
-#pragma unroll
-  for (int j = 0; j < AC; ++j) araw[j] = __float_as_uint(actions[(size_t)i * act_ld + j]);
-  float a[AC];
-#pragma unroll
-  for (int j = 0; j < AC; ++j) a[j] = __uint_as_float(araw[j]);
-  const EnvStepped r = env_step_body<KIND>(d, i, a, horizon, seed);
-  const float reward = r.reward;
-  const bool terminal = r.terminal, truncated = r.truncated;
-  float so[OB], fin[OB], nx[OB];
+  float so[OB], fin[OB];
   env_observe<KIND>(r.s, r.g0, so);
   env_observe<KIND>(r.fin, r.g0, fin);
   env_observe<KIND>(r.nx, r.g, nx);
-#pragma unroll
-  for (int j = 0; j < OB; ++j) obs[(size_t)i * obs_ld + j] = nx[j];
-  // the record, element by element through selects (no indexed local array), four elements per store
+  const bool truncated = r.truncated;
   const int tail = L.next_off + L.next_width;
-  const uint32_t rbits = __float_as_uint(reward), dbits = __float_as_uint(terminal ? 1.0f : 0.0f);
-  uint4* __restrict__ rec = (uint4*)(records + (size_t)i * (size_t)L.record_len);
+  const uint32_t rbits = __float_as_uint(r.reward), dbits = __float_as_uint(r.terminal ? 1.0f : 0.0f);
+  uint4* __restrict__ rec = (uint4*)row;
   for (int c = 0; c < L.record_len / 4; ++c) {
     uint32_t w[4];
 #pragma unroll
@@ -296,6 +285,26 @@ __global__ __launch_bounds__(256) void k_env_step_rec(EnvDev d, const float* __r
     }
     rec[c] = make_uint4(w[0], w[1], w[2], w[3]);
   }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_env_step_rec(EnvDev d, const float* __restrict__ actions, long long act_ld, EnvRec L,
+                                                      float* __restrict__ records, float* __restrict__ obs, long long obs_ld, int horizon,
+                                                      uint64_t seed) {
+  constexpr int OB = EnvTask<KIND>::OB, AC = EnvTask<KIND>::AC;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.n) return;
+  uint32_t araw[AC];
+#pragma unroll
+  for (int j = 0; j < AC; ++j) araw[j] = __float_as_uint(actions[(size_t)i * act_ld + j]);
+  float a[AC];
+#pragma unroll
+  for (int j = 0; j < AC; ++j) a[j] = __uint_as_float(araw[j]);
+  const EnvStepped r = env_step_body<KIND>(d, i, a, horizon, seed);
+  float nx[OB];
+  env_write_record<KIND>(r, araw, L, records + (size_t)i * (size_t)L.record_len, nx);
+#pragma unroll
+  for (int j = 0; j < OB; ++j) obs[(size_t)i * obs_ld + j] = nx[j];
 }
 
 template <int KIND>

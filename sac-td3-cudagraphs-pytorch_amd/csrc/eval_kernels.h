@@ -73,6 +73,104 @@ __device__ __forceinline__ void ev_ln_relu(float4 v[4], const float* g, const fl
   for (int q = 0; q < 4; ++q) { v[q].x = fmaxf(v[q].x, 0.f); v[q].y = fmaxf(v[q].y, 0.f); v[q].z = fmaxf(v[q].z, 0.f); v[q].w = fmaxf(v[q].w, 0.f); }
 }
 
+// What thread `tid` of a tile's workgroup keeps of the online actor for a whole call: row tid of W1 (K = OB <= 8) and b1[tid]; b2 of the four
+// layer-2 columns it receives; where W2 lies.
+template <int OB>
+struct EvActorRegs {
+  float w1[OB], b1c, b2c[4];
+  const float* W2;
+};
+
+// once per call: R, and the LDS-resident operands -- Ln [4][256] = g1, be1, g2, be2; Whs [4][256] = the head's rows, zero beyond nh
+template <int OB>
+__device__ __forceinline__ void ev_actor_load(const EvalActor& A, int nh, int tid, EvActorRegs<OB>& R, float* Ln, float* Whs) {
+  const float* __restrict__ P = A.P;
+  const int lane = tid & 63, wave = tid >> 6, r = lane & 15;
+#pragma unroll
+  for (int k = 0; k < OB; ++k) R.w1[k] = P[A.W1 + tid * A.ld1 + k];
+  R.b1c = P[A.b1 + tid];
+#pragma unroll
+  for (int tt = 0; tt < 4; ++tt) R.b2c[tt] = P[A.b2 + wave * 64 + tt * 16 + r];
+  Ln[tid] = P[A.g1 + tid]; Ln[EV_HID + tid] = P[A.be1 + tid]; Ln[2 * EV_HID + tid] = P[A.g2 + tid]; Ln[3 * EV_HID + tid] = P[A.be2 + tid];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) Whs[m * EV_HID + tid] = m < nh ? P[A.Wh + min(m, nh - 1) * EV_HID + tid] : 0.f;
+  R.W2 = P + A.W2;
+}
+
+// THE actor pass of one step, steps 2 to 5 of the list above, for the 16 rows of observations in Os (the caller's barrier stands behind
+// their write): -> u[m], the head's output m of row tid >> 4 plus bh[m], in every lane of the row.  Three block barriers; every thread
+// of the workgroup calls it.  k_eval_rollout and k_collect_rollout (collect_kernels.h) are this plus what they do with u.
+template <int OB>
+__device__ __forceinline__ void ev_actor_pass(const EvActorRegs<OB>& R, const float* Os, float* H1, float* H2, const float* Ln, const float* Whs,
+                                              const float bh[4], int ln, int tid, float u[4]) {
+  const int row = tid >> 4, sub = tid & 15;
+  const int lane = tid & 63, wave = tid >> 6, r = lane & 15, kq = lane >> 4;
+  // 2. layer 1, column tid
+#pragma unroll
+  for (int rr = 0; rr < EV_TILE; ++rr) {
+    const float4 oa = *(const float4*)(Os + rr * 8), ob = *(const float4*)(Os + rr * 8 + 4);
+    const float o[8] = {oa.x, oa.y, oa.z, oa.w, ob.x, ob.y, ob.z, ob.w};
+    float z = R.b1c;
+#pragma unroll
+    for (int k = 0; k < OB; ++k) z += o[k] * R.w1[k];
+    H1[rr * EV_AS + tid] = z;
+  }
+  __syncthreads();
+  // 3. LayerNorm + ReLU of H1, in place (a thread rewrites the 16 elements it read)
+  {
+    float4 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = *(const float4*)(H1 + row * EV_AS + 4 * sub + 64 * q);
+    ev_ln_relu(v, Ln, Ln + EV_HID, sub, ln);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) *(float4*)(H1 + row * EV_AS + 4 * sub + 64 * q) = v[q];
+  }
+  __syncthreads();
+  // 4. layer 2: H2[16][64 wave .. + 63] = H1 W2^T + b2.  Lane (r, kq) feeds A[r][k] and B[k][col r] with k = 16 c + 4 kq + m for the
+  //    m-th of four MFMAs (any order of k serves both operands alike); it receives D[4 kq + m'][col r].
+  {
+    float4 av[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) av[c] = *(const float4*)(H1 + r * EV_AS + 16 * c + 4 * kq);
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt) {
+      const int col = wave * 64 + tt * 16 + r;
+      const float4* __restrict__ wrow = (const float4*)(R.W2 + (size_t)col * EV_HID + 4 * kq);
+      float4 wv[16];
+#pragma unroll
+      for (int c = 0; c < 16; ++c) wv[c] = wrow[4 * c];
+      ev_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 16; ++c) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].x, wv[c].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].y, wv[c].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].z, wv[c].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].w, wv[c].w, acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int m = 0; m < 4; ++m) H2[(4 * kq + m) * EV_AS + col] = acc[m] + R.b2c[tt];
+    }
+  }
+  __syncthreads();
+  // 5. LayerNorm + ReLU of H2 in registers, the head
+  {
+    float4 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = *(const float4*)(H2 + row * EV_AS + 4 * sub + 64 * q);
+    ev_ln_relu(v, Ln + 2 * EV_HID, Ln + 3 * EV_HID, sub, ln);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      float part = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 w = *(const float4*)(Whs + m * EV_HID + 4 * sub + 64 * q);
+        part += ((v[q].x * w.x) + (v[q].y * w.y)) + ((v[q].z * w.z) + (v[q].w * w.w));
+      }
+      u[m] = ev_sum16(part) + bh[m];
+    }
+  }
+}
+
 template <int KIND>
 __global__ __launch_bounds__(256) void k_eval_rollout(EnvDev d, EvalLaunch p) {
   constexpr int OB = EnvTask<KIND>::OB, AC = EnvTask<KIND>::AC, NS = EnvTask<KIND>::NS;
@@ -83,7 +181,6 @@ __global__ __launch_bounds__(256) void k_eval_rollout(EnvDev d, EvalLaunch p) {
   __shared__ __attribute__((aligned(16))) float Ln[4 * EV_HID];      // g1, be1, g2, be2
   __shared__ __attribute__((aligned(16))) float Whs[4 * EV_HID];     // the head's rows, zero beyond nh
   const int tid = threadIdx.x, row = tid >> 4, sub = tid & 15;
-  const int lane = tid & 63, wave = tid >> 6, r = lane & 15, kq = lane >> 4;
   const size_t n = (size_t)d.n;
   const int i = blockIdx.x * EV_TILE + row;
   const bool lead = sub == 0;                // the thread that writes row `row` of Os
@@ -92,18 +189,9 @@ __global__ __launch_bounds__(256) void k_eval_rollout(EnvDev d, EvalLaunch p) {
   const float* __restrict__ P = A.P;
   const int nh = A.sac ? 2 * AC : AC;
 
-  // ---- once per call: the parameters that stay in registers / LDS
-  float w1[OB];
-#pragma unroll
-  for (int k = 0; k < OB; ++k) w1[k] = P[A.W1 + tid * A.ld1 + k];
-  const float b1c = P[A.b1 + tid];
-  float b2c[4];
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt) b2c[tt] = P[A.b2 + wave * 64 + tt * 16 + r];
-  Ln[tid] = P[A.g1 + tid]; Ln[EV_HID + tid] = P[A.be1 + tid]; Ln[2 * EV_HID + tid] = P[A.g2 + tid]; Ln[3 * EV_HID + tid] = P[A.be2 + tid];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) Whs[m * EV_HID + tid] = m < nh ? P[A.Wh + min(m, nh - 1) * EV_HID + tid] : 0.f;
-  const float* __restrict__ W2 = P + A.W2;
+  // ---- once per call: the parameters that stay in registers / LDS (ev_actor_load)
+  EvActorRegs<OB> R;
+  ev_actor_load<OB>(A, nh, tid, R, Ln, Whs);
 
   // ---- the owner's env, in registers
   float s[4] = {0.f, 0.f, 0.f, 0.f}, g[2] = {0.f, 0.f};
@@ -142,71 +230,9 @@ __global__ __launch_bounds__(256) void k_eval_rollout(EnvDev d, EvalLaunch p) {
       *(float4*)(Os + row * 8 + 4) = make_float4(o[4], o[5], o[6], o[7]);
     }
     __syncthreads();
-    // 2. layer 1, column tid
-#pragma unroll
-    for (int rr = 0; rr < EV_TILE; ++rr) {
-      const float4 oa = *(const float4*)(Os + rr * 8), ob = *(const float4*)(Os + rr * 8 + 4);
-      const float o[8] = {oa.x, oa.y, oa.z, oa.w, ob.x, ob.y, ob.z, ob.w};
-      float z = b1c;
-#pragma unroll
-      for (int k = 0; k < OB; ++k) z += o[k] * w1[k];
-      H1[rr * EV_AS + tid] = z;
-    }
-    __syncthreads();
-    // 3. LayerNorm + ReLU of H1, in place (a thread rewrites the 16 elements it read)
-    {
-      float4 v[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] = *(const float4*)(H1 + row * EV_AS + 4 * sub + 64 * q);
-      ev_ln_relu(v, Ln, Ln + EV_HID, sub, A.ln);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *(float4*)(H1 + row * EV_AS + 4 * sub + 64 * q) = v[q];
-    }
-    __syncthreads();
-    // 4. layer 2: H2[16][64 wave .. + 63] = H1 W2^T + b2.  Lane (r, kq) feeds A[r][k] and B[k][col r] with k = 16 c + 4 kq + m for the
-    //    m-th of four MFMAs (any order of k serves both operands alike); it receives D[4 kq + m'][col r].
-    {
-      float4 av[16];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) av[c] = *(const float4*)(H1 + r * EV_AS + 16 * c + 4 * kq);
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) {
-        const int col = wave * 64 + tt * 16 + r;
-        const float4* __restrict__ wrow = (const float4*)(W2 + (size_t)col * EV_HID + 4 * kq);
-        float4 wv[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) wv[c] = wrow[4 * c];
-        ev_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].x, wv[c].x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].y, wv[c].y, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].z, wv[c].z, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].w, wv[c].w, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m) H2[(4 * kq + m) * EV_AS + col] = acc[m] + b2c[tt];
-      }
-    }
-    __syncthreads();
-    // 5. LayerNorm + ReLU of H2 in registers, the head
+    // 2. - 5. the actor pass -> the head's outputs
     float u[4];
-    {
-      float4 v[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] = *(const float4*)(H2 + row * EV_AS + 4 * sub + 64 * q);
-      ev_ln_relu(v, Ln + 2 * EV_HID, Ln + 3 * EV_HID, sub, A.ln);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        float part = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 w = *(const float4*)(Whs + m * EV_HID + 4 * sub + 64 * q);
-          part += ((v[q].x * w.x) + (v[q].y * w.y)) + ((v[q].z * w.z) + (v[q].w * w.w));
-        }
-        u[m] = ev_sum16(part) + bh[m];
-      }
-    }
+    ev_actor_pass<OB>(R, Os, H1, H2, Ln, Whs, bh, A.ln, tid, u);
     // 6. the owner: action, records, env step
     if (owner) {
       float a[AC], e[AC];

@@ -351,6 +351,8 @@ def mode_flags(args, plan) -> dict:
         flags["hindsight"] = True
     if getattr(args, "fused_rollout", False):    # (the same: the key is there only when the flag was given)
         flags["fused_rollout"] = True
+    if getattr(args, "collected_rollout", False):           # (the same)
+        flags["collected_rollout"] = True
     if getattr(args, "reset_every", None) is not None:      # (the same)
         flags["reset_every"] = int(args.reset_every)
         flags["reset_what"] = reset_names(getattr(args, "reset_what", None))
@@ -370,7 +372,7 @@ def reset_names(text=None) -> tuple:
 
 def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, prior_fraction, updates_per_step, overlap_acting: bool,
                    device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False,
-                   reset_every=None, reset_what=None, init: str = "torch", num_updates=None) -> dict:
+                   reset_every=None, reset_what=None, init: str = "torch", num_updates=None, collected_rollout: bool = False) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
@@ -379,6 +381,8 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     graph launch; the key is in the result only when it was given.
     `fused_rollout` (--fused_rollout: a loop body as one graph launch, loop.NativeRollout.cycle): asked of loop.rollout_for's own rules
     and of loop.update_plan beside the other keywords; the key is in the result only when it was given.
+    `collected_rollout` (--collected_rollout: a segment as one call, loop.NativeRollout.collect): asked of loop.rollout_for's rules with
+    the job's action_repeat, no env looked at; the key is in the result only when it was given.
     `reset_every` / `reset_what` (--reset_every N [--reset_what actor,critics,alpha]: periodic resets of the networks on the kept ring,
     loop.train reset_every=...): asked of loop.update_plan's table as well -- with `num_updates`, the length of an offline plan, which
     has to reach N; the keys are in the result only when --reset_every was given.  `init` (--init: who makes the initial parameters)
@@ -387,6 +391,9 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
         raise ValueError(f'--init is "torch" or "engine", not {init!r}')
     if fused_rollout and not (native_rollout and not overlap_acting):      # (its two rules stand in front of the env's: no env is looked at)
         loop.rollout_for(None, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, fused_rollout=True)
+    if collected_rollout:                                                  # (the same: its rules stand in front of the env's)
+        loop.collected_rollout_rules(overlap=overlap_acting, native_rollout=native_rollout, fused_rollout=fused_rollout,
+                                     action_repeat=int(cfg.action_repeat), segment_len=int(cfg.segment_len))
     update = dict(fused=not prioritized and n_step == 1 and prior_fraction is None and not hindsight,
                   prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch,
                   prior_fraction=None if prior_fraction is None else float(prior_fraction), updates_per_step=int(updates_per_step))
@@ -397,14 +404,15 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     if reset_every is not None:
         update["reset_every"], update["reset_what"] = int(reset_every), tuple(reset_what if reset_what is not None else loop.RESET_ALL)
     loop.update_plan(cfg, sampler=None, **update, **(dict(num_updates=int(num_updates)) if num_updates is not None else {}))
-    return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats))
+    rollout = dict(collected_rollout=True) if collected_rollout else {}
+    return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout)
 
 
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
             native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, init: str = "torch",
-            reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, **over):
+            reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, collected_rollout: bool = False, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -416,6 +424,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     `hindsight`: the engine relabels goals while it stages each batch (loop.train hindsight=...; needs an env id with a goal layout:
     hindsight_plan refuses otherwise); with `one_launch` the draw and the relabelling are part of the iteration's one graph.
     `fused_rollout`: with `native_rollout`, a loop body past learning_starts as one graph launch (loop.train fused_rollout=True).
+    `collected_rollout`: with `native_rollout`, every segment is one library call (loop.train collected_rollout=True).
     `init`: "engine" = the initial parameters come from the engine's own initialiser under the job's seed (Agent init="engine"), not
     from torch's; `reset_every` [, `reset_what`]: periodic resets of the networks on the kept ring (loop.train / loop.train_offline
     reset_every=...).
@@ -488,7 +497,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
                             updates_per_step=updates_per_step, overlap_acting=overlap_acting, device_env=device_env,
                             native_rollout=native_rollout, policy_stats=policy_stats,
                             **(dict(hindsight=hindsight_keywords(env_id, cfg.num_envs)) if hindsight else {}),
-                            **(dict(fused_rollout=True) if fused_rollout else {}), **resets)
+                            **(dict(fused_rollout=True) if fused_rollout else {}),
+                            **(dict(collected_rollout=True) if collected_rollout else {}), **resets)
         metrics = loop.train(cfg, env, agent, evaluator=ev, **kw, **bias)
     agent.engine.sync()
     dt = time.time() - t0
@@ -520,6 +530,8 @@ def _worker_main(args, plan, flags) -> int:
                     out["one_launch"] = True
             if args.fused_rollout:               # (the same: a key only when the flag was given)
                 out["fused_rollout"] = True
+            if args.collected_rollout:           # (the same)
+                out["collected_rollout"] = True
             for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias"):      # (the same)
                 if k in flags:
                     out[k] = flags[k]
@@ -564,6 +576,10 @@ def main(argv=None) -> int:
     ap.add_argument("--fused_rollout", action="store_true",
                     help="with --device_env --native_rollout: past learning_starts a loop body -- env step, ring append, next action, update -- "
                          "is one library call and one graph launch (loop.train fused_rollout=True); excludes the other draws")
+    ap.add_argument("--collected_rollout", action="store_true",
+                    help="with --device_env --native_rollout: every segment of segment_len env steps -- actions, env steps, ring records, the "
+                         "append -- is one library call and two launches (loop.train collected_rollout=True); excludes --fused_rollout and "
+                         "--overlap_acting, needs action_repeat 1")
     ap.add_argument("--hindsight", action="store_true",
                     help="with an env bundle whose tasks have a goal (native_goal): the engine relabels goals while it stages each batch -- "
                          "hindsight experience replay, the future strategy, window = the task's horizon (loop.train hindsight=...; the "

@@ -179,6 +179,7 @@ class NativeRollout:
             raise self._error(f"sactd3_rollout_create failed ({rc}): {self._lib.sactd3_rollout_last_error(None).decode()}")
         self._choose, self._advance = self._lib.sactd3_rollout_choose, self._lib.sactd3_rollout_advance
         self._random, self._explore = _lib.ROLLOUT_RANDOM, _lib.ROLLOUT_EXPLORE
+        self._slabs, self._max_steps = {}, _lib.COLLECT_MAX_STEPS     # collect(): steps -> (slab, eps or None), made at first use
         env.seed = int(seed)
         self._ck(self._lib.sactd3_rollout_reset(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.steps = 0
@@ -242,6 +243,42 @@ class NativeRollout:
         if do_actor:
             agent.actor_updates_so_far += delay
 
+    def collect(self, steps: int, mode: Optional[int] = None, eps: bool = False):
+        """`steps` x (`choose()`, `advance()`) as ONE ctypes call and two launches (include/sactd3_rollout_collect.h:
+        sactd3_rollout_collect): the collect kernel rolls all envs for `steps` steps under the current policy -- or, with the random
+        phase's draw, bit for bit as the call sequence does -- and writes every transition as a ring record into a slab, time-major;
+        the engine's own append takes the slab.  `mode` (None: random while `agent.timesteps_so_far < learning_starts`, else explore; or
+        one of _lib.ROLLOUT_RANDOM / _EXPLORE / _EXPLOIT).  The slab [steps * n, record_floats] -- and with `eps=True` the draws
+        [steps, n, a] -- are allocated once per `steps` and returned as VIEWS the next call of the same `steps` overwrites:
+        -> records, or (records, eps).  For `action_repeat` 1 (the caller decides that: train(collected_rollout=True)).  ValueError for
+        `steps` outside [1, 4096], before anything is allocated; the library's own refusals -- `steps * n` above the ring slots an append
+        may use among them -- come as EngineError from the call."""
+        steps = int(steps)
+        if not 1 <= steps <= self._max_steps:
+            raise ValueError(f"collect: steps must be in [1, {self._max_steps}], got {steps}")
+        if mode is None:
+            mode = self._random if self.agent.timesteps_so_far < self.learning_starts else self._explore
+        slab = self._slabs.get(steps)
+        if slab is None or (eps and slab[1] is None):
+            import torch
+            n, dev = self.env.num_envs, self.obs.device
+            rec = slab[0] if slab is not None else torch.zeros((steps * n, self.records.shape[1]), dtype=torch.float32, device=dev)
+            slab = self._slabs[steps] = (rec, torch.zeros((steps, n, self.actions.shape[1]), dtype=torch.float32, device=dev) if eps else None)
+        rec, draws = slab
+        rc = self._lib.sactd3_rollout_collect(self._h, int(mode), steps, rec.data_ptr(), draws.data_ptr() if eps else None)
+        if rc:
+            self._ck(rc)
+        self.steps += steps
+        return (rec, draws) if eps else rec
+
+    def collect_stats(self) -> Dict[str, int]:
+        """counters of the handle's collected segments (sactd3_rollout_collect_stats); `collect_ctr` is a device word: waits for the
+        engine's stream"""
+        import ctypes as C
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.sactd3_rollout_collect_stats(self._h, out))
+        return dict(zip(("calls", "env_steps", "calls_that_drew", "collect_ctr"), (int(v) for v in out)))
+
     def cycle_stats(self) -> Dict[str, int]:
         """host counters of the handle's cycles (sactd3_rollout_cycle_stats), and `clamped`: appends that found a ring length or cursor
         outside the ring in device memory (sactd3_rollout_cycle_clamped: 0 in every sound run; waits for the engine's stream)"""
@@ -266,12 +303,32 @@ def segment(env, agent, seed: int, segment_len: int, learning_starts: int, actio
         ro.advance()
 
 
-def rollout_for(env, *, overlap: bool, device_env: bool, native_rollout: bool, fused_rollout: bool = False):
+def collected_rollout_rules(*, overlap: bool, native_rollout: bool, fused_rollout: bool, action_repeat: int, segment_len: int) -> None:
+    """What `collected_rollout=True` (a segment as one `NativeRollout.collect`) needs and excludes, looked at without an env: ValueError."""
+    if not native_rollout:
+        raise ValueError("collected_rollout=True needs native_rollout=True: the segment is a call of the native rollout's handle")
+    if fused_rollout:
+        raise ValueError("collected_rollout=True and fused_rollout=True exclude each other: a cycle is one env step, a collect a whole segment")
+    if overlap:
+        raise ValueError("collected_rollout=True and overlap=True exclude each other: the segment acts inside its own launch, on the learner stream")
+    if int(action_repeat) != 1:
+        raise ValueError("collected_rollout=True needs action_repeat == 1: the collect kernel chooses an action with every step")
+    if int(segment_len) < 1:
+        raise ValueError("collected_rollout=True needs segment_len >= 1")
+
+
+def rollout_for(env, *, overlap: bool, device_env: bool, native_rollout: bool, fused_rollout: bool = False,
+                collected_rollout: bool = False, action_repeat: int = 1, segment_len: int = 1):
     """Which of the three classes above drives `env` for train(): refuses what excludes each other, constructs nothing.  -> None for the
     plain host case (segment() makes its own `Rollout`), else what to call with (env, agent, seed, learning_starts, action_repeat).
     Both device rollouts act on the learner stream, so neither goes with `overlap`; the native one needs an env on the GPU that emits
     ring records (`step_records`: envs.NativeVecEnv).  `fused_rollout` (a loop body as one `NativeRollout.cycle`) needs the native
-    rollout -- its two rules come first, before `env` is looked at; what it needs of the update keywords is `update_plan`'s."""
+    rollout -- its two rules come first, before `env` is looked at; what it needs of the update keywords is `update_plan`'s.
+    `collected_rollout` (a segment as one `NativeRollout.collect`) needs the native rollout and `action_repeat` 1, excludes
+    `fused_rollout` and `overlap` and takes any `segment_len` >= 1 (`collected_rollout_rules`, in front of the env's as well)."""
+    if collected_rollout:
+        collected_rollout_rules(overlap=overlap, native_rollout=native_rollout, fused_rollout=fused_rollout, action_repeat=action_repeat,
+                                segment_len=segment_len)
     if fused_rollout and not native_rollout:
         raise ValueError("fused_rollout=True needs native_rollout=True: the cycle is a call of the native rollout's handle")
     if fused_rollout and overlap:
@@ -579,7 +636,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           n_step: int = 1, one_launch: bool = False, prior_fraction: Optional[float] = None,
           updates_per_step: int = 1, policy_stats: int = 0, native_rollout: bool = False,
           hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False,
-          reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, q_bias: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+          reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, q_bias: Optional[Dict[str, Any]] = None,
+          collected_rollout: bool = False) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -600,6 +658,16 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     wherever the step count in front of it is at or past `learning_starts`, so that its choice is an exploring one and an update
     follows; every other body -- the random phase, the step that crosses `learning_starts` -- goes through the call sequence, and
     with `updates_per_step` > 1 the further updates do.  The run ends bit for bit as the native_rollout=True run does.  Off by default.
+    `collected_rollout=True` (needs native_rollout=True and action_repeat == 1; excludes fused_rollout and overlap; any segment_len >= 1):
+    a segment -- segment_len steps of all envs, their actions, their ring records, the append -- is ONE library call and two launches
+    (`NativeRollout.collect`) in place of segment_len choose / advance pairs; everything behind it in a loop body is unchanged, so every
+    update form, `updates_per_step`, resets and the vitals work with it, pinned rows and engine-owned priorities included (the append
+    is the engine's own).  One semantic difference: the action that opens a segment is chosen AFTER the update in front of it, with
+    that update's parameters, not before it (`segment()` chooses, then yields) -- and a policy action comes from the collect kernel,
+    which sums in another order than `predict`, with draws of a stream of its own.  So the run is not bit for bit the
+    native_rollout=True run; its random phase is.  A segment must fit the ring slots an append may use (segment_len * num_envs <=
+    rb_capacity minus the pinned rows): that is the engine's to know and is refused by the first `collect`, as an EngineError, not here.
+    Off by default.
     `sampler` (a ProportionalSampler): prioritised replay, call by call on the device -- the sampler's rows and importance weights
     through `rb.sample_at`, the critic update weighted by them, its TD errors (`agent.td_errors`) back into the sampler's priorities;
     the actor updates train on the same rows, unweighted.
@@ -636,7 +704,9 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
                        prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
                        reset_every=reset_every, reset_what=reset_what)
     resets = plan.reset is not None
-    make_rollout = rollout_for(env, overlap=overlap, device_env=device_env, native_rollout=native_rollout, fused_rollout=fused_rollout)
+    make_rollout = rollout_for(env, overlap=overlap, device_env=device_env, native_rollout=native_rollout, fused_rollout=fused_rollout,
+                               **(dict(collected_rollout=True, action_repeat=cfg.action_repeat, segment_len=cfg.segment_len)
+                                  if collected_rollout else {}))
     if plan.priorities is not None:                                       # (nothing above touched the agent's engine)
         agent.rb.enable_priorities(**plan.priorities)
     if plan.hindsight is not None:
@@ -658,6 +728,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
             if cycled:
                 ro.cycle(i)
                 i += 1
+            elif collected_rollout:
+                ro.collect(cfg.segment_len)
             else:
                 next(seg_gen)
             agent.timesteps_so_far += step_rows
