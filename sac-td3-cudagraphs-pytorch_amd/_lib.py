@@ -78,6 +78,10 @@ STREAM_COLLECT = 0x900              # csrc/collect_kernels.h: SACTD3_STREAM_COLL
 INIT_SYMBOLS = ["sactd3_init_params", "sactd3_init_stats"]
 INIT_ACTOR, INIT_CRITICS, INIT_ALPHA = 1, 2, 4   # sactd3_init_params `what` (SACTD3_INIT_*)
 INIT_ALL = INIT_ACTOR | INIT_CRITICS | INIT_ALPHA
+# every symbol include/sactd3_dormant.h declares (tests/test_dormant_host.py checks the header against this list)
+DORMANT_SYMBOLS = ["sactd3_dormant_scan_device", "sactd3_dormant_stats", "sactd3_redo"]
+DORMANT_ACTOR, DORMANT_CRITICS = 1, 2   # `what` of sactd3_dormant_scan_device / sactd3_redo (SACTD3_DORMANT_*)
+DORMANT_PAIRS = ("actor_l1", "actor_l2", "q1_l1", "q1_l2", "q2_l1", "q2_l2")   # the six (net, layer) pairs, net-major
 # every symbol include/sactd3_eval.h declares (tests/test_eval_rollout_host.py checks the header against this list)
 EVAL_SYMBOLS = ["sactd3_eval_rollout", "sactd3_eval_stats"]
 EVAL_GREEDY, EVAL_SAMPLE = 0, 1     # sactd3_eval_config.mode (SACTD3_EVAL_*)
@@ -347,6 +351,13 @@ def load_library():
     }
     assert sorted(init_sig) == sorted(INIT_SYMBOLS)
     sig.update(init_sig)
+    dormant_sig = {
+        "sactd3_dormant_scan_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_uint32, C.c_float, vp, vp, C.c_int]),
+        "sactd3_dormant_stats": (C.c_int, [vp, i64p]),
+        "sactd3_redo": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_uint32]),
+    }
+    assert sorted(dormant_sig) == sorted(DORMANT_SYMBOLS)
+    sig.update(dormant_sig)
     eval_sig = {
         "sactd3_eval_rollout": (C.c_int, [vp, vp, C.POINTER(CEvalConfig), C.POINTER(CEvalOut), vp, C.c_int]),
         "sactd3_eval_stats": (C.c_int, [vp, i64p]),

@@ -645,6 +645,8 @@ class Agent:
         ob_dim, ac_dim = int(net_shapes["ob_shape"][-1]), int(net_shapes["ac_shape"][-1])
         self.device, self.hps = device, hps
         self.resets_so_far = 0      # reset_networks() calls: run-time state, not part of a checkpoint
+        self.recycles_so_far = 0    # recycle_dormant() calls: the same
+        self._dormant_gen = None    # dormant()'s index generator, made at its first call
         self.min_ac, self.max_ac = np.asarray(min_ac, np.float32), np.asarray(max_ac, np.float32)
         self.timesteps_so_far = 0
         self.actor_updates_so_far = 0
@@ -694,6 +696,40 @@ class Agent:
         self.engine.init_params(bits, epoch=self.resets_so_far + 1)
         self.resets_so_far += 1
         return self.resets_so_far
+
+    def dormant(self, rows: int = 1024, tau: float = 0.025, seed: Optional[int] = None, what=("actor", "critics")) -> Dict[str, float]:
+        """The dormant-neuron ratio (Sokar et al. 2023) of the online nets over `rows` ring rows drawn uniformly on the device with a
+        torch generator of this method's own -- seeded by `seed` at its first use (None: the engine's seed); the training index
+        stream is not touched and training does not see the call (Engine.dormant_scan).  -> the fraction of hidden units whose
+        score is at or below `tau`, per net asked for: {"actor": ., "critics": .} (the critics: both nets).
+        The masks stay in the engine for one recycle_dormant()."""
+        import torch
+        eng = self.engine
+        dev = torch.device("cuda", eng.cfg.device_id)
+        if self._dormant_gen is None:
+            self._dormant_gen = torch.Generator(device=dev)
+            self._dormant_gen.manual_seed(int(eng.cfg.seed if seed is None else seed))
+        n = len(self.rb) if self.rb is not None else eng.rb_len()
+        if n < 1:
+            raise ValueError("dormant: the replay ring is empty")
+        index = torch.randint(0, n, (int(rows),), generator=self._dormant_gen, device=dev, dtype=torch.int64)
+        got = eng.dormant_scan(index, what=what, tau=tau)["dormant"]
+        bits = eng._dormant_bits(what)
+        out = {}
+        if bits & _lib.DORMANT_ACTOR:
+            out["actor"] = (got["actor_l1"] + got["actor_l2"]) / 512.0
+        if bits & _lib.DORMANT_CRITICS:
+            out["critics"] = (got["q1_l1"] + got["q1_l2"] + got["q2_l1"] + got["q2_l2"]) / 1024.0
+        return out
+
+    def recycle_dormant(self, what=("actor", "critics")) -> int:
+        """ReDo: re-initialise the hidden units the last dormant() marked in the nets `what` names and keep everything else
+        (Engine.redo), at epoch recycles_so_far + 1 under the engine's seed.  -> recycles_so_far, which counts these calls; like
+        resets_so_far it is run-time state and is NOT saved in a checkpoint."""
+        epoch = self.recycles_so_far + 1
+        self.engine.redo(what, epoch=epoch)
+        self.recycles_so_far = epoch
+        return epoch
 
     # -- parameters
     def load_flat(self, actor: np.ndarray, critics: np.ndarray, also_targets: bool = True) -> None:

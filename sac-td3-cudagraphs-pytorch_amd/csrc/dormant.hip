@@ -1,0 +1,47 @@
+// The dormant-neuron scan's and the ReDo recycler's translation unit: their four kernels (dormant_kernels.h) and the launchers
+// engine.hip calls (dormant.h).  A translation unit of its own inside libsactd3_hip.so, as param_init.hip and hindsight.hip are:
+// engine.hip gains no kernel.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "dormant_kernels.h"
+
+// what the kernels' address arithmetic relies on; the engine's checks (sactd3_dormant_scan_device, sactd3_redo) come first, these stand
+// between any caller and the launch
+static bool net_ok(const DormantNet& N, bool written) {
+  if (!N.P || ((uintptr_t)N.P & 15u) || N.id < 0 || N.id >= DM_NETS || N.K < 1 || N.ld1 < N.K || N.ld1 < 4 || N.nh < 1) return false;
+  if (written && (!N.M || !N.V || (((uintptr_t)N.M | (uintptr_t)N.V) & 15u))) return false;
+  if ((N.ld1 | N.W1 | N.b1 | N.g1 | N.be1 | N.W2 | N.b2 | N.g2 | N.be2 | N.Wh) & 3) return false;
+  return N.W1 >= 0 && N.W1 + (long)DM_HID * N.ld1 <= N.b1 && N.b1 + DM_HID <= N.g1 && N.g1 + DM_HID <= N.be1 && N.be1 + DM_HID <= N.W2 &&
+         N.W2 + DM_HID * DM_HID <= N.b2 && N.b2 + DM_HID <= N.g2 && N.g2 + DM_HID <= N.be2 && N.be2 + DM_HID <= N.Wh;
+}
+static bool nets_ok(const DormantNet* net, int nnets, bool written) {
+  if (nnets < 1 || nnets > DM_NETS) return false;
+  for (int i = 0; i < nnets; ++i)
+    if (!net_ok(net[i], written) || (i > 0 && net[i].id <= net[i - 1].id)) return false;
+  return true;
+}
+static bool state_ok(const DormantState& s) { return s.part && s.slots && s.rows && s.scores && s.mask && s.words; }
+
+hipError_t dormant_scan_launch(const DormantScanArgs& p, hipStream_t stream) {
+  if (!nets_ok(p.net, p.nnets, false) || !state_ok(p.st)) return hipErrorInvalidValue;
+  if (!p.ring || ((uintptr_t)p.ring & 15u) || !p.idx || p.idx_ld < 1 || p.n < 1 || p.n > DM_MAXN || p.len < 1 || (p.rec_f & 3)) return hipErrorInvalidValue;
+  if (!(p.tau >= 0.f) || p.tau == __builtin_inff()) return hipErrorInvalidValue;
+  for (int i = 0; i < p.nnets; ++i)
+    if (p.net[i].ld1 > p.rec_f) return hipErrorInvalidValue;      // (a row's 16-byte reads stay inside its record)
+  hipLaunchKernelGGL(k_dormant_compact, dim3(1), dim3(256), 0, stream, p);
+  hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return he;
+  hipLaunchKernelGGL(k_dormant_scan, dim3(dormant_groups(p.n), p.nnets), dim3(256), 0, stream, p);
+  he = hipGetLastError();
+  if (he != hipSuccess) return he;
+  hipLaunchKernelGGL(k_dormant_finish, dim3(2, p.nnets), dim3(256), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t dormant_redo_launch(const RedoArgs& p, hipStream_t stream) {
+  if (!nets_ok(p.net, p.nnets, true) || !state_ok(p.st)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_redo_recycle, dim3(DM_HID / 16, 2, p.nnets), dim3(256), 0, stream, p);
+  return hipGetLastError();
+}

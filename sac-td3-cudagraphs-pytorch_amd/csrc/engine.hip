@@ -35,6 +35,9 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 // ... and the parameter initialiser (param_init.hip; its C ABI is include/sactd3_init.h, defined at the end of the extern "C" block below)
 #include "param_init.h"
 #include "../../include/sactd3_init.h"
+// ... and the dormant-neuron scan with its recycler (dormant.hip; its C ABI is include/sactd3_dormant.h, defined behind the initialiser's)
+#include "dormant.h"
+#include "../../include/sactd3_dormant.h"
 // ... and the evaluation rollout, whose kernel is compiled with the env kernels (env.hip): host code only here, at the end of this file
 #include "eval_rollout.h"
 // ... and the collected rollout segment, split the same way (collect_rollout.h)
@@ -317,6 +320,14 @@ struct sactd3_engine {
   // A training segment in one launch (sactd3_rollout_collect; include/sactd3_rollout_collect.h; the kernel: collect_kernels.h, compiled
   // in env.hip).  cl_ctr: the device word that numbers the feature's draws (stream 0x900), made at the first call.
   int* cl_ctr = nullptr;
+  // The dormant-neuron scan and ReDo recycling (sactd3_dormant_scan_device / sactd3_redo; include/sactd3_dormant.h; device code:
+  // dormant_kernels.h, a translation unit of its own).  dm: the workgroups' partial sums and row counts, the scores, the masks and the
+  // device words, all made at the first scan -- an engine that never scans holds nothing more than before.  dm_scanned[0 actor, 1 critics]:
+  // a scan of that family has run and neither a redo nor sactd3_init_params has used up / outdated its mask.
+  // dm_host: {scans, redo calls}.
+  DormantState dm{};
+  bool dm_scanned[2] = {false, false};
+  int64_t dm_host[2] = {};
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -4157,6 +4168,8 @@ int sactd3_init_params(sactd3_engine* e, uint32_t what, uint64_t seed, uint32_t 
   const hipError_t he = param_init_fanout_launch(f, e->stream);
   if (he != hipSuccess) return e->fail(SACTD3_EHIP, "init_params: k_init_fanout", he);
   ++e->init_host[0]; e->init_host[1] = g.n;
+  if (what & SACTD3_INIT_ACTOR) e->dm_scanned[0] = false;                   // a mask of the parameters of before is no mask of these
+  if (what & SACTD3_INIT_CRITICS) e->dm_scanned[1] = false;
   return 0;
 }
 
@@ -4164,6 +4177,102 @@ int sactd3_init_stats(sactd3_engine* e, int64_t out[4]) {
   if (!e || !out) return SACTD3_EINVAL;
   const int64_t host[3] = {e->init_host[0], e->init_host[1], 0};
   return stats_with_words(e, host, e->init_redrawn, 1, 2, out);
+}
+
+// ---- the dormant-neuron scan and ReDo recycling (include/sactd3_dormant.h)
+// the online nets `what` names (a sum of SACTD3_DORMANT_*), in ascending id, as the kernels of dormant.hip read them
+static int dormant_nets(sactd3_engine* e, uint32_t what, DormantNet* out) {
+  int n = 0;
+  for (int id = 0; id < DM_NETS; ++id) {      // 0: the actor; 1, 2: the critics
+    if (!(what & (id ? SACTD3_DORMANT_CRITICS : SACTD3_DORMANT_ACTOR))) continue;
+    const NetLayout& L = id ? e->Lc : e->La;
+    const size_t off = id ? (size_t)(id - 1) * L.size : 0;
+    DormantNet N{};
+    N.P = (id ? e->Pc : e->Pa) + off; N.M = (id ? e->Mc : e->Ma) + off; N.V = (id ? e->Vc : e->Va) + off;
+    N.id = id; N.K = L.K; N.ld1 = L.ld1; N.nh = L.nh;
+    N.W1 = L.W1; N.b1 = L.b1; N.g1 = L.g1; N.be1 = L.be1; N.W2 = L.W2; N.b2 = L.b2; N.g2 = L.g2; N.be2 = L.be2; N.Wh = L.Wh;
+    out[n++] = N;
+  }
+  return n;
+}
+static int dormant_what(sactd3_engine* e, uint32_t what, const char* who) {
+  if (what == 0 || (what & ~(uint32_t)(SACTD3_DORMANT_ACTOR | SACTD3_DORMANT_CRITICS))) {
+    e->err = std::string(who) + ": `what` is a non-empty sum of SACTD3_DORMANT_ACTOR, _CRITICS";
+    return SACTD3_EINVAL;
+  }
+  return 0;
+}
+
+int sactd3_dormant_scan_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, int n, uint32_t what, float tau,
+                               float* scores, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first: a refused call has launched, allocated, counted and marked nothing
+  if (!idx) return e->fail(SACTD3_EINVAL, "dormant_scan_device: `idx` is NULL");
+  if (n < 1 || n > DM_MAXN) return e->fail(SACTD3_EINVAL, "dormant_scan_device: 1 <= n <= 65536 required");
+  if (idx_ld < 1) return e->fail(SACTD3_EINVAL, "dormant_scan_device: row stride of `idx` is below its width");
+  RCCHK(dormant_what(e, what, "dormant_scan_device"));
+  if (!(tau >= 0.f) || !std::isfinite(tau)) return e->fail(SACTD3_EINVAL, "dormant_scan_device: tau must be finite and >= 0");
+  if (flags & ~(SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) return e->fail(SACTD3_EINVAL, "dormant_scan_device: unknown flag");
+  USE_DEVICE(e);
+  RCCHK(device_ptr_check(e, idx, "dormant_scan_device", "idx"));
+  if (scores) RCCHK(device_ptr_check(e, scores, "dormant_scan_device", "scores"));
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "dormant_scan_device: buffer is empty");
+  RCCHK(first_use_alloc(e, &e->dm.part, (size_t)DM_NETS * 2 * DM_MAXG * DM_HID, false));      // (never zeroed: a scan writes every partial it reads)
+  RCCHK(first_use_alloc(e, &e->dm.slots, (size_t)DM_MAXN, false));                            // (the same: k_dormant_compact writes what the scan reads)
+  RCCHK(first_use_alloc(e, &e->dm.rows, 4, false));
+  RCCHK(first_use_alloc(e, &e->dm.scores, (size_t)DM_PAIRS * DM_HID));
+  RCCHK(first_use_alloc(e, &e->dm.mask, (size_t)DM_PAIRS * DM_HID));
+  RCCHK(first_use_alloc(e, &e->dm.words, (size_t)DM_WORDS));
+  DormantScanArgs g{};
+  g.ring = e->ring; g.rec_f = e->rec_f; g.len = (int)e->rb_len;
+  g.idx = (const long long*)idx; g.idx_ld = (long)idx_ld; g.n = n; g.ln = e->cfg.layer_norm; g.tau = tau;
+  g.nnets = dormant_nets(e, what, g.net); g.st = e->dm; g.out = scores;
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  const int ordered = (flags & (SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) ? SACTD3_SRC_ORDERED : 0;      // (one pair of events serves both sides)
+  RCCHK(src_order_begin(e, caller, ordered));
+  const hipError_t he = dormant_scan_launch(g, e->stream);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "dormant_scan_device: k_dormant_scan / k_dormant_finish", he);
+  RCCHK(src_order_end(e, caller, ordered));
+  if (what & SACTD3_DORMANT_ACTOR) e->dm_scanned[0] = true;
+  if (what & SACTD3_DORMANT_CRITICS) e->dm_scanned[1] = true;
+  ++e->dm_host[0];
+  return 0;
+}
+
+int sactd3_dormant_stats(sactd3_engine* e, int64_t out[16]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int w[DM_WORDS] = {};
+  if (e->dm.words) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(w, e->dm.words, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  out[0] = e->dm_host[0]; out[1] = w[DM_W_VALID]; out[2] = w[DM_W_REFUSED];
+  for (int i = 0; i < DM_PAIRS; ++i) out[3 + i] = w[DM_W_COUNT + i];
+  out[9] = e->dm_host[1]; out[10] = w[DM_W_RECYCLED]; out[11] = w[DM_W_LEFT_ZERO];
+  return 0;
+}
+
+int sactd3_redo(sactd3_engine* e, uint32_t what, uint64_t seed, uint32_t epoch) {
+  if (!e) return SACTD3_EINVAL;
+  RCCHK(dormant_what(e, what, "redo"));
+  if (((what & SACTD3_DORMANT_ACTOR) && !e->dm_scanned[0]) || ((what & SACTD3_DORMANT_CRITICS) && !e->dm_scanned[1]))
+    return e->fail(SACTD3_ESTATE, "redo: no scan of these nets since their last redo / init_params (sactd3_dormant_scan_device first)");
+  if (e->act_inflight) return e->fail(SACTD3_ESTATE, "redo: an acting call is in flight (sactd3_predict_end first)");
+  USE_DEVICE(e);
+  CHAIN_BREAK(e);
+  if (what & SACTD3_DORMANT_ACTOR) RCCHK(actor_write_begin(e));              // the next acting call waits for this one
+  if (what & SACTD3_DORMANT_CRITICS) e->grads_stale[0] = true;               // the gradient arenas no longer belong to these parameters
+  if (what & SACTD3_DORMANT_ACTOR) e->grads_stale[1] = true;
+  RedoArgs g{};
+  g.nnets = dormant_nets(e, what, g.net); g.st = e->dm; g.seed = seed; g.epoch = epoch;
+  const hipError_t he = dormant_redo_launch(g, e->stream);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "redo: k_redo_recycle", he);
+  if (what & SACTD3_DORMANT_ACTOR) e->dm_scanned[0] = false;                 // a mask is good for one redo
+  if (what & SACTD3_DORMANT_CRITICS) e->dm_scanned[1] = false;
+  ++e->dm_host[1];
+  return 0;
 }
 
 }  // extern "C"

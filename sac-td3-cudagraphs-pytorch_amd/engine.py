@@ -194,6 +194,60 @@ class Engine:
         st = self._stats(self.lib.sactd3_init_stats, ("calls", "matrices", "columns_redrawn", "reserved0"))
         return {k: st[k] for k in ("calls", "matrices", "columns_redrawn")}
 
+    # -- the dormant-neuron ratio over ring rows and ReDo recycling (include/sactd3_dormant.h)
+    @staticmethod
+    def _dormant_bits(what) -> int:
+        names = [w.strip() for w in what.split(",")] if isinstance(what, str) else list(what)
+        known = {"actor": _lib.DORMANT_ACTOR, "critics": _lib.DORMANT_CRITICS}
+        if not names or any(w not in known for w in names):
+            raise ValueError(f"dormant: `what` is a non-empty choice of {sorted(known)}, got {what!r}")
+        bits = 0
+        for w in names:
+            bits |= known[w]
+        return bits
+
+    def dormant_scan(self, index, what=("actor", "critics"), tau: float = 0.025, scores: bool = False) -> Dict[str, object]:
+        """sactd3_dormant_scan_device: the dormant-neuron scores (Sokar et al. 2023, eq. 1) of the online nets `what` names over the
+        ring rows `index` (a 1-D int64 array in this device's memory, up to 65536 rows; a slot outside the ring is refused and
+        counted, never read).  The kernels read the ring records where they are and run on the engine's stream, ordered on the GPU
+        against torch's current stream; training and acting do not see the call.  One host wait, for the counters.
+        -> {"dormant": {pair: count} for the six pairs of _lib.DORMANT_PAIRS, "valid_rows", "refused_rows" (of this scan)
+            [, "scores": a [6, 256] float32 CUDA tensor; rows of nets not asked for are 0]}"""
+        import torch
+        cai = getattr(index, "__cuda_array_interface__", None)
+        if cai is None or cai["typestr"] != "<i8" or len(cai["shape"]) != 1:
+            raise TypeError("dormant_scan: `index` is a 1-D int64 array in the memory of the engine's device")
+        n, strides = int(cai["shape"][0]), cai.get("strides")
+        ld = 1 if strides is None or n <= 1 else strides[0] // 8
+        if ld < 1 or (strides is not None and n > 1 and strides[0] % 8):
+            raise ValueError("dormant_scan: `index` needs a positive stride in whole elements")
+        dev = torch.device("cuda", self.cfg.device_id)
+        out = torch.zeros(6, 256, dtype=torch.float32, device=dev) if scores else None
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+        self._ck(self.lib.sactd3_dormant_scan_device(self._h, _vp(int(cai["data"][0])), ld, n, self._dormant_bits(what), float(tau),
+                                                     _vp(out.data_ptr() if scores else 0), _vp(stream), _lib.SRC_ORDERED | _lib.DST_ORDERED))
+        st = self.dormant_stats()
+        got = {"dormant": dict(st["dormant"]), "valid_rows": st["valid_rows"], "refused_rows": n - st["valid_rows"]}      # (a row is one or the other)
+        if scores:
+            got["scores"] = out
+        return got
+
+    def redo(self, what, seed: Optional[int] = None, epoch: int = 1) -> None:
+        """sactd3_redo: recycle the neurons the last scan marked in the nets `what` names (ReDo): a fresh incoming row at the
+        initialiser's row norm from Philox stream 0xA00 at (seed, epoch), bias 0, LayerNorm weight 1 / bias 0, outgoing column 0,
+        Adam's moments 0 at exactly those elements; targets untouched.  seed None: the engine's configured seed.  Enqueued on the
+        engine's stream: no wait, no copy.  A mask is good for one redo: EngineError without a scan since the last one."""
+        seed = self.cfg.seed if seed is None else seed
+        self._ck(self.lib.sactd3_redo(self._h, self._dormant_bits(what), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch)))
+
+    def dormant_stats(self) -> Dict[str, object]:
+        """counters of the scan and the recycler (sactd3_dormant_stats; waits for the engine's stream: most live on the device)"""
+        out = (C.c_int64 * 16)()
+        self._ck(self.lib.sactd3_dormant_stats(self._h, out))
+        v = [int(x) for x in out]
+        return {"scans": v[0], "valid_rows": v[1], "rows_refused": v[2], "dormant": dict(zip(_lib.DORMANT_PAIRS, v[3:9])),
+                "redo_calls": v[9], "recycled": v[10], "rows_left_zero": v[11]}
+
     # -- replay
     def _rows(self, obs, act, rew, nobs, done):
         o, a = self.cfg.ob_dim, self.cfg.ac_dim

@@ -358,6 +358,14 @@ def mode_flags(args, plan) -> dict:
         flags["reset_what"] = reset_names(getattr(args, "reset_what", None))
     elif getattr(args, "reset_what", None) is not None:
         raise ValueError("--reset_what needs --reset_every N: it names the networks that rule resets")
+    if getattr(args, "dormant", None) is not None:          # (the same)
+        flags["dormant"] = int(args.dormant)
+        if getattr(args, "dormant_tau", None) is not None:
+            flags["dormant_tau"] = float(args.dormant_tau)
+    elif getattr(args, "dormant_tau", None) is not None:
+        raise ValueError("--dormant_tau needs --dormant ROWS: it is the threshold of that scan")
+    if getattr(args, "redo_every", None) is not None:       # (the same; without --dormant: refused by train_keywords)
+        flags["redo_every"] = int(args.redo_every)
     if getattr(args, "init", "torch") != "torch":           # (the same)
         flags["init"] = args.init
     if getattr(args, "eval_one_launch", False) or getattr(args, "q_bias", 0):      # (the same: keys only when a flag was given; every job
@@ -372,7 +380,8 @@ def reset_names(text=None) -> tuple:
 
 def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, prior_fraction, updates_per_step, overlap_acting: bool,
                    device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False,
-                   reset_every=None, reset_what=None, init: str = "torch", num_updates=None, collected_rollout: bool = False) -> dict:
+                   reset_every=None, reset_what=None, init: str = "torch", num_updates=None, collected_rollout: bool = False,
+                   dormant=None, dormant_tau=None, redo_every=None) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
@@ -386,7 +395,10 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     `reset_every` / `reset_what` (--reset_every N [--reset_what actor,critics,alpha]: periodic resets of the networks on the kept ring,
     loop.train reset_every=...): asked of loop.update_plan's table as well -- with `num_updates`, the length of an offline plan, which
     has to reach N; the keys are in the result only when --reset_every was given.  `init` (--init: who makes the initial parameters)
-    is the Agent's keyword, not loop.train's: checked here, never in the result."""
+    is the Agent's keyword, not loop.train's: checked here, never in the result.
+    `dormant` [, `dormant_tau`] (--dormant ROWS [--dormant_tau T]: the dormant-neuron ratio at every evaluation, loop.train dormant=...)
+    and `redo_every` (--redo_every N: ReDo recycling on that scan): asked of loop.redo_rule; the keys are in the result only when the
+    flags were given."""
     if init not in ("torch", "engine"):
         raise ValueError(f'--init is "torch" or "engine", not {init!r}')
     if fused_rollout and not (native_rollout and not overlap_acting):      # (its two rules stand in front of the env's: no env is looked at)
@@ -405,14 +417,28 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
         update["reset_every"], update["reset_what"] = int(reset_every), tuple(reset_what if reset_what is not None else loop.RESET_ALL)
     loop.update_plan(cfg, sampler=None, **update, **(dict(num_updates=int(num_updates)) if num_updates is not None else {}))
     rollout = dict(collected_rollout=True) if collected_rollout else {}
-    return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout)
+    watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates)
+    return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout, **watch)
+
+
+def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_every=None, num_updates=None) -> dict:
+    """--dormant ROWS [--dormant_tau T] [--redo_every N] as the keywords loop.train and loop.train_offline take, asked of loop.redo_rule
+    (ValueError for what they would refuse); {} without the flags"""
+    kw = {}
+    if dormant is not None:
+        kw["dormant"] = dict(rows=int(dormant), **(dict(tau=float(dormant_tau)) if dormant_tau is not None else {}))
+    if redo_every is not None:
+        kw["redo_every"] = int(redo_every)
+    loop.redo_rule(kw.get("dormant"), redo_every, loop.REDO_ALL, reset_every, num_updates)
+    return kw
 
 
 def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_factory=None, overlap_acting: bool = False,
             device_env: bool = False, prioritized: bool = False, n_step: int = 1, one_launch: bool = False,
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
             native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, init: str = "torch",
-            reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, collected_rollout: bool = False, **over):
+            reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, collected_rollout: bool = False,
+            dormant=None, dormant_tau=None, redo_every=None, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -468,6 +494,9 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     agent = Agent({"ob_shape": (o,), "ac_shape": (a,)}, np.full(a, -bound, np.float32), np.full(a, bound, np.float32),
                   torch.device("cuda", device_index), cfg, rb, seed=seed, **(dict(init=init) if init != "torch" else {}))
     resets = dict(reset_every=reset_every, reset_what=reset_what) if reset_every is not None else {}
+    offline = offline_dataset is not None and prior_fraction is None
+    watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every,
+                             int(num_updates if num_updates is not None else cfg.num_timesteps) if offline else None)
     run_dir = Path(out_dir) / f"{env_id}__{algo}__seed{seed:02d}"
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
@@ -488,10 +517,10 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
             raise ValueError(f"{offline_dataset}: observations / actions are {data['observations'].shape[1:]} / {data['actions'].shape[1:]}, "
                              f"{env_id} has ({o},) / ({a},)")
         loop.load_dataset(agent, data, pin=prior_fraction is not None)
-    if offline_dataset is not None and prior_fraction is None:
+    if offline:
         metrics = loop.train_offline(cfg, agent, num_updates=int(num_updates if num_updates is not None else cfg.num_timesteps),
                                      evaluator=ev, eval_every_updates=int(cfg.eval_every), policy_stats=int(policy_stats),
-                                     **({k: v for k, v in resets.items() if v is not None}), **bias)
+                                     **({k: v for k, v in resets.items() if v is not None}), **bias, **watch)
     else:
         kw = train_keywords(cfg, prioritized=prioritized, n_step=n_step, one_launch=one_launch, prior_fraction=prior_fraction,
                             updates_per_step=updates_per_step, overlap_acting=overlap_acting, device_env=device_env,
@@ -499,7 +528,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
                             **(dict(hindsight=hindsight_keywords(env_id, cfg.num_envs)) if hindsight else {}),
                             **(dict(fused_rollout=True) if fused_rollout else {}),
                             **(dict(collected_rollout=True) if collected_rollout else {}), **resets)
-        metrics = loop.train(cfg, env, agent, evaluator=ev, **kw, **bias)
+        metrics = loop.train(cfg, env, agent, evaluator=ev, **kw, **bias, **watch)
     agent.engine.sync()
     dt = time.time() - t0
     tab.close()
@@ -532,7 +561,7 @@ def _worker_main(args, plan, flags) -> int:
                 out["fused_rollout"] = True
             if args.collected_rollout:           # (the same)
                 out["collected_rollout"] = True
-            for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias"):      # (the same)
+            for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias", "dormant", "dormant_tau", "redo_every"):      # (the same)
                 if k in flags:
                     out[k] = flags[k]
         else:
@@ -608,6 +637,12 @@ def main(argv=None) -> int:
     ap.add_argument("--reset_every", type=int, default=None, metavar="N",
                     help="reset the networks on the kept replay ring whenever the update count reaches a multiple of N (loop.train "
                          "reset_every=...): the companion of a high --updates_per_step")
+    ap.add_argument("--dormant", type=int, default=None, metavar="ROWS",
+                    help="at every evaluation: the dormant-neuron ratio of the online nets over ROWS ring rows, scanned on the device "
+                         "(loop.train dormant=...; vitals/dormant_actor, vitals/dormant_critics)")
+    ap.add_argument("--dormant_tau", type=float, default=None, metavar="T", help="with --dormant: the score at or below which a unit is dormant (default 0.025)")
+    ap.add_argument("--redo_every", type=int, default=None, metavar="N",
+                    help="with --dormant: ReDo -- every N critic updates, scan and re-initialise the dormant units (excludes --reset_every)")
     ap.add_argument("--reset_what", default=None, metavar="actor,critics,alpha",
                     help="with --reset_every: the networks a reset starts over (default: all three; TD3 has no alpha)")
     ap.add_argument("--policy_stats", type=int, default=0, metavar="N",

@@ -447,6 +447,65 @@ class QBias:
         return self.last
 
 
+REDO_ALL = ("actor", "critics")      # the networks dormant / redo_every may name
+
+
+class Dormant:
+    """`dormant=dict(rows=, tau= [, seed=])` of train / train_offline: at every evaluation point `agent.dormant` -- the dormant-neuron
+    ratio (Sokar et al. 2023) of the online nets over `rows` ring rows drawn with a generator of its own, one scan on the engine's
+    stream.  -> vitals/dormant_actor, vitals/dormant_critics (fractions of the hidden units) and vitals/recycled (recycle_dormant
+    calls so far).  The scan has scratch of its own and touches no counter: the run's bits are those of the run without it."""
+    KEYS = ("vitals/dormant_actor", "vitals/dormant_critics", "vitals/recycled")
+
+    def __init__(self, agent, spec):
+        self.agent, self.kw, self.last = agent, dict(spec), {}
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        got = self.agent.dormant(**self.kw)
+        self.last = {"vitals/dormant_actor": got["actor"], "vitals/dormant_critics": got["critics"],
+                     "vitals/recycled": int(self.agent.recycles_so_far)}
+        if tabular is not None:
+            for k, v in self.last.items():
+                tabular.record(k, v)
+        return self.last
+
+
+def redo_rule(dormant, redo_every, redo_what=REDO_ALL, reset_every=None, num_updates: Optional[int] = None):
+    """The keyword rules of `dormant` / `redo_every` / `redo_what`, asked before an agent is touched (ValueError), and the rule itself:
+    None without `redo_every`, else redo(agent, before, first=None) -> the update count now, with the contract of update_plan's reset:
+    if the count has reached a further multiple of redo_every since `before`: `first()`, one scan (agent.dormant(**dormant)) and
+    `agent.recycle_dormant(redo_what)` -- ReDo, between two loop bodies."""
+    spec = dormant if dormant is not None else {}
+    names = [w.strip() for w in redo_what.split(",")] if isinstance(redo_what, str) else list(redo_what)
+    for bad, msg in (
+        (dormant is not None and (not isinstance(dormant, dict) or set(dormant) - {"rows", "tau", "seed"} or "rows" not in dormant),
+         "dormant must be a dict with `rows` [, `tau`, `seed`]"),
+        (dormant is not None and isinstance(dormant, dict) and not 1 <= int(spec.get("rows", 1)) <= 65536, "dormant: 1 <= rows <= 65536"),
+        (dormant is not None and isinstance(dormant, dict) and not 0.0 <= float(spec.get("tau", 0.025)) < float("inf"), "dormant: tau must be finite and >= 0"),
+        (redo_every is not None and dormant is None, "redo_every needs dormant=dict(rows=, tau=): the scan that marks what is recycled"),
+        (redo_every is not None and reset_every is not None, "redo_every and reset_every exclude each other: recycle the dormant units or reset the networks"),
+        (redo_every is not None and int(redo_every) < 1, f"redo_every must be >= 1, got {redo_every}"),
+        (redo_every is not None and (not names or any(w not in REDO_ALL for w in names)), f"redo_what: a non-empty choice of {list(REDO_ALL)}, got {redo_what!r}"),
+        (redo_every is not None and num_updates is not None and int(redo_every) > int(num_updates),
+         f"redo_every={redo_every} is never reached by a plan of {num_updates} updates"),
+    ):
+        if bad:
+            raise ValueError(msg)
+    if redo_every is None:
+        return None
+    every, what, kw = int(redo_every), tuple(names), dict(spec)
+
+    def redo(agent, before, first=None):
+        now = int(agent.qnet_updates_so_far)
+        if now // every > before // every:
+            if first is not None:
+                first()
+            agent.dormant(**kw, what=what)
+            agent.recycle_dormant(what)
+        return now
+    return redo
+
+
 class _Vitals:
     """the diagnostics of an evaluation point, in order, as one: what _eval_point calls and _last_metrics reads"""
 
@@ -463,9 +522,10 @@ class _Vitals:
         return {k: v for part in self.parts for k, v in part.last.items()}
 
 
-def _vitals(agent, policy_stats: int, q_bias, cfg: Any):
-    """PolicyStats and / or QBias as train / train_offline were asked for them; None: neither (and no call is made, no field of cfg read)"""
+def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None):
+    """PolicyStats, QBias and / or Dormant as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
     parts = ([PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0))] if policy_stats else []) + ([QBias(agent, q_bias)] if q_bias is not None else [])
+    parts += [Dormant(agent, dormant)] if dormant is not None else []
     return None if not parts else parts[0] if len(parts) == 1 else _Vitals(parts)
 
 
@@ -637,7 +697,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           updates_per_step: int = 1, policy_stats: int = 0, native_rollout: bool = False,
           hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False,
           reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, q_bias: Optional[Dict[str, Any]] = None,
-          collected_rollout: bool = False) -> Dict[str, float]:
+          collected_rollout: bool = False, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
+          redo_what: Any = REDO_ALL) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -698,8 +759,14 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     dropped.  vitals/resets (`agent.resets_so_far`) is recorded with the evaluator's table and returned with the last metrics.
     `q_bias=dict(env=, seed=)` (default None: off, and no call is made): at every evaluation point the normalised Q-bias of the current
     policy on fresh episodes of `env` (QBias; an envs.NativeVecEnv of its own) -- vitals/q_bias_mean, vitals/q_bias_std and
-    vitals/q_bias_rows, recorded and returned like the policy stats; the run itself is bit for bit the run without it."""
-    pstats = _vitals(agent, policy_stats, q_bias, cfg)
+    vitals/q_bias_rows, recorded and returned like the policy stats; the run itself is bit for bit the run without it.
+    `dormant=dict(rows=, tau= [, seed=])` (default None: off, and no call is made): at every evaluation point the dormant-neuron ratio
+    of the online nets over `rows` ring rows (Dormant) -- vitals/dormant_actor, vitals/dormant_critics, vitals/recycled; the run itself
+    is bit for bit the run without it.  `redo_every=N` (needs `dormant`, excludes `reset_every`; `redo_what`: any of "actor",
+    "critics"): ReDo -- whenever `agent.qnet_updates_so_far` reaches a multiple of N, one scan and `agent.recycle_dormant(redo_what)`
+    between two loop bodies, on the schedule of `reset_every`."""
+    redo = redo_rule(dormant, redo_every, redo_what, reset_every)         # (refusals before the agent is touched)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant)
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
                        prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
                        reset_every=reset_every, reset_what=reset_what)
@@ -717,7 +784,7 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     i = 0
     tlog: Dict[str, Any] = {}
     step_rows = cfg.segment_len * cfg.num_envs
-    seen = int(agent.qnet_updates_so_far) if resets else 0               # the update count the reset rule last looked at
+    seen = int(agent.qnet_updates_so_far) if resets or redo is not None else 0      # the update count the reset / redo rule last looked at
     try:
         while agent.timesteps_so_far <= cfg.num_timesteps:
             if evaluator is not None:
@@ -746,6 +813,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
                 _eval_point(agent, pstats, evaluator, on_eval, agent.timesteps_so_far, resets)
             if resets:                                                    # between two bodies, whatever form they take; resolve: the
                 seen = plan.reset(agent, seen, resolve)                   # engine refuses a reset under an acting call in flight
+            elif redo is not None:                                        # (the two exclude each other)
+                seen = redo(agent, seen, resolve)
     finally:
         if fused_rollout and ro is not None:
             ro.close()                                                    # the engine holds graphs of this binding: dropped with it, here
@@ -791,7 +860,8 @@ def load_dataset(agent, data, chunk: int = 65536, pin: bool = False) -> int:
 def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Evaluator"] = None,
                   on_eval: Optional[Callable[[Any, int], None]] = None, eval_every_updates: Optional[int] = None,
                   policy_stats: int = 0, reset_every: Optional[int] = None, reset_what: Any = RESET_ALL,
-                  q_bias: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+                  q_bias: Optional[Dict[str, Any]] = None, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
+                  redo_what: Any = REDO_ALL) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
@@ -800,15 +870,20 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     `timesteps_so_far` alone (no env step was taken).  With plain TD3 or SAC this diverges on most datasets -- the actor climbs Q where
     no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
     only), `q_bias=dict(env=, seed=)` as for train.  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
-    is refused (update_plan's table).  Returns the last metrics."""
+    is refused (update_plan's table).  `dormant` / `redo_every` / `redo_what` as for train: the runs also end where a redo is due.
+    Returns the last metrics."""
     num_updates = int(num_updates)
     if num_updates < 0:
         raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
+    redo = redo_rule(dormant, redo_every, redo_what, reset_every, num_updates)      # (before the agent is touched)
     reset = None
     if reset_every is not None:                                           # (before the agent is touched)
         reset = update_plan(cfg, fused=True, sampler=None, prioritized=None, n_step=1, one_launch=False, prior_fraction=None,
                             updates_per_step=1, reset_every=reset_every, reset_what=reset_what, num_updates=num_updates).reset
-    pstats = _vitals(agent, policy_stats, q_bias, cfg)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant)
+    resets = reset is not None                                            # vitals/resets belongs to a run that resets
+    if redo is not None:
+        reset, reset_every = redo, redo_every                             # the same schedule: the runs end where a redo is due
     every = num_updates if eval_every_updates is None else int(eval_every_updates)
     if eval_every_updates is not None and every < 1:
         raise ValueError(f"train_offline: eval_every_updates must be >= 1, got {eval_every_updates}")
@@ -825,10 +900,10 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
         agent.actor_updates_so_far += delay * len(range(-(-i // period) * period, end, period))      # the iterations with i % period == 0
         i = end
         if i % every == 0 or i == num_updates:
-            _eval_point(agent, pstats, evaluator, on_eval, i, reset is not None)
+            _eval_point(agent, pstats, evaluator, on_eval, i, resets)
         if reset is not None:
             seen = reset(agent, seen)
-    return _last_metrics(agent, pstats, reset is not None)
+    return _last_metrics(agent, pstats, resets)
 
 
 class Tabular:
