@@ -74,6 +74,10 @@ ROLLOUT_CYCLE_SYMBOLS = ["sactd3_rollout_cycle", "sactd3_rollout_cycle_stats", "
 ROLLOUT_COLLECT_SYMBOLS = ["sactd3_rollout_collect", "sactd3_rollout_collect_stats"]
 COLLECT_MAX_STEPS = 4096            # SACTD3_COLLECT_MAX_STEPS
 STREAM_COLLECT = 0x900              # csrc/collect_kernels.h: SACTD3_STREAM_COLLECT
+# every symbol include/sactd3_noise.h declares (tests/test_colored_noise_host.py checks the header against this list)
+NOISE_SYMBOLS = ["sactd3_colored_noise_device", "sactd3_rollout_noise_configure", "sactd3_rollout_collect_colored", "sactd3_rollout_noise_stats"]
+STREAM_COLORED = 0xB00              # csrc/noise_kernels.h: SACTD3_STREAM_COLORED
+NOISE_MIN_LEN, NOISE_MAX_LEN = 64, 4096   # chunk lengths: powers of two in this range
 # every symbol include/sactd3_init.h declares (tests/test_param_init_host.py checks the header against this list)
 INIT_SYMBOLS = ["sactd3_init_params", "sactd3_init_stats"]
 INIT_ACTOR, INIT_CRITICS, INIT_ALPHA = 1, 2, 4   # sactd3_init_params `what` (SACTD3_INIT_*)
@@ -345,6 +349,14 @@ def load_library():
     }
     assert sorted(collect_sig) == sorted(ROLLOUT_COLLECT_SYMBOLS)
     sig.update(collect_sig)
+    noise_sig = {
+        "sactd3_colored_noise_device": (C.c_int, [vp, C.c_float, C.c_int, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_int64, vp, C.c_int]),
+        "sactd3_rollout_noise_configure": (C.c_int, [vp, C.c_float, C.c_int]),
+        "sactd3_rollout_collect_colored": (C.c_int, [vp, C.c_int, vp, vp]),
+        "sactd3_rollout_noise_stats": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(noise_sig) == sorted(NOISE_SYMBOLS)
+    sig.update(noise_sig)
     init_sig = {
         "sactd3_init_params": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_uint32]),
         "sactd3_init_stats": (C.c_int, [vp, i64p]),

@@ -38,6 +38,9 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 // ... and the dormant-neuron scan with its recycler (dormant.hip; its C ABI is include/sactd3_dormant.h, defined behind the initialiser's)
 #include "dormant.h"
 #include "../../include/sactd3_dormant.h"
+// ... and the coloured-noise generator (noise.hip; its C ABI is include/sactd3_noise.h, defined behind the dormant scan's)
+#include "noise.h"
+#include "../../include/sactd3_noise.h"
 // ... and the evaluation rollout, whose kernel is compiled with the env kernels (env.hip): host code only here, at the end of this file
 #include "eval_rollout.h"
 // ... and the collected rollout segment, split the same way (collect_rollout.h)
@@ -328,6 +331,11 @@ struct sactd3_engine {
   DormantState dm{};
   bool dm_scanned[2] = {false, false};
   int64_t dm_host[2] = {};
+  // Coloured exploration noise (sactd3_colored_noise_device; include/sactd3_noise.h; device code: noise_kernels.h, a translation unit of
+  // its own).  nz_tables: the amplitude and twiddle tables of every (beta, length) pair asked for so far, each made at its first use --
+  // an engine that never generates holds nothing more than before.
+  struct NoiseTable { float beta; int len; float* dev; };
+  std::vector<NoiseTable> nz_tables;
 
   int fail(int code, const char* what, hipError_t he = hipSuccess) {
     err = what;
@@ -4273,6 +4281,43 @@ int sactd3_redo(sactd3_engine* e, uint32_t what, uint64_t seed, uint32_t epoch) 
   if (what & SACTD3_DORMANT_CRITICS) e->dm_scanned[1] = false;
   ++e->dm_host[1];
   return 0;
+}
+
+// ---- coloured exploration noise (include/sactd3_noise.h): the stand-alone generator.  Like a scan it writes the caller's memory and
+// nothing of the engine's: no CHAIN_BREAK, no counter, allowed while an acting call is in flight.
+int sactd3_colored_noise_device(sactd3_engine* e, float beta, int length, int sequences, uint32_t chunk, uint32_t epoch, float* out,
+                                int64_t out_ld, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first: a refused call has launched, allocated and counted nothing
+  if (!out) return e->fail(SACTD3_EINVAL, "colored_noise_device: `out` is NULL");
+  if (const char* why = noise_refusal(beta, length)) { e->err = std::string("colored_noise_device: ") + why; return SACTD3_EINVAL; }
+  if (sequences < 1) return e->fail(SACTD3_EINVAL, "colored_noise_device: sequences >= 1 required");
+  if (epoch >= NZ_MAX_EPOCH) return e->fail(SACTD3_EINVAL, "colored_noise_device: epoch must be below 65536");
+  if (out_ld < sequences) return e->fail(SACTD3_EINVAL, "colored_noise_device: row stride of `out` is below `sequences`");
+  if (flags & ~(SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) return e->fail(SACTD3_EINVAL, "colored_noise_device: unknown flag");
+  USE_DEVICE(e);
+  RCCHK(device_ptr_check(e, out, "colored_noise_device", "out"));
+  float* tab = nullptr;
+  for (const auto& t : e->nz_tables)
+    if (t.beta == beta && t.len == length) tab = t.dev;
+  if (!tab) {      // the pair's first use: the tables, float64 on the host, rounded once, copied before the call returns
+    if (e->nz_tables.size() >= 32) return e->fail(SACTD3_ESTATE, "colored_noise_device: 32 (beta, length) pairs are in use already");
+    std::vector<float> host(noise_table_floats(length));
+    noise_tables(beta, length, host.data());
+    RCCHK(first_use_alloc(e, &tab, host.size(), false));
+    HIPCHK(hipMemcpy(tab, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    e->nz_tables.push_back({beta, length, tab});
+  }
+  NoiseArgs g{};
+  g.amp = tab; g.tw = (const float2*)(tab + noise_amp_floats(length)); g.seed = (const unsigned long long*)&e->ctl->seed;
+  g.chunk = chunk; g.epoch = epoch; g.sequences = sequences; g.out = out; g.ld = (long long)out_ld;
+  for (g.log_len = 0; (1 << g.log_len) < length; ++g.log_len) {}
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  const int ordered = (flags & (SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) ? SACTD3_SRC_ORDERED : 0;      // (one pair of events serves both sides)
+  RCCHK(src_order_begin(e, caller, ordered));
+  const hipError_t he = noise_launch(g, e->stream);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "colored_noise_device: k_colored_noise", he);
+  return src_order_end(e, caller, ordered);
 }
 
 }  // extern "C"

@@ -20,10 +20,13 @@
 #include "../../include/sactd3_env.h"
 #include "../../include/sactd3_rollout.h"
 #include "../../include/sactd3_eval.h"
+#include "../../include/sactd3_noise.h"
 #include "env_kernels.h"
 #include "eval_kernels.h"
 #include "collect_kernels.h"
+#include "collect_colored_kernels.h"
 #include "rollout_cycle.h"
+#include "noise.h"
 
 #define ENV_API extern "C" __attribute__((visibility("default")))
 
@@ -380,6 +383,14 @@ struct sactd3_rollout {
   int64_t stats[ROLLOUT_NUM_STATS] = {};
   int64_t cycle_stats[CYCLE_NUM_STATS] = {};      // (the engine counts in them: CycleBinding::stats)
   int64_t collect_stats[3] = {};        // sactd3_rollout_collect: {calls, env steps, calls that drew}
+  // the exploration process of sactd3_rollout_noise_configure (include/sactd3_noise.h): nz_len == 0: none.  nz_slab [2][nz_len][S] is the
+  // rollout's own allocation; nz_have[slot]: the chunk that slot holds (-1: none); nz_made: chunks generated so far
+  float nz_beta = 0.f;
+  int nz_len = 0;
+  float* nz_slab = nullptr;
+  size_t nz_floats = 0;
+  int64_t nz_pos = 0, nz_have[2] = {-1, -1}, nz_made = 0;
+  uint32_t nz_epoch = 0;
   bool cycled = false;                  // a cycle reached the engine: it may hold graphs of this binding (sactd3_rollout_destroy)
   std::string err;
 
@@ -435,6 +446,7 @@ ENV_API int sactd3_rollout_create(sactd3_engine* eng, sactd3_env* env, const sac
 // (neither handle nor any buffer is the rollout's; the cycle graphs of its binding, which the engine keeps, go with it)
 ENV_API void sactd3_rollout_destroy(sactd3_rollout* r) {
   if (r && r->cycled) engine_rollout_cycle_release(r->eng, r);
+  if (r && r->nz_slab && hipSetDevice(r->env->cfg.device_id) == hipSuccess) (void)hipFree(r->nz_slab);      // (waits for what still reads it)
   delete r;
 }
 
@@ -535,7 +547,9 @@ ENV_API int sactd3_rollout_cycle_clamped(sactd3_rollout* r, int64_t* out) {
 // Every refusal stands in front of the first side effect.  The launches, all on the engine's learner stream between ONE pair of events
 // against the rollout's: k_collect_rollout, the append of its slab (flags 0: the slab was written on the stream that reads it), the
 // counter tick of a call that drew.
-ENV_API int sactd3_rollout_collect(sactd3_rollout* r, int mode, int steps, float* records, float* eps) {
+// `colored`: sactd3_rollout_collect_colored (include/sactd3_noise.h) -- its two refusals, the generator for the chunks the segment reads
+// that are not yet in their slots, the coloured kernel instance, no counter tick, pos += steps.
+static int collect_segment(sactd3_rollout* r, int mode, int steps, float* records, float* eps, bool colored) {
   return guarded([&]() -> int {
     if (!r) return SACTD3_EINVAL;
     sactd3_env* e = r->env;
@@ -547,6 +561,8 @@ ENV_API int sactd3_rollout_collect(sactd3_rollout* r, int mode, int steps, float
     if (steps < 1 || steps > SACTD3_COLLECT_MAX_STEPS) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: steps must be in [1, 4096]");
     if (!on_device(records, dev)) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: `records` is not device memory of the handles' device");
     if (eps && !on_device(eps, dev)) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect: `eps` is not device memory of the handles' device");
+    if (colored && !r->nz_len) return r->fail(SACTD3_ESTATE, "sactd3_rollout_collect_colored: the rollout has no process (sactd3_rollout_noise_configure first)");
+    if (colored && steps > r->nz_len) return r->fail(SACTD3_EINVAL, "sactd3_rollout_collect_colored: steps is above the process's chunk length");
     const int64_t rows = (int64_t)steps * r->n;
     CollectActor ca{};
     int rc = engine_collect_open(r->eng, e->info.ob_dim, e->info.ac_dim, dev, rows, r->stream, &ca);
@@ -559,7 +575,29 @@ ENV_API int sactd3_rollout_collect(sactd3_rollout* r, int mode, int steps, float
     p.L = EnvRec{r->lay.record_len, r->lay.next_off, r->lay.next_width};
     p.records = records; p.eps = eps; p.obs = b.obs; p.obs_ld = (long long)b.obs_ld; p.actions = b.actions; p.actions_ld = (long long)b.actions_ld;
     const dim3 grid((unsigned)((e->d.n + EV_TILE - 1) / EV_TILE));
-    with_kind(e->cfg.kind, [&](auto K) { hipLaunchKernelGGL(k_collect_rollout<decltype(K)::value>, grid, dim3(256), 0, ca.A.stream, e->d, p); });
+    if (colored) {
+      const int L = r->nz_len;
+      const int64_t S = (int64_t)r->n * e->info.ac_dim, c0 = r->nz_pos / L, c1 = (r->nz_pos + steps - 1) / L;
+      for (int64_t c = c0; c <= c1; ++c) {      // (c1 <= c0 + 1: steps <= L)
+        if (r->nz_have[c & 1] == c) continue;
+        rc = sactd3_colored_noise_device(r->eng, r->nz_beta, L, (int)S, (uint32_t)c, r->nz_epoch, r->nz_slab + (size_t)(c & 1) * L * S, S, nullptr, 0);
+        if ((rc = r->from_engine(rc, "sactd3_colored_noise_device"))) {
+          (void)engine_collect_close(r->eng, 0, r->stream);
+          return rc;
+        }
+        // (booked at enqueue time: in stream order the chunk IS in its slot for every later launch, whatever becomes of this call.  If the
+        // append below is refused behind the kernel, the envs have moved while pos has not -- the white call's half-done case, see the
+        // header -- and the next call reads these rows again.)
+        r->nz_have[c & 1] = c; ++r->nz_made;
+      }
+      CollectLaunchColored pc{};
+      static_cast<CollectLaunch&>(pc) = p;
+      const int row0 = (int)(r->nz_pos % L);      // rows row0 .. L - 1 of slot c0 & 1, then rows 0 .. of the other slot: steps - wrap <= row0 of them
+      pc.z = CollectNoise{r->nz_slab + ((size_t)(c0 & 1) * L + row0) * S, r->nz_slab + (size_t)((c0 & 1) ^ 1) * L * S, L - row0, (long long)S};
+      with_kind(e->cfg.kind, [&](auto K) { hipLaunchKernelGGL(k_collect_rollout_colored<decltype(K)::value>, grid, dim3(256), 0, ca.A.stream, e->d, pc); });
+    } else {
+      with_kind(e->cfg.kind, [&](auto K) { hipLaunchKernelGGL(k_collect_rollout<decltype(K)::value>, grid, dim3(256), 0, ca.A.stream, e->d, p); });
+    }
     // a HIP error behind the opening half of the event pair: the pair is closed (no tick), so that the rollout's stream still stands
     // behind whatever the learner stream was given, and the call's own error is what is reported
     auto broken = [&](int code) {
@@ -570,7 +608,8 @@ ENV_API int sactd3_rollout_collect(sactd3_rollout* r, int mode, int steps, float
       return broken(r->fail(SACTD3_EHIP, std::string("sactd3_rollout_collect: k_collect_rollout: ") + hipGetErrorString(he)));
     rc = sactd3_rb_extend_records_device(r->eng, records, (int)rows, nullptr, 0);
     if ((rc = r->from_engine(rc, "sactd3_rb_extend_records_device"))) return broken(rc);
-    const bool drew = mode == SACTD3_ROLLOUT_EXPLORE;
+    const bool drew = mode == SACTD3_ROLLOUT_EXPLORE && !colored;      // (a coloured segment draws nothing from stream 0x900)
+    if (colored) r->nz_pos += steps;
     rc = engine_collect_close(r->eng, drew ? 1 : 0, r->stream);
     if ((rc = r->from_engine(rc, "sactd3_rollout_collect"))) return rc;
     // the counters of `steps` choose + advance calls, and the feature's own
@@ -581,6 +620,44 @@ ENV_API int sactd3_rollout_collect(sactd3_rollout* r, int mode, int steps, float
     if (drew) ++r->collect_stats[2];
     return SACTD3_OK;
   });
+}
+
+ENV_API int sactd3_rollout_collect(sactd3_rollout* r, int mode, int steps, float* records, float* eps) {
+  return collect_segment(r, mode, steps, records, eps, false);
+}
+
+// ---------------------------------------------------------------------------------------------------- include/sactd3_noise.h
+ENV_API int sactd3_rollout_collect_colored(sactd3_rollout* r, int steps, float* records, float* eps) {
+  return collect_segment(r, SACTD3_ROLLOUT_EXPLORE, steps, records, eps, true);
+}
+
+ENV_API int sactd3_rollout_noise_configure(sactd3_rollout* r, float beta, int length) {
+  return guarded([&]() -> int {
+    if (!r) return SACTD3_EINVAL;
+    if (length == 0) {      // (the slab stays for a later process of its size)
+      r->nz_len = 0;
+      return SACTD3_OK;
+    }
+    if (const char* why = noise_refusal(beta, length)) return r->fail(SACTD3_EINVAL, std::string("sactd3_rollout_noise_configure: ") + why);
+    if (r->nz_epoch + 1 >= NZ_MAX_EPOCH) return r->fail(SACTD3_ESTATE, "sactd3_rollout_noise_configure: this handle has used up its 65535 epochs");
+    const size_t floats = (size_t)2 * length * r->n * r->env->info.ac_dim;
+    if (floats > r->nz_floats) {
+      if (hipSetDevice(r->env->cfg.device_id) != hipSuccess) return r->fail(SACTD3_EHIP, "sactd3_rollout_noise_configure: hipSetDevice");
+      void* v = nullptr;
+      if (const hipError_t he = hipMalloc(&v, floats * sizeof(float))) return r->fail(SACTD3_EHIP, std::string("sactd3_rollout_noise_configure: hipMalloc: ") + hipGetErrorString(he));
+      if (r->nz_slab) (void)hipFree(r->nz_slab);      // (waits for what still reads it)
+      r->nz_slab = (float*)v; r->nz_floats = floats;
+    }
+    r->nz_beta = beta; r->nz_len = length; r->nz_pos = 0; r->nz_have[0] = r->nz_have[1] = -1;
+    ++r->nz_epoch;
+    return SACTD3_OK;
+  });
+}
+
+ENV_API int sactd3_rollout_noise_stats(const sactd3_rollout* r, int64_t out[4]) {
+  if (!r || !out) return SACTD3_EINVAL;
+  out[0] = r->nz_len; out[1] = r->nz_pos; out[2] = r->nz_made; out[3] = r->nz_epoch;
+  return SACTD3_OK;
 }
 
 ENV_API int sactd3_rollout_collect_stats(sactd3_rollout* r, int64_t out[4]) {

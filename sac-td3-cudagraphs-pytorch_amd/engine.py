@@ -248,6 +248,29 @@ class Engine:
         return {"scans": v[0], "valid_rows": v[1], "rows_refused": v[2], "dormant": dict(zip(_lib.DORMANT_PAIRS, v[3:9])),
                 "redo_calls": v[9], "recycled": v[10], "rows_left_zero": v[11]}
 
+    # -- coloured exploration noise (include/sactd3_noise.h)
+    def colored_noise(self, beta: float, length: int, sequences: int, chunk: int = 0, epoch: int = 0, out=None):
+        """sactd3_colored_noise_device: chunk `chunk` of `sequences` independent 1/f^beta Gaussian sequences (beta in [0, 2]: 0 white,
+        1 pink, 2 red; every element N(0, 1)) of `length` steps, a power of two in [64, 4096] -- a pure function of (the engine's seed,
+        epoch, chunk, sequence, beta, length), generated by one inverse FFT per pair of sequences on the engine's stream, ordered on the
+        GPU against torch's current stream; no wait, no copy, and training and acting do not see the call.  `out`: None, or a float32
+        CUDA tensor [length, >= sequences] with unit column stride, of which columns 0 .. sequences - 1 are written.
+        -> the [length, sequences] tensor (a view of `out` if given)"""
+        import torch
+        dev = torch.device("cuda", self.cfg.device_id)
+        length, sequences = int(length), int(sequences)
+        if out is None:
+            if not 1 <= sequences or not 1 <= length <= _lib.NOISE_MAX_LEN:      # (before anything is allocated; the library refuses the rest)
+                raise ValueError("colored_noise: sequences >= 1 and length in [64, 4096] required")
+            out = torch.empty(length, sequences, dtype=torch.float32, device=dev)
+        elif (out.dtype != torch.float32 or out.dim() != 2 or out.device != dev or out.shape[0] != length or out.shape[1] < sequences
+              or out.stride(1) != 1):
+            raise ValueError("colored_noise: `out` is a float32 [length, >= sequences] tensor of the engine's device with unit column stride")
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+        self._ck(self.lib.sactd3_colored_noise_device(self._h, float(beta), length, sequences, int(chunk) & 0xFFFFFFFF, int(epoch), _vp(out.data_ptr()),
+                                                      int(out.stride(0)), _vp(stream), _lib.SRC_ORDERED | _lib.DST_ORDERED))
+        return out[:, :sequences]
+
     # -- replay
     def _rows(self, obs, act, rew, nobs, done):
         o, a = self.cfg.ob_dim, self.cfg.ac_dim

@@ -353,6 +353,12 @@ def mode_flags(args, plan) -> dict:
         flags["fused_rollout"] = True
     if getattr(args, "collected_rollout", False):           # (the same)
         flags["collected_rollout"] = True
+    if getattr(args, "exploration_beta", None) is not None:  # (the same; without --collected_rollout: refused by train_keywords)
+        flags["exploration_beta"] = float(args.exploration_beta)
+        if getattr(args, "exploration_len", None) is not None:
+            flags["exploration_len"] = int(args.exploration_len)
+    elif getattr(args, "exploration_len", None) is not None:
+        raise ValueError("--exploration_len needs --exploration_beta B: it is the chunk length of that noise")
     if getattr(args, "reset_every", None) is not None:      # (the same)
         flags["reset_every"] = int(args.reset_every)
         flags["reset_what"] = reset_names(getattr(args, "reset_what", None))
@@ -381,7 +387,7 @@ def reset_names(text=None) -> tuple:
 def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, prior_fraction, updates_per_step, overlap_acting: bool,
                    device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False,
                    reset_every=None, reset_what=None, init: str = "torch", num_updates=None, collected_rollout: bool = False,
-                   dormant=None, dormant_tau=None, redo_every=None) -> dict:
+                   dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
@@ -398,7 +404,10 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     is the Agent's keyword, not loop.train's: checked here, never in the result.
     `dormant` [, `dormant_tau`] (--dormant ROWS [--dormant_tau T]: the dormant-neuron ratio at every evaluation, loop.train dormant=...)
     and `redo_every` (--redo_every N: ReDo recycling on that scan): asked of loop.redo_rule; the keys are in the result only when the
-    flags were given."""
+    flags were given.
+    `exploration_beta` [, `exploration_len`] (--exploration_beta B [--exploration_len L]: coloured exploration noise in the collected
+    segments, loop.train exploration_beta=...): asked of loop.exploration_rule with the job's segment_len; the keys are in the result
+    only when --exploration_beta was given."""
     if init not in ("torch", "engine"):
         raise ValueError(f'--init is "torch" or "engine", not {init!r}')
     if fused_rollout and not (native_rollout and not overlap_acting):      # (its two rules stand in front of the env's: no env is looked at)
@@ -406,6 +415,11 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     if collected_rollout:                                                  # (the same: its rules stand in front of the env's)
         loop.collected_rollout_rules(overlap=overlap_acting, native_rollout=native_rollout, fused_rollout=fused_rollout,
                                      action_repeat=int(cfg.action_repeat), segment_len=int(cfg.segment_len))
+    noise = {}
+    if exploration_beta is not None:
+        noise = dict(exploration_beta=float(exploration_beta), **(dict(exploration_len=int(exploration_len)) if exploration_len is not None else {}))
+        loop.exploration_rule(noise["exploration_beta"], noise.get("exploration_len", 256), collected_rollout=collected_rollout,
+                              segment_len=int(cfg.segment_len))
     update = dict(fused=not prioritized and n_step == 1 and prior_fraction is None and not hindsight,
                   prioritized=dict(alpha=0.6, beta=0.4, eps=1e-6) if prioritized else None, n_step=n_step, one_launch=one_launch,
                   prior_fraction=None if prior_fraction is None else float(prior_fraction), updates_per_step=int(updates_per_step))
@@ -418,7 +432,7 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     loop.update_plan(cfg, sampler=None, **update, **(dict(num_updates=int(num_updates)) if num_updates is not None else {}))
     rollout = dict(collected_rollout=True) if collected_rollout else {}
     watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates)
-    return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout, **watch)
+    return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout, **noise, **watch)
 
 
 def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_every=None, num_updates=None) -> dict:
@@ -438,7 +452,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
             native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, init: str = "torch",
             reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, collected_rollout: bool = False,
-            dormant=None, dormant_tau=None, redo_every=None, **over):
+            dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -451,6 +465,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     hindsight_plan refuses otherwise); with `one_launch` the draw and the relabelling are part of the iteration's one graph.
     `fused_rollout`: with `native_rollout`, a loop body past learning_starts as one graph launch (loop.train fused_rollout=True).
     `collected_rollout`: with `native_rollout`, every segment is one library call (loop.train collected_rollout=True).
+    `exploration_beta` [, `exploration_len`]: with `collected_rollout`, the policy-phase segments explore with 1/f^beta noise generated on
+    the device (loop.train exploration_beta=...).
     `init`: "engine" = the initial parameters come from the engine's own initialiser under the job's seed (Agent init="engine"), not
     from torch's; `reset_every` [, `reset_what`]: periodic resets of the networks on the kept ring (loop.train / loop.train_offline
     reset_every=...).
@@ -527,7 +543,9 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
                             native_rollout=native_rollout, policy_stats=policy_stats,
                             **(dict(hindsight=hindsight_keywords(env_id, cfg.num_envs)) if hindsight else {}),
                             **(dict(fused_rollout=True) if fused_rollout else {}),
-                            **(dict(collected_rollout=True) if collected_rollout else {}), **resets)
+                            **(dict(collected_rollout=True) if collected_rollout else {}),
+                            **(dict(exploration_beta=exploration_beta, exploration_len=exploration_len) if exploration_beta is not None else {}),
+                            **resets)
         metrics = loop.train(cfg, env, agent, evaluator=ev, **kw, **bias, **watch)
     agent.engine.sync()
     dt = time.time() - t0
@@ -561,7 +579,8 @@ def _worker_main(args, plan, flags) -> int:
                 out["fused_rollout"] = True
             if args.collected_rollout:           # (the same)
                 out["collected_rollout"] = True
-            for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias", "dormant", "dormant_tau", "redo_every"):      # (the same)
+            for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias", "dormant", "dormant_tau", "redo_every",
+                      "exploration_beta", "exploration_len"):      # (the same)
                 if k in flags:
                     out[k] = flags[k]
         else:
@@ -609,6 +628,11 @@ def main(argv=None) -> int:
                     help="with --device_env --native_rollout: every segment of segment_len env steps -- actions, env steps, ring records, the "
                          "append -- is one library call and two launches (loop.train collected_rollout=True); excludes --fused_rollout and "
                          "--overlap_acting, needs action_repeat 1")
+    ap.add_argument("--exploration_beta", type=float, default=None, metavar="B",
+                    help="with --collected_rollout: coloured exploration noise -- the policy-phase segments explore with a 1/f^B process per "
+                         "action component, generated on the device (loop.train exploration_beta=...; 0 white, 1 pink, 2 red)")
+    ap.add_argument("--exploration_len", type=int, default=None, metavar="L",
+                    help="with --exploration_beta: the chunk length of the noise, a power of two in [64, 4096], >= segment_len (default 256)")
     ap.add_argument("--hindsight", action="store_true",
                     help="with an env bundle whose tasks have a goal (native_goal): the engine relabels goals while it stages each batch -- "
                          "hindsight experience replay, the future strategy, window = the task's horizon (loop.train hindsight=...; the "

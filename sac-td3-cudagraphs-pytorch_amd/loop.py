@@ -243,7 +243,19 @@ class NativeRollout:
         if do_actor:
             agent.actor_updates_so_far += delay
 
-    def collect(self, steps: int, mode: Optional[int] = None, eps: bool = False):
+    def configure_noise(self, beta: float, length: int) -> None:
+        """sactd3_rollout_noise_configure (include/sactd3_noise.h): give the rollout a 1/f^beta exploration process in chunks of `length`
+        steps (a power of two in [64, 4096]; 0 removes it) -- what `collect(colored=True)` explores with.  Position 0, a fresh epoch."""
+        self._ck(self._lib.sactd3_rollout_noise_configure(self._h, float(beta), int(length)))
+
+    def noise_stats(self) -> Dict[str, int]:
+        """host state of the rollout's exploration process (sactd3_rollout_noise_stats)"""
+        import ctypes as C
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.sactd3_rollout_noise_stats(self._h, out))
+        return dict(zip(("length", "pos", "chunks_generated", "epoch"), (int(v) for v in out)))
+
+    def collect(self, steps: int, mode: Optional[int] = None, eps: bool = False, colored: bool = False):
         """`steps` x (`choose()`, `advance()`) as ONE ctypes call and two launches (include/sactd3_rollout_collect.h:
         sactd3_rollout_collect): the collect kernel rolls all envs for `steps` steps under the current policy -- or, with the random
         phase's draw, bit for bit as the call sequence does -- and writes every transition as a ring record into a slab, time-major;
@@ -252,8 +264,11 @@ class NativeRollout:
         [steps, n, a] -- are allocated once per `steps` and returned as VIEWS the next call of the same `steps` overwrites:
         -> records, or (records, eps).  For `action_repeat` 1 (the caller decides that: train(collected_rollout=True)).  ValueError for
         `steps` outside [1, 4096], before anything is allocated; the library's own refusals -- `steps * n` above the ring slots an append
-        may use among them -- come as EngineError from the call."""
+        may use among them -- come as EngineError from the call.  `colored=True` (sactd3_rollout_collect_colored; `mode` None or explore):
+        the exploring segment with e taken from the process of `configure_noise` in place of the white draw."""
         steps = int(steps)
+        if colored and mode not in (None, self._explore):
+            raise ValueError("collect: colored=True is the exploring mode")
         if not 1 <= steps <= self._max_steps:
             raise ValueError(f"collect: steps must be in [1, {self._max_steps}], got {steps}")
         if mode is None:
@@ -265,7 +280,10 @@ class NativeRollout:
             rec = slab[0] if slab is not None else torch.zeros((steps * n, self.records.shape[1]), dtype=torch.float32, device=dev)
             slab = self._slabs[steps] = (rec, torch.zeros((steps, n, self.actions.shape[1]), dtype=torch.float32, device=dev) if eps else None)
         rec, draws = slab
-        rc = self._lib.sactd3_rollout_collect(self._h, int(mode), steps, rec.data_ptr(), draws.data_ptr() if eps else None)
+        if colored:
+            rc = self._lib.sactd3_rollout_collect_colored(self._h, steps, rec.data_ptr(), draws.data_ptr() if eps else None)
+        else:
+            rc = self._lib.sactd3_rollout_collect(self._h, int(mode), steps, rec.data_ptr(), draws.data_ptr() if eps else None)
         if rc:
             self._ck(rc)
         self.steps += steps
@@ -303,7 +321,24 @@ def segment(env, agent, seed: int, segment_len: int, learning_starts: int, actio
         ro.advance()
 
 
-def collected_rollout_rules(*, overlap: bool, native_rollout: bool, fused_rollout: bool, action_repeat: int, segment_len: int) -> None:
+def exploration_rule(exploration_beta, exploration_len, *, collected_rollout: bool, segment_len: int) -> None:
+    """What `exploration_beta` (coloured exploration noise, include/sactd3_noise.h) needs, looked at without an env: ValueError."""
+    if exploration_beta is None:
+        return
+    from . import _lib
+    if not collected_rollout:
+        raise ValueError("exploration_beta needs collected_rollout=True: the noise process feeds the collect kernel")
+    if not 0.0 <= float(exploration_beta) <= 2.0:
+        raise ValueError(f"exploration_beta must be in [0, 2], got {exploration_beta!r}")
+    n = int(exploration_len)
+    if not _lib.NOISE_MIN_LEN <= n <= _lib.NOISE_MAX_LEN or n & (n - 1):
+        raise ValueError(f"exploration_len must be a power of two in [{_lib.NOISE_MIN_LEN}, {_lib.NOISE_MAX_LEN}], got {exploration_len!r}")
+    if n < int(segment_len):
+        raise ValueError(f"exploration_len ({n}) must be >= segment_len ({segment_len}): a segment reads at most two chunks")
+
+
+def collected_rollout_rules(*, overlap: bool, native_rollout: bool, fused_rollout: bool, action_repeat: int, segment_len: int,
+                            exploration_beta=None, exploration_len: int = 256) -> None:
     """What `collected_rollout=True` (a segment as one `NativeRollout.collect`) needs and excludes, looked at without an env: ValueError."""
     if not native_rollout:
         raise ValueError("collected_rollout=True needs native_rollout=True: the segment is a call of the native rollout's handle")
@@ -315,20 +350,25 @@ def collected_rollout_rules(*, overlap: bool, native_rollout: bool, fused_rollou
         raise ValueError("collected_rollout=True needs action_repeat == 1: the collect kernel chooses an action with every step")
     if int(segment_len) < 1:
         raise ValueError("collected_rollout=True needs segment_len >= 1")
+    exploration_rule(exploration_beta, exploration_len, collected_rollout=True, segment_len=segment_len)
 
 
 def rollout_for(env, *, overlap: bool, device_env: bool, native_rollout: bool, fused_rollout: bool = False,
-                collected_rollout: bool = False, action_repeat: int = 1, segment_len: int = 1):
+                collected_rollout: bool = False, action_repeat: int = 1, segment_len: int = 1, exploration_beta=None,
+                exploration_len: int = 256):
     """Which of the three classes above drives `env` for train(): refuses what excludes each other, constructs nothing.  -> None for the
     plain host case (segment() makes its own `Rollout`), else what to call with (env, agent, seed, learning_starts, action_repeat).
     Both device rollouts act on the learner stream, so neither goes with `overlap`; the native one needs an env on the GPU that emits
     ring records (`step_records`: envs.NativeVecEnv).  `fused_rollout` (a loop body as one `NativeRollout.cycle`) needs the native
     rollout -- its two rules come first, before `env` is looked at; what it needs of the update keywords is `update_plan`'s.
     `collected_rollout` (a segment as one `NativeRollout.collect`) needs the native rollout and `action_repeat` 1, excludes
-    `fused_rollout` and `overlap` and takes any `segment_len` >= 1 (`collected_rollout_rules`, in front of the env's as well)."""
+    `fused_rollout` and `overlap` and takes any `segment_len` >= 1 (`collected_rollout_rules`, in front of the env's as well).
+    `exploration_beta` (coloured exploration noise) needs `collected_rollout` and `exploration_len` >= `segment_len` (`exploration_rule`)."""
     if collected_rollout:
         collected_rollout_rules(overlap=overlap, native_rollout=native_rollout, fused_rollout=fused_rollout, action_repeat=action_repeat,
-                                segment_len=segment_len)
+                                segment_len=segment_len, exploration_beta=exploration_beta, exploration_len=exploration_len)
+    else:
+        exploration_rule(exploration_beta, exploration_len, collected_rollout=False, segment_len=segment_len)
     if fused_rollout and not native_rollout:
         raise ValueError("fused_rollout=True needs native_rollout=True: the cycle is a call of the native rollout's handle")
     if fused_rollout and overlap:
@@ -698,7 +738,7 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False,
           reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, q_bias: Optional[Dict[str, Any]] = None,
           collected_rollout: bool = False, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
-          redo_what: Any = REDO_ALL) -> Dict[str, float]:
+          redo_what: Any = REDO_ALL, exploration_beta: Optional[float] = None, exploration_len: int = 256) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -729,6 +769,10 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     native_rollout=True run; its random phase is.  A segment must fit the ring slots an append may use (segment_len * num_envs <=
     rb_capacity minus the pinned rows): that is the engine's to know and is refused by the first `collect`, as an EngineError, not here.
     Off by default.
+    `exploration_beta=B` (default None: the white draw; needs collected_rollout=True; `exploration_len` a power of two in [64, 4096],
+    >= segment_len): coloured exploration noise (Eberhard et al. 2023; include/sactd3_noise.h) -- every policy-phase segment is collected
+    with e from a 1/f^B process per action component, generated on the device in chunks of `exploration_len` steps
+    (`NativeRollout.configure_noise`, `collect(colored=True)`); B = 1 is pink noise.  The random phase is unchanged.
     `sampler` (a ProportionalSampler): prioritised replay, call by call on the device -- the sampler's rows and importance weights
     through `rb.sample_at`, the critic update weighted by them, its TD errors (`agent.td_errors`) back into the sampler's priorities;
     the actor updates train on the same rows, unweighted.
@@ -772,14 +816,17 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
                        reset_every=reset_every, reset_what=reset_what)
     resets = plan.reset is not None
     make_rollout = rollout_for(env, overlap=overlap, device_env=device_env, native_rollout=native_rollout, fused_rollout=fused_rollout,
-                               **(dict(collected_rollout=True, action_repeat=cfg.action_repeat, segment_len=cfg.segment_len)
-                                  if collected_rollout else {}))
+                               **(dict(collected_rollout=True, action_repeat=cfg.action_repeat) if collected_rollout else {}),
+                               **(dict(exploration_beta=exploration_beta, exploration_len=exploration_len) if exploration_beta is not None else {}),
+                               **(dict(segment_len=cfg.segment_len) if collected_rollout or exploration_beta is not None else {}))
     if plan.priorities is not None:                                       # (nothing above touched the agent's engine)
         agent.rb.enable_priorities(**plan.priorities)
     if plan.hindsight is not None:
         agent.rb.configure_hindsight(**plan.hindsight)
     ro = make_rollout(env, agent, cfg.seed, cfg.learning_starts, cfg.action_repeat) if make_rollout is not None else None
     resolve = ro.resolve if ro is not None else (lambda: None)            # (segment()'s own host rollout never has an action pending)
+    if exploration_beta is not None:
+        ro.configure_noise(exploration_beta, exploration_len)
     seg_gen = segment(env, agent, cfg.seed, cfg.segment_len, cfg.learning_starts, cfg.action_repeat, rollout=ro)
     i = 0
     tlog: Dict[str, Any] = {}
@@ -796,7 +843,10 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
                 ro.cycle(i)
                 i += 1
             elif collected_rollout:
-                ro.collect(cfg.segment_len)
+                if exploration_beta is not None and agent.timesteps_so_far >= cfg.learning_starts:
+                    ro.collect(cfg.segment_len, colored=True)
+                else:
+                    ro.collect(cfg.segment_len)
             else:
                 next(seg_gen)
             agent.timesteps_so_far += step_rows
