@@ -86,6 +86,10 @@ INIT_ALL = INIT_ACTOR | INIT_CRITICS | INIT_ALPHA
 DORMANT_SYMBOLS = ["sactd3_dormant_scan_device", "sactd3_dormant_stats", "sactd3_redo"]
 DORMANT_ACTOR, DORMANT_CRITICS = 1, 2   # `what` of sactd3_dormant_scan_device / sactd3_redo (SACTD3_DORMANT_*)
 DORMANT_PAIRS = ("actor_l1", "actor_l2", "q1_l1", "q1_l2", "q2_l1", "q2_l2")   # the six (net, layer) pairs, net-major
+# every symbol include/sactd3_feature_rank.h declares (tests/test_feature_rank_host.py checks the header against this list)
+FEATURE_RANK_SYMBOLS = ["sactd3_feature_rank_device", "sactd3_feature_rank_stats"]
+FEATURE_RANK_NETS = ("actor", "q1", "q2")   # the order of the nets in its outputs
+FEATURE_RANK_SUMMARY = ("trace", "lambda_sum", "rank", "srank", "erank", "stable", "sweeps", "converged")   # summary[net][8]
 # every symbol include/sactd3_eval.h declares (tests/test_eval_rollout_host.py checks the header against this list)
 EVAL_SYMBOLS = ["sactd3_eval_rollout", "sactd3_eval_stats"]
 EVAL_GREEDY, EVAL_SAMPLE = 0, 1     # sactd3_eval_config.mode (SACTD3_EVAL_*)
@@ -370,6 +374,12 @@ def load_library():
     }
     assert sorted(dormant_sig) == sorted(DORMANT_SYMBOLS)
     sig.update(dormant_sig)
+    feature_rank_sig = {
+        "sactd3_feature_rank_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_uint32, C.c_float, C.c_float, vp, vp, vp, C.c_int]),
+        "sactd3_feature_rank_stats": (C.c_int, [vp, i64p, C.POINTER(C.c_float)]),
+    }
+    assert sorted(feature_rank_sig) == sorted(FEATURE_RANK_SYMBOLS)
+    sig.update(feature_rank_sig)
     eval_sig = {
         "sactd3_eval_rollout": (C.c_int, [vp, vp, C.POINTER(CEvalConfig), C.POINTER(CEvalOut), vp, C.c_int]),
         "sactd3_eval_stats": (C.c_int, [vp, i64p]),

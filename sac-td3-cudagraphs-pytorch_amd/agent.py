@@ -647,6 +647,7 @@ class Agent:
         self.resets_so_far = 0      # reset_networks() calls: run-time state, not part of a checkpoint
         self.recycles_so_far = 0    # recycle_dormant() calls: the same
         self._dormant_gen = None    # dormant()'s index generator, made at its first call
+        self._feature_rank_gen = None    # feature_rank()'s, the same
         self.min_ac, self.max_ac = np.asarray(min_ac, np.float32), np.asarray(max_ac, np.float32)
         self.timesteps_so_far = 0
         self.actor_updates_so_far = 0
@@ -721,6 +722,30 @@ class Agent:
         if bits & _lib.DORMANT_CRITICS:
             out["critics"] = (got["q1_l1"] + got["q1_l2"] + got["q2_l1"] + got["q2_l2"]) / 1024.0
         return out
+
+    def feature_rank(self, rows: int = 1024, delta: float = 0.01, seed: Optional[int] = None, what=("actor", "critics")) -> Dict[str, float]:
+        """The feature rank of the online nets' last hidden layer over `rows` ring rows (at most 4096) drawn uniformly on the device
+        with a torch generator of this method's own -- seeded by `seed` at its first use (None: the engine's seed); neither the
+        training index stream nor dormant()'s is touched and training does not see the call (Engine.feature_rank).
+        -> {"srank_<net>", "erank_<net>", "rank_<net>", "converged_<net>"} for <net> in actor, q1, q2 as asked for: Kumar et al.'s
+        effective rank at `delta`, Roy & Vetterli's, the number of singular values above the engine's floor, and whether the solver
+        ended on a sweep without a rotation (0: it ran out of sweeps -- a RuntimeWarning says so, the figures are its last sweep's)."""
+        import torch
+        eng = self.engine
+        dev = torch.device("cuda", eng.cfg.device_id)
+        if self._feature_rank_gen is None:
+            self._feature_rank_gen = torch.Generator(device=dev)
+            self._feature_rank_gen.manual_seed(int(eng.cfg.seed if seed is None else seed))
+        n = len(self.rb) if self.rb is not None else eng.rb_len()
+        if n < 1:
+            raise ValueError("feature_rank: the replay ring is empty")
+        index = torch.randint(0, n, (int(rows),), generator=self._feature_rank_gen, device=dev, dtype=torch.int64)
+        got = eng.feature_rank(index, what=what, delta=delta)
+        late = [net for net, ok in got["converged"].items() if not ok]
+        if late:
+            import warnings
+            warnings.warn(f"feature_rank: the eigen-solver did not converge in {got['sweeps'][late[0]]} sweeps for {late}", RuntimeWarning)
+        return {f"{name}_{net}": got[name][net] for name in ("srank", "erank", "rank", "converged") for net in got["rank"]}
 
     def recycle_dormant(self, what=("actor", "critics")) -> int:
         """ReDo: re-initialise the hidden units the last dormant() marked in the nets `what` names and keep everything else

@@ -1,11 +1,13 @@
-// The dormant-neuron scan's and the ReDo recycler's translation unit: their four kernels (dormant_kernels.h) and the launchers
-// engine.hip calls (dormant.h).  A translation unit of its own inside libsactd3_hip.so, as param_init.hip and hindsight.hip are:
+// The plasticity diagnostics' translation unit: the dormant-neuron scan's and the ReDo recycler's four kernels (dormant_kernels.h), the
+// feature-rank call's two (feature_rank_kernels.h, which uses the scan's compaction kernel and helpers) and the launchers engine.hip
+// calls (dormant.h, feature_rank.h).  A translation unit of its own inside libsactd3_hip.so, as param_init.hip and hindsight.hip are:
 // engine.hip gains no kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "dormant_kernels.h"
+#include "feature_rank_kernels.h"
 
 // what the kernels' address arithmetic relies on; the engine's checks (sactd3_dormant_scan_device, sactd3_redo) come first, these stand
 // between any caller and the launch
@@ -43,5 +45,24 @@ hipError_t dormant_scan_launch(const DormantScanArgs& p, hipStream_t stream) {
 hipError_t dormant_redo_launch(const RedoArgs& p, hipStream_t stream) {
   if (!nets_ok(p.net, p.nnets, true) || !state_ok(p.st)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_redo_recycle, dim3(DM_HID / 16, 2, p.nnets), dim3(256), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t feature_rank_launch(const FrankArgs& q, hipStream_t stream) {
+  const DormantScanArgs& p = q.scan;
+  const FrankState& s = q.st;
+  if (!nets_ok(p.net, p.nnets, false) || !s.part || ((uintptr_t)s.part & 15u) || !s.slots || !s.rows || !s.lambda || !s.summary || !s.words) return hipErrorInvalidValue;
+  if (p.st.slots != s.slots || p.st.rows != s.rows) return hipErrorInvalidValue;      // (k_dormant_compact writes this call's list, no scan's)
+  if (!p.ring || ((uintptr_t)p.ring & 15u) || !p.idx || p.idx_ld < 1 || p.n < 1 || p.n > FR_MAXN || p.len < 1 || (p.rec_f & 3)) return hipErrorInvalidValue;
+  if (!(q.delta > 0.f && q.delta < 1.f) || !(q.floor >= 1e-6f && q.floor < 1.f)) return hipErrorInvalidValue;
+  for (int i = 0; i < p.nnets; ++i)
+    if (p.net[i].ld1 > p.rec_f) return hipErrorInvalidValue;      // (a row's 16-byte reads stay inside its record)
+  hipLaunchKernelGGL(k_dormant_compact, dim3(1), dim3(256), 0, stream, p);
+  hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return he;
+  hipLaunchKernelGGL(k_frank_gram, dim3(frank_groups(p.n), p.nnets, 2), dim3(256), 0, stream, q);
+  he = hipGetLastError();
+  if (he != hipSuccess) return he;
+  hipLaunchKernelGGL(k_frank_eig, dim3(p.nnets), dim3(FR_THREADS), 0, stream, q);
   return hipGetLastError();
 }

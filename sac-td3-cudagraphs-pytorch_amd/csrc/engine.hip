@@ -38,6 +38,9 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 // ... and the dormant-neuron scan with its recycler (dormant.hip; its C ABI is include/sactd3_dormant.h, defined behind the initialiser's)
 #include "dormant.h"
 #include "../../include/sactd3_dormant.h"
+// ... and the feature-rank call (feature_rank_kernels.h, compiled in dormant.hip; its C ABI is include/sactd3_feature_rank.h, defined behind the scan's)
+#include "feature_rank.h"
+#include "../../include/sactd3_feature_rank.h"
 // ... and the coloured-noise generator (noise.hip; its C ABI is include/sactd3_noise.h, defined behind the dormant scan's)
 #include "noise.h"
 #include "../../include/sactd3_noise.h"
@@ -331,6 +334,11 @@ struct sactd3_engine {
   DormantState dm{};
   bool dm_scanned[2] = {false, false};
   int64_t dm_host[2] = {};
+  // The feature rank (sactd3_feature_rank_device; include/sactd3_feature_rank.h; device code: feature_rank_kernels.h, in the dormant
+  // scan's translation unit).  fr: the slot list, the Gram partials, the spectra, the summaries and the device words, all made at the
+  // first call and shared with nothing -- an engine that never asks holds nothing more than before.  fr_calls: the calls.
+  FrankState fr{};
+  int64_t fr_calls = 0;
   // Coloured exploration noise (sactd3_colored_noise_device; include/sactd3_noise.h; device code: noise_kernels.h, a translation unit of
   // its own).  nz_tables: the amplitude and twiddle tables of every (beta, length) pair asked for so far, each made at its first use --
   // an engine that never generates holds nothing more than before.
@@ -4280,6 +4288,66 @@ int sactd3_redo(sactd3_engine* e, uint32_t what, uint64_t seed, uint32_t epoch) 
   if (what & SACTD3_DORMANT_ACTOR) e->dm_scanned[0] = false;                 // a mask is good for one redo
   if (what & SACTD3_DORMANT_CRITICS) e->dm_scanned[1] = false;
   ++e->dm_host[1];
+  return 0;
+}
+
+// ---- the feature rank (include/sactd3_feature_rank.h): like a scan it writes memory of its own and the caller's, nothing else of the
+// engine's: no CHAIN_BREAK, no counter, allowed while an acting call is in flight
+int sactd3_feature_rank_device(sactd3_engine* e, const int64_t* idx, int64_t idx_ld, int n, uint32_t what, float delta, float floor,
+                               float* spectrum, float* gram, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first: a refused call has launched, allocated and counted nothing
+  if (!idx) return e->fail(SACTD3_EINVAL, "feature_rank_device: `idx` is NULL");
+  if (n < 1 || n > FR_MAXN) return e->fail(SACTD3_EINVAL, "feature_rank_device: 1 <= n <= 4096 required");
+  if (idx_ld < 1) return e->fail(SACTD3_EINVAL, "feature_rank_device: row stride of `idx` is below its width");
+  RCCHK(dormant_what(e, what, "feature_rank_device"));
+  if (!(delta > 0.f && delta < 1.f)) return e->fail(SACTD3_EINVAL, "feature_rank_device: delta must lie in (0, 1)");
+  if (!(floor >= 1e-6f && floor < 1.f)) return e->fail(SACTD3_EINVAL, "feature_rank_device: floor must lie in [1e-6, 1)");
+  if (flags & ~(SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) return e->fail(SACTD3_EINVAL, "feature_rank_device: unknown flag");
+  USE_DEVICE(e);
+  RCCHK(device_ptr_check(e, idx, "feature_rank_device", "idx"));
+  if (spectrum) RCCHK(device_ptr_check(e, spectrum, "feature_rank_device", "spectrum"));
+  if (gram) RCCHK(device_ptr_check(e, gram, "feature_rank_device", "gram"));
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "feature_rank_device: buffer is empty");
+  RCCHK(first_use_alloc(e, &e->fr.part, (size_t)DM_NETS * FR_MAXG * DM_HID * DM_HID, false));      // (never zeroed: a call writes every partial it reads)
+  RCCHK(first_use_alloc(e, &e->fr.slots, (size_t)FR_MAXN, false));                                 // (the same: k_dormant_compact writes what k_frank_gram reads)
+  RCCHK(first_use_alloc(e, &e->fr.rows, 4, false));
+  RCCHK(first_use_alloc(e, &e->fr.lambda, (size_t)DM_NETS * DM_HID));
+  RCCHK(first_use_alloc(e, &e->fr.summary, (size_t)DM_NETS * FR_SUMMARY));
+  RCCHK(first_use_alloc(e, &e->fr.words, (size_t)FR_WORDS));
+  FrankArgs g{};
+  g.scan.ring = e->ring; g.scan.rec_f = e->rec_f; g.scan.len = (int)e->rb_len;
+  g.scan.idx = (const long long*)idx; g.scan.idx_ld = (long)idx_ld; g.scan.n = n; g.scan.ln = e->cfg.layer_norm;
+  g.scan.nnets = dormant_nets(e, what, g.scan.net);
+  g.scan.st.slots = e->fr.slots; g.scan.st.rows = e->fr.rows;      // (of DormantState the compaction kernel touches these two alone)
+  g.st = e->fr; g.delta = delta; g.floor = floor; g.spectrum = spectrum; g.gram = gram;
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  const int ordered = (flags & (SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) ? SACTD3_SRC_ORDERED : 0;      // (one pair of events serves both sides)
+  RCCHK(src_order_begin(e, caller, ordered));
+  const hipError_t he = feature_rank_launch(g, e->stream);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "feature_rank_device: k_frank_gram / k_frank_eig", he);
+  RCCHK(src_order_end(e, caller, ordered));
+  ++e->fr_calls;
+  return 0;
+}
+
+int sactd3_feature_rank_stats(sactd3_engine* e, int64_t counters[16], float summary[3][8]) {
+  if (!e || !counters || !summary) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int w[FR_WORDS] = {};
+  float sm[DM_NETS * FR_SUMMARY] = {};
+  if (e->fr.words) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(w, e->fr.words, sizeof(w), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sm, e->fr.summary, sizeof(sm), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 16; ++i) counters[i] = 0;
+  counters[0] = e->fr_calls; counters[1] = w[FR_W_VALID]; counters[2] = w[FR_W_REFUSED];
+  for (int i = 0; i < DM_NETS; ++i) {
+    counters[3 + i] = w[FR_W_RANK + i]; counters[6 + i] = w[FR_W_SRANK + i]; counters[9 + i] = w[FR_W_SWEEPS + i];
+    counters[12] += w[FR_W_UNCONVERGED + i];
+    for (int k = 0; k < FR_SUMMARY; ++k) summary[i][k] = sm[i * FR_SUMMARY + k];
+  }
   return 0;
 }
 

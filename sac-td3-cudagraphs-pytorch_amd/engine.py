@@ -248,6 +248,57 @@ class Engine:
         return {"scans": v[0], "valid_rows": v[1], "rows_refused": v[2], "dormant": dict(zip(_lib.DORMANT_PAIRS, v[3:9])),
                 "redo_calls": v[9], "recycled": v[10], "rows_left_zero": v[11]}
 
+    # -- the feature rank: the Gram spectrum of the last hidden layer over ring rows (include/sactd3_feature_rank.h)
+    def feature_rank(self, index, what=("actor", "critics"), delta: float = 0.01, floor: float = 1e-4, spectrum: bool = False,
+                     gram: bool = False) -> Dict[str, object]:
+        """sactd3_feature_rank_device: the eigenvalues of M = Phi^T Phi / V, Phi the second hidden layer of the online nets `what`
+        names over the ring rows `index` (a 1-D int64 array in this device's memory, up to 4096 rows; a slot outside the ring is
+        refused and counted, never read), and the ranks read from them: `rank` (singular values above sqrt(floor) of the largest),
+        `srank` (Kumar et al. 2021, at `delta`), `erank` (Roy & Vetterli), `stable`.  Three launches on the engine's stream, ordered
+        on the GPU against torch's current stream; training, acting and the dormant scan do not see the call.  One host wait, for
+        the summary.
+        -> {"valid_rows", "refused_rows", and per name of _lib.FEATURE_RANK_SUMMARY a dict {net: value} over the nets asked for
+            ("actor", "q1", "q2") [, "lambda": a [3, 256] float32 CUDA tensor, descending; "gram": [3, 256, 256]; rows of nets not
+            asked for are 0]}"""
+        import torch
+        cai = getattr(index, "__cuda_array_interface__", None)
+        if cai is None or cai["typestr"] != "<i8" or len(cai["shape"]) != 1:
+            raise TypeError("feature_rank: `index` is a 1-D int64 array in the memory of the engine's device")
+        n, strides = int(cai["shape"][0]), cai.get("strides")
+        ld = 1 if strides is None or n <= 1 else strides[0] // 8
+        if ld < 1 or (strides is not None and n > 1 and strides[0] % 8):
+            raise ValueError("feature_rank: `index` needs a positive stride in whole elements")
+        bits = self._dormant_bits(what)
+        dev = torch.device("cuda", self.cfg.device_id)
+        lam = torch.zeros(3, 256, dtype=torch.float32, device=dev) if spectrum else None
+        mat = torch.zeros(3, 256, 256, dtype=torch.float32, device=dev) if gram else None
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+        self._ck(self.lib.sactd3_feature_rank_device(self._h, _vp(int(cai["data"][0])), ld, n, bits, float(delta), float(floor),
+                                                     _vp(lam.data_ptr() if spectrum else 0), _vp(mat.data_ptr() if gram else 0),
+                                                     _vp(stream), _lib.SRC_ORDERED | _lib.DST_ORDERED))
+        st = self.feature_rank_stats()
+        nets = [k for k in _lib.FEATURE_RANK_NETS if bits & (_lib.DORMANT_ACTOR if k == "actor" else _lib.DORMANT_CRITICS)]
+        got = {"valid_rows": st["valid_rows"], "refused_rows": n - st["valid_rows"]}      # (a row is one or the other)
+        for name in _lib.FEATURE_RANK_SUMMARY:
+            got[name] = {k: st[name][k] for k in nets}
+        if spectrum:
+            got["lambda"] = lam
+        if gram:
+            got["gram"] = mat
+        return got
+
+    def feature_rank_stats(self) -> Dict[str, object]:
+        """counters and the last summaries of feature_rank (sactd3_feature_rank_stats; waits for the engine's stream: they live on
+        the device)"""
+        out, sm = (C.c_int64 * 16)(), (C.c_float * 24)()
+        self._ck(self.lib.sactd3_feature_rank_stats(self._h, out, sm))
+        v = [int(x) for x in out]
+        st = {"calls": v[0], "valid_rows": v[1], "rows_refused": v[2], "not_converged": v[12]}
+        for j, name in enumerate(_lib.FEATURE_RANK_SUMMARY):
+            whole = name in ("rank", "srank", "sweeps", "converged")
+            st[name] = {k: (int(sm[8 * i + j]) if whole else float(sm[8 * i + j])) for i, k in enumerate(_lib.FEATURE_RANK_NETS)}
+        return st
+
     # -- coloured exploration noise (include/sactd3_noise.h)
     def colored_noise(self, beta: float, length: int, sequences: int, chunk: int = 0, epoch: int = 0, out=None):
         """sactd3_colored_noise_device: chunk `chunk` of `sequences` independent 1/f^beta Gaussian sequences (beta in [0, 2]: 0 white,

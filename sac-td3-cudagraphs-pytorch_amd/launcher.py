@@ -372,6 +372,12 @@ def mode_flags(args, plan) -> dict:
         raise ValueError("--dormant_tau needs --dormant ROWS: it is the threshold of that scan")
     if getattr(args, "redo_every", None) is not None:       # (the same; without --dormant: refused by train_keywords)
         flags["redo_every"] = int(args.redo_every)
+    if getattr(args, "feature_rank", None) is not None:     # (the same)
+        flags["feature_rank"] = int(args.feature_rank)
+        if getattr(args, "feature_rank_delta", None) is not None:
+            flags["feature_rank_delta"] = float(args.feature_rank_delta)
+    elif getattr(args, "feature_rank_delta", None) is not None:
+        raise ValueError("--feature_rank_delta needs --feature_rank ROWS: it is the delta of that call's srank")
     if getattr(args, "init", "torch") != "torch":           # (the same)
         flags["init"] = args.init
     if getattr(args, "eval_one_launch", False) or getattr(args, "q_bias", 0):      # (the same: keys only when a flag was given; every job
@@ -387,7 +393,8 @@ def reset_names(text=None) -> tuple:
 def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, prior_fraction, updates_per_step, overlap_acting: bool,
                    device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False,
                    reset_every=None, reset_what=None, init: str = "torch", num_updates=None, collected_rollout: bool = False,
-                   dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None) -> dict:
+                   dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None,
+                   feature_rank=None, feature_rank_delta=None) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
@@ -404,7 +411,8 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     is the Agent's keyword, not loop.train's: checked here, never in the result.
     `dormant` [, `dormant_tau`] (--dormant ROWS [--dormant_tau T]: the dormant-neuron ratio at every evaluation, loop.train dormant=...)
     and `redo_every` (--redo_every N: ReDo recycling on that scan): asked of loop.redo_rule; the keys are in the result only when the
-    flags were given.
+    flags were given.  `feature_rank` [, `feature_rank_delta`] (--feature_rank ROWS [--feature_rank_delta D]: the effective rank of the
+    last hidden layer at every evaluation, loop.train feature_rank=...): asked of loop.feature_rank_rule, the key the same way.
     `exploration_beta` [, `exploration_len`] (--exploration_beta B [--exploration_len L]: coloured exploration noise in the collected
     segments, loop.train exploration_beta=...): asked of loop.exploration_rule with the job's segment_len; the keys are in the result
     only when --exploration_beta was given."""
@@ -431,19 +439,26 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
         update["reset_every"], update["reset_what"] = int(reset_every), tuple(reset_what if reset_what is not None else loop.RESET_ALL)
     loop.update_plan(cfg, sampler=None, **update, **(dict(num_updates=int(num_updates)) if num_updates is not None else {}))
     rollout = dict(collected_rollout=True) if collected_rollout else {}
-    watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates)
+    watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates, feature_rank, feature_rank_delta)
     return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout, **noise, **watch)
 
 
-def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_every=None, num_updates=None) -> dict:
-    """--dormant ROWS [--dormant_tau T] [--redo_every N] as the keywords loop.train and loop.train_offline take, asked of loop.redo_rule
-    (ValueError for what they would refuse); {} without the flags"""
+def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_every=None, num_updates=None, feature_rank=None,
+                     feature_rank_delta=None) -> dict:
+    """--dormant ROWS [--dormant_tau T] [--redo_every N] [--feature_rank ROWS [--feature_rank_delta D]] as the keywords loop.train and
+    loop.train_offline take, asked of loop.redo_rule and loop.feature_rank_rule (ValueError for what they would refuse); {} without
+    the flags"""
     kw = {}
     if dormant is not None:
         kw["dormant"] = dict(rows=int(dormant), **(dict(tau=float(dormant_tau)) if dormant_tau is not None else {}))
     if redo_every is not None:
         kw["redo_every"] = int(redo_every)
     loop.redo_rule(kw.get("dormant"), redo_every, loop.REDO_ALL, reset_every, num_updates)
+    if feature_rank is not None:
+        kw["feature_rank"] = dict(rows=int(feature_rank), **(dict(delta=float(feature_rank_delta)) if feature_rank_delta is not None else {}))
+        loop.feature_rank_rule(kw["feature_rank"])
+    elif feature_rank_delta is not None:
+        raise ValueError("feature_rank_delta needs feature_rank ROWS: it is the delta of that call's srank")
     return kw
 
 
@@ -452,7 +467,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
             offline_dataset=None, num_updates=None, prior_fraction=None, updates_per_step: int = 1, policy_stats: int = 0,
             native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, init: str = "torch",
             reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, collected_rollout: bool = False,
-            dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None, **over):
+            dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None,
+            feature_rank=None, feature_rank_delta=None, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -472,7 +488,9 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     reset_every=...).
     `eval_one_launch`: with `device_env` on a native id, every evaluation window is one kernel launch (envs.device_episodes
     one_launch=True); `q_bias` = N > 0: N further evaluation envs, and at every evaluation the normalised Q-bias of the current policy on
-    fresh episodes of them (loop.train q_bias=dict(env=, seed=)); both need what eval_plan states."""
+    fresh episodes of them (loop.train q_bias=dict(env=, seed=)); both need what eval_plan states.
+    `feature_rank` [, `feature_rank_delta`]: the effective rank of the last hidden layer over that many ring rows at every evaluation
+    (loop.train / loop.train_offline feature_rank=...)."""
     import json
     import time
     from pathlib import Path
@@ -512,7 +530,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     resets = dict(reset_every=reset_every, reset_what=reset_what) if reset_every is not None else {}
     offline = offline_dataset is not None and prior_fraction is None
     watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every,
-                             int(num_updates if num_updates is not None else cfg.num_timesteps) if offline else None)
+                             int(num_updates if num_updates is not None else cfg.num_timesteps) if offline else None,
+                             feature_rank, feature_rank_delta)
     run_dir = Path(out_dir) / f"{env_id}__{algo}__seed{seed:02d}"
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
@@ -580,7 +599,7 @@ def _worker_main(args, plan, flags) -> int:
             if args.collected_rollout:           # (the same)
                 out["collected_rollout"] = True
             for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias", "dormant", "dormant_tau", "redo_every",
-                      "exploration_beta", "exploration_len"):      # (the same)
+                      "exploration_beta", "exploration_len", "feature_rank", "feature_rank_delta"):      # (the same)
                 if k in flags:
                     out[k] = flags[k]
         else:
@@ -665,6 +684,10 @@ def main(argv=None) -> int:
                     help="at every evaluation: the dormant-neuron ratio of the online nets over ROWS ring rows, scanned on the device "
                          "(loop.train dormant=...; vitals/dormant_actor, vitals/dormant_critics)")
     ap.add_argument("--dormant_tau", type=float, default=None, metavar="T", help="with --dormant: the score at or below which a unit is dormant (default 0.025)")
+    ap.add_argument("--feature_rank", type=int, default=None, metavar="ROWS",
+                    help="at every evaluation: the effective rank of the online nets' last hidden layer over ROWS ring rows (at most 4096), "
+                         "on the device (loop.train feature_rank=...; vitals/srank_actor, vitals/srank_critics, vitals/erank_*)")
+    ap.add_argument("--feature_rank_delta", type=float, default=None, metavar="D", help="with --feature_rank: the delta of srank (default 0.01)")
     ap.add_argument("--redo_every", type=int, default=None, metavar="N",
                     help="with --dormant: ReDo -- every N critic updates, scan and re-initialise the dormant units (excludes --reset_every)")
     ap.add_argument("--reset_what", default=None, metavar="actor,critics,alpha",

@@ -510,6 +510,39 @@ class Dormant:
         return self.last
 
 
+class FeatureRank:
+    """`feature_rank=dict(rows=, delta= [, seed=])` of train / train_offline: at every evaluation point `agent.feature_rank` -- the
+    effective rank of the online nets' last hidden layer (Kumar et al. 2021; Roy & Vetterli) over `rows` ring rows drawn with a
+    generator of its own.  -> vitals/srank_actor, vitals/srank_critics, vitals/erank_actor, vitals/erank_critics (the critics: the
+    smaller of the two) and vitals/feature_rank_converged (0 where the solver of any net ran out of sweeps).  The call has device memory of its own and touches no counter: the run's bits are those of the run without it."""
+    KEYS = ("vitals/srank_actor", "vitals/srank_critics", "vitals/erank_actor", "vitals/erank_critics", "vitals/feature_rank_converged")
+
+    def __init__(self, agent, spec):
+        self.agent, self.kw, self.last = agent, dict(spec), {}
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        got = self.agent.feature_rank(**self.kw)
+        self.last = {f"vitals/{k}_actor": got[f"{k}_actor"] for k in ("srank", "erank")}
+        self.last.update({f"vitals/{k}_critics": min(got[f"{k}_q1"], got[f"{k}_q2"]) for k in ("srank", "erank")})
+        self.last["vitals/feature_rank_converged"] = min(int(got[f"converged_{net}"]) for net in ("actor", "q1", "q2"))
+        if tabular is not None:
+            for k, v in self.last.items():
+                tabular.record(k, v)
+        return self.last
+
+
+def feature_rank_rule(feature_rank):
+    """the keyword rule of `feature_rank`, asked before an agent is touched (ValueError)"""
+    if feature_rank is None:
+        return
+    if not isinstance(feature_rank, dict) or set(feature_rank) - {"rows", "delta", "seed"} or "rows" not in feature_rank:
+        raise ValueError("feature_rank must be a dict with `rows` [, `delta`, `seed`]")
+    if not 1 <= int(feature_rank["rows"]) <= 4096:
+        raise ValueError("feature_rank: 1 <= rows <= 4096")
+    if not 0.0 < float(feature_rank.get("delta", 0.01)) < 1.0:
+        raise ValueError("feature_rank: delta must lie in (0, 1)")
+
+
 def redo_rule(dormant, redo_every, redo_what=REDO_ALL, reset_every=None, num_updates: Optional[int] = None):
     """The keyword rules of `dormant` / `redo_every` / `redo_what`, asked before an agent is touched (ValueError), and the rule itself:
     None without `redo_every`, else redo(agent, before, first=None) -> the update count now, with the contract of update_plan's reset:
@@ -562,10 +595,11 @@ class _Vitals:
         return {k: v for part in self.parts for k, v in part.last.items()}
 
 
-def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None):
-    """PolicyStats, QBias and / or Dormant as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
+def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None):
+    """PolicyStats, QBias, Dormant and / or FeatureRank as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
     parts = ([PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0))] if policy_stats else []) + ([QBias(agent, q_bias)] if q_bias is not None else [])
     parts += [Dormant(agent, dormant)] if dormant is not None else []
+    parts += [FeatureRank(agent, feature_rank)] if feature_rank is not None else []
     return None if not parts else parts[0] if len(parts) == 1 else _Vitals(parts)
 
 
@@ -738,7 +772,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           hindsight: Optional[Dict[str, Any]] = None, fused_rollout: bool = False,
           reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, q_bias: Optional[Dict[str, Any]] = None,
           collected_rollout: bool = False, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
-          redo_what: Any = REDO_ALL, exploration_beta: Optional[float] = None, exploration_len: int = 256) -> Dict[str, float]:
+          redo_what: Any = REDO_ALL, exploration_beta: Optional[float] = None, exploration_len: int = 256,
+          feature_rank: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -808,9 +843,13 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     of the online nets over `rows` ring rows (Dormant) -- vitals/dormant_actor, vitals/dormant_critics, vitals/recycled; the run itself
     is bit for bit the run without it.  `redo_every=N` (needs `dormant`, excludes `reset_every`; `redo_what`: any of "actor",
     "critics"): ReDo -- whenever `agent.qnet_updates_so_far` reaches a multiple of N, one scan and `agent.recycle_dormant(redo_what)`
-    between two loop bodies, on the schedule of `reset_every`."""
+    between two loop bodies, on the schedule of `reset_every`.
+    `feature_rank=dict(rows=, delta= [, seed=])` (default None: off, and no call is made): at every evaluation point the effective rank
+    of the online nets' last hidden layer over `rows` ring rows (FeatureRank) -- vitals/srank_actor, vitals/srank_critics,
+    vitals/erank_actor, vitals/erank_critics, vitals/feature_rank_converged; the run itself is bit for bit the run without it."""
     redo = redo_rule(dormant, redo_every, redo_what, reset_every)         # (refusals before the agent is touched)
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant)
+    feature_rank_rule(feature_rank)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank)
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
                        prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
                        reset_every=reset_every, reset_what=reset_what)
@@ -911,7 +950,7 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
                   on_eval: Optional[Callable[[Any, int], None]] = None, eval_every_updates: Optional[int] = None,
                   policy_stats: int = 0, reset_every: Optional[int] = None, reset_what: Any = RESET_ALL,
                   q_bias: Optional[Dict[str, Any]] = None, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
-                  redo_what: Any = REDO_ALL) -> Dict[str, float]:
+                  redo_what: Any = REDO_ALL, feature_rank: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
@@ -921,16 +960,17 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
     only), `q_bias=dict(env=, seed=)` as for train.  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
     is refused (update_plan's table).  `dormant` / `redo_every` / `redo_what` as for train: the runs also end where a redo is due.
-    Returns the last metrics."""
+    `feature_rank` as for train.  Returns the last metrics."""
     num_updates = int(num_updates)
     if num_updates < 0:
         raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
     redo = redo_rule(dormant, redo_every, redo_what, reset_every, num_updates)      # (before the agent is touched)
+    feature_rank_rule(feature_rank)
     reset = None
     if reset_every is not None:                                           # (before the agent is touched)
         reset = update_plan(cfg, fused=True, sampler=None, prioritized=None, n_step=1, one_launch=False, prior_fraction=None,
                             updates_per_step=1, reset_every=reset_every, reset_what=reset_what, num_updates=num_updates).reset
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank)
     resets = reset is not None                                            # vitals/resets belongs to a run that resets
     if redo is not None:
         reset, reset_every = redo, redo_every                             # the same schedule: the runs end where a redo is due
