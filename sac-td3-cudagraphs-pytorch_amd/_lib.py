@@ -90,6 +90,10 @@ DORMANT_PAIRS = ("actor_l1", "actor_l2", "q1_l1", "q1_l2", "q2_l1", "q2_l2")   #
 FEATURE_RANK_SYMBOLS = ["sactd3_feature_rank_device", "sactd3_feature_rank_stats"]
 FEATURE_RANK_NETS = ("actor", "q1", "q2")   # the order of the nets in its outputs
 FEATURE_RANK_SUMMARY = ("trace", "lambda_sum", "rank", "srank", "erank", "stable", "sweeps", "converged")   # summary[net][8]
+# every symbol include/sactd3_action_values.h declares (tests/test_action_values_host.py checks the header against this list)
+ACTION_VALUES_SYMBOLS = ["sactd3_action_values_device", "sactd3_action_values_stats"]
+AV_POLICY, AV_UNIFORM = 0, 1        # `source` of sactd3_action_values_device (SACTD3_AV_*)
+AV_SUMMARY = ("q_max", "q_mean", "q_lme", "q_std", "soft_value", "q_data", "logp_mean", "finite")   # summary[row][8]
 # every symbol include/sactd3_eval.h declares (tests/test_eval_rollout_host.py checks the header against this list)
 EVAL_SYMBOLS = ["sactd3_eval_rollout", "sactd3_eval_stats"]
 EVAL_GREEDY, EVAL_SAMPLE = 0, 1     # sactd3_eval_config.mode (SACTD3_EVAL_*)
@@ -137,6 +141,14 @@ POLICY_IO_FIELDS = (("actions", "a"), ("eps", "a"), ("mode", "a"), ("mean", "a")
 class CPolicyIO(C.Structure):
     """sactd3_policy_io: nine pointers (None = not given / not wanted), each with its row stride in elements"""
     _fields_ = [(n, t) for f, _ in POLICY_IO_FIELDS for n, t in ((f, C.c_void_p), (f + "_ld", C.c_int64))]
+
+
+class CActionValuesIO(C.Structure):
+    """sactd3_action_values_io: device pointers (None = not given / not wanted), the strided ones with their row stride in elements"""
+    _fields_ = [("actions", C.c_void_p), ("actions_ld", C.c_int64), ("eps", C.c_void_p), ("eps_ld", C.c_int64),
+                ("summary", C.c_void_p), ("summary_ld", C.c_int64), ("best_index", C.c_void_p),
+                ("best_action", C.c_void_p), ("best_action_ld", C.c_int64),
+                ("cand", C.c_void_p), ("cand_q", C.c_void_p), ("cand_logp", C.c_void_p), ("eps_out", C.c_void_p)]
 
 
 class CHindsightConfig(C.Structure):
@@ -380,6 +392,13 @@ def load_library():
     }
     assert sorted(feature_rank_sig) == sorted(FEATURE_RANK_SYMBOLS)
     sig.update(feature_rank_sig)
+    action_values_sig = {
+        "sactd3_action_values_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                  C.POINTER(CActionValuesIO), vp, C.c_int]),
+        "sactd3_action_values_stats": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(action_values_sig) == sorted(ACTION_VALUES_SYMBOLS)
+    sig.update(action_values_sig)
     eval_sig = {
         "sactd3_eval_rollout": (C.c_int, [vp, vp, C.POINTER(CEvalConfig), C.POINTER(CEvalOut), vp, C.c_int]),
         "sactd3_eval_stats": (C.c_int, [vp, i64p]),

@@ -648,6 +648,7 @@ class Agent:
         self.recycles_so_far = 0    # recycle_dormant() calls: the same
         self._dormant_gen = None    # dormant()'s index generator, made at its first call
         self._feature_rank_gen = None    # feature_rank()'s, the same
+        self._ood_gen = None        # ood_gap()'s, the same
         self.min_ac, self.max_ac = np.asarray(min_ac, np.float32), np.asarray(max_ac, np.float32)
         self.timesteps_so_far = 0
         self.actor_updates_so_far = 0
@@ -746,6 +747,48 @@ class Agent:
             import warnings
             warnings.warn(f"feature_rank: the eigen-solver did not converge in {got['sweeps'][late[0]]} sweeps for {late}", RuntimeWarning)
         return {f"{name}_{net}": got[name][net] for name in ("srank", "erank", "rank", "converged") for net in got["rank"]}
+
+    def action_values(self, in_td: Mapping[str, Any], *, candidates: int = 16, source: str = "policy", target: bool = False,
+                      sigma: float = 0.2, tau: float = 1.0, eps: Any = None, dump: bool = False) -> Dict[str, Any]:
+        """What the critics think of actions the data does not contain (include/sactd3_action_values.h): per row of `observations`
+        (float32, on the engine's device) `candidates` actions sampled from the policy (`source="policy"`) or uniformly in the bounds
+        ("uniform"), scored by the twin critics in one kernel that computes the state's share of the first layer once per row.
+        With an `actions` key `q_data` is min_k Q_k(s, a_data).  -> a dict of tensors on that device: `summary` [n, 8] and its columns
+        q_max, q_mean, q_lme, q_std, soft_value, q_data, logp_mean, finite; `best_index`, `best_action`; with `dump` every candidate,
+        its two Q-values, its log-density and the draws (Engine.action_values).  No host wait; training and acting do not see it."""
+        return self.engine.action_values(_detached(in_td["observations"]), _detached(in_td["actions"]) if "actions" in in_td else None,
+                                         candidates=candidates, source=source, target=target, sigma=sigma, tau=tau, eps=eps, dump=dump)
+
+    def predict_best_of(self, in_td: Mapping[str, Any], candidates: int = 16, out: Any = None):
+        """Act by the best of `candidates` policy samples under min(Q1, Q2) (EMaQ / SfBC / IDQL-style selection): observations
+        [n, ob_dim] on the engine's device -> actions [n, ac_dim] on that device, no host wait.  `out`: a float32 tensor to copy into."""
+        best = self.action_values(in_td, candidates=candidates)["best_action"]
+        if out is None:
+            return best
+        out[: best.shape[0]].copy_(best)
+        return out[: best.shape[0]]
+
+    def ood_gap(self, rows: int = 256, candidates: int = 16, seed: Optional[int] = None) -> Dict[str, float]:
+        """The over-estimation signal of offline RL on `rows` ring rows drawn with a torch generator of this method's own (seeded at
+        its first use; None: the engine's seed): the mean of max_a Q(s, a) - Q(s, a_data) over `candidates` policy samples and over
+        as many uniform ones, and the mean sampled soft value.  Two action_values calls; one host wait for the three means.
+        -> {"ood_gap_policy", "ood_gap_uniform", "value_sampled"}"""
+        import torch
+        eng = self.engine
+        dev = torch.device("cuda", eng.cfg.device_id)
+        if self._ood_gen is None:
+            self._ood_gen = torch.Generator(device=dev)
+            self._ood_gen.manual_seed(int(eng.cfg.seed if seed is None else seed))
+        n = len(self.rb) if self.rb is not None else eng.rb_len()
+        if n < 1:
+            raise ValueError("ood_gap: the replay ring is empty")
+        index = torch.randint(0, n, (int(rows),), generator=self._ood_gen, device=dev, dtype=torch.int64)
+        got = self.rb.rows(index)
+        td = {"observations": got["observations"], "actions": got["actions"]}
+        pol = self.action_values(td, candidates=candidates, source="policy")
+        uni = self.action_values(td, candidates=candidates, source="uniform")
+        three = torch.stack([(pol["q_max"] - pol["q_data"]).mean(), (uni["q_max"] - uni["q_data"]).mean(), pol["soft_value"].mean()]).tolist()
+        return dict(zip(("ood_gap_policy", "ood_gap_uniform", "value_sampled"), three))
 
     def recycle_dormant(self, what=("actor", "critics")) -> int:
         """ReDo: re-initialise the hidden units the last dormant() marked in the nets `what` names and keep everything else

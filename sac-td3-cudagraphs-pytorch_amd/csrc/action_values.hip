@@ -1,0 +1,40 @@
+// The candidate-scoring call's translation unit: k_action_values<16 | 32 | 64> and k_av_finish (action_values_kernels.h) and the launcher
+// engine.hip calls (action_values.h).  A translation unit of its own inside libsactd3_hip.so, as dormant.hip and param_init.hip are:
+// engine.hip gains no kernel.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "action_values_kernels.h"
+
+// what the kernel's address arithmetic relies on; the engine's checks (sactd3_action_values_device) come first, these stand between any
+// caller and the launch
+static bool av_net_ok(const DormantNet& N, int bh, int ob, int a) {
+  if (!N.P || ((uintptr_t)N.P & 15u) || N.K != ob + a || N.ld1 < N.K || N.nh != 1) return false;
+  if ((N.ld1 | N.W1 | N.b1 | N.g1 | N.be1 | N.W2 | N.b2 | N.g2 | N.be2 | N.Wh | bh) & 3) return false;
+  return N.W1 >= 0 && N.W1 + (long)DM_HID * N.ld1 <= N.b1 && N.b1 + DM_HID <= N.g1 && N.g1 + DM_HID <= N.be1 && N.be1 + DM_HID <= N.W2 &&
+         N.W2 + DM_HID * DM_HID <= N.b2 && N.b2 + DM_HID <= N.g2 && N.g2 + DM_HID <= N.be2 && N.be2 + DM_HID <= N.Wh && N.Wh + DM_HID <= bh;
+}
+
+hipError_t action_values_launch(const AvArgs& p, int candidates, hipStream_t stream) {
+  if (candidates != 16 && candidates != 32 && candidates != 64) return hipErrorInvalidValue;
+  if (p.ob < 1 || p.a < 1 || p.a > AV_MAXA || p.m < 1 || p.m > AV_CHUNK || p.row0 < 0) return hipErrorInvalidValue;
+  if (!av_net_ok(p.net[0], p.bh[0], p.ob, p.a) || !av_net_ok(p.net[1], p.bh[1], p.ob, p.a)) return hipErrorInvalidValue;
+  if (!p.x || ((uintptr_t)p.x & 15u) || (p.ldo & 3) || p.ldo < p.ob) return hipErrorInvalidValue;
+  if (p.source != AV_SRC_POLICY && p.source != AV_SRC_UNIFORM) return hipErrorInvalidValue;
+  if (p.source == AV_SRC_POLICY && (!p.head || p.head_ld < (p.sac ? 2 : 1) * p.a)) return hipErrorInvalidValue;
+  if (!p.scale || !p.bias || !p.lo || !p.hi || !p.seed || !p.words || !p.bad || (p.soft && !p.log_alpha)) return hipErrorInvalidValue;
+  if (!(p.tau > 0.f) || !std::isfinite(p.tau) || !(p.sigma >= 0.f) || !std::isfinite(p.sigma)) return hipErrorInvalidValue;
+  if ((p.actions && p.actions_ld < p.a) || (p.eps && p.eps_ld < (long)candidates * p.a)) return hipErrorInvalidValue;
+  if ((p.summary && p.summary_ld < 8) || (p.best_action && p.best_action_ld < p.a)) return hipErrorInvalidValue;
+  if (p.cand_q && ((uintptr_t)p.cand_q & 7u)) return hipErrorInvalidValue;      // (a candidate's pair is one 8-byte store)
+  const int groups = av_groups(p.m, candidates);      // (<= AV_MAXWG: m <= AV_CHUNK)
+  if (candidates == 16) hipLaunchKernelGGL(k_action_values<16>, dim3(groups), dim3(256), 0, stream, p);
+  else if (candidates == 32) hipLaunchKernelGGL(k_action_values<32>, dim3(groups), dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL(k_action_values<64>, dim3(groups), dim3(256), 0, stream, p);
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return he;
+  hipLaunchKernelGGL(k_av_finish, dim3(1), dim3(256), 0, stream, p.words, (const int*)p.bad, groups, p.tick);
+  return hipGetLastError();
+}

@@ -44,6 +44,10 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 // ... and the coloured-noise generator (noise.hip; its C ABI is include/sactd3_noise.h, defined behind the dormant scan's)
 #include "noise.h"
 #include "../../include/sactd3_noise.h"
+// ... and the candidate-scoring call (action_values.hip; its C ABI is include/sactd3_action_values.h, defined behind the feature rank's)
+#include "action_values.h"
+#include "../../include/sactd3_action_values.h"
+static_assert(AV_SRC_POLICY == SACTD3_AV_POLICY && AV_SRC_UNIFORM == SACTD3_AV_UNIFORM, "the kernel's `source` is the C ABI's");
 // ... and the evaluation rollout, whose kernel is compiled with the env kernels (env.hip): host code only here, at the end of this file
 #include "eval_rollout.h"
 // ... and the collected rollout segment, split the same way (collect_rollout.h)
@@ -339,6 +343,14 @@ struct sactd3_engine {
   // first call and shared with nothing -- an engine that never asks holds nothing more than before.  fr_calls: the calls.
   FrankState fr{};
   int64_t fr_calls = 0;
+  // Scoring sampled candidate actions per state (sactd3_action_values_device; include/sactd3_action_values.h; device code:
+  // action_values_kernels.h, a translation unit of its own).  av_x / av_z1 / av_z2 / av_head: packed observations, the actor trunk's two
+  // outputs and the actor head's outputs for AV_CHUNK rows; av_words: av_ctr and the non-finite-row counter; av_bad: the workgroups'
+  // counts of one launch.  All made at the first call and shared with nothing -- an engine that never asks holds nothing more than
+  // before.  av_host: {calls, rows, calls that drew natively}.
+  float *av_x = nullptr, *av_z1 = nullptr, *av_z2 = nullptr, *av_head = nullptr;
+  int *av_words = nullptr, *av_bad = nullptr;
+  int64_t av_host[3] = {};
   // Coloured exploration noise (sactd3_colored_noise_device; include/sactd3_noise.h; device code: noise_kernels.h, a translation unit of
   // its own).  nz_tables: the amplitude and twiddle tables of every (beta, length) pair asked for so far, each made at its first use --
   // an engine that never generates holds nothing more than before.
@@ -4348,6 +4360,104 @@ int sactd3_feature_rank_stats(sactd3_engine* e, int64_t counters[16], float summ
     counters[12] += w[FR_W_UNCONVERGED + i];
     for (int k = 0; k < FR_SUMMARY; ++k) summary[i][k] = sm[i * FR_SUMMARY + k];
   }
+  return 0;
+}
+
+// ---- scoring sampled candidate actions per state (include/sactd3_action_values.h).  Per chunk of AV_CHUNK rows: the pack kernel, then --
+// POLICY -- the actor trunk in its pinned shape and the policy head kernel into this feature's scratch (the launches sactd3_policy_device
+// issues, on other memory and with no draw, so PiCtl is never read), then k_action_values<N> and k_av_finish (action_values.hip).  Like
+// a scoring call it writes memory of its own and the caller's, nothing else of the engine's: no CHAIN_BREAK, no counter of training,
+// acting or the policy query, allowed while an acting call is in flight.
+int sactd3_action_values_device(sactd3_engine* e, const float* obs, int64_t obs_ld, int n, int candidates, int source, int which,
+                                float sigma, float tau, const sactd3_action_values_io* io, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first: a refused call has launched, allocated and counted nothing
+  if (!obs || !io) return e->fail(SACTD3_EINVAL, "action_values_device: null argument");
+  if (!(io->summary || io->best_index || io->best_action || io->cand || io->cand_q || io->cand_logp || io->eps_out))
+    return e->fail(SACTD3_EINVAL, "action_values_device: no output is set");
+  RCCHK(qvalues_args(e, "action_values_device", n, which));
+  if (candidates != 16 && candidates != 32 && candidates != 64) return e->fail(SACTD3_EINVAL, "action_values_device: `candidates` is 16, 32 or 64");
+  if (source != SACTD3_AV_POLICY && source != SACTD3_AV_UNIFORM) return e->fail(SACTD3_EINVAL, "action_values_device: `source` is SACTD3_AV_POLICY or SACTD3_AV_UNIFORM");
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "action_values_device: unknown flag");
+  if (!(sigma >= 0.f) || !std::isfinite(sigma)) return e->fail(SACTD3_EINVAL, "action_values_device: sigma must be finite and >= 0");
+  if (!(tau > 0.f) || !std::isfinite(tau)) return e->fail(SACTD3_EINVAL, "action_values_device: tau must be finite and > 0");
+  if (obs_ld < e->o) return e->fail(SACTD3_EINVAL, "action_values_device: row stride of `obs` is below its width");
+  if (e->a > AV_MAXA) return e->fail(SACTD3_EINVAL, "action_values_device: more than 32 action dimensions");
+  USE_DEVICE(e);
+  const int a = e->a, N = candidates;
+  const FieldRow rows[9] = {
+      {io->actions, io->actions_ld, a, "actions"}, {io->eps, io->eps_ld, N * a, "eps"}, {io->summary, io->summary_ld, SACTD3_AV_SUMMARY, "summary"},
+      {io->best_index, 1, 1, "best_index"}, {io->best_action, io->best_action_ld, a, "best_action"}, {io->cand, 1, 1, "cand"},
+      {io->cand_q, 1, 1, "cand_q"}, {io->cand_logp, 1, 1, "cand_logp"}, {io->eps_out, 1, 1, "eps_out"}};
+  RCCHK(device_ptr_check(e, obs, "action_values_device", "obs"));
+  RCCHK(field_rows_check(e, rows, 9, false, "action_values_device", nullptr));
+  const bool policy = source == SACTD3_AV_POLICY, sac = !e->cfg.prefer_td3_over_sac;
+  const int head_ld = (sac ? 2 : 1) * a;
+  RCCHK(first_use_alloc(e, &e->av_x, (size_t)AV_CHUNK * e->ldo));
+  RCCHK(first_use_alloc(e, &e->av_words, (size_t)AV_WORDS));
+  RCCHK(first_use_alloc(e, &e->av_bad, (size_t)AV_MAXWG));
+  if (policy) {
+    RCCHK(first_use_alloc(e, &e->av_z1, (size_t)AV_CHUNK * HID));
+    RCCHK(first_use_alloc(e, &e->av_z2, (size_t)AV_CHUNK * HID));
+    RCCHK(first_use_alloc(e, &e->av_head, (size_t)AV_CHUNK * head_ld));
+  }
+  AvArgs g{};
+  for (int k = 0; k < 2; ++k) {
+    const NetLayout& L = e->Lc;
+    DormantNet& Nn = g.net[k];
+    Nn.P = (which == SACTD3_Q_TARGET ? e->Tc : e->Pc) + (size_t)k * L.size;
+    Nn.id = k + 1; Nn.K = L.K; Nn.ld1 = L.ld1; Nn.nh = L.nh;
+    Nn.W1 = L.W1; Nn.b1 = L.b1; Nn.g1 = L.g1; Nn.be1 = L.be1; Nn.W2 = L.W2; Nn.b2 = L.b2; Nn.g2 = L.g2; Nn.be2 = L.be2; Nn.Wh = L.Wh;
+    g.bh[k] = L.bh;
+  }
+  g.ob = e->o; g.a = a; g.ln = e->cfg.layer_norm; g.source = source; g.sac = sac ? 1 : 0; g.soft = (sac && policy) ? 1 : 0;
+  g.sigma = sigma; g.tau = tau; g.x = e->av_x; g.ldo = e->ldo; g.head = policy ? e->av_head : nullptr; g.head_ld = head_ld;
+  g.scale = e->scale; g.bias = e->bias; g.lo = e->min_ac; g.hi = e->max_ac; g.log_alpha = e->la; g.seed = &e->ctl->seed;
+  g.words = e->av_words; g.bad = e->av_bad;
+  g.actions_ld = (long)io->actions_ld; g.eps_ld = (long)io->eps_ld; g.summary_ld = (long)io->summary_ld; g.best_action_ld = (long)io->best_action_ld;
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  EnqCtx x{e, e->stream};
+  TrunkTicks tk{nullptr, nullptr, nullptr, nullptr, 0.f};
+  tk.pin_shape = true;
+  RCCHK(src_order_begin(e, caller, flags));
+  for (int64_t r0 = 0; r0 < n; r0 += AV_CHUNK) {
+    const int m = (int)std::min<int64_t>(AV_CHUNK, n - r0);
+    RCCHK(launch_obs_pack(x, obs + r0 * obs_ld, obs_ld, e->av_x, m));
+    if (policy) {
+      const TrunkGrp ga{e->av_x, e->Pa, e->av_z1, e->av_z2, nullptr, nullptr, nullptr};
+      RCCHK(enqueue_trunk(x, e->ldo, e->o, m, e->La, 0, 1, 1, &ga, tk));
+      PiHead h{};      // no draw, no given action: the head kernel reads neither PiCtl nor DevCtl
+      h.z2 = e->av_z2; h.P = e->Pa; h.L = e->La; h.n = m; h.a = a; h.ln = e->cfg.layer_norm; h.sac = sac ? 1 : 0;
+      h.scale = e->scale; h.bias = e->bias; h.ctl = e->ctl;
+      if (sac) { h.mean = e->av_head; h.mean_ld = head_ld; h.log_std = e->av_head + a; h.log_std_ld = head_ld; }
+      else { h.mode = e->av_head; h.mode_ld = head_ld; }
+      RCCHK(launch_pi_head(x, h));
+    }
+    auto at = [&](auto* p, int64_t ld) { return p ? p + r0 * ld : p; };
+    g.m = m; g.row0 = (long)r0; g.tick = (!io->eps && r0 + m >= n) ? 1 : 0;
+    g.actions = at(io->actions, io->actions_ld); g.eps = at(io->eps, io->eps_ld); g.summary = at(io->summary, io->summary_ld);
+    g.best_index = at(io->best_index, 1); g.best_action = at(io->best_action, io->best_action_ld);
+    g.cand = at(io->cand, (int64_t)N * a); g.cand_q = at(io->cand_q, (int64_t)N * 2); g.cand_logp = at(io->cand_logp, N);
+    g.eps_out = at(io->eps_out, (int64_t)N * a);
+    const hipError_t he = action_values_launch(g, N, e->stream);
+    if (he != hipSuccess) return e->fail(SACTD3_EHIP, "action_values_device: k_action_values / k_av_finish", he);
+  }
+  RCCHK(src_order_end(e, caller, flags));
+  ++e->av_host[0]; e->av_host[1] += n;
+  if (!io->eps) ++e->av_host[2];
+  return 0;
+}
+
+int sactd3_action_values_stats(sactd3_engine* e, int64_t out[8]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int w[AV_WORDS] = {};
+  if (e->av_words) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(w, e->av_words, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = e->av_host[0]; out[1] = e->av_host[1]; out[2] = e->av_host[2]; out[3] = w[AV_W_NONFINITE]; out[4] = w[AV_W_CTR];
   return 0;
 }
 

@@ -299,6 +299,65 @@ class Engine:
             st[name] = {k: (int(sm[8 * i + j]) if whole else float(sm[8 * i + j])) for i, k in enumerate(_lib.FEATURE_RANK_NETS)}
         return st
 
+    # -- the critics at one state under N sampled candidate actions (include/sactd3_action_values.h)
+    def action_values(self, obs, actions=None, candidates: int = 16, source: str = "policy", target: bool = False, sigma: float = 0.2,
+                      tau: float = 1.0, eps=None, dump: bool = False) -> Dict[str, object]:
+        """sactd3_action_values_device: per row of `obs` (a float32 CUDA tensor [n, ob_dim] of this device) `candidates` (16, 32 or 64)
+        actions -- `source` "policy": the online actor's samples (TD3: its mode + sigma-scaled noise, clamped), "uniform": uniform in
+        the action bounds -- scored by the online or (`target`) the target critics, the state's share of the first layer computed
+        once per row.  `actions` [n, ac_dim]: the data actions, for `q_data`.  `eps` [n, candidates * ac_dim] (or [n, candidates,
+        ac_dim]): injected draws; None: a Philox stream of the call's own.  Eager launches on the engine's stream, ordered on the GPU
+        against torch's current stream; no host wait; training and acting do not see the call.
+        -> {"summary": [n, 8] (the columns _lib.AV_SUMMARY names) and each column under its name as a view, "best_index": [n] int32,
+            "best_action": [n, ac_dim] [, with `dump`: "cand" [n, N, ac_dim], "cand_q" [n, N, 2], "cand_logp" [n, N], "eps" [n, N, ac_dim]]}"""
+        import torch
+        o, a, N = self.cfg.ob_dim, self.cfg.ac_dim, int(candidates)
+        dev = torch.device("cuda", self.cfg.device_id)
+        if source not in ("policy", "uniform"):
+            raise ValueError(f"action_values: `source` is 'policy' or 'uniform', got {source!r}")
+
+        def rows(x, width, name, n=None):
+            if not (isinstance(x, torch.Tensor) and x.device == dev and x.dtype == torch.float32):
+                raise TypeError(f"action_values: `{name}` is a float32 tensor in the memory of the engine's device")
+            x = x.reshape(x.shape[0], -1) if x.dim() > 1 else x.reshape(1, -1)
+            if x.shape[1] != width or (n is not None and x.shape[0] != n):
+                raise ValueError(f"action_values: `{name}` has shape {tuple(x.shape)}, expected [{'n' if n is None else n}, {width}]")
+            return x if x.stride(1) == 1 and x.stride(0) >= width else x.contiguous()
+
+        obs = rows(obs, o, "obs")
+        n = obs.shape[0]
+        io, keep = _lib.CActionValuesIO(), [obs]
+        for name, x, width in (("actions", actions, a), ("eps", eps, N * a)):
+            if x is not None:
+                x = rows(x, width, name, n)
+                keep.append(x)
+                setattr(io, name, x.data_ptr())
+                setattr(io, name + "_ld", x.stride(0))
+        out = {"summary": torch.empty(n, 8, dtype=torch.float32, device=dev), "best_index": torch.empty(n, dtype=torch.int32, device=dev),
+               "best_action": torch.empty(n, a, dtype=torch.float32, device=dev)}
+        if dump:
+            out.update(cand=torch.empty(n, N, a, dtype=torch.float32, device=dev), cand_q=torch.empty(n, N, 2, dtype=torch.float32, device=dev),
+                       cand_logp=torch.empty(n, N, dtype=torch.float32, device=dev), eps=torch.empty(n, N, a, dtype=torch.float32, device=dev))
+        for field, key in (("summary", "summary"), ("best_index", "best_index"), ("best_action", "best_action"), ("cand", "cand"),
+                           ("cand_q", "cand_q"), ("cand_logp", "cand_logp"), ("eps_out", "eps")):
+            if key in out:
+                setattr(io, field, out[key].data_ptr())
+        io.summary_ld, io.best_action_ld = 8, a
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+        self._ck(self.lib.sactd3_action_values_device(self._h, _vp(obs.data_ptr()), obs.stride(0), n, N,
+                                                      _lib.AV_POLICY if source == "policy" else _lib.AV_UNIFORM,
+                                                      _lib.Q_TARGET if target else _lib.Q_ONLINE, float(sigma), float(tau), C.byref(io),
+                                                      _vp(stream), _lib.SRC_ORDERED))
+        del keep
+        out.update({name: out["summary"][:, i] for i, name in enumerate(_lib.AV_SUMMARY)})
+        return out
+
+    def action_values_stats(self) -> Dict[str, int]:
+        """counters of action_values (sactd3_action_values_stats; waits for the engine's stream: the last two live on the device)"""
+        out = (C.c_int64 * 8)()
+        self._ck(self.lib.sactd3_action_values_stats(self._h, out))
+        return dict(zip(("calls", "rows", "native_draw_calls", "rows_nonfinite", "av_ctr"), (int(x) for x in out)))
+
     # -- coloured exploration noise (include/sactd3_noise.h)
     def colored_noise(self, beta: float, length: int, sequences: int, chunk: int = 0, epoch: int = 0, out=None):
         """sactd3_colored_noise_device: chunk `chunk` of `sequences` independent 1/f^beta Gaussian sequences (beta in [0, 2]: 0 white,

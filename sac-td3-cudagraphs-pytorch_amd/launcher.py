@@ -378,6 +378,12 @@ def mode_flags(args, plan) -> dict:
             flags["feature_rank_delta"] = float(args.feature_rank_delta)
     elif getattr(args, "feature_rank_delta", None) is not None:
         raise ValueError("--feature_rank_delta needs --feature_rank ROWS: it is the delta of that call's srank")
+    if getattr(args, "ood_gap", None) is not None:          # (the same)
+        flags["ood_gap"] = int(args.ood_gap)
+        if getattr(args, "ood_candidates", None) is not None:
+            flags["ood_candidates"] = int(args.ood_candidates)
+    elif getattr(args, "ood_candidates", None) is not None:
+        raise ValueError("--ood_candidates needs --ood_gap ROWS: it is the number of sampled actions of that call")
     if getattr(args, "init", "torch") != "torch":           # (the same)
         flags["init"] = args.init
     if getattr(args, "eval_one_launch", False) or getattr(args, "q_bias", 0):      # (the same: keys only when a flag was given; every job
@@ -394,7 +400,7 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
                    device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False,
                    reset_every=None, reset_what=None, init: str = "torch", num_updates=None, collected_rollout: bool = False,
                    dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None,
-                   feature_rank=None, feature_rank_delta=None) -> dict:
+                   feature_rank=None, feature_rank_delta=None, ood_gap=None, ood_candidates=None) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
@@ -413,6 +419,8 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     and `redo_every` (--redo_every N: ReDo recycling on that scan): asked of loop.redo_rule; the keys are in the result only when the
     flags were given.  `feature_rank` [, `feature_rank_delta`] (--feature_rank ROWS [--feature_rank_delta D]: the effective rank of the
     last hidden layer at every evaluation, loop.train feature_rank=...): asked of loop.feature_rank_rule, the key the same way.
+    `ood_gap` [, `ood_candidates`] (--ood_gap ROWS [--ood_candidates N]: the critics under sampled actions at every evaluation,
+    loop.train ood_gap=...): asked of loop.ood_gap_rule, the key the same way.
     `exploration_beta` [, `exploration_len`] (--exploration_beta B [--exploration_len L]: coloured exploration noise in the collected
     segments, loop.train exploration_beta=...): asked of loop.exploration_rule with the job's segment_len; the keys are in the result
     only when --exploration_beta was given."""
@@ -439,15 +447,15 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
         update["reset_every"], update["reset_what"] = int(reset_every), tuple(reset_what if reset_what is not None else loop.RESET_ALL)
     loop.update_plan(cfg, sampler=None, **update, **(dict(num_updates=int(num_updates)) if num_updates is not None else {}))
     rollout = dict(collected_rollout=True) if collected_rollout else {}
-    watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates, feature_rank, feature_rank_delta)
+    watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates, feature_rank, feature_rank_delta, ood_gap, ood_candidates)
     return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout, **noise, **watch)
 
 
 def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_every=None, num_updates=None, feature_rank=None,
-                     feature_rank_delta=None) -> dict:
-    """--dormant ROWS [--dormant_tau T] [--redo_every N] [--feature_rank ROWS [--feature_rank_delta D]] as the keywords loop.train and
-    loop.train_offline take, asked of loop.redo_rule and loop.feature_rank_rule (ValueError for what they would refuse); {} without
-    the flags"""
+                     feature_rank_delta=None, ood_gap=None, ood_candidates=None) -> dict:
+    """--dormant ROWS [--dormant_tau T] [--redo_every N] [--feature_rank ROWS [--feature_rank_delta D]] [--ood_gap ROWS
+    [--ood_candidates N]] as the keywords loop.train and loop.train_offline take, asked of loop.redo_rule, loop.feature_rank_rule and
+    loop.ood_gap_rule (ValueError for what they would refuse); {} without the flags"""
     kw = {}
     if dormant is not None:
         kw["dormant"] = dict(rows=int(dormant), **(dict(tau=float(dormant_tau)) if dormant_tau is not None else {}))
@@ -459,6 +467,11 @@ def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_ever
         loop.feature_rank_rule(kw["feature_rank"])
     elif feature_rank_delta is not None:
         raise ValueError("feature_rank_delta needs feature_rank ROWS: it is the delta of that call's srank")
+    if ood_gap is not None:
+        kw["ood_gap"] = dict(rows=int(ood_gap), **(dict(candidates=int(ood_candidates)) if ood_candidates is not None else {}))
+        loop.ood_gap_rule(kw["ood_gap"])
+    elif ood_candidates is not None:
+        raise ValueError("ood_candidates needs ood_gap ROWS: it is the number of sampled actions of that call")
     return kw
 
 
@@ -468,7 +481,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
             native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, init: str = "torch",
             reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, collected_rollout: bool = False,
             dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None,
-            feature_rank=None, feature_rank_delta=None, **over):
+            feature_rank=None, feature_rank_delta=None, ood_gap=None, ood_candidates=None, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -490,7 +503,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     one_launch=True); `q_bias` = N > 0: N further evaluation envs, and at every evaluation the normalised Q-bias of the current policy on
     fresh episodes of them (loop.train q_bias=dict(env=, seed=)); both need what eval_plan states.
     `feature_rank` [, `feature_rank_delta`]: the effective rank of the last hidden layer over that many ring rows at every evaluation
-    (loop.train / loop.train_offline feature_rank=...)."""
+    (loop.train / loop.train_offline feature_rank=...).  `ood_gap` [, `ood_candidates`]: the critics at that many ring rows under sampled
+    actions at every evaluation (loop.train / loop.train_offline ood_gap=...)."""
     import json
     import time
     from pathlib import Path
@@ -531,7 +545,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     offline = offline_dataset is not None and prior_fraction is None
     watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every,
                              int(num_updates if num_updates is not None else cfg.num_timesteps) if offline else None,
-                             feature_rank, feature_rank_delta)
+                             feature_rank, feature_rank_delta, ood_gap, ood_candidates)
     run_dir = Path(out_dir) / f"{env_id}__{algo}__seed{seed:02d}"
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
@@ -599,7 +613,7 @@ def _worker_main(args, plan, flags) -> int:
             if args.collected_rollout:           # (the same)
                 out["collected_rollout"] = True
             for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias", "dormant", "dormant_tau", "redo_every",
-                      "exploration_beta", "exploration_len", "feature_rank", "feature_rank_delta"):      # (the same)
+                      "exploration_beta", "exploration_len", "feature_rank", "feature_rank_delta", "ood_gap", "ood_candidates"):      # (the same)
                 if k in flags:
                     out[k] = flags[k]
         else:
@@ -688,6 +702,10 @@ def main(argv=None) -> int:
                     help="at every evaluation: the effective rank of the online nets' last hidden layer over ROWS ring rows (at most 4096), "
                          "on the device (loop.train feature_rank=...; vitals/srank_actor, vitals/srank_critics, vitals/erank_*)")
     ap.add_argument("--feature_rank_delta", type=float, default=None, metavar="D", help="with --feature_rank: the delta of srank (default 0.01)")
+    ap.add_argument("--ood_gap", type=int, default=None, metavar="ROWS",
+                    help="at every evaluation: the critics at ROWS ring rows under sampled actions, on the device (loop.train ood_gap=...; "
+                         "vitals/ood_gap_policy, vitals/ood_gap_uniform, vitals/value_sampled)")
+    ap.add_argument("--ood_candidates", type=int, default=None, metavar="N", help="with --ood_gap: sampled actions per row, 16, 32 or 64 (default 16)")
     ap.add_argument("--redo_every", type=int, default=None, metavar="N",
                     help="with --dormant: ReDo -- every N critic updates, scan and re-initialise the dormant units (excludes --reset_every)")
     ap.add_argument("--reset_what", default=None, metavar="actor,critics,alpha",

@@ -543,6 +543,38 @@ def feature_rank_rule(feature_rank):
         raise ValueError("feature_rank: delta must lie in (0, 1)")
 
 
+class OodGap:
+    """`ood_gap=dict(rows=, candidates= [, seed=])` of train / train_offline: at every evaluation point `agent.ood_gap` -- what the
+    critics think of actions the data does not contain, over `rows` ring rows drawn with a generator of its own: one policy-sampled and
+    one uniform Agent.action_values call.  -> vitals/ood_gap_policy, vitals/ood_gap_uniform (the mean of max_a Q(s, a) - Q(s, a_data))
+    and vitals/value_sampled (the mean sampled soft value).  The calls have device memory and a draw counter of their own: the run's bits
+    are those of the run without them."""
+    KEYS = ("vitals/ood_gap_policy", "vitals/ood_gap_uniform", "vitals/value_sampled")
+
+    def __init__(self, agent, spec):
+        self.agent, self.kw, self.last = agent, dict(spec), {}
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        got = self.agent.ood_gap(**self.kw)
+        self.last = {f"vitals/{k}": got[k] for k in ("ood_gap_policy", "ood_gap_uniform", "value_sampled")}
+        if tabular is not None:
+            for k, v in self.last.items():
+                tabular.record(k, v)
+        return self.last
+
+
+def ood_gap_rule(ood_gap):
+    """the keyword rule of `ood_gap`, asked before an agent is touched (ValueError)"""
+    if ood_gap is None:
+        return
+    if not isinstance(ood_gap, dict) or set(ood_gap) - {"rows", "candidates", "seed"} or "rows" not in ood_gap:
+        raise ValueError("ood_gap must be a dict with `rows` [, `candidates`, `seed`]")
+    if not 1 <= int(ood_gap["rows"]) <= 65536:
+        raise ValueError("ood_gap: 1 <= rows <= 65536")
+    if int(ood_gap.get("candidates", 16)) not in (16, 32, 64):
+        raise ValueError("ood_gap: candidates is 16, 32 or 64")
+
+
 def redo_rule(dormant, redo_every, redo_what=REDO_ALL, reset_every=None, num_updates: Optional[int] = None):
     """The keyword rules of `dormant` / `redo_every` / `redo_what`, asked before an agent is touched (ValueError), and the rule itself:
     None without `redo_every`, else redo(agent, before, first=None) -> the update count now, with the contract of update_plan's reset:
@@ -595,11 +627,12 @@ class _Vitals:
         return {k: v for part in self.parts for k, v in part.last.items()}
 
 
-def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None):
-    """PolicyStats, QBias, Dormant and / or FeatureRank as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
+def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None, ood_gap=None):
+    """PolicyStats, QBias, Dormant, FeatureRank and / or OodGap as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
     parts = ([PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0))] if policy_stats else []) + ([QBias(agent, q_bias)] if q_bias is not None else [])
     parts += [Dormant(agent, dormant)] if dormant is not None else []
     parts += [FeatureRank(agent, feature_rank)] if feature_rank is not None else []
+    parts += [OodGap(agent, ood_gap)] if ood_gap is not None else []
     return None if not parts else parts[0] if len(parts) == 1 else _Vitals(parts)
 
 
@@ -773,7 +806,7 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, q_bias: Optional[Dict[str, Any]] = None,
           collected_rollout: bool = False, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
           redo_what: Any = REDO_ALL, exploration_beta: Optional[float] = None, exploration_len: int = 256,
-          feature_rank: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+          feature_rank: Optional[Dict[str, Any]] = None, ood_gap: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -846,10 +879,14 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     between two loop bodies, on the schedule of `reset_every`.
     `feature_rank=dict(rows=, delta= [, seed=])` (default None: off, and no call is made): at every evaluation point the effective rank
     of the online nets' last hidden layer over `rows` ring rows (FeatureRank) -- vitals/srank_actor, vitals/srank_critics,
-    vitals/erank_actor, vitals/erank_critics, vitals/feature_rank_converged; the run itself is bit for bit the run without it."""
+    vitals/erank_actor, vitals/erank_critics, vitals/feature_rank_converged; the run itself is bit for bit the run without it.
+    `ood_gap=dict(rows=, candidates= [, seed=])` (default None: off, and no call is made): at every evaluation point the critics at
+    `rows` ring rows under `candidates` policy-sampled and as many uniform actions (OodGap) -- vitals/ood_gap_policy,
+    vitals/ood_gap_uniform, vitals/value_sampled; the run itself is bit for bit the run without it."""
     redo = redo_rule(dormant, redo_every, redo_what, reset_every)         # (refusals before the agent is touched)
     feature_rank_rule(feature_rank)
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank)
+    ood_gap_rule(ood_gap)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap)
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
                        prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
                        reset_every=reset_every, reset_what=reset_what)
@@ -950,7 +987,8 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
                   on_eval: Optional[Callable[[Any, int], None]] = None, eval_every_updates: Optional[int] = None,
                   policy_stats: int = 0, reset_every: Optional[int] = None, reset_what: Any = RESET_ALL,
                   q_bias: Optional[Dict[str, Any]] = None, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
-                  redo_what: Any = REDO_ALL, feature_rank: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+                  redo_what: Any = REDO_ALL, feature_rank: Optional[Dict[str, Any]] = None,
+                  ood_gap: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
@@ -960,17 +998,18 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
     only), `q_bias=dict(env=, seed=)` as for train.  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
     is refused (update_plan's table).  `dormant` / `redo_every` / `redo_what` as for train: the runs also end where a redo is due.
-    `feature_rank` as for train.  Returns the last metrics."""
+    `feature_rank` and `ood_gap` as for train.  Returns the last metrics."""
     num_updates = int(num_updates)
     if num_updates < 0:
         raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
     redo = redo_rule(dormant, redo_every, redo_what, reset_every, num_updates)      # (before the agent is touched)
     feature_rank_rule(feature_rank)
+    ood_gap_rule(ood_gap)
     reset = None
     if reset_every is not None:                                           # (before the agent is touched)
         reset = update_plan(cfg, fused=True, sampler=None, prioritized=None, n_step=1, one_launch=False, prior_fraction=None,
                             updates_per_step=1, reset_every=reset_every, reset_what=reset_what, num_updates=num_updates).reset
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap)
     resets = reset is not None                                            # vitals/resets belongs to a run that resets
     if redo is not None:
         reset, reset_every = redo, redo_every                             # the same schedule: the runs end where a redo is due
