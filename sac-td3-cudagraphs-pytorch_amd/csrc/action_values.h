@@ -1,8 +1,10 @@
 // What engine.hip knows of the candidate-scoring call (action_values.hip, action_values_kernels.h; include/sactd3_action_values.h is its
-// C ABI): the argument struct and one host launcher.  The two critics are described as DormantNet (dormant.h), as the feature-rank call
-// describes its nets; nothing else crosses between the translation units.
+// C ABI): the argument struct and one host launcher.  The two critics are described as NetView (net_view.h), as the scan and the
+// feature-rank call describe their nets; nothing else crosses between the translation units.
 #pragma once
-#include "dormant.h"
+#include <hip/hip_runtime.h>
+
+#include "net_view.h"
 
 #define AV_ROWS 64         // candidate rows of one workgroup: four 16-row MFMA tiles = 64 / N observations with their N candidates
 #define AV_DROWS 16        // ... and one more tile whose rows 0 .. 64 / N - 1 are the observations' data actions (worked only when given)
@@ -16,7 +18,7 @@
 enum { AV_W_CTR = 0 /* av_ctr: numbers the native draws */, AV_W_NONFINITE = 1 /* rows with a non-finite input so far */, AV_WORDS = 4 };
 
 struct AvArgs {
-  DormantNet net[2]; int bh[2];             // the two critics of `which` (P: their parameter block; M, V unused) and their head bias offsets
+  NetView net[2]; int bh[2];             // the two critics of `which` (P: their parameter block; M, V unused) and their head bias offsets
   int ob, a, ln;                            // widths; sactd3_config::layer_norm
   int m; long row0;                         // observation rows of this launch; the row of the call its row 0 is (numbers the native draws)
   int source, sac, soft;                    // SACTD3_AV_*; the actor is SAC's; column 4 is the soft value (SAC with POLICY)

@@ -43,14 +43,14 @@ template <int KIND>
 __global__ __launch_bounds__(256) void k_collect_rollout(EnvDev d, CollectLaunch p) {
   constexpr int OB = EnvTask<KIND>::OB, AC = EnvTask<KIND>::AC, NS = EnvTask<KIND>::NS;
   static_assert(OB <= 8 && AC <= 2, "Os rows are 8 floats, the head holds at most 4 outputs");
-  __shared__ __attribute__((aligned(16))) float Os[EV_TILE * 8];
-  __shared__ __attribute__((aligned(16))) float H1[EV_TILE * EV_AS];
-  __shared__ __attribute__((aligned(16))) float H2[EV_TILE * EV_AS];
-  __shared__ __attribute__((aligned(16))) float Ln[4 * EV_HID];
-  __shared__ __attribute__((aligned(16))) float Whs[4 * EV_HID];
+  __shared__ __attribute__((aligned(16))) float Os[HT_TILE * 8];
+  __shared__ __attribute__((aligned(16))) float H1[HT_TILE * HT_AS];
+  __shared__ __attribute__((aligned(16))) float H2[HT_TILE * HT_AS];
+  __shared__ __attribute__((aligned(16))) float Ln[4 * HT_HID];
+  __shared__ __attribute__((aligned(16))) float Whs[4 * HT_HID];
   const int tid = threadIdx.x, row = tid >> 4, sub = tid & 15;
   const size_t n = (size_t)d.n;
-  const int i = blockIdx.x * EV_TILE + row;
+  const int i = blockIdx.x * HT_TILE + row;
   const bool lead = sub == 0;
   const bool owner = lead && i < d.n;
   const EvalActor& A = p.A;

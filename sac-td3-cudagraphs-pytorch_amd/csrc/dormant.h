@@ -4,22 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define DM_HID 256
+#include "net_view.h"
+
 #define DM_NETS 3          // 0: the actor; 1, 2: the critics.  Pair (net, layer) = 2 net + layer, layer 0 / 1 = the two hidden layers
 #define DM_PAIRS 6
-#define DM_TILE 16         // ring rows per tile: the 16 rows of v_mfma_f32_16x16x4f32
 #define DM_MAXG 128        // workgroups per net: min(ceil(n / 16), 128) are launched, G = min(ceil(V / 16), 128) of them work (V: the valid rows)
 #define DM_MAXN 65536      // rows of one scan
 // device words of the feature (DormantState::words)
 enum { DM_W_COUNT = 0 /* .. 5: dormant neurons per pair, last scan */, DM_W_VALID = 6, DM_W_REFUSED = 7, DM_W_RECYCLED = 8, DM_W_LEFT_ZERO = 9, DM_WORDS = 16 };
 
-// One online net as the kernels read it: P its parameter block, the NetLayout offsets, K the input width (the record's leading K floats).
-// M / V: Adam's exp_avg / exp_avg_sq of the same block (the recycler alone writes them).  id: 0 the actor, 1 / 2 the critics.
-struct DormantNet {
-  float *P, *M, *V;
-  int id, K, ld1, nh;
-  int W1, b1, g1, be1, W2, b2, g2, be2, Wh;
-};
 // The feature's own device memory, made at its first scan.
 struct DormantState {
   float* part;       // [DM_NETS][2][DM_MAXG][256] column sums of a workgroup's tiles
@@ -34,17 +27,17 @@ struct DormantScanArgs {
   const long long* idx; long idx_ld; int n;     // slot of row r: idx[r * idx_ld]
   int ln;                                       // sactd3_config::layer_norm
   float tau;
-  DormantNet net[DM_NETS]; int nnets;           // the scanned nets, in ascending id
+  NetView net[DM_NETS]; int nnets;           // the scanned nets, in ascending id
   DormantState st;
   float* out;                                   // NULL, or the caller's [DM_PAIRS][256]: rows of the scanned nets are written
 };
 struct RedoArgs {
-  DormantNet net[DM_NETS]; int nnets;
+  NetView net[DM_NETS]; int nnets;
   DormantState st;
   unsigned long long seed; unsigned epoch;      // the Philox key and the first counter word
 };
 
-static inline int dormant_groups(int n) { const int t = (n + DM_TILE - 1) / DM_TILE; return t < DM_MAXG ? t : DM_MAXG; }
+static inline int dormant_groups(int n) { const int t = (n + HT_TILE - 1) / HT_TILE; return t < DM_MAXG ? t : DM_MAXG; }
 
 // hipErrorInvalidValue, and nothing is launched, where an argument is outside what the kernels' address arithmetic holds; otherwise
 // hipGetLastError() behind the launch.  dormant_scan_launch issues k_dormant_compact, k_dormant_scan and k_dormant_finish.

@@ -4208,18 +4208,23 @@ int sactd3_init_stats(sactd3_engine* e, int64_t out[4]) {
 }
 
 // ---- the dormant-neuron scan and ReDo recycling (include/sactd3_dormant.h)
-// the online nets `what` names (a sum of SACTD3_DORMANT_*), in ascending id, as the kernels of dormant.hip read them
-static int dormant_nets(sactd3_engine* e, uint32_t what, DormantNet* out) {
+// net `id` (0: the actor; 1, 2: the critics) of layout L as the kernels of dormant.hip and action_values.hip read it; P / M / V: its own
+// parameter block and, where a kernel writes parameters, Adam's two moments of it (else NULL)
+static NetView net_view(float* P, float* M, float* V, const NetLayout& L, int id) {
+  NetView N{};
+  N.P = P; N.M = M; N.V = V;
+  N.id = id; N.K = L.K; N.ld1 = L.ld1; N.nh = L.nh;
+  N.W1 = L.W1; N.b1 = L.b1; N.g1 = L.g1; N.be1 = L.be1; N.W2 = L.W2; N.b2 = L.b2; N.g2 = L.g2; N.be2 = L.be2; N.Wh = L.Wh;
+  return N;
+}
+// the online nets `what` names (a sum of SACTD3_DORMANT_*), in ascending id
+static int dormant_nets(sactd3_engine* e, uint32_t what, NetView* out) {
   int n = 0;
-  for (int id = 0; id < DM_NETS; ++id) {      // 0: the actor; 1, 2: the critics
+  for (int id = 0; id < DM_NETS; ++id) {
     if (!(what & (id ? SACTD3_DORMANT_CRITICS : SACTD3_DORMANT_ACTOR))) continue;
     const NetLayout& L = id ? e->Lc : e->La;
     const size_t off = id ? (size_t)(id - 1) * L.size : 0;
-    DormantNet N{};
-    N.P = (id ? e->Pc : e->Pa) + off; N.M = (id ? e->Mc : e->Ma) + off; N.V = (id ? e->Vc : e->Va) + off;
-    N.id = id; N.K = L.K; N.ld1 = L.ld1; N.nh = L.nh;
-    N.W1 = L.W1; N.b1 = L.b1; N.g1 = L.g1; N.be1 = L.be1; N.W2 = L.W2; N.b2 = L.b2; N.g2 = L.g2; N.be2 = L.be2; N.Wh = L.Wh;
-    out[n++] = N;
+    out[n++] = net_view((id ? e->Pc : e->Pa) + off, (id ? e->Mc : e->Ma) + off, (id ? e->Vc : e->Va) + off, L, id);
   }
   return n;
 }
@@ -4245,11 +4250,11 @@ int sactd3_dormant_scan_device(sactd3_engine* e, const int64_t* idx, int64_t idx
   RCCHK(device_ptr_check(e, idx, "dormant_scan_device", "idx"));
   if (scores) RCCHK(device_ptr_check(e, scores, "dormant_scan_device", "scores"));
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "dormant_scan_device: buffer is empty");
-  RCCHK(first_use_alloc(e, &e->dm.part, (size_t)DM_NETS * 2 * DM_MAXG * DM_HID, false));      // (never zeroed: a scan writes every partial it reads)
+  RCCHK(first_use_alloc(e, &e->dm.part, (size_t)DM_NETS * 2 * DM_MAXG * HT_HID, false));      // (never zeroed: a scan writes every partial it reads)
   RCCHK(first_use_alloc(e, &e->dm.slots, (size_t)DM_MAXN, false));                            // (the same: k_dormant_compact writes what the scan reads)
   RCCHK(first_use_alloc(e, &e->dm.rows, 4, false));
-  RCCHK(first_use_alloc(e, &e->dm.scores, (size_t)DM_PAIRS * DM_HID));
-  RCCHK(first_use_alloc(e, &e->dm.mask, (size_t)DM_PAIRS * DM_HID));
+  RCCHK(first_use_alloc(e, &e->dm.scores, (size_t)DM_PAIRS * HT_HID));
+  RCCHK(first_use_alloc(e, &e->dm.mask, (size_t)DM_PAIRS * HT_HID));
   RCCHK(first_use_alloc(e, &e->dm.words, (size_t)DM_WORDS));
   DormantScanArgs g{};
   g.ring = e->ring; g.rec_f = e->rec_f; g.len = (int)e->rb_len;
@@ -4321,10 +4326,10 @@ int sactd3_feature_rank_device(sactd3_engine* e, const int64_t* idx, int64_t idx
   if (spectrum) RCCHK(device_ptr_check(e, spectrum, "feature_rank_device", "spectrum"));
   if (gram) RCCHK(device_ptr_check(e, gram, "feature_rank_device", "gram"));
   if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "feature_rank_device: buffer is empty");
-  RCCHK(first_use_alloc(e, &e->fr.part, (size_t)DM_NETS * FR_MAXG * DM_HID * DM_HID, false));      // (never zeroed: a call writes every partial it reads)
+  RCCHK(first_use_alloc(e, &e->fr.part, (size_t)DM_NETS * FR_MAXG * HT_HID * HT_HID, false));      // (never zeroed: a call writes every partial it reads)
   RCCHK(first_use_alloc(e, &e->fr.slots, (size_t)FR_MAXN, false));                                 // (the same: k_dormant_compact writes what k_frank_gram reads)
   RCCHK(first_use_alloc(e, &e->fr.rows, 4, false));
-  RCCHK(first_use_alloc(e, &e->fr.lambda, (size_t)DM_NETS * DM_HID));
+  RCCHK(first_use_alloc(e, &e->fr.lambda, (size_t)DM_NETS * HT_HID));
   RCCHK(first_use_alloc(e, &e->fr.summary, (size_t)DM_NETS * FR_SUMMARY));
   RCCHK(first_use_alloc(e, &e->fr.words, (size_t)FR_WORDS));
   FrankArgs g{};
@@ -4403,12 +4408,8 @@ int sactd3_action_values_device(sactd3_engine* e, const float* obs, int64_t obs_
   }
   AvArgs g{};
   for (int k = 0; k < 2; ++k) {
-    const NetLayout& L = e->Lc;
-    DormantNet& Nn = g.net[k];
-    Nn.P = (which == SACTD3_Q_TARGET ? e->Tc : e->Pc) + (size_t)k * L.size;
-    Nn.id = k + 1; Nn.K = L.K; Nn.ld1 = L.ld1; Nn.nh = L.nh;
-    Nn.W1 = L.W1; Nn.b1 = L.b1; Nn.g1 = L.g1; Nn.be1 = L.be1; Nn.W2 = L.W2; Nn.b2 = L.b2; Nn.g2 = L.g2; Nn.be2 = L.be2; Nn.Wh = L.Wh;
-    g.bh[k] = L.bh;
+    g.net[k] = net_view((which == SACTD3_Q_TARGET ? e->Tc : e->Pc) + (size_t)k * e->Lc.size, nullptr, nullptr, e->Lc, k + 1);
+    g.bh[k] = e->Lc.bh;
   }
   g.ob = e->o; g.a = a; g.ln = e->cfg.layer_norm; g.source = source; g.sac = sac ? 1 : 0; g.soft = (sac && policy) ? 1 : 0;
   g.sigma = sigma; g.tau = tau; g.x = e->av_x; g.ldo = e->ldo; g.head = policy ? e->av_head : nullptr; g.head_ld = head_ld;

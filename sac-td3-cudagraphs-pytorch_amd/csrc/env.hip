@@ -574,7 +574,7 @@ static int collect_segment(sactd3_rollout* r, int mode, int steps, float* record
     p.lo = e->info.min_ac; p.span = e->info.max_ac - e->info.min_ac; p.env_seed = e->cfg.seed;
     p.L = EnvRec{r->lay.record_len, r->lay.next_off, r->lay.next_width};
     p.records = records; p.eps = eps; p.obs = b.obs; p.obs_ld = (long long)b.obs_ld; p.actions = b.actions; p.actions_ld = (long long)b.actions_ld;
-    const dim3 grid((unsigned)((e->d.n + EV_TILE - 1) / EV_TILE));
+    const dim3 grid((unsigned)((e->d.n + HT_TILE - 1) / HT_TILE));
     if (colored) {
       const int L = r->nz_len;
       const int64_t S = (int64_t)r->n * e->info.ac_dim, c0 = r->nz_pos / L, c1 = (r->nz_pos + steps - 1) / L;
@@ -714,7 +714,7 @@ ENV_API int sactd3_eval_rollout(sactd3_engine* eng, sactd3_env* e, const sactd3_
     p.A = A; p.T = T; p.horizon = info.horizon; p.sample = sample ? 1 : 0; p.soft = cfg->soft; p.gamma = cfg->gamma; p.env_seed = e->cfg.seed;
     p.obs = out->obs; p.actions = out->actions; p.eps = out->eps; p.reward = out->reward; p.logp = out->logp; p.rtg = out->rtg; p.live = out->live;
     p.ep_return = out->ep_return; p.ep_length = out->ep_length; p.ep_terminated = out->ep_terminated; p.g0 = out->g0; p.alpha = out->alpha;
-    const dim3 grid((unsigned)((e->d.n + EV_TILE - 1) / EV_TILE));
+    const dim3 grid((unsigned)((e->d.n + HT_TILE - 1) / HT_TILE));
     with_kind(e->cfg.kind, [&](auto K) { hipLaunchKernelGGL(k_eval_rollout<decltype(K)::value>, grid, dim3(256), 0, A.stream, e->d, p); });
     if (const hipError_t he = hipGetLastError()) return engine_eval_fail(eng, SACTD3_EHIP, (std::string("eval_rollout: k_eval_rollout: ") + hipGetErrorString(he)).c_str());
     return engine_eval_close(eng, sample ? 1 : 0, rows, caller_stream, flags);

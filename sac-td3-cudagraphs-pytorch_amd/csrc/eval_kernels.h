@@ -6,10 +6,7 @@
 // Per step, between block barriers (LDS only: Os the tile's observations, H1 / H2 the two hidden layers' rows):
 //   1. owners: o_t = env_observe(state) -> Os and the `obs` record
 //   2. layer 1: thread c holds row c of W1 (K <= 8) and b1[c] in registers for the whole call: z1[r][c] for the 16 rows -> H1
-//   3. thread (row = t >> 4, sub = t & 15) holds columns 4 sub + 64 q .. + 3: LayerNorm (two-pass, eps inside the root) + ReLU in place
-//   4. layer 2 (K = 256) on the matrix cores: wave w owns columns 64 w .. 64 w + 63 as four 16 x 16 tiles, the tile's 16 envs are the 16
-//      rows of v_mfma_f32_16x16x4f32; W2 (256 KB, above the LDS) is read through the cache every step, 16 bytes per lane and request,
-//      64 contiguous bytes per weight row and request; + b2 -> H2
+//   3. - 4. hidden_tile.h: LayerNorm + ReLU in place, layer 2 on the matrix cores (W2 through the cache every step), + b2 -> H2
 //   5. LayerNorm + ReLU of H2 in registers, the head (nh <= 4 outputs from LDS-resident Wh) as 16-lane sums -> the owner
 //   6. owners: the action (policy_kernels.h: `mode`, or `sample` / `sample_logp` with the draw of this feature's stream), the records, then
 //      env_step_body<KIND> with it -- cleaning, physics, flags, books, auto-reset: used, not restated
@@ -19,11 +16,6 @@
 #include "eval_rollout.h"
 
 #define SACTD3_STREAM_EVAL 0x800u   // third counter word of every draw of this feature; words (eval_ctr, t, 0x800, element >> 2)
-#define EV_HID 256
-#define EV_AS 260                   // LDS row stride of the 256-wide rows: 16-byte aligned, odd in float4 units
-#define EV_TILE 16
-
-typedef float ev_f32x4 __attribute__((ext_vector_type(4)));
 
 struct EvalLaunch {
   EvalActor A;
@@ -38,40 +30,7 @@ struct EvalLaunch {
 
 #pragma clang fp contract(off)
 
-// sum over the 16 lanes that share a row; every lane gets it
-__device__ __forceinline__ float ev_sum16(float v) {
-  v += __shfl_xor(v, 1, 16);
-  v += __shfl_xor(v, 2, 16);
-  v += __shfl_xor(v, 4, 16);
-  v += __shfl_xor(v, 8, 16);
-  return v;
-}
-
-// LayerNorm (ln == 0: identity) + ReLU of the 16 columns a thread holds of its row; g / be: the affine pair in LDS
-__device__ __forceinline__ void ev_ln_relu(float4 v[4], const float* g, const float* be, int sub, int ln) {
-  if (ln) {
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) s += (v[q].x + v[q].y) + (v[q].z + v[q].w);
-    const float mean = ev_sum16(s) * (1.0f / EV_HID);
-    float ss = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      v[q].x -= mean; v[q].y -= mean; v[q].z -= mean; v[q].w -= mean;
-      ss += ((v[q].x * v[q].x) + (v[q].y * v[q].y)) + ((v[q].z * v[q].z) + (v[q].w * v[q].w));
-    }
-    const float var = ev_sum16(ss) * (1.0f / EV_HID);
-    const float rstd = 1.0f / sqrtf(var + 1e-5f);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 gg = *(const float4*)(g + 4 * sub + 64 * q), bb = *(const float4*)(be + 4 * sub + 64 * q);
-      v[q].x = (v[q].x * rstd) * gg.x + bb.x; v[q].y = (v[q].y * rstd) * gg.y + bb.y;
-      v[q].z = (v[q].z * rstd) * gg.z + bb.z; v[q].w = (v[q].w * rstd) * gg.w + bb.w;
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { v[q].x = fmaxf(v[q].x, 0.f); v[q].y = fmaxf(v[q].y, 0.f); v[q].z = fmaxf(v[q].z, 0.f); v[q].w = fmaxf(v[q].w, 0.f); }
-}
+#include "hidden_tile.h"      // (inside the region where contraction is off)
 
 // What thread `tid` of a tile's workgroup keeps of the online actor for a whole call: row tid of W1 (K = OB <= 8) and b1[tid]; b2 of the four
 // layer-2 columns it receives; where W2 lies.
@@ -91,9 +50,9 @@ __device__ __forceinline__ void ev_actor_load(const EvalActor& A, int nh, int ti
   R.b1c = P[A.b1 + tid];
 #pragma unroll
   for (int tt = 0; tt < 4; ++tt) R.b2c[tt] = P[A.b2 + wave * 64 + tt * 16 + r];
-  Ln[tid] = P[A.g1 + tid]; Ln[EV_HID + tid] = P[A.be1 + tid]; Ln[2 * EV_HID + tid] = P[A.g2 + tid]; Ln[3 * EV_HID + tid] = P[A.be2 + tid];
+  Ln[tid] = P[A.g1 + tid]; Ln[HT_HID + tid] = P[A.be1 + tid]; Ln[2 * HT_HID + tid] = P[A.g2 + tid]; Ln[3 * HT_HID + tid] = P[A.be2 + tid];
 #pragma unroll
-  for (int m = 0; m < 4; ++m) Whs[m * EV_HID + tid] = m < nh ? P[A.Wh + min(m, nh - 1) * EV_HID + tid] : 0.f;
+  for (int m = 0; m < 4; ++m) Whs[m * HT_HID + tid] = m < nh ? P[A.Wh + min(m, nh - 1) * HT_HID + tid] : 0.f;
   R.W2 = P + A.W2;
 }
 
@@ -107,66 +66,34 @@ __device__ __forceinline__ void ev_actor_pass(const EvActorRegs<OB>& R, const fl
   const int lane = tid & 63, wave = tid >> 6, r = lane & 15, kq = lane >> 4;
   // 2. layer 1, column tid
 #pragma unroll
-  for (int rr = 0; rr < EV_TILE; ++rr) {
+  for (int rr = 0; rr < HT_TILE; ++rr) {
     const float4 oa = *(const float4*)(Os + rr * 8), ob = *(const float4*)(Os + rr * 8 + 4);
     const float o[8] = {oa.x, oa.y, oa.z, oa.w, ob.x, ob.y, ob.z, ob.w};
     float z = R.b1c;
 #pragma unroll
     for (int k = 0; k < OB; ++k) z += o[k] * R.w1[k];
-    H1[rr * EV_AS + tid] = z;
+    H1[rr * HT_AS + tid] = z;
   }
   __syncthreads();
-  // 3. LayerNorm + ReLU of H1, in place (a thread rewrites the 16 elements it read)
-  {
-    float4 v[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = *(const float4*)(H1 + row * EV_AS + 4 * sub + 64 * q);
-    ev_ln_relu(v, Ln, Ln + EV_HID, sub, ln);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) *(float4*)(H1 + row * EV_AS + 4 * sub + 64 * q) = v[q];
-  }
+  // 3. LayerNorm + ReLU of H1, in place; 4. layer 2: H2[16][64 wave .. + 63] = H1 W2^T + b2
+  ht_ln_relu_lds(H1 + row * HT_AS, Ln, Ln + HT_HID, sub, ln);
   __syncthreads();
-  // 4. layer 2: H2[16][64 wave .. + 63] = H1 W2^T + b2.  Lane (r, kq) feeds A[r][k] and B[k][col r] with k = 16 c + 4 kq + m for the
-  //    m-th of four MFMAs (any order of k serves both operands alike); it receives D[4 kq + m'][col r].
-  {
-    float4 av[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) av[c] = *(const float4*)(H1 + r * EV_AS + 16 * c + 4 * kq);
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const int col = wave * 64 + tt * 16 + r;
-      const float4* __restrict__ wrow = (const float4*)(R.W2 + (size_t)col * EV_HID + 4 * kq);
-      float4 wv[16];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) wv[c] = wrow[4 * c];
-      ev_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].x, wv[c].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].y, wv[c].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].z, wv[c].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c].w, wv[c].w, acc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int m = 0; m < 4; ++m) H2[(4 * kq + m) * EV_AS + col] = acc[m] + R.b2c[tt];
-    }
-  }
+  ht_layer2(H1, R.W2, R.b2c, H2, wave, r, kq);
   __syncthreads();
   // 5. LayerNorm + ReLU of H2 in registers, the head
   {
     float4 v[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = *(const float4*)(H2 + row * EV_AS + 4 * sub + 64 * q);
-    ev_ln_relu(v, Ln + 2 * EV_HID, Ln + 3 * EV_HID, sub, ln);
+    ht_load_row(H2 + row * HT_AS, sub, v);
+    ht_ln_relu(v, Ln + 2 * HT_HID, Ln + 3 * HT_HID, sub, ln);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       float part = 0.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float4 w = *(const float4*)(Whs + m * EV_HID + 4 * sub + 64 * q);
+        const float4 w = *(const float4*)(Whs + m * HT_HID + 4 * sub + 64 * q);
         part += ((v[q].x * w.x) + (v[q].y * w.y)) + ((v[q].z * w.z) + (v[q].w * w.w));
       }
-      u[m] = ev_sum16(part) + bh[m];
+      u[m] = ht_sum16(part) + bh[m];
     }
   }
 }
@@ -175,14 +102,14 @@ template <int KIND>
 __global__ __launch_bounds__(256) void k_eval_rollout(EnvDev d, EvalLaunch p) {
   constexpr int OB = EnvTask<KIND>::OB, AC = EnvTask<KIND>::AC, NS = EnvTask<KIND>::NS;
   static_assert(OB <= 8 && AC <= 2, "Os rows are 8 floats, the head holds at most 4 outputs");
-  __shared__ __attribute__((aligned(16))) float Os[EV_TILE * 8];
-  __shared__ __attribute__((aligned(16))) float H1[EV_TILE * EV_AS];
-  __shared__ __attribute__((aligned(16))) float H2[EV_TILE * EV_AS];
-  __shared__ __attribute__((aligned(16))) float Ln[4 * EV_HID];      // g1, be1, g2, be2
-  __shared__ __attribute__((aligned(16))) float Whs[4 * EV_HID];     // the head's rows, zero beyond nh
+  __shared__ __attribute__((aligned(16))) float Os[HT_TILE * 8];
+  __shared__ __attribute__((aligned(16))) float H1[HT_TILE * HT_AS];
+  __shared__ __attribute__((aligned(16))) float H2[HT_TILE * HT_AS];
+  __shared__ __attribute__((aligned(16))) float Ln[4 * HT_HID];      // g1, be1, g2, be2
+  __shared__ __attribute__((aligned(16))) float Whs[4 * HT_HID];     // the head's rows, zero beyond nh
   const int tid = threadIdx.x, row = tid >> 4, sub = tid & 15;
   const size_t n = (size_t)d.n;
-  const int i = blockIdx.x * EV_TILE + row;
+  const int i = blockIdx.x * HT_TILE + row;
   const bool lead = sub == 0;                // the thread that writes row `row` of Os
   const bool owner = lead && i < d.n;        // ... and owns env i
   const EvalActor& A = p.A;
@@ -243,8 +170,7 @@ __global__ __launch_bounds__(256) void k_eval_rollout(EnvDev d, EvalLaunch p) {
         if (A.sac && p.sample) {
           const uint32_t el = (uint32_t)i * (uint32_t)AC + (uint32_t)j;
           const float4 z = philox_box_muller4(philox4x32_10(ctr, (uint32_t)t, SACTD3_STREAM_EVAL, el >> 2, (uint32_t)key, (uint32_t)(key >> 32)));
-          const uint32_t k = el & 3u;
-          e[j] = k == 0u ? z.x : (k == 1u ? z.y : (k == 2u ? z.z : z.w));
+          e[j] = ht_pick(z, el & 3u);
           const float u0 = u[j], u1 = u[AC + j];
           const float tt = tanhf(u1);
           const float log_std = -5.0f + 3.5f * (tt + 1.0f);

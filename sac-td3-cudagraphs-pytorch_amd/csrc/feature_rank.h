@@ -1,8 +1,9 @@
 // What engine.hip knows of the feature-rank call (feature_rank_kernels.h, compiled in dormant.hip -- the plasticity-diagnostics unit;
-// include/sactd3_feature_rank.h is its C ABI): the argument struct and the host launcher.  The call shares k_dormant_compact, the dm_*
-// helpers and DormantNet with the dormant scan and no device memory: a scan's state and this call's never meet.
+// include/sactd3_feature_rank.h is its C ABI): the argument struct and the host launcher.  The call shares k_dormant_compact, the
+// hidden tile (hidden_tile.h) and NetView (net_view.h) with the dormant scan and no device memory: a scan's state and this call's never meet.
 #pragma once
 #include "dormant.h"
+#include "net_view.h"
 
 #define FR_MAXG 16         // workgroups per (net, column half): min(ceil(n / 16), 16) are launched, G = min(ceil(V / 16), 16) of them work
 #define FR_MAXN 4096       // rows of one call
@@ -28,7 +29,7 @@ struct FrankArgs {
   float* gram;               // NULL, or the caller's [DM_NETS][256][256]: the same
 };
 
-static inline int frank_groups(int n) { const int t = (n + DM_TILE - 1) / DM_TILE; return t < FR_MAXG ? t : FR_MAXG; }
+static inline int frank_groups(int n) { const int t = (n + HT_TILE - 1) / HT_TILE; return t < FR_MAXG ? t : FR_MAXG; }
 
 // hipErrorInvalidValue, and nothing is launched, where an argument is outside what the kernels' address arithmetic holds; otherwise
 // hipGetLastError() behind the launch.  Issues k_dormant_compact, k_frank_gram and k_frank_eig.

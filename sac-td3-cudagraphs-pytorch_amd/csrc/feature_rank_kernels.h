@@ -1,12 +1,11 @@
 // Device code of the feature-rank call (include/sactd3_feature_rank.h): the spectrum of M = H2^T H2 / V, H2 the second hidden layer of
 // an online net over V valid ring rows.  Included by dormant.hip behind dormant_kernels.h: k_dormant_compact (unchanged, on this call's
-// own slot list) and the dm_* helpers are used as they are, under that file's pragmas (contraction off, no packed fp32 instructions).
+// own slot list), dm_pick and hidden_tile.h are used as they are, under dormant.hip's pragmas (contraction off, no packed fp32 instructions).
 //
 // k_frank_gram: grid (min(ceil(n / 16), 16), nets, 2), 256 threads, of which G = min(ceil(V / 16), 16) per (net, half) work.  Workgroup
-//   (g, net, half) walks the 16-row tiles g, g + G, ... of the checked list.  Per tile: the scan's gather, layer 1 over any K, LayerNorm +
-//   ReLU and layer 2 (k_dormant_scan's steps 1 - 3 and 5, operation for operation), rows behind V stored as zeros; then H2^T H2 of the
-//   tile for the Gram columns 128 half .. + 127 onto accumulators that stay in registers for the whole call: wave w owns the Gram rows
-//   64 w .. + 63 as 4 x 8 tiles of 16 x 16 (128 accumulator registers per lane), each fed by four v_mfma_f32_16x16x4f32 whose k are the
+//   (g, net, half) walks the 16-row tiles g, g + G, ... of the checked list.  Per tile: the ring front end, LayerNorm + ReLU and layer 2
+//   of hidden_tile.h as k_dormant_scan calls them, rows behind V stored as zeros; then H2^T H2 of the tile for the Gram columns
+//   128 half .. + 127 onto accumulators that stay in registers for the whole call: wave w owns the Gram rows 64 w .. + 63 as 4 x 8 tiles of 16 x 16 (128 accumulator registers per lane), each fed by four v_mfma_f32_16x16x4f32 whose k are the
 //   tile's four row quads -- lane (r, kq) reads H2[4 kq + m][i0 + r] and H2[4 kq + m][j0 + r] for the m-th of them; with the row stride of
 //   260 floats the 64 lanes of such a read touch 64 different LDS banks.  Both halves recompute the forward pass (about two thirds of a
 //   tile's MACs): splitting the Gram's columns, not the rows, keeps the accumulators out of memory until the end and the partials at
@@ -31,112 +30,53 @@
 #pragma once
 #include "feature_rank.h"
 
-#define FR_TRI (DM_HID * (DM_HID + 1) / 2)      // floats of the packed upper triangle
-#define FR_PAIRS (DM_HID / 2)
+#define FR_TRI (HT_HID * (HT_HID + 1) / 2)      // floats of the packed upper triangle
+#define FR_PAIRS (HT_HID / 2)
 #define FR_BLOCKS (FR_PAIRS * (FR_PAIRS + 1) / 2)
 #define FR_THREADS 1024
 #define FR_PER ((FR_BLOCKS + FR_THREADS - 1) / FR_THREADS)
 #define FR_U 5.9604644775390625e-8f             // 2^-24, the unit roundoff of fp32
 #define FR_TINY 9.31322574615478515625e-10f     // 2^-30: an off-diagonal element at or below this share of the trace is left alone
 
-// (contraction is off for the whole unit: dormant_kernels.h; its no-packed-fp32 attribute ends with that file, so it is asked for again)
-#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
-
 __global__ __launch_bounds__(256) void k_frank_gram(FrankArgs q) {
-  __shared__ __attribute__((aligned(16))) float Xs[DM_TILE * DM_XS];
-  __shared__ __attribute__((aligned(16))) float H1[DM_TILE * DM_AS];
-  __shared__ __attribute__((aligned(16))) float H2[DM_TILE * DM_AS];
-  __shared__ __attribute__((aligned(16))) float Ln[4 * DM_HID];      // g1, be1, g2, be2
+  __shared__ __attribute__((aligned(16))) float Xs[HT_TILE * HT_XS];
+  __shared__ __attribute__((aligned(16))) float H1[HT_TILE * HT_AS];
+  __shared__ __attribute__((aligned(16))) float H2[HT_TILE * HT_AS];
+  __shared__ __attribute__((aligned(16))) float Ln[4 * HT_HID];      // g1, be1, g2, be2
   const DormantScanArgs& p = q.scan;
   const int tid = threadIdx.x, row = tid >> 4, sub = tid & 15;
   const int lane = tid & 63, wave = tid >> 6, r = lane & 15, kq = lane >> 4, half = blockIdx.z;
   if ((int)blockIdx.y >= p.nnets || half > 1) return;
-  const DormantNet N = dm_pick(p.net, blockIdx.y);
-  const float* __restrict__ P = N.P;
+  const NetView N = dm_pick(p.net, blockIdx.y);
   const int V = min(max(p.st.rows[0], 0), p.n);      // k_dormant_compact's, one launch ahead on this stream
-  const int g = blockIdx.x, ntiles = (V + DM_TILE - 1) / DM_TILE, G = min(ntiles, FR_MAXG);
+  const int g = blockIdx.x, ntiles = (V + HT_TILE - 1) / HT_TILE, G = min(ntiles, FR_MAXG);
   if (g >= G) return;                                // (block-uniform; k_frank_eig reads the partials of [0, G) alone)
 
-  Ln[tid] = P[N.g1 + tid]; Ln[DM_HID + tid] = P[N.be1 + tid]; Ln[2 * DM_HID + tid] = P[N.g2 + tid]; Ln[3 * DM_HID + tid] = P[N.be2 + tid];
   float b1c[4], b2c[4];
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt) { b1c[tt] = P[N.b1 + wave * 64 + tt * 16 + r]; b2c[tt] = P[N.b2 + wave * 64 + tt * 16 + r]; }
-  const int Kp = N.ld1;
-  dm_f32x4 gr[4][8];      // Gram rows 64 wave + 16 ti + 4 kq + m, column 128 half + 16 tj + r
+  ht_ring_load(N, tid, Ln, b1c, b2c);
+  ht_f32x4 gr[4][8];      // Gram rows 64 wave + 16 ti + 4 kq + m, column 128 half + 16 tj + r
 #pragma unroll
   for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
-    for (int tj = 0; tj < 8; ++tj) gr[ti][tj] = dm_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int tj = 0; tj < 8; ++tj) gr[ti][tj] = ht_f32x4{0.f, 0.f, 0.f, 0.f};
 
   for (int tile = g; tile < ntiles; tile += G) {
-    // 1. this thread's row: its slot, checked
-    const int ri = tile * DM_TILE + row;
-    const int slot = ri < V ? p.st.slots[ri] : 0;
-    const bool ok = ri < V && slot >= 0 && slot < p.len;
-    const float* __restrict__ rec = p.ring + (size_t)(ok ? slot : 0) * (size_t)p.rec_f;
-    // 2. layer 1 over the K chunks
-    dm_f32x4 acc[4];
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) acc[tt] = dm_f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < N.K; k0 += DM_KC) {
-      {
-        const int kk = k0 + 4 * sub;
-        const float4 x = *(const float4*)(rec + min(kk, Kp - 4));      // (always inside the record; selected below)
-        *(float4*)(Xs + row * DM_XS + 4 * sub) = dm_below(x, kk, N.K, ok);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < DM_KC / 16; ++c) {
-        if (k0 + 16 * c < N.K) {
-          const int kb = k0 + 16 * c + 4 * kq;
-          const float4 av = *(const float4*)(Xs + r * DM_XS + 16 * c + 4 * kq);
-          float4 wv[4];
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) wv[tt] = *(const float4*)(P + N.W1 + (size_t)(wave * 64 + tt * 16 + r) * (size_t)N.ld1 + min(kb, Kp - 4));
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) acc[tt] = dm_mfma4(av, dm_below(wv[tt], kb, N.K, true), acc[tt]);
-        }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) H1[(4 * kq + m) * DM_AS + wave * 64 + tt * 16 + r] = acc[tt][m] + b1c[tt];
+    const bool ok = ht_ring_layer1(N, p.ring, p.rec_f, p.len, p.st.slots, V, tile, Xs, H1, b1c, tid);
     __syncthreads();
-    // 3. LayerNorm + ReLU of H1, in place
-    dm_ln_relu(H1 + row * DM_AS, Ln, Ln + DM_HID, sub, p.ln);
+    ht_ln_relu_lds(H1 + row * HT_AS, Ln, Ln + HT_HID, sub, p.ln);
     __syncthreads();
-    // 5. layer 2: H2[16][64 wave .. + 63] = H1 W2^T + b2
-    {
-      float4 av[16];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) av[c] = *(const float4*)(H1 + r * DM_AS + 16 * c + 4 * kq);
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) {
-        const int col = wave * 64 + tt * 16 + r;
-        const float4* __restrict__ wrow = (const float4*)(P + N.W2 + (size_t)col * DM_HID + 4 * kq);
-        float4 wv[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) wv[c] = wrow[4 * c];
-        dm_f32x4 a2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 16; ++c) a2 = dm_mfma4(av[c], wv[c], a2);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) H2[(4 * kq + m) * DM_AS + col] = a2[m] + b2c[tt];
-      }
-    }
+    ht_layer2(H1, N.P + N.W2, b2c, H2, wave, r, kq);
     __syncthreads();
-    dm_ln_relu(H2 + row * DM_AS, Ln + 2 * DM_HID, Ln + 3 * DM_HID, sub, p.ln);
+    ht_ln_relu_lds(H2 + row * HT_AS, Ln + 2 * HT_HID, Ln + 3 * HT_HID, sub, p.ln);
     if (!ok) {      // a row behind V adds nothing to the Gram matrix (the 16 elements this thread has just written)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) *(float4*)(H2 + row * DM_AS + 4 * sub + 64 * c) = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int c = 0; c < 4; ++c) *(float4*)(H2 + row * HT_AS + 4 * sub + 64 * c) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
     // 6. gr += H2^T H2 of this tile: the m-th MFMA of a 16 x 16 tile takes the rows 4 kq + m
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-      const float* __restrict__ h = H2 + (4 * kq + m) * DM_AS + r;
+      const float* __restrict__ h = H2 + (4 * kq + m) * HT_AS + r;
       float a[4], b[8];
 #pragma unroll
       for (int ti = 0; ti < 4; ++ti) a[ti] = h[wave * 64 + ti * 16];
@@ -150,58 +90,58 @@ __global__ __launch_bounds__(256) void k_frank_gram(FrankArgs q) {
     __syncthreads();      // H2 is written again by the next tile
   }
 
-  float* __restrict__ out = q.st.part + ((size_t)N.id * FR_MAXG + g) * (size_t)(DM_HID * DM_HID);
+  float* __restrict__ out = q.st.part + ((size_t)N.id * FR_MAXG + g) * (size_t)(HT_HID * HT_HID);
 #pragma unroll
   for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
     for (int tj = 0; tj < 8; ++tj)
-      *(float4*)(out + (size_t)(half * 128 + tj * 16 + r) * DM_HID + wave * 64 + ti * 16 + 4 * kq) =
+      *(float4*)(out + (size_t)(half * 128 + tj * 16 + r) * HT_HID + wave * 64 + ti * 16 + 4 * kq) =
           make_float4(gr[ti][tj][0], gr[ti][tj][1], gr[ti][tj][2], gr[ti][tj][3]);
 }
 
 // where element (i, j), i <= j, lies in the packed upper triangle
-__device__ __forceinline__ int fr_at(int i, int j) { return ((i * (2 * DM_HID - 1 - i)) >> 1) + j; }
+__device__ __forceinline__ int fr_at(int i, int j) { return ((i * (2 * HT_HID - 1 - i)) >> 1) + j; }
 __device__ __forceinline__ int fr_sym(int x, int y) { return x <= y ? fr_at(x, y) : fr_at(y, x); }
 // pair k of round t of the round-robin order
 __device__ __forceinline__ void fr_pair(int t, int k, int& p, int& q) {
   const int u = t + k, d = t - k;
-  p = k == 0 ? DM_HID - 1 : (u >= DM_HID - 1 ? u - (DM_HID - 1) : u);
-  q = d < 0 ? d + (DM_HID - 1) : d;
+  p = k == 0 ? HT_HID - 1 : (u >= HT_HID - 1 ? u - (HT_HID - 1) : u);
+  q = d < 0 ? d + (HT_HID - 1) : d;
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_frank_eig(FrankArgs q) {
   __shared__ float A[FR_TRI];
   __shared__ __attribute__((aligned(16))) float4 rot[FR_PAIRS];      // (s, tau, t, -) of the round's pairs; the tail's scratch behind the solver
-  __shared__ float lam[DM_HID], sor[DM_HID];
-  __shared__ float lo[DM_HID];      // what the updates of diagonal element i rounded away: lambda_i = A_ii + lo_i
+  __shared__ float lam[HT_HID], sor[HT_HID];
+  __shared__ float lo[HT_HID];      // what the updates of diagonal element i rounded away: lambda_i = A_ii + lo_i
   __shared__ int rotated[FR_SWEEPS];
   __shared__ float scal[2];
   const int tid = threadIdx.x;
   if ((int)blockIdx.x >= q.scan.nnets) return;
   const int id = dm_pick(q.scan.net, blockIdx.x).id;
   const int V = min(max(q.scan.st.rows[0], 0), q.scan.n), R = q.scan.st.rows[1];
-  const int tiles = (V + DM_TILE - 1) / DM_TILE, G = tiles < FR_MAXG ? tiles : FR_MAXG;
+  const int tiles = (V + HT_TILE - 1) / HT_TILE, G = tiles < FR_MAXG ? tiles : FR_MAXG;
 
   // ---- load
   {
-    const float* __restrict__ part = q.st.part + (size_t)id * FR_MAXG * (size_t)(DM_HID * DM_HID);
-    float* __restrict__ gram = q.gram ? q.gram + (size_t)id * (DM_HID * DM_HID) : nullptr;
-    for (int e = tid; e < DM_HID * DM_HID; e += FR_THREADS) {
-      const int i = e >> 8, j = e & (DM_HID - 1);
+    const float* __restrict__ part = q.st.part + (size_t)id * FR_MAXG * (size_t)(HT_HID * HT_HID);
+    float* __restrict__ gram = q.gram ? q.gram + (size_t)id * (HT_HID * HT_HID) : nullptr;
+    for (int e = tid; e < HT_HID * HT_HID; e += FR_THREADS) {
+      const int i = e >> 8, j = e & (HT_HID - 1);
       if (i > j) continue;
       float s = 0.f;
-      for (int g = 0; g < G; ++g) s += part[(size_t)g * (DM_HID * DM_HID) + e];
+      for (int g = 0; g < G; ++g) s += part[(size_t)g * (HT_HID * HT_HID) + e];
       const float m = V > 0 ? s / (float)V : 0.f;
       A[fr_at(i, j)] = m;
-      if (gram) { gram[i * DM_HID + j] = m; gram[j * DM_HID + i] = m; }
+      if (gram) { gram[i * HT_HID + j] = m; gram[j * HT_HID + i] = m; }
     }
     if (tid < FR_SWEEPS) rotated[tid] = 0;
-    if (tid < DM_HID) lo[tid] = 0.f;
+    if (tid < HT_HID) lo[tid] = 0.f;
   }
   __syncthreads();
-  if (tid < DM_HID) lam[tid] = A[fr_at(tid, tid)];
+  if (tid < HT_HID) lam[tid] = A[fr_at(tid, tid)];
   __syncthreads();
-  for (int w = DM_HID / 2; w >= 1; w >>= 1) {
+  for (int w = HT_HID / 2; w >= 1; w >>= 1) {
     if (tid < w) lam[tid] = lam[tid] + lam[tid + w];
     __syncthreads();
   }
@@ -220,7 +160,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_frank_eig(FrankArgs q) {
   if (V > 0) {      // (block-uniform)
     converged = 0;
     for (int sweep = 0; sweep < FR_SWEEPS && !converged; ++sweep) {
-      for (int t = 0; t < DM_HID - 1; ++t) {
+      for (int t = 0; t < HT_HID - 1; ++t) {
         if (tid < FR_PAIRS) {
           int pp, qq;
           fr_pair(t, tid, pp, qq);
@@ -283,34 +223,34 @@ __global__ __launch_bounds__(FR_THREADS) void k_frank_eig(FrankArgs q) {
   __syncthreads();      // (with V == 0 no barrier of the solver stands between the trace's read of lam[0] and the stores below)
   float* __restrict__ sig = lam;              // sigma_i in place of the clamped diagonal, once that is sorted
   float* __restrict__ ent = (float*)rot;      // p_i ln p_i
-  if (tid < DM_HID) lam[tid] = fmaxf(A[fr_at(tid, tid)] + lo[tid], 0.f);
+  if (tid < HT_HID) lam[tid] = fmaxf(A[fr_at(tid, tid)] + lo[tid], 0.f);
   __syncthreads();
-  if (tid < DM_HID) {
+  if (tid < HT_HID) {
     const float v = lam[tid];
     int before = 0;
-    for (int j = 0; j < DM_HID; ++j) {
+    for (int j = 0; j < HT_HID; ++j) {
       const float w = lam[j];
       before += (w > v || (w == v && j < tid)) ? 1 : 0;
     }
-    sor[before & (DM_HID - 1)] = v;      // (a permutation of 0 .. 255 for any values that compare; the mask keeps a NaN's store inside)
+    sor[before & (HT_HID - 1)] = v;      // (a permutation of 0 .. 255 for any values that compare; the mask keeps a NaN's store inside)
   }
   __syncthreads();
   const float lam1 = sor[0];
-  if (tid < DM_HID) {
+  if (tid < HT_HID) {
     const float v = sor[tid];
-    q.st.lambda[id * DM_HID + tid] = v;
-    if (q.spectrum) q.spectrum[id * DM_HID + tid] = v;
+    q.st.lambda[id * HT_HID + tid] = v;
+    if (q.spectrum) q.spectrum[id * HT_HID + tid] = v;
     sig[tid] = (lam1 > 0.f && v > q.floor * lam1) ? sqrtf(v) : 0.f;
   }
   __syncthreads();
   if (tid == 0) {
     float s = 0.f, cs = 0.f, l = 0.f, cl = 0.f;
-    for (int i = 0; i < DM_HID; ++i) { dm_kahan(s, cs, sig[i]); dm_kahan(l, cl, sor[i]); }
+    for (int i = 0; i < HT_HID; ++i) { ht_kahan(s, cs, sig[i]); ht_kahan(l, cl, sor[i]); }
     scal[0] = s; scal[1] = l;
   }
   __syncthreads();
   const float S = scal[0], lsum = scal[1];
-  if (tid < DM_HID) {
+  if (tid < HT_HID) {
     const float pr = S > 0.f ? sig[tid] / S : 0.f;
     ent[tid] = pr > 0.f ? pr * logf(pr) : 0.f;
   }
@@ -319,11 +259,11 @@ __global__ __launch_bounds__(FR_THREADS) void k_frank_eig(FrankArgs q) {
     float h = 0.f, ch = 0.f, run = 0.f, cr = 0.f;
     const float need = (1.0f - q.delta) * S;
     int rank = 0, srank = 0;
-    for (int i = 0; i < DM_HID; ++i) {
-      dm_kahan(h, ch, ent[i]);
+    for (int i = 0; i < HT_HID; ++i) {
+      ht_kahan(h, ch, ent[i]);
       if (sig[i] > 0.f) ++rank;
       if (S > 0.f && srank == 0) {
-        dm_kahan(run, cr, sig[i]);
+        ht_kahan(run, cr, sig[i]);
         if (run >= need) srank = i + 1;
       }
     }
@@ -343,5 +283,3 @@ __global__ __launch_bounds__(FR_THREADS) void k_frank_eig(FrankArgs q) {
     }
   }
 }
-
-#pragma clang attribute pop
