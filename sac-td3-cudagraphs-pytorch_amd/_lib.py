@@ -94,6 +94,10 @@ FEATURE_RANK_SUMMARY = ("trace", "lambda_sum", "rank", "srank", "erank", "stable
 ACTION_VALUES_SYMBOLS = ["sactd3_action_values_device", "sactd3_action_values_stats"]
 AV_POLICY, AV_UNIFORM = 0, 1        # `source` of sactd3_action_values_device (SACTD3_AV_*)
 AV_SUMMARY = ("q_max", "q_mean", "q_lme", "q_std", "soft_value", "q_data", "logp_mean", "finite")   # summary[row][8]
+# every symbol include/sactd3_action_gradient.h declares (tests/test_action_gradient_host.py checks the header against this list)
+ACTION_GRADIENT_SYMBOLS = ["sactd3_action_gradient_device", "sactd3_action_gradient_stats"]
+AG_MAX_STEPS = 16                   # `steps` of sactd3_action_gradient_device at most (SACTD3_AG_MAX_STEPS)
+AG_SUMMARY = ("q_min_start", "q_min_end", "grad_norm_q1", "grad_norm_q2", "grad_cos", "moved", "held_steps", "reserved")   # summary[row][8]
 # every symbol include/sactd3_eval.h declares (tests/test_eval_rollout_host.py checks the header against this list)
 EVAL_SYMBOLS = ["sactd3_eval_rollout", "sactd3_eval_stats"]
 EVAL_GREEDY, EVAL_SAMPLE = 0, 1     # sactd3_eval_config.mode (SACTD3_EVAL_*)
@@ -149,6 +153,13 @@ class CActionValuesIO(C.Structure):
                 ("summary", C.c_void_p), ("summary_ld", C.c_int64), ("best_index", C.c_void_p),
                 ("best_action", C.c_void_p), ("best_action_ld", C.c_int64),
                 ("cand", C.c_void_p), ("cand_q", C.c_void_p), ("cand_logp", C.c_void_p), ("eps_out", C.c_void_p)]
+
+
+class CActionGradientIO(C.Structure):
+    """sactd3_action_gradient_io: device pointers (None = not wanted), the strided ones with their row stride in elements"""
+    _fields_ = [("q_start", C.c_void_p), ("q_start_ld", C.c_int64), ("grad", C.c_void_p), ("grad_obs", C.c_void_p),
+                ("refined", C.c_void_p), ("refined_ld", C.c_int64), ("q_end", C.c_void_p), ("q_end_ld", C.c_int64),
+                ("summary", C.c_void_p), ("summary_ld", C.c_int64)]
 
 
 class CHindsightConfig(C.Structure):
@@ -399,6 +410,13 @@ def load_library():
     }
     assert sorted(action_values_sig) == sorted(ACTION_VALUES_SYMBOLS)
     sig.update(action_values_sig)
+    action_gradient_sig = {
+        "sactd3_action_gradient_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                    C.POINTER(CActionGradientIO), vp, C.c_int]),
+        "sactd3_action_gradient_stats": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(action_gradient_sig) == sorted(ACTION_GRADIENT_SYMBOLS)
+    sig.update(action_gradient_sig)
     eval_sig = {
         "sactd3_eval_rollout": (C.c_int, [vp, vp, C.POINTER(CEvalConfig), C.POINTER(CEvalOut), vp, C.c_int]),
         "sactd3_eval_stats": (C.c_int, [vp, i64p]),

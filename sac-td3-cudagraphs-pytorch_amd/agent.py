@@ -649,6 +649,7 @@ class Agent:
         self._dormant_gen = None    # dormant()'s index generator, made at its first call
         self._feature_rank_gen = None    # feature_rank()'s, the same
         self._ood_gen = None        # ood_gap()'s, the same
+        self._smooth_gen = None     # critic_smoothness()'s, the same
         self.min_ac, self.max_ac = np.asarray(min_ac, np.float32), np.asarray(max_ac, np.float32)
         self.timesteps_so_far = 0
         self.actor_updates_so_far = 0
@@ -789,6 +790,51 @@ class Agent:
         uni = self.action_values(td, candidates=candidates, source="uniform")
         three = torch.stack([(pol["q_max"] - pol["q_data"]).mean(), (uni["q_max"] - uni["q_data"]).mean(), pol["soft_value"].mean()]).tolist()
         return dict(zip(("ood_gap_policy", "ood_gap_uniform", "value_sampled"), three))
+
+    def action_gradient(self, obs, actions, which: str = "online", steps: int = 0, lr: float = 0.0, grad_obs: bool = False,
+                        out: Any = None) -> Dict[str, Any]:
+        """dQ/da of the twin critics at `obs` / `actions` (float32 tensors on the engine's device), with `grad_obs` also dQ/ds, and
+        `steps` steps of projected ascent on min(Q1, Q2) of length `lr` (normalised action units) inside the same kernel
+        (include/sactd3_action_gradient.h; Engine.action_gradient).  -> a dict of tensors on that device: q_start, grad, refined, q_end,
+        summary and its columns [, grad_obs].  No host wait; training and acting do not see it."""
+        return self.engine.action_gradient(_detached(obs), _detached(actions), which=which, steps=steps, lr=lr, grad_obs=grad_obs, out=out)
+
+    def predict_refined(self, obs, steps: int = 4, lr: float = 0.05, out: Any = None):
+        """Act by a few ascent steps on the critics from the policy's own action: `obs` [n, ob_dim] on the engine's device (or a mapping with
+        `observations`) -> policy(obs)["mode"] refined by `steps` steps of length `lr` on min(Q1, Q2), [n, ac_dim] on that device, inside the bounds, no
+        host wait.  `out`: a float32 tensor to copy into."""
+        obs = _detached(obs["observations"] if isinstance(obs, Mapping) else obs)
+        mode = self.policy({"observations": obs})["mode"]
+        best = self.engine.action_gradient(obs, mode, steps=steps, lr=lr)["refined"]
+        if out is None:
+            return best
+        out[: best.shape[0]].copy_(best)
+        return out[: best.shape[0]]
+
+    def critic_smoothness(self, rows: int = 256, steps: int = 4, lr: float = 0.05, seed: Optional[int] = None) -> Dict[str, float]:
+        """How steep the critics are in the action, on `rows` ring rows drawn with a torch generator of this method's own (seeded at
+        its first use; None: the engine's seed): the mean of ||dQ_k/da|| over both critics at the data actions, the mean cosine between
+        the twin critics' action gradients there, and the mean gain of min(Q1, Q2) over `steps` ascent steps of length `lr` from the
+        policy's mode.  Two action_gradient calls; one host wait for the three means.
+        -> {"action_grad_norm", "action_grad_cos", "refine_gain"}"""
+        import torch
+        eng = self.engine
+        dev = torch.device("cuda", eng.cfg.device_id)
+        if self._smooth_gen is None:
+            self._smooth_gen = torch.Generator(device=dev)
+            self._smooth_gen.manual_seed(int(eng.cfg.seed if seed is None else seed))
+        n = len(self.rb) if self.rb is not None else eng.rb_len()
+        if n < 1:
+            raise ValueError("critic_smoothness: the replay ring is empty")
+        index = torch.randint(0, n, (int(rows),), generator=self._smooth_gen, device=dev, dtype=torch.int64)
+        got = self.rb.rows(index)
+        obs = got["observations"]
+        data = self.engine.action_gradient(obs, got["actions"])
+        mode = self.policy({"observations": obs})["mode"]
+        pol = self.engine.action_gradient(obs, mode, steps=steps, lr=lr)
+        three = torch.stack([0.5 * (data["grad_norm_q1"] + data["grad_norm_q2"]).mean(), data["grad_cos"].mean(),
+                             (pol["q_min_end"] - pol["q_min_start"]).mean()]).tolist()
+        return dict(zip(("action_grad_norm", "action_grad_cos", "refine_gain"), three))
 
     def recycle_dormant(self, what=("actor", "critics")) -> int:
         """ReDo: re-initialise the hidden units the last dormant() marked in the nets `what` names and keep everything else

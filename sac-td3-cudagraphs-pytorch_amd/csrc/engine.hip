@@ -48,6 +48,10 @@ __global__ void k_set_int1(int* dst, int v) { if (threadIdx.x == 0 && blockIdx.x
 #include "action_values.h"
 #include "../../include/sactd3_action_values.h"
 static_assert(AV_SRC_POLICY == SACTD3_AV_POLICY && AV_SRC_UNIFORM == SACTD3_AV_UNIFORM, "the kernel's `source` is the C ABI's");
+// ... and the action-gradient call (action_gradient.hip; its C ABI is include/sactd3_action_gradient.h, defined behind the candidate scoring's)
+#include "action_gradient.h"
+#include "../../include/sactd3_action_gradient.h"
+static_assert(AG_SUMMARY == SACTD3_AG_SUMMARY && AG_MAXSTEPS == SACTD3_AG_MAX_STEPS, "the kernel's limits are the C ABI's");
 // ... and the evaluation rollout, whose kernel is compiled with the env kernels (env.hip): host code only here, at the end of this file
 #include "eval_rollout.h"
 // ... and the collected rollout segment, split the same way (collect_rollout.h)
@@ -351,6 +355,11 @@ struct sactd3_engine {
   float *av_x = nullptr, *av_z1 = nullptr, *av_z2 = nullptr, *av_head = nullptr;
   int *av_words = nullptr, *av_bad = nullptr;
   int64_t av_host[3] = {};
+  // Action gradients of the twin critics with in-kernel ascent (sactd3_action_gradient_device; include/sactd3_action_gradient.h; device
+  // code: action_gradient_kernels.h, a translation unit of its own).  ag_words: the non-finite-row counter; ag_bad: the workgroups'
+  // counts of one launch.  Made at the first call and shared with nothing.  ag_host: {calls, rows, ascent steps x rows}.
+  int *ag_words = nullptr, *ag_bad = nullptr;
+  int64_t ag_host[3] = {};
   // Coloured exploration noise (sactd3_colored_noise_device; include/sactd3_noise.h; device code: noise_kernels.h, a translation unit of
   // its own).  nz_tables: the amplitude and twiddle tables of every (beta, length) pair asked for so far, each made at its first use --
   // an engine that never generates holds nothing more than before.
@@ -4459,6 +4468,71 @@ int sactd3_action_values_stats(sactd3_engine* e, int64_t out[8]) {
   }
   for (int i = 0; i < 8; ++i) out[i] = 0;
   out[0] = e->av_host[0]; out[1] = e->av_host[1]; out[2] = e->av_host[2]; out[3] = w[AV_W_NONFINITE]; out[4] = w[AV_W_CTR];
+  return 0;
+}
+
+// ---- action gradients of the twin critics, with in-kernel ascent (include/sactd3_action_gradient.h).  Per chunk of AG_CHUNK rows:
+// k_action_gradient, which reads the caller's rows where they lie (no pack kernel), and k_ag_finish (action_gradient.hip).  Like a scoring
+// call it writes memory of its own and the caller's, nothing else of the engine's: no CHAIN_BREAK, no counter of training, acting or
+// another feature, allowed while an acting call is in flight.
+int sactd3_action_gradient_device(sactd3_engine* e, const float* obs, int64_t obs_ld, const float* actions, int64_t actions_ld,
+                                  int n, int which, int steps, float lr, const sactd3_action_gradient_io* io,
+                                  void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first: a refused call has launched, allocated and counted nothing
+  if (!obs || !actions || !io) return e->fail(SACTD3_EINVAL, "action_gradient_device: null argument");
+  if (!(io->q_start || io->grad || io->grad_obs || io->refined || io->q_end || io->summary))
+    return e->fail(SACTD3_EINVAL, "action_gradient_device: no output is set");
+  RCCHK(qvalues_args(e, "action_gradient_device", n, which));
+  if (steps < 0 || steps > SACTD3_AG_MAX_STEPS) return e->fail(SACTD3_EINVAL, "action_gradient_device: 0 <= steps <= 16 required");
+  if (steps > 0 && (!(lr >= 0.f) || !std::isfinite(lr))) return e->fail(SACTD3_EINVAL, "action_gradient_device: lr must be finite and >= 0");
+  if (flags & ~SACTD3_SRC_ORDERED) return e->fail(SACTD3_EINVAL, "action_gradient_device: unknown flag");
+  if (e->a > AG_MAXA) return e->fail(SACTD3_EINVAL, "action_gradient_device: more than 32 action dimensions");
+  USE_DEVICE(e);
+  const int a = e->a, o = e->o;
+  const FieldRow in[2] = {{obs, obs_ld, o, "obs"}, {actions, actions_ld, a, "actions"}};
+  const FieldRow out[6] = {{io->q_start, io->q_start_ld, 2, "q_start"}, {io->grad, 1, 1, "grad"}, {io->grad_obs, 1, 1, "grad_obs"},
+                           {io->refined, io->refined_ld, a, "refined"}, {io->q_end, io->q_end_ld, 2, "q_end"},
+                           {io->summary, io->summary_ld, SACTD3_AG_SUMMARY, "summary"}};
+  RCCHK(field_rows_check(e, in, 2, true, "action_gradient_device", nullptr));
+  RCCHK(field_rows_check(e, out, 6, false, "action_gradient_device", nullptr));
+  RCCHK(first_use_alloc(e, &e->ag_words, (size_t)AG_WORDS));
+  RCCHK(first_use_alloc(e, &e->ag_bad, (size_t)AG_MAXWG));
+  AgArgs g{};
+  for (int k = 0; k < 2; ++k) {
+    g.net[k] = net_view((which == SACTD3_Q_TARGET ? e->Tc : e->Pc) + (size_t)k * e->Lc.size, nullptr, nullptr, e->Lc, k + 1);
+    g.bh[k] = e->Lc.bh;
+  }
+  g.ob = o; g.a = a; g.ln = e->cfg.layer_norm; g.n = (long)n; g.steps = steps; g.lr = steps > 0 ? lr : 0.f;
+  g.scale = e->scale; g.lo = e->min_ac; g.hi = e->max_ac; g.words = e->ag_words; g.bad = e->ag_bad;
+  g.obs_ld = (long)obs_ld; g.actions_ld = (long)actions_ld;
+  g.q_start_ld = (long)io->q_start_ld; g.refined_ld = (long)io->refined_ld; g.q_end_ld = (long)io->q_end_ld; g.summary_ld = (long)io->summary_ld;
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  RCCHK(src_order_begin(e, caller, flags));
+  for (int64_t r0 = 0; r0 < n; r0 += AG_CHUNK) {
+    auto at = [&](auto* p, int64_t ld) { return p ? p + r0 * ld : p; };
+    g.m = (int)std::min<int64_t>(AG_CHUNK, n - r0);
+    g.obs = at(obs, obs_ld); g.actions = at(actions, actions_ld);
+    g.q_start = at(io->q_start, io->q_start_ld); g.grad = at(io->grad, a); g.grad_obs = at(io->grad_obs, o);
+    g.refined = at(io->refined, io->refined_ld); g.q_end = at(io->q_end, io->q_end_ld); g.summary = at(io->summary, io->summary_ld);
+    const hipError_t he = action_gradient_launch(g, e->stream);
+    if (he != hipSuccess) return e->fail(SACTD3_EHIP, "action_gradient_device: k_action_gradient / k_ag_finish", he);
+  }
+  RCCHK(src_order_end(e, caller, flags));
+  ++e->ag_host[0]; e->ag_host[1] += n; e->ag_host[2] += (int64_t)steps * n;
+  return 0;
+}
+
+int sactd3_action_gradient_stats(sactd3_engine* e, int64_t out[8]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int w[AG_WORDS] = {};
+  if (e->ag_words) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(w, e->ag_words, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = e->ag_host[0]; out[1] = e->ag_host[1]; out[2] = w[AG_W_NONFINITE]; out[3] = e->ag_host[2];
   return 0;
 }
 

@@ -358,6 +358,62 @@ class Engine:
         self._ck(self.lib.sactd3_action_values_stats(self._h, out))
         return dict(zip(("calls", "rows", "native_draw_calls", "rows_nonfinite", "av_ctr"), (int(x) for x in out)))
 
+    # -- action gradients of the twin critics, with in-kernel ascent (include/sactd3_action_gradient.h)
+    def action_gradient(self, obs, actions, which: str = "online", steps: int = 0, lr: float = 0.0, grad_obs: bool = False,
+                        out=None) -> Dict[str, object]:
+        """sactd3_action_gradient_device: per row of `obs` [n, ob_dim] and `actions` [n, ac_dim] (float32 CUDA tensors of this device)
+        Q1, Q2 and dQ_k/da of the online or (`which="target"`) the target critics, with `grad_obs` also dQ_k/ds, and `steps` (0 .. 16)
+        steps of projected ascent on min(Q1, Q2), each of length `lr` in normalised action units, inside the one kernel.  Eager
+        launches on the engine's stream, ordered on the GPU against torch's current stream; no host wait; training and acting do not
+        see the call.  `out`: a mapping of preallocated contiguous float32 tensors of that device under the keys below.
+        -> {"q_start": [n, 2], "grad": [2, n, ac_dim], "refined": [n, ac_dim], "q_end": [n, 2], "summary": [n, 8] (the columns
+            _lib.AG_SUMMARY names) and each column under its name as a view [, "grad_obs": [2, n, ob_dim]]}"""
+        import torch
+        o, a = self.cfg.ob_dim, self.cfg.ac_dim
+        dev = torch.device("cuda", self.cfg.device_id)
+        if which not in ("online", "target"):
+            raise ValueError(f"action_gradient: `which` is 'online' or 'target', got {which!r}")
+
+        def rows(x, width, name, n=None):
+            if not (isinstance(x, torch.Tensor) and x.device == dev and x.dtype == torch.float32):
+                raise TypeError(f"action_gradient: `{name}` is a float32 tensor in the memory of the engine's device")
+            x = x.reshape(x.shape[0], -1) if x.dim() > 1 else x.reshape(1, -1)
+            if x.shape[1] != width or (n is not None and x.shape[0] != n):
+                raise ValueError(f"action_gradient: `{name}` has shape {tuple(x.shape)}, expected [{'n' if n is None else n}, {width}]")
+            return x if x.stride(1) == 1 and x.stride(0) >= width else x.contiguous()
+
+        obs = rows(obs, o, "obs")
+        n = obs.shape[0]
+        actions = rows(actions, a, "actions", n)
+        shapes = {"q_start": (n, 2), "grad": (2, n, a), "refined": (n, a), "q_end": (n, 2), "summary": (n, 8)}
+        if grad_obs:
+            shapes["grad_obs"] = (2, n, o)
+        res = {}
+        for key, shape in shapes.items():
+            t = out.get(key) if out else None
+            if t is None:
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            elif not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"action_gradient: out[{key!r}] is a contiguous float32 tensor {shape} of the engine's device")
+            res[key] = t
+        io = _lib.CActionGradientIO()
+        for key, t in res.items():
+            setattr(io, key, t.data_ptr())
+        io.q_start_ld, io.refined_ld, io.q_end_ld, io.summary_ld = 2, a, 2, 8
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+        self._ck(self.lib.sactd3_action_gradient_device(self._h, _vp(obs.data_ptr()), obs.stride(0), _vp(actions.data_ptr()), actions.stride(0),
+                                                        n, _lib.Q_TARGET if which == "target" else _lib.Q_ONLINE, int(steps), float(lr),
+                                                        C.byref(io), _vp(stream), _lib.SRC_ORDERED))
+        del obs, actions
+        res.update({name: res["summary"][:, i] for i, name in enumerate(_lib.AG_SUMMARY)})
+        return res
+
+    def action_gradient_stats(self) -> Dict[str, int]:
+        """counters of action_gradient (sactd3_action_gradient_stats; waits for the engine's stream: rows_nonfinite lives on the device)"""
+        out = (C.c_int64 * 8)()
+        self._ck(self.lib.sactd3_action_gradient_stats(self._h, out))
+        return dict(zip(("calls", "rows", "rows_nonfinite", "ascent_steps"), (int(x) for x in out)))
+
     # -- coloured exploration noise (include/sactd3_noise.h)
     def colored_noise(self, beta: float, length: int, sequences: int, chunk: int = 0, epoch: int = 0, out=None):
         """sactd3_colored_noise_device: chunk `chunk` of `sequences` independent 1/f^beta Gaussian sequences (beta in [0, 2]: 0 white,

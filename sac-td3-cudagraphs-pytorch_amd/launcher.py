@@ -384,6 +384,13 @@ def mode_flags(args, plan) -> dict:
             flags["ood_candidates"] = int(args.ood_candidates)
     elif getattr(args, "ood_candidates", None) is not None:
         raise ValueError("--ood_candidates needs --ood_gap ROWS: it is the number of sampled actions of that call")
+    if getattr(args, "action_grad", None) is not None:      # (the same)
+        flags["action_grad"] = int(args.action_grad)
+        for k, cast in (("action_grad_steps", int), ("action_grad_lr", float)):
+            if getattr(args, k, None) is not None:
+                flags[k] = cast(getattr(args, k))
+    elif getattr(args, "action_grad_steps", None) is not None or getattr(args, "action_grad_lr", None) is not None:
+        raise ValueError("--action_grad_steps / --action_grad_lr need --action_grad ROWS: they are the ascent of that call")
     if getattr(args, "init", "torch") != "torch":           # (the same)
         flags["init"] = args.init
     if getattr(args, "eval_one_launch", False) or getattr(args, "q_bias", 0):      # (the same: keys only when a flag was given; every job
@@ -400,7 +407,8 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
                    device_env: bool, native_rollout: bool, policy_stats: int, hindsight=None, fused_rollout: bool = False,
                    reset_every=None, reset_what=None, init: str = "torch", num_updates=None, collected_rollout: bool = False,
                    dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None,
-                   feature_rank=None, feature_rank_delta=None, ood_gap=None, ood_candidates=None) -> dict:
+                   feature_rank=None, feature_rank_delta=None, ood_gap=None, ood_candidates=None, action_grad=None,
+                   action_grad_steps=None, action_grad_lr=None) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
@@ -421,6 +429,8 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     last hidden layer at every evaluation, loop.train feature_rank=...): asked of loop.feature_rank_rule, the key the same way.
     `ood_gap` [, `ood_candidates`] (--ood_gap ROWS [--ood_candidates N]: the critics under sampled actions at every evaluation,
     loop.train ood_gap=...): asked of loop.ood_gap_rule, the key the same way.
+    `action_grad` [, `action_grad_steps`, `action_grad_lr`] (--action_grad ROWS [--action_grad_steps K] [--action_grad_lr LR]: the
+    critics' action gradients at every evaluation, loop.train action_grad=...): asked of loop.action_grad_rule, the key the same way.
     `exploration_beta` [, `exploration_len`] (--exploration_beta B [--exploration_len L]: coloured exploration noise in the collected
     segments, loop.train exploration_beta=...): asked of loop.exploration_rule with the job's segment_len; the keys are in the result
     only when --exploration_beta was given."""
@@ -447,15 +457,18 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
         update["reset_every"], update["reset_what"] = int(reset_every), tuple(reset_what if reset_what is not None else loop.RESET_ALL)
     loop.update_plan(cfg, sampler=None, **update, **(dict(num_updates=int(num_updates)) if num_updates is not None else {}))
     rollout = dict(collected_rollout=True) if collected_rollout else {}
-    watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates, feature_rank, feature_rank_delta, ood_gap, ood_candidates)
+    watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates, feature_rank, feature_rank_delta, ood_gap, ood_candidates,
+                             action_grad, action_grad_steps, action_grad_lr)
     return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout, **noise, **watch)
 
 
 def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_every=None, num_updates=None, feature_rank=None,
-                     feature_rank_delta=None, ood_gap=None, ood_candidates=None) -> dict:
+                     feature_rank_delta=None, ood_gap=None, ood_candidates=None, action_grad=None, action_grad_steps=None,
+                     action_grad_lr=None) -> dict:
     """--dormant ROWS [--dormant_tau T] [--redo_every N] [--feature_rank ROWS [--feature_rank_delta D]] [--ood_gap ROWS
-    [--ood_candidates N]] as the keywords loop.train and loop.train_offline take, asked of loop.redo_rule, loop.feature_rank_rule and
-    loop.ood_gap_rule (ValueError for what they would refuse); {} without the flags"""
+    [--ood_candidates N]] [--action_grad ROWS [--action_grad_steps K] [--action_grad_lr LR]] as the keywords loop.train and
+    loop.train_offline take, asked of loop.redo_rule, loop.feature_rank_rule, loop.ood_gap_rule and loop.action_grad_rule (ValueError
+    for what they would refuse); {} without the flags"""
     kw = {}
     if dormant is not None:
         kw["dormant"] = dict(rows=int(dormant), **(dict(tau=float(dormant_tau)) if dormant_tau is not None else {}))
@@ -472,6 +485,12 @@ def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_ever
         loop.ood_gap_rule(kw["ood_gap"])
     elif ood_candidates is not None:
         raise ValueError("ood_candidates needs ood_gap ROWS: it is the number of sampled actions of that call")
+    if action_grad is not None:
+        kw["action_grad"] = dict(rows=int(action_grad), **(dict(steps=int(action_grad_steps)) if action_grad_steps is not None else {}),
+                                 **(dict(lr=float(action_grad_lr)) if action_grad_lr is not None else {}))
+        loop.action_grad_rule(kw["action_grad"])
+    elif action_grad_steps is not None or action_grad_lr is not None:
+        raise ValueError("action_grad_steps / action_grad_lr need action_grad ROWS: they are the ascent of that call")
     return kw
 
 
@@ -481,7 +500,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
             native_rollout: bool = False, hindsight: bool = False, fused_rollout: bool = False, init: str = "torch",
             reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, collected_rollout: bool = False,
             dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None,
-            feature_rank=None, feature_rank_delta=None, ood_gap=None, ood_candidates=None, **over):
+            feature_rank=None, feature_rank_delta=None, ood_gap=None, ood_candidates=None, action_grad=None, action_grad_steps=None,
+            action_grad_lr=None, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -504,7 +524,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     fresh episodes of them (loop.train q_bias=dict(env=, seed=)); both need what eval_plan states.
     `feature_rank` [, `feature_rank_delta`]: the effective rank of the last hidden layer over that many ring rows at every evaluation
     (loop.train / loop.train_offline feature_rank=...).  `ood_gap` [, `ood_candidates`]: the critics at that many ring rows under sampled
-    actions at every evaluation (loop.train / loop.train_offline ood_gap=...)."""
+    actions at every evaluation (loop.train / loop.train_offline ood_gap=...).  `action_grad` [, `action_grad_steps`, `action_grad_lr`]:
+    the critics' action gradients at that many ring rows at every evaluation (loop.train / loop.train_offline action_grad=...)."""
     import json
     import time
     from pathlib import Path
@@ -545,7 +566,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     offline = offline_dataset is not None and prior_fraction is None
     watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every,
                              int(num_updates if num_updates is not None else cfg.num_timesteps) if offline else None,
-                             feature_rank, feature_rank_delta, ood_gap, ood_candidates)
+                             feature_rank, feature_rank_delta, ood_gap, ood_candidates, action_grad, action_grad_steps, action_grad_lr)
     run_dir = Path(out_dir) / f"{env_id}__{algo}__seed{seed:02d}"
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
@@ -613,7 +634,8 @@ def _worker_main(args, plan, flags) -> int:
             if args.collected_rollout:           # (the same)
                 out["collected_rollout"] = True
             for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias", "dormant", "dormant_tau", "redo_every",
-                      "exploration_beta", "exploration_len", "feature_rank", "feature_rank_delta", "ood_gap", "ood_candidates"):      # (the same)
+                      "exploration_beta", "exploration_len", "feature_rank", "feature_rank_delta", "ood_gap", "ood_candidates",
+                      "action_grad", "action_grad_steps", "action_grad_lr"):      # (the same)
                 if k in flags:
                     out[k] = flags[k]
         else:
@@ -705,6 +727,11 @@ def main(argv=None) -> int:
     ap.add_argument("--ood_gap", type=int, default=None, metavar="ROWS",
                     help="at every evaluation: the critics at ROWS ring rows under sampled actions, on the device (loop.train ood_gap=...; "
                          "vitals/ood_gap_policy, vitals/ood_gap_uniform, vitals/value_sampled)")
+    ap.add_argument("--action_grad", type=int, default=None, metavar="ROWS",
+                    help="at every evaluation: the critics' action gradients at ROWS ring rows, on the device (loop.train action_grad=...; "
+                         "vitals/action_grad_norm, vitals/action_grad_cos, vitals/refine_gain)")
+    ap.add_argument("--action_grad_steps", type=int, default=None, metavar="K", help="with --action_grad: ascent steps from the policy's mode, 0 .. 16 (default 4)")
+    ap.add_argument("--action_grad_lr", type=float, default=None, metavar="LR", help="with --action_grad: length of a step in normalised action units (default 0.05)")
     ap.add_argument("--ood_candidates", type=int, default=None, metavar="N", help="with --ood_gap: sampled actions per row, 16, 32 or 64 (default 16)")
     ap.add_argument("--redo_every", type=int, default=None, metavar="N",
                     help="with --dormant: ReDo -- every N critic updates, scan and re-initialise the dormant units (excludes --reset_every)")

@@ -575,6 +575,40 @@ def ood_gap_rule(ood_gap):
         raise ValueError("ood_gap: candidates is 16, 32 or 64")
 
 
+class ActionGrad:
+    """`action_grad=dict(rows= [, steps=, lr=, seed=])` of train / train_offline: at every evaluation point `agent.critic_smoothness`
+    -- the critics' action gradients over `rows` ring rows drawn with a generator of its own, at the data actions and along a few ascent
+    steps from the policy's mode.  -> vitals/action_grad_norm, vitals/action_grad_cos, vitals/refine_gain.  The calls have device memory
+    of their own: the run's bits are those of the run without them."""
+    KEYS = ("vitals/action_grad_norm", "vitals/action_grad_cos", "vitals/refine_gain")
+
+    def __init__(self, agent, spec):
+        self.agent, self.kw, self.last = agent, dict(spec), {}
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        got = self.agent.critic_smoothness(**self.kw)
+        self.last = {f"vitals/{k}": got[k] for k in ("action_grad_norm", "action_grad_cos", "refine_gain")}
+        if tabular is not None:
+            for k, v in self.last.items():
+                tabular.record(k, v)
+        return self.last
+
+
+def action_grad_rule(action_grad):
+    """the keyword rule of `action_grad`, asked before an agent is touched (ValueError)"""
+    if action_grad is None:
+        return
+    if not isinstance(action_grad, dict) or set(action_grad) - {"rows", "steps", "lr", "seed"} or "rows" not in action_grad:
+        raise ValueError("action_grad must be a dict with `rows` [, `steps`, `lr`, `seed`]")
+    if not 1 <= int(action_grad["rows"]) <= 65536:
+        raise ValueError("action_grad: 1 <= rows <= 65536")
+    if not 0 <= int(action_grad.get("steps", 4)) <= 16:
+        raise ValueError("action_grad: 0 <= steps <= 16")
+    lr = float(action_grad.get("lr", 0.05))
+    if not (lr >= 0.0 and lr != float("inf")):
+        raise ValueError("action_grad: lr must be finite and >= 0")
+
+
 def redo_rule(dormant, redo_every, redo_what=REDO_ALL, reset_every=None, num_updates: Optional[int] = None):
     """The keyword rules of `dormant` / `redo_every` / `redo_what`, asked before an agent is touched (ValueError), and the rule itself:
     None without `redo_every`, else redo(agent, before, first=None) -> the update count now, with the contract of update_plan's reset:
@@ -627,12 +661,13 @@ class _Vitals:
         return {k: v for part in self.parts for k, v in part.last.items()}
 
 
-def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None, ood_gap=None):
-    """PolicyStats, QBias, Dormant, FeatureRank and / or OodGap as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
+def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None, ood_gap=None, action_grad=None):
+    """PolicyStats, QBias, Dormant, FeatureRank, OodGap and / or ActionGrad as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
     parts = ([PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0))] if policy_stats else []) + ([QBias(agent, q_bias)] if q_bias is not None else [])
     parts += [Dormant(agent, dormant)] if dormant is not None else []
     parts += [FeatureRank(agent, feature_rank)] if feature_rank is not None else []
     parts += [OodGap(agent, ood_gap)] if ood_gap is not None else []
+    parts += [ActionGrad(agent, action_grad)] if action_grad is not None else []
     return None if not parts else parts[0] if len(parts) == 1 else _Vitals(parts)
 
 
@@ -806,7 +841,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           reset_every: Optional[int] = None, reset_what: Any = RESET_ALL, q_bias: Optional[Dict[str, Any]] = None,
           collected_rollout: bool = False, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
           redo_what: Any = REDO_ALL, exploration_beta: Optional[float] = None, exploration_len: int = 256,
-          feature_rank: Optional[Dict[str, Any]] = None, ood_gap: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+          feature_rank: Optional[Dict[str, Any]] = None, ood_gap: Optional[Dict[str, Any]] = None,
+          action_grad: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -882,11 +918,15 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     vitals/erank_actor, vitals/erank_critics, vitals/feature_rank_converged; the run itself is bit for bit the run without it.
     `ood_gap=dict(rows=, candidates= [, seed=])` (default None: off, and no call is made): at every evaluation point the critics at
     `rows` ring rows under `candidates` policy-sampled and as many uniform actions (OodGap) -- vitals/ood_gap_policy,
-    vitals/ood_gap_uniform, vitals/value_sampled; the run itself is bit for bit the run without it."""
+    vitals/ood_gap_uniform, vitals/value_sampled; the run itself is bit for bit the run without it.
+    `action_grad=dict(rows= [, steps=, lr=, seed=])` (default None: off, and no call is made): at every evaluation point the critics'
+    action gradients at `rows` ring rows (ActionGrad) -- vitals/action_grad_norm, vitals/action_grad_cos, vitals/refine_gain; the run
+    itself is bit for bit the run without it."""
     redo = redo_rule(dormant, redo_every, redo_what, reset_every)         # (refusals before the agent is touched)
     feature_rank_rule(feature_rank)
     ood_gap_rule(ood_gap)
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap)
+    action_grad_rule(action_grad)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad)
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
                        prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
                        reset_every=reset_every, reset_what=reset_what)
@@ -988,7 +1028,7 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
                   policy_stats: int = 0, reset_every: Optional[int] = None, reset_what: Any = RESET_ALL,
                   q_bias: Optional[Dict[str, Any]] = None, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
                   redo_what: Any = REDO_ALL, feature_rank: Optional[Dict[str, Any]] = None,
-                  ood_gap: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+                  ood_gap: Optional[Dict[str, Any]] = None, action_grad: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
@@ -998,18 +1038,19 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
     only), `q_bias=dict(env=, seed=)` as for train.  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
     is refused (update_plan's table).  `dormant` / `redo_every` / `redo_what` as for train: the runs also end where a redo is due.
-    `feature_rank` and `ood_gap` as for train.  Returns the last metrics."""
+    `feature_rank`, `ood_gap` and `action_grad` as for train.  Returns the last metrics."""
     num_updates = int(num_updates)
     if num_updates < 0:
         raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
     redo = redo_rule(dormant, redo_every, redo_what, reset_every, num_updates)      # (before the agent is touched)
     feature_rank_rule(feature_rank)
     ood_gap_rule(ood_gap)
+    action_grad_rule(action_grad)
     reset = None
     if reset_every is not None:                                           # (before the agent is touched)
         reset = update_plan(cfg, fused=True, sampler=None, prioritized=None, n_step=1, one_launch=False, prior_fraction=None,
                             updates_per_step=1, reset_every=reset_every, reset_what=reset_what, num_updates=num_updates).reset
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad)
     resets = reset is not None                                            # vitals/resets belongs to a run that resets
     if redo is not None:
         reset, reset_every = redo, redo_every                             # the same schedule: the runs end where a redo is due
