@@ -98,6 +98,10 @@ AV_SUMMARY = ("q_max", "q_mean", "q_lme", "q_std", "soft_value", "q_data", "logp
 ACTION_GRADIENT_SYMBOLS = ["sactd3_action_gradient_device", "sactd3_action_gradient_stats"]
 AG_MAX_STEPS = 16                   # `steps` of sactd3_action_gradient_device at most (SACTD3_AG_MAX_STEPS)
 AG_SUMMARY = ("q_min_start", "q_min_end", "grad_norm_q1", "grad_norm_q2", "grad_cos", "moved", "held_steps", "reserved")   # summary[row][8]
+# every symbol include/sactd3_ring_knn.h declares (tests/test_ring_knn_host.py checks the header against this list)
+RING_KNN_SYMBOLS = ["sactd3_ring_knn_device", "sactd3_ring_knn_stats"]
+KNN_STATE, KNN_STATE_ACTION = 0, 1  # `key` of sactd3_ring_knn_device (SACTD3_KNN_*)
+KNN_MAX_K, KNN_MAX_D = 16, 416      # SACTD3_KNN_MAX_K, SACTD3_KNN_MAX_D
 # every symbol include/sactd3_eval.h declares (tests/test_eval_rollout_host.py checks the header against this list)
 EVAL_SYMBOLS = ["sactd3_eval_rollout", "sactd3_eval_stats"]
 EVAL_GREEDY, EVAL_SAMPLE = 0, 1     # sactd3_eval_config.mode (SACTD3_EVAL_*)
@@ -160,6 +164,12 @@ class CActionGradientIO(C.Structure):
     _fields_ = [("q_start", C.c_void_p), ("q_start_ld", C.c_int64), ("grad", C.c_void_p), ("grad_obs", C.c_void_p),
                 ("refined", C.c_void_p), ("refined_ld", C.c_int64), ("q_end", C.c_void_p), ("q_end_ld", C.c_int64),
                 ("summary", C.c_void_p), ("summary_ld", C.c_int64)]
+
+
+class CRingKnnIO(C.Structure):
+    """sactd3_ring_knn_io: device pointers (None = not given / not wanted), the strided ones with their row stride in elements"""
+    _fields_ = [("offset", C.c_void_p), ("scale", C.c_void_p), ("exclude", C.c_void_p), ("exclude_ld", C.c_int64),
+                ("index", C.c_void_p), ("index_ld", C.c_int64), ("dist2", C.c_void_p), ("dist2_ld", C.c_int64)]
 
 
 class CHindsightConfig(C.Structure):
@@ -417,6 +427,13 @@ def load_library():
     }
     assert sorted(action_gradient_sig) == sorted(ACTION_GRADIENT_SYMBOLS)
     sig.update(action_gradient_sig)
+    ring_knn_sig = {
+        "sactd3_ring_knn_device": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                             C.POINTER(CRingKnnIO), vp, C.c_int]),
+        "sactd3_ring_knn_stats": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(ring_knn_sig) == sorted(RING_KNN_SYMBOLS)
+    sig.update(ring_knn_sig)
     eval_sig = {
         "sactd3_eval_rollout": (C.c_int, [vp, vp, C.POINTER(CEvalConfig), C.POINTER(CEvalOut), vp, C.c_int]),
         "sactd3_eval_stats": (C.c_int, [vp, i64p]),

@@ -650,6 +650,7 @@ class Agent:
         self._feature_rank_gen = None    # feature_rank()'s, the same
         self._ood_gen = None        # ood_gap()'s, the same
         self._smooth_gen = None     # critic_smoothness()'s, the same
+        self._knn_gen = None        # knn_vitals()'s, the same
         self.min_ac, self.max_ac = np.asarray(min_ac, np.float32), np.asarray(max_ac, np.float32)
         self.timesteps_so_far = 0
         self.actor_updates_so_far = 0
@@ -835,6 +836,64 @@ class Agent:
         three = torch.stack([0.5 * (data["grad_norm_q1"] + data["grad_norm_q2"]).mean(), data["grad_cos"].mean(),
                              (pol["q_min_end"] - pol["q_min_start"]).mean()]).tolist()
         return dict(zip(("action_grad_norm", "action_grad_cos", "refine_gain"), three))
+
+    def ring_knn(self, queries, k: int, key: str = "state", offset=None, scale=None, exclude=None, first: int = 0, count=None,
+                 out: Any = None) -> Dict[str, Any]:
+        """The `k` nearest ring rows of each row of `queries` (a float32 tensor on the engine's device), searched on the device
+        (include/sactd3_ring_knn.h; Engine.ring_knn) -> {"index": int64 [n, k], "dist2": float32 [n, k]} on that device.  No host
+        wait; training and acting do not see it."""
+        return self.engine.ring_knn(_detached(queries), k, key=key, offset=offset, scale=scale, exclude=exclude, first=first, count=count, out=out)
+
+    def state_novelty(self, index, k: int = 5, offset=None, scale=None) -> Dict[str, Any]:
+        """The particle-based novelty of the states in the ring slots `index` (as for ReplayBuffer.rows) among all ring states, each
+        with its own slot excluded (APT, Liu & Abbeel 2021; RE3, Seo et al. 2021): -> {"bonus": 0.5 * log1p(dist2_k) [n], "dist2":
+        the squared distance to the k-th nearest other state [n] (+inf where fewer than k exist)} on the engine's device; no host wait."""
+        import torch
+        index = torch.as_tensor(index, dtype=torch.int64, device=torch.device("cuda", self.engine.cfg.device_id)).reshape(-1)
+        got = self.engine.ring_knn(self.rb.rows(index)["observations"], k, key="state", offset=offset, scale=scale, exclude=index)
+        d2 = got["dist2"][:, int(k) - 1]
+        return {"bonus": 0.5 * torch.log1p(d2), "dist2": d2}
+
+    def dataset_distance(self, obs, beta: float = 2.0, k: int = 1, first: int = 0, count=None) -> Dict[str, Any]:
+        """The dataset-constraint distance of the policy at `obs` [n, ob_dim] (float32 on the engine's device; PRDC, Ran et al. 2023):
+        from (beta s, pi(s) / sc), pi's mode and sc the action half-range, to the nearest (beta s_i, a_i / sc) among the ring slots
+        [first, first + count).  -> {"index": [n, k], "dist2": [n, k], "action_dist2": [n, k] the action part of dist2 alone, computed
+        in torch from the rows found} on that device; no host wait."""
+        import torch
+        eng = self.engine
+        dev = torch.device("cuda", eng.cfg.device_id)
+        obs = _detached(obs).reshape(-1, eng.cfg.ob_dim)
+        mode = self.policy({"observations": obs})["mode"]
+        inv = torch.as_tensor(2.0 / (self.max_ac - self.min_ac), dtype=torch.float32, device=dev)
+        scale = torch.cat([torch.full((eng.cfg.ob_dim,), float(beta), dtype=torch.float32, device=dev), inv])
+        got = eng.ring_knn(torch.cat([obs, mode], dim=1), k, key="state_action", scale=scale, first=first, count=count)
+        found = self.rb.rows(got["index"].clamp(min=0).reshape(-1))["actions"].reshape(obs.shape[0], int(k), -1)
+        part = (((mode[:, None, :] - found) * inv) ** 2).sum(-1)
+        got["action_dist2"] = torch.where(got["index"] >= 0, part, torch.full_like(part, float("inf")))
+        return got
+
+    def knn_vitals(self, rows: int = 256, k: int = 5, beta: float = 2.0, seed: Optional[int] = None) -> Dict[str, float]:
+        """Coverage and drift on `rows` ring slots drawn with a torch generator of this method's own (seeded at its first use; None:
+        the engine's seed): the mean particle bonus of their states (state_novelty) and the mean distance sqrt(dist2) of the policy at
+        those states from the data (dataset_distance; among the pinned rows alone where rows are pinned).  One host wait for the two
+        means.  -> {"knn_state_entropy", "knn_policy_distance"}"""
+        import torch
+        eng = self.engine
+        dev = torch.device("cuda", eng.cfg.device_id)
+        if self._knn_gen is None:
+            self._knn_gen = torch.Generator(device=dev)
+            self._knn_gen.manual_seed(int(eng.cfg.seed if seed is None else seed))
+        n = len(self.rb) if self.rb is not None else eng.rb_len()
+        if n < 1:
+            raise ValueError("knn_vitals: the replay ring is empty")
+        index = torch.randint(0, n, (int(rows),), generator=self._knn_gen, device=dev, dtype=torch.int64)
+        bonus = self.state_novelty(index, k=k)["bonus"]
+        pinned = eng.rb_pinned()
+        far = self.dataset_distance(self.rb.rows(index)["observations"], beta=beta, k=1, count=pinned if pinned > 0 else None)
+        ok = torch.isfinite(bonus)      # (a ring with k rows or fewer has no k-th other state)
+        two = torch.stack([torch.where(ok, bonus, torch.zeros_like(bonus)).sum() / ok.sum().clamp(min=1),
+                           far["dist2"][:, 0].sqrt().mean()]).tolist()
+        return dict(zip(("knn_state_entropy", "knn_policy_distance"), two))
 
     def recycle_dormant(self, what=("actor", "critics")) -> int:
         """ReDo: re-initialise the hidden units the last dormant() marked in the nets `what` names and keep everything else

@@ -52,6 +52,10 @@ static_assert(AV_SRC_POLICY == SACTD3_AV_POLICY && AV_SRC_UNIFORM == SACTD3_AV_U
 #include "action_gradient.h"
 #include "../../include/sactd3_action_gradient.h"
 static_assert(AG_SUMMARY == SACTD3_AG_SUMMARY && AG_MAXSTEPS == SACTD3_AG_MAX_STEPS, "the kernel's limits are the C ABI's");
+// ... and the nearest-ring-rows call (ring_knn.hip; its C ABI is include/sactd3_ring_knn.h, defined behind the action-gradient call's)
+#include "ring_knn.h"
+#include "../../include/sactd3_ring_knn.h"
+static_assert(KNN_MAXK == SACTD3_KNN_MAX_K && KNN_MAXD == SACTD3_KNN_MAX_D, "the kernel's limits are the C ABI's");
 // ... and the evaluation rollout, whose kernel is compiled with the env kernels (env.hip): host code only here, at the end of this file
 #include "eval_rollout.h"
 // ... and the collected rollout segment, split the same way (collect_rollout.h)
@@ -360,6 +364,13 @@ struct sactd3_engine {
   // counts of one launch.  Made at the first call and shared with nothing.  ag_host: {calls, rows, ascent steps x rows}.
   int *ag_words = nullptr, *ag_bad = nullptr;
   int64_t ag_host[3] = {};
+  // The k nearest ring rows of a query (sactd3_ring_knn_device; include/sactd3_ring_knn.h; device code: ring_knn_kernels.h, a translation
+  // unit of its own).  kn_sel / kn_slot: the partial slab [slice][query][k] of one launch; kn_qflags, kn_bad: the queries' flags and the
+  // slices' counts of one launch; kn_words: the counters.  Made at the first call and shared with nothing.  kn_host: {calls, queries,
+  // ring rows scanned}.
+  float* kn_sel = nullptr;
+  int *kn_slot = nullptr, *kn_qflags = nullptr, *kn_bad = nullptr, *kn_words = nullptr;
+  int64_t kn_host[3] = {};
   // Coloured exploration noise (sactd3_colored_noise_device; include/sactd3_noise.h; device code: noise_kernels.h, a translation unit of
   // its own).  nz_tables: the amplitude and twiddle tables of every (beta, length) pair asked for so far, each made at its first use --
   // an engine that never generates holds nothing more than before.
@@ -4533,6 +4544,74 @@ int sactd3_action_gradient_stats(sactd3_engine* e, int64_t out[8]) {
   }
   for (int i = 0; i < 8; ++i) out[i] = 0;
   out[0] = e->ag_host[0]; out[1] = e->ag_host[1]; out[2] = w[AG_W_NONFINITE]; out[3] = e->ag_host[2];
+  return 0;
+}
+
+// ---- the k nearest ring rows of each query (include/sactd3_ring_knn.h).  Per chunk of KNN_CHUNK queries: k_knn_scan<DP> over (ring
+// slices) x (query tiles), which reads the ring records and the caller's queries where they lie, k_knn_finish and k_knn_count
+// (ring_knn.hip).  Like a scoring call it writes memory of its own and the caller's, nothing else of the engine's: no CHAIN_BREAK, no
+// counter of training, acting or another feature, allowed while an acting call is in flight.
+int sactd3_ring_knn_device(sactd3_engine* e, const float* queries, int64_t queries_ld, int n, int k, int key,
+                           int64_t first, int64_t count, const sactd3_ring_knn_io* io, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first: a refused call has launched, allocated and counted nothing
+  if (!queries || !io) return e->fail(SACTD3_EINVAL, "ring_knn_device: null argument");
+  if (!(io->index || io->dist2)) return e->fail(SACTD3_EINVAL, "ring_knn_device: no output is set");
+  if (n < 1) return e->fail(SACTD3_EINVAL, "ring_knn_device: n >= 1 required");
+  if (k < 1 || k > SACTD3_KNN_MAX_K) return e->fail(SACTD3_EINVAL, "ring_knn_device: 1 <= k <= 16 required");
+  if (key != SACTD3_KNN_STATE && key != SACTD3_KNN_STATE_ACTION) return e->fail(SACTD3_EINVAL, "ring_knn_device: unknown key");
+  if (flags & ~(SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) return e->fail(SACTD3_EINVAL, "ring_knn_device: unknown flag");
+  if (first < 0 || count < 0) return e->fail(SACTD3_EINVAL, "ring_knn_device: first >= 0 and count >= 0 required");
+  const int D = key == SACTD3_KNN_STATE ? e->o : e->o + e->a;
+  if (D > SACTD3_KNN_MAX_D) return e->fail(SACTD3_EINVAL, "ring_knn_device: the key is wider than SACTD3_KNN_MAX_D");
+  USE_DEVICE(e);
+  const FieldRow in[1] = {{queries, queries_ld, D, "queries"}};
+  const FieldRow opt[5] = {{io->offset, D, D, "offset"}, {io->scale, D, D, "scale"}, {io->exclude, io->exclude_ld, 1, "exclude"},
+                           {io->index, io->index_ld, k, "index"}, {io->dist2, io->dist2_ld, k, "dist2"}};
+  RCCHK(field_rows_check(e, in, 1, true, "ring_knn_device", nullptr));
+  RCCHK(field_rows_check(e, opt, 5, false, "ring_knn_device", nullptr));
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "ring_knn_device: buffer is empty");
+  const int64_t last = count == 0 ? e->rb_len : std::min<int64_t>(e->rb_len, first + std::min<int64_t>(count, e->rb_len));
+  if (first >= last) return e->fail(SACTD3_ESTATE, "ring_knn_device: the range is empty inside [0, rb_len)");
+  RCCHK(first_use_alloc(e, &e->kn_sel, KNN_SLAB, false));        // (never zeroed: a scan writes every partial the finish reads)
+  RCCHK(first_use_alloc(e, &e->kn_slot, KNN_SLAB, false));
+  RCCHK(first_use_alloc(e, &e->kn_qflags, (size_t)KNN_CHUNK, false));
+  RCCHK(first_use_alloc(e, &e->kn_bad, (size_t)KNN_MAXSLICES, false));
+  RCCHK(first_use_alloc(e, &e->kn_words, (size_t)KNN_WORDS));
+  KnnArgs g{};
+  g.ring = e->ring; g.rec_f = e->rec_f; g.D = D; g.k = k; g.first = (long)first; g.last = (long)last;
+  knn_slices(g.last - g.first, &g.slice_rows, &g.nslices);
+  g.offset = io->offset; g.scale = io->scale;
+  g.q_ld = (long)queries_ld; g.exclude_ld = (long)io->exclude_ld; g.index_ld = (long)io->index_ld; g.dist2_ld = (long)io->dist2_ld;
+  g.part_sel = e->kn_sel; g.part_slot = e->kn_slot; g.qflags = e->kn_qflags; g.bad = e->kn_bad; g.words = e->kn_words;
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  const int ordered = (flags & (SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) ? SACTD3_SRC_ORDERED : 0;      // (one pair of events serves both sides)
+  RCCHK(src_order_begin(e, caller, ordered));
+  for (int64_t r0 = 0; r0 < n; r0 += KNN_CHUNK) {
+    auto at = [&](auto* p, int64_t ld) { return p ? p + r0 * ld : p; };
+    g.m = (int)std::min<int64_t>(KNN_CHUNK, n - r0);
+    g.count_rows = r0 == 0;
+    g.q = at(queries, queries_ld); g.exclude = (const long long*)at(io->exclude, io->exclude_ld);
+    g.index = (long long*)at(io->index, io->index_ld); g.dist2 = at(io->dist2, io->dist2_ld);
+    const hipError_t he = ring_knn_launch(g, (long)e->rb_len, e->stream);
+    if (he != hipSuccess) return e->fail(SACTD3_EHIP, "ring_knn_device: k_knn_scan / k_knn_finish / k_knn_count", he);
+  }
+  RCCHK(src_order_end(e, caller, ordered));
+  ++e->kn_host[0]; e->kn_host[1] += n; e->kn_host[2] += last - first;
+  return 0;
+}
+
+int sactd3_ring_knn_stats(sactd3_engine* e, int64_t out[8]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  int w[KNN_WORDS] = {};
+  if (e->kn_words) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(w, e->kn_words, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = e->kn_host[0]; out[1] = e->kn_host[1]; out[2] = e->kn_host[2];
+  out[3] = w[KNN_W_BADQ]; out[4] = w[KNN_W_BADROWS]; out[5] = w[KNN_W_SHORT];
   return 0;
 }
 

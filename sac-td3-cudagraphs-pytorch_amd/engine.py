@@ -414,6 +414,78 @@ class Engine:
         self._ck(self.lib.sactd3_action_gradient_stats(self._h, out))
         return dict(zip(("calls", "rows", "rows_nonfinite", "ascent_steps"), (int(x) for x in out)))
 
+    # -- the k nearest ring rows of each query (include/sactd3_ring_knn.h)
+    def ring_knn(self, queries, k: int, key: str = "state", offset=None, scale=None, exclude=None, first: int = 0, count=None,
+                 out=None) -> Dict[str, object]:
+        """sactd3_ring_knn_device: per row of `queries` [n, D] (a float32 CUDA tensor of this device; D = ob_dim with `key="state"`,
+        ob_dim + ac_dim with `key="state_action"`) the `k` (1 .. 16) nearest ring rows among the slots [first, first + count) (`count`
+        None: to the ring's length), both sides transformed as (key - offset) * scale (`offset`, `scale`: float32 [D] on the device,
+        None: 0 / 1), `exclude` (int64 [n], -1: none) naming one slot per query that is never reported.  Eager launches on the engine's
+        stream, ordered on the GPU against torch's current stream; no host wait; training and acting do not see the call.  `out`: a
+        mapping of preallocated contiguous tensors of that device under the keys below.
+        -> {"index": int64 [n, k] ring slots by (dist2, slot) ascending, -1 where fewer than k exist, "dist2": float32 [n, k]}"""
+        import torch
+        dev = torch.device("cuda", self.cfg.device_id)
+        if key not in ("state", "state_action"):
+            raise ValueError(f"ring_knn: `key` is 'state' or 'state_action', got {key!r}")
+        D = self.cfg.ob_dim + (self.cfg.ac_dim if key == "state_action" else 0)
+        k = int(k)
+        if not 1 <= k <= _lib.KNN_MAX_K:
+            raise ValueError(f"ring_knn: 1 <= k <= {_lib.KNN_MAX_K}, got {k}")
+        if int(first) < 0 or (count is not None and int(count) < 1):
+            raise ValueError("ring_knn: first >= 0 and count >= 1 (None: to the ring's length)")
+
+        def given(x, dtype, name):
+            if not (isinstance(x, torch.Tensor) and x.device == dev and x.dtype == dtype):
+                raise TypeError(f"ring_knn: `{name}` is a {str(dtype).split('.')[1]} tensor in the memory of the engine's device")
+            return x
+
+        queries = given(queries, torch.float32, "queries")
+        queries = queries.reshape(queries.shape[0], -1) if queries.dim() > 1 else queries.reshape(1, -1)
+        if queries.shape[1] != D:
+            raise ValueError(f"ring_knn: `queries` has shape {tuple(queries.shape)}, expected [n, {D}]")
+        if not (queries.stride(1) == 1 and queries.stride(0) >= D):
+            queries = queries.contiguous()
+        n = queries.shape[0]
+        io = _lib.CRingKnnIO()
+        keep = [queries]
+        for name, x in (("offset", offset), ("scale", scale)):
+            if x is not None:
+                x = given(x, torch.float32, name).reshape(-1).contiguous()
+                if x.shape[0] != D:
+                    raise ValueError(f"ring_knn: `{name}` has {x.shape[0]} elements, expected {D}")
+                keep.append(x)
+                setattr(io, name, x.data_ptr())
+        if exclude is not None:
+            exclude = given(exclude, torch.int64, "exclude").reshape(-1).contiguous()
+            if exclude.shape[0] != n:
+                raise ValueError(f"ring_knn: `exclude` has {exclude.shape[0]} elements, expected {n}")
+            keep.append(exclude)
+            io.exclude, io.exclude_ld = exclude.data_ptr(), 1
+        res = {}
+        for name, dtype in (("index", torch.int64), ("dist2", torch.float32)):
+            t = out.get(name) if out else None
+            if t is None:
+                t = torch.empty((n, k), dtype=dtype, device=dev)
+            elif not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == (n, k) and t.is_contiguous()):
+                raise ValueError(f"ring_knn: out[{name!r}] is a contiguous {str(dtype).split('.')[1]} tensor {(n, k)} of the engine's device")
+            res[name] = t
+            setattr(io, name, t.data_ptr())
+        io.index_ld = io.dist2_ld = k
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+        self._ck(self.lib.sactd3_ring_knn_device(self._h, _vp(queries.data_ptr()), queries.stride(0), n, k,
+                                                 _lib.KNN_STATE_ACTION if key == "state_action" else _lib.KNN_STATE, int(first),
+                                                 0 if count is None else int(count), C.byref(io), _vp(stream),
+                                                 _lib.SRC_ORDERED | _lib.DST_ORDERED))
+        del keep
+        return res
+
+    def ring_knn_stats(self) -> Dict[str, int]:
+        """counters of ring_knn (sactd3_ring_knn_stats; waits for the engine's stream: three of them live on the device)"""
+        out = (C.c_int64 * 8)()
+        self._ck(self.lib.sactd3_ring_knn_stats(self._h, out))
+        return dict(zip(("calls", "queries", "rows_scanned", "queries_nonfinite", "ring_keys_nonfinite", "short_results"), (int(x) for x in out)))
+
     # -- coloured exploration noise (include/sactd3_noise.h)
     def colored_noise(self, beta: float, length: int, sequences: int, chunk: int = 0, epoch: int = 0, out=None):
         """sactd3_colored_noise_device: chunk `chunk` of `sequences` independent 1/f^beta Gaussian sequences (beta in [0, 2]: 0 white,

@@ -609,6 +609,40 @@ def action_grad_rule(action_grad):
         raise ValueError("action_grad: lr must be finite and >= 0")
 
 
+class Knn:
+    """`knn=dict(rows= [, k=, beta=, seed=])` of train / train_offline: at every evaluation point `agent.knn_vitals` -- the k nearest
+    ring rows of `rows` ring states drawn with a generator of its own, and of the policy's (state, action) pairs there, searched on the
+    device.  -> vitals/knn_state_entropy, vitals/knn_policy_distance.  The calls have device memory of their own: the run's bits are
+    those of the run without them."""
+    KEYS = ("vitals/knn_state_entropy", "vitals/knn_policy_distance")
+
+    def __init__(self, agent, spec):
+        self.agent, self.kw, self.last = agent, dict(spec), {}
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        got = self.agent.knn_vitals(**self.kw)
+        self.last = {f"vitals/{k}": got[k] for k in ("knn_state_entropy", "knn_policy_distance")}
+        if tabular is not None:
+            for k, v in self.last.items():
+                tabular.record(k, v)
+        return self.last
+
+
+def knn_rule(knn):
+    """the keyword rule of `knn`, asked before an agent is touched (ValueError)"""
+    if knn is None:
+        return
+    if not isinstance(knn, dict) or set(knn) - {"rows", "k", "beta", "seed"} or "rows" not in knn:
+        raise ValueError("knn must be a dict with `rows` [, `k`, `beta`, `seed`]")
+    if not 1 <= int(knn["rows"]) <= 65536:
+        raise ValueError("knn: 1 <= rows <= 65536")
+    if not 1 <= int(knn.get("k", 5)) <= 16:
+        raise ValueError("knn: 1 <= k <= 16")
+    beta = float(knn.get("beta", 2.0))
+    if not (beta > 0.0 and beta != float("inf")):
+        raise ValueError("knn: beta must be finite and > 0")
+
+
 def redo_rule(dormant, redo_every, redo_what=REDO_ALL, reset_every=None, num_updates: Optional[int] = None):
     """The keyword rules of `dormant` / `redo_every` / `redo_what`, asked before an agent is touched (ValueError), and the rule itself:
     None without `redo_every`, else redo(agent, before, first=None) -> the update count now, with the contract of update_plan's reset:
@@ -661,13 +695,14 @@ class _Vitals:
         return {k: v for part in self.parts for k, v in part.last.items()}
 
 
-def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None, ood_gap=None, action_grad=None):
-    """PolicyStats, QBias, Dormant, FeatureRank, OodGap and / or ActionGrad as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
+def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None, ood_gap=None, action_grad=None, knn=None):
+    """PolicyStats, QBias, Dormant, FeatureRank, OodGap, ActionGrad and / or Knn as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
     parts = ([PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0))] if policy_stats else []) + ([QBias(agent, q_bias)] if q_bias is not None else [])
     parts += [Dormant(agent, dormant)] if dormant is not None else []
     parts += [FeatureRank(agent, feature_rank)] if feature_rank is not None else []
     parts += [OodGap(agent, ood_gap)] if ood_gap is not None else []
     parts += [ActionGrad(agent, action_grad)] if action_grad is not None else []
+    parts += [Knn(agent, knn)] if knn is not None else []
     return None if not parts else parts[0] if len(parts) == 1 else _Vitals(parts)
 
 
@@ -842,7 +877,7 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           collected_rollout: bool = False, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
           redo_what: Any = REDO_ALL, exploration_beta: Optional[float] = None, exploration_len: int = 256,
           feature_rank: Optional[Dict[str, Any]] = None, ood_gap: Optional[Dict[str, Any]] = None,
-          action_grad: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+          action_grad: Optional[Dict[str, Any]] = None, knn: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -921,12 +956,16 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     vitals/ood_gap_uniform, vitals/value_sampled; the run itself is bit for bit the run without it.
     `action_grad=dict(rows= [, steps=, lr=, seed=])` (default None: off, and no call is made): at every evaluation point the critics'
     action gradients at `rows` ring rows (ActionGrad) -- vitals/action_grad_norm, vitals/action_grad_cos, vitals/refine_gain; the run
-    itself is bit for bit the run without it."""
+    itself is bit for bit the run without it.
+    `knn=dict(rows= [, k=, beta=, seed=])` (default None: off, and no call is made): at every evaluation point the k nearest ring rows
+    of `rows` ring states and of the policy's (state, action) pairs there (Knn) -- vitals/knn_state_entropy,
+    vitals/knn_policy_distance; the run itself is bit for bit the run without it."""
     redo = redo_rule(dormant, redo_every, redo_what, reset_every)         # (refusals before the agent is touched)
     feature_rank_rule(feature_rank)
     ood_gap_rule(ood_gap)
     action_grad_rule(action_grad)
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad)
+    knn_rule(knn)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad, knn)
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
                        prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
                        reset_every=reset_every, reset_what=reset_what)
@@ -1028,7 +1067,8 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
                   policy_stats: int = 0, reset_every: Optional[int] = None, reset_what: Any = RESET_ALL,
                   q_bias: Optional[Dict[str, Any]] = None, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
                   redo_what: Any = REDO_ALL, feature_rank: Optional[Dict[str, Any]] = None,
-                  ood_gap: Optional[Dict[str, Any]] = None, action_grad: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+                  ood_gap: Optional[Dict[str, Any]] = None, action_grad: Optional[Dict[str, Any]] = None,
+                  knn: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
@@ -1038,7 +1078,7 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
     only), `q_bias=dict(env=, seed=)` as for train.  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
     is refused (update_plan's table).  `dormant` / `redo_every` / `redo_what` as for train: the runs also end where a redo is due.
-    `feature_rank`, `ood_gap` and `action_grad` as for train.  Returns the last metrics."""
+    `feature_rank`, `ood_gap`, `action_grad` and `knn` as for train.  Returns the last metrics."""
     num_updates = int(num_updates)
     if num_updates < 0:
         raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
@@ -1046,11 +1086,12 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     feature_rank_rule(feature_rank)
     ood_gap_rule(ood_gap)
     action_grad_rule(action_grad)
+    knn_rule(knn)
     reset = None
     if reset_every is not None:                                           # (before the agent is touched)
         reset = update_plan(cfg, fused=True, sampler=None, prioritized=None, n_step=1, one_launch=False, prior_fraction=None,
                             updates_per_step=1, reset_every=reset_every, reset_what=reset_what, num_updates=num_updates).reset
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad, knn)
     resets = reset is not None                                            # vitals/resets belongs to a run that resets
     if redo is not None:
         reset, reset_every = redo, redo_every                             # the same schedule: the runs end where a redo is due
