@@ -102,6 +102,10 @@ AG_SUMMARY = ("q_min_start", "q_min_end", "grad_norm_q1", "grad_norm_q2", "grad_
 RING_KNN_SYMBOLS = ["sactd3_ring_knn_device", "sactd3_ring_knn_stats"]
 KNN_STATE, KNN_STATE_ACTION = 0, 1  # `key` of sactd3_ring_knn_device (SACTD3_KNN_*)
 KNN_MAX_K, KNN_MAX_D = 16, 416      # SACTD3_KNN_MAX_K, SACTD3_KNN_MAX_D
+# every symbol include/sactd3_returns.h declares (tests/test_returns_host.py checks the header against this list)
+RETURNS_SYMBOLS = ["sactd3_returns_to_go_device", "sactd3_returns_to_go_stats"]
+RTG_TERMINATED, RTG_TRUNCATED, RTG_OPEN, RTG_START = 1, 2, 4, 8      # bits of `ends` (SACTD3_RTG_*)
+RTG_SPAN = 2048                     # positions of one workgroup of the scan (SACTD3_RTG_SPAN)
 # every symbol include/sactd3_eval.h declares (tests/test_eval_rollout_host.py checks the header against this list)
 EVAL_SYMBOLS = ["sactd3_eval_rollout", "sactd3_eval_stats"]
 EVAL_GREEDY, EVAL_SAMPLE = 0, 1     # sactd3_eval_config.mode (SACTD3_EVAL_*)
@@ -170,6 +174,11 @@ class CRingKnnIO(C.Structure):
     """sactd3_ring_knn_io: device pointers (None = not given / not wanted), the strided ones with their row stride in elements"""
     _fields_ = [("offset", C.c_void_p), ("scale", C.c_void_p), ("exclude", C.c_void_p), ("exclude_ld", C.c_int64),
                 ("index", C.c_void_p), ("index_ld", C.c_int64), ("dist2", C.c_void_p), ("dist2_ld", C.c_int64)]
+
+
+class CReturnsIO(C.Structure):
+    """sactd3_returns_io: device pointers (None = not wanted), each with the stride between two slots in elements"""
+    _fields_ = [(f, t) for n in ("returns", "undiscounted", "length", "last", "ends") for f, t in ((n, C.c_void_p), (n + "_ld", C.c_int64))]
 
 
 class CHindsightConfig(C.Structure):
@@ -434,6 +443,12 @@ def load_library():
     }
     assert sorted(ring_knn_sig) == sorted(RING_KNN_SYMBOLS)
     sig.update(ring_knn_sig)
+    returns_sig = {
+        "sactd3_returns_to_go_device": (C.c_int, [vp, C.c_float, C.c_int, C.c_int64, C.c_int64, C.POINTER(CReturnsIO), vp, C.c_int]),
+        "sactd3_returns_to_go_stats": (C.c_int, [vp, i64p]),
+    }
+    assert sorted(returns_sig) == sorted(RETURNS_SYMBOLS)
+    sig.update(returns_sig)
     eval_sig = {
         "sactd3_eval_rollout": (C.c_int, [vp, vp, C.POINTER(CEvalConfig), C.POINTER(CEvalOut), vp, C.c_int]),
         "sactd3_eval_stats": (C.c_int, [vp, i64p]),

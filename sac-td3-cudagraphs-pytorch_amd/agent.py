@@ -602,6 +602,32 @@ class ReplayBuffer:
         eng.rb_read_rows_device(ptr, ld, n, fields, _producer_stream(index, eng.cfg.device_id))
         return tensors
 
+    def returns_to_go(self, stride: Optional[int] = None, gamma: Optional[float] = None, out: Optional[Mapping[str, Any]] = None) -> Dict[str, Any]:
+        """What actually happened after every stored row: the Monte-Carlo return-to-go of each ring row to the end of its episode as
+        the ring holds it, computed on the device from the records themselves (include/sactd3_returns.h; Engine.returns_to_go).
+        `stride`: the number of envs that fed the ring in lock-step (None: 1, a dataset loaded episode by episode).  The whole ring,
+        or the pinned prefix alone where rows are pinned (rows behind it keep what `out` held).  -> a dict of tensors of len(rb) rows
+        on the engine's device: "returns", "undiscounted", "length", "last", "ends".  No host wait."""
+        eng = self._need()
+        pinned = eng.rb_pinned()
+        return eng.returns_to_go(gamma, 1 if stride is None else int(stride), 0, pinned if pinned > 0 else None, out)
+
+    def episode_stats(self, stride: Optional[int] = None) -> Dict[str, float]:
+        """Return and length statistics of the episodes the ring holds whole: over the rows no row links into (RTG_START) whose
+        chain does not run into the end of the range (RTG_OPEN), from returns_to_go's outputs by torch reductions and one host wait.
+        -> {"episodes", "return_mean", "return_min", "return_max", "length_mean"} (NaN statistics where no episode counts)"""
+        import torch
+        got = self.returns_to_go(stride, gamma=1.0)
+        n = self.pinned or len(self)
+        ends, u, length = got["ends"][:n], got["undiscounted"][:n].double(), got["length"][:n].double()
+        m = ((ends & _lib.RTG_START) != 0) & ((ends & _lib.RTG_OPEN) == 0)
+        inf = torch.full_like(u, float("inf"))
+        k, s, lo, hi, ls = torch.stack([m.sum().double(), torch.where(m, u, torch.zeros_like(u)).sum(), torch.where(m, u, inf).min(),
+                                        torch.where(m, u, -inf).max(), torch.where(m, length, torch.zeros_like(u)).sum()]).tolist()
+        nan = float("nan")
+        return {"episodes": int(k), "return_mean": s / k if k else nan, "return_min": lo if k else nan, "return_max": hi if k else nan,
+                "length_mean": ls / k if k else nan}
+
     def __len__(self) -> int:
         return 0 if self._engine is None else self._engine.rb_len()
 
@@ -651,6 +677,7 @@ class Agent:
         self._ood_gen = None        # ood_gap()'s, the same
         self._smooth_gen = None     # critic_smoothness()'s, the same
         self._knn_gen = None        # knn_vitals()'s, the same
+        self._mc_gen = None         # mc_q_bias()'s, the same
         self.min_ac, self.max_ac = np.asarray(min_ac, np.float32), np.asarray(max_ac, np.float32)
         self.timesteps_so_far = 0
         self.actor_updates_so_far = 0
@@ -894,6 +921,38 @@ class Agent:
         two = torch.stack([torch.where(ok, bonus, torch.zeros_like(bonus)).sum() / ok.sum().clamp(min=1),
                            far["dist2"][:, 0].sqrt().mean()]).tolist()
         return dict(zip(("knn_state_entropy", "knn_policy_distance"), two))
+
+    def mc_q_bias(self, rows: int = 4096, stride: Optional[int] = None, tail_tol: float = 0.05, seed: Optional[int] = None) -> Dict[str, Any]:
+        """The critics' bias on the data: Q(s, a) of stored rows against the return the data itself shows behind them
+        (ReplayBuffer.returns_to_go at the config's gamma).  `rows` slots are drawn, with a torch generator of this method's own
+        (seeded at its first use; None: the engine's seed), among the rows whose chain TERMINATED or is long enough for
+        gamma^L <= tail_tol -- the admission rule of envs.q_bias: a cut chain lacks the tail behind the cut.  They are scored with
+        q_values (online critics, the stored action); bias = min_k Q_k - G.  One host wait for the final statistics.
+        -> {"mean", "std": of bias / |mean G| over the drawn rows, "bias_mean", "bias_std", "return_mean", "rows", "admitted"}"""
+        import torch
+        eng = self.engine
+        dev = torch.device("cuda", eng.cfg.device_id)
+        if int(rows) < 1 or not 0.0 < float(tail_tol) <= 1.0:
+            raise ValueError("mc_q_bias: rows >= 1 and tail_tol in (0, 1]")
+        if self._mc_gen is None:
+            self._mc_gen = torch.Generator(device=dev)
+            self._mc_gen.manual_seed(int(eng.cfg.seed if seed is None else seed))
+        got = self.rb.returns_to_go(stride)
+        n = self.rb.pinned or len(self.rb)
+        g = float(np.float32(eng.cfg.gamma))
+        ok = ((got["ends"][:n] & _lib.RTG_TERMINATED) != 0) | (torch.full((n,), g, dtype=torch.float64, device=dev) ** got["length"][:n].double() <= float(tail_tol))
+        slots = ok.nonzero().reshape(-1)
+        if slots.numel() == 0:
+            raise ValueError(f"mc_q_bias: no row counts -- no chain terminated and none is long enough for gamma^L <= {tail_tol} (gamma {g})")
+        index = slots[torch.randint(0, slots.numel(), (int(rows),), generator=self._mc_gen, device=dev, dtype=torch.int64)]
+        rec = self.rb.rows(index)
+        q = self.q_values({"observations": rec["observations"], "actions": rec["actions"]})
+        G = got["returns"][index].double()
+        bias = q.view(2, -1).min(0).values.double() - G
+        mean, sq, g_mean = torch.stack([bias.mean(), (bias * bias).mean(), G.mean()]).tolist()      # the final statistics: the one transfer
+        std, scale = float(np.sqrt(max(sq - mean * mean, 0.0))), abs(g_mean)
+        return {"mean": mean / scale if scale > 0 else float("nan"), "std": std / scale if scale > 0 else float("nan"),
+                "bias_mean": mean, "bias_std": std, "return_mean": g_mean, "rows": int(rows), "admitted": int(slots.numel())}
 
     def recycle_dormant(self, what=("actor", "critics")) -> int:
         """ReDo: re-initialise the hidden units the last dormant() marked in the nets `what` names and keep everything else

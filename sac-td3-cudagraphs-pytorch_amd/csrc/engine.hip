@@ -56,6 +56,11 @@ static_assert(AG_SUMMARY == SACTD3_AG_SUMMARY && AG_MAXSTEPS == SACTD3_AG_MAX_ST
 #include "ring_knn.h"
 #include "../../include/sactd3_ring_knn.h"
 static_assert(KNN_MAXK == SACTD3_KNN_MAX_K && KNN_MAXD == SACTD3_KNN_MAX_D, "the kernel's limits are the C ABI's");
+// ... and the returns-to-go call (returns.hip; its C ABI is include/sactd3_returns.h, defined behind the nearest-ring-rows call's)
+#include "returns.h"
+#include "../../include/sactd3_returns.h"
+static_assert(RTG_SPAN == SACTD3_RTG_SPAN && RTG_TERMINATED == SACTD3_RTG_TERMINATED && RTG_TRUNCATED == SACTD3_RTG_TRUNCATED &&
+              RTG_OPEN == SACTD3_RTG_OPEN && RTG_START == SACTD3_RTG_START, "the kernel's constants are the C ABI's");
 // ... and the evaluation rollout, whose kernel is compiled with the env kernels (env.hip): host code only here, at the end of this file
 #include "eval_rollout.h"
 // ... and the collected rollout segment, split the same way (collect_rollout.h)
@@ -371,6 +376,13 @@ struct sactd3_engine {
   float* kn_sel = nullptr;
   int *kn_slot = nullptr, *kn_qflags = nullptr, *kn_bad = nullptr, *kn_words = nullptr;
   int64_t kn_host[3] = {};
+  // Returns-to-go of ring rows (sactd3_returns_to_go_device; include/sactd3_returns.h; device code: returns_kernels.h, a translation
+  // unit of its own).  rt_f / rt_i: the local results per position and the carries per span of one call, sized by the ring's capacity
+  // (rtg_scratch); rt_words: the counters.  Made at the first call and shared with nothing.  rt_host: {calls, rows scanned}.
+  float* rt_f = nullptr;
+  int* rt_i = nullptr;
+  unsigned long long* rt_words = nullptr;
+  int64_t rt_host[2] = {};
   // Coloured exploration noise (sactd3_colored_noise_device; include/sactd3_noise.h; device code: noise_kernels.h, a translation unit of
   // its own).  nz_tables: the amplitude and twiddle tables of every (beta, length) pair asked for so far, each made at its first use --
   // an engine that never generates holds nothing more than before.
@@ -4612,6 +4624,67 @@ int sactd3_ring_knn_stats(sactd3_engine* e, int64_t out[8]) {
   for (int i = 0; i < 8; ++i) out[i] = 0;
   out[0] = e->kn_host[0]; out[1] = e->kn_host[1]; out[2] = e->kn_host[2];
   out[3] = w[KNN_W_BADQ]; out[4] = w[KNN_W_BADROWS]; out[5] = w[KNN_W_SHORT];
+  return 0;
+}
+
+// ---- returns-to-go of ring rows (include/sactd3_returns.h): k_rtg_scan over spans of RTG_SPAN chain-major positions, which reads the
+// ring records where they lie, the single-workgroup k_rtg_carry and k_rtg_apply, which scatters to the caller's arrays by slot
+// (returns.hip).  Like a search it writes memory of its own and the caller's, nothing else of the engine's: no CHAIN_BREAK, no counter
+// of training, acting or another feature, allowed while an acting call is in flight.
+int sactd3_returns_to_go_device(sactd3_engine* e, float gamma, int stride, int64_t first, int64_t count,
+                                const sactd3_returns_io* io, void* caller_stream, int flags) {
+  if (!e) return SACTD3_EINVAL;
+  // refusals first: a refused call has launched, allocated and counted nothing
+  if (!io) return e->fail(SACTD3_EINVAL, "returns_to_go_device: null argument");
+  if (!(gamma >= 0.f && gamma <= 1.f)) return e->fail(SACTD3_EINVAL, "returns_to_go_device: 0 <= gamma <= 1 required");
+  const int64_t cap = e->cfg.rb_capacity;
+  if (stride < 1 || stride > cap) return e->fail(SACTD3_EINVAL, "returns_to_go_device: 1 <= stride <= rb_capacity required");
+  if (flags & ~(SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) return e->fail(SACTD3_EINVAL, "returns_to_go_device: unknown flag");
+  if (first < 0 || count < 0 || (count == 0 && first != 0))
+    return e->fail(SACTD3_EINVAL, "returns_to_go_device: first >= 0 and count >= 0 required, and first == 0 beside count == 0");
+  USE_DEVICE(e);
+  const FieldRow out[5] = {{io->returns, io->returns_ld, 1, "returns"}, {io->undiscounted, io->undiscounted_ld, 1, "undiscounted"},
+                           {io->length, io->length_ld, 1, "length"}, {io->last, io->last_ld, 1, "last"}, {io->ends, io->ends_ld, 1, "ends"}};
+  RCCHK(field_rows_check(e, out, 5, false, "returns_to_go_device", "no output is set"));
+  if (e->rb_len <= 0) return e->fail(SACTD3_ESTATE, "returns_to_go_device: buffer is empty");
+  if (count > e->rb_len || first > e->rb_len - count) return e->fail(SACTD3_EINVAL, "returns_to_go_device: the range leaves [0, rb_len)");
+  if (count == 0 && e->rb_pinned > 0)
+    return e->fail(SACTD3_ESTATE, "returns_to_go_device: rows are pinned (sactd3_rb_pin): the age order has two wrap points there; ask by range");
+  RCCHK(first_use_alloc(e, &e->rt_f, rtg_scratch((long)cap), false));      // (never zeroed: a scan writes every word the later launches read)
+  RCCHK(first_use_alloc(e, &e->rt_i, rtg_scratch((long)cap), false));
+  RCCHK(first_use_alloc(e, &e->rt_words, (size_t)RTG_WORDS));
+  RtgArgs g{};
+  g.ring = (const float4*)e->ring; g.rec4 = e->rec4; g.cx = e->cx; g.cn = e->cn; g.o = e->o;
+  g.cap = (int)cap; g.stride = stride; g.gamma = gamma;
+  g.n = (int)(count == 0 ? e->rb_len : count);
+  g.base = (int)(count == 0 ? (e->rb_len < cap ? 0 : e->rb_cursor) : first);
+  g.q = g.n / stride; g.rem = g.n % stride;
+  g.sf = e->rt_f; g.si = e->rt_i; g.words = e->rt_words;
+  g.returns = io->returns; g.returns_ld = (long)io->returns_ld; g.undiscounted = io->undiscounted; g.undiscounted_ld = (long)io->undiscounted_ld;
+  g.length = io->length; g.length_ld = (long)io->length_ld; g.last = io->last; g.last_ld = (long)io->last_ld;
+  g.ends = io->ends; g.ends_ld = (long)io->ends_ld;
+  const hipStream_t caller = (hipStream_t)caller_stream;
+  const int ordered = (flags & (SACTD3_SRC_ORDERED | SACTD3_DST_ORDERED)) ? SACTD3_SRC_ORDERED : 0;      // (one pair of events serves both sides)
+  RCCHK(src_order_begin(e, caller, ordered));
+  const hipError_t he = returns_launch(g, (long)e->rb_len, e->stream);
+  if (he != hipSuccess) return e->fail(SACTD3_EHIP, "returns_to_go_device: k_rtg_scan / k_rtg_carry / k_rtg_apply", he);
+  RCCHK(src_order_end(e, caller, ordered));
+  ++e->rt_host[0]; e->rt_host[1] += g.n;
+  return 0;
+}
+
+int sactd3_returns_to_go_stats(sactd3_engine* e, int64_t out[8]) {
+  if (!e || !out) return SACTD3_EINVAL;
+  USE_DEVICE(e);
+  unsigned long long w[RTG_WORDS] = {};
+  if (e->rt_words) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(w, e->rt_words, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = e->rt_host[0]; out[1] = e->rt_host[1];
+  out[2] = (int64_t)w[RTG_W_TERMINATED]; out[3] = (int64_t)w[RTG_W_TRUNCATED]; out[4] = (int64_t)w[RTG_W_OPEN];
+  out[5] = (int64_t)w[RTG_W_START]; out[6] = (int64_t)w[RTG_W_BADR];
   return 0;
 }
 

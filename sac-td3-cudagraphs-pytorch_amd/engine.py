@@ -486,6 +486,51 @@ class Engine:
         self._ck(self.lib.sactd3_ring_knn_stats(self._h, out))
         return dict(zip(("calls", "queries", "rows_scanned", "queries_nonfinite", "ring_keys_nonfinite", "short_results"), (int(x) for x in out)))
 
+    # -- returns-to-go of ring rows (include/sactd3_returns.h)
+    RTG_OUT = (("returns", "float32"), ("undiscounted", "float32"), ("length", "int32"), ("last", "int32"), ("ends", "int32"))
+
+    def returns_to_go(self, gamma=None, stride: int = 1, first: int = 0, count=None, out=None) -> Dict[str, object]:
+        """sactd3_returns_to_go_device: the Monte-Carlo return-to-go of every ring row of a range, from the records themselves.  The
+        successor of a row is the row `stride` appends later (`stride`: the number of envs that fed the ring in lock-step); a chain
+        ends at a termination flag, where s' and the successor's s differ as bit patterns, or where the range ends.  `count` None: the
+        whole ring in age order (refused while rows are pinned); else the slots [first, first + count) in slot order.  `gamma` None:
+        the config's.  Eager launches on the engine's stream, ordered on the GPU against torch's current stream; no host wait;
+        training and acting do not see the call.  `out`: a mapping of preallocated contiguous tensors of `rb_len()` rows under the keys
+        below (a key left out is made here); rows outside the range keep what they held (torch.empty otherwise).
+        -> {"returns": float32 [len], "undiscounted": float32 [len], "length": int32 [len], "last": int32 [len] the slot of the chain's
+        last row, "ends": int32 [len] one of RTG_TERMINATED / RTG_TRUNCATED / RTG_OPEN, plus RTG_START where no row links into the row}"""
+        import torch
+        dev = torch.device("cuda", self.cfg.device_id)
+        gamma = float(self.cfg.gamma if gamma is None else gamma)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"returns_to_go: 0 <= gamma <= 1, got {gamma}")
+        if int(stride) < 1 or int(first) < 0 or (count is not None and int(count) < 1):
+            raise ValueError("returns_to_go: stride >= 1, first >= 0 and count >= 1 (None: the whole ring in age order)")
+        if count is None and int(first) != 0:
+            raise ValueError("returns_to_go: `first` belongs to a range: pass `count` as well")
+        n = self.rb_len()
+        io, res = _lib.CReturnsIO(), {}
+        for name, dtype in self.RTG_OUT:
+            dtype = getattr(torch, dtype)
+            t = out.get(name) if out else None
+            if t is None:
+                t = torch.empty((n,), dtype=dtype, device=dev)
+            elif not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == (n,) and t.is_contiguous()):
+                raise ValueError(f"returns_to_go: out[{name!r}] is a contiguous {str(dtype).split('.')[1]} tensor ({n},) of the engine's device")
+            res[name] = t
+            setattr(io, name, t.data_ptr() if n else None)
+            setattr(io, name + "_ld", 1)
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+        self._ck(self.lib.sactd3_returns_to_go_device(self._h, gamma, int(stride), int(first), 0 if count is None else int(count), C.byref(io),
+                                                      _vp(stream), _lib.SRC_ORDERED | _lib.DST_ORDERED))
+        return res
+
+    def returns_stats(self) -> Dict[str, int]:
+        """counters of returns_to_go (sactd3_returns_to_go_stats; waits for the engine's stream: five of them live on the device)"""
+        out = (C.c_int64 * 8)()
+        self._ck(self.lib.sactd3_returns_to_go_stats(self._h, out))
+        return dict(zip(("calls", "rows_scanned", "terminated", "truncated", "open", "starts", "rewards_nonfinite"), (int(x) for x in out)))
+
     # -- coloured exploration noise (include/sactd3_noise.h)
     def colored_noise(self, beta: float, length: int, sequences: int, chunk: int = 0, epoch: int = 0, out=None):
         """sactd3_colored_noise_device: chunk `chunk` of `sequences` independent 1/f^beta Gaussian sequences (beta in [0, 2]: 0 white,

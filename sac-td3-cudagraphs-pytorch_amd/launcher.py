@@ -398,6 +398,12 @@ def mode_flags(args, plan) -> dict:
                 flags[k] = cast(getattr(args, k))
     elif getattr(args, "knn_k", None) is not None or getattr(args, "knn_beta", None) is not None:
         raise ValueError("--knn_k / --knn_beta need --knn ROWS: they belong to that search")
+    if getattr(args, "mc_returns", None) is not None:       # (the same)
+        flags["mc_returns"] = int(args.mc_returns)
+        if getattr(args, "mc_stride", None) is not None:
+            flags["mc_stride"] = int(args.mc_stride)
+    elif getattr(args, "mc_stride", None) is not None:
+        raise ValueError("--mc_stride needs --mc_returns ROWS: it is the chain stride of that call")
     if getattr(args, "init", "torch") != "torch":           # (the same)
         flags["init"] = args.init
     if getattr(args, "eval_one_launch", False) or getattr(args, "q_bias", 0):      # (the same: keys only when a flag was given; every job
@@ -415,7 +421,7 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
                    reset_every=None, reset_what=None, init: str = "torch", num_updates=None, collected_rollout: bool = False,
                    dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None,
                    feature_rank=None, feature_rank_delta=None, ood_gap=None, ood_candidates=None, action_grad=None,
-                   action_grad_steps=None, action_grad_lr=None, knn=None, knn_k=None, knn_beta=None) -> dict:
+                   action_grad_steps=None, action_grad_lr=None, knn=None, knn_k=None, knn_beta=None, mc_returns=None, mc_stride=None) -> dict:
     """The command line's facts as the keywords of loop.train, in this one place, and asked of loop.update_plan on the way (`cfg`: a
     job_config; no agent, no GPU): ValueError for a run that loop.train would refuse.  run_job passes the keywords on; main() asks
     before a worker starts.  --prioritized is the engine-owned proportional priorities (Schaul et al. 2016: alpha 0.6, beta 0.4); it,
@@ -440,6 +446,8 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     critics' action gradients at every evaluation, loop.train action_grad=...): asked of loop.action_grad_rule, the key the same way.
     `knn` [, `knn_k`, `knn_beta`] (--knn ROWS [--knn_k K] [--knn_beta B]: nearest-ring-row vitals at every evaluation, loop.train
     knn=...): asked of loop.knn_rule, the key the same way.
+    `mc_returns` [, `mc_stride`] (--mc_returns ROWS [--mc_stride S]: the critics' bias against the ring's own returns-to-go at every
+    evaluation, loop.train mc_returns=...): asked of loop.mc_returns_rule, the key the same way.
     `exploration_beta` [, `exploration_len`] (--exploration_beta B [--exploration_len L]: coloured exploration noise in the collected
     segments, loop.train exploration_beta=...): asked of loop.exploration_rule with the job's segment_len; the keys are in the result
     only when --exploration_beta was given."""
@@ -467,17 +475,18 @@ def train_keywords(cfg, *, prioritized: bool, n_step: int, one_launch: bool, pri
     loop.update_plan(cfg, sampler=None, **update, **(dict(num_updates=int(num_updates)) if num_updates is not None else {}))
     rollout = dict(collected_rollout=True) if collected_rollout else {}
     watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every, num_updates, feature_rank, feature_rank_delta, ood_gap, ood_candidates,
-                             action_grad, action_grad_steps, action_grad_lr, knn, knn_k, knn_beta)
+                             action_grad, action_grad_steps, action_grad_lr, knn, knn_k, knn_beta, mc_returns, mc_stride)
     return dict(update, overlap=overlap_acting, device_env=device_env, native_rollout=native_rollout, policy_stats=int(policy_stats), **rollout, **noise, **watch)
 
 
 def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_every=None, num_updates=None, feature_rank=None,
                      feature_rank_delta=None, ood_gap=None, ood_candidates=None, action_grad=None, action_grad_steps=None,
-                     action_grad_lr=None, knn=None, knn_k=None, knn_beta=None) -> dict:
+                     action_grad_lr=None, knn=None, knn_k=None, knn_beta=None, mc_returns=None, mc_stride=None) -> dict:
     """--dormant ROWS [--dormant_tau T] [--redo_every N] [--feature_rank ROWS [--feature_rank_delta D]] [--ood_gap ROWS
     [--ood_candidates N]] [--action_grad ROWS [--action_grad_steps K] [--action_grad_lr LR]] [--knn ROWS [--knn_k K] [--knn_beta B]] as
     the keywords loop.train and loop.train_offline take, asked of loop.redo_rule, loop.feature_rank_rule, loop.ood_gap_rule,
-    loop.action_grad_rule and loop.knn_rule (ValueError for what they would refuse); {} without the flags"""
+    loop.action_grad_rule and loop.knn_rule (ValueError for what they would refuse); {} without the flags.  `mc_returns` [, `mc_stride`]
+    (--mc_returns ROWS [--mc_stride S]) the same way, asked of loop.mc_returns_rule."""
     kw = {}
     if dormant is not None:
         kw["dormant"] = dict(rows=int(dormant), **(dict(tau=float(dormant_tau)) if dormant_tau is not None else {}))
@@ -506,6 +515,11 @@ def dormant_keywords(dormant=None, dormant_tau=None, redo_every=None, reset_ever
         loop.knn_rule(kw["knn"])
     elif knn_k is not None or knn_beta is not None:
         raise ValueError("knn_k / knn_beta need knn ROWS: they belong to that search")
+    if mc_returns is not None:
+        kw["mc_returns"] = dict(rows=int(mc_returns), **(dict(stride=int(mc_stride)) if mc_stride is not None else {}))
+        loop.mc_returns_rule(kw["mc_returns"])
+    elif mc_stride is not None:
+        raise ValueError("mc_stride needs mc_returns ROWS: it is the chain stride of that call")
     return kw
 
 
@@ -516,7 +530,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
             reset_every=None, reset_what=None, eval_one_launch: bool = False, q_bias: int = 0, collected_rollout: bool = False,
             dormant=None, dormant_tau=None, redo_every=None, exploration_beta=None, exploration_len=None,
             feature_rank=None, feature_rank_delta=None, ood_gap=None, ood_candidates=None, action_grad=None, action_grad_steps=None,
-            action_grad_lr=None, knn=None, knn_k=None, knn_beta=None, **over):
+            action_grad_lr=None, knn=None, knn_k=None, knn_beta=None, mc_returns=None, mc_stride=None, **over):
     """One (env, seed) run = what one `main.py train` process of the reference does (main.py:126-195), on one GPU.
     `offline_dataset` (an .npz with the keys of rb.extend): no env loop -- the ring is filled once (loop.load_dataset) and
     `num_updates` iterations (default: cfg.num_timesteps) run through loop.train_offline, evaluated every cfg.eval_every of them;
@@ -542,7 +556,8 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     actions at every evaluation (loop.train / loop.train_offline ood_gap=...).  `action_grad` [, `action_grad_steps`, `action_grad_lr`]:
     the critics' action gradients at that many ring rows at every evaluation (loop.train / loop.train_offline action_grad=...).
     `knn` [, `knn_k`, `knn_beta`]: nearest-ring-row vitals of that many ring rows at every evaluation (loop.train / loop.train_offline
-    knn=...)."""
+    knn=...).  `mc_returns` [, `mc_stride`]: the critics' bias on that many stored rows against the ring's own returns-to-go at every
+    evaluation (loop.train / loop.train_offline mc_returns=...)."""
     import json
     import time
     from pathlib import Path
@@ -584,7 +599,7 @@ def run_job(algo: str, env_id: str, seed: int, device_index: int, out_dir, env_f
     watch = dormant_keywords(dormant, dormant_tau, redo_every, reset_every,
                              int(num_updates if num_updates is not None else cfg.num_timesteps) if offline else None,
                              feature_rank, feature_rank_delta, ood_gap, ood_candidates, action_grad, action_grad_steps, action_grad_lr,
-                             knn, knn_k, knn_beta)
+                             knn, knn_k, knn_beta, mc_returns, mc_stride)
     run_dir = Path(out_dir) / f"{env_id}__{algo}__seed{seed:02d}"
     tab = loop.Tabular(run_dir)
     ev = loop.Evaluator(cfg, eval_env, agent, tabular=tab, ckpt_dir=run_dir)
@@ -653,7 +668,7 @@ def _worker_main(args, plan, flags) -> int:
                 out["collected_rollout"] = True
             for k in ("init", "reset_every", "reset_what", "eval_one_launch", "q_bias", "dormant", "dormant_tau", "redo_every",
                       "exploration_beta", "exploration_len", "feature_rank", "feature_rank_delta", "ood_gap", "ood_candidates",
-                      "action_grad", "action_grad_steps", "action_grad_lr", "knn", "knn_k", "knn_beta"):      # (the same)
+                      "action_grad", "action_grad_steps", "action_grad_lr", "knn", "knn_k", "knn_beta", "mc_returns", "mc_stride"):      # (the same)
                 if k in flags:
                     out[k] = flags[k]
         else:
@@ -755,6 +770,10 @@ def main(argv=None) -> int:
                          "device (loop.train knn=...; vitals/knn_state_entropy, vitals/knn_policy_distance)")
     ap.add_argument("--knn_k", type=int, default=None, metavar="K", help="with --knn: the neighbour of the state bonus, 1 .. 16 (default 5)")
     ap.add_argument("--knn_beta", type=float, default=None, metavar="B", help="with --knn: weight of the state columns in the policy distance (default 2)")
+    ap.add_argument("--mc_returns", type=int, default=None, metavar="ROWS",
+                    help="at every evaluation: the critics at ROWS stored rows against the ring's own returns-to-go, computed on the device "
+                         "(loop.train mc_returns=...; vitals/q_bias_data_mean, vitals/q_bias_data_std, vitals/q_bias_data_rows)")
+    ap.add_argument("--mc_stride", type=int, default=None, metavar="S", help="with --mc_returns: the envs that feed the ring in lock-step (default 1)")
     ap.add_argument("--ood_candidates", type=int, default=None, metavar="N", help="with --ood_gap: sampled actions per row, 16, 32 or 64 (default 16)")
     ap.add_argument("--redo_every", type=int, default=None, metavar="N",
                     help="with --dormant: ReDo -- every N critic updates, scan and re-initialise the dormant units (excludes --reset_every)")

@@ -643,6 +643,39 @@ def knn_rule(knn):
         raise ValueError("knn: beta must be finite and > 0")
 
 
+class McReturns:
+    """`mc_returns=dict(rows= [, stride=, tail_tol=, seed=])` of train / train_offline: at every evaluation point `agent.mc_q_bias` --
+    the critics at `rows` stored (s, a) pairs against the returns-to-go the ring itself shows behind them, computed on the device.
+    -> vitals/q_bias_data_mean, vitals/q_bias_data_std, vitals/q_bias_data_rows.  The calls have device memory of their own: the run's
+    bits are those of the run without them."""
+    KEYS = ("vitals/q_bias_data_mean", "vitals/q_bias_data_std", "vitals/q_bias_data_rows")
+
+    def __init__(self, agent, spec):
+        self.agent, self.kw, self.last = agent, dict(spec), {}
+
+    def __call__(self, tabular: Optional["Tabular"] = None) -> Dict[str, float]:
+        got = self.agent.mc_q_bias(**self.kw)
+        self.last = dict(zip(self.KEYS, (got["mean"], got["std"], float(got["rows"]))))
+        if tabular is not None:
+            for k, v in self.last.items():
+                tabular.record(k, v)
+        return self.last
+
+
+def mc_returns_rule(mc_returns):
+    """the keyword rule of `mc_returns`, asked before an agent is touched (ValueError)"""
+    if mc_returns is None:
+        return
+    if not isinstance(mc_returns, dict) or set(mc_returns) - {"rows", "stride", "tail_tol", "seed"} or "rows" not in mc_returns:
+        raise ValueError("mc_returns must be a dict with `rows` [, `stride`, `tail_tol`, `seed`]")
+    if not 1 <= int(mc_returns["rows"]) <= 65536:
+        raise ValueError("mc_returns: 1 <= rows <= 65536")
+    if mc_returns.get("stride") is not None and int(mc_returns["stride"]) < 1:
+        raise ValueError("mc_returns: stride >= 1")
+    if not 0.0 < float(mc_returns.get("tail_tol", 0.05)) <= 1.0:
+        raise ValueError("mc_returns: tail_tol must be in (0, 1]")
+
+
 def redo_rule(dormant, redo_every, redo_what=REDO_ALL, reset_every=None, num_updates: Optional[int] = None):
     """The keyword rules of `dormant` / `redo_every` / `redo_what`, asked before an agent is touched (ValueError), and the rule itself:
     None without `redo_every`, else redo(agent, before, first=None) -> the update count now, with the contract of update_plan's reset:
@@ -695,14 +728,16 @@ class _Vitals:
         return {k: v for part in self.parts for k, v in part.last.items()}
 
 
-def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None, ood_gap=None, action_grad=None, knn=None):
-    """PolicyStats, QBias, Dormant, FeatureRank, OodGap, ActionGrad and / or Knn as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
+def _vitals(agent, policy_stats: int, q_bias, cfg: Any, dormant=None, feature_rank=None, ood_gap=None, action_grad=None, knn=None,
+            mc_returns=None):
+    """PolicyStats, QBias, Dormant, FeatureRank, OodGap, ActionGrad, Knn and / or McReturns as train / train_offline were asked for them; None: none of them (and no call is made, no field of cfg read)"""
     parts = ([PolicyStats(agent, policy_stats, getattr(cfg, "seed", 0))] if policy_stats else []) + ([QBias(agent, q_bias)] if q_bias is not None else [])
     parts += [Dormant(agent, dormant)] if dormant is not None else []
     parts += [FeatureRank(agent, feature_rank)] if feature_rank is not None else []
     parts += [OodGap(agent, ood_gap)] if ood_gap is not None else []
     parts += [ActionGrad(agent, action_grad)] if action_grad is not None else []
     parts += [Knn(agent, knn)] if knn is not None else []
+    parts += [McReturns(agent, mc_returns)] if mc_returns is not None else []
     return None if not parts else parts[0] if len(parts) == 1 else _Vitals(parts)
 
 
@@ -877,7 +912,8 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
           collected_rollout: bool = False, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
           redo_what: Any = REDO_ALL, exploration_beta: Optional[float] = None, exploration_len: int = 256,
           feature_rank: Optional[Dict[str, Any]] = None, ood_gap: Optional[Dict[str, Any]] = None,
-          action_grad: Optional[Dict[str, Any]] = None, knn: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+          action_grad: Optional[Dict[str, Any]] = None, knn: Optional[Dict[str, Any]] = None,
+          mc_returns: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """Control flow of orchestrator.py:317-352 (no wandb / tqdm / checkpoint upload): interact, count, wait for
     `learning_starts`, then per iteration sample -> critic update -> (every delay+1 iterations) delay x actor
     update -> target update, with the reference's counters.  `fused=True` issues the whole iteration as one graph
@@ -959,13 +995,18 @@ def train(cfg: Any, env, agent, *, fused: bool = True, on_eval: Optional[Callabl
     itself is bit for bit the run without it.
     `knn=dict(rows= [, k=, beta=, seed=])` (default None: off, and no call is made): at every evaluation point the k nearest ring rows
     of `rows` ring states and of the policy's (state, action) pairs there (Knn) -- vitals/knn_state_entropy,
-    vitals/knn_policy_distance; the run itself is bit for bit the run without it."""
+    vitals/knn_policy_distance; the run itself is bit for bit the run without it.
+    `mc_returns=dict(rows= [, stride=, tail_tol=, seed=])` (default None: off, and no call is made): at every evaluation point the
+    critics' bias on `rows` stored rows against the ring's own returns-to-go (McReturns; `stride`: the envs that feed the ring in
+    lock-step) -- vitals/q_bias_data_mean, vitals/q_bias_data_std, vitals/q_bias_data_rows; the run itself is bit for bit the run
+    without it."""
     redo = redo_rule(dormant, redo_every, redo_what, reset_every)         # (refusals before the agent is touched)
     feature_rank_rule(feature_rank)
     ood_gap_rule(ood_gap)
     action_grad_rule(action_grad)
     knn_rule(knn)
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad, knn)
+    mc_returns_rule(mc_returns)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad, knn, mc_returns)
     plan = update_plan(cfg, fused=fused, sampler=sampler, prioritized=prioritized, n_step=n_step, one_launch=one_launch,
                        prior_fraction=prior_fraction, updates_per_step=updates_per_step, hindsight=hindsight, fused_rollout=fused_rollout,
                        reset_every=reset_every, reset_what=reset_what)
@@ -1068,7 +1109,7 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
                   q_bias: Optional[Dict[str, Any]] = None, dormant: Optional[Dict[str, Any]] = None, redo_every: Optional[int] = None,
                   redo_what: Any = REDO_ALL, feature_rank: Optional[Dict[str, Any]] = None,
                   ood_gap: Optional[Dict[str, Any]] = None, action_grad: Optional[Dict[str, Any]] = None,
-                  knn: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
+                  knn: Optional[Dict[str, Any]] = None, mc_returns: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
     """`num_updates` iterations of orchestrator.py:337-352 on the ring as it stands (load_dataset), with no environment step in
     between: the iterations go out through `agent.engine.run_iterations` -- whole periods of the actor schedule as one graph launch,
     runs of periods as one launch where the engine has them -- in runs that end where an evaluation is due (every
@@ -1078,7 +1119,7 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     no data constrains it; TD3+BC (`hps.bc_alpha` > 0, e.g. 2.5) is the algorithm it is meant for.  `policy_stats=N` as for train (SAC
     only), `q_bias=dict(env=, seed=)` as for train.  `reset_every` / `reset_what` as for train: the runs also end where a reset is due, and a `reset_every` above `num_updates`
     is refused (update_plan's table).  `dormant` / `redo_every` / `redo_what` as for train: the runs also end where a redo is due.
-    `feature_rank`, `ood_gap`, `action_grad` and `knn` as for train.  Returns the last metrics."""
+    `feature_rank`, `ood_gap`, `action_grad`, `knn` and `mc_returns` as for train.  Returns the last metrics."""
     num_updates = int(num_updates)
     if num_updates < 0:
         raise ValueError(f"train_offline: num_updates must be >= 0, got {num_updates}")
@@ -1087,11 +1128,12 @@ def train_offline(cfg: Any, agent, *, num_updates: int, evaluator: Optional["Eva
     ood_gap_rule(ood_gap)
     action_grad_rule(action_grad)
     knn_rule(knn)
+    mc_returns_rule(mc_returns)
     reset = None
     if reset_every is not None:                                           # (before the agent is touched)
         reset = update_plan(cfg, fused=True, sampler=None, prioritized=None, n_step=1, one_launch=False, prior_fraction=None,
                             updates_per_step=1, reset_every=reset_every, reset_what=reset_what, num_updates=num_updates).reset
-    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad, knn)
+    pstats = _vitals(agent, policy_stats, q_bias, cfg, dormant, feature_rank, ood_gap, action_grad, knn, mc_returns)
     resets = reset is not None                                            # vitals/resets belongs to a run that resets
     if redo is not None:
         reset, reset_every = redo, redo_every                             # the same schedule: the runs end where a redo is due
